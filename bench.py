@@ -1,6 +1,6 @@
 """Headline benchmark: env-steps/sec of the simulation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--agents 4] [--res 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--agents 4] [--res 64] [--dump-outputs DIR]
 
 Workload (BASELINE.json `metric`): 4096 envs x 4 agents x 64-ray RGBD per GPU, seeded synthetic cubicasa-like
 floorplans, random momentum actions. One *step* = one pass of the hot path over the whole batch: `ms_physics` then
@@ -23,9 +23,15 @@ Rank 0 prints one JSON line.
 
 Timing: a timed region is the W untimed warm-up steps from the spawn points and then exactly K steps between barrier +
 synchronize pairs - steps W..W+K of one fixed trajectory of the env loop (recorded beforehand: the velocities handed to
-`ms_physics` at every step), the same in every region. Regions are repeated until they add up to a quarter of a second
-and `value` / `ms_per_step` are the MEDIAN region's (min and max beside it), so that a K = 20 run is as repeatable as a
-K = 200 one and times the same kind of step.
+`ms_physics` at every step). Each leg of the headline runs that region untimed for a quarter of a second (the device's
+clocks and caches at work) and then times ONE region, so --steps sets the number of timed steps; ask for more steps for
+a longer window (a K = 20 region lasts about a millisecond). The `shapes` block repeats its timed regions until they
+add up to a floor and reports the MEDIAN region's.
+
+With --dump-outputs DIR, after the timed steps, bench.py writes what the timed path computed in its last step (step W+K-1 of the
+trajectory, whatever leg ran last): `progress` from ms_physics, the render planes it was asked for, the agents' state,
+as DIR/<name>.npy (float32; int32 planes as float64), at most 64 MB in all - a seeded sample of envs when more.
+The inputs depend on the arguments alone, so two builds can be compared output for output.
 
 Besides the contract fields the line carries
   roofline      render kernel (the dominant one): algorithmic bytes per launch / its mean launch time (HIP events
@@ -59,8 +65,8 @@ os.environ.setdefault('HIP_FORCE_DEV_KERNARG', '1')
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-HBM_PEAK_GBPS = 8000.   # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
-FP32_VECTOR_PEAK_TFLOPS = 157.3   # same guide: 256 CUs x 2.4 GHz x 256 flop/clk (packed FMA), the VALU ceiling SURVEY 8(d) names
+HBM_PEAK_GBPS = 8000.   # MI355X: 8.0 TB/s spec (6.29 TB/s measured copy)
+FP32_VECTOR_PEAK_TFLOPS = 157.3   # MI355X: 256 CUs x 2.4 GHz x 256 flop/clk (packed FMA), the VALU ceiling SURVEY 8(d) names
 _T0 = time.perf_counter()
 # processes that generate floorplans (forked before the GPU is touched). None under a profiler: rocprofv3's counter
 # collection hangs on forked children (seen with --pmc), and a profile does not care how long the plans took
@@ -471,6 +477,7 @@ class _Gpu:
             if ev is not None:
                 ev[2].record()
         if one_launch:
+            fused.results = state
             return fused
 
         def step(view, ev=None):
@@ -480,6 +487,7 @@ class _Gpu:
             state['r'] = cuda.render(scenery, view, fields=fields, out=state.get('r'))
             if ev is not None:
                 ev[2].record()
+        step.results = state          # (the result buffers every step writes into: the graph's replays too)
         return step
 
     def graph(self, fn):
@@ -543,11 +551,13 @@ def launch_ranks(args, argv):
     raise SystemExit(subprocess.call(cmd, env=env, cwd=ROOT))
 
 
-def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields=None, graph=True, eager_floor=None, graph_floor=.25,
+def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields=None, graph=True, eager_floor=None, graph_floor=None,
                   one_launch=False):
     """The timing protocol (module docstring) on one world: a dry run of the env loop records the W + K steps' inputs;
     the K timed steps are then launched one by one with HIP events around every step and every render (`eager`) and, with
-    `graph`, replayed as one HIP graph - timed regions repeated until they add up to the floors. Returns the raw numbers."""
+    `graph`, replayed as one HIP graph. A leg with a floor repeats its timed region until the regions add up to it; without
+    one it times exactly one region of K steps. Returns the raw numbers, and in `last` what the hot path handed its caller
+    in the last step (step W+K-1 of the trajectory: every region ends there)."""
     from megastep_amd import cuda, modules, sharding
     device = dev.device
     N, A = core.n_envs, core.n_agents
@@ -606,10 +616,21 @@ def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields
         # barrier (half a millisecond of TCP on 2 ranks) would have read as a 5x ceiling on the 8-GPU line.
         return sharding.max_over_ranks(own[-1])
 
-    def repeated(run, floor_s=0.25, least=5, most=400):
+    def repeated(run, floor_s=None, least=5, most=400, warm_s=.25):
         """`run` (exactly K steps) timed again and again - every region bracketed as above - until the regions add up to
-        `floor_s` seconds: with the driver's --steps 20 one region lasts a millisecond, too short to be a measurement on
-        its own. All ranks repeat equally often (the count comes from the first region's MAX over ranks)."""
+        `floor_s` seconds; all ranks repeat equally often (the count comes from the first region's MAX over ranks). Without
+        a floor the region is timed once, after `warm_s` seconds of it untimed: a device that idled while the host
+        recorded the inputs or the graph has not got its clocks back up by the first millisecond."""
+        if floor_s is None:
+            t0 = time.perf_counter()
+            for _ in range(most):
+                rewind()
+                run()
+                dev.sync()
+                if time.perf_counter() - t0 >= warm_s:
+                    break
+            events.clear()
+            return np.array([timed(run)])
         first = timed(run)
         n = int(min(max(np.ceil(floor_s/max(first, 1e-9)), least), most))
         return np.array([first] + [timed(run) for _ in range(n - 1)])
@@ -623,8 +644,6 @@ def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields
             evs[i][0].record()
             hot(views[warmup + i], evs[i])
         events.append(evs)
-    if eager_floor is None:
-        eager_floor = 0.1 if steps < 100 else 0.
     eager_runs = repeated(eager, floor_s=eager_floor)
     m = {'eager_runs': eager_runs,
          'step_ms': np.array([e[0].elapsed_time(e[2]) for evs in events for e in evs]),
@@ -638,7 +657,50 @@ def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields
     runs = m['graph_runs'] if m['graph_runs'] is not None else eager_runs
     m['runs'] = runs
     m['own_ms_per_step'] = 1e3*float(np.median(own[-len(runs):]))/steps
+    m['last'] = last_outputs(views[-1], getattr(hot, 'results', {}), fields)
     return m
+
+
+def last_outputs(view, results, fields):
+    """The arrays the hot path's caller holds after a step, by name: the agents' state (updated in place: ms_physics moves
+    them and zeroes the velocity of those it stops), ms_physics' `progress` and the render planes that were asked for."""
+    out = {k: getattr(view, k) for k in ('angles', 'positions', 'velocity', 'angvelocity')}
+    if 'pr' in results:
+        p, r = results['pr']
+    else:
+        p, r = results.get('p'), results.get('r')
+    if p is not None:
+        out['progress'] = p.progress
+    if r is not None:
+        for f in fields or ('indices', 'locations', 'dots', 'distances', 'screen'):
+            out[f] = getattr(r, f)
+    return out
+
+
+DUMP_BYTES = 64*10**6
+
+
+def dump_outputs(directory, outputs, rank=0, world=1, seed=0):
+    """`outputs` as directory/<name>.npy: float tensors as float32, integer ones as float64 (exact). Every array's first
+    axis is the env; when they would take more than DUMP_BYTES (this rank's share of it), a fixed seeded sample of envs is
+    written instead and its indices go to `sampled_envs`. With several ranks every name carries its rank."""
+    arrays = {}
+    for k, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrays[k] = a.astype(np.float32 if a.dtype.kind == 'f' else np.float64)
+    n = len(next(iter(arrays.values())))
+    per_env = sum(a.nbytes for a in arrays.values())/max(n, 1)
+    budget = DUMP_BYTES//world
+    if per_env*n > budget:
+        keep = int(budget//(per_env + 8))                  # (the sample's own index list counts too)
+        envs = np.sort(np.random.RandomState(seed).choice(n, keep, replace=False))
+        arrays = {k: a[envs] for k, a in arrays.items()}
+        arrays['sampled_envs'] = envs.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    prefix = f'rank{rank}_' if world > 1 else ''
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, prefix + k + '.npy'), a)
+    return sorted(arrays)
 
 
 def ray_groups(dev, core):
@@ -845,6 +907,8 @@ def main(argv=None):
     ap.add_argument('--plan-cache', default=None, help='pickle of generated floorplans: loaded if it exists, written (and the run ended) with '
                                                        '--plans-only - for profiled runs, which cannot fork plan workers')
     ap.add_argument('--plans-only', action='store_true')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help="after the timed steps, write what the hot path computed in "
+                                                                        "its last step as DIR/<name>.npy (at most 64 MB)")
     ap.add_argument('--baseline-line', default=None, help="file holding the JSON line of the same command at --gpus 1: the line then "
                                                           "carries scaling_efficiency = value / (N x that line's value)")
     args = ap.parse_args(argv)
@@ -913,11 +977,15 @@ def main(argv=None):
     step_ms, render_each = m['step_ms'], m['render_each']
     eager_s = float(np.median(eager_runs))
     render_ms = float(np.median(render_each))
-    log(f'eager leg: {1e3*eager_s/args.steps:.4f} ms/step (median of {len(eager_runs)} regions of {args.steps} steps)')
+    log(f'eager leg: {1e3*eager_s/args.steps:.4f} ms/step ({len(eager_runs)} timed region of {args.steps} steps)')
     graph_s = None
     if graph_runs is not None:
         graph_s = float(np.median(graph_runs))
-        log(f'graph leg: {1e3*graph_s/args.steps:.4f} ms/step (median of {len(graph_runs)} replays of {args.steps} steps)')
+        log(f'graph leg: {1e3*graph_s/args.steps:.4f} ms/step ({len(graph_runs)} timed replay of {args.steps} steps)')
+    if args.dump_outputs:
+        names = dump_outputs(args.dump_outputs, m['last'], rank, world)
+        log(f'outputs of the last timed step written to {args.dump_outputs}: {", ".join(names)}')
+    del m['last']
 
     elapsed = graph_s if graph_s is not None else eager_s
     # every rank's own median region of the leg `value` comes from (before it waits for the others): an imbalance shows here
@@ -953,7 +1021,7 @@ def main(argv=None):
             'parallelism': f'env-sharded x{world} (contiguous slices balanced by lines x agents x rays), no collectives'},
         'agent_steps_per_sec': value*A,
         'per_rank': {'envs': [n for n, _ in per_rank], 'ms_per_step': [t for _, t in per_rank]},
-        # `value` is the MEDIAN timed region (each exactly K steps between barrier + synchronize pairs); the spread:
+        # `value` is one timed region of exactly K steps between barrier + synchronize pairs (a floor would take the median):
         'timed_regions': {'count': int(len(runs)), 'ms_per_step_min': 1e3*float(runs.min())/args.steps,
                           'ms_per_step_median': ms_per_step, 'ms_per_step_max': 1e3*float(runs.max())/args.steps},
         'eager': {'value': n_total*args.steps/eager_s, 'ms_per_step': 1e3*eager_s/args.steps, 'timed_regions': int(len(eager_runs)),

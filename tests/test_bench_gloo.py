@@ -125,3 +125,52 @@ def test_every_rank_builds_its_own_slice_and_the_slices_make_the_world(monkeypat
     # the same cuts as sharding a built world by its measured cost would make
     for r in range(world):
         assert sharding.env_slice(72, r, world, sharding.render_cost(whole.scenery, 16)) == cuts[r]
+
+
+def test_steps_sets_the_timed_steps():
+    """--steps K times K steps: one region of exactly K steps in each leg, not regions repeated until a time floor."""
+    out = _run(1)
+    assert out['steps'] == 6 and out['timed_regions']['count'] == 1 and out['eager']['timed_regions'] == 1
+    t = out['timed_regions']
+    assert t['ms_per_step_min'] == t['ms_per_step_median'] == t['ms_per_step_max'] == out['ms_per_step']
+
+
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's arrays as DIR/<name>.npy, float32; the same arguments give the same
+    arrays, and another K ends the trajectory elsewhere."""
+    import numpy as np
+    runs = []
+    for tag, steps in (('a', '6'), ('b', '6'), ('c', '7')):
+        _run(1, ('--dump-outputs', str(tmp_path/tag), '--steps', steps))
+        runs.append({p.stem: np.load(p) for p in (tmp_path/tag).glob('*.npy')})
+    a, b, c = runs
+    assert sorted(a) == ['angles', 'angvelocity', 'positions', 'velocity']
+    assert all(v.dtype == np.float32 and len(v) == 24 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert not np.array_equal(a['positions'], c['positions'])
+
+
+def test_dump_outputs_samples_envs_past_the_budget(tmp_path):
+    """Outputs larger than the budget are written as a fixed seeded sample of envs, with the sample's indices; integer
+    planes go out as float64."""
+    script = f"""
+import sys, numpy as np, torch
+sys.path.insert(0, {ROOT!r})
+import bench
+bench.DUMP_BYTES = 20000
+n = 1000
+outs = dict(distances=torch.arange(n*4, dtype=torch.float32).reshape(n, 4), indices=torch.arange(n*2, dtype=torch.int32).reshape(n, 2))
+for d in ('x', 'y'):
+    bench.dump_outputs({str(tmp_path)!r} + '/' + d, outs)
+"""
+    proc = subprocess.run([sys.executable, '-c', script], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    import numpy as np
+    x = {p.stem: np.load(p) for p in (tmp_path/'x').glob('*.npy')}
+    y = {p.stem: np.load(p) for p in (tmp_path/'y').glob('*.npy')}
+    assert sorted(x) == ['distances', 'indices', 'sampled_envs'] and sum(v.nbytes for v in x.values()) <= 20000
+    envs = x['sampled_envs'].astype(np.int64)
+    assert 0 < len(envs) < 1000 and np.all(np.diff(envs) > 0)
+    assert x['indices'].dtype == np.float64 and np.array_equal(x['indices'][:, 0], 2*envs)
+    assert x['distances'].dtype == np.float32 and np.array_equal(x['distances'][:, 0], 4*envs)
+    assert all(np.array_equal(x[k], y[k]) for k in x)
