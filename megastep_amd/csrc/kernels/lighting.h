@@ -91,9 +91,6 @@ __device__ inline float grid_light_intensity(
         lst.x = inside ? lst_.x : 0u; lst.y = inside ? lst_.y : 0u;
     }
     LG_CLK(0, st.x + __float_as_uint(Ii))                                // the lights' rows and the cell's verdicts have arrived
-#if defined(MS_LIGHT_ABLATE) && MS_LIGHT_ABLATE == 2
-    return __uint_as_float(st.x ^ lst.y) + Ii;                           // (ablation: the loads and the cell look-up only)
-#endif
     const bool shortcut = !MANY && __ballot((lane < ni) & !(Ii >= 0.f)) == 0ull;   // every contribution non-negative, finite
     // every intensity zero or of an everyday size (uniform): a contribution 2 I / max(d^2, 1) is then a division in range
     // (div_inrange: the same bits for 8 instructions instead of 11 - these loops are what the waves a launch waits for run)
@@ -104,7 +101,7 @@ __device__ inline float grid_light_intensity(
     // (Round 5 let 1e-30 .. 1e30 and 10^15 m through: gaps of 200 orders and denormal quotients, where the claim was not checked.)
     const bool light_ok = ((Ii == 0.f) || ((Ii >= 1.e-12f) && (Ii <= 1.e12f))) && (fabsf(Ix) <= 1.e6f) && (fabsf(Iy) <= 1.e6f);
     const bool point_ok = (fabsf(cx_l) <= 1.e6f) && (fabsf(cy_l) <= 1.e6f);
-    const bool nice = MS_DIV_INRANGE && __ballot(((lane < ni) && !light_ok) || (dynamic && !point_ok)) == 0ull;
+    const bool nice = __ballot(((lane < ni) && !light_ok) || (dynamic && !point_ok)) == 0ull;
     auto contribution = [&](const float num, const float den) { return nice ? div_inrange(num, den) : num/den; };
     // ---- the sum over the lights the grid proves unblocked, in light order.  Rays around one target mostly share
     // a cell, so: one pass per distinct verdict word set, scalar loop over its LIT bits (01 in the 2-bit fields)
@@ -136,17 +133,11 @@ __device__ inline float grid_light_intensity(
         }
     }
     LG_CLK(1, part)                                                      // ... the sum over the LIT lights is done
-#if defined(MS_LIGHT_ABLATE) && MS_LIGHT_ABLATE == 3
-    return part;                                                         // (ablation: up to the sum over the LIT lights)
-#endif
     // saturated: the reference's min(sum, 1) is exactly 1 whatever the unknown lights do (see dynlight_kernel)
     const bool saturated = dynamic & shortcut & (part >= 1.001f);
     const bool need = dynamic & !saturated & has_unk;
     // Everyone else is done: with no light left open the reference's in-order sum over the unblocked lights IS `part`
     if (!__ballot(need)) return MANY ? acc_in : (saturated ? 1.f : ms_min(part, 1.f));
-#if defined(MS_LIGHT_ABLATE) && MS_LIGHT_ABLATE == 4
-    return part;                                                         // (ablation: nothing done about open lights)
-#endif
     // (`telemetry`, for the probe build only: rays with open lights, of them without a list, lists, rounds of pairs, lights)
     telemetry = 0x80000000u | (unsigned)__popcll(__ballot(need)) | ((unsigned)min(ni, 63) << 25);
 

@@ -32,9 +32,6 @@ __host__ __device__ inline float ms_max(float a, float b) { if (a != a) return b
 // wall's length + 1e-6; numerators of hits that can be taken are >= 1e-5.  Where the operands leave the range - a numerator that
 // is zero or below 2^-104, coordinates beyond 10^15 - the quotient is a float output within its 1e-5 tolerance (zero, or a few
 // ulps of something tiny) or the s of a hit inside the near plane that the comparison throws away either way; never a hit index.
-#ifndef MS_DIV_INRANGE
-#define MS_DIV_INRANGE 1               // (0: plain `/` everywhere - the A/B, and the same bits)
-#endif
 __device__ inline float rcp_refined(const float d) {                   // 1/d to within an ulp: the reciprocal the steps below share
     const float r = __builtin_amdgcn_rcpf(d);
     return __builtin_fmaf(__builtin_fmaf(-d, r, 1.f), r, r);
@@ -45,11 +42,7 @@ __device__ inline float div_by_refined(const float n, const float d, const float
     return __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
 }
 __device__ inline float div_inrange(const float n, const float d) {
-#if MS_DIV_INRANGE
     return div_by_refined(n, d, rcp_refined(d));
-#else
-    return n/d;
-#endif
 }
 
 // Exact unsigned division by a divisor the host knows before the launch (agents per env, ray groups per agent, lines per agent):

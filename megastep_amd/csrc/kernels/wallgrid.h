@@ -274,15 +274,12 @@ __global__ __launch_bounds__(WG) void wallgrid_scan_kernel(const MsScenery sc, c
     // vis: cell after cell of the group - its occluders sorted into sectors of directions (see WG_SECTORS), then lane = candidate,
     // 64 to a wave, each against the occluders of the sector its middle lies in
     const int vis_chunks = (n_vis + WAVE - 1)/WAVE;
-#ifndef MS_WG_SECTORS
-#define MS_WG_SECTORS 1                                                  // (0: every target meets every occluder, as until round 6 - the A/B)
-#endif
     for (int j = 0; j < n_group; j++) {
         const int c = cell_of(j);
         const WgCell k = wg_cell_of(geom, sc.wg_cell, c);
         const float cx = .5f*(k.x0 + k.x1), cy = .5f*(k.y0 + k.y1);
         bool sorted = false;
-        if (MS_WG_SECTORS && n_occ > 16) {
+        if (n_occ > 16) {
             if (tid <= WG_SECTORS) s_sect_at[tid] = 0;
             if (tid < WG_SECTORS) s_sect_fill[tid] = 0;
             __syncthreads();
@@ -338,7 +335,7 @@ __global__ __launch_bounds__(WG) void wallgrid_scan_kernel(const MsScenery sc, c
             }
             if (!hidden) atomicOr(&rows[(long long)(WG_ROWS*c)*W32 + (id >> 5)], 1u << (id & 31));
         }
-        if (MS_WG_SECTORS && n_occ > 16) __syncthreads();                 // (the next cell sorts into the same lists)
+        if (n_occ > 16) __syncthreads();                 // (the next cell sorts into the same lists)
     }
     // near: lane = candidate
     const int near_chunks = (n_near + WAVE - 1)/WAVE;

@@ -15,7 +15,7 @@
 //                   agent's sin/cos for the renderer.  MOVE = 1 runs the movement modules' velocity update first,
 //                   EXTRA = 1 the envs' respawn / lifespan / IMU bookkeeping.
 //                                                            (reference: kernels.cu:179-230, modules.py:24-118,263-366)
-//   render_kernel<IMPL, RW, OBS, SHADE, NG, STEP>   (OBS = 2: pooled observations only, no plane stores in the kernel; STEP = 1: a
+//   render_kernel<OBS, SHADE, NG, STEP>   (OBS = 2: pooled observations only, no plane stores in the kernel; STEP = 1: a
 //                   single-agent env's physics step first, in the same wave - ms_step_render's one launch a step)
 //                   one wavefront per (env, agent, 64-ray group) - or, NG = 4, per four such groups
 //                   that share one list of lines, the launch's last envs left to one-group waves (256 rays and up on large
@@ -27,9 +27,8 @@
 //                   the order-dependent nearest-hit rule is resolved from the three smallest keys (or a literal fold
 //                   where it must be); rays that landed on an agent are lit through the light grid; shading; optional
 //                   pooled observations, crosshair ids and first-sight books.  draw, raycast and shader (three launches +
-//                   five allocations in the reference) are one launch.  IMPL = 2 is the product; 1 (per-chunk pair
-//                   windows) and 0 (literal order, every line) exist in -DMS_AB_IMPLS=1 builds for A/B runs and produce
-//                   the same bits.                               (reference: kernels.cu:297-475)
+//                   five allocations in the reference) are one launch.
+//                                                            (reference: kernels.cu:297-475)
 //   render_prep_kernel, dynlight_kernel   the renderer's helpers for callers without a heading cache / light grid.
 //   visibility_kernel, bake_sum_kernel    the two-phase bake: per (representative env, light) the walls that can shadow
 //                   each angular bin; per texel the sum over the lights, occluders looked up by bin.
@@ -296,7 +295,7 @@ void ms_host_ray_interval_wide(const float* pose, const float* line, int res, fl
     const float last_local = (float)(r_last - r0);
     float xa, ya, xb, yb;
     agent_frame(pose[3], pose[2], line[0] - pose[0], line[1] - pose[1], line[2] - pose[0], line[3] - pose[1], xa, ya, xb, yb);
-    ray_interval<(MS_V2_OPTS & 2) ? 1 : 0>(xa, ya, xb, yb, true, x_clip, c_a, c_b, g0, last_local, *first, *count, (float)nr);
+    ray_interval(xa, ya, xb, yb, true, x_clip, c_a, c_b, g0, last_local, *first, *count, (float)nr);
 }
 void ms_host_ray_interval(const float* pose, const float* line, int res, float fov, float agent_radius, int group, int* first, int* count) {
     ms_host_ray_interval_wide(pose, line, res, fov, agent_radius, 1, group, first, count);
@@ -508,9 +507,6 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     const int R = cfg->res;
     const int slots = wave_slots_here();                                 // the current device's wave slots for this kernel
     bool wide_ok = true;
-#if MS_AB_IMPLS
-    if (getenv("MEGASTEP_RENDER_IMPL")) wide_ok = false;
-#endif
     // (without a light grid the rays that land on an agent are lit by dynlight_kernel, which takes them by groups of 64)
     if (!(sc->lg_vals && sc->lg_starts && sc->lg_geom && sc->lg_cell > 0.f) && sc->n_agents > 1 && (out->screen || out->obs_rgb)) wide_ok = false;
     RenderConsts rc;
@@ -524,13 +520,6 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     rc.ws_headings = 16 + (int)((ws_queue + 1) & ~1LL);
     // kernels.cu:22
     const float half_screen = tanf(3.14159265358979323846f/180.f*cfg->fov/2.);
-#if MS_AB_IMPLS
-    // MEGASTEP_RENDER_IMPL: "seq" (literal order, slowest), "pairs" (round 1's pair raycast), anything else the product's
-    // kernel; all three produce the same bits.  Read per call: tests switch it.
-    const char* impl_env = getenv("MEGASTEP_RENDER_IMPL");
-    const bool seq = impl_env && impl_env[0] == 's';
-    const bool pairs1 = impl_env && impl_env[0] == 'p';
-#endif
     // the light grid is all or nothing: render_kernel lights agent-hit rays itself when it is there
     MsScenery scn = *sc;
     const bool grid = sc->lg_vals && sc->lg_starts && sc->lg_geom && sc->lg_cell > 0.f;
@@ -551,7 +540,7 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     MsAgents agn = *ag;
     MsRender outn = *out;
     if (out->obs_depth) outn.obs_max_depth = 1.f/out->obs_max_depth;     // (the kernel multiplies: see the pooled depth in render.h)
-    const bool colour = out->screen || out->obs_rgb;                      // else: render_kernel<.,.,1,0>, which has no pass 3
+    const bool colour = out->screen || out->obs_rgb;                      // else: render_kernel<1,0>, which has no pass 3
     const bool one_kernel = grid || sc->n_agents == 1 || !colour;        // (nothing to light without colour)
     if (ag->headings && one_kernel) {
         if ((uintptr_t)ag->headings % 16) return MS_EINVAL;
@@ -573,15 +562,11 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     const bool obs = pooled || !all_planes;
     if (progress) {
         // The fused step (render_kernel<..., STEP = 1>): one agent per env and at most 64 rays - the agent is ONE wave, which
-        // runs the env's physics first and renders from the pose it ends on; the product raycast; and a wall grid that either
+        // runs the env's physics first and renders from the pose it ends on; and a wall grid that either
         // serves both halves of the step or neither (ms_render goes without it when the call's near plane or field of view is
         // outside what its vis lists were built for, ms_step_physics never does).
-        bool older = false;
-#if MS_AB_IMPLS
-        older = seq || pairs1;
-#endif
         const bool physics_listed = sc->wg_cells != nullptr;
-        if (sc->n_agents != 1 || R > WAVE || ng != 1 || older || physics_listed != walls_listed ||
+        if (sc->n_agents != 1 || R > WAVE || ng != 1 || physics_listed != walls_listed ||
             (physics_listed && (!sc->wg_near_rows || ((uintptr_t)sc->wg_near_rows % 16)))) return MS_EUNSUPPORTED;
         agn = *ag;                                                       // (the wave works the heading out itself and leaves it in the cache, if there is one)
         outn.workspace = nullptr;
@@ -592,32 +577,19 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     rc.skip_own = (sc->model_radius > 0.f && sc->model_radius*1.01f < cfg->agent_radius) ? 1 : 0;
     rc.inv_res = ((R & (R - 1)) == 0 && half_screen > 1e-3f) ? 1.f/(float)R : 0.f;
     rc.telemetry = g_pair_telemetry;
-    bool older_raycast = false;
-#if MS_AB_IMPLS
-    older_raycast = seq || pairs1;                                       // (their instantiations are the colour ones, whatever is asked for)
-#endif
-    // (the instantiations with optional outputs - every colourless one, and with MS_OBS_MASK the colour one of pooled observations
-    // at one ray group a wave - read which are wanted from here: see OUT_* in render.h)
-    if ((!colour || (MS_OBS_MASK && obs && ng == 1)) && !older_raycast)
+    // (the instantiations with optional outputs - every colourless one, and the colour one of pooled observations at one ray
+    // group a wave - read which are wanted from here: see OUT_* in render.h)
+    if (!colour || (obs && ng == 1))
         outn.obs_subsample = (out->obs_subsample & 0xff) | (((out->indices ? OUT_INDICES : 0) | (out->locations ? OUT_LOCATIONS : 0) |
                               (out->dots ? OUT_DOTS : 0) | (out->distances ? OUT_DISTANCES : 0) | (out->obs_depth ? OUT_DEPTH : 0) |
                               (out->obs_centre ? OUT_CENTRE : 0) | (out->seen_stamp ? OUT_SEEN : 0) | (out->screen ? OUT_SCREEN : 0) |
                               (out->obs_rgb ? OUT_RGB : 0)) << 8);
-    constexpr int RW = 1;
-    const int rblocks = (int)((n_fans + RW - 1)/RW);
-    const dim3 rgrid(rblocks), rblock(RW*WAVE);
+    const dim3 rgrid((int)n_fans), rblock(WAVE);
     const hipStream_t hs = (hipStream_t)stream;
     // (colour, and not one per-ray plane wanted - the demo envs' request: the instantiation that has no plane stores in it)
     [[maybe_unused]] const bool no_planes = colour && !out->indices && !out->locations && !out->dots && !out->distances && !out->screen;
-#define MS_LAUNCH_RENDER(I, O) \
-    hipLaunchKernelGGL((render_kernel<I, RW, O, 1>), rgrid, rblock, 0, hs, scn, agn, outn, cfg->agent_radius, half_screen, R, (int)n_fans, rc)
-#if MS_AB_IMPLS
-    if (seq) { if (obs) MS_LAUNCH_RENDER(0, 1); else MS_LAUNCH_RENDER(0, 0); }
-    else if (pairs1) { if (obs) MS_LAUNCH_RENDER(1, 1); else MS_LAUNCH_RENDER(1, 0); }
-    else
-#endif
 #define MS_LAUNCH_RENDER_NG(O, S, NG_) \
-    hipLaunchKernelGGL((render_kernel<2, RW, O, S, NG_>), rgrid, rblock, 0, hs, scn, agn, outn, cfg->agent_radius, half_screen, R, (int)n_fans, rc)
+    hipLaunchKernelGGL((render_kernel<O, S, NG_>), rgrid, rblock, 0, hs, scn, agn, outn, cfg->agent_radius, half_screen, R, (int)n_fans, rc)
 #define MS_LAUNCH_RENDER_OS(NG_) \
     { if (!colour) MS_LAUNCH_RENDER_NG(1, 0, NG_); else if (no_planes) MS_LAUNCH_RENDER_NG(2, 1, NG_); else if (obs) MS_LAUNCH_RENDER_NG(1, 1, NG_); \
       else MS_LAUNCH_RENDER_NG(0, 1, NG_); }
@@ -629,7 +601,7 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
         rcs.ex = ex ? *ex : MsStepExtras{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 1.f, 1.f};
         rcs.ex.imu_ang_scale = 1.f/rcs.ex.imu_ang_scale; rcs.ex.imu_speed_scale = 1.f/rcs.ex.imu_speed_scale;
 #define MS_LAUNCH_STEP(O, S) \
-    hipLaunchKernelGGL((render_kernel<2, RW, O, S, 1, 1>), rgrid, rblock, 0, hs, scn, agn, outn, cfg->agent_radius, half_screen, R, (int)n_fans, rcs)
+    hipLaunchKernelGGL((render_kernel<O, S, 1, 1>), rgrid, rblock, 0, hs, scn, agn, outn, cfg->agent_radius, half_screen, R, (int)n_fans, rcs)
         if (!colour) MS_LAUNCH_STEP(1, 0); else if (obs) MS_LAUNCH_STEP(1, 1); else MS_LAUNCH_STEP(0, 1);
 #undef MS_LAUNCH_STEP
     }
@@ -638,7 +610,6 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     else MS_LAUNCH_RENDER_OS(1)
 #undef MS_LAUNCH_RENDER_OS
 #undef MS_LAUNCH_RENDER_NG
-#undef MS_LAUNCH_RENDER
     // without a grid: second launch.  With one agent per env no ray can land on an agent line (own lines sit
     // inside the near plane), so there is nothing to light.
     if (!grid && sc->n_agents > 1 && colour)

@@ -1,4 +1,4 @@
-"""The renderer without its shading pass (render_kernel<.,.,1,0>): what a caller gets who asks for no colour - the
+"""The renderer without its shading pass (render_kernel<1,0>): what a caller gets who asks for no colour - the
 reference's Depth reads `distances` only (modules.py:170-184), BASELINE config 2 is Explorer "depth-only" - against the
 oracle and against the full renderer's own planes."""
 import numpy as np

@@ -36,14 +36,9 @@ def _same(x, y):
     return torch.equal(torch.nan_to_num(x.float(), nan=-7.), torch.nan_to_num(y.float(), nan=-7.))
 
 
-#: (an A/B build asked for one of its older raycasts - `make ab`, MEGASTEP_RENDER_IMPL=pairs|seq - has no one-launch step: the two
-#: launches then, with the same results, which is all these tests compare)
-OLDER_RAYCAST = bool(__import__('os').environ.get('MEGASTEP_RENDER_IMPL'))
-
-
 def _fused():
     from megastep_amd import _lib
-    return bool(_lib.lib().ms_debug_last_step_fused()) or OLDER_RAYCAST
+    return bool(_lib.lib().ms_debug_last_step_fused())
 
 
 def _both_ways(c, steps, rng, fields=None, pooled=None, speed=(4., 40.), expect_fused=True, prepare=None):
@@ -67,7 +62,7 @@ def _both_ways(c, steps, rng, fields=None, pooled=None, speed=(4., 40.), expect_
                 prepare(c, i)
             if fused:
                 p, r = cuda.step_render(c.scenery, c.agents, fields=fields, pooled=pooled)
-                assert _fused() == (expect_fused or OLDER_RAYCAST)
+                assert _fused() == expect_fused
             else:
                 p = cuda.physics(c.scenery, c.agents)
                 r = cuda.render(c.scenery, c.agents, fields=fields, pooled=pooled)
@@ -105,7 +100,7 @@ def test_one_launch_equals_the_two_calls(n_envs, res, fov, kw):
 
 
 def test_one_launch_with_every_family_of_outputs():
-    """Depth-only (render_kernel<2,1,1,0,1,1>), pooled observations (<2,1,1,1,1,1>) and all five planes (<2,1,0,1,1,1>)."""
+    """Depth-only (render_kernel<1,0,1,1>), pooled observations (<1,1,1,1>) and all five planes (<0,1,1,1>)."""
     c, _ = _world(32, 1, 64, 130., seed=4)
     rng = np.random.RandomState(6)
     _both_ways(c, 4, rng, fields=('distances',))

@@ -1,4 +1,4 @@
-"""The wall grid's build under the library in use (MEGASTEP_HIP_LIB selects a variant, e.g. one built with -DMS_WG_SECTORS=0): for a
+"""The wall grid's build under the library in use (MEGASTEP_HIP_LIB selects a build, e.g. one of another commit): for a
 few worlds the seconds the grid took and a checksum of everything it holds - cell headers, vis entries, near rows - so that two
 builds can be held against each other bit for bit.   usage: python tools/ab_wallgrid_scan.py [--c5]"""
 import hashlib

@@ -7,5 +7,5 @@ for v in "$@"; do
   name=${v%%:*}; flags=${v#*:}
   ( /opt/rocm/bin/hipcc $F $flags -Rpass-analysis=kernel-resource-usage -o variants/$name.so megastep_hip.hip > /tmp/bv_$name.log 2>&1
     grep -E "error" /tmp/bv_$name.log | head -3
-    grep -E "Function Name|VGPRs:|Spill|ScratchSize|Occupancy" /tmp/bv_$name.log | sed 's/.*remark: //; s/ \[-Rpass.*//' | paste - - - - - - | grep "render_kernelILi2ELi1ELi0" | sed "s/^.*RenderConstsE/$name:/" | tr -s ' \t' ' ' ) &
+    grep -E "Function Name|VGPRs:|Spill|ScratchSize|Occupancy" /tmp/bv_$name.log | sed 's/.*remark: //; s/ \[-Rpass.*//' | paste - - - - - - | grep "render_kernelILi0E" | sed "s/^.*RenderConstsE/$name:/" | tr -s ' \t' ' ' ) &
 done; wait

@@ -2,7 +2,7 @@
 wave's vector instructions are.  usage: python tools/static_profile.py [kernel-name-substring] [min VALU per block]"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-want = sys.argv[1] if len(sys.argv) > 1 else 'render_kernelILi2ELi1ELi0E'
+want = sys.argv[1] if len(sys.argv) > 1 else 'render_kernelILi0E'
 floor = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 flags = '--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -fno-slp-vectorize --cuda-device-only -S'.split()
 subprocess.run(['/opt/rocm/bin/hipcc', *flags, *sys.argv[3:], '-o', '/tmp/ms.s', f'{root}/megastep_amd/csrc/megastep_hip.hip'], check=True, stderr=subprocess.DEVNULL)
