@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 16
+#define MS_ABI_VERSION 17
 
 #define MS_OK            0
 #define MS_EINVAL       -1   /* bad argument (null pointer, non-positive size, ...) */
@@ -329,6 +329,34 @@ typedef struct MsExplorer {
     int*            length_out;    /* (N) out, optional                                                           */
 } MsExplorer;
 int ms_explorer_books(int n_envs, const MsExplorer* books, void* hip_stream);
+
+/* Ray queries against the scenery (no counterpart in the reference, whose only rays are the render's camera fans,
+ * kernels.cu:326-382): R rays per env, each from its own origin along its own direction vector, cast by the reference's
+ * per-ray rule (kernels.cu:349-382) statement for statement - over the env's lines in line order, q = intersect(p, ru, L),
+ * a hit when 0 <= q.t <= 1, better when near/|ru| < q.s < nearest - 1e-4; dot = dot(ru, v)/(|ru||v| + 1e-6), distance =
+ * nearest*|ru| - with the same outputs and miss values as ms_render.  With agents, the lines are the static walls and every
+ * agent's model drawn at its current pose (the rows ms_render would leave in lines_vals, computed in registers: lines_vals
+ * is only read); without (NULL), the static walls alone.  The wall grid is used where it is exact - the origin inside its
+ * env's grid, near*1.001 < wg_near and 1 <= |ru|^2 <= 64 - and every line of the env otherwise; same bits either way. */
+typedef struct MsRaycast {
+    int          n_rays;      /* R: rays per env                                                              */
+    const float* origins;     /* (N, R, 2) p, 8-byte aligned                                                  */
+    const float* dirs;        /* (N, R, 2) ru (any length), 8-byte aligned                                    */
+    float        near_plane;  /* hits at s <= near/|ru| are ignored (ms_render: MsConfig.agent_radius)        */
+    int*         indices;     /* (N, R) line index within the env, -1 on a miss      (each output NULL = not wanted) */
+    float*       locations;   /* (N, R) position along the line, NaN on a miss       */
+    float*       dots;        /* (N, R) ray . line direction,    NaN on a miss       */
+    float*       distances;   /* (N, R) metres, +inf on a miss                       */
+    int*         agents;      /* (N, R) agent whose model the ray hit, else -1       */
+    int*         grid_rays;   /* optional counter (tests): rays that took the wall grid are added to grid_rays[0] */
+} MsRaycast;
+/* config: agent_radius is unused (the near plane travels in MsRaycast), res and fov are not needed either; it may be NULL. */
+int ms_raycast(const MsScenery* scenery, const MsAgents* agents /* NULL: static walls only */, const MsRaycast* rays,
+               const MsConfig* config, void* hip_stream);
+/* The direction vector ru of every camera ray ms_render casts with `config` (res, fov): (N, A, res, 2), by the render's own
+ * device code (ray_y, kernels.cu:234-236,334-337).  Cast from the agents' positions by ms_raycast with near = agent_radius
+ * and the agents, these rays give ms_render's indices, locations, dots and distances bit for bit.  Reads angles only. */
+int ms_camera_rays(const MsAgents* agents, int n_envs, int n_agents, const MsConfig* config, float* dirs, void* hip_stream);
 
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of

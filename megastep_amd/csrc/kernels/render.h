@@ -16,6 +16,30 @@ __device__ __attribute__((noinline)) float2 sincospi_called(const float x) {
     return make_float2(s_, c_);
 }
 
+// A model row (ax, ay, bx, by) in the agent frame drawn at heading (s, c) = sincospi_f(angle/180) and position p: the
+// draw step's arithmetic (kernels.cu:305-314), shared by every place that draws one - the render's waves, drawn_line_of,
+// and raycast_kernel (raycast.h), whose agent rows must be these bits.
+__device__ inline float4 drawn_row(const float s, const float c, const float px, const float py, const float4 mdl) {
+    float4 w;
+    w.x = c*mdl.x - s*mdl.y + px; w.y = s*mdl.x + c*mdl.y + py;
+    w.z = c*mdl.z - s*mdl.w + px; w.w = s*mdl.z + c*mdl.w + py;
+    return w;
+}
+// Column r's ray direction vector ru of an agent at heading (sn, cs) = sincospi_f(angle/180): ray_y and the rotation of
+// (1, ray_y), kernels.cu:234-236,334-337.  (At a power-of-two resolution - 64, 128, 256, 512: every shape anyone runs - the
+// division by R only moves the exponent, and the product with inv_res = 1/R is the correctly rounded quotient itself: one
+// multiply for the dozen instructions of a division; inv_res = 0 otherwise, see camera_inv_res.  The numerator is at least
+// half_screen in size: no underflow.)  The render and ms_camera_rays both form their rays here.
+__device__ inline void camera_ray(const float cs, const float sn, const int r, const float Rf, const float half_screen,
+                                  const float inv_res, float& rx, float& ry) {
+    const float num = (Rf - 2*(float)r - 1)*half_screen;
+    const float uy = inv_res != 0.f ? num*inv_res : div_inrange(num, Rf);
+    rx = cs*1.f - sn*uy; ry = sn*1.f + cs*uy;
+}
+__host__ inline float camera_inv_res(const int R, const float half_screen) {
+    return ((R & (R - 1)) == 0 && half_screen > 1e-3f) ? 1.f/(float)R : 0.f;
+}
+
 // (The work is in a function that is not inlined and takes plain pointers: it serves sceneries with more than 64 agents
 // per env only, and a copy of its binary64 sin/cos at each of the render kernel's half-dozen call sites is code every
 // wave would have to be fetched past.)
@@ -25,13 +49,7 @@ __device__ __attribute__((noinline)) float4 drawn_line_of(const float* angles, c
     float s, c;
     sincospi_f(angles[n*n_agents + a]/180.f, s, c);
     const float2 p = reinterpret_cast<const float2*>(positions)[n*n_agents + a];
-    const float4 mdl = reinterpret_cast<const float4*>(model)[m];
-    float4 w;
-    w.x = c*mdl.x - s*mdl.y + p.x;
-    w.y = s*mdl.x + c*mdl.y + p.y;
-    w.z = c*mdl.z - s*mdl.w + p.x;
-    w.w = s*mdl.z + c*mdl.w + p.y;
-    return w;
+    return drawn_row(s, c, p.x, p.y, reinterpret_cast<const float4*>(model)[m]);
 }
 __device__ inline float4 drawn_line(const MsScenery& sc, const MsAgents& ag, int n, int l) {
     return drawn_line_of(ag.angles, ag.positions, sc.model, sc.n_agents, sc.n_model, n, l);
@@ -562,10 +580,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         const float px_ = __shfl(ag_p.x, la, WAVE), py_ = __shfl(ag_p.y, la, WAVE);
         float4 mdl = row;
         if (!have_row) mdl = reinterpret_cast<const float4*>(sc.model)[l - la*sc.n_model];   // (uniform)
-        float4 w;
-        w.x = c_*mdl.x - s_*mdl.y + px_; w.y = s_*mdl.x + c_*mdl.y + py_;
-        w.z = c_*mdl.z - s_*mdl.w + px_; w.w = s_*mdl.z + c_*mdl.w + py_;
-        return w;
+        return drawn_row(s_, c_, px_, py_, mdl);
     };
     auto agent_line = [&](const int l_) { return agent_line_m(l_, false, make_float4(0.f, 0.f, 0.f, 0.f)); };
     // --- this wave's agent: heading and position (kernels.cu:334-339)
@@ -618,12 +633,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         return sqrt_normal(rx_*rx_ + ry_*ry_);                          // (|r|^2 = (cos^2 + sin^2)(1 + uy^2): 1 to 1 + half_screen^2)
     };
     auto ray_of = [&](const int r_, float& rx_, float& ry_, float& rlen_, float& near_) {
-        // ray_y, kernels.cu:234-236.  (At a power-of-two resolution - 64, 128, 256, 512: every shape anyone runs - the
-        // division by R only moves the exponent, and the product with 1/R is the correctly rounded quotient itself: one
-        // multiply for the dozen instructions of a division.  The numerator is at least half_screen in size: no underflow.)
-        const float num = (Rf - 2*(float)r_ - 1)*half_screen;
-        const float uy = rc.inv_res != 0.f ? num*rc.inv_res : div_inrange(num, Rf);
-        rx_ = cs*1.f - sn*uy; ry_ = sn*1.f + cs*uy;
+        camera_ray(cs, sn, r_, Rf, half_screen, rc.inv_res, rx_, ry_);
         rlen_ = ray_len(rx_, ry_);
         near_ = div_inrange(agent_radius, rlen_);
     };

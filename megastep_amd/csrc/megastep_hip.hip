@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h.
 //
-// Thirteen kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Fifteen kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -38,6 +38,10 @@
 //   wallgrid_scan_kernel, wallgrid_fill_kernel   the wall grid: per cell of a floorplan which walls can matter to a ray
 //                   from the cell (one wall hiding another from the whole cell, exactly) and which an agent in it can
 //                   touch; and the lists made of that.   (replaces the all-lines loops kernels.cu:203-205,352-377)
+//   raycast_kernel, camera_rays_kernel   ray queries: one lane per caller-given ray (origin, direction), the reference's
+//                   per-ray fold over the agents drawn in registers and the vis list of the origin's cell (or every
+//                   wall); and the render's own camera rays as data.   (reference: kernels.cu:234-236,349-382; no
+//                   counterpart as an entry point)
 //   explorer_kernel     the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
 //   deathmatch_kernel   the Deathmatch env's game logic between frames (revive, crosshairs, hits and wounds, health, damage,
@@ -124,6 +128,7 @@ struct Probe {
 #include "kernels/render.h"
 #include "kernels/bake.h"
 #include "kernels/wallgrid.h"
+#include "kernels/raycast.h"
 #include "kernels/envlogic.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -575,7 +580,7 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     rc.c_b = 0.5f*(float)R/half_screen;
     rc.by_m = divisor_of((unsigned)sc->n_model);
     rc.skip_own = (sc->model_radius > 0.f && sc->model_radius*1.01f < cfg->agent_radius) ? 1 : 0;
-    rc.inv_res = ((R & (R - 1)) == 0 && half_screen > 1e-3f) ? 1.f/(float)R : 0.f;
+    rc.inv_res = camera_inv_res(R, half_screen);
     rc.telemetry = g_pair_telemetry;
     // (the instantiations with optional outputs - every colourless one, and the colour one of pooled observations at one ray
     // group a wave - read which are wanted from here: see OUT_* in render.h)
@@ -654,6 +659,38 @@ int ms_step_render(const MsScenery* sc, const MsAgents* ag, float* progress, con
     return ms_move_step_render(sc, ag, nullptr, nullptr, progress, out, cfg, stream);
 }
 int ms_debug_last_step_fused(void) { return g_last_step_fused; }
+
+// Ray queries (raycast.h): arguments checked in full before anything is launched.
+int ms_raycast(const MsScenery* sc, const MsAgents* ag, const MsRaycast* rq, const MsConfig* cfg, void* stream) {
+    (void)cfg;
+    if (!scenery_ok(sc) || !rq || rq->n_rays < 1 || !rq->origins || !rq->dirs || !(rq->near_plane >= 0.f) ||
+        ((uintptr_t)rq->origins % 8) || ((uintptr_t)rq->dirs % 8)) return MS_EINVAL;
+    if (ag && (!ag->angles || !ag->positions || ((uintptr_t)ag->positions % 8))) return MS_EINVAL;
+    const long long total = (long long)sc->n_envs*rq->n_rays;
+    if (total > 0x7fffff00LL) return MS_EUNSUPPORTED;
+    // the wall grid serves this call's rays when its vis lists were built for a near plane beyond this one (as ms_render asks)
+    const bool gridded = sc->wg_cells && sc->wg_starts && sc->wg_geom && sc->wg_pool && sc->wg_pool_base && sc->wg_cell > 0.f &&
+                         rq->near_plane*1.001f < sc->wg_near;
+    if (gridded && (((uintptr_t)sc->wg_cells % 16) || ((uintptr_t)sc->wg_geom % 16))) return MS_EINVAL;
+    const MsAgents no_agents{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const unsigned blocks = (unsigned)((total + WG - 1)/WG);
+    hipLaunchKernelGGL(raycast_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *sc, ag ? *ag : no_agents, *rq, ag ? 1 : 0,
+                       gridded ? 1 : 0, (int)total);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MS_OK : hip_fail(e);
+}
+
+int ms_camera_rays(const MsAgents* ag, int n_envs, int n_agents, const MsConfig* cfg, float* dirs, void* stream) {
+    if (!ag || !ag->angles || n_envs < 1 || n_agents < 1 || !config_ok(cfg) || !dirs || ((uintptr_t)dirs % 8)) return MS_EINVAL;
+    const long long total = (long long)n_envs*n_agents*cfg->res;
+    if ((long long)n_envs*n_agents > 0x7fffffffLL || total > 0x7fffff00LL*(long long)WG) return MS_EUNSUPPORTED;
+    // kernels.cu:22, as ms_render works it out
+    const float half_screen = tanf(3.14159265358979323846f/180.f*cfg->fov/2.);
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, ag->angles,
+                       n_envs*n_agents, cfg->res, half_screen, camera_inv_res(cfg->res, half_screen), reinterpret_cast<float2*>(dirs));
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MS_OK : hip_fail(e);
+}
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {
     (void)cfg;
