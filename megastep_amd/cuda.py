@@ -11,9 +11,9 @@ reference: docs/faq.rst:23-26): calling bake/physics/render on non-GPU tensors r
 import ctypes as C
 import numbers
 import os
-import sys
 import torch
-from . import _lib
+from . import _lib, grids
+from ._lib import _on, _stream
 
 # ---------------------------------------------------------------------------------------------------------------------
 # initialize                                                                   reference: kernels.cu:18-27
@@ -254,10 +254,11 @@ class Scenery:
                 raise RuntimeError('geom must have one entry per env, on the same device as the lines')
         self._geom = geom
         self._struct = None
-        self._lg = None             # the light grid's tensors; made by _as_struct unless sharding carried one over
+        self._lg = None             # the grids.LightGrid, or None; decided by _as_struct unless sharding carried one over
+        self._lg_decided = False
         self._wg_sum = None         # checksum of the static walls the wall grid was built from
         self._wg_weights = None
-        self._wg = None             # the wall grid's tensors (cells, starts, geom, cell, reaches, near plane, pool, near rows, pool bases); made by bake()
+        self._wg = None             # the grids.WallGrid, or None; made by bake()
         self._wg_report = self._lg_report = None      # what was built, at which cell size, in how many bytes (grid_report())
         self._dev = None
 
@@ -289,117 +290,6 @@ class Scenery:
     #: None: an eighth of the device's memory (36 GB of an MI355X's 288; 8 GiB for tensors that are not on a GPU).
     LIGHT_GRID_BYTES = int(float(os.environ['MEGASTEP_LIGHT_GRID_BYTES'])) if os.environ.get('MEGASTEP_LIGHT_GRID_BYTES') else None
 
-    def _light_grid_budget(self):
-        if self.LIGHT_GRID_BYTES is not None:
-            return int(self.LIGHT_GRID_BYTES)
-        dev = self._lines.vals.device
-        return _memory_share(dev, 8) if dev.type == 'cuda' else 8 << 30
-
-    def _light_grid(self):
-        """Storage and geometry of the light grid (see include/megastep_hip.h): a uniform grid over each env's walls,
-        half a metre of slack around them: per cell the lights' verdicts and a candidate list drawn from a shared pool.
-        `bake` fills it in; zeros mean 'unknown, test every wall', which is always safe. Envs that share their
-        geometry (`geom`) share their representative's cells. 264 bytes per cell (16 verdicts + 8 list header + 12 pool
-        words of 4 + 16 each), i.e. hundreds of times the floorplan's own lines - hence the sharing, the byte budget
-        (LIGHT_GRID_BYTES) and no grid at all for single-agent sceneries, whose rays never land on an agent."""
-        ln = self._lines
-        dev = ln.vals.device
-        n_envs = len(ln)
-        lo, hi = self._wall_bounds()
-        origin = torch.floor(lo) - .5
-        rep = torch.arange(n_envs, device=dev) if self._geom is None else self._geom.long()
-        is_rep = rep == torch.arange(n_envs, device=dev)
-        cell, with_rows = float(self.LIGHT_GRID_CELL), True
-        budget = self._light_grid_budget()
-        while True:
-            dims = torch.ceil((hi + .5 - origin)/cell).clamp(1, 4096)
-            # the grid holds 64 lights per env: an env with more gets no cells, and the renderer meets every wall for the
-            # rays that land on an agent there (the other envs keep their grids, and the launch stays one kernel)
-            dims = torch.where((self._lights.widths <= 64)[:, None], dims, torch.zeros_like(dims))
-            cells = (dims[:, 0]*dims[:, 1]).long()
-            own = cells*is_rep                                             # members own no cells
-            total = int(own.sum())
-            words = min(1 + self.LIGHT_GRID_POOL*total, 2**31 - 1)
-            size = 24*(total + 1) + (20 if with_rows else 4)*words
-            if size <= budget or cell >= 8.:
-                break
-            if with_rows:
-                with_rows = False
-            else:
-                cell *= 2
-        starts = (own.cumsum(0) - own)[rep].to(torch.int32)
-        geom = torch.cat([origin, dims], 1).float()[rep].contiguous()
-        vals = torch.zeros((total + 1, 4), dtype=torch.int32, device=dev)     # (+ a row for rays outside the last env's grid to read)
-        lists = torch.zeros((total + 1, 2), dtype=torch.int32, device=dev)
-        pool = torch.zeros(words, dtype=torch.int32, device=dev)
-        # the candidates' walls, next to their entries (MsScenery.lg_pool_rows; optional)
-        rows = torch.zeros((words, 4), dtype=torch.float32, device=dev) if with_rows else None
-        self._lg_report = dict(bytes=size, cell=cell, cells=total, candidate_rows=with_rows, budget=budget,
-                               floorplans=int(is_rep.sum()))
-        if os.environ.get('MEGASTEP_VERBOSE'):
-            print(f'megastep_amd: light grid of {size/2**20:.0f} MiB: {total} cells of {cell:g} m over {int(is_rep.sum())} floorplans'
-                  + ('' if with_rows else ', without candidate rows') + (f' (asked for {self.LIGHT_GRID_CELL:g} m: over the '
-                  f'{budget/2**30:.1f} GiB budget)' if cell != self.LIGHT_GRID_CELL or not with_rows else ''), flush=True)
-        return vals, starts.contiguous(), geom, cell, max(int(cells.max()), 1), lists, pool, rows
-
-    def grid_report(self):
-        """What bake() built around the floorplans, for logs and bench lines: {'wall_grid': {bytes, cell, floorplans, ...} or
-        None, 'light_grid': {bytes, cell, cells, candidate_rows, ...} or None, 'bake_seconds': {lighting, wall_grid} of the last
-        cuda.bake()} - the sizes actually allocated and the cell sizes actually used (either grid coarsens itself to stay inside
-        its byte budget)."""
-        marks = getattr(self, '_bake_marks', None)
-        if getattr(self, '_bake_s', None) is None and marks is not None and marks[0] is not None:
-            ev, wall_grid = marks
-            ev[2].synchronize()
-            self._bake_s = dict(lighting=ev[0].elapsed_time(ev[1])*1e-3, wall_grid=ev[1].elapsed_time(ev[2])*1e-3 if wall_grid else 0.)
-        return dict(wall_grid=self._wg_report, light_grid=self._lg_report, bake_seconds=getattr(self, '_bake_s', None))
-
-    def _wall_bounds(self):
-        """(n_envs, 2) lower and upper corner of each env's static walls (finite coordinates only; 0, 0 without any)."""
-        ln = self._lines
-        dev = ln.vals.device
-        n_envs = len(ln)
-        env = ln.inverse.long()
-        static = (torch.arange(ln.vals.shape[0], device=dev) - ln.starts.long()[env]) >= self._n_agents*self._model.shape[0]
-        env, pts = env[static], ln.vals[static]              # the walls; agent rows move
-        big = torch.finfo(torch.float32).max
-        fin = torch.isfinite(pts)
-        idx = env[:, None].expand(-1, 2)
-        lo = torch.full((n_envs, 2), big, device=dev).scatter_reduce_(0, idx, torch.where(fin, pts, big).amin(1), 'amin')
-        hi = torch.full((n_envs, 2), -big, device=dev).scatter_reduce_(0, idx, torch.where(fin, pts, -big).amax(1), 'amax')
-        empty = (lo > hi).any(1)                             # an env without (finite) walls gets a 1 x 1 grid at the origin
-        lo[empty], hi[empty] = 0., 0.
-        return lo, hi
-
-    def _as_struct(self):
-        if self._struct is None:
-            li, ln, tx = self._lights, self._lines, self._textures
-            if self._lg is None:
-                # (one agent per env: no ray ever lands on an agent line, so nothing would consult the grid)
-                wanted = self._n_agents > 1 and self.LIGHT_GRID
-                self._lg = self._light_grid() if wanted else (None, None, None, 0., 0, None, None, None)
-            lg = self._lg
-            self._struct = _lib.MsScenery(
-                len(ln), self._n_agents, self._model.shape[0],
-                li.vals.data_ptr(), li.widths.data_ptr(), li.starts.data_ptr(),
-                ln.vals.data_ptr(), ln.widths.data_ptr(), ln.starts.data_ptr(), ln.inverse.data_ptr(),
-                tx.vals.data_ptr(), tx.widths.data_ptr(), tx.starts.data_ptr(), tx.inverse.data_ptr(),
-                self._model.data_ptr(), self._baked.vals.data_ptr(),
-                ln.vals.shape[0], li.vals.shape[0], tx.vals.shape[0],
-                *(t.data_ptr() if t is not None else None for t in lg[:3]), lg[3], lg[4],
-                *(t.data_ptr() if t is not None else None for t in lg[5:7]), lg[6].shape[0] if lg[6] is not None else 0,
-                lg[7].data_ptr() if len(lg) > 7 and lg[7] is not None else None,
-                self._geom.data_ptr() if self._geom is not None else None, None, None, 0,
-                *self._wall_grid_fields(), self._model_radius)
-        return self._struct
-
-    def _wall_grid_fields(self):
-        wg = self._wg
-        if wg is None:
-            return (None, None, None, 0., 0., 0., 0., None, None, None)
-        cells, starts, geom, cell, reach_lo, reach, near, pool, rows, pool_base = wg
-        return (cells.data_ptr(), starts.data_ptr(), geom.data_ptr(), cell, reach_lo, reach, near, pool.data_ptr(), pool_base.data_ptr(), rows.data_ptr())
-
     #: the wall grid (include/megastep_hip.h, MsScenery.wg_*): cell size in metres; the step lengths its collision lists
     #: cover (0.7 m: the momentum module at its defaults never reaches farther; 1.3 m: nor does the simple one at 10 fps);
     #: the near plane its visibility lists allow for; how much memory it may take - beyond that the cells are doubled in
@@ -416,208 +306,61 @@ class Scenery:
     WALL_GRID_SCRATCH = 1 << 30         # bytes of bitmaps in flight while it is built
     WALL_GRID_COARSE = 4                # the parent level's cells, in cells (None: one level, every wall a candidate)
 
-    def _wall_grid_budget(self):
-        if self.WALL_GRID_BYTES is not None:
-            return int(self.WALL_GRID_BYTES)
-        return _memory_share(self._device(), 4)
+    def grid_report(self):
+        """What bake() built around the floorplans, for logs and bench lines: {'wall_grid': {bytes, cell, floorplans, ...} or
+        None, 'light_grid': {bytes, cell, cells, candidate_rows, ...} or None, 'bake_seconds': {lighting, wall_grid} of the last
+        cuda.bake()} - the sizes actually allocated and the cell sizes actually used (either grid coarsens itself to stay inside
+        its byte budget)."""
+        marks = getattr(self, '_bake_marks', None)
+        if getattr(self, '_bake_s', None) is None and marks is not None and marks[0] is not None:
+            ev, wall_grid = marks
+            ev[2].synchronize()
+            self._bake_s = dict(lighting=ev[0].elapsed_time(ev[1])*1e-3, wall_grid=ev[1].elapsed_time(ev[2])*1e-3 if wall_grid else 0.)
+        return dict(wall_grid=self._wg_report, light_grid=self._lg_report, bake_seconds=getattr(self, '_bake_s', None))
 
-    def _scan_level(self, cell, parent, final, usable):
-        """One level of the wall grid: cells of size `cell` over every representative floorplan, scanned (against the
-        parent level's lists, if there is one) and filled. Returns (hdr (cells + 1, 4) int32 holding uint32s, starts, geom,
-        pool int16, near rows float32 or None, bytes) - or None where there is nothing to build / the budget is exceeded."""
-        dev = self._device()
-        ln = self._lines
-        n_envs = len(ln)
-        af = self._n_agents*self._model.shape[0]
-        walls = (ln.widths.long() - af).clamp(min=0)
-        arange = torch.arange(n_envs, device=dev)
-        rep = arange if self._geom is None else self._geom.long()
-        is_rep = rep == arange
-        lo, hi = self._wall_bounds()
-        h = _lib.lib()
-        origin = torch.floor(lo) - .5
-        dims = torch.ceil((hi + .5 - origin)/self.WALL_GRID_CELL).clamp(min=1)      # in the finest cells ...
-        scale = round(cell/self.WALL_GRID_CELL)
-        dims = torch.ceil(dims/scale)                                               # ... so that every level covers the same ground
-        cells = (dims[:, 0]*dims[:, 1])
-        dims = torch.where(usable[:, None], dims, torch.zeros_like(dims))           # (the same envs at every level)
-        cells = torch.where(usable, cells, torch.zeros_like(cells)).long()
-        own = cells*is_rep                                             # members own no cells
-        starts = (own.cumsum(0) - own)[rep].to(torch.int32).contiguous()
-        geom = torch.cat([origin, dims], 1).float()[rep].contiguous()
-        total = int(own.sum())
-        if total == 0:
-            return None
-        w32 = (walls + 31)//32
-        row_words = 3*own*w32                                          # bitmap words per representative
-        reps = torch.nonzero(own > 0).flatten()
-        struct = _lib.MsScenery.from_buffer_copy(self._as_struct())
-        struct.wg_starts, struct.wg_geom, struct.wg_cell = starts.data_ptr(), geom.data_ptr(), cell
-        struct.wg_reach_lo, struct.wg_reach, struct.wg_near = *self.WALL_GRID_REACH, self.WALL_GRID_NEAR
-        par = None
-        if parent is not None:
-            par = _lib.MsWallGridParent(parent[0].data_ptr(), parent[1].data_ptr(), parent[2].data_ptr(), parent[3], parent[4].data_ptr())
-        counts = torch.zeros((total, 3), dtype=torch.int32, device=dev)
-        # groups of representatives whose bitmaps fit the scratch budget (and a launch's grid)
-        words = row_words[reps]
-        group = torch.maximum((words.cumsum(0) - words)*4//self.WALL_GRID_SCRATCH, torch.arange(len(reps), device=dev)//60000)
-        bounds = [0] + (torch.nonzero(group[1:] != group[:-1]).flatten() + 1).tolist() + [len(reps)]
-        pools, nears = [], []
-        budget = self._wall_grid_budget()
-        cell_rows = torch.zeros((total + 1, 4), dtype=torch.int64, device=dev)     # (+ the row agents outside the last grid read)
-        # where each floorplan's vis lists start in the pool (MsScenery.wg_pool_base; the final level's cells count their
-        # "first vis entry" from there: a world of thousands of large plans has more entries than 32 bits number)
-        pool_base = torch.zeros(n_envs, dtype=torch.int64, device=dev)
-        struct.wg_pool_base = pool_base.data_ptr()
-        base_p = base_n = 0
-        with _on(dev):
-            for g0, g1 in zip(bounds[:-1], bounds[1:]):
-                r = reps[g0:g1]
-                r32 = r.to(torch.int32).contiguous()
-                gw = row_words[r]
-                bits_starts = torch.zeros(n_envs, dtype=torch.int64, device=dev)
-                bits_starts[r] = gw.cumsum(0) - gw
-                bits = torch.zeros(max(int(gw.sum()), 1), dtype=torch.int32, device=dev)
-                mc = int(cells[r].max())
-                groups = int(parent[5][r].max()) if parent is not None else (mc + 3)//4
-                _lib.check(h.ms_wallgrid_scan(C.byref(struct), C.byref(par) if par is not None else None, r32.data_ptr(), len(r), groups,
-                                              bits_starts.data_ptr(), bits.data_ptr(), counts.data_ptr(), _stream(dev)))
-                # the cells of this group, in storage order, and their lists' places in the pools
-                span = own[r]
-                rows = torch.repeat_interleave(starts[r].long() - (span.cumsum(0) - span), span) + torch.arange(int(span.sum()), device=dev)
-                cnt = counts[rows].long()                              # (cells, 3): vis, near within the short reach, near beyond
-                n_vis, n_near = cnt[:, 0], cnt[:, 1] + cnt[:, 2]
-                if final:                                              # vis -> pool (entries), near -> rows
-                    off_v, off_n = n_vis.cumsum(0) - n_vis, n_near.cumsum(0) - n_near + base_n
-                    add_p, add_n = int(n_vis.sum()), int(n_near.sum())
-                    # ... the vis lists numbered from their floorplan's own start
-                    first_cell = span.cumsum(0) - span                 # each representative's first cell among this group's
-                    rep_off = off_v[first_cell.clamp(max=len(off_v) - 1)]
-                    pool_base[r] = rep_off + base_p
-                    off_v = off_v - torch.repeat_interleave(rep_off, span)
-                else:                                                  # both lists as indices, back to back
-                    both = torch.stack([n_vis, n_near], 1).flatten()
-                    off = (both.cumsum(0) - both + base_p).view(-1, 2)
-                    off_v, off_n = off[:, 0], off[:, 1]
-                    add_p, add_n = int(both.sum()), 0
-                if (4 if final else 2)*(base_p + add_p) + 16*(base_n + add_n) > budget \
-                        or (not final and base_p + add_p >= 2**32 - 64) or (final and int(off_v.max()) + int(n_vis.max()) >= 2**32 - 64) \
-                        or base_n + add_n >= 2**32 \
-                        or int(n_near.max()) > 65535:
-                    return None
-                cell_rows[rows] = torch.stack([off_v, n_vis, off_n, cnt[:, 1] + (n_near << 16)], 1)
-                hdr = _as_u32(cell_rows)
-                # (final level: vis entries of 32 bits - wall and view arc; a parent level: bare 16-bit wall numbers)
-                pool = torch.zeros(add_p + 64, dtype=torch.int32 if final else torch.int16, device=dev)
-                near = torch.zeros((max(add_n, 1), 4), dtype=torch.float32, device=dev) if final else None
-                struct.wg_cells = hdr.data_ptr()
-                # the fill kernel writes at the headers' offsets: hand it this group's pools displaced by what came before
-                _lib.check(h.ms_wallgrid_fill(C.byref(struct), r32.data_ptr(), len(r), mc, bits_starts.data_ptr(), bits.data_ptr(),
-                                              None if final else C.c_void_p(pool.data_ptr() - 2*base_p),
-                                              C.c_void_p(pool.data_ptr() - 4*base_p) if final else None,      # (+ wg_pool_base[n], in the kernel)
-                                              C.c_void_p(near.data_ptr() - 16*base_n) if final else None, _stream(dev)))
-                torch.cuda.current_stream(dev).synchronize()           # (hdr / bits / pools of this group are done with)
-                pools.append(pool[:add_p])
-                if final:
-                    nears.append(near[:add_n])
-                base_p, base_n = base_p + add_p, base_n + add_n
-        pool = torch.cat(pools + [torch.zeros(64, dtype=pools[0].dtype, device=dev)])
-        near = torch.cat(nears + [torch.zeros((1, 4), dtype=torch.float32, device=dev)]) if final else None
-        pool_base = pool_base[rep].contiguous()                       # (members: their representative's)
-        return _as_u32(cell_rows), starts, geom, pool, near, cells.to(torch.int32), pool_base
+    _light_grid = grids.light_grid      # (builds a fresh light grid each call; _as_struct decides once per scenery)
 
-    def _wall_checksum(self):
-        """A 64-bit checksum of the static walls' rows as they are now (their bits, position-weighted, summed modulo 2^64):
-        what the wall grid was built from, if taken when it was. (The weights - zero for the agents' rows, which every
-        render rewrites - are made once per scenery: the check itself is one multiply-and-sum over the lines.)"""
-        ln = self._lines
-        if self._wg_weights is None:
-            af = self._n_agents*self._model.shape[0]
-            k = torch.arange(ln.vals.shape[0], device=ln.vals.device)
-            static = (k - ln.starts.long()[ln.inverse.long()]) >= af
-            self._wg_weights = ((8*k[:, None] + 2*torch.arange(4, device=k.device)[None] + 1)*0x9E3779B1)*static[:, None]   # odd, distinct per word
-        return int((ln.vals.reshape(-1, 4).view(torch.int32)*self._wg_weights).sum())
+    def _as_struct(self):
+        if self._struct is None:
+            li, ln, tx = self._lights, self._lines, self._textures
+            if not self._lg_decided:
+                # (one agent per env: no ray ever lands on an agent line, so nothing would consult the grid)
+                self._lg = self._light_grid() if self._n_agents > 1 and self.LIGHT_GRID else None
+                self._lg_decided = True
+            self._struct = _lib.MsScenery(
+                n_envs=len(ln), n_agents=self._n_agents, n_model=self._model.shape[0],
+                lights_vals=li.vals.data_ptr(), lights_widths=li.widths.data_ptr(), lights_starts=li.starts.data_ptr(),
+                lines_vals=ln.vals.data_ptr(), lines_widths=ln.widths.data_ptr(), lines_starts=ln.starts.data_ptr(), lines_inverse=ln.inverse.data_ptr(),
+                textures_vals=tx.vals.data_ptr(), textures_widths=tx.widths.data_ptr(), textures_starts=tx.starts.data_ptr(),
+                textures_inverse=tx.inverse.data_ptr(), model=self._model.data_ptr(), baked_vals=self._baked.vals.data_ptr(),
+                n_lines_total=ln.vals.shape[0], n_lights_total=li.vals.shape[0], n_texels_total=tx.vals.shape[0],
+                env_geom=self._geom.data_ptr() if self._geom is not None else None, model_radius=self._model_radius,
+                **grids.struct_fields(self._lg, self._wg))
+        return self._struct
 
     def check_wall_grid(self):
         """Raises if the static walls are no longer the ones the wall grid was built from (see :func:`bake`): rays and
         collisions that walk a stale grid silently miss the walls that moved. One reduction over the lines and a sync -
         switched on for every :func:`render` / :func:`physics` call by ``MEGASTEP_CHECK_GRID=1`` (as the test suite runs)."""
-        if self._wg is not None and self._wg_sum != self._wall_checksum():
+        if self._wg is not None and self._wg_sum != grids.wall_checksum(self):
             raise RuntimeError('static walls have been changed since cuda.bake() built the wall grid from them: bake again '
                                '(or bake(wall_grid=False) to go without a grid)')
 
     def _build_wall_grid(self):
-        """Builds the wall grid from the static walls as they are now (called by :func:`bake`): per floorplan a uniform
-        grid, per cell the walls a ray from the cell can be decided by and the walls an agent in it can run into - first
-        for cells WALL_GRID_COARSE times the size, whose lists are all that the cells proper then look at. Installs ``_wg``."""
-        self._wg, self._struct = None, None
-        self._wg_sum = None
-        self._wg_report = None
-        if not self.WALL_GRID:
-            return
-        ln = self._lines
-        if len(ln) == 0 or int((ln.widths.long() - self._n_agents*self._model.shape[0]).max()) <= 0:
-            return
-        lo, hi = self._wall_bounds()
-        walls = (ln.widths.long() - self._n_agents*self._model.shape[0]).clamp(min=0)
-        for cell in (self.WALL_GRID_CELL, 2*self.WALL_GRID_CELL, 4*self.WALL_GRID_CELL):
-            # which envs get a grid at all: some walls, not too many for 16-bit indices, not too large an area
-            extent = torch.ceil((hi - lo + 1.5)/cell).clamp(min=1)
-            usable = (extent[:, 0]*extent[:, 1] <= self.WALL_GRID_MAX_CELLS) & (walls > 0) & (walls <= 65535)
-            parent = None
-            if self.WALL_GRID_COARSE:
-                try:
-                    level = self._scan_level(cell*self.WALL_GRID_COARSE, None, False, usable)
-                except torch.cuda.OutOfMemoryError:
-                    level = None
-                    torch.cuda.empty_cache()
-                if level is not None:
-                    hdr, starts, geom, pool, _, cells, _ = level
-                    parent = (hdr, starts, geom, float(cell*self.WALL_GRID_COARSE), pool, cells)
-            try:
-                level = self._scan_level(cell, parent, True, usable)
-            except torch.cuda.OutOfMemoryError:
-                # (the budget is an estimate of the final size; the build's peak is higher - on a device that is nearly full the
-                # next coarser level is the answer, not a crash)
-                level, parent = None, None
-                torch.cuda.empty_cache()
-            if level is not None:
-                hdr, starts, geom, pool, near, _, pool_base = level
-                self._wg = (hdr, starts, geom, float(cell), float(self.WALL_GRID_REACH[0]), float(self.WALL_GRID_REACH[1]),
-                            float(self.WALL_GRID_NEAR), pool, near, pool_base)
-                self._wg_sum = self._wall_checksum()
-                self._struct = None
-                size = sum(t.numel()*t.element_size() for t in (hdr, starts, geom, pool, near, pool_base))
-                arange = torch.arange(len(ln), device=hdr.device)
-                reps = int((usable & ((self._geom.long() if self._geom is not None else arange) == arange)).sum())
-                self._wg_report = dict(bytes=size, bytes_per_floorplan=size/max(reps, 1), cell=float(cell), cells=int(hdr.shape[0] - 1),
-                                       envs=int(usable.sum()), floorplans=reps,
-                                       vis_entries=int(pool.numel() - 64), near_rows=int(near.shape[0] - 1), budget=self._wall_grid_budget(),
-                                       coarsened=cell != self.WALL_GRID_CELL)
-                if os.environ.get('MEGASTEP_VERBOSE') or cell != self.WALL_GRID_CELL:
-                    # (a grid that had to coarsen costs the step 3-6 %: never silently)
-                    print(f'megastep_amd: wall grid of {size/2**20:.0f} MiB for {int(usable.sum())} envs ({reps} floorplans) at {cell:g} m cells'
-                          + (f' - {self.WALL_GRID_CELL:g} m cells would not fit WALL_GRID_BYTES = {self._wall_grid_budget()/2**30:.1f} GiB'
-                             if cell != self.WALL_GRID_CELL else ''), file=sys.stderr, flush=True)
-                return
-        self._wg_report = dict(bytes=0, cell=None, budget=self._wall_grid_budget(), note='no env a grid could be built for, or none within the budget')
-        print(f'megastep_amd: no wall grid built (no env it could serve, or not even {4*self.WALL_GRID_CELL:g} m cells within WALL_GRID_BYTES = '
-              f'{self._wall_grid_budget()/2**30:.1f} GiB): every ray and agent meets every wall of its env', file=sys.stderr, flush=True)
+        """(Re)builds the wall grid from the static walls as they are now (called by :func:`bake`; see grids.wall_grid)."""
+        self._wg = self._wg_sum = self._wg_report = self._struct = None      # (the scans read a struct without a wall grid)
+        self._wg = grids.wall_grid(self) if self.WALL_GRID else None
+        self._wg_sum, self._struct = (grids.wall_checksum(self) if self._wg is not None else None), None
 
     def _bake_plan(self):
         """Scratch for the two-phase bake (MsScenery.bake_vis): for each representative env, lights x ceil(texels/64)
         words. Returns (vis, starts) - torch tensors that must outlive the launch."""
         li, ln, tx = self._lights, self._lines, self._textures
-        dev = ln.vals.device
-        n_envs = len(ln)
         first, last = ln.starts.long(), (ln.ends - 1).long().clamp(min=0)
         texels = torch.where(ln.widths > 0, tx.ends.long()[last] - tx.starts.long()[first], torch.zeros_like(first))
-        words = li.widths.long()*((texels + 63)//64)
-        rep = torch.arange(n_envs, device=dev) if self._geom is None else self._geom.long()
-        own = words*(rep == torch.arange(n_envs, device=dev))
-        starts = (own.cumsum(0) - own)[rep].contiguous()
+        lay = grids.representatives(li.widths.long()*((texels + 63)//64), self._geom)
         # (zeroed: a row that visibility_kernel's bounds check skipped reads as 'nothing blocks', never as garbage)
-        return torch.zeros(max(int(own.sum()), 1), dtype=torch.int64, device=dev), starts
+        return torch.zeros(max(lay.total, 1), dtype=torch.int64, device=ln.vals.device), lay.starts.contiguous()
 
     def _device(self):
         """The GPU all of this scenery's tensors live on (checked once; the tensors cannot be swapped out)."""
@@ -662,49 +405,6 @@ class Physics:
 # ---------------------------------------------------------------------------------------------------------------------
 # kernels
 # ---------------------------------------------------------------------------------------------------------------------
-_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-
-
-def _stream(dev):
-    # (the current stream's handle straight from torch's C side: torch.cuda.current_stream() builds a Stream object around it
-    # first - 5 us of the host's 25 per launch, three launches a step)
-    if _raw_stream is not None and dev.index is not None:
-        return C.c_void_p(_raw_stream(dev.index))
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _as_u32(t):
-    """An int64 tensor of values below 2^32 as the int32 tensor whose bits are those values as uint32."""
-    return torch.where(t >= 2**31, t - 2**32, t).to(torch.int32).contiguous()
-
-
-def _memory_share(dev, fraction):
-    """The default byte budget of a grid: 1/`fraction` of the device's memory - but never more than a third of what is FREE on
-    it right now (next to a policy and its optimizer, or on a small GPU, a share of the TOTAL is memory that is not there:
-    ADVICE r5; building a wall grid peaks at about twice its final size, so a third of the free memory is what can be afforded)."""
-    total = torch.cuda.get_device_properties(dev).total_memory
-    try:
-        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)   # (+ what torch's cache holds idle)
-    except Exception:
-        free = total
-    return int(min(total//fraction, free//3))
-
-
-class _on:
-    """Makes ``dev`` the current HIP device for the launch if it is not already."""
-
-    def __init__(self, dev):
-        self._guard = None if dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self._guard is not None:
-            self._guard.__enter__()
-
-    def __exit__(self, *exc):
-        if self._guard is not None:
-            self._guard.__exit__(*exc)
-
-
 def _agents_on(agents, dev):
     if agents._dev != dev:
         if agents._dev is None or not agents._dev.type == 'cuda':
@@ -1009,7 +709,7 @@ def _render_buffers(scenery, n, a, r, fields, pooled, dev):
     """One allocation for the wanted outputs (reference: five at::empty calls, kernels.cu:461-469), the pooled
     observations and the kernels' scratch (MS_RENDER_WORKSPACE_INTS), and the MsRender that points into it."""
     scenery._as_struct()
-    lit = a == 1 or scenery._lg[0] is not None
+    lit = a == 1 or scenery._lg is not None
     key = (n, a, r, None if fields is None else tuple(fields), None if pooled is None else tuple(sorted(pooled.items())), lit)
     layout = _layouts.get(key)
     if layout is None:

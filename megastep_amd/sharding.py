@@ -5,7 +5,8 @@ of a node each own ``n_envs/8`` envs and never talk to each other; xGMI/RCCL car
 One process per GPU (the reference's implicit current-device model, common.h:39-41).
 """
 import torch
-from . import cuda
+from . import cuda, grids
+_shard_light_grid = lambda lg, *a, **kw: grids.shard_light_grid(grids.LightGrid(*lg, *[None]*(8 - len(lg))), *a, **kw)   # (fields in order; pool_rows optional)
 
 
 def env_slice(n_envs, rank, world_size, cost=None):
@@ -67,42 +68,12 @@ def shard_scenery(scenery, rank, world_size, device=None, cost=None):
     out.baked.vals.copy_(scenery.baked[l0:l1].vals)
     # the light grid (what ms_bake caches about which lights reach which cells) is per floorplan: carry the slice's over
     parent = getattr(scenery, '_lg', None)
-    if parent is not None and parent[0] is not None and out.model.is_cuda:
-        out._lg = _shard_light_grid(parent, start, stop, device, geom)
+    if parent is not None and out.model.is_cuda:
+        out._lg, out._lg_decided = grids.shard_light_grid(parent, start, stop, device, geom), True
     # the wall grid (per floorplan, too) is rebuilt from the shard's own walls: two launches
     if getattr(scenery, '_wg', None) is not None and out.model.is_cuda:
         out._build_wall_grid()
     return out
-
-
-def _shard_light_grid(lg, start, stop, device, geom=None):
-    """Envs [start, stop) of a baked light grid (cuda.Scenery._light_grid's tuple): the cells of the slice's
-    representative envs (`geom`, slice-local; None = every env its own) back to back, the candidate lists repacked into
-    a pool of their own (the parent's pool is filled in no particular order)."""
-    vals, starts, grid, cell, _, lists, pool = lg[:7]
-    pool_rows = lg[7] if len(lg) > 7 else None
-    dev = vals.device
-    n = stop - start
-    rep = torch.arange(n, device=dev) if geom is None else geom.long().to(dev)
-    sub_geom = grid[start:stop]
-    cells = (sub_geom[:, 2]*sub_geom[:, 3]).long()
-    own = cells*(rep == torch.arange(n, device=dev))
-    new_starts = (own.cumsum(0) - own)
-    total = int(own.sum())
-    # for every cell of the shard, the parent's row it copies
-    src = torch.arange(total, device=dev) + torch.repeat_interleave(starts[start:stop].long() - new_starts, own, output_size=total)
-    rows = lists[src].long() & 0xffffffff
-    count = torch.where(rows[:, 1] != 0, rows[:, 1] & 0x7fffffff, torch.zeros_like(rows[:, 1]))
-    first = count.cumsum(0) - count                                   # 0-based position in the new pool's payload
-    cell_of = torch.repeat_interleave(torch.arange(len(count), device=dev), count)
-    take = rows[cell_of, 0] + (torch.arange(int(count.sum()), device=dev) - first[cell_of])
-    sub_pool = torch.cat([count.sum()[None].to(pool.dtype), pool[take]])
-    sub_rows = None if pool_rows is None else torch.cat([torch.zeros_like(pool_rows[:1]), pool_rows[take]]).to(device).contiguous()
-    sub_lists = torch.stack([torch.where(rows[:, 1] != 0, first + 1, torch.zeros_like(first)), rows[:, 1]], 1).to(torch.int32)
-    pad = lambda t: torch.cat([t, torch.zeros_like(t[:1])])               # (the row rays outside the last env's grid read)
-    return (pad(vals[src]).to(device).contiguous().clone(), new_starts[rep].to(torch.int32).to(device).contiguous(),
-            sub_geom.to(device).contiguous().clone(), cell, max(int(cells.max()), 1), pad(sub_lists).to(device).contiguous(),
-            sub_pool.to(device).contiguous(), sub_rows)
 
 
 def max_over_ranks(seconds, device=None):

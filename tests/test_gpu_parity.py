@@ -240,7 +240,9 @@ def test_light_grid_verdicts_hold_for_every_sampled_point():
     evaluate the reference's obstructed() test against all walls."""
     c, _ = _world(6, 2, 64, 130, seed=3)
     sc = c.scenery
-    vals, starts, geom, cell, _, lists, pool, pool_rows = (t.cpu().numpy() if torch.is_tensor(t) else t for t in sc._lg)
+    lg = sc._lg
+    vals, starts, geom, lists, pool, pool_rows = (t.cpu().numpy() for t in (lg.vals, lg.starts, lg.geom, lg.lists, lg.pool, lg.pool_rows))
+    cell = lg.cell
     pool = pool.astype(np.uint32)
     rng = np.random.RandomState(0)
     n_lit = n_dark = n_open = n_listed = n_cells = 0
@@ -305,7 +307,7 @@ def test_crowded_rooms_exercise_dynamic_lighting(monkeypatch, res, fov, cell, bu
     c, geometries = _world(24, 4, res, fov, seed=5)
     if budget is not None:
         rep = c.scenery.grid_report()['light_grid']
-        assert not rep['candidate_rows'] and c.scenery._lg[7] is None and (rep['cell'] == cell) == (budget == 'no rows')
+        assert not rep['candidate_rows'] and c.scenery._lg.pool_rows is None and (rep['cell'] == cell) == (budget == 'no rows')
     rng = np.random.RandomState(2)
     pos = np.zeros((24, 4, 2), np.float32)
     ang = np.zeros((24, 4), np.float32)
@@ -324,7 +326,7 @@ def test_crowded_rooms_exercise_dynamic_lighting(monkeypatch, res, fov, cell, bu
     idx = r.indices.cpu().numpy()
     assert ((idx >= 0) & (idx < 32)).mean() > .05, 'expected plenty of rays on agents'
     if cell > .25:
-        counts = (c.scenery._lg[5].view(-1, 2)[:, 1].cpu().numpy().astype(np.int64)) & 0x7fffffff
+        counts = (c.scenery._lg.lists.view(-1, 2)[:, 1].cpu().numpy().astype(np.int64)) & 0x7fffffff
         assert counts.max() > 64, 'expected candidate lists longer than one batch'
     util.assert_render_matches(c, r, ref.render())
 
@@ -408,7 +410,7 @@ def test_unbaked_scenery_and_shards_render_exactly():
         util.assert_render_matches(c, cuda.render(c.scenery, c.agents), ref.render())
     full = scene.scenery(gs, 3, device='cuda', random=np.random.RandomState(0))
     shard = sharding.shard_scenery(full, 1, 2)
-    assert torch.equal(shard._lg[0][:-1], full._lg[0][int(full._lg[1][3]):-1]) and shard._lg[0].any()     # (both end in a padding row)
+    assert torch.equal(shard._lg.vals[:-1], full._lg.vals[int(full._lg.starts[3]):-1]) and shard._lg.vals.any()     # (both end in a padding row)
     c = core.Core(shard, res=64, fov=130)
     util.spawn(c, gs[3:], seed=2)
     c.agents.positions[:, 2] = c.agents.positions[:, 0] + torch.tensor([.1, .45], device=c.device)
@@ -435,7 +437,7 @@ def test_more_than_64_lights_and_agents(monkeypatch):
         sc = scene.scenery(geoms, 3, device='cuda', random=np.random.RandomState(0))
         assert (sc._as_struct().lg_vals is not None) == grid
         if grid:                                                    # cells for the envs the grid can hold, none for the others
-            assert (sc._lg[2][:, 2] > 0).tolist() == [False, True, False, True]
+            assert (sc._lg.geom[:, 2] > 0).tolist() == [False, True, False, True]
         c = core.Core(sc, res=64, fov=130)
         spots = np.array([[3., 3.], [4., 3.1], [3.5, 4.]], np.float32) + rng.uniform(-.2, .2, (4, 3, 2)).astype(np.float32)
         c.agents.positions[:] = torch.as_tensor(spots, device=c.device)     # a triangle of agents looking at each other

@@ -167,7 +167,7 @@ def test_the_wall_grid_changes_no_bit_and_is_taken():
     assert torch.equal(worlds[0].scenery.lines.vals, worlds[1].scenery.lines.vals)
     rng = np.random.RandomState(12)
     o, d = _random_rays(worlds[0], rng, 1024, clustered=512)
-    wg_near = worlds[0].scenery._wg[6]
+    wg_near = worlds[0].scenery._wg.near
     for near, with_agents in ((.1, True), (.1, False), (wg_near*2, True), (0., False)):
         results = []
         for c in worlds:

@@ -91,7 +91,7 @@ def test_c5_per_gpu_shape_on_the_references_floorplan_diversity():
     assert rep['cell'] == cuda.Scenery.WALL_GRID_CELL and not rep['coarsened']
     assert rep['vis_entries'] > 3*2**30                                 # (measured: 6.9 x 10^9)
     if rep['vis_entries'] > 2**32:
-        assert int(c.scenery._wg[9].max()) > 2**32                      # pool bases beyond 32 bits are in play
+        assert int(c.scenery._wg.pool_base.max()) > 2**32                      # pool bases beyond 32 bits are in play
     exact = _check_sample(c, [0, 1, 4095, 4096, 20000, 28671, 32766, 32767], steps=2)
     print('C5 / 4096 plans baked bitwise-equal fraction:', exact)
 

@@ -28,7 +28,9 @@ def test_lists_built_on_the_gpu_are_the_host_scans():
     c, geometries = _world(12, 2, n_unique=5)
     sc = c.scenery
     assert sc._wg is not None
-    cells, starts, geom, cell, reach_lo, reach, near, pool, rows, pool_base = sc._wg
+    wg = sc._wg
+    cells, starts, geom, cell, pool, rows, pool_base = wg.cells, wg.starts, wg.geom, wg.cell, wg.pool, wg.near_rows, wg.pool_base
+    reach_lo, reach, near = wg.reach_lo, wg.reach, wg.near
     assert (reach_lo, reach, near) == tuple(np.float32([REACH_LO, REACH, NEAR]).astype(float)) or (reach_lo, reach, near) == (REACH_LO, REACH, NEAR)
     cells = cells.cpu().numpy().view(np.uint32)
     starts, geom, pool, rows = starts.cpu().numpy(), geom.cpu().numpy(), pool.cpu().numpy().view(np.uint32), rows.cpu().numpy()
@@ -116,10 +118,10 @@ def test_where_the_lists_do_not_apply_every_wall_is_met():
 def test_a_grid_too_big_for_its_budget_is_coarsened_or_left_out(monkeypatch):
     from megastep_amd import cuda
     c, _ = _world(4, 1, n_unique=2)
-    needed = 4*c.scenery._wg[7].numel() + 4*c.scenery._wg[8].numel()
+    needed = 4*c.scenery._wg.pool.numel() + 4*c.scenery._wg.near_rows.numel()
     monkeypatch.setattr(cuda.Scenery, 'WALL_GRID_BYTES', needed//2)
     c, _ = _world(4, 1, n_unique=2)
-    assert c.scenery._wg is not None and c.scenery._wg[3] > cuda.Scenery.WALL_GRID_CELL
+    assert c.scenery._wg is not None and c.scenery._wg.cell > cuda.Scenery.WALL_GRID_CELL
     ref = util.OracleWorld(c)
     util.assert_render_matches(c, cuda.render(c.scenery, c.agents), ref.render())
     monkeypatch.setattr(cuda.Scenery, 'WALL_GRID_BYTES', 100)

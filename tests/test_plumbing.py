@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 import torch
-from megastep_amd import core, cuda, cubicasa, geometry, ragged, scene, sharding, spaces, toys
+from megastep_amd import core, cuda, cubicasa, geometry, grids, ragged, scene, sharding, spaces, toys
 
 
 def test_box_room_scenery_on_cpu():
@@ -101,18 +101,18 @@ def test_the_light_grid_stays_inside_its_byte_budget(monkeypatch):
     its cells until it fits; what was built is in grid_report()."""
     g = cubicasa.sample(6, n_unique=16, seed=2)
     s = scene.scenery(g, 2, device='cpu', bake=False)
-    full = s._light_grid()
+    full = grids.light_grid(s)
     rep = s.grid_report()['light_grid']
-    assert rep['cell'] == cuda.Scenery.LIGHT_GRID_CELL and rep['candidate_rows'] and full[7] is not None and rep['floorplans'] == 6
-    assert rep['bytes'] == 24*(rep['cells'] + 1) + 20*full[6].shape[0]                      # verdicts + headers, pool words + their rows
+    assert rep['cell'] == cuda.Scenery.LIGHT_GRID_CELL and rep['candidate_rows'] and full.pool_rows is not None and rep['floorplans'] == 6
+    assert rep['bytes'] == 24*(rep['cells'] + 1) + 20*full.pool.shape[0]                    # verdicts + headers, pool words + their rows
     monkeypatch.setattr(cuda.Scenery, 'LIGHT_GRID_BYTES', rep['bytes'] - 1)
-    lean = s._light_grid()
+    lean = grids.light_grid(s)
     r = s.grid_report()['light_grid']
-    assert lean[7] is None and not r['candidate_rows'] and r['cell'] == rep['cell'] and r['bytes'] < rep['bytes']//3
+    assert lean.pool_rows is None and not r['candidate_rows'] and r['cell'] == rep['cell'] and r['bytes'] < rep['bytes']//3
     monkeypatch.setattr(cuda.Scenery, 'LIGHT_GRID_BYTES', rep['bytes']//20)
-    coarse = s._light_grid()
+    coarse = grids.light_grid(s)
     r = s.grid_report()['light_grid']
-    assert r['cell'] > rep['cell'] and r['bytes'] <= rep['bytes']//20 and coarse[3] == r['cell'] and coarse[0].shape[0] == r['cells'] + 1
+    assert r['cell'] > rep['cell'] and r['bytes'] <= rep['bytes']//20 and coarse.cell == r['cell'] and coarse.vals.shape[0] == r['cells'] + 1
     # a shard carries the lean grid over like any other (no rows to repack)
     assert s.grid_report()['wall_grid'] is None                                            # (never baked: no wall grid)
 
@@ -205,10 +205,9 @@ def test_shard_scenery_reassembles():
 
 
 def test_light_grid_shard_repacks_candidate_lists():
-    """sharding._shard_light_grid: a shard's cells keep their verdicts and candidate lists; the lists move to a
+    """grids.shard_light_grid: a shard's cells keep their verdicts and candidate lists; the lists move to a
     pool of the shard's own (the parent's pool is filled in no particular order). Pure tensor logic, so it runs here."""
     import torch
-    from megastep_amd import sharding
     rng = np.random.RandomState(0)
     dims = np.array([[3, 2], [1, 4], [2, 2], [5, 1]])
     cells = dims.prod(1)
@@ -233,13 +232,14 @@ def test_light_grid_shard_repacks_candidate_lists():
     to_i32 = lambda a: torch.tensor((np.asarray(a, np.int64) & 0xffffffff).astype(np.uint32).view(np.int32))
     # (next to every candidate its wall's row: here a row that names its entry, so that the repacking can be followed)
     rows = torch.tensor(np.asarray(pool, np.float64)[:, None]*np.array([1., 2., 3., 4.]) % 1000, dtype=torch.float32)
-    lg = (vals, starts, geom, .25, int(cells.max()), to_i32(lists), to_i32(pool), rows)
+    lg = grids.LightGrid(vals, starts, geom, .25, int(cells.max()), to_i32(lists), to_i32(pool), rows)
     for start, stop in [(0, 2), (1, 4), (2, 3), (0, 4)]:
-        v, s, g, cell, mx, l, p, pr = sharding._shard_light_grid(lg, start, stop, 'cpu')
+        sub = grids.shard_light_grid(lg, start, stop, 'cpu')
+        v, s, g, cell, mx, l, p, pr = sub.vals, sub.starts, sub.geom, sub.cell, sub.max_cells, sub.lists, sub.pool, sub.pool_rows
         assert pr.shape == (len(p), 4)
         want_rows = torch.tensor(((p.long() & 0xffffffff).double().numpy()[:, None]*np.array([1., 2., 3., 4.])) % 1000, dtype=torch.float32)
         assert torch.equal(pr[1:], want_rows[1:])                          # every entry still has its own row beside it
-        assert sharding._shard_light_grid(lg[:7], start, stop, 'cpu')[7] is None     # (a grid baked without rows shards without them)
+        assert grids.shard_light_grid(lg._replace(pool_rows=None), start, stop, 'cpu').pool_rows is None     # (a grid baked without rows shards without them)
         c0, c1 = int(starts[start]), int(starts[stop]) if stop < 4 else total
         assert torch.equal(v[:-1], vals[c0:c1]) and not v[-1].any() and torch.equal(g, geom[start:stop]) and cell == .25    # (+ the padding row)
         assert len(l) == len(v)
@@ -328,7 +328,8 @@ def test_shards_of_sceneries_with_shared_floorplans():
     vals = torch.arange(14*4, dtype=torch.int32).view(14, 4)
     lists = torch.zeros((14, 2), dtype=torch.int32)
     pool_ = torch.zeros(1, dtype=torch.int32)
-    v, s, g, cell, mx, l, p, _ = sharding._shard_light_grid((vals, starts, grid, .25, 6, lists, pool_), 4, 7, 'cpu', shard.geom)
+    sub = grids.shard_light_grid(grids.LightGrid(vals, starts, grid, .25, 6, lists, pool_, None), 4, 7, 'cpu', shard.geom)
+    v, s, g = sub.vals, sub.starts, sub.geom
     assert s.tolist() == [0, 0, 4] and torch.equal(v[:-1], torch.cat([vals[6:10], vals[0:6]])) and torch.equal(g, grid[4:7])     # (v ends in a padding row)
 
 

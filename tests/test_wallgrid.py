@@ -38,7 +38,7 @@ def wall_arc(wall, origin, dims, c, cell=CELL, slack=.01):
 
 
 def grid_of(walls, cell=CELL):
-    """Origin and dims as cuda.Scenery._build_wall_grid lays them out."""
+    """Origin and dims as grids.scan_level lays them out."""
     fin = walls[np.isfinite(walls).all((1, 2))]
     lo, hi = fin.reshape(-1, 2).min(0), fin.reshape(-1, 2).max(0)
     origin = np.floor(lo) - .5

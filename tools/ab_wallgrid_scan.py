@@ -15,10 +15,10 @@ bench.PLAN_WORKERS = 32
 
 def digest(sc):
     h = hashlib.sha256()
-    cells, starts, geom, cell, reach_lo, reach, near, pool, rows, pool_base = sc._wg
-    for t in (cells, starts, geom, pool_base):
+    wg = sc._wg
+    for t in (wg.cells, wg.starts, wg.geom, wg.pool_base):
         h.update(t.cpu().numpy().tobytes())
-    for t in (pool, rows):                                                # (large: a device-side fold first)
+    for t in (wg.pool, wg.near_rows):                                                # (large: a device-side fold first)
         v = t.reshape(-1).view(torch.int32).long()
         w = (torch.arange(v.numel(), device=v.device) % 1000003) + 1
         h.update(str(int((v*w).sum())).encode())

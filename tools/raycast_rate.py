@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
+from megastep_amd import grids   # noqa: E402
 
 
 def timed(fn, repeats, warmup):
@@ -41,7 +42,7 @@ def timed(fn, repeats, warmup):
 def random_rays(scenery, n_rays, seed):
     """(N, R, 2) origins over each env's walls' bounding box and directions of length 1 to 4, on the device."""
     g = torch.Generator(device=scenery.lines.vals.device).manual_seed(seed)
-    lo, hi = scenery._wall_bounds()
+    lo, hi = grids.wall_bounds(scenery)
     n = len(scenery.lines)
     dev = scenery.lines.vals.device
     u = torch.rand((n, n_rays, 2), generator=g, device=dev)
