@@ -1,6 +1,6 @@
 """Headline benchmark: env-steps/sec of the simulation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--agents 4] [--res 64] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--agents 4] [--res 64] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json `metric`): 4096 envs x 4 agents x 64-ray RGBD per GPU, seeded synthetic cubicasa-like
 floorplans, random momentum actions. One *step* = one pass of the hot path over the whole batch: `ms_physics` then
@@ -8,9 +8,10 @@ floorplans, random momentum actions. One *step* = one pass of the hot path over 
 from random actions) are resident in HBM and read in place.
 
 The K timed steps are enqueued as ONE HIP graph (2K kernel nodes, recorded once, replayed inside the timed regions):
-`value` is the replays' rate - what the kernels can do with the host out of the way. The same K steps launched one by
-one from Python (`eager`) are timed beside it, with HIP events around every step and every render for the per-step
-spread and the roofline.
+`value` is the replays' rate - what the kernels can do with the host out of the way. A plain run does only that: it
+builds the world, warms up, times the K steps, writes its outputs if asked and prints the line. With --full the same K
+steps launched one by one from Python (`eager`) are timed beside it, with HIP events around every step and every render
+for the per-step spread and the roofline, and the auxiliary legs listed at the end run after the headline.
 
 With --gpus N>1 there is one rank per GPU: `python bench.py --gpus N` on its own starts the N ranks itself
 (torch.distributed.run on this node, 127.0.0.1, a free port; it refuses if the node has fewer GPUs), and under a launcher
@@ -33,7 +34,9 @@ trajectory, whatever leg ran last): `progress` from ms_physics, the render plane
 as DIR/<name>.npy (float32; int32 planes as float64), at most 64 MB in all - a seeded sample of envs when more.
 The inputs depend on the arguments alone, so two builds can be compared output for output.
 
-Besides the contract fields the line carries
+With --full, besides the contract fields, the line carries (with N > 1 only `eager` and `roofline`; the CPU baselines, `shapes`
+and the env.step() rates can each still be left out by their --no-* option)
+  eager         the eager leg's rate and the spread of its per-step HIP-event times;
   roofline      render kernel (the dominant one): algorithmic bytes per launch / its mean launch time (HIP events
                 around every render launch of the eager timed region) against the 8 TB/s HBM peak;
   cpu_baseline  a pure-PyTorch CPU step (oracle/torch_step.py, the restatement of the reference's kernels as tensor
@@ -551,13 +554,14 @@ def launch_ranks(args, argv):
     raise SystemExit(subprocess.call(cmd, env=env, cwd=ROOT))
 
 
-def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields=None, graph=True, eager_floor=None, graph_floor=None,
-                  one_launch=False):
+def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields=None, graph=True, eager=True, eager_floor=None,
+                  graph_floor=None, one_launch=False):
     """The timing protocol (module docstring) on one world: a dry run of the env loop records the W + K steps' inputs;
-    the K timed steps are then launched one by one with HIP events around every step and every render (`eager`) and, with
-    `graph`, replayed as one HIP graph. A leg with a floor repeats its timed region until the regions add up to it; without
-    one it times exactly one region of K steps. Returns the raw numbers, and in `last` what the hot path handed its caller
-    in the last step (step W+K-1 of the trajectory: every region ends there)."""
+    the K timed steps are then launched one by one with HIP events around every step and every render (`eager`, always
+    without `graph`) and, with `graph`, replayed as one HIP graph. A leg with a floor repeats its timed region until the
+    regions add up to it; without one it times exactly one region of K steps. Returns the raw numbers (None for a leg that
+    did not run), and in `last` what the hot path handed its caller in the last step (step W+K-1 of the trajectory: every
+    region ends there)."""
     from megastep_amd import cuda, modules, sharding
     device = dev.device
     N, A = core.n_envs, core.n_agents
@@ -637,24 +641,24 @@ def time_hot_path(dev, core, steps, warmup, barrier=lambda: None, rank=0, fields
 
     # ---- eager: K steps launched one by one, events around every step and every render
     events = []
+    m = {'eager_runs': None, 'step_ms': None, 'render_each': None, 'graph_runs': None}
 
-    def eager():
+    def eager_steps():
         evs = [(dev.event(), dev.event(), dev.event()) for _ in range(steps)]
         for i in range(steps):
             evs[i][0].record()
             hot(views[warmup + i], evs[i])
         events.append(evs)
-    eager_runs = repeated(eager, floor_s=eager_floor)
-    m = {'eager_runs': eager_runs,
-         'step_ms': np.array([e[0].elapsed_time(e[2]) for evs in events for e in evs]),
-         'render_each': np.array([e[1].elapsed_time(e[2]) for evs in events for e in evs]),
-         'graph_runs': None}
+    if eager or not graph:
+        m['eager_runs'] = repeated(eager_steps, floor_s=eager_floor)
+        m['step_ms'] = np.array([e[0].elapsed_time(e[2]) for evs in events for e in evs])
+        m['render_each'] = np.array([e[1].elapsed_time(e[2]) for evs in events for e in evs])
     # ---- graph: the same K steps as one HIP graph, replayed
     if graph:
         replay = dev.graph(lambda: [hot(views[warmup + i]) for i in range(steps)])
         replay()                                                       # (instantiation / first-launch costs stay outside)
         m['graph_runs'] = repeated(replay, floor_s=graph_floor)
-    runs = m['graph_runs'] if m['graph_runs'] is not None else eager_runs
+    runs = m['graph_runs'] if m['graph_runs'] is not None else m['eager_runs']
     m['runs'] = runs
     m['own_ms_per_step'] = 1e3*float(np.median(own[-len(runs):]))/steps
     m['last'] = last_outputs(views[-1], getattr(hot, 'results', {}), fields)
@@ -895,6 +899,8 @@ def main(argv=None):
     ap.add_argument('--one-launch', action='store_true', help="the step through ms_step_render: one launch a step for single-agent worlds of up "
                                                             "to 64 rays (BASELINE config 2), the two launches for every other shape")
     ap.add_argument('--fast-build', action='store_true', help="draw textures, lights and spawns on the device (10^4+ envs)")
+    ap.add_argument('--full', action='store_true', help="besides the headline, the eager leg and the roofline and (N = 1) the CPU "
+                                                        "baselines, the whole-env.step() rates and the other BASELINE shapes")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-env-fps', action='store_true', help="skip the whole-env.step() rates")
     ap.add_argument('--no-shapes', action='store_true', help="skip the other BASELINE shapes (the `shapes` block)")
@@ -929,7 +935,7 @@ def main(argv=None):
     if os.environ.get('BENCH_WATCHDOG_S'):       # where is it, if it is still running by then?
         faulthandler.dump_traceback_later(float(os.environ['BENCH_WATCHDOG_S']), repeat=True)
     n_unique = plan_count(args.envs, args.agents, args.unique)
-    extras = rank == 0 and world == 1 and not args.dry_run_cpu
+    extras = args.full and rank == 0 and world == 1 and not args.dry_run_cpu
     # Floorplans first, on forked workers, before this process touches its GPU: the headline's pool (which the C3 / 512-ray
     # shapes share) and, if the `shapes` block is wanted, C2's one-plan-per-env pool and the large maps.
     if args.plan_cache and os.path.exists(args.plan_cache):
@@ -972,12 +978,14 @@ def main(argv=None):
     scenery = core.scenery
     log(f'world built: {N} envs on this rank')
     fields = ('distances',) if args.depth_only else None
-    m = time_hot_path(dev, core, args.steps, args.warmup, barrier, rank, fields=fields, graph=not args.no_graph, one_launch=args.one_launch)
+    m = time_hot_path(dev, core, args.steps, args.warmup, barrier, rank, fields=fields, graph=not args.no_graph, eager=args.full,
+                      one_launch=args.one_launch)
     eager_runs, graph_runs, runs = m['eager_runs'], m['graph_runs'], m['runs']
     step_ms, render_each = m['step_ms'], m['render_each']
-    eager_s = float(np.median(eager_runs))
-    render_ms = float(np.median(render_each))
-    log(f'eager leg: {1e3*eager_s/args.steps:.4f} ms/step ({len(eager_runs)} timed region of {args.steps} steps)')
+    eager_s = None
+    if eager_runs is not None:
+        eager_s = float(np.median(eager_runs))
+        log(f'eager leg: {1e3*eager_s/args.steps:.4f} ms/step ({len(eager_runs)} timed region of {args.steps} steps)')
     graph_s = None
     if graph_runs is not None:
         graph_s = float(np.median(graph_runs))
@@ -996,12 +1004,8 @@ def main(argv=None):
         dist.all_gather_object(gathered, per_rank[0])
         per_rank = gathered
         n_total = sum(n for n, _ in per_rank)
-    rb, pb = algorithmic_bytes(core, fields)
-    flops = all_pairs_flops(core)
-    achieved = rb/(render_ms*1e-3)/1e9
     ms_per_step = 1e3*elapsed/args.steps
     value = n_total*args.steps/elapsed
-    traffic, traffic_source = measured_traffic(args)
     outputs = 'depth-only (distances)' if args.depth_only else 'RGBD'
 
     out = {
@@ -1024,28 +1028,37 @@ def main(argv=None):
         # `value` is one timed region of exactly K steps between barrier + synchronize pairs (a floor would take the median):
         'timed_regions': {'count': int(len(runs)), 'ms_per_step_min': 1e3*float(runs.min())/args.steps,
                           'ms_per_step_median': ms_per_step, 'ms_per_step_max': 1e3*float(runs.max())/args.steps},
-        'eager': {'value': n_total*args.steps/eager_s, 'ms_per_step': 1e3*eager_s/args.steps, 'timed_regions': int(len(eager_runs)),
-                  'step_ms_hip_events': {'min': float(step_ms.min()), 'median': float(np.median(step_ms)), 'max': float(step_ms.max())}},
-        'roofline': {
-            # (<IMPL, RW, OBS, SHADE, NG>; NG - 64-ray groups per wave - as ms_render picks it: four from 256 rays up on launches
-            # of two and a half rounds of such waves)
-            'kernel': 'ms_render = render_kernel<2,1,%s,%d> (headings cached by ms_physics)' % (
-                '1,0' if args.depth_only else '0,1', ray_groups(dev, core)) + (' with STEP = 1: the env\'s physics step in the same wave'
-                                                                                 if args.one_launch else ''),
-            'bound': 'hbm', 'achieved': achieved,
-            'peak': HBM_PEAK_GBPS, 'unit': 'GB/s', 'frac': achieved/HBM_PEAK_GBPS,
-            'traffic': traffic, 'traffic_source': traffic_source,
-            'algorithmic_bytes_per_launch': rb, 'avg_launch_ms': render_ms,
-            'avg_launch_ms_source': 'median over HIP-event pairs on the stream around every ms_render of the eager leg (in place, '
-                                    'between the physics launches; the pair also times its own two event packets, about 1 us)',
-            'launch_ms_min_max': [float(render_each.min()), float(render_each.max())], 'launches_timed': int(len(render_each)),
-            'step_algorithmic_bytes': rb + pb, 'step_achieved_GBps': (rb + pb)/(ms_per_step*1e-3)/1e9,
-            # the raycast meets the fp32 VALU ceiling before the HBM one - the reference's all-pairs work
-            # over this kernel's time, against the vector peak (the kernel culls, so this is an equivalent rate)
-            'valu': {'all_pairs_flops_per_launch': flops, 'all_pairs_equivalent_TFLOPs': flops/(render_ms*1e-3)/1e12,
-                     'peak_fp32_vector_TFLOPs': FP32_VECTOR_PEAK_TFLOPS,
-                     'frac_of_peak': flops/(render_ms*1e-3)/1e12/FP32_VECTOR_PEAK_TFLOPS}},
     }
+    if args.full:
+        # the eager leg and the render launch's roofline from its HIP events (a leg of its own: --full only)
+        rb, pb = algorithmic_bytes(core, fields)
+        flops = all_pairs_flops(core)
+        render_ms = float(np.median(render_each))
+        achieved = rb/(render_ms*1e-3)/1e9
+        traffic, traffic_source = measured_traffic(args)
+        out.update({
+            'eager': {'value': n_total*args.steps/eager_s, 'ms_per_step': 1e3*eager_s/args.steps, 'timed_regions': int(len(eager_runs)),
+                      'step_ms_hip_events': {'min': float(step_ms.min()), 'median': float(np.median(step_ms)), 'max': float(step_ms.max())}},
+            'roofline': {
+                # (<IMPL, RW, OBS, SHADE, NG>; NG - 64-ray groups per wave - as ms_render picks it: four from 256 rays up on launches
+                # of two and a half rounds of such waves)
+                'kernel': 'ms_render = render_kernel<2,1,%s,%d> (headings cached by ms_physics)' % (
+                    '1,0' if args.depth_only else '0,1', ray_groups(dev, core)) + (' with STEP = 1: the env\'s physics step in the same wave'
+                                                                                     if args.one_launch else ''),
+                'bound': 'hbm', 'achieved': achieved,
+                'peak': HBM_PEAK_GBPS, 'unit': 'GB/s', 'frac': achieved/HBM_PEAK_GBPS,
+                'traffic': traffic, 'traffic_source': traffic_source,
+                'algorithmic_bytes_per_launch': rb, 'avg_launch_ms': render_ms,
+                'avg_launch_ms_source': 'median over HIP-event pairs on the stream around every ms_render of the eager leg (in place, '
+                                        'between the physics launches; the pair also times its own two event packets, about 1 us)',
+                'launch_ms_min_max': [float(render_each.min()), float(render_each.max())], 'launches_timed': int(len(render_each)),
+                'step_algorithmic_bytes': rb + pb, 'step_achieved_GBps': (rb + pb)/(ms_per_step*1e-3)/1e9,
+                # the raycast meets the fp32 VALU ceiling before the HBM one - the reference's all-pairs work
+                # over this kernel's time, against the vector peak (the kernel culls, so this is an equivalent rate)
+                'valu': {'all_pairs_flops_per_launch': flops, 'all_pairs_equivalent_TFLOPs': flops/(render_ms*1e-3)/1e12,
+                         'peak_fp32_vector_TFLOPs': FP32_VECTOR_PEAK_TFLOPS,
+                         'frac_of_peak': flops/(render_ms*1e-3)/1e12/FP32_VECTOR_PEAK_TFLOPS}},
+        })
     if distributed:
         # what the driver needs to read a 1 -> 8 curve: whose time `value` is, and what each rank's host side ran with
         aff = sorted(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else []

@@ -27,7 +27,7 @@ def _run(nproc, extra=(), self_launch=False, environ=()):
 
 
 def test_bench_line_two_ranks_gloo():
-    out = _run(2)
+    out = _run(2, ('--full',))
     assert out['n_gpus'] == 2 and out['steps'] == 6 and out['warmup'] == 2 and out['scaling'] == 'weak'
     assert out['metric'] == 'env-steps/sec' and out['higher_is_better'] is True and out['vs_baseline'] is None
     cfg = out['config']
@@ -129,10 +129,24 @@ def test_every_rank_builds_its_own_slice_and_the_slices_make_the_world(monkeypat
 
 def test_steps_sets_the_timed_steps():
     """--steps K times K steps: one region of exactly K steps in each leg, not regions repeated until a time floor."""
-    out = _run(1)
+    out = _run(1, ('--full',))
     assert out['steps'] == 6 and out['timed_regions']['count'] == 1 and out['eager']['timed_regions'] == 1
     t = out['timed_regions']
     assert t['ms_per_step_min'] == t['ms_per_step_median'] == t['ms_per_step_max'] == out['ms_per_step']
+
+
+def test_a_plain_run_times_the_headline_alone():
+    """Without --full the line is the headline and what describes it: the HIP-graph leg's K steps; the eager leg and the
+    roofline from its HIP events are --full's, and the same arguments with --full add them and leave the rest as it is."""
+    plain, full = _run(1), _run(1, ('--full',))
+    assert 'eager' not in plain and 'roofline' not in plain
+    assert plain['timed_regions']['count'] == 1 and 'HIP graph' in plain['config']['launch']
+    assert abs(plain['value'] - 24*6/(plain['ms_per_step']*6e-3)) < 1e-6*plain['value']
+    assert full['eager']['timed_regions'] == 1 and full['roofline']['launches_timed'] == 6
+    assert sorted(set(full) - set(plain)) == ['eager', 'roofline'] and plain['config'] == full['config']
+    # --no-graph: the eager leg IS the headline, timed without --full too
+    eager = _run(1, ('--no-graph',))
+    assert 'eager' in eager['config']['launch'] and eager['timed_regions']['count'] == 1 and 'roofline' not in eager
 
 
 def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):

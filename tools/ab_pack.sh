@@ -3,7 +3,7 @@
 # setting of MEGASTEP_PHYSICS_PACK and bench shape.   usage: tools/ab_pack.sh "1 0 4 8" "--envs 32768 --agents 1 ..." [...]
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 packs=$1; shift
-lean="--no-cpu-baseline --no-env-fps --no-shapes --plan-workers 0 --steps 40 --warmup 5"
+lean="--full --no-cpu-baseline --no-env-fps --no-shapes --plan-workers 0 --steps 40 --warmup 5"
 for shape in "$@"; do for k in $packs; do
   MEGASTEP_PHYSICS_PACK=$k timeout 300 rocprofv3 --kernel-trace --stats -d gpurun_out/abp -o r --output-format csv -- python bench.py $lean $shape > gpurun_out/abp.log 2> gpurun_out/abp.err
   python - "$k" "$shape" <<'PY'

@@ -10,7 +10,7 @@ out=gpurun_out/prof_$tag; mkdir -p $out
 # (floorplans first, in a plain process that may fork its workers: the profiled runs load them - 4096 large plans are 90 s on one core)
 python bench.py --plan-cache /tmp/plans_$tag.pkl --plans-only $shape > /dev/null 2> $out/plans.log
 lean="--no-cpu-baseline --no-env-fps --no-shapes --plan-workers 0 --plan-cache /tmp/plans_$tag.pkl"
-rocprofv3 --kernel-trace --stats -d $out/stats -o bench --output-format csv -- python bench.py --steps 100 --warmup 10 $lean $shape > $out/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/stats -o bench --output-format csv -- python bench.py --full --steps 100 --warmup 10 $lean $shape > $out/bench_stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/fetch -o bench --output-format csv -- python bench.py --steps 10 --warmup 3 --no-graph $lean $shape > $out/bench_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $out/write -o bench --output-format csv -- python bench.py --steps 10 --warmup 3 --no-graph $lean $shape > $out/bench_write.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT --kernel-trace -d $out/sq -o bench --output-format csv -- python bench.py --steps 10 --warmup 3 --no-graph $lean $shape > $out/bench_sq.log 2>&1
