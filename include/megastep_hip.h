@@ -358,6 +358,34 @@ int ms_raycast(const MsScenery* scenery, const MsAgents* agents /* NULL: static 
  * and the agents, these rays give ms_render's indices, locations, dots and distances bit for bit.  Reads angles only. */
 int ms_camera_rays(const MsAgents* agents, int n_envs, int n_agents, const MsConfig* config, float* dirs, void* hip_stream);
 
+/* Top-down pictures of the envs (the reference draws them with matplotlib, plotting.py; no kernel): image k shows env
+ * envs[k] through n_views views.  A view is six floats g, an affine map from pixel coordinates to world metres; every
+ * step below is one binary32 operation, in this order, without contraction.
+ *   pixel (row i from the top, column j):  u = j + 0.5, w = i + 0.5, x = (g0 u + g1 w) + g2, y = (g3 u + g4 w) + g5
+ *   line l of the env (env-local, rows (ax, ay, bx, by)):  vx = bx - ax, vy = by - ay, px = x - ax, py = y - ay,
+ *     vv = vx vx + vy vy, t = vv > 0 ? (px vx + py vy)/vv : 0 clamped to [0, 1] (a NaN stays NaN),
+ *     dx = px - t vx, dy = py - t vy, d2 = dx dx + dy dy; the line covers the pixel when d2 <= h h (h = half_width)
+ *   the winner: the covering line of least d2, the lower index on equal d2 (a NaN never covers); its colour is texel
+ *     q = min((int)(t (float)width_l), width_l - 1) of the line: texture[q] baked[q] for a static line when `lit`,
+ *     texture[q] otherwise, (0, 0, 0) for a line without texels; a pixel no line covers: `background` and index -1.
+ * With agents, the A M agent rows are drawn at the agents' current poses (the rows ms_render would leave in lines_vals, in
+ * registers: nothing is written to the scenery); without (NULL), they are read as lines_vals holds them.  An env id out of
+ * [0, n_envs) gives an image of `background` and -1; env ids are read on the device only. */
+typedef struct MsOverhead {
+    int          n_images;       /* K                                                                    */
+    int          n_views;        /* V: views per image                                                   */
+    int          height, width;  /* H, W: pixels                                                         */
+    const int*   envs;           /* (K,) env of every image; NULL: image k shows env k                   */
+    const float* views;          /* (K, V, 6) g0..g5 of every view                                       */
+    float        half_width;     /* h, metres (>= 0)                                                      */
+    int          lit;            /* static lines' texels times their baked light                         */
+    float        background[3];  /* linear RGB of a pixel no line covers                                 */
+    float*       rgb;            /* (K, V, 3, H, W) linear RGB, planar   (either output NULL = not wanted; not both) */
+    int*         indices;        /* (K, V, H, W) env-local line index, -1 where none                    */
+} MsOverhead;
+int ms_overhead(const MsScenery* scenery, const MsAgents* agents /* NULL: agent rows as stored */, const MsOverhead* overhead,
+                void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

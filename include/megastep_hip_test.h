@@ -47,6 +47,13 @@ int ms_debug_ray_group_tail(float rounds, int envs);
 /* Has ms_render's waves add their (line, ray) pair and pair-window counts to workspace[3] and [4] (two atomics per wave on
  * one address: milliseconds at 10^5 waves - tools/pair_stats.py only).  Per calling thread. */
 int ms_debug_pair_telemetry(int on);
+/* ms_overhead's tile cull: 0 makes every tile keep every line of its env (pass 1 keeps all), 1 (the default) culls.  Per
+ * calling thread; tests - either setting produces the same bits. */
+int ms_debug_overhead_cull(int on);
+/* Host instantiation of ms_overhead's tile cull, for CPU tests: may line = (ax, ay, bx, by) cover any pixel of tile
+ * (tile_row, tile_col) - 16 x 16 pixels, clipped to a height x width image - under view (g0..g5) at half width h?  1 = the
+ * kernel keeps the line for that tile, 0 = it drops it. */
+int ms_host_overhead_keeps(const float* view, int height, int width, int tile_row, int tile_col, float half_width, const float* line);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

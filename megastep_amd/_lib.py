@@ -86,10 +86,16 @@ class MsRaycast(C.Structure):
                 ('agents', C.c_void_p), ('grid_rays', C.c_void_p)]
 
 
+class MsOverhead(C.Structure):
+    _fields_ = [('n_images', C.c_int), ('n_views', C.c_int), ('height', C.c_int), ('width', C.c_int), ('envs', C.c_void_p),
+                ('views', C.c_void_p), ('half_width', C.c_float), ('lit', C.c_int), ('background', C.c_float*3),
+                ('rgb', C.c_void_p), ('indices', C.c_void_p)]
+
+
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare
 SYMBOLS = ('ms_host_ray_interval_wide', 'ms_debug_ray_groups', 'ms_debug_last_render_groups', 'ms_debug_last_step_fused', 'ms_step_render', 'ms_move_step_render', 'ms_debug_ray_group_tail', 'ms_debug_physics_pack', 'ms_host_render_plan', 'ms_host_render_block', 'ms_host_physics_pack', 'ms_debug_pair_telemetry', 'ms_test_arithmetic', 'ms_abi_version', 'ms_strerror', 'ms_last_hip_error', 'ms_device_count', 'ms_bake', 'ms_physics', 'ms_move_physics',
            'ms_step_physics', 'ms_deathmatch_shoot', 'ms_explorer_books',
-           'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_host_sincospi', 'ms_host_bake_point_bin', 'ms_host_bake_wall_bins',
+           'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_debug_overhead_cull', 'ms_host_overhead_keeps', 'ms_host_sincospi', 'ms_host_bake_point_bin', 'ms_host_bake_wall_bins',
            'ms_wallgrid_scan', 'ms_wallgrid_fill', 'ms_host_wall_hidden', 'ms_host_wall_sectors', 'ms_host_wallgrid_cell', 'ms_host_wall_arc',
            'ms_host_wedge_meets', 'ms_host_agents_apart', 'ms_host_wall_beyond_reach', 'ms_host_ray_interval', 'ms_host_fold_hits', 'ms_host_lightgrid_cell', 'ms_host_wall_reach')
 
@@ -184,6 +190,11 @@ def lib():
         handle.ms_render.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsRender), C.POINTER(MsConfig), C.c_void_p]
         handle.ms_raycast.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsRaycast), C.POINTER(MsConfig), C.c_void_p]
         handle.ms_camera_rays.argtypes = [C.POINTER(MsAgents), C.c_int, C.c_int, C.POINTER(MsConfig), C.c_void_p, C.c_void_p]
+        handle.ms_overhead.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsOverhead), C.c_void_p]
+        handle.ms_debug_overhead_cull.argtypes = [C.c_int]
+        handle.ms_debug_overhead_cull.restype = C.c_int
+        handle.ms_host_overhead_keeps.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p]
+        handle.ms_host_overhead_keeps.restype = C.c_int
         handle.ms_host_sincospi.argtypes = [C.c_float, _f32p, _f32p]
         handle.ms_host_bake_point_bin.argtypes = [C.c_float]*4
         handle.ms_host_bake_point_bin.restype = C.c_int
@@ -237,7 +248,7 @@ def lib():
         handle.ms_host_wallgrid_cell.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int,
                                                  C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         handle.ms_host_wallgrid_cell.restype = None
-        for name in ('ms_bake', 'ms_physics', 'ms_move_physics', 'ms_step_physics', 'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_wallgrid_scan', 'ms_wallgrid_fill'):
+        for name in ('ms_bake', 'ms_physics', 'ms_move_physics', 'ms_step_physics', 'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_wallgrid_scan', 'ms_wallgrid_fill'):
             getattr(handle, name).restype = C.c_int
         if handle.ms_abi_version() != ABI_VERSION:
             raise ImportError(f'{LIB_PATH} has ABI {handle.ms_abi_version()}, this package needs {ABI_VERSION}; rebuild it')

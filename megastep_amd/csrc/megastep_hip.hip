@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h.
 //
-// Fifteen kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Sixteen kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -42,6 +42,9 @@
 //                   per-ray fold over the agents drawn in registers and the vis list of the origin's cell (or every
 //                   wall); and the render's own camera rays as data.   (reference: kernels.cu:234-236,349-382; no
 //                   counterpart as an entry point)
+//   overhead_kernel     top-down pictures: one workgroup per 16 x 16 tile of an image, the env's lines culled against the
+//                   tile's footprint into LDS, then each lane's pixel folded over them.   (reference: plotting.py draws
+//                   these with matplotlib, one env at a time on the host)
 //   explorer_kernel     the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
 //   deathmatch_kernel   the Deathmatch env's game logic between frames (revive, crosshairs, hits and wounds, health, damage,
@@ -81,6 +84,7 @@ thread_local float g_tail_rounds = -1.f;    // ms_debug_ray_group_tail: < 0 = ms
 thread_local int g_tail_envs = -1;          //   ... >= 0: that many envs exactly
 thread_local int g_last_step_fused = 0;     // ms_debug_last_step_fused: did this thread's last ms_step_render go out as one launch?
 thread_local int g_last_render_groups = 0;  // ms_debug_last_render_groups: the NG this thread's last ms_render launched
+thread_local int g_overhead_cull = 1;       // ms_debug_overhead_cull: 0 = ms_overhead's tiles keep every line
 
 // -DMS_PROBE=1 (`make probe`, tools/probe_waves.py): every wave of physics_kernel and render_kernel leaves a record of
 // time stamps (s_memtime at its start, at a few points where something it waited for has arrived, at its end) and of
@@ -129,6 +133,7 @@ struct Probe {
 #include "kernels/bake.h"
 #include "kernels/wallgrid.h"
 #include "kernels/raycast.h"
+#include "kernels/overhead.h"
 #include "kernels/envlogic.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -690,6 +695,43 @@ int ms_camera_rays(const MsAgents* ag, int n_envs, int n_agents, const MsConfig*
                        n_envs*n_agents, cfg->res, half_screen, camera_inv_res(cfg->res, half_screen), reinterpret_cast<float2*>(dirs));
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MS_OK : hip_fail(e);
+}
+
+// Top-down pictures (overhead.h): arguments checked in full before anything is launched; the env ids are the kernel's to check.
+int ms_overhead(const MsScenery* sc, const MsAgents* ag, const MsOverhead* ov, void* stream) {
+    if (!scenery_ok(sc) || !ov || ov->n_images < 1 || ov->n_views < 1 || ov->height < 1 || ov->width < 1 || !ov->views ||
+        (!ov->rgb && !ov->indices) || !(ov->half_width >= 0.f) || !(ov->half_width < INFINITY)) return MS_EINVAL;
+    if (ov->rgb && (!sc->textures_vals || !sc->textures_widths || !sc->textures_starts || (ov->lit && !sc->baked_vals))) return MS_EINVAL;
+    if (ag && (!ag->angles || !ag->positions || ((uintptr_t)ag->positions % 8))) return MS_EINVAL;
+    if (ov->height > (1 << 15) || ov->width > (1 << 15)) return MS_EUNSUPPORTED;
+    OvArgs a;
+    a.envs = ov->envs; a.views = ov->views; a.rgb = ov->rgb; a.indices = ov->indices;
+    a.n_views = ov->n_views; a.height = ov->height; a.width = ov->width;
+    a.tiles_x = (ov->width + OV_TILE - 1)/OV_TILE; a.tiles_y = (ov->height + OV_TILE - 1)/OV_TILE;
+    a.half_width = ov->half_width; a.h2 = ov->half_width*ov->half_width;
+    a.bg_r = ov->background[0]; a.bg_g = ov->background[1]; a.bg_b = ov->background[2];
+    a.lit = ov->lit ? 1 : 0; a.with_agents = ag ? 1 : 0; a.cull = g_overhead_cull ? 1 : 0;
+    const MsAgents no_agents{nullptr, nullptr, nullptr, nullptr, nullptr};
+    // (a launch of at most 2^22 blocks - 2^30 lanes - at a time: the (image, view, tile) number is 64-bit, the grid's is not)
+    const long long total = (long long)ov->n_images*ov->n_views*a.tiles_x*a.tiles_y;
+    const long long per_launch = 1LL << 22;
+    for (long long b0 = 0; b0 < total; b0 += per_launch) {
+        a.block0 = b0;
+        const unsigned blocks = (unsigned)(total - b0 < per_launch ? total - b0 : per_launch);
+        hipLaunchKernelGGL(overhead_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *sc, ag ? *ag : no_agents, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e);
+    }
+    return MS_OK;
+}
+
+int ms_debug_overhead_cull(int on) { g_overhead_cull = on; return MS_OK; }
+
+int ms_host_overhead_keeps(const float* g, int height, int width, int tile_row, int tile_col, float half_width, const float* line) {
+    const int i0 = tile_row*OV_TILE, j0 = tile_col*OV_TILE;
+    const OvBox box = ov_footprint(g[0], g[1], g[2], g[3], g[4], g[5], i0, j0, i0 + OV_TILE - 1 < height - 1 ? i0 + OV_TILE - 1 : height - 1,
+                                   j0 + OV_TILE - 1 < width - 1 ? j0 + OV_TILE - 1 : width - 1);
+    return ov_keeps(box, half_width, make_float4(line[0], line[1], line[2], line[3])) ? 1 : 0;
 }
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {

@@ -237,6 +237,35 @@ class RGB:
         return self._last_obs[e].clone()
 
 
+class Overhead:
+
+    def __init__(self, core, size=32, radius=4., n_agents=None, half_width=None):
+        """Egocentric top-down maps, (n_env, n_agent, 3, size, size) linear RGB: each agent at the centre of its own
+        ``2*radius`` metre square, its heading up, the walls in their baked light and the agents at their current poses
+        (:func:`cuda.agent_views`, :func:`cuda.overhead`; no counterpart in the reference). Lines are drawn
+        ``half_width`` metres either side (default: ``scene.line_half_width`` of the pixel size). The tensor a call returns is
+        written again by the next call (the module keeps its buffers): clone it to keep it."""
+        from . import scene
+        self.core = core
+        self.size, self.radius = int(size), float(radius)
+        self.half_width = scene.line_half_width(2*self.radius/self.size) if half_width is None else float(half_width)
+        self.space = spaces.MultiImage(n_agents or core.n_agents, 3, self.size, self.size)
+        self._out = None
+
+    def views(self):
+        """(n_env, n_agent, 6): the views of the agents' maps as they stand now."""
+        return cuda.agent_views(self.core.agents, self.size, self.radius)
+
+    def __call__(self):
+        self._out = cuda.overhead(self.core.scenery, self.views(), self.size, agents=self.core.agents,
+                                  half_width=self.half_width, fields=('rgb',), out=self._out)
+        self._last_obs = self._out.rgb
+        return self._last_obs
+
+    def state(self, e=0):
+        return self._last_obs[e].clone()
+
+
 class IMU:
 
     def __init__(self, core, speed_scale=10., ang_scale=360., n_agents=None):

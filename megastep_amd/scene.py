@@ -239,3 +239,36 @@ def scenery(geometries, n_agents=1, device='cuda', random=np.random, bake=True, 
     if bake:
         cuda.bake(result)
     return result
+
+
+# ---- pictures -------------------------------------------------------------------------------------------------------
+
+def line_half_width(metres_per_pixel):
+    """The half width :func:`display` and ``modules.Overhead`` draw lines at: 5 cm, or half a pixel's diagonal where pixels
+    are larger - a line then covers the centre of every pixel it passes through, and never breaks into dots."""
+    return max(.05, float(metres_per_pixel)/2**.5)
+
+
+def display(scenery, e=0, size=512, agents=None):
+    """Env ``e`` from above as a ``(size, size, 3)`` uint8 image (the reference's ``scene.display``, scene.py:102-114,
+    without matplotlib): the floorplan framed as ``plotting.extent(zoom=False)`` frames it, on the reference's background,
+    drawn by :func:`cuda.overhead` with the baked light, gamma-encoded; the lights as yellow dots whose opacity is their
+    normalised intensity (``plotting.plot_lights``). The agents are where the last render drew them, or with ``agents`` at
+    their current poses."""
+    views = cuda.plan_views(scenery, size, envs=[e])
+    g = views[0, 0].cpu().numpy().astype(np.float64)
+    envs = torch.tensor([e], dtype=torch.int32, device=views.device)
+    r = cuda.overhead(scenery, views, size, agents=agents, envs=envs, half_width=line_half_width(g[0]), fields=('rgb',))
+    image = core.gamma_encode(np.clip(r.rgb[0, 0].permute(1, 2, 0).cpu().numpy().astype(np.float64), 0, 1))
+    lights = scenery.lights[e].cpu().numpy().astype(np.float64)
+    if len(lights):
+        centres = np.arange(size) + .5
+        x = g[0]*centres[None, :] + g[1]*centres[:, None] + g[2]
+        y = g[3]*centres[None, :] + g[4]*centres[:, None] + g[5]
+        vmin, vmax = lights[:, 2].min() - 1e-2, lights[:, 2].max()
+        radius = max(.05, abs(g[0]))
+        for lx, ly, intensity in lights:
+            alpha = (intensity - vmin)/(vmax - vmin)
+            dot = (x - lx)**2 + (y - ly)**2 <= radius**2
+            image[dot] = (1 - alpha)*image[dot] + alpha*np.array([1., 1., 0.])
+    return np.round(255*image).astype(np.uint8)
