@@ -33,6 +33,8 @@ extern "C" {
 #define MS_EHIP         -2   /* a HIP runtime call failed; see ms_last_hip_error()  */
 #define MS_EUNSUPPORTED -3   /* shape outside what the kernels support              */
 #define MS_ENODEVICE    -4   /* no usable gfx950 device                             */
+/* An entry point that returns MS_EINVAL or MS_EUNSUPPORTED has enqueued nothing: every argument is checked, and every
+ * choice of launch made, before the first launch. */
 
 /* Replaces `initialize(agent_radius, res, fov, fps)` (wrappers.cpp:53, kernels.cu:18-27). */
 typedef struct MsConfig {
@@ -274,7 +276,9 @@ int ms_render(const MsScenery* scenery, const MsAgents* agents, const MsRender* 
  * shape) the agent is a single wavefront, which runs its env's physics step (kernels.cu:179-230) and renders from the pose it
  * ends on (kernels.cu:297-475); nothing crosses waves, so there is nothing to order between two launches.  Every other shape
  * (several agents per env, more than 64 rays, a wall grid that serves one half of the step only) is ms_physics followed by
- * ms_render, as if the caller had made the two calls.  Same results as the two calls, bit for bit, either way. */
+ * ms_render, as if the caller had made the two calls.  Which of the two it is, is decided before anything is launched: a call
+ * that ms_render would refuse is refused before the physics step moves any agent.  Same results as the two calls, bit for
+ * bit, either way. */
 int ms_step_render(const MsScenery* scenery, const MsAgents* agents, float* progress, const MsRender* out,
                    const MsConfig* config, void* hip_stream);
 /* ... with the movement prologue and the env's bookkeeping of ms_step_physics around the step (either may be NULL): a whole

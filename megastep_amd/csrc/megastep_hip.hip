@@ -194,6 +194,7 @@ int physics_pack_of(const int n_envs, const int n_agents, const bool gridded, co
 // host side of the C-ABI
 // ------------------------------------------------------------------------------------------------
 int hip_fail(hipError_t e) { g_last_hip_error = (int)e; return MS_EHIP; }
+int launch_status() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? MS_OK : hip_fail(e); }   // (after the launches)
 
 // The wave slots render_kernel has on the CURRENT device (CUs x 4 SIMDs x the waves per SIMD its registers are held to): what
 // sizes a launch's choice of ray groups and its tail.  Looked up once per device (a process may drive several, of different
@@ -218,6 +219,36 @@ bool scenery_ok(const MsScenery* s) {
 bool agents_ok(const MsAgents* a) { return a && a->angles && a->positions && a->angvelocity && a->velocity; }
 bool config_ok(const MsConfig* c) {
     return c && c->res > 0 && c->fps > 0.f && c->agent_radius > 0.f && c->fov > 0.f && c->fov < 180.f;
+}
+MsAgents agents_or_none(const MsAgents* a) { return a ? *a : MsAgents{nullptr, nullptr, nullptr, nullptr, nullptr}; }
+
+// kernels.cu:22: the camera's half-width at unit distance, as every launch that casts its rays works it out
+float half_screen_of(const float fov) { return tanf(3.14159265358979323846f/180.f*fov/2.); }
+
+// The light grid is all or nothing: render_kernel lights agent-hit rays itself when it is there.
+bool light_grid_in(const MsScenery* sc) { return sc->lg_vals && sc->lg_starts && sc->lg_geom && sc->lg_cell > 0.f; }
+// The wall grid's vis lists serve rays of this near plane: they were built for near planes below wg_near (wallgrid_scan_kernel).
+bool vis_lists_serve(const MsScenery* sc, const float near_plane) {
+    return sc->wg_cells && sc->wg_starts && sc->wg_geom && sc->wg_pool && sc->wg_pool_base && sc->wg_cell > 0.f &&
+           near_plane*1.001f < sc->wg_near;
+}
+
+// (the optional structs of ms_step_physics / ms_move_step_render, checked alike)
+bool step_options_ok(const MsMovement* mv, const MsStepExtras* ex) {
+    if (mv && (!mv->actions || !mv->table || mv->n_actions < 1 || !(mv->keep == mv->keep))) return false;
+    if (ex) {
+        if (ex->spawn_positions && (!ex->spawn_angles || !ex->respawn_mask || !ex->respawn_choice || ex->n_spawns < 1 ||
+                                    ((uintptr_t)ex->spawn_positions % 8))) return false;
+        if (ex->lifespans && (!ex->max_lifespans || !ex->fresh_max)) return false;
+        if (ex->imu && !(ex->imu_ang_scale == ex->imu_ang_scale && ex->imu_speed_scale == ex->imu_speed_scale)) return false;
+    }
+    return true;
+}
+// ... and as the kernels take them: all-NULL structs for none, the IMU scales inverted (the kernels multiply: see their IMU reading)
+void step_options_of(const MsMovement* mv, const MsStepExtras* ex, MsMovement& mvv, MsStepExtras& exv) {
+    mvv = mv ? *mv : MsMovement{nullptr, nullptr, 0, 0.f};
+    exv = ex ? *ex : MsStepExtras{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 1.f, 1.f};
+    exv.imu_ang_scale = 1.f/exv.imu_ang_scale; exv.imu_speed_scale = 1.f/exv.imu_speed_scale;
 }
 
 }  // namespace
@@ -290,14 +321,13 @@ int ms_test_arithmetic(const float* n, const float* d, float* q_inrange, float* 
     const long long blocks = (count + WG - 1)/WG;
     if (blocks > 0x7fffffffLL) return MS_EUNSUPPORTED;
     hipLaunchKernelGGL(arithmetic_test_kernel, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, n, d, q_inrange, q_ieee, x, r_any, r_ieee, count);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 void ms_host_ray_interval_wide(const float* pose, const float* line, int res, float fov, float agent_radius, int groups, int wave,
                                int* first, int* count) {
     // (the launch-invariant values as ms_render works them out, the per-wave ones as render_kernel does)
-    const float half_screen = tanf(3.14159265358979323846f/180.f*fov/2.);
+    const float half_screen = half_screen_of(fov);
     const float x_clip = 0.5f*agent_radius/sqrtf(1.f + half_screen*half_screen), c_b = 0.5f*(float)res/half_screen;
     const int nr = WAVE*groups, r0 = wave*nr;
     const float c_a = 0.5f*((float)res - 1.f), g0 = (float)r0;
@@ -427,8 +457,7 @@ int ms_wallgrid_scan(const MsScenery* sc, const MsWallGridParent* parent, const 
     if (n_reps > 65535) return MS_EUNSUPPORTED;
     hipLaunchKernelGGL(wallgrid_scan_kernel, dim3((unsigned)max_groups, (unsigned)n_reps), dim3(WG), 0, (hipStream_t)stream,
                        *sc, par, reps, bits_starts, bits, counts);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 int ms_wallgrid_fill(const MsScenery* sc, const int* reps, int n_reps, int max_cells,
@@ -442,20 +471,7 @@ int ms_wallgrid_fill(const MsScenery* sc, const int* reps, int n_reps, int max_c
     if (blocks > 0x7fffffffLL || n_reps > 65535) return MS_EUNSUPPORTED;
     hipLaunchKernelGGL(wallgrid_fill_kernel, dim3((unsigned)blocks, (unsigned)n_reps), dim3(WG), 0, (hipStream_t)stream,
                        *sc, reps, bits_starts, bits, pool, reinterpret_cast<float4*>(near_rows), vis_entries);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
-}
-
-// (the optional structs of ms_step_physics / ms_move_step_render, checked alike)
-static bool step_options_ok(const MsMovement* mv, const MsStepExtras* ex) {
-    if (mv && (!mv->actions || !mv->table || mv->n_actions < 1 || !(mv->keep == mv->keep))) return false;
-    if (ex) {
-        if (ex->spawn_positions && (!ex->spawn_angles || !ex->respawn_mask || !ex->respawn_choice || ex->n_spawns < 1 ||
-                                    ((uintptr_t)ex->spawn_positions % 8))) return false;
-        if (ex->lifespans && (!ex->max_lifespans || !ex->fresh_max)) return false;
-        if (ex->imu && !(ex->imu_ang_scale == ex->imu_ang_scale && ex->imu_speed_scale == ex->imu_speed_scale)) return false;
-    }
-    return true;
+    return launch_status();
 }
 
 int ms_step_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* mv, const MsStepExtras* ex, float* progress,
@@ -468,11 +484,8 @@ int ms_step_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* m
     // per wave: 2 float4 + a float + an unsigned per agent, rounded up to whole float4s
     const size_t slice = ((sizeof(float)*8 + sizeof(float) + sizeof(unsigned))*(size_t)sc->n_agents*pack + 15)/16;
     if (slice*16 > 56*1024) return MS_EUNSUPPORTED;
-    const MsMovement no_move{nullptr, nullptr, 0, 0.f};
-    const MsStepExtras no_extras{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 1.f, 1.f};
-    const MsMovement mvv = mv ? *mv : no_move;
-    MsStepExtras exv = ex ? *ex : no_extras;
-    exv.imu_ang_scale = 1.f/exv.imu_ang_scale; exv.imu_speed_scale = 1.f/exv.imu_speed_scale;   // (the kernel multiplies: see its IMU reading)
+    MsMovement mvv; MsStepExtras exv;
+    step_options_of(mv, ex, mvv, exv);
     MsScenery scn = *sc;
     if (!sc->wg_cells) { scn.wg_geom = sc->lines_vals; scn.wg_starts = sc->lines_starts; }   // (rows the kernel may read: see there)
     const hipStream_t hs = (hipStream_t)stream;
@@ -487,8 +500,7 @@ int ms_step_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* m
     else MS_LAUNCH_PHYSICS(0, 0)
 #undef MS_LAUNCH_PHYSICS_P
 #undef MS_LAUNCH_PHYSICS
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 int ms_move_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* mv, float* progress, const MsConfig* cfg,
@@ -500,10 +512,24 @@ int ms_physics(const MsScenery* sc, const MsAgents* ag, float* progress, const M
     return ms_step_physics(sc, ag, nullptr, nullptr, progress, cfg, stream);
 }
 
-// ms_render, and - with `progress` - ms_step_render's fused launch (returns MS_EUNSUPPORTED, having launched nothing, where that
-// one does not apply: the caller then makes the two calls)
-static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender* out, const MsConfig* cfg, void* stream, float* progress,
-                         const MsMovement* mv = nullptr, const MsStepExtras* ex = nullptr) {
+// The render call, decided in full before anything is launched: render_prepare makes every check and choice, render_enqueue
+// launches what they came to.  A call refused has enqueued nothing; and given `progress` (ms_move_step_render's step),
+// render_prepare tells whether the step is one launch (L.fused) - if not, L is the plain render that follows ms_step_physics.
+struct RenderLaunch {
+    RenderPlan plan;                                  // render_kernel's NG and blocks
+    RenderConstsStep rc;                              // (the STEP = 1 part is set only where the step is fused)
+    MsScenery scn; MsAgents agn; MsRender outn;       // the copies render_kernel gets
+    const MsAgents* ag; const MsRender* out;          // the caller's, as render_prep_kernel and dynlight_kernel get them
+    float agent_radius, half_screen; int R;
+    bool colour, obs, no_planes;                      // which instantiation of render_kernel
+    bool light_grid, walls_listed;
+    bool prep;        // headings from render_prep_kernel (else from the cache, from render_kernel itself, or from the fused wave)
+    bool dynlight;    // dynlight_kernel afterwards: it lights the rays that landed on an agent
+    bool fused;       // the physics step in the render's waves (render_kernel<..., STEP = 1>)
+};
+
+static int render_prepare(const MsScenery* sc, const MsAgents* ag, const MsRender* out, const MsConfig* cfg, float* progress,
+                          const MsMovement* mv, const MsStepExtras* ex, RenderLaunch& L) {
     if (!scenery_ok(sc) || !agents_ok(ag) || !config_ok(cfg) || !out || !sc->textures_vals || !sc->textures_widths ||
         !sc->textures_starts || !sc->baked_vals || !sc->lights_widths || !sc->lights_starts) return MS_EINVAL;
     if ((out->seen_stamp != nullptr) != (out->seen_epoch != nullptr) || (out->seen_stamp != nullptr) != (out->seen_count != nullptr)) return MS_EINVAL;
@@ -515,117 +541,93 @@ static int render_launch(const MsScenery* sc, const MsAgents* ag, const MsRender
     }
     if (sc->n_lights_total > 0 && !sc->lights_vals) return MS_EINVAL;
     const int R = cfg->res;
-    const int slots = wave_slots_here();                                 // the current device's wave slots for this kernel
-    bool wide_ok = true;
-    // (without a light grid the rays that land on an agent are lit by dynlight_kernel, which takes them by groups of 64)
-    if (!(sc->lg_vals && sc->lg_starts && sc->lg_geom && sc->lg_cell > 0.f) && sc->n_agents > 1 && (out->screen || out->obs_rgb)) wide_ok = false;
-    RenderConsts rc;
-    const RenderPlan plan = render_plan(sc->n_envs, sc->n_agents, R, slots, wide_ok ? g_ray_groups : 1, g_tail_rounds, g_tail_envs, rc);
-    const int ng = plan.ng;
-    g_last_render_groups = ng;
-    const long long n_fans = plan.n_blocks;
+    L.R = R; L.agent_radius = cfg->agent_radius; L.ag = ag; L.out = out;
+    L.light_grid = light_grid_in(sc);
+    L.colour = out->screen || out->obs_rgb;                              // else: render_kernel<1,0>, which has no pass 3
+    // Without a light grid the rays that land on an agent are lit by dynlight_kernel, which takes them by groups of 64.  With
+    // one agent per env no ray can land on an agent line (own lines sit inside the near plane), so there is nothing to light.
+    L.dynlight = !L.light_grid && sc->n_agents > 1 && L.colour;
+    L.plan = render_plan(sc->n_envs, sc->n_agents, R, wave_slots_here(), L.dynlight ? 1 : g_ray_groups, g_tail_rounds, g_tail_envs, L.rc);
     // the workspace's layout (MS_RENDER_WORKSPACE_INTS): 16 counters, a queue of one entry per (env, agent, 64 rays), the headings
     const long long ws_queue = (long long)sc->n_envs*sc->n_agents*((R + WAVE - 1)/WAVE);
-    if (n_fans > 0x7fffffffLL || ws_queue > 0x7fffff00LL) return MS_EUNSUPPORTED;
-    rc.ws_headings = 16 + (int)((ws_queue + 1) & ~1LL);
-    // kernels.cu:22
-    const float half_screen = tanf(3.14159265358979323846f/180.f*cfg->fov/2.);
-    // the light grid is all or nothing: render_kernel lights agent-hit rays itself when it is there
-    MsScenery scn = *sc;
-    const bool grid = sc->lg_vals && sc->lg_starts && sc->lg_geom && sc->lg_cell > 0.f;
-    if (!grid) scn.lg_vals = nullptr;
+    if (L.plan.n_blocks > 0x7fffffffLL || ws_queue > 0x7fffff00LL) return MS_EUNSUPPORTED;
+    L.rc.ws_headings = 16 + (int)((ws_queue + 1) & ~1LL);
+    const float half_screen = L.half_screen = half_screen_of(cfg->fov);
+    // the light grid is all or nothing (light_grid_in) ...
+    L.scn = *sc;
+    if (!L.light_grid) L.scn.lg_vals = nullptr;
     // ... and so is the wall grid: its vis lists were built for near planes below wg_near and ray direction vectors no
     // longer than sqrt(WG_MAX_RU2) (wallgrid_scan_kernel); a call outside that meets every wall instead
-    const bool walls_listed = sc->wg_cells && sc->wg_starts && sc->wg_geom && sc->wg_pool && sc->wg_pool_base && sc->wg_cell > 0.f &&
-                              cfg->agent_radius*1.001f < sc->wg_near && 1.f + half_screen*half_screen <= WG_MAX_RU2;
-    if (walls_listed && (((uintptr_t)sc->wg_cells % 16) || ((uintptr_t)sc->wg_geom % 16))) return MS_EINVAL;
-    if (!walls_listed) {                                                 // (the kernel reads a row of each whatever happens: see there)
-        scn.wg_cells = nullptr;
-        scn.wg_geom = sc->lines_vals;                                    // at least 16 bytes per env: every env has its agents' lines
-        scn.wg_starts = sc->lines_starts;
-        scn.wg_pool_base = reinterpret_cast<const long long*>(sc->lines_vals);   // (16 bytes of lines per env at least: 8 are there)
+    L.walls_listed = vis_lists_serve(sc, cfg->agent_radius) && 1.f + half_screen*half_screen <= WG_MAX_RU2;
+    if (L.walls_listed && (((uintptr_t)sc->wg_cells % 16) || ((uintptr_t)sc->wg_geom % 16))) return MS_EINVAL;
+    if (!L.walls_listed) {                                               // (the kernel reads a row of each whatever happens: see there)
+        L.scn.wg_cells = nullptr;
+        L.scn.wg_geom = sc->lines_vals;                                  // at least 16 bytes per env: every env has its agents' lines
+        L.scn.wg_starts = sc->lines_starts;
+        L.scn.wg_pool_base = reinterpret_cast<const long long*>(sc->lines_vals);   // (16 bytes of lines per env at least: 8 are there)
     }
-    // Headings: from ms_physics' cache when the agents carry one and a single kernel does the whole job (then the
-    // workspace is not needed at all); otherwise from render_prep_kernel, which also resets the workspace's counters.
-    MsAgents agn = *ag;
-    MsRender outn = *out;
-    if (out->obs_depth) outn.obs_max_depth = 1.f/out->obs_max_depth;     // (the kernel multiplies: see the pooled depth in render.h)
-    const bool colour = out->screen || out->obs_rgb;                      // else: render_kernel<1,0>, which has no pass 3
-    const bool one_kernel = grid || sc->n_agents == 1 || !colour;        // (nothing to light without colour)
-    if (ag->headings && one_kernel) {
-        if ((uintptr_t)ag->headings % 16) return MS_EINVAL;
-        outn.workspace = nullptr;
-    } else if (!progress) {
-        agn.headings = nullptr;
-        if (out->workspace) {
-            if ((uintptr_t)out->workspace % 8) return MS_EINVAL;
-            const int na = sc->n_envs*sc->n_agents;
-            hipLaunchKernelGGL(render_prep_kernel, dim3((na + WG - 1)/WG), dim3(WG), 0, (hipStream_t)stream,
-                               *ag, out->workspace, na, rc.ws_headings);
-        }
-    }
-    // dynlight_kernel reads the per-ray outputs back: only the one-kernel path can do without some of them
+    // dynlight_kernel reads the per-ray outputs back and patches `screen`: only the one-kernel path can do without some of them
     const bool all_planes = out->indices && out->locations && out->dots && out->distances && out->screen;
     const bool pooled = out->obs_rgb || out->obs_depth || out->obs_centre || out->seen_stamp;
-    if (colour && (!all_planes || pooled) && !(grid || sc->n_agents == 1)) return MS_EUNSUPPORTED;   // dynlight_kernel patches `screen` afterwards
-    if (!all_planes && !pooled && !out->indices && !out->locations && !out->dots && !out->distances && !out->screen) return MS_EINVAL;
-    const bool obs = pooled || !all_planes;
-    if (progress) {
-        // The fused step (render_kernel<..., STEP = 1>): one agent per env and at most 64 rays - the agent is ONE wave, which
-        // runs the env's physics first and renders from the pose it ends on; and a wall grid that either
-        // serves both halves of the step or neither (ms_render goes without it when the call's near plane or field of view is
-        // outside what its vis lists were built for, ms_step_physics never does).
-        const bool physics_listed = sc->wg_cells != nullptr;
-        if (sc->n_agents != 1 || R > WAVE || ng != 1 || physics_listed != walls_listed ||
-            (physics_listed && (!sc->wg_near_rows || ((uintptr_t)sc->wg_near_rows % 16)))) return MS_EUNSUPPORTED;
-        agn = *ag;                                                       // (the wave works the heading out itself and leaves it in the cache, if there is one)
-        outn.workspace = nullptr;
-    }
-    rc.x_clip = 0.5f*cfg->agent_radius/sqrtf(1.f + half_screen*half_screen);
-    rc.c_b = 0.5f*(float)R/half_screen;
-    rc.by_m = divisor_of((unsigned)sc->n_model);
-    rc.skip_own = (sc->model_radius > 0.f && sc->model_radius*1.01f < cfg->agent_radius) ? 1 : 0;
-    rc.inv_res = camera_inv_res(R, half_screen);
-    rc.telemetry = g_pair_telemetry;
+    if (L.dynlight && (!all_planes || pooled)) return MS_EUNSUPPORTED;
+    if (!pooled && !out->indices && !out->locations && !out->dots && !out->distances && !out->screen) return MS_EINVAL;
+    L.obs = pooled || !all_planes;
+    // (colour, and not one per-ray plane wanted - the demo envs' request: the instantiation that has no plane stores in it)
+    L.no_planes = L.colour && !out->indices && !out->locations && !out->dots && !out->distances && !out->screen;
+    // The fused step: one agent per env and at most 64 rays - the agent is ONE wave, which runs the env's physics first and
+    // renders from the pose it ends on; and a wall grid that serves both halves of the step or neither (ms_render goes without
+    // it when the call's near plane or field of view is outside what its vis lists were built for, ms_step_physics never does).
+    const bool physics_listed = sc->wg_cells != nullptr;
+    L.fused = progress && sc->n_agents == 1 && R <= WAVE && L.plan.ng == 1 && physics_listed == L.walls_listed &&
+              (!physics_listed || (sc->wg_near_rows && (uintptr_t)sc->wg_near_rows % 16 == 0));
+    // Headings: from ms_physics' cache when the agents carry one and a single kernel does the whole job (then the workspace is
+    // not needed at all); the fused wave works them out itself (and leaves them in the cache, if there is one); otherwise
+    // render_prep_kernel, which also resets the workspace's counters - or, without a workspace, render_kernel - works them out.
+    const bool cached = ag->headings && !L.dynlight;
+    L.prep = !cached && !L.fused && out->workspace;
+    if ((cached && (uintptr_t)ag->headings % 16) || (L.prep && (uintptr_t)out->workspace % 8)) return MS_EINVAL;
+    L.agn = *ag;
+    L.outn = *out;
+    if (!cached && !L.fused) L.agn.headings = nullptr;
+    if (!L.prep) L.outn.workspace = nullptr;
+    if (out->obs_depth) L.outn.obs_max_depth = 1.f/out->obs_max_depth;  // (the kernel multiplies: see the pooled depth in render.h)
+    L.rc.x_clip = 0.5f*cfg->agent_radius/sqrtf(1.f + half_screen*half_screen);
+    L.rc.c_b = 0.5f*(float)R/half_screen;
+    L.rc.by_m = divisor_of((unsigned)sc->n_model);
+    L.rc.skip_own = (sc->model_radius > 0.f && sc->model_radius*1.01f < cfg->agent_radius) ? 1 : 0;
+    L.rc.inv_res = camera_inv_res(R, half_screen);
+    L.rc.telemetry = g_pair_telemetry;
     // (the instantiations with optional outputs - every colourless one, and the colour one of pooled observations at one ray
     // group a wave - read which are wanted from here: see OUT_* in render.h)
-    if (!colour || (obs && ng == 1))
-        outn.obs_subsample = (out->obs_subsample & 0xff) | (((out->indices ? OUT_INDICES : 0) | (out->locations ? OUT_LOCATIONS : 0) |
-                              (out->dots ? OUT_DOTS : 0) | (out->distances ? OUT_DISTANCES : 0) | (out->obs_depth ? OUT_DEPTH : 0) |
-                              (out->obs_centre ? OUT_CENTRE : 0) | (out->seen_stamp ? OUT_SEEN : 0) | (out->screen ? OUT_SCREEN : 0) |
-                              (out->obs_rgb ? OUT_RGB : 0)) << 8);
-    const dim3 rgrid((int)n_fans), rblock(WAVE);
-    const hipStream_t hs = (hipStream_t)stream;
-    // (colour, and not one per-ray plane wanted - the demo envs' request: the instantiation that has no plane stores in it)
-    [[maybe_unused]] const bool no_planes = colour && !out->indices && !out->locations && !out->dots && !out->distances && !out->screen;
-#define MS_LAUNCH_RENDER_NG(O, S, NG_) \
-    hipLaunchKernelGGL((render_kernel<O, S, NG_>), rgrid, rblock, 0, hs, scn, agn, outn, cfg->agent_radius, half_screen, R, (int)n_fans, rc)
-#define MS_LAUNCH_RENDER_OS(NG_) \
-    { if (!colour) MS_LAUNCH_RENDER_NG(1, 0, NG_); else if (no_planes) MS_LAUNCH_RENDER_NG(2, 1, NG_); else if (obs) MS_LAUNCH_RENDER_NG(1, 1, NG_); \
-      else MS_LAUNCH_RENDER_NG(0, 1, NG_); }
-    if (progress) {
-        RenderConstsStep rcs;
-        static_cast<RenderConsts&>(rcs) = rc;
-        rcs.progress = progress; rcs.fps = cfg->fps; rcs.wg_cells_physics = sc->wg_cells;
-        rcs.mv = mv ? *mv : MsMovement{nullptr, nullptr, 0, 0.f};
-        rcs.ex = ex ? *ex : MsStepExtras{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 1.f, 1.f};
-        rcs.ex.imu_ang_scale = 1.f/rcs.ex.imu_ang_scale; rcs.ex.imu_speed_scale = 1.f/rcs.ex.imu_speed_scale;
-#define MS_LAUNCH_STEP(O, S) \
-    hipLaunchKernelGGL((render_kernel<O, S, 1, 1>), rgrid, rblock, 0, hs, scn, agn, outn, cfg->agent_radius, half_screen, R, (int)n_fans, rcs)
-        if (!colour) MS_LAUNCH_STEP(1, 0); else if (obs) MS_LAUNCH_STEP(1, 1); else MS_LAUNCH_STEP(0, 1);
-#undef MS_LAUNCH_STEP
+    if (!L.colour || (L.obs && L.plan.ng == 1))
+        L.outn.obs_subsample = (out->obs_subsample & 0xff) | (((out->indices ? OUT_INDICES : 0) | (out->locations ? OUT_LOCATIONS : 0) |
+                                (out->dots ? OUT_DOTS : 0) | (out->distances ? OUT_DISTANCES : 0) | (out->obs_depth ? OUT_DEPTH : 0) |
+                                (out->obs_centre ? OUT_CENTRE : 0) | (out->seen_stamp ? OUT_SEEN : 0) | (out->screen ? OUT_SCREEN : 0) |
+                                (out->obs_rgb ? OUT_RGB : 0)) << 8);
+    if (L.fused) {
+        L.rc.progress = progress; L.rc.fps = cfg->fps; L.rc.wg_cells_physics = sc->wg_cells;
+        step_options_of(mv, ex, L.rc.mv, L.rc.ex);
     }
-    else if (ng == 4) MS_LAUNCH_RENDER_OS(4)
-    else if (ng == 2) MS_LAUNCH_RENDER_OS(2)
+    return MS_OK;
+}
+
+static int render_enqueue(const RenderLaunch& L, const hipStream_t hs) {
+    g_last_render_groups = L.plan.ng;
+    const int na = L.scn.n_envs*L.scn.n_agents;
+    if (L.prep) hipLaunchKernelGGL(render_prep_kernel, dim3((na + WG - 1)/WG), dim3(WG), 0, hs, *L.ag, L.out->workspace, na, L.rc.ws_headings);
+    // (the STEP = 0 instantiations take the RenderConsts part of L.rc)
+#define MS_LAUNCH_RENDER(O, S, NG_, STEP_) hipLaunchKernelGGL((render_kernel<O, S, NG_, STEP_>), dim3((int)L.plan.n_blocks), dim3(WAVE), 0, hs, \
+                                                              L.scn, L.agn, L.outn, L.agent_radius, L.half_screen, L.R, (int)L.plan.n_blocks, L.rc)
+#define MS_LAUNCH_RENDER_OS(NG_) { if (!L.colour) MS_LAUNCH_RENDER(1, 0, NG_, 0); else if (L.no_planes) MS_LAUNCH_RENDER(2, 1, NG_, 0); \
+                                   else if (L.obs) MS_LAUNCH_RENDER(1, 1, NG_, 0); else MS_LAUNCH_RENDER(0, 1, NG_, 0); }
+    if (L.fused) { if (!L.colour) MS_LAUNCH_RENDER(1, 0, 1, 1); else if (L.obs) MS_LAUNCH_RENDER(1, 1, 1, 1); else MS_LAUNCH_RENDER(0, 1, 1, 1); }
+    else if (L.plan.ng == 4) MS_LAUNCH_RENDER_OS(4)
+    else if (L.plan.ng == 2) MS_LAUNCH_RENDER_OS(2)
     else MS_LAUNCH_RENDER_OS(1)
 #undef MS_LAUNCH_RENDER_OS
-#undef MS_LAUNCH_RENDER_NG
-    // without a grid: second launch.  With one agent per env no ray can land on an agent line (own lines sit
-    // inside the near plane), so there is nothing to light.
-    if (!grid && sc->n_agents > 1 && colour)
-        hipLaunchKernelGGL(dynlight_kernel, dim3((int)n_fans), dim3(WG), 0, (hipStream_t)stream, scn, *ag, *out, R);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+#undef MS_LAUNCH_RENDER
+    if (L.dynlight) hipLaunchKernelGGL(dynlight_kernel, dim3((int)L.plan.n_blocks), dim3(WG), 0, hs, L.scn, *L.ag, *L.out, L.R);
+    return launch_status();
 }
 
 int ms_deathmatch_shoot(int n_envs, int n_agents, const MsDeathmatch* dm, void* stream) {
@@ -635,30 +637,33 @@ int ms_deathmatch_shoot(int n_envs, int n_agents, const MsDeathmatch* dm, void* 
     const long long rows = (long long)n_envs*n_agents, blocks = (rows + WG - 1)/WG;
     if (blocks > 0x7fffffffLL) return MS_EUNSUPPORTED;
     hipLaunchKernelGGL(deathmatch_kernel, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, *dm, n_envs, n_agents);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 int ms_explorer_books(int n_envs, const MsExplorer* ex, void* stream) {
     if (n_envs <= 0 || !ex || !ex->tally || !ex->before || !ex->lengths || !ex->epoch || !ex->over || !ex->reward || ex->pixels <= 0 ||
         ((uintptr_t)ex->tally % 4) || ((uintptr_t)ex->before % 4) || ((uintptr_t)ex->lengths % 4) || ((uintptr_t)ex->epoch % 4)) return MS_EINVAL;
     hipLaunchKernelGGL(explorer_kernel, dim3((unsigned)((n_envs + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, *ex, n_envs);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 int ms_render(const MsScenery* sc, const MsAgents* ag, const MsRender* out, const MsConfig* cfg, void* stream) {
-    return render_launch(sc, ag, out, cfg, stream, nullptr);
+    RenderLaunch L;
+    const int planned = render_prepare(sc, ag, out, cfg, nullptr, nullptr, nullptr, L);
+    return planned != MS_OK ? planned : render_enqueue(L, (hipStream_t)stream);
 }
 
 int ms_move_step_render(const MsScenery* sc, const MsAgents* ag, const MsMovement* mv, const MsStepExtras* ex, float* progress,
                         const MsRender* out, const MsConfig* cfg, void* stream) {
     if (!progress || !step_options_ok(mv, ex)) return MS_EINVAL;
-    const int fused = render_launch(sc, ag, out, cfg, stream, progress, mv, ex);
-    g_last_step_fused = fused == MS_OK ? 1 : 0;
-    if (fused != MS_EUNSUPPORTED) return fused;
-    const int p = ms_step_physics(sc, ag, mv, ex, progress, cfg, stream);
-    return p != MS_OK ? p : render_launch(sc, ag, out, cfg, stream, nullptr);
+    RenderLaunch L;
+    const int planned = render_prepare(sc, ag, out, cfg, progress, mv, ex, L);
+    g_last_step_fused = 0;
+    if (planned != MS_OK) return planned;
+    const int p = L.fused ? MS_OK : ms_step_physics(sc, ag, mv, ex, progress, cfg, stream);
+    const int r = p != MS_OK ? p : render_enqueue(L, (hipStream_t)stream);
+    g_last_step_fused = L.fused && r == MS_OK;
+    return r;
 }
 int ms_step_render(const MsScenery* sc, const MsAgents* ag, float* progress, const MsRender* out, const MsConfig* cfg, void* stream) {
     return ms_move_step_render(sc, ag, nullptr, nullptr, progress, out, cfg, stream);
@@ -673,28 +678,22 @@ int ms_raycast(const MsScenery* sc, const MsAgents* ag, const MsRaycast* rq, con
     if (ag && (!ag->angles || !ag->positions || ((uintptr_t)ag->positions % 8))) return MS_EINVAL;
     const long long total = (long long)sc->n_envs*rq->n_rays;
     if (total > 0x7fffff00LL) return MS_EUNSUPPORTED;
-    // the wall grid serves this call's rays when its vis lists were built for a near plane beyond this one (as ms_render asks)
-    const bool gridded = sc->wg_cells && sc->wg_starts && sc->wg_geom && sc->wg_pool && sc->wg_pool_base && sc->wg_cell > 0.f &&
-                         rq->near_plane*1.001f < sc->wg_near;
+    const bool gridded = vis_lists_serve(sc, rq->near_plane);
     if (gridded && (((uintptr_t)sc->wg_cells % 16) || ((uintptr_t)sc->wg_geom % 16))) return MS_EINVAL;
-    const MsAgents no_agents{nullptr, nullptr, nullptr, nullptr, nullptr};
     const unsigned blocks = (unsigned)((total + WG - 1)/WG);
-    hipLaunchKernelGGL(raycast_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *sc, ag ? *ag : no_agents, *rq, ag ? 1 : 0,
+    hipLaunchKernelGGL(raycast_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *sc, agents_or_none(ag), *rq, ag ? 1 : 0,
                        gridded ? 1 : 0, (int)total);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 int ms_camera_rays(const MsAgents* ag, int n_envs, int n_agents, const MsConfig* cfg, float* dirs, void* stream) {
     if (!ag || !ag->angles || n_envs < 1 || n_agents < 1 || !config_ok(cfg) || !dirs || ((uintptr_t)dirs % 8)) return MS_EINVAL;
     const long long total = (long long)n_envs*n_agents*cfg->res;
     if ((long long)n_envs*n_agents > 0x7fffffffLL || total > 0x7fffff00LL*(long long)WG) return MS_EUNSUPPORTED;
-    // kernels.cu:22, as ms_render works it out
-    const float half_screen = tanf(3.14159265358979323846f/180.f*cfg->fov/2.);
+    const float half_screen = half_screen_of(cfg->fov);
     hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, ag->angles,
                        n_envs*n_agents, cfg->res, half_screen, camera_inv_res(cfg->res, half_screen), reinterpret_cast<float2*>(dirs));
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 // Top-down pictures (overhead.h): arguments checked in full before anything is launched; the env ids are the kernel's to check.
@@ -711,16 +710,14 @@ int ms_overhead(const MsScenery* sc, const MsAgents* ag, const MsOverhead* ov, v
     a.half_width = ov->half_width; a.h2 = ov->half_width*ov->half_width;
     a.bg_r = ov->background[0]; a.bg_g = ov->background[1]; a.bg_b = ov->background[2];
     a.lit = ov->lit ? 1 : 0; a.with_agents = ag ? 1 : 0; a.cull = g_overhead_cull ? 1 : 0;
-    const MsAgents no_agents{nullptr, nullptr, nullptr, nullptr, nullptr};
     // (a launch of at most 2^22 blocks - 2^30 lanes - at a time: the (image, view, tile) number is 64-bit, the grid's is not)
     const long long total = (long long)ov->n_images*ov->n_views*a.tiles_x*a.tiles_y;
     const long long per_launch = 1LL << 22;
     for (long long b0 = 0; b0 < total; b0 += per_launch) {
         a.block0 = b0;
         const unsigned blocks = (unsigned)(total - b0 < per_launch ? total - b0 : per_launch);
-        hipLaunchKernelGGL(overhead_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *sc, ag ? *ag : no_agents, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e);
+        hipLaunchKernelGGL(overhead_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *sc, agents_or_none(ag), a);
+        if (const int status = launch_status(); status != MS_OK) return status;
     }
     return MS_OK;
 }
@@ -739,9 +736,14 @@ int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {
     if (!scenery_ok(sc) || !sc->textures_widths || !sc->textures_starts || !sc->textures_inverse ||
         !sc->baked_vals || !sc->lights_widths || !sc->lights_starts) return MS_EINVAL;
     if (sc->n_lights_total > 0 && !sc->lights_vals) return MS_EINVAL;
+    if (sc->n_texels_total > 0 && sc->bake_vis &&
+        (!sc->bake_vis_starts || sc->bake_vis_words < 0 || !sc->lines_inverse || ((uintptr_t)sc->bake_vis % 8))) return MS_EINVAL;
+    if (sc->lg_vals && (!sc->lg_starts || !sc->lg_geom || !(sc->lg_cell > 0.f) || sc->lg_max_cells <= 0 || ((uintptr_t)sc->lg_vals % 16) ||
+                        ((uintptr_t)sc->lg_geom % 16) || (sc->lg_list != nullptr) != (sc->lg_pool != nullptr) ||
+                        (sc->lg_pool && sc->lg_pool_size < 1) || (sc->lg_pool_rows && (!sc->lg_pool || ((uintptr_t)sc->lg_pool_rows % 16))) ||
+                        ((uintptr_t)sc->lg_list % 8))) return MS_EINVAL;
     if (sc->n_texels_total > 0 && sc->bake_vis) {
         // two phases: visibility once per representative env and light, then the per-env sums
-        if (!sc->bake_vis_starts || sc->bake_vis_words < 0 || !sc->lines_inverse || ((uintptr_t)sc->bake_vis % 8)) return MS_EINVAL;
         const char* be = getenv("MEGASTEP_BAKE_BINS");                 // =0: every texel meets every wall (A/B runs)
         const bool bins = !(be && be[0] == '0');
         if (sc->n_lights_total > 0)
@@ -752,11 +754,6 @@ int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {
         hipLaunchKernelGGL(bake_kernel, dim3(sc->n_envs), dim3(WG), 0, (hipStream_t)stream, *sc);
     }
     if (sc->lg_vals) {
-        if (!sc->lg_starts || !sc->lg_geom || !(sc->lg_cell > 0.f) || sc->lg_max_cells <= 0 || ((uintptr_t)sc->lg_vals % 16) ||
-            ((uintptr_t)sc->lg_geom % 16)) return MS_EINVAL;
-        if ((sc->lg_list != nullptr) != (sc->lg_pool != nullptr) || (sc->lg_pool && sc->lg_pool_size < 1) ||
-            (sc->lg_pool_rows && (!sc->lg_pool || ((uintptr_t)sc->lg_pool_rows % 16))) ||
-            ((uintptr_t)sc->lg_list % 8)) return MS_EINVAL;
         const dim3 cells((sc->lg_max_cells + WG - 1)/WG, sc->n_envs);
         hipLaunchKernelGGL(lightgrid_kernel, cells, dim3(WG), 0, (hipStream_t)stream, *sc);
         if (sc->lg_list) {
@@ -764,8 +761,7 @@ int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {
             hipLaunchKernelGGL(lightlist_kernel, cells, dim3(WG), 0, (hipStream_t)stream, *sc);
         }
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MS_OK : hip_fail(e);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -413,6 +413,14 @@ def _agents_on(agents, dev):
         raise RuntimeError(f'all tensors must live on one device; got {agents._dev} and {dev}')
 
 
+def _ms_agents(agents, step, telemetry=False):
+    """The MsAgents a launch gets: with the heading cache where the launch fills it (a physics step, while the agents use the
+    cache) or reads it (a render after a physics call filled it - not with ``telemetry``, whose counters the self-contained path
+    keeps), else without."""
+    cached = agents._use_cache if step else agents._cached and not telemetry
+    return agents._struct if cached else agents._plain
+
+
 def bake(scenery, scratch=True, wall_grid=True):
     """Pre-computes the static lighting of every texel into ``scenery.baked`` (reference: wrappers.cpp:61,
     kernels.cu:270-293). ``scratch=False`` selects the library's self-contained one-pass kernel (no temporary
@@ -525,7 +533,7 @@ def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=No
     _ab_switches()
     _check_grid(scenery, dev)
     with _on(dev):
-        _lib.check(_lib.lib().ms_step_physics(C.byref(scenery._as_struct()), C.byref(agents._struct if agents._use_cache else agents._plain),
+        _lib.check(_lib.lib().ms_step_physics(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)),
                                               mv, ex, C.c_void_p(progress.data_ptr()), C.byref(_cfg(agents, config)), _stream(dev)))
     agents._cached = agents._use_cache
     agents._epoch += 1
@@ -614,18 +622,18 @@ def step_render(scenery, agents, fields=None, pooled=None, out=None, seen=None, 
     single-agent env of up to 64 rays - the reference's tutorial env - is then one launch); ``out``: the ``(Physics, Render)`` of an
     earlier call, to write into. Returns ``(Physics, Render)``."""
     physics_out, render_out = out if out is not None else (None, None)
+    dev, cfg, result = _render_call(scenery, agents, fields, pooled, render_out, seen, config)
+    mv, ex = _step_options(agents, tuple(agents.angles.shape), movement, respawn, lifespans, imu)
     progress = torch.empty_like(agents.angles) if physics_out is None else physics_out.progress
-    shape = (len(scenery.lines), scenery.n_agents)
-    if agents.angles.shape != shape:
-        raise RuntimeError('agents do not match the scenery')
-    options = _step_options(agents, shape, movement, respawn, lifespans, imu)
-    r = render(scenery, agents, fields=fields, pooled=pooled, out=render_out, seen=seen, config=config, _progress=(progress, *options))
+    with _on(dev):
+        _lib.check(_lib.lib().ms_move_step_render(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)), mv, ex,
+                                                  C.c_void_p(progress.data_ptr()), C.byref(result._struct), C.byref(cfg), _stream(dev)))
     agents._cached = agents._use_cache
     agents._epoch += 1
-    return (Physics(progress) if physics_out is None else physics_out), r
+    return (Physics(progress) if physics_out is None else physics_out), result
 
 
-def render(scenery, agents, fields=None, pooled=None, telemetry=False, out=None, seen=None, config=None, _progress=None):
+def render(scenery, agents, fields=None, pooled=None, telemetry=False, out=None, seen=None, config=None):
     """Casts ``res`` rays per agent and shades them; also rewrites the agents' model lines in ``scenery.lines``
     (reference: wrappers.cpp:82, kernels.cu:452-475). Returns :class:`Render`.
 
@@ -646,6 +654,22 @@ def render(scenery, agents, fields=None, pooled=None, telemetry=False, out=None,
     The contract the wall grid adds: hit indices come from the per-cell lists :func:`bake` made of the
     static walls, so walls must not be moved in place afterwards without baking again - ``Scenery.check_wall_grid()`` /
     ``MEGASTEP_CHECK_GRID=1`` detect it (the reference reads ``lines`` afresh every call and has no such rule)."""
+    dev, cfg, result = _render_call(scenery, agents, fields, pooled, out, seen, config)
+    with _on(dev):
+        if telemetry:
+            _lib.lib().ms_debug_pair_telemetry(1)               # the kernels' pair counters too (tools/pair_stats.py)
+        try:
+            _lib.check(_lib.lib().ms_render(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=False, telemetry=telemetry)),
+                                            C.byref(result._struct), C.byref(cfg), _stream(dev)))
+        finally:
+            if telemetry:
+                _lib.lib().ms_debug_pair_telemetry(0)
+    return result
+
+
+def _render_call(scenery, agents, fields, pooled, out, seen, config):
+    """What :func:`render` and :func:`step_render` check and prepare alike: the device, the shapes, the config, the first-sight
+    books and the :class:`Render` to write into (``out``, or fresh buffers). Returns ``(device, config, Render)``."""
     dev = scenery._device()
     _agents_on(agents, dev)
     n, a = agents.angles.shape
@@ -679,22 +703,7 @@ def render(scenery, agents, fields=None, pooled=None, telemetry=False, out=None,
             result._struct.seen_stamp, result._struct.seen_epoch, result._struct.seen_count = seen_ptrs
     _ab_switches()
     _check_grid(scenery, dev)
-    with _on(dev):
-        use_cache = agents._cached and not telemetry
-        if telemetry:
-            _lib.lib().ms_debug_pair_telemetry(1)               # the kernels' pair counters too (tools/pair_stats.py)
-        try:
-            if _progress is not None:                            # step_render: the physics step first, in the same launch where it can be
-                progress, mv, ex = _progress
-                _lib.check(_lib.lib().ms_move_step_render(C.byref(scenery._as_struct()), C.byref(agents._struct if agents._use_cache else agents._plain),
-                                                          mv, ex, C.c_void_p(progress.data_ptr()), C.byref(result._struct), C.byref(cfg), _stream(dev)))
-            else:
-                _lib.check(_lib.lib().ms_render(C.byref(scenery._as_struct()), C.byref(agents._struct if use_cache else agents._plain),
-                                                C.byref(result._struct), C.byref(cfg), _stream(dev)))
-        finally:
-            if telemetry:
-                _lib.lib().ms_debug_pair_telemetry(0)
-    return result
+    return dev, cfg, result
 
 
 _layouts = {}

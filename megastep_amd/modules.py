@@ -105,11 +105,13 @@ class MomentumMovement:
         self._actionset = _actionset(core, accel, ang_accel)
         self._table = _table(self._actionset)
         self.decay = decay
-        self.keep = 1 - decay
         self.space = spaces.MultiDiscrete(n_agents or core.n_agents, 7)
 
+    #: the share of the old velocity a step keeps (see cuda.physics' ``movement``)
+    keep = property(lambda self: 1 - self.decay)
+
     def __call__(self, decision, respawn=None, imu=None):
-        return _move(self.core, self._actionset, decision.actions, 1 - self.decay, respawn, imu, self._table)
+        return _move(self.core, self._actionset, decision.actions, self.keep, respawn, imu, self._table)
 
 
 def unpack(d):

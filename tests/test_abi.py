@@ -67,6 +67,18 @@ def test_bad_arguments_are_rejected_before_any_launch():
     assert h.ms_physics(C.byref(sc), C.byref(ag), None, C.byref(cfg), None) == -1
     with pytest.raises(RuntimeError, match='invalid argument'):
         _lib.check(h.ms_render(C.byref(sc), C.byref(ag), C.byref(out), C.byref(cfg), None))
+    # (NULL pointers and zeroed structs only: nothing here may get as far as a launch)
+    assert h.ms_step_render(None, None, None, None, C.byref(cfg), None) == -1
+    assert h.ms_step_render(C.byref(sc), C.byref(ag), None, C.byref(out), C.byref(cfg), None) == -1
+    assert h.ms_move_step_render(None, None, None, None, None, None, C.byref(cfg), None) == -1
+    assert h.ms_move_step_render(C.byref(sc), C.byref(ag), C.byref(_lib.MsMovement()), C.byref(_lib.MsStepExtras()), None,
+                                 C.byref(out), C.byref(cfg), None) == -1
+    assert h.ms_raycast(None, None, None, None, None) == -1
+    assert h.ms_raycast(C.byref(sc), C.byref(ag), C.byref(_lib.MsRaycast()), None, None) == -1
+    assert h.ms_camera_rays(None, 1, 1, C.byref(cfg), None, None) == -1
+    assert h.ms_camera_rays(C.byref(ag), 1, 1, C.byref(cfg), None, None) == -1
+    assert h.ms_overhead(None, None, None, None) == -1
+    assert h.ms_overhead(C.byref(sc), C.byref(ag), C.byref(_lib.MsOverhead()), None) == -1
 
 
 def test_kernel_sincospi_is_bitwise_the_oracles(oracle):

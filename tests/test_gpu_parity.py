@@ -98,6 +98,22 @@ def test_errors_are_loud():
         cuda.physics(scenery, agents)
 
 
+def test_a_bake_it_refuses_has_launched_nothing():
+    """ms_bake checks the light grid's fields (here: a misaligned lg_vals) before its bake kernels write baked_vals."""
+    import ctypes as C
+    from megastep_amd import _lib, cuda
+    c, _ = _world(3, 2, 64, 130, seed=2)
+    struct = _lib.MsScenery.from_buffer_copy(c.scenery._as_struct())
+    assert struct.lg_vals is not None
+    struct.lg_vals += 4
+    baked = c.scenery.baked.vals
+    baked.fill_(-7.)
+    code = _lib.lib().ms_bake(C.byref(struct), None, cuda._stream(c.device))
+    torch.cuda.synchronize()
+    assert code == -1
+    assert bool((baked == -7.).all()), 'the refused bake wrote baked_vals'
+
+
 def _custom_world(walls_per_env, n_agents, res, fov, positions, angles, lights=None):
     """A Core over hand-made wall sets (one (W, 2, 2) array per env), agents placed explicitly."""
     from megastep_amd import core, scene, arrdict

@@ -265,3 +265,53 @@ def test_the_tutorial_env_steps_in_one_launch():
     for t, (x, y) in enumerate(zip(*rollouts)):
         assert _same(x, y), t
     assert (rollouts[0][-1] - 3.).abs().max() > .1
+
+
+def _c_call(c):
+    """The scenery, config and stream arguments of a direct C-ABI call on `c`."""
+    import ctypes as C
+    from megastep_amd import cuda
+    return C.byref(c.scenery._as_struct()), C.byref(cuda._cfg(c.agents)), cuda._stream(c.device)
+
+
+def test_a_render_it_refuses_has_launched_nothing():
+    """ms_render refuses a request for no output at all (MS_EINVAL) before render_prep_kernel has written the workspace."""
+    import ctypes as C
+    from megastep_amd import _lib
+    c, _ = _world(4, 2, 64, 130., seed=9)
+    n, a, r = c.n_envs, c.n_agents, 64
+    workspace = torch.full((18 + n*a*((r + 63)//64) + 2*n*a,), 0x5a5a5a5a, dtype=torch.int32, device=c.device)   # MS_RENDER_WORKSPACE_INTS
+    sc, cfg, stream = _c_call(c)
+    out = _lib.MsRender(workspace=workspace.data_ptr())
+    code = _lib.lib().ms_render(sc, C.byref(c.agents._plain), C.byref(out), cfg, stream)
+    torch.cuda.synchronize()
+    assert code == -1
+    assert bool((workspace == 0x5a5a5a5a).all()), 'the refused render wrote the workspace'
+
+
+def test_a_step_whose_render_is_refused_moves_nobody(monkeypatch):
+    """Colour with pooled observations on a multi-agent scenery without a light grid is a render ms_render refuses
+    (MS_EUNSUPPORTED: dynlight_kernel would need every plane); ms_move_step_render refuses the step before its physics half
+    has moved an agent or written `progress`."""
+    import ctypes as C
+    from megastep_amd import _lib, cuda
+    monkeypatch.setattr(cuda.Scenery, 'LIGHT_GRID', False)
+    c, _ = _world(4, 2, 64, 130., seed=10)
+    assert c.scenery._as_struct().lg_vals is None
+    util.random_velocities(c, np.random.RandomState(11))
+    agents = c.agents
+    assert bool((agents.velocity != 0).any())
+    n, a, r, sub = c.n_envs, c.n_agents, 64, 4
+    screen = torch.zeros((n, a, r, 3), device=c.device)
+    obs_rgb = torch.zeros((n, a, 3, r//sub), device=c.device)
+    progress = torch.full((n, a), -7., device=c.device)
+    before = [t.clone() for t in (agents.angles, agents.positions, agents.angvelocity, agents.velocity)]
+    sc, cfg, stream = _c_call(c)
+    out = _lib.MsRender(screen=screen.data_ptr(), obs_rgb=obs_rgb.data_ptr(), obs_subsample=sub, obs_max_depth=10.)
+    code = _lib.lib().ms_move_step_render(sc, C.byref(agents._plain), None, None, C.c_void_p(progress.data_ptr()), C.byref(out), cfg, stream)
+    torch.cuda.synchronize()
+    assert code == -3
+    for k, (x, y) in enumerate(zip(before, (agents.angles, agents.positions, agents.angvelocity, agents.velocity))):
+        assert torch.equal(x, y), f'agent tensor {k} changed'
+    assert bool((progress == -7.).all()), 'the refused step wrote progress'
+    assert not _fused()
