@@ -79,6 +79,14 @@ __host__ __device__ inline void wg_wedge(const float p_right, const float p_left
 __host__ __device__ inline bool wg_arcs_meet(const int lo8, const int hi8, const int wa8, const int wb8) {
     return (((wa8 - lo8) & 255) <= ((hi8 - lo8) & 255)) | (((lo8 - wa8) & 255) <= ((wb8 - wa8) & 255));
 }
+// The cell of an env's wall grid (geom = (x0, y0, nx, ny), cells `cell` wide - grown by a centimetre: the hardware's reciprocal will
+// do) that (x, y) lies in, from the env's first, and whether it is inside at all (NaNs, no grid: outside - and then 0, which exists).
+__device__ inline int wg_cell_at(const float4 geom, const float cell, const float x, const float y, bool& inside) {
+    const float inv_cell = __builtin_amdgcn_rcpf(cell);
+    const float fx = floorf((x - geom.x)*inv_cell), fy = floorf((y - geom.y)*inv_cell);
+    inside = (fx >= 0.f) & (fx < geom.z) & (fy >= 0.f) & (fy < geom.w);
+    return inside ? (int)fy*(int)geom.z + (int)fx : 0;
+}
 
 // sin(pi x), cos(pi x); stands in for sinpif/cospif (kernels.cu:305-306,336-337).  The range
 // reduction is exact in binary32, the kernel is a Taylor series in binary64 rounded once.

@@ -21,6 +21,47 @@ constexpr int PHYS_AHEAD = 4;          // wall chunks in flight per wave (six: n
 constexpr int PHYS_FEW = 4;            // up to this many agents per env, their reach boxes ride in scalar registers
 constexpr int PHYS_PAIRS = (PHYS_FEW + 1)*WAVE;   // capacity of a wave's (wall, agent) pair list: a flush's worth + one chunk's worth for PHYS_FEW agents
 
+// The per-agent rules of a step, on values: physics_kernel and the one-launch step (render.h) call them with loads, stores and lanes of their own.
+// the spawn pose of agent i, if it is to be respawned (modules.py:321-326)
+__device__ inline void spawn_pose(const MsStepExtras& ex, const int i, float2& p, float& ang) {
+    const long long c = min(max(ex.respawn_choice[i], 0ll), (long long)ex.n_spawns - 1);
+    p = reinterpret_cast<const float2*>(ex.spawn_positions)[(size_t)i*ex.n_spawns + c];
+    ang = ex.spawn_angles[(size_t)i*ex.n_spawns + c];
+}
+// agent i's new age (modules.py:361-366): 0 if `reset` (its respawn mask) is set or comes out set because it has lived its span
+__device__ inline int lifespan_tick(const MsStepExtras& ex, const int i, bool& reset) {
+    const int life = ex.lifespans[i] + 1;
+    reset = reset | (life >= ex.max_lifespans[i]);
+    return reset ? 0 : life;
+}
+// the movement modules' velocity update (modules.py:57-66,106-118): the action's delta turned into the global frame, blended in
+__device__ inline void move_velocity(const float keep, const float ang, const float dx, const float dy, const float dw, float2& v, float& w) {
+    const float a_ = 0.017453292519943295f*ang;                         // np.pi/180*angles, in binary32 like torch
+    const float s_ = sinf(a_), c_ = cosf(a_);
+    const float gx = c_*dx - s_*dy, gy = s_*dx + c_*dy;
+    if (keep == 0.f) { w = dw; v = make_float2(gx, gy); }
+    else { w = keep*w + dw; v = make_float2(keep*v.x + gx, keep*v.y + gy); }
+}
+// how many of a cell's near walls (its header hdr) an agent of this reach meets: the short tier if the reach is within wg_reach_lo
+__device__ inline int near_count(const uint4 hdr, const float reach, const float reach_lo) {
+    return (int)((reach <= reach_lo) ? (hdr.w & 0xffffu) : (hdr.w >> 16));
+}
+// the integration epilogue (kernels.cu:224-227): the fraction x of the step the agent can take; stopped (x < 1): at rest
+__device__ inline bool integrate(const float x, const float fps, float2& p, float& ang, float2& v, float& w) {
+    p.x = p.x + x*v.x/fps;
+    p.y = p.y + x*v.y/fps;
+    ang = normalize_degrees(ang + x*w/fps);
+    const bool stopped = x < 1;
+    if (stopped) { v = make_float2(0.f, 0.f); w = 0.f; }
+    return stopped;
+}
+// the IMU reading (modules.py:263-270, to_local_frame :24-31); the scales are reciprocals: ATen's `a * (1.f/b)` for tensor / scalar
+__device__ inline float3 imu_reading(const MsStepExtras& ex, const float ang, const float2 v, const float w) {
+    const float a_ = 0.017453292519943295f*ang;                         // (as move_velocity)
+    const float s_ = sinf(a_), c_ = cosf(a_);
+    return make_float3(w*ex.imu_ang_scale, (c_*v.x + s_*v.y)*ex.imu_speed_scale, (-s_*v.x + c_*v.y)*ex.imu_speed_scale);
+}
+
 // MOVE = 1: the movement modules' velocity update runs first (MsMovement), on the state this wave is loading anyway
 // EXTRA = 1: the environment's bookkeeping (MsStepExtras: lifespans, respawns, IMU) runs in the same launch
 // PACK = 1: a wave takes `pack_envs` consecutive envs side by side (ms_step_physics: worlds of several rounds of waves with a
@@ -80,26 +121,18 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
     my_p = make_float2(0.f, 0.f); my_v = make_float2(0.f, 0.f); my_w = 0.f; my_ang = 0.f;
     if (lane < A) { my_p = pos2[nA + lane]; my_v = vel2[nA + lane]; my_w = ag.angvelocity[nA + lane]; my_ang = ag.angles[nA + lane]; }
 
-    // the spawn pose of agent i, if it is to be respawned (modules.py:321-326)
-    auto spawn_pose = [&](const int i, float2& p, float& ang) {
-        const long long c = min(max(ex.respawn_choice[i], 0ll), (long long)ex.n_spawns - 1);
-        p = reinterpret_cast<const float2*>(ex.spawn_positions)[(size_t)i*ex.n_spawns + c];
-        ang = ex.spawn_angles[(size_t)i*ex.n_spawns + c];
-    };
     if constexpr (EXTRA == 1) {
         for (int t = lane; t < A; t += WAVE) {
             const int i = nA + t;
             bool reset = ex.respawn_mask && ex.respawn_mask[i];
-            if (ex.lifespans) {                                          // modules.py:361-366
-                int life = ex.lifespans[i] + 1;
-                reset = reset | (life >= ex.max_lifespans[i]);
-                if (reset) { life = 0; ex.max_lifespans[i] = ex.fresh_max[i]; }
-                ex.lifespans[i] = life;
+            if (ex.lifespans) {
+                ex.lifespans[i] = lifespan_tick(ex, i, reset);
+                if (reset) ex.max_lifespans[i] = ex.fresh_max[i];
                 if (ex.respawn_mask) ex.respawn_mask[i] = reset ? 1 : 0;
             }
             if (reset && ex.spawn_positions && !ex.respawn_after) {
                 float2 p; float ang;
-                spawn_pose(i, p, ang);
+                spawn_pose(ex, i, p, ang);
                 if (t == lane) { my_p = p; my_ang = ang; my_v = make_float2(0.f, 0.f); my_w = 0.f; }
                 // through memory as well: agents beyond the first 64 live there, and the movement prologue and the
                 // epilogue's "velocity only changes on a collision" rule read it back
@@ -111,17 +144,12 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         }
     }
     if constexpr (MOVE == 1) {
-        // modules.py:57-66,106-118: look the action up, turn its velocity delta into the global frame, blend
         // (the table - seven actions, three floats each - rides in the lanes of one register, asked for up front: looked
         // up in memory by the action it would be a round trip behind the actions' own)
         const bool small_table = 3*mv.n_actions <= WAVE;
         const float tab = mv.table[min(lane, 3*mv.n_actions - 1)];
         auto moved = [&](const int i, const float ang, float2& v, float& w, const float dx, const float dy, const float dw) {
-            const float a_ = 0.017453292519943295f*ang;                 // np.pi/180*angles, in binary32 like torch
-            const float s_ = sinf(a_), c_ = cosf(a_);
-            const float gx = c_*dx - s_*dy, gy = s_*dx + c_*dy;
-            if (mv.keep == 0.f) { w = dw; v = make_float2(gx, gy); }
-            else { w = mv.keep*w + dw; v = make_float2(mv.keep*v.x + gx, mv.keep*v.y + gy); }
+            move_velocity(mv.keep, ang, dx, dy, dw, v, w);
             ag.angvelocity[i] = w;
             reinterpret_cast<float2*>(ag.velocity)[i] = v;
         };
@@ -205,15 +233,12 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         int count = 0;
         bool ok = A <= WAVE;
         if (lane < A) {
-            const float4 geom = wg_geom_n;
-            const float inv_cell = __builtin_amdgcn_rcpf(sc.wg_cell);
             const float4 me = s_task[lane];
-            const float fx = floorf((me.x - geom.x)*inv_cell), fy = floorf((me.y - geom.y)*inv_cell);
-            const bool inside = (fx >= 0.f) & (fx < geom.z) & (fy >= 0.f) & (fy < geom.w);   // (NaNs: outside)
-            const uint4 hdr = reinterpret_cast<const uint4*>(sc.wg_cells)[wg_start_n + (inside ? (int)fy*(int)geom.z + (int)fx : 0)];
+            bool inside;
+            const uint4 hdr = reinterpret_cast<const uint4*>(sc.wg_cells)[wg_start_n + wg_cell_at(wg_geom_n, sc.wg_cell, me.x, me.y, inside)];
             ok = (A <= WAVE) & inside & (my_reach <= sc.wg_reach);       // (a lane per agent: more than 64 of them take the sweep)
             first = hdr.z;
-            count = ok ? (int)((my_reach <= sc.wg_reach_lo) ? (hdr.w & 0xffffu) : (hdr.w >> 16)) : 0;
+            count = ok ? near_count(hdr, my_reach, sc.wg_reach_lo) : 0;
         }
         PROBE_AT(2, count)                                                   // ... the cells' headers
         const unsigned long long uncovered = __ballot(!ok);
@@ -339,7 +364,6 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
     PROBE_VAL(5, swept ? 1 : 0)
     PROBE_VAL(6, __popcll(__ballot((lane < A) && (bits_f(s_prog[min(lane, A - 1)]) < 1.f))))
     PROBE_AT(3, s_prog[min(lane, A - 1)])                                // every wall has been met
-    // epilogue, kernels.cu:224-227
     float2* pos2w = reinterpret_cast<float2*>(ag.positions);
     float2* vel2w = reinterpret_cast<float2*>(ag.velocity);
     for (int t = lane; t < A; t += WAVE) {
@@ -348,24 +372,20 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         float2 p = my_p, v = my_v;
         float w_ = my_w, ang = my_ang;
         if (t != lane) { p = pos2w[i]; v = vel2w[i]; w_ = ag.angvelocity[i]; ang = ag.angles[i]; }
-        p.x = p.x + x*v.x/fps;
-        p.y = p.y + x*v.y/fps;
-        float turned = normalize_degrees(ang + x*w_/fps);
-        bool stopped = x < 1;
-        if (stopped) { v = make_float2(0.f, 0.f); w_ = 0.f; }
+        bool stopped = integrate(x, fps, p, ang, v, w_);
         if constexpr (EXTRA == 1) {
             if (ex.spawn_positions && ex.respawn_after && ex.respawn_mask && ex.respawn_mask[i]) {
-                spawn_pose(i, p, turned);
+                spawn_pose(ex, i, p, ang);
                 v = make_float2(0.f, 0.f); w_ = 0.f;
                 stopped = true;
             }
         }
         pos2w[i] = p;
-        ag.angles[i] = turned;
+        ag.angles[i] = ang;
         if (ag.headings) {                                   // what render_prep_kernel would compute, one launch earlier
             float hs, hc;
-            sincospi_f(turned/180.f, hs, hc);
-            reinterpret_cast<float4*>(ag.headings)[i] = make_float4(turned, hs, hc, 0.f);
+            sincospi_f(ang/180.f, hs, hc);
+            reinterpret_cast<float4*>(ag.headings)[i] = make_float4(ang, hs, hc, 0.f);
         }
         if (stopped) {
             vel2w[i] = v;
@@ -373,14 +393,11 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         }
         progress[i] = x;
         if constexpr (EXTRA == 1) {
-            if (ex.imu) {                                    // modules.py:263-270, to_local_frame :24-31
-                const float a_ = 0.017453292519943295f*turned;
-                const float s_ = sinf(a_), c_ = cosf(a_);
-                // (times the reciprocals ms_step_physics left in the two fields: the modules divide a tensor by a Python scalar, which
-                // ATen evaluates as `a * (1.f/b)` - torch's own bits)
-                ex.imu[3*i] = w_*ex.imu_ang_scale;
-                ex.imu[3*i + 1] = (c_*v.x + s_*v.y)*ex.imu_speed_scale;
-                ex.imu[3*i + 2] = (-s_*v.x + c_*v.y)*ex.imu_speed_scale;
+            if (ex.imu) {
+                const float3 m = imu_reading(ex, ang, v, w_);
+                ex.imu[3*i] = m.x;
+                ex.imu[3*i + 1] = m.y;
+                ex.imu[3*i + 2] = m.z;
             }
         }
     }

@@ -80,13 +80,11 @@ __global__ __launch_bounds__(WG) void raycast_kernel(const MsScenery sc, const M
         bool listed = false;
         int cell = -1;
         if (gridded) {
-            const float4 geom = reinterpret_cast<const float4*>(sc.wg_geom)[n_w];
-            const float inv_cell = __builtin_amdgcn_rcpf(sc.wg_cell);   // (cells are grown by a centimetre: an ulp is nothing; as render_kernel)
-            const float fx = floorf((p.x - geom.x)*inv_cell), fy = floorf((p.y - geom.y)*inv_cell);
-            const bool inside = (fx >= 0.f) & (fx < geom.z) & (fy >= 0.f) & (fy < geom.w);    // (NaNs, an env without a grid: outside)
+            bool inside;
+            const int c = wg_cell_at(reinterpret_cast<const float4*>(sc.wg_geom)[n_w], sc.wg_cell, p.x, p.y, inside);
             const float ru2 = len2(ru);
             listed = inside & (ru2 >= 1.f) & (ru2 <= WG_MAX_RU2);
-            cell = listed ? sc.wg_starts[n_w] + (int)fy*(int)geom.z + (int)fx : -1;
+            cell = listed ? sc.wg_starts[n_w] + c : -1;
         }
         // (first the cells' list lengths alone: the lists are walked only if all of them together are shorter than the
         // env's walls - else every listed ray joins the sweep, and a wave of scattered rays pays a few header loads for it)

@@ -438,35 +438,27 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
     }
     };
     if constexpr (STEP == 1) {
-        // ---- the env's physics step (physics_kernel for its one agent, kernels.cu:179-230), every lane with the agent's state,
-        // lane = wall for the tests.  Same functions, same operations in the same order as physics_kernel: the same bits.
+        // ---- the env's physics step and its bookkeeping by physics.h's helpers, as physics_kernel: lane = wall for the tests, lane 0 writes
         float2 p_ = reinterpret_cast<const float2*>(ag.positions)[n], v_ = reinterpret_cast<const float2*>(ag.velocity)[n];
         float w_ = ag.angvelocity[n], ang_ = ag.angles[n];
-        // ---- what ms_step_physics runs around the step (MsStepExtras, MsMovement; physics_kernel<MOVE, EXTRA>), for this one agent,
-        // statement for statement in its order; every lane works the same values out, lane 0 writes (uniform branches: a caller
-        // that hands over neither pays two scalar compares)
         const MsStepExtras& ex = rc.ex;
-        const MsMovement& mv = rc.mv;
         bool respawn_now = false;
         float2 spawn_p = make_float2(0.f, 0.f);
         float spawn_ang = 0.f;
-        if (ex.respawn_mask || ex.lifespans) {                               // modules.py:361-366, :312-326
+        if (ex.respawn_mask || ex.lifespans) {                               // (uniform: without extras, two scalar compares)
             bool reset = ex.respawn_mask && ex.respawn_mask[n];
             if (ex.lifespans) {
-                int life = ex.lifespans[n] + 1;
-                reset = reset | (life >= ex.max_lifespans[n]);
+                const int life = lifespan_tick(ex, n, reset);
                 const int fresh = ex.fresh_max[n];
                 __builtin_amdgcn_wave_barrier();                                 // (every lane has read before lane 0 writes)
                 if (lane == 0) {
                     if (reset) ex.max_lifespans[n] = fresh;
-                    ex.lifespans[n] = reset ? 0 : life;
+                    ex.lifespans[n] = life;
                     if (ex.respawn_mask) ex.respawn_mask[n] = reset ? 1 : 0;
                 }
             }
             if (reset && ex.spawn_positions) {
-                const long long c_ = min(max(ex.respawn_choice[n], 0ll), (long long)ex.n_spawns - 1);
-                spawn_p = reinterpret_cast<const float2*>(ex.spawn_positions)[(size_t)n*ex.n_spawns + c_];
-                spawn_ang = ex.spawn_angles[(size_t)n*ex.n_spawns + c_];
+                spawn_pose(ex, n, spawn_p, spawn_ang);
                 respawn_now = true;
                 if (!ex.respawn_after) {
                     p_ = spawn_p; ang_ = spawn_ang; v_ = make_float2(0.f, 0.f); w_ = 0.f;
@@ -479,14 +471,9 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
                 }
             }
         }
-        if (mv.actions) {                                                    // modules.py:57-66,106-118
-            const long long act = min(max(mv.actions[n], 0ll), (long long)mv.n_actions - 1);
-            const float dx = mv.table[3*act], dy = mv.table[3*act + 1], dw = mv.table[3*act + 2];
-            const float a_ = 0.017453292519943295f*ang_;                     // np.pi/180*angles, in binary32 like torch
-            const float s_ = sinf(a_), c_ = cosf(a_);
-            const float gx = c_*dx - s_*dy, gy = s_*dx + c_*dy;
-            if (mv.keep == 0.f) { w_ = dw; v_ = make_float2(gx, gy); }
-            else { w_ = mv.keep*w_ + dw; v_ = make_float2(mv.keep*v_.x + gx, mv.keep*v_.y + gy); }
+        if (rc.mv.actions) {
+            const long long act = min(max(rc.mv.actions[n], 0ll), (long long)rc.mv.n_actions - 1);
+            move_velocity(rc.mv.keep, ang_, rc.mv.table[3*act], rc.mv.table[3*act + 1], rc.mv.table[3*act + 2], v_, w_);
             if (lane == 0) {
                 ag.angvelocity[n] = w_;
                 reinterpret_cast<float2*>(ag.velocity)[n] = v_;
@@ -504,16 +491,13 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         unsigned near_first = 0u;
         int n_src = max(L - AF, 0);
         if (rc.wg_cells_physics) {                                          // (uniform)
-            const float4 geom = wg_geom_n;
-            const float inv_cell = __builtin_amdgcn_rcpf(sc.wg_cell);
-            const float fx = floorf((p0.x - geom.x)*inv_cell), fy = floorf((p0.y - geom.y)*inv_cell);
-            const bool inside = (fx >= 0.f) & (fx < geom.z) & (fy >= 0.f) & (fy < geom.w);       // (NaNs: outside)
-            const int cell_id = __builtin_amdgcn_readfirstlane(wg_start_n + (inside ? (int)fy*(int)geom.z + (int)fx : 0));
+            bool inside;
+            const int cell_id = __builtin_amdgcn_readfirstlane(wg_start_n + wg_cell_at(wg_geom_n, sc.wg_cell, p0.x, p0.y, inside));
             const uint4 hdr = reinterpret_cast<const uint4*>(rc.wg_cells_physics)[cell_id];
             listed_p = __builtin_amdgcn_readfirstlane((inside & (my_reach <= sc.wg_reach)) ? 1 : 0) != 0;
             if (listed_p) {
                 near_first = (unsigned)__builtin_amdgcn_readfirstlane((int)hdr.z);
-                n_src = __builtin_amdgcn_readfirstlane((int)((my_reach <= sc.wg_reach_lo) ? (hdr.w & 0xffffu) : (hdr.w >> 16)));
+                n_src = __builtin_amdgcn_readfirstlane(near_count(hdr, my_reach, sc.wg_reach_lo));
             }
         }
         unsigned xb = f_bits(1.f);
@@ -529,37 +513,32 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         #pragma unroll
         for (int o = 1; o < WAVE; o <<= 1) xb = min(xb, (unsigned)__shfl_xor((int)xb, o, WAVE));
         const float x = bits_f(xb);
-        // the epilogue, kernels.cu:224-227
-        float2 p_new = make_float2(p_.x + x*v_.x/rc.fps, p_.y + x*v_.y/rc.fps);
-        float turned = normalize_degrees(ang_ + x*w_/rc.fps);
-        bool stopped = x < 1;
-        if (stopped) { v_ = make_float2(0.f, 0.f); w_ = 0.f; }
+        bool stopped = integrate(x, rc.fps, p_, ang_, v_, w_);
         if (respawn_now && ex.respawn_after && ex.respawn_mask) {            // Explorer's order: the step first, then the new pose
-            p_new = spawn_p; turned = spawn_ang;
+            p_ = spawn_p; ang_ = spawn_ang;
             v_ = make_float2(0.f, 0.f); w_ = 0.f;
             stopped = true;
         }
-        const float2 hsc = sincospi_called(turned/180.f);
+        const float2 hsc = sincospi_called(ang_/180.f);
         if (lane == 0) {
-            reinterpret_cast<float2*>(ag.positions)[n] = p_new;
-            ag.angles[n] = turned;
-            if (ag.headings) reinterpret_cast<float4*>(ag.headings)[n] = make_float4(turned, hsc.x, hsc.y, 0.f);
+            reinterpret_cast<float2*>(ag.positions)[n] = p_;
+            ag.angles[n] = ang_;
+            if (ag.headings) reinterpret_cast<float4*>(ag.headings)[n] = make_float4(ang_, hsc.x, hsc.y, 0.f);
             if (stopped) {
                 reinterpret_cast<float2*>(ag.velocity)[n] = v_;
                 ag.angvelocity[n] = w_;
             }
             rc.progress[n] = x;
         }
-        if (ex.imu) {                                                        // modules.py:263-270, to_local_frame :24-31
-            const float a_ = 0.017453292519943295f*turned;
-            const float s_ = sinf(a_), c_ = cosf(a_);
+        if (ex.imu) {
+            const float3 m = imu_reading(ex, ang_, v_, w_);
             if (lane == 0) {
-                ex.imu[3*n] = w_*ex.imu_ang_scale;                           // (the reciprocals: see physics_kernel)
-                ex.imu[3*n + 1] = (c_*v_.x + s_*v_.y)*ex.imu_speed_scale;
-                ex.imu[3*n + 2] = (-s_*v_.x + c_*v_.y)*ex.imu_speed_scale;
+                ex.imu[3*n] = m.x;
+                ex.imu[3*n + 1] = m.y;
+                ex.imu[3*n + 2] = m.z;
             }
         }
-        ag_s = hsc.x; ag_c = hsc.y; ag_p = p_new;                            // the pose the rays are cast from
+        ag_s = hsc.x; ag_c = hsc.y; ag_p = p_;                               // the pose the rays are cast from
     } else {
         load_agents();
     }
@@ -602,12 +581,9 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
     unsigned wg_first = 0u;
     int wg_count = -1;
     if (sc.wg_cells) {                                                  // (the same for every wave of the launch)
-        const float4 geom = wg_geom_n;
-        const float inv_cell = __builtin_amdgcn_rcpf(sc.wg_cell);       // (cells are grown by a centimetre: an ulp is nothing)
-        const float fx = floorf((pp.x - geom.x)*inv_cell), fy = floorf((pp.y - geom.y)*inv_cell);
-        const bool inside = (fx >= 0.f) & (fx < geom.z) & (fy >= 0.f) & (fy < geom.w);    // (NaNs, an env without a grid: outside)
+        bool inside;
         // every wave reads a header that exists - its cell's, or the row at its env's start (the array is padded by one)
-        const int cell_id = __builtin_amdgcn_readfirstlane(wg_start_n + (inside ? (int)fy*(int)geom.z + (int)fx : 0));
+        const int cell_id = __builtin_amdgcn_readfirstlane(wg_start_n + wg_cell_at(wg_geom_n, sc.wg_cell, pp.x, pp.y, inside));
         const uint4 hdr = reinterpret_cast<const uint4*>(sc.wg_cells)[cell_id];
         wg_first = inside ? hdr.x : 0u;
         wg_count = inside ? (int)hdr.y : -1;
