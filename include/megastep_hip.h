@@ -390,6 +390,68 @@ typedef struct MsOverhead {
 int ms_overhead(const MsScenery* scenery, const MsAgents* agents /* NULL: agent rows as stored */, const MsOverhead* overhead,
                 void* hip_stream);
 
+/* Shortest-path distance fields on the floorplans: how far it is from a point to a goal when one has to walk round the
+ * walls.  Every step below is one binary32 operation, in the order given, without contraction: tests/test_navfield_host.py
+ * restates it in numpy bit for bit (nav_rule), and the GPU tests hold the kernels to EQUALITY with it.
+ *   nav grid      Env n's cells are squares of side c = cell; column j, row i (y grows with i) has the centre
+ *                 x = ((float)(jx0 + j) + 0.5f)*c, y = ((float)(iy0 + i) + 0.5f)*c.  geom[n] = (jx0, iy0, nx, ny) is the
+ *                 caller's (cuda.nav_grid: the static walls' bounding box and one cell of margin); env n's nx*ny cells
+ *                 start at starts[n], row-major: ragged, not padded.
+ *   free cells    A cell is blocked (0) when any STATIC line of its env (lines from n_agents*n_model on) covers its centre
+ *                 under MsOverhead's rule with half_width = r = clearance - the same vx, vy, px, py, vv, t, dx, dy, d2
+ *                 sequence, d2 <= r*r; a NaN never covers - else free (1).  Agent rows are not looked at.
+ *   edges         A free cell is joined to its free 4-neighbours with weight ws = c, and to a free diagonal neighbour with
+ *                 weight wd = c*1.41421356f only if the two cells that share a side with both are free too (no corner is
+ *                 cut).  c <= 1.4f*r is required: a wall across an edge between two free centres would come within half
+ *                 the edge's length, at most c sqrt(2)/2 <= 0.99 r, of the nearer one, which would then be blocked - so
+ *                 no path of the graph passes through a wall, however thin or oblique.
+ *   anchors       of a point p = (x, y): fx = floorf(x/c - 0.5f), fy likewise; without anchors when either is a NaN or
+ *                 |.| >= 2^30; else j0 = (int)fx - jx0, i0 = (int)fy - iy0 and the anchors are those of the four cells
+ *                 (i0 + {0,1}, j0 + {0,1}) that lie in the grid and are free.  leg(a) = sqrtf(dx*dx + dy*dy), (dx, dy)
+ *                 from the anchor's centre to p, the root correctly rounded.  A leg is at most c sqrt(2) <= 1.98 r long:
+ *                 from a point further than r from every wall (an agent's centre, a spawn point) it crosses no wall.
+ *   field         of goal p: D[a] = leg(a) at p's anchors, then the least fixed point of D[v] = min(D[v], D[u] + w(u, v))
+ *                 over all edges; +inf on blocked cells, on cells no path reaches, everywhere when p has no anchor.
+ *                 x -> fl(x + w) is monotone and every value a cell ever holds is the left-to-right binary32 sum along a
+ *                 path from an anchor, so the fixed point does not depend on the order of relaxation: it is what Dijkstra
+ *                 with binary32 additions returns.  The 8-connected metric: up to 8 % above the any-angle shortest path.
+ *   query         g(p) = min over p's anchors a of (D[a] + leg(a)); +inf without an anchor or with a goal index out of
+ *                 [0, n_goals).
+ * All outputs are the caller's; nothing is allocated, nothing waits for the device: all three calls can be captured in a
+ * HIP graph.  Every argument is checked in full before the first launch (MS_EINVAL). */
+typedef struct MsNavGrid {
+    int                  n_envs;       /* N                                                                            */
+    float                cell;         /* c, metres (> 0, <= 1.4f*clearance)                                           */
+    float                clearance;    /* r, metres (> 0)                                                              */
+    const int*           geom;         /* (N, 4) jx0, iy0, nx, ny; 16-byte aligned                                     */
+    const long long*     starts;       /* (N+1,) first cell of every env; starts[N] = all cells                        */
+    int                  max_framed;   /* the largest (nx + 2)*(ny + 2) of any env with cells (0: no env has any): sizes
+                                          the launches; a larger env still gets the right bits, slowly                  */
+    unsigned char*       free_cells;   /* (starts[N],) 1 free, 0 blocked: written by ms_nav_free, read by the others   */
+} MsNavGrid;
+typedef struct MsNavFields {
+    int                  n_goals;      /* G: goals (fields) per env                                                    */
+    const float*         goals;        /* (N, G, 2) x, y; 8-byte aligned                                               */
+    const unsigned char* mask;         /* (N, G) non-zero: compute this field; NULL: all.  Read on the device only.    */
+    float*               fields;       /* G*starts[N] floats: field (n, g) at G*starts[n] + g*nx*ny, row-major         */
+    int*                 passes;       /* (N, G) or NULL: relaxation passes each computed field took (telemetry)       */
+} MsNavFields;
+typedef struct MsNavQuery {
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y; 8-byte aligned                                               */
+    const int*           goal;         /* (N, P) which of the env's fields each point asks; NULL: P == G, point k field k */
+    const float*         fields;       /* as MsNavFields.fields                                                        */
+    int                  n_goals;      /* G of `fields`                                                                */
+    float*               out;          /* (N, P) g(p)                                                                  */
+} MsNavQuery;
+/* ms_nav_free    fills grid->free_cells from the scenery's static walls (one-off per scenery and (cell, clearance)).
+ * ms_nav_fields  computes the fields of the marked goals, one workgroup per field, the field resident in LDS while it
+ *                fits (about 32 000 cells); fields that are masked out are left as they are.
+ * ms_nav_query   g(p) for P points per env, each against one of the env's G fields. */
+int ms_nav_free(const MsScenery* scenery, const MsNavGrid* grid, void* hip_stream);
+int ms_nav_fields(const MsNavGrid* grid, const MsNavFields* fields, void* hip_stream);
+int ms_nav_query(const MsNavGrid* grid, const MsNavQuery* query, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

@@ -1,0 +1,240 @@
+// kernels/navfield.h -- nav_free_kernel, nav_relax_kernel, nav_query_kernel.
+// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after overhead.h: a cell
+// is blocked by overhead.h's ov_fold, the very statements of MsOverhead's rule); not a header to compile on its own.
+// ------------------------------------------------------------------------------------------------
+// shortest-path distance fields on the floorplans                          no counterpart in the reference
+// ------------------------------------------------------------------------------------------------
+// The contract is written out in include/megastep_hip.h (MsNavGrid) and DESIGN.md section 3.14: a grid of square cells over
+// every env's static walls, a cell blocked when a wall comes within the clearance of its centre; free cells joined to their
+// free 4-neighbours (weight c) and, where no corner is cut, to their diagonal ones (weight c*1.41421356f); the field of a
+// goal is the least fixed point of D[v] = min(D[v], D[u] + w(u, v)) from the goal's anchors.  Every value a cell ever holds
+// is the left-to-right binary32 sum along some path and x -> fl(x + w) is monotone, so ANY schedule that stops only when no
+// edge can lower anything ends on the same bits.  tests/test_navfield_host.py restates all of it in numpy.
+//
+//   nav_free_kernel    one lane a cell, the env's static walls staged through LDS a block of WG at a time.
+//   nav_relax_kernel   one workgroup per field.  The field lives in LDS (a frame of blocked cells round it, so that no
+//                      neighbour needs a bounds check) next to a byte a cell: bit 0 free, bits 1-4 which diagonals are
+//                      open.  A pass: every lane relaxes cells tid, tid + T, ... IN PLACE from their eight neighbours -
+//                      consecutive lanes read consecutive words whatever the row pitch, so no read or write meets a bank
+//                      conflict; the lanes race, on purpose: a cell is written by its own lane only and only ever lowered,
+//                      a stale read costs a pass, never a bit.  One barrier a pass carries the "something changed" flag;
+//                      the first pass in which no lane lowered anything saw constant values throughout, so no edge can
+//                      lower anything: the fixed point.  Then the field is stored once.  Three instantiations by the LDS
+//                      they declare (40, 80, 160 KiB: four, two, one workgroup a CU); a field too large for the launch's
+//                      one runs the same relaxation on the field in global memory - slower, the same bits.
+//   nav_query_kernel   one lane a point: the point's (at most four) anchors gathered from its field.
+constexpr int NAV_LDS_SMALL = 40*1024, NAV_LDS_MEDIUM = 80*1024, NAV_LDS_LARGE = 160*1024;
+constexpr int nav_capacity(const int lds_bytes) { return (lds_bytes - 64)/5/4*4; }      // framed cells: a float and a byte each
+constexpr float NAV_DIAGONAL = 1.41421356f;
+constexpr float NAV_INDEX_LIMIT = 1073741824.f;      // |floorf(x/c - .5f)| at or beyond 2^30 (or a NaN): the point has no anchor
+
+struct NavArgs {                                     // MsNavGrid, checked
+    const int* geom;                                 // (N, 4) jx0, iy0, nx, ny
+    const long long* starts;                         // (N + 1,) first cell of every env
+    int n_envs;
+    float cell, clearance;
+};
+
+__device__ inline float nav_centre(const int origin, const int k, const float c) { return ((float)(origin + k) + .5f)*c; }
+
+// The cell (i0, j0) whose centre is the last at or below p on both axes - p's anchors are (i0 + {0, 1}, j0 + {0, 1}); false:
+// p has none (NaN, or further out than any grid).
+__device__ inline bool nav_anchor_corner(const float x, const float y, const float c, const int jx0, const int iy0, long long& i0, long long& j0) {
+    const float fx = floorf(x/c - .5f), fy = floorf(y/c - .5f);
+    if (!(fabsf(fx) < NAV_INDEX_LIMIT) || !(fabsf(fy) < NAV_INDEX_LIMIT)) return false;
+    j0 = (long long)fx - jx0; i0 = (long long)fy - iy0;
+    return true;
+}
+
+__device__ inline float nav_leg(const float x, const float y, const int jx0, const int iy0, const int i, const int j, const float c) {
+    const float dx = x - nav_centre(jx0, j, c), dy = y - nav_centre(iy0, i, c);
+    return sqrtf(dx*dx + dy*dy);
+}
+
+// Racy by design (see above): relaxed atomics are plain loads and stores that the compiler may not invent, merge or carry
+// across passes.
+__device__ inline float nav_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ inline void nav_store(float* p, const float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+__global__ __launch_bounds__(WG) void nav_free_kernel(const MsScenery sc, const NavArgs a, unsigned char* free_cells) {
+    __shared__ float4 s_rows[WG];
+    const int e = blockIdx.y, tid = threadIdx.x;
+    const int4 g = reinterpret_cast<const int4*>(a.geom)[e];
+    const long long cells = (long long)g.z*g.w;
+    const long long k = (long long)blockIdx.x*WG + tid;
+    if ((long long)blockIdx.x*WG >= cells) return;                      // (uniform: the grid is sized for the largest env)
+    const bool live = k < cells;
+    const int i = live ? (int)(k / g.z) : 0, j = live ? (int)(k - (long long)i*g.z) : 0;
+    const float x = nav_centre(g.x, j, a.cell), y = nav_centre(g.y, i, a.cell);
+    const float h2 = a.clearance*a.clearance;
+    const int AF = sc.n_agents*sc.n_model;
+    const int L = sc.lines_widths[e];
+    const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[e];
+    OvBest best{INFINITY, INT_MAX, 0.f};
+    for (int l0 = AF; l0 < L; l0 += WG) {
+        if (l0 + tid < L) s_rows[tid] = rows[l0 + tid];
+        __syncthreads();
+        const int count = min(WG, L - l0);
+        for (int q = 0; q < count; q++) ov_fold(x, y, s_rows[q], l0 + q, h2, best);
+        __syncthreads();
+    }
+    if (live) free_cells[a.starts[e] + k] = best.idx == INT_MAX ? 1 : 0;
+}
+
+struct NavFieldArgs {
+    const float* goals;                              // (N, G, 2)
+    const unsigned char* mask;                       // (N, G) or NULL
+    const unsigned char* free_cells;
+    float* fields;
+    int* passes;                                     // (N, G) or NULL: passes the field took (0: masked out)
+    int n_goals;
+};
+
+// The lowered value of a cell from its neighbours' (the min first, one addition per weight: x -> fl(x + w) is monotone, so
+// fl(min + w) is the min of the sums).
+__device__ inline float nav_relaxed(const float d, const float straight, const float diagonal, const float ws, const float wd) {
+    return fminf(d, fminf(straight + ws, diagonal + wd));
+}
+
+template <int LDS_BYTES, int THREADS>
+__global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, const NavFieldArgs f) {
+    constexpr int CAP = nav_capacity(LDS_BYTES);
+    __shared__ float s_d[CAP];
+    __shared__ unsigned char s_m[CAP];
+    __shared__ int s_flag[3];
+    const int tid = threadIdx.x;
+    const long long field = blockIdx.x;                                // (n, g): n G + g
+    const int e = (int)(field / f.n_goals), gi = (int)(field - (long long)e*f.n_goals);
+    if (f.mask && !f.mask[field]) return;                               // (uniform) left as it is
+    const int4 g = reinterpret_cast<const int4*>(a.geom)[e];
+    const int nx = g.z, ny = g.w;
+    const long long cells = (long long)nx*ny;
+    if (cells <= 0) { if (f.passes && tid == 0) f.passes[field] = 0; return; }
+    const unsigned char* const fr = f.free_cells + a.starts[e];
+    float* const out = f.fields + (long long)f.n_goals*a.starts[e] + (long long)gi*cells;
+    const float c = a.cell, ws = c, wd = c*NAV_DIAGONAL;
+    const float2 p = reinterpret_cast<const float2*>(f.goals)[field];
+    long long i0, j0;
+    const bool anchored = nav_anchor_corner(p.x, p.y, c, g.x, g.y, i0, j0);
+    const long long framed = (long long)(nx + 2)*(ny + 2);
+    int passes = 0;
+
+    if (framed <= CAP) {
+        const int P = nx + 2, n = (int)framed;
+        for (int k = tid; k < n; k += THREADS) {
+            const int i = k / P - 1, j = k - (i + 1)*P - 1;
+            s_d[k] = INFINITY;
+            s_m[k] = ((i >= 0) & (i < ny) & (j >= 0) & (j < nx)) ? fr[(long long)i*nx + j] & 1 : 0;
+        }
+        if (tid < 3) s_flag[tid] = 0;
+        __syncthreads();
+        for (int k = tid; k < n; k += THREADS) {                       // which diagonals are open: neither corner is cut
+            if (s_m[k] & 1) {
+                const int N_ = s_m[k - P] & 1, S_ = s_m[k + P] & 1, W_ = s_m[k - 1] & 1, E_ = s_m[k + 1] & 1;
+                const int m = 1 | ((N_ & W_ & s_m[k - P - 1]) << 1) | ((N_ & E_ & s_m[k - P + 1]) << 2) |
+                              ((S_ & W_ & s_m[k + P - 1]) << 3) | ((S_ & E_ & s_m[k + P + 1]) << 4);
+                s_m[k] = (unsigned char)m;                              // (bit 0, all a neighbour reads, does not change)
+            }
+        }
+        if (anchored && tid < 4) {
+            const long long i = i0 + (tid >> 1), j = j0 + (tid & 1);
+            if ((i >= 0) & (i < ny) & (j >= 0) & (j < nx)) {
+                const int k = ((int)i + 1)*P + (int)j + 1;
+                if (s_m[k] & 1) s_d[k] = nav_leg(p.x, p.y, g.x, g.y, (int)i, (int)j, c);
+            }
+        }
+        __syncthreads();
+        for (;;) {
+            if (tid == 0) s_flag[(passes + 1) % 3] = 0;                 // (last read two barriers ago)
+            bool changed = false;
+            for (int k = tid; k < n; k += THREADS) {
+                const int m = s_m[k];
+                if (m & 1) {
+                    const float d = nav_load(s_d + k);
+                    const float st = fminf(fminf(nav_load(s_d + k - 1), nav_load(s_d + k + 1)), fminf(nav_load(s_d + k - P), nav_load(s_d + k + P)));
+                    const float nw = m & 2 ? nav_load(s_d + k - P - 1) : INFINITY, ne = m & 4 ? nav_load(s_d + k - P + 1) : INFINITY;
+                    const float sw = m & 8 ? nav_load(s_d + k + P - 1) : INFINITY, se = m & 16 ? nav_load(s_d + k + P + 1) : INFINITY;
+                    const float v = nav_relaxed(d, st, fminf(fminf(nw, ne), fminf(sw, se)), ws, wd);
+                    if (v < d) { nav_store(s_d + k, v); changed = true; }
+                }
+            }
+            if (changed) s_flag[passes % 3] = 1;
+            __syncthreads();
+            const int again = s_flag[passes % 3];
+            passes++;
+            if (!again) break;                                          // (uniform)
+        }
+        for (long long k = tid; k < cells; k += THREADS) {
+            const int i = (int)(k / nx), j = (int)(k - (long long)i*nx);
+            out[k] = s_d[(i + 1)*P + j + 1];
+        }
+    } else {
+        // the same relaxation on the field where it is stored
+        for (long long k = tid; k < cells; k += THREADS) out[k] = INFINITY;
+        if (tid < 3) s_flag[tid] = 0;
+        __syncthreads();
+        if (anchored && tid < 4) {
+            const long long i = i0 + (tid >> 1), j = j0 + (tid & 1);
+            if ((i >= 0) & (i < ny) & (j >= 0) & (j < nx) && (fr[i*nx + j] & 1)) out[i*nx + j] = nav_leg(p.x, p.y, g.x, g.y, (int)i, (int)j, c);
+        }
+        __syncthreads();
+        for (;;) {
+            if (tid == 0) s_flag[(passes + 1) % 3] = 0;
+            bool changed = false;
+            for (long long k = tid; k < cells; k += THREADS) {
+                if (!(fr[k] & 1)) continue;
+                const int i = (int)(k / nx), j = (int)(k - (long long)i*nx);
+                const bool up = i > 0, down = i < ny - 1, left = j > 0, right = j < nx - 1;
+                const bool N_ = up && (fr[k - nx] & 1), S_ = down && (fr[k + nx] & 1), W_ = left && (fr[k - 1] & 1), E_ = right && (fr[k + 1] & 1);
+                const float d = nav_load(out + k);
+                const float st = fminf(fminf(W_ ? nav_load(out + k - 1) : INFINITY, E_ ? nav_load(out + k + 1) : INFINITY),
+                                       fminf(N_ ? nav_load(out + k - nx) : INFINITY, S_ ? nav_load(out + k + nx) : INFINITY));
+                const float nw = N_ && W_ && (fr[k - nx - 1] & 1) ? nav_load(out + k - nx - 1) : INFINITY;
+                const float ne = N_ && E_ && (fr[k - nx + 1] & 1) ? nav_load(out + k - nx + 1) : INFINITY;
+                const float sw = S_ && W_ && (fr[k + nx - 1] & 1) ? nav_load(out + k + nx - 1) : INFINITY;
+                const float se = S_ && E_ && (fr[k + nx + 1] & 1) ? nav_load(out + k + nx + 1) : INFINITY;
+                const float v = nav_relaxed(d, st, fminf(fminf(nw, ne), fminf(sw, se)), ws, wd);
+                if (v < d) { nav_store(out + k, v); changed = true; }
+            }
+            if (changed) s_flag[passes % 3] = 1;
+            __syncthreads();                                            // (the workgroup's stores are visible to its loads from here on)
+            const int again = s_flag[passes % 3];
+            passes++;
+            if (!again) break;
+        }
+    }
+    if (f.passes && tid == 0) f.passes[field] = passes;
+}
+
+struct NavQueryArgs {
+    const float* points;                             // (N, P, 2)
+    const int* goal;                                 // (N, P) or NULL
+    const float* fields;
+    float* out;                                      // (N, P)
+    int n_points, n_goals;
+    long long total;                                 // N P
+};
+
+__global__ __launch_bounds__(WG) void nav_query_kernel(const NavArgs a, const NavQueryArgs q) {
+    const long long at = (long long)blockIdx.x*WG + threadIdx.x;
+    if (at >= q.total) return;
+    const int e = (int)(at / q.n_points), k = (int)(at - (long long)e*q.n_points);
+    const int gi = q.goal ? q.goal[at] : k;
+    const int4 g = reinterpret_cast<const int4*>(a.geom)[e];
+    const int nx = g.z, ny = g.w;
+    const long long cells = (long long)nx*ny;
+    float best = INFINITY;
+    const float2 p = reinterpret_cast<const float2*>(q.points)[at];
+    long long i0, j0;
+    if ((gi >= 0) & (gi < q.n_goals) && cells > 0 && nav_anchor_corner(p.x, p.y, a.cell, g.x, g.y, i0, j0)) {
+        const float* const D = q.fields + (long long)q.n_goals*a.starts[e] + (long long)gi*cells;
+        for (int t = 0; t < 4; t++) {
+            const long long i = i0 + (t >> 1), j = j0 + (t & 1);
+            if ((i >= 0) & (i < ny) & (j >= 0) & (j < nx)) {
+                const float d = D[i*nx + j];                            // (+inf on a blocked cell: it is no anchor)
+                if (d < INFINITY) best = fminf(best, d + nav_leg(p.x, p.y, g.x, g.y, (int)i, (int)j, a.cell));
+            }
+        }
+    }
+    q.out[at] = best;
+}

@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h.
 //
-// Sixteen kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Nineteen kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -45,6 +45,9 @@
 //   overhead_kernel     top-down pictures: one workgroup per 16 x 16 tile of an image, the env's lines culled against the
 //                   tile's footprint into LDS, then each lane's pixel folded over them.   (reference: plotting.py draws
 //                   these with matplotlib, one env at a time on the host)
+//   nav_free_kernel, nav_relax_kernel, nav_query_kernel   shortest-path distance fields: which cells of a grid over a floorplan
+//                   keep the agent's radius clear of every wall; per goal one workgroup that relaxes the 8-connected field in
+//                   LDS until nothing changes; and the distance from any point to a goal, four gathers.   (no counterpart)
 //   explorer_kernel     the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
 //   deathmatch_kernel   the Deathmatch env's game logic between frames (revive, crosshairs, hits and wounds, health, damage,
@@ -134,6 +137,7 @@ struct Probe {
 #include "kernels/wallgrid.h"
 #include "kernels/raycast.h"
 #include "kernels/overhead.h"
+#include "kernels/navfield.h"
 #include "kernels/envlogic.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -729,6 +733,50 @@ int ms_host_overhead_keeps(const float* g, int height, int width, int tile_row, 
     const OvBox box = ov_footprint(g[0], g[1], g[2], g[3], g[4], g[5], i0, j0, i0 + OV_TILE - 1 < height - 1 ? i0 + OV_TILE - 1 : height - 1,
                                    j0 + OV_TILE - 1 < width - 1 ? j0 + OV_TILE - 1 : width - 1);
     return ov_keeps(box, half_width, make_float4(line[0], line[1], line[2], line[3])) ? 1 : 0;
+}
+
+// Distance fields (navfield.h): every argument checked in full before the first launch; nothing is allocated, nothing waits.
+static bool nav_grid_ok(const MsNavGrid* g) {
+    return g && g->n_envs > 0 && g->cell > 0.f && g->cell < INFINITY && g->clearance > 0.f && g->clearance < INFINITY &&
+           g->cell <= 1.4f*g->clearance && g->geom && g->starts && g->free_cells && g->max_framed >= 0 && ((uintptr_t)g->geom % 16 == 0);
+}
+static NavArgs nav_args(const MsNavGrid* g) { return NavArgs{g->geom, g->starts, g->n_envs, g->cell, g->clearance}; }
+
+int ms_nav_free(const MsScenery* sc, const MsNavGrid* grid, void* stream) {
+    if (!scenery_ok(sc) || !nav_grid_ok(grid) || grid->n_envs != sc->n_envs) return MS_EINVAL;
+    if (grid->n_envs > 65535) return MS_EUNSUPPORTED;
+    if (grid->max_framed == 0) return MS_OK;
+    const unsigned blocks = (unsigned)(((long long)grid->max_framed + WG - 1)/WG);        // (at least the largest env's cells)
+    hipLaunchKernelGGL(nav_free_kernel, dim3(blocks, (unsigned)grid->n_envs), dim3(WG), 0, (hipStream_t)stream, *sc, nav_args(grid), grid->free_cells);
+    return launch_status();
+}
+
+int ms_nav_fields(const MsNavGrid* grid, const MsNavFields* nf, void* stream) {
+    if (!nav_grid_ok(grid) || !nf || nf->n_goals < 1 || !nf->goals || !nf->fields || ((uintptr_t)nf->goals % 8)) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*nf->n_goals;
+    if (total > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    const NavFieldArgs f{nf->goals, nf->mask, grid->free_cells, nf->fields, nf->passes, nf->n_goals};
+    // the least LDS that holds the largest env's framed field: more workgroups a CU (a field that still does not fit - or an
+    // env larger than max_framed says - relaxes in global memory)
+    const long long framed = grid->max_framed;
+    const dim3 fields((unsigned)total);
+    if (framed <= nav_capacity(NAV_LDS_SMALL))
+        hipLaunchKernelGGL((nav_relax_kernel<NAV_LDS_SMALL, 512>), fields, dim3(512), 0, (hipStream_t)stream, nav_args(grid), f);
+    else if (framed <= nav_capacity(NAV_LDS_MEDIUM))
+        hipLaunchKernelGGL((nav_relax_kernel<NAV_LDS_MEDIUM, 1024>), fields, dim3(1024), 0, (hipStream_t)stream, nav_args(grid), f);
+    else
+        hipLaunchKernelGGL((nav_relax_kernel<NAV_LDS_LARGE, 1024>), fields, dim3(1024), 0, (hipStream_t)stream, nav_args(grid), f);
+    return launch_status();
+}
+
+int ms_nav_query(const MsNavGrid* grid, const MsNavQuery* nq, void* stream) {
+    if (!nav_grid_ok(grid) || !nq || nq->n_points < 1 || nq->n_goals < 1 || !nq->points || !nq->fields || !nq->out ||
+        (!nq->goal && nq->n_points != nq->n_goals) || ((uintptr_t)nq->points % 8)) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*nq->n_points;
+    if (total > 0x7fffff00LL) return MS_EUNSUPPORTED;
+    const NavQueryArgs q{nq->points, nq->goal, nq->fields, nq->out, nq->n_points, nq->n_goals, total};
+    hipLaunchKernelGGL(nav_query_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
+    return launch_status();
 }
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {

@@ -1,0 +1,95 @@
+"""Point-goal navigation: every agent is given a goal it can walk to and is rewarded for its progress along the shortest
+path - last step's walking distance minus this step's - plus a bonus when it arrives within ``arrive`` metres, which also
+ends its episode. An agent without a goal it can walk to - none of its candidates was reachable, or it has left the cells
+the nav grid can see - is flagged (``Goals.stranded``), earns nothing and starts over at the next step. No counterpart in the reference, whose two envs are an explorer and a deathmatch; this is the third env
+every user of such a simulator writes, on the distance fields of :func:`megastep_amd.cuda.distance_fields`.
+
+A step has no host synchronisation and draws no random numbers of its own besides :class:`~megastep_amd.modules.RandomLifespans`',
+so it can be captured in a HIP graph (:class:`megastep_amd.graphs.GraphedStep`)."""
+import torch
+
+from ... import arrdict, core, cubicasa, cuda, dotdict, modules, scene
+from .explorer import _plan_workers
+
+
+def books(before, now, reset, stranded, arrive, bonus):
+    """The arithmetic between two frames, all (n_env, n_agent): ``before`` / ``now`` the walking distances to the goal at the
+    last step and at this one, ``reset`` who started over this step, ``stranded`` who has no goal. Returns (reward, ended):
+    progress - nothing on a reset step, nothing where either distance is not finite - plus ``bonus`` on arrival; an agent's
+    episode ends when it arrives (``now < arrive``) or is stranded."""
+    arrived = (now < arrive) & ~stranded
+    counts = torch.isfinite(before) & torch.isfinite(now) & ~reset
+    reward = torch.where(counts, before - now, torch.zeros_like(now)) + bonus*arrived
+    return reward, arrived | stranded
+
+
+class PointGoal:
+
+    def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, arrive=.5, bonus=1., max_lifespan=512,
+                 candidates=8, n_spawns=100, **kwargs):
+        """``cell``: the nav grid's cell size; ``arrive``: how near the goal counts as there, metres (walking distance);
+        ``bonus``: the reward for arriving; ``max_lifespan``: episodes end after a random number of steps up to this
+        (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`."""
+        if geometries is None:
+            geometries = cubicasa.sample(n_envs, workers=_plan_workers(), context='subprocess')
+        self.core = core.Core(scene.scenery(geometries, n_agents, device=device), *args, res=4*64, fov=130, **kwargs)
+        c = self.core
+        self.device = c.device
+        self.arrive, self.bonus = float(arrive), float(bonus)
+
+        self._mover = modules.MomentumMovement(c)
+        self._respawner = modules.RandomSpawns(geometries, c, n_spawns=n_spawns)
+        self._lifespans = modules.RandomLifespans(c, max_lifespan)
+        self._rgb = modules.RGB(c, subsample=4)
+        self._depth = modules.Depth(c, subsample=4)
+        self.grid = cuda.nav_grid(c.scenery, cell, config=c.config)
+        # goals come from the spawn table; one closer than twice `arrive` would be a bonus for nothing
+        self._goals = modules.Goals(geometries, c, self.grid, candidates=candidates, min_distance=2*self.arrive,
+                                    table=self._respawner._spawns.positions)
+        self.action_space = self._mover.space
+        self.obs_space = dotdict.dotdict(rgb=self._rgb.space, d=self._depth.space, goal=self._goals.space)
+
+        self._over = c.agent_full(True)                 # who starts over at the next step
+        self._episodes = torch.zeros((c.n_envs, c.n_agents), dtype=torch.long, device=c.device)
+        self._distance = torch.full((c.n_envs, c.n_agents), float('inf'), device=c.device)
+
+    def _respawn(self, over):
+        """The respawn of the agents marked, as a request the physics launch carries out after its step: each agent walks its
+        own (randomly ordered) spawn table, one entry per episode."""
+        spawns = self._respawner._spawns
+        choices = self._episodes % spawns.angles.shape[2]
+        request = dict(mask=over.contiguous(), choices=choices.contiguous(), positions=spawns.positions, angles=spawns.angles, after=True)
+        self._episodes += over
+        return request
+
+    def _world(self, reset):
+        self._goals(reset)
+        now = self._goals.distances()
+        # An agent can squeeze into a spot the grid has no free cell near (a gap between a pillar and a wall that is wider than
+        # the agent and narrower than the grid can see): from there no distance is defined. It counts as stranded from then on -
+        # no reward, and a new episode at the next step.
+        self._goals.stranded |= ~torch.isfinite(now)
+        reward, ended = books(self._distance, now, reset, self._goals.stranded, self.arrive, self.bonus)
+        self._distance.copy_(now)
+        self._over.copy_(self._lifespans(ended))
+        frame = modules.render(self.core, observers=(self._rgb, self._depth), fields=())
+        obs = arrdict.arrdict(rgb=self._rgb(frame), d=self._depth(frame), goal=self._goals.observation())
+        return arrdict.arrdict(obs=obs, reset=reset.any(-1), reward=reward)
+
+    @torch.no_grad()
+    def reset(self):
+        everyone = self.core.agent_full(True)
+        modules._respawn(self.core.agents, {**self._respawn(everyone), 'after': False})
+        return self._world(everyone)
+
+    @torch.no_grad()
+    def step(self, decision):
+        """Moves the agents; those whose episode ended at the last step start a new one instead (a new spot, a new goal) and earn
+        nothing for this frame. ``reset`` (n_env,): an agent of the env started over; ``reward`` (n_env, n_agent)."""
+        over = self._over.clone()
+        self._mover(decision, respawn=self._respawn(over))
+        return self._world(over)
+
+    def state(self, e=0):
+        return arrdict.arrdict(core=self.core.state(e), rgb=self._rgb.state(e), d=self._depth.state(e), goals=self._goals.state(e),
+                               distance=self._distance[e].clone(), lifespan=self._lifespans.state(e))

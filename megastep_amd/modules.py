@@ -407,3 +407,78 @@ class RandomLifespans:
 
     def state(self, e):
         return arrdict.arrdict(lifespan=self._lifespans[e], max_lifespans=self._max_lifespans[e]).clone()
+
+
+class Goals:
+
+    def __init__(self, geometries, core, grid, candidates=8, min_distance=0., table=None, n_spawns=100):
+        """A goal per agent, and how far the agent has to walk to it (no counterpart in the reference).
+
+        ``grid`` is the scenery's :func:`cuda.nav_grid`. Goals come from a table of free points per agent - ``table``
+        (n_env, n_agent, S, 2), for instance a :class:`RandomSpawns`' own; default: ``n_spawns`` points drawn as it draws
+        them. A floorplan is not one connected space (closets without a door, pillars), so a goal picked blindly is, for a
+        fair share of agents, one that cannot be reached. The rule here: the agent's next ``candidates`` table entries (each
+        agent walks its table cyclically, ``candidates`` entries per draw - the table is in random order, and no random
+        numbers are drawn per step) are measured from where the agent stands, and the first whose walking distance is finite
+        and at least ``min_distance`` is the goal. An agent that found none is flagged in :attr:`stranded` and its goal is the
+        spot it stands on. Nothing waits for the host: a draw is two masked :func:`cuda.distance_fields` launches (the field
+        round the agent, to measure the candidates; the field of the goal) and a :meth:`cuda.DistanceFields.at`."""
+        self.core = core
+        self.grid = grid
+        self.candidates, self.min_distance = int(candidates), float(min_distance)
+        if table is None:
+            table = torch.as_tensor(random_empty_positions(geometries, core.n_agents, n_spawns), dtype=torch.float32)
+        self._table = table.to(core.device).float().contiguous()
+        n, a, s = self._table.shape[:3]
+        if (n, a) != (core.n_envs, core.n_agents) or self._table.shape[3:] != (2,):
+            raise RuntimeError(f'table must be ({core.n_envs}, {core.n_agents}, S, 2); got {tuple(self._table.shape)}')
+        self.space = spaces.MultiVector(core.n_agents, 3)
+        self.stranded = core.agent_full(False)
+        self._draws = torch.zeros((n, a), dtype=torch.long, device=core.device)
+        self._step = (s//2 + torch.arange(self.candidates, device=core.device))[None, None, :]
+        self._agent = torch.arange(a, dtype=torch.int32, device=core.device)[None, :, None].expand(n, a, self.candidates).reshape(n, -1).contiguous()
+        self._around = self._fields = None
+
+    #: (n_env, n_agent, 2): every agent's goal
+    goals = property(lambda self: self._fields.goals)
+    #: the :class:`cuda.DistanceFields` of the goals
+    fields = property(lambda self: self._fields)
+
+    @staticmethod
+    def choose(distances, candidates, here, min_distance=0.):
+        """The rule: ``distances`` (N, A, K) from each agent to its K ``candidates`` (N, A, K, 2) -> ((N, A, 2) goals: the first
+        candidate whose distance is finite and at least ``min_distance``; (N, A) bool: there was none, and the goal is ``here``)."""
+        good = torch.isfinite(distances) & (distances >= min_distance)
+        first = good.int().argmax(-1)                                   # (the first of the largest: the first True)
+        stranded = ~good.any(-1)
+        goal = candidates.gather(2, first[..., None, None].expand(-1, -1, 1, 2)).squeeze(2)
+        return torch.where(stranded[..., None], here, goal), stranded
+
+    def __call__(self, reset):
+        """Agents marked in the (n_env, n_agent) bool ``reset`` get a new goal, reachable from where they stand now."""
+        n, a, s = self._table.shape[:3]
+        reset = reset.contiguous()
+        here = self.core.agents.positions
+        index = (self._draws[..., None]*self.candidates + self._step) % s
+        self._draws += reset
+        candidates = self._table.gather(2, index[..., None].expand(-1, -1, -1, 2))
+        self._around = cuda.distance_fields(self.grid, here, mask=reset, out=self._around)
+        distances = self._around.at(candidates.reshape(n, a*self.candidates, 2), goal=self._agent).reshape(n, a, self.candidates)
+        goal, stranded = self.choose(distances, candidates, here, self.min_distance)
+        torch.where(reset, stranded, self.stranded, out=self.stranded)
+        self._fields = cuda.distance_fields(self.grid, goal.contiguous(), mask=reset, out=self._fields)
+        return self.goals
+
+    def distances(self):
+        """(n_env, n_agent): how far every agent has to walk to its goal now; +inf where no path exists."""
+        return self._fields.at(self.core.agents.positions)
+
+    def observation(self):
+        """(n_env, n_agent, 3): the goal's offset in the agent's frame, and its length (the straight line, which is what a
+        compass knows: the walking distance is the env's to reward, not the agent's to see)."""
+        agents = self.core.agents
+        offset = self.goals - agents.positions
+        return torch.cat([to_local_frame(agents.angles, offset), offset.norm(dim=-1, keepdim=True)], -1)
+
+    def state(self, e=0):
+        return arrdict.arrdict(goals=self.goals[e], stranded=self.stranded[e]).clone()

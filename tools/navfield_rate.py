@@ -1,0 +1,199 @@
+"""What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
+
+    python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
+                                  [--only fields|query|torch|envs]
+
+The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
+from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
+  (a) cuda.distance_fields (ms_nav_fields) for all the goals, and the pass count of the slowest field;
+  (b) one DistanceFields.at (ms_nav_query) of one point an env;
+  (c) PointGoal(envs).step eager and replayed as a HIP graph, next to Explorer(envs).step;
+  (t) the yardstick for (a): the same fields by torch - the grids padded to the largest plan, (N, H, W) tensors, eight
+      shifted minimums a sweep, swept until nothing changes (checked every 16 sweeps: each check is a host round trip).  It
+      runs on the first `--torch-envs` envs and is scaled to `--envs`; its fields are compared with the kernel's as bits -
+      a third statement of the rule beside tests/test_navfield_host.nav_rule and the kernel.
+`--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
+--only fields`).  Needs a GPU: there is no CPU fall-back.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
+
+
+def timed(fn, repeats, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b)*1e-3)
+    times = np.array(times)
+    return float(np.median(times)), float(times.min()), float(times.max())
+
+
+def torch_fields(grid, goals, envs):
+    """The fields of goal 0 of the first `envs` envs by tensor ops, as (envs, H, W) padded to the largest grid."""
+    geom = grid._host_geom[:envs]
+    H, W = int(geom[:, 3].max()) + 2, int(geom[:, 2].max()) + 2
+    dev = grid.free.device
+    c = torch.tensor(grid.cell, dtype=torch.float32, device=dev)
+    ws, wd = c, c*torch.tensor(1.41421356, dtype=torch.float32, device=dev)
+    free = torch.zeros((envs, H, W), dtype=torch.bool, device=dev)
+    for e in range(envs):
+        s, ny, nx = grid.cells(e)
+        free[e, 1:ny + 1, 1:nx + 1] = grid.free[s:s + ny*nx].reshape(ny, nx).bool()
+    inf = torch.tensor(float('inf'), device=dev)
+
+    def shifted(t, di, dj, fill):
+        out = torch.full_like(t, fill)
+        out[:, max(di, 0):H + min(di, 0), max(dj, 0):W + min(dj, 0)] = t[:, max(-di, 0):H + min(-di, 0), max(-dj, 0):W + min(-dj, 0)]
+        return out
+
+    open_ = {}
+    for di in (-1, 1):
+        for dj in (-1, 1):                                              # a diagonal step from (i - di, j - dj) into (i, j) cuts no corner
+            open_[di, dj] = free & shifted(free, di, dj, False) & shifted(free, di, 0, False) & shifted(free, 0, dj, False)
+
+    def run():
+        D = torch.full((envs, H, W), float('inf'), device=dev)
+        # the anchors, as the contract forms them
+        g = goals[:envs, 0]
+        jx0, iy0 = (torch.as_tensor(geom[:, k].astype(np.int64), device=dev) for k in (0, 1))
+        j0 = torch.floor(g[:, 0]/c - .5).long() - jx0
+        i0 = torch.floor(g[:, 1]/c - .5).long() - iy0
+        e = torch.arange(envs, device=dev)
+        for a in (0, 1):
+            for b in (0, 1):
+                i, j = i0 + a, j0 + b
+                ok = (i >= 0) & (i < H - 2) & (j >= 0) & (j < W - 2)
+                ic, jc = i.clamp(0, H - 3), j.clamp(0, W - 3)
+                dx = g[:, 0] - ((jx0 + jc).float() + .5)*c
+                dy = g[:, 1] - ((iy0 + ic).float() + .5)*c
+                leg = torch.sqrt(dx*dx + dy*dy)
+                ok = ok & free[e, ic + 1, jc + 1]
+                D[e, ic + 1, jc + 1] = torch.where(ok, leg, D[e, ic + 1, jc + 1])
+        sweeps = 0
+        while True:
+            before = D
+            for _ in range(16):
+                new = D
+                for di, dj in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+                    new = torch.minimum(new, shifted(D, di, dj, float('inf')) + ws)
+                for (di, dj), ok in open_.items():
+                    new = torch.minimum(new, torch.where(ok, shifted(D, di, dj, float('inf')) + wd, inf))
+                D = torch.where(free, new, inf)
+                sweeps += 1
+            if torch.equal(D, before):
+                return D, sweeps
+    return run
+
+
+def env_rates(env, n, steps, warm):
+    from megastep_amd import arrdict
+    A = env.action_space.shape[0]
+    env.reset()
+    actions = torch.randint(0, 7, (n, A), device='cuda')
+    decision = arrdict.arrdict(actions=actions)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warm):
+            env.step(decision)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(steps):
+        env.step(decision)
+    torch.cuda.synchronize()
+    eager = (time.perf_counter() - t)/steps
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        env.step(decision)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(steps):
+        actions.random_(0, 7)
+        g.replay()
+    torch.cuda.synchronize()
+    return eager, (time.perf_counter() - t)/steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--envs', type=int, default=4096)
+    ap.add_argument('--distinct', type=int, default=1024)
+    ap.add_argument('--repeats', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--torch-envs', type=int, default=256)
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs'))
+    ap.add_argument('--json')
+    args = ap.parse_args()
+    from megastep_amd import core, cubicasa, cuda, modules, scene
+    from megastep_amd.demo import Explorer, PointGoal
+
+    np.random.seed(0); torch.manual_seed(0)
+    pool = cubicasa.sample(args.distinct, split='all', n_unique=args.distinct, workers=16, context='subprocess')
+    geoms = [pool[i % len(pool)] for i in range(args.envs)]
+    out = dict(envs=args.envs, distinct=len(pool))
+    want = lambda part: args.only in (None, part)
+
+    if want('fields') or want('query') or want('torch'):
+        sc = scene.scenery(geoms, 1, device='cuda', bake=False)
+        c = core.Core(sc, res=64)
+        grid = cuda.nav_grid(sc)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        goals, points = table[:, :, 0].contiguous(), table[:, :, 1].contiguous()
+        fields = cuda.distance_fields(grid, goals, passes=True)
+        cells = np.diff(grid._host_starts)
+        out.update(cells_total=int(grid.n_cells), cells_largest=int(cells.max()), cells_median=int(np.median(cells)))
+        if want('fields'):
+            med, lo, hi = timed(lambda: fields.update(), args.repeats, args.warmup)
+            out['fields'] = dict(seconds=med, min=lo, max=hi, goals=args.envs, passes_most=int(fields.passes.max()),
+                                 passes_median=int(fields.passes.median()), finite_share=float(torch.isfinite(fields.values).float().mean()))
+            print(f"(a) distance_fields, {args.envs} goals: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; most passes {out['fields']['passes_most']}")
+        if want('query'):
+            med, lo, hi = timed(lambda: fields.at(points), 5*args.repeats, args.warmup)
+            out['query'] = dict(seconds=med, min=lo, max=hi, points=args.envs)
+            print(f'(b) at, {args.envs} x 1 points: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        if want('torch'):
+            k = min(args.torch_envs, args.envs)
+            run = torch_fields(grid, goals, k)
+            D, sweeps = run()
+            same = all(torch.equal(D[e, 1:grid.cells(e)[1] + 1, 1:grid.cells(e)[2] + 1].view(torch.int32), fields.image(e, 0).view(torch.int32))
+                       for e in range(k))
+            med, lo, hi = timed(lambda: run(), max(args.repeats//3, 2), 1)
+            out['torch'] = dict(envs=k, seconds=med, scaled_seconds=med*args.envs/k, sweeps=sweeps, equal_bits=bool(same))
+            print(f'(t) torch sweeps, {k} goals: {med*1e3:.1f} ms, {sweeps} sweeps -> {med*args.envs/k*1e3:.1f} ms for {args.envs}; equal bits: {same}')
+        del sc, c, grid, fields
+        torch.cuda.empty_cache()
+
+    if want('envs'):
+        for name, make in (('PointGoal', lambda: PointGoal(args.envs, geometries=geoms)), ('Explorer', lambda: Explorer(args.envs, geometries=geoms))):
+            env = make()
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[name] = dict(eager_seconds=eager, graph_seconds=graphed)
+            print(f'(c) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
