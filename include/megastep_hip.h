@@ -162,6 +162,19 @@ typedef struct MsAgents {
      * (an agent turned by the caller in between).  Same function, same bits either way - it saves ms_render a launch.
      * Must start as NaNs (or any value no angle takes); pass NULL to ms_render to get its self-contained path. */
     float* headings;
+    /* Optional fan schedule (NULL = none; no counterpart in the reference), (2, N, A) int: [costs | order].  Where every agent
+     * is ONE wave of ms_render - at most 64 rays, one 64-ray group a wave, two launches a step - the wave leaves a small
+     * integer in costs[n A + a]: an estimate of how long it lived, from what it counted on its way (pair windows, list
+     * length, a ray on an agent, lights left open, rays redone by the literal fold).  The next ms_step_physics / ms_physics
+     * sorts each XCD's run of fans by it, slowest first, into order[slot] = fan - a few extra waves of its own launch - and
+     * the ms_render behind it starts its waves in that order: a frame's slow fans are, by and large, the last frame's, and
+     * a launch that starts them first does not end waiting for them.  Which fan a wave is changes nothing it computes:
+     * same bits with and without.  `costs` may hold anything (every value is a class; the sort writes a permutation of
+     * each run whatever it reads); `order` must start as the identity, 0 .. N A - 1, so that a render before any physics
+     * call is served.  A table sorted for one (N, A) must not be handed to a call with another.
+     * (The field is the struct's last and MS_ABI_VERSION stays 17: a caller built against the header without it must be
+     * rebuilt - the library reads the field of every MsAgents it is given.) */
+    int* schedule;
 } MsAgents;
 
 /* Replaces `Render` (common.h:216-222). Caller-allocated outputs.  With a light grid in the scenery any of the

@@ -40,6 +40,16 @@ int ms_debug_last_step_fused(void);
 long long ms_host_render_plan(int n_envs, int n_agents, int res, int slots, int pinned_groups, float tail_rounds, int tail_envs, int* groups);
 int ms_host_render_block(int n_envs, int n_agents, int res, int slots, int pinned_groups, float tail_rounds, int tail_envs, long long block, int* out4);
 int ms_host_physics_pack(int n_envs, int n_agents, int gridded, int pinned);
+/* The fan schedule (MsAgents.schedule): 0 = ms_step_physics sorts nothing and ms_render deals its waves in fan order whether the
+ * agents carry a schedule or not, 1 = they use it where the shape qualifies.  Per calling thread; A/B runs and tests - either
+ * setting produces the same bits. */
+int ms_debug_render_order(int on);
+/* Host mirror of the sort ms_step_physics' extra waves do, for CPU tests: order[slot] = fan for the n_fans = N A one-fan blocks
+ * of a render launch, from costs[fan] (any 32-bit pattern: a cost's class is min((unsigned)cost, 63)).  XCD x's run of slots -
+ * [x q + min(x, r), ...) with q = n_fans / 8, r = n_fans % 8, the first r runs one longer: render_block's - holds a permutation
+ * of the same run of fans, classes descending.  (Fans of one class may come in another order on the device.)  Returns the
+ * number of sort blocks the launch would carry. */
+int ms_host_order_fans(int n_fans, const int* costs, int* order);
 /* A launch of waves of several groups ends with waves of one group for its last envs; their share, in rounds of the machine's
  * wave slots' worth of the wide waves' work (< 0: ms_render's own, half a round; 0: none; large: every env), or, if
  * envs >= 0, that many envs exactly.  Per calling thread; A/B runs and tests - every setting produces the same bits. */

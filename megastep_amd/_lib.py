@@ -47,7 +47,7 @@ class MsWallGridParent(C.Structure):
 
 class MsAgents(C.Structure):
     _fields_ = [('angles', C.c_void_p), ('positions', C.c_void_p), ('angvelocity', C.c_void_p), ('velocity', C.c_void_p),
-                ('headings', C.c_void_p)]
+                ('headings', C.c_void_p), ('schedule', C.c_void_p)]
 
 
 class MsMovement(C.Structure):
@@ -107,7 +107,7 @@ class MsNavQuery(C.Structure):
 
 
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare
-SYMBOLS = ('ms_host_ray_interval_wide', 'ms_debug_ray_groups', 'ms_debug_last_render_groups', 'ms_debug_last_step_fused', 'ms_step_render', 'ms_move_step_render', 'ms_debug_ray_group_tail', 'ms_debug_physics_pack', 'ms_host_render_plan', 'ms_host_render_block', 'ms_host_physics_pack', 'ms_debug_pair_telemetry', 'ms_test_arithmetic', 'ms_abi_version', 'ms_strerror', 'ms_last_hip_error', 'ms_device_count', 'ms_bake', 'ms_physics', 'ms_move_physics',
+SYMBOLS = ('ms_host_ray_interval_wide', 'ms_debug_render_order', 'ms_host_order_fans', 'ms_debug_ray_groups', 'ms_debug_last_render_groups', 'ms_debug_last_step_fused', 'ms_step_render', 'ms_move_step_render', 'ms_debug_ray_group_tail', 'ms_debug_physics_pack', 'ms_host_render_plan', 'ms_host_render_block', 'ms_host_physics_pack', 'ms_debug_pair_telemetry', 'ms_test_arithmetic', 'ms_abi_version', 'ms_strerror', 'ms_last_hip_error', 'ms_device_count', 'ms_bake', 'ms_physics', 'ms_move_physics',
            'ms_step_physics', 'ms_deathmatch_shoot', 'ms_explorer_books',
            'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_nav_free', 'ms_nav_fields', 'ms_nav_query', 'ms_debug_overhead_cull', 'ms_host_overhead_keeps', 'ms_host_sincospi', 'ms_host_bake_point_bin', 'ms_host_bake_wall_bins',
            'ms_wallgrid_scan', 'ms_wallgrid_fill', 'ms_host_wall_hidden', 'ms_host_wall_sectors', 'ms_host_wallgrid_cell', 'ms_host_wall_arc',
@@ -245,6 +245,10 @@ def lib():
         handle.ms_host_physics_pack.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         handle.ms_host_physics_pack.restype = C.c_int
         handle.ms_debug_ray_group_tail.restype = C.c_int
+        handle.ms_debug_render_order.argtypes = [C.c_int]
+        handle.ms_debug_render_order.restype = C.c_int
+        handle.ms_host_order_fans.argtypes = [C.c_int, _i32p, _i32p]
+        handle.ms_host_order_fans.restype = C.c_int
         handle.ms_debug_pair_telemetry.argtypes = [C.c_int]
         handle.ms_debug_pair_telemetry.restype = C.c_int
         handle.ms_test_arithmetic.argtypes = [C.c_void_p]*7 + [C.c_longlong, C.c_void_p]

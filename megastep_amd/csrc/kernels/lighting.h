@@ -49,7 +49,7 @@ struct LightScene {                   // what grid_light_intensity reads of an M
 // 64 lights, in the lights' order - the loop below, which everyone else passes once: per group every wall is met through
 // the corridor sweep, and the reference's running sum (kernels.cu:261-264) carries over from group to group.
 __device__ inline float grid_light_intensity(
-        const LightScene sc, const MsAgents& ag, const int n, const int lane, const bool dynamic, const int nearest_idx,
+        const LightScene sc, const AgentsK& ag, const int n, const int lane, const bool dynamic, const int nearest_idx,
         const float cx_l, const float cy_l, const int L, const float4* __restrict__ ln,
         LightPair* s_pair, unsigned* s_shadow, unsigned& telemetry, [[maybe_unused]] unsigned* clk = nullptr) {
 #if MS_PROBE

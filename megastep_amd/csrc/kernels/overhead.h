@@ -96,7 +96,7 @@ __device__ inline void ov_fold(const float x, const float y, const float4 L, con
     if ((d2 <= h2) & ((d2 < b.d2) | ((d2 == b.d2) & (l < b.idx)))) { b.d2 = d2; b.idx = l; b.t = t; }
 }
 
-__global__ __launch_bounds__(WG) void overhead_kernel(const MsScenery sc, const MsAgents ag, const OvArgs a) {
+__global__ __launch_bounds__(WG) void overhead_kernel(const MsScenery sc, const AgentsK ag, const OvArgs a) {
     __shared__ float4 s_rows[OV_CHUNK];
     __shared__ int s_idx[OV_CHUNK];
     __shared__ int s_wave[WAVES];

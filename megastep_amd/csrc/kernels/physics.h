@@ -62,6 +62,71 @@ __device__ inline float3 imu_reading(const MsStepExtras& ex, const float ang, co
     return make_float3(w*ex.imu_ang_scale, (c_*v.x + s_*v.y)*ex.imu_speed_scale, (-s_*v.x + c_*v.y)*ex.imu_speed_scale);
 }
 
+// ------------------------------------------------------------------------------------------------
+// the fan schedule (MsAgents.schedule): last frame's render costs sorted into this frame's starting order
+// ------------------------------------------------------------------------------------------------
+// A render launch of one-fan blocks (render_block, ng == 1, one 64-ray group an agent) gives XCD x the contiguous run of fans
+// [x q + min(x, r), + q + (x < r)), q = n_fans/8, r = n_fans % 8, in the order of its blocks.  The sort stays inside a run - the
+// env -> L2 placement is kept - and is a counting sort by cost class, slowest class first, done by a few waves a run, in
+// front of the physics launch's own blocks (physics_kernel's first lines).  A run of more than FAN_SORT_MAX fans is shared by K
+// waves: wave k sorts a contiguous K-th of the run's fans into the slots k, k + K, k + 2K ... of the run, so that the run as a
+// whole is K sorted lists dealt round-robin - slowest first again, to within K.  Every fan gets its class's first rank plus an
+// LDS atomic count: a permutation of the run whatever the costs hold.
+constexpr int FAN_CLASSES = 64;        // a cost's class: min((unsigned)cost, 63) - a quarter of a microsecond each (render.h: fan_cost)
+constexpr int FAN_SORT_EACH = 8;       // fans a lane of a sort wave takes: their costs are ONE batch of loads, their classes stay in registers
+constexpr int FAN_SORT_MAX = FAN_SORT_EACH*WAVE;   // fans one sort wave takes (the headline's runs of 2048: four waves each, 32 in all)
+struct FanSort { int* schedule; int n_fans, per_run, n_blocks; };   // costs | order; sort waves per run (K) and in all (8 K, 0: none)
+__host__ __device__ inline int fan_class(const int cost) { return (unsigned)cost < (unsigned)(FAN_CLASSES - 1) ? cost : FAN_CLASSES - 1; }
+__host__ inline int fan_sort_per_run(const int n_fans) { return ((n_fans >> 3) + ((n_fans & 7) ? 1 : 0) + FAN_SORT_MAX - 1)/FAN_SORT_MAX; }
+// sort wave `block` of 8 K: the fans it takes, first_fan .. first_fan + count - 1, and where rank j of them goes: slot first_slot + K j
+__host__ __device__ inline void fan_sort_part(const int n_fans, const int K, const int block, int& first_fan, int& count, int& first_slot) {
+    const int xcd = block/K, k = block - xcd*K;
+    const int q8 = n_fans >> 3, r8 = n_fans & 7;
+    const int run = xcd*q8 + (xcd < r8 ? xcd : r8), len = q8 + (xcd < r8 ? 1 : 0);
+    const int lo = len/K, rem = len - lo*K;
+    count = lo + (k < rem ? 1 : 0);                                      // (the slots k, k + K, ... below len: as many)
+    first_fan = run + k*lo + (k < rem ? k : rem);
+    first_slot = run + k;
+}
+// (One wave for a whole run of 2048, its 32 loads a lane one after the other in a loop with the LDS atomics, took 19 us - longer
+// than the whole physics launch; a batch of eight loads in flight a lane and four waves a run: see DESIGN 3.6.)
+__device__ inline void fan_sort_wave(const FanSort fs, const int block, const int lane, int* s_cnt) {
+    int first_fan, count, first_slot;
+    fan_sort_part(fs.n_fans, fs.per_run, block, first_fan, count, first_slot);
+    const int* __restrict__ costs = fs.schedule;
+    int* __restrict__ order = fs.schedule + fs.n_fans;
+    s_cnt[lane] = 0;
+    int cls[FAN_SORT_EACH];
+    #pragma unroll
+    for (int j = 0; j < FAN_SORT_EACH; j++) {                            // (unguarded: a fan of the table read again - see count below)
+        const int i = j*WAVE + lane;
+        cls[j] = fan_class(costs[first_fan + (i < count ? i : 0)]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    #pragma unroll
+    for (int j = 0; j < FAN_SORT_EACH; j++) if (j*WAVE + lane < count) atomicAdd(&s_cnt[cls[j]], 1);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // lane j looks after class 63 - j: the slowest class takes the first ranks
+    const int mine = s_cnt[FAN_CLASSES - 1 - lane];
+    const int incl = wave_scan_add(mine);
+    __builtin_amdgcn_wave_barrier();
+    s_cnt[FAN_CLASSES - 1 - lane] = incl - mine;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    #pragma unroll
+    for (int j = 0; j < FAN_SORT_EACH; j++) {
+        const int i = j*WAVE + lane;
+        if (i < count) {
+            const int rank = atomicAdd(&s_cnt[cls[j]], 1);               // (< count: the classes' counts add up to it)
+            order[first_slot + fs.per_run*rank] = first_fan + i;
+        }
+    }
+}
+
 // MOVE = 1: the movement modules' velocity update runs first (MsMovement), on the state this wave is loading anyway
 // EXTRA = 1: the environment's bookkeeping (MsStepExtras: lifespans, respawns, IMU) runs in the same launch
 // PACK = 1: a wave takes `pack_envs` consecutive envs side by side (ms_step_physics: worlds of several rounds of waves with a
@@ -71,15 +136,32 @@ __device__ inline float3 imu_reading(const MsStepExtras& ex, const float ang, co
 //   who can run into whom, whose cell lists, which env falls back to meeting all its walls - looks at lane / n_agents.
 template <int MOVE, int EXTRA, int PACK = 0>
 __global__ __launch_bounds__(WAVE) void physics_kernel(
-        const MsScenery sc, const MsAgents ag, float* __restrict__ progress,
-        const float agent_radius, const float fps, const MsMovement mv, const MsStepExtras ex, const int pack_envs, const Divisor by_a) {
-    PROBE_INIT
+        const MsScenery sc, const AgentsK ag, float* __restrict__ progress,
+        const float agent_radius, const float fps, const MsMovement mv, const MsStepExtras ex, const int pack_envs, const Divisor by_a,
+        const FanSort fs) {
     extern __shared__ float4 s_dyn[];            // per agent: (p, v/fps) | reach box | reach^2 | progress bits
     __shared__ float4 s_wall[PHYS_PAIRS];        // walls near ...
     __shared__ int s_tag[PHYS_PAIRS];            // ... this agent
+    static_assert(PHYS_PAIRS >= FAN_CLASSES, "a sort wave's counts fit a physics wave's LDS");
+    // (the fan schedule's sort waves: the launch's first blocks, so that they start at once and are done long before its last wave)
+    // (What a physics wave's first loads need of the kernel's arguments is asked for HERE, with the sort waves' count: hipcc gathers
+    // argument loads to the top of a kernel only as far as its first branch, and behind this one they were a second round trip
+    // to the scalar cache for every wave - physics 8.64 -> 8.71 us at the headline shape.)
+    // (Tied to the count the branch asks, and not volatile: a volatile statement counts as a store, and behind one hipcc reads the
+    // env's rows with vector loads instead of scalar ones.)
+    int n_sort = fs.n_blocks;
+    asm("" : "+s"(n_sort) : "s"(sc.n_envs), "s"(sc.n_agents), "s"(sc.n_model), "s"(sc.wg_geom), "s"(sc.wg_starts), "s"(sc.wg_cells),
+                            "s"(sc.lines_vals), "s"(sc.lines_widths), "s"(sc.lines_starts), "s"(ag.positions), "s"(ag.velocity),
+                            "s"(pack_envs), "s"(by_a.mul), "s"(by_a.sh1), "s"(by_a.sh2));
+    if ((int)blockIdx.x < n_sort) {
+        fan_sort_wave(fs, blockIdx.x, threadIdx.x, s_tag);
+        return;
+    }
+    PROBE_INIT
     const int A1 = sc.n_agents, AF = sc.n_agents*sc.n_model;            // agents per env
     const int lane = threadIdx.x;
-    const int n = PACK ? blockIdx.x*pack_envs : blockIdx.x;              // the host launches one wave per env (PACK: per pack_envs envs; n: the first)
+    const int blk = blockIdx.x - n_sort;
+    const int n = PACK ? blk*pack_envs : blk;                            // the host launches one wave per env (PACK: per pack_envs envs; n: the first)
     const int E = PACK ? min(pack_envs, sc.n_envs - n) : 1;
     const int A = PACK ? A1*E : A1;                                      // the wave's agents: rows nA .. nA + A - 1 of every (N, A) array
     const int nA = n*A1;

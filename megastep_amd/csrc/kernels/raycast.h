@@ -46,7 +46,7 @@ __device__ inline void ray_fold(const P2 p, const P2 ru, const float near_s, con
 // lists of all its rays' cells together are shorter than the env's walls; else those rays meet every wall, as do the rays
 // that cannot take the grid and every ray of a wave that straddles two envs (per lane then).  Rays cast from everywhere at once - a wave of 64 cells - are served by the all-walls
 // sweep: a list walk per ray would be 64 walks of scattered loads.
-__global__ __launch_bounds__(WG) void raycast_kernel(const MsScenery sc, const MsAgents ag, const MsRaycast q, const int with_agents,
+__global__ __launch_bounds__(WG) void raycast_kernel(const MsScenery sc, const AgentsK ag, const MsRaycast q, const int with_agents,
                                                      const int gridded, const int n_total) {
     const int i_raw = blockIdx.x*WG + threadIdx.x;
     const bool live = i_raw < n_total;

@@ -51,7 +51,7 @@ __device__ __attribute__((noinline)) float4 drawn_line_of(const float* angles, c
     const float2 p = reinterpret_cast<const float2*>(positions)[n*n_agents + a];
     return drawn_row(s, c, p.x, p.y, reinterpret_cast<const float4*>(model)[m]);
 }
-__device__ inline float4 drawn_line(const MsScenery& sc, const MsAgents& ag, int n, int l) {
+__device__ inline float4 drawn_line(const MsScenery& sc, const AgentsK& ag, int n, int l) {
     return drawn_line_of(ag.angles, ag.positions, sc.model, sc.n_agents, sc.n_model, n, l);
 }
 
@@ -121,6 +121,11 @@ struct RenderConstsStep : RenderConsts {
     MsMovement mv;                 // ms_step_physics' optional prologue and bookkeeping, as it takes them (all-NULL structs: none)
     MsStepExtras ex;
 };
+// ... and what the instantiations of one ray group a wave take on top (NG = 1, STEP = 0: where an agent can be ONE fan), again as a
+// type of its own: the fan schedule (MsAgents.schedule: costs | order), NULL unless ms_render found the call to qualify.
+struct RenderConstsOrder : RenderConsts {
+    int* schedule;
+};
 // Which of MsRender's optional outputs are there, as bits - for the COLOURLESS instantiations, which ask a scalar register the
 // wave has had since its first instruction whether an output is wanted and only fetch a pointer from the kernel-argument segment
 // when it is: asked of the pointers themselves every check was a scalar load and a wait of its own, per group of rays, for
@@ -155,15 +160,24 @@ __global__ __launch_bounds__(WG) void arithmetic_test_kernel(const float* __rest
 //     draining for most of one such life; the short waves are what the slots that come free take up then (render_plan sizes the
 //     second part: about half a round of the long ones' work).  Every XCD has as many blocks as the one with the most envs
 //     needs: one with an env fewer lets its last blocks go.
+//   ng == 1 with a fan schedule (MsAgents.schedule; render_kernel, ORDERED): the slot is worked out as above, and the fan is what
+//     the table names for it - physics.h's sort waves permute fans inside an XCD's run only, so the placement stands.
+__host__ __device__ inline int render_slot(const int b, const int n_blocks) {
+    const int xcd = b & 7, ix = b >> 3;
+    const int q8 = n_blocks >> 3, r8 = n_blocks & 7;
+    return xcd*q8 + (xcd < r8 ? xcd : r8) + ix;
+}
+__host__ __device__ inline void render_fan(const int fan, const int A, const int R, const RenderConsts& rc, int& n, int& a, int& r0, int& span) {
+    const int G = (R + WAVE - 1)/WAVE, F = A*G;       // g: which run of 64 rays of the agent's this wave casts
+    n = div_by(fan, rc.by_f); const int rem = fan - n*F; a = div_by(rem, rc.by_g); r0 = (rem - a*G)*WAVE; span = WAVE;
+}
 __host__ __device__ inline bool render_block(const int b, const int n_blocks, const int A, const int R, const int ng, const RenderConsts& rc,
                                              int& n, int& a, int& r0, int& span, int& fan) {
     const int xcd = b & 7, ix = b >> 3;
     fan = b;                                                             // (ng == 1: the run's number, env-major, that dynlight_kernel's queue holds)
     if (ng == 1) {
-        const int q8 = n_blocks >> 3, r8 = n_blocks & 7;
-        fan = xcd*q8 + (xcd < r8 ? xcd : r8) + ix;
-        const int G = (R + WAVE - 1)/WAVE, F = A*G;   // g: which run of 64 rays of the agent's this wave casts
-        n = div_by(fan, rc.by_f); const int rem = fan - n*F; a = div_by(rem, rc.by_g); r0 = (rem - a*G)*WAVE; span = WAVE;
+        fan = render_slot(b, n_blocks);
+        render_fan(fan, A, R, rc, n, a, r0, span);
         return true;
     }
     const int NR = ng*WAVE;
@@ -184,7 +198,7 @@ __host__ __device__ inline bool render_block(const int b, const int n_blocks, co
     return true;
 }
 
-__global__ __launch_bounds__(WG) void render_prep_kernel(const MsAgents ag, int* __restrict__ workspace,
+__global__ __launch_bounds__(WG) void render_prep_kernel(const AgentsK ag, int* __restrict__ workspace,
                                                          const int n_agents_total, const int headings_at) {
     const int i = blockIdx.x*WG + threadIdx.x;
     if (i == 0) { workspace[0] = 0; workspace[1] = 0; workspace[2] = 0; workspace[3] = 0; workspace[4] = 0; }
@@ -201,9 +215,11 @@ __global__ __launch_bounds__(WG) void render_prep_kernel(const MsAgents ag, int*
 // vector-register lanes, which costs two memory round trips (a parked value has to have arrived) and ~40 instructions
 // per wave before the first ray is cast.  The asm statement keeps the loads from being hoisted back up.
 
-struct RenderArgs { MsScenery sc; MsAgents ag; MsRender out; float agent_radius, half_screen; int R, n_fans; RenderConsts rc; };
+struct RenderArgs { MsScenery sc; AgentsK ag; MsRender out; float agent_radius, half_screen; int R, n_fans; RenderConsts rc; };
 static_assert(offsetof(RenderArgs, ag) == sizeof(MsScenery) && offsetof(RenderArgs, n_fans) + 4 == offsetof(RenderArgs, rc),
               "RenderArgs must mirror render_kernel's parameters");
+struct RenderArgsOrder { MsScenery sc; AgentsK ag; MsRender out; float agent_radius, half_screen; int R, n_fans; RenderConstsOrder rc; };
+// (... of the instantiations that take the fan schedule behind their constants: the same members up to `rc`, so a LateArgs reads both)
 typedef const RenderArgs __attribute__((address_space(4)))* LateArgs;
 __device__ inline LateArgs late_args() {
     LateArgs p = (LateArgs)__builtin_amdgcn_kernarg_segment_ptr();
@@ -362,10 +378,11 @@ __host__ __device__ inline void ray_interval(float xa, float ya, float xb, float
 #endif
 template <int OBS, int SHADE = 1, int NG = 1, int STEP = 0>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? MS_WAVES_WIDE : MS_WAVES, NG > 1 ? MS_WAVES_WIDE : MS_WAVES))) void render_kernel(
-        const MsScenery sc, const MsAgents ag, const MsRender out,
+        const MsScenery sc, const AgentsK ag, const MsRender out,
         const float agent_radius, const float half_screen, const int R, const int n_fans,
-        const std::conditional_t<STEP == 1, RenderConstsStep, RenderConsts> rc) {
+        const std::conditional_t<STEP == 1, RenderConstsStep, std::conditional_t<NG == 1, RenderConstsOrder, RenderConsts>> rc) {
     static_assert(STEP == 0 || NG == 1, "the fused step: one group of rays");
+    constexpr bool ORDERED = NG == 1 && STEP == 0;   // (may be given a fan schedule: rc.schedule)
     // The wave's LDS is one raw block, so that the lighting at the end can reuse what the raycast is done with (its layout:
     // see the raycast)
     PROBE_INIT
@@ -393,7 +410,16 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
     [[maybe_unused]] int fan = b;                                        // (what the probe and dynlight_kernel's queue label a wave with)
     const int A = sc.n_agents, AF = sc.n_agents*sc.n_model;
     int n, a, r0, span;
-    if (!render_block(b, n_fans, A, R, NG, rc, n, a, r0, span, fan)) return;
+    if constexpr (ORDERED) {
+        // render_block's ng == 1, with the fan looked up in the schedule's order where there is one: one scalar load in front of
+        // the env's rows.  (No branch - see render_block: without a table the load is of a word that exists, and thrown away.  The
+        // table holds a permutation of the fans; whatever else someone left there is at least a fan of this launch.)
+        const int slot = render_slot(b, n_fans);
+        const int* const at = rc.schedule ? rc.schedule + n_fans + slot : sc.lines_starts;
+        const int named = *at;
+        fan = rc.schedule ? (int)min((unsigned)named, (unsigned)(n_fans - 1)) : slot;
+        render_fan(fan, A, R, rc, n, a, r0, span);
+    } else if (!render_block(b, n_fans, A, R, NG, rc, n, a, r0, span, fan)) return;
     const int r = r0 + lane;                       // (this lane's ray in the wave's first group)
     const int r_last = min(r0 + span - 1, R - 1);
     [[maybe_unused]] const int n_live = r_last - r0 + 1;
@@ -641,6 +667,12 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
     constexpr bool MASKED = !COLOUR || (OBS >= 1 && NG == 1);
     [[maybe_unused]] const int out_mask_ = MASKED ? (out.obs_subsample >> 8) : 0;
 #define MS_WANTED(BIT, PTR) (MASKED ? ((out_mask_ & (BIT)) != 0) : ((PTR) != nullptr))
+    // The fan's cost for the schedule (MsAgents.schedule), in quarters of a microsecond of a wave's life over the plainest wave's,
+    // from what the wave counts anyway - no clock is read.  The weights are the probe's (profiles/r04_wave_probe_headline.txt): a
+    // pass-2 window and 32 lines of list a quarter each; a ray on an agent +2.6 us (the grid's lighting: 11.4 us of life against
+    // 8.8); lights left open another 1.8 on top (13.2); a ray redone by the literal fold 0.9 (waves with one: resolution 0.82 us
+    // against 0.13).  physics.h's sort waves class it (fan_class).
+    [[maybe_unused]] int fan_cost = 0;
     // what depends on the winner's number alone: its row, its texel count and first texel
     // (plain scalars in and out: as a struct by value this cost every wave 32 bytes of scratch memory)
     auto winner_of = [&](const int nearest_idx, float4& hw_mem, int& tex_w, int& tstart) {
@@ -734,10 +766,12 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
                     reinterpret_cast<LightPair*>(&s_raw[O_EPI]), reinterpret_cast<unsigned*>(&s_raw[O_EPI + 2048]), light_telemetry);
 #endif
                 PROBE_VAL(2, light_telemetry)
+                if constexpr (ORDERED) fan_cost += (light_telemetry & 0x7fu) ? 7 : 0;    // (rays with lights the grid leaves open)
             } else if constexpr (NG == 1) {      // (wide waves never come here: without a light grid ms_render launches NG = 1 -
                 // and `fan`, which nothing else needs, was one of the values the wide colour instantiations spilled)
                 if (out.workspace && lane == 0) out.workspace[16 + atomicAdd(&out.workspace[0], 1)] = fan;
             }
+            if constexpr (ORDERED) fan_cost += 10;
         }
         // the 2-tap filter, and the texels and baked light under it - again for every lane (a miss looks at texel 0 of the
         // env's first line and throws the result away)
@@ -748,6 +782,11 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         const float* __restrict__ tr = l_tex_vals + 3*(size_t)(tstart + f.r);
         tl0 = tl[0]; tl1 = tl[1]; tl2 = tl[2]; tr0 = tr[0]; tr1 = tr[1]; tr2 = tr[2];
         if (is_hit & !dynamic) intensity = f.lw*bk_l + f.rw*bk_r;
+    }
+    if constexpr (ORDERED) {
+        // (with a schedule an agent is one fan: its number is the agent's row.  A plain vector store by one lane.)
+        int* const schedule = reinterpret_cast<const RenderArgsOrder __attribute__((address_space(4)))*>(late)->rc.schedule;
+        if (schedule && lane == 0) schedule[n*A + a] = fan_cost;
     }
     if constexpr (OBS >= 1) {
         if (MS_WANTED(OUT_SEEN, late->out.seen_stamp)) {           // explorer.py:34-58: which texels are seen for the first time
@@ -1156,6 +1195,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         // The literal fold for the rays that need it (kernels.cu:352-377): per such ray the hits, folded in line order
         // into the ray's own state, which lives in the ray's lane
         const unsigned long long amb = __ballot(ambiguous);
+        if constexpr (ORDERED) fan_cost = n_windows + (list_n >> 5) + 4*(int)__popcll(amb);
         PROBE_VAL(11, n_pairs_total) PROBE_VAL(12, n_drains == 1 ? list_n : -1) PROBE_VAL(13, __popcll(amb))
 #if MS_PROBE
         const unsigned t_fold0 = (unsigned)clock64();
@@ -1552,7 +1592,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
 //     bit into that ray's shadow words (LDS atomic, shared by the four waves).
 
 __global__ __launch_bounds__(WG) void dynlight_kernel(
-        const MsScenery sc, const MsAgents ag, const MsRender out, const int R) {
+        const MsScenery sc, const AgentsK ag, const MsRender out, const int R) {
     __shared__ LightPair s_pair[WAVES][PAIRS];
     __shared__ unsigned s_shadow[2*WAVE];        // per ray: 64 light bits, OR-ed by all waves
 

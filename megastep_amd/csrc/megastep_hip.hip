@@ -13,7 +13,8 @@
 //                   over all the env's walls (buffer loads in flight, lane = wall, reach boxes in scalar registers,
 //                   compacted pairs); the exact collision test, atomicMin fold, integration epilogue; leaves each
 //                   agent's sin/cos for the renderer.  MOVE = 1 runs the movement modules' velocity update first,
-//                   EXTRA = 1 the envs' respawn / lifespan / IMU bookkeeping.
+//                   EXTRA = 1 the envs' respawn / lifespan / IMU bookkeeping.  Where the agents carry a fan schedule, the
+//                   launch's first blocks sort the last render's costs into the next render's starting order.
 //                                                            (reference: kernels.cu:179-230, modules.py:24-118,263-366)
 //   render_kernel<OBS, SHADE, NG, STEP>   (OBS = 2: pooled observations only, no plane stores in the kernel; STEP = 1: a
 //                   single-agent env's physics step first, in the same wave - ms_step_render's one launch a step)
@@ -88,6 +89,14 @@ thread_local int g_tail_envs = -1;          //   ... >= 0: that many envs exactl
 thread_local int g_last_step_fused = 0;     // ms_debug_last_step_fused: did this thread's last ms_step_render go out as one launch?
 thread_local int g_last_render_groups = 0;  // ms_debug_last_render_groups: the NG this thread's last ms_render launched
 thread_local int g_overhead_cull = 1;       // ms_debug_overhead_cull: 0 = ms_overhead's tiles keep every line
+thread_local int g_render_order = 1;        // ms_debug_render_order: 0 = MsAgents.schedule is neither sorted nor followed
+
+// The agents as the kernels take them: MsAgents less its fan schedule, which only physics_kernel's sort waves (FanSort) and the
+// render instantiations of one ray group a wave (RenderConstsOrder) are given, behind their other arguments - so that the
+// kernel-argument segment of every kernel is byte for byte what it was before there was a schedule (render.h, RenderConstsStep:
+// the wide colour instantiations' time moves with their argument layout).
+struct AgentsK { float* angles; float* positions; float* angvelocity; float* velocity; float* headings; };
+AgentsK agents_k(const MsAgents& a) { return AgentsK{a.angles, a.positions, a.angvelocity, a.velocity, a.headings}; }
 
 // -DMS_PROBE=1 (`make probe`, tools/probe_waves.py): every wave of physics_kernel and render_kernel leaves a record of
 // time stamps (s_memtime at its start, at a few points where something it waited for has arrived, at its end) and of
@@ -224,7 +233,12 @@ bool agents_ok(const MsAgents* a) { return a && a->angles && a->positions && a->
 bool config_ok(const MsConfig* c) {
     return c && c->res > 0 && c->fps > 0.f && c->agent_radius > 0.f && c->fov > 0.f && c->fov < 180.f;
 }
-MsAgents agents_or_none(const MsAgents* a) { return a ? *a : MsAgents{nullptr, nullptr, nullptr, nullptr, nullptr}; }
+AgentsK agents_or_none(const MsAgents* a) { return a ? agents_k(*a) : AgentsK{nullptr, nullptr, nullptr, nullptr, nullptr}; }
+// The fan schedule serves launches in which every agent is ONE wave of the render: at most 64 rays (ms_step_physics sorts on this
+// alone - it cannot know what the render behind it will be asked for; a table nobody follows costs it a few dozen short waves).
+bool schedule_serves(const MsAgents* a, const MsScenery* sc, const int R) {
+    return g_render_order && a->schedule && R <= WAVE && (long long)sc->n_envs*sc->n_agents <= 0x3fffffffLL;
+}
 
 // kernels.cu:22: the camera's half-width at unit distance, as every launch that casts its rays works it out
 float half_screen_of(const float fov) { return tanf(3.14159265358979323846f/180.f*fov/2.); }
@@ -317,6 +331,20 @@ int ms_host_render_block(int n_envs, int n_agents, int res, int slots, int pinne
 }
 int ms_debug_ray_group_tail(float rounds, int envs) { g_tail_rounds = rounds; g_tail_envs = envs; return MS_OK; }
 int ms_debug_pair_telemetry(int on) { g_pair_telemetry = on ? 1 : 0; return MS_OK; }
+int ms_debug_render_order(int on) { g_render_order = on ? 1 : 0; return MS_OK; }
+int ms_host_order_fans(int n_fans, const int* costs, int* order) {
+    // fan_sort_wave, sort wave after sort wave: the classes' first ranks, slowest class first, then every fan its class's next rank
+    if (n_fans < 1 || !costs || !order) return -1;
+    const int K = fan_sort_per_run(n_fans);
+    for (int block = 0; block < 8*K; block++) {
+        int first_fan, count, first_slot, next[FAN_CLASSES] = {0};
+        fan_sort_part(n_fans, K, block, first_fan, count, first_slot);
+        for (int i = 0; i < count; i++) next[fan_class(costs[first_fan + i])]++;
+        for (int c = FAN_CLASSES - 1, rank = 0; c >= 0; c--) { const int m = next[c]; next[c] = rank; rank += m; }
+        for (int i = 0; i < count; i++) order[first_slot + K*next[fan_class(costs[first_fan + i])]++] = first_fan + i;
+    }
+    return 8*K;
+}
 
 int ms_test_arithmetic(const float* n, const float* d, float* q_inrange, float* q_ieee, const float* x, float* r_any, float* r_ieee,
                        long long count, void* stream) {
@@ -481,7 +509,7 @@ int ms_wallgrid_fill(const MsScenery* sc, const int* reps, int n_reps, int max_c
 int ms_step_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* mv, const MsStepExtras* ex, float* progress,
                     const MsConfig* cfg, void* stream) {
     if (!scenery_ok(sc) || !agents_ok(ag) || !progress || !config_ok(cfg)) return MS_EINVAL;
-    if (!step_options_ok(mv, ex)) return MS_EINVAL;
+    if (!step_options_ok(mv, ex) || ((uintptr_t)ag->schedule % 4)) return MS_EINVAL;
     if (sc->wg_cells && (!sc->wg_starts || !sc->wg_geom || !sc->wg_near_rows || !(sc->wg_cell > 0.f) || ((uintptr_t)sc->wg_cells % 16) ||
                          ((uintptr_t)sc->wg_geom % 16) || ((uintptr_t)sc->wg_near_rows % 16))) return MS_EINVAL;
     const int pack = physics_pack_of(sc->n_envs, sc->n_agents, sc->wg_cells != nullptr, g_physics_pack);
@@ -494,9 +522,16 @@ int ms_step_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* m
     if (!sc->wg_cells) { scn.wg_geom = sc->lines_vals; scn.wg_starts = sc->lines_starts; }   // (rows the kernel may read: see there)
     const hipStream_t hs = (hipStream_t)stream;
     const Divisor by_a = divisor_of((unsigned)sc->n_agents);
+    const AgentsK agk = agents_k(*ag);
+    // the fan schedule's sort waves, in front of the launch's own (physics.h): last frame's render costs into this frame's order
+    FanSort fs{nullptr, 0, 1, 0};
+    if (schedule_serves(ag, sc, cfg->res)) {
+        fs.schedule = ag->schedule; fs.n_fans = sc->n_envs*sc->n_agents;
+        fs.per_run = fan_sort_per_run(fs.n_fans); fs.n_blocks = 8*fs.per_run;
+    }
     // one wavefront per env (several envs per wave, one AFTER the other: 2 -> +25 %, 4 -> +85 % at 4096 envs; side by side: PACK)
 #define MS_LAUNCH_PHYSICS_P(M, E, P) \
-    hipLaunchKernelGGL((physics_kernel<M, E, P>), dim3((sc->n_envs + pack - 1)/pack), dim3(WAVE), slice*16, hs, scn, *ag, progress, cfg->agent_radius, cfg->fps, mvv, exv, pack, by_a)
+    hipLaunchKernelGGL((physics_kernel<M, E, P>), dim3(fs.n_blocks + (sc->n_envs + pack - 1)/pack), dim3(WAVE), slice*16, hs, scn, agk, progress, cfg->agent_radius, cfg->fps, mvv, exv, pack, by_a, fs)
 #define MS_LAUNCH_PHYSICS(M, E) { if (pack > 1) MS_LAUNCH_PHYSICS_P(M, E, 1); else MS_LAUNCH_PHYSICS_P(M, E, 0); }
     if (mv && ex) MS_LAUNCH_PHYSICS(1, 1)
     else if (ex) MS_LAUNCH_PHYSICS(0, 1)
@@ -522,7 +557,8 @@ int ms_physics(const MsScenery* sc, const MsAgents* ag, float* progress, const M
 struct RenderLaunch {
     RenderPlan plan;                                  // render_kernel's NG and blocks
     RenderConstsStep rc;                              // (the STEP = 1 part is set only where the step is fused)
-    MsScenery scn; MsAgents agn; MsRender outn;       // the copies render_kernel gets
+    int* schedule;                                    // the fan schedule, where the launch follows it (else NULL): RenderConstsOrder's
+    MsScenery scn; AgentsK agn; MsRender outn;        // the copies render_kernel gets
     const MsAgents* ag; const MsRender* out;          // the caller's, as render_prep_kernel and dynlight_kernel get them
     float agent_radius, half_screen; int R;
     bool colour, obs, no_planes;                      // which instantiation of render_kernel
@@ -590,8 +626,11 @@ static int render_prepare(const MsScenery* sc, const MsAgents* ag, const MsRende
     const bool cached = ag->headings && !L.dynlight;
     L.prep = !cached && !L.fused && out->workspace;
     if ((cached && (uintptr_t)ag->headings % 16) || (L.prep && (uintptr_t)out->workspace % 8)) return MS_EINVAL;
-    L.agn = *ag;
+    L.agn = agents_k(*ag);
     L.outn = *out;
+    // the fan schedule: every agent one fan, one launch of one-group waves behind a physics launch of its own
+    L.schedule = (schedule_serves(ag, sc, R) && L.plan.ng == 1 && !L.fused) ? ag->schedule : nullptr;
+    if (L.schedule && (uintptr_t)L.schedule % 4) return MS_EINVAL;
     if (!cached && !L.fused) L.agn.headings = nullptr;
     if (!L.prep) L.outn.workspace = nullptr;
     if (out->obs_depth) L.outn.obs_max_depth = 1.f/out->obs_max_depth;  // (the kernel multiplies: see the pooled depth in render.h)
@@ -618,8 +657,10 @@ static int render_prepare(const MsScenery* sc, const MsAgents* ag, const MsRende
 static int render_enqueue(const RenderLaunch& L, const hipStream_t hs) {
     g_last_render_groups = L.plan.ng;
     const int na = L.scn.n_envs*L.scn.n_agents;
-    if (L.prep) hipLaunchKernelGGL(render_prep_kernel, dim3((na + WG - 1)/WG), dim3(WG), 0, hs, *L.ag, L.out->workspace, na, L.rc.ws_headings);
-    // (the STEP = 0 instantiations take the RenderConsts part of L.rc)
+    if (L.prep) hipLaunchKernelGGL(render_prep_kernel, dim3((na + WG - 1)/WG), dim3(WG), 0, hs, agents_k(*L.ag), L.out->workspace, na, L.rc.ws_headings);
+    // (the STEP = 0 instantiations take the RenderConsts part of L.rc - those of one ray group a wave with the schedule behind it)
+    RenderConstsOrder rco;
+    static_cast<RenderConsts&>(rco) = L.rc; rco.schedule = L.schedule;
 #define MS_LAUNCH_RENDER(O, S, NG_, STEP_) hipLaunchKernelGGL((render_kernel<O, S, NG_, STEP_>), dim3((int)L.plan.n_blocks), dim3(WAVE), 0, hs, \
                                                               L.scn, L.agn, L.outn, L.agent_radius, L.half_screen, L.R, (int)L.plan.n_blocks, L.rc)
 #define MS_LAUNCH_RENDER_OS(NG_) { if (!L.colour) MS_LAUNCH_RENDER(1, 0, NG_, 0); else if (L.no_planes) MS_LAUNCH_RENDER(2, 1, NG_, 0); \
@@ -627,10 +668,16 @@ static int render_enqueue(const RenderLaunch& L, const hipStream_t hs) {
     if (L.fused) { if (!L.colour) MS_LAUNCH_RENDER(1, 0, 1, 1); else if (L.obs) MS_LAUNCH_RENDER(1, 1, 1, 1); else MS_LAUNCH_RENDER(0, 1, 1, 1); }
     else if (L.plan.ng == 4) MS_LAUNCH_RENDER_OS(4)
     else if (L.plan.ng == 2) MS_LAUNCH_RENDER_OS(2)
-    else MS_LAUNCH_RENDER_OS(1)
+    else {
+#define MS_LAUNCH_RENDER_1(O, S) hipLaunchKernelGGL((render_kernel<O, S, 1, 0>), dim3((int)L.plan.n_blocks), dim3(WAVE), 0, hs, \
+                                                    L.scn, L.agn, L.outn, L.agent_radius, L.half_screen, L.R, (int)L.plan.n_blocks, rco)
+        if (!L.colour) MS_LAUNCH_RENDER_1(1, 0); else if (L.no_planes) MS_LAUNCH_RENDER_1(2, 1);
+        else if (L.obs) MS_LAUNCH_RENDER_1(1, 1); else MS_LAUNCH_RENDER_1(0, 1);
+#undef MS_LAUNCH_RENDER_1
+    }
 #undef MS_LAUNCH_RENDER_OS
 #undef MS_LAUNCH_RENDER
-    if (L.dynlight) hipLaunchKernelGGL(dynlight_kernel, dim3((int)L.plan.n_blocks), dim3(WG), 0, hs, L.scn, *L.ag, *L.out, L.R);
+    if (L.dynlight) hipLaunchKernelGGL(dynlight_kernel, dim3((int)L.plan.n_blocks), dim3(WG), 0, hs, L.scn, agents_k(*L.ag), *L.out, L.R);
     return launch_status();
 }
 

@@ -39,6 +39,9 @@ def _ab_switches():
     k = os.environ.get('MEGASTEP_PHYSICS_PACK')
     if k:
         _lib.lib().ms_debug_physics_pack(int(k))         # envs a physics wave takes side by side (default: by the world's size)
+    o = os.environ.get('MEGASTEP_RENDER_ORDER')
+    if o:
+        _lib.lib().ms_debug_render_order(int(o))         # the fan schedule: 0 = render waves in fan order, 1 = slowest of last frame first
     t, e = os.environ.get('MEGASTEP_RAY_GROUP_TAIL'), os.environ.get('MEGASTEP_RAY_GROUP_TAIL_ENVS')
     if t or e:                                           # the one-group waves at the end of a launch of wide ones: in rounds / in envs
         _lib.lib().ms_debug_ray_group_tail(float(t) if t else -1., int(e) if e else -1)
@@ -187,6 +190,8 @@ class Agents:
 
     #: ``False`` sends ms_render through its own heading kernel instead of the cache ms_physics leaves (tests, A/B runs)
     HEADING_CACHE = True
+    #: ``False`` leaves ``MsAgents.schedule`` NULL: the render deals its waves in fan order (tests, A/B runs)
+    SCHEDULE = True
 
     def __init__(self, angles, positions, angvelocity, velocity, config=None):
         #: the constants :func:`physics` / :func:`render` use for these agents (:func:`config`); None: initialize()'s
@@ -201,9 +206,15 @@ class Agents:
         # The heading cache (include/megastep_hip.h, MsAgents.headings): physics leaves each agent's sin/cos there for
         # the next render. `_struct` carries it; `_plain` does not, for renders before any physics call has filled it.
         self._headings = torch.full((n, a, 4), float('nan'), dtype=torch.float32, device=angles.device)
+        # The fan schedule (MsAgents.schedule): the render leaves every (env, agent)'s cost in its first half, the next physics
+        # step sorts them into its second half - the order the render behind it starts its waves in. The identity to begin
+        # with, so that a render before any physics is served; SCHEDULE = False goes without (today's mapping).
+        self._schedule = torch.stack([torch.zeros(n*a, dtype=torch.int32, device=angles.device),
+                                      torch.arange(n*a, dtype=torch.int32, device=angles.device)]) if self.SCHEDULE else None
         ptrs = (angles.data_ptr(), positions.data_ptr(), angvelocity.data_ptr(), velocity.data_ptr())
-        self._struct = _lib.MsAgents(*ptrs, self._headings.data_ptr())
-        self._plain = _lib.MsAgents(*ptrs, None)
+        schedule = self._schedule.data_ptr() if self.SCHEDULE and angles.device.type == 'cuda' else None
+        self._struct = _lib.MsAgents(*ptrs, self._headings.data_ptr(), schedule)
+        self._plain = _lib.MsAgents(*ptrs, None, schedule)
         self._cached = False
         self._epoch = 0             # moved on by every physics call and every respawn (modules.IMU's stale-reading check)
         # (measured at 16 k to 262 k agents: one launch and one kernel boundary fewer per step, 1-3 % of the step)
