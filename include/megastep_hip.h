@@ -465,6 +465,69 @@ int ms_nav_free(const MsScenery* scenery, const MsNavGrid* grid, void* hip_strea
 int ms_nav_fields(const MsNavGrid* grid, const MsNavFields* fields, void* hip_stream);
 int ms_nav_query(const MsNavGrid* grid, const MsNavQuery* query, void* hip_stream);
 
+/* Paths and look-ahead waypoints on the distance fields: which way to go, not only how far.  As above every step is one
+ * binary32 operation in the order given, without contraction; tests/test_navpath_host.py restates it in numpy (path_rule)
+ * and the kernels - and their host instantiations, ms_host_nav_waypoint / ms_host_nav_path - are held to EQUALITY with it.
+ * c, free, centre, leg and the anchor corner (i0, j0) are MsNavGrid's; D is the field of goal q = goals[n, g]; p the point.
+ *   start         over p's anchor cells in the query's order - t = 0..3, cell (i0 + (t>>1), j0 + (t&1)), in range, D < +inf:
+ *                 a* is the first that attains the least fl(D[a] + leg(p, a)) (replaced on a strict <, from +inf).  None:
+ *                 no path - exactly when ms_nav_query gives +inf, a goal index out of [0, n_goals) and an env without
+ *                 cells included.
+ *   hop           from cell v = (i, j).  If v is one of the four cells (iq0 + {0,1}, jq0 + {0,1}) round q (q has an anchor
+ *                 corner) and leg(q, v) == D[v], the chain ends at v: its next and last point is q itself.  Otherwise over
+ *                 the neighbours u = (i + di, j + dj) in the order (di, dj) = (0,+1) (+1,0) (0,-1) (-1,0) (+1,+1) (+1,-1)
+ *                 (-1,-1) (-1,+1): a neighbour counts if it is in range and free, a diagonal one only if (i + di, j) and
+ *                 (i, j + dj) are free too; its value is fl(D[u] + w), w = c straight, c*1.41421356f diagonal.  The next
+ *                 cell is the first neighbour that attains the least value (replaced on a strict <, from +inf), provided
+ *                 D[u] < D[v] - at a fixed point of the relaxation that least value IS D[v].  No such neighbour (a stale or
+ *                 foreign field): the chain is BROKEN and stops there; D falls at every hop, so no input makes a chain
+ *                 longer than the env's cells.
+ *   chain         x_0 = centre(a*), x_1, ... the centres of the cells the hops reach, the last point q.
+ *   sight         from p to a point x: dx = x.x - p.x, dy = x.y - p.y, len = sqrtf(dx*dx + dy*dy), k = ceilf(len/(0.5f*c)),
+ *                 K = (int)k (no sight when k is not below 2^20); for s = 1 .. K-1: t = (float)s/(float)K, the sample
+ *                 (p.x + dx*t, p.y + dy*t), its anchor corner (i0, j0): all four cells (i0 + {0,1}, j0 + {0,1}) must be in
+ *                 range and free.  True when every sample passes (vacuously for K <= 1).  Every point of the segment is
+ *                 within c/2 of a sample or an end, so inside the block of four free cells round that sample or inside a
+ *                 free end cell: the centre of the cell it lies in is free and within 0.71 c <= 0.99 r of it - a wall
+ *                 through the point would have blocked that centre (the edges' argument, the same 1 % margin).
+ *   waypoint      with look-ahead L (1..64): the candidates are the first L chain points x_0 .. x_{n-1} (n < L where the chain
+ *                 ends or breaks earlier).  The base index b = 1 when leg(p, x_0) <= 0.5f*c and n >= 2, else 0: x_b is
+ *                 always admissible (for b = 1, p lies inside cell x_0 and p -> x_1 stays in x_0, x_1 and the two open side
+ *                 cells of a diagonal; without it a point ON a centre next to a wall would be sent to where it stands).
+ *                 k > b is admissible when sight(p, x_k).  The waypoint is x_k for the LARGEST admissible k; hops = k.
+ *                 NaN, NaN and hops = -1 without a path.  A broken chain offers the points it got.
+ *   path          p, x_0, x_1, ..., q into (N, P, M, 2), NaN in the slots not written; counts = the number of points of the
+ *                 whole path however long (the first M are written), 0 without a path, the number got, negated, for a
+ *                 broken chain.
+ * Other agents are no obstacles: the grid is the building.  Nothing is allocated, nothing waits, no float atomics: both
+ * calls can be captured in a HIP graph.  Every argument is checked in full before the first launch (MS_EINVAL). */
+typedef struct MsNavWaypoints {
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y; 8-byte aligned                                               */
+    const int*           goal;         /* (N, P) which of the env's fields each point follows; NULL: P == G, point k field k */
+    const float*         fields;       /* as MsNavFields.fields                                                        */
+    const float*         goals;        /* (N, G, 2) the fields' goals, as MsNavFields.goals; 8-byte aligned            */
+    int                  n_goals;      /* G of `fields` and `goals`                                                    */
+    int                  lookahead;    /* L, 1..64                                                                     */
+    float*               waypoints;    /* (N, P, 2) out; 8-byte aligned                                                */
+    int*                 hops;         /* (N, P) out, or NULL: the chosen index k, -1 without a path                   */
+} MsNavWaypoints;
+typedef struct MsNavPaths {
+    int                  n_points;     /* P                                                                            */
+    const float*         points;       /* (N, P, 2); 8-byte aligned                                                    */
+    const int*           goal;         /* (N, P) or NULL, as above                                                     */
+    const float*         fields;
+    const float*         goals;        /* (N, G, 2); 8-byte aligned                                                    */
+    int                  n_goals;
+    int                  max_points;   /* M >= 2: points written per path                                              */
+    float*               paths;        /* (N, P, M, 2) out                                                             */
+    int*                 counts;       /* (N, P) out                                                                   */
+} MsNavPaths;
+/* ms_nav_waypoints  one wavefront per point (the per-step call of an expert: N x A points).
+ * ms_nav_paths      one lane per point; walks every chain to its end. */
+int ms_nav_waypoints(const MsNavGrid* grid, const MsNavWaypoints* waypoints, void* hip_stream);
+int ms_nav_paths(const MsNavGrid* grid, const MsNavPaths* paths, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

@@ -64,6 +64,15 @@ int ms_debug_overhead_cull(int on);
  * (tile_row, tile_col) - 16 x 16 pixels, clipped to a height x width image - under view (g0..g5) at half width h?  1 = the
  * kernel keeps the line for that tile, 0 = it drops it. */
 int ms_host_overhead_keeps(const float* view, int height, int width, int tile_row, int tile_col, float half_width, const float* line);
+/* Host instantiations of the path rule's device functions (kernels/navpath.h: start, hop, sight) for ONE env and ONE query on
+ * HOST arrays: geom = (jx0, iy0, nx, ny), free_cells and D (ny x nx, row-major) the env's free bytes and the goal's field,
+ * goal and point (x, y).  ms_host_nav_waypoint writes the waypoint (NaN, NaN without a path) and returns the chosen index
+ * (-1 without a path; -2: lookahead outside 1..64); ms_host_nav_path writes max_points x 2 floats (NaN in the slots not
+ * written) and returns MsNavPaths' count (max_points < 2: 0, nothing written). */
+int ms_host_nav_waypoint(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal,
+                         const float* point, int lookahead, float* waypoint);
+int ms_host_nav_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal,
+                     const float* point, int max_points, float* points);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

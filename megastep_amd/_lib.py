@@ -106,10 +106,20 @@ class MsNavQuery(C.Structure):
                 ('out', C.c_void_p)]
 
 
+class MsNavWaypoints(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('goal', C.c_void_p), ('fields', C.c_void_p), ('goals', C.c_void_p),
+                ('n_goals', C.c_int), ('lookahead', C.c_int), ('waypoints', C.c_void_p), ('hops', C.c_void_p)]
+
+
+class MsNavPaths(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('goal', C.c_void_p), ('fields', C.c_void_p), ('goals', C.c_void_p),
+                ('n_goals', C.c_int), ('max_points', C.c_int), ('paths', C.c_void_p), ('counts', C.c_void_p)]
+
+
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare
 SYMBOLS = ('ms_host_ray_interval_wide', 'ms_debug_render_order', 'ms_host_order_fans', 'ms_debug_ray_groups', 'ms_debug_last_render_groups', 'ms_debug_last_step_fused', 'ms_step_render', 'ms_move_step_render', 'ms_debug_ray_group_tail', 'ms_debug_physics_pack', 'ms_host_render_plan', 'ms_host_render_block', 'ms_host_physics_pack', 'ms_debug_pair_telemetry', 'ms_test_arithmetic', 'ms_abi_version', 'ms_strerror', 'ms_last_hip_error', 'ms_device_count', 'ms_bake', 'ms_physics', 'ms_move_physics',
            'ms_step_physics', 'ms_deathmatch_shoot', 'ms_explorer_books',
-           'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_nav_free', 'ms_nav_fields', 'ms_nav_query', 'ms_debug_overhead_cull', 'ms_host_overhead_keeps', 'ms_host_sincospi', 'ms_host_bake_point_bin', 'ms_host_bake_wall_bins',
+           'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_nav_free', 'ms_nav_fields', 'ms_nav_query', 'ms_nav_waypoints', 'ms_nav_paths', 'ms_host_nav_waypoint', 'ms_host_nav_path', 'ms_debug_overhead_cull', 'ms_host_overhead_keeps', 'ms_host_sincospi', 'ms_host_bake_point_bin', 'ms_host_bake_wall_bins',
            'ms_wallgrid_scan', 'ms_wallgrid_fill', 'ms_host_wall_hidden', 'ms_host_wall_sectors', 'ms_host_wallgrid_cell', 'ms_host_wall_arc',
            'ms_host_wedge_meets', 'ms_host_agents_apart', 'ms_host_wall_beyond_reach', 'ms_host_ray_interval', 'ms_host_fold_hits', 'ms_host_lightgrid_cell', 'ms_host_wall_reach')
 
@@ -208,6 +218,12 @@ def lib():
         handle.ms_nav_free.argtypes = [C.POINTER(MsScenery), C.POINTER(MsNavGrid), C.c_void_p]
         handle.ms_nav_fields.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavFields), C.c_void_p]
         handle.ms_nav_query.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavQuery), C.c_void_p]
+        handle.ms_nav_waypoints.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavWaypoints), C.c_void_p]
+        handle.ms_nav_paths.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavPaths), C.c_void_p]
+        handle.ms_host_nav_waypoint.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        handle.ms_host_nav_waypoint.restype = C.c_int
+        handle.ms_host_nav_path.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        handle.ms_host_nav_path.restype = C.c_int
         handle.ms_debug_overhead_cull.argtypes = [C.c_int]
         handle.ms_debug_overhead_cull.restype = C.c_int
         handle.ms_host_overhead_keeps.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p]
@@ -269,7 +285,7 @@ def lib():
         handle.ms_host_wallgrid_cell.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int,
                                                  C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         handle.ms_host_wallgrid_cell.restype = None
-        for name in ('ms_bake', 'ms_physics', 'ms_move_physics', 'ms_step_physics', 'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_nav_free', 'ms_nav_fields', 'ms_nav_query', 'ms_wallgrid_scan', 'ms_wallgrid_fill'):
+        for name in ('ms_bake', 'ms_physics', 'ms_move_physics', 'ms_step_physics', 'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_nav_free', 'ms_nav_fields', 'ms_nav_query', 'ms_nav_waypoints', 'ms_nav_paths', 'ms_wallgrid_scan', 'ms_wallgrid_fill'):
             getattr(handle, name).restype = C.c_int
         if handle.ms_abi_version() != ABI_VERSION:
             raise ImportError(f'{LIB_PATH} has ABI {handle.ms_abi_version()}, this package needs {ABI_VERSION}; rebuild it')

@@ -35,18 +35,18 @@ struct NavArgs {                                     // MsNavGrid, checked
     float cell, clearance;
 };
 
-__device__ inline float nav_centre(const int origin, const int k, const float c) { return ((float)(origin + k) + .5f)*c; }
+__host__ __device__ inline float nav_centre(const int origin, const int k, const float c) { return ((float)(origin + k) + .5f)*c; }
 
 // The cell (i0, j0) whose centre is the last at or below p on both axes - p's anchors are (i0 + {0, 1}, j0 + {0, 1}); false:
 // p has none (NaN, or further out than any grid).
-__device__ inline bool nav_anchor_corner(const float x, const float y, const float c, const int jx0, const int iy0, long long& i0, long long& j0) {
+__host__ __device__ inline bool nav_anchor_corner(const float x, const float y, const float c, const int jx0, const int iy0, long long& i0, long long& j0) {
     const float fx = floorf(x/c - .5f), fy = floorf(y/c - .5f);
     if (!(fabsf(fx) < NAV_INDEX_LIMIT) || !(fabsf(fy) < NAV_INDEX_LIMIT)) return false;
     j0 = (long long)fx - jx0; i0 = (long long)fy - iy0;
     return true;
 }
 
-__device__ inline float nav_leg(const float x, const float y, const int jx0, const int iy0, const int i, const int j, const float c) {
+__host__ __device__ inline float nav_leg(const float x, const float y, const int jx0, const int iy0, const int i, const int j, const float c) {
     const float dx = x - nav_centre(jx0, j, c), dy = y - nav_centre(iy0, i, c);
     return sqrtf(dx*dx + dy*dy);
 }

@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h.
 //
-// Nineteen kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Twenty-one kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -49,6 +49,9 @@
 //   nav_free_kernel, nav_relax_kernel, nav_query_kernel   shortest-path distance fields: which cells of a grid over a floorplan
 //                   keep the agent's radius clear of every wall; per goal one workgroup that relaxes the 8-connected field in
 //                   LDS until nothing changes; and the distance from any point to a goal, four gathers.   (no counterpart)
+//   nav_waypoint_kernel, nav_path_kernel   which way to go on those fields: one wavefront per point descends the field a
+//                   neighbour a lane and picks the furthest of the next cells the point can see; and whole paths, a lane
+//                   each.   (no counterpart)
 //   explorer_kernel     the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
 //   deathmatch_kernel   the Deathmatch env's game logic between frames (revive, crosshairs, hits and wounds, health, damage,
@@ -147,6 +150,7 @@ struct Probe {
 #include "kernels/raycast.h"
 #include "kernels/overhead.h"
 #include "kernels/navfield.h"
+#include "kernels/navpath.h"
 #include "kernels/envlogic.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -824,6 +828,62 @@ int ms_nav_query(const MsNavGrid* grid, const MsNavQuery* nq, void* stream) {
     const NavQueryArgs q{nq->points, nq->goal, nq->fields, nq->out, nq->n_points, nq->n_goals, total};
     hipLaunchKernelGGL(nav_query_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
     return launch_status();
+}
+
+// Paths and waypoints (navpath.h): the same discipline.
+static bool nav_follow_ok(const MsNavGrid* grid, int n_points, const float* points, const int* goal, const float* fields, const float* goals,
+                          int n_goals) {
+    return nav_grid_ok(grid) && n_points >= 1 && n_goals >= 1 && points && fields && goals && (goal || n_points == n_goals) &&
+           ((uintptr_t)points % 8 == 0) && ((uintptr_t)goals % 8 == 0) && ((uintptr_t)fields % 4 == 0) && ((uintptr_t)goal % 4 == 0);
+}
+
+int ms_nav_waypoints(const MsNavGrid* grid, const MsNavWaypoints* w, void* stream) {
+    if (!w || !nav_follow_ok(grid, w->n_points, w->points, w->goal, w->fields, w->goals, w->n_goals) || w->lookahead < 1 ||
+        w->lookahead > WAVE || !w->waypoints || ((uintptr_t)w->waypoints % 8) || ((uintptr_t)w->hops % 4)) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*w->n_points;
+    if ((total + WAVES - 1)/WAVES > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    const NavPathArgs q{w->points, w->goal, w->fields, w->goals, grid->free_cells, w->waypoints, w->hops, nullptr, nullptr,
+                        w->n_points, w->n_goals, w->lookahead, 0, total};
+    hipLaunchKernelGGL(nav_waypoint_kernel, dim3((unsigned)((total + WAVES - 1)/WAVES)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
+    return launch_status();
+}
+
+int ms_nav_paths(const MsNavGrid* grid, const MsNavPaths* np, void* stream) {
+    if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->goals, np->n_goals) || np->max_points < 2 ||
+        !np->paths || !np->counts || ((uintptr_t)np->paths % 4) || ((uintptr_t)np->counts % 4)) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*np->n_points;
+    if (total > 0x7fffff00LL) return MS_EUNSUPPORTED;
+    const NavPathArgs q{np->points, np->goal, np->fields, np->goals, grid->free_cells, nullptr, nullptr, np->paths, np->counts,
+                        np->n_points, np->n_goals, 0, np->max_points, total};
+    hipLaunchKernelGGL(nav_path_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
+    return launch_status();
+}
+
+static bool nav_host_env(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal, const float* point,
+                         NavEnv& g) {
+    if (!geom || !free_cells || !D || !goal || !point || !(cell > 0.f) || geom[2] <= 0 || geom[3] <= 0) return false;
+    g = NavEnv{geom[0], geom[1], geom[2], geom[3], cell, free_cells, D};
+    return true;
+}
+
+int ms_host_nav_waypoint(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal, const float* point,
+                         int lookahead, float* waypoint) {
+    if (lookahead < 1 || lookahead > WAVE || !waypoint) return -2;
+    waypoint[0] = waypoint[1] = NAN;
+    NavEnv g;
+    if (!nav_host_env(geom, cell, free_cells, D, goal, point, g)) return -1;
+    return nav_waypoint_serial(g, nav_goal(g, goal[0], goal[1]), point[0], point[1], lookahead, waypoint[0], waypoint[1]);
+}
+
+int ms_host_nav_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal, const float* point,
+                     int max_points, float* points) {
+    if (max_points < 2 || !points) return 0;
+    NavEnv g;
+    if (!nav_host_env(geom, cell, free_cells, D, goal, point, g)) {
+        for (int k = 0; k < 2*max_points; k++) points[k] = NAN;
+        return 0;
+    }
+    return nav_path(g, nav_goal(g, goal[0], goal[1]), point[0], point[1], (long long)g.nx*g.ny, max_points, points);
 }
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {

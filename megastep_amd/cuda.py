@@ -1198,6 +1198,75 @@ class DistanceFields:
             _lib.check(_lib.lib().ms_nav_query(C.byref(grid._struct), C.byref(spec), _stream(dev)))
         return out
 
+    def _queries(self, points, goal):
+        """:meth:`at`'s argument rules, for the calls that follow the fields: (n, p, goal as int32 or None, device)."""
+        grid = self.grid
+        _check(points, 'points', torch.float32, 3)
+        n, p = points.shape[:2]
+        if n != grid.n_envs or points.shape[2] != 2 or p < 1:
+            raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
+        if goal is None:
+            if p != self.n_goals:
+                raise RuntimeError(f'without goal, points must be one per field ({self.n_goals}); got {p}')
+        else:
+            if not isinstance(goal, torch.Tensor) or goal.dtype.is_floating_point or goal.shape != (n, p):
+                raise RuntimeError(f'goal must be an (N, P) = ({n}, {p}) integer tensor')
+            goal = goal.to(torch.int32).contiguous()
+        dev = _require_gpu(points, self.values, self.goals, grid.free, *([goal] if goal is not None else []))
+        return n, p, goal, dev
+
+    def waypoints(self, points, goal=None, lookahead=16, hops=False, out=None):
+        """(N, P, 2) float32: where to head for from each of ``points`` (N, P, 2) to walk to its goal (``goal``: as :meth:`at`) -
+        the furthest of the next ``lookahead`` (1..64) cells down the field that the point can see in a straight line clear of
+        the walls, the goal itself once that is in sight; NaN where no path exists (exactly where :meth:`at` gives +inf).
+        Heading for the waypoint, step after step, walks round the walls to the goal, and less far than :meth:`at` says: the
+        look-ahead cuts the grid's 8-direction staircase short. ``hops=True`` also returns (N, P) int32: how many cells
+        ahead the waypoint is (-1: no path). ``out``: the (N, P, 2) tensor to write. One launch, a wavefront a point, no host
+        synchronisation. The rule: include/megastep_hip.h (``MsNavWaypoints``), DESIGN.md 3.15."""
+        if not isinstance(lookahead, int) or not 1 <= lookahead <= 64:
+            raise RuntimeError(f'lookahead must be an integer in 1..64; got {lookahead}')
+        n, p, goal, dev = self._queries(points, goal)
+        if out is None:
+            out = torch.empty((n, p, 2), dtype=torch.float32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.shape != (n, p, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise RuntimeError('`out` must be a contiguous (N, P, 2) float32 tensor on the fields\' device')
+        chosen = torch.empty((n, p), dtype=torch.int32, device=dev) if hops else None
+        spec = _lib.MsNavWaypoints(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
+                                   self.goals.data_ptr(), self.n_goals, lookahead, out.data_ptr(), chosen.data_ptr() if hops else None)
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_waypoints(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        return (out, chosen) if hops else out
+
+    def paths(self, points, goal=None, max_points=256):
+        """The whole path from each of ``points`` (N, P, 2) to its goal (``goal``: as :meth:`at`), as a :class:`Paths`: the point,
+        the centres of the cells down the field, the goal; the first ``max_points`` of them written. One launch, a lane a
+        path, no host synchronisation; for drawing and for scoring, not for every step - that is :meth:`waypoints`."""
+        if not isinstance(max_points, int) or not 2 <= max_points <= 2**20:
+            raise RuntimeError(f'max_points must be an integer in 2..2^20; got {max_points}')
+        n, p, goal, dev = self._queries(points, goal)
+        pts = torch.empty((n, p, max_points, 2), dtype=torch.float32, device=dev)
+        counts = torch.empty((n, p), dtype=torch.int32, device=dev)
+        spec = _lib.MsNavPaths(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
+                               self.goals.data_ptr(), self.n_goals, max_points, pts.data_ptr(), counts.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_paths(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        return Paths(pts, counts)
+
+
+class Paths:
+    """Result of :meth:`DistanceFields.paths`. ``points`` (N, P, M, 2) float32: path (e, k)'s points - where it starts, cell
+    centre after cell centre, the goal - NaN in the slots not written; ``counts`` (N, P) int32: the points of the whole path,
+    which may be more than the M written; 0 where no path exists; negative (the points got, negated) where the field did not
+    lead to its goal - a stale field, or one of another grid."""
+
+    def __init__(self, points, counts):
+        self.points, self.counts = points, counts
+
+    def path(self, e, k):
+        """(n, 2): the written points of path ``k`` of env ``e`` (synchronises: n comes from the device)."""
+        n = min(abs(int(self.counts[e, k])), self.points.shape[2])
+        return self.points[e, k, :n]
+
 
 def _nav_fields_call(fields, mask):
     grid = fields.grid
@@ -1217,7 +1286,8 @@ def distance_fields(grid, goals, mask=None, out=None, passes=False):
     """Shortest-path distance fields on the :func:`nav_grid`: for every env and each of its ``G`` goals (``goals``: (N, G, 2)
     float32 world points) the distance from every free cell to the goal along the grid's 8-connected graph - straight steps
     of ``cell``, diagonal steps of ``cell*1.41421356`` that cut no corner - joined to the goal by the straight legs from the
-    free cells round it. The 8-connected metric is up to 8 % longer than the true (any-angle) shortest path in open space.
+    free cells round it. The 8-connected metric is up to 8 % longer than the true (any-angle) shortest path in open space;
+    an agent that heads for :meth:`DistanceFields.waypoints` cuts the staircase short and walks less than the field says.
     One launch, one workgroup per field, the field relaxed in LDS until nothing changes; the result does not depend on the
     order of relaxation and equals Dijkstra's with binary32 additions bit for bit (include/megastep_hip.h, ``MsNavGrid``).
 

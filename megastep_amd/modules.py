@@ -473,6 +473,11 @@ class Goals:
         """(n_env, n_agent): how far every agent has to walk to its goal now; +inf where no path exists."""
         return self._fields.at(self.core.agents.positions)
 
+    def waypoints(self, lookahead=16):
+        """(n_env, n_agent, 2): where every agent should head for now to walk to its own goal
+        (:meth:`cuda.DistanceFields.waypoints`); NaN where no path exists."""
+        return self._fields.waypoints(self.core.agents.positions, lookahead=lookahead)
+
     def observation(self):
         """(n_env, n_agent, 3): the goal's offset in the agent's frame, and its length (the straight line, which is what a
         compass knows: the walking distance is the env's to reward, not the agent's to see)."""
@@ -482,3 +487,59 @@ class Goals:
 
     def state(self, e=0):
         return arrdict.arrdict(goals=self.goals[e], stranded=self.stranded[e]).clone()
+
+
+class PathFollower:
+
+    def __init__(self, core, goals, lookahead=16, cone=45., speed=2.):
+        """The shortest-path expert over a :class:`Goals`: every agent turns towards its waypoint - the furthest of the next
+        ``lookahead`` cells of its shortest path that it can see (:meth:`Goals.waypoints`) - and walks once that lies within
+        ``cone`` degrees of straight ahead. Something to imitate, to fill a replay buffer with, to score a learned policy
+        against (Habitat's ``ShortestPathFollower``; no counterpart in the reference). Other agents are not obstacles to
+        it: the paths are the building's. One launch and a few tensor ops; nothing waits for the host.
+
+        The paths keep a POINT clear of the walls, and an agent is a disc as wide as that clearance that physics stops dead
+        - velocity and spin - whenever it touches anything. So two things are added to the plain rule (:meth:`choose`):
+        under momentum the agent stops accelerating once it is faster than ``speed`` times the waypoint's distance (a
+        waypoint is near exactly where a corner hides the rest of the path); and an agent found at a dead stop tries a
+        sidestep, the other sidestep, a step back and a step forward in turn until one of them frees it - pressed against a
+        wall it can no longer even turn. The module counts the dead stops, so call it once per step."""
+        self.core, self.goals = core, goals
+        self.lookahead, self.cone, self.speed = int(lookahead), float(cone), speed
+        self._blocked = torch.zeros((core.n_envs, core.n_agents), dtype=torch.long, device=core.device)
+
+    #: what an agent at a dead stop tries, in turn: strafe right, strafe left, back, forward
+    ESCAPE = (3, 4, 2, 1)
+    #: the least speed limit, m/s: one forward action from rest under :class:`MomentumMovement` stays below it
+    CREEP = .6
+
+    @staticmethod
+    def choose(local, cone=45., velocity=None, blocked=None, speed=2.):
+        """The rule, a pure function of its arguments. ``local`` (..., 2): the waypoint's offset in the agent's frame (x to the
+        right, y ahead, as :func:`to_local_frame` gives it): forward (1) when ``y > 0`` and ``|x| <= y*tan(cone)``; otherwise
+        turn left (5) when ``x < 0``, else turn right (6). ``velocity`` (..., 2), optional: the agent's velocity in its own
+        frame, m/s - forward becomes nothing (0) while the speed ahead exceeds ``max(speed*|local|, CREEP)``. ``blocked``
+        (...) integers, optional: for how many decisions in a row the agent has been at a dead stop - where positive, the
+        action is ``ESCAPE[(blocked - 1) % 4]`` instead. Nothing (0) where the waypoint is NaN. Returns (...) int64, the
+        movement modules' actions."""
+        x, y = local[..., 0], local[..., 1]
+        ahead = (y > 0) & (x.abs() <= y*float(np.tan(np.deg2rad(cone))))
+        actions = torch.where(ahead, 1, torch.where(x < 0, 5, 6))
+        if velocity is not None and speed is not None:
+            limit = (speed*local.norm(dim=-1)).clamp(min=PathFollower.CREEP)
+            actions = torch.where(ahead & (velocity[..., 1] > limit), 0, actions)
+        if blocked is not None:
+            turn = (blocked - 1) % 4                                    # (scalars only: nothing here may copy from the host)
+            e0, e1, e2, e3 = PathFollower.ESCAPE
+            escape = torch.where(turn == 0, e0, torch.where(turn == 1, e1, torch.where(turn == 2, e2, e3)))
+            actions = torch.where(blocked > 0, escape, actions)
+        return torch.where(torch.isnan(x) | torch.isnan(y), 0, actions)
+
+    def __call__(self):
+        """``arrdict(actions=(n_env, n_agent) int64)``: the decision for the agents as they stand."""
+        agents = self.core.agents
+        still = (agents.velocity == 0).all(-1) & (agents.angvelocity == 0)
+        self._blocked.copy_(torch.where(still, self._blocked + 1, torch.zeros_like(self._blocked)))
+        local = to_local_frame(agents.angles, self.goals.waypoints(self.lookahead) - agents.positions)
+        velocity = to_local_frame(agents.angles, agents.velocity)
+        return arrdict.arrdict(actions=self.choose(local, self.cone, velocity, self._blocked, self.speed))

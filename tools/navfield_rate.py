@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs]
+                                  [--only fields|query|torch|envs|expert]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -12,6 +12,11 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       shifted minimums a sweep, swept until nothing changes (checked every 16 sweeps: each check is a host round trip).  It
       runs on the first `--torch-envs` envs and is scaled to `--envs`; its fields are compared with the kernel's as bits -
       a third statement of the rule beside tests/test_navfield_host.nav_rule and the kernel.
+  (e) the shortest-path expert: one DistanceFields.waypoints (ms_nav_waypoints) of one agent an env and one DistanceFields.paths
+      (ms_nav_paths, 256 points a path); PointGoal(envs): expert() + step() eager and replayed as a HIP graph, next to step()
+      alone; and from a 200-step rollout of PointGoal(64), under the expert and under the compass policy of the PointGoal tests
+      (turn until the goal's straight line is ahead, then walk; one step in four random): arrivals, episodes, and the mean of
+      (metres walked)/(walking distance at the episode's start) over the episodes that arrived.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -131,6 +136,58 @@ def env_rates(env, n, steps, warm):
     return eager, (time.perf_counter() - t)/steps
 
 
+class ExpertStep:
+    """An env whose step is the expert's own: expert() + step(), the decision handed in ignored."""
+
+    def __init__(self, env):
+        self.env, self.action_space = env, env.action_space
+
+    def reset(self):
+        return self.env.reset()
+
+    def step(self, decision):
+        return self.env.step(self.env.expert())
+
+
+def rollout_score(env, steps, policy, seed=1):
+    """(episodes, arrivals, mean walked/start distance, mean walked/distance covered - both over the episodes that arrived)
+    of `steps` steps under 'expert' (env.expert()) or 'compass'; episodes in which the agent was stranded do not count."""
+    from megastep_amd import arrdict
+    rng = np.random.RandomState(seed)
+    n, a = env.core.n_envs, env.core.n_agents
+    world = env.reset()
+    reset, g, stranded, at = [], [], [], []
+
+    def note(world):
+        reset.append(world.reset.cpu().numpy()); g.append(env._distance[:, 0].double().cpu().numpy())
+        stranded.append(env._goals.stranded[:, 0].cpu().numpy()); at.append(env.core.agents.positions[:, 0].double().cpu().numpy())
+    note(world)
+    for _ in range(steps):
+        if policy == 'expert':
+            decision = env.expert()
+        else:
+            x, y = (world.obs.goal[..., k].cpu().numpy() for k in (0, 1))
+            seek = np.where((y > 0) & (np.abs(x) < y), 1, np.where(x < 0, 5, 6))
+            decision = arrdict.arrdict(actions=torch.as_tensor(np.where(rng.rand(n, a) < .25, rng.randint(0, 7, (n, a)), seek), device='cuda'))
+        world = env.step(decision)
+        note(world)
+    reset, g, stranded, at = (np.stack(v) for v in (reset, g, stranded, at))
+    episodes = arrivals = 0
+    of_start, of_covered = [], []
+    for e in range(n):
+        starts = list(np.nonzero(reset[:, e])[0]) + [len(reset)]
+        for s, t in zip(starts[:-1], starts[1:]):
+            if stranded[s:t, e].any():
+                continue
+            episodes += 1
+            if g[t - 1, e] < env.arrive:
+                arrivals += 1
+                walked = np.linalg.norm(np.diff(at[s:t, e], axis=0), axis=1).sum()
+                of_start.append(walked/g[s, e]); of_covered.append(walked/(g[s, e] - g[t - 1, e]))
+    mean = lambda v: float(np.mean(v)) if v else None
+    return dict(episodes=episodes, arrivals=arrivals, walked_over_start_distance=mean(of_start), walked_over_distance_covered=mean(of_covered))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', type=int, default=4096)
@@ -138,7 +195,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
@@ -188,6 +245,42 @@ def main():
             print(f'(c) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
             del env
             torch.cuda.empty_cache()
+
+    if want('expert'):
+        sc = scene.scenery(geoms, 1, device='cuda', bake=False)
+        grid = cuda.nav_grid(sc)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        goals, points = table[:, :, 0].contiguous(), table[:, :, 1].contiguous()
+        fields = cuda.distance_fields(grid, goals)
+        way = torch.empty_like(points)
+        med, lo, hi = timed(lambda: fields.waypoints(points, out=way), 5*args.repeats, args.warmup)
+        chosen = fields.waypoints(points, hops=True)[1]
+        out['waypoints'] = dict(seconds=med, min=lo, max=hi, points=args.envs, lookahead=16, with_a_path=float((chosen >= 0).float().mean()),
+                                mean_index=float(chosen[chosen >= 0].float().mean()))
+        print(f"(e) waypoints, {args.envs} x 1 points: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]; mean index {out['waypoints']['mean_index']:.2f}")
+        med, lo, hi = timed(lambda: fields.paths(points, max_points=256), args.repeats, args.warmup)
+        counts = fields.paths(points, max_points=256).counts
+        out['paths'] = dict(seconds=med, min=lo, max=hi, points=args.envs, max_points=256, longest=int(counts.max()), mean_points=float(counts[counts > 0].float().mean()))
+        print(f"(e) paths, {args.envs} x 1 paths of up to 256 points: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]; longest {out['paths']['longest']} points")
+        del sc, grid, fields
+        torch.cuda.empty_cache()
+        env = PointGoal(args.envs, geometries=geoms)
+        eager, graphed = env_rates(env, args.envs, 60, 10)
+        del env
+        torch.cuda.empty_cache()
+        env = ExpertStep(PointGoal(args.envs, geometries=geoms))
+        expert_eager, expert_graphed = env_rates(env, args.envs, 60, 10)
+        out['expert_step'] = dict(step_eager_seconds=eager, step_graph_seconds=graphed, expert_step_eager_seconds=expert_eager,
+                                  expert_step_graph_seconds=expert_graphed)
+        print(f'(e) PointGoal({args.envs}): step eager {eager*1e3:.3f} ms, graph {graphed*1e3:.3f} ms; expert + step eager {expert_eager*1e3:.3f} ms, '
+              f'graph {expert_graphed*1e3:.3f} ms')
+        del env
+        torch.cuda.empty_cache()
+        small = cubicasa.sample(64, seed=7, n_unique=64)
+        for policy in ('expert', 'compass'):
+            torch.manual_seed(3); np.random.seed(3)
+            out['rollout_' + policy] = score = rollout_score(PointGoal(64, geometries=small, bonus=0., max_lifespan=120), 200, policy)
+            print(f'(e) PointGoal(64), 200 steps, {policy}: {score}')
 
     if args.json:
         with open(args.json, 'w') as f:
