@@ -116,12 +116,69 @@ class MsNavPaths(C.Structure):
                 ('n_goals', C.c_int), ('max_points', C.c_int), ('paths', C.c_void_p), ('counts', C.c_void_p)]
 
 
-#: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare
-SYMBOLS = ('ms_host_ray_interval_wide', 'ms_debug_render_order', 'ms_host_order_fans', 'ms_debug_ray_groups', 'ms_debug_last_render_groups', 'ms_debug_last_step_fused', 'ms_step_render', 'ms_move_step_render', 'ms_debug_ray_group_tail', 'ms_debug_physics_pack', 'ms_host_render_plan', 'ms_host_render_block', 'ms_host_physics_pack', 'ms_debug_pair_telemetry', 'ms_test_arithmetic', 'ms_abi_version', 'ms_strerror', 'ms_last_hip_error', 'ms_device_count', 'ms_bake', 'ms_physics', 'ms_move_physics',
-           'ms_step_physics', 'ms_deathmatch_shoot', 'ms_explorer_books',
-           'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_nav_free', 'ms_nav_fields', 'ms_nav_query', 'ms_nav_waypoints', 'ms_nav_paths', 'ms_host_nav_waypoint', 'ms_host_nav_path', 'ms_debug_overhead_cull', 'ms_host_overhead_keeps', 'ms_host_sincospi', 'ms_host_bake_point_bin', 'ms_host_bake_wall_bins',
-           'ms_wallgrid_scan', 'ms_wallgrid_fill', 'ms_host_wall_hidden', 'ms_host_wall_sectors', 'ms_host_wallgrid_cell', 'ms_host_wall_arc',
-           'ms_host_wedge_meets', 'ms_host_agents_apart', 'ms_host_wall_beyond_reach', 'ms_host_ray_interval', 'ms_host_fold_hits', 'ms_host_lightgrid_cell', 'ms_host_wall_reach')
+_int, _flt, _ptr, _p = C.c_int, C.c_float, C.c_void_p, C.POINTER
+
+#: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare, as
+#: ``name: (restype, [argtypes])`` - the one place a prototype is written down: lib() binds by it, and tests/test_abi.py holds
+#: it against the headers' declarations
+PROTOTYPES = {
+    'ms_abi_version': (_int, []),
+    'ms_strerror': (C.c_char_p, [_int]),
+    'ms_last_hip_error': (_int, []),
+    'ms_device_count': (_int, []),
+    'ms_bake': (_int, [_p(MsScenery), _p(MsConfig), _ptr]),
+    'ms_physics': (_int, [_p(MsScenery), _p(MsAgents), _ptr, _p(MsConfig), _ptr]),
+    'ms_move_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _ptr, _p(MsConfig), _ptr]),
+    'ms_step_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _ptr, _p(MsConfig), _ptr]),
+    'ms_render': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRender), _p(MsConfig), _ptr]),
+    'ms_step_render': (_int, [_p(MsScenery), _p(MsAgents), _ptr, _p(MsRender), _p(MsConfig), _ptr]),
+    'ms_move_step_render': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _ptr, _p(MsRender), _p(MsConfig), _ptr]),
+    'ms_deathmatch_shoot': (_int, [_int, _int, _p(MsDeathmatch), _ptr]),
+    'ms_explorer_books': (_int, [_int, _p(MsExplorer), _ptr]),
+    'ms_raycast': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRaycast), _p(MsConfig), _ptr]),
+    'ms_camera_rays': (_int, [_p(MsAgents), _int, _int, _p(MsConfig), _ptr, _ptr]),
+    'ms_overhead': (_int, [_p(MsScenery), _p(MsAgents), _p(MsOverhead), _ptr]),
+    'ms_nav_free': (_int, [_p(MsScenery), _p(MsNavGrid), _ptr]),
+    'ms_nav_fields': (_int, [_p(MsNavGrid), _p(MsNavFields), _ptr]),
+    'ms_nav_query': (_int, [_p(MsNavGrid), _p(MsNavQuery), _ptr]),
+    'ms_nav_waypoints': (_int, [_p(MsNavGrid), _p(MsNavWaypoints), _ptr]),
+    'ms_nav_paths': (_int, [_p(MsNavGrid), _p(MsNavPaths), _ptr]),
+    'ms_wallgrid_scan': (_int, [_p(MsScenery), _p(MsWallGridParent), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr]),
+    'ms_wallgrid_fill': (_int, [_p(MsScenery), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # the test hooks
+    'ms_host_ray_interval': (None, [_f32p, _f32p, _int, _flt, _flt, _int, _i32p, _i32p]),
+    'ms_host_ray_interval_wide': (None, [_f32p, _f32p, _int, _flt, _flt, _int, _int, _i32p, _i32p]),
+    'ms_debug_ray_groups': (_int, [_int]),
+    'ms_debug_physics_pack': (_int, [_int]),
+    'ms_debug_last_render_groups': (_int, []),
+    'ms_debug_last_step_fused': (_int, []),
+    'ms_host_render_plan': (C.c_longlong, [_int, _int, _int, _int, _int, _flt, _int, _i32p]),
+    'ms_host_render_block': (_int, [_int, _int, _int, _int, _int, _flt, _int, C.c_longlong, _i32p]),
+    'ms_host_physics_pack': (_int, [_int, _int, _int, _int]),
+    'ms_debug_render_order': (_int, [_int]),
+    'ms_host_order_fans': (_int, [_int, _i32p, _i32p]),
+    'ms_debug_ray_group_tail': (_int, [_flt, _int]),
+    'ms_debug_pair_telemetry': (_int, [_int]),
+    'ms_debug_overhead_cull': (_int, [_int]),
+    'ms_host_overhead_keeps': (_int, [_f32p, _int, _int, _int, _int, _flt, _f32p]),
+    'ms_host_nav_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_host_nav_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
+    'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
+    'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),
+    'ms_host_agents_apart': (_int, [_f32p, _f32p, _flt]),
+    'ms_host_wall_beyond_reach': (_int, [_f32p, _f32p, _flt]),
+    'ms_host_wall_reach': (_flt, [_f32p, _flt]),
+    'ms_host_wall_hidden': (_int, [_flt]*4 + [_f32p, _f32p, _flt]),
+    'ms_host_wall_sectors': (None, [_flt]*4 + [_f32p, _i32p, _i32p, _f32p, _i32p]),
+    'ms_host_wallgrid_cell': (None, [_ptr, _int, _flt, _flt, _int, _int, _flt, _int, _flt, _flt, _flt, _ptr, _ptr]),
+    'ms_host_wall_arc': (None, [_flt]*4 + [_f32p, _i32p, _i32p]),
+    'ms_host_wedge_meets': (_int, [_flt]*4 + [_int, _int]),
+    'ms_host_sincospi': (None, [_flt, _f32p, _f32p]),
+    'ms_host_bake_point_bin': (_int, [_flt]*4),
+    'ms_host_bake_wall_bins': (None, [_flt]*6 + [_i32p, _i32p]),
+}
+SYMBOLS = tuple(PROTOTYPES)
 
 
 def _source_hash():
@@ -189,104 +246,9 @@ def lib():
         missing = [s for s in SYMBOLS if not hasattr(handle, s)]
         if missing:
             raise ImportError(f'{LIB_PATH} does not export {missing}')
-        handle.ms_abi_version.restype = C.c_int
-        handle.ms_strerror.restype = C.c_char_p
-        handle.ms_strerror.argtypes = [C.c_int]
-        handle.ms_last_hip_error.restype = C.c_int
-        handle.ms_device_count.restype = C.c_int
-        handle.ms_bake.argtypes = [C.POINTER(MsScenery), C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_physics.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.c_void_p, C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_move_physics.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsMovement), C.c_void_p,
-                                           C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_step_physics.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsMovement), C.POINTER(MsStepExtras),
-                                           C.c_void_p, C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_step_render.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.c_void_p, C.POINTER(MsRender), C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_step_render.restype = C.c_int
-        handle.ms_move_step_render.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsMovement), C.POINTER(MsStepExtras),
-                                               C.c_void_p, C.POINTER(MsRender), C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_move_step_render.restype = C.c_int
-        handle.ms_debug_last_step_fused.argtypes = []
-        handle.ms_debug_last_step_fused.restype = C.c_int
-        handle.ms_explorer_books.argtypes = [C.c_int, C.POINTER(MsExplorer), C.c_void_p]
-        handle.ms_explorer_books.restype = C.c_int
-        handle.ms_deathmatch_shoot.argtypes = [C.c_int, C.c_int, C.POINTER(MsDeathmatch), C.c_void_p]
-        handle.ms_deathmatch_shoot.restype = C.c_int
-        handle.ms_render.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsRender), C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_raycast.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsRaycast), C.POINTER(MsConfig), C.c_void_p]
-        handle.ms_camera_rays.argtypes = [C.POINTER(MsAgents), C.c_int, C.c_int, C.POINTER(MsConfig), C.c_void_p, C.c_void_p]
-        handle.ms_overhead.argtypes = [C.POINTER(MsScenery), C.POINTER(MsAgents), C.POINTER(MsOverhead), C.c_void_p]
-        handle.ms_nav_free.argtypes = [C.POINTER(MsScenery), C.POINTER(MsNavGrid), C.c_void_p]
-        handle.ms_nav_fields.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavFields), C.c_void_p]
-        handle.ms_nav_query.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavQuery), C.c_void_p]
-        handle.ms_nav_waypoints.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavWaypoints), C.c_void_p]
-        handle.ms_nav_paths.argtypes = [C.POINTER(MsNavGrid), C.POINTER(MsNavPaths), C.c_void_p]
-        handle.ms_host_nav_waypoint.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        handle.ms_host_nav_waypoint.restype = C.c_int
-        handle.ms_host_nav_path.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        handle.ms_host_nav_path.restype = C.c_int
-        handle.ms_debug_overhead_cull.argtypes = [C.c_int]
-        handle.ms_debug_overhead_cull.restype = C.c_int
-        handle.ms_host_overhead_keeps.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p]
-        handle.ms_host_overhead_keeps.restype = C.c_int
-        handle.ms_host_sincospi.argtypes = [C.c_float, _f32p, _f32p]
-        handle.ms_host_bake_point_bin.argtypes = [C.c_float]*4
-        handle.ms_host_bake_point_bin.restype = C.c_int
-        handle.ms_host_bake_wall_bins.argtypes = [C.c_float]*6 + [_i32p, _i32p]
-        handle.ms_host_bake_wall_bins.restype = None
-        handle.ms_wallgrid_scan.argtypes = [C.POINTER(MsScenery), C.POINTER(MsWallGridParent), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
-        handle.ms_wallgrid_fill.argtypes = [C.POINTER(MsScenery), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
-        handle.ms_host_wall_sectors.argtypes = [C.c_float]*4 + [_f32p, _i32p, _i32p, _f32p, _i32p]
-        handle.ms_host_wall_sectors.restype = None
-        handle.ms_host_wall_arc.argtypes = [C.c_float]*4 + [_f32p, _i32p, _i32p]
-        handle.ms_host_wall_arc.restype = None
-        handle.ms_host_wedge_meets.argtypes = [C.c_float]*4 + [C.c_int, C.c_int]
-        handle.ms_host_wedge_meets.restype = C.c_int
-        handle.ms_host_ray_interval.argtypes = [_f32p, _f32p, C.c_int, C.c_float, C.c_float, C.c_int, _i32p, _i32p]
-        handle.ms_host_ray_interval.restype = None
-        handle.ms_host_ray_interval_wide.argtypes = [_f32p, _f32p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _i32p, _i32p]
-        handle.ms_host_ray_interval_wide.restype = None
-        handle.ms_debug_ray_groups.argtypes = [C.c_int]
-        handle.ms_debug_ray_groups.restype = C.c_int
-        handle.ms_debug_last_render_groups.argtypes = []
-        handle.ms_debug_last_render_groups.restype = C.c_int
-        handle.ms_debug_ray_group_tail.argtypes = [C.c_float, C.c_int]
-        handle.ms_debug_physics_pack.argtypes = [C.c_int]
-        handle.ms_debug_physics_pack.restype = C.c_int
-        handle.ms_host_render_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int)]
-        handle.ms_host_render_plan.restype = C.c_longlong
-        handle.ms_host_render_block.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
-        handle.ms_host_render_block.restype = C.c_int
-        handle.ms_host_physics_pack.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-        handle.ms_host_physics_pack.restype = C.c_int
-        handle.ms_debug_ray_group_tail.restype = C.c_int
-        handle.ms_debug_render_order.argtypes = [C.c_int]
-        handle.ms_debug_render_order.restype = C.c_int
-        handle.ms_host_order_fans.argtypes = [C.c_int, _i32p, _i32p]
-        handle.ms_host_order_fans.restype = C.c_int
-        handle.ms_debug_pair_telemetry.argtypes = [C.c_int]
-        handle.ms_debug_pair_telemetry.restype = C.c_int
-        handle.ms_test_arithmetic.argtypes = [C.c_void_p]*7 + [C.c_longlong, C.c_void_p]
-        handle.ms_test_arithmetic.restype = C.c_int
-        handle.ms_host_fold_hits.argtypes = [_f32p, _i32p, C.c_int, _i32p, _f32p, _i32p]
-        handle.ms_host_fold_hits.restype = C.c_int
-        handle.ms_host_lightgrid_cell.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
-                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        handle.ms_host_lightgrid_cell.restype = C.c_int
-        handle.ms_host_agents_apart.argtypes = [_f32p, _f32p, C.c_float]
-        handle.ms_host_agents_apart.restype = C.c_int
-        handle.ms_host_wall_beyond_reach.argtypes = [_f32p, _f32p, C.c_float]
-        handle.ms_host_wall_beyond_reach.restype = C.c_int
-        handle.ms_host_wall_reach.argtypes = [_f32p, C.c_float]
-        handle.ms_host_wall_reach.restype = C.c_float
-        handle.ms_host_wall_hidden.argtypes = [C.c_float]*4 + [_f32p, _f32p, C.c_float]
-        handle.ms_host_wall_hidden.restype = C.c_int
-        handle.ms_host_wallgrid_cell.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int,
-                                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-        handle.ms_host_wallgrid_cell.restype = None
-        for name in ('ms_bake', 'ms_physics', 'ms_move_physics', 'ms_step_physics', 'ms_render', 'ms_raycast', 'ms_camera_rays', 'ms_overhead', 'ms_nav_free', 'ms_nav_fields', 'ms_nav_query', 'ms_nav_waypoints', 'ms_nav_paths', 'ms_wallgrid_scan', 'ms_wallgrid_fill'):
-            getattr(handle, name).restype = C.c_int
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if handle.ms_abi_version() != ABI_VERSION:
             raise ImportError(f'{LIB_PATH} has ABI {handle.ms_abi_version()}, this package needs {ABI_VERSION}; rebuild it')
         _lib = handle

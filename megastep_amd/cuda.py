@@ -5,23 +5,23 @@ Mirrors the reference's pybind module ``megastepcuda`` (reference: megastep/src/
 point is a hand-written gfx950 kernel reached through the C-ABI in ``include/megastep_hip.h``. Tensors stay torch-owned
 (PyTorch-ROCm is the allocator/stream plumbing); the kernels run on ``torch.cuda.current_stream()``.
 
+The calls without a counterpart in the reference live in modules named after the kernel files they drive - ``rays``,
+``overhead``, ``nav`` and ``envlogic`` - and are imported at the end of this one, so each is still ``cuda.<name>``.
+
 There is no CPU implementation here, exactly as in the reference ("If you haven't got CUDA, megastep will not work",
 reference: docs/faq.rst:23-26): calling bake/physics/render on non-GPU tensors raises.
 """
 import ctypes as C
-import math
 import numbers
 import os
 import torch
-from . import _lib, grids
+from . import _call, _lib, grids
 from ._lib import _on, _stream
+from ._call import _agents_on, _cfg, _check, _require_gpu, config
 
 # ---------------------------------------------------------------------------------------------------------------------
 # initialize                                                                   reference: kernels.cu:18-27
 # ---------------------------------------------------------------------------------------------------------------------
-_config = None
-
-
 _switched = __import__('threading').local()
 
 
@@ -47,64 +47,13 @@ def _ab_switches():
         _lib.lib().ms_debug_ray_group_tail(float(t) if t else -1., int(e) if e else -1)
 
 
-def config(agent_radius, res, fov, fps):
-    """The four constants of :func:`initialize` as a value (the C-ABI's ``MsConfig``, passed by value with every launch):
-    what a :class:`~megastep_amd.core.Core` keeps for itself and hangs on its ``Agents``, so that several Cores of
-    different resolutions, fields of view or frame rates live side by side in one process - on one device or several."""
-    if not (0 < fov < 180):
-        raise RuntimeError('fov must be in (0, 180) degrees')
-    if res <= 0 or fps <= 0 or agent_radius <= 0:
-        raise RuntimeError('agent_radius, res and fps must be positive')
-    return _lib.MsConfig(float(agent_radius), int(res), float(fov), float(fps))
-
-
 def initialize(agent_radius, res, fov, fps):
     """Sets the constants used by :func:`physics` and :func:`render` for callers that hand them bare tensors' holders
     (reference: wrappers.cpp:53) - the drop-in path. As in the reference this is process-global; unlike it, nothing
     device-side is mutated (the values travel by value with every launch), and it is only the FALLBACK: a call that is
     given ``config=``, or whose ``agents`` carry one (every ``Core``'s do), never looks at it."""
-    global _config
-    _config = config(agent_radius, res, fov, fps)
+    _call._config = config(agent_radius, res, fov, fps)
     _ab_switches()
-
-
-def _cfg(agents=None, explicit=None):
-    """The constants of one call: the ``config=`` argument, else the ones the agents' Core hung on them, else initialize()'s."""
-    if explicit is not None:
-        if not isinstance(explicit, _lib.MsConfig):
-            raise RuntimeError('config must come from megastep_amd.cuda.config(agent_radius, res, fov, fps)')
-        return explicit
-    own = getattr(agents, '_config', None)
-    if own is not None:
-        return own
-    if _config is None:
-        raise RuntimeError('megastep_amd.cuda.initialize(agent_radius, res, fov, fps) has not been called')
-    return _config
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# checks                                                                       reference: common.h:12-14,33-37
-# ---------------------------------------------------------------------------------------------------------------------
-def _check(t, name, dtype, ndim):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f'{name} must be a tensor')
-    if not t.is_contiguous():
-        raise RuntimeError(f'{name} must be contiguous')
-    if t.dtype != dtype:
-        raise RuntimeError(f'{name} must have dtype {dtype}, not {t.dtype}')
-    if t.ndim != ndim:
-        raise RuntimeError(f'{name} must be {ndim}-dimensional, not {t.ndim}')
-    return t
-
-
-def _require_gpu(*tensors):
-    dev = tensors[0].device
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError('megastep_amd kernels need GPU (HIP) tensors; got a tensor on ' + str(t.device))
-        if t.device != dev:
-            raise RuntimeError(f'all tensors must live on one device; got {t.device} and {dev}')
-    return dev
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -272,6 +221,7 @@ class Scenery:
         self._wg_weights = None
         self._wg = None             # the grids.WallGrid, or None; made by bake()
         self._wg_report = self._lg_report = None      # what was built, at which cell size, in how many bytes (grid_report())
+        self._bake_marks = self._bake_s = None        # the last bake()'s events, and the seconds read off them (grid_report())
         self._dev = None
 
     n_agents = property(lambda self: self._n_agents)
@@ -323,12 +273,12 @@ class Scenery:
         None, 'light_grid': {bytes, cell, cells, candidate_rows, ...} or None, 'bake_seconds': {lighting, wall_grid} of the last
         cuda.bake()} - the sizes actually allocated and the cell sizes actually used (either grid coarsens itself to stay inside
         its byte budget)."""
-        marks = getattr(self, '_bake_marks', None)
-        if getattr(self, '_bake_s', None) is None and marks is not None and marks[0] is not None:
+        marks = self._bake_marks
+        if self._bake_s is None and marks is not None and marks[0] is not None:
             ev, wall_grid = marks
             ev[2].synchronize()
             self._bake_s = dict(lighting=ev[0].elapsed_time(ev[1])*1e-3, wall_grid=ev[1].elapsed_time(ev[2])*1e-3 if wall_grid else 0.)
-        return dict(wall_grid=self._wg_report, light_grid=self._lg_report, bake_seconds=getattr(self, '_bake_s', None))
+        return dict(wall_grid=self._wg_report, light_grid=self._lg_report, bake_seconds=self._bake_s)
 
     _light_grid = grids.light_grid      # (builds a fresh light grid each call; _as_struct decides once per scenery)
 
@@ -357,6 +307,14 @@ class Scenery:
         if self._wg is not None and self._wg_sum != grids.wall_checksum(self):
             raise RuntimeError('static walls have been changed since cuda.bake() built the wall grid from them: bake again '
                                '(or bake(wall_grid=False) to go without a grid)')
+
+    def _check_grid(self, dev):
+        """What every call that walks the wall grid asks first while ``CHECK_GRID`` is on (not inside a stream capture)."""
+        if CHECK_GRID and self._wg is not None:
+            with _on(dev):                                                    # (the stream that matters is `dev`'s current one)
+                capturing = torch.cuda.is_current_stream_capturing()
+            if not capturing:
+                self.check_wall_grid()
 
     def _build_wall_grid(self):
         """(Re)builds the wall grid from the static walls as they are now (called by :func:`bake`; see grids.wall_grid)."""
@@ -417,13 +375,6 @@ class Physics:
 # ---------------------------------------------------------------------------------------------------------------------
 # kernels
 # ---------------------------------------------------------------------------------------------------------------------
-def _agents_on(agents, dev):
-    if agents._dev != dev:
-        if agents._dev is None or not agents._dev.type == 'cuda':
-            raise RuntimeError('megastep_amd kernels need GPU (HIP) tensors; the agents are on ' + str(agents._dev or 'several devices'))
-        raise RuntimeError(f'all tensors must live on one device; got {agents._dev} and {dev}')
-
-
 def _ms_agents(agents, step, telemetry=False):
     """The MsAgents a launch gets: with the heading cache where the launch fills it (a physics step, while the agents use the
     cache) or reads it (a render after a physics call filled it - not with ``telemetry``, whose counters the self-contained path
@@ -444,7 +395,7 @@ def bake(scenery, scratch=True, wall_grid=True):
     dev = scenery._device()
     # bake uses none of the initialize() constants (kernels.cu:238-293), and scene.scenery() calls it before any Core
     # exists, so the config is optional here
-    cfg = C.byref(_config) if _config is not None else None
+    cfg = C.byref(_call._config) if _call._config is not None else None
     struct = scenery._as_struct()
     if scratch:
         vis, starts = scenery._bake_plan()
@@ -540,85 +491,32 @@ def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=No
         raise RuntimeError('agents do not match the scenery: expected (n_envs, n_agents) = '
                            f'{shape}, got {tuple(agents.angles.shape)}')
     mv, ex = _step_options(agents, shape, movement, respawn, lifespans, imu)
-    progress = torch.empty_like(agents.angles) if out is None else out.progress      # `out`: an earlier call's Physics
+    progress = _progress(agents, out)
     _ab_switches()
-    _check_grid(scenery, dev)
+    scenery._check_grid(dev)
     with _on(dev):
         _lib.check(_lib.lib().ms_step_physics(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)),
                                               mv, ex, C.c_void_p(progress.data_ptr()), C.byref(_cfg(agents, config)), _stream(dev)))
+    return _stepped(agents, progress, out)
+
+
+def _progress(agents, out):
+    """The (N, A) tensor a step writes its progress to: the one of ``out``, an earlier call's Physics, else a fresh one."""
+    return torch.empty_like(agents.angles) if out is None else out.progress
+
+
+def _stepped(agents, progress, out):
+    """What a step leaves behind: the agents' heading cache filled (where they use it) and their epoch moved on; ``progress``
+    as a :class:`Physics` - ``out`` if the step wrote into one."""
     agents._cached = agents._use_cache
     agents._epoch += 1
     return Physics(progress) if out is None else out
-
-
-def deathmatch_shoot(centre, positions, upper, health, damage, dead, clearance=1., hit_damage=.05, tick_damage=.001,
-                     out=None, matchings=False):
-    """The Deathmatch env's game logic between one frame and the next as ONE launch (include/megastep_hip.h, MsDeathmatch;
-    reference: demo/envs/deathmatch.py:46-88 - ``_reset`` + ``_shoot`` + the ``health`` observation, some twenty tensor ops).
-
-    ``centre`` (N, A, 2) int32: :func:`render`'s ``obs_centre`` of this frame; ``positions`` (N, A, 2); ``upper`` (N, 2): the
-    floorplans' extents + clearance; ``health``, ``damage`` (N, A) float32 and ``dead`` (N, A) bool, all updated IN PLACE:
-    agents marked in ``dead`` (the mask this step's physics launch respawned by) start from health 1 / damage 0, then
-    everyone takes this frame's hits, wounds and strays, and ``dead`` becomes ``health <= 0`` - the next step's mask.
-    Returns ``(reset, reward, health_obs[, matchings])``: the incoming ``dead``, the hits dealt, a copy of the new health -
-    fresh tensors, or the ones of an earlier call passed as ``out``."""
-    n, a = health.shape
-    _check(centre, 'centre', torch.int32, 3); _check(positions, 'positions', torch.float32, 3); _check(upper, 'upper', torch.float32, 2)
-    _check(health, 'health', torch.float32, 2); _check(damage, 'damage', torch.float32, 2); _check(dead, 'dead', torch.bool, 2)
-    if centre.shape != (n, a, 2) or positions.shape != (n, a, 2) or upper.shape != (n, 2) or damage.shape != (n, a) or dead.shape != (n, a):
-        raise RuntimeError('deathmatch_shoot: centre (N, A, 2), positions (N, A, 2), upper (N, 2), health / damage / dead (N, A)')
-    dev = _require_gpu(centre, positions, upper, health, damage, dead)
-    if out is None:
-        out = (torch.empty_like(dead), torch.empty_like(health), torch.empty_like(health)) + \
-              ((torch.empty((n, a, a), dtype=torch.bool, device=dev),) if matchings else ())
-    dm = _lib.MsDeathmatch(centre.data_ptr(), positions.data_ptr(), upper.data_ptr(), float(clearance), float(hit_damage), float(tick_damage),
-                           health.data_ptr(), damage.data_ptr(), dead.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                           out[3].data_ptr() if len(out) > 3 else None)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_deathmatch_shoot(n, a, C.byref(dm), _stream(dev)))
-    return out
-
-
-def explorer_books(tally, before, lengths, epoch, over, slack, pixels, display=False):
-    """The Explorer env's bookkeeping between one frame and the next as ONE launch (include/megastep_hip.h, MsExplorer;
-    reference: demo/envs/explorer.py:45-90 - the reward, the counters of ``_reset`` and the episode rule of ``step``, a dozen
-    tensor ops). ``tally`` is the first-sight count :func:`render` keeps (``seen=``), ``epoch`` its epochs; ``before``,
-    ``lengths`` (N,) int32 and ``over`` (N,) bool are the env's own - all updated IN PLACE: ``over`` comes in as the envs this
-    step respawned (they get no reward) and leaves as the envs the next step is to respawn, which have already forgotten what
-    they saw. Returns ``(reset, reward)`` - the incoming ``over`` and this frame's reward - plus, with ``display``, the
-    potential and the lengths as this step leaves them."""
-    n = tally.shape[0]
-    for name, t in (('tally', tally), ('before', before), ('lengths', lengths), ('epoch', epoch)):
-        _check(t, name, torch.int32, 1)
-        if t.shape != (n,):
-            raise RuntimeError('explorer_books: tally, before, lengths, epoch and over must all be (N,)')
-    _check(over, 'over', torch.bool, 1)
-    if over.shape != (n,):
-        raise RuntimeError('explorer_books: tally, before, lengths, epoch and over must all be (N,)')
-    dev = _require_gpu(tally, before, lengths, epoch, over)
-    ptrs = (tally.data_ptr(), before.data_ptr(), lengths.data_ptr(), epoch.data_ptr(), over.data_ptr())
-    reset = torch.empty_like(over)
-    rest = torch.empty((3 if display else 1, n), dtype=torch.float32, device=dev)         # (one allocation: reward | potential | lengths)
-    out = (reset, rest[0]) + ((rest[1], rest[2].view(torch.int32)) if display else ())
-    ex = _lib.MsExplorer(*ptrs, int(slack), int(pixels),
-                         reset.data_ptr(), rest.data_ptr(), rest.data_ptr() + 4*n if display else None, rest.data_ptr() + 8*n if display else None)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_explorer_books(n, C.byref(ex), _stream(dev)))
-    return out
 
 
 FIELDS = ('indices', 'locations', 'dots', 'distances', 'screen')
 #: MEGASTEP_CHECK_GRID=1: every render / physics call first makes sure the static walls are still the ones the wall grid
 #: was built from (a reduction over the lines and a host sync per call - for debugging and the test suite, off by default)
 CHECK_GRID = os.environ.get('MEGASTEP_CHECK_GRID', '0') not in ('', '0')
-
-
-def _check_grid(scenery, dev):
-    if CHECK_GRID and scenery._wg is not None:
-        with _on(dev):                                                    # (the stream that matters is `dev`'s current one)
-            capturing = torch.cuda.is_current_stream_capturing()
-        if not capturing:
-            scenery.check_wall_grid()
 
 
 def step_render(scenery, agents, fields=None, pooled=None, out=None, seen=None, config=None, movement=None, respawn=None,
@@ -635,13 +533,11 @@ def step_render(scenery, agents, fields=None, pooled=None, out=None, seen=None, 
     physics_out, render_out = out if out is not None else (None, None)
     dev, cfg, result = _render_call(scenery, agents, fields, pooled, render_out, seen, config)
     mv, ex = _step_options(agents, tuple(agents.angles.shape), movement, respawn, lifespans, imu)
-    progress = torch.empty_like(agents.angles) if physics_out is None else physics_out.progress
+    progress = _progress(agents, physics_out)
     with _on(dev):
         _lib.check(_lib.lib().ms_move_step_render(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)), mv, ex,
                                                   C.c_void_p(progress.data_ptr()), C.byref(result._struct), C.byref(cfg), _stream(dev)))
-    agents._cached = agents._use_cache
-    agents._epoch += 1
-    return (Physics(progress) if physics_out is None else physics_out), result
+    return _stepped(agents, progress, physics_out), result
 
 
 def render(scenery, agents, fields=None, pooled=None, telemetry=False, out=None, seen=None, config=None):
@@ -713,17 +609,22 @@ def _render_call(scenery, agents, fields, pooled, out, seen, config):
         if seen is not None:
             result._struct.seen_stamp, result._struct.seen_epoch, result._struct.seen_count = seen_ptrs
     _ab_switches()
-    _check_grid(scenery, dev)
+    scenery._check_grid(dev)
     return dev, cfg, result
 
 
 _layouts = {}
+def _selection(fields, pooled):
+    """A call's ``fields`` and ``pooled`` arguments as two hashable, comparable values."""
+    return None if fields is None else tuple(fields), None if pooled is None else tuple(sorted(pooled.items()))
+
+
 def _render_key(spec):
     """A render call's shapes, fields, pooling and books as a comparable value (see ``out=``)."""
     if spec is None:
         return None
     n, a, res, fields, pooled, dev, seen_ptrs = spec
-    return (n, a, res, None if fields is None else tuple(fields), None if pooled is None else tuple(sorted(pooled.items())), dev, seen_ptrs)
+    return (n, a, res, *_selection(fields, pooled), dev, seen_ptrs)
 
 
 def _render_buffers(scenery, n, a, r, fields, pooled, dev):
@@ -731,7 +632,7 @@ def _render_buffers(scenery, n, a, r, fields, pooled, dev):
     observations and the kernels' scratch (MS_RENDER_WORKSPACE_INTS), and the MsRender that points into it."""
     scenery._as_struct()
     lit = a == 1 or scenery._lg is not None
-    key = (n, a, r, None if fields is None else tuple(fields), None if pooled is None else tuple(sorted(pooled.items())), lit)
+    key = (n, a, r, *_selection(fields, pooled), lit)
     layout = _layouts.get(key)
     if layout is None:
         layout = _layouts[key] = _render_layout(n, a, r, fields, pooled, lit)
@@ -787,532 +688,9 @@ def _render_layout(n, a, r, fields, pooled, lit):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# ray queries                                                  no counterpart in the reference (its rays: kernels.cu:326-382)
+# the calls without a counterpart in the reference, from the modules that hold them
 # ---------------------------------------------------------------------------------------------------------------------
-RAYCAST_FIELDS = ('indices', 'locations', 'dots', 'distances', 'agents')
-
-
-class Raycast:
-    """Result of :func:`raycast`: (N, R) planes - ``indices`` (int32, env-local line, -1 on a miss), ``locations``,
-    ``dots`` (NaN on a miss), ``distances`` (+inf on a miss) and ``agents`` (int32, the agent whose body the ray hit, else
-    -1). Fields that were not asked for are ``None``."""
-
-    def __init__(self, indices, locations, dots, distances, agents):
-        self._t = (indices, locations, dots, distances, agents)
-
-    indices = property(lambda self: self._t[0])
-    locations = property(lambda self: self._t[1])
-    dots = property(lambda self: self._t[2])
-    distances = property(lambda self: self._t[3])
-    agents = property(lambda self: self._t[4])
-
-
-def raycast(scenery, origins, directions, agents=None, near=None, fields=None, out=None, config=None, grid_rays=None):
-    """Casts R rays per env from ``origins`` along ``directions`` (both (N, R, 2) float32; a direction need not have unit
-    length) by the render's per-ray rule (reference: kernels.cu:349-382) and returns :class:`Raycast`. With ``agents`` the
-    rays meet the static walls and every agent's body at its current pose (drawn in registers: ``scenery.lines`` is not
-    written); without, the static walls alone. ``near``: hits nearer than ``near`` (along the ray, in metres) are ignored -
-    default the config's ``agent_radius``, which is what keeps an agent's own rays off its body. ``fields`` names the wanted
-    outputs (default all of ``RAYCAST_FIELDS``); ``out`` takes the :class:`Raycast` of an earlier call with the same shapes and
-    fields to write into. ``config``: see :func:`physics` (only needed for the default ``near``). ``grid_rays``: an optional
-    one-element int32 tensor the kernel adds the number of rays that took the wall grid to (tests).
-
-    No host synchronisation: the call can be captured in a HIP graph and sits safely between :func:`physics` and
-    :func:`render`. The wall grid serves where it is exact and every line where not; the bits are the same."""
-    _check(origins, 'origins', torch.float32, 3)
-    _check(directions, 'directions', torch.float32, 3)
-    n, r = origins.shape[:2]
-    if origins.shape[2] != 2 or directions.shape != origins.shape:
-        raise RuntimeError(f'origins and directions must both be (N, R, 2); got {tuple(origins.shape)} and {tuple(directions.shape)}')
-    if n != len(scenery.lines) or r < 1:
-        raise RuntimeError(f'origins must be (n_envs, R, 2) with n_envs = {len(scenery.lines)} and R >= 1; got {tuple(origins.shape)}')
-    if agents is not None and tuple(agents.angles.shape) != (n, scenery.n_agents):
-        raise RuntimeError('agents do not match the scenery')
-    want = RAYCAST_FIELDS if fields is None else tuple(fields)
-    if any(f not in RAYCAST_FIELDS for f in want):
-        raise RuntimeError(f'fields must be among {RAYCAST_FIELDS}')
-    dev = _require_gpu(origins, directions)
-    if scenery._device() != dev:
-        raise RuntimeError(f'all tensors must live on one device; got {scenery._device()} and {dev}')
-    if agents is not None:
-        _agents_on(agents, dev)
-    if near is None:
-        near = _cfg(agents, config).agent_radius
-    if not near >= 0:
-        raise RuntimeError('near must be a non-negative number')
-    if grid_rays is not None:
-        _check(grid_rays, 'grid_rays', torch.int32, 1)
-        _require_gpu(grid_rays)
-    key = (n, r, want, dev)
-    if out is not None:
-        if getattr(out, '_key', None) != key:
-            raise RuntimeError('`out` must come from a raycast call with the same shapes and fields')
-        result = out
-    else:
-        planes = [torch.empty((n, r), dtype=torch.int32 if f in ('indices', 'agents') else torch.float32, device=dev)
-                  if f in want else None for f in RAYCAST_FIELDS]
-        result = Raycast(*planes)
-        result._key = key
-    ptrs = [t.data_ptr() if t is not None else None for t in result._t]
-    query = _lib.MsRaycast(r, origins.data_ptr(), directions.data_ptr(), float(near), *ptrs,
-                           grid_rays.data_ptr() if grid_rays is not None else None)
-    _check_grid(scenery, dev)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_raycast(C.byref(scenery._as_struct()), C.byref(agents._plain) if agents is not None else None,
-                                         C.byref(query), None, _stream(dev)))
-    return result
-
-
-def camera_rays(agents, config=None):
-    """The direction vector of every ray :func:`render` casts, (N, A, res, 2) float32 - by the render's own device code (ray_y,
-    reference kernels.cu:234-236,334-337). ``raycast(scenery, positions broadcast over the rays, camera_rays(agents),
-    agents=agents)`` then gives the render's ``indices``, ``locations``, ``dots`` and ``distances`` bit for bit.
-    ``config``: see :func:`physics` (``res`` and ``fov`` are read)."""
-    dev = agents._dev
-    if dev is None or dev.type != 'cuda':
-        raise RuntimeError('megastep_amd kernels need GPU (HIP) tensors; the agents are on ' + str(dev or 'several devices'))
-    cfg = _cfg(agents, config)
-    n, a = agents.angles.shape
-    dirs = torch.empty((n, a, cfg.res, 2), dtype=torch.float32, device=dev)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_camera_rays(C.byref(agents._plain), n, a, C.byref(cfg), C.c_void_p(dirs.data_ptr()), _stream(dev)))
-    return dirs
-
-
-def line_of_sight(scenery, agents, a, b, near=None, config=None):
-    """(N,) bool: in every env, whether agent ``a`` sees agent ``b`` - the ray from ``a``'s position towards ``b``'s either
-    first hits ``b``'s body or meets nothing nearer than ``b``'s position. One :func:`raycast` of one ray per env (with the
-    agents' bodies; ``near`` as there). ``a`` and ``b`` are agent numbers, or (N,) int64 tensors of them."""
-    n = agents.angles.shape[0]
-    rows = torch.arange(n, device=agents.positions.device)
-    pa, pb = agents.positions[rows, a], agents.positions[rows, b]
-    hit = raycast(scenery, pa[:, None].contiguous(), (pb - pa)[:, None].contiguous(), agents=agents, near=near,
-                  fields=('distances', 'agents'), config=config)
-    d = pb - pa
-    span = torch.sqrt(d[:, 0]*d[:, 0] + d[:, 1]*d[:, 1])             # |b - a|: the ray's direction vector's length, as the kernel has it
-    target = b if isinstance(b, int) else b.to(torch.int32)
-    return (hit.agents[:, 0] == target) | (hit.distances[:, 0] >= span)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# top-down pictures                                     reference: plotting.py (matplotlib, one env at a time on the host)
-# ---------------------------------------------------------------------------------------------------------------------
-OVERHEAD_FIELDS = ('rgb', 'indices')
-#: the reference's background (plotting.adjust_view: '#c6c1b3'), decoded to linear RGB
-OVERHEAD_BACKGROUND = tuple(float((c/255)**2.2) for c in (0xc6, 0xc1, 0xb3))
-
-
-class Overhead:
-    """Result of :func:`overhead`: ``rgb`` (K, V, 3, H, W) float32 linear RGB, planar (``spaces.MultiImage``'s layout), and
-    ``indices`` (K, V, H, W) int32, the env-local line each pixel shows or -1 (an agent's lines are the first ``A*M``:
-    ``index // M`` is the agent). Fields that were not asked for are ``None``."""
-
-    def __init__(self, rgb, indices):
-        self._t = (rgb, indices)
-
-    rgb = property(lambda self: self._t[0])
-    indices = property(lambda self: self._t[1])
-
-
-def _hw(size):
-    h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
-    if h < 1 or w < 1:
-        raise RuntimeError(f'size must be positive; got {size}')
-    return h, w
-
-
-def overhead(scenery, views, size, agents=None, envs=None, half_width=.05, lit=True, background=OVERHEAD_BACKGROUND,
-             fields=None, out=None):
-    """Draws the envs from above into tensors, every image in one launch. Image k shows env ``envs[k]`` (default: env k,
-    one image per env) through each of its views: ``views`` is (K, V, 6) float32, an affine map per view from pixel
-    coordinates (column + .5, row + .5; row 0 at the top) to world metres, ``x = g0 u + g1 w + g2``, ``y = g3 u + g4 w + g5``
-    (:func:`plan_views`, :func:`agent_views`). ``size``: an int or (H, W). A pixel shows the nearest line within
-    ``half_width`` metres of its centre - its texel, times its baked light for a wall when ``lit`` - or ``background``
-    (linear RGB). With ``agents`` the agents are drawn at their current poses (in registers: ``scenery.lines`` is not
-    written); without, their lines are taken as the scenery holds them - where the last :func:`render` drew them, which is
-    what the reference's ``scene.display`` shows. An env id out of range gives an image of ``background`` and -1.
-
-    ``fields``: the wanted outputs among ``OVERHEAD_FIELDS`` (default both); ``out``: the :class:`Overhead` of an earlier call
-    with the same shapes and fields to write into. No host synchronisation: the call can be captured in a HIP graph. The
-    per-pixel rule is written out in include/megastep_hip.h (``MsOverhead``) and DESIGN.md 3.13."""
-    _check(views, 'views', torch.float32, 3)
-    h, w = _hw(size)
-    k, v = views.shape[:2]
-    if views.shape[2] != 6 or k < 1 or v < 1:
-        raise RuntimeError(f'views must be (K, V, 6) with K, V >= 1; got {tuple(views.shape)}')
-    if envs is None:
-        if k != len(scenery.lines):
-            raise RuntimeError(f'without envs, views must have one row per env ({len(scenery.lines)}); got {tuple(views.shape)}')
-    else:
-        if not isinstance(envs, torch.Tensor) or envs.dtype.is_floating_point or envs.dtype == torch.bool:
-            raise RuntimeError('envs must be an integer tensor')
-        if envs.shape != (k,):
-            raise RuntimeError(f'envs must be (K,) = ({k},); got {tuple(envs.shape)}')
-    if agents is not None and tuple(agents.angles.shape) != (len(scenery.lines), scenery.n_agents):
-        raise RuntimeError('agents do not match the scenery')
-    want = OVERHEAD_FIELDS if fields is None else tuple(fields)
-    if not want or any(f not in OVERHEAD_FIELDS for f in want):
-        raise RuntimeError(f'fields must be a non-empty selection of {OVERHEAD_FIELDS}')
-    if not 0 <= half_width < float('inf'):
-        raise RuntimeError('half_width must be a non-negative number')
-    if len(background) != 3:
-        raise RuntimeError('background must be three linear RGB values')
-    dev = _require_gpu(views, *([envs] if envs is not None else []))
-    if scenery._device() != dev:
-        raise RuntimeError(f'all tensors must live on one device; got {scenery._device()} and {dev}')
-    if agents is not None:
-        _agents_on(agents, dev)
-    if envs is not None and envs.dtype != torch.int32:
-        envs = envs.to(torch.int32)
-    envs = envs.contiguous() if envs is not None else None
-    key = (k, v, h, w, want, dev)
-    if out is not None:
-        if getattr(out, '_key', None) != key:
-            raise RuntimeError('`out` must come from an overhead call with the same shapes and fields')
-        result = out
-    else:
-        result = Overhead(torch.empty((k, v, 3, h, w), dtype=torch.float32, device=dev) if 'rgb' in want else None,
-                          torch.empty((k, v, h, w), dtype=torch.int32, device=dev) if 'indices' in want else None)
-        result._key = key
-    rgb, idx = result._t
-    spec = _lib.MsOverhead(k, v, h, w, envs.data_ptr() if envs is not None else None, views.data_ptr(), float(half_width),
-                           1 if lit else 0, (C.c_float*3)(*map(float, background)), rgb.data_ptr() if rgb is not None else None,
-                           idx.data_ptr() if idx is not None else None)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_overhead(C.byref(scenery._as_struct()), C.byref(agents._plain) if agents is not None else None,
-                                          C.byref(spec), _stream(dev)))
-    return result
-
-
-def _view_rows(cx, cy, ex, ey, sx, sy, h, w):
-    """(..., 6) views: pixel (u, w) -> centre + (u - W/2) * ex*s + (w - H/2) * ey*s, for unit axes ex (right) and ey (down)
-    in world coordinates, s = (sx, sy) the metres per pixel."""
-    return torch.stack([ex[0]*sx, ey[0]*sy, cx - ex[0]*sx*(w/2) - ey[0]*sy*(h/2),
-                        ex[1]*sx, ey[1]*sy, cy - ex[1]*sx*(w/2) - ey[1]*sy*(h/2)], -1)
-
-
-def plan_views(scenery, size, envs=None, margin=1.):
-    """(K, 1, 6) views for :func:`overhead` of whole floorplans, north up: the square the reference's
-    ``plotting.extent(zoom=False)`` frames - the env's static lines' bounding box grown by ``margin`` metres on every side,
-    squared about its centre - fitted into an image of ``size`` (an int or (H, W)). ``envs``: which envs (default all).
-    Worked out with tensor ops on the lines' device, without a host synchronisation."""
-    h, w = _hw(size)
-    lines = scenery.lines
-    vals, widths, starts, inverse = lines.vals, lines.widths.long(), lines.starts.long(), lines.inverse.long()
-    n = len(widths)
-    af = scenery.n_agents*scenery.model.shape[0]
-    static = (torch.arange(vals.shape[0], device=vals.device) - starts[inverse]) >= af
-    pts = vals.reshape(-1, 4)
-    inf = torch.full((n, 2), float('inf'), dtype=torch.float32, device=vals.device)
-    lo_pts = torch.where(static[:, None], torch.minimum(pts[:, :2], pts[:, 2:]), torch.full_like(pts[:, :2], float('inf')))
-    hi_pts = torch.where(static[:, None], torch.maximum(pts[:, :2], pts[:, 2:]), torch.full_like(pts[:, :2], -float('inf')))
-    index = inverse[:, None].expand(-1, 2)
-    lo = inf.scatter_reduce(0, index, lo_pts, 'amin')
-    hi = (-inf).scatter_reduce(0, index, hi_pts, 'amax')
-    empty = ~torch.isfinite(lo).all(1)                                   # (an env without walls: a 2 margin square about 0)
-    lo = torch.where(empty[:, None], torch.zeros_like(lo), lo) - margin
-    hi = torch.where(empty[:, None], torch.zeros_like(hi), hi) + margin
-    if envs is not None:
-        envs = torch.as_tensor(envs, device=vals.device).long()
-        lo, hi = lo[envs], hi[envs]
-    centre = (lo + hi)/2
-    half = torch.maximum(hi[:, 0] - lo[:, 0], hi[:, 1] - lo[:, 1])/2
-    s = 2*half/min(h, w)
-    one, zero = torch.ones_like(s), torch.zeros_like(s)
-    rows = _view_rows(centre[:, 0], centre[:, 1], (one, zero), (zero, -one), s, s, h, w)
-    return rows[:, None].float().contiguous()
-
-
-def agent_views(agents, size, radius):
-    """(N, A, 6) views for :func:`overhead` around every agent: the agent at the image's centre, its heading pointing up,
-    the image ``2*radius`` metres across (along its shorter side; ``size`` an int or (H, W)). The egocentric local map."""
-    h, w = _hw(size)
-    a = agents.angles*(math.pi/180)
-    fx, fy = torch.cos(a), torch.sin(a)                                  # forward: up the image
-    s = torch.full_like(fx, 2*float(radius)/min(h, w))
-    p = agents.positions
-    rows = _view_rows(p[..., 0], p[..., 1], (fy, -fx), (-fx, -fy), s, s, h, w)    # right of the heading, and down = backward
-    return rows.float().contiguous()
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# shortest-path distance fields                                                no counterpart in the reference
-# ---------------------------------------------------------------------------------------------------------------------
-def _static_boxes(scenery):
-    """((N, 2) lo, (N, 2) hi) float32: the bounding box of every env's static lines (+inf / -inf for an env without any)."""
-    lines = scenery.lines
-    vals, starts, inverse = lines.vals, lines.starts.long(), lines.inverse.long()
-    n = len(lines.widths)
-    af = scenery.n_agents*scenery.model.shape[0]
-    static = (torch.arange(vals.shape[0], device=vals.device) - starts[inverse]) >= af
-    pts = vals.reshape(-1, 4)
-    inf = torch.full((n, 2), float('inf'), dtype=torch.float32, device=vals.device)
-    lo_pts = torch.where(static[:, None], torch.minimum(pts[:, :2], pts[:, 2:]), torch.full_like(pts[:, :2], float('inf')))
-    hi_pts = torch.where(static[:, None], torch.maximum(pts[:, :2], pts[:, 2:]), torch.full_like(pts[:, :2], -float('inf')))
-    index = inverse[:, None].expand(-1, 2)
-    return inf.scatter_reduce(0, index, lo_pts, 'amin'), (-inf).scatter_reduce(0, index, hi_pts, 'amax')
-
-
-def nav_geometry(scenery, cell):
-    """The nav grids' placement, on the host: ((N, 4) int32 numpy ``jx0, iy0, nx, ny``, (N + 1,) int64 numpy cell starts). Env n's
-    grid covers the bounding box of its static walls and one cell of margin round it: columns ``floor(xmin/c) - 1`` to
-    ``floor(xmax/c) + 1``, rows likewise; an env without finite static walls gets no cells."""
-    import numpy as np
-    lo, hi = (t.double().cpu().numpy() for t in _static_boxes(scenery))
-    ok = np.isfinite(lo).all(1) & np.isfinite(hi).all(1)
-    c = float(np.float32(cell))
-    first = np.floor(np.where(ok[:, None], lo, 0.)/c).astype(np.int64) - 1
-    last = np.floor(np.where(ok[:, None], hi, 0.)/c).astype(np.int64) + 1
-    size = np.where(ok[:, None], last - first + 1, 0)
-    if (np.abs(first) > 2**24).any() or (size > 2**15).any():
-        raise RuntimeError(f'a nav grid of {cell} m cells over these walls would be larger than 32768 cells a side')
-    geom = np.concatenate([first, size], 1).astype(np.int32)
-    starts = np.concatenate([[0], np.cumsum(size[:, 0]*size[:, 1])]).astype(np.int64)
-    return geom, starts
-
-
-class NavGrid:
-    """Result of :func:`nav_grid`: which cells of a grid over every env's floorplan keep ``clearance`` metres clear of every
-    static wall. ``geom`` (N, 4) int32 ``jx0, iy0, nx, ny``: cell (row i, column j) of env n has its centre at
-    ``((jx0 + j) + .5)*cell, ((iy0 + i) + .5)*cell``; ``starts`` (N + 1,) int64: env n's ``nx*ny`` cells are
-    ``free[starts[n]:starts[n + 1]]``, row-major (ragged, not padded); ``free`` uint8, 1 free / 0 blocked."""
-
-    def __init__(self, geom, starts, free, cell, clearance, host_geom, host_starts):
-        self.geom, self.starts, self.free = geom, starts, free
-        self.cell, self.clearance = float(cell), float(clearance)
-        self._host_geom, self._host_starts = host_geom, host_starts
-        framed = (host_geom[:, 2].astype('int64') + 2)*(host_geom[:, 3].astype('int64') + 2)
-        framed = framed[(host_geom[:, 2] > 0) & (host_geom[:, 3] > 0)]
-        self._max_framed = int(framed.max()) if len(framed) else 0
-        self._struct = _lib.MsNavGrid(len(host_geom), self.cell, self.clearance, geom.data_ptr(), starts.data_ptr(), self._max_framed,
-                                      free.data_ptr())
-
-    n_envs = property(lambda self: len(self._host_geom))
-    #: cells of all envs together
-    n_cells = property(lambda self: int(self._host_starts[-1]))
-
-    def cells(self, e):
-        """(first cell, ny, nx) of env ``e`` (host numbers: no synchronisation)."""
-        return int(self._host_starts[e]), int(self._host_geom[e, 3]), int(self._host_geom[e, 2])
-
-    def image(self, e):
-        """(ny, nx) bool: env ``e``'s free cells, row 0 at the lowest y."""
-        s, ny, nx = self.cells(e)
-        return self.free[s:s + ny*nx].reshape(ny, nx).bool()
-
-    def centres(self, e):
-        """((nx,) x, (ny,) y) float32 of env ``e``'s cell centres, as the kernels form them."""
-        jx0, iy0, nx, ny = (int(v) for v in self._host_geom[e])
-        dev = self.free.device
-        x = (torch.arange(jx0, jx0 + nx, device=dev).float() + .5)*torch.tensor(self.cell, dtype=torch.float32, device=dev)
-        y = (torch.arange(iy0, iy0 + ny, device=dev).float() + .5)*torch.tensor(self.cell, dtype=torch.float32, device=dev)
-        return x, y
-
-
-def nav_grid(scenery, cell=.125, clearance=None, config=None):
-    """The navigation grid of every env: square cells of ``cell`` metres over the env's static walls, a cell *free* when no
-    static wall comes within ``clearance`` metres of its centre (default: the configured ``agent_radius``) - the very rule
-    :func:`overhead` draws lines of that half width by. One launch; needs neither :func:`bake` nor the wall grid. The agents'
-    own lines are not looked at: the grid is the building, not who is in it.
-
-    ``cell`` must be at most ``1.4*clearance``: then no edge between two free cells (and no leg from a point that is itself
-    ``clearance`` clear of the walls to a free cell next to it) can cross a wall, however thin or oblique - see
-    include/megastep_hip.h (``MsNavGrid``) and DESIGN.md 3.14. Envs are gridded one by one, whether or not they share a
-    floorplan."""
-    import numpy as np
-    if clearance is None:
-        clearance = _cfg(explicit=config).agent_radius
-    if not (cell > 0 and clearance > 0 and cell < float('inf') and clearance < float('inf')):
-        raise RuntimeError('cell and clearance must be positive numbers')
-    if np.float32(cell) > np.float32(1.4)*np.float32(clearance):
-        raise RuntimeError(f'cell ({cell}) must be at most 1.4 x clearance ({clearance}): a coarser grid could step through a wall')
-    dev = scenery._device()
-    host_geom, host_starts = nav_geometry(scenery, cell)
-    geom = torch.as_tensor(host_geom, device=dev).contiguous()
-    starts = torch.as_tensor(host_starts, device=dev).contiguous()
-    free = torch.zeros(max(int(host_starts[-1]), 1), dtype=torch.uint8, device=dev)
-    grid = NavGrid(geom, starts, free, cell, clearance, host_geom, host_starts)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_nav_free(C.byref(scenery._as_struct()), C.byref(grid._struct), _stream(dev)))
-    return grid
-
-
-class DistanceFields:
-    """Result of :func:`distance_fields`: for each env ``G`` fields, field (n, g) holding for every cell of env n's grid the
-    length of the shortest 8-connected path from the cell's centre to ``goals[n, g]`` (+inf on blocked cells and on cells no
-    path reaches). ``values`` is the flat float32 store: field (n, g) starts at ``G*grid.starts[n] + g*nx*ny``."""
-
-    def __init__(self, grid, goals, values, passes=None):
-        self.grid, self.goals, self.values, self.passes = grid, goals, values, passes
-
-    n_goals = property(lambda self: self.goals.shape[1])
-
-    def image(self, e, g=0):
-        """(ny, nx) float32 view of field ``g`` of env ``e``, row 0 at the lowest y."""
-        s, ny, nx = self.grid.cells(e)
-        at = self.n_goals*s + g*ny*nx
-        return self.values[at:at + ny*nx].reshape(ny, nx)
-
-    def update(self, goals=None, mask=None):
-        """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place - for ``goals`` (N, G, 2), which are
-        copied into :attr:`goals` where marked, or for the goals as they stand. One launch, no host synchronisation."""
-        if goals is not None:
-            _check(goals, 'goals', torch.float32, 3)
-            if goals.shape != self.goals.shape:
-                raise RuntimeError(f'goals must be {tuple(self.goals.shape)}; got {tuple(goals.shape)}')
-            if goals is not self.goals:
-                if mask is None:
-                    self.goals.copy_(goals)
-                else:
-                    torch.where(mask[..., None], goals, self.goals, out=self.goals)
-        _nav_fields_call(self, mask)
-        return self
-
-    def at(self, points, goal=None, out=None):
-        """(N, P) float32: the distance from each of ``points`` (N, P, 2) to a goal of its env - ``goal`` (N, P) integers name
-        the field each point asks, default point k against field k (then P must be G). The distance is the least, over the
-        (at most four) free cells round the point, of the cell's value plus the straight leg to its centre: continuous
-        enough that an agent's progress per step is not quantised to cells. +inf where no path exists. Meant for points
-        that are themselves ``clearance`` clear of the walls (an agent's centre, a spawn point): the leg of any other point
-        may cross a wall. One launch, no host synchronisation."""
-        grid = self.grid
-        _check(points, 'points', torch.float32, 3)
-        n, p = points.shape[:2]
-        if n != grid.n_envs or points.shape[2] != 2 or p < 1:
-            raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
-        if goal is None:
-            if p != self.n_goals:
-                raise RuntimeError(f'without goal, points must be one per field ({self.n_goals}); got {p}')
-        else:
-            if not isinstance(goal, torch.Tensor) or goal.dtype.is_floating_point or goal.shape != (n, p):
-                raise RuntimeError(f'goal must be an (N, P) = ({n}, {p}) integer tensor')
-            goal = goal.to(torch.int32).contiguous()
-        dev = _require_gpu(points, self.values, *([goal] if goal is not None else []))
-        if out is None:
-            out = torch.empty((n, p), dtype=torch.float32, device=dev)
-        elif out.shape != (n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise RuntimeError('`out` must be a contiguous (N, P) float32 tensor on the fields\' device')
-        spec = _lib.MsNavQuery(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
-                               self.n_goals, out.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_query(C.byref(grid._struct), C.byref(spec), _stream(dev)))
-        return out
-
-    def _queries(self, points, goal):
-        """:meth:`at`'s argument rules, for the calls that follow the fields: (n, p, goal as int32 or None, device)."""
-        grid = self.grid
-        _check(points, 'points', torch.float32, 3)
-        n, p = points.shape[:2]
-        if n != grid.n_envs or points.shape[2] != 2 or p < 1:
-            raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
-        if goal is None:
-            if p != self.n_goals:
-                raise RuntimeError(f'without goal, points must be one per field ({self.n_goals}); got {p}')
-        else:
-            if not isinstance(goal, torch.Tensor) or goal.dtype.is_floating_point or goal.shape != (n, p):
-                raise RuntimeError(f'goal must be an (N, P) = ({n}, {p}) integer tensor')
-            goal = goal.to(torch.int32).contiguous()
-        dev = _require_gpu(points, self.values, self.goals, grid.free, *([goal] if goal is not None else []))
-        return n, p, goal, dev
-
-    def waypoints(self, points, goal=None, lookahead=16, hops=False, out=None):
-        """(N, P, 2) float32: where to head for from each of ``points`` (N, P, 2) to walk to its goal (``goal``: as :meth:`at`) -
-        the furthest of the next ``lookahead`` (1..64) cells down the field that the point can see in a straight line clear of
-        the walls, the goal itself once that is in sight; NaN where no path exists (exactly where :meth:`at` gives +inf).
-        Heading for the waypoint, step after step, walks round the walls to the goal, and less far than :meth:`at` says: the
-        look-ahead cuts the grid's 8-direction staircase short. ``hops=True`` also returns (N, P) int32: how many cells
-        ahead the waypoint is (-1: no path). ``out``: the (N, P, 2) tensor to write. One launch, a wavefront a point, no host
-        synchronisation. The rule: include/megastep_hip.h (``MsNavWaypoints``), DESIGN.md 3.15."""
-        if not isinstance(lookahead, int) or not 1 <= lookahead <= 64:
-            raise RuntimeError(f'lookahead must be an integer in 1..64; got {lookahead}')
-        n, p, goal, dev = self._queries(points, goal)
-        if out is None:
-            out = torch.empty((n, p, 2), dtype=torch.float32, device=dev)
-        elif not isinstance(out, torch.Tensor) or out.shape != (n, p, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise RuntimeError('`out` must be a contiguous (N, P, 2) float32 tensor on the fields\' device')
-        chosen = torch.empty((n, p), dtype=torch.int32, device=dev) if hops else None
-        spec = _lib.MsNavWaypoints(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
-                                   self.goals.data_ptr(), self.n_goals, lookahead, out.data_ptr(), chosen.data_ptr() if hops else None)
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_waypoints(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
-        return (out, chosen) if hops else out
-
-    def paths(self, points, goal=None, max_points=256):
-        """The whole path from each of ``points`` (N, P, 2) to its goal (``goal``: as :meth:`at`), as a :class:`Paths`: the point,
-        the centres of the cells down the field, the goal; the first ``max_points`` of them written. One launch, a lane a
-        path, no host synchronisation; for drawing and for scoring, not for every step - that is :meth:`waypoints`."""
-        if not isinstance(max_points, int) or not 2 <= max_points <= 2**20:
-            raise RuntimeError(f'max_points must be an integer in 2..2^20; got {max_points}')
-        n, p, goal, dev = self._queries(points, goal)
-        pts = torch.empty((n, p, max_points, 2), dtype=torch.float32, device=dev)
-        counts = torch.empty((n, p), dtype=torch.int32, device=dev)
-        spec = _lib.MsNavPaths(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
-                               self.goals.data_ptr(), self.n_goals, max_points, pts.data_ptr(), counts.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_paths(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
-        return Paths(pts, counts)
-
-
-class Paths:
-    """Result of :meth:`DistanceFields.paths`. ``points`` (N, P, M, 2) float32: path (e, k)'s points - where it starts, cell
-    centre after cell centre, the goal - NaN in the slots not written; ``counts`` (N, P) int32: the points of the whole path,
-    which may be more than the M written; 0 where no path exists; negative (the points got, negated) where the field did not
-    lead to its goal - a stale field, or one of another grid."""
-
-    def __init__(self, points, counts):
-        self.points, self.counts = points, counts
-
-    def path(self, e, k):
-        """(n, 2): the written points of path ``k`` of env ``e`` (synchronises: n comes from the device)."""
-        n = min(abs(int(self.counts[e, k])), self.points.shape[2])
-        return self.points[e, k, :n]
-
-
-def _nav_fields_call(fields, mask):
-    grid = fields.grid
-    n, g = fields.goals.shape[:2]
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (n, g):
-            raise RuntimeError(f'mask must be an (N, G) = ({n}, {g}) bool tensor')
-        mask = mask.contiguous()
-    dev = _require_gpu(fields.goals, fields.values, grid.free, *([mask] if mask is not None else []))
-    spec = _lib.MsNavFields(g, fields.goals.data_ptr(), mask.data_ptr() if mask is not None else None, fields.values.data_ptr(),
-                            fields.passes.data_ptr() if fields.passes is not None else None)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_nav_fields(C.byref(grid._struct), C.byref(spec), _stream(dev)))
-
-
-def distance_fields(grid, goals, mask=None, out=None, passes=False):
-    """Shortest-path distance fields on the :func:`nav_grid`: for every env and each of its ``G`` goals (``goals``: (N, G, 2)
-    float32 world points) the distance from every free cell to the goal along the grid's 8-connected graph - straight steps
-    of ``cell``, diagonal steps of ``cell*1.41421356`` that cut no corner - joined to the goal by the straight legs from the
-    free cells round it. The 8-connected metric is up to 8 % longer than the true (any-angle) shortest path in open space;
-    an agent that heads for :meth:`DistanceFields.waypoints` cuts the staircase short and walks less than the field says.
-    One launch, one workgroup per field, the field relaxed in LDS until nothing changes; the result does not depend on the
-    order of relaxation and equals Dijkstra's with binary32 additions bit for bit (include/megastep_hip.h, ``MsNavGrid``).
-
-    ``mask`` (N, G) bool: compute only the marked fields (the others keep what ``out`` held); ``out``: the
-    :class:`DistanceFields` of an earlier call with the same grid and G to write into (its goals are updated where marked);
-    ``passes=True`` also records the relaxation passes each field took (``.passes``, (N, G) int32). No host synchronisation:
-    the call can be captured in a HIP graph."""
-    _check(goals, 'goals', torch.float32, 3)
-    n, g = goals.shape[:2]
-    if n != grid.n_envs or g < 1 or goals.shape[2] != 2:
-        raise RuntimeError(f'goals must be (N, G, 2) with N = {grid.n_envs} and G >= 1; got {tuple(goals.shape)}')
-    if out is not None:
-        if out.grid is not grid or out.goals.shape != goals.shape:
-            raise RuntimeError('`out` must come from a distance_fields call with the same grid and number of goals')
-        return out.update(goals, mask)
-    dev = goals.device
-    values = torch.empty(max(g*grid.n_cells, 1), dtype=torch.float32, device=dev)
-    if mask is not None:
-        values.fill_(float('inf'))                                      # (a field never computed is a field nothing reaches)
-    fields = DistanceFields(grid, goals.clone(), values, torch.zeros((n, g), dtype=torch.int32, device=dev) if passes else None)
-    _nav_fields_call(fields, mask)
-    return fields
-
-
-def geodesic(grid, a, b):
-    """(N, P) float32: the walking distance from ``a[n, k]`` to ``b[n, k]`` (both (N, P, 2)) - the fields of ``b``, asked at
-    ``a``. A convenience for a handful of pairs; keep the :func:`distance_fields` when the goals stay."""
-    return distance_fields(grid, b).at(a)
+from .envlogic import deathmatch_shoot, explorer_books
+from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
+from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, plan_views, agent_views
+from .nav import nav_geometry, NavGrid, nav_grid, DistanceFields, Paths, distance_fields, geodesic

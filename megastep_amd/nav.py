@@ -1,0 +1,278 @@
+"""Navigation grids, shortest-path distance fields, waypoints and paths on the floorplans (kernels: ``csrc/kernels/navfield.h``,
+``csrc/kernels/navpath.h``). No counterpart in the reference; reached as ``megastep_amd.cuda.<name>``."""
+import ctypes as C
+import torch
+from . import _lib
+from ._lib import _on, _stream
+from ._call import _cfg, _check, _require_gpu
+
+
+def _static_boxes(scenery):
+    """((N, 2) lo, (N, 2) hi) float32: the bounding box of every env's static lines (+inf / -inf for an env without any)."""
+    lines = scenery.lines
+    vals, starts, inverse = lines.vals, lines.starts.long(), lines.inverse.long()
+    n = len(lines.widths)
+    af = scenery.n_agents*scenery.model.shape[0]
+    static = (torch.arange(vals.shape[0], device=vals.device) - starts[inverse]) >= af
+    pts = vals.reshape(-1, 4)
+    inf = torch.full((n, 2), float('inf'), dtype=torch.float32, device=vals.device)
+    lo_pts = torch.where(static[:, None], torch.minimum(pts[:, :2], pts[:, 2:]), torch.full_like(pts[:, :2], float('inf')))
+    hi_pts = torch.where(static[:, None], torch.maximum(pts[:, :2], pts[:, 2:]), torch.full_like(pts[:, :2], -float('inf')))
+    index = inverse[:, None].expand(-1, 2)
+    return inf.scatter_reduce(0, index, lo_pts, 'amin'), (-inf).scatter_reduce(0, index, hi_pts, 'amax')
+
+
+def nav_geometry(scenery, cell):
+    """The nav grids' placement, on the host: ((N, 4) int32 numpy ``jx0, iy0, nx, ny``, (N + 1,) int64 numpy cell starts). Env n's
+    grid covers the bounding box of its static walls and one cell of margin round it: columns ``floor(xmin/c) - 1`` to
+    ``floor(xmax/c) + 1``, rows likewise; an env without finite static walls gets no cells."""
+    import numpy as np
+    lo, hi = (t.double().cpu().numpy() for t in _static_boxes(scenery))
+    ok = np.isfinite(lo).all(1) & np.isfinite(hi).all(1)
+    c = float(np.float32(cell))
+    first = np.floor(np.where(ok[:, None], lo, 0.)/c).astype(np.int64) - 1
+    last = np.floor(np.where(ok[:, None], hi, 0.)/c).astype(np.int64) + 1
+    size = np.where(ok[:, None], last - first + 1, 0)
+    if (np.abs(first) > 2**24).any() or (size > 2**15).any():
+        raise RuntimeError(f'a nav grid of {cell} m cells over these walls would be larger than 32768 cells a side')
+    geom = np.concatenate([first, size], 1).astype(np.int32)
+    starts = np.concatenate([[0], np.cumsum(size[:, 0]*size[:, 1])]).astype(np.int64)
+    return geom, starts
+
+
+class NavGrid:
+    """Result of :func:`nav_grid`: which cells of a grid over every env's floorplan keep ``clearance`` metres clear of every
+    static wall. ``geom`` (N, 4) int32 ``jx0, iy0, nx, ny``: cell (row i, column j) of env n has its centre at
+    ``((jx0 + j) + .5)*cell, ((iy0 + i) + .5)*cell``; ``starts`` (N + 1,) int64: env n's ``nx*ny`` cells are
+    ``free[starts[n]:starts[n + 1]]``, row-major (ragged, not padded); ``free`` uint8, 1 free / 0 blocked."""
+
+    def __init__(self, geom, starts, free, cell, clearance, host_geom, host_starts):
+        self.geom, self.starts, self.free = geom, starts, free
+        self.cell, self.clearance = float(cell), float(clearance)
+        self._host_geom, self._host_starts = host_geom, host_starts
+        framed = (host_geom[:, 2].astype('int64') + 2)*(host_geom[:, 3].astype('int64') + 2)
+        framed = framed[(host_geom[:, 2] > 0) & (host_geom[:, 3] > 0)]
+        self._max_framed = int(framed.max()) if len(framed) else 0
+        self._struct = _lib.MsNavGrid(len(host_geom), self.cell, self.clearance, geom.data_ptr(), starts.data_ptr(), self._max_framed,
+                                      free.data_ptr())
+
+    n_envs = property(lambda self: len(self._host_geom))
+    #: cells of all envs together
+    n_cells = property(lambda self: int(self._host_starts[-1]))
+
+    def cells(self, e):
+        """(first cell, ny, nx) of env ``e`` (host numbers: no synchronisation)."""
+        return int(self._host_starts[e]), int(self._host_geom[e, 3]), int(self._host_geom[e, 2])
+
+    def image(self, e):
+        """(ny, nx) bool: env ``e``'s free cells, row 0 at the lowest y."""
+        s, ny, nx = self.cells(e)
+        return self.free[s:s + ny*nx].reshape(ny, nx).bool()
+
+    def centres(self, e):
+        """((nx,) x, (ny,) y) float32 of env ``e``'s cell centres, as the kernels form them."""
+        jx0, iy0, nx, ny = (int(v) for v in self._host_geom[e])
+        dev = self.free.device
+        x = (torch.arange(jx0, jx0 + nx, device=dev).float() + .5)*torch.tensor(self.cell, dtype=torch.float32, device=dev)
+        y = (torch.arange(iy0, iy0 + ny, device=dev).float() + .5)*torch.tensor(self.cell, dtype=torch.float32, device=dev)
+        return x, y
+
+
+def nav_grid(scenery, cell=.125, clearance=None, config=None):
+    """The navigation grid of every env: square cells of ``cell`` metres over the env's static walls, a cell *free* when no
+    static wall comes within ``clearance`` metres of its centre (default: the configured ``agent_radius``) - the very rule
+    :func:`overhead` draws lines of that half width by. One launch; needs neither :func:`bake` nor the wall grid. The agents'
+    own lines are not looked at: the grid is the building, not who is in it.
+
+    ``cell`` must be at most ``1.4*clearance``: then no edge between two free cells (and no leg from a point that is itself
+    ``clearance`` clear of the walls to a free cell next to it) can cross a wall, however thin or oblique - see
+    include/megastep_hip.h (``MsNavGrid``) and DESIGN.md 3.14. Envs are gridded one by one, whether or not they share a
+    floorplan."""
+    import numpy as np
+    if clearance is None:
+        clearance = _cfg(explicit=config).agent_radius
+    if not (cell > 0 and clearance > 0 and cell < float('inf') and clearance < float('inf')):
+        raise RuntimeError('cell and clearance must be positive numbers')
+    if np.float32(cell) > np.float32(1.4)*np.float32(clearance):
+        raise RuntimeError(f'cell ({cell}) must be at most 1.4 x clearance ({clearance}): a coarser grid could step through a wall')
+    dev = scenery._device()
+    host_geom, host_starts = nav_geometry(scenery, cell)
+    geom = torch.as_tensor(host_geom, device=dev).contiguous()
+    starts = torch.as_tensor(host_starts, device=dev).contiguous()
+    free = torch.zeros(max(int(host_starts[-1]), 1), dtype=torch.uint8, device=dev)
+    grid = NavGrid(geom, starts, free, cell, clearance, host_geom, host_starts)
+    with _on(dev):
+        _lib.check(_lib.lib().ms_nav_free(C.byref(scenery._as_struct()), C.byref(grid._struct), _stream(dev)))
+    return grid
+
+
+class DistanceFields:
+    """Result of :func:`distance_fields`: for each env ``G`` fields, field (n, g) holding for every cell of env n's grid the
+    length of the shortest 8-connected path from the cell's centre to ``goals[n, g]`` (+inf on blocked cells and on cells no
+    path reaches). ``values`` is the flat float32 store: field (n, g) starts at ``G*grid.starts[n] + g*nx*ny``."""
+
+    def __init__(self, grid, goals, values, passes=None):
+        self.grid, self.goals, self.values, self.passes = grid, goals, values, passes
+
+    n_goals = property(lambda self: self.goals.shape[1])
+
+    def image(self, e, g=0):
+        """(ny, nx) float32 view of field ``g`` of env ``e``, row 0 at the lowest y."""
+        s, ny, nx = self.grid.cells(e)
+        at = self.n_goals*s + g*ny*nx
+        return self.values[at:at + ny*nx].reshape(ny, nx)
+
+    def update(self, goals=None, mask=None):
+        """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place - for ``goals`` (N, G, 2), which are
+        copied into :attr:`goals` where marked, or for the goals as they stand. One launch, no host synchronisation."""
+        if goals is not None:
+            _check(goals, 'goals', torch.float32, 3)
+            if goals.shape != self.goals.shape:
+                raise RuntimeError(f'goals must be {tuple(self.goals.shape)}; got {tuple(goals.shape)}')
+            if goals is not self.goals:
+                if mask is None:
+                    self.goals.copy_(goals)
+                else:
+                    torch.where(mask[..., None], goals, self.goals, out=self.goals)
+        _nav_fields_call(self, mask)
+        return self
+
+    def at(self, points, goal=None, out=None):
+        """(N, P) float32: the distance from each of ``points`` (N, P, 2) to a goal of its env - ``goal`` (N, P) integers name
+        the field each point asks, default point k against field k (then P must be G). The distance is the least, over the
+        (at most four) free cells round the point, of the cell's value plus the straight leg to its centre: continuous
+        enough that an agent's progress per step is not quantised to cells. +inf where no path exists. Meant for points
+        that are themselves ``clearance`` clear of the walls (an agent's centre, a spawn point): the leg of any other point
+        may cross a wall. One launch, no host synchronisation."""
+        n, p, goal, dev = self._queries(points, goal)
+        out = _answer(out, (n, p), dev)
+        spec = _lib.MsNavQuery(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
+                               self.n_goals, out.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_query(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        return out
+
+    def _queries(self, points, goal):
+        """The argument rules of :meth:`at` and of the calls that follow the fields: (n, p, goal as int32 or None, device)."""
+        grid = self.grid
+        _check(points, 'points', torch.float32, 3)
+        n, p = points.shape[:2]
+        if n != grid.n_envs or points.shape[2] != 2 or p < 1:
+            raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
+        if goal is None:
+            if p != self.n_goals:
+                raise RuntimeError(f'without goal, points must be one per field ({self.n_goals}); got {p}')
+        else:
+            if not isinstance(goal, torch.Tensor) or goal.dtype.is_floating_point or goal.shape != (n, p):
+                raise RuntimeError(f'goal must be an (N, P) = ({n}, {p}) integer tensor')
+            goal = goal.to(torch.int32).contiguous()
+        dev = _require_gpu(points, self.values, self.goals, grid.free, *([goal] if goal is not None else []))
+        return n, p, goal, dev
+
+    def waypoints(self, points, goal=None, lookahead=16, hops=False, out=None):
+        """(N, P, 2) float32: where to head for from each of ``points`` (N, P, 2) to walk to its goal (``goal``: as :meth:`at`) -
+        the furthest of the next ``lookahead`` (1..64) cells down the field that the point can see in a straight line clear of
+        the walls, the goal itself once that is in sight; NaN where no path exists (exactly where :meth:`at` gives +inf).
+        Heading for the waypoint, step after step, walks round the walls to the goal, and less far than :meth:`at` says: the
+        look-ahead cuts the grid's 8-direction staircase short. ``hops=True`` also returns (N, P) int32: how many cells
+        ahead the waypoint is (-1: no path). ``out``: the (N, P, 2) tensor to write. One launch, a wavefront a point, no host
+        synchronisation. The rule: include/megastep_hip.h (``MsNavWaypoints``), DESIGN.md 3.15."""
+        if not isinstance(lookahead, int) or not 1 <= lookahead <= 64:
+            raise RuntimeError(f'lookahead must be an integer in 1..64; got {lookahead}')
+        n, p, goal, dev = self._queries(points, goal)
+        out = _answer(out, (n, p, 2), dev)
+        chosen = torch.empty((n, p), dtype=torch.int32, device=dev) if hops else None
+        spec = _lib.MsNavWaypoints(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
+                                   self.goals.data_ptr(), self.n_goals, lookahead, out.data_ptr(), chosen.data_ptr() if hops else None)
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_waypoints(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        return (out, chosen) if hops else out
+
+    def paths(self, points, goal=None, max_points=256):
+        """The whole path from each of ``points`` (N, P, 2) to its goal (``goal``: as :meth:`at`), as a :class:`Paths`: the point,
+        the centres of the cells down the field, the goal; the first ``max_points`` of them written. One launch, a lane a
+        path, no host synchronisation; for drawing and for scoring, not for every step - that is :meth:`waypoints`."""
+        if not isinstance(max_points, int) or not 2 <= max_points <= 2**20:
+            raise RuntimeError(f'max_points must be an integer in 2..2^20; got {max_points}')
+        n, p, goal, dev = self._queries(points, goal)
+        pts = torch.empty((n, p, max_points, 2), dtype=torch.float32, device=dev)
+        counts = torch.empty((n, p), dtype=torch.int32, device=dev)
+        spec = _lib.MsNavPaths(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
+                               self.goals.data_ptr(), self.n_goals, max_points, pts.data_ptr(), counts.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_paths(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        return Paths(pts, counts)
+
+
+def _answer(out, shape, dev):
+    """The tensor a query writes its (N, P[, 2]) answer to: ``out`` if it fits, a fresh one without."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if not isinstance(out, torch.Tensor) or out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"`out` must be a contiguous (N, P{', 2'*(len(shape) - 2)}) float32 tensor on the fields' device")
+    return out
+
+
+class Paths:
+    """Result of :meth:`DistanceFields.paths`. ``points`` (N, P, M, 2) float32: path (e, k)'s points - where it starts, cell
+    centre after cell centre, the goal - NaN in the slots not written; ``counts`` (N, P) int32: the points of the whole path,
+    which may be more than the M written; 0 where no path exists; negative (the points got, negated) where the field did not
+    lead to its goal - a stale field, or one of another grid."""
+
+    def __init__(self, points, counts):
+        self.points, self.counts = points, counts
+
+    def path(self, e, k):
+        """(n, 2): the written points of path ``k`` of env ``e`` (synchronises: n comes from the device)."""
+        n = min(abs(int(self.counts[e, k])), self.points.shape[2])
+        return self.points[e, k, :n]
+
+
+def _nav_fields_call(fields, mask):
+    grid = fields.grid
+    n, g = fields.goals.shape[:2]
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (n, g):
+            raise RuntimeError(f'mask must be an (N, G) = ({n}, {g}) bool tensor')
+        mask = mask.contiguous()
+    dev = _require_gpu(fields.goals, fields.values, grid.free, *([mask] if mask is not None else []))
+    spec = _lib.MsNavFields(g, fields.goals.data_ptr(), mask.data_ptr() if mask is not None else None, fields.values.data_ptr(),
+                            fields.passes.data_ptr() if fields.passes is not None else None)
+    with _on(dev):
+        _lib.check(_lib.lib().ms_nav_fields(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+
+
+def distance_fields(grid, goals, mask=None, out=None, passes=False):
+    """Shortest-path distance fields on the :func:`nav_grid`: for every env and each of its ``G`` goals (``goals``: (N, G, 2)
+    float32 world points) the distance from every free cell to the goal along the grid's 8-connected graph - straight steps
+    of ``cell``, diagonal steps of ``cell*1.41421356`` that cut no corner - joined to the goal by the straight legs from the
+    free cells round it. The 8-connected metric is up to 8 % longer than the true (any-angle) shortest path in open space;
+    an agent that heads for :meth:`DistanceFields.waypoints` cuts the staircase short and walks less than the field says.
+    One launch, one workgroup per field, the field relaxed in LDS until nothing changes; the result does not depend on the
+    order of relaxation and equals Dijkstra's with binary32 additions bit for bit (include/megastep_hip.h, ``MsNavGrid``).
+
+    ``mask`` (N, G) bool: compute only the marked fields (the others keep what ``out`` held); ``out``: the
+    :class:`DistanceFields` of an earlier call with the same grid and G to write into (its goals are updated where marked);
+    ``passes=True`` also records the relaxation passes each field took (``.passes``, (N, G) int32). No host synchronisation:
+    the call can be captured in a HIP graph."""
+    _check(goals, 'goals', torch.float32, 3)
+    n, g = goals.shape[:2]
+    if n != grid.n_envs or g < 1 or goals.shape[2] != 2:
+        raise RuntimeError(f'goals must be (N, G, 2) with N = {grid.n_envs} and G >= 1; got {tuple(goals.shape)}')
+    if out is not None:
+        if out.grid is not grid or out.goals.shape != goals.shape:
+            raise RuntimeError('`out` must come from a distance_fields call with the same grid and number of goals')
+        return out.update(goals, mask)
+    dev = goals.device
+    values = torch.empty(max(g*grid.n_cells, 1), dtype=torch.float32, device=dev)
+    if mask is not None:
+        values.fill_(float('inf'))                                      # (a field never computed is a field nothing reaches)
+    fields = DistanceFields(grid, goals.clone(), values, torch.zeros((n, g), dtype=torch.int32, device=dev) if passes else None)
+    _nav_fields_call(fields, mask)
+    return fields
+
+
+def geodesic(grid, a, b):
+    """(N, P) float32: the walking distance from ``a[n, k]`` to ``b[n, k]`` (both (N, P, 2)) - the fields of ``b``, asked at
+    ``a``. A convenience for a handful of pairs; keep the :func:`distance_fields` when the goals stay."""
+    return distance_fields(grid, b).at(a)

@@ -41,16 +41,50 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layouts_match_the_header():
-    """ctypes mirrors of the structs must have the C layout: check sizes against a C compile of the header."""
+    """ctypes mirrors of the structs must have the C layout: every struct the boundary header typedefs has a mirror, and the
+    size and every field's offset of each mirror are those of a C compile of the header."""
     import subprocess, tempfile
     from megastep_amd import _lib
-    src = '#include <stdio.h>\n#include "megastep_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu", sizeof(MsConfig), sizeof(MsScenery), sizeof(MsAgents), sizeof(MsRender), sizeof(MsMovement), sizeof(MsStepExtras), sizeof(MsDeathmatch), sizeof(MsExplorer));}'
+    mirrors = {k: v for k, v in vars(_lib).items() if k.startswith('Ms') and isinstance(v, type) and issubclass(v, C.Structure)}
+    text = open(os.path.join(ROOT, 'include', 'megastep_hip.h')).read()
+    assert sorted(re.findall(r'^\}\s*(Ms\w+)\s*;', text, flags=re.M)) == sorted(mirrors) and len(mirrors) >= 16
+    want, exprs = [], []
+    for name, cls in sorted(mirrors.items()):
+        want.append(C.sizeof(cls))
+        exprs.append(f'sizeof({name})')
+        for field, _ in cls._fields_:
+            want.append(getattr(cls, field).offset)
+            exprs.append(f'offsetof({name}, {field})')
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "megastep_hip.h"\nint main(){' \
+        + ''.join(f'printf("%zu ", (size_t){e});' for e in exprs) + 'return 0;}'
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, 't.c'), 'w').write(src)
         subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), os.path.join(d, 't.c'), '-o', os.path.join(d, 't')])
-        sizes = list(map(int, subprocess.check_output([os.path.join(d, 't')]).split()))
-    assert sizes == [C.sizeof(_lib.MsConfig), C.sizeof(_lib.MsScenery), C.sizeof(_lib.MsAgents), C.sizeof(_lib.MsRender),
-                     C.sizeof(_lib.MsMovement), C.sizeof(_lib.MsStepExtras), C.sizeof(_lib.MsDeathmatch), C.sizeof(_lib.MsExplorer)]
+        got = list(map(int, subprocess.check_output([os.path.join(d, 't')]).split()))
+    assert len(got) == len(want) >= 185
+    assert not [(e, g, w) for e, g, w in zip(exprs, got, want) if g != w]
+
+
+def test_prototypes_match_the_headers():
+    """The loader's one table against the two headers: every declared function is bound with as many arguments as it is declared
+    with, and with the return type it is declared with."""
+    from megastep_amd import _lib
+    returns = {'int': C.c_int, 'void': None, 'float': C.c_float, 'long long': C.c_longlong, 'const char*': C.c_char_p}
+    declared = {}
+    for h in ('megastep_hip.h', 'megastep_hip_test.h'):
+        text = open(os.path.join(ROOT, 'include', h)).read()
+        text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+        text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)               # (declarations follow a #define / #endif directly)
+        for ret, name, args in re.findall(r'\b(const\s+char\s*\*|long\s+long|int|void|float)\s+(ms_[a-z_0-9]+)\s*\(([^()]*)\)\s*;', text):
+            assert name not in declared, name
+            ret = 'const char*' if ret.startswith('const') else ' '.join(ret.split())
+            declared[name] = (returns[ret], 0 if args.strip() in ('', 'void') else args.count(',') + 1)
+    assert sorted(declared) == declared_symbols() == sorted(_lib.PROTOTYPES)
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        assert (restype, len(argtypes)) == declared[name], name
+    handle = _lib.lib()                                                  # ... and the table is what the loaded library is bound by
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        assert getattr(handle, name).restype is restype and list(getattr(handle, name).argtypes) == argtypes, name
 
 
 def test_bad_arguments_are_rejected_before_any_launch():

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_two_cores_of_different_shapes_step_alternately():
-    from megastep_amd import core, cubicasa, cuda, modules, scene
+    from megastep_amd import _call, core, cubicasa, cuda, modules, scene
     np.random.seed(3)
     geometries = cubicasa.sample(5, n_unique=16, seed=4)
     worlds = []
@@ -20,7 +20,7 @@ def test_two_cores_of_different_shapes_step_alternately():
         util.spawn(c, geometries, seed=res)
         worlds.append((c, util.OracleWorld(c)))
     # the process-global fallback now holds the LAST core's constants; every core must still be served with its own
-    assert cuda._config.res == 48
+    assert _call._config.res == 48
     rng = np.random.RandomState(0)
     for step in range(3):
         for c, ref in worlds if step % 2 == 0 else worlds[::-1]:
