@@ -528,6 +528,57 @@ typedef struct MsNavPaths {
 int ms_nav_waypoints(const MsNavGrid* grid, const MsNavWaypoints* waypoints, void* hip_stream);
 int ms_nav_paths(const MsNavGrid* grid, const MsNavPaths* paths, void* hip_stream);
 
+/* Seen maps: which cells of the nav grid the depth rays of an agent (of any viewer) have passed over - floor coverage for
+ * exploration rewards, a mask to hand a policy or to draw.  As above every step is one binary32 operation in the order given,
+ * without contraction, divisions and roots correctly rounded; tests/test_navseen_host.py restates it in numpy (seen_rule) and
+ * the kernel - and its host instantiation, ms_host_nav_seen - are held to EQUALITY with it.  c, geom and starts are MsNavGrid's.
+ *   maps          S maps per env; map (n, s) holds one byte per cell of env n, 0 unseen, 1 seen, row-major, and starts at
+ *                 S*starts[n] + s*nx*ny (MsNavFields.fields' layout).  `countable`, starts[N] bytes shared by an env's maps
+ *                 (bit 0), says which cells count; NULL: the grid's free_cells.
+ *   viewers       P per env, R rays each: origins (N, P, 2), dirs (N, P, R, 2) of any length, distances (N, P, R) in metres -
+ *                 what ms_render / ms_raycast return for the rays of ms_camera_rays.  slot (N, P) names the map viewer p
+ *                 marks; NULL: P == S and viewer k marks map k.  A slot outside [0, S) skips the viewer.
+ *   a ray         origin o, direction d, distance dist: rlen = sqrtf(dx*dx + dy*dy).  The ray is skipped when a component
+ *                 of o or d is not finite, rlen is not finite or not > 0, dist is a NaN or not > 0.  reach = dist < max_range ?
+ *                 dist : max_range (max_range finite and > 0; a ray that missed, +inf, reaches max_range); ux = dx/rlen,
+ *                 uy = dy/rlen; ex = ux*reach, ey = uy*reach; K = (int)ceilf(sqrtf(ex*ex + ey*ey)/(0.5f*c)) - the sight's
+ *                 count of MsNavWaypoints, samples at most half a cell apart; the ray is skipped when that is not below 2^20
+ *                 (or a NaN); K = 0 counts as 1.
+ *   samples       s = 0 .. K, both ends: t = (float)s/(float)K, x = ox + ex*t, y = oy + ey*t, fx = floorf(x/c),
+ *                 fy = floorf(y/c).  A sample is skipped when fx or fy is a NaN or |.| >= 2^30; else j = (int)fx - jx0,
+ *                 i = (int)fy - iy0, skipped when (i, j) is outside the grid; else cell (i, j) of the viewer's map is marked.
+ *   a call        1. the maps named in reset ((N, S) bytes, non-zero; NULL: none) are cleared;  2. all rays mark;
+ *                 3. gained[n, s] = the cells of map (n, s) that were 0 before the marks (after the reset), are 1 after and are
+ *                 countable - a cell hit by many rays, or by two viewers of one map, counts once;  4. total[n, s] =
+ *                 (reset ? 0 : total[n, s]) + gained[n, s].  Either output may be NULL.  An env without cells marks nothing
+ *                 and gains 0.  Marks are idempotent and the counts integers: nothing depends on the order of execution.
+ *   no wall is seen through (with free_cells as the countable mask).  A cell that straddles a wall has its centre within
+ *                 0.71 c <= 0.99 r of it: blocked, never countable - the cell of a hit point that rounded to the wall's far
+ *                 side included.  A countable cell that holds a sample has its centre within 0.71 c of a point the ray
+ *                 reached, and no wall lies between the two: it would come within 0.71 c of the centre and block the cell.
+ * One launch, one workgroup per map - the map's only writer in the call - with the call's marks as a bitmask in LDS, one bit
+ * per cell: max_cells, the most cells (nx*ny) any env has, sizes it.  More than 2^20 (128 KiB of bits: a 128 m square at
+ * 0.125 m): MS_EUNSUPPORTED, nothing enqueued; an env with more cells than max_cells says marks nothing and gains 0.  No
+ * global atomics, nothing allocated, nothing waits: the call can be captured in a HIP graph.  Every argument is checked in
+ * full before the launch (MS_EINVAL). */
+typedef struct MsNavSeen {
+    int                  n_maps;       /* S: maps per env                                                              */
+    int                  n_viewers;    /* P: viewers per env                                                           */
+    int                  n_rays;       /* R: rays per viewer                                                           */
+    const float*         origins;      /* (N, P, 2); 8-byte aligned                                                    */
+    const float*         dirs;         /* (N, P, R, 2); 8-byte aligned                                                 */
+    const float*         distances;    /* (N, P, R)                                                                    */
+    const int*           slot;         /* (N, P) the map each viewer marks; NULL: P == S, viewer k map k               */
+    float                max_range;    /* metres, finite and > 0                                                       */
+    const unsigned char* reset;        /* (N, S) non-zero: clear the map first; NULL: none                             */
+    const unsigned char* countable;    /* (starts[N],) bit 0: the cell counts; NULL: the grid's free_cells             */
+    unsigned char*       maps;         /* S*starts[N] bytes in / out: map (n, s) at S*starts[n] + s*nx*ny              */
+    int*                 gained;       /* (N, S) out, or NULL                                                          */
+    int*                 total;        /* (N, S) in / out, or NULL                                                     */
+    int                  max_cells;    /* the largest nx*ny of any env (0: no env has cells), at most 2^20             */
+} MsNavSeen;
+int ms_nav_seen(const MsNavGrid* grid, const MsNavSeen* seen, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

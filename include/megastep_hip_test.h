@@ -73,6 +73,14 @@ int ms_host_nav_waypoint(const int* geom, float cell, const unsigned char* free_
                          const float* point, int lookahead, float* waypoint);
 int ms_host_nav_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal,
                      const float* point, int max_points, float* points);
+/* Host instantiation of the seen maps' rule (kernels/navseen.h: the ray, the sample - the very functions every lane of
+ * nav_seen_kernel evaluates) for ONE env on HOST arrays, one call of ms_nav_seen: geom = (jx0, iy0, nx, ny), countable
+ * (ny x nx bytes), origins (P, 2), dirs (P, R, 2), distances (P, R), slot (P) or NULL (then P == S), reset (S) or NULL, maps
+ * (S, ny, nx) in / out, gained (S) out and total (S) in / out, either or NULL.  Returns 0, or -1 for arguments ms_nav_seen
+ * would refuse.  An env without cells (nx*ny <= 0) marks nothing and gains 0. */
+int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable, int n_maps, int n_viewers, int n_rays,
+                     const float* origins, const float* dirs, const float* distances, const int* slot, float max_range,
+                     const unsigned char* reset, unsigned char* maps, int* gained, int* total);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

@@ -116,6 +116,12 @@ class MsNavPaths(C.Structure):
                 ('n_goals', C.c_int), ('max_points', C.c_int), ('paths', C.c_void_p), ('counts', C.c_void_p)]
 
 
+class MsNavSeen(C.Structure):
+    _fields_ = [('n_maps', C.c_int), ('n_viewers', C.c_int), ('n_rays', C.c_int), ('origins', C.c_void_p), ('dirs', C.c_void_p),
+                ('distances', C.c_void_p), ('slot', C.c_void_p), ('max_range', C.c_float), ('reset', C.c_void_p), ('countable', C.c_void_p),
+                ('maps', C.c_void_p), ('gained', C.c_void_p), ('total', C.c_void_p), ('max_cells', C.c_int)]
+
+
 _int, _flt, _ptr, _p = C.c_int, C.c_float, C.c_void_p, C.POINTER
 
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare, as
@@ -143,6 +149,7 @@ PROTOTYPES = {
     'ms_nav_query': (_int, [_p(MsNavGrid), _p(MsNavQuery), _ptr]),
     'ms_nav_waypoints': (_int, [_p(MsNavGrid), _p(MsNavWaypoints), _ptr]),
     'ms_nav_paths': (_int, [_p(MsNavGrid), _p(MsNavPaths), _ptr]),
+    'ms_nav_seen': (_int, [_p(MsNavGrid), _p(MsNavSeen), _ptr]),
     'ms_wallgrid_scan': (_int, [_p(MsScenery), _p(MsWallGridParent), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr]),
     'ms_wallgrid_fill': (_int, [_p(MsScenery), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # the test hooks
@@ -163,6 +170,7 @@ PROTOTYPES = {
     'ms_host_overhead_keeps': (_int, [_f32p, _int, _int, _int, _int, _flt, _f32p]),
     'ms_host_nav_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),

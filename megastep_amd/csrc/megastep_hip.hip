@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h, navseen.h.
 //
-// Twenty-one kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Twenty-two kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -52,6 +52,9 @@
 //   nav_waypoint_kernel, nav_path_kernel   which way to go on those fields: one wavefront per point descends the field a
 //                   neighbour a lane and picks the furthest of the next cells the point can see; and whole paths, a lane
 //                   each.   (no counterpart)
+//   nav_seen_kernel     seen maps: one workgroup per map marks the grid cells under the samples of its viewers' depth rays in
+//                   an LDS bitmask, merges it into the map and counts the countable cells seen for the first time.
+//                                                            (no counterpart)
 //   explorer_kernel     the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
 //   deathmatch_kernel   the Deathmatch env's game logic between frames (revive, crosshairs, hits and wounds, health, damage,
@@ -151,6 +154,7 @@ struct Probe {
 #include "kernels/overhead.h"
 #include "kernels/navfield.h"
 #include "kernels/navpath.h"
+#include "kernels/navseen.h"
 #include "kernels/envlogic.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -884,6 +888,39 @@ int ms_host_nav_path(const int* geom, float cell, const unsigned char* free_cell
         return 0;
     }
     return nav_path(g, nav_goal(g, goal[0], goal[1]), point[0], point[1], (long long)g.nx*g.ny, max_points, points);
+}
+
+// Seen maps (navseen.h): the same discipline; an env of more than 2^20 cells is refused, and nothing is enqueued.
+constexpr int NAV_SEEN_MAX_CELLS = 1 << 20;
+static bool nav_seen_ok(const MsNavSeen* v) {
+    return v && v->n_maps >= 1 && v->n_viewers >= 1 && v->n_rays >= 1 && v->origins && v->dirs && v->distances && v->maps &&
+           (v->slot || v->n_viewers == v->n_maps) && v->max_range > 0.f && v->max_range < INFINITY &&
+           v->max_cells >= 0 && ((uintptr_t)v->origins % 8 == 0) && ((uintptr_t)v->dirs % 8 == 0) && ((uintptr_t)v->distances % 4 == 0) &&
+           ((uintptr_t)v->slot % 4 == 0) && ((uintptr_t)v->gained % 4 == 0) && ((uintptr_t)v->total % 4 == 0);
+}
+
+int ms_nav_seen(const MsNavGrid* grid, const MsNavSeen* v, void* stream) {
+    if (!nav_grid_ok(grid) || !nav_seen_ok(v)) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*v->n_maps;
+    if (v->max_cells > NAV_SEEN_MAX_CELLS || total > 0x7fffffffLL || (long long)grid->n_envs*v->n_viewers > 0x7fffffffLL/v->n_rays)
+        return MS_EUNSUPPORTED;
+    const NavSeenArgs q{v->origins, v->dirs, v->distances, v->slot, v->reset, v->countable ? v->countable : grid->free_cells, v->maps,
+                        v->gained, v->total, v->n_maps, v->n_viewers, v->n_rays, v->max_cells, v->max_range};
+    const size_t lds = (size_t)((v->max_cells + 31)/32)*sizeof(unsigned);                   // (at most 128 KiB of the CU's 160)
+    if (lds > 64*1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(nav_seen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)lds) != hipSuccess) return hip_fail(hipGetLastError());
+    hipLaunchKernelGGL(nav_seen_kernel, dim3((unsigned)total), dim3(WG), lds, (hipStream_t)stream, nav_args(grid), q);
+    return launch_status();
+}
+
+int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable, int n_maps, int n_viewers, int n_rays,
+                     const float* origins, const float* dirs, const float* distances, const int* slot, float max_range,
+                     const unsigned char* reset, unsigned char* maps, int* gained, int* total) {
+    if (!geom || !(cell > 0.f) || !(cell < INFINITY) || n_maps < 1 || n_viewers < 1 || n_rays < 1 || !origins || !dirs || !distances ||
+        !maps || !countable || !(slot || n_viewers == n_maps) || !(max_range > 0.f) || !(max_range < INFINITY)) return -1;
+    seen_serial(SeenGrid{geom[0], geom[1], geom[2], geom[3], cell}, countable, n_maps, n_viewers, n_rays, origins, dirs, distances, slot,
+                max_range, reset, maps, gained, total);
+    return 0;
 }
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {

@@ -2,3 +2,4 @@ from .minimal import Minimal  # noqa: F401
 from .explorer import Explorer  # noqa: F401
 from .deathmatch import Deathmatch  # noqa: F401
 from .pointgoal import PointGoal  # noqa: F401
+from .floorcoverage import FloorCoverage  # noqa: F401

@@ -489,6 +489,48 @@ class Goals:
         return arrdict.arrdict(goals=self.goals[e], stranded=self.stranded[e]).clone()
 
 
+class Coverage:
+
+    def __init__(self, core, grid, max_range=10., shared=False, countable=None):
+        """Floor coverage: which cells of the nav grid every agent's depth rays have passed over since it started over, and
+        how much floor each new frame adds (:func:`cuda.seen_maps`; no counterpart in the reference, whose Explorer rewards
+        wall texels). ``grid`` is the scenery's :func:`cuda.nav_grid`; rays are followed for at most ``max_range`` metres;
+        ``countable``: the cells that count (default: the grid's free cells - then no wall is seen through). Every agent has
+        a map of its own; ``shared=True`` gives an env's agents ONE map, which any of them starting over clears, and each of
+        them the map's whole gain. One launch behind the render's, nothing waits for the host."""
+        self.core, self.grid = core, grid
+        self.max_range, self.shared = float(max_range), bool(shared)
+        self.maps = cuda.seen_maps(grid, 1 if shared else core.n_agents, countable)
+        self.space = spaces.MultiVector(core.n_agents, 1)
+        self._slot = torch.zeros((core.n_envs, core.n_agents), dtype=torch.int32, device=core.device) if shared else None
+        self._gained = torch.zeros((core.n_envs, self.maps.n_maps), dtype=torch.int32, device=core.device)
+        self._area = torch.tensor(grid.cell, dtype=torch.float32, device=core.device)**2
+
+    def _per_agent(self, t):
+        return t.expand(-1, self.core.n_agents) if self.shared else t
+
+    def __call__(self, frame, reset=None):
+        """(n_env, n_agent) float32: the floor each agent saw for the first time in ``frame`` - a render of the agents as they
+        stand, with its ``distances`` - in square metres. ``reset`` (n_env, n_agent) bool: the agents that started over this
+        step; their maps are cleared before the frame is marked."""
+        if reset is not None and self.shared:
+            reset = reset.any(-1, keepdim=True)
+        gained = self.maps.mark_render(self.core.agents, frame, slot=self._slot, max_range=self.max_range, reset=reset, out=self._gained)
+        return self._per_agent(gained.float()*self._area)
+
+    def fraction(self):
+        """(n_env, n_agent) float32: the share of the countable floor each agent('s map) has seen."""
+        return self._per_agent(self.maps.fraction())
+
+    def observation(self):
+        """(n_env, n_agent, 1): :meth:`fraction`."""
+        return self.fraction().unsqueeze(-1)
+
+    def state(self, e=0):
+        """(S, ny, nx) bool: a copy of env ``e``'s maps, row 0 at the lowest y."""
+        return torch.stack([self.maps.image(e, s) for s in range(self.maps.n_maps)]).clone()
+
+
 class PathFollower:
 
     def __init__(self, core, goals, lookahead=16, cone=45., speed=2.):

@@ -1,5 +1,6 @@
-"""Navigation grids, shortest-path distance fields, waypoints and paths on the floorplans (kernels: ``csrc/kernels/navfield.h``,
-``csrc/kernels/navpath.h``). No counterpart in the reference; reached as ``megastep_amd.cuda.<name>``."""
+"""Navigation grids, shortest-path distance fields, waypoints and paths on the floorplans, and the seen maps of the depth rays
+(kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``). No counterpart in the reference;
+reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
 from . import _lib
@@ -65,7 +66,8 @@ class NavGrid:
         return int(self._host_starts[e]), int(self._host_geom[e, 3]), int(self._host_geom[e, 2])
 
     def image(self, e):
-        """(ny, nx) bool: env ``e``'s free cells, row 0 at the lowest y."""
+        """(ny, nx) bool: env ``e``'s free cells, row 0 at the lowest y (row i holds the cells centred at ``y = ((iy0 + i) + .5)*cell``):
+        the convention of :meth:`SeenMaps.image` and :meth:`DistanceFields.image`."""
         s, ny, nx = self.cells(e)
         return self.free[s:s + ny*nx].reshape(ny, nx).bool()
 
@@ -276,3 +278,118 @@ def geodesic(grid, a, b):
     """(N, P) float32: the walking distance from ``a[n, k]`` to ``b[n, k]`` (both (N, P, 2)) - the fields of ``b``, asked at
     ``a``. A convenience for a handful of pairs; keep the :func:`distance_fields` when the goals stay."""
     return distance_fields(grid, b).at(a)
+
+
+#: the most cells an env may have for :func:`seen_maps`: the kernel keeps a call's marks as one bit per cell in LDS (128 KiB)
+SEEN_MAX_CELLS = 2**20
+
+
+class SeenMaps:
+    """Result of :func:`seen_maps`: for each env ``S`` maps, map (n, s) holding one byte per cell of env n's grid - 1 where a
+    depth ray of a viewer of that map has passed over the cell since the map was last cleared. ``values`` is the flat uint8
+    store: map (n, s) starts at ``S*grid.starts[n] + s*nx*ny`` (the layout of :class:`DistanceFields`); ``countable`` the
+    uint8 mask (one byte per cell of the grid, shared by an env's maps) of the cells that count; ``totals`` (N, S) int32: the
+    countable cells seen; ``n_countable`` (N,) int32: the countable cells there are."""
+
+    def __init__(self, grid, n_maps, values, countable, totals, n_countable):
+        self.grid, self.n_maps, self.values, self.countable, self.totals, self.n_countable = grid, int(n_maps), values, countable, totals, n_countable
+        cells = grid._host_geom[:, 2].astype('int64')*grid._host_geom[:, 3].astype('int64')
+        self._max_cells = int(cells.max()) if len(cells) else 0
+
+    def image(self, e, s=0):
+        """(ny, nx) bool view of map ``s`` of env ``e``, row 0 at the lowest y - the convention of :meth:`NavGrid.image`, so the
+        two can be laid over each other as they are."""
+        first, ny, nx = self.grid.cells(e)
+        at = self.n_maps*first + s*ny*nx
+        return self.values[at:at + ny*nx].view(torch.bool).reshape(ny, nx)
+
+    def fraction(self):
+        """(N, S) float32: the share of its env's countable cells each map has seen; 0 where nothing is countable."""
+        return self.totals.float()/self.n_countable.clamp(min=1)[:, None].float()
+
+    def mark(self, origins, dirs, distances, slot=None, max_range=10., reset=None, out=None):
+        """Marks the cells the rays pass over and returns ``gained`` (N, S) int32: the countable cells each map saw for the first
+        time. ``origins`` (N, P, 2): where the P viewers of each env stand; ``dirs`` (N, P, R, 2): their R rays' directions (any
+        length; :func:`camera_rays`); ``distances`` (N, P, R): how far each ray got, metres (+inf: it met nothing), as
+        :func:`render` and :func:`raycast` return them. A ray is followed up to ``min(distance, max_range)`` and sampled at most
+        half a cell apart, both ends included; the cell under every sample is marked. ``slot`` (N, P) integers: the map each
+        viewer marks (outside 0..S-1: the viewer is skipped); default viewer k marks map k (then P must be S). ``reset`` (N, S)
+        bool: maps cleared (and their totals zeroed) before the marks - an agent that starts over. ``out``: the (N, S) int32
+        tensor to write ``gained`` to. :attr:`totals` moves on by what was gained.
+
+        With the grid's free cells as the countable mask no wall is seen through: the cell a hit point falls in, and any cell
+        a wall runs through, has its centre within the clearance of that wall, so it is blocked and never counts. One launch, a
+        workgroup a map, no host synchronisation. The rule: include/megastep_hip.h (``MsNavSeen``), DESIGN.md 3.16."""
+        grid, S = self.grid, self.n_maps
+        _check(origins, 'origins', torch.float32, 3)
+        _check(dirs, 'dirs', torch.float32, 4)
+        _check(distances, 'distances', torch.float32, 3)
+        n, p = origins.shape[:2]
+        r = dirs.shape[2]
+        if n != grid.n_envs or origins.shape[2] != 2 or p < 1 or r < 1 or dirs.shape != (n, p, r, 2) or distances.shape != (n, p, r):
+            raise RuntimeError(f'origins, dirs and distances must be (N, P, 2), (N, P, R, 2) and (N, P, R) with N = {grid.n_envs}; got '
+                               f'{tuple(origins.shape)}, {tuple(dirs.shape)} and {tuple(distances.shape)}')
+        if slot is None:
+            if p != S:
+                raise RuntimeError(f'without slot, the viewers must be one per map ({S}); got {p}')
+        else:
+            if not isinstance(slot, torch.Tensor) or slot.dtype.is_floating_point or slot.dtype == torch.bool or slot.shape != (n, p):
+                raise RuntimeError(f'slot must be an (N, P) = ({n}, {p}) integer tensor')
+            slot = slot.to(torch.int32).contiguous()
+        if reset is not None:
+            if not isinstance(reset, torch.Tensor) or reset.dtype != torch.bool or reset.shape != (n, S):
+                raise RuntimeError(f'reset must be an (N, S) = ({n}, {S}) bool tensor')
+            reset = reset.contiguous()
+        if not (0 < max_range < float('inf')):
+            raise RuntimeError(f'max_range must be a positive number; got {max_range}')
+        if self._max_cells > SEEN_MAX_CELLS:
+            raise RuntimeError(f'an env of this grid has {self._max_cells} cells; seen maps take at most {SEEN_MAX_CELLS} an env')
+        dev = _require_gpu(origins, dirs, distances, self.values, self.countable, self.totals, grid.free,
+                           *(t for t in (slot, reset) if t is not None))
+        if out is None:
+            out = torch.empty((n, S), dtype=torch.int32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.shape != (n, S) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+            raise RuntimeError("`out` must be a contiguous (N, S) int32 tensor on the maps' device")
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        spec = _lib.MsNavSeen(S, p, r, origins.data_ptr(), dirs.data_ptr(), distances.data_ptr(), ptr(slot), float(max_range), ptr(reset),
+                              self.countable.data_ptr(), self.values.data_ptr(), out.data_ptr(), self.totals.data_ptr(), self._max_cells)
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_seen(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return out
+
+    def mark_render(self, agents, frame, slot=None, max_range=10., reset=None, out=None, config=None):
+        """:meth:`mark` for the agents' own camera rays: ``frame`` is what :func:`render` (or ``modules.render``) returned for
+        ``agents``, with its ``distances``; the directions are :func:`camera_rays`' and the origins the agents' positions. The
+        viewers are the agents: by default agent k marks map k."""
+        from .rays import camera_rays
+        dirs = camera_rays(agents, config=config)
+        n, a, r = dirs.shape[:3]
+        distances = getattr(frame, 'distances', None) if not isinstance(frame, dict) else frame.get('distances')
+        if distances is None:
+            raise RuntimeError('the frame has no distances: render with fields that include them')
+        return self.mark(agents.positions, dirs, distances.reshape(n, a, r), slot=slot, max_range=max_range, reset=reset, out=out)
+
+
+def seen_maps(grid, n_maps, countable=None):
+    """``n_maps`` seen maps per env on the :func:`nav_grid`, all unseen: which cells of the floor the depth rays of an agent have
+    passed over (:meth:`SeenMaps.mark`) - coverage rewards on floor area, a mask to hand a policy or to draw. ``countable``: a
+    uint8 or bool tensor of one entry per cell of the grid (``grid.free``'s layout) naming the cells that count towards
+    ``gained``, ``totals`` and :meth:`SeenMaps.fraction`; default the grid's free cells. Marks are kept for every cell, counted
+    or not."""
+    if not isinstance(n_maps, int) or n_maps < 1:
+        raise RuntimeError(f'n_maps must be a positive integer; got {n_maps}')
+    dev = grid.free.device
+    if countable is None:
+        countable = grid.free
+    else:
+        if not isinstance(countable, torch.Tensor) or countable.dtype not in (torch.uint8, torch.bool) or countable.shape != grid.free.shape:
+            raise RuntimeError(f'countable must be a uint8 or bool tensor of {tuple(grid.free.shape)}, one entry per cell of the grid')
+        countable = countable.to(device=dev, dtype=torch.uint8).contiguous()
+    if int(grid._host_geom[:, 2:].astype('int64').prod(1).max(initial=0)) > SEEN_MAX_CELLS:
+        raise RuntimeError(f'seen maps take at most {SEEN_MAX_CELLS} cells an env')
+    n = grid.n_envs
+    values = torch.zeros(max(n_maps*grid.n_cells, 1), dtype=torch.uint8, device=dev)
+    starts = torch.as_tensor(grid._host_starts, device=dev)
+    sums = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (countable[:grid.n_cells] & 1).long().cumsum(0)])
+    n_countable = (sums[starts[1:]] - sums[starts[:-1]]).int()
+    return SeenMaps(grid, n_maps, values, countable, torch.zeros((n, n_maps), dtype=torch.int32, device=dev), n_countable)

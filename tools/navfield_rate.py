@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert]
+                                  [--only fields|query|torch|envs|expert|seen]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -17,6 +17,12 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       alone; and from a 200-step rollout of PointGoal(64), under the expert and under the compass policy of the PointGoal tests
       (turn until the goal's straight line is ahead, then walk; one step in four random): arrivals, episodes, and the mean of
       (metres walked)/(walking distance at the episode's start) over the episodes that arrived.
+  (s) the seen maps, at Explorer's shape - `--envs` envs x 1 agent x 256 rays: one SeenMaps.mark (ms_nav_seen) on a rendered
+      frame - on maps that already hold the frame's cells (nothing to store), and with every map reset by the call (everything
+      to clear and store) - next to the cuda.render launch that made the frame's distances; the torch formulation of the same
+      rule on the same inputs (a padded (N, R, samples) index tensor, then a scatter and a second pass for the count), on the
+      first `--torch-envs` envs and scaled, its maps and counts compared with the kernel's; FloorCoverage(envs).step eager
+      and replayed as a HIP graph.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -136,6 +142,44 @@ def env_rates(env, n, steps, warm):
     return eager, (time.perf_counter() - t)/steps
 
 
+def torch_seen(grid, countable, origins, dirs, distances, max_range, envs):
+    """The seen maps' rule by tensor ops for the first `envs` envs, one viewer and one map each: returns run() -> (flat maps of
+    those envs, gained (envs,)) from empty maps."""
+    dev = origins.device
+    c = torch.tensor(grid.cell, dtype=torch.float32, device=dev)
+    geom = torch.as_tensor(grid._host_geom[:envs].astype(np.int64), device=dev)
+    starts = torch.as_tensor(grid._host_starts[:envs + 1], device=dev)
+    n_cells = int(grid._host_starts[envs])
+    o, d, dist = origins[:envs, 0], dirs[:envs, 0], distances[:envs, 0]
+    counts = (countable[:n_cells] & 1).bool()
+    m = torch.tensor(max_range, dtype=torch.float32, device=dev)
+
+    def run():
+        dx, dy = d[..., 0], d[..., 1]
+        rlen = torch.sqrt(dx*dx + dy*dy)
+        keep = torch.isfinite(o).all(-1)[:, None] & torch.isfinite(d).all(-1) & torch.isfinite(rlen) & (rlen > 0) & (dist > 0)
+        reach = torch.where(dist < m, dist, m)
+        ex, ey = dx/rlen*reach, dy/rlen*reach
+        k = torch.ceil(torch.sqrt(ex*ex + ey*ey)/(.5*c))
+        keep = keep & (k < 1048576.)
+        K = torch.where(keep, k, torch.ones_like(k)).clamp(min=1)
+        s = torch.arange(int(K.max()) + 1, dtype=torch.float32, device=dev)                # (a host round trip: the padding)
+        t = s/K[..., None]
+        x, y = o[:, None, None, 0] + ex[..., None]*t, o[:, None, None, 1] + ey[..., None]*t
+        fx, fy = torch.floor(x/c), torch.floor(y/c)
+        ok = keep[..., None] & (s <= K[..., None]) & (fx.abs() < 2.**30) & (fy.abs() < 2.**30)
+        j = torch.where(ok, fx, torch.zeros_like(fx)).long() - geom[:, None, None, 0]
+        i = torch.where(ok, fy, torch.zeros_like(fy)).long() - geom[:, None, None, 1]
+        nx, ny = geom[:, None, None, 2], geom[:, None, None, 3]
+        ok = ok & (i >= 0) & (i < ny) & (j >= 0) & (j < nx)
+        cell = starts[:envs, None, None] + i*nx + j
+        seen = torch.zeros(n_cells + 1, dtype=torch.bool, device=dev)
+        seen[torch.where(ok, cell, torch.full_like(cell, n_cells))] = True                 # the scatter (the spare slot: skipped samples)
+        new = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (seen[:n_cells] & counts).long().cumsum(0)])   # the second pass
+        return seen[:n_cells], (new[starts[1:]] - new[starts[:-1]]).int()
+    return run
+
+
 class ExpertStep:
     """An env whose step is the expert's own: expert() + step(), the decision handed in ignored."""
 
@@ -195,11 +239,11 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
-    from megastep_amd.demo import Explorer, PointGoal
+    from megastep_amd.demo import Explorer, FloorCoverage, PointGoal
 
     np.random.seed(0); torch.manual_seed(0)
     pool = cubicasa.sample(args.distinct, split='all', n_unique=args.distinct, workers=16, context='subprocess')
@@ -281,6 +325,47 @@ def main():
             torch.manual_seed(3); np.random.seed(3)
             out['rollout_' + policy] = score = rollout_score(PointGoal(64, geometries=small, bonus=0., max_lifespan=120), 200, policy)
             print(f'(e) PointGoal(64), 200 steps, {policy}: {score}')
+
+    if want('seen'):
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        maps = cuda.seen_maps(grid, 1)
+        frame = cuda.render(sc, c.agents, fields=('distances',))
+        med, lo, hi = timed(lambda: cuda.render(sc, c.agents, fields=('distances',), out=frame), 5*args.repeats, args.warmup)
+        out['seen_render'] = dict(seconds=med, min=lo, max=hi, rays=256)
+        print(f'(s) render, {args.envs} x 1 x 256 rays, distances only: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        origins, dirs, distances = c.agents.positions, cuda.camera_rays(c.agents), frame.distances
+        gained = maps.mark(origins, dirs, distances).clone()
+        everyone = torch.ones((args.envs, 1), dtype=torch.bool, device='cuda')
+        buffer = torch.empty_like(gained)
+        med, lo, hi = timed(lambda: maps.mark(origins, dirs, distances, out=buffer), 5*args.repeats, args.warmup)
+        fresh = timed(lambda: maps.mark(origins, dirs, distances, reset=everyone, out=buffer), 5*args.repeats, args.warmup)
+        cells = np.diff(grid._host_starts)
+        out['seen_mark'] = dict(seconds=med, min=lo, max=hi, reset_seconds=fresh[0], reset_min=fresh[1], reset_max=fresh[2], rays=256,
+                                max_range=10., cells_largest=int(cells.max()), cells_median=int(np.median(cells)),
+                                gained_mean=float(gained.float().mean()), same_after_reset=bool(torch.equal(buffer, gained)))
+        print(f"(s) mark, {args.envs} x 1 x 256 rays: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}] on maps that hold the cells; "
+              f"{fresh[0]*1e6:.1f} us [{fresh[1]*1e6:.1f}, {fresh[2]*1e6:.1f}] with every map reset; {out['seen_mark']['gained_mean']:.0f} cells gained a map")
+        k = min(args.torch_envs, args.envs)
+        run = torch_seen(grid, maps.countable, origins, dirs, distances, 10., k)
+        seen, new = run()
+        first, last = 0, int(grid._host_starts[k])
+        same = bool(torch.equal(seen, maps.values[first:last].bool()) and torch.equal(new, gained[:k, 0]))
+        med, lo, hi = timed(lambda: run(), max(args.repeats//3, 2), 1)
+        out['seen_torch'] = dict(envs=k, seconds=med, scaled_seconds=med*args.envs/k, equal_bits=same)
+        print(f'(s) torch samples + scatter, {k} envs: {med*1e3:.2f} ms -> {med*args.envs/k*1e3:.1f} ms for {args.envs}; equal maps and counts: {same}')
+        del sc, c, grid, maps
+        torch.cuda.empty_cache()
+        env = FloorCoverage(args.envs, geometries=geoms)
+        eager, graphed = env_rates(env, args.envs, 60, 10)
+        out['FloorCoverage'] = dict(eager_seconds=eager, graph_seconds=graphed)
+        print(f'(s) FloorCoverage({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+        del env
+        torch.cuda.empty_cache()
 
     if args.json:
         with open(args.json, 'w') as f:
