@@ -528,6 +528,65 @@ typedef struct MsNavPaths {
 int ms_nav_waypoints(const MsNavGrid* grid, const MsNavWaypoints* waypoints, void* hip_stream);
 int ms_nav_paths(const MsNavGrid* grid, const MsNavPaths* paths, void* hip_stream);
 
+/* Seeded fields: how far it is on foot to the NEAREST of a set of cells, and which way - the distance to the nearest floor an
+ * agent has not seen (the frontier), to the nearest door cell, to any of K pickups.  The graph, its weights and the binary32
+ * discipline are MsNavGrid's; tests/test_navseed_host.py restates the rule in numpy (seed_rule) and the kernels - and their
+ * host instantiations, ms_host_nav_seed_field / _waypoint / _path - are held to EQUALITY with it.
+ *   marks         a byte per cell and field, in MsNavSeen.maps' / MsNavFields.fields' layout: field (n, g) reads the nx*ny
+ *                 bytes from G*starts[n] + g*nx*ny (a seen map is one).  `among`, starts[N] bytes in free_cells' layout shared
+ *                 by an env's fields, or NULL.  Both are read when the call runs, not kept.
+ *   seed          cell k is a seed of field (n, g) when free[k] & 1, and among == NULL or among[k] & 1, and
+ *                 (marks[k] & 1) == where, where in {0, 1}.
+ *   field         D[seed] = +0.f, then the least fixed point of D[v] = min(D[v], fl(D[u] + w(u, v))) over MsNavGrid's edges:
+ *                 +inf on blocked cells, on cells no seed reaches, everywhere without a seed.  Every value is still the
+ *                 left-to-right binary32 sum along a path from some seed and x -> fl(x + w) is monotone: the fixed point does
+ *                 not depend on the order of relaxation, and is what a multi-source Dijkstra with binary32 additions returns,
+ *                 as bits.  D[v] == 0 exactly on seeds: every other cell holds a sum of positive weights.
+ *   n_seeds       the seeds of field (n, g); 0 for an env without cells.
+ *   query         ms_nav_query serves a seeded field as it is.
+ *   following     MsNavWaypoints' rule with one change - there is no goal point.  start: unchanged.  hop: from cell v, if
+ *                 D[v] == 0.f the chain ends at v: centre(v) is its last point and nothing follows it; otherwise the hop
+ *                 is unchanged.  chain, sight, the base index b and "the largest admissible k": unchanged.  A start whose a*
+ *                 is a seed has the chain [x_0]: the waypoint is x_0 and hops = 0.  NaN, NaN and hops = -1 where the query
+ *                 gives +inf.  path: p, x_0, ..., the seed's centre; counts positive when the chain ended on a seed, the
+ *                 number got, negated, for a broken chain, 0 without a path.
+ * One launch each, the launches of ms_nav_fields / ms_nav_waypoints / ms_nav_paths; masked-out fields keep fields, passes and
+ * n_seeds as they are.  Nothing is allocated, nothing waits: all can be captured in a HIP graph.  Every argument is checked in
+ * full before the launch (MS_EINVAL). */
+typedef struct MsNavSeedFields {
+    int                  n_fields;     /* G: fields per env                                                            */
+    const unsigned char* marks;        /* G*starts[N] bytes, bit 0: the field's layout                                 */
+    int                  where;        /* 0 or 1: a seed's mark                                                        */
+    const unsigned char* among;        /* (starts[N],) bit 0: the cell may be a seed; NULL: every free cell may        */
+    const unsigned char* mask;         /* (N, G) non-zero: compute this field; NULL: all.  Read on the device only.    */
+    float*               fields;       /* G*starts[N] floats out, as MsNavFields.fields                                */
+    int*                 passes;       /* (N, G) or NULL: relaxation passes each computed field took (telemetry)       */
+    int*                 n_seeds;      /* (N, G) or NULL: the seeds of each computed field                             */
+} MsNavSeedFields;
+typedef struct MsNavSeedWaypoints {    /* MsNavWaypoints without goals                                                 */
+    int                  n_points;
+    const float*         points;       /* (N, P, 2); 8-byte aligned                                                    */
+    const int*           goal;         /* (N, P) which of the env's fields each point follows; NULL: P == G            */
+    const float*         fields;       /* as MsNavSeedFields.fields                                                    */
+    int                  n_goals;      /* G of `fields`                                                                */
+    int                  lookahead;    /* L, 1..64                                                                     */
+    float*               waypoints;    /* (N, P, 2) out; 8-byte aligned                                                */
+    int*                 hops;         /* (N, P) out, or NULL                                                          */
+} MsNavSeedWaypoints;
+typedef struct MsNavSeedPaths {        /* MsNavPaths without goals                                                     */
+    int                  n_points;
+    const float*         points;       /* (N, P, 2); 8-byte aligned                                                    */
+    const int*           goal;         /* (N, P) or NULL, as above                                                     */
+    const float*         fields;
+    int                  n_goals;
+    int                  max_points;   /* M >= 2                                                                       */
+    float*               paths;        /* (N, P, M, 2) out                                                             */
+    int*                 counts;       /* (N, P) out                                                                   */
+} MsNavSeedPaths;
+int ms_nav_seed_fields(const MsNavGrid* grid, const MsNavSeedFields* fields, void* hip_stream);
+int ms_nav_seed_waypoints(const MsNavGrid* grid, const MsNavSeedWaypoints* waypoints, void* hip_stream);
+int ms_nav_seed_paths(const MsNavGrid* grid, const MsNavSeedPaths* paths, void* hip_stream);
+
 /* Seen maps: which cells of the nav grid the depth rays of an agent (of any viewer) have passed over - floor coverage for
  * exploration rewards, a mask to hand a policy or to draw.  As above every step is one binary32 operation in the order given,
  * without contraction, divisions and roots correctly rounded; tests/test_navseen_host.py restates it in numpy (seen_rule) and

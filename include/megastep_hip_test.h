@@ -73,6 +73,19 @@ int ms_host_nav_waypoint(const int* geom, float cell, const unsigned char* free_
                          const float* point, int lookahead, float* waypoint);
 int ms_host_nav_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal,
                      const float* point, int max_points, float* points);
+/* Host instantiations of the seeded fields (MsNavSeedFields) for ONE env on HOST arrays: geom, free_cells as above, marks
+ * (ny x nx bytes: one field's), among (ny x nx bytes) or NULL.  ms_host_nav_seed_field seeds D (ny x nx, out) by the kernel's
+ * own predicate and sweeps the kernel's own per-cell function over it, in place, until a sweep lowers nothing - framed != 0:
+ * on a framed copy with the bytes the kernel keeps in LDS (nav_cell_framed), else on D as stored (nav_cell_stored, the
+ * global-memory path); writes the number of seeds to n_seeds (or NULL) and returns the sweeps taken, 0 for an env without
+ * cells, -1 for arguments ms_nav_seed_fields would refuse.  ms_host_nav_seed_waypoint / _path follow a seeded field D as
+ * nav_waypoint_kernel / nav_path_kernel do, with the returns of ms_host_nav_waypoint / ms_host_nav_path. */
+int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* free_cells, const unsigned char* marks, int where,
+                           const unsigned char* among, int framed, float* D, int* n_seeds);
+int ms_host_nav_seed_waypoint(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* point,
+                              int lookahead, float* waypoint);
+int ms_host_nav_seed_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* point,
+                          int max_points, float* points);
 /* Host instantiation of the seen maps' rule (kernels/navseen.h: the ray, the sample - the very functions every lane of
  * nav_seen_kernel evaluates) for ONE env on HOST arrays, one call of ms_nav_seen: geom = (jx0, iy0, nx, ny), countable
  * (ny x nx bytes), origins (P, 2), dirs (P, R, 2), distances (P, R), slot (P) or NULL (then P == S), reset (S) or NULL, maps

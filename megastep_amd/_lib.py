@@ -116,6 +116,21 @@ class MsNavPaths(C.Structure):
                 ('n_goals', C.c_int), ('max_points', C.c_int), ('paths', C.c_void_p), ('counts', C.c_void_p)]
 
 
+class MsNavSeedFields(C.Structure):
+    _fields_ = [('n_fields', C.c_int), ('marks', C.c_void_p), ('where', C.c_int), ('among', C.c_void_p), ('mask', C.c_void_p),
+                ('fields', C.c_void_p), ('passes', C.c_void_p), ('n_seeds', C.c_void_p)]
+
+
+class MsNavSeedWaypoints(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('goal', C.c_void_p), ('fields', C.c_void_p), ('n_goals', C.c_int),
+                ('lookahead', C.c_int), ('waypoints', C.c_void_p), ('hops', C.c_void_p)]
+
+
+class MsNavSeedPaths(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('goal', C.c_void_p), ('fields', C.c_void_p), ('n_goals', C.c_int),
+                ('max_points', C.c_int), ('paths', C.c_void_p), ('counts', C.c_void_p)]
+
+
 class MsNavSeen(C.Structure):
     _fields_ = [('n_maps', C.c_int), ('n_viewers', C.c_int), ('n_rays', C.c_int), ('origins', C.c_void_p), ('dirs', C.c_void_p),
                 ('distances', C.c_void_p), ('slot', C.c_void_p), ('max_range', C.c_float), ('reset', C.c_void_p), ('countable', C.c_void_p),
@@ -150,6 +165,9 @@ PROTOTYPES = {
     'ms_nav_waypoints': (_int, [_p(MsNavGrid), _p(MsNavWaypoints), _ptr]),
     'ms_nav_paths': (_int, [_p(MsNavGrid), _p(MsNavPaths), _ptr]),
     'ms_nav_seen': (_int, [_p(MsNavGrid), _p(MsNavSeen), _ptr]),
+    'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
+    'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
+    'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
     'ms_wallgrid_scan': (_int, [_p(MsScenery), _p(MsWallGridParent), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr]),
     'ms_wallgrid_fill': (_int, [_p(MsScenery), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # the test hooks
@@ -170,6 +188,9 @@ PROTOTYPES = {
     'ms_host_overhead_keeps': (_int, [_f32p, _int, _int, _int, _int, _flt, _f32p]),
     'ms_host_nav_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_host_nav_seed_field': (_int, [_ptr, _flt, _ptr, _ptr, _int, _ptr, _int, _ptr, _ptr]),
+    'ms_host_nav_seed_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_host_nav_seed_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),

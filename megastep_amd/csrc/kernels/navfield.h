@@ -1,4 +1,4 @@
-// kernels/navfield.h -- nav_free_kernel, nav_relax_kernel, nav_query_kernel.
+// kernels/navfield.h -- nav_free_kernel, nav_relax_kernel (single-goal and seeded), nav_query_kernel.
 // Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after overhead.h: a cell
 // is blocked by overhead.h's ov_fold, the very statements of MsOverhead's rule); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
@@ -22,6 +22,8 @@
 //                      lower anything: the fixed point.  Then the field is stored once.  Three instantiations by the LDS
 //                      they declare (40, 80, 160 KiB: four, two, one workgroup a CU); a field too large for the launch's
 //                      one runs the same relaxation on the field in global memory - slower, the same bits.
+//                      SEEDED (MsNavSeedFields): the sources are a set of cells at +0.f instead of a goal's
+//                      anchors at their legs - the fill, the passes and the store are the single-goal kernel's.
 //   nav_query_kernel   one lane a point: the point's (at most four) anchors gathered from its field.
 constexpr int NAV_LDS_SMALL = 40*1024, NAV_LDS_MEDIUM = 80*1024, NAV_LDS_LARGE = 160*1024;
 constexpr int nav_capacity(const int lds_bytes) { return (lds_bytes - 64)/5/4*4; }      // framed cells: a float and a byte each
@@ -53,7 +55,13 @@ __host__ __device__ inline float nav_leg(const float x, const float y, const int
 
 // Racy by design (see above): relaxed atomics are plain loads and stores that the compiler may not invent, merge or carry
 // across passes.
-__device__ inline float nav_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__host__ __device__ inline float nav_load(const float* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+    return *p;                                       // (the host instantiations sweep serially)
+#endif
+}
 __device__ inline void nav_store(float* p, const float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 __global__ __launch_bounds__(WG) void nav_free_kernel(const MsScenery sc, const NavArgs a, unsigned char* free_cells) {
@@ -82,26 +90,130 @@ __global__ __launch_bounds__(WG) void nav_free_kernel(const MsScenery sc, const 
 }
 
 struct NavFieldArgs {
-    const float* goals;                              // (N, G, 2)
+    const float* goals;                              // (N, G, 2); NULL for seeded fields
     const unsigned char* mask;                       // (N, G) or NULL
     const unsigned char* free_cells;
     float* fields;
     int* passes;                                     // (N, G) or NULL: passes the field took (0: masked out)
     int n_goals;
+    const unsigned char* marks;                      // seeded fields only: a byte a cell and field, the fields' layout
+    const unsigned char* among;                      //   a byte a cell (free_cells' layout) or NULL
+    int where;                                       //   0 or 1: the value of a seed's mark
+    int* n_seeds;                                    //   (N, G) or NULL: the seeds of every computed field
 };
+
+// The per-cell pieces of the relaxation are __host__ __device__ functions over plain pointers: ms_host_nav_seed_field sweeps
+// them over host arrays, so the CPU suite holds this very text to the rule (tests/test_navseed_host.py).
 
 // The lowered value of a cell from its neighbours' (the min first, one addition per weight: x -> fl(x + w) is monotone, so
 // fl(min + w) is the min of the sums).
-__device__ inline float nav_relaxed(const float d, const float straight, const float diagonal, const float ws, const float wd) {
+__host__ __device__ inline float nav_relaxed(const float d, const float straight, const float diagonal, const float ws, const float wd) {
     return fminf(d, fminf(straight + ws, diagonal + wd));
 }
 
-template <int LDS_BYTES, int THREADS>
+// Is cell k of its env a seed (MsNavSeedFields): free, among the cells that may be one, its mark's bit 0 equal to `where`.
+__host__ __device__ inline bool nav_is_seed(const unsigned char* fr, const unsigned char* among, const unsigned char* marks, const long long k,
+                                            const int where) {
+    return (fr[k] & 1) && (!among || (among[k] & 1)) && (marks[k] & 1) == where;
+}
+
+// The framed field (row pitch P = nx + 2, a ring of blocked cells round the env's): bit 0 of framed cell k, and the cell of
+// the env it stands for (-1: the frame).
+__host__ __device__ inline int nav_frame_free(const unsigned char* fr, const int nx, const int ny, const int P, const int k, long long& cell) {
+    const int i = k / P - 1, j = k - (i + 1)*P - 1;
+    const bool inside = (i >= 0) & (i < ny) & (j >= 0) & (j < nx);
+    cell = inside ? (long long)i*nx + j : -1;
+    return inside ? fr[cell] & 1 : 0;
+}
+
+// Bits 0-4 of a free framed cell's byte: which diagonals are open - neither corner is cut.  Reads bit 0 of the neighbours only.
+__host__ __device__ inline int nav_frame_open(const unsigned char* s_m, const int k, const int P) {
+    const int N_ = s_m[k - P] & 1, S_ = s_m[k + P] & 1, W_ = s_m[k - 1] & 1, E_ = s_m[k + 1] & 1;
+    return 1 | ((N_ & W_ & s_m[k - P - 1]) << 1) | ((N_ & E_ & s_m[k - P + 1]) << 2) | ((S_ & W_ & s_m[k + P - 1]) << 3) |
+           ((S_ & E_ & s_m[k + P + 1]) << 4);
+}
+
+// What one relaxation makes of free cell k (value d, byte m) of the framed field, from its eight neighbours; a neighbour that
+// does not count is never read as less than +inf (a blocked one holds +inf, a closed diagonal is skipped).
+__host__ __device__ inline float nav_cell_framed(const float* s_d, const int m, const int k, const int P, const float d, const float ws, const float wd) {
+    const float st = fminf(fminf(nav_load(s_d + k - 1), nav_load(s_d + k + 1)), fminf(nav_load(s_d + k - P), nav_load(s_d + k + P)));
+    const float nw = m & 2 ? nav_load(s_d + k - P - 1) : INFINITY, ne = m & 4 ? nav_load(s_d + k - P + 1) : INFINITY;
+    const float sw = m & 8 ? nav_load(s_d + k + P - 1) : INFINITY, se = m & 16 ? nav_load(s_d + k + P + 1) : INFINITY;
+    return nav_relaxed(d, st, fminf(fminf(nw, ne), fminf(sw, se)), ws, wd);
+}
+
+// The same of free cell k (value d) of the field as it is stored: nx x ny, no frame, every neighbour bounds-checked.
+__host__ __device__ inline float nav_cell_stored(const float* out, const unsigned char* fr, const int nx, const int ny, const long long k, const float d,
+                                                 const float ws, const float wd) {
+    const int i = (int)(k / nx), j = (int)(k - (long long)i*nx);
+    const bool up = i > 0, down = i < ny - 1, left = j > 0, right = j < nx - 1;
+    const bool N_ = up && (fr[k - nx] & 1), S_ = down && (fr[k + nx] & 1), W_ = left && (fr[k - 1] & 1), E_ = right && (fr[k + 1] & 1);
+    const float st = fminf(fminf(W_ ? nav_load(out + k - 1) : INFINITY, E_ ? nav_load(out + k + 1) : INFINITY),
+                           fminf(N_ ? nav_load(out + k - nx) : INFINITY, S_ ? nav_load(out + k + nx) : INFINITY));
+    const float nw = N_ && W_ && (fr[k - nx - 1] & 1) ? nav_load(out + k - nx - 1) : INFINITY;
+    const float ne = N_ && E_ && (fr[k - nx + 1] & 1) ? nav_load(out + k - nx + 1) : INFINITY;
+    const float sw = S_ && W_ && (fr[k + nx - 1] & 1) ? nav_load(out + k + nx - 1) : INFINITY;
+    const float se = S_ && E_ && (fr[k + nx + 1] & 1) ? nav_load(out + k + nx + 1) : INFINITY;
+    return nav_relaxed(d, st, fminf(fminf(nw, ne), fminf(sw, se)), ws, wd);
+}
+
+// The passes, shared by the single-goal and the seeded kernel: relax in place until a pass lowers nothing; returns the passes
+// taken.  s_flag[0..2] start zeroed, behind a barrier.
+template <int THREADS>
+__device__ inline int nav_passes_framed(float* s_d, const unsigned char* s_m, int* s_flag, const int n, const int P, const float ws, const float wd) {
+    const int tid = threadIdx.x;
+    int passes = 0;
+    for (;;) {
+        if (tid == 0) s_flag[(passes + 1) % 3] = 0;                     // (last read two barriers ago)
+        bool changed = false;
+        for (int k = tid; k < n; k += THREADS) {
+            const int m = s_m[k];
+            if (m & 1) {
+                const float d = nav_load(s_d + k);
+                const float v = nav_cell_framed(s_d, m, k, P, d, ws, wd);
+                if (v < d) { nav_store(s_d + k, v); changed = true; }
+            }
+        }
+        if (changed) s_flag[passes % 3] = 1;
+        __syncthreads();
+        const int again = s_flag[passes % 3];
+        passes++;
+        if (!again) return passes;                                      // (uniform)
+    }
+}
+
+template <int THREADS>
+__device__ inline int nav_passes_stored(float* out, const unsigned char* fr, int* s_flag, const long long cells, const int nx, const int ny, const float ws,
+                                        const float wd) {
+    const int tid = threadIdx.x;
+    int passes = 0;
+    for (;;) {
+        if (tid == 0) s_flag[(passes + 1) % 3] = 0;
+        bool changed = false;
+        for (long long k = tid; k < cells; k += THREADS) {
+            if (!(fr[k] & 1)) continue;
+            const float d = nav_load(out + k);
+            const float v = nav_cell_stored(out, fr, nx, ny, k, d, ws, wd);
+            if (v < d) { nav_store(out + k, v); changed = true; }
+        }
+        if (changed) s_flag[passes % 3] = 1;
+        __syncthreads();                                                // (the workgroup's stores are visible to its loads from here on)
+        const int again = s_flag[passes % 3];
+        passes++;
+        if (!again) return passes;
+    }
+}
+
+// SEEDED: the field's sources are the cells nav_is_seed names (value +0.f) instead of a goal's anchors (value: their leg).  A
+// seed keeps bit 5 of its byte; the seeds are counted a wave at a time - one ballot a round, one LDS atomic a wave - into
+// s_flag[3].
+template <int LDS_BYTES, int THREADS, bool SEEDED>
 __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, const NavFieldArgs f) {
     constexpr int CAP = nav_capacity(LDS_BYTES);
+    constexpr int FLAGS = SEEDED ? 4 : 3;
     __shared__ float s_d[CAP];
     __shared__ unsigned char s_m[CAP];
-    __shared__ int s_flag[3];
+    __shared__ int s_flag[FLAGS];
     const int tid = threadIdx.x;
     const long long field = blockIdx.x;                                // (n, g): n G + g
     const int e = (int)(field / f.n_goals), gi = (int)(field - (long long)e*f.n_goals);
@@ -109,34 +221,47 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
     const int4 g = reinterpret_cast<const int4*>(a.geom)[e];
     const int nx = g.z, ny = g.w;
     const long long cells = (long long)nx*ny;
-    if (cells <= 0) { if (f.passes && tid == 0) f.passes[field] = 0; return; }
+    if (cells <= 0) {
+        if (f.passes && tid == 0) f.passes[field] = 0;
+        if (SEEDED && f.n_seeds && tid == 0) f.n_seeds[field] = 0;
+        return;
+    }
     const unsigned char* const fr = f.free_cells + a.starts[e];
-    float* const out = f.fields + (long long)f.n_goals*a.starts[e] + (long long)gi*cells;
+    const long long first = (long long)f.n_goals*a.starts[e] + (long long)gi*cells;
+    float* const out = f.fields + first;
+    const unsigned char* const marks = SEEDED ? f.marks + first : nullptr;
+    const unsigned char* const among = SEEDED && f.among ? f.among + a.starts[e] : nullptr;
     const float c = a.cell, ws = c, wd = c*NAV_DIAGONAL;
-    const float2 p = reinterpret_cast<const float2*>(f.goals)[field];
-    long long i0, j0;
-    const bool anchored = nav_anchor_corner(p.x, p.y, c, g.x, g.y, i0, j0);
+    float2 p = make_float2(0.f, 0.f);
+    long long i0 = 0, j0 = 0;
+    bool anchored = false;
+    if constexpr (!SEEDED) {
+        p = reinterpret_cast<const float2*>(f.goals)[field];
+        anchored = nav_anchor_corner(p.x, p.y, c, g.x, g.y, i0, j0);
+    }
     const long long framed = (long long)(nx + 2)*(ny + 2);
-    int passes = 0;
+    int passes = 0, seeds = 0;
 
     if (framed <= CAP) {
         const int P = nx + 2, n = (int)framed;
         for (int k = tid; k < n; k += THREADS) {
-            const int i = k / P - 1, j = k - (i + 1)*P - 1;
-            s_d[k] = INFINITY;
-            s_m[k] = ((i >= 0) & (i < ny) & (j >= 0) & (j < nx)) ? fr[(long long)i*nx + j] & 1 : 0;
+            long long cell;
+            const int fb = nav_frame_free(fr, nx, ny, P, k, cell);
+            bool seed = false;
+            if constexpr (SEEDED) seed = fb && nav_is_seed(fr, among, marks, cell, f.where);
+            s_d[k] = seed ? 0.f : INFINITY;
+            s_m[k] = (unsigned char)(fb | (seed ? 32 : 0));
         }
-        if (tid < 3) s_flag[tid] = 0;
+        if (tid < FLAGS) s_flag[tid] = 0;
         __syncthreads();
         for (int k = tid; k < n; k += THREADS) {                       // which diagonals are open: neither corner is cut
-            if (s_m[k] & 1) {
-                const int N_ = s_m[k - P] & 1, S_ = s_m[k + P] & 1, W_ = s_m[k - 1] & 1, E_ = s_m[k + 1] & 1;
-                const int m = 1 | ((N_ & W_ & s_m[k - P - 1]) << 1) | ((N_ & E_ & s_m[k - P + 1]) << 2) |
-                              ((S_ & W_ & s_m[k + P - 1]) << 3) | ((S_ & E_ & s_m[k + P + 1]) << 4);
-                s_m[k] = (unsigned char)m;                              // (bit 0, all a neighbour reads, does not change)
-            }
+            const int m = s_m[k];
+            if (m & 1) s_m[k] = (unsigned char)(nav_frame_open(s_m, k, P) | (m & 32));      // (bit 0, all a neighbour reads, does not change)
+            if constexpr (SEEDED) seeds += __popcll(__ballot(m & 32)); // (lane 0 has its wave's lowest k: it is in every round its wave is)
         }
-        if (anchored && tid < 4) {
+        if constexpr (SEEDED) {
+            if ((tid & 63) == 0 && seeds) atomicAdd(&s_flag[3], seeds);
+        } else if (anchored && tid < 4) {
             const long long i = i0 + (tid >> 1), j = j0 + (tid & 1);
             if ((i >= 0) & (i < ny) & (j >= 0) & (j < nx)) {
                 const int k = ((int)i + 1)*P + (int)j + 1;
@@ -144,66 +269,34 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
             }
         }
         __syncthreads();
-        for (;;) {
-            if (tid == 0) s_flag[(passes + 1) % 3] = 0;                 // (last read two barriers ago)
-            bool changed = false;
-            for (int k = tid; k < n; k += THREADS) {
-                const int m = s_m[k];
-                if (m & 1) {
-                    const float d = nav_load(s_d + k);
-                    const float st = fminf(fminf(nav_load(s_d + k - 1), nav_load(s_d + k + 1)), fminf(nav_load(s_d + k - P), nav_load(s_d + k + P)));
-                    const float nw = m & 2 ? nav_load(s_d + k - P - 1) : INFINITY, ne = m & 4 ? nav_load(s_d + k - P + 1) : INFINITY;
-                    const float sw = m & 8 ? nav_load(s_d + k + P - 1) : INFINITY, se = m & 16 ? nav_load(s_d + k + P + 1) : INFINITY;
-                    const float v = nav_relaxed(d, st, fminf(fminf(nw, ne), fminf(sw, se)), ws, wd);
-                    if (v < d) { nav_store(s_d + k, v); changed = true; }
-                }
-            }
-            if (changed) s_flag[passes % 3] = 1;
-            __syncthreads();
-            const int again = s_flag[passes % 3];
-            passes++;
-            if (!again) break;                                          // (uniform)
-        }
+        passes = nav_passes_framed<THREADS>(s_d, s_m, s_flag, n, P, ws, wd);
         for (long long k = tid; k < cells; k += THREADS) {
             const int i = (int)(k / nx), j = (int)(k - (long long)i*nx);
             out[k] = s_d[(i + 1)*P + j + 1];
         }
     } else {
         // the same relaxation on the field where it is stored
-        for (long long k = tid; k < cells; k += THREADS) out[k] = INFINITY;
-        if (tid < 3) s_flag[tid] = 0;
+        for (long long k = tid; k < cells; k += THREADS) {
+            bool seed = false;
+            if constexpr (SEEDED) {
+                seed = nav_is_seed(fr, among, marks, k, f.where);
+                seeds += __popcll(__ballot(seed));
+            }
+            out[k] = seed ? 0.f : INFINITY;
+        }
+        if (tid < FLAGS) s_flag[tid] = 0;
         __syncthreads();
-        if (anchored && tid < 4) {
+        if constexpr (SEEDED) {
+            if ((tid & 63) == 0 && seeds) atomicAdd(&s_flag[3], seeds);
+        } else if (anchored && tid < 4) {
             const long long i = i0 + (tid >> 1), j = j0 + (tid & 1);
             if ((i >= 0) & (i < ny) & (j >= 0) & (j < nx) && (fr[i*nx + j] & 1)) out[i*nx + j] = nav_leg(p.x, p.y, g.x, g.y, (int)i, (int)j, c);
         }
         __syncthreads();
-        for (;;) {
-            if (tid == 0) s_flag[(passes + 1) % 3] = 0;
-            bool changed = false;
-            for (long long k = tid; k < cells; k += THREADS) {
-                if (!(fr[k] & 1)) continue;
-                const int i = (int)(k / nx), j = (int)(k - (long long)i*nx);
-                const bool up = i > 0, down = i < ny - 1, left = j > 0, right = j < nx - 1;
-                const bool N_ = up && (fr[k - nx] & 1), S_ = down && (fr[k + nx] & 1), W_ = left && (fr[k - 1] & 1), E_ = right && (fr[k + 1] & 1);
-                const float d = nav_load(out + k);
-                const float st = fminf(fminf(W_ ? nav_load(out + k - 1) : INFINITY, E_ ? nav_load(out + k + 1) : INFINITY),
-                                       fminf(N_ ? nav_load(out + k - nx) : INFINITY, S_ ? nav_load(out + k + nx) : INFINITY));
-                const float nw = N_ && W_ && (fr[k - nx - 1] & 1) ? nav_load(out + k - nx - 1) : INFINITY;
-                const float ne = N_ && E_ && (fr[k - nx + 1] & 1) ? nav_load(out + k - nx + 1) : INFINITY;
-                const float sw = S_ && W_ && (fr[k + nx - 1] & 1) ? nav_load(out + k + nx - 1) : INFINITY;
-                const float se = S_ && E_ && (fr[k + nx + 1] & 1) ? nav_load(out + k + nx + 1) : INFINITY;
-                const float v = nav_relaxed(d, st, fminf(fminf(nw, ne), fminf(sw, se)), ws, wd);
-                if (v < d) { nav_store(out + k, v); changed = true; }
-            }
-            if (changed) s_flag[passes % 3] = 1;
-            __syncthreads();                                            // (the workgroup's stores are visible to its loads from here on)
-            const int again = s_flag[passes % 3];
-            passes++;
-            if (!again) break;
-        }
+        passes = nav_passes_stored<THREADS>(out, fr, s_flag, cells, nx, ny, ws, wd);
     }
     if (f.passes && tid == 0) f.passes[field] = passes;
+    if (SEEDED && f.n_seeds && tid == 0) f.n_seeds[field] = s_flag[FLAGS - 1];
 }
 
 struct NavQueryArgs {

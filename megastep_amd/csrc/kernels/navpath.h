@@ -32,13 +32,15 @@ struct NavGoal {                                     // the field's goal q and i
     float x, y;
     bool anchored;
     long long i0, j0;
+    bool seeded;                                     // a seeded field (MsNavSeedFields): no goal point, a chain ends on a cell at 0
 };
 
 __host__ __device__ inline NavGoal nav_goal(const NavEnv& g, const float x, const float y) {
-    NavGoal q{x, y, false, 0, 0};
+    NavGoal q{x, y, false, 0, 0, false};
     q.anchored = nav_anchor_corner(x, y, g.c, g.jx0, g.iy0, q.i0, q.j0);
     return q;
 }
+__host__ __device__ inline NavGoal nav_seeded() { return NavGoal{0.f, 0.f, false, 0, 0, true}; }
 
 __host__ __device__ inline bool nav_is_free(const NavEnv& g, const long long i, const long long j) {
     return (i >= 0) & (i < g.ny) & (j >= 0) & (j < g.nx) && (g.free[i*g.nx + j] & 1);
@@ -79,14 +81,16 @@ __host__ __device__ inline float nav_neighbour(const NavEnv& g, const int i, con
     return du + (t < 4 ? g.c : g.c*NAV_DIAGONAL);
 }
 
-// Does the chain end at cell (i, j): one of the goal's anchor cells whose value is its own leg to the goal.
+// Does the chain end at cell (i, j): one of the goal's anchor cells whose value is its own leg to the goal; on a seeded
+// field, a seed - the cells at 0, every other one holding a sum of positive weights.
 __host__ __device__ inline bool nav_chain_ends(const NavEnv& g, const NavGoal& q, const int i, const int j) {
+    if (q.seeded) return g.D[(long long)i*g.nx + j] == 0.f;
     if (!q.anchored || i < q.i0 || i > q.i0 + 1 || j < q.j0 || j > q.j0 + 1) return false;
     return nav_leg(q.x, q.y, g.jx0, g.iy0, i, j, g.c) == g.D[(long long)i*g.nx + j];
 }
 
 // One hop from cell (i, j).  1: on to the next cell, now in (i, j); 0: the chain ends here, its last point is the goal
-// itself; -1: broken (no neighbour below D[v]: a stale or foreign field) - it stops.
+// itself (seeded: this cell's centre); -1: broken (no neighbour below D[v]: a stale or foreign field) - it stops.
 __host__ __device__ inline int nav_hop(const NavEnv& g, const NavGoal& q, int& i, int& j) {
     if (nav_chain_ends(g, q, i, j)) return 0;
     float best = INFINITY, dbest = INFINITY;
@@ -126,9 +130,9 @@ __host__ __device__ inline bool nav_sight(const NavEnv& g, const float px, const
     return true;
 }
 
-// The path from p: p, x_0, x_1, ..., q.  Walks the whole chain (at most `cells` hops: D falls at every one), writes the first
-// M points to out (M x 2; NaN in the slots beyond) and returns the number of points: 0 without a path, negated for a
-// broken chain.
+// The path from p: p, x_0, x_1, ..., q (seeded: ..., the seed's centre).  Walks the whole chain (at most `cells` hops: D falls
+// at every one), writes the first M points to out (M x 2; NaN in the slots beyond) and returns the number of points: 0 without
+// a path, negated for a broken chain.
 __host__ __device__ inline int nav_path(const NavEnv& g, const NavGoal& q, const float px, const float py, const long long cells, const int M, float* out) {
     int count = 0, i = 0, j = 0, state = -1;
     float leg0;
@@ -140,7 +144,7 @@ __host__ __device__ inline int nav_path(const NavEnv& g, const NavGoal& q, const
             state = nav_hop(g, q, i, j);
             if (state != 1) break;
         }
-        if (state == 0) {
+        if (state == 0 && !q.seeded) {
             if (count < M) { out[2*count] = q.x; out[2*count + 1] = q.y; }
             count++;
         }
@@ -160,7 +164,7 @@ inline int nav_waypoint_serial(const NavEnv& g, const NavGoal& q, const float px
         xs[n] = nav_centre(g.jx0, j, g.c); ys[n] = nav_centre(g.iy0, i, g.c); n++;
         if (n >= L) break;
         const int state = nav_hop(g, q, i, j);
-        if (state == 0) { xs[n] = q.x; ys[n] = q.y; n++; }
+        if (state == 0 && !q.seeded) { xs[n] = q.x; ys[n] = q.y; n++; }
         if (state != 1) break;
     }
     const int b = (leg0 <= .5f*g.c && n >= 2) ? 1 : 0;
@@ -174,7 +178,7 @@ struct NavPathArgs {                                 // MsNavWaypoints / MsNavPa
     const float* points;                             // (N, P, 2)
     const int* goal;                                 // (N, P) or NULL
     const float* fields;
-    const float* goals;                              // (N, G, 2)
+    const float* goals;                              // (N, G, 2); NULL: seeded fields, which have none
     const unsigned char* free_cells;
     float* waypoints;                                // (N, P, 2)
     int* hops;                                       // (N, P) or NULL
@@ -192,8 +196,10 @@ __device__ inline bool nav_bind(const NavArgs& a, const NavPathArgs& q, const lo
     cells = (long long)geom.z*geom.w;
     if ((gi < 0) | (gi >= q.n_goals) || cells <= 0) return false;
     g = NavEnv{geom.x, geom.y, geom.z, geom.w, a.cell, q.free_cells + a.starts[e], q.fields + (long long)q.n_goals*a.starts[e] + (long long)gi*cells};
-    const float2 p = reinterpret_cast<const float2*>(q.goals)[(long long)e*q.n_goals + gi];
-    goal = nav_goal(g, p.x, p.y);
+    if (q.goals) {
+        const float2 p = reinterpret_cast<const float2*>(q.goals)[(long long)e*q.n_goals + gi];
+        goal = nav_goal(g, p.x, p.y);
+    } else goal = nav_seeded();
     return true;
 }
 
@@ -217,8 +223,10 @@ __global__ __launch_bounds__(WG) void nav_waypoint_kernel(const NavArgs a, const
             n++;
             if (n >= L) break;
             if (nav_chain_ends(g, goal, i, j)) {
-                if (lane == n) { mx = goal.x; my = goal.y; }
-                n++;
+                if (!goal.seeded) {                                     // (uniform: the launch's mode)
+                    if (lane == n) { mx = goal.x; my = goal.y; }
+                    n++;
+                }
                 break;
             }
             // nav_hop's fold, a neighbour a lane: the least value, then the first lane that holds it

@@ -48,7 +48,8 @@
 //                   these with matplotlib, one env at a time on the host)
 //   nav_free_kernel, nav_relax_kernel, nav_query_kernel   shortest-path distance fields: which cells of a grid over a floorplan
 //                   keep the agent's radius clear of every wall; per goal one workgroup that relaxes the 8-connected field in
-//                   LDS until nothing changes; and the distance from any point to a goal, four gathers.   (no counterpart)
+//                   LDS until nothing changes - from a goal's anchors, or (SEEDED) from a set of cells at 0: the distance to
+//                   the nearest of them; and the distance from any point to a goal, four gathers.   (no counterpart)
 //   nav_waypoint_kernel, nav_path_kernel   which way to go on those fields: one wavefront per point descends the field a
 //                   neighbour a lane and picks the furthest of the next cells the point can see; and whole paths, a lane
 //                   each.   (no counterpart)
@@ -72,6 +73,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <vector>
 #include "../../include/megastep_hip_test.h"
 
 namespace {
@@ -806,22 +808,38 @@ int ms_nav_free(const MsScenery* sc, const MsNavGrid* grid, void* stream) {
     return launch_status();
 }
 
+// The launch of either relaxation: the least LDS that holds the largest env's framed field - more workgroups a CU (a field
+// that still does not fit - or an env larger than max_framed says - relaxes in global memory).
+static int nav_relax_launch(const MsNavGrid* grid, const NavFieldArgs& f, long long total, bool seeded, void* stream) {
+    const long long framed = grid->max_framed;
+    void (*kernel)(NavArgs, NavFieldArgs);
+    int threads = 1024;
+    if (framed <= nav_capacity(NAV_LDS_SMALL)) {
+        kernel = seeded ? nav_relax_kernel<NAV_LDS_SMALL, 512, true> : nav_relax_kernel<NAV_LDS_SMALL, 512, false>;
+        threads = 512;
+    } else if (framed <= nav_capacity(NAV_LDS_MEDIUM))
+        kernel = seeded ? nav_relax_kernel<NAV_LDS_MEDIUM, 1024, true> : nav_relax_kernel<NAV_LDS_MEDIUM, 1024, false>;
+    else
+        kernel = seeded ? nav_relax_kernel<NAV_LDS_LARGE, 1024, true> : nav_relax_kernel<NAV_LDS_LARGE, 1024, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(threads), 0, (hipStream_t)stream, nav_args(grid), f);
+    return launch_status();
+}
+
 int ms_nav_fields(const MsNavGrid* grid, const MsNavFields* nf, void* stream) {
     if (!nav_grid_ok(grid) || !nf || nf->n_goals < 1 || !nf->goals || !nf->fields || ((uintptr_t)nf->goals % 8)) return MS_EINVAL;
     const long long total = (long long)grid->n_envs*nf->n_goals;
     if (total > 0x7fffffffLL) return MS_EUNSUPPORTED;
-    const NavFieldArgs f{nf->goals, nf->mask, grid->free_cells, nf->fields, nf->passes, nf->n_goals};
-    // the least LDS that holds the largest env's framed field: more workgroups a CU (a field that still does not fit - or an
-    // env larger than max_framed says - relaxes in global memory)
-    const long long framed = grid->max_framed;
-    const dim3 fields((unsigned)total);
-    if (framed <= nav_capacity(NAV_LDS_SMALL))
-        hipLaunchKernelGGL((nav_relax_kernel<NAV_LDS_SMALL, 512>), fields, dim3(512), 0, (hipStream_t)stream, nav_args(grid), f);
-    else if (framed <= nav_capacity(NAV_LDS_MEDIUM))
-        hipLaunchKernelGGL((nav_relax_kernel<NAV_LDS_MEDIUM, 1024>), fields, dim3(1024), 0, (hipStream_t)stream, nav_args(grid), f);
-    else
-        hipLaunchKernelGGL((nav_relax_kernel<NAV_LDS_LARGE, 1024>), fields, dim3(1024), 0, (hipStream_t)stream, nav_args(grid), f);
-    return launch_status();
+    const NavFieldArgs f{nf->goals, nf->mask, grid->free_cells, nf->fields, nf->passes, nf->n_goals, nullptr, nullptr, 0, nullptr};
+    return nav_relax_launch(grid, f, total, false, stream);
+}
+
+int ms_nav_seed_fields(const MsNavGrid* grid, const MsNavSeedFields* sf, void* stream) {
+    if (!nav_grid_ok(grid) || !sf || sf->n_fields < 1 || !sf->marks || !sf->fields || (sf->where != 0 && sf->where != 1) ||
+        ((uintptr_t)sf->fields % 4) || ((uintptr_t)sf->passes % 4) || ((uintptr_t)sf->n_seeds % 4)) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*sf->n_fields;
+    if (total > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    const NavFieldArgs f{nullptr, sf->mask, grid->free_cells, sf->fields, sf->passes, sf->n_fields, sf->marks, sf->among, sf->where, sf->n_seeds};
+    return nav_relax_launch(grid, f, total, true, stream);
 }
 
 int ms_nav_query(const MsNavGrid* grid, const MsNavQuery* nq, void* stream) {
@@ -835,32 +853,58 @@ int ms_nav_query(const MsNavGrid* grid, const MsNavQuery* nq, void* stream) {
 }
 
 // Paths and waypoints (navpath.h): the same discipline.
-static bool nav_follow_ok(const MsNavGrid* grid, int n_points, const float* points, const int* goal, const float* fields, const float* goals,
-                          int n_goals) {
-    return nav_grid_ok(grid) && n_points >= 1 && n_goals >= 1 && points && fields && goals && (goal || n_points == n_goals) &&
-           ((uintptr_t)points % 8 == 0) && ((uintptr_t)goals % 8 == 0) && ((uintptr_t)fields % 4 == 0) && ((uintptr_t)goal % 4 == 0);
+static bool nav_follow_ok(const MsNavGrid* grid, int n_points, const float* points, const int* goal, const float* fields, int n_goals) {
+    return nav_grid_ok(grid) && n_points >= 1 && n_goals >= 1 && points && fields && (goal || n_points == n_goals) &&
+           ((uintptr_t)points % 8 == 0) && ((uintptr_t)fields % 4 == 0) && ((uintptr_t)goal % 4 == 0);
 }
+static bool nav_goals_ok(const float* goals) { return goals && ((uintptr_t)goals % 8 == 0); }
 
-int ms_nav_waypoints(const MsNavGrid* grid, const MsNavWaypoints* w, void* stream) {
-    if (!w || !nav_follow_ok(grid, w->n_points, w->points, w->goal, w->fields, w->goals, w->n_goals) || w->lookahead < 1 ||
-        w->lookahead > WAVE || !w->waypoints || ((uintptr_t)w->waypoints % 8) || ((uintptr_t)w->hops % 4)) return MS_EINVAL;
-    const long long total = (long long)grid->n_envs*w->n_points;
+// The two launches, for fields of goals and - goals NULL - for seeded fields; the arguments are checked by then.
+static int nav_waypoints_launch(const MsNavGrid* grid, int n_points, const float* points, const int* goal, const float* fields, const float* goals,
+                                int n_goals, int lookahead, float* waypoints, int* hops, void* stream) {
+    const long long total = (long long)grid->n_envs*n_points;
     if ((total + WAVES - 1)/WAVES > 0x7fffffffLL) return MS_EUNSUPPORTED;
-    const NavPathArgs q{w->points, w->goal, w->fields, w->goals, grid->free_cells, w->waypoints, w->hops, nullptr, nullptr,
-                        w->n_points, w->n_goals, w->lookahead, 0, total};
+    const NavPathArgs q{points, goal, fields, goals, grid->free_cells, waypoints, hops, nullptr, nullptr, n_points, n_goals, lookahead, 0, total};
     hipLaunchKernelGGL(nav_waypoint_kernel, dim3((unsigned)((total + WAVES - 1)/WAVES)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
     return launch_status();
 }
-
-int ms_nav_paths(const MsNavGrid* grid, const MsNavPaths* np, void* stream) {
-    if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->goals, np->n_goals) || np->max_points < 2 ||
-        !np->paths || !np->counts || ((uintptr_t)np->paths % 4) || ((uintptr_t)np->counts % 4)) return MS_EINVAL;
-    const long long total = (long long)grid->n_envs*np->n_points;
+static int nav_paths_launch(const MsNavGrid* grid, int n_points, const float* points, const int* goal, const float* fields, const float* goals,
+                            int n_goals, int max_points, float* paths, int* counts, void* stream) {
+    const long long total = (long long)grid->n_envs*n_points;
     if (total > 0x7fffff00LL) return MS_EUNSUPPORTED;
-    const NavPathArgs q{np->points, np->goal, np->fields, np->goals, grid->free_cells, nullptr, nullptr, np->paths, np->counts,
-                        np->n_points, np->n_goals, 0, np->max_points, total};
+    const NavPathArgs q{points, goal, fields, goals, grid->free_cells, nullptr, nullptr, paths, counts, n_points, n_goals, 0, max_points, total};
     hipLaunchKernelGGL(nav_path_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
     return launch_status();
+}
+static bool nav_waypoints_ok(int lookahead, const float* waypoints, const int* hops) {
+    return lookahead >= 1 && lookahead <= WAVE && waypoints && ((uintptr_t)waypoints % 8 == 0) && ((uintptr_t)hops % 4 == 0);
+}
+static bool nav_paths_ok(int max_points, const float* paths, const int* counts) {
+    return max_points >= 2 && paths && counts && ((uintptr_t)paths % 4 == 0) && ((uintptr_t)counts % 4 == 0);
+}
+
+int ms_nav_waypoints(const MsNavGrid* grid, const MsNavWaypoints* w, void* stream) {
+    if (!w || !nav_follow_ok(grid, w->n_points, w->points, w->goal, w->fields, w->n_goals) || !nav_goals_ok(w->goals) ||
+        !nav_waypoints_ok(w->lookahead, w->waypoints, w->hops)) return MS_EINVAL;
+    return nav_waypoints_launch(grid, w->n_points, w->points, w->goal, w->fields, w->goals, w->n_goals, w->lookahead, w->waypoints, w->hops, stream);
+}
+
+int ms_nav_paths(const MsNavGrid* grid, const MsNavPaths* np, void* stream) {
+    if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->n_goals) || !nav_goals_ok(np->goals) ||
+        !nav_paths_ok(np->max_points, np->paths, np->counts)) return MS_EINVAL;
+    return nav_paths_launch(grid, np->n_points, np->points, np->goal, np->fields, np->goals, np->n_goals, np->max_points, np->paths, np->counts, stream);
+}
+
+int ms_nav_seed_waypoints(const MsNavGrid* grid, const MsNavSeedWaypoints* w, void* stream) {
+    if (!w || !nav_follow_ok(grid, w->n_points, w->points, w->goal, w->fields, w->n_goals) ||
+        !nav_waypoints_ok(w->lookahead, w->waypoints, w->hops)) return MS_EINVAL;
+    return nav_waypoints_launch(grid, w->n_points, w->points, w->goal, w->fields, nullptr, w->n_goals, w->lookahead, w->waypoints, w->hops, stream);
+}
+
+int ms_nav_seed_paths(const MsNavGrid* grid, const MsNavSeedPaths* np, void* stream) {
+    if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->n_goals) ||
+        !nav_paths_ok(np->max_points, np->paths, np->counts)) return MS_EINVAL;
+    return nav_paths_launch(grid, np->n_points, np->points, np->goal, np->fields, nullptr, np->n_goals, np->max_points, np->paths, np->counts, stream);
 }
 
 static bool nav_host_env(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal, const float* point,
@@ -888,6 +932,79 @@ int ms_host_nav_path(const int* geom, float cell, const unsigned char* free_cell
         return 0;
     }
     return nav_path(g, nav_goal(g, goal[0], goal[1]), point[0], point[1], (long long)g.nx*g.ny, max_points, points);
+}
+
+int ms_host_nav_seed_waypoint(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* point, int lookahead,
+                              float* waypoint) {
+    if (lookahead < 1 || lookahead > WAVE || !waypoint) return -2;
+    waypoint[0] = waypoint[1] = NAN;
+    NavEnv g;
+    if (!nav_host_env(geom, cell, free_cells, D, point, point, g)) return -1;
+    return nav_waypoint_serial(g, nav_seeded(), point[0], point[1], lookahead, waypoint[0], waypoint[1]);
+}
+
+int ms_host_nav_seed_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* point, int max_points,
+                          float* points) {
+    if (max_points < 2 || !points) return 0;
+    NavEnv g;
+    if (!nav_host_env(geom, cell, free_cells, D, point, point, g)) {
+        for (int k = 0; k < 2*max_points; k++) points[k] = NAN;
+        return 0;
+    }
+    return nav_path(g, nav_seeded(), point[0], point[1], (long long)g.nx*g.ny, max_points, points);
+}
+
+int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* free_cells, const unsigned char* marks, int where,
+                           const unsigned char* among, int framed, float* D, int* n_seeds) {
+    if (!geom || !(cell > 0.f) || !(cell < INFINITY) || (where != 0 && where != 1) || geom[2] < 0 || geom[3] < 0) return -1;
+    const int nx = geom[2], ny = geom[3];
+    const long long cells = (long long)nx*ny;
+    if (n_seeds) *n_seeds = 0;
+    if (cells <= 0) return 0;
+    if (!free_cells || !marks || !D || (long long)(nx + 2)*(ny + 2) > 0x7fffffffLL) return -1;
+    const float ws = cell, wd = cell*NAV_DIAGONAL;
+    int seeds = 0, sweeps = 0;
+    if (framed) {
+        // as the kernel fills its LDS: the frame, the bytes, the seeds; then nav_cell_framed swept in place
+        const int P = nx + 2, n = (nx + 2)*(ny + 2);
+        std::vector<float> d(n);
+        std::vector<unsigned char> m(n);
+        for (int k = 0; k < n; k++) {
+            long long at;
+            const int fb = nav_frame_free(free_cells, nx, ny, P, k, at);
+            const bool seed = fb && nav_is_seed(free_cells, among, marks, at, where);
+            d[k] = seed ? 0.f : INFINITY;
+            m[k] = (unsigned char)(fb | (seed ? 32 : 0));
+            seeds += seed;
+        }
+        for (int k = 0; k < n; k++)
+            if (m[k] & 1) m[k] = (unsigned char)(nav_frame_open(m.data(), k, P) | (m[k] & 32));
+        for (bool changed = true; changed; sweeps++) {
+            changed = false;
+            for (int k = 0; k < n; k++) {
+                if (!(m[k] & 1)) continue;
+                const float v = nav_cell_framed(d.data(), m[k], k, P, d[k], ws, wd);
+                if (v < d[k]) { d[k] = v; changed = true; }
+            }
+        }
+        for (long long k = 0; k < cells; k++) D[k] = d[(k / nx + 1)*P + k % nx + 1];
+    } else {
+        for (long long k = 0; k < cells; k++) {
+            const bool seed = nav_is_seed(free_cells, among, marks, k, where);
+            D[k] = seed ? 0.f : INFINITY;
+            seeds += seed;
+        }
+        for (bool changed = true; changed; sweeps++) {
+            changed = false;
+            for (long long k = 0; k < cells; k++) {
+                if (!(free_cells[k] & 1)) continue;
+                const float v = nav_cell_stored(D, free_cells, nx, ny, k, D[k], ws, wd);
+                if (v < D[k]) { D[k] = v; changed = true; }
+            }
+        }
+    }
+    if (n_seeds) *n_seeds = seeds;
+    return sweeps;
 }
 
 // Seen maps (navseen.h): the same discipline; an env of more than 2^20 cells is refused, and nothing is enqueued.

@@ -47,6 +47,8 @@ class FloorCoverage:
 
         self._over = c.agent_full(True)                 # who starts over at the next step
         self._episodes = torch.zeros((c.n_envs, c.n_agents), dtype=torch.long, device=c.device)
+        self._fresh = c.agent_full(False)               # who started over since the expert was last asked
+        self._frontiers = self._follower = None         # made when the expert is first asked: they cost nothing until then
 
     #: the :class:`~megastep_amd.cuda.SeenMaps`
     maps = property(lambda self: self._coverage.maps)
@@ -63,6 +65,7 @@ class FloorCoverage:
     def _world(self, reset):
         frame = modules.render(self.core, observers=(self._rgb, self._depth), fields=('distances',))
         reward = self._coverage(frame, reset)           # (the maps of those who started over are cleared by the same launch)
+        self._fresh |= reset
         ended = self._coverage.fraction() >= self.complete
         self._over.copy_(self._lifespans(ended))
         obs = arrdict.arrdict(rgb=self._rgb(frame), d=self._depth(frame), coverage=self._coverage.observation())
@@ -81,6 +84,20 @@ class FloorCoverage:
         over = self._over.clone()
         self._mover(decision, respawn=self._respawn(over))
         return self._world(over)
+
+    @torch.no_grad()
+    def expert(self):
+        """``arrdict(actions=(n_env, n_agent))``: what the frontier follower does in the current state - every agent towards the
+        waypoint of the nearest floor its map has not seen (:class:`~megastep_amd.modules.Frontiers` under a
+        :class:`~megastep_amd.modules.PathFollower`); nothing (0) where nothing is left to see. Nothing waits for the host:
+        ``env.step(env.expert())`` can sit in one graph, once a first call outside it has made the fields. The fields are
+        refreshed, and the follower counts the steps an agent has been stuck, on every call: ask once per step."""
+        if self._frontiers is None:
+            self._frontiers = modules.Frontiers(self.core, self._coverage)
+            self._follower = modules.PathFollower(self.core, self._frontiers, cone=15.)
+        self._frontiers(self._fresh)
+        self._fresh.zero_()
+        return self._follower()
 
     def state(self, e=0):
         return arrdict.arrdict(core=self.core.state(e), rgb=self._rgb.state(e), d=self._depth.state(e), seen=self._coverage.state(e),

@@ -531,10 +531,50 @@ class Coverage:
         return torch.stack([self.maps.image(e, s) for s in range(self.maps.n_maps)]).clone()
 
 
+class Frontiers:
+
+    def __init__(self, core, coverage, refresh=8):
+        """How far every agent has to walk to the nearest floor its map has not seen, and which way (no counterpart in the
+        reference): the frontier fields of a :class:`Coverage`'s maps (:meth:`cuda.SeenMaps.frontier_fields`), one field per
+        map. A field is recomputed every ``refresh`` steps of its agent and when the agent starts over; in between it is a
+        few steps stale, which costs a detour at worst - a stale field is still a whole field, and leads to a cell that was
+        unseen when it was computed. :meth:`waypoints` has the shape :class:`PathFollower` takes from :class:`Goals`. With
+        ``coverage.shared`` an env has one field, which all its agents follow. Nothing waits for the host: which fields are
+        due is decided on the device, so a call can sit in a HIP graph."""
+        self.core, self.coverage, self.refresh = core, coverage, int(refresh)
+        if self.refresh < 1:
+            raise RuntimeError(f'refresh must be a positive integer; got {refresh}')
+        self._steps = torch.zeros((core.n_envs, core.n_agents), dtype=torch.long, device=core.device)
+        self._field = coverage._slot                    # (n_env, n_agent) zeros when the map is shared, else None: agent k field k
+        self.fields = coverage.maps.frontier_fields()
+
+    def __call__(self, reset=None):
+        """Recomputes the fields that are due: those of the agents marked in the (n_env, n_agent) bool ``reset`` - they started
+        over, their maps are empty again - and those whose agent has taken a multiple of ``refresh`` steps since. Call once per
+        step, after the maps were marked."""
+        if reset is not None:
+            self._steps.masked_fill_(reset, 0)
+        due = self._steps % self.refresh == 0
+        self._steps += 1
+        if self.coverage.shared:
+            due = due.any(-1, keepdim=True)
+        self.fields.update(due)
+        return self.fields
+
+    def distance(self):
+        """(n_env, n_agent): how far every agent has to walk to the nearest unseen floor; +inf where there is none it can reach."""
+        return self.fields.at(self.core.agents.positions, goal=self._field)
+
+    def waypoints(self, lookahead=16):
+        """(n_env, n_agent, 2): where every agent should head for now to walk to the nearest unseen floor
+        (:meth:`cuda.SeededFields.waypoints`); NaN where :meth:`distance` is +inf."""
+        return self.fields.waypoints(self.core.agents.positions, goal=self._field, lookahead=lookahead)
+
+
 class PathFollower:
 
     def __init__(self, core, goals, lookahead=16, cone=45., speed=2.):
-        """The shortest-path expert over a :class:`Goals`: every agent turns towards its waypoint - the furthest of the next
+        """The shortest-path expert over a :class:`Goals` (or a :class:`Frontiers`: anything with ``waypoints(lookahead)``): every agent turns towards its waypoint - the furthest of the next
         ``lookahead`` cells of its shortest path that it can see (:meth:`Goals.waypoints`) - and walks once that lies within
         ``cone`` degrees of straight ahead. Something to imitate, to fill a replay buffer with, to score a learned policy
         against (Habitat's ``ShortestPathFollower``; no counterpart in the reference). Other agents are not obstacles to

@@ -1,4 +1,5 @@
-"""Navigation grids, shortest-path distance fields, waypoints and paths on the floorplans, and the seen maps of the depth rays
+"""Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
+floorplans, and the seen maps of the depth rays
 (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``). No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
@@ -108,36 +109,16 @@ def nav_grid(scenery, cell=.125, clearance=None, config=None):
     return grid
 
 
-class DistanceFields:
-    """Result of :func:`distance_fields`: for each env ``G`` fields, field (n, g) holding for every cell of env n's grid the
-    length of the shortest 8-connected path from the cell's centre to ``goals[n, g]`` (+inf on blocked cells and on cells no
-    path reaches). ``values`` is the flat float32 store: field (n, g) starts at ``G*grid.starts[n] + g*nx*ny``."""
-
-    def __init__(self, grid, goals, values, passes=None):
-        self.grid, self.goals, self.values, self.passes = grid, goals, values, passes
-
-    n_goals = property(lambda self: self.goals.shape[1])
+class _Fields:
+    """What :class:`DistanceFields` and :class:`SeededFields` share: the flat store of ``n_goals`` fields per env, its views, the
+    query and the argument rules of the calls that follow the fields. A subclass names its own tensors (``_own``) and makes the
+    two launches that differ (``_waypoints_call``, ``_paths_call``)."""
 
     def image(self, e, g=0):
         """(ny, nx) float32 view of field ``g`` of env ``e``, row 0 at the lowest y."""
         s, ny, nx = self.grid.cells(e)
         at = self.n_goals*s + g*ny*nx
         return self.values[at:at + ny*nx].reshape(ny, nx)
-
-    def update(self, goals=None, mask=None):
-        """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place - for ``goals`` (N, G, 2), which are
-        copied into :attr:`goals` where marked, or for the goals as they stand. One launch, no host synchronisation."""
-        if goals is not None:
-            _check(goals, 'goals', torch.float32, 3)
-            if goals.shape != self.goals.shape:
-                raise RuntimeError(f'goals must be {tuple(self.goals.shape)}; got {tuple(goals.shape)}')
-            if goals is not self.goals:
-                if mask is None:
-                    self.goals.copy_(goals)
-                else:
-                    torch.where(mask[..., None], goals, self.goals, out=self.goals)
-        _nav_fields_call(self, mask)
-        return self
 
     def at(self, points, goal=None, out=None):
         """(N, P) float32: the distance from each of ``points`` (N, P, 2) to a goal of its env - ``goal`` (N, P) integers name
@@ -168,7 +149,7 @@ class DistanceFields:
             if not isinstance(goal, torch.Tensor) or goal.dtype.is_floating_point or goal.shape != (n, p):
                 raise RuntimeError(f'goal must be an (N, P) = ({n}, {p}) integer tensor')
             goal = goal.to(torch.int32).contiguous()
-        dev = _require_gpu(points, self.values, self.goals, grid.free, *([goal] if goal is not None else []))
+        dev = _require_gpu(points, self.values, *self._own(), grid.free, *([goal] if goal is not None else []))
         return n, p, goal, dev
 
     def waypoints(self, points, goal=None, lookahead=16, hops=False, out=None):
@@ -184,10 +165,9 @@ class DistanceFields:
         n, p, goal, dev = self._queries(points, goal)
         out = _answer(out, (n, p, 2), dev)
         chosen = torch.empty((n, p), dtype=torch.int32, device=dev) if hops else None
-        spec = _lib.MsNavWaypoints(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
-                                   self.goals.data_ptr(), self.n_goals, lookahead, out.data_ptr(), chosen.data_ptr() if hops else None)
         with _on(dev):
-            _lib.check(_lib.lib().ms_nav_waypoints(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+            _lib.check(self._waypoints_call(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, lookahead, out.data_ptr(),
+                                            chosen.data_ptr() if hops else None, _stream(dev)))
         return (out, chosen) if hops else out
 
     def paths(self, points, goal=None, max_points=256):
@@ -199,11 +179,47 @@ class DistanceFields:
         n, p, goal, dev = self._queries(points, goal)
         pts = torch.empty((n, p, max_points, 2), dtype=torch.float32, device=dev)
         counts = torch.empty((n, p), dtype=torch.int32, device=dev)
-        spec = _lib.MsNavPaths(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
-                               self.goals.data_ptr(), self.n_goals, max_points, pts.data_ptr(), counts.data_ptr())
         with _on(dev):
-            _lib.check(_lib.lib().ms_nav_paths(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+            _lib.check(self._paths_call(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, max_points, pts.data_ptr(),
+                                        counts.data_ptr(), _stream(dev)))
         return Paths(pts, counts)
+
+
+class DistanceFields(_Fields):
+    """Result of :func:`distance_fields`: for each env ``G`` fields, field (n, g) holding for every cell of env n's grid the
+    length of the shortest 8-connected path from the cell's centre to ``goals[n, g]`` (+inf on blocked cells and on cells no
+    path reaches). ``values`` is the flat float32 store: field (n, g) starts at ``G*grid.starts[n] + g*nx*ny``."""
+
+    def __init__(self, grid, goals, values, passes=None):
+        self.grid, self.goals, self.values, self.passes = grid, goals, values, passes
+
+    n_goals = property(lambda self: self.goals.shape[1])
+
+    def _own(self):
+        return (self.goals,)
+
+    def _waypoints_call(self, p, points, goal, lookahead, out, hops, stream):
+        spec = _lib.MsNavWaypoints(p, points, goal, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, lookahead, out, hops)
+        return _lib.lib().ms_nav_waypoints(C.byref(self.grid._struct), C.byref(spec), stream)
+
+    def _paths_call(self, p, points, goal, max_points, out, counts, stream):
+        spec = _lib.MsNavPaths(p, points, goal, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, max_points, out, counts)
+        return _lib.lib().ms_nav_paths(C.byref(self.grid._struct), C.byref(spec), stream)
+
+    def update(self, goals=None, mask=None):
+        """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place - for ``goals`` (N, G, 2), which are
+        copied into :attr:`goals` where marked, or for the goals as they stand. One launch, no host synchronisation."""
+        if goals is not None:
+            _check(goals, 'goals', torch.float32, 3)
+            if goals.shape != self.goals.shape:
+                raise RuntimeError(f'goals must be {tuple(self.goals.shape)}; got {tuple(goals.shape)}')
+            if goals is not self.goals:
+                if mask is None:
+                    self.goals.copy_(goals)
+                else:
+                    torch.where(mask[..., None], goals, self.goals, out=self.goals)
+        _nav_fields_call(self, mask)
+        return self
 
 
 def _answer(out, shape, dev):
@@ -278,6 +294,101 @@ def geodesic(grid, a, b):
     """(N, P) float32: the walking distance from ``a[n, k]`` to ``b[n, k]`` (both (N, P, 2)) - the fields of ``b``, asked at
     ``a``. A convenience for a handful of pairs; keep the :func:`distance_fields` when the goals stay."""
     return distance_fields(grid, b).at(a)
+
+
+class SeededFields(_Fields):
+    """Result of :func:`seeded_fields`: for each env ``G`` fields, field (n, g) holding for every cell of env n's grid the length
+    of the shortest 8-connected path from the cell's centre to the NEAREST seed of that field (0 on the seeds, +inf on blocked
+    cells, on cells no seed reaches and everywhere when the field has no seed). ``values`` is the flat float32 store, in
+    :class:`DistanceFields`' layout; ``marks`` the byte per cell and field the seeds are read from - kept by reference, so
+    :meth:`update` sees them as they stand; ``n_seeds`` (N, G) int32: the seeds each field had when it was last computed;
+    ``passes`` (N, G) int32 or None. :meth:`at`, :meth:`waypoints` and :meth:`paths` are :class:`DistanceFields`', with one
+    change: there is no goal point - a chain ends on the first seed's centre, and a start that stands by a seed is sent to it
+    (``hops`` 0). The rule: include/megastep_hip.h (``MsNavSeedFields``), DESIGN.md 3.17."""
+
+    def __init__(self, grid, marks, n_fields, where, among, values, n_seeds, passes=None):
+        self.grid, self.marks, self.where, self.among = grid, marks, bool(where), among
+        self.values, self.n_seeds, self.passes = values, n_seeds, passes
+        self._n_fields = int(n_fields)
+
+    n_goals = property(lambda self: self._n_fields)
+    n_fields = n_goals
+
+    def _own(self):
+        return ()
+
+    def _waypoints_call(self, p, points, goal, lookahead, out, hops, stream):
+        spec = _lib.MsNavSeedWaypoints(p, points, goal, self.values.data_ptr(), self.n_goals, lookahead, out, hops)
+        return _lib.lib().ms_nav_seed_waypoints(C.byref(self.grid._struct), C.byref(spec), stream)
+
+    def _paths_call(self, p, points, goal, max_points, out, counts, stream):
+        spec = _lib.MsNavSeedPaths(p, points, goal, self.values.data_ptr(), self.n_goals, max_points, out, counts)
+        return _lib.lib().ms_nav_seed_paths(C.byref(self.grid._struct), C.byref(spec), stream)
+
+    def update(self, mask=None):
+        """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place, from :attr:`marks` as they stand now.
+        One launch, no host synchronisation."""
+        grid, g = self.grid, self.n_goals
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, g):
+                raise RuntimeError(f'mask must be an (N, G) = ({grid.n_envs}, {g}) bool tensor')
+            mask = mask.contiguous()
+        dev = _require_gpu(self.marks, self.values, self.n_seeds, grid.free, *(t for t in (self.among, mask, self.passes) if t is not None))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        spec = _lib.MsNavSeedFields(g, self.marks.data_ptr(), int(self.where), ptr(self.among), ptr(mask), self.values.data_ptr(),
+                                    ptr(self.passes), self.n_seeds.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_seed_fields(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return self
+
+
+def _cell_bytes(t, name, length, what):
+    """``t`` as the uint8 tensor a kernel reads a byte per cell from, sharing its memory: a contiguous 1-D uint8 or bool tensor
+    of ``length`` entries."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.bool) or t.ndim != 1 or not t.is_contiguous():
+        raise RuntimeError(f'{name} must be a contiguous 1-dimensional uint8 or bool tensor')
+    if t.shape[0] != length:
+        raise RuntimeError(f'{name} must have {length} entries, {what}; got {t.shape[0]}')
+    return t.view(torch.uint8)
+
+
+def seeded_fields(grid, marks, n_fields, where=True, among=None, mask=None, out=None, passes=False):
+    """Shortest-path distance fields on the :func:`nav_grid` whose sources are a SET of cells: for every env ``n_fields`` fields,
+    each the walking distance from every free cell to the nearest seed of that field along :func:`distance_fields`' graph.
+    ``marks``: a uint8 or bool tensor of ``n_fields*grid.n_cells`` entries, a byte per cell and field in the layout of
+    :attr:`SeenMaps.values` (field (n, g) at ``G*grid.starts[n] + g*nx*ny``) - kept by reference, not copied, so a live seen map
+    can be the source. A cell is a seed of its field when it is free, its mark's bit 0 equals ``where``, and - with ``among``,
+    a uint8 or bool tensor of one entry per cell of the grid (``grid.free``'s layout) shared by an env's fields - its ``among``
+    bit is set. Distance to the nearest door cell, to any of K pickups, to the nearest floor not yet seen
+    (:meth:`SeenMaps.frontier_fields`).
+
+    One launch, one workgroup per field: :func:`distance_fields`' relaxation from many sources at 0 instead of a goal's anchors;
+    the result does not depend on the order of relaxation and equals a multi-source Dijkstra's with binary32 additions bit for
+    bit (include/megastep_hip.h, ``MsNavSeedFields``).
+
+    ``mask`` (N, G) bool: compute only the marked fields (the others keep what ``out`` held; +inf without ``out``); ``out``: the
+    :class:`SeededFields` of an earlier call with the same grid, marks and arguments to write into; ``passes=True`` also records
+    the relaxation passes each field took. No host synchronisation: the call can be captured in a HIP graph."""
+    if not isinstance(n_fields, int) or n_fields < 1:
+        raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
+    marks = _cell_bytes(marks, 'marks', max(n_fields*grid.n_cells, 1), f'a byte per cell and field (n_fields*n_cells = {n_fields}*{grid.n_cells})')
+    if among is not None:
+        among = _cell_bytes(among, 'among', grid.free.shape[0], 'one per cell of the grid')
+    where = bool(where)
+    if out is not None:
+        if not isinstance(out, SeededFields) or out.grid is not grid or out.n_goals != n_fields or out.where != where or \
+                out.marks.data_ptr() != marks.data_ptr() or (out.among is None) != (among is None) or \
+                (among is not None and out.among.data_ptr() != among.data_ptr()):
+            raise RuntimeError('`out` must come from a seeded_fields call with the same grid, marks, n_fields, where and among')
+        return out.update(mask)
+    dev = _require_gpu(marks, grid.free, *(t for t in (among,) if t is not None))
+    values = torch.empty(max(n_fields*grid.n_cells, 1), dtype=torch.float32, device=dev)
+    if mask is not None:
+        values.fill_(float('inf'))                                      # (a field never computed is a field nothing reaches)
+    shape = (grid.n_envs, n_fields)
+    fields = SeededFields(grid, marks, n_fields, where, among, values, torch.zeros(shape, dtype=torch.int32, device=dev),
+                          torch.zeros(shape, dtype=torch.int32, device=dev) if passes else None)
+    return fields.update(mask)
 
 
 #: the most cells an env may have for :func:`seen_maps`: the kernel keeps a call's marks as one bit per cell in LDS (128 KiB)
@@ -368,6 +479,15 @@ class SeenMaps:
         if distances is None:
             raise RuntimeError('the frame has no distances: render with fields that include them')
         return self.mark(agents.positions, dirs, distances.reshape(n, a, r), slot=slot, max_range=max_range, reset=reset, out=out)
+
+
+    def frontier_fields(self, mask=None, out=None, passes=False):
+        """The walking distance from every cell to the nearest countable cell each map has NOT seen, as a :class:`SeededFields`
+        of one field per map: ``seeded_fields(grid, self.values, self.n_maps, where=False, among=self.countable)``. The fields
+        read the maps by reference: :meth:`SeededFields.update` follows the marks. With a countable mask of cells that can be
+        walked to (:class:`~megastep_amd.demo.envs.floorcoverage.FloorCoverage`'s) every seed can be reached; a field without
+        a seed - nothing is left to see - is +inf throughout. ``mask``, ``out``, ``passes``: as :func:`seeded_fields`."""
+        return seeded_fields(self.grid, self.values, self.n_maps, where=False, among=self.countable, mask=mask, out=out, passes=passes)
 
 
 def seen_maps(grid, n_maps, countable=None):

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen]
+                                  [--only fields|query|torch|envs|expert|seen|frontier]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -23,6 +23,11 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       rule on the same inputs (a padded (N, R, samples) index tensor, then a scatter and a second pass for the count), on the
       first `--torch-envs` envs and scaled, its maps and counts compared with the kernel's; FloorCoverage(envs).step eager
       and replayed as a HIP graph.
+  (f) the frontier fields, at Explorer's shape: SeenMaps.frontier_fields (ms_nav_seed_fields) for `--envs` maps right after one
+      marked frame, and again once the maps hold 80 % of the countable floor (every cell but a random fifth marked by hand),
+      with the passes of the slowest field, next to cuda.distance_fields of one goal an env on the same grid; one seeded
+      waypoints call of one agent an env; FloorCoverage(envs): expert() + step() eager and replayed as a HIP graph, next to
+      step() alone under random actions.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -239,7 +244,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
@@ -364,6 +369,58 @@ def main():
         eager, graphed = env_rates(env, args.envs, 60, 10)
         out['FloorCoverage'] = dict(eager_seconds=eager, graph_seconds=graphed)
         print(f'(s) FloorCoverage({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+        del env
+        torch.cuda.empty_cache()
+
+    if want('frontier'):
+        from megastep_amd.demo.envs.floorcoverage import reachable
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        maps = cuda.seen_maps(grid, 1, reachable(grid, table[:, 0, 0]))
+        maps.mark_render(c.agents, cuda.render(sc, c.agents, fields=('distances',)))
+        frontier = maps.frontier_fields(passes=True)
+        stats = lambda f: dict(passes_most=int(f.passes.max()), passes_median=int(f.passes.median()),
+                               seeds_mean=float(f.n_seeds.float().mean()), seen_share=float(maps.fraction().mean()))
+        med, lo, hi = timed(lambda: frontier.update(), args.repeats, args.warmup)
+        out['frontier_first_frame'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, **stats(frontier))
+        print(f"(f) frontier_fields, {args.envs} maps after one frame: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; {out['frontier_first_frame']}")
+        way = torch.empty((args.envs, 1, 2), device='cuda')
+        med, lo, hi = timed(lambda: frontier.waypoints(c.agents.positions, out=way), 5*args.repeats, args.warmup)
+        chosen = frontier.waypoints(c.agents.positions, hops=True)[1]
+        out['frontier_waypoints'] = dict(seconds=med, min=lo, max=hi, points=args.envs, lookahead=16, with_a_path=float((chosen >= 0).float().mean()),
+                                         mean_index=float(chosen[chosen >= 0].float().mean()))
+        print(f"(f) seeded waypoints, {args.envs} x 1 points: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]; mean index {out['frontier_waypoints']['mean_index']:.2f}")
+        goals = table[:, :, 1].contiguous()
+        single = cuda.distance_fields(grid, goals, passes=True)
+        med, lo, hi = timed(lambda: single.update(), args.repeats, args.warmup)
+        out['frontier_single_goal'] = dict(seconds=med, min=lo, max=hi, goals=args.envs, passes_most=int(single.passes.max()),
+                                           passes_median=int(single.passes.median()))
+        print(f"(f) distance_fields on the same grid, {args.envs} goals: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; most passes {int(single.passes.max())}")
+        # 80 % seen: every cell marked but a random fifth
+        maps.values.copy_((torch.rand(maps.values.shape, device='cuda') >= .2).to(torch.uint8))
+        counted = (maps.values[:grid.n_cells] & maps.countable[:grid.n_cells] & 1).long()
+        sums = torch.cat([torch.zeros(1, dtype=torch.int64, device='cuda'), counted.cumsum(0)])
+        starts = torch.as_tensor(grid._host_starts, device='cuda')
+        maps.totals.copy_((sums[starts[1:]] - sums[starts[:-1]]).int()[:, None])
+        med, lo, hi = timed(lambda: frontier.update(), args.repeats, args.warmup)
+        out['frontier_80_percent'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, **stats(frontier))
+        print(f"(f) frontier_fields, {args.envs} maps 80 % seen: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; {out['frontier_80_percent']}")
+        del sc, c, grid, maps, frontier, single
+        torch.cuda.empty_cache()
+        env = FloorCoverage(args.envs, geometries=geoms)
+        eager, graphed = env_rates(env, args.envs, 60, 10)
+        del env
+        torch.cuda.empty_cache()
+        env = ExpertStep(FloorCoverage(args.envs, geometries=geoms))
+        expert_eager, expert_graphed = env_rates(env, args.envs, 60, 10)
+        out['frontier_expert_step'] = dict(step_eager_seconds=eager, step_graph_seconds=graphed, expert_step_eager_seconds=expert_eager,
+                                           expert_step_graph_seconds=expert_graphed)
+        print(f'(f) FloorCoverage({args.envs}): step eager {eager*1e3:.3f} ms, graph {graphed*1e3:.3f} ms; expert + step eager {expert_eager*1e3:.3f} ms, '
+              f'graph {expert_graphed*1e3:.3f} ms')
         del env
         torch.cuda.empty_cache()
 
