@@ -638,6 +638,61 @@ typedef struct MsNavSeen {
 } MsNavSeen;
 int ms_nav_seen(const MsNavGrid* grid, const MsNavSeen* seen, void* hip_stream);
 
+/* Map windows: per-cell stores of the nav grid - free cells, seen maps, distance fields, any marks - cropped, turned and
+ * resampled into images through affine views: the egocentric map of an agent, its heading up, of what IT has seen.  As above
+ * every step is one binary32 operation in the order given, without contraction, divisions correctly rounded;
+ * tests/test_navwindow_host.py restates it in numpy (window_rule) and the kernel - and its host instantiation,
+ * ms_host_nav_windows - are held to EQUALITY with it.  c, geom and starts are MsNavGrid's.
+ *   layers        a layer holds n_fields stores per env, store (n, f) of nx*ny cells from n_fields*starts[n] + f*nx*ny on,
+ *                 row-major with row 0 at the lowest y (MsNavFields.fields' and MsNavSeen.maps' layout), as bytes (is_float 0)
+ *                 or binary32 floats (is_float 1).  `field` (N, P) names the store view (n, p) reads; NULL: store 0 when
+ *                 n_fields == 1, else n_fields == P and view p reads store p (anything else is refused).  Field indices are
+ *                 read on the device only; one outside [0, n_fields) is a BAD index, see the pixel.
+ *   views         (N, P, 6): MsOverhead's six floats g0..g5 of view p of env n.
+ *   sample points pixel (row i from the top, column j), k = samples, sub-sample (a, b), a and b in 0 .. k-1:
+ *                 u = (float)j + ((float)b + .5f)/(float)k, w = (float)i + ((float)a + .5f)/(float)k,
+ *                 x = (g0 u + g1 w) + g2, y = (g3 u + g4 w) + g5.  With k = 1 this is MsOverhead's pixel centre.
+ *   the cell      under a sample, as MsNavSeen finds it: fx = floorf(x/c), fy = floorf(y/c); no cell when fx or fy is a NaN
+ *                 or |.| >= 2^30; else j = (int)fx - jx0, i = (int)fy - iy0, no cell when (i, j) is outside the grid.  An env
+ *                 without cells (nx <= 0 or ny <= 0) has no cell anywhere.
+ *   the value     of a sample in one channel: `outside` without a cell; else, if the channel has a gate (a byte layer with a
+ *                 `field` of its own) and the gate's byte at the cell is 0: `hidden`; else for a byte source 1.f when
+ *                 (byte != 0) == where and 0.f otherwise, for a float source holding D at the cell v = D*scale, then
+ *                 v < 1 ? (v > 0 ? v : 0) : 1 - a NaN and +inf give 1.
+ *   the pixel     acc = 0.f, then acc += value over a (outer) and b (inner), then acc/(float)(k*k).  A channel whose source
+ *                 index is BAD for a view has `outside` in every pixel of that image; else one whose gate index is BAD has
+ *                 `hidden` in every pixel - neither through the sum.
+ *   out           (N, P, C, H, W) binary32, planar.
+ * One launch for every image and channel; the channels travel in the kernel's arguments by value, so `channels` is a HOST
+ * array of n_channels (1..8) entries.  samples in 1..4, height and width in 1..1024, a gate must be bytes (a gate with values
+ * NULL is no gate).  Every output element has one writer and a fixed serial sum: nothing depends on the order of execution.
+ * Nothing is allocated, nothing is copied to the device, nothing waits: the call can be captured in a HIP graph.  Every
+ * argument is checked in full before the launch (MS_EINVAL). */
+typedef struct MsNavLayer {
+    const void*          values;       /* n_fields*starts[N] bytes (is_float 0) or floats (is_float 1)                  */
+    int                  is_float;     /* 0 or 1                                                                       */
+    int                  n_fields;     /* G >= 1: stores per env                                                       */
+    const int*           field;        /* (N, P) the store each view reads; NULL: n_fields == 1 or n_fields == P       */
+} MsNavLayer;
+typedef struct MsNavChannel {
+    MsNavLayer           source;
+    MsNavLayer           gate;         /* values NULL: none (the other members are then not looked at); else bytes     */
+    int                  where;        /* 0 or 1: the byte that gives 1.f (byte sources)                               */
+    float                scale;        /* float sources: v = D*scale                                                   */
+    float                outside;      /* a sample without a cell                                                      */
+    float                hidden;       /* a sample whose gate byte is 0                                                */
+} MsNavChannel;
+typedef struct MsNavWindows {
+    int                  n_views;      /* P >= 1: views per env                                                        */
+    int                  height, width;/* H, W: 1..1024                                                                */
+    int                  samples;      /* k: 1..4, k*k sub-samples a pixel                                             */
+    const float*         views;        /* (N, P, 6)                                                                    */
+    int                  n_channels;   /* C: 1..8                                                                      */
+    const MsNavChannel*  channels;     /* (C,) HOST memory                                                             */
+    float*               out;          /* (N, P, C, H, W)                                                              */
+} MsNavWindows;
+int ms_nav_windows(const MsNavGrid* grid, const MsNavWindows* windows, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

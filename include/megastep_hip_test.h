@@ -94,6 +94,11 @@ int ms_host_nav_seed_path(const int* geom, float cell, const unsigned char* free
 int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable, int n_maps, int n_viewers, int n_rays,
                      const float* origins, const float* dirs, const float* distances, const int* slot, float max_range,
                      const unsigned char* reset, unsigned char* maps, int* gained, int* total);
+/* Host instantiation of the map windows' rule (kernels/navwindow.h: the sample point, the cell, the channel value and the
+ * pixel's sum - the very functions every lane of nav_window_kernel evaluates) for one whole call of ms_nav_windows on HOST
+ * arrays: every pointer of `grid` (geom, starts; free_cells is checked, not read) and of `windows` (views, the layers' values and
+ * fields, out) is host memory.  Returns what ms_nav_windows would: MS_OK, or MS_EINVAL for arguments it would refuse. */
+int ms_host_nav_windows(const MsNavGrid* grid, const MsNavWindows* windows);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

@@ -137,6 +137,20 @@ class MsNavSeen(C.Structure):
                 ('maps', C.c_void_p), ('gained', C.c_void_p), ('total', C.c_void_p), ('max_cells', C.c_int)]
 
 
+class MsNavLayer(C.Structure):
+    _fields_ = [('values', C.c_void_p), ('is_float', C.c_int), ('n_fields', C.c_int), ('field', C.c_void_p)]
+
+
+class MsNavChannel(C.Structure):
+    _fields_ = [('source', MsNavLayer), ('gate', MsNavLayer), ('where', C.c_int), ('scale', C.c_float), ('outside', C.c_float),
+                ('hidden', C.c_float)]
+
+
+class MsNavWindows(C.Structure):
+    _fields_ = [('n_views', C.c_int), ('height', C.c_int), ('width', C.c_int), ('samples', C.c_int), ('views', C.c_void_p),
+                ('n_channels', C.c_int), ('channels', C.POINTER(MsNavChannel)), ('out', C.c_void_p)]
+
+
 _int, _flt, _ptr, _p = C.c_int, C.c_float, C.c_void_p, C.POINTER
 
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare, as
@@ -165,6 +179,7 @@ PROTOTYPES = {
     'ms_nav_waypoints': (_int, [_p(MsNavGrid), _p(MsNavWaypoints), _ptr]),
     'ms_nav_paths': (_int, [_p(MsNavGrid), _p(MsNavPaths), _ptr]),
     'ms_nav_seen': (_int, [_p(MsNavGrid), _p(MsNavSeen), _ptr]),
+    'ms_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows), _ptr]),
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
     'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
     'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
@@ -192,6 +207,7 @@ PROTOTYPES = {
     'ms_host_nav_seed_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_seed_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
+    'ms_host_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows)]),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),

@@ -2,7 +2,7 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h, navseen.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h, navseen.h, navwindow.h.
 //
 // Twenty-two kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
@@ -56,7 +56,10 @@
 //   nav_seen_kernel     seen maps: one workgroup per map marks the grid cells under the samples of its viewers' depth rays in
 //                   an LDS bitmask, merges it into the map and counts the countable cells seen for the first time.
 //                                                            (no counterpart)
-//   explorer_kernel     the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
+//   nav_window_kernel   map windows: per-cell stores (free cells, seen maps, fields) cropped and turned into images through
+//                   affine views, every image and channel in one launch, a lane a pixel.
+//                                                            (no counterpart)
+//   explorer_kernel    the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
 //   deathmatch_kernel   the Deathmatch env's game logic between frames (revive, crosshairs, hits and wounds, health, damage,
 //                   reward, next step's dead) as one element-wise launch behind ms_render.
@@ -157,6 +160,7 @@ struct Probe {
 #include "kernels/navfield.h"
 #include "kernels/navpath.h"
 #include "kernels/navseen.h"
+#include "kernels/navwindow.h"
 #include "kernels/envlogic.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1038,6 +1042,61 @@ int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable
     seen_serial(SeenGrid{geom[0], geom[1], geom[2], geom[3], cell}, countable, n_maps, n_viewers, n_rays, origins, dirs, distances, slot,
                 max_range, reset, maps, gained, total);
     return 0;
+}
+
+// Map windows (navwindow.h): the same discipline; the channels go into the kernel's arguments by value.
+static bool nav_layer_ok(const MsNavLayer& l, const int n_views) {
+    return l.values && (l.is_float == 0 || l.is_float == 1) && l.n_fields >= 1 && (l.field || l.n_fields == 1 || l.n_fields == n_views) &&
+           ((uintptr_t)l.field % 4 == 0) && (!l.is_float || (uintptr_t)l.values % 4 == 0);
+}
+static bool nav_windows_ok(const MsNavWindows* w) {
+    if (!w || w->n_views < 1 || w->height < 1 || w->height > WIN_MAX_SIDE || w->width < 1 || w->width > WIN_MAX_SIDE ||
+        w->samples < 1 || w->samples > WIN_MAX_SAMPLES || w->n_channels < 1 || w->n_channels > WIN_MAX_CHANNELS || !w->views ||
+        !w->channels || !w->out || ((uintptr_t)w->views % 4) || ((uintptr_t)w->out % 4)) return false;
+    for (int c = 0; c < w->n_channels; c++) {
+        const MsNavChannel& ch = w->channels[c];
+        if (!nav_layer_ok(ch.source, w->n_views) || (ch.where != 0 && ch.where != 1)) return false;
+        if (ch.gate.values && (!nav_layer_ok(ch.gate, w->n_views) || ch.gate.is_float)) return false;
+    }
+    return true;
+}
+static NavWindowArgs nav_window_args(const MsNavWindows* w) {
+    NavWindowArgs q{w->views, w->out, w->n_views, w->height, w->width, w->n_channels, {}};
+    for (int c = 0; c < w->n_channels; c++) {
+        const MsNavChannel& ch = w->channels[c];
+        const bool gated = ch.gate.values != nullptr;
+        q.ch[c] = WinChannel{ch.source.values, ch.source.field, static_cast<const unsigned char*>(ch.gate.values), gated ? ch.gate.field : nullptr,
+                             ch.source.n_fields, gated ? ch.gate.n_fields : 1, ch.source.is_float, ch.where, ch.scale, ch.outside, ch.hidden};
+    }
+    return q;
+}
+
+int ms_nav_windows(const MsNavGrid* grid, const MsNavWindows* w, void* stream) {
+    if (!nav_grid_ok(grid) || !nav_windows_ok(w)) return MS_EINVAL;
+    const long long images = (long long)grid->n_envs*w->n_views;
+    if (images > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    const NavWindowArgs q = nav_window_args(w);
+    const dim3 blocks((unsigned)images, (unsigned)((w->height*w->width + WG - 1)/WG));      // (y: at most 4096)
+    const hipStream_t s = (hipStream_t)stream;
+    switch (w->samples) {
+        case 1: hipLaunchKernelGGL(nav_window_kernel<1>, blocks, dim3(WG), 0, s, nav_args(grid), q); break;
+        case 2: hipLaunchKernelGGL(nav_window_kernel<2>, blocks, dim3(WG), 0, s, nav_args(grid), q); break;
+        case 3: hipLaunchKernelGGL(nav_window_kernel<3>, blocks, dim3(WG), 0, s, nav_args(grid), q); break;
+        default: hipLaunchKernelGGL(nav_window_kernel<4>, blocks, dim3(WG), 0, s, nav_args(grid), q); break;
+    }
+    return launch_status();
+}
+
+int ms_host_nav_windows(const MsNavGrid* grid, const MsNavWindows* w) {
+    if (!nav_grid_ok(grid) || !nav_windows_ok(w)) return MS_EINVAL;
+    const NavWindowArgs q = nav_window_args(w);
+    switch (w->samples) {
+        case 1: win_serial<1>(nav_args(grid), q); break;
+        case 2: win_serial<2>(nav_args(grid), q); break;
+        case 3: win_serial<3>(nav_args(grid), q); break;
+        default: win_serial<4>(nav_args(grid), q); break;
+    }
+    return MS_OK;
 }
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {

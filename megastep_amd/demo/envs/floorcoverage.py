@@ -20,10 +20,12 @@ def reachable(grid, points):
 class FloorCoverage:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, max_range=10., complete=.9, max_lifespan=512,
-                 n_spawns=100, shared=False, **kwargs):
+                 n_spawns=100, shared=False, local_map=None, **kwargs):
         """``cell``: the nav grid's cell size; ``max_range``: how far a ray is followed, metres; ``complete``: the share of the
         floor that ends an episode; ``max_lifespan``: episodes end after a random number of steps up to this
-        (:class:`~megastep_amd.modules.RandomLifespans`); ``shared``: see :class:`~megastep_amd.modules.Coverage`.
+        (:class:`~megastep_amd.modules.RandomLifespans`); ``shared``: see :class:`~megastep_amd.modules.Coverage`; ``local_map``:
+        ``True``, or a dict of :class:`~megastep_amd.modules.LocalMap`'s keyword arguments, adds ``obs['map']`` and ``obs_space['map']`` (read them by key: ``.map`` is the tree's method) - the egocentric
+        window of what the agent has seen so far, taken after the frame's marks; without it the env makes no such launch.
 
         The floor that counts is what can be walked to from the env's first spawn point: the free margin the grid keeps round
         the building, and rooms without a door, are never in the denominator."""
@@ -44,6 +46,10 @@ class FloorCoverage:
         self._coverage = modules.Coverage(c, self.grid, max_range=max_range, shared=shared, countable=countable)
         self.action_space = self._mover.space
         self.obs_space = dotdict.dotdict(rgb=self._rgb.space, d=self._depth.space, coverage=self._coverage.space)
+        self._local = None
+        if local_map:
+            self._local = modules.LocalMap(c, self._coverage, **(local_map if isinstance(local_map, dict) else {}))
+            self.obs_space['map'] = self._local.space     # (by key: `.map` is the tree's method)
 
         self._over = c.agent_full(True)                 # who starts over at the next step
         self._episodes = torch.zeros((c.n_envs, c.n_agents), dtype=torch.long, device=c.device)
@@ -69,6 +75,8 @@ class FloorCoverage:
         ended = self._coverage.fraction() >= self.complete
         self._over.copy_(self._lifespans(ended))
         obs = arrdict.arrdict(rgb=self._rgb(frame), d=self._depth(frame), coverage=self._coverage.observation())
+        if self._local is not None:
+            obs['map'] = self._local()
         return arrdict.arrdict(obs=obs, reset=reset.any(-1), reward=reward)
 
     @torch.no_grad()
@@ -100,5 +108,8 @@ class FloorCoverage:
         return self._follower()
 
     def state(self, e=0):
-        return arrdict.arrdict(core=self.core.state(e), rgb=self._rgb.state(e), d=self._depth.state(e), seen=self._coverage.state(e),
-                               fraction=self._coverage.fraction()[e].clone(), lifespan=self._lifespans.state(e))
+        state = arrdict.arrdict(core=self.core.state(e), rgb=self._rgb.state(e), d=self._depth.state(e), seen=self._coverage.state(e),
+                                fraction=self._coverage.fraction()[e].clone(), lifespan=self._lifespans.state(e))
+        if self._local is not None:
+            state['map'] = self._local.state(e)
+        return state

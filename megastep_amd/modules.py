@@ -531,6 +531,50 @@ class Coverage:
         return torch.stack([self.maps.image(e, s) for s in range(self.maps.n_maps)]).clone()
 
 
+class LocalMap:
+
+    #: the channels that have a name
+    NAMED = ('floor', 'wall', 'seen')
+
+    def __init__(self, core, coverage, size=32, radius=4., channels=('floor', 'wall'), samples=1):
+        """Egocentric maps of what each agent has SEEN, (n_env, n_agent, C, size, size): the agent at the centre of its own
+        ``2*radius`` metre square, its heading up (:func:`cuda.agent_views`, :func:`cuda.local_maps`; no counterpart in the
+        reference). ``coverage`` is the :class:`Coverage` whose seen maps gate the picture - with ``coverage.shared`` every
+        agent of an env reads the env's one map. Unlike :class:`Overhead`, which draws the scenery's walls whether anybody has
+        looked at them or not, nothing shows here before a depth ray has passed over it. ``channels`` names them: ``'floor'``
+        - 1 on the free cells of the nav grid the map has seen; ``'wall'`` - 1 on the blocked cells it has seen (the cells
+        rays ended on stay marked); ``'seen'`` - the map itself; or any :func:`cuda.map_channel`, a frontier or a goal field
+        say. 0 where nothing is seen and beyond the grid. ``samples``: sub-samples a side per pixel, for pixels larger than a
+        cell. The tensor a call returns is written again by the next call (the module keeps its buffer): clone it to keep it."""
+        self.core, self.coverage = core, coverage
+        self.size, self.radius, self.samples = int(size), float(radius), int(samples)
+        grid, maps = coverage.grid, coverage.maps
+        seen = cuda.cell_layer(maps, field=coverage._slot)
+        made = {'floor': lambda: cuda.map_channel(grid, where=True, gate=seen), 'wall': lambda: cuda.map_channel(grid, where=False, gate=seen),
+                'seen': lambda: cuda.map_channel(seen)}
+        self.channels = []
+        for ch in channels:
+            if isinstance(ch, str):
+                if ch not in made:
+                    raise RuntimeError(f'a named channel is one of {self.NAMED}; got {ch!r}')
+                ch = made[ch]()
+            self.channels.append(ch)
+        self.space = spaces.MultiImage(core.n_agents, len(self.channels), self.size, self.size)
+        self._out = None
+
+    def views(self):
+        """(n_env, n_agent, 6): the views of the agents' maps as they stand now."""
+        return cuda.agent_views(self.core.agents, self.size, self.radius)
+
+    def __call__(self):
+        """The windows of the maps as they stand: call after the frame's marks."""
+        self._out = cuda.local_maps(self.coverage.grid, self.views(), self.size, self.channels, samples=self.samples, out=self._out)
+        return self._out
+
+    def state(self, e=0):
+        return self._out[e].clone()
+
+
 class Frontiers:
 
     def __init__(self, core, coverage, refresh=8):

@@ -1,12 +1,12 @@
 """Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
-floorplans, and the seen maps of the depth rays
-(kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``). No counterpart in the reference;
+floorplans, the seen maps of the depth rays, and windows of all of them as images round the agents
+(kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``). No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
 from . import _lib
 from ._lib import _on, _stream
-from ._call import _cfg, _check, _require_gpu
+from ._call import _cfg, _check, _hw, _require_gpu
 
 
 def _static_boxes(scenery):
@@ -513,3 +513,145 @@ def seen_maps(grid, n_maps, countable=None):
     sums = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (countable[:grid.n_cells] & 1).long().cumsum(0)])
     n_countable = (sums[starts[1:]] - sums[starts[:-1]]).int()
     return SeenMaps(grid, n_maps, values, countable, torch.zeros((n, n_maps), dtype=torch.int32, device=dev), n_countable)
+
+
+#: the most channels, samples a side and pixels a side of :func:`local_maps`
+WINDOW_MAX_CHANNELS, WINDOW_MAX_SAMPLES, WINDOW_MAX_SIDE = 8, 4, 1024
+
+
+class CellLayer:
+    """Result of :func:`cell_layer`: a per-cell store :func:`local_maps` reads. ``values``: the flat uint8 or float32 store of
+    ``n_fields`` stores per env; ``field``: the (N, P) int32 tensor naming the store each view reads, or None."""
+
+    def __init__(self, values, n_fields, field):
+        self.values, self.n_fields, self.field = values, int(n_fields), field
+
+    is_float = property(lambda self: self.values.dtype == torch.float32)
+
+    def _tensors(self):
+        return (self.values,) if self.field is None else (self.values, self.field)
+
+
+def cell_layer(values, n_fields=1, field=None):
+    """A per-cell store as a layer for :func:`map_channel`: ``values`` is a contiguous 1-dimensional uint8, bool or float32 tensor
+    of (at least) ``n_fields*grid.n_cells`` entries in the layout the fields and maps use - ``n_fields`` stores per env, store (n, f) at
+    ``n_fields*grid.starts[n] + f*nx*ny``, row-major with row 0 at the lowest y - kept by reference, so a live seen map or field
+    can be the source. ``field``: an (N, P) integer tensor naming the store each view reads; without it store 0 is read when
+    ``n_fields`` is 1 and view p reads store p when ``n_fields`` is the number of views. A :class:`NavGrid` (its ``free``), a
+    :class:`SeenMaps`, a :class:`DistanceFields` and a :class:`SeededFields` are layers as they are, with their own number of
+    stores; ``cell_layer(maps, field=slot)`` gives one of them a ``field``."""
+    if isinstance(values, CellLayer):
+        values, n_fields = values.values, values.n_fields
+    elif isinstance(values, NavGrid):
+        values, n_fields = values.free, 1
+    elif isinstance(values, SeenMaps):
+        values, n_fields = values.values, values.n_maps
+    elif isinstance(values, _Fields):
+        values, n_fields = values.values, values.n_goals
+    if not isinstance(n_fields, int) or n_fields < 1:
+        raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
+    if not isinstance(values, torch.Tensor) or values.dtype not in (torch.uint8, torch.bool, torch.float32) or values.ndim != 1 or \
+            not values.is_contiguous():
+        raise RuntimeError('a layer must be a contiguous 1-dimensional uint8, bool or float32 tensor')
+    if values.dtype == torch.bool:
+        values = values.view(torch.uint8)
+    if field is not None:
+        if not isinstance(field, torch.Tensor) or field.dtype.is_floating_point or field.dtype == torch.bool or field.ndim != 2:
+            raise RuntimeError('field must be an (N, P) integer tensor')
+        if field.dtype != torch.int32 or not field.is_contiguous():
+            field = field.to(torch.int32).contiguous()
+    return CellLayer(values, n_fields, field)
+
+
+def _layer(x):
+    return x if isinstance(x, CellLayer) else cell_layer(x)
+
+
+class MapChannel:
+    """Result of :func:`map_channel`: one channel of :func:`local_maps`."""
+
+    def __init__(self, source, where, scale, gate, outside, hidden):
+        self.source, self.where, self.scale, self.gate, self.outside, self.hidden = source, where, scale, gate, outside, hidden
+
+
+def map_channel(source, where=True, scale=None, gate=None, outside=0., hidden=0.):
+    """One channel of :func:`local_maps`. ``source``: a layer (:func:`cell_layer`, or a :class:`NavGrid`, :class:`SeenMaps`,
+    :class:`DistanceFields` or :class:`SeededFields` as it is). A byte source gives 1 where ``(byte != 0) == where`` and 0
+    elsewhere; a float source holding D gives ``D*scale`` clamped to [0, 1] (a NaN and +inf: 1), and ``scale`` is required.
+    ``gate``: a byte layer with a ``field`` of its own; where its byte is 0 the channel shows ``hidden`` - ``grid.free`` gated by
+    an agent's seen map is the floor that agent knows. ``outside``: what a sample beyond the env's grid shows."""
+    source = _layer(source)
+    gate = None if gate is None else _layer(gate)
+    if gate is not None and gate.is_float:
+        raise RuntimeError('a gate must be a byte layer (uint8 or bool), not float32')
+    if source.is_float:
+        if scale is None:
+            raise RuntimeError('a float32 source needs a scale: the channel shows D*scale clamped to [0, 1]')
+        scale = float(scale)
+    return MapChannel(source, bool(where), 0. if scale is None else float(scale), gate, float(outside), float(hidden))
+
+
+def _window_layer(layer, name, grid, n, p, spec):
+    """Checks ``layer`` against the grid and the views and fills in the MsNavLayer ``spec``; returns its tensors."""
+    want = layer.n_fields*grid.n_cells
+    if layer.values.shape[0] < want:
+        raise RuntimeError(f"{name} must have at least {want} entries, a value per cell and store (n_fields*n_cells = {layer.n_fields}*{grid.n_cells}); "
+                           f'got {layer.values.shape[0]}')
+    if layer.field is None:
+        if layer.n_fields not in (1, p):
+            raise RuntimeError(f'without field, {name} must hold one store per env or one per view ({p}); it holds {layer.n_fields}')
+    elif layer.field.shape != (n, p):
+        raise RuntimeError(f"{name}'s field must be (N, P) = ({n}, {p}); got {tuple(layer.field.shape)}")
+    spec.values, spec.is_float, spec.n_fields = layer.values.data_ptr(), int(layer.is_float), layer.n_fields
+    spec.field = layer.field.data_ptr() if layer.field is not None else None
+    return layer._tensors()
+
+
+def local_maps(grid, views, size, channels, samples=1, out=None):
+    """Per-cell stores of the :func:`nav_grid` cropped, turned and resampled into images: (N, P, C, H, W) float32, planar
+    (``spaces.MultiImage``'s layout), image (n, p) showing env n through ``views[n, p]`` - the six-number affine maps of
+    :func:`overhead`, so :func:`agent_views` gives every agent the egocentric window round it, its heading up, and
+    :func:`plan_views` the whole plan. ``size``: an int or (H, W), at most 1024 a side. ``channels``: 1 to 8
+    :func:`map_channel`; a bare layer stands for ``map_channel(layer)``. ``samples`` (1..4): a pixel is the mean of
+    ``samples**2`` sub-samples, each the value of the cell under it - for pixels larger than a cell. ``out``: the tensor of an
+    earlier call with the same shapes to write into.
+
+    One launch for every image and channel, a lane a pixel, the cell under a sample found once for all channels; no host
+    synchronisation, nothing allocated besides ``out``: the call can be captured in a HIP graph. The rule is written out in
+    include/megastep_hip.h (``MsNavWindows``) and DESIGN.md 3.18; the kernel computes it bit for bit."""
+    _check(views, 'views', torch.float32, 3)
+    h, w = _hw(size)
+    n, p = views.shape[:2]
+    if n != grid.n_envs or p < 1 or views.shape[2] != 6:
+        raise RuntimeError(f'views must be (N, P, 6) with N = {grid.n_envs} and P >= 1; got {tuple(views.shape)}')
+    if h > WINDOW_MAX_SIDE or w > WINDOW_MAX_SIDE:
+        raise RuntimeError(f'size must be at most {WINDOW_MAX_SIDE} a side; got {size}')
+    if not isinstance(samples, int) or not 1 <= samples <= WINDOW_MAX_SAMPLES:
+        raise RuntimeError(f'samples must be an integer in 1..{WINDOW_MAX_SAMPLES}; got {samples}')
+    channels = [ch if isinstance(ch, MapChannel) else map_channel(ch) for ch in channels]
+    c = len(channels)
+    if not 1 <= c <= WINDOW_MAX_CHANNELS:
+        raise RuntimeError(f'channels must be 1 to {WINDOW_MAX_CHANNELS} map_channel; got {c}')
+    specs = (_lib.MsNavChannel*c)()
+    tensors = [views, grid.free]
+    for k, (ch, spec) in enumerate(zip(channels, specs)):
+        if ch.gate is not None and ch.gate.is_float:
+            raise RuntimeError('a gate must be a byte layer (uint8 or bool), not float32')
+        if ch.source.is_float and ch.scale is None:
+            raise RuntimeError('a float32 source needs a scale')
+        tensors += _window_layer(ch.source, f"channel {k}'s source", grid, n, p, spec.source)
+        if ch.gate is not None:
+            tensors += _window_layer(ch.gate, f"channel {k}'s gate", grid, n, p, spec.gate)
+        spec.where, spec.scale, spec.outside, spec.hidden = int(bool(ch.where)), float(ch.scale or 0.), float(ch.outside), float(ch.hidden)
+    shape = (n, p, c, h, w)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise RuntimeError(f'`out` must be a contiguous (N, P, C, H, W) = {shape} float32 tensor')
+        tensors.append(out)
+    dev = _require_gpu(*tensors)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    spec = _lib.MsNavWindows(p, h, w, samples, views.data_ptr(), c, specs, out.data_ptr())
+    with _on(dev):
+        _lib.check(_lib.lib().ms_nav_windows(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+    return out

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -28,6 +28,13 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       with the passes of the slowest field, next to cuda.distance_fields of one goal an env on the same grid; one seeded
       waypoints call of one agent an env; FloorCoverage(envs): expert() + step() eager and replayed as a HIP graph, next to
       step() alone under random actions.
+  (w) the map windows, at `--envs` envs x 1 agent, on seen maps that hold one rendered frame: one cuda.local_maps
+      (ms_nav_windows) of floor and wall at 32 x 32 with samples=1 through cuda.agent_views (radius 4 m), and one of floor, wall and
+      the frontier distance at 64 x 64 with samples=2 - each timed as 20 calls back to back between two events, with the output's
+      bytes (N A C H W 4: essentially the kernel's algorithmic traffic) over that time next to the 6.3 TB/s the HBM sustains
+      (MI355X_MICROARCH.md; 8 TB/s spec) - next to the torch formulation of the same rule on the same inputs (index arithmetic
+      and gathers; the first `--torch-envs` envs, scaled; outputs compared as bits) and to modules.Overhead at the same size;
+      FloorCoverage(envs, local_map=True).step eager and replayed as a HIP graph, next to FloorCoverage(envs).step.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -185,6 +192,45 @@ def torch_seen(grid, countable, origins, dirs, distances, max_range, envs):
     return run
 
 
+def torch_windows(grid, views, size, samples, channels, envs):
+    """The map windows' rule by tensor ops for the first `envs` envs, one view and one store a layer each: `channels` is a list
+    of (source values, is_float, where, scale, gate values or None); returns run() -> (envs, 1, C, H, W). outside = hidden = 0."""
+    dev = views.device
+    H, W = size
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+    c, k = f32(grid.cell), f32(samples)
+    geom = torch.as_tensor(grid._host_geom[:envs].astype(np.int64), device=dev)[:, :, None, None]
+    starts = torch.as_tensor(grid._host_starts[:envs], device=dev)[:, None, None]
+    g = views[:envs, 0, :, None, None]
+    i, j = torch.arange(H, device=dev).float()[None, :, None], torch.arange(W, device=dev).float()[None, None, :]
+    zero, one = f32(0.), f32(1.)
+
+    def run():
+        out = torch.zeros((envs, 1, len(channels), H, W), dtype=torch.float32, device=dev)
+        for a in range(samples):
+            for b in range(samples):
+                u, w = j + (f32(b) + .5)/k, i + (f32(a) + .5)/k
+                x, y = (g[:, 0]*u + g[:, 1]*w) + g[:, 2], (g[:, 3]*u + g[:, 4]*w) + g[:, 5]
+                fx, fy = torch.floor(x/c), torch.floor(y/c)
+                ok = (fx.abs() < 2.**30) & (fy.abs() < 2.**30)
+                jj = torch.where(ok, fx, torch.zeros_like(fx)).long() - geom[:, 0]
+                ii = torch.where(ok, fy, torch.zeros_like(fy)).long() - geom[:, 1]
+                ok = ok & (ii >= 0) & (ii < geom[:, 3]) & (jj >= 0) & (jj < geom[:, 2])
+                cell = torch.where(ok, starts + ii*geom[:, 2] + jj, torch.zeros_like(ii))
+                for n, (values, is_float, where, scale, gate) in enumerate(channels):
+                    src = values[cell]
+                    if is_float:
+                        v = src*f32(scale)
+                        value = torch.where(v < 1, torch.where(v > 0, v, zero), one)
+                    else:
+                        value = torch.where((src != 0) == where, one, zero)
+                    if gate is not None:
+                        value = torch.where(gate[cell] == 0, zero, value)
+                    out[:, 0, n] = out[:, 0, n] + torch.where(ok, value, zero)
+        return out/f32(samples*samples)
+    return run
+
+
 class ExpertStep:
     """An env whose step is the expert's own: expert() + step(), the decision handed in ignored."""
 
@@ -244,7 +290,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
@@ -423,6 +469,56 @@ def main():
               f'graph {expert_graphed*1e3:.3f} ms')
         del env
         torch.cuda.empty_cache()
+
+    if want('window'):
+        from megastep_amd.demo.envs.floorcoverage import reachable
+        HBM = 6.3e12                                                     # bytes/s the HBM sustains (MI355X_MICROARCH.md; 8e12 spec)
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        maps = cuda.seen_maps(grid, 1, reachable(grid, table[:, 0, 0]))
+        maps.mark_render(c.agents, cuda.render(sc, c.agents, fields=('distances',)))
+        frontier = maps.frontier_fields()
+        floor, wall = cuda.map_channel(grid, gate=maps), cuda.map_channel(grid, where=False, gate=maps)
+        far = cuda.map_channel(frontier, scale=.1)
+        k, batch = min(args.torch_envs, args.envs), 20
+        for name, size, samples, channels, plain in (
+                ('window_32', 32, 1, [floor, wall], [(grid.free, False, True, 0., maps.values), (grid.free, False, False, 0., maps.values)]),
+                ('window_64', 64, 2, [floor, wall, far], [(grid.free, False, True, 0., maps.values), (grid.free, False, False, 0., maps.values),
+                                                          (frontier.values, True, True, .1, None)])):
+            views = cuda.agent_views(c.agents, size, 4.)
+            buffer = cuda.local_maps(grid, views, size, channels, samples=samples)
+
+            def calls():
+                for _ in range(batch):
+                    cuda.local_maps(grid, views, size, channels, samples=samples, out=buffer)
+            med, lo, hi = (t/batch for t in timed(calls, args.repeats, args.warmup))
+            nbytes = buffer.numel()*4
+            run = torch_windows(grid, views, (size, size), samples, plain, k)
+            same = bool(torch.equal(run().view(torch.int32), buffer[:k].view(torch.int32)))
+            tmed = timed(lambda: run(), max(args.repeats//3, 2), 1)[0]
+            over = modules.Overhead(c, size=size, radius=4.)
+            omed = timed(lambda: over(), args.repeats, args.warmup)[0]
+            out[name] = dict(seconds=med, min=lo, max=hi, size=size, samples=samples, channels=len(channels), output_bytes=nbytes,
+                             bytes_per_second=nbytes/med, share_of_hbm_sustained=nbytes/med/HBM, torch_envs=k, torch_seconds=tmed,
+                             torch_scaled_seconds=tmed*args.envs/k, torch_equal_bits=same, overhead_seconds=omed)
+            print(f'(w) local_maps, {args.envs} x 1 x {len(channels)} x {size} x {size}, samples={samples}: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}] a call '
+                  f'({batch} back to back); {nbytes/1e6:.1f} MB out -> {nbytes/med/1e12:.2f} TB/s, {100*nbytes/med/HBM:.0f} % of 6.3 TB/s; torch, {k} envs: '
+                  f'{tmed*1e3:.2f} ms -> {tmed*args.envs/k*1e3:.1f} ms for {args.envs}, equal bits: {same}; modules.Overhead at {size}: {omed*1e6:.1f} us')
+            del over, buffer
+        del sc, c, grid, maps, frontier
+        torch.cuda.empty_cache()
+        for name, make in (('FloorCoverage_local_map', lambda: FloorCoverage(args.envs, geometries=geoms, local_map=True)),
+                           ('FloorCoverage_plain', lambda: FloorCoverage(args.envs, geometries=geoms))):
+            env = make()
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[name] = dict(eager_seconds=eager, graph_seconds=graphed)
+            print(f'(w) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
 
     if args.json:
         with open(args.json, 'w') as f:
