@@ -21,12 +21,10 @@
  *             columns: which wall each ray lands on, each wall's colour
  *             direction through texture, shading and gamma);
  *             tests/golden/make_docs_images.py, tests/test_oracle.py.
- *   render (distances, locations, dots, brightness) / bake : PARITY UNPINNED
- *             by the reference (it has no test, fixture or golden vector for
- *             them - the image's textures and light were drawn from an unseeded
- *             RNG - and its CUDA extension can be neither built nor run in the
- *             authoring container).  Pinned only by analytic closed forms
- *             (tests/test_oracle.py).
+ *   everything : the reference's own kernels, compiled for the host by
+ *             oracle/reference.py, give the same bits as this file - bake,
+ *             progress, agents, indices, locations, dots, distances, screen -
+ *             on every world of tests/test_reference_pin.py.
  *
  * Deliberate, documented definitions where the CUDA source leaves the bits to
  * the toolchain (all within the 1e-5 tolerance of BASELINE.json):
@@ -440,5 +438,8 @@ float oracle_collision_cc(float p0x, float p0y, float v0x, float v0y, float p1x,
 float oracle_normalize_degrees(float a) { return normalize_degrees(a); }
 void oracle_filter(float x, int w, int* l, int* r, float* lw, float* rw) {
     const Filt f = filter(x, w); *l = f.l; *r = f.r; *lw = f.lw; *rw = f.rw;
+}
+void oracle_sincospi_many(const float* x, float* s, float* c, long n) {
+    for (long i = 0; i < n; i++) oracle_sincospi(x[i], s + i, c + i);
 }
 int oracle_abi_version(void) { return 1; }

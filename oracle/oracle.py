@@ -49,10 +49,13 @@ class OrConfig(C.Structure):
 
 
 def build(force=False):
-    """Compiles the oracle with gcc (oracle/Makefile)."""
+    """Compiles the oracle with gcc (oracle/Makefile) and, where its sources are, the reference's own kernels for the
+    host into oracle/_ref/ (oracle/reference.py): what the oracle is pinned to."""
     src = os.path.join(_HERE, 'megastep_oracle.c')
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
         subprocess.check_call(['make', '-C', _HERE, '-B', 'libmegastep_oracle.so'], stdout=subprocess.DEVNULL)
+    from oracle import reference
+    reference.build(force=force)
     return _LIB_PATH
 
 
@@ -70,6 +73,7 @@ def lib():
         _lib.oracle_bake.argtypes = [C.POINTER(OrScenery), C.POINTER(OrConfig)]
         _lib.oracle_ragged_index.argtypes = [_i32p, C.c_int, _i32p, _i32p, _i32p]
         _lib.oracle_sincospi.argtypes = [C.c_float, _f32p, _f32p]
+        _lib.oracle_sincospi_many.argtypes = [_f32p, _f32p, _f32p, C.c_long]
         _lib.oracle_collision_cs.argtypes = [C.c_float]*9
         _lib.oracle_collision_cs.restype = C.c_float
         _lib.oracle_collision_cc.argtypes = [C.c_float]*9
@@ -106,6 +110,14 @@ def sincospi(x):
     s, c = C.c_float(), C.c_float()
     lib().oracle_sincospi(np.float32(x), C.byref(s), C.byref(c))
     return np.float32(s.value), np.float32(c.value)
+
+
+def sincospi_many(x):
+    """(sin(pi x), cos(pi x)) over an array of binary32 arguments."""
+    x = _f32(x).ravel()
+    s, c = np.empty_like(x), np.empty_like(x)
+    lib().oracle_sincospi_many(_p(x), _p(s), _p(c), len(x))
+    return s, c
 
 
 def config(agent_radius, res, fov, fps):

@@ -79,21 +79,7 @@ def test_stacks_of_coincident_walls_under_every_number_of_groups(groups):
     other (kernels.cu:369), in shuffled line order, 512 rays over 40 degrees so that a wave's 256 rays all see the stack; one
     env with 150 such walls, whose (line, ray) pairs - 64 lines x 256 rays a batch - overflow the pair list several times."""
     from megastep_amd import cuda
-    rng = np.random.RandomState(5)
-    offsets = np.array([0., 0., 2e-5, 5e-5, 9e-5, 1e-4, 1.1e-4, 2e-4, 3e-4, 1e-3])
-    envs, pos, ang = [], [], []
-    for e in range(24):
-        k = 150 if e == 0 else 70 if e == 1 else rng.randint(2, 9)
-        xs = 4. + rng.choice(offsets, k)*rng.choice([1, 1, -1], k) + rng.choice([0., 0., .5], k)
-        walls = [[[x, 1. + rng.uniform(-.2, .2)], [x, 3. + rng.uniform(-.2, .2)]] for x in xs]
-        if e % 3 == 0:
-            walls += [[[4., 3.], [2., 3.]], [[2., 3.], [2., 1.]], [[2., 1.], [4., 1.]]]
-        if e % 4 == 0:
-            walls += [walls[0], [walls[1][1], walls[1][0]]]
-        envs.append(np.array(walls)[rng.permutation(len(walls))])
-        pos.append([[rng.uniform(2.2, 3.9), rng.uniform(1.5, 2.5)]])
-        ang.append([rng.uniform(-20, 20)])
-    c = _custom_world(envs, 1, 512, 40, pos, ang)
+    c = util.coincident_stacks_world()
     ref = util.OracleWorld(c)
     ref.bake(); ref.pull_baked(c); ref.pull_agents(c)
     want = ref.render()

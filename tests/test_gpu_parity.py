@@ -11,17 +11,7 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
-def _world(n_envs, n_agents, res, fov, seed=0, large=False, toy=None):
-    from megastep_amd import core, cubicasa, scene, toys
-    np.random.seed(seed)
-    if toy is not None:
-        geometries = n_envs*[getattr(toys, toy)()]
-    else:
-        geometries = cubicasa.sample(n_envs, n_unique=64, seed=seed + 1, large=large)
-    scenery = scene.scenery(geometries, n_agents, device='cuda', random=np.random.RandomState(seed))
-    c = core.Core(scenery, res=res, fov=fov, fps=10)
-    util.spawn(c, geometries, seed=seed)
-    return c, geometries
+_world = util.plan_world
 
 
 @pytest.mark.parametrize('n_envs,n_agents,res,fov,toy', [
@@ -114,40 +104,14 @@ def test_a_bake_it_refuses_has_launched_nothing():
     assert bool((baked == -7.).all()), 'the refused bake wrote baked_vals'
 
 
-def _custom_world(walls_per_env, n_agents, res, fov, positions, angles, lights=None):
-    """A Core over hand-made wall sets (one (W, 2, 2) array per env), agents placed explicitly."""
-    from megastep_amd import core, scene, arrdict
-    geoms = [arrdict.arrdict(walls=np.asarray(w, float), lights=np.array([[2., 2.]]) if lights is None else lights,
-                             masks=np.ones((4, 4), np.int16), res=.2) for w in walls_per_env]
-    np.random.seed(0)
-    scenery = scene.scenery(geoms, n_agents, device='cuda', random=np.random.RandomState(0))
-    c = core.Core(scenery, res=res, fov=fov, fps=10)
-    c.agents.positions[:] = torch.as_tensor(np.asarray(positions, np.float32), device=c.device)
-    c.agents.angles[:] = torch.as_tensor(np.asarray(angles, np.float32), device=c.device)
-    return c
+_custom_world = util.custom_world
 
 
 def test_hysteresis_band_adversarial():
     """Stacks of (nearly) coincident walls in shuffled order: the 1e-4 z-fight rule (kernels.cu:369) makes the
     winner depend on line order, which is exactly what the atomic-argmin path has to reproduce. Offsets straddle
     the band: 0, 2e-5, 5e-5, 9e-5, 1e-4, 1.1e-4, 2e-4, 1e-3."""
-    rng = np.random.RandomState(3)
-    offsets = np.array([0., 0., 2e-5, 5e-5, 9e-5, 1e-4, 1.1e-4, 2e-4, 3e-4, 1e-3])
-    envs, pos, ang = [], [], []
-    for e in range(48):
-        k = rng.randint(2, 9)
-        xs = 4. + rng.choice(offsets, k)*rng.choice([1, 1, -1], k) + rng.choice([0., 0., .5], k)
-        walls = [[[x, 1. + rng.uniform(-.2, .2)], [x, 3. + rng.uniform(-.2, .2)]] for x in xs]
-        if e % 3 == 0:      # an enclosing corner so that rays through shared vertices occur too
-            walls += [[[4., 3.], [2., 3.]], [[2., 3.], [2., 1.]], [[2., 1.], [4., 1.]]]
-        if e % 4 == 0:      # duplicates and reversed duplicates
-            walls += [walls[0], [walls[1][1], walls[1][0]]]
-        order = rng.permutation(len(walls))
-        envs.append(np.array(walls)[order])
-        pos.append([[rng.uniform(2.2, 3.9), rng.uniform(1.5, 2.5)]])
-        ang.append([rng.uniform(-30, 30)])
-    # pad every env to its own length is fine: Ragged
-    c = _custom_world(envs, 1, 64, 100, pos, ang)
+    c = util.hysteresis_band_world()
     from megastep_amd import cuda
     ref = util.OracleWorld(c)
     ref.bake(); ref.pull_baked(c); ref.pull_agents(c)
@@ -160,13 +124,7 @@ def test_hysteresis_band_adversarial():
 
 def test_agent_wedged_between_coincident_walls():
     """An agent 0.11 m from a wall that is doubled by a flush pillar face: most of its rays tie."""
-    wall = [[[2., 1.], [2., 2.2]], [[2., 2.2], [2., 4.]]]
-    pillar = [[[2., 2.], [2.3, 2.]], [[2.3, 2.], [2.3, 2.4]], [[2.3, 2.4], [2., 2.4]], [[2., 2.4], [2., 2.]]]
-    triple = pillar + [[[2., 2.05], [2., 2.35]]]
-    box = [[[1., 1.], [4., 1.]], [[4., 1.], [4., 4.]], [[4., 4.], [1., 4.]], [[1., 4.], [1., 1.]]]
-    envs = [np.array(wall + pillar + box), np.array(pillar + wall + box), np.array(wall + triple + box),
-            np.array(triple[::-1] + wall + box)]
-    c = _custom_world(envs, 1, 64, 130, [[[2.11, 2.2]]]*4, [[180.], [170.], [-175.], [180.]])
+    c = util.wedged_agent_world()
     from megastep_amd import cuda
     ref = util.OracleWorld(c)
     ref.bake(); ref.pull_baked(c); ref.pull_agents(c)
@@ -227,12 +185,8 @@ def test_full_benchmark_size_on_oblique_floorplans_matches_oracle():
 def test_step_on_oblique_floorplans_matches_oracle(n_envs, n_agents, res, fov, large):
     """Small oblique worlds through every instantiation family: the plain one, wide single-agent fans on large plans, the
     reference Deathmatch's 512 rays, a ragged last group at a wide view - four steps each, lines written back included."""
-    from megastep_amd import core, cubicasa, cuda, scene
-    np.random.seed(11)
-    geometries = cubicasa.sample(n_envs, n_unique=16, seed=12, large=large, oblique=True)
-    scenery = scene.scenery(geometries, n_agents, device='cuda', random=np.random.RandomState(11))
-    c = core.Core(scenery, res=res, fov=fov, fps=10)
-    util.spawn(c, geometries, seed=11)
+    from megastep_amd import cuda
+    c, geometries = util.oblique_world(n_envs, n_agents, res, fov, large)
     ref = util.OracleWorld(c)
     np.testing.assert_allclose(c.scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
     ref.pull_baked(c)
@@ -368,22 +322,10 @@ def test_large_maps_and_extreme_views(n_envs, n_agents, res, fov):
 def test_ragged_edge_cases():
     """An env without lights, an env with a single wall, an env with more walls than one LDS staging pass of the
     bake kernels holds (2048), side by side with a normal one."""
-    from megastep_amd import cuda, toys, arrdict
+    from megastep_amd import cuda
     rng = np.random.RandomState(0)
-    box = toys.box()
-    many = np.concatenate([box.walls] + [np.array([[[x, y], [x + .03, y + .02]]]) for x in np.linspace(1.5, 5.5, 50) for y in np.linspace(1.5, 5.5, 44)])
-    assert len(many) > 2048
-    geoms = [
-        arrdict.arrdict(walls=box.walls, lights=np.zeros((0, 2)), masks=box.masks, res=.2),          # dark room
-        arrdict.arrdict(walls=box.walls[:1], lights=box.lights, masks=box.masks, res=.2),            # one wall
-        arrdict.arrdict(walls=many, lights=np.array([[3.5, 3.5], [2., 5.]]), masks=box.masks, res=.2),
-        box]
-    from megastep_amd import core, scene
-    np.random.seed(0)
-    scenery = scene.scenery(geoms, 2, device='cuda', random=np.random.RandomState(0))
-    c = core.Core(scenery, res=64, fov=130)
-    c.agents.positions[:] = torch.as_tensor(rng.uniform(2, 5, (4, 2, 2)).astype(np.float32), device=c.device)
-    c.agents.angles[:] = torch.as_tensor(rng.uniform(-180, 180, (4, 2)).astype(np.float32), device=c.device)
+    c = util.ragged_edge_world(rng)
+    scenery = c.scenery
     ref = util.OracleWorld(c)
     np.testing.assert_allclose(scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
     ref.pull_baked(c)
@@ -440,24 +382,16 @@ def test_more_than_64_lights_and_agents(monkeypatch):
     agent there meet the walls group of 64 lights after group of 64 - inside the render kernel, next to envs that do have
     their grids: one launch, pooled observations and all (reference: kernels.cu:245-267 has no such limit). Without any
     grid the separate lighting kernel does the same. Past 64 agents per env the per-wave agent cache is bypassed."""
-    from megastep_amd import arrdict, core, cuda, modules, scene, toys
+    from megastep_amd import cuda, modules
     rng = np.random.RandomState(0)
-    box = toys.box()
-    pillars = np.concatenate([np.array([[[x, y], [x + .2, y]], [[x + .2, y], [x + .2, y + .2]], [[x + .2, y + .2], [x, y + .2]],
-                                        [[x, y + .2], [x, y]]]) for x, y in rng.uniform(1.5, 5.3, (6, 2))])
-    walls = np.concatenate([box.walls, pillars])
-    geoms = [arrdict.arrdict(walls=walls, lights=rng.uniform(1.2, 5.8, (k, 2)), masks=box.masks, res=.2) for k in (70, 9, 150, 64)]
+    geoms = util.many_lights_geometries(rng)
     for grid in (True, False):
         monkeypatch.setattr(cuda.Scenery, 'LIGHT_GRID', grid)
-        np.random.seed(0)
-        sc = scene.scenery(geoms, 3, device='cuda', random=np.random.RandomState(0))
+        c = util.many_lights_world(geoms, rng)
+        sc = c.scenery
         assert (sc._as_struct().lg_vals is not None) == grid
         if grid:                                                    # cells for the envs the grid can hold, none for the others
             assert (sc._lg.geom[:, 2] > 0).tolist() == [False, True, False, True]
-        c = core.Core(sc, res=64, fov=130)
-        spots = np.array([[3., 3.], [4., 3.1], [3.5, 4.]], np.float32) + rng.uniform(-.2, .2, (4, 3, 2)).astype(np.float32)
-        c.agents.positions[:] = torch.as_tensor(spots, device=c.device)     # a triangle of agents looking at each other
-        c.agents.angles[:] = torch.as_tensor(np.array([30., 150., -90.], np.float32) + rng.uniform(-10, 10, (4, 3)).astype(np.float32), device=c.device)
         ref = util.OracleWorld(c)
         np.testing.assert_allclose(sc.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
         ref.pull_baked(c); ref.pull_agents(c)
@@ -474,10 +408,7 @@ def test_more_than_64_lights_and_agents(monkeypatch):
             torch.testing.assert_close(rgb(frame), modules.downsample(full, 4).mean(-1), rtol=0, atol=1e-5)
     monkeypatch.setattr(cuda.Scenery, 'LIGHT_GRID', True)
 
-    crowd = scene.scenery([toys.box(8)], 66, device='cuda', random=np.random.RandomState(0))
-    c = core.Core(crowd, res=16, fov=130)
-    c.agents.positions[:] = torch.as_tensor(rng.uniform(1.5, 8.5, (1, 66, 2)).astype(np.float32), device=c.device)
-    c.agents.angles[:] = torch.as_tensor(rng.uniform(-180, 180, (1, 66)).astype(np.float32), device=c.device)
+    c = util.crowd_world(rng)
     ref = util.OracleWorld(c)
     ref.bake(); ref.pull_baked(c)
     util.random_velocities(c, rng, speed=3.)

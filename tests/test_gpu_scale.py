@@ -156,18 +156,8 @@ def test_bake_more_walls_than_fit_in_lds_and_many_lights():
 def test_crawling_agents_meet_far_walls_like_the_reference():
     """project() divides by (|v| + 1e-6) (kernels.cu:91-107): for |v| below ~1e-6 per step its distances shrink until
     endpoints metres away pass `d < r` and the reference stops the agent. The reach cull must not hide those walls."""
-    from megastep_amd import core, cuda, scene, toys
-    sc = scene.scenery(64*[toys.box()], 1, device='cuda')
-    c = core.Core(sc, res=8, fps=10)
-    rng = np.random.RandomState(0)
-    pos = rng.uniform(1.5, 5.5, (64, 1, 2)).astype(np.float32)
-    pos[0] = [5., 5.]
-    speed = 10.**rng.uniform(-9, -2, (64, 1, 1))
-    ang = rng.uniform(0, 2*np.pi, (64, 1, 1))
-    vel = (10*speed*np.concatenate([np.cos(ang), np.sin(ang)], -1)).astype(np.float32)      # v/fps = speed
-    vel[0] = [1e-6, 0.]
-    c.agents.positions[:] = torch.as_tensor(pos, device='cuda')
-    c.agents.velocity[:] = torch.as_tensor(vel, device='cuda')
+    from megastep_amd import cuda
+    c = util.crawling_agents_world()
     ref = util.OracleWorld(c)
     p = cuda.physics(c.scenery, c.agents)
     prog_ref, agents_ref = ref.physics()
@@ -182,26 +172,8 @@ def test_agents_meet_agents_like_the_reference_whatever_their_relative_velocity(
     """The reach cull in front of the agent-agent test: pairs at every distance around the threshold, relative
     velocities from a brisk walk down to 1e-9 a step (project()'s `+ 1e-6` stretches the reach of a pair that moves
     almost in step, kernels.cu:91-107), pairs in perfect step, pairs with a NaN or an infinity in their state."""
-    from megastep_amd import core, cuda, scene, toys
-    E = 512
-    sc = scene.scenery(E*[toys.box()], n_agents, device='cuda')
-    c = core.Core(sc, res=8, fps=10)
-    rng = np.random.RandomState(3)
-    base = rng.uniform(2.5, 3.5, (E, 1, 2))
-    gap = 10.**rng.uniform(-2.5, .7, (E, n_agents, 1))                    # 3 mm .. 5 m from the first agent
-    ang = rng.uniform(0, 2*np.pi, (E, n_agents, 1))
-    pos = (base + gap*np.concatenate([np.cos(ang), np.sin(ang)], -1)).astype(np.float32)
-    pos[:, 0] = base[:, 0]
-    common = rng.uniform(-3, 3, (E, 1, 2))*(rng.rand(E, 1, 1) < .8)       # a fifth of the envs: no common drift
-    rel = 10.**rng.uniform(-8, .5, (E, n_agents, 1))                      # 10 x the relative velocity per step
-    rang = rng.uniform(0, 2*np.pi, (E, n_agents, 1))
-    vel = (common + rel*np.concatenate([np.cos(rang), np.sin(rang)], -1)).astype(np.float32)
-    vel[::7, 1] = vel[::7, 0]                                             # in perfect step
-    vel[5::31, 1, 0] = np.nan
-    vel[11::37, 0, 1] = np.inf
-    pos[17::41, 1, 0] = np.nan
-    c.agents.positions[:] = torch.as_tensor(pos, device='cuda')
-    c.agents.velocity[:] = torch.as_tensor(vel, device='cuda')
+    from megastep_amd import cuda
+    c = util.agents_meeting_agents_world(n_agents)
     ref = util.OracleWorld(c)
     p = cuda.physics(c.scenery, c.agents)
     prog_ref, agents_ref = ref.physics()
@@ -215,22 +187,8 @@ def test_walls_with_non_finite_coordinates_go_through_the_exact_test(n_agents):
     """A NaN or an infinity among a wall's coordinates: the reach boxes cannot judge such a wall, so the sweep hands it to
     the exact test for every agent (with four agents or fewer and with more - the two sweeps), like the reference, which
     tests every wall. The progress must come out as the oracle's, whatever that is."""
-    from megastep_amd import core, cuda, scene, toys
-    sc = scene.scenery([toys.box() for _ in range(48)], n_agents, device='cuda')     # (48 floorplans of their own: their walls are about to differ)
-    c = core.Core(sc, res=8, fps=10)
-    rng = np.random.RandomState(1)
-    AF = n_agents*sc.model.shape[0]
-    lines = sc.lines.vals.reshape(48, -1, 4)                  # (env, line, xyxy): the box's four walls follow the agents' lines
-    assert lines.shape[1] == AF + 4
-    bad = [np.nan, np.inf, -np.inf]
-    for e in range(1, 48):                                    # env 0 stays clean
-        wall, coord = AF + rng.randint(4), rng.randint(4)
-        lines[e, wall, coord] = bad[e % 3]
-        if e % 5 == 0:
-            lines[e, wall, (coord + 2) % 4] = bad[(e + 1) % 3]
-    cuda.bake(sc)                                             # walls were moved: the wall grid (and the baked light) start over
-    c.agents.positions[:] = torch.as_tensor(rng.uniform(1.2, 4.8, (48, n_agents, 2)).astype(np.float32), device='cuda')
-    util.random_velocities(c, rng, speed=6.)
+    from megastep_amd import cuda
+    c = util.non_finite_walls_world(n_agents)
     ref = util.OracleWorld(c)
     p = cuda.physics(c.scenery, c.agents)
     prog_ref, _ = ref.physics()
