@@ -693,6 +693,57 @@ typedef struct MsNavWindows {
 } MsNavWindows;
 int ms_nav_windows(const MsNavGrid* grid, const MsNavWindows* windows, void* hip_stream);
 
+/* Cell draws: K cells drawn uniformly at random, with replacement, among the free cells of an env that satisfy a predicate on a
+ * layer - goals in a band of walking distance, spawns anywhere an agent fits, a random unseen cell - from a counter the kernel
+ * advances itself, so a captured step draws fresh numbers at every replay.  Every step is integer arithmetic;
+ * tests/test_navdraw_host.py restates it in numpy (draw_rule) and the kernel - and its host instantiation, ms_host_nav_draws -
+ * are held to EQUALITY with it.  c, geom and starts are MsNavGrid's.
+ *   draw sets     P per env; set (n, p) makes K draws.  `source` and `gate` are layers as MsNavWindows reads them: set (n, p)
+ *                 reads the store field[n, p] names; NULL: store 0 when n_fields == 1, else n_fields == P and set p reads
+ *                 store p (anything else is refused).  A field index outside [0, n_fields), of the source or of the gate,
+ *                 leaves the set without a qualifying cell.
+ *   qualifying    cell k of env n (row-major, row 0 at the lowest y) qualifies for set (n, p) when  1. free_cells is non-zero
+ *                 there;  2. the source's predicate holds: for a byte source (byte != 0) == where, for a binary32 source
+ *                 holding D lo <= D && D <= hi - a NaN, and +-inf outside the band, fail;  3. the gate (a byte layer; values
+ *                 NULL: none), if there is one, is non-zero there.  q_0 < q_1 < ... < q_{M-1} are the set's qualifying cells.
+ *                 An env without cells (or with more than max_cells says) has M = 0.
+ *   the hash      mix(a): a ^= a >> 16; a *= 0x85ebca6b; a ^= a >> 13; a *= 0xc2b2ae35; a ^= a >> 16 (murmur3's finaliser, on
+ *                 32 bits).  h = fold(seed_lo, seed_hi, n*P + p, counter[n, p], k, stream): s = 0x9e3779b9, then
+ *                 s = mix(s + word) modulo 2^32 for each of the six words in that order; seed_lo / seed_hi are the low and
+ *                 high 32 bits of `seed`.  fold(0, 0, 0, 0, 0, 0) = 0xe88cf1a4; fold(12345, 0, 2, 9, 4, 0) = 0xf8f4d17a.
+ *   a draw        draw k picks q_r with r = ((uint64)h * M) >> 32, h of stream 0: the bias is at most M / 2^32.
+ *                 uniforms[n, p, k] = (float)(h >> 8) * 2^-24 with h of stream 1, in [0, 1): a spare number per draw (a
+ *                 spawn's heading).
+ *   outputs       cells (N, P, K): the cell's index within its env, -1 when M = 0; points (N, P, K, 2): its centre as the nav
+ *                 grid forms it, x = ((float)(jx0 + j) + 0.5f)*c, y likewise, NaN when M = 0; uniforms (N, P, K); values
+ *                 (N, P, K), binary32 sources only, or NULL: D at the cell, NaN when M = 0; counts (N, P): M.
+ *   the counter   (N, P) in / out: the rule reads it; the kernel then adds 1 (modulo 2^32) for every set it computed.
+ *   mask          (N, P) bytes or NULL: a set whose byte is 0 is not touched at all - its outputs, its counts and its counter
+ *                 keep what they held.
+ * One launch, one workgroup per set, the qualifying cells as a bitmap in LDS, one bit per cell: max_cells, the most cells
+ * (nx*ny) any env has, sizes it.  More than 2^20: MS_EUNSUPPORTED, nothing enqueued.  K in 1..256, a gate must be bytes, lo
+ * and hi must not be NaN (they are not looked at for a byte source), values must be NULL for a byte source.  No atomics,
+ * nothing allocated, nothing waits: the call can be captured in a HIP graph.  Every argument is checked in full before the
+ * launch (MS_EINVAL). */
+typedef struct MsNavDraws {
+    MsNavLayer           source;
+    MsNavLayer           gate;         /* values NULL: none (the other members are then not looked at); else bytes     */
+    int                  where;        /* 0 or 1: the byte that qualifies (byte sources)                               */
+    float                lo, hi;       /* the band, both ends in (binary32 sources)                                    */
+    int                  n_sets;       /* P >= 1: draw sets per env                                                    */
+    int                  n_draws;      /* K: 1..256 draws per set                                                      */
+    unsigned long long   seed;
+    int*                 counter;      /* (N, P) in / out                                                              */
+    const unsigned char* mask;         /* (N, P) non-zero: compute this set; NULL: all                                 */
+    int*                 cells;        /* (N, P, K) out                                                                */
+    float*               points;       /* (N, P, K, 2) out                                                             */
+    float*               uniforms;     /* (N, P, K) out                                                                */
+    float*               values;       /* (N, P, K) out, or NULL                                                       */
+    int*                 counts;       /* (N, P) out                                                                   */
+    int                  max_cells;    /* the largest nx*ny of any env (0: no env has cells), at most 2^20             */
+} MsNavDraws;
+int ms_nav_draws(const MsNavGrid* grid, const MsNavDraws* draws, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

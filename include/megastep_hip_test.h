@@ -99,6 +99,11 @@ int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable
  * arrays: every pointer of `grid` (geom, starts; free_cells is checked, not read) and of `windows` (views, the layers' values and
  * fields, out) is host memory.  Returns what ms_nav_windows would: MS_OK, or MS_EINVAL for arguments it would refuse. */
 int ms_host_nav_windows(const MsNavGrid* grid, const MsNavWindows* windows);
+/* Host instantiation of the cell draws' rule (kernels/navdraw.h: the predicate, the hash, the rank and the n-th-set-bit select -
+ * the very functions every lane of nav_draw_kernel evaluates) for one whole call of ms_nav_draws on HOST arrays, swept serially:
+ * every pointer of `grid` and of `draws` is host memory.  Returns what ms_nav_draws would: MS_OK, MS_EINVAL for arguments it
+ * would refuse, MS_EUNSUPPORTED for more than 2^20 cells an env. */
+int ms_host_nav_draws(const MsNavGrid* grid, const MsNavDraws* draws);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

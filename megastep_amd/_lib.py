@@ -151,6 +151,12 @@ class MsNavWindows(C.Structure):
                 ('n_channels', C.c_int), ('channels', C.POINTER(MsNavChannel)), ('out', C.c_void_p)]
 
 
+class MsNavDraws(C.Structure):
+    _fields_ = [('source', MsNavLayer), ('gate', MsNavLayer), ('where', C.c_int), ('lo', C.c_float), ('hi', C.c_float), ('n_sets', C.c_int),
+                ('n_draws', C.c_int), ('seed', C.c_ulonglong), ('counter', C.c_void_p), ('mask', C.c_void_p), ('cells', C.c_void_p),
+                ('points', C.c_void_p), ('uniforms', C.c_void_p), ('values', C.c_void_p), ('counts', C.c_void_p), ('max_cells', C.c_int)]
+
+
 _int, _flt, _ptr, _p = C.c_int, C.c_float, C.c_void_p, C.POINTER
 
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare, as
@@ -180,6 +186,7 @@ PROTOTYPES = {
     'ms_nav_paths': (_int, [_p(MsNavGrid), _p(MsNavPaths), _ptr]),
     'ms_nav_seen': (_int, [_p(MsNavGrid), _p(MsNavSeen), _ptr]),
     'ms_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows), _ptr]),
+    'ms_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws), _ptr]),
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
     'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
     'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
@@ -208,6 +215,7 @@ PROTOTYPES = {
     'ms_host_nav_seed_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
     'ms_host_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows)]),
+    'ms_host_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws)]),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),

@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h, navseen.h, navwindow.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h, navseen.h, navwindow.h, navdraw.h.
 //
-// Twenty-two kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Twenty-three kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -58,6 +58,9 @@
 //                                                            (no counterpart)
 //   nav_window_kernel   map windows: per-cell stores (free cells, seen maps, fields) cropped and turned into images through
 //                   affine views, every image and channel in one launch, a lane a pixel.
+//                                                            (no counterpart)
+//   nav_draw_kernel     cell draws: one workgroup per draw set ballots the env's qualifying cells into an LDS bitmap, scans the
+//                   popcounts and picks each draw's cell by rank, from a hash of a counter it moves on itself.
 //                                                            (no counterpart)
 //   explorer_kernel    the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
@@ -161,6 +164,7 @@ struct Probe {
 #include "kernels/navpath.h"
 #include "kernels/navseen.h"
 #include "kernels/navwindow.h"
+#include "kernels/navdraw.h"
 #include "kernels/envlogic.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1096,6 +1100,43 @@ int ms_host_nav_windows(const MsNavGrid* grid, const MsNavWindows* w) {
         case 3: win_serial<3>(nav_args(grid), q); break;
         default: win_serial<4>(nav_args(grid), q); break;
     }
+    return MS_OK;
+}
+
+// Cell draws (navdraw.h): the same discipline; the bitmap's size is the seen maps'.
+static int nav_draws_check(const MsNavGrid* grid, const MsNavDraws* d) {
+    if (!nav_grid_ok(grid) || !d || d->n_sets < 1 || d->n_draws < 1 || d->n_draws > DRAW_MAX_DRAWS || !nav_layer_ok(d->source, d->n_sets) ||
+        (d->where != 0 && d->where != 1) || (d->gate.values && (!nav_layer_ok(d->gate, d->n_sets) || d->gate.is_float)) ||
+        (d->source.is_float && (d->lo != d->lo || d->hi != d->hi)) || (d->values && !d->source.is_float) ||
+        !d->counter || !d->cells || !d->points || !d->uniforms || !d->counts || d->max_cells < 0 ||
+        ((uintptr_t)d->counter % 4) || ((uintptr_t)d->cells % 4) || ((uintptr_t)d->points % 4) || ((uintptr_t)d->uniforms % 4) ||
+        ((uintptr_t)d->values % 4) || ((uintptr_t)d->counts % 4)) return MS_EINVAL;
+    if (d->max_cells > NAV_SEEN_MAX_CELLS || (long long)grid->n_envs*d->n_sets > 0x7fffffffLL/d->n_draws) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static NavDrawArgs nav_draw_args(const MsNavGrid* grid, const MsNavDraws* d) {
+    const bool gated = d->gate.values != nullptr;
+    return NavDrawArgs{d->source.values, d->source.field, static_cast<const unsigned char*>(d->gate.values), gated ? d->gate.field : nullptr,
+                       grid->free_cells, d->mask, d->counter, d->cells, d->points, d->uniforms, d->values, d->counts,
+                       d->source.n_fields, gated ? d->gate.n_fields : 1, d->source.is_float, d->where, d->lo, d->hi,
+                       (unsigned)(d->seed & 0xffffffffull), (unsigned)(d->seed >> 32), d->n_sets, d->n_draws, d->max_cells};
+}
+
+int ms_nav_draws(const MsNavGrid* grid, const MsNavDraws* d, void* stream) {
+    const int status = nav_draws_check(grid, d);
+    if (status != MS_OK) return status;
+    const size_t lds = (size_t)((d->max_cells + 63)/64 + WG)*sizeof(unsigned long long);      // (at most 130 KiB of the CU's 160)
+    if (lds > 64*1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(nav_draw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)lds) != hipSuccess) return hip_fail(hipGetLastError());
+    hipLaunchKernelGGL(nav_draw_kernel, dim3((unsigned)((long long)grid->n_envs*d->n_sets)), dim3(WG), lds, (hipStream_t)stream,
+                       nav_args(grid), nav_draw_args(grid, d));
+    return launch_status();
+}
+
+int ms_host_nav_draws(const MsNavGrid* grid, const MsNavDraws* d) {
+    const int status = nav_draws_check(grid, d);
+    if (status != MS_OK) return status;
+    draw_serial(nav_args(grid), nav_draw_args(grid, d));
     return MS_OK;
 }
 

@@ -26,10 +26,14 @@ def books(before, now, reset, stranded, arrive, bonus):
 class PointGoal:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, arrive=.5, bonus=1., max_lifespan=512,
-                 candidates=8, n_spawns=100, **kwargs):
+                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, **kwargs):
         """``cell``: the nav grid's cell size; ``arrive``: how near the goal counts as there, metres (walking distance);
         ``bonus``: the reward for arriving; ``max_lifespan``: episodes end after a random number of steps up to this
-        (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`."""
+        (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`.
+        ``goal_range=(lo, hi)``: goals drawn on the device at a walking distance of ``lo`` to ``hi`` metres from where the agent
+        starts (:class:`~megastep_amd.modules.SampledGoals`) instead of from the spawn table; ``sampled_spawns=True``: spawns
+        drawn on the device among the nav grid's free cells (:class:`~megastep_amd.modules.SampledSpawns`) instead of from a
+        table made on the host."""
         if geometries is None:
             geometries = cubicasa.sample(n_envs, workers=_plan_workers(), context='subprocess')
         self.core = core.Core(scene.scenery(geometries, n_agents, device=device), *args, res=4*64, fov=130, **kwargs)
@@ -38,14 +42,19 @@ class PointGoal:
         self.arrive, self.bonus = float(arrive), float(bonus)
 
         self._mover = modules.MomentumMovement(c)
-        self._respawner = modules.RandomSpawns(geometries, c, n_spawns=n_spawns)
+        self._respawner = None if sampled_spawns else modules.RandomSpawns(geometries, c, n_spawns=n_spawns)
         self._lifespans = modules.RandomLifespans(c, max_lifespan)
         self._rgb = modules.RGB(c, subsample=4)
         self._depth = modules.Depth(c, subsample=4)
         self.grid = cuda.nav_grid(c.scenery, cell, config=c.config)
-        # goals come from the spawn table; one closer than twice `arrive` would be a bonus for nothing
-        self._goals = modules.Goals(geometries, c, self.grid, candidates=candidates, min_distance=2*self.arrive,
-                                    table=self._respawner._spawns.positions)
+        if sampled_spawns:
+            self._respawner = modules.SampledSpawns(c, self.grid)
+        if goal_range is not None:
+            self._goals = modules.SampledGoals(c, self.grid, *goal_range)
+        else:
+            # goals come from the spawn table; one closer than twice `arrive` would be a bonus for nothing
+            self._goals = modules.Goals(geometries, c, self.grid, candidates=candidates, min_distance=2*self.arrive,
+                                        table=None if sampled_spawns else self._respawner._spawns.positions, n_spawns=n_spawns)
         self._follower = modules.PathFollower(c, self._goals, cone=15.)     # (under momentum a narrow cone walks a third less far: DESIGN 3.15)
         self.action_space = self._mover.space
         self.obs_space = dotdict.dotdict(rgb=self._rgb.space, d=self._depth.space, goal=self._goals.space)
@@ -56,7 +65,9 @@ class PointGoal:
 
     def _respawn(self, over):
         """The respawn of the agents marked, as a request the physics launch carries out after its step: each agent walks its
-        own (randomly ordered) spawn table, one entry per episode."""
+        own (randomly ordered) spawn table, one entry per episode - or, with ``sampled_spawns``, draws a cell."""
+        if isinstance(self._respawner, modules.SampledSpawns):
+            return self._respawner.draw(over, after=True)
         spawns = self._respawner._spawns
         choices = self._episodes % spawns.angles.shape[2]
         request = dict(mask=over.contiguous(), choices=choices.contiguous(), positions=spawns.positions, angles=spawns.angles, after=True)

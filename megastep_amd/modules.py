@@ -489,6 +489,91 @@ class Goals:
         return arrdict.arrdict(goals=self.goals[e], stranded=self.stranded[e]).clone()
 
 
+class SampledGoals:
+
+    def __init__(self, core, grid, min_distance, max_distance, seed=0):
+        """A goal per agent at a chosen walking distance (no counterpart in the reference): :class:`Goals`' interface - so
+        :class:`PathFollower` and the envs take it unchanged - with the goal drawn on the device by :func:`cuda.cell_draws`,
+        uniformly among the free cells of the agent's env whose walking distance from where the agent stands lies in
+        ``[min_distance, max_distance]`` metres. Such a goal is reachable by construction, there is no table and no candidate
+        count, and moving the band from episode to episode is a curriculum. A draw is three launches and nothing waits for
+        the host: the masked :func:`cuda.distance_fields` round the agents; one cell drawn in the band of that field; the
+        masked field of the goals. An agent whose band holds no cell - a closet smaller than ``min_distance`` - is flagged in
+        :attr:`stranded` (exactly ``draws.counts == 0``) and its goal is the spot it stands on. The band is on the cell's own
+        value: the agent's distance to the goal, which adds the leg from the agent to a cell next to it, can be up to a cell's
+        diagonal outside it."""
+        self.core, self.grid = core, grid
+        self.min_distance, self.max_distance, self.seed = float(min_distance), float(max_distance), int(seed)
+        if not 0 <= self.min_distance <= self.max_distance:
+            raise RuntimeError(f'the band must be 0 <= min_distance <= max_distance; got {min_distance}, {max_distance}')
+        self.space = spaces.MultiVector(core.n_agents, 3)
+        self.stranded = core.agent_full(False)
+        self._around = self._fields = self._draws = None
+
+    #: (n_env, n_agent, 2): every agent's goal
+    goals = property(lambda self: self._fields.goals)
+    #: the :class:`cuda.DistanceFields` of the goals
+    fields = property(lambda self: self._fields)
+    #: the :class:`cuda.CellDraws` of the last draw (None before the first)
+    draws = property(lambda self: self._draws)
+
+    def __call__(self, reset):
+        """Agents marked in the (n_env, n_agent) bool ``reset`` get a new goal, in the band from where they stand now."""
+        reset = reset.contiguous()
+        here = self.core.agents.positions
+        self._around = cuda.distance_fields(self.grid, here, mask=reset, out=self._around)
+        if self._draws is None:
+            self._draws = cuda.cell_draws(self.grid, self._around, self.core.n_agents, 1, lo=self.min_distance, hi=self.max_distance,
+                                          seed=self.seed, mask=reset)
+        else:
+            self._draws.again(mask=reset)
+        stranded = self._draws.counts == 0
+        goal = torch.where(stranded[..., None], here, self._draws.points[:, :, 0])
+        torch.where(reset, stranded, self.stranded, out=self.stranded)
+        self._fields = cuda.distance_fields(self.grid, goal.contiguous(), mask=reset, out=self._fields)
+        return self.goals
+
+    distances, waypoints, observation, state = Goals.distances, Goals.waypoints, Goals.observation, Goals.state
+
+
+class SampledSpawns:
+
+    def __init__(self, core, grid, seed=0, within=None):
+        """Respawns agents on a cell of the nav grid drawn on the device by :func:`cuda.cell_draws` (no counterpart in the
+        reference): :class:`RandomSpawns`' interface without its table. A spawn is the centre of a cell drawn uniformly among
+        the env's free cells - every one of them a spot the agent fits, by the grid's own clearance - or, with ``within`` (a
+        float32 layer, :func:`cuda.cell_layer`'s, one store an env or one per agent: a distance field from a reference point,
+        say), among the free cells where it is finite: the cells of the same connected space as the reference. The heading is
+        the draw's spare uniform number, ``uniforms*360 - 180``. Every agent draws for itself: two agents of an env may draw
+        the same cell, as they may in the reference's table. An agent of an env without a qualifying cell stays where it is."""
+        self.core, self.grid, self.seed = core, grid, int(seed)
+        self._within = within
+        self._choices = torch.zeros((core.n_envs, core.n_agents), dtype=torch.long, device=core.device)
+        self._draws = None
+
+    #: the :class:`cuda.CellDraws` of the last draw (None before the first)
+    draws = property(lambda self: self._draws)
+
+    def draw(self, reset, after=False):
+        """The respawn of the agents marked in the (n_env, n_agent) bool mask ``reset`` as a request in
+        :meth:`RandomSpawns.draw`'s form: a table of one freshly drawn spawn per agent, ``choices`` all zero."""
+        reset = reset.contiguous()
+        if self._draws is None:
+            if self._within is None:
+                self._draws = cuda.cell_draws(self.grid, self.grid, self.core.n_agents, 1, seed=self.seed, mask=reset)
+            else:
+                self._draws = cuda.cell_draws(self.grid, self._within, self.core.n_agents, 1, lo=-float('inf'), hi=torch.finfo(torch.float32).max,
+                                              seed=self.seed, mask=reset)
+        else:
+            self._draws.again(mask=reset)
+        d = self._draws
+        return dict(mask=reset & (d.counts > 0), choices=self._choices, positions=d.points, angles=d.uniforms*360. - 180., after=after)
+
+    def __call__(self, reset):
+        """``reset`` is an (n_env, n_agent) bool mask; the marked agents get a new pose and zero velocity."""
+        _respawn(self.core.agents, self.draw(reset))
+
+
 class Coverage:
 
     def __init__(self, core, grid, max_range=10., shared=False, countable=None):

@@ -1,6 +1,7 @@
 """Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
-floorplans, the seen maps of the depth rays, and windows of all of them as images round the agents
-(kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``). No counterpart in the reference;
+floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
+they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``,
+``csrc/kernels/navdraw.h``). No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
@@ -655,3 +656,105 @@ def local_maps(grid, views, size, channels, samples=1, out=None):
     with _on(dev):
         _lib.check(_lib.lib().ms_nav_windows(C.byref(grid._struct), C.byref(spec), _stream(dev)))
     return out
+
+
+#: the most draws a set of :func:`cell_draws` makes: the kernel gives a lane of its workgroup to each
+DRAW_MAX_DRAWS = 256
+
+
+class CellDraws:
+    """Result of :func:`cell_draws`: ``n_sets`` draw sets per env of ``n_draws`` draws each. ``cells`` (N, P, K) int32: the index of
+    each drawn cell within its env's grid, row-major with row 0 at the lowest y, -1 where no cell of the env qualified; ``points``
+    (N, P, K, 2) float32: the cells' centres (NaN where none qualified); ``uniforms`` (N, P, K) float32: a spare uniform number in
+    [0, 1) per draw; ``values`` (N, P, K) float32, None for a byte source: what the source holds at the cell; ``counts`` (N, P)
+    int32: how many cells qualified; ``counter`` (N, P) int32: how many times each set has been drawn - the kernel reads it and
+    moves it on, so the next draw of a set is another one. ``source`` and ``gate`` are kept by reference: :meth:`again` reads
+    them as they stand."""
+
+    def __init__(self, grid, n_sets, n_draws, cells, points, uniforms, values, counts, counter):
+        self.grid, self.n_sets, self.n_draws = grid, int(n_sets), int(n_draws)
+        self.cells, self.points, self.uniforms, self.values, self.counts, self.counter = cells, points, uniforms, values, counts, counter
+        cells_of = grid._host_geom[:, 2].astype('int64')*grid._host_geom[:, 3].astype('int64')
+        self._max_cells = int(cells_of.max()) if len(cells_of) else 0
+
+    def _set(self, source, gate, where, lo, hi, seed):
+        """Takes the arguments of a call: checks the layers against the grid and the sets and fills in the MsNavDraws."""
+        grid, n, p = self.grid, self.grid.n_envs, self.n_sets
+        spec = _lib.MsNavDraws()
+        tensors = [grid.free, self.cells, self.points, self.uniforms, self.counts, self.counter]
+        tensors += _window_layer(source, 'source', grid, n, p, spec.source)
+        if gate is not None:
+            tensors += _window_layer(gate, 'gate', grid, n, p, spec.gate)
+        spec.where, spec.lo, spec.hi = int(bool(where)), float(lo or 0.), float(hi or 0.)
+        spec.n_sets, spec.n_draws, spec.seed, spec.max_cells = p, self.n_draws, seed, self._max_cells
+        spec.counter, spec.cells, spec.points = self.counter.data_ptr(), self.cells.data_ptr(), self.points.data_ptr()
+        spec.uniforms, spec.counts = self.uniforms.data_ptr(), self.counts.data_ptr()
+        if self.values is not None:
+            spec.values = self.values.data_ptr()
+            tensors.append(self.values)
+        self.source, self.gate, self.where, self.lo, self.hi, self.seed = source, gate, bool(where), lo, hi, seed
+        self._spec, self._tensors = spec, tensors
+
+    def again(self, mask=None):
+        """Draws again in place, from the layers as they stand now; the counter moves on, so the draws are new ones. ``mask``
+        (N, P) bool: only the marked sets are drawn - the others keep their draws, their counts and their counter. One launch, no
+        host synchronisation, nothing allocated: the call can be captured in a HIP graph, and every replay draws afresh."""
+        grid = self.grid
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, self.n_sets):
+                raise RuntimeError(f'mask must be an (N, P) = ({grid.n_envs}, {self.n_sets}) bool tensor')
+            mask = mask.contiguous()
+        dev = _require_gpu(*self._tensors, *([mask] if mask is not None else []))
+        self._spec.mask = mask.data_ptr() if mask is not None else None
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_draws(C.byref(grid._struct), C.byref(self._spec), _stream(dev)))
+        return self
+
+
+def cell_draws(grid, source, n_sets, n_draws, lo=None, hi=None, where=True, gate=None, seed=0, mask=None, out=None):
+    """Cells of the :func:`nav_grid` drawn uniformly at random: for every env ``n_sets`` draw sets of ``n_draws`` (1..256) draws each,
+    with replacement, among the env's free cells that satisfy a predicate on ``source`` - a layer (:func:`cell_layer`, or a
+    :class:`NavGrid`, :class:`SeenMaps`, :class:`DistanceFields` or :class:`SeededFields` as it is), read per set the way
+    :func:`local_maps` reads a layer per view: one store an env, one per set, or the one the layer's ``field`` (N, P) names. A byte
+    source qualifies a cell where ``(byte != 0) == where``; a float32 source holding D where ``lo <= D <= hi`` (both required
+    then, both ends in; a NaN never qualifies) - a band of a distance field is a goal at a chosen walking distance, reachable by
+    construction; ``grid`` itself any spot an agent fits; a seen map with ``where=False`` a cell not yet seen. ``gate``: a byte
+    layer; only cells where its byte is non-zero qualify.
+
+    The numbers come from a hash of ``seed``, the set, the draw and the set's own counter, which the kernel moves on by one in
+    every call that computes the set: nothing is drawn on the host, and a captured :meth:`CellDraws.again` draws afresh at every
+    replay. ``mask`` (N, P) bool: only the marked sets are computed; ``out``: the :class:`CellDraws` of an earlier call with the same
+    grid, ``n_sets``, ``n_draws`` and kind of source to write into - its counter goes on counting. One launch, a workgroup a set, no
+    host synchronisation. The rule is written out in include/megastep_hip.h (``MsNavDraws``) and DESIGN.md 3.19; the kernel
+    computes it exactly."""
+    if not isinstance(n_sets, int) or n_sets < 1:
+        raise RuntimeError(f'n_sets must be a positive integer; got {n_sets}')
+    if not isinstance(n_draws, int) or not 1 <= n_draws <= DRAW_MAX_DRAWS:
+        raise RuntimeError(f'n_draws must be an integer in 1..{DRAW_MAX_DRAWS}; got {n_draws}')
+    if not isinstance(seed, int) or not 0 <= seed < 2**64:
+        raise RuntimeError(f'seed must be an integer in 0..2^64 - 1; got {seed}')
+    source = _layer(source)
+    gate = None if gate is None else _layer(gate)
+    if gate is not None and gate.is_float:
+        raise RuntimeError('a gate must be a byte layer (uint8 or bool), not float32')
+    if source.is_float:
+        if lo is None or hi is None or lo != lo or hi != hi:
+            raise RuntimeError('a float32 source needs the bounds lo and hi of its band (numbers, not NaN)')
+        lo, hi = float(lo), float(hi)
+    elif lo is not None or hi is not None:
+        raise RuntimeError('a byte source takes no bounds: lo and hi go with a float32 source')
+    n, shape = grid.n_envs, (grid.n_envs, n_sets, n_draws)
+    if out is not None:
+        if not isinstance(out, CellDraws) or out.grid is not grid or tuple(out.cells.shape) != shape or (out.values is not None) != source.is_float:
+            raise RuntimeError(f'`out` must come from a cell_draws call with the same grid, (N, P, K) = {shape} and kind of source')
+        draws = out
+    else:
+        if int(grid._host_geom[:, 2:].astype('int64').prod(1).max(initial=0)) > SEEN_MAX_CELLS:
+            raise RuntimeError(f'cell draws take at most {SEEN_MAX_CELLS} cells an env')
+        dev = grid.free.device
+        new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)
+        draws = CellDraws(grid, n_sets, n_draws, new(shape, torch.int32, -1), new(shape + (2,), torch.float32, float('nan')),
+                          new(shape, torch.float32, 0.), new(shape, torch.float32, float('nan')) if source.is_float else None,
+                          new((n, n_sets), torch.int32, 0), new((n, n_sets), torch.int32, 0))
+    draws._set(source, gate, where, lo, hi, seed)
+    return draws.again(mask)

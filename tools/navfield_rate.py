@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -35,6 +35,12 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       (MI355X_MICROARCH.md; 8 TB/s spec) - next to the torch formulation of the same rule on the same inputs (index arithmetic
       and gathers; the first `--torch-envs` envs, scaled; outputs compared as bits) and to modules.Overhead at the same size;
       FloorCoverage(envs, local_map=True).step eager and replayed as a HIP graph, next to FloorCoverage(envs).step.
+  (d) the cell draws, at `--envs` envs x 1 agent: one cuda.cell_draws (ms_nav_draws) of K = 1 and one of K = 64 in the band 2 to 8 m
+      of the distance field round a spawn point - each timed as 20 CellDraws.again() back to back between two events - next to
+      the torch formulation of the same rule on the same inputs (the qualify mask padded to the largest plan, a cumsum, the same
+      hash in int64 tensor ops and a searchsorted; the first `--torch-envs` envs, scaled; its cells compared with the kernel's);
+      PointGoal(envs, goal_range=(2., 8.), sampled_spawns=True).step eager and replayed as a HIP graph, next to the plain
+      PointGoal(envs).step.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -231,6 +237,37 @@ def torch_windows(grid, views, size, samples, channels, envs):
     return run
 
 
+def torch_draws(grid, D, lo, hi, K, seed, envs):
+    """The cell draws' rule by tensor ops for the first `envs` envs, one set each, from counter 0, on a float32 source of one
+    store an env: returns run() -> ((envs, K) cells, (envs,) counts)."""
+    dev = D.device
+    cells = torch.as_tensor(np.diff(grid._host_starts[:envs + 1]), device=dev)
+    starts = torch.as_tensor(grid._host_starts[:envs], device=dev)
+    span = torch.arange(int(cells.max()), device=dev)
+    valid = span[None, :] < cells[:, None]
+    at = torch.where(valid, starts[:, None] + span[None, :], torch.zeros_like(starts[:, None]))
+    m32 = 0xffffffff
+
+    def mix(a):
+        a = a ^ (a >> 16)
+        a = (a*0x85ebca6b) & m32
+        a = a ^ (a >> 13)
+        a = (a*0xc2b2ae35) & m32
+        return a ^ (a >> 16)
+
+    def run():
+        q = valid & (grid.free[at] != 0) & (D[at] >= lo) & (D[at] <= hi)
+        cum = q.long().cumsum(1)
+        M = cum[:, -1]
+        s = torch.full((envs, K), 0x9e3779b9, dtype=torch.int64, device=dev)
+        for word in (seed & m32, seed >> 32, torch.arange(envs, device=dev)[:, None], 0, torch.arange(K, device=dev)[None, :], 0):
+            s = mix((s + word) & m32)
+        r = (s*M[:, None]) >> 32
+        cell = torch.searchsorted(cum, r + 1)
+        return torch.where(M[:, None] > 0, cell, torch.full_like(cell, -1)), M
+    return run
+
+
 class ExpertStep:
     """An env whose step is the expert's own: expert() + step(), the decision handed in ignored."""
 
@@ -290,7 +327,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
@@ -517,6 +554,43 @@ def main():
             eager, graphed = env_rates(env, args.envs, 60, 10)
             out[name] = dict(eager_seconds=eager, graph_seconds=graphed)
             print(f'(w) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+
+    if want('draws'):
+        sc = scene.scenery(geoms, 1, device='cuda', bake=False)
+        c = core.Core(sc, res=64)
+        grid = cuda.nav_grid(sc, config=c.config)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        fields = cuda.distance_fields(grid, table[:, :, 0].contiguous())
+        cells = np.diff(grid._host_starts)
+        k, batch = min(args.torch_envs, args.envs), 20
+        for K in (1, 64):
+            draws = cuda.cell_draws(grid, fields, 1, K, lo=2., hi=8., seed=7)
+            cells_first, counts = draws.cells[:k, 0].long().clone(), draws.counts[:k, 0].long().clone()
+
+            def calls():
+                for _ in range(batch):
+                    draws.again()
+            med, lo, hi = (t/batch for t in timed(calls, args.repeats, args.warmup))
+            run = torch_draws(grid, fields.values, 2., 8., K, 7, k)
+            got = run()
+            same = bool(torch.equal(got[0], cells_first) and torch.equal(got[1], counts))
+            tmed = timed(lambda: run(), max(args.repeats//3, 2), 1)[0]
+            out[f'draws_{K}'] = dict(seconds=med, min=lo, max=hi, sets=args.envs, draws=K, cells_largest=int(cells.max()), cells_median=int(np.median(cells)),
+                                     qualifying_mean=float(draws.counts.float().mean()), empty_sets=int((draws.counts == 0).sum()), torch_envs=k,
+                                     torch_seconds=tmed, torch_scaled_seconds=tmed*args.envs/k, torch_equal=same)
+            print(f"(d) cell_draws, {args.envs} x 1 sets of {K}: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}] a call ({batch} back to back); "
+                  f"{out[f'draws_{K}']['qualifying_mean']:.0f} cells qualify a set; torch, {k} envs: {tmed*1e3:.2f} ms -> {tmed*args.envs/k*1e3:.1f} ms "
+                  f'for {args.envs}, equal cells and counts: {same}')
+        del sc, c, grid, fields, draws
+        torch.cuda.empty_cache()
+        for name, make in (('PointGoal_sampled', lambda: PointGoal(args.envs, geometries=geoms, goal_range=(2., 8.), sampled_spawns=True)),
+                           ('PointGoal_plain', lambda: PointGoal(args.envs, geometries=geoms))):
+            env = make()
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[name] = dict(eager_seconds=eager, graph_seconds=graphed)
+            print(f'(d) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
             del env
             torch.cuda.empty_cache()
 
