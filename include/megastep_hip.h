@@ -744,6 +744,80 @@ typedef struct MsNavDraws {
 } MsNavDraws;
 int ms_nav_draws(const MsNavGrid* grid, const MsNavDraws* draws, void* hip_stream);
 
+/* Regions: which cells of the nav grid belong together - the connected components of any per-cell mask, each cell labelled with
+ * its component and the component's area: the rooms an agent can walk between, the clusters the unseen floor falls into.  Every
+ * step is integer arithmetic but the area; tests/test_navregion_host.py restates it in numpy (region_rule, a flood fill) and the
+ * kernels - and their host instantiations, ms_host_nav_regions / _region_query / _region_masks - are held to EQUALITY with it.
+ * c, geom and starts are MsNavGrid's.
+ *   regions field (n, g) is field g of env n, G per env; its stores use the fields' layout: field (n, g) starts at
+ *                 G*starts[n] + g*nx*ny, row-major, row 0 at the lowest y.
+ *   open cells    without marks (NULL): cell k is open when free_cells[k] & 1.  With marks (a byte per cell and field, the
+ *                 fields' layout), where in {0, 1} and among (a byte per cell of the grid, or NULL): when MsNavSeedFields' seed
+ *                 predicate holds - free[k] & 1, and among == NULL or among[k] & 1, and (marks[k] & 1) == where; the kernels
+ *                 call the very function the seeded fields call, so a frontier field's seeds ARE a frontier regions field's
+ *                 open cells.  among is not looked at without marks.
+ *   edges         two open cells are joined when they are 4-neighbours inside the env's nx x ny; rows do not wrap.  On the free
+ *                 cells this is exactly the connectivity of MsNavGrid's graph: a diagonal edge u - v exists only when both
+ *                 cells that share a side with u and v are free, and then u - side - v is a path of straight edges; so the
+ *                 regions of the grid are exactly the sets on which a distance field is finite.
+ *   labels        int32 per cell: the least row-major index, within the env, of an open cell of the cell's component; -1 on a
+ *                 closed cell.  Canonical: any algorithm and any schedule gives the same.
+ *   areas         binary32 per cell: (float)cells_in_component*(c*c), those two binary32 multiplications in that order; 0.f
+ *                 on a closed cell.  A float layer in square metres: MsNavDraws' band and MsNavChannel's scale read it as it is.
+ *   summary       (N, G) int32 each: counts - the regions; open_cells - the open cells; largest - the label of the region with
+ *                 the most cells, the least such label on a tie, -1 without an open cell; largest_cells - its cells (0 then);
+ *                 passes (or NULL) - the passes the propagation took (telemetry: depends on the schedule).  An env without
+ *                 cells: 0, 0, -1, 0, 0.
+ *   query         a point's anchors are MsNavGrid's four cells (i0 + (t>>1), j0 + (t&1)), t = 0..3; labels_at (N, P, 4) holds
+ *                 the label under each, -1 where the anchor is outside the grid or closed; all -1 for a NaN point, one further
+ *                 out than 2^30 cells, an env without cells, a field index outside [0, G).  field (N, P) names the regions
+ *                 field each point asks; NULL: MsNavLayer's rule - field 0 when G == 1, else G == P and point p asks field p.
+ *   masks         P requests per env; out holds P byte stores per env in the fields' layout (request (n, p) at
+ *                 P*starts[n] + p*nx*ny).  A byte is 1 where labels[k] >= 0 and labels[k] is in the request's wanted set: the
+ *                 non-negative anchor labels of points[n, p] (up to four: a point between two diagonally touching cells wants
+ *                 two regions), or the one label wanted[n, p] (-1, or any label no cell holds: an empty mask).  Exactly one of
+ *                 points and wanted is given.  field: as the query's.  Every byte of every store is written.  With P = 1 the
+ *                 store has free_cells' layout: an among, a countable mask or a gate as it is.
+ * ms_nav_regions: one launch, one workgroup per field, the labels in LDS while the field fits ((nx + 2)*(ny + 2) int32 in 40,
+ * 80 or 160 KiB, chosen by max_framed); a larger field is labelled in its `labels` store, to the same bits.  Fields that are
+ * masked out keep labels, areas and summary as they are.  marks and among are read when the call runs.  Integer atomics only,
+ * one writer per output element, nothing allocated, nothing waits: all three calls can be captured in a HIP graph.  Every
+ * argument is checked in full before the launch (MS_EINVAL). */
+typedef struct MsNavRegions {
+    int                  n_fields;     /* G: regions fields per env                                                    */
+    const unsigned char* marks;        /* G*starts[N] bytes, bit 0: the fields' layout; NULL: the open cells are the free cells */
+    int                  where;        /* 0 or 1: an open cell's mark (with marks)                                     */
+    const unsigned char* among;        /* (starts[N],) bit 0: the cell may be open; NULL: every free cell may (with marks) */
+    const unsigned char* mask;         /* (N, G) non-zero: compute this field; NULL: all.  Read on the device only.    */
+    int*                 labels;       /* G*starts[N] int32 out                                                        */
+    float*               areas;        /* G*starts[N] floats out                                                       */
+    int*                 counts;       /* (N, G) out                                                                   */
+    int*                 open_cells;   /* (N, G) out                                                                   */
+    int*                 largest;      /* (N, G) out                                                                   */
+    int*                 largest_cells;/* (N, G) out                                                                   */
+    int*                 passes;       /* (N, G) out, or NULL                                                          */
+} MsNavRegions;
+typedef struct MsNavRegionQuery {
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y                                                               */
+    const int*           field;        /* (N, P) the regions field each point asks; NULL: G == 1 or G == P             */
+    const int*           labels;       /* as MsNavRegions.labels                                                       */
+    int                  n_fields;     /* G of `labels`                                                                */
+    int*                 labels_at;    /* (N, P, 4) out                                                                */
+} MsNavRegionQuery;
+typedef struct MsNavRegionMasks {
+    int                  n_requests;   /* P: requests per env                                                          */
+    const float*         points;       /* (N, P, 2), or NULL: `wanted` is given                                        */
+    const int*           wanted;       /* (N, P) one label each, or NULL: `points` is given                            */
+    const int*           field;        /* (N, P) the regions field each request reads; NULL: G == 1 or G == P          */
+    const int*           labels;       /* as MsNavRegions.labels                                                       */
+    int                  n_fields;     /* G of `labels`                                                                */
+    unsigned char*       out;          /* P*starts[N] bytes out                                                        */
+} MsNavRegionMasks;
+int ms_nav_regions(const MsNavGrid* grid, const MsNavRegions* regions, void* hip_stream);
+int ms_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* query, void* hip_stream);
+int ms_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* masks, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

@@ -104,6 +104,17 @@ int ms_host_nav_windows(const MsNavGrid* grid, const MsNavWindows* windows);
  * every pointer of `grid` and of `draws` is host memory.  Returns what ms_nav_draws would: MS_OK, MS_EINVAL for arguments it
  * would refuse, MS_EUNSUPPORTED for more than 2^20 cells an env. */
 int ms_host_nav_draws(const MsNavGrid* grid, const MsNavDraws* draws);
+/* Host instantiations of the regions' rule (kernels/navregion.h: the open test, the fill, one cell's lowered and jumped value,
+ * the count at the roots, the area, the largest key, the anchor labels and the mask byte - the very functions every lane of
+ * nav_region_kernel, nav_region_query_kernel and nav_region_mask_kernel evaluates) for one whole call each on HOST arrays, swept
+ * serially: every pointer of `grid` and of the argument struct is host memory.  ms_host_nav_regions labels a field on a framed
+ * copy when it fits the LDS of the launch ms_nav_regions would choose by grid->max_framed, else in its `labels` store - the
+ * kernel's two paths.  They return what the device entries would: MS_OK, or MS_EINVAL for arguments they would refuse.
+ * ms_host_nav_region_capacity writes the three capacities, in framed cells, of nav_region_kernel's instantiations. */
+int ms_host_nav_regions(const MsNavGrid* grid, const MsNavRegions* regions);
+int ms_host_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* query);
+int ms_host_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* masks);
+int ms_host_nav_region_capacity(int* capacities);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

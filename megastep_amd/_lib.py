@@ -157,6 +157,22 @@ class MsNavDraws(C.Structure):
                 ('points', C.c_void_p), ('uniforms', C.c_void_p), ('values', C.c_void_p), ('counts', C.c_void_p), ('max_cells', C.c_int)]
 
 
+class MsNavRegions(C.Structure):
+    _fields_ = [('n_fields', C.c_int), ('marks', C.c_void_p), ('where', C.c_int), ('among', C.c_void_p), ('mask', C.c_void_p),
+                ('labels', C.c_void_p), ('areas', C.c_void_p), ('counts', C.c_void_p), ('open_cells', C.c_void_p), ('largest', C.c_void_p),
+                ('largest_cells', C.c_void_p), ('passes', C.c_void_p)]
+
+
+class MsNavRegionQuery(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('field', C.c_void_p), ('labels', C.c_void_p), ('n_fields', C.c_int),
+                ('labels_at', C.c_void_p)]
+
+
+class MsNavRegionMasks(C.Structure):
+    _fields_ = [('n_requests', C.c_int), ('points', C.c_void_p), ('wanted', C.c_void_p), ('field', C.c_void_p), ('labels', C.c_void_p),
+                ('n_fields', C.c_int), ('out', C.c_void_p)]
+
+
 _int, _flt, _ptr, _p = C.c_int, C.c_float, C.c_void_p, C.POINTER
 
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare, as
@@ -187,6 +203,9 @@ PROTOTYPES = {
     'ms_nav_seen': (_int, [_p(MsNavGrid), _p(MsNavSeen), _ptr]),
     'ms_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows), _ptr]),
     'ms_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws), _ptr]),
+    'ms_nav_regions': (_int, [_p(MsNavGrid), _p(MsNavRegions), _ptr]),
+    'ms_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery), _ptr]),
+    'ms_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks), _ptr]),
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
     'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
     'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
@@ -216,6 +235,10 @@ PROTOTYPES = {
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
     'ms_host_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows)]),
     'ms_host_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws)]),
+    'ms_host_nav_regions': (_int, [_p(MsNavGrid), _p(MsNavRegions)]),
+    'ms_host_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery)]),
+    'ms_host_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks)]),
+    'ms_host_nav_region_capacity': (_int, [_ptr]),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),

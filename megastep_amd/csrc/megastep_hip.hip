@@ -2,7 +2,7 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navpath.h, navseen.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navregion.h, navpath.h, navseen.h, navwindow.h, navdraw.h.
 //
 // Twenty-three kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
@@ -161,6 +161,7 @@ struct Probe {
 #include "kernels/raycast.h"
 #include "kernels/overhead.h"
 #include "kernels/navfield.h"
+#include "kernels/navregion.h"
 #include "kernels/navpath.h"
 #include "kernels/navseen.h"
 #include "kernels/navwindow.h"
@@ -1137,6 +1138,102 @@ int ms_host_nav_draws(const MsNavGrid* grid, const MsNavDraws* d) {
     const int status = nav_draws_check(grid, d);
     if (status != MS_OK) return status;
     draw_serial(nav_args(grid), nav_draw_args(grid, d));
+    return MS_OK;
+}
+
+// Regions (navregion.h): the same discipline; the launch's LDS is chosen as the relaxation's, by the largest framed field.
+static int nav_region_capacity_for(const MsNavGrid* grid) {
+    const long long framed = grid->max_framed;
+    return framed <= region_capacity(NAV_LDS_SMALL) ? region_capacity(NAV_LDS_SMALL)
+         : framed <= region_capacity(NAV_LDS_MEDIUM) ? region_capacity(NAV_LDS_MEDIUM) : region_capacity(NAV_LDS_LARGE);
+}
+static int nav_regions_check(const MsNavGrid* grid, const MsNavRegions* r) {
+    if (!nav_grid_ok(grid) || !r || r->n_fields < 1 || (r->marks && r->where != 0 && r->where != 1) || !r->labels || !r->areas || !r->counts ||
+        !r->open_cells || !r->largest || !r->largest_cells || ((uintptr_t)r->labels % 4) || ((uintptr_t)r->areas % 4) ||
+        ((uintptr_t)r->counts % 4) || ((uintptr_t)r->open_cells % 4) || ((uintptr_t)r->largest % 4) || ((uintptr_t)r->largest_cells % 4) ||
+        ((uintptr_t)r->passes % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*r->n_fields > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static NavRegionArgs nav_region_args(const MsNavGrid* grid, const MsNavRegions* r) {
+    return NavRegionArgs{grid->free_cells, r->marks, r->marks ? r->among : nullptr, r->mask, r->labels, r->areas, r->counts, r->open_cells,
+                         r->largest, r->largest_cells, r->passes, r->n_fields, r->marks ? r->where : 1};
+}
+static int nav_region_query_check(const MsNavGrid* grid, const MsNavRegionQuery* q) {
+    if (!nav_grid_ok(grid) || !q || q->n_points < 1 || q->n_fields < 1 || !q->points || !q->labels || !q->labels_at ||
+        (!q->field && q->n_fields != 1 && q->n_fields != q->n_points) || ((uintptr_t)q->points % 4) || ((uintptr_t)q->field % 4) ||
+        ((uintptr_t)q->labels % 4) || ((uintptr_t)q->labels_at % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*q->n_points > 0x7fffff00LL/4) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static int nav_region_masks_check(const MsNavGrid* grid, const MsNavRegionMasks* m) {
+    if (!nav_grid_ok(grid) || !m || m->n_requests < 1 || m->n_fields < 1 || (m->points != nullptr) == (m->wanted != nullptr) || !m->labels ||
+        !m->out || (!m->field && m->n_fields != 1 && m->n_fields != m->n_requests) || ((uintptr_t)m->points % 4) || ((uintptr_t)m->wanted % 4) ||
+        ((uintptr_t)m->field % 4) || ((uintptr_t)m->labels % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*m->n_requests > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+
+int ms_nav_regions(const MsNavGrid* grid, const MsNavRegions* r, void* stream) {
+    const int status = nav_regions_check(grid, r);
+    if (status != MS_OK) return status;
+    const int capacity = nav_region_capacity_for(grid);
+    void (*kernel)(NavArgs, NavRegionArgs);
+    int threads = 1024;
+    if (capacity == region_capacity(NAV_LDS_SMALL)) { kernel = nav_region_kernel<NAV_LDS_SMALL, 512>; threads = 512; }
+    else if (capacity == region_capacity(NAV_LDS_MEDIUM)) kernel = nav_region_kernel<NAV_LDS_MEDIUM, 1024>;
+    else kernel = nav_region_kernel<NAV_LDS_LARGE, 1024>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)grid->n_envs*r->n_fields)), dim3(threads), 0, (hipStream_t)stream, nav_args(grid),
+                       nav_region_args(grid, r));
+    return launch_status();
+}
+
+int ms_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* q, void* stream) {
+    const int status = nav_region_query_check(grid, q);
+    if (status != MS_OK) return status;
+    const long long total = (long long)grid->n_envs*q->n_points;
+    const NavRegionQueryArgs a{q->points, q->field, q->labels, q->labels_at, q->n_points, q->n_fields, total};
+    hipLaunchKernelGGL(nav_region_query_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), a);
+    return launch_status();
+}
+
+int ms_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* m, void* stream) {
+    const int status = nav_region_masks_check(grid, m);
+    if (status != MS_OK) return status;
+    if (grid->max_framed == 0) return MS_OK;                            // (no env has cells: nothing to write)
+    const long long runs = ((long long)grid->max_framed + WG - 1)/WG;  // (at least the largest env's cells; the kernel strides beyond)
+    const NavRegionMaskArgs a{m->points, m->wanted, m->field, m->labels, m->out, m->n_requests, m->n_fields};
+    hipLaunchKernelGGL(nav_region_mask_kernel, dim3((unsigned)((long long)grid->n_envs*m->n_requests), (unsigned)(runs < 4096 ? runs : 4096)), dim3(WG), 0,
+                       (hipStream_t)stream, nav_args(grid), a);
+    return launch_status();
+}
+
+int ms_host_nav_regions(const MsNavGrid* grid, const MsNavRegions* r) {
+    const int status = nav_regions_check(grid, r);
+    if (status != MS_OK) return status;
+    region_serial(nav_args(grid), nav_region_args(grid, r), nav_region_capacity_for(grid));
+    return MS_OK;
+}
+
+int ms_host_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* q) {
+    const int status = nav_region_query_check(grid, q);
+    if (status != MS_OK) return status;
+    const long long total = (long long)grid->n_envs*q->n_points;
+    const NavRegionQueryArgs a{q->points, q->field, q->labels, q->labels_at, q->n_points, q->n_fields, total};
+    for (long long at = 0; at < total; at++) region_query_one(nav_args(grid), a, at);
+    return MS_OK;
+}
+
+int ms_host_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* m) {
+    const int status = nav_region_masks_check(grid, m);
+    if (status != MS_OK) return status;
+    region_mask_serial(nav_args(grid), NavRegionMaskArgs{m->points, m->wanted, m->field, m->labels, m->out, m->n_requests, m->n_fields});
+    return MS_OK;
+}
+
+int ms_host_nav_region_capacity(int* capacities) {
+    if (!capacities) return MS_EINVAL;
+    capacities[0] = region_capacity(NAV_LDS_SMALL); capacities[1] = region_capacity(NAV_LDS_MEDIUM); capacities[2] = region_capacity(NAV_LDS_LARGE);
     return MS_OK;
 }
 

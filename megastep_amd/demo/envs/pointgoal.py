@@ -26,14 +26,18 @@ def books(before, now, reset, stranded, arrive, bonus):
 class PointGoal:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, arrive=.5, bonus=1., max_lifespan=512,
-                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, **kwargs):
+                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, **kwargs):
         """``cell``: the nav grid's cell size; ``arrive``: how near the goal counts as there, metres (walking distance);
         ``bonus``: the reward for arriving; ``max_lifespan``: episodes end after a random number of steps up to this
         (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`.
         ``goal_range=(lo, hi)``: goals drawn on the device at a walking distance of ``lo`` to ``hi`` metres from where the agent
         starts (:class:`~megastep_amd.modules.SampledGoals`) instead of from the spawn table; ``sampled_spawns=True``: spawns
         drawn on the device among the nav grid's free cells (:class:`~megastep_amd.modules.SampledSpawns`) instead of from a
-        table made on the host."""
+        table made on the host. ``one_region=True`` (with ``sampled_spawns``): the spawns are drawn in the env's largest connected
+        space only (:func:`~megastep_amd.cuda.regions` of the grid, once), so all agents of an env can reach one another and no
+        spawn lands in a closet."""
+        if one_region and not sampled_spawns:
+            raise RuntimeError('one_region gates the sampled spawns: it needs sampled_spawns=True')
         if geometries is None:
             geometries = cubicasa.sample(n_envs, workers=_plan_workers(), context='subprocess')
         self.core = core.Core(scene.scenery(geometries, n_agents, device=device), *args, res=4*64, fov=130, **kwargs)
@@ -47,8 +51,9 @@ class PointGoal:
         self._rgb = modules.RGB(c, subsample=4)
         self._depth = modules.Depth(c, subsample=4)
         self.grid = cuda.nav_grid(c.scenery, cell, config=c.config)
+        self.regions = cuda.regions(self.grid) if one_region else None
         if sampled_spawns:
-            self._respawner = modules.SampledSpawns(c, self.grid)
+            self._respawner = modules.SampledSpawns(c, self.grid, gate=self.regions.largest_mask() if one_region else None)
         if goal_range is not None:
             self._goals = modules.SampledGoals(c, self.grid, *goal_range)
         else:

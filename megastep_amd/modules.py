@@ -538,16 +538,18 @@ class SampledGoals:
 
 class SampledSpawns:
 
-    def __init__(self, core, grid, seed=0, within=None):
+    def __init__(self, core, grid, seed=0, within=None, gate=None):
         """Respawns agents on a cell of the nav grid drawn on the device by :func:`cuda.cell_draws` (no counterpart in the
         reference): :class:`RandomSpawns`' interface without its table. A spawn is the centre of a cell drawn uniformly among
         the env's free cells - every one of them a spot the agent fits, by the grid's own clearance - or, with ``within`` (a
         float32 layer, :func:`cuda.cell_layer`'s, one store an env or one per agent: a distance field from a reference point,
         say), among the free cells where it is finite: the cells of the same connected space as the reference. The heading is
         the draw's spare uniform number, ``uniforms*360 - 180``. Every agent draws for itself: two agents of an env may draw
-        the same cell, as they may in the reference's table. An agent of an env without a qualifying cell stays where it is."""
+        the same cell, as they may in the reference's table. An agent of an env without a qualifying cell stays where it is.
+        ``gate``: a byte layer (:meth:`cuda.Regions.largest_mask`, say: every agent of an env into the env's largest connected
+        space); only cells where its byte is set are drawn - a connectivity test as what it is, for no distance field at all."""
         self.core, self.grid, self.seed = core, grid, int(seed)
-        self._within = within
+        self._within, self._gate = within, gate
         self._choices = torch.zeros((core.n_envs, core.n_agents), dtype=torch.long, device=core.device)
         self._draws = None
 
@@ -559,11 +561,12 @@ class SampledSpawns:
         :meth:`RandomSpawns.draw`'s form: a table of one freshly drawn spawn per agent, ``choices`` all zero."""
         reset = reset.contiguous()
         if self._draws is None:
+            gate = {} if self._gate is None else dict(gate=self._gate)
             if self._within is None:
-                self._draws = cuda.cell_draws(self.grid, self.grid, self.core.n_agents, 1, seed=self.seed, mask=reset)
+                self._draws = cuda.cell_draws(self.grid, self.grid, self.core.n_agents, 1, seed=self.seed, mask=reset, **gate)
             else:
                 self._draws = cuda.cell_draws(self.grid, self._within, self.core.n_agents, 1, lo=-float('inf'), hi=torch.finfo(torch.float32).max,
-                                              seed=self.seed, mask=reset)
+                                              seed=self.seed, mask=reset, **gate)
         else:
             self._draws.again(mask=reset)
         d = self._draws

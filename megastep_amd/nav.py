@@ -1,7 +1,7 @@
 """Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
 floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
 they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``,
-``csrc/kernels/navdraw.h``). No counterpart in the reference;
+``csrc/kernels/navdraw.h``), and the connected regions of any per-cell mask (``csrc/kernels/navregion.h``). No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
@@ -490,6 +490,14 @@ class SeenMaps:
         a seed - nothing is left to see - is +inf throughout. ``mask``, ``out``, ``passes``: as :func:`seeded_fields`."""
         return seeded_fields(self.grid, self.values, self.n_maps, where=False, among=self.countable, mask=mask, out=out, passes=passes)
 
+    def frontier_regions(self, mask=None, out=None, passes=False):
+        """The clusters the countable cells each map has NOT seen fall into, as a :class:`Regions` of one field per map:
+        ``regions(grid, self.values, self.n_maps, where=False, among=self.countable)`` - :meth:`frontier_fields`' arguments, so a
+        frontier field's seeds are exactly the open cells here, and ``areas`` says how much unseen floor hangs together at each
+        of them: a sliver behind a pillar or a room. The regions read the maps by reference: :meth:`Regions.update` follows the
+        marks. ``mask``, ``out``, ``passes``: as :func:`regions`."""
+        return regions(self.grid, self.values, self.n_maps, where=False, among=self.countable, mask=mask, out=out, passes=passes)
+
 
 def seen_maps(grid, n_maps, countable=None):
     """``n_maps`` seen maps per env on the :func:`nav_grid`, all unseen: which cells of the floor the depth rays of an agent have
@@ -540,7 +548,8 @@ def cell_layer(values, n_fields=1, field=None):
     can be the source. ``field``: an (N, P) integer tensor naming the store each view reads; without it store 0 is read when
     ``n_fields`` is 1 and view p reads store p when ``n_fields`` is the number of views. A :class:`NavGrid` (its ``free``), a
     :class:`SeenMaps`, a :class:`DistanceFields` and a :class:`SeededFields` are layers as they are, with their own number of
-    stores; ``cell_layer(maps, field=slot)`` gives one of them a ``field``."""
+    stores, and so is a :class:`Regions` (its ``areas``, square metres); ``cell_layer(maps, field=slot)`` gives one of them a
+    ``field``."""
     if isinstance(values, CellLayer):
         values, n_fields = values.values, values.n_fields
     elif isinstance(values, NavGrid):
@@ -549,6 +558,8 @@ def cell_layer(values, n_fields=1, field=None):
         values, n_fields = values.values, values.n_maps
     elif isinstance(values, _Fields):
         values, n_fields = values.values, values.n_goals
+    elif isinstance(values, Regions):
+        values, n_fields = values.areas, values.n_fields
     if not isinstance(n_fields, int) or n_fields < 1:
         raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
     if not isinstance(values, torch.Tensor) or values.dtype not in (torch.uint8, torch.bool, torch.float32) or values.ndim != 1 or \
@@ -758,3 +769,188 @@ def cell_draws(grid, source, n_sets, n_draws, lo=None, hi=None, where=True, gate
                           new((n, n_sets), torch.int32, 0), new((n, n_sets), torch.int32, 0))
     draws._set(source, gate, where, lo, hi, seed)
     return draws.again(mask)
+
+
+#: the framed cells - ``(nx + 2)*(ny + 2)`` - an env may have for :func:`regions` to label it in LDS, for each of the kernel's three
+#: instantiations (40, 80 and 160 KiB); the launch is the least that holds the grid's largest env, and a larger env is labelled
+#: in global memory, to the same result
+REGION_CAPACITY = (10224, 20464, 40944)
+
+
+class Regions:
+    """Result of :func:`regions`: for each env ``G`` regions fields, field (n, g) labelling the connected components of its open
+    cells. ``labels``: the flat int32 store, field (n, g) at ``G*grid.starts[n] + g*nx*ny`` (the layout of
+    :class:`DistanceFields`) - the least row-major index, within the env, of an open cell of the cell's component, -1 on a closed
+    cell; ``areas``: the flat float32 store in the same layout - the component's area in square metres, 0 on a closed cell (a
+    layer: :func:`cell_layer` of a :class:`Regions` is this store); ``counts``, ``open_cells``, ``largest``, ``largest_cells``
+    (N, G) int32: the regions, the open cells, the label of the region with the most cells (the least on a tie, -1 without an
+    open cell) and its cells; ``passes`` (N, G) int32 or None. ``marks`` and ``among`` are kept by reference: :meth:`update`
+    sees them as they stand. The rule: include/megastep_hip.h (``MsNavRegions``), DESIGN.md 3.20."""
+
+    def __init__(self, grid, marks, n_fields, where, among, labels, areas, counts, open_cells, largest, largest_cells, passes=None):
+        self.grid, self.marks, self.where, self.among = grid, marks, bool(where), among
+        self.labels, self.areas, self.counts, self.open_cells = labels, areas, counts, open_cells
+        self.largest, self.largest_cells, self.passes = largest, largest_cells, passes
+        self._n_fields = int(n_fields)
+
+    n_fields = property(lambda self: self._n_fields)
+
+    def _view(self, store, e, g):
+        s, ny, nx = self.grid.cells(e)
+        at = self.n_fields*s + g*ny*nx
+        return store[at:at + ny*nx].reshape(ny, nx)
+
+    def image(self, e, g=0):
+        """(ny, nx) int32 view of the labels of field ``g`` of env ``e``, row 0 at the lowest y."""
+        return self._view(self.labels, e, g)
+
+    def area_image(self, e, g=0):
+        """(ny, nx) float32 view of the areas of field ``g`` of env ``e``, row 0 at the lowest y."""
+        return self._view(self.areas, e, g)
+
+    def update(self, mask=None):
+        """Labels the fields marked in the (N, G) bool ``mask`` (default all) again in place, from :attr:`marks` and
+        :attr:`among` as they stand now; the others keep labels, areas and summary. One launch, no host synchronisation, nothing
+        allocated: the call can be captured in a HIP graph."""
+        grid, g = self.grid, self.n_fields
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, g):
+                raise RuntimeError(f'mask must be an (N, G) = ({grid.n_envs}, {g}) bool tensor')
+            mask = mask.contiguous()
+        dev = _require_gpu(self.labels, self.areas, self.counts, self.open_cells, self.largest, self.largest_cells, grid.free,
+                           *(t for t in (self.marks, self.among, mask, self.passes) if t is not None))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        spec = _lib.MsNavRegions(g, ptr(self.marks), int(self.where), ptr(self.among), ptr(mask), self.labels.data_ptr(), self.areas.data_ptr(),
+                                 self.counts.data_ptr(), self.open_cells.data_ptr(), self.largest.data_ptr(), self.largest_cells.data_ptr(),
+                                 ptr(self.passes))
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_regions(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return self
+
+    def _requests(self, n, p, field, *tensors):
+        """The argument rules of a query's or a request's ``field``: (field as int32 or None, device)."""
+        if field is None:
+            if self.n_fields not in (1, p):
+                raise RuntimeError(f'without field, there must be one regions field per env or one per point ({p}); there are {self.n_fields}')
+        else:
+            if not isinstance(field, torch.Tensor) or field.dtype.is_floating_point or field.dtype == torch.bool or field.shape != (n, p):
+                raise RuntimeError(f'field must be an (N, P) = ({n}, {p}) integer tensor')
+            field = field.to(torch.int32).contiguous()
+        return field, _require_gpu(*tensors, self.labels, self.grid.free, *([field] if field is not None else []))
+
+    def _points(self, points, name='points'):
+        _check(points, name, torch.float32, 3)
+        n, p = points.shape[:2]
+        if n != self.grid.n_envs or points.shape[2] != 2 or p < 1:
+            raise RuntimeError(f'{name} must be (N, P, 2) with N = {self.grid.n_envs}; got {tuple(points.shape)}')
+        return n, p
+
+    def labels_at(self, points, field=None):
+        """(N, P, 4) int32: the label under each of the four cells round each of ``points`` (N, P, 2) - the anchors of
+        :meth:`DistanceFields.at`, in its order - and -1 where that cell is outside the grid or closed. ``field`` (N, P) integers
+        name the regions field each point asks; default the one field, or point k field k (then P must be G). All -1 for a NaN
+        point, a point far from the grid, an env without cells and a field index out of range. One launch, no host
+        synchronisation."""
+        n, p = self._points(points)
+        field, dev = self._requests(n, p, field, points)
+        out = torch.empty((n, p, 4), dtype=torch.int32, device=dev)
+        spec = _lib.MsNavRegionQuery(p, points.data_ptr(), field.data_ptr() if field is not None else None, self.labels.data_ptr(),
+                                     self.n_fields, out.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_region_query(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        return out
+
+    def at(self, points, field=None):
+        """(N, P) int32: the region each of ``points`` stands in - the least non-negative label of :meth:`labels_at`, -1 without
+        one."""
+        found = self.labels_at(points, field)
+        top = torch.iinfo(torch.int32).max
+        least = torch.where(found < 0, torch.full_like(found, top), found).amin(-1)
+        return torch.where(least == top, torch.full_like(least, -1), least)
+
+    def together(self, a, b, field=None):
+        """(N, P) bool: can one walk from ``a[n, k]`` to ``b[n, k]`` (both (N, P, 2)) - does some anchor of the one share a label
+        with some anchor of the other. On the regions of the grid itself this is exactly where :func:`geodesic` is finite, for
+        two launches of a lane a point instead of a distance field a pair."""
+        la, lb = self.labels_at(a, field), self.labels_at(b, field)
+        return ((la[..., :, None] == lb[..., None, :]) & (la[..., :, None] >= 0)).any(-1).any(-1)
+
+    def masks(self, points=None, labels=None, field=None, out=None):
+        """Byte masks of chosen regions, as a :class:`CellLayer` of ``P`` stores per env (store (n, p) at
+        ``P*grid.starts[n] + p*nx*ny``): a byte is 1 on the cells of the regions request (n, p) wants. Exactly one of ``points``
+        (N, P, 2) float32 - the regions under the point's four anchors: where one can walk to from there - and ``labels`` (N, P)
+        integers - that one region; -1 wants none - is given. ``field``: as :meth:`labels_at`. ``out``: the layer of an earlier call
+        with the same P to write into; every byte is written, so it needs no clearing. With P = 1 the layer has ``grid.free``'s
+        layout: :func:`seeded_fields`' ``among`` and :func:`seen_maps`' ``countable`` take its ``values``, and
+        :func:`cell_draws` and :func:`map_channel` take it as a ``gate`` or a source, as it is. One launch, no host
+        synchronisation."""
+        if (points is None) == (labels is None):
+            raise RuntimeError('exactly one of points and labels must be given')
+        grid = self.grid
+        if points is not None:
+            n, p = self._points(points)
+            given = points
+        else:
+            if not isinstance(labels, torch.Tensor) or labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.ndim != 2 or \
+                    labels.shape[0] != grid.n_envs or labels.shape[1] < 1:
+                raise RuntimeError(f'labels must be an (N, P) integer tensor with N = {grid.n_envs}')
+            n, p = labels.shape
+            given = labels = labels.to(torch.int32).contiguous()
+        field, dev = self._requests(n, p, field, given)
+        size = max(p*grid.n_cells, 1)
+        if out is None:
+            out = CellLayer(torch.zeros(size, dtype=torch.uint8, device=dev), p, None)
+        elif not isinstance(out, CellLayer) or out.is_float or out.n_fields != p or out.values.shape[0] != size or out.values.device != dev:
+            raise RuntimeError(f'`out` must be the layer of a masks call with the same grid and P = {p}')
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        spec = _lib.MsNavRegionMasks(p, ptr(points), ptr(labels), ptr(field), self.labels.data_ptr(), self.n_fields, out.values.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_region_masks(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return out
+
+    def largest_mask(self, out=None):
+        """The byte mask of every env's largest region, ``grid.free``'s layout: ``masks(labels=self.largest[:, :1])``. One regions
+        field per env only."""
+        if self.n_fields != 1:
+            raise RuntimeError(f'largest_mask is for one regions field per env; there are {self.n_fields}: use masks(labels=..., field=...)')
+        return self.masks(labels=self.largest[:, :1], out=out)
+
+
+def regions(grid, marks=None, n_fields=1, where=True, among=None, mask=None, out=None, passes=False):
+    """The connected regions of the :func:`nav_grid`: which cells belong together. Without ``marks`` the open cells are the grid's
+    free cells, and two cells share a label exactly when one can walk from one to the other - where a :func:`distance_fields`
+    field of the one is finite on the other (the diagonal steps of the fields' graph join nothing its straight steps do not:
+    DESIGN.md 3.20). With ``marks``, ``n_fields``, ``where`` and ``among`` - :func:`seeded_fields`' arguments, by its rules - the open
+    cells of field (n, g) are the cells that would be its seeds: the unseen floor of a seen map falls into clusters
+    (:meth:`SeenMaps.frontier_regions`). Open cells are joined to their open 4-neighbours; a cell's label is the least row-major
+    index within its env of an open cell of its component, its area the component's cells times ``cell**2``; see
+    :class:`Regions`.
+
+    One launch, one workgroup per field: min-label propagation with pointer jumping in LDS, until nothing changes; the labels are
+    canonical, so the result does not depend on the schedule (include/megastep_hip.h, ``MsNavRegions``).
+
+    ``mask`` (N, G) bool: label only the marked fields (the others keep what ``out`` held; no open cell without ``out``);
+    ``out``: the :class:`Regions` of an earlier call with the same grid, marks and arguments to write into; ``passes=True`` also
+    records the passes each field took. No host synchronisation: the call can be captured in a HIP graph."""
+    if not isinstance(n_fields, int) or n_fields < 1:
+        raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
+    if marks is not None:
+        marks = _cell_bytes(marks, 'marks', max(n_fields*grid.n_cells, 1), f'a byte per cell and field (n_fields*n_cells = {n_fields}*{grid.n_cells})')
+    if among is not None:
+        if marks is None:
+            raise RuntimeError('among goes with marks: without marks the open cells are the free cells')
+        among = _cell_bytes(among, 'among', grid.free.shape[0], 'one per cell of the grid')
+    where = bool(where)
+    same = lambda a, b: (a is None) == (b is None) and (a is None or a.data_ptr() == b.data_ptr())
+    if out is not None:
+        if not isinstance(out, Regions) or out.grid is not grid or out.n_fields != n_fields or out.where != where or \
+                not same(out.marks, marks) or not same(out.among, among):
+            raise RuntimeError('`out` must come from a regions call with the same grid, marks, n_fields, where and among')
+        return out.update(mask)
+    dev = _require_gpu(grid.free, *(t for t in (marks, among) if t is not None))
+    size, shape = max(n_fields*grid.n_cells, 1), (grid.n_envs, n_fields)
+    new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)
+    result = Regions(grid, marks, n_fields, where, among, new((size,), torch.int32, -1), new((size,), torch.float32, 0.),
+                     new(shape, torch.int32, 0), new(shape, torch.int32, 0), new(shape, torch.int32, -1), new(shape, torch.int32, 0),
+                     new(shape, torch.int32, 0) if passes else None)
+    return result.update(mask)

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -41,6 +41,14 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       hash in int64 tensor ops and a searchsorted; the first `--torch-envs` envs, scaled; its cells compared with the kernel's);
       PointGoal(envs, goal_range=(2., 8.), sampled_spawns=True).step eager and replayed as a HIP graph, next to the plain
       PointGoal(envs).step.
+  (r) the regions, at `--envs` envs x 1 agent, the maximum and median `passes` reported for every regions call: one cuda.regions
+      (ms_nav_regions) of the grid next to floorcoverage.reachable() on the same grid - the single-goal field launch it
+      replaces - with Regions.masks(points=) of the same point compared with reachable()'s mask as bytes; the torch formulation
+      of min-label propagation (the grids padded to the largest plan, four shifted minimums a sweep, swept until nothing
+      changes, checked every 16 sweeps; the first `--torch-envs` envs, scaled; labels compared for equality);
+      SeenMaps.frontier_regions right after one marked frame, and with 80 % seen; one Regions.masks call;
+      PointGoal(envs, goal_range=(2., 8.), sampled_spawns=True, one_region=True).step eager and replayed as a HIP graph, next
+      to the same env without one_region.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -127,6 +135,41 @@ def torch_fields(grid, goals, envs):
                 sweeps += 1
             if torch.equal(D, before):
                 return D, sweeps
+    return run
+
+
+def torch_regions(grid, envs):
+    """The labels of the first `envs` envs' free cells by tensor ops: (envs, H, W) int32 padded to the largest grid, a frame of closed
+    cells round each; a cell's label is its own row-major index within its env; min over the four shifts until nothing changes."""
+    geom = grid._host_geom[:envs]
+    H, W = int(geom[:, 3].max()) + 2, int(geom[:, 2].max()) + 2
+    dev = grid.free.device
+    top = torch.iinfo(torch.int32).max
+    free = torch.zeros((envs, H, W), dtype=torch.bool, device=dev)
+    own = torch.full((envs, H, W), top, dtype=torch.int32, device=dev)
+    for e in range(envs):
+        s, ny, nx = grid.cells(e)
+        free[e, 1:ny + 1, 1:nx + 1] = grid.free[s:s + ny*nx].reshape(ny, nx).bool()
+        own[e, 1:ny + 1, 1:nx + 1] = torch.arange(ny*nx, dtype=torch.int32, device=dev).reshape(ny, nx)
+    start = torch.where(free, own, torch.full_like(own, top))
+
+    def shifted(t, di, dj):
+        out = torch.full_like(t, top)
+        out[:, max(di, 0):H + min(di, 0), max(dj, 0):W + min(dj, 0)] = t[:, max(-di, 0):H + min(-di, 0), max(-dj, 0):W + min(-dj, 0)]
+        return out
+
+    def run():
+        L, sweeps = start, 0
+        while True:
+            before = L
+            for _ in range(16):
+                new = L
+                for di, dj in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+                    new = torch.minimum(new, shifted(L, di, dj))
+                L = torch.where(free, new, start)
+                sweeps += 1
+            if torch.equal(L, before):
+                return torch.where(free, L, torch.full_like(L, -1)), sweeps
     return run
 
 
@@ -327,7 +370,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
@@ -591,6 +634,59 @@ def main():
             eager, graphed = env_rates(env, args.envs, 60, 10)
             out[name] = dict(eager_seconds=eager, graph_seconds=graphed)
             print(f'(d) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+
+    if want('regions'):
+        from megastep_amd.demo.envs.floorcoverage import reachable
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        passes = lambda r: dict(passes_most=int(r.passes.max()), passes_median=int(r.passes.median()))
+        r = cuda.regions(grid, passes=True)
+        med, lo, hi = timed(lambda: r.update(), args.repeats, args.warmup)
+        spawn = table[:, 0, 0].contiguous()
+        rmed, rlo, rhi = timed(lambda: reachable(grid, spawn), args.repeats, args.warmup)
+        layer = r.masks(points=spawn[:, None].contiguous())
+        same = bool(torch.equal(layer.values[:grid.n_cells], reachable(grid, spawn)[:grid.n_cells]))
+        out['regions'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, regions_mean=float(r.counts.float().mean()), regions_most=int(r.counts.max()),
+                              reachable_seconds=rmed, reachable_min=rlo, reachable_max=rhi, mask_equal_bytes=same, **passes(r))
+        print(f"(r) regions, {args.envs} grids: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; {out['regions']}")
+        batch = 20
+
+        def calls():
+            for _ in range(batch):
+                r.masks(points=spawn[:, None], out=layer)
+        mmed, mlo, mhi = (t/batch for t in timed(calls, args.repeats, args.warmup))
+        out['region_masks'] = dict(seconds=mmed, min=mlo, max=mhi, requests=args.envs, bytes=int(grid.n_cells))
+        print(f'(r) masks, {args.envs} x 1 requests, {grid.n_cells/1e6:.1f} MB out: {mmed*1e6:.1f} us [{mlo*1e6:.1f}, {mhi*1e6:.1f}] a call ({batch} back to back)')
+        k = min(args.torch_envs, args.envs)
+        run = torch_regions(grid, k)
+        L, sweeps = run()
+        same = all(torch.equal(L[e, 1:grid.cells(e)[1] + 1, 1:grid.cells(e)[2] + 1], r.image(e)) for e in range(k))
+        tmed = timed(lambda: run(), max(args.repeats//3, 2), 1)[0]
+        out['regions_torch'] = dict(envs=k, seconds=tmed, scaled_seconds=tmed*args.envs/k, sweeps=sweeps, equal_labels=bool(same))
+        print(f'(r) torch min-label sweeps, {k} grids: {tmed*1e3:.1f} ms, {sweeps} sweeps -> {tmed*args.envs/k*1e3:.1f} ms for {args.envs}; equal labels: {same}')
+        maps = cuda.seen_maps(grid, 1, reachable(grid, spawn))
+        maps.mark_render(c.agents, cuda.render(sc, c.agents, fields=('distances',)))
+        fr = maps.frontier_regions(passes=True)
+        med, lo, hi = timed(lambda: fr.update(), args.repeats, args.warmup)
+        out['frontier_regions_first_frame'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, regions_mean=float(fr.counts.float().mean()), **passes(fr))
+        print(f"(r) frontier_regions, {args.envs} maps after one frame: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; {out['frontier_regions_first_frame']}")
+        maps.values.copy_((torch.rand(maps.values.shape, device='cuda') >= .2).to(torch.uint8))
+        med, lo, hi = timed(lambda: fr.update(), args.repeats, args.warmup)
+        out['frontier_regions_80_percent'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, regions_mean=float(fr.counts.float().mean()), **passes(fr))
+        print(f"(r) frontier_regions, {args.envs} maps 80 % seen: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; {out['frontier_regions_80_percent']}")
+        del sc, c, grid, maps, fr, r, layer
+        torch.cuda.empty_cache()
+        for name, extra in (('PointGoal_one_region', dict(one_region=True)), ('PointGoal_sampled', dict())):
+            env = PointGoal(args.envs, geometries=geoms, goal_range=(2., 8.), sampled_spawns=True, **extra)
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[name] = dict(eager_seconds=eager, graph_seconds=graphed)
+            print(f'(r) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
             del env
             torch.cuda.empty_cache()
 
