@@ -818,6 +818,62 @@ int ms_nav_regions(const MsNavGrid* grid, const MsNavRegions* regions, void* hip
 int ms_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* query, void* hip_stream);
 int ms_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* masks, void* hip_stream);
 
+/* View fields: what can be seen from a place - the cells of the nav grid whose centre is in sight of a viewpoint, how many of them
+ * count, and how many of those a seen map has not seen yet: the score of a candidate standpoint, the cells an opponent at p sees.
+ * Every step below is one binary32 operation, in the order given, without contraction; tests/test_navview_host.py restates it in
+ * numpy (view_rule) and the kernel - and its host instantiation, ms_host_nav_views - is held to EQUALITY with it.  c, geom and
+ * starts are MsNavGrid's.  P viewpoints per env; for viewpoint (px, py) = points[n, p] and cell (i, j) of env n:
+ *   centre        x = ((float)(jx0 + j) + 0.5f)*c, y = ((float)(iy0 + i) + 0.5f)*c - MsNavGrid's.
+ *   range         rx = x - px, ry = y - py, rr = rx*rx + ry*ry; in range iff rr <= R2, R2 = max_range*max_range formed once.
+ *   cone          with headings (hx, hy) = headings[n, p]: hlen = sqrtf(hx*hx + hy*hy); a viewpoint whose hlen is not finite or not
+ *                 > 0 sees nothing; len = sqrtf(rr), dotp = hx*rx + hy*ry, lim = (cos_half*len)*hlen; in the cone iff dotp >= lim
+ *                 (a cell whose centre is the viewpoint is in every cone).
+ *   a wall        is a row (ax, ay, bx, by) of the env's STATIC lines (rows n_agents*n_model .. L - 1 of the env in
+ *                 MsScenery.lines_vals: the rows ms_nav_free reads).  It blocks the cell iff all three hold:
+ *                 meets   min(ax, bx) <= max(px, x) && max(ax, bx) >= min(px, x), and the same in y (comparisons only: any cull
+ *                         of far walls consistent with it is bit-safe);
+ *                 apart   vx = bx - ax, vy = by - ay, o1 = vx*(py - ay) - vy*(px - ax), o2 = vx*(y - ay) - vy*(x - ax):
+ *                         (o1 < 0 && o2 > 0) || (o1 > 0 && o2 < 0) - viewpoint and centre strictly on opposite sides of the wall's line;
+ *                 across  o3 = rx*(ay - py) - ry*(ax - px), o4 = rx*(by - py) - ry*(bx - px):
+ *                         (o3 <= 0 && o4 >= 0) || (o3 >= 0 && o4 <= 0) - the wall's ends on opposite sides of the sight line, zero
+ *                         included, so that a sight line through the vertex two walls share is blocked.
+ *                 A wall with a NaN fails a comparison of `apart` and blocks nothing.
+ *   visible       iff px and py are finite, the cell is in range, in the cone if one is given, and no static wall blocks it.  The
+ *                 agents' own lines are not looked at: the grid is the building.
+ *   values        store (n, p) holds 1 on visible cells and 0 on all others, for EVERY cell of the env, free or not (a blocked cell on
+ *                 the viewer's side of a wall is a known obstacle), in the seen maps' layout: store (n, p) at P*starts[n] + p*nx*ny,
+ *                 row-major, row 0 at the lowest y.  Every byte of a computed store is written: it needs no clearing.  A byte a
+ *                 cell: ms_nav_seed_fields' marks, ms_nav_regions' marks, an MsNavLayer as it is.
+ *   counts        counts[n, p] = the visible cells whose countable byte has bit 0 set (countable: free_cells' layout; required).
+ *   gains         with unseen (the byte store of seen maps, S = n_maps per env: map (n, s) at S*starts[n] + s*nx*ny) and slot (N, P)
+ *                 (NULL: map p when P == S, map 0 when S == 1): gains[n, p] = the visible countable cells whose byte in map
+ *                 slot[n, p] has bit 0 clear; 0 for a slot outside 0 .. S - 1.
+ *   mask          (N, P) bytes: a viewpoint marked 0 keeps its bytes, its count and its gain untouched.
+ *   no cells      an env without cells: counts and gains 0, nothing stored.
+ * Refused before any launch (MS_EINVAL): P < 1; a NULL points or countable; no output at all (values, counts and gains all NULL);
+ * max_range not positive and finite; cos_half outside [-1, 1] (or a NaN) when headings is given; gains without unseen; unseen with
+ * S < 1, or without slot when S is neither 1 nor P; points or headings not 8-byte aligned; a scenery of another number of envs.
+ * One launch, one workgroup per viewpoint: the walls whose box meets the box of everything in range are staged in LDS (more than
+ * 512 of them: read from the scenery instead, same result), a lane a cell of the window round the viewpoint.  With values == NULL no
+ * byte is written: scoring needs no store.  Integer counts with one writer each, no atomics, nothing allocated, nothing waits: the
+ * call can be captured in a HIP graph. */
+typedef struct MsNavViews {
+    int                  n_points;     /* P: viewpoints per env                                                         */
+    const float*         points;       /* (N, P, 2) x, y; 8-byte aligned                                                */
+    const float*         headings;     /* (N, P, 2) any length, or NULL: no cone; 8-byte aligned                        */
+    float                max_range;    /* R, metres (> 0, finite)                                                       */
+    float                cos_half;     /* the cosine of half the cone's angle, in [-1, 1] (with headings)               */
+    const unsigned char* countable;    /* (starts[N],) bit 0: the cell counts                                           */
+    const unsigned char* unseen;       /* S*starts[N] bytes, bit 0: seen; NULL: no gains                                */
+    int                  n_maps;       /* S of `unseen`                                                                 */
+    const int*           slot;         /* (N, P) the map each viewpoint is scored against; NULL: S == 1 or S == P       */
+    const unsigned char* mask;         /* (N, P) non-zero: compute this viewpoint; NULL: all.  Read on the device only. */
+    unsigned char*       values;       /* P*starts[N] bytes out, or NULL                                                */
+    int*                 counts;       /* (N, P) out, or NULL                                                           */
+    int*                 gains;        /* (N, P) out, or NULL                                                           */
+} MsNavViews;
+int ms_nav_views(const MsScenery* scenery, const MsNavGrid* grid, const MsNavViews* views, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

@@ -115,6 +115,15 @@ int ms_host_nav_regions(const MsNavGrid* grid, const MsNavRegions* regions);
 int ms_host_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* query);
 int ms_host_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* masks);
 int ms_host_nav_region_capacity(int* capacities);
+/* Host instantiation of the view fields' rule (kernels/navview.h: view_in_range, view_in_cone, view_wall_blocks, the window and the
+ * wall cull - the very functions every lane of nav_view_kernel evaluates) for one whole call of ms_nav_views on HOST arrays, swept
+ * serially: every pointer of `grid` and of `views` is host memory, and in place of an MsScenery `walls` holds the STATIC rows of all
+ * envs, four floats each, env n's rows wall_starts[n] .. wall_starts[n + 1] - 1.  It goes through the kernel's window and cull, and
+ * through both wall paths: a viewpoint that keeps more than `capacity` rows (0: the kernel's, ms_host_nav_view_capacity(); a smaller
+ * one lets a test reach the other path with few walls) sweeps all its env's rows instead of the staged ones.  Returns what
+ * ms_nav_views would: MS_OK, or MS_EINVAL for arguments it would refuse (and for a capacity above the kernel's). */
+int ms_host_nav_views(const MsNavGrid* grid, const MsNavViews* views, const float* walls, const long long* wall_starts, int capacity);
+int ms_host_nav_view_capacity(void);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

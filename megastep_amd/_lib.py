@@ -173,6 +173,12 @@ class MsNavRegionMasks(C.Structure):
                 ('n_fields', C.c_int), ('out', C.c_void_p)]
 
 
+class MsNavViews(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('headings', C.c_void_p), ('max_range', C.c_float), ('cos_half', C.c_float),
+                ('countable', C.c_void_p), ('unseen', C.c_void_p), ('n_maps', C.c_int), ('slot', C.c_void_p), ('mask', C.c_void_p),
+                ('values', C.c_void_p), ('counts', C.c_void_p), ('gains', C.c_void_p)]
+
+
 _int, _flt, _ptr, _p = C.c_int, C.c_float, C.c_void_p, C.POINTER
 
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare, as
@@ -206,6 +212,7 @@ PROTOTYPES = {
     'ms_nav_regions': (_int, [_p(MsNavGrid), _p(MsNavRegions), _ptr]),
     'ms_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery), _ptr]),
     'ms_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks), _ptr]),
+    'ms_nav_views': (_int, [_p(MsScenery), _p(MsNavGrid), _p(MsNavViews), _ptr]),
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
     'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
     'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
@@ -239,6 +246,8 @@ PROTOTYPES = {
     'ms_host_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery)]),
     'ms_host_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks)]),
     'ms_host_nav_region_capacity': (_int, [_ptr]),
+    'ms_host_nav_views': (_int, [_p(MsNavGrid), _p(MsNavViews), _ptr, _ptr, _int]),
+    'ms_host_nav_view_capacity': (_int, []),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),

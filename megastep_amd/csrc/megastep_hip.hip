@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navregion.h, navpath.h, navseen.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navregion.h, navview.h, navpath.h, navseen.h, navwindow.h, navdraw.h.
 //
-// Twenty-three kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Twenty-four kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -61,6 +61,9 @@
 //                                                            (no counterpart)
 //   nav_draw_kernel     cell draws: one workgroup per draw set ballots the env's qualifying cells into an LDS bitmap, scans the
 //                   popcounts and picks each draw's cell by rank, from a hash of a counter it moves on itself.
+//                                                            (no counterpart)
+//   nav_view_kernel     view fields: one workgroup per viewpoint culls the env's static walls into LDS and tests the centre of
+//                   every cell in range against them, a lane a cell: the cells in sight, how many count, how many are new.
 //                                                            (no counterpart)
 //   explorer_kernel    the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
@@ -162,6 +165,7 @@ struct Probe {
 #include "kernels/overhead.h"
 #include "kernels/navfield.h"
 #include "kernels/navregion.h"
+#include "kernels/navview.h"
 #include "kernels/navpath.h"
 #include "kernels/navseen.h"
 #include "kernels/navwindow.h"
@@ -1236,6 +1240,41 @@ int ms_host_nav_region_capacity(int* capacities) {
     capacities[0] = region_capacity(NAV_LDS_SMALL); capacities[1] = region_capacity(NAV_LDS_MEDIUM); capacities[2] = region_capacity(NAV_LDS_LARGE);
     return MS_OK;
 }
+
+// View fields (navview.h): the same discipline.  An env of more than 2^30 cells cannot be (MsNavGrid's geom is 32768 a side at most
+// in cuda.nav_grid; here it is max_framed, an int, that bounds it).
+static int nav_views_check(const MsNavGrid* grid, const MsNavViews* v) {
+    if (!nav_grid_ok(grid) || !v || v->n_points < 1 || !v->points || !v->countable || (!v->values && !v->counts && !v->gains) ||
+        !(v->max_range > 0.f) || !(v->max_range < INFINITY) || (v->headings && !(v->cos_half >= -1.f && v->cos_half <= 1.f)) ||
+        (v->gains && !v->unseen) || (v->unseen && v->n_maps < 1) ||
+        (v->unseen && !v->slot && v->n_maps != 1 && v->n_maps != v->n_points) || ((uintptr_t)v->points % 8) || ((uintptr_t)v->headings % 8) ||
+        ((uintptr_t)v->slot % 4) || ((uintptr_t)v->counts % 4) || ((uintptr_t)v->gains % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*v->n_points > 0x7fffffffLL || grid->max_framed > (1 << 30)) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static NavViewArgs nav_view_args(const MsNavViews* v, const int capacity) {
+    return NavViewArgs{v->points, v->headings, v->mask, v->countable, v->unseen, v->unseen ? v->slot : nullptr, v->values, v->counts, v->gains,
+                       v->n_points, v->unseen ? v->n_maps : 0, capacity, v->max_range, v->max_range*v->max_range, v->headings ? v->cos_half : 0.f};
+}
+
+int ms_nav_views(const MsScenery* sc, const MsNavGrid* grid, const MsNavViews* v, void* stream) {
+    if (!scenery_ok(sc) || !nav_grid_ok(grid) || grid->n_envs != sc->n_envs) return MS_EINVAL;
+    const int status = nav_views_check(grid, v);
+    if (status != MS_OK) return status;
+    hipLaunchKernelGGL(nav_view_kernel, dim3((unsigned)((long long)grid->n_envs*v->n_points)), dim3(WG), 0, (hipStream_t)stream, *sc, nav_args(grid),
+                       nav_view_args(v, VIEW_WALL_CAPACITY));
+    return launch_status();
+}
+
+int ms_host_nav_views(const MsNavGrid* grid, const MsNavViews* v, const float* walls, const long long* wall_starts, int capacity) {
+    const int status = nav_views_check(grid, v);
+    if (status != MS_OK) return status;
+    if (!walls || !wall_starts || capacity > VIEW_WALL_CAPACITY) return MS_EINVAL;
+    view_serial(nav_args(grid), nav_view_args(v, capacity > 0 ? capacity : VIEW_WALL_CAPACITY), reinterpret_cast<const float4*>(walls), wall_starts);
+    return MS_OK;
+}
+
+int ms_host_nav_view_capacity(void) { return VIEW_WALL_CAPACITY; }
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {
     (void)cfg;

@@ -55,6 +55,7 @@ class FloorCoverage:
         self._episodes = torch.zeros((c.n_envs, c.n_agents), dtype=torch.long, device=c.device)
         self._fresh = c.agent_full(False)               # who started over since the expert was last asked
         self._frontiers = self._follower = None         # made when the expert is first asked: they cost nothing until then
+        self._views = self._views_follower = None
 
     #: the :class:`~megastep_amd.cuda.SeenMaps`
     maps = property(lambda self: self._coverage.maps)
@@ -94,12 +95,23 @@ class FloorCoverage:
         return self._world(over)
 
     @torch.no_grad()
-    def expert(self):
+    def expert(self, kind='frontier'):
         """``arrdict(actions=(n_env, n_agent))``: what the frontier follower does in the current state - every agent towards the
         waypoint of the nearest floor its map has not seen (:class:`~megastep_amd.modules.Frontiers` under a
         :class:`~megastep_amd.modules.PathFollower`); nothing (0) where nothing is left to see. Nothing waits for the host:
         ``env.step(env.expert())`` can sit in one graph, once a first call outside it has made the fields. The fields are
-        refreshed, and the follower counts the steps an agent has been stuck, on every call: ask once per step."""
+        refreshed, and the follower counts the steps an agent has been stuck, on every call: ask once per step.
+        ``kind='views'``: the next-best-view follower instead - every agent towards the candidate standpoint that would reveal
+        the most unseen floor per metre walked (:class:`~megastep_amd.modules.BestViews`); ask one kind per step."""
+        if kind == 'views':
+            if self._views is None:
+                self._views = modules.BestViews(self.core, self._coverage)
+                self._views_follower = modules.PathFollower(self.core, self._views, cone=15.)
+            self._views(self._fresh)
+            self._fresh.zero_()
+            return self._views_follower()
+        if kind != 'frontier':
+            raise RuntimeError(f"kind must be 'frontier' or 'views'; got {kind!r}")
         if self._frontiers is None:
             self._frontiers = modules.Frontiers(self.core, self._coverage)
             self._follower = modules.PathFollower(self.core, self._frontiers, cone=15.)

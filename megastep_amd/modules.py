@@ -688,6 +688,7 @@ class Frontiers:
             self._steps.masked_fill_(reset, 0)
         due = self._steps % self.refresh == 0
         self._steps += 1
+        self.due = due                                  # ((n_env, n_agent) bool: whose field was due at this call)
         if self.coverage.shared:
             due = due.any(-1, keepdim=True)
         self.fields.update(due)
@@ -703,10 +704,108 @@ class Frontiers:
         return self.fields.waypoints(self.core.agents.positions, goal=self._field, lookahead=lookahead)
 
 
+class BestViews:
+
+    def __init__(self, core, coverage, n_candidates=16, max_range=None, band=(.25, 3.), refresh=8, seed=0):
+        """Next-best-view goals over a :class:`Coverage` (no counterpart in the reference): :class:`Frontiers`' interface - so
+        :class:`PathFollower` takes it unchanged - with a goal chosen by what standing there would REVEAL instead of the nearest
+        unseen cell, be that a sliver behind a pillar or the doorway of an unseen room. It holds a :class:`Frontiers` of the same
+        coverage, and for the agents that are due by its device-side rule (every ``refresh`` steps, and when they start over):
+
+        * draws ``n_candidates`` cells within ``band`` metres (walking) of floor the agent's map has not seen -
+          :func:`cuda.cell_draws` on the frontier field with ``lo`` and ``hi`` - so every candidate is reachable from unseen floor
+          that counts, hence from the agent;
+        * measures the walk to each with a masked :func:`cuda.distance_fields` round the agents and its ``at``;
+        * scores each by :func:`cuda.view_fields` ``(..., unseen=coverage.maps, slot=..., store=False).gains``: the countable cells
+          in sight of it, within ``max_range`` (default the coverage's), that the agent's map lacks;
+        * takes a masked :func:`cuda.distance_fields` of the goal :meth:`choose` picks.
+
+        An agent without a candidate worth walking to follows its frontier field, as under :class:`Frontiers`. Nothing waits for
+        the host: everything is driven by masks, so a call can sit in a HIP graph once a first call outside it has made the
+        tensors."""
+        self.core, self.coverage = core, coverage
+        self.n_candidates, self.seed = int(n_candidates), int(seed)
+        self.max_range = float(coverage.max_range if max_range is None else max_range)
+        self.band = (float(band[0]), float(band[1]))
+        from .nav import DRAW_MAX_DRAWS
+        if not 1 <= self.n_candidates <= DRAW_MAX_DRAWS:
+            raise RuntimeError(f'n_candidates must be in 1..{DRAW_MAX_DRAWS}; got {n_candidates}')
+        if not 0 <= self.band[0] <= self.band[1]:
+            raise RuntimeError(f'the band must be 0 <= lo <= hi; got {band}')
+        self.frontiers = Frontiers(core, coverage, refresh)
+        n, a, k = core.n_envs, core.n_agents, self.n_candidates
+        agent = torch.arange(a, dtype=torch.int32, device=core.device)[None, :, None].expand(n, a, k).reshape(n, -1).contiguous()
+        self._agent = agent                             # (n_env, n_agent*K): the agent - its field, its map - of each candidate
+        self._slot = torch.zeros_like(agent) if coverage.shared else agent
+        self._goal = core.agents.positions.clone()
+        #: (n_env, n_agent) bool: the agent found no candidate with a finite walk and a positive gain, and follows the frontier
+        self.none = core.agent_full(True)
+        self._draws = self._around = self._views = self._fields = None
+        self.gains = self.distances = None
+
+    #: (n_env, n_agent, 2): every agent's goal (where :attr:`none`: the spot it stood on when it found none)
+    goals = property(lambda self: self._goal)
+    #: (n_env, n_agent, K, 2): the candidates of the last draw of every agent (NaN where its band held no cell)
+    candidates = property(lambda self: self._draws.points)
+    #: the :class:`cuda.DistanceFields` of the goals
+    fields = property(lambda self: self._fields)
+
+    @staticmethod
+    def choose(gains, distances, d0=1.):
+        """The rule, a pure function: ``gains`` (..., K) integers and ``distances`` (..., K) -> ((...) int64: the first candidate
+        with the largest ``gains/(distances + d0)`` among those with a finite distance and a positive gain; (...) bool ``none``:
+        there is no such candidate - the index is 0 then)."""
+        k = gains.shape[-1]
+        valid = torch.isfinite(distances) & (gains > 0)
+        score = torch.where(valid, gains.float()/(distances + d0), torch.full_like(distances, -1.))
+        best = valid & (score == score.amax(-1, keepdim=True))
+        order = torch.arange(k, device=gains.device).expand(best.shape)
+        first = torch.where(best, order, torch.full_like(order, k)).amin(-1)
+        none = ~valid.any(-1)
+        return torch.where(none, torch.zeros_like(first), first), none
+
+    def __call__(self, reset=None):
+        """Refreshes the frontier fields and, for the agents that are due, the goals. Call once per step, after the maps were
+        marked. ``reset`` (n_env, n_agent) bool: the agents that started over."""
+        c, grid = self.core, self.coverage.grid
+        n, a, k = c.n_envs, c.n_agents, self.n_candidates
+        fields = self.frontiers(reset)
+        due = self.frontiers.due.contiguous()
+        here = c.agents.positions
+        if self._draws is None:
+            source = cuda.cell_layer(fields, field=self.frontiers._field)
+            self._draws = cuda.cell_draws(grid, source, a, k, lo=self.band[0], hi=self.band[1], seed=self.seed, mask=due)
+        else:
+            self._draws.again(mask=due)
+        points = self._draws.points.reshape(n, a*k, 2)
+        self._around = cuda.distance_fields(grid, here, mask=due, out=self._around)
+        distances = self._around.at(points, goal=self._agent).reshape(n, a, k)
+        each = due[:, :, None].expand(n, a, k).reshape(n, a*k).contiguous()
+        if self._views is None:
+            self._views = cuda.view_fields(grid, c.scenery, points, self.max_range, unseen=self.coverage.maps, slot=self._slot, store=False, mask=each)
+        else:
+            self._views.update(each)
+        gains = self._views.gains.reshape(n, a, k)
+        index, none = self.choose(gains, distances)
+        goal = self._draws.points.gather(2, index[..., None, None].expand(-1, -1, 1, 2)).squeeze(2)
+        goal = torch.where(none[..., None], here, goal)
+        self._goal.copy_(torch.where(due[..., None], goal, self._goal))
+        self.none.copy_(torch.where(due, none, self.none))
+        self.gains, self.distances = gains, distances
+        self._fields = cuda.distance_fields(grid, self._goal, mask=due, out=self._fields)
+        return self._fields
+
+    def waypoints(self, lookahead=16):
+        """(n_env, n_agent, 2): where every agent should head for now: towards its goal (:meth:`cuda.DistanceFields.waypoints`),
+        or, where it has :attr:`none`, towards the nearest unseen floor (:meth:`Frontiers.waypoints`)."""
+        own = self._fields.waypoints(self.core.agents.positions, lookahead=lookahead)
+        return torch.where(self.none[..., None], self.frontiers.waypoints(lookahead), own)
+
+
 class PathFollower:
 
     def __init__(self, core, goals, lookahead=16, cone=45., speed=2.):
-        """The shortest-path expert over a :class:`Goals` (or a :class:`Frontiers`: anything with ``waypoints(lookahead)``): every agent turns towards its waypoint - the furthest of the next
+        """The shortest-path expert over a :class:`Goals` (or a :class:`Frontiers` or a :class:`BestViews`: anything with ``waypoints(lookahead)``): every agent turns towards its waypoint - the furthest of the next
         ``lookahead`` cells of its shortest path that it can see (:meth:`Goals.waypoints`) - and walks once that lies within
         ``cone`` degrees of straight ahead. Something to imitate, to fill a replay buffer with, to score a learned policy
         against (Habitat's ``ShortestPathFollower``; no counterpart in the reference). Other agents are not obstacles to

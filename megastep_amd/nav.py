@@ -1,7 +1,8 @@
 """Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
 floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
 they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``,
-``csrc/kernels/navdraw.h``), and the connected regions of any per-cell mask (``csrc/kernels/navregion.h``). No counterpart in the reference;
+``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), and the cells in sight of a
+point (``csrc/kernels/navview.h``). No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
@@ -548,8 +549,8 @@ def cell_layer(values, n_fields=1, field=None):
     can be the source. ``field``: an (N, P) integer tensor naming the store each view reads; without it store 0 is read when
     ``n_fields`` is 1 and view p reads store p when ``n_fields`` is the number of views. A :class:`NavGrid` (its ``free``), a
     :class:`SeenMaps`, a :class:`DistanceFields` and a :class:`SeededFields` are layers as they are, with their own number of
-    stores, and so is a :class:`Regions` (its ``areas``, square metres); ``cell_layer(maps, field=slot)`` gives one of them a
-    ``field``."""
+    stores, and so are a :class:`Regions` (its ``areas``, square metres) and a :class:`ViewFields` (its ``values``, a store a
+    viewpoint); ``cell_layer(maps, field=slot)`` gives one of them a ``field``."""
     if isinstance(values, CellLayer):
         values, n_fields = values.values, values.n_fields
     elif isinstance(values, NavGrid):
@@ -560,6 +561,8 @@ def cell_layer(values, n_fields=1, field=None):
         values, n_fields = values.values, values.n_goals
     elif isinstance(values, Regions):
         values, n_fields = values.areas, values.n_fields
+    elif isinstance(values, ViewFields):
+        values, n_fields = values.values, values.n_points
     if not isinstance(n_fields, int) or n_fields < 1:
         raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
     if not isinstance(values, torch.Tensor) or values.dtype not in (torch.uint8, torch.bool, torch.float32) or values.ndim != 1 or \
@@ -588,7 +591,7 @@ class MapChannel:
 
 def map_channel(source, where=True, scale=None, gate=None, outside=0., hidden=0.):
     """One channel of :func:`local_maps`. ``source``: a layer (:func:`cell_layer`, or a :class:`NavGrid`, :class:`SeenMaps`,
-    :class:`DistanceFields` or :class:`SeededFields` as it is). A byte source gives 1 where ``(byte != 0) == where`` and 0
+    :class:`DistanceFields`, :class:`SeededFields`, :class:`Regions` or :class:`ViewFields` as it is). A byte source gives 1 where ``(byte != 0) == where`` and 0
     elsewhere; a float source holding D gives ``D*scale`` clamped to [0, 1] (a NaN and +inf: 1), and ``scale`` is required.
     ``gate``: a byte layer with a ``field`` of its own; where its byte is 0 the channel shows ``hidden`` - ``grid.free`` gated by
     an agent's seen map is the floor that agent knows. ``outside``: what a sample beyond the env's grid shows."""
@@ -725,7 +728,7 @@ class CellDraws:
 def cell_draws(grid, source, n_sets, n_draws, lo=None, hi=None, where=True, gate=None, seed=0, mask=None, out=None):
     """Cells of the :func:`nav_grid` drawn uniformly at random: for every env ``n_sets`` draw sets of ``n_draws`` (1..256) draws each,
     with replacement, among the env's free cells that satisfy a predicate on ``source`` - a layer (:func:`cell_layer`, or a
-    :class:`NavGrid`, :class:`SeenMaps`, :class:`DistanceFields` or :class:`SeededFields` as it is), read per set the way
+    :class:`NavGrid`, :class:`SeenMaps`, :class:`DistanceFields`, :class:`SeededFields`, :class:`Regions` or :class:`ViewFields` as it is), read per set the way
     :func:`local_maps` reads a layer per view: one store an env, one per set, or the one the layer's ``field`` (N, P) names. A byte
     source qualifies a cell where ``(byte != 0) == where``; a float32 source holding D where ``lo <= D <= hi`` (both required
     then, both ends in; a NaN never qualifies) - a band of a distance field is a goal at a chosen walking distance, reachable by
@@ -954,3 +957,132 @@ def regions(grid, marks=None, n_fields=1, where=True, among=None, mask=None, out
                      new(shape, torch.int32, 0), new(shape, torch.int32, 0), new(shape, torch.int32, -1), new(shape, torch.int32, 0),
                      new(shape, torch.int32, 0) if passes else None)
     return result.update(mask)
+
+
+#: the static walls :func:`view_fields`' kernel stages in LDS for one viewpoint - those whose bounding box meets the box of everything
+#: in range; a viewpoint that keeps more reads its env's walls from global memory instead, to the same result
+VIEW_WALL_CAPACITY = 512
+
+
+class ViewFields:
+    """Result of :func:`view_fields`: for each env ``P`` viewpoints, and for viewpoint (n, p) the cells of env n's grid whose centre
+    is in sight of it. ``values``: the flat uint8 store, a byte a cell - 1 in sight, 0 not - store (n, p) at
+    ``P*grid.starts[n] + p*nx*ny`` (the layout of :class:`SeenMaps`: a layer, :func:`seeded_fields`' and :func:`regions`' ``marks``),
+    None with ``store=False``; ``counts`` (N, P) int32: the visible cells that count; ``gains`` (N, P) int32, None without
+    ``unseen``: those of them the viewpoint's seen map has not seen. ``points``, ``headings``, ``countable``, ``slot`` and the maps are
+    kept by reference: :meth:`update` reads them as they stand. The rule: include/megastep_hip.h (``MsNavViews``), DESIGN.md 3.21."""
+
+    def __init__(self, grid, scenery, points, max_range, headings, cos_half, countable, unseen, slot, values, counts, gains):
+        self.grid, self.scenery, self.points, self.max_range, self.headings, self.cos_half = grid, scenery, points, float(max_range), headings, cos_half
+        self.countable, self.unseen, self.slot, self.values, self.counts, self.gains = countable, unseen, slot, values, counts, gains
+
+    n_points = property(lambda self: self.points.shape[1])
+
+    def image(self, e, p=0):
+        """(ny, nx) bool view of the store of viewpoint ``p`` of env ``e``, row 0 at the lowest y."""
+        if self.values is None:
+            raise RuntimeError('these view fields keep no byte store (store=False)')
+        first, ny, nx = self.grid.cells(e)
+        at = self.n_points*first + p*ny*nx
+        return self.values[at:at + ny*nx].view(torch.bool).reshape(ny, nx)
+
+    def update(self, mask=None):
+        """Computes the viewpoints marked in the (N, P) bool ``mask`` (default all) again in place, from :attr:`points` and
+        :attr:`headings` as they stand now - move them in place - and from the maps as they stand; the others keep their bytes,
+        count and gain. One launch, no host synchronisation, nothing allocated: the call can be captured in a HIP graph."""
+        grid, p = self.grid, self.n_points
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, p):
+                raise RuntimeError(f'mask must be an (N, P) = ({grid.n_envs}, {p}) bool tensor')
+            mask = mask.contiguous()
+        maps = self.unseen.values if self.unseen is not None else None
+        dev = _require_gpu(self.points, self.countable, self.counts, grid.free,
+                           *(t for t in (self.headings, maps, self.slot, mask, self.values, self.gains) if t is not None))
+        if self.scenery._device() != dev:
+            raise RuntimeError(f'all tensors must live on one device; got {self.scenery._device()} and {dev}')
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        spec = _lib.MsNavViews(p, self.points.data_ptr(), ptr(self.headings), self.max_range, self.cos_half if self.headings is not None else 0.,
+                               self.countable.data_ptr(), ptr(maps), self.unseen.n_maps if self.unseen is not None else 0, ptr(self.slot), ptr(mask),
+                               ptr(self.values), self.counts.data_ptr(), ptr(self.gains))
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_views(C.byref(self.scenery._as_struct()), C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return self
+
+
+def view_fields(grid, scenery, points, max_range=10., headings=None, fov=None, countable=None, unseen=None, slot=None, store=True, mask=None,
+                out=None):
+    """What can be seen from a place: for every env and each of its ``P`` viewpoints (``points``: (N, P, 2) float32 world points) the
+    cells of the :func:`nav_grid` whose CENTRE is in sight - no further than ``max_range`` metres, within ``fov`` degrees round
+    ``headings`` (N, P, 2; any length) when both are given, and with no static wall of ``scenery`` across the straight line between
+    the two. The agents' own lines are not looked at: the grid is the building. A byte a cell for every cell, free or not - a blocked
+    cell on the viewer's side of a wall is a known obstacle - so an opponent's view is a layer: ``cell_draws(grid, views, ...,
+    where=False)`` draws a hiding spot, ``seeded_fields(grid, views.values, P, where=False)`` is the walking distance to cover,
+    :func:`regions` labels the pockets, :func:`local_maps` shows it to a policy.
+
+    ``counts`` is the number of visible cells that count: ``countable``, a uint8 or bool tensor of one entry per cell of the grid,
+    default ``unseen.countable`` with ``unseen``, else the grid's free cells. ``unseen``: a :class:`SeenMaps`; then ``gains`` is the
+    number of visible countable cells the viewpoint's map has NOT seen - what standing there would reveal; ``slot`` (N, P) integers
+    names the map of each viewpoint (outside 0..S-1: gain 0), default viewpoint k map k (then P must be S) or the env's one map.
+    ``store=False`` keeps no bytes at all, only the counts: scoring candidate standpoints costs 4 bytes a viewpoint.
+
+    One launch, one workgroup per viewpoint: the walls near enough to matter staged in LDS, a lane a cell of the window round the
+    viewpoint; exact - the rule is written out in include/megastep_hip.h (``MsNavViews``) and DESIGN.md 3.21, every operation binary32
+    in a fixed order, and the kernel computes it bit for bit. Unlike a ring of :func:`raycast` rays through :meth:`SeenMaps.mark`
+    it misses no cell at range and marks no cell whose centre is hidden.
+
+    ``mask`` (N, P) bool: compute only the marked viewpoints (the others keep what ``out`` held; nothing in sight without ``out``);
+    ``out``: the :class:`ViewFields` of an earlier call with the same grid, P and kind of outputs to write into - it takes this call's
+    arguments. ``points`` and ``headings`` are kept by reference, not copied: :meth:`ViewFields.update` follows them. No host
+    synchronisation: the call can be captured in a HIP graph."""
+    import math
+    _check(points, 'points', torch.float32, 3)
+    n, p = points.shape[:2]
+    if n != grid.n_envs or p < 1 or points.shape[2] != 2:
+        raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs} and P >= 1; got {tuple(points.shape)}')
+    if not isinstance(max_range, (int, float)) or not (0 < max_range < float('inf')):
+        raise RuntimeError(f'max_range must be a positive number; got {max_range}')
+    if (headings is None) != (fov is None):
+        raise RuntimeError('headings and fov go together: a cone needs both')
+    cos_half = 0.
+    if headings is not None:
+        _check(headings, 'headings', torch.float32, 3)
+        if headings.shape != points.shape:
+            raise RuntimeError(f'headings must be (N, P, 2) = {tuple(points.shape)}; got {tuple(headings.shape)}')
+        if not isinstance(fov, (int, float)) or not (0 <= fov <= 360):
+            raise RuntimeError(f'fov must be a number of degrees in 0..360; got {fov}')
+        cos_half = max(-1., min(1., math.cos(math.radians(float(fov))/2.)))
+    if unseen is not None and not isinstance(unseen, SeenMaps):
+        raise RuntimeError('unseen must be a SeenMaps')
+    if unseen is not None and unseen.grid is not grid:
+        raise RuntimeError("unseen must be seen maps of the same grid")
+    if countable is None:
+        countable = unseen.countable if unseen is not None else grid.free
+    else:
+        countable = _cell_bytes(countable, 'countable', grid.free.shape[0], 'one per cell of the grid')
+    if slot is not None:
+        if unseen is None:
+            raise RuntimeError('slot goes with unseen: it names the seen map of each viewpoint')
+        if not isinstance(slot, torch.Tensor) or slot.dtype.is_floating_point or slot.dtype == torch.bool or slot.shape != (n, p):
+            raise RuntimeError(f'slot must be an (N, P) = ({n}, {p}) integer tensor')
+        if slot.dtype != torch.int32 or not slot.is_contiguous():
+            slot = slot.to(torch.int32).contiguous()
+    elif unseen is not None and unseen.n_maps not in (1, p):
+        raise RuntimeError(f'without slot, unseen must hold one map per env or one per viewpoint ({p}); it holds {unseen.n_maps}')
+    if not hasattr(scenery, 'lines') or len(scenery.lines) != n:
+        raise RuntimeError(f'scenery must be the Scenery the grid was laid over: {n} envs')
+    store = bool(store)
+    size = max(p*grid.n_cells, 1)
+    if out is not None:
+        if not isinstance(out, ViewFields) or out.grid is not grid or out.n_points != p or (out.values is not None) != store or \
+                (out.gains is not None) != (unseen is not None):
+            raise RuntimeError('`out` must come from a view_fields call with the same grid, P, store and use of unseen')
+        views = out
+        views.scenery, views.points, views.max_range, views.headings, views.cos_half = scenery, points, float(max_range), headings, cos_half
+        views.countable, views.unseen, views.slot = countable, unseen, slot
+    else:
+        dev = _require_gpu(points, grid.free, countable)
+        views = ViewFields(grid, scenery, points, max_range, headings, cos_half, countable, unseen, slot,
+                           torch.zeros(size, dtype=torch.uint8, device=dev) if store else None,
+                           torch.zeros((n, p), dtype=torch.int32, device=dev),
+                           torch.zeros((n, p), dtype=torch.int32, device=dev) if unseen is not None else None)
+    return views.update(mask)

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -49,6 +49,15 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       SeenMaps.frontier_regions right after one marked frame, and with 80 % seen; one Regions.masks call;
       PointGoal(envs, goal_range=(2., 8.), sampled_spawns=True, one_region=True).step eager and replayed as a HIP graph, next
       to the same env without one_region.
+  (v) the view fields, at `--envs` envs: one cuda.view_fields (ms_nav_views) of P = 1 viewpoint an env at R = 10 m with the byte
+      store, and one of P = 16 candidate standpoints an env at R = 5 m with store=False and gains against seen maps that hold one
+      rendered frame - each timed as 20 ViewFields.update() back to back between two events - next to the torch formulation of
+      the same rule at the same shape (the grids padded to the largest plan, the walls padded to the most an env has, a loop over
+      the wall index of (envs, H, W) binary32 tensor ops in the rule's order; the first `--torch-envs` envs, scaled; bytes,
+      counts and gains compared for equality: the one gate on time is that the kernel is the faster); for time only,
+      cuda.raycast of a ring of 720 rays an env plus SeenMaps.mark of them; FloorCoverage(envs): expert('views') + step()
+      eager and replayed as a HIP graph, next to expert() + step(); and FloorCoverage(64), 300 steps, in one run under
+      expert('views'), expert('frontier') and uniformly random actions: episodes ended by coverage and mean final fraction.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -314,14 +323,89 @@ def torch_draws(grid, D, lo, hi, K, seed, envs):
 class ExpertStep:
     """An env whose step is the expert's own: expert() + step(), the decision handed in ignored."""
 
-    def __init__(self, env):
-        self.env, self.action_space = env, env.action_space
+    def __init__(self, env, *kind):
+        self.env, self.action_space, self.kind = env, env.action_space, kind
 
     def reset(self):
         return self.env.reset()
 
     def step(self, decision):
-        return self.env.step(self.env.expert())
+        return self.env.step(self.env.expert(*self.kind))
+
+
+def torch_views(grid, scenery, points, R, countable, maps, slot, envs):
+    """ms_nav_views' rule for the first `envs` envs by tensor ops: (envs, H, W) binary32 tensors padded to the largest grid, the
+    static walls padded with NaN rows (which block nothing) to the most an env has, one pass of the rule's statements per wall
+    index and viewpoint.  Returns run() -> (visible (envs, P, H, W) bool, counts, gains (envs, P) int64)."""
+    geom = grid._host_geom[:envs]
+    H, W = int(geom[:, 3].max()), int(geom[:, 2].max())
+    dev = grid.free.device
+    P = points.shape[1]
+    af = scenery.n_agents*scenery.model.shape[0]
+    starts, widths = scenery.lines.starts[:envs].tolist(), scenery.lines.widths[:envs].tolist()
+    most = max(w - af for w in widths)
+    walls = torch.full((envs, most, 4), float('nan'), device=dev)
+    inside = torch.zeros((envs, H, W), dtype=torch.bool, device=dev)
+    counts = torch.zeros((envs, H, W), dtype=torch.bool, device=dev)
+    seen = torch.zeros((envs, maps.n_maps if maps is not None else 1, H, W), dtype=torch.bool, device=dev)
+    for e in range(envs):
+        walls[e, :widths[e] - af] = scenery.lines.vals[starts[e] + af:starts[e] + widths[e]].reshape(-1, 4)
+        first, ny, nx = grid.cells(e)
+        inside[e, :ny, :nx] = True
+        counts[e, :ny, :nx] = (countable[first:first + ny*nx] & 1).bool().reshape(ny, nx)
+        if maps is not None:
+            S = maps.n_maps
+            seen[e, :, :ny, :nx] = (maps.values[S*first:S*(first + ny*nx)] & 1).bool().reshape(S, ny, nx)
+    g = torch.as_tensor(geom, device=dev)
+    c = torch.tensor(grid.cell, dtype=torch.float32, device=dev)
+    x = (((g[:, 0, None] + torch.arange(W, device=dev)[None]).float() + .5)*c)[:, None, :].expand(envs, H, W).contiguous()
+    y = (((g[:, 1, None] + torch.arange(H, device=dev)[None]).float() + .5)*c)[:, :, None].expand(envs, H, W).contiguous()
+    R2 = torch.tensor(R, dtype=torch.float32, device=dev)*torch.tensor(R, dtype=torch.float32, device=dev)
+
+    def run():
+        vis = torch.zeros((envs, P, H, W), dtype=torch.bool, device=dev)
+        for p in range(P):
+            px, py = points[:envs, p, 0, None, None], points[:envs, p, 1, None, None]
+            rx, ry = x - px, y - py
+            ok = inside & (rx*rx + ry*ry <= R2) & torch.isfinite(px) & torch.isfinite(py)
+            sx0, sx1, sy0, sy1 = torch.minimum(px, x), torch.maximum(px, x), torch.minimum(py, y), torch.maximum(py, y)
+            for l in range(most):
+                ax, ay, bx, by = (walls[:, l, k, None, None] for k in range(4))
+                meets = (torch.minimum(ax, bx) <= sx1) & (torch.maximum(ax, bx) >= sx0) & (torch.minimum(ay, by) <= sy1) & (torch.maximum(ay, by) >= sy0)
+                vx, vy = bx - ax, by - ay
+                o1 = vx*(py - ay) - vy*(px - ax)
+                o2 = vx*(y - ay) - vy*(x - ax)
+                o3 = rx*(ay - py) - ry*(ax - px)
+                o4 = rx*(by - py) - ry*(bx - px)
+                ok &= ~(meets & (((o1 < 0) & (o2 > 0)) | ((o1 > 0) & (o2 < 0))) & (((o3 <= 0) & (o4 >= 0)) | ((o3 >= 0) & (o4 <= 0))))
+            vis[:, p] = ok
+        counted = vis & counts[:, None]
+        gains = None
+        if maps is not None:
+            which = slot[:envs].long() if slot is not None else torch.zeros((envs, P), dtype=torch.long, device=dev)
+            fresh = ~seen[torch.arange(envs, device=dev)[:, None], which]
+            gains = (counted & fresh).sum((-1, -2))
+        return vis, counted.sum((-1, -2)), gains
+    return run
+
+
+def coverage_score(env, steps, policy, seed=1):
+    """(episodes ended by coverage, by lifespan, mean final fraction over all episodes) of `steps` steps of a FloorCoverage under
+    expert(policy), or uniformly random actions."""
+    from megastep_amd import arrdict
+    rng = np.random.RandomState(seed)
+    n, a = env.core.n_envs, env.core.n_agents
+    env.reset()
+    by_coverage = by_lifespan = 0
+    final = []
+    for _ in range(steps):
+        fraction, over = env._coverage.fraction().clone(), env._over.clone()
+        done = fraction >= env.complete
+        by_coverage += int((over & done).sum()); by_lifespan += int((over & ~done).sum())
+        final += fraction[over].tolist()
+        env.step(arrdict.arrdict(actions=torch.as_tensor(rng.randint(0, 7, (n, a)), device='cuda')) if policy == 'random' else env.expert(policy))
+    final += env._coverage.fraction().reshape(-1).tolist()
+    return dict(ended_by_coverage=by_coverage, ended_by_lifespan=by_lifespan, mean_final_fraction=float(np.mean(final)))
 
 
 def rollout_score(env, steps, policy, seed=1):
@@ -370,7 +454,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
@@ -689,6 +773,73 @@ def main():
             print(f'(r) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
             del env
             torch.cuda.empty_cache()
+
+    if want('views'):
+        from megastep_amd.demo.envs.floorcoverage import reachable
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 17), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        maps = cuda.seen_maps(grid, 1, reachable(grid, table[:, 0, 0]))
+        maps.mark_render(c.agents, cuda.render(sc, c.agents, fields=('distances',)))
+        k, batch = min(args.torch_envs, args.envs), 20
+        cells = np.diff(grid._host_starts)
+        walls = (sc.lines.widths - sc.n_agents*sc.model.shape[0]).float()
+        for name, pts, R, kw in (('views_1_store', table[:, 0, :1].contiguous(), 10., dict()),
+                                 ('views_16_gains', table[:, 0, 1:17].contiguous(), 5., dict(unseen=maps, store=False))):
+            v = cuda.view_fields(grid, sc, pts, R, countable=maps.countable, **kw)
+
+            def calls():
+                for _ in range(batch):
+                    v.update()
+            med, lo, hi = (t/batch for t in timed(calls, args.repeats, args.warmup))
+            run = torch_views(grid, sc, pts, R, maps.countable, kw.get('unseen'), None, k)
+            vis, counts, gains = run()
+            same = bool(torch.equal(counts, v.counts[:k].long()))
+            if v.gains is not None:
+                same = same and bool(torch.equal(gains, v.gains[:k].long()))
+            if v.values is not None:
+                same = same and all(torch.equal(vis[e, p, :grid.cells(e)[1], :grid.cells(e)[2]], v.image(e, p)) for e in range(k) for p in range(pts.shape[1]))
+            tmed = timed(lambda: run(), 2, 1)[0]
+            out[name] = dict(seconds=med, min=lo, max=hi, viewpoints=pts.shape[1], max_range=R, store=v.values is not None, cells_largest=int(cells.max()),
+                             cells_median=int(np.median(cells)), walls_mean=float(walls.mean()), walls_most=int(walls.max()),
+                             counts_mean=float(v.counts.float().mean()), gains_mean=float(v.gains.float().mean()) if v.gains is not None else None,
+                             torch_envs=k, torch_seconds=tmed, torch_scaled_seconds=tmed*args.envs/k, torch_equal=same,
+                             faster_than_torch=bool(med < tmed*args.envs/k))
+            print(f"(v) view_fields, {args.envs} x {pts.shape[1]} viewpoints, R = {R}, store={v.values is not None}: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}] "
+                  f"a call ({batch} back to back); {out[name]['counts_mean']:.0f} countable cells in sight; torch, {k} envs: {tmed*1e3:.1f} ms -> "
+                  f"{tmed*args.envs/k*1e3:.0f} ms for {args.envs}, equal: {same}")
+            assert same and med < tmed*args.envs/k, 'the kernel must equal the torch formulation and be the faster'
+            del v, run, vis
+        angle = torch.arange(720, device='cuda').float()*(2*np.pi/720)
+        dirs = torch.stack([angle.cos(), angle.sin()], -1)[None].expand(args.envs, 720, 2).contiguous()
+        origins = table[:, 0, :1].expand(args.envs, 720, 2).contiguous()
+        ring = cuda.raycast(sc, origins, dirs, fields=('distances',), config=c.config)
+        scratch = cuda.seen_maps(grid, 1, maps.countable)
+        gained = torch.empty((args.envs, 1), dtype=torch.int32, device='cuda')
+
+        def ring_and_mark():
+            cuda.raycast(sc, origins, dirs, fields=('distances',), config=c.config, out=ring)
+            scratch.mark(table[:, 0, :1].contiguous(), dirs[:, None], ring.distances[:, None], out=gained)
+        med, lo, hi = timed(ring_and_mark, args.repeats, args.warmup)
+        out['views_ring_and_mark'] = dict(seconds=med, min=lo, max=hi, rays=720)
+        print(f'(v) raycast of a 720-ray ring + mark, {args.envs} envs (time only: another rule): {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]')
+        del sc, c, grid, maps, scratch, ring
+        torch.cuda.empty_cache()
+        for name, kind in (('FloorCoverage_views_expert', ('views',)), ('FloorCoverage_frontier_expert', ())):
+            env = ExpertStep(FloorCoverage(args.envs, geometries=geoms), *kind)
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[name] = dict(expert_step_eager_seconds=eager, expert_step_graph_seconds=graphed)
+            print(f'(v) {name}({args.envs}): expert + step eager {eager*1e3:.3f} ms, graph {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+        small = cubicasa.sample(64, seed=7, n_unique=64)
+        for policy in ('views', 'frontier', 'random'):
+            torch.manual_seed(3); np.random.seed(3)
+            out['coverage_' + policy] = score = coverage_score(FloorCoverage(64, geometries=small, max_lifespan=300), 300, policy)
+            print(f'(v) FloorCoverage(64), 300 steps, {policy}: {score}')
 
     if args.json:
         with open(args.json, 'w') as f:
