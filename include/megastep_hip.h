@@ -874,6 +874,74 @@ typedef struct MsNavViews {
 } MsNavViews;
 int ms_nav_views(const MsScenery* scenery, const MsNavGrid* grid, const MsNavViews* views, void* hip_stream);
 
+/* Basins: WHICH seed a cell of a seeded field leads to - whose agent is nearest (a geodesic Voronoi diagram of the floor), which
+ * frontier cluster, which pickup a cell drains to - and how many cells each seed, or each id, holds.  Every output is an integer
+ * with one definition; tests/test_navbasin_host.py restates it in numpy (basin_rule, point_mark_rule, basin_query_rule: chains
+ * followed cell by cell) and the kernels - and their host instantiations, ms_host_nav_basins / _basin_query / _point_marks - are
+ * held to EQUALITY with it.  c, geom and starts are MsNavGrid's.  Take field (n, g) of an MsNavSeedFields store, its values D AS THEY
+ * STAND when the call runs, and a cell v of env n's grid:
+ *   succ(v)       what MsNavSeedFields' `following` hop does from v - the kernels call the very function ms_nav_seed_paths and
+ *                 ms_nav_seed_waypoints follow: if D[v] == 0.f the chain ends at v, a seed; otherwise the next cell is the first of
+ *                 the eight neighbours (MsNavWaypoints' order and rules) that attains the least fl(D[u] + w), provided D[u] < D[v];
+ *                 without such a neighbour the chain is BROKEN at v (a stale or foreign field).
+ *   end(v)        the seed the chain v, succ(v), succ(succ(v)), ... ends on.  A hop needs a strictly lower value: whatever floats
+ *                 the store holds, the successor graph has no cycle and every chain ends or breaks within the env's cells.
+ *   label(v)      -1 when v is blocked (free_cells[v] & 1 clear), when D[v] is not < +inf (a NaN too), or when v's chain breaks;
+ *                 otherwise end(v)'s row-major index within the env's grid - or, with ids, ids[first + end(v)] as stored: ids is an
+ *                 int32 per cell and field in the fields' layout (field (n, g) at first = G*starts[n] + g*nx*ny); a negative id
+ *                 reads as "no basin" wherever a label is tested.  ids must not be the labels store.
+ *   sizes         with n_ids = K in 1..256: sizes[n, g, k] = the cells whose label is k, 0 <= k < K; labels outside that range are
+ *                 counted nowhere.  K = 0: no sizes (the pointer must be NULL then, and non-NULL otherwise).
+ *   reached       reached[n, g] = the cells with label >= 0.  passes (or NULL): the passes the jumps took (telemetry: depends on
+ *                 the schedule; at most ceil(log2(longest chain)) + 1).  An env without cells: sizes 0, reached 0, passes 0.
+ *   query         from a point p: MsNavWaypoints' start picks the anchor a* the query's minimum is attained at, and the answer is
+ *                 the label stored at a*; -1 exactly where ms_nav_query gives +inf (a NaN point, an env without cells and a field
+ *                 index outside [0, G) included).  field (N, P): the field each point asks; NULL: MsNavLayer's rule - field 0
+ *                 when G == 1, else G == P and point k asks field k.
+ *   point marks   the seeds of "nearest agent": for point (n, k) every FREE cell among its four anchors (MsNavGrid's, in the
+ *                 query's order) gets mark byte 1 and id min(what it holds, id_k), id_k = point_ids[n, k], or k without
+ *                 point_ids.  The store is picked by `field` as the query's.  Two points that share an anchor leave the lower id;
+ *                 a point without an anchor (a NaN, one further out than 2^30 cells, a field index out of range, an env without
+ *                 cells) marks nothing.  Nothing is cleared: the caller zeroes marks and fills ids (with INT_MAX) beforehand.
+ *   masks         ms_nav_region_masks turns the labels store into byte layers as it is (labels = MsNavBasins.labels, wanted = ids).
+ * ms_nav_basins: one launch, one workgroup per field: succ once per cell into an int32 per cell in LDS while the env fits (40, 80
+ * or 160 KiB, chosen by max_framed, which bounds the cells from above), then pointer jumps N[k] = N[N[k]] in place until a pass
+ * changes nothing; a larger env runs the same jumps in its `labels` store, to the same result.  Fields that are masked out keep
+ * labels, sizes, reached and passes as they are.  Integer atomics only, one writer per output element, nothing allocated, nothing
+ * waits: all three calls can be captured in a HIP graph.  Every argument is checked in full before the launch (MS_EINVAL). */
+typedef struct MsNavBasins {
+    int                  n_fields;     /* G: fields per env                                                            */
+    const float*         fields;       /* as MsNavSeedFields.fields                                                    */
+    const int*           ids;          /* G*starts[N] int32, the fields' layout; NULL: a label is the seed's cell index */
+    int                  n_ids;        /* K, 0..256: the ids counted in sizes                                          */
+    const unsigned char* mask;         /* (N, G) non-zero: compute this field; NULL: all.  Read on the device only.    */
+    int*                 labels;       /* G*starts[N] int32 out                                                        */
+    int*                 sizes;        /* (N, G, K) out; NULL exactly when K == 0                                      */
+    int*                 reached;      /* (N, G) out                                                                   */
+    int*                 passes;       /* (N, G) out, or NULL                                                          */
+} MsNavBasins;
+typedef struct MsNavBasinQuery {
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y                                                               */
+    const int*           field;        /* (N, P) the field each point asks; NULL: G == 1 or G == P                     */
+    const float*         fields;       /* as MsNavSeedFields.fields                                                    */
+    const int*           labels;       /* as MsNavBasins.labels                                                        */
+    int                  n_fields;     /* G of `fields` and `labels`                                                   */
+    int*                 out;          /* (N, P) out                                                                   */
+} MsNavBasinQuery;
+typedef struct MsNavPointMarks {
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y                                                               */
+    const int*           field;        /* (N, P) the store each point marks; NULL: G == 1 or G == P                    */
+    const int*           point_ids;    /* (N, P) the id of each point; NULL: point k has id k                          */
+    int                  n_fields;     /* G of `marks` and `ids`                                                       */
+    unsigned char*       marks;        /* G*starts[N] bytes in / out                                                   */
+    int*                 ids;          /* G*starts[N] int32 in / out                                                   */
+} MsNavPointMarks;
+int ms_nav_basins(const MsNavGrid* grid, const MsNavBasins* basins, void* hip_stream);
+int ms_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* query, void* hip_stream);
+int ms_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* marks, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

@@ -115,6 +115,17 @@ int ms_host_nav_regions(const MsNavGrid* grid, const MsNavRegions* regions);
 int ms_host_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* query);
 int ms_host_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* masks);
 int ms_host_nav_region_capacity(int* capacities);
+/* Host instantiations of the basins' rule (kernels/navbasin.h: a cell's successor through nav_hop, the jump, the label, the anchor
+ * nav_start picks and a point's marks - the very functions every lane of nav_basin_kernel, nav_basin_query_kernel and
+ * nav_point_mark_kernel evaluates) for one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the
+ * argument struct is host memory.  ms_host_nav_basins jumps in a copy of the successors when the env fits the LDS of the launch
+ * ms_nav_basins would choose by grid->max_framed, else in its `labels` store - the kernel's two paths.  They return what the device
+ * entries would: MS_OK, or MS_EINVAL for arguments they would refuse.  ms_host_nav_basin_capacity writes the three capacities, in
+ * cells, of nav_basin_kernel's instantiations. */
+int ms_host_nav_basins(const MsNavGrid* grid, const MsNavBasins* basins);
+int ms_host_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* query);
+int ms_host_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* marks);
+int ms_host_nav_basin_capacity(int* capacities);
 /* Host instantiation of the view fields' rule (kernels/navview.h: view_in_range, view_in_cone, view_wall_blocks, the window and the
  * wall cull - the very functions every lane of nav_view_kernel evaluates) for one whole call of ms_nav_views on HOST arrays, swept
  * serially: every pointer of `grid` and of `views` is host memory, and in place of an MsScenery `walls` holds the STATIC rows of all

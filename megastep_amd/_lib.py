@@ -173,6 +173,21 @@ class MsNavRegionMasks(C.Structure):
                 ('n_fields', C.c_int), ('out', C.c_void_p)]
 
 
+class MsNavBasins(C.Structure):
+    _fields_ = [('n_fields', C.c_int), ('fields', C.c_void_p), ('ids', C.c_void_p), ('n_ids', C.c_int), ('mask', C.c_void_p),
+                ('labels', C.c_void_p), ('sizes', C.c_void_p), ('reached', C.c_void_p), ('passes', C.c_void_p)]
+
+
+class MsNavBasinQuery(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('field', C.c_void_p), ('fields', C.c_void_p), ('labels', C.c_void_p),
+                ('n_fields', C.c_int), ('out', C.c_void_p)]
+
+
+class MsNavPointMarks(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('field', C.c_void_p), ('point_ids', C.c_void_p), ('n_fields', C.c_int),
+                ('marks', C.c_void_p), ('ids', C.c_void_p)]
+
+
 class MsNavViews(C.Structure):
     _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('headings', C.c_void_p), ('max_range', C.c_float), ('cos_half', C.c_float),
                 ('countable', C.c_void_p), ('unseen', C.c_void_p), ('n_maps', C.c_int), ('slot', C.c_void_p), ('mask', C.c_void_p),
@@ -213,6 +228,9 @@ PROTOTYPES = {
     'ms_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery), _ptr]),
     'ms_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks), _ptr]),
     'ms_nav_views': (_int, [_p(MsScenery), _p(MsNavGrid), _p(MsNavViews), _ptr]),
+    'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
+    'ms_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery), _ptr]),
+    'ms_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks), _ptr]),
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
     'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
     'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
@@ -246,6 +264,10 @@ PROTOTYPES = {
     'ms_host_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery)]),
     'ms_host_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks)]),
     'ms_host_nav_region_capacity': (_int, [_ptr]),
+    'ms_host_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins)]),
+    'ms_host_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery)]),
+    'ms_host_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks)]),
+    'ms_host_nav_basin_capacity': (_int, [_ptr]),
     'ms_host_nav_views': (_int, [_p(MsNavGrid), _p(MsNavViews), _ptr, _ptr, _int]),
     'ms_host_nav_view_capacity': (_int, []),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),

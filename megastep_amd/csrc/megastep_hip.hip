@@ -2,7 +2,7 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navregion.h, navview.h, navpath.h, navseen.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navregion.h, navview.h, navpath.h, navbasin.h, navseen.h, navwindow.h, navdraw.h.
 //
 // Twenty-four kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
@@ -167,6 +167,7 @@ struct Probe {
 #include "kernels/navregion.h"
 #include "kernels/navview.h"
 #include "kernels/navpath.h"
+#include "kernels/navbasin.h"
 #include "kernels/navseen.h"
 #include "kernels/navwindow.h"
 #include "kernels/navdraw.h"
@@ -1238,6 +1239,104 @@ int ms_host_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* m) {
 int ms_host_nav_region_capacity(int* capacities) {
     if (!capacities) return MS_EINVAL;
     capacities[0] = region_capacity(NAV_LDS_SMALL); capacities[1] = region_capacity(NAV_LDS_MEDIUM); capacities[2] = region_capacity(NAV_LDS_LARGE);
+    return MS_OK;
+}
+
+// Basins (navbasin.h): the same discipline; the launch's LDS is chosen by max_framed, which bounds every env's cells from above.
+static int nav_basin_capacity_for(const MsNavGrid* grid) {
+    const long long framed = grid->max_framed;
+    return framed <= basin_capacity(NAV_LDS_SMALL) ? basin_capacity(NAV_LDS_SMALL)
+         : framed <= basin_capacity(NAV_LDS_MEDIUM) ? basin_capacity(NAV_LDS_MEDIUM) : basin_capacity(NAV_LDS_LARGE);
+}
+static int nav_basins_check(const MsNavGrid* grid, const MsNavBasins* b) {
+    if (!nav_grid_ok(grid) || !b || b->n_fields < 1 || !b->fields || !b->labels || !b->reached || b->n_ids < 0 || b->n_ids > BASIN_MAX_IDS ||
+        (b->sizes != nullptr) != (b->n_ids > 0) || b->ids == b->labels || ((uintptr_t)b->fields % 4) || ((uintptr_t)b->ids % 4) ||
+        ((uintptr_t)b->labels % 4) || ((uintptr_t)b->sizes % 4) || ((uintptr_t)b->reached % 4) || ((uintptr_t)b->passes % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*b->n_fields > 0x7fffffffLL/(b->n_ids > 0 ? b->n_ids : 1)) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static NavBasinArgs nav_basin_args(const MsNavGrid* grid, const MsNavBasins* b) {
+    return NavBasinArgs{grid->free_cells, b->fields, b->ids, b->mask, b->labels, b->sizes, b->reached, b->passes, b->n_fields, b->n_ids};
+}
+static int nav_basin_query_check(const MsNavGrid* grid, const MsNavBasinQuery* q) {
+    if (!nav_grid_ok(grid) || !q || q->n_points < 1 || q->n_fields < 1 || !q->points || !q->fields || !q->labels || !q->out ||
+        (!q->field && q->n_fields != 1 && q->n_fields != q->n_points) || ((uintptr_t)q->points % 4) || ((uintptr_t)q->field % 4) ||
+        ((uintptr_t)q->fields % 4) || ((uintptr_t)q->labels % 4) || ((uintptr_t)q->out % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*q->n_points > 0x7fffff00LL) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static NavBasinQueryArgs nav_basin_query_args(const MsNavGrid* grid, const MsNavBasinQuery* q) {
+    return NavBasinQueryArgs{q->points, q->field, grid->free_cells, q->fields, q->labels, q->out, q->n_points, q->n_fields,
+                             (long long)grid->n_envs*q->n_points};
+}
+static int nav_point_marks_check(const MsNavGrid* grid, const MsNavPointMarks* m) {
+    if (!nav_grid_ok(grid) || !m || m->n_points < 1 || m->n_fields < 1 || !m->points || !m->marks || !m->ids ||
+        (!m->field && m->n_fields != 1 && m->n_fields != m->n_points) || ((uintptr_t)m->points % 4) || ((uintptr_t)m->field % 4) ||
+        ((uintptr_t)m->point_ids % 4) || ((uintptr_t)m->ids % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*m->n_points > 0x7fffff00LL) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static NavPointMarkArgs nav_point_mark_args(const MsNavGrid* grid, const MsNavPointMarks* m) {
+    return NavPointMarkArgs{m->points, m->field, m->point_ids, grid->free_cells, m->marks, m->ids, m->n_points, m->n_fields,
+                            (long long)grid->n_envs*m->n_points};
+}
+
+int ms_nav_basins(const MsNavGrid* grid, const MsNavBasins* b, void* stream) {
+    const int status = nav_basins_check(grid, b);
+    if (status != MS_OK) return status;
+    const int capacity = nav_basin_capacity_for(grid);
+    void (*kernel)(NavArgs, NavBasinArgs);
+    int threads = 1024;
+    if (capacity == basin_capacity(NAV_LDS_SMALL)) { kernel = nav_basin_kernel<NAV_LDS_SMALL, 512>; threads = 512; }
+    else if (capacity == basin_capacity(NAV_LDS_MEDIUM)) kernel = nav_basin_kernel<NAV_LDS_MEDIUM, 1024>;
+    else kernel = nav_basin_kernel<NAV_LDS_LARGE, 1024>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)grid->n_envs*b->n_fields)), dim3(threads), 0, (hipStream_t)stream, nav_args(grid),
+                       nav_basin_args(grid, b));
+    return launch_status();
+}
+
+int ms_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* q, void* stream) {
+    const int status = nav_basin_query_check(grid, q);
+    if (status != MS_OK) return status;
+    const NavBasinQueryArgs a = nav_basin_query_args(grid, q);
+    hipLaunchKernelGGL(nav_basin_query_kernel, dim3((unsigned)((a.total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), a);
+    return launch_status();
+}
+
+int ms_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* m, void* stream) {
+    const int status = nav_point_marks_check(grid, m);
+    if (status != MS_OK) return status;
+    const NavPointMarkArgs a = nav_point_mark_args(grid, m);
+    hipLaunchKernelGGL(nav_point_mark_kernel, dim3((unsigned)((a.total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), a);
+    return launch_status();
+}
+
+int ms_host_nav_basins(const MsNavGrid* grid, const MsNavBasins* b) {
+    const int status = nav_basins_check(grid, b);
+    if (status != MS_OK) return status;
+    basin_serial(nav_args(grid), nav_basin_args(grid, b), nav_basin_capacity_for(grid));
+    return MS_OK;
+}
+
+int ms_host_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* q) {
+    const int status = nav_basin_query_check(grid, q);
+    if (status != MS_OK) return status;
+    const NavBasinQueryArgs a = nav_basin_query_args(grid, q);
+    for (long long at = 0; at < a.total; at++) basin_query_one(nav_args(grid), a, at);
+    return MS_OK;
+}
+
+int ms_host_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* m) {
+    const int status = nav_point_marks_check(grid, m);
+    if (status != MS_OK) return status;
+    const NavPointMarkArgs a = nav_point_mark_args(grid, m);
+    for (long long at = 0; at < a.total; at++) point_mark_one(nav_args(grid), a, at);
+    return MS_OK;
+}
+
+int ms_host_nav_basin_capacity(int* capacities) {
+    if (!capacities) return MS_EINVAL;
+    capacities[0] = basin_capacity(NAV_LDS_SMALL); capacities[1] = basin_capacity(NAV_LDS_MEDIUM); capacities[2] = basin_capacity(NAV_LDS_LARGE);
     return MS_OK;
 }
 

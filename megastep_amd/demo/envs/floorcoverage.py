@@ -56,6 +56,7 @@ class FloorCoverage:
         self._fresh = c.agent_full(False)               # who started over since the expert was last asked
         self._frontiers = self._follower = None         # made when the expert is first asked: they cost nothing until then
         self._views = self._views_follower = None
+        self._split = self._split_follower = self.territories = None
 
     #: the :class:`~megastep_amd.cuda.SeenMaps`
     maps = property(lambda self: self._coverage.maps)
@@ -102,7 +103,22 @@ class FloorCoverage:
         ``env.step(env.expert())`` can sit in one graph, once a first call outside it has made the fields. The fields are
         refreshed, and the follower counts the steps an agent has been stuck, on every call: ask once per step.
         ``kind='views'``: the next-best-view follower instead - every agent towards the candidate standpoint that would reveal
-        the most unseen floor per metre walked (:class:`~megastep_amd.modules.BestViews`); ask one kind per step."""
+        the most unseen floor per metre walked (:class:`~megastep_amd.modules.BestViews`). ``kind='split'``, for ``shared=True``
+        with several agents: the frontier follower over ``Frontiers(territories=Territories(...))`` - every agent towards the
+        nearest unseen floor of the part of the plan it is the nearest agent to, so that an env's agents part ways. Ask one kind
+        per step."""
+        if kind not in ('frontier', 'views', 'split'):
+            raise RuntimeError(f"kind must be 'frontier', 'views' or 'split'; got {kind!r}")
+        if kind == 'split':
+            if not self._coverage.shared:
+                raise RuntimeError("expert('split') needs shared=True: agents with a map each have a frontier each already")
+            if self._split is None:
+                self.territories = modules.Territories(self.core, self.grid)
+                self._split = modules.Frontiers(self.core, self._coverage, territories=self.territories)
+                self._split_follower = modules.PathFollower(self.core, self._split, cone=15.)
+            self._split(self._fresh)
+            self._fresh.zero_()
+            return self._split_follower()
         if kind == 'views':
             if self._views is None:
                 self._views = modules.BestViews(self.core, self._coverage)
@@ -110,8 +126,6 @@ class FloorCoverage:
             self._views(self._fresh)
             self._fresh.zero_()
             return self._views_follower()
-        if kind != 'frontier':
-            raise RuntimeError(f"kind must be 'frontier' or 'views'; got {kind!r}")
         if self._frontiers is None:
             self._frontiers = modules.Frontiers(self.core, self._coverage)
             self._follower = modules.PathFollower(self.core, self._frontiers, cone=15.)

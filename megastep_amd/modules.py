@@ -663,22 +663,88 @@ class LocalMap:
         return self._out[e].clone()
 
 
+class Territories:
+
+    def __init__(self, core, grid, refresh=8):
+        """Whose agent is nearest, on foot, to every cell of the floor (no counterpart in the reference): the nav grid partitioned
+        by nearest agent - a geodesic Voronoi diagram. The agents' cells are the seeds (:func:`cuda.point_marks` of their
+        positions, agent k with id k), a :func:`cuda.seeded_fields` of them the walking distance to the nearest agent, and
+        :func:`cuda.basins` of that field says which agent it is. ``basins.labels`` holds the agent's number per cell, -1 where no
+        agent can walk to; :attr:`masks` is a :class:`cuda.CellLayer` of one byte store per agent - its territory, a
+        :func:`cuda.seeded_fields` ``marks``, a gate or a :func:`cuda.map_channel` as it is. An env's territories are recomputed
+        every ``refresh`` steps and when one of its agents starts over. Nothing waits for the host: which envs are due is decided on
+        the device, so a call can sit in a HIP graph."""
+        self.core, self.grid, self.refresh = core, grid, int(refresh)
+        if self.refresh < 1:
+            raise RuntimeError(f'refresh must be a positive integer; got {refresh}')
+        n, a = core.n_envs, core.n_agents
+        self._steps = torch.zeros((n,), dtype=torch.long, device=core.device)
+        self.seeds = cuda.point_marks(grid, core.agents.positions, 1)
+        self.near = cuda.seeded_fields(grid, self.seeds.marks, 1)
+        self.basins = cuda.basins(self.near, ids=self.seeds.ids, n_ids=a)
+        self._wanted = torch.arange(a, dtype=torch.int32, device=core.device).expand(n, a).contiguous()
+        #: a :class:`cuda.CellLayer` of one byte store per agent: 1 on the cells nearest to it
+        self.masks = self.basins.masks(labels=self._wanted)
+        self._area = torch.tensor(grid.cell, dtype=torch.float32, device=core.device)**2
+
+    def __call__(self, reset=None):
+        """Recomputes the territories of the envs that are due: those with an agent marked in the (n_env, n_agent) bool ``reset``
+        and those that have taken a multiple of ``refresh`` steps since. Call once per step."""
+        if reset is not None:
+            self._steps.masked_fill_(reset.any(-1), 0)
+        due = (self._steps % self.refresh == 0)[:, None]
+        self._steps += 1
+        self.due = due                                  # ((n_env, 1) bool: whose territories were due at this call)
+        self.seeds.points = self.core.agents.positions
+        self.seeds.update()
+        self.near.update(due)
+        self.basins.update(due)
+        self.basins.masks(labels=self._wanted, out=self.masks)
+        return self.masks
+
+    def areas(self):
+        """(n_env, n_agent) float32: the floor each agent holds, in square metres."""
+        return self.basins.sizes[:, 0].float()*self._area
+
+
 class Frontiers:
 
-    def __init__(self, core, coverage, refresh=8):
+    def __init__(self, core, coverage, refresh=8, territories=None):
         """How far every agent has to walk to the nearest floor its map has not seen, and which way (no counterpart in the
         reference): the frontier fields of a :class:`Coverage`'s maps (:meth:`cuda.SeenMaps.frontier_fields`), one field per
         map. A field is recomputed every ``refresh`` steps of its agent and when the agent starts over; in between it is a
         few steps stale, which costs a detour at worst - a stale field is still a whole field, and leads to a cell that was
         unseen when it was computed. :meth:`waypoints` has the shape :class:`PathFollower` takes from :class:`Goals`. With
         ``coverage.shared`` an env has one field, which all its agents follow. Nothing waits for the host: which fields are
-        due is decided on the device, so a call can sit in a HIP graph."""
+        due is decided on the device, so a call can sit in a HIP graph.
+
+        ``territories``: a :class:`Territories` of the same core and grid, with a shared coverage: then every agent ALSO has a field
+        of its own (:attr:`own`) - the walk to the nearest unseen floor within its own territory,
+        ``seeded_fields(grid, territories.masks.values, A, where=True, among=unseen)`` - and follows that, so that an env's agents
+        part ways instead of walking to the same unseen cell; an agent whose territory holds no unseen floor follows the env's
+        shared field (:meth:`fallback`). The module calls the territories itself, once per call."""
         self.core, self.coverage, self.refresh = core, coverage, int(refresh)
         if self.refresh < 1:
             raise RuntimeError(f'refresh must be a positive integer; got {refresh}')
+        if territories is not None and not coverage.shared:
+            raise RuntimeError('territories go with a shared coverage: with a map of its own each agent has its own frontier already')
         self._steps = torch.zeros((core.n_envs, core.n_agents), dtype=torch.long, device=core.device)
         self._field = coverage._slot                    # (n_env, n_agent) zeros when the map is shared, else None: agent k field k
         self.fields = coverage.maps.frontier_fields()
+        self.territories, self.own = territories, None
+        if territories is not None:
+            maps = coverage.maps
+            self._unseen = torch.zeros_like(maps.countable)           # (grid.free's layout: the shared map is one store an env)
+            self._refresh_unseen()
+            self.own = cuda.seeded_fields(coverage.grid, territories.masks.values, core.n_agents, where=True, among=self._unseen)
+
+    def _refresh_unseen(self):
+        """unseen = ~seen & countable, in place, by byte ops on the env-layout stores."""
+        maps = self.coverage.maps
+        n = min(self._unseen.shape[0], maps.values.shape[0])
+        torch.bitwise_xor(maps.values[:n], 1, out=self._unseen[:n])
+        self._unseen[:n] &= maps.countable[:n]
+        self._unseen[:n] &= 1
 
     def __call__(self, reset=None):
         """Recomputes the fields that are due: those of the agents marked in the (n_env, n_agent) bool ``reset`` - they started
@@ -689,19 +755,35 @@ class Frontiers:
         due = self._steps % self.refresh == 0
         self._steps += 1
         self.due = due                                  # ((n_env, n_agent) bool: whose field was due at this call)
+        if self.territories is not None:
+            self.territories(reset)
+            self._refresh_unseen()
+            self.own.update(due.any(-1, keepdim=True).expand_as(due).contiguous())      # (an env's agents share the map: all or none)
         if self.coverage.shared:
             due = due.any(-1, keepdim=True)
         self.fields.update(due)
         return self.fields
 
+    @staticmethod
+    def fallback(own, shared):
+        """The rule, a pure function: ``own`` where it is a number, ``shared`` where it is NaN or +inf - an agent whose own
+        territory holds no unseen floor it can walk to follows the env's field instead."""
+        return torch.where(torch.isnan(own) | torch.isinf(own), shared, own)
+
     def distance(self):
         """(n_env, n_agent): how far every agent has to walk to the nearest unseen floor; +inf where there is none it can reach."""
-        return self.fields.at(self.core.agents.positions, goal=self._field)
+        shared = self.fields.at(self.core.agents.positions, goal=self._field)
+        if self.own is None:
+            return shared
+        return self.fallback(self.own.at(self.core.agents.positions), shared)
 
     def waypoints(self, lookahead=16):
         """(n_env, n_agent, 2): where every agent should head for now to walk to the nearest unseen floor
         (:meth:`cuda.SeededFields.waypoints`); NaN where :meth:`distance` is +inf."""
-        return self.fields.waypoints(self.core.agents.positions, goal=self._field, lookahead=lookahead)
+        shared = self.fields.waypoints(self.core.agents.positions, goal=self._field, lookahead=lookahead)
+        if self.own is None:
+            return shared
+        return self.fallback(self.own.waypoints(self.core.agents.positions, lookahead=lookahead), shared)
 
 
 class BestViews:

@@ -1,8 +1,9 @@
 """Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
 floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
 they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``,
-``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), and the cells in sight of a
-point (``csrc/kernels/navview.h``). No counterpart in the reference;
+``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), the cells in sight of a
+point (``csrc/kernels/navview.h``), and the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``). No counterpart in
+the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
@@ -326,6 +327,10 @@ class SeededFields(_Fields):
     def _paths_call(self, p, points, goal, max_points, out, counts, stream):
         spec = _lib.MsNavSeedPaths(p, points, goal, self.values.data_ptr(), self.n_goals, max_points, out, counts)
         return _lib.lib().ms_nav_seed_paths(C.byref(self.grid._struct), C.byref(spec), stream)
+
+    def basins(self, ids=None, n_ids=0, mask=None, out=None, passes=False):
+        """:func:`basins` of these fields: which seed each cell leads to."""
+        return basins(self, ids=ids, n_ids=n_ids, mask=mask, out=out, passes=passes)
 
     def update(self, mask=None):
         """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place, from :attr:`marks` as they stand now.
@@ -1086,3 +1091,217 @@ def view_fields(grid, scenery, points, max_range=10., headings=None, fov=None, c
                            torch.zeros((n, p), dtype=torch.int32, device=dev),
                            torch.zeros((n, p), dtype=torch.int32, device=dev) if unseen is not None else None)
     return views.update(mask)
+
+
+#: the cells - ``nx*ny`` - an env may have for :func:`basins` to keep its successors in LDS, for each of the kernel's three
+#: instantiations (40, 80 and 160 KiB, less the 256 size counters); the launch is the least whose capacity holds the framed cells
+#: ``(nx + 2)*(ny + 2)`` of the grid's largest env, and a larger env is jumped in global memory, to the same result
+BASIN_CAPACITY = (9968, 20208, 40688)
+#: the most ids :func:`basins` counts the sizes of
+BASIN_MAX_IDS = 256
+_INT_MAX = 2**31 - 1
+
+
+def _field_rule(field, n, p, g, what):
+    """The argument rule of a per-point ``field``: int32 (N, P) or None - then one store an env, or one per point."""
+    if field is None:
+        if g not in (1, p):
+            raise RuntimeError(f'without {what}, there must be one field per env or one per point ({p}); there are {g}')
+        return None
+    if not isinstance(field, torch.Tensor) or field.dtype.is_floating_point or field.dtype == torch.bool or field.shape != (n, p):
+        raise RuntimeError(f'{what} must be an (N, P) = ({n}, {p}) integer tensor')
+    return field.to(torch.int32).contiguous()
+
+
+class PointMarks:
+    """Result of :func:`point_marks`: the cells round each of ``points`` as the seeds of ``n_fields`` seeded fields per env.
+    ``marks``: the flat uint8 store, a byte a cell and field in the fields' layout (:func:`seeded_fields`' ``marks``) - 1 on every
+    free cell among a point's four anchors; ``ids``: the flat int32 store in the same layout - the least id of the points that
+    marked the cell, ``2**31 - 1`` where none did (:func:`basins`' ``ids``). ``points``, ``point_ids`` and ``field`` are kept by
+    reference: :meth:`update` reads them as they stand."""
+
+    def __init__(self, grid, points, n_fields, point_ids, field, marks, ids):
+        self.grid, self.points, self.point_ids, self.field, self.marks, self.ids = grid, points, point_ids, field, marks, ids
+        self._n_fields = int(n_fields)
+
+    n_fields = property(lambda self: self._n_fields)
+    n_points = property(lambda self: self.points.shape[1])
+
+    def image(self, e, g=0):
+        """(ny, nx) int32 view of the ids of store ``g`` of env ``e``, row 0 at the lowest y."""
+        s, ny, nx = self.grid.cells(e)
+        at = self.n_fields*s + g*ny*nx
+        return self.ids[at:at + ny*nx].reshape(ny, nx)
+
+    def update(self):
+        """Clears both stores and marks again in place, from :attr:`points` as they stand now - move them in place. Two fills and
+        one launch of a lane a point, no host synchronisation, nothing allocated: the call can be captured in a HIP graph."""
+        grid = self.grid
+        dev = _require_gpu(self.points, self.marks, self.ids, grid.free, *(t for t in (self.point_ids, self.field) if t is not None))
+        self.marks.zero_()
+        self.ids.fill_(_INT_MAX)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        spec = _lib.MsNavPointMarks(self.n_points, self.points.data_ptr(), ptr(self.field), ptr(self.point_ids), self.n_fields,
+                                    self.marks.data_ptr(), self.ids.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_point_marks(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return self
+
+
+def point_marks(grid, points, n_fields=1, ids=None, field=None):
+    """The cells round points as seeds: for every env ``n_fields`` mark stores, and for point (n, k) of ``points`` (N, P, 2) float32 -
+    kept by reference - mark byte 1 and id ``min(what the cell holds, id_k)`` on every FREE cell among the point's four anchors
+    (:meth:`DistanceFields.at`'s). ``ids`` (N, P) integers: the points' ids, default ``k``. ``field`` (N, P) integers: the store
+    each point marks; default the one store, or point k store k (then ``n_fields`` must be P). Two points that share an anchor leave
+    the lower id; a point without an anchor (NaN, far from the grid, a field index out of range) marks nothing.
+
+    ``seeded_fields(grid, seeds.marks, n_fields)`` is then the walking distance to the nearest point, and
+    ``basins(fields, ids=seeds.ids, n_ids=P)`` says WHICH point that is: with the agents' positions, the floor partitioned by
+    nearest agent. See :class:`PointMarks`; the rule: include/megastep_hip.h (``MsNavPointMarks``), DESIGN.md 3.22."""
+    if not isinstance(n_fields, int) or n_fields < 1:
+        raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
+    _check(points, 'points', torch.float32, 3)
+    n, p = points.shape[:2]
+    if n != grid.n_envs or points.shape[2] != 2 or p < 1:
+        raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
+    field = _field_rule(field, n, p, n_fields, 'field')
+    if ids is not None:
+        if not isinstance(ids, torch.Tensor) or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.shape != (n, p):
+            raise RuntimeError(f'ids must be an (N, P) = ({n}, {p}) integer tensor')
+        if ids.dtype != torch.int32 or not ids.is_contiguous():
+            ids = ids.to(torch.int32).contiguous()
+    dev = _require_gpu(points, grid.free, *(t for t in (ids, field) if t is not None))
+    size = max(n_fields*grid.n_cells, 1)
+    seeds = PointMarks(grid, points, n_fields, ids, field, torch.zeros(size, dtype=torch.uint8, device=dev),
+                       torch.full((size,), _INT_MAX, dtype=torch.int32, device=dev))
+    return seeds.update()
+
+
+class Basins:
+    """Result of :func:`basins`: for each field of a :class:`SeededFields` the seed every cell's path ends on. ``labels``: the flat
+    int32 store in the fields' layout (field (n, g) at ``G*grid.starts[n] + g*nx*ny``) - the row-major index within the env of the
+    seed the cell's chain of :meth:`SeededFields.paths` hops ends on, or, with ``ids``, what ``ids`` holds at that seed; -1 on a
+    blocked cell, on a cell no seed reaches and on a cell whose chain breaks (a stale field). ``sizes`` (N, G, K) int32, None without
+    ``n_ids``: the cells of each label 0..K-1; ``reached`` (N, G) int32: the cells with a label >= 0; ``passes`` (N, G) int32 or
+    None. ``fields`` and ``ids`` are kept by reference: :meth:`update` reads them as they stand. The rule: include/megastep_hip.h
+    (``MsNavBasins``), DESIGN.md 3.22."""
+
+    def __init__(self, fields, ids, n_ids, labels, sizes, reached, passes=None):
+        self.fields, self.grid, self.ids, self.n_ids = fields, fields.grid, ids, int(n_ids)
+        self.labels, self.sizes, self.reached, self.passes = labels, sizes, reached, passes
+
+    n_fields = property(lambda self: self.fields.n_goals)
+
+    def image(self, e, g=0):
+        """(ny, nx) int32 view of the labels of field ``g`` of env ``e``, row 0 at the lowest y."""
+        s, ny, nx = self.grid.cells(e)
+        at = self.n_fields*s + g*ny*nx
+        return self.labels[at:at + ny*nx].reshape(ny, nx)
+
+    def update(self, mask=None):
+        """Labels the fields marked in the (N, G) bool ``mask`` (default all) again in place, from the fields' values and
+        :attr:`ids` as they stand now; the others keep labels, sizes, reached and passes. One launch, no host synchronisation,
+        nothing allocated: the call can be captured in a HIP graph."""
+        grid, g = self.grid, self.n_fields
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, g):
+                raise RuntimeError(f'mask must be an (N, G) = ({grid.n_envs}, {g}) bool tensor')
+            mask = mask.contiguous()
+        dev = _require_gpu(self.fields.values, self.labels, self.reached, grid.free,
+                           *(t for t in (self.ids, mask, self.sizes, self.passes) if t is not None))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        spec = _lib.MsNavBasins(g, self.fields.values.data_ptr(), ptr(self.ids), self.n_ids, ptr(mask), self.labels.data_ptr(),
+                                ptr(self.sizes), self.reached.data_ptr(), ptr(self.passes))
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_basins(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return self
+
+    def at(self, points, goal=None):
+        """(N, P) int32: the label each of ``points`` (N, P, 2) leads to - that of the cell :meth:`SeededFields.paths` starts from,
+        the anchor :meth:`SeededFields.at`'s minimum is attained at; -1 exactly where that distance is +inf. ``goal`` (N, P)
+        integers name the field each point asks; default the one field, or point k field k (then P must be G). One launch, a lane
+        a point, no host synchronisation."""
+        grid = self.grid
+        _check(points, 'points', torch.float32, 3)
+        n, p = points.shape[:2]
+        if n != grid.n_envs or points.shape[2] != 2 or p < 1:
+            raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
+        goal = _field_rule(goal, n, p, self.n_fields, 'goal')
+        dev = _require_gpu(points, self.fields.values, self.labels, grid.free, *([goal] if goal is not None else []))
+        out = torch.empty((n, p), dtype=torch.int32, device=dev)
+        spec = _lib.MsNavBasinQuery(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.fields.values.data_ptr(),
+                                    self.labels.data_ptr(), self.n_fields, out.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_basin_query(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return out
+
+    def masks(self, labels, field=None, out=None):
+        """Byte masks of chosen basins, as a :class:`CellLayer` of ``P`` stores per env (store (n, p) at
+        ``P*grid.starts[n] + p*nx*ny``): a byte is 1 on the cells whose label is ``labels[n, p]`` ((N, P) integers; a negative one
+        wants none). ``field`` (N, P) integers: the field each request reads; default the one field, or request p field p.
+        ``out``: the layer of an earlier call with the same P to write into; every byte is written. With ids 0..A-1 and
+        ``labels=torch.arange(A).expand(N, A)`` the stores are the agents' territories: :func:`seeded_fields`' ``marks``, a
+        ``gate``, a :func:`map_channel` as they are. :meth:`Regions.masks`' launch (``ms_nav_region_masks``), no host
+        synchronisation."""
+        grid = self.grid
+        if not isinstance(labels, torch.Tensor) or labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.ndim != 2 or \
+                labels.shape[0] != grid.n_envs or labels.shape[1] < 1:
+            raise RuntimeError(f'labels must be an (N, P) integer tensor with N = {grid.n_envs}')
+        n, p = labels.shape
+        labels = labels.to(torch.int32).contiguous()
+        field = _field_rule(field, n, p, self.n_fields, 'field')
+        dev = _require_gpu(labels, self.labels, grid.free, *([field] if field is not None else []))
+        size = max(p*grid.n_cells, 1)
+        if out is None:
+            out = CellLayer(torch.zeros(size, dtype=torch.uint8, device=dev), p, None)
+        elif not isinstance(out, CellLayer) or out.is_float or out.n_fields != p or out.values.shape[0] != size or out.values.device != dev:
+            raise RuntimeError(f'`out` must be the layer of a masks call with the same grid and P = {p}')
+        spec = _lib.MsNavRegionMasks(p, None, labels.data_ptr(), field.data_ptr() if field is not None else None, self.labels.data_ptr(),
+                                     self.n_fields, out.values.data_ptr())
+        with _on(dev):
+            _lib.check(_lib.lib().ms_nav_region_masks(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        return out
+
+
+def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
+    """Which seed each cell of a :class:`SeededFields` leads to: for every field and every cell of its env the seed that the chain
+    of hops :meth:`SeededFields.paths` and :meth:`SeededFields.waypoints` follow from the cell ends on - as the seed's row-major cell
+    index within the env, or, with ``ids`` (a contiguous int32 tensor of one entry per cell and field in the fields' layout: a
+    :class:`PointMarks`' ``ids``, a :class:`Regions`' ``labels``), as what ``ids`` holds at that seed. With the agents' cells as seeds
+    this is the floor partitioned by nearest agent - a geodesic Voronoi diagram; with the unseen floor as seeds and
+    ``ids=maps.frontier_regions().labels``, the frontier cluster nearest to every cell. ``n_ids`` (0..256): also count, per field, the
+    cells of each label 0..n_ids-1 (``sizes``). See :class:`Basins`.
+
+    One launch, one workgroup per field: a cell's successor once, through the very hop the paths follow, then pointer jumping in LDS
+    until nothing changes; every output is an integer with one definition (include/megastep_hip.h, ``MsNavBasins``).
+    The fields' values are read as they stand: on a stale field a cell whose chain breaks gets -1, and the call still ends.
+
+    ``mask`` (N, G) bool: label only the marked fields (the others keep what ``out`` held; -1 and 0 without ``out``); ``out``: the
+    :class:`Basins` of an earlier call with the same fields, ids and n_ids to write into; ``passes=True`` also records the passes
+    each field took. A :class:`DistanceFields` is refused: a single goal's chains end on the goal's four anchors, not on a seed. No
+    host synchronisation: the call can be captured in a HIP graph."""
+    if isinstance(fields, DistanceFields):
+        raise RuntimeError("basins are of seeded fields: a DistanceFields has one goal, and its chains end on the goal's four anchors - "
+                           'nothing to tell apart')
+    if not isinstance(fields, SeededFields):
+        raise RuntimeError('fields must be a SeededFields')
+    grid, g = fields.grid, fields.n_goals
+    if not isinstance(n_ids, int) or isinstance(n_ids, bool) or not 0 <= n_ids <= BASIN_MAX_IDS:
+        raise RuntimeError(f'n_ids must be an integer in 0..{BASIN_MAX_IDS}; got {n_ids}')
+    size = max(g*grid.n_cells, 1)
+    if ids is not None:
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.ndim != 1 or not ids.is_contiguous():
+            raise RuntimeError('ids must be a contiguous 1-dimensional int32 tensor')
+        if ids.shape[0] != size:
+            raise RuntimeError(f'ids must have {size} entries, an int per cell and field (n_fields*n_cells = {g}*{grid.n_cells}); got {ids.shape[0]}')
+    if out is not None:
+        if not isinstance(out, Basins) or out.fields is not fields or out.n_ids != n_ids or (out.ids is None) != (ids is None) or \
+                (ids is not None and out.ids.data_ptr() != ids.data_ptr()):
+            raise RuntimeError('`out` must come from a basins call with the same fields, ids and n_ids')
+        return out.update(mask)
+    dev = _require_gpu(fields.values, grid.free, *([ids] if ids is not None else []))
+    shape = (grid.n_envs, g)
+    new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)
+    result = Basins(fields, ids, n_ids, new((size,), torch.int32, -1), new(shape + (n_ids,), torch.int32, 0) if n_ids else None,
+                    new(shape, torch.int32, 0), new(shape, torch.int32, 0) if passes else None)
+    return result.update(mask)

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -58,6 +58,15 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       cuda.raycast of a ring of 720 rays an env plus SeenMaps.mark of them; FloorCoverage(envs): expert('views') + step()
       eager and replayed as a HIP graph, next to expert() + step(); and FloorCoverage(64), 300 steps, in one run under
       expert('views'), expert('frontier') and uniformly random actions: episodes ended by coverage and mean final fraction.
+  (z) the basins, at `--envs` envs, the maximum and median `passes` reported for every basins call: one cuda.basins
+      (ms_nav_basins) of the frontier field right after one marked frame, its labels through ids = frontier_regions().labels, next
+      to the seeded_fields launch before it; one cuda.basins of a two-agent cuda.point_marks field with n_ids = 2, next to the
+      point_marks and seeded_fields launches before it; the torch formulation of the same rule on that field (the grids padded to
+      the largest plan, the successor index by eight shifted folds in the rule's order, then N = N[N] by gathers until nothing
+      changes, a host round trip a jump; the first `--torch-envs` envs, scaled; labels compared for equality); one Basins.at of
+      `--envs` x 1 points; FloorCoverage(envs, n_agents=2, shared=True): expert('split') + step() eager and replayed as a HIP
+      graph, next to expert() + step(); and FloorCoverage(64, n_agents=2, shared=True), 300 steps, in one run under
+      expert('split'), expert('frontier') and uniformly random actions: episodes ended by coverage and mean final fraction.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -179,6 +188,59 @@ def torch_regions(grid, envs):
                 sweeps += 1
             if torch.equal(L, before):
                 return torch.where(free, L, torch.full_like(L, -1)), sweeps
+    return run
+
+
+def torch_basins(grid, fields, ids, envs):
+    """The basins of field 0 of the first `envs` envs by tensor ops, as (envs, H*W) labels padded to the largest grid: the successor
+    of every cell by a fold over the eight shifted grids in the rule's order, then N = N[N] until nothing changes."""
+    from megastep_amd import cuda
+    geom = grid._host_geom[:envs]
+    H, W = int(geom[:, 3].max()) + 2, int(geom[:, 2].max()) + 2
+    dev = grid.free.device
+    inf = float('inf')
+    c = torch.tensor(grid.cell, dtype=torch.float32, device=dev)
+    ws, wd = c, c*torch.tensor(1.41421356, dtype=torch.float32, device=dev)
+    free = torch.zeros((envs, H, W), dtype=torch.bool, device=dev)
+    D = torch.full((envs, H, W), inf, dtype=torch.float32, device=dev)
+    name = torch.full((envs, H, W), -1, dtype=torch.int32, device=dev)   # (what a cell's label is when a chain ends on it)
+    g = fields.n_goals
+    for e in range(envs):
+        s, ny, nx = grid.cells(e)
+        free[e, 1:ny + 1, 1:nx + 1] = grid.free[s:s + ny*nx].reshape(ny, nx).bool()
+        D[e, 1:ny + 1, 1:nx + 1] = fields.values[g*s:g*s + ny*nx].reshape(ny, nx)
+        name[e, 1:ny + 1, 1:nx + 1] = (ids[g*s:g*s + ny*nx] if ids is not None else torch.arange(ny*nx, dtype=torch.int32, device=dev)).reshape(ny, nx)
+    own = torch.arange(H*W, device=dev).reshape(1, H, W).expand(envs, H, W)
+    dead = H*W                                                           # (one more slot an env, which names itself)
+
+    def shifted(t, di, dj, fill):
+        out = torch.full_like(t, fill)
+        out[:, max(-di, 0):H + min(-di, 0), max(-dj, 0):W + min(-dj, 0)] = t[:, max(di, 0):H + min(di, 0), max(dj, 0):W + min(dj, 0)]
+        return out
+
+    def run():
+        best, below = torch.full_like(D, inf), torch.full_like(D, inf)
+        target = torch.full((envs, H, W), dead, dtype=torch.int64, device=dev)
+        for di, dj in ((0, 1), (1, 0), (0, -1), (-1, 0), (1, 1), (1, -1), (-1, -1), (-1, 1)):
+            ok = shifted(free, di, dj, False)
+            if di and dj:
+                ok = ok & shifted(free, di, 0, False) & shifted(free, 0, dj, False)
+            du = shifted(D, di, dj, inf)
+            v = torch.where(ok, du + (wd if di and dj else ws), torch.full_like(D, inf))
+            take = v < best
+            best, below, target = torch.where(take, v, best), torch.where(take, du, below), torch.where(take, own + (di*W + dj), target)
+        succ = torch.where(D == 0, own, torch.where(below < D, target, torch.full_like(target, dead)))
+        succ = torch.where(free & (D < inf), succ, torch.full_like(succ, dead))
+        N = torch.cat([succ.reshape(envs, -1), torch.full((envs, 1), dead, dtype=torch.int64, device=dev)], 1)
+        jumps = 0
+        while True:
+            new = N.gather(1, N)
+            jumps += 1
+            if torch.equal(new, N):
+                break
+            N = new
+        names = torch.cat([name.reshape(envs, -1), torch.full((envs, 1), -1, dtype=torch.int32, device=dev)], 1)
+        return names.gather(1, N)[:, :-1].reshape(envs, H, W), jumps
     return run
 
 
@@ -454,7 +516,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins'))
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
@@ -840,6 +902,66 @@ def main():
             torch.manual_seed(3); np.random.seed(3)
             out['coverage_' + policy] = score = coverage_score(FloorCoverage(64, geometries=small, max_lifespan=300), 300, policy)
             print(f'(v) FloorCoverage(64), 300 steps, {policy}: {score}')
+
+    if want('basins'):
+        from megastep_amd.demo.envs.floorcoverage import reachable
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        passes = lambda b: dict(passes_most=int(b.passes.max()), passes_median=int(b.passes.median()))
+        maps = cuda.seen_maps(grid, 1, reachable(grid, table[:, 0, 0].contiguous()))
+        maps.mark_render(c.agents, cuda.render(sc, c.agents, fields=('distances',)))
+        frontier, clusters = maps.frontier_fields(passes=True), maps.frontier_regions()
+        fmed, flo, fhi = timed(lambda: frontier.update(), args.repeats, args.warmup)
+        b = cuda.basins(frontier, ids=clusters.labels, passes=True)
+        med, lo, hi = timed(lambda: b.update(), args.repeats, args.warmup)
+        out['basins_frontier'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, seeded_fields_seconds=fmed, seeded_fields_min=flo,
+                                      seeded_fields_max=fhi, reached_mean=float(b.reached.float().mean()), clusters_mean=float(clusters.counts.float().mean()),
+                                      **passes(b))
+        print(f"(z) basins of the frontier field, {args.envs} maps after one frame: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}] next to "
+              f"seeded_fields {fmed*1e3:.3f} ms; {out['basins_frontier']}")
+        points = table[:, 0, 1:3].contiguous()                          # (two points an env: the two agents)
+        seeds = cuda.point_marks(grid, points, n_fields=1)
+        near = cuda.seeded_fields(grid, seeds.marks, 1, passes=True)
+        own = cuda.basins(near, ids=seeds.ids, n_ids=2, passes=True)
+        smed, slo, shi = timed(lambda: seeds.update(), args.repeats, args.warmup)
+        nmed, nlo, nhi = timed(lambda: near.update(), args.repeats, args.warmup)
+        med, lo, hi = timed(lambda: own.update(), args.repeats, args.warmup)
+        out['basins_two_agents'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, point_marks_seconds=smed, seeded_fields_seconds=nmed,
+                                        seeded_fields_min=nlo, seeded_fields_max=nhi, smaller_share_mean=float((own.sizes[:, 0].min(-1).values.float()
+                                                                                                           / own.reached[:, 0].clamp(min=1).float()).mean()),
+                                        field_passes_most=int(near.passes.max()), **passes(own))
+        print(f"(z) basins of a two-agent point_marks field, {args.envs} envs, n_ids=2: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}] next to point_marks "
+              f"{smed*1e6:.1f} us and seeded_fields {nmed*1e3:.3f} ms; {out['basins_two_agents']}")
+        k = min(args.torch_envs, args.envs)
+        run = torch_basins(grid, near, seeds.ids, k)
+        L, jumps = run()
+        same = all(torch.equal(L[e, 1:grid.cells(e)[1] + 1, 1:grid.cells(e)[2] + 1], own.image(e)) for e in range(k))
+        tmed = timed(lambda: run(), max(args.repeats//3, 2), 1)[0]
+        out['basins_torch'] = dict(envs=k, seconds=tmed, scaled_seconds=tmed*args.envs/k, jumps=jumps, equal_labels=bool(same))
+        print(f'(z) torch successors and N = N[N], {k} grids: {tmed*1e3:.1f} ms, {jumps} jumps -> {tmed*args.envs/k*1e3:.1f} ms for {args.envs}; equal labels: {same}')
+        spot = table[:, 0, 3:4].contiguous()
+        amed, alo, ahi = timed(lambda: own.at(spot), 5*args.repeats, args.warmup)
+        out['basins_at'] = dict(seconds=amed, min=alo, max=ahi, points=args.envs)
+        print(f'(z) Basins.at, {args.envs} x 1 points: {amed*1e6:.1f} us [{alo*1e6:.1f}, {ahi*1e6:.1f}]')
+        del sc, c, grid, maps, frontier, clusters, b, seeds, near, own, run, L
+        torch.cuda.empty_cache()
+        for name, kind in (('FloorCoverage_shared_split_expert', ('split',)), ('FloorCoverage_shared_frontier_expert', ())):
+            env = ExpertStep(FloorCoverage(args.envs, n_agents=2, shared=True, geometries=geoms), *kind)
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[name] = dict(expert_step_eager_seconds=eager, expert_step_graph_seconds=graphed)
+            print(f'(z) {name}({args.envs}, n_agents=2): expert + step eager {eager*1e3:.3f} ms, graph {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+        small = cubicasa.sample(64, seed=7, n_unique=64)
+        for policy in ('split', 'frontier', 'random'):
+            torch.manual_seed(3); np.random.seed(3)
+            env = FloorCoverage(64, n_agents=2, shared=True, geometries=small, max_lifespan=300)
+            out['shared_coverage_' + policy] = score = coverage_score(env, 300, policy)
+            print(f'(z) FloorCoverage(64, n_agents=2, shared=True), 300 steps, {policy}: {score}')
 
     if args.json:
         with open(args.json, 'w') as f:
