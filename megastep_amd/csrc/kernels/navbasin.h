@@ -1,7 +1,7 @@
 // kernels/navbasin.h -- nav_basin_kernel, nav_basin_query_kernel, nav_point_mark_kernel.
 // Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after navpath.h, whose NavEnv,
-// nav_seeded, nav_hop and nav_start it follows the fields with, and navregion.h, whose region_load / region_store / region_field it
-// shares); not a header to compile on its own.
+// nav_seeded, nav_hop and nav_start it follows the fields with; the grid, the relaxed loads and stores, the store rule and the
+// settle loop are navfield.h's); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // basins: the seed each cell's path ends on                                 no counterpart in the reference
 // ------------------------------------------------------------------------------------------------
@@ -15,7 +15,7 @@
 //                       a seed names itself; a blocked, unreachable or broken cell holds BASIN_DEAD (-1), which no jump follows.
 //                       Then it pointer-jumps IN PLACE, N[k] = N[N[k]] (basin_jump), through relaxed workgroup-scope atomics -
 //                       the lanes race, on purpose - one barrier a pass carrying the "something changed" flag
-//                       (nav_passes_framed's three rotating slots), until a pass changes nothing.
+//                       (nav_settle's three rotating slots), until a pass changes nothing.
 //                       INVARIANT: read BASIN_DEAD as one more cell at the far end of every broken chain.  Every value a slot
 //                       ever holds is a cell of its own chain, at or beyond its successor (succ(k): yes; N[v] for such a v: v is on
 //                       k's chain, what v's slot holds is on v's chain at or beyond succ(v), so on k's beyond v, by induction -
@@ -46,10 +46,16 @@ __host__ __device__ inline int basin_succ(const NavEnv& g, const int k) {
 }
 
 // What one pass makes of slot k, which holds v: N[v] - v when v is dead already.
-__host__ __device__ inline int basin_jump(const int* N, const int v) { return v < 0 ? v : region_load(N + v); }
+__host__ __device__ inline int basin_jump(const int* N, const int v) { return v < 0 ? v : nav_load(N + v); }
 
 // The label of a cell whose slot ended on `end`: -1 dead, the seed's index, or - with ids, the field's store - what it holds there.
 __host__ __device__ inline int basin_label(const int end, const int* ids) { return end < 0 ? -1 : ids ? ids[end] : end; }
+
+// Env e's grid with one of its fields, as navpath.h's pieces read them.
+__host__ __device__ inline NavEnv basin_env(const NavArgs& a, const int e, const unsigned char* free_cells, const float* D) {
+    const NavCells c = nav_cells(a, e);
+    return NavEnv{c.jx0, c.iy0, c.nx, c.ny, c.c, free_cells + a.starts[e], D};
+}
 
 struct NavBasinArgs {                                // MsNavBasins, checked
     const unsigned char* free_cells;
@@ -67,14 +73,13 @@ struct NavBasinArgs {                                // MsNavBasins, checked
 // copy when the env fits `capacity` cells, else in its labels store.
 inline void basin_serial_field(const NavArgs& a, const NavBasinArgs& b, const long long field, const int capacity) {
     const int e = (int)(field / b.n_fields), gi = (int)(field - (long long)e*b.n_fields);
-    const int nx = a.geom[4*e + 2], ny = a.geom[4*e + 3];
-    const long long cells = nx > 0 && ny > 0 ? (long long)nx*ny : 0;
+    const long long cells = nav_count(a, e);
     int* const sizes = b.n_ids ? b.sizes + field*b.n_ids : nullptr;
     for (int k = 0; k < b.n_ids; k++) sizes[k] = 0;
     int passes = 0, reached = 0;
     if (cells > 0) {
         const long long first = (long long)b.n_fields*a.starts[e] + (long long)gi*cells;
-        const NavEnv g{a.geom[4*e], a.geom[4*e + 1], nx, ny, a.cell, b.free_cells + a.starts[e], b.fields + first};
+        const NavEnv g = basin_env(a, e, b.free_cells, b.fields + first);
         const int* const ids = b.ids ? b.ids + first : nullptr;
         int* const out = b.labels + first;
         std::vector<int> copy(cells <= capacity ? (size_t)cells : 0);
@@ -85,7 +90,7 @@ inline void basin_serial_field(const NavArgs& a, const NavBasinArgs& b, const lo
             changed = false;
             for (int k = 0; k < n; k++) {
                 const int v = N[k], w = basin_jump(N, v);
-                if (w != v) { region_store(N + k, w); changed = true; }
+                if (w != v) { nav_store(N + k, w); changed = true; }
             }
         }
         for (int k = 0; k < n; k++) {
@@ -102,27 +107,6 @@ inline void basin_serial_field(const NavArgs& a, const NavBasinArgs& b, const lo
 inline void basin_serial(const NavArgs& a, const NavBasinArgs& b, const int capacity) {
     for (long long field = 0; field < (long long)a.n_envs*b.n_fields; field++)
         if (!b.mask || b.mask[field]) basin_serial_field(a, b, field, capacity);
-}
-
-// The jumps on the n slots of N (LDS, or the labels store in global memory): until a pass changes nothing; returns the passes
-// taken.  s_flag[0..2] start zeroed, behind a barrier.
-template <int THREADS>
-__device__ inline int basin_passes(int* N, int* s_flag, const int n) {
-    const int tid = threadIdx.x;
-    int passes = 0;
-    for (;;) {
-        if (tid == 0) s_flag[(passes + 1) % 3] = 0;                     // (last read two barriers ago)
-        bool changed = false;
-        for (int k = tid; k < n; k += THREADS) {
-            const int v = region_load(N + k), w = basin_jump(N, v);
-            if (w != v) { region_store(N + k, w); changed = true; }
-        }
-        if (changed) s_flag[passes % 3] = 1;
-        __syncthreads();                                                // (the workgroup's stores are visible to its loads from here on)
-        const int again = s_flag[passes % 3];
-        passes++;
-        if (!again) return passes;                                      // (uniform)
-    }
 }
 
 // One cell's share of the sizes: a cell whose label is in 0 .. K - 1 adds one to that counter - one atomic for the wave where all
@@ -170,15 +154,19 @@ __global__ __launch_bounds__(THREADS) void nav_basin_kernel(const NavArgs a, con
     if (tid == 0) s_reached = 0;
     if (tid < BASIN_MAX_IDS) s_size[tid] = 0;
     int* const slots = cells <= CAP ? N : out;                          // (uniform) in LDS, or where the labels are stored
-    for (int k = tid; k < n; k += THREADS) region_store(slots + k, basin_succ(g, k));
+    for (int k = tid; k < n; k += THREADS) nav_store(slots + k, basin_succ(g, k));
     __syncthreads();
-    const int passes = basin_passes<THREADS>(slots, s_flag, n);
+    const int passes = nav_settle<THREADS>(s_flag, n, [=](const int k) {         // the jumps, in LDS or on the labels store
+        const int v = nav_load(slots + k), w = basin_jump(slots, v);
+        if (w != v) nav_store(slots + k, w);
+        return w != v;
+    });
     int reached = 0;
     for (int k0 = 0; k0 < n; k0 += THREADS) {                           // (whole waves go round: basin_count ballots)
         const int k = k0 + tid;
         int label = -1;
         if (k < n) {
-            label = basin_label(region_load(slots + k), ids);           // (a slot is read and written by its own lane only from here on)
+            label = basin_label(nav_load(slots + k), ids);              // (a slot is read and written by its own lane only from here on)
             out[k] = label;
             reached += label >= 0;
         }
@@ -208,16 +196,15 @@ struct NavBasinQueryArgs {                           // MsNavBasinQuery, checked
 // Point `at` = (e, k): the label under the anchor nav_start picks on the field it asks; -1 without one.
 __host__ __device__ inline void basin_query_one(const NavArgs& a, const NavBasinQueryArgs& q, const long long at) {
     const int e = (int)(at / q.n_points), k = (int)(at - (long long)e*q.n_points);
-    const int nx = a.geom[4*e + 2], ny = a.geom[4*e + 3];
-    const long long cells = nx > 0 && ny > 0 ? (long long)nx*ny : 0;
-    const int f = region_field(q.field, q.n_fields, at, k);
+    const long long cells = nav_count(a, e);
+    const int f = nav_layer_store(q.field, q.n_fields, at, k);
     int label = -1;
     if ((f >= 0) & (cells > 0)) {
         const long long first = (long long)q.n_fields*a.starts[e] + (long long)f*cells;
-        const NavEnv g{a.geom[4*e], a.geom[4*e + 1], nx, ny, a.cell, q.free_cells + a.starts[e], q.fields + first};
+        const NavEnv g = basin_env(a, e, q.free_cells, q.fields + first);
         int i = 0, j = 0;
         float leg0;
-        if (nav_start(g, q.points[2*at], q.points[2*at + 1], i, j, leg0)) label = q.labels[first + (long long)i*nx + j];
+        if (nav_start(g, q.points[2*at], q.points[2*at + 1], i, j, leg0)) label = q.labels[first + (long long)i*g.nx + j];
     }
     q.out[at] = label;
 }
@@ -241,11 +228,13 @@ struct NavPointMarkArgs {                            // MsNavPointMarks, checked
 // Point `at` = (e, k): every free cell among its four anchors gets mark byte 1 and the least of its id and the point's.
 __host__ __device__ inline void point_mark_one(const NavArgs& a, const NavPointMarkArgs& q, const long long at) {
     const int e = (int)(at / q.n_points), k = (int)(at - (long long)e*q.n_points);
-    const int nx = a.geom[4*e + 2], ny = a.geom[4*e + 3];
-    const long long cells = nx > 0 && ny > 0 ? (long long)nx*ny : 0;
-    const int f = region_field(q.field, q.n_fields, at, k);
+    const long long cells = nav_count(a, e);
+    const int f = nav_layer_store(q.field, q.n_fields, at, k);
+    if ((f < 0) | (cells <= 0)) return;
+    const NavCells c = nav_cells(a, e);
+    const int nx = c.nx, ny = c.ny;
     long long i0, j0;
-    if ((f < 0) | (cells <= 0) || !nav_anchor_corner(q.points[2*at], q.points[2*at + 1], a.cell, a.geom[4*e], a.geom[4*e + 1], i0, j0)) return;
+    if (!nav_anchor_corner(q.points[2*at], q.points[2*at + 1], c.c, c.jx0, c.iy0, i0, j0)) return;
     const unsigned char* const fr = q.free_cells + a.starts[e];
     const long long first = (long long)q.n_fields*a.starts[e] + (long long)f*cells;
     const int id = q.point_ids ? q.point_ids[at] : k;

@@ -1,6 +1,6 @@
 // kernels/navdraw.h -- nav_draw_kernel.
-// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after navwindow.h, whose
-// win_store picks the store a set reads in a layer); not a header to compile on its own.
+// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after navwindow.h; the
+// store a set reads in a layer is navfield.h's nav_layer_store); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // cell draws: uniform random free cells of an env that satisfy a predicate on a layer      no counterpart in the reference
 // ------------------------------------------------------------------------------------------------
@@ -90,8 +90,8 @@ struct NavDrawArgs {                                 // MsNavDraws, checked
 // The stores set (n, p) reads, from the env's first cell on; false: a field index is bad, nothing qualifies.
 __host__ __device__ inline bool draw_stores(const NavDrawArgs& q, const long long first, const long long cells, const long long set, const int p,
                                             const void*& source, const unsigned char*& gate) {
-    const int fs = win_store(q.source_field, q.source_fields, set, p);
-    const int fg = q.gate ? win_store(q.gate_field, q.gate_fields, set, p) : 0;
+    const int fs = nav_layer_store(q.source_field, q.source_fields, set, p);
+    const int fg = q.gate ? nav_layer_store(q.gate_field, q.gate_fields, set, p) : 0;
     if ((fs < 0) | (fg < 0)) return false;
     const long long at = (long long)q.source_fields*first + (long long)fs*cells;
     source = q.is_float ? static_cast<const void*>(static_cast<const float*>(q.source) + at)
@@ -101,7 +101,7 @@ __host__ __device__ inline bool draw_stores(const NavDrawArgs& q, const long lon
 }
 
 // Draw k of set `set`: cell = the chosen cell, -1 when M = 0.
-__host__ __device__ inline void draw_write(const NavDrawArgs& q, const SeenGrid& g, const void* source, const long long set, const int k,
+__host__ __device__ inline void draw_write(const NavDrawArgs& q, const NavCells& g, const void* source, const long long set, const int k,
                                            const unsigned counter, const long long cell) {
     const long long at = set*q.n_draws + k;
     q.cells[at] = (int)cell;
@@ -124,7 +124,7 @@ inline void draw_serial(const NavArgs& a, const NavDrawArgs& q) {
     for (long long set = 0; set < (long long)a.n_envs*q.n_sets; set++) {
         if (q.mask && !q.mask[set]) continue;
         const int e = (int)(set / q.n_sets), p = (int)(set - (long long)e*q.n_sets);
-        const SeenGrid g{a.geom[4*e], a.geom[4*e + 1], a.geom[4*e + 2], a.geom[4*e + 3], a.cell};
+        const NavCells g = nav_cells(a, e);
         long long cells = g.nx > 0 && g.ny > 0 ? (long long)g.nx*g.ny : 0;
         if (cells > q.max_cells) cells = 0;
         const void* source = nullptr;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(WG) void nav_draw_kernel(const NavArgs a, const Nav
     if (q.mask && !q.mask[set]) return;                                 // (uniform) not touched at all
     const int e = (int)(set / q.n_sets), p = (int)(set - (long long)e*q.n_sets);
     const int4 geom = reinterpret_cast<const int4*>(a.geom)[e];
-    const SeenGrid g{geom.x, geom.y, geom.z, geom.w, a.cell};
+    const NavCells g{geom.x, geom.y, geom.z, geom.w, a.cell};
     long long cells = geom.z > 0 && geom.w > 0 ? (long long)geom.z*geom.w : 0;
     if (cells > q.max_cells) cells = 0;                                 // (uniform) more than the launch has bits for
     const unsigned counter = (unsigned)q.counter[set];                  // (read by every lane before the first barrier)

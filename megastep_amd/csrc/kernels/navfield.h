@@ -37,7 +37,26 @@ struct NavArgs {                                     // MsNavGrid, checked
     float cell, clearance;
 };
 
+// One env's grid as the per-cell pieces read it.
+struct NavCells { int jx0, iy0, nx, ny; float c; };
+__host__ __device__ inline NavCells nav_cells(const NavArgs& a, const int e) {
+    return NavCells{a.geom[4*e], a.geom[4*e + 1], a.geom[4*e + 2], a.geom[4*e + 3], a.cell};
+}
+// Env e's cells, 0 without any: all that a piece which may have nothing to do reads of the grid before it knows.
+__host__ __device__ inline long long nav_count(const NavArgs& a, const int e) {
+    const int nx = a.geom[4*e + 2], ny = a.geom[4*e + 3];
+    return nx > 0 && ny > 0 ? (long long)nx*ny : 0;
+}
+
 __host__ __device__ inline float nav_centre(const int origin, const int k, const float c) { return ((float)(origin + k) + .5f)*c; }
+__host__ __device__ inline bool nav_finite(const float v) { return fabsf(v) < INFINITY; }
+
+// The store item k of its env - a view, a draw set, a point, a request; `at` = (n, k) - reads in a layer of n_fields stores
+// (MsNavLayer's rule): the one `field` names, else the env's one store or store k; -1: a bad index.
+__host__ __device__ inline int nav_layer_store(const int* field, const int n_fields, const long long at, const int k) {
+    const int f = field ? field[at] : (n_fields == 1 ? 0 : k);
+    return ((f >= 0) & (f < n_fields)) ? f : -1;
+}
 
 // The cell (i0, j0) whose centre is the last at or below p on both axes - p's anchors are (i0 + {0, 1}, j0 + {0, 1}); false:
 // p has none (NaN, or further out than any grid).
@@ -54,15 +73,45 @@ __host__ __device__ inline float nav_leg(const float x, const float y, const int
 }
 
 // Racy by design (see above): relaxed atomics are plain loads and stores that the compiler may not invent, merge or carry
-// across passes.
-__host__ __device__ inline float nav_load(const float* p) {
+// across passes.  For the fields' floats and for the labels' and successors' ints (navregion.h, navbasin.h).
+template <class T>
+__host__ __device__ inline T nav_load(const T* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #else
     return *p;                                       // (the host instantiations sweep serially)
 #endif
 }
-__device__ inline void nav_store(float* p, const float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+template <class T>
+__host__ __device__ inline void nav_store(T* p, const T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#else
+    *p = v;
+#endif
+}
+
+// The settle loop of every kernel that sweeps to a fixed point (the relaxation here, navregion.h's labels, navbasin.h's jumps):
+// lane tid takes items tid, tid + T, ... of n, `cell(k)` says whether it changed item k, and the sweeps end with the first that
+// changed nothing; returns the passes taken.  One barrier a pass carries the "something changed" flag through three rotating
+// slots - a pass sets its own, reads it behind the barrier and clears the next one's, which was last read two barriers ago - and
+// makes the workgroup's stores visible to its loads.  s_flag[0..2] start zeroed, behind a barrier.
+template <int THREADS, class Index, class Cell>
+__device__ inline int nav_settle(int* s_flag, const Index n, const Cell cell) {
+    const int tid = threadIdx.x;
+    int passes = 0;
+    for (;;) {
+        if (tid == 0) s_flag[(passes + 1) % 3] = 0;
+        bool changed = false;
+        for (Index k = tid; k < n; k += THREADS)
+            if (cell(k)) changed = true;
+        if (changed) s_flag[passes % 3] = 1;
+        __syncthreads();
+        const int again = s_flag[passes % 3];
+        passes++;
+        if (!again) return passes;                                      // (uniform)
+    }
+}
 
 __global__ __launch_bounds__(WG) void nav_free_kernel(const MsScenery sc, const NavArgs a, unsigned char* free_cells) {
     __shared__ float4 s_rows[WG];
@@ -157,53 +206,6 @@ __host__ __device__ inline float nav_cell_stored(const float* out, const unsigne
     return nav_relaxed(d, st, fminf(fminf(nw, ne), fminf(sw, se)), ws, wd);
 }
 
-// The passes, shared by the single-goal and the seeded kernel: relax in place until a pass lowers nothing; returns the passes
-// taken.  s_flag[0..2] start zeroed, behind a barrier.
-template <int THREADS>
-__device__ inline int nav_passes_framed(float* s_d, const unsigned char* s_m, int* s_flag, const int n, const int P, const float ws, const float wd) {
-    const int tid = threadIdx.x;
-    int passes = 0;
-    for (;;) {
-        if (tid == 0) s_flag[(passes + 1) % 3] = 0;                     // (last read two barriers ago)
-        bool changed = false;
-        for (int k = tid; k < n; k += THREADS) {
-            const int m = s_m[k];
-            if (m & 1) {
-                const float d = nav_load(s_d + k);
-                const float v = nav_cell_framed(s_d, m, k, P, d, ws, wd);
-                if (v < d) { nav_store(s_d + k, v); changed = true; }
-            }
-        }
-        if (changed) s_flag[passes % 3] = 1;
-        __syncthreads();
-        const int again = s_flag[passes % 3];
-        passes++;
-        if (!again) return passes;                                      // (uniform)
-    }
-}
-
-template <int THREADS>
-__device__ inline int nav_passes_stored(float* out, const unsigned char* fr, int* s_flag, const long long cells, const int nx, const int ny, const float ws,
-                                        const float wd) {
-    const int tid = threadIdx.x;
-    int passes = 0;
-    for (;;) {
-        if (tid == 0) s_flag[(passes + 1) % 3] = 0;
-        bool changed = false;
-        for (long long k = tid; k < cells; k += THREADS) {
-            if (!(fr[k] & 1)) continue;
-            const float d = nav_load(out + k);
-            const float v = nav_cell_stored(out, fr, nx, ny, k, d, ws, wd);
-            if (v < d) { nav_store(out + k, v); changed = true; }
-        }
-        if (changed) s_flag[passes % 3] = 1;
-        __syncthreads();                                                // (the workgroup's stores are visible to its loads from here on)
-        const int again = s_flag[passes % 3];
-        passes++;
-        if (!again) return passes;
-    }
-}
-
 // SEEDED: the field's sources are the cells nav_is_seed names (value +0.f) instead of a goal's anchors (value: their leg).  A
 // seed keeps bit 5 of its byte; the seeds are counted a wave at a time - one ballot a round, one LDS atomic a wave - into
 // s_flag[3].
@@ -269,7 +271,13 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
             }
         }
         __syncthreads();
-        passes = nav_passes_framed<THREADS>(s_d, s_m, s_flag, n, P, ws, wd);
+        passes = nav_settle<THREADS>(s_flag, n, [=](const int k) {
+            const int m = s_m[k];
+            if (!(m & 1)) return false;
+            const float d = nav_load(s_d + k), v = nav_cell_framed(s_d, m, k, P, d, ws, wd);
+            if (v < d) nav_store(s_d + k, v);
+            return v < d;
+        });
         for (long long k = tid; k < cells; k += THREADS) {
             const int i = (int)(k / nx), j = (int)(k - (long long)i*nx);
             out[k] = s_d[(i + 1)*P + j + 1];
@@ -293,7 +301,12 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
             if ((i >= 0) & (i < ny) & (j >= 0) & (j < nx) && (fr[i*nx + j] & 1)) out[i*nx + j] = nav_leg(p.x, p.y, g.x, g.y, (int)i, (int)j, c);
         }
         __syncthreads();
-        passes = nav_passes_stored<THREADS>(out, fr, s_flag, cells, nx, ny, ws, wd);
+        passes = nav_settle<THREADS>(s_flag, cells, [=](const long long k) {
+            if (!(fr[k] & 1)) return false;
+            const float d = nav_load(out + k), v = nav_cell_stored(out, fr, nx, ny, k, d, ws, wd);
+            if (v < d) nav_store(out + k, v);
+            return v < d;
+        });
     }
     if (f.passes && tid == 0) f.passes[field] = passes;
     if (SEEDED && f.n_seeds && tid == 0) f.n_seeds[field] = s_flag[FLAGS - 1];

@@ -1,6 +1,6 @@
 // kernels/navregion.h -- nav_region_kernel, nav_region_query_kernel, nav_region_mask_kernel.
 // Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after navfield.h, whose
-// NavArgs, nav_is_seed, nav_anchor_corner and loop control it shares); not a header to compile on its own.
+// NavArgs, NavCells, nav_is_seed, nav_anchor_corner, nav_load / nav_store, nav_layer_store and settle loop it shares); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // regions: the connected spaces of the nav grid, labelled                   no counterpart in the reference
 // ------------------------------------------------------------------------------------------------
@@ -26,7 +26,7 @@
 //                       cell's at most its neighbours': every component is constant, at a value m that is one of its cells and
 //                       at most the index of every cell of it - its least index, whatever the schedule.  The jump is what turns
 //                       a corridor's hundreds of passes into a handful: a lowered label is handed on through L, not cell by cell.
-//                       One barrier a pass carries the "something changed" flag (nav_passes_framed's three rotating slots).
+//                       One barrier a pass carries the "something changed" flag (nav_settle's three rotating slots).
 //                       AFTER the fixed point the sizes are counted IN PLACE: a root (L[k] == k) turns its slot into -1, every
 //                       other open cell subtracts one from its root's slot - an integer LDS atomic, one a wave where the wave's
 //                       cells share a root - so that a root's slot holds -(cells of its component) and every other slot still
@@ -42,21 +42,6 @@
 //                       labels and stores of the bytes contiguous; every byte of the store is written, the zeros too.
 constexpr int region_capacity(const int lds_bytes) { return (lds_bytes - 64)/4; }      // framed cells: an int each
 
-__host__ __device__ inline int region_load(const int* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    return *p;                                       // (the host instantiations sweep serially)
-#endif
-}
-__host__ __device__ inline void region_store(int* p, const int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    *p = v;
-#endif
-}
-
 // Is cell k of its env open: free (marks NULL), or a seed of MsNavSeedFields' rule - nav_is_seed, the very function.
 __host__ __device__ inline bool region_open(const unsigned char* fr, const unsigned char* among, const unsigned char* marks, const long long k,
                                             const int where) {
@@ -71,7 +56,7 @@ __host__ __device__ inline int region_fill(const bool open, const int index) { r
 // v, jumped: L[v], L[L[v]], ... while that lowers (v is an open cell's index; the values only fall, so this ends).
 __host__ __device__ inline int region_jump(const int* L, int v) {
     for (;;) {
-        const int w = region_load(L + v);
+        const int w = nav_load(L + v);
         if (w >= v) return v;
         v = w;
     }
@@ -79,8 +64,8 @@ __host__ __device__ inline int region_jump(const int* L, int v) {
 
 // What one pass makes of open cell k (value own) of the framed labels: the least of its own and its four neighbours', jumped.
 __host__ __device__ inline int region_lowered_framed(const int* L, const int k, const int P, const int own) {
-    const int v = region_min(region_min(own, region_min(region_load(L + k - 1), region_load(L + k + 1))),
-                             region_min(region_load(L + k - P), region_load(L + k + P)));
+    const int v = region_min(region_min(own, region_min(nav_load(L + k - 1), nav_load(L + k + 1))),
+                             region_min(nav_load(L + k - P), nav_load(L + k + P)));
     return region_jump(L, v);
 }
 
@@ -88,10 +73,10 @@ __host__ __device__ inline int region_lowered_framed(const int* L, const int k, 
 __host__ __device__ inline int region_lowered_stored(const int* L, const int nx, const int ny, const long long k, const int own) {
     const int i = (int)(k / nx), j = (int)(k - (long long)i*nx);
     int v = own;
-    if (j > 0) v = region_min(v, region_load(L + k - 1));
-    if (j < nx - 1) v = region_min(v, region_load(L + k + 1));
-    if (i > 0) v = region_min(v, region_load(L + k - nx));
-    if (i < ny - 1) v = region_min(v, region_load(L + k + nx));
+    if (j > 0) v = region_min(v, nav_load(L + k - 1));
+    if (j < nx - 1) v = region_min(v, nav_load(L + k + 1));
+    if (i > 0) v = region_min(v, nav_load(L + k - nx));
+    if (i < ny - 1) v = region_min(v, nav_load(L + k + nx));
     return region_jump(L, v);
 }
 
@@ -126,22 +111,15 @@ __host__ __device__ inline unsigned long long region_key(const int cells, const 
 __host__ __device__ inline int region_key_label(const unsigned long long key) { return key ? INT_MAX - (int)(unsigned)(key & 0xffffffffull) : -1; }
 __host__ __device__ inline int region_key_cells(const unsigned long long key) { return (int)(key >> 32); }
 
-// The store request / point k of env e reads (MsNavLayer's rule); -1: a bad index.
-__host__ __device__ inline int region_field(const int* field, const int n_fields, const long long at, const int k) {
-    const int f = field ? field[at] : (n_fields == 1 ? 0 : k);
-    return ((f >= 0) & (f < n_fields)) ? f : -1;
-}
-
 // The labels under the four anchors of (x, y), in the order i0 + (t>>1), j0 + (t&1); -1 outside the grid and on a closed cell
 // (which holds -1).  `labels`: the field's store, or NULL (a bad field index, an env without cells): all -1.
-__host__ __device__ inline void region_anchor_labels(const int* labels, const int jx0, const int iy0, const int nx, const int ny, const float c,
-                                                     const float x, const float y, int out[4]) {
+__host__ __device__ inline void region_anchor_labels(const int* labels, const NavCells& g, const float x, const float y, int out[4]) {
     out[0] = out[1] = out[2] = out[3] = -1;
     long long i0, j0;
-    if (!labels || !nav_anchor_corner(x, y, c, jx0, iy0, i0, j0)) return;
+    if (!labels || !nav_anchor_corner(x, y, g.c, g.jx0, g.iy0, i0, j0)) return;
     for (int t = 0; t < 4; t++) {
         const long long i = i0 + (t >> 1), j = j0 + (t & 1);
-        if ((i >= 0) & (i < ny) & (j >= 0) & (j < nx)) out[t] = labels[i*nx + j];
+        if ((i >= 0) & (i < g.ny) & (j >= 0) & (j < g.nx)) out[t] = labels[i*g.nx + j];
     }
 }
 
@@ -181,7 +159,8 @@ __host__ __device__ inline void region_sum(RegionSums& s, const int held, const 
 // the field fits `capacity` framed cells, else on the labels as they are stored.
 inline void region_serial_field(const NavArgs& a, const NavRegionArgs& r, const long long field, const int capacity) {
     const int e = (int)(field / r.n_fields), gi = (int)(field - (long long)e*r.n_fields);
-    const int nx = a.geom[4*e + 2], ny = a.geom[4*e + 3];
+    const NavCells g = nav_cells(a, e);
+    const int nx = g.nx, ny = g.ny;
     const long long cells = nx > 0 && ny > 0 ? (long long)nx*ny : 0;
     RegionSums s{0, 0, 0ull};
     int passes = 0;
@@ -254,52 +233,6 @@ inline void region_serial(const NavArgs& a, const NavRegionArgs& r, const int ca
         if (!r.mask || r.mask[field]) region_serial_field(a, r, field, capacity);
 }
 
-// The passes on the framed labels in LDS: until a pass lowers nothing; returns the passes taken.  s_flag[0..2] start zeroed,
-// behind a barrier.
-template <int THREADS>
-__device__ inline int region_passes_framed(int* L, int* s_flag, const int n, const int P) {
-    const int tid = threadIdx.x;
-    int passes = 0;
-    for (;;) {
-        if (tid == 0) s_flag[(passes + 1) % 3] = 0;                     // (last read two barriers ago)
-        bool changed = false;
-        for (int k = tid; k < n; k += THREADS) {
-            const int own = region_load(L + k);
-            if (own != INT_MAX) {
-                const int v = region_lowered_framed(L, k, P, own);
-                if (v < own) { region_lower(L, k, own, v); changed = true; }
-            }
-        }
-        if (changed) s_flag[passes % 3] = 1;
-        __syncthreads();
-        const int again = s_flag[passes % 3];
-        passes++;
-        if (!again) return passes;                                      // (uniform)
-    }
-}
-
-template <int THREADS>
-__device__ inline int region_passes_stored(int* L, int* s_flag, const long long cells, const int nx, const int ny) {
-    const int tid = threadIdx.x;
-    int passes = 0;
-    for (;;) {
-        if (tid == 0) s_flag[(passes + 1) % 3] = 0;
-        bool changed = false;
-        for (long long k = tid; k < cells; k += THREADS) {
-            const int own = region_load(L + k);
-            if (own != INT_MAX) {
-                const int v = region_lowered_stored(L, nx, ny, k, own);
-                if (v < own) { region_lower(L, k, own, v); changed = true; }
-            }
-        }
-        if (changed) s_flag[passes % 3] = 1;
-        __syncthreads();                                                // (the workgroup's stores are visible to its loads from here on)
-        const int again = s_flag[passes % 3];
-        passes++;
-        if (!again) return passes;
-    }
-}
-
 // One cell's share of the count: a cell that is no root takes one off its root's slot - one atomic for the wave where all of
 // the wave's cells in this round share a root (a room), one a lane otherwise.
 __device__ inline void region_count(int* L, const int held) {
@@ -370,7 +303,13 @@ __global__ __launch_bounds__(THREADS) void nav_region_kernel(const NavArgs a, co
             L[k] = region_fill(cell >= 0 && region_open(fr, among, marks, cell, r.where), k);
         }
         __syncthreads();
-        passes = region_passes_framed<THREADS>(L, s_flag, n, P);
+        passes = nav_settle<THREADS>(s_flag, n, [=](const int k) {
+            const int own = nav_load(L + k);
+            if (own == INT_MAX) return false;
+            const int v = region_lowered_framed(L, k, P, own);
+            if (v < own) region_lower(L, k, own, v);
+            return v < own;
+        });
         // the count, in place: roots to -1, the others take one off their root's, behind a barrier each
         for (int k = tid; k < n; k += THREADS)
             if (region_is_root(L[k], k)) L[k] = -1;
@@ -390,15 +329,21 @@ __global__ __launch_bounds__(THREADS) void nav_region_kernel(const NavArgs a, co
         // the same propagation and count on the labels where they are stored
         for (long long k = tid; k < cells; k += THREADS) out[k] = region_fill(region_open(fr, among, marks, k, r.where), (int)k);
         __syncthreads();
-        passes = region_passes_stored<THREADS>(out, s_flag, cells, nx, ny);
+        passes = nav_settle<THREADS>(s_flag, cells, [=](const long long k) {
+            const int own = nav_load(out + k);
+            if (own == INT_MAX) return false;
+            const int v = region_lowered_stored(out, nx, ny, k, own);
+            if (v < own) region_lower(out, k, own, v);
+            return v < own;
+        });
         for (long long k = tid; k < cells; k += THREADS)
             if (region_is_root(out[k], (int)k)) out[k] = -1;
         __syncthreads();
-        for (long long k = tid; k < cells; k += THREADS) region_count(out, region_load(out + k));
+        for (long long k = tid; k < cells; k += THREADS) region_count(out, nav_load(out + k));
         __syncthreads();
         for (long long k = tid; k < cells; k += THREADS) {
-            const int held = region_load(out + k);
-            const int label = region_label(held, (int)k), n_cells = region_cells(held, ((held >= 0) & (held != INT_MAX)) ? region_load(out + held) : 0);
+            const int held = nav_load(out + k);
+            const int label = region_label(held, (int)k), n_cells = region_cells(held, ((held >= 0) & (held != INT_MAX)) ? nav_load(out + held) : 0);
             areas[k] = region_area(n_cells, a.cell);
             region_sum(s, held, n_cells, label);
         }
@@ -428,18 +373,19 @@ struct NavRegionQueryArgs {                          // MsNavRegionQuery, checke
 
 // Point `at` = (e, k) of a query: the store it asks (NULL: none) and its env's grid.
 __host__ __device__ inline const int* region_asked(const NavArgs& a, const int* labels, const int* field, const int n_fields, const long long at,
-                                                   const int e, const int k, int& jx0, int& iy0, int& nx, int& ny) {
-    jx0 = a.geom[4*e]; iy0 = a.geom[4*e + 1]; nx = a.geom[4*e + 2]; ny = a.geom[4*e + 3];
-    const long long cells = nx > 0 && ny > 0 ? (long long)nx*ny : 0;
-    const int f = region_field(field, n_fields, at, k);
+                                                   const int e, const int k, NavCells& g) {
+    g = nav_cells(a, e);
+    const long long cells = g.nx > 0 && g.ny > 0 ? (long long)g.nx*g.ny : 0;
+    const int f = nav_layer_store(field, n_fields, at, k);
     return ((f >= 0) & (cells > 0)) ? labels + ((long long)n_fields*a.starts[e] + (long long)f*cells) : nullptr;
 }
 
 __host__ __device__ inline void region_query_one(const NavArgs& a, const NavRegionQueryArgs& q, const long long at) {
     const int e = (int)(at / q.n_points), k = (int)(at - (long long)e*q.n_points);
-    int jx0, iy0, nx, ny, w[4];
-    const int* const labels = region_asked(a, q.labels, q.field, q.n_fields, at, e, k, jx0, iy0, nx, ny);
-    region_anchor_labels(labels, jx0, iy0, nx, ny, a.cell, q.points[2*at], q.points[2*at + 1], w);
+    NavCells g;
+    int w[4];
+    const int* const labels = region_asked(a, q.labels, q.field, q.n_fields, at, e, k, g);
+    region_anchor_labels(labels, g, q.points[2*at], q.points[2*at + 1], w);
     for (int t = 0; t < 4; t++) q.out[4*at + t] = w[t];
 }
 
@@ -461,11 +407,11 @@ struct NavRegionMaskArgs {                           // MsNavRegionMasks, checke
 __host__ __device__ inline const int* region_request(const NavArgs& a, const NavRegionMaskArgs& q, const long long at, int w[4], long long& cells,
                                                      unsigned char*& out) {
     const int e = (int)(at / q.n_requests), p = (int)(at - (long long)e*q.n_requests);
-    int jx0, iy0, nx, ny;
-    const int* const labels = region_asked(a, q.labels, q.field, q.n_fields, at, e, p, jx0, iy0, nx, ny);
-    cells = nx > 0 && ny > 0 ? (long long)nx*ny : 0;
+    NavCells g;
+    const int* const labels = region_asked(a, q.labels, q.field, q.n_fields, at, e, p, g);
+    cells = g.nx > 0 && g.ny > 0 ? (long long)g.nx*g.ny : 0;
     out = q.out + ((long long)q.n_requests*a.starts[e] + (long long)p*cells);
-    if (q.points) region_anchor_labels(labels, jx0, iy0, nx, ny, a.cell, q.points[2*at], q.points[2*at + 1], w);
+    if (q.points) region_anchor_labels(labels, g, q.points[2*at], q.points[2*at + 1], w);
     else { w[0] = q.wanted[at]; w[1] = w[2] = w[3] = -1; }
     return labels;
 }

@@ -22,17 +22,14 @@
 //                     countable byte counted.  The count is reduced by shuffles within the wave, through LDS across the
 //                     waves; one lane stores gained and total.  A reset map is zeroed in global memory by the workgroup
 //                     before the barrier (a workgroup's stores are visible to its loads behind one).
-struct SeenGrid { int jx0, iy0, nx, ny; float c; };
 struct SeenRay { float ox, oy, ex, ey; int K; };     // the ray cut at its reach: samples o + e*(s/K), s = 0 .. K
-
-__host__ __device__ inline bool seen_finite(const float v) { return fabsf(v) < INFINITY; }
 
 // The ray as the samples read it; false: skipped.
 __host__ __device__ inline bool seen_ray(const float c, const float ox, const float oy, const float dx, const float dy, const float dist,
                                          const float max_range, SeenRay& r) {
-    if (!(seen_finite(ox) && seen_finite(oy) && seen_finite(dx) && seen_finite(dy))) return false;
+    if (!(nav_finite(ox) && nav_finite(oy) && nav_finite(dx) && nav_finite(dy))) return false;
     const float rlen = sqrtf(dx*dx + dy*dy);
-    if (!seen_finite(rlen) || !(rlen > 0.f) || !(dist > 0.f)) return false;      // (a NaN distance is not > 0)
+    if (!nav_finite(rlen) || !(rlen > 0.f) || !(dist > 0.f)) return false;      // (a NaN distance is not > 0)
     const float reach = dist < max_range ? dist : max_range;
     const float ux = dx/rlen, uy = dy/rlen;
     r.ox = ox; r.oy = oy;
@@ -44,7 +41,7 @@ __host__ __device__ inline bool seen_ray(const float c, const float ox, const fl
 }
 
 // The cell under sample s of the ray, row-major in its env's grid; -1: none (outside the grid, or further than any).
-__host__ __device__ inline long long seen_sample(const SeenGrid& g, const SeenRay& r, const int s) {
+__host__ __device__ inline long long seen_sample(const NavCells& g, const SeenRay& r, const int s) {
     const float t = (float)s/(float)r.K;
     const float x = r.ox + r.ex*t, y = r.oy + r.ey*t;
     const float fx = floorf(x/g.c), fy = floorf(y/g.c);
@@ -55,7 +52,7 @@ __host__ __device__ inline long long seen_sample(const SeenGrid& g, const SeenRa
 }
 
 // One call for one env, serially (host instantiation only): a cell is gained when its byte goes from 0 to 1 and it counts.
-inline void seen_serial(const SeenGrid& g, const unsigned char* countable, const int S, const int P, const int R, const float* origins,
+inline void seen_serial(const NavCells& g, const unsigned char* countable, const int S, const int P, const int R, const float* origins,
                         const float* dirs, const float* distances, const int* slot, const float max_range, const unsigned char* reset,
                         unsigned char* maps, int* gained, int* total) {
     const long long cells = g.nx > 0 && g.ny > 0 ? (long long)g.nx*g.ny : 0;
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(WG) void nav_seen_kernel(const NavArgs a, const Nav
         }
         return;
     }
-    const SeenGrid g{geom.x, geom.y, geom.z, geom.w, a.cell};
+    const NavCells g{geom.x, geom.y, geom.z, geom.w, a.cell};
     const int words = (int)((cells + 31) >> 5);
     unsigned char* const m = q.maps + (long long)q.n_maps*a.starts[e] + (long long)s*cells;
     const unsigned char* const counts = q.countable + a.starts[e];

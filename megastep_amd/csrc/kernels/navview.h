@@ -32,16 +32,14 @@ struct ViewPoint { float px, py, hx, hy, hlen; bool cone; };
 struct ViewWindow { int i0, i1, j0, j1; };           // rows i0 .. i1 - 1, columns j0 .. j1 - 1
 struct ViewBox { float x0, y0, x1, y1; };            // p -+ R1: holds every in-range centre
 
-__host__ __device__ inline bool view_finite(const float v) { return fabsf(v) < INFINITY; }
-
 // The viewpoint as the cells read it; false: it sees nothing (a NaN or infinite point; with a cone, a heading without a length).
 __host__ __device__ inline bool view_point(const float px, const float py, const bool cone, const float hx, const float hy, ViewPoint& v) {
     v.px = px; v.py = py; v.hx = 0.f; v.hy = 0.f; v.hlen = 0.f; v.cone = cone;
-    if (!(view_finite(px) && view_finite(py))) return false;
+    if (!(nav_finite(px) && nav_finite(py))) return false;
     if (!cone) return true;
     v.hx = hx; v.hy = hy;
     v.hlen = sqrtf(v.hx*v.hx + v.hy*v.hy);
-    return view_finite(v.hlen) && v.hlen > 0.f;
+    return nav_finite(v.hlen) && v.hlen > 0.f;
 }
 
 __host__ __device__ inline bool view_in_range(const float rr, const float R2) { return rr <= R2; }
@@ -123,8 +121,7 @@ struct NavViewArgs {                                 // MsNavViews, checked
 // The map viewpoint (n, p) reads its gains against: -1 none (no maps asked for, or a slot outside 0 .. S - 1).
 __host__ __device__ inline int view_slot(const NavViewArgs& q, const long long vp, const int p) {
     if (!q.unseen || !q.gains) return -1;
-    const int s = q.slot ? q.slot[vp] : (q.n_maps == 1 ? 0 : p);
-    return s >= 0 && s < q.n_maps ? s : -1;
+    return nav_layer_store(q.slot, q.n_maps, vp, p);
 }
 
 // One cell of the window against the walls given: is it in sight?  (host: the serial sweep's inner loop)
@@ -141,7 +138,8 @@ inline void view_serial(const NavArgs& a, const NavViewArgs& q, const float4* wa
         for (int p = 0; p < q.n_points; p++) {
             const long long vp = (long long)e*q.n_points + p;
             if (q.mask && !q.mask[vp]) continue;
-            const int jx0 = a.geom[4*e], iy0 = a.geom[4*e + 1], nx = a.geom[4*e + 2], ny = a.geom[4*e + 3];
+            const NavCells g = nav_cells(a, e);
+            const int jx0 = g.jx0, iy0 = g.iy0, nx = g.nx, ny = g.ny;
             const long long cells = nx > 0 && ny > 0 ? (long long)nx*ny : 0;
             if (cells <= 0) {
                 if (q.counts) q.counts[vp] = 0;

@@ -1,6 +1,6 @@
 // kernels/navwindow.h -- nav_window_kernel.
-// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after navseen.h, whose
-// SeenGrid names an env's grid); not a header to compile on its own.
+// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after navseen.h; an
+// env's grid is navfield.h's NavCells, the store a view reads its nav_layer_store); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // map windows: per-cell stores cropped and turned into images round each agent      no counterpart in the reference
 // ------------------------------------------------------------------------------------------------
@@ -10,7 +10,7 @@
 // element has one writer and a fixed serial sum, so nothing depends on the order of execution.
 // tests/test_navwindow_host.py restates all of it in numpy (window_rule).
 //
-// The rule's pieces - win_point, win_cell, win_store, win_byte, win_float, win_pixel - are __host__ __device__ functions over
+// The rule's pieces - win_point, win_cell, win_byte, win_float, win_pixel - are __host__ __device__ functions over
 // plain numbers: ms_host_nav_windows runs them on host arrays, so the CPU suite holds this very text to window_rule, bit for bit.
 //
 //   nav_window_kernel<K>   one launch for every image and every channel; K = samples, so that the K*K cells of a pixel are
@@ -52,18 +52,12 @@ __host__ __device__ inline void win_point(const WinView& g, const int i, const i
 }
 
 // The cell under (x, y), row-major in its env's grid; -1: none (seen_sample's statements).
-__host__ __device__ inline long long win_cell(const SeenGrid& g, const float x, const float y) {
+__host__ __device__ inline long long win_cell(const NavCells& g, const float x, const float y) {
     const float fx = floorf(x/g.c), fy = floorf(y/g.c);
     if (!(fabsf(fx) < NAV_INDEX_LIMIT) || !(fabsf(fy) < NAV_INDEX_LIMIT)) return -1;
     const long long j = (long long)(int)fx - g.jx0, i = (long long)(int)fy - g.iy0;   // (|fx|, |fy| < 2^30: the int holds them)
     if ((i < 0) | (i >= g.ny) | (j < 0) | (j >= g.nx)) return -1;
     return i*g.nx + j;
-}
-
-// The store view p of image (n, p) reads in a layer of n_fields stores; -1: a bad index.
-__host__ __device__ inline int win_store(const int* field, const int n_fields, const long long image, const int p) {
-    const int f = field ? field[image] : (n_fields == 1 ? 0 : p);
-    return ((f >= 0) & (f < n_fields)) ? f : -1;
 }
 
 __host__ __device__ inline float win_byte(const unsigned char byte, const int where) { return (byte != 0) == (where != 0) ? 1.f : 0.f; }
@@ -93,7 +87,7 @@ __host__ __device__ inline float win_pixel(const WinChannel& ch, const void* sou
 
 // One pixel of every channel: out points at the pixel in the image's first plane, planes hw apart.
 template <int K>
-__host__ __device__ inline void win_pixels(const SeenGrid& g, const long long first, const WinView& view, const NavWindowArgs& q,
+__host__ __device__ inline void win_pixels(const NavCells& g, const long long first, const WinView& view, const NavWindowArgs& q,
                                            const long long image, const int p, const int i, const int j, const long long hw, float* out) {
     const long long cells = g.nx > 0 && g.ny > 0 ? (long long)g.nx*g.ny : 0;
     long long cell[K*K];
@@ -108,8 +102,8 @@ __host__ __device__ inline void win_pixels(const SeenGrid& g, const long long fi
     }
     for (int c = 0; c < q.n_channels; c++) {
         const WinChannel& ch = q.ch[c];
-        const int fs = win_store(ch.source_field, ch.source_fields, image, p);
-        const int fg = ch.gate ? win_store(ch.gate_field, ch.gate_fields, image, p) : 0;
+        const int fs = nav_layer_store(ch.source_field, ch.source_fields, image, p);
+        const int fg = ch.gate ? nav_layer_store(ch.gate_field, ch.gate_fields, image, p) : 0;
         float v;
         if (fs < 0) v = ch.outside;
         else if (fg < 0) v = ch.hidden;
@@ -130,7 +124,7 @@ inline void win_serial(const NavArgs& a, const NavWindowArgs& q) {
     const long long hw = (long long)q.height*q.width;
     for (long long image = 0; image < (long long)a.n_envs*q.n_views; image++) {
         const int e = (int)(image / q.n_views), p = (int)(image - (long long)e*q.n_views);
-        const SeenGrid g{a.geom[4*e], a.geom[4*e + 1], a.geom[4*e + 2], a.geom[4*e + 3], a.cell};
+        const NavCells g = nav_cells(a, e);
         const float* const v = q.views + image*6;
         const WinView view{v[0], v[1], v[2], v[3], v[4], v[5]};
         for (int i = 0; i < q.height; i++)
@@ -147,7 +141,7 @@ __global__ __launch_bounds__(WG) void nav_window_kernel(const NavArgs a, const N
     if (px >= hw) return;
     const int e = (int)(image / (unsigned)q.n_views), p = (int)(image - (unsigned)e*(unsigned)q.n_views);
     const int4 geom = reinterpret_cast<const int4*>(a.geom)[e];
-    const SeenGrid g{geom.x, geom.y, geom.z, geom.w, a.cell};
+    const NavCells g{geom.x, geom.y, geom.z, geom.w, a.cell};
     const float* const v = q.views + (long long)image*6;
     const WinView view{v[0], v[1], v[2], v[3], v[4], v[5]};
     const int i = px / q.width, j = px - i*q.width;

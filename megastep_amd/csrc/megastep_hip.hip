@@ -822,20 +822,29 @@ int ms_nav_free(const MsScenery* sc, const MsNavGrid* grid, void* stream) {
     return launch_status();
 }
 
-// The launch of either relaxation: the least LDS that holds the largest env's framed field - more workgroups a CU (a field
-// that still does not fit - or an env larger than max_framed says - relaxes in global memory).
+// The three LDS tiers of the kernels that keep an env's field in LDS (relaxation, regions, basins) and the threads of each
+// tier's instantiations.  A launch takes the least tier whose capacity - by the kernel's own capacity function - holds the
+// largest env's framed field: more workgroups a CU (an env that still does not fit - or is larger than max_framed says - runs in
+// global memory).
+constexpr int NAV_TIER_LDS[3] = {NAV_LDS_SMALL, NAV_LDS_MEDIUM, NAV_LDS_LARGE}, NAV_TIER_THREADS[3] = {512, 1024, 1024};
+static int nav_tier(const MsNavGrid* grid, int (*capacity)(int)) {
+    return grid->max_framed <= capacity(NAV_TIER_LDS[0]) ? 0 : grid->max_framed <= capacity(NAV_TIER_LDS[1]) ? 1 : 2;
+}
+static int nav_capacity_for(const MsNavGrid* grid, int (*capacity)(int)) { return capacity(NAV_TIER_LDS[nav_tier(grid, capacity)]); }
+static int nav_host_capacities(int* capacities, int (*capacity)(int)) {
+    if (!capacities) return MS_EINVAL;
+    for (int t = 0; t < 3; t++) capacities[t] = capacity(NAV_TIER_LDS[t]);
+    return MS_OK;
+}
+
+// The launch of either relaxation.
 static int nav_relax_launch(const MsNavGrid* grid, const NavFieldArgs& f, long long total, bool seeded, void* stream) {
-    const long long framed = grid->max_framed;
-    void (*kernel)(NavArgs, NavFieldArgs);
-    int threads = 1024;
-    if (framed <= nav_capacity(NAV_LDS_SMALL)) {
-        kernel = seeded ? nav_relax_kernel<NAV_LDS_SMALL, 512, true> : nav_relax_kernel<NAV_LDS_SMALL, 512, false>;
-        threads = 512;
-    } else if (framed <= nav_capacity(NAV_LDS_MEDIUM))
-        kernel = seeded ? nav_relax_kernel<NAV_LDS_MEDIUM, 1024, true> : nav_relax_kernel<NAV_LDS_MEDIUM, 1024, false>;
-    else
-        kernel = seeded ? nav_relax_kernel<NAV_LDS_LARGE, 1024, true> : nav_relax_kernel<NAV_LDS_LARGE, 1024, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(threads), 0, (hipStream_t)stream, nav_args(grid), f);
+    static void (*const kernels[3][2])(NavArgs, NavFieldArgs) = {                   // [tier][seeded, single-goal]
+        {nav_relax_kernel<NAV_LDS_SMALL, 512, true>, nav_relax_kernel<NAV_LDS_SMALL, 512, false>},
+        {nav_relax_kernel<NAV_LDS_MEDIUM, 1024, true>, nav_relax_kernel<NAV_LDS_MEDIUM, 1024, false>},
+        {nav_relax_kernel<NAV_LDS_LARGE, 1024, true>, nav_relax_kernel<NAV_LDS_LARGE, 1024, false>}};
+    const int t = nav_tier(grid, nav_capacity);
+    hipLaunchKernelGGL(kernels[t][seeded ? 0 : 1], dim3((unsigned)total), dim3(NAV_TIER_THREADS[t]), 0, (hipStream_t)stream, nav_args(grid), f);
     return launch_status();
 }
 
@@ -1049,7 +1058,7 @@ int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable
                      const unsigned char* reset, unsigned char* maps, int* gained, int* total) {
     if (!geom || !(cell > 0.f) || !(cell < INFINITY) || n_maps < 1 || n_viewers < 1 || n_rays < 1 || !origins || !dirs || !distances ||
         !maps || !countable || !(slot || n_viewers == n_maps) || !(max_range > 0.f) || !(max_range < INFINITY)) return -1;
-    seen_serial(SeenGrid{geom[0], geom[1], geom[2], geom[3], cell}, countable, n_maps, n_viewers, n_rays, origins, dirs, distances, slot,
+    seen_serial(NavCells{geom[0], geom[1], geom[2], geom[3], cell}, countable, n_maps, n_viewers, n_rays, origins, dirs, distances, slot,
                 max_range, reset, maps, gained, total);
     return 0;
 }
@@ -1147,11 +1156,6 @@ int ms_host_nav_draws(const MsNavGrid* grid, const MsNavDraws* d) {
 }
 
 // Regions (navregion.h): the same discipline; the launch's LDS is chosen as the relaxation's, by the largest framed field.
-static int nav_region_capacity_for(const MsNavGrid* grid) {
-    const long long framed = grid->max_framed;
-    return framed <= region_capacity(NAV_LDS_SMALL) ? region_capacity(NAV_LDS_SMALL)
-         : framed <= region_capacity(NAV_LDS_MEDIUM) ? region_capacity(NAV_LDS_MEDIUM) : region_capacity(NAV_LDS_LARGE);
-}
 static int nav_regions_check(const MsNavGrid* grid, const MsNavRegions* r) {
     if (!nav_grid_ok(grid) || !r || r->n_fields < 1 || (r->marks && r->where != 0 && r->where != 1) || !r->labels || !r->areas || !r->counts ||
         !r->open_cells || !r->largest || !r->largest_cells || ((uintptr_t)r->labels % 4) || ((uintptr_t)r->areas % 4) ||
@@ -1182,14 +1186,11 @@ static int nav_region_masks_check(const MsNavGrid* grid, const MsNavRegionMasks*
 int ms_nav_regions(const MsNavGrid* grid, const MsNavRegions* r, void* stream) {
     const int status = nav_regions_check(grid, r);
     if (status != MS_OK) return status;
-    const int capacity = nav_region_capacity_for(grid);
-    void (*kernel)(NavArgs, NavRegionArgs);
-    int threads = 1024;
-    if (capacity == region_capacity(NAV_LDS_SMALL)) { kernel = nav_region_kernel<NAV_LDS_SMALL, 512>; threads = 512; }
-    else if (capacity == region_capacity(NAV_LDS_MEDIUM)) kernel = nav_region_kernel<NAV_LDS_MEDIUM, 1024>;
-    else kernel = nav_region_kernel<NAV_LDS_LARGE, 1024>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)grid->n_envs*r->n_fields)), dim3(threads), 0, (hipStream_t)stream, nav_args(grid),
-                       nav_region_args(grid, r));
+    static void (*const kernels[3])(NavArgs, NavRegionArgs) = {nav_region_kernel<NAV_LDS_SMALL, 512>, nav_region_kernel<NAV_LDS_MEDIUM, 1024>,
+                                                               nav_region_kernel<NAV_LDS_LARGE, 1024>};
+    const int t = nav_tier(grid, region_capacity);
+    hipLaunchKernelGGL(kernels[t], dim3((unsigned)((long long)grid->n_envs*r->n_fields)), dim3(NAV_TIER_THREADS[t]), 0, (hipStream_t)stream,
+                       nav_args(grid), nav_region_args(grid, r));
     return launch_status();
 }
 
@@ -1216,7 +1217,7 @@ int ms_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* m, void* 
 int ms_host_nav_regions(const MsNavGrid* grid, const MsNavRegions* r) {
     const int status = nav_regions_check(grid, r);
     if (status != MS_OK) return status;
-    region_serial(nav_args(grid), nav_region_args(grid, r), nav_region_capacity_for(grid));
+    region_serial(nav_args(grid), nav_region_args(grid, r), nav_capacity_for(grid, region_capacity));
     return MS_OK;
 }
 
@@ -1236,18 +1237,9 @@ int ms_host_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* m) {
     return MS_OK;
 }
 
-int ms_host_nav_region_capacity(int* capacities) {
-    if (!capacities) return MS_EINVAL;
-    capacities[0] = region_capacity(NAV_LDS_SMALL); capacities[1] = region_capacity(NAV_LDS_MEDIUM); capacities[2] = region_capacity(NAV_LDS_LARGE);
-    return MS_OK;
-}
+int ms_host_nav_region_capacity(int* capacities) { return nav_host_capacities(capacities, region_capacity); }
 
 // Basins (navbasin.h): the same discipline; the launch's LDS is chosen by max_framed, which bounds every env's cells from above.
-static int nav_basin_capacity_for(const MsNavGrid* grid) {
-    const long long framed = grid->max_framed;
-    return framed <= basin_capacity(NAV_LDS_SMALL) ? basin_capacity(NAV_LDS_SMALL)
-         : framed <= basin_capacity(NAV_LDS_MEDIUM) ? basin_capacity(NAV_LDS_MEDIUM) : basin_capacity(NAV_LDS_LARGE);
-}
 static int nav_basins_check(const MsNavGrid* grid, const MsNavBasins* b) {
     if (!nav_grid_ok(grid) || !b || b->n_fields < 1 || !b->fields || !b->labels || !b->reached || b->n_ids < 0 || b->n_ids > BASIN_MAX_IDS ||
         (b->sizes != nullptr) != (b->n_ids > 0) || b->ids == b->labels || ((uintptr_t)b->fields % 4) || ((uintptr_t)b->ids % 4) ||
@@ -1284,14 +1276,11 @@ static NavPointMarkArgs nav_point_mark_args(const MsNavGrid* grid, const MsNavPo
 int ms_nav_basins(const MsNavGrid* grid, const MsNavBasins* b, void* stream) {
     const int status = nav_basins_check(grid, b);
     if (status != MS_OK) return status;
-    const int capacity = nav_basin_capacity_for(grid);
-    void (*kernel)(NavArgs, NavBasinArgs);
-    int threads = 1024;
-    if (capacity == basin_capacity(NAV_LDS_SMALL)) { kernel = nav_basin_kernel<NAV_LDS_SMALL, 512>; threads = 512; }
-    else if (capacity == basin_capacity(NAV_LDS_MEDIUM)) kernel = nav_basin_kernel<NAV_LDS_MEDIUM, 1024>;
-    else kernel = nav_basin_kernel<NAV_LDS_LARGE, 1024>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)grid->n_envs*b->n_fields)), dim3(threads), 0, (hipStream_t)stream, nav_args(grid),
-                       nav_basin_args(grid, b));
+    static void (*const kernels[3])(NavArgs, NavBasinArgs) = {nav_basin_kernel<NAV_LDS_SMALL, 512>, nav_basin_kernel<NAV_LDS_MEDIUM, 1024>,
+                                                              nav_basin_kernel<NAV_LDS_LARGE, 1024>};
+    const int t = nav_tier(grid, basin_capacity);
+    hipLaunchKernelGGL(kernels[t], dim3((unsigned)((long long)grid->n_envs*b->n_fields)), dim3(NAV_TIER_THREADS[t]), 0, (hipStream_t)stream,
+                       nav_args(grid), nav_basin_args(grid, b));
     return launch_status();
 }
 
@@ -1314,7 +1303,7 @@ int ms_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* m, void* st
 int ms_host_nav_basins(const MsNavGrid* grid, const MsNavBasins* b) {
     const int status = nav_basins_check(grid, b);
     if (status != MS_OK) return status;
-    basin_serial(nav_args(grid), nav_basin_args(grid, b), nav_basin_capacity_for(grid));
+    basin_serial(nav_args(grid), nav_basin_args(grid, b), nav_capacity_for(grid, basin_capacity));
     return MS_OK;
 }
 
@@ -1334,11 +1323,7 @@ int ms_host_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* m) {
     return MS_OK;
 }
 
-int ms_host_nav_basin_capacity(int* capacities) {
-    if (!capacities) return MS_EINVAL;
-    capacities[0] = basin_capacity(NAV_LDS_SMALL); capacities[1] = basin_capacity(NAV_LDS_MEDIUM); capacities[2] = basin_capacity(NAV_LDS_LARGE);
-    return MS_OK;
-}
+int ms_host_nav_basin_capacity(int* capacities) { return nav_host_capacities(capacities, basin_capacity); }
 
 // View fields (navview.h): the same discipline.  An env of more than 2^30 cells cannot be (MsNavGrid's geom is 32768 a side at most
 // in cuda.nav_grid; here it is max_framed, an int, that bounds it).

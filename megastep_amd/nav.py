@@ -2,14 +2,95 @@
 floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
 they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``,
 ``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), the cells in sight of a
-point (``csrc/kernels/navview.h``), and the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``). No counterpart in
-the reference;
+point (``csrc/kernels/navview.h``), and the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``).
+No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
 from . import _lib
 from ._lib import _on, _stream
 from ._call import _cfg, _check, _hw, _require_gpu
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the argument rules and the launch the calls below share, each stated once
+# ---------------------------------------------------------------------------------------------------------------------
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _some(*tensors):
+    """Those of ``tensors`` that were given."""
+    return [t for t in tensors if t is not None]
+
+
+def _new(dev):
+    return lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)
+
+
+def _same(a, b):
+    """Are ``a`` and ``b`` the same memory, or both None: what an ``out`` was made with against what this call was given."""
+    return (a is None) == (b is None) and (a is None or a.data_ptr() == b.data_ptr())
+
+
+def _fits(out, shape, dtype):
+    return isinstance(out, torch.Tensor) and out.shape == shape and out.dtype == dtype and out.is_contiguous()
+
+
+def _mask(mask, n, g, letters, name='mask'):
+    """``mask`` as the kernels read it: an (N, G) bool tensor, made contiguous; None stays None."""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (n, g):
+        raise RuntimeError(f'{name} must be an (N, {letters}) = ({n}, {g}) bool tensor')
+    return mask.contiguous()
+
+
+def _index(t, name, n=None, p=None):
+    """``t`` as the (N, P) int32 tensor a kernel reads an index per item from - a store, a map, a label, an id: any integer dtype,
+    but not bool (that is a mask mistaken for an index), converted only when it is not int32 or not contiguous, so that a tensor
+    a result keeps by reference stays the caller's own. ``n``, ``p``: what N and P must be, where the call knows them."""
+    if not isinstance(t, torch.Tensor) or t.dtype.is_floating_point or t.dtype == torch.bool or t.ndim != 2 or \
+            (n is not None and (t.shape[0] != n or t.shape[1] < 1)) or (p is not None and t.shape[1] != p):
+        raise RuntimeError(f'{name} must be an (N, P){"" if p is None else f" = ({n}, {p})"} integer tensor'
+                           f'{"" if n is None or p is not None else f" with N = {n}"}')
+    return t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous()
+
+
+def _points(grid, points, name='points'):
+    """The rule of the points a call asks at: (N, P, 2) float32 with N the grid's envs and P >= 1; returns (N, P)."""
+    _check(points, name, torch.float32, 3)
+    n, p = points.shape[:2]
+    if n != grid.n_envs or points.shape[2] != 2 or p < 1:
+        raise RuntimeError(f'{name} must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
+    return n, p
+
+
+def _default_store(count, p, message):
+    """Without an index item k of ``p`` reads the one store its env has, or store k: ``count`` stores must be 1 or ``p``."""
+    if count not in (1, p):
+        raise RuntimeError(message)
+
+
+def _field_rule(field, n, p, g, what):
+    """The argument rule of a per-point ``field``: int32 (N, P) or None - then one store an env, or one per point."""
+    if field is None:
+        return _default_store(g, p, f'without {what}, there must be one field per env or one per point ({p}); there are {g}')
+    return _index(field, what, n, p)
+
+
+def _store_view(grid, store, n_stores, e, k):
+    """(ny, nx) view of store ``k`` of env ``e`` in a flat ``store`` of ``n_stores`` an env, row 0 at the lowest y."""
+    s, ny, nx = grid.cells(e)
+    at = n_stores*s + k*ny*nx
+    return store[at:at + ny*nx].reshape(ny, nx)
+
+
+def _launch(dev, entry, grid, spec, *before):
+    """The tail of every call: ``ms_nav_<entry>(*before, grid, spec, stream)`` on ``dev``, its status checked."""
+    args = [*before, grid._struct] + ([] if spec is None else [spec])
+    with _on(dev):
+        _lib.check(getattr(_lib.lib(), 'ms_nav_' + entry)(*(C.byref(a) for a in args), _stream(dev)))
 
 
 def _static_boxes(scenery):
@@ -58,6 +139,7 @@ class NavGrid:
         framed = (host_geom[:, 2].astype('int64') + 2)*(host_geom[:, 3].astype('int64') + 2)
         framed = framed[(host_geom[:, 2] > 0) & (host_geom[:, 3] > 0)]
         self._max_framed = int(framed.max()) if len(framed) else 0
+        self._max_cells = int(host_geom[:, 2:].astype('int64').prod(1).max(initial=0))        # the largest env's
         self._struct = _lib.MsNavGrid(len(host_geom), self.cell, self.clearance, geom.data_ptr(), starts.data_ptr(), self._max_framed,
                                       free.data_ptr())
 
@@ -107,21 +189,18 @@ def nav_grid(scenery, cell=.125, clearance=None, config=None):
     starts = torch.as_tensor(host_starts, device=dev).contiguous()
     free = torch.zeros(max(int(host_starts[-1]), 1), dtype=torch.uint8, device=dev)
     grid = NavGrid(geom, starts, free, cell, clearance, host_geom, host_starts)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_nav_free(C.byref(scenery._as_struct()), C.byref(grid._struct), _stream(dev)))
+    _launch(dev, 'free', grid, None, scenery._as_struct())
     return grid
 
 
 class _Fields:
     """What :class:`DistanceFields` and :class:`SeededFields` share: the flat store of ``n_goals`` fields per env, its views, the
     query and the argument rules of the calls that follow the fields. A subclass names its own tensors (``_own``) and makes the
-    two launches that differ (``_waypoints_call``, ``_paths_call``)."""
+    two launches that differ (``_waypoints_call``, ``_paths_call``: the entry's name, the grid and the filled-in spec)."""
 
     def image(self, e, g=0):
         """(ny, nx) float32 view of field ``g`` of env ``e``, row 0 at the lowest y."""
-        s, ny, nx = self.grid.cells(e)
-        at = self.n_goals*s + g*ny*nx
-        return self.values[at:at + ny*nx].reshape(ny, nx)
+        return _store_view(self.grid, self.values, self.n_goals, e, g)
 
     def at(self, points, goal=None, out=None):
         """(N, P) float32: the distance from each of ``points`` (N, P, 2) to a goal of its env - ``goal`` (N, P) integers name
@@ -132,28 +211,17 @@ class _Fields:
         may cross a wall. One launch, no host synchronisation."""
         n, p, goal, dev = self._queries(points, goal)
         out = _answer(out, (n, p), dev)
-        spec = _lib.MsNavQuery(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.values.data_ptr(),
-                               self.n_goals, out.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_query(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        _launch(dev, 'query', self.grid, _lib.MsNavQuery(p, points.data_ptr(), _ptr(goal), self.values.data_ptr(), self.n_goals, out.data_ptr()))
         return out
 
     def _queries(self, points, goal):
         """The argument rules of :meth:`at` and of the calls that follow the fields: (n, p, goal as int32 or None, device)."""
-        grid = self.grid
-        _check(points, 'points', torch.float32, 3)
-        n, p = points.shape[:2]
-        if n != grid.n_envs or points.shape[2] != 2 or p < 1:
-            raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
-        if goal is None:
-            if p != self.n_goals:
-                raise RuntimeError(f'without goal, points must be one per field ({self.n_goals}); got {p}')
-        else:
-            if not isinstance(goal, torch.Tensor) or goal.dtype.is_floating_point or goal.shape != (n, p):
-                raise RuntimeError(f'goal must be an (N, P) = ({n}, {p}) integer tensor')
-            goal = goal.to(torch.int32).contiguous()
-        dev = _require_gpu(points, self.values, *self._own(), grid.free, *([goal] if goal is not None else []))
-        return n, p, goal, dev
+        n, p = _points(self.grid, points)
+        if goal is not None:
+            goal = _index(goal, 'goal', n, p)
+        elif p != self.n_goals:
+            raise RuntimeError(f'without goal, points must be one per field ({self.n_goals}); got {p}')
+        return n, p, goal, _require_gpu(points, self.values, *self._own(), self.grid.free, *_some(goal))
 
     def waypoints(self, points, goal=None, lookahead=16, hops=False, out=None):
         """(N, P, 2) float32: where to head for from each of ``points`` (N, P, 2) to walk to its goal (``goal``: as :meth:`at`) -
@@ -168,9 +236,7 @@ class _Fields:
         n, p, goal, dev = self._queries(points, goal)
         out = _answer(out, (n, p, 2), dev)
         chosen = torch.empty((n, p), dtype=torch.int32, device=dev) if hops else None
-        with _on(dev):
-            _lib.check(self._waypoints_call(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, lookahead, out.data_ptr(),
-                                            chosen.data_ptr() if hops else None, _stream(dev)))
+        _launch(dev, *self._waypoints_call(p, points.data_ptr(), _ptr(goal), lookahead, out.data_ptr(), _ptr(chosen)))
         return (out, chosen) if hops else out
 
     def paths(self, points, goal=None, max_points=256):
@@ -182,9 +248,7 @@ class _Fields:
         n, p, goal, dev = self._queries(points, goal)
         pts = torch.empty((n, p, max_points, 2), dtype=torch.float32, device=dev)
         counts = torch.empty((n, p), dtype=torch.int32, device=dev)
-        with _on(dev):
-            _lib.check(self._paths_call(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, max_points, pts.data_ptr(),
-                                        counts.data_ptr(), _stream(dev)))
+        _launch(dev, *self._paths_call(p, points.data_ptr(), _ptr(goal), max_points, pts.data_ptr(), counts.data_ptr()))
         return Paths(pts, counts)
 
 
@@ -201,13 +265,11 @@ class DistanceFields(_Fields):
     def _own(self):
         return (self.goals,)
 
-    def _waypoints_call(self, p, points, goal, lookahead, out, hops, stream):
-        spec = _lib.MsNavWaypoints(p, points, goal, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, lookahead, out, hops)
-        return _lib.lib().ms_nav_waypoints(C.byref(self.grid._struct), C.byref(spec), stream)
+    def _waypoints_call(self, p, points, goal, lookahead, out, hops):
+        return 'waypoints', self.grid, _lib.MsNavWaypoints(p, points, goal, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, lookahead, out, hops)
 
-    def _paths_call(self, p, points, goal, max_points, out, counts, stream):
-        spec = _lib.MsNavPaths(p, points, goal, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, max_points, out, counts)
-        return _lib.lib().ms_nav_paths(C.byref(self.grid._struct), C.byref(spec), stream)
+    def _paths_call(self, p, points, goal, max_points, out, counts):
+        return 'paths', self.grid, _lib.MsNavPaths(p, points, goal, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, max_points, out, counts)
 
     def update(self, goals=None, mask=None):
         """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place - for ``goals`` (N, G, 2), which are
@@ -229,7 +291,7 @@ def _answer(out, shape, dev):
     """The tensor a query writes its (N, P[, 2]) answer to: ``out`` if it fits, a fresh one without."""
     if out is None:
         return torch.empty(shape, dtype=torch.float32, device=dev)
-    if not isinstance(out, torch.Tensor) or out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+    if not _fits(out, shape, torch.float32) or out.device != dev:
         raise RuntimeError(f"`out` must be a contiguous (N, P{', 2'*(len(shape) - 2)}) float32 tensor on the fields' device")
     return out
 
@@ -252,15 +314,9 @@ class Paths:
 def _nav_fields_call(fields, mask):
     grid = fields.grid
     n, g = fields.goals.shape[:2]
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (n, g):
-            raise RuntimeError(f'mask must be an (N, G) = ({n}, {g}) bool tensor')
-        mask = mask.contiguous()
-    dev = _require_gpu(fields.goals, fields.values, grid.free, *([mask] if mask is not None else []))
-    spec = _lib.MsNavFields(g, fields.goals.data_ptr(), mask.data_ptr() if mask is not None else None, fields.values.data_ptr(),
-                            fields.passes.data_ptr() if fields.passes is not None else None)
-    with _on(dev):
-        _lib.check(_lib.lib().ms_nav_fields(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+    mask = _mask(mask, n, g, 'G')
+    dev = _require_gpu(fields.goals, fields.values, grid.free, *_some(mask))
+    _launch(dev, 'fields', grid, _lib.MsNavFields(g, fields.goals.data_ptr(), _ptr(mask), fields.values.data_ptr(), _ptr(fields.passes)))
 
 
 def distance_fields(grid, goals, mask=None, out=None, passes=False):
@@ -320,13 +376,11 @@ class SeededFields(_Fields):
     def _own(self):
         return ()
 
-    def _waypoints_call(self, p, points, goal, lookahead, out, hops, stream):
-        spec = _lib.MsNavSeedWaypoints(p, points, goal, self.values.data_ptr(), self.n_goals, lookahead, out, hops)
-        return _lib.lib().ms_nav_seed_waypoints(C.byref(self.grid._struct), C.byref(spec), stream)
+    def _waypoints_call(self, p, points, goal, lookahead, out, hops):
+        return 'seed_waypoints', self.grid, _lib.MsNavSeedWaypoints(p, points, goal, self.values.data_ptr(), self.n_goals, lookahead, out, hops)
 
-    def _paths_call(self, p, points, goal, max_points, out, counts, stream):
-        spec = _lib.MsNavSeedPaths(p, points, goal, self.values.data_ptr(), self.n_goals, max_points, out, counts)
-        return _lib.lib().ms_nav_seed_paths(C.byref(self.grid._struct), C.byref(spec), stream)
+    def _paths_call(self, p, points, goal, max_points, out, counts):
+        return 'seed_paths', self.grid, _lib.MsNavSeedPaths(p, points, goal, self.values.data_ptr(), self.n_goals, max_points, out, counts)
 
     def basins(self, ids=None, n_ids=0, mask=None, out=None, passes=False):
         """:func:`basins` of these fields: which seed each cell leads to."""
@@ -336,16 +390,10 @@ class SeededFields(_Fields):
         """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place, from :attr:`marks` as they stand now.
         One launch, no host synchronisation."""
         grid, g = self.grid, self.n_goals
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, g):
-                raise RuntimeError(f'mask must be an (N, G) = ({grid.n_envs}, {g}) bool tensor')
-            mask = mask.contiguous()
-        dev = _require_gpu(self.marks, self.values, self.n_seeds, grid.free, *(t for t in (self.among, mask, self.passes) if t is not None))
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        spec = _lib.MsNavSeedFields(g, self.marks.data_ptr(), int(self.where), ptr(self.among), ptr(mask), self.values.data_ptr(),
-                                    ptr(self.passes), self.n_seeds.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_seed_fields(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        mask = _mask(mask, grid.n_envs, g, 'G')
+        dev = _require_gpu(self.marks, self.values, self.n_seeds, grid.free, *_some(self.among, mask, self.passes))
+        _launch(dev, 'seed_fields', grid, _lib.MsNavSeedFields(g, self.marks.data_ptr(), int(self.where), _ptr(self.among), _ptr(mask),
+                                                               self.values.data_ptr(), _ptr(self.passes), self.n_seeds.data_ptr()))
         return self
 
 
@@ -384,11 +432,10 @@ def seeded_fields(grid, marks, n_fields, where=True, among=None, mask=None, out=
     where = bool(where)
     if out is not None:
         if not isinstance(out, SeededFields) or out.grid is not grid or out.n_goals != n_fields or out.where != where or \
-                out.marks.data_ptr() != marks.data_ptr() or (out.among is None) != (among is None) or \
-                (among is not None and out.among.data_ptr() != among.data_ptr()):
+                not _same(out.marks, marks) or not _same(out.among, among):
             raise RuntimeError('`out` must come from a seeded_fields call with the same grid, marks, n_fields, where and among')
         return out.update(mask)
-    dev = _require_gpu(marks, grid.free, *(t for t in (among,) if t is not None))
+    dev = _require_gpu(marks, grid.free, *_some(among))
     values = torch.empty(max(n_fields*grid.n_cells, 1), dtype=torch.float32, device=dev)
     if mask is not None:
         values.fill_(float('inf'))                                      # (a field never computed is a field nothing reaches)
@@ -411,15 +458,11 @@ class SeenMaps:
 
     def __init__(self, grid, n_maps, values, countable, totals, n_countable):
         self.grid, self.n_maps, self.values, self.countable, self.totals, self.n_countable = grid, int(n_maps), values, countable, totals, n_countable
-        cells = grid._host_geom[:, 2].astype('int64')*grid._host_geom[:, 3].astype('int64')
-        self._max_cells = int(cells.max()) if len(cells) else 0
 
     def image(self, e, s=0):
         """(ny, nx) bool view of map ``s`` of env ``e``, row 0 at the lowest y - the convention of :meth:`NavGrid.image`, so the
         two can be laid over each other as they are."""
-        first, ny, nx = self.grid.cells(e)
-        at = self.n_maps*first + s*ny*nx
-        return self.values[at:at + ny*nx].view(torch.bool).reshape(ny, nx)
+        return _store_view(self.grid, self.values.view(torch.bool), self.n_maps, e, s)
 
     def fraction(self):
         """(N, S) float32: the share of its env's countable cells each map has seen; 0 where nothing is countable."""
@@ -447,32 +490,23 @@ class SeenMaps:
         if n != grid.n_envs or origins.shape[2] != 2 or p < 1 or r < 1 or dirs.shape != (n, p, r, 2) or distances.shape != (n, p, r):
             raise RuntimeError(f'origins, dirs and distances must be (N, P, 2), (N, P, R, 2) and (N, P, R) with N = {grid.n_envs}; got '
                                f'{tuple(origins.shape)}, {tuple(dirs.shape)} and {tuple(distances.shape)}')
-        if slot is None:
-            if p != S:
-                raise RuntimeError(f'without slot, the viewers must be one per map ({S}); got {p}')
-        else:
-            if not isinstance(slot, torch.Tensor) or slot.dtype.is_floating_point or slot.dtype == torch.bool or slot.shape != (n, p):
-                raise RuntimeError(f'slot must be an (N, P) = ({n}, {p}) integer tensor')
-            slot = slot.to(torch.int32).contiguous()
-        if reset is not None:
-            if not isinstance(reset, torch.Tensor) or reset.dtype != torch.bool or reset.shape != (n, S):
-                raise RuntimeError(f'reset must be an (N, S) = ({n}, {S}) bool tensor')
-            reset = reset.contiguous()
+        if slot is not None:
+            slot = _index(slot, 'slot', n, p)
+        elif p != S:
+            raise RuntimeError(f'without slot, the viewers must be one per map ({S}); got {p}')
+        reset = _mask(reset, n, S, 'S', 'reset')
         if not (0 < max_range < float('inf')):
             raise RuntimeError(f'max_range must be a positive number; got {max_range}')
-        if self._max_cells > SEEN_MAX_CELLS:
-            raise RuntimeError(f'an env of this grid has {self._max_cells} cells; seen maps take at most {SEEN_MAX_CELLS} an env')
-        dev = _require_gpu(origins, dirs, distances, self.values, self.countable, self.totals, grid.free,
-                           *(t for t in (slot, reset) if t is not None))
+        if grid._max_cells > SEEN_MAX_CELLS:
+            raise RuntimeError(f'an env of this grid has {grid._max_cells} cells; seen maps take at most {SEEN_MAX_CELLS} an env')
+        dev = _require_gpu(origins, dirs, distances, self.values, self.countable, self.totals, grid.free, *_some(slot, reset))
         if out is None:
             out = torch.empty((n, S), dtype=torch.int32, device=dev)
-        elif not isinstance(out, torch.Tensor) or out.shape != (n, S) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+        elif not _fits(out, (n, S), torch.int32) or out.device != dev:
             raise RuntimeError("`out` must be a contiguous (N, S) int32 tensor on the maps' device")
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        spec = _lib.MsNavSeen(S, p, r, origins.data_ptr(), dirs.data_ptr(), distances.data_ptr(), ptr(slot), float(max_range), ptr(reset),
-                              self.countable.data_ptr(), self.values.data_ptr(), out.data_ptr(), self.totals.data_ptr(), self._max_cells)
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_seen(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        _launch(dev, 'seen', grid, _lib.MsNavSeen(S, p, r, origins.data_ptr(), dirs.data_ptr(), distances.data_ptr(), _ptr(slot), float(max_range),
+                                                  _ptr(reset), self.countable.data_ptr(), self.values.data_ptr(), out.data_ptr(),
+                                                  self.totals.data_ptr(), grid._max_cells))
         return out
 
     def mark_render(self, agents, frame, slot=None, max_range=10., reset=None, out=None, config=None):
@@ -520,7 +554,7 @@ def seen_maps(grid, n_maps, countable=None):
         if not isinstance(countable, torch.Tensor) or countable.dtype not in (torch.uint8, torch.bool) or countable.shape != grid.free.shape:
             raise RuntimeError(f'countable must be a uint8 or bool tensor of {tuple(grid.free.shape)}, one entry per cell of the grid')
         countable = countable.to(device=dev, dtype=torch.uint8).contiguous()
-    if int(grid._host_geom[:, 2:].astype('int64').prod(1).max(initial=0)) > SEEN_MAX_CELLS:
+    if grid._max_cells > SEEN_MAX_CELLS:
         raise RuntimeError(f'seen maps take at most {SEEN_MAX_CELLS} cells an env')
     n = grid.n_envs
     values = torch.zeros(max(n_maps*grid.n_cells, 1), dtype=torch.uint8, device=dev)
@@ -575,12 +609,7 @@ def cell_layer(values, n_fields=1, field=None):
         raise RuntimeError('a layer must be a contiguous 1-dimensional uint8, bool or float32 tensor')
     if values.dtype == torch.bool:
         values = values.view(torch.uint8)
-    if field is not None:
-        if not isinstance(field, torch.Tensor) or field.dtype.is_floating_point or field.dtype == torch.bool or field.ndim != 2:
-            raise RuntimeError('field must be an (N, P) integer tensor')
-        if field.dtype != torch.int32 or not field.is_contiguous():
-            field = field.to(torch.int32).contiguous()
-    return CellLayer(values, n_fields, field)
+    return CellLayer(values, n_fields, None if field is None else _index(field, 'field'))
 
 
 def _layer(x):
@@ -618,12 +647,11 @@ def _window_layer(layer, name, grid, n, p, spec):
         raise RuntimeError(f"{name} must have at least {want} entries, a value per cell and store (n_fields*n_cells = {layer.n_fields}*{grid.n_cells}); "
                            f'got {layer.values.shape[0]}')
     if layer.field is None:
-        if layer.n_fields not in (1, p):
-            raise RuntimeError(f'without field, {name} must hold one store per env or one per view ({p}); it holds {layer.n_fields}')
+        _default_store(layer.n_fields, p, f'without field, {name} must hold one store per env or one per view ({p}); it holds {layer.n_fields}')
     elif layer.field.shape != (n, p):
         raise RuntimeError(f"{name}'s field must be (N, P) = ({n}, {p}); got {tuple(layer.field.shape)}")
     spec.values, spec.is_float, spec.n_fields = layer.values.data_ptr(), int(layer.is_float), layer.n_fields
-    spec.field = layer.field.data_ptr() if layer.field is not None else None
+    spec.field = _ptr(layer.field)
     return layer._tensors()
 
 
@@ -655,7 +683,7 @@ def local_maps(grid, views, size, channels, samples=1, out=None):
     specs = (_lib.MsNavChannel*c)()
     tensors = [views, grid.free]
     for k, (ch, spec) in enumerate(zip(channels, specs)):
-        if ch.gate is not None and ch.gate.is_float:
+        if ch.gate is not None and ch.gate.is_float:                    # (a MapChannel made by hand has not been through map_channel)
             raise RuntimeError('a gate must be a byte layer (uint8 or bool), not float32')
         if ch.source.is_float and ch.scale is None:
             raise RuntimeError('a float32 source needs a scale')
@@ -665,15 +693,13 @@ def local_maps(grid, views, size, channels, samples=1, out=None):
         spec.where, spec.scale, spec.outside, spec.hidden = int(bool(ch.where)), float(ch.scale or 0.), float(ch.outside), float(ch.hidden)
     shape = (n, p, c, h, w)
     if out is not None:
-        if not isinstance(out, torch.Tensor) or out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        if not _fits(out, shape, torch.float32):
             raise RuntimeError(f'`out` must be a contiguous (N, P, C, H, W) = {shape} float32 tensor')
         tensors.append(out)
     dev = _require_gpu(*tensors)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
-    spec = _lib.MsNavWindows(p, h, w, samples, views.data_ptr(), c, specs, out.data_ptr())
-    with _on(dev):
-        _lib.check(_lib.lib().ms_nav_windows(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+    _launch(dev, 'windows', grid, _lib.MsNavWindows(p, h, w, samples, views.data_ptr(), c, specs, out.data_ptr()))
     return out
 
 
@@ -693,8 +719,6 @@ class CellDraws:
     def __init__(self, grid, n_sets, n_draws, cells, points, uniforms, values, counts, counter):
         self.grid, self.n_sets, self.n_draws = grid, int(n_sets), int(n_draws)
         self.cells, self.points, self.uniforms, self.values, self.counts, self.counter = cells, points, uniforms, values, counts, counter
-        cells_of = grid._host_geom[:, 2].astype('int64')*grid._host_geom[:, 3].astype('int64')
-        self._max_cells = int(cells_of.max()) if len(cells_of) else 0
 
     def _set(self, source, gate, where, lo, hi, seed):
         """Takes the arguments of a call: checks the layers against the grid and the sets and fills in the MsNavDraws."""
@@ -705,7 +729,7 @@ class CellDraws:
         if gate is not None:
             tensors += _window_layer(gate, 'gate', grid, n, p, spec.gate)
         spec.where, spec.lo, spec.hi = int(bool(where)), float(lo or 0.), float(hi or 0.)
-        spec.n_sets, spec.n_draws, spec.seed, spec.max_cells = p, self.n_draws, seed, self._max_cells
+        spec.n_sets, spec.n_draws, spec.seed, spec.max_cells = p, self.n_draws, seed, grid._max_cells
         spec.counter, spec.cells, spec.points = self.counter.data_ptr(), self.cells.data_ptr(), self.points.data_ptr()
         spec.uniforms, spec.counts = self.uniforms.data_ptr(), self.counts.data_ptr()
         if self.values is not None:
@@ -718,15 +742,10 @@ class CellDraws:
         """Draws again in place, from the layers as they stand now; the counter moves on, so the draws are new ones. ``mask``
         (N, P) bool: only the marked sets are drawn - the others keep their draws, their counts and their counter. One launch, no
         host synchronisation, nothing allocated: the call can be captured in a HIP graph, and every replay draws afresh."""
-        grid = self.grid
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, self.n_sets):
-                raise RuntimeError(f'mask must be an (N, P) = ({grid.n_envs}, {self.n_sets}) bool tensor')
-            mask = mask.contiguous()
-        dev = _require_gpu(*self._tensors, *([mask] if mask is not None else []))
-        self._spec.mask = mask.data_ptr() if mask is not None else None
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_draws(C.byref(grid._struct), C.byref(self._spec), _stream(dev)))
+        mask = _mask(mask, self.grid.n_envs, self.n_sets, 'P')
+        dev = _require_gpu(*self._tensors, *_some(mask))
+        self._spec.mask = _ptr(mask)
+        _launch(dev, 'draws', self.grid, self._spec)
         return self
 
 
@@ -768,10 +787,9 @@ def cell_draws(grid, source, n_sets, n_draws, lo=None, hi=None, where=True, gate
             raise RuntimeError(f'`out` must come from a cell_draws call with the same grid, (N, P, K) = {shape} and kind of source')
         draws = out
     else:
-        if int(grid._host_geom[:, 2:].astype('int64').prod(1).max(initial=0)) > SEEN_MAX_CELLS:
+        if grid._max_cells > SEEN_MAX_CELLS:
             raise RuntimeError(f'cell draws take at most {SEEN_MAX_CELLS} cells an env')
-        dev = grid.free.device
-        new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)
+        new = _new(grid.free.device)
         draws = CellDraws(grid, n_sets, n_draws, new(shape, torch.int32, -1), new(shape + (2,), torch.float32, float('nan')),
                           new(shape, torch.float32, 0.), new(shape, torch.float32, float('nan')) if source.is_float else None,
                           new((n, n_sets), torch.int32, 0), new((n, n_sets), torch.int32, 0))
@@ -783,6 +801,25 @@ def cell_draws(grid, source, n_sets, n_draws, lo=None, hi=None, where=True, gate
 #: instantiations (40, 80 and 160 KiB); the launch is the least that holds the grid's largest env, and a larger env is labelled
 #: in global memory, to the same result
 REGION_CAPACITY = (10224, 20464, 40944)
+
+
+def _masks(grid, store, n_fields, points, labels, field, out):
+    """:meth:`Regions.masks` and :meth:`Basins.masks`: the requests' rules and the one launch, on the labels ``store``."""
+    if points is not None:
+        n, p = _points(grid, points)
+    else:
+        labels = _index(labels, 'labels', grid.n_envs)
+        n, p = labels.shape
+    field = _field_rule(field, n, p, n_fields, 'field')
+    dev = _require_gpu(points if points is not None else labels, store, grid.free, *_some(field))
+    size = max(p*grid.n_cells, 1)
+    if out is None:
+        out = CellLayer(torch.zeros(size, dtype=torch.uint8, device=dev), p, None)
+    elif not isinstance(out, CellLayer) or out.is_float or out.n_fields != p or out.values.shape[0] != size or out.values.device != dev:
+        raise RuntimeError(f'`out` must be the layer of a masks call with the same grid and P = {p}')
+    _launch(dev, 'region_masks', grid, _lib.MsNavRegionMasks(p, _ptr(points), _ptr(labels), _ptr(field), store.data_ptr(), n_fields,
+                                                              out.values.data_ptr()))
+    return out
 
 
 class Regions:
@@ -803,55 +840,26 @@ class Regions:
 
     n_fields = property(lambda self: self._n_fields)
 
-    def _view(self, store, e, g):
-        s, ny, nx = self.grid.cells(e)
-        at = self.n_fields*s + g*ny*nx
-        return store[at:at + ny*nx].reshape(ny, nx)
-
     def image(self, e, g=0):
         """(ny, nx) int32 view of the labels of field ``g`` of env ``e``, row 0 at the lowest y."""
-        return self._view(self.labels, e, g)
+        return _store_view(self.grid, self.labels, self.n_fields, e, g)
 
     def area_image(self, e, g=0):
         """(ny, nx) float32 view of the areas of field ``g`` of env ``e``, row 0 at the lowest y."""
-        return self._view(self.areas, e, g)
+        return _store_view(self.grid, self.areas, self.n_fields, e, g)
 
     def update(self, mask=None):
         """Labels the fields marked in the (N, G) bool ``mask`` (default all) again in place, from :attr:`marks` and
         :attr:`among` as they stand now; the others keep labels, areas and summary. One launch, no host synchronisation, nothing
         allocated: the call can be captured in a HIP graph."""
         grid, g = self.grid, self.n_fields
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, g):
-                raise RuntimeError(f'mask must be an (N, G) = ({grid.n_envs}, {g}) bool tensor')
-            mask = mask.contiguous()
+        mask = _mask(mask, grid.n_envs, g, 'G')
         dev = _require_gpu(self.labels, self.areas, self.counts, self.open_cells, self.largest, self.largest_cells, grid.free,
-                           *(t for t in (self.marks, self.among, mask, self.passes) if t is not None))
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        spec = _lib.MsNavRegions(g, ptr(self.marks), int(self.where), ptr(self.among), ptr(mask), self.labels.data_ptr(), self.areas.data_ptr(),
-                                 self.counts.data_ptr(), self.open_cells.data_ptr(), self.largest.data_ptr(), self.largest_cells.data_ptr(),
-                                 ptr(self.passes))
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_regions(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+                           *_some(self.marks, self.among, mask, self.passes))
+        _launch(dev, 'regions', grid, _lib.MsNavRegions(g, _ptr(self.marks), int(self.where), _ptr(self.among), _ptr(mask), self.labels.data_ptr(),
+                                                        self.areas.data_ptr(), self.counts.data_ptr(), self.open_cells.data_ptr(),
+                                                        self.largest.data_ptr(), self.largest_cells.data_ptr(), _ptr(self.passes)))
         return self
-
-    def _requests(self, n, p, field, *tensors):
-        """The argument rules of a query's or a request's ``field``: (field as int32 or None, device)."""
-        if field is None:
-            if self.n_fields not in (1, p):
-                raise RuntimeError(f'without field, there must be one regions field per env or one per point ({p}); there are {self.n_fields}')
-        else:
-            if not isinstance(field, torch.Tensor) or field.dtype.is_floating_point or field.dtype == torch.bool or field.shape != (n, p):
-                raise RuntimeError(f'field must be an (N, P) = ({n}, {p}) integer tensor')
-            field = field.to(torch.int32).contiguous()
-        return field, _require_gpu(*tensors, self.labels, self.grid.free, *([field] if field is not None else []))
-
-    def _points(self, points, name='points'):
-        _check(points, name, torch.float32, 3)
-        n, p = points.shape[:2]
-        if n != self.grid.n_envs or points.shape[2] != 2 or p < 1:
-            raise RuntimeError(f'{name} must be (N, P, 2) with N = {self.grid.n_envs}; got {tuple(points.shape)}')
-        return n, p
 
     def labels_at(self, points, field=None):
         """(N, P, 4) int32: the label under each of the four cells round each of ``points`` (N, P, 2) - the anchors of
@@ -859,13 +867,12 @@ class Regions:
         name the regions field each point asks; default the one field, or point k field k (then P must be G). All -1 for a NaN
         point, a point far from the grid, an env without cells and a field index out of range. One launch, no host
         synchronisation."""
-        n, p = self._points(points)
-        field, dev = self._requests(n, p, field, points)
+        n, p = _points(self.grid, points)
+        field = _field_rule(field, n, p, self.n_fields, 'field')
+        dev = _require_gpu(points, self.labels, self.grid.free, *_some(field))
         out = torch.empty((n, p, 4), dtype=torch.int32, device=dev)
-        spec = _lib.MsNavRegionQuery(p, points.data_ptr(), field.data_ptr() if field is not None else None, self.labels.data_ptr(),
-                                     self.n_fields, out.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_region_query(C.byref(self.grid._struct), C.byref(spec), _stream(dev)))
+        _launch(dev, 'region_query', self.grid, _lib.MsNavRegionQuery(p, points.data_ptr(), _ptr(field), self.labels.data_ptr(), self.n_fields,
+                                                                      out.data_ptr()))
         return out
 
     def at(self, points, field=None):
@@ -894,27 +901,7 @@ class Regions:
         synchronisation."""
         if (points is None) == (labels is None):
             raise RuntimeError('exactly one of points and labels must be given')
-        grid = self.grid
-        if points is not None:
-            n, p = self._points(points)
-            given = points
-        else:
-            if not isinstance(labels, torch.Tensor) or labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.ndim != 2 or \
-                    labels.shape[0] != grid.n_envs or labels.shape[1] < 1:
-                raise RuntimeError(f'labels must be an (N, P) integer tensor with N = {grid.n_envs}')
-            n, p = labels.shape
-            given = labels = labels.to(torch.int32).contiguous()
-        field, dev = self._requests(n, p, field, given)
-        size = max(p*grid.n_cells, 1)
-        if out is None:
-            out = CellLayer(torch.zeros(size, dtype=torch.uint8, device=dev), p, None)
-        elif not isinstance(out, CellLayer) or out.is_float or out.n_fields != p or out.values.shape[0] != size or out.values.device != dev:
-            raise RuntimeError(f'`out` must be the layer of a masks call with the same grid and P = {p}')
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        spec = _lib.MsNavRegionMasks(p, ptr(points), ptr(labels), ptr(field), self.labels.data_ptr(), self.n_fields, out.values.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_region_masks(C.byref(grid._struct), C.byref(spec), _stream(dev)))
-        return out
+        return _masks(self.grid, self.labels, self.n_fields, points, labels, field, out)
 
     def largest_mask(self, out=None):
         """The byte mask of every env's largest region, ``grid.free``'s layout: ``masks(labels=self.largest[:, :1])``. One regions
@@ -949,15 +936,13 @@ def regions(grid, marks=None, n_fields=1, where=True, among=None, mask=None, out
             raise RuntimeError('among goes with marks: without marks the open cells are the free cells')
         among = _cell_bytes(among, 'among', grid.free.shape[0], 'one per cell of the grid')
     where = bool(where)
-    same = lambda a, b: (a is None) == (b is None) and (a is None or a.data_ptr() == b.data_ptr())
     if out is not None:
         if not isinstance(out, Regions) or out.grid is not grid or out.n_fields != n_fields or out.where != where or \
-                not same(out.marks, marks) or not same(out.among, among):
+                not _same(out.marks, marks) or not _same(out.among, among):
             raise RuntimeError('`out` must come from a regions call with the same grid, marks, n_fields, where and among')
         return out.update(mask)
-    dev = _require_gpu(grid.free, *(t for t in (marks, among) if t is not None))
+    new = _new(_require_gpu(grid.free, *_some(marks, among)))
     size, shape = max(n_fields*grid.n_cells, 1), (grid.n_envs, n_fields)
-    new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)
     result = Regions(grid, marks, n_fields, where, among, new((size,), torch.int32, -1), new((size,), torch.float32, 0.),
                      new(shape, torch.int32, 0), new(shape, torch.int32, 0), new(shape, torch.int32, -1), new(shape, torch.int32, 0),
                      new(shape, torch.int32, 0) if passes else None)
@@ -987,30 +972,22 @@ class ViewFields:
         """(ny, nx) bool view of the store of viewpoint ``p`` of env ``e``, row 0 at the lowest y."""
         if self.values is None:
             raise RuntimeError('these view fields keep no byte store (store=False)')
-        first, ny, nx = self.grid.cells(e)
-        at = self.n_points*first + p*ny*nx
-        return self.values[at:at + ny*nx].view(torch.bool).reshape(ny, nx)
+        return _store_view(self.grid, self.values.view(torch.bool), self.n_points, e, p)
 
     def update(self, mask=None):
         """Computes the viewpoints marked in the (N, P) bool ``mask`` (default all) again in place, from :attr:`points` and
         :attr:`headings` as they stand now - move them in place - and from the maps as they stand; the others keep their bytes,
         count and gain. One launch, no host synchronisation, nothing allocated: the call can be captured in a HIP graph."""
         grid, p = self.grid, self.n_points
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, p):
-                raise RuntimeError(f'mask must be an (N, P) = ({grid.n_envs}, {p}) bool tensor')
-            mask = mask.contiguous()
+        mask = _mask(mask, grid.n_envs, p, 'P')
         maps = self.unseen.values if self.unseen is not None else None
-        dev = _require_gpu(self.points, self.countable, self.counts, grid.free,
-                           *(t for t in (self.headings, maps, self.slot, mask, self.values, self.gains) if t is not None))
+        dev = _require_gpu(self.points, self.countable, self.counts, grid.free, *_some(self.headings, maps, self.slot, mask, self.values, self.gains))
         if self.scenery._device() != dev:
             raise RuntimeError(f'all tensors must live on one device; got {self.scenery._device()} and {dev}')
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        spec = _lib.MsNavViews(p, self.points.data_ptr(), ptr(self.headings), self.max_range, self.cos_half if self.headings is not None else 0.,
-                               self.countable.data_ptr(), ptr(maps), self.unseen.n_maps if self.unseen is not None else 0, ptr(self.slot), ptr(mask),
-                               ptr(self.values), self.counts.data_ptr(), ptr(self.gains))
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_views(C.byref(self.scenery._as_struct()), C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        spec = _lib.MsNavViews(p, self.points.data_ptr(), _ptr(self.headings), self.max_range, self.cos_half if self.headings is not None else 0.,
+                               self.countable.data_ptr(), _ptr(maps), self.unseen.n_maps if self.unseen is not None else 0, _ptr(self.slot),
+                               _ptr(mask), _ptr(self.values), self.counts.data_ptr(), _ptr(self.gains))
+        _launch(dev, 'views', grid, spec, self.scenery._as_struct())
         return self
 
 
@@ -1040,10 +1017,7 @@ def view_fields(grid, scenery, points, max_range=10., headings=None, fov=None, c
     arguments. ``points`` and ``headings`` are kept by reference, not copied: :meth:`ViewFields.update` follows them. No host
     synchronisation: the call can be captured in a HIP graph."""
     import math
-    _check(points, 'points', torch.float32, 3)
-    n, p = points.shape[:2]
-    if n != grid.n_envs or p < 1 or points.shape[2] != 2:
-        raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs} and P >= 1; got {tuple(points.shape)}')
+    n, p = _points(grid, points)
     if not isinstance(max_range, (int, float)) or not (0 < max_range < float('inf')):
         raise RuntimeError(f'max_range must be a positive number; got {max_range}')
     if (headings is None) != (fov is None):
@@ -1067,12 +1041,9 @@ def view_fields(grid, scenery, points, max_range=10., headings=None, fov=None, c
     if slot is not None:
         if unseen is None:
             raise RuntimeError('slot goes with unseen: it names the seen map of each viewpoint')
-        if not isinstance(slot, torch.Tensor) or slot.dtype.is_floating_point or slot.dtype == torch.bool or slot.shape != (n, p):
-            raise RuntimeError(f'slot must be an (N, P) = ({n}, {p}) integer tensor')
-        if slot.dtype != torch.int32 or not slot.is_contiguous():
-            slot = slot.to(torch.int32).contiguous()
-    elif unseen is not None and unseen.n_maps not in (1, p):
-        raise RuntimeError(f'without slot, unseen must hold one map per env or one per viewpoint ({p}); it holds {unseen.n_maps}')
+        slot = _index(slot, 'slot', n, p)
+    elif unseen is not None:
+        _default_store(unseen.n_maps, p, f'without slot, unseen must hold one map per env or one per viewpoint ({p}); it holds {unseen.n_maps}')
     if not hasattr(scenery, 'lines') or len(scenery.lines) != n:
         raise RuntimeError(f'scenery must be the Scenery the grid was laid over: {n} envs')
     store = bool(store)
@@ -1102,17 +1073,6 @@ BASIN_MAX_IDS = 256
 _INT_MAX = 2**31 - 1
 
 
-def _field_rule(field, n, p, g, what):
-    """The argument rule of a per-point ``field``: int32 (N, P) or None - then one store an env, or one per point."""
-    if field is None:
-        if g not in (1, p):
-            raise RuntimeError(f'without {what}, there must be one field per env or one per point ({p}); there are {g}')
-        return None
-    if not isinstance(field, torch.Tensor) or field.dtype.is_floating_point or field.dtype == torch.bool or field.shape != (n, p):
-        raise RuntimeError(f'{what} must be an (N, P) = ({n}, {p}) integer tensor')
-    return field.to(torch.int32).contiguous()
-
-
 class PointMarks:
     """Result of :func:`point_marks`: the cells round each of ``points`` as the seeds of ``n_fields`` seeded fields per env.
     ``marks``: the flat uint8 store, a byte a cell and field in the fields' layout (:func:`seeded_fields`' ``marks``) - 1 on every
@@ -1129,22 +1089,17 @@ class PointMarks:
 
     def image(self, e, g=0):
         """(ny, nx) int32 view of the ids of store ``g`` of env ``e``, row 0 at the lowest y."""
-        s, ny, nx = self.grid.cells(e)
-        at = self.n_fields*s + g*ny*nx
-        return self.ids[at:at + ny*nx].reshape(ny, nx)
+        return _store_view(self.grid, self.ids, self.n_fields, e, g)
 
     def update(self):
         """Clears both stores and marks again in place, from :attr:`points` as they stand now - move them in place. Two fills and
         one launch of a lane a point, no host synchronisation, nothing allocated: the call can be captured in a HIP graph."""
         grid = self.grid
-        dev = _require_gpu(self.points, self.marks, self.ids, grid.free, *(t for t in (self.point_ids, self.field) if t is not None))
+        dev = _require_gpu(self.points, self.marks, self.ids, grid.free, *_some(self.point_ids, self.field))
         self.marks.zero_()
         self.ids.fill_(_INT_MAX)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        spec = _lib.MsNavPointMarks(self.n_points, self.points.data_ptr(), ptr(self.field), ptr(self.point_ids), self.n_fields,
-                                    self.marks.data_ptr(), self.ids.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_point_marks(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        _launch(dev, 'point_marks', grid, _lib.MsNavPointMarks(self.n_points, self.points.data_ptr(), _ptr(self.field), _ptr(self.point_ids),
+                                                               self.n_fields, self.marks.data_ptr(), self.ids.data_ptr()))
         return self
 
 
@@ -1160,17 +1115,11 @@ def point_marks(grid, points, n_fields=1, ids=None, field=None):
     nearest agent. See :class:`PointMarks`; the rule: include/megastep_hip.h (``MsNavPointMarks``), DESIGN.md 3.22."""
     if not isinstance(n_fields, int) or n_fields < 1:
         raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
-    _check(points, 'points', torch.float32, 3)
-    n, p = points.shape[:2]
-    if n != grid.n_envs or points.shape[2] != 2 or p < 1:
-        raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
+    n, p = _points(grid, points)
     field = _field_rule(field, n, p, n_fields, 'field')
     if ids is not None:
-        if not isinstance(ids, torch.Tensor) or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.shape != (n, p):
-            raise RuntimeError(f'ids must be an (N, P) = ({n}, {p}) integer tensor')
-        if ids.dtype != torch.int32 or not ids.is_contiguous():
-            ids = ids.to(torch.int32).contiguous()
-    dev = _require_gpu(points, grid.free, *(t for t in (ids, field) if t is not None))
+        ids = _index(ids, 'ids', n, p)
+    dev = _require_gpu(points, grid.free, *_some(ids, field))
     size = max(n_fields*grid.n_cells, 1)
     seeds = PointMarks(grid, points, n_fields, ids, field, torch.zeros(size, dtype=torch.uint8, device=dev),
                        torch.full((size,), _INT_MAX, dtype=torch.int32, device=dev))
@@ -1194,26 +1143,17 @@ class Basins:
 
     def image(self, e, g=0):
         """(ny, nx) int32 view of the labels of field ``g`` of env ``e``, row 0 at the lowest y."""
-        s, ny, nx = self.grid.cells(e)
-        at = self.n_fields*s + g*ny*nx
-        return self.labels[at:at + ny*nx].reshape(ny, nx)
+        return _store_view(self.grid, self.labels, self.n_fields, e, g)
 
     def update(self, mask=None):
         """Labels the fields marked in the (N, G) bool ``mask`` (default all) again in place, from the fields' values and
         :attr:`ids` as they stand now; the others keep labels, sizes, reached and passes. One launch, no host synchronisation,
         nothing allocated: the call can be captured in a HIP graph."""
         grid, g = self.grid, self.n_fields
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs, g):
-                raise RuntimeError(f'mask must be an (N, G) = ({grid.n_envs}, {g}) bool tensor')
-            mask = mask.contiguous()
-        dev = _require_gpu(self.fields.values, self.labels, self.reached, grid.free,
-                           *(t for t in (self.ids, mask, self.sizes, self.passes) if t is not None))
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        spec = _lib.MsNavBasins(g, self.fields.values.data_ptr(), ptr(self.ids), self.n_ids, ptr(mask), self.labels.data_ptr(),
-                                ptr(self.sizes), self.reached.data_ptr(), ptr(self.passes))
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_basins(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        mask = _mask(mask, grid.n_envs, g, 'G')
+        dev = _require_gpu(self.fields.values, self.labels, self.reached, grid.free, *_some(self.ids, mask, self.sizes, self.passes))
+        _launch(dev, 'basins', grid, _lib.MsNavBasins(g, self.fields.values.data_ptr(), _ptr(self.ids), self.n_ids, _ptr(mask), self.labels.data_ptr(),
+                                                      _ptr(self.sizes), self.reached.data_ptr(), _ptr(self.passes)))
         return self
 
     def at(self, points, goal=None):
@@ -1222,17 +1162,12 @@ class Basins:
         integers name the field each point asks; default the one field, or point k field k (then P must be G). One launch, a lane
         a point, no host synchronisation."""
         grid = self.grid
-        _check(points, 'points', torch.float32, 3)
-        n, p = points.shape[:2]
-        if n != grid.n_envs or points.shape[2] != 2 or p < 1:
-            raise RuntimeError(f'points must be (N, P, 2) with N = {grid.n_envs}; got {tuple(points.shape)}')
+        n, p = _points(grid, points)
         goal = _field_rule(goal, n, p, self.n_fields, 'goal')
-        dev = _require_gpu(points, self.fields.values, self.labels, grid.free, *([goal] if goal is not None else []))
+        dev = _require_gpu(points, self.fields.values, self.labels, grid.free, *_some(goal))
         out = torch.empty((n, p), dtype=torch.int32, device=dev)
-        spec = _lib.MsNavBasinQuery(p, points.data_ptr(), goal.data_ptr() if goal is not None else None, self.fields.values.data_ptr(),
-                                    self.labels.data_ptr(), self.n_fields, out.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_basin_query(C.byref(grid._struct), C.byref(spec), _stream(dev)))
+        _launch(dev, 'basin_query', grid, _lib.MsNavBasinQuery(p, points.data_ptr(), _ptr(goal), self.fields.values.data_ptr(), self.labels.data_ptr(),
+                                                               self.n_fields, out.data_ptr()))
         return out
 
     def masks(self, labels, field=None, out=None):
@@ -1243,24 +1178,7 @@ class Basins:
         ``labels=torch.arange(A).expand(N, A)`` the stores are the agents' territories: :func:`seeded_fields`' ``marks``, a
         ``gate``, a :func:`map_channel` as they are. :meth:`Regions.masks`' launch (``ms_nav_region_masks``), no host
         synchronisation."""
-        grid = self.grid
-        if not isinstance(labels, torch.Tensor) or labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.ndim != 2 or \
-                labels.shape[0] != grid.n_envs or labels.shape[1] < 1:
-            raise RuntimeError(f'labels must be an (N, P) integer tensor with N = {grid.n_envs}')
-        n, p = labels.shape
-        labels = labels.to(torch.int32).contiguous()
-        field = _field_rule(field, n, p, self.n_fields, 'field')
-        dev = _require_gpu(labels, self.labels, grid.free, *([field] if field is not None else []))
-        size = max(p*grid.n_cells, 1)
-        if out is None:
-            out = CellLayer(torch.zeros(size, dtype=torch.uint8, device=dev), p, None)
-        elif not isinstance(out, CellLayer) or out.is_float or out.n_fields != p or out.values.shape[0] != size or out.values.device != dev:
-            raise RuntimeError(f'`out` must be the layer of a masks call with the same grid and P = {p}')
-        spec = _lib.MsNavRegionMasks(p, None, labels.data_ptr(), field.data_ptr() if field is not None else None, self.labels.data_ptr(),
-                                     self.n_fields, out.values.data_ptr())
-        with _on(dev):
-            _lib.check(_lib.lib().ms_nav_region_masks(C.byref(grid._struct), C.byref(spec), _stream(dev)))
-        return out
+        return _masks(self.grid, self.labels, self.n_fields, None, labels, field, out)
 
 
 def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
@@ -1295,13 +1213,11 @@ def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
         if ids.shape[0] != size:
             raise RuntimeError(f'ids must have {size} entries, an int per cell and field (n_fields*n_cells = {g}*{grid.n_cells}); got {ids.shape[0]}')
     if out is not None:
-        if not isinstance(out, Basins) or out.fields is not fields or out.n_ids != n_ids or (out.ids is None) != (ids is None) or \
-                (ids is not None and out.ids.data_ptr() != ids.data_ptr()):
+        if not isinstance(out, Basins) or out.fields is not fields or out.n_ids != n_ids or not _same(out.ids, ids):
             raise RuntimeError('`out` must come from a basins call with the same fields, ids and n_ids')
         return out.update(mask)
-    dev = _require_gpu(fields.values, grid.free, *([ids] if ids is not None else []))
+    new = _new(_require_gpu(fields.values, grid.free, *_some(ids)))
     shape = (grid.n_envs, g)
-    new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=dev)
     result = Basins(fields, ids, n_ids, new((size,), torch.int32, -1), new(shape + (n_ids,), torch.int32, 0) if n_ids else None,
                     new(shape, torch.int32, 0), new(shape, torch.int32, 0) if passes else None)
     return result.update(mask)

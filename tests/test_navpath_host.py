@@ -486,6 +486,8 @@ def test_the_python_calls_refuse_what_they_cannot_do():
             call(pts, goal=torch.zeros(2, 3))
         with pytest.raises(RuntimeError, match='integer'):
             call(pts, goal=torch.zeros(2, 4, dtype=torch.int64))
+        with pytest.raises(RuntimeError, match='integer'):
+            call(pts, goal=torch.zeros(2, 3, dtype=torch.bool))        # (a mask mistaken for an index)
     for bad in (0, 65, 2.5):
         with pytest.raises(RuntimeError, match='lookahead'):
             fields.waypoints(pts, lookahead=bad)
