@@ -86,6 +86,9 @@ int ms_host_nav_seed_waypoint(const int* geom, float cell, const unsigned char* 
                               int lookahead, float* waypoint);
 int ms_host_nav_seed_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* point,
                           int max_points, float* points);
+/* ms_host_nav_field_capacity writes the three capacities, in framed cells, of nav_relax_kernel's instantiations (single-goal and
+ * seeded alike): MS_OK, or MS_EINVAL for NULL. */
+int ms_host_nav_field_capacity(int* capacities);
 /* Host instantiation of the seen maps' rule (kernels/navseen.h: the ray, the sample - the very functions every lane of
  * nav_seen_kernel evaluates) for ONE env on HOST arrays, one call of ms_nav_seen: geom = (jx0, iy0, nx, ny), countable
  * (ny x nx bytes), origins (P, 2), dirs (P, R, 2), distances (P, R), slot (P) or NULL (then P == S), reset (S) or NULL, maps

@@ -257,6 +257,7 @@ PROTOTYPES = {
     'ms_host_nav_seed_field': (_int, [_ptr, _flt, _ptr, _ptr, _int, _ptr, _int, _ptr, _ptr]),
     'ms_host_nav_seed_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_seed_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_host_nav_field_capacity': (_int, [_ptr]),
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
     'ms_host_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows)]),
     'ms_host_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws)]),

@@ -1030,6 +1030,8 @@ int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* fre
     return sweeps;
 }
 
+int ms_host_nav_field_capacity(int* capacities) { return nav_host_capacities(capacities, nav_capacity); }
+
 // Seen maps (navseen.h): the same discipline; an env of more than 2^20 cells is refused, and nothing is enqueued.
 constexpr int NAV_SEEN_MAX_CELLS = 1 << 20;
 static bool nav_seen_ok(const MsNavSeen* v) {

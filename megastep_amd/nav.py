@@ -193,6 +193,12 @@ def nav_grid(scenery, cell=.125, clearance=None, config=None):
     return grid
 
 
+#: the framed cells - ``(nx + 2)*(ny + 2)`` - an env may have for :func:`distance_fields` and :func:`seeded_fields` to relax it in
+#: LDS, for each of the kernel's three instantiations (40, 80 and 160 KiB); the launch is the least that holds the grid's largest
+#: env, and a larger env is relaxed in global memory, to the same bits
+FIELD_CAPACITY = (8176, 16368, 32752)
+
+
 class _Fields:
     """What :class:`DistanceFields` and :class:`SeededFields` share: the flat store of ``n_goals`` fields per env, its views, the
     query and the argument rules of the calls that follow the fields. A subclass names its own tensors (``_own``) and makes the

@@ -29,7 +29,7 @@ def _draw_goals(geoms, n_goals, rng):
     return goals
 
 
-def _check(sc, grid, fields, goals, rng, n_points=48, worth=None):
+def _check(sc, grid, fields, goals, rng, n_points=48, worth=None, cell=CELL, clearance=RADIUS):
     """Free cells, every field and a batch of queries of every env against nav_rule, as bits. Returns how many goals had an
     anchor and a finite region of more than 500 cells."""
     n, G = goals.shape[:2]
@@ -45,16 +45,16 @@ def _check(sc, grid, fields, goals, rng, n_points=48, worth=None):
     for e in range(n):
         walls = _walls(sc, e)
         ge = tuple(int(v) for v in geom[e])
-        assert ge == nav_rule.geometry(walls, CELL)
-        free = nav_rule.free(walls, ge, CELL, RADIUS)
+        assert ge == nav_rule.geometry(walls, cell)
+        free = nav_rule.free(walls, ge, cell, clearance)
         assert np.array_equal(grid.image(e).cpu().numpy(), free), e
-        graph = nav_rule._neighbours(free, CELL)
-        want = [nav_rule.field(free, ge, CELL, goals[e, g], graph) for g in range(G)]
+        graph = nav_rule._neighbours(free, cell)
+        want = [nav_rule.field(free, ge, cell, goals[e, g], graph) for g in range(G)]
         for g in range(G):
             got = fields.image(e, g).cpu().numpy()
             assert np.array_equal(bits(got), bits(want[g])), (e, g, int((bits(got) != bits(want[g])).sum()))
-            good += bool(nav_rule.anchors(goals[e, g], ge, CELL, free)) and int(np.isfinite(want[g]).sum()) > 500
-        want_q = np.array([nav_rule.query(want[which[e, k]], ge, CELL, free, points[e, k]) for k in range(n_points)], F)
+            good += bool(nav_rule.anchors(goals[e, g], ge, cell, free)) and int(np.isfinite(want[g]).sum()) > 500
+        want_q = np.array([nav_rule.query(want[which[e, k]], ge, cell, free, points[e, k]) for k in range(n_points)], F)
         assert np.array_equal(bits(got_q[e]), bits(want_q)), e
     return good
 

@@ -13,22 +13,22 @@ from tests.test_gpu_navfield import _custom, _draw_goals, _scenery, _walls
 pytestmark = pytest.mark.gpu
 
 
-def _worlds(grid, fields, e):
+def _worlds(grid, fields, e, cell=CELL):
     """path_rule's worlds of env e, one per field, and their hop tables - read back from the device."""
     geom = tuple(int(v) for v in grid.geom[e].cpu())
     free = grid.image(e).cpu().numpy()
-    worlds = [(geom, CELL, free, fields.image(e, g).cpu().numpy(), fields.goals[e, g].cpu().numpy()) for g in range(fields.n_goals)]
+    worlds = [(geom, cell, free, fields.image(e, g).cpu().numpy(), fields.goals[e, g].cpu().numpy()) for g in range(fields.n_goals)]
     return worlds, [path_rule.hops(w) for w in worlds]
 
 
-def _rule(grid, fields, points, which, lookahead=None, max_points=None):
+def _rule(grid, fields, points, which, lookahead=None, max_points=None, cell=CELL):
     """What path_rule says for points (N, P, 2) following fields `which` (N, P): (waypoints, hops) or (paths, counts)."""
     n, p = points.shape[:2]
     G = fields.n_goals
     way, hops = np.full((n, p, 2), np.nan, F), np.full((n, p), -1, np.int32)
     paths, counts = np.full((n, p, max_points or 1, 2), np.nan, F), np.zeros((n, p), np.int32)
     for e in range(n):
-        worlds, tables = _worlds(grid, fields, e)
+        worlds, tables = _worlds(grid, fields, e, cell)
         for k in range(p):
             g = int(which[e, k])
             if not 0 <= g < G:

@@ -20,19 +20,19 @@ def _env(grid, e):
     return tuple(int(v) for v in grid.geom[e].cpu()), _np(grid.image(e)), slice(first, first + ny*nx)
 
 
-def _rule_fields(grid, marks, n_fields, where, among):
+def _rule_fields(grid, marks, n_fields, where, among, cell=CELL):
     """seed_rule's fields for marks in the fields' layout: ([env][field] (ny, nx) float32, (N, G) seed counts)."""
     marks, among = _np(marks), None if among is None else _np(among)
     fields, counts = [], np.zeros((grid.n_envs, n_fields), np.int32)
     for e in range(grid.n_envs):
         geom, free, cells = _env(grid, e)
-        graph = nav_rule._neighbours(free, CELL) if free.size else None
+        graph = nav_rule._neighbours(free, cell) if free.size else None
         row = []
         for g in range(n_fields):
             at = n_fields*cells.start + g*free.size
             seeds = seed_rule.seeds(free, marks[at:at + free.size].reshape(free.shape), where, None if among is None else among[cells].reshape(free.shape))
             counts[e, g] = seeds.sum()
-            row.append(seed_rule.field(free, CELL, seeds, graph))
+            row.append(seed_rule.field(free, cell, seeds, graph))
         fields.append(row)
     return fields, counts
 
@@ -48,7 +48,7 @@ def _fields_equal(grid, got, want):
     return worth
 
 
-def _queries_equal(grid, got, want, points, which):
+def _queries_equal(grid, got, want, points, which, cell=CELL):
     """`at` for points (N, P, 2) against fields `which` (N, P), out-of-range indices included, as bits."""
     have = got.at(torch.as_tensor(points, device='cuda'), goal=torch.as_tensor(which, device='cuda'))
     rule = np.full(which.shape, np.inf, F)
@@ -56,7 +56,7 @@ def _queries_equal(grid, got, want, points, which):
         geom, free, _ = _env(grid, e)
         for k in range(which.shape[1]):
             if 0 <= which[e, k] < got.n_goals:
-                rule[e, k] = seed_rule.query((geom, CELL, free, want[e][which[e, k]]), points[e, k])
+                rule[e, k] = seed_rule.query((geom, cell, free, want[e][which[e, k]]), points[e, k])
     assert np.array_equal(bits(_np(have)), bits(rule))
     return rule
 
@@ -147,14 +147,14 @@ def test_a_large_plan_relaxes_in_global_memory_to_the_same_bits():
     assert _fields_equal(grid, seen, want) == 2
 
 
-def _follow_rule(grid, fields, points, which, lookahead=None, max_points=None):
+def _follow_rule(grid, fields, points, which, lookahead=None, max_points=None, cell=CELL):
     """What seed_rule says for points (N, P, 2) following fields `which` (N, P) of the device's own fields."""
     n, p = points.shape[:2]
     way, hops = np.full((n, p, 2), np.nan, F), np.full((n, p), -1, np.int32)
     paths, counts = np.full((n, p, max_points or 1, 2), np.nan, F), np.zeros((n, p), np.int32)
     for e in range(n):
         geom, free, _ = _env(grid, e)
-        worlds = [(geom, CELL, free, _np(fields.image(e, g))) for g in range(fields.n_goals)]
+        worlds = [(geom, cell, free, _np(fields.image(e, g))) for g in range(fields.n_goals)]
         tables = [seed_rule.hops(world) for world in worlds]
         for k in range(p):
             g = int(which[e, k])

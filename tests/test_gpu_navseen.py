@@ -35,8 +35,9 @@ def _np(t):
 class _Mirror:
     """seen_rule's copy of a SeenMaps: the maps and totals of every env, moved on call by call."""
 
-    def __init__(self, maps):
+    def __init__(self, maps, cell=CELL):
         grid = maps.grid
+        self.cell = cell
         self.S = maps.n_maps
         self.geom = [tuple(int(v) for v in g) for g in _np(grid.geom)]
         self.countable = [_np(maps.countable)[grid.cells(e)[0]:grid.cells(e)[0] + grid.cells(e)[1]*grid.cells(e)[2]] for e in range(grid.n_envs)]
@@ -48,7 +49,7 @@ class _Mirror:
         gained = np.zeros_like(self.totals)
         for e, geom in enumerate(self.geom):
             self.maps[e], gained[e], self.totals[e] = seen_rule.call(
-                geom, CELL, self.countable[e], self.maps[e], self.totals[e], origins[e], dirs[e], distances[e],
+                geom, self.cell, self.countable[e], self.maps[e], self.totals[e], origins[e], dirs[e], distances[e],
                 slot=None if slot is None else slot[e], max_range=max_range, reset=None if reset is None else reset[e])
         return gained
 
@@ -121,14 +122,14 @@ def test_a_large_plan_with_many_words_a_lane_and_rays_cut_by_max_range():
     assert (mirror.totals > 0).all() and mirror.totals.sum() > 300
 
 
-def _by_hand(geoms_and_free, device='cuda'):
+def _by_hand(geoms_and_free, device='cuda', cell=CELL, clearance=RADIUS):
     """A NavGrid laid out by hand: [(geom, free (ny, nx) bool)] per env."""
     from megastep_amd import cuda
     geom = np.array([g for g, _ in geoms_and_free], np.int32)
     starts = np.concatenate([[0], np.cumsum(geom[:, 2].astype(np.int64)*geom[:, 3])]).astype(np.int64)
     free = np.concatenate([f.reshape(-1).astype(np.uint8) for _, f in geoms_and_free] + [np.zeros(1, np.uint8)])
     dev = lambda a: torch.as_tensor(a, device=device)
-    return cuda.NavGrid(dev(geom), dev(starts), dev(free), CELL, RADIUS, geom, starts)
+    return cuda.NavGrid(dev(geom), dev(starts), dev(free), cell, clearance, geom, starts)
 
 
 def _fans(rng, centres, R, reach, device='cuda'):

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from tests.test_abi import ROOT, declared_symbols
-from tests.test_navfield_host import CELL, RADIUS, F, INF, nav_rule
+from tests.test_navfield_host import CELL, CELLS, RADIUS, F, INF, nav_rule
 from tests.test_navpath_host import NEIGHBOURS, path_rule
 from tests.test_navseed_host import host_follow, seed_rule
 from tests.test_navregion_host import _Host, _max_framed, serpentine
@@ -251,28 +251,29 @@ def bound(longest):
 class _World:
     """Envs laid out by hand: [(geom, free (ny, nx) bool, [seeds (ny, nx) bool]*G)], the fields by seed_rule's Dijkstra."""
 
-    def __init__(self, envs, G=1):
+    def __init__(self, envs, G=1, cell=CELL, clearance=RADIUS):
+        self.cell, self.clearance = cell, clearance
         self.geom = np.array([g for g, _, _ in envs], np.int32)
         self.images = [np.asarray(f, bool) for _, f, _ in envs]
         self.starts = np.concatenate([[0], np.cumsum([f.size for f in self.images])]).astype(np.int64)
         self.free = np.concatenate([f.reshape(-1) for f in self.images] + [np.zeros(0, bool)]).astype(np.uint8)
         self.G, self.N = G, len(envs)
         self.seeds = [[np.asarray(s, bool) & f for s in seeds] for (_, _, seeds), f in zip(envs, self.images)]
-        self.values = np.concatenate([seed_rule.field(f, CELL, s).reshape(-1) if f.size else np.zeros(0, F)
+        self.values = np.concatenate([seed_rule.field(f, cell, s).reshape(-1) if f.size else np.zeros(0, F)
                                       for f, seeds in zip(self.images, self.seeds) for s in seeds] + [np.zeros(0, F)]).astype(F)
 
     def host(self, **kw):
-        return _BasinHost(self.geom, self.starts, self.free, **kw)
+        return _BasinHost(self.geom, self.starts, self.free, cell=self.cell, clearance=self.clearance, **kw)
 
     def rule(self, values=None, **kw):
-        return basin_rule.call(self.geom, self.starts, CELL, self.free, self.values if values is None else values, self.G, **kw)
+        return basin_rule.call(self.geom, self.starts, self.cell, self.free, self.values if values is None else values, self.G, **kw)
 
     def at(self, n, g=0):
         cells = self.images[n].size
         return self.G*int(self.starts[n]) + g*cells, cells
 
     def centre(self, n, i, j, di=0., dj=0.):
-        return [(int(self.geom[n][0]) + j + .5 + dj)*CELL, (int(self.geom[n][1]) + i + .5 + di)*CELL]
+        return [(int(self.geom[n][0]) + j + .5 + dj)*self.cell, (int(self.geom[n][1]) + i + .5 + di)*self.cell]
 
 
 def _cells(shape, *cells):
@@ -313,15 +314,17 @@ def hand():
     return _HAND[0]
 
 
-def _index(point, geom):
+def _index(point, geom, cell=CELL):
     jx0, iy0, nx, ny = geom
-    j, i = int(np.floor(float(point[0])/CELL)) - jx0, int(np.floor(float(point[1])/CELL)) - iy0
+    j, i = int(np.floor(float(point[0])/cell)) - jx0, int(np.floor(float(point[1])/cell)) - iy0
     assert 0 <= i < ny and 0 <= j < nx
     return i*nx + j
 
 
 @pytest.mark.parametrize('launch', ['fits', 'stored'])
 def test_on_the_hand_made_grids_the_label_is_the_cell_the_path_ends_on(launch):
+    """At a cell of 0.125 only: that most paths start on the very cell they are asked from (`own > .8*checked`) is a property of
+    centres that are exact in binary32, not of the kernel."""
     w = hand()
     from megastep_amd import nav
     assert nav.BASIN_CAPACITY[0] < w.images[6].size <= _max_framed(w.geom) <= nav.BASIN_CAPACITY[1]
@@ -507,29 +510,38 @@ def test_the_two_statements_of_the_successor_agree():
 # ---------------------------------------------------------------------------------------------------------------------
 # the six plans: seeds by point marks at two points an env, queries from every spawn point
 # ---------------------------------------------------------------------------------------------------------------------
-_PLANS = []
+_PLANS = {}
 
 
-def plan_world():
+def plan_world(cell=CELL, r=RADIUS):
     """(w, marks, ids, points): test_navseed_host's six plans as one grid of one field an env, seeded by point_mark_rule at two
     spawn points an env."""
-    if not _PLANS:
+    if (cell, r) not in _PLANS:
         from tests.test_navseed_host import cases
-        cs = cases()[::2]
+        cs = cases(cell, r)[::2]
         rng = np.random.RandomState(23)
         geom = np.array([c.geom for c in cs], np.int32)
         starts = np.concatenate([[0], np.cumsum([c.free.size for c in cs])]).astype(np.int64)
         free = np.concatenate([c.free.reshape(-1) for c in cs]).astype(np.uint8)
         points = np.stack([(c.points[rng.choice(len(c.points), 2, replace=False)] + rng.uniform(-.05, .05, (2, 2))).astype(F) for c in cs])
-        marks, ids = point_mark_rule.call(geom, starts, CELL, free, points)
-        w = _World([(tuple(c.geom), c.free, [marks[starts[n]:starts[n + 1]].reshape(c.free.shape) != 0]) for n, c in enumerate(cs)])
+        marks, ids = point_mark_rule.call(geom, starts, cell, free, points)
+        w = _World([(tuple(c.geom), c.free, [marks[starts[n]:starts[n + 1]].reshape(c.free.shape) != 0]) for n, c in enumerate(cs)],
+                   cell=cell, clearance=r)
         w.cases = cs
-        _PLANS.append((w, marks, ids, points))
-    return _PLANS[0]
+        _PLANS[cell, r] = (w, marks, ids, points)
+    return _PLANS[cell, r]
 
 
 def test_on_the_six_plans_point_marks_and_basins_are_the_rules():
-    w, marks, ids, points = plan_world()
+    _point_marks_and_basins_are_the_rules(*plan_world())
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_point_marks_and_basins_are_the_rules_at_other_cell_widths(cell, r):
+    _point_marks_and_basins_are_the_rules(*plan_world(cell, r))
+
+
+def _point_marks_and_basins_are_the_rules(w, marks, ids, points):
     host = w.host()
     got_marks, got_ids = host.marks(points)
     assert np.array_equal(got_marks, marks) and np.array_equal(got_ids, ids)
@@ -537,39 +549,50 @@ def test_on_the_six_plans_point_marks_and_basins_are_the_rules():
     got = host.basins(w.values, 1, ids, 2)
     want = w.rule(ids=ids, n_ids=2)
     same(got, want)
-    assert np.array_equal(got['sizes'].sum(-1), got['reached']) and (got['sizes'] > 100).all()
+    assert np.array_equal(got['sizes'].sum(-1), got['reached']) and (got['sizes'] > 100*(CELL/w.cell)**2).all()      # (the same floor, in cells)
     print('passes of the serial sweeps on the six plans:', got['passes'].reshape(-1).tolist(), 'longest chains:', want['longest'].reshape(-1).tolist())
     assert all(1 <= got['passes'][n, 0] <= bound(want['longest'][n, 0]) for n in range(6))
 
 
 def test_on_the_six_plans_the_query_from_every_spawn_point_is_the_cell_its_path_ends_on():
-    w, marks, ids, points = plan_world()
+    assert _query_is_the_cell_the_path_ends_on(*plan_world()) > 15000
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_the_query_is_the_cell_the_path_ends_on_at_other_cell_widths(cell, r):
+    """From every fourth spawn point of the same plans; the spawn points themselves do not move with the cell."""
+    assert _query_is_the_cell_the_path_ends_on(*plan_world(cell, r), stride=4) > 15000/4*.9
+
+
+def _query_is_the_cell_the_path_ends_on(w, marks, ids, points, stride=1):
     host = w.host()
     cells_of = host.basins(w.values)['labels']                           # (no ids: a label is the seed's cell)
     owners = host.basins(w.values, 1, ids, 2)['labels']
-    P = max(len(c.points) for c in w.cases)
+    asked = [c.points[::stride] for c in w.cases]
+    P = max(len(a) for a in asked)
     spawns = np.full((6, P, 2), np.nan, F)
-    for n, c in enumerate(w.cases):
-        spawns[n, :len(c.points)] = c.points
+    for n, a in enumerate(asked):
+        spawns[n, :len(a)] = a
     field = np.zeros((6, P), np.int32)
     got = host.at(w.values, cells_of, 1, spawns, field)
-    assert np.array_equal(got, basin_query_rule.call(w.geom, w.starts, CELL, w.free, w.values, cells_of, 1, spawns, field))
+    assert np.array_equal(got, basin_query_rule.call(w.geom, w.starts, w.cell, w.free, w.values, cells_of, 1, spawns, field))
     assert np.array_equal(got, host.at(w.values, cells_of, 1, spawns))    # (one field: the default asks it)
     who = host.at(w.values, owners, 1, spawns)
     found = 0
     for n, c in enumerate(w.cases):
         at, cells = w.at(n)
-        assert (got[n, len(c.points):] == -1).all()                      # (the NaN points)
-        for k, p in enumerate(c.points):
+        assert (got[n, len(asked[n]):] == -1).all()                      # (the NaN points)
+        for k, p in enumerate(asked[n]):
             pts, count = host_follow(c.world[:3] + (w.values[at:at + cells].reshape(c.free.shape),), p, max_points=cells + 2)
             if count == 0:
                 assert got[n, k] == -1 and who[n, k] == -1
                 continue
             assert count >= 2                                            # (a converged field: no chain breaks)
-            cell = _index(pts[count - 1], tuple(c.geom))
+            cell = _index(pts[count - 1], tuple(c.geom), w.cell)
             assert got[n, k] == cell and who[n, k] == ids[at + cell], (n, k)
             found += 1
-    assert found > 15000 and set(np.unique(who).tolist()) >= {0, 1}
+    assert set(np.unique(who).tolist()) >= {0, 1}
+    return found
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from tests.test_abi import ROOT, declared_symbols
-from tests.test_navfield_host import CELL, RADIUS, F, bits, nav_rule
+from tests.test_navfield_host import CELL, CELLS, RADIUS, F, bits, nav_rule
 from tests.test_navwindow_host import Layer
 
 INF, NAN = F(np.inf), F(np.nan)
@@ -129,7 +129,7 @@ def _layer_spec(layer, keep):
 class _Host:
     """ms_host_nav_draws on host arrays, the outputs its own (sentinels to begin with): call after call moves the counter on."""
 
-    def __init__(self, geom, starts, cell, free, source, P, K, counter=None, lo=None, hi=None, where=True, gate=None, seed=0):
+    def __init__(self, geom, starts, cell, free, source, P, K, counter=None, lo=None, hi=None, where=True, gate=None, seed=0, clearance=RADIUS):
         from megastep_amd import _lib
         self.geom, self.starts, self.free = _aligned(geom), np.ascontiguousarray(starts, np.int64), np.ascontiguousarray(free, np.uint8)
         N = len(self.geom)
@@ -138,7 +138,7 @@ class _Host:
         self.counter = np.zeros((N, P), np.int32) if counter is None else np.array(counter, np.int32)
         self._keep = []
         cells = self.geom[:, 2].astype(np.int64)*self.geom[:, 3]
-        self.grid = _lib.MsNavGrid(N, cell, RADIUS, self.geom.ctypes.data, self.starts.ctypes.data, 0, self.free.ctypes.data)
+        self.grid = _lib.MsNavGrid(N, cell, clearance, self.geom.ctypes.data, self.starts.ctypes.data, 0, self.free.ctypes.data)
         o = self.out
         self.spec = _lib.MsNavDraws(source=_layer_spec(source, self._keep), gate=_layer_spec(gate, self._keep) if gate is not None else _lib.MsNavLayer(),
                                     where=int(bool(where)), lo=0. if lo is None else float(lo), hi=0. if hi is None else float(hi), n_sets=P, n_draws=K,
@@ -165,11 +165,11 @@ def same(got, want):
             assert np.array_equal(bits(got[key]), bits(want[key])), (key, int((bits(got[key]) != bits(want[key])).sum()))
 
 
-def _same(geom, starts, free, source, P, K, counter=None, **kw):
+def _same(geom, starts, free, source, P, K, counter=None, cell=CELL, clearance=RADIUS, **kw):
     """One call of the host instantiation against one of the rule; returns the rule's result."""
-    host = _Host(geom, starts, CELL, free, source, P, K, counter=counter, **kw)
+    host = _Host(geom, starts, cell, free, source, P, K, counter=counter, clearance=clearance, **kw)
     counter = host.counter.copy()
-    want = draw_rule.call(geom, starts, CELL, free, source, P, K, counter, **kw)
+    want = draw_rule.call(geom, starts, cell, free, source, P, K, counter, **kw)
     same(host(), want)
     return want
 
@@ -310,34 +310,44 @@ def test_a_field_names_the_store_each_set_reads_and_a_bad_index_leaves_it_empty(
 # ---------------------------------------------------------------------------------------------------------------------
 # real plans
 # ---------------------------------------------------------------------------------------------------------------------
-_PLANS = []
+_PLANS = {}
 
 
-def plan_world():
+def plan_world(cell=CELL, r=RADIUS):
     """test_navseen_host's six plans (three plain, three oblique) as ONE grid, and the rule's distance field round each plan's
     first viewer: (geom, starts, free, D)."""
-    if not _PLANS:
+    if (cell, r) not in _PLANS:
         from tests.test_navseen_host import cases
-        cs = cases()
+        cs = cases(cell, r)
         geom = np.array([c.geom for c in cs], np.int32)
         starts = np.concatenate([[0], np.cumsum([c.free.size for c in cs])]).astype(np.int64)
         free = np.concatenate([c.free.reshape(-1).astype(np.uint8) for c in cs])
-        D = np.concatenate([nav_rule.field(c.free, c.geom, CELL, c.origins[0]).reshape(-1) for c in cs])
-        _PLANS.append((geom, starts, free, D))
-    return _PLANS[0]
+        D = np.concatenate([nav_rule.field(c.free, c.geom, cell, c.origins[0]).reshape(-1) for c in cs])
+        _PLANS[cell, r] = (geom, starts, free, D)
+    return _PLANS[cell, r]
 
 
 def test_on_real_plans_every_drawn_cell_is_free_and_at_a_distance_in_the_band():
-    geom, starts, free, D = plan_world()
+    _drawn_cells_are_free_and_in_the_band(CELL, RADIUS)
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_on_real_plans_the_draws_are_the_rule_at_other_cell_widths(cell, r):
+    """A drawn point is its cell's centre, ((origin + k) + .5)*c: rounded when the cell is no power of two."""
+    _drawn_cells_are_free_and_in_the_band(cell, r)
+
+
+def _drawn_cells_are_free_and_in_the_band(cell, r):
+    geom, starts, free, D = plan_world(cell, r)
     lo, hi = F(2.), F(5.)
     for K in (1, 7, 256):
-        want = _same(geom, starts, free, Layer(D), 2, K, lo=lo, hi=hi, seed=K)
+        want = _same(geom, starts, free, Layer(D), 2, K, lo=lo, hi=hi, seed=K, cell=cell, clearance=r)
         assert (want['counts'] > 50).all() and (want['cells'] >= 0).all()
         at = starts[:-1, None, None] + want['cells']
         assert (free[at] != 0).all() and np.array_equal(bits(D[at]), bits(want['values']))
         assert ((want['values'] >= lo) & (want['values'] <= hi)).all()
         for n in range(len(geom)):
-            x, y = nav_rule.centres(tuple(geom[n]), CELL)
+            x, y = nav_rule.centres(tuple(geom[n]), cell)
             nx = int(geom[n, 2])
             assert np.array_equal(want['points'][n, ..., 0], x[want['cells'][n] % nx]) and np.array_equal(want['points'][n, ..., 1], y[want['cells'][n]//nx])
     assert len(np.unique(want['cells'][0])) > 100

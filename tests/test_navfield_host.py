@@ -19,6 +19,11 @@ F = np.float32
 INF = F(np.inf)
 DIAGONAL = F(1.41421356)
 CELL, RADIUS = .125, .15/2**.5          # the defaults: cuda.nav_grid's cell and core.AGENT_RADIUS
+# (cell, clearance) pairs whose cell is no power of two - at .125 a centre ((origin + k) + .5)*c, a quotient x/c, a diagonal
+# c*1.41421356f, a sample count len/(.5f*c) and an area cells*(c*c) are all exact, so a slip in any of them goes unseen there;
+# each has cell <= 1.4*clearance, the last with a clearance that is not the default either.  The nav tests that hold the library
+# to a numpy rule run at these too (tests/test_gpu_navcells.py and the `_at_other_cell_widths` tests of the host modules).
+CELLS = [(.1, RADIUS), (.14, RADIUS), (.2, .15)]
 
 
 class nav_rule:
@@ -443,6 +448,26 @@ def test_nav_geometry_is_the_rules_and_the_python_calls_refuse_what_they_cannot_
         cuda.nav_grid(sc, cell=.2, clearance=RADIUS)
     with pytest.raises(RuntimeError, match='positive'):
         cuda.nav_grid(sc, cell=0., clearance=RADIUS)
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_nav_geometry_is_the_rules_at_other_cell_widths(cell, r):
+    """floor(x/c) of the walls' bounding box at cells that are no power of two, and the pairs pass nav_grid's own check (what is
+    refused then is the CPU scenery)."""
+    from megastep_amd import cuda
+    geoms, sc = _cpu_scenery(3)
+    geom, starts = cuda.nav_geometry(sc, cell)
+    af = sc.n_agents*sc.model.shape[0]
+    for e in range(3):
+        walls = sc.lines[e][af:].numpy()
+        assert tuple(geom[e]) == nav_rule.geometry(walls, cell)
+        x, y = nav_rule.centres(tuple(geom[e]), cell)
+        pts = walls.reshape(-1, 2)
+        assert x[0] <= pts[:, 0].min() - cell/2 and x[-1] > pts[:, 0].max() + cell/2
+        assert y[0] <= pts[:, 1].min() - cell/2 and y[-1] > pts[:, 1].max() + cell/2
+    assert starts[0] == 0 and np.array_equal(np.diff(starts), geom[:, 2].astype(np.int64)*geom[:, 3])
+    with pytest.raises(RuntimeError, match='GPU'):
+        cuda.nav_grid(sc, cell=cell, clearance=r)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from tests.test_abi import ROOT, declared_symbols
-from tests.test_navfield_host import CELL, DIAGONAL, F, INF, RADIUS, _crossings, _world, bits, nav_rule, plans, spawn_points
+from tests.test_navfield_host import CELL, CELLS, DIAGONAL, F, INF, RADIUS, _crossings, _world, bits, nav_rule, plans, spawn_points
 
 NAN = F(np.nan)
 NEIGHBOURS = ((0, 1), (1, 0), (0, -1), (-1, 0), (1, 1), (1, -1), (-1, -1), (-1, 1))
@@ -179,25 +179,25 @@ class path_rule:
 # the inputs: three plain and three oblique plans, a goal each, sixty starts each
 # ---------------------------------------------------------------------------------------------------------------------
 class _Case:
-    def __init__(self, g, rng):
-        self.walls, self.geom, self.free = _world(g)
+    def __init__(self, g, rng, cell=CELL, r=RADIUS):
+        self.walls, self.geom, self.free = _world(g, cell, r)
         pts = spawn_points(g)
         self.goal = (pts[rng.randint(len(pts))] + rng.uniform(-.05, .05, 2)).astype(F)
         self.points = (pts[rng.choice(len(pts), 60)] + rng.uniform(-.05, .05, (60, 2))).astype(F)
-        self.D = nav_rule.field(self.free, self.geom, CELL, self.goal)
-        self.world = (self.geom, CELL, self.free, self.D, self.goal)
+        self.D = nav_rule.field(self.free, self.geom, cell, self.goal)
+        self.world = (self.geom, cell, self.free, self.D, self.goal)
         self.table = path_rule.hops(self.world)
-        self.g = np.array([nav_rule.query(self.D, self.geom, CELL, self.free, p) for p in self.points], F)
+        self.g = np.array([nav_rule.query(self.D, self.geom, cell, self.free, p) for p in self.points], F)
 
 
-_CASES = []
+_CASES = {}
 
 
-def cases():
-    if not _CASES:
+def cases(cell=CELL, r=RADIUS):
+    if (cell, r) not in _CASES:
         rng = np.random.RandomState(21)
-        _CASES.extend(_Case(g, rng) for g in plans(3) + plans(3, oblique=True))
-    return _CASES
+        _CASES[cell, r] = [_Case(g, rng, cell, r) for g in plans(3) + plans(3, oblique=True)]
+    return _CASES[cell, r]
 
 
 def test_every_finite_query_has_a_chain_that_ends_on_the_goal():
@@ -297,8 +297,21 @@ def _same(world, p, table, lookaheads=(16,), max_points=(8,)):
 
 
 def test_the_host_instantiations_are_the_rule_bit_for_bit():
+    _host_instantiations_are_the_rule(cases())
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_the_host_instantiations_are_the_rule_at_other_cell_widths(cell, r):
+    """The same comparison on the same plans, goals and starts, gridded at cells that are no power of two."""
+    found = cases(cell, r)
+    assert sum(np.isfinite(case.g).sum() for case in found) >= .8*sum(len(case.g) for case in found)
+    assert all(np.isfinite(case.D).sum() > 500 for case in found)
+    _host_instantiations_are_the_rule(found)
+
+
+def _host_instantiations_are_the_rule(found):
     cut = 0
-    for case in cases():
+    for case in found:
         for k, p in enumerate(case.points):
             count = _same(case.world, p, case.table, (1, 2, 16, 64) if k % 4 == 0 else (16,), (8, 256) if k % 4 == 0 else (8,))
             cut += count > 8

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from tests.test_abi import ROOT, declared_symbols
-from tests.test_navfield_host import CELL, RADIUS, F, bits, nav_rule
+from tests.test_navfield_host import CELL, CELLS, RADIUS, F, bits, nav_rule
 from tests.test_navdraw_host import _aligned
 
 NAN = F(np.nan)
@@ -184,12 +184,12 @@ def _max_framed(geom):
 class _Host:
     """The three host entries on one grid of host arrays; the outputs start as sentinels."""
 
-    def __init__(self, geom, starts, free, cell=CELL, max_framed=None):
+    def __init__(self, geom, starts, free, cell=CELL, max_framed=None, clearance=RADIUS):
         from megastep_amd import _lib
         self.geom, self.starts = _aligned(geom), np.ascontiguousarray(starts, np.int64)
         self.free = np.ascontiguousarray(np.concatenate([np.asarray(free, np.uint8).reshape(-1), np.zeros(1, np.uint8)]))
         self.N, self.cell = len(self.geom), cell
-        self.grid = _lib.MsNavGrid(self.N, cell, RADIUS, self.geom.ctypes.data, self.starts.ctypes.data,
+        self.grid = _lib.MsNavGrid(self.N, cell, clearance, self.geom.ctypes.data, self.starts.ctypes.data,
                                    _max_framed(self.geom) if max_framed is None else max_framed, self.free.ctypes.data)
         self.h = _lib.lib()
 
@@ -451,18 +451,41 @@ def test_masks_by_a_straddling_point_are_two_regions_and_the_mask_of_minus_one_i
 # ---------------------------------------------------------------------------------------------------------------------
 # real plans
 # ---------------------------------------------------------------------------------------------------------------------
-_PLANS = []
+_PLANS = {}
 
 
-def plan_regions():
+def plan_regions(cell=CELL, r=RADIUS):
     """test_navdraw_host's plan_world - the six plans as one grid, and the rule's field round each plan's first viewer - with the
     host's regions of it and the rule's: (geom, starts, free, D, host, got, want)."""
-    if not _PLANS:
+    if (cell, r) not in _PLANS:
         from tests.test_navdraw_host import plan_world
-        geom, starts, free, D = plan_world()
-        host = _Host(geom, starts, free)
-        _PLANS.append((geom, starts, free, D, host, host.regions(), region_rule.call(geom, starts, CELL, free)))
-    return _PLANS[0]
+        geom, starts, free, D = plan_world(cell, r)
+        host = _Host(geom, starts, free, cell=cell, clearance=r)
+        _PLANS[cell, r] = (geom, starts, free, D, host, host.regions(), region_rule.call(geom, starts, cell, free))
+    return _PLANS[cell, r]
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_on_the_six_plans_the_labels_areas_masks_and_pairs_are_the_rules_at_other_cell_widths(cell, r):
+    """Labels and float areas - cells*(c*c), rounded when the cell is no power of two - then the labels at points, the mask of a
+    point and whether two points are together, each against the rule and against the distance field's finiteness."""
+    from tests.test_navseen_host import cases
+    geom, starts, free, D, host, got, want = plan_regions(cell, r)
+    same(got, want)
+    assert (want['counts'] >= 1).all() and (want['largest_cells'] > 500*(CELL/cell)**2).all() and (got['passes'] >= 1).all()
+    cs = cases(cell, r)
+    points = np.stack([c.origins[:1] for c in cs]).astype(F)
+    masks = host.masks(got['labels'], 1, points=points)
+    assert np.array_equal(masks, region_rule.masks(geom, starts, cell, want['labels'], 1, points=points))
+    assert np.array_equal(masks[:len(D)], np.isfinite(D).astype(np.uint8)) and masks.sum() > 3000*(CELL/cell)**2
+    rng = np.random.RandomState(13)
+    a = np.stack([c.origins[0] + rng.uniform(-3., 3., (32, 2)) for c in cs]).astype(F)
+    b = np.repeat(points, 32, 1)
+    la = host.labels_at(got['labels'], 1, a)
+    assert np.array_equal(la, region_rule.labels_at(geom, starts, cell, want['labels'], 1, a)) and (la >= 0).any(-1).mean() > .5
+    finite = np.array([[np.isfinite(nav_rule.query(D[starts[n]:starts[n + 1]].reshape(c.free.shape), c.geom, cell, c.free, p)) for p in a[n]]
+                       for n, c in enumerate(cs)])
+    assert np.array_equal(region_rule.together(la, host.labels_at(got['labels'], 1, b)), finite) and finite.any() and (~finite).any()
 
 
 def test_on_the_six_plans_the_labels_are_the_rules():

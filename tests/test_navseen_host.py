@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from tests.test_abi import ROOT, declared_symbols
-from tests.test_navfield_host import CELL, RADIUS, F, _world, nav_rule, plans, spawn_points
+from tests.test_navfield_host import CELL, CELLS, RADIUS, F, _world, nav_rule, plans, spawn_points
 
 INF, NAN = F(np.inf), F(np.nan)
 
@@ -131,9 +131,9 @@ def _host(geom, cell, countable, maps, totals, origins, dirs, distances, slot=No
     return maps, gained, totals
 
 
-def _same(geom, countable, maps, totals, origins, dirs, distances, **kw):
-    want = seen_rule.call(geom, CELL, countable, maps, totals, origins, dirs, distances, **kw)
-    got = _host(geom, CELL, countable, maps, totals, origins, dirs, distances, **kw)
+def _same(geom, countable, maps, totals, origins, dirs, distances, cell=CELL, **kw):
+    want = seen_rule.call(geom, cell, countable, maps, totals, origins, dirs, distances, **kw)
+    got = _host(geom, cell, countable, maps, totals, origins, dirs, distances, **kw)
     assert np.array_equal(got[0], want[0]), int((got[0] != want[0]).sum())
     assert got[1].tolist() == want[1].tolist() and got[2].tolist() == want[2].tolist(), (got[1:], want[1:])
     return want
@@ -147,11 +147,28 @@ class _Case:
     pass
 
 
-_CASES = []
+_CASES = {}
 
 
-def cases():
-    if not _CASES:
+def cases(cell=CELL, r=RADIUS):
+    """The cases gridded at `cell` with clearance `r`: the viewers, rays and distances are the same whatever the grid."""
+    if (cell, r) not in _CASES:
+        found = _CASES[cell, r] = []
+        for base, g in zip(_rendered(), plans(3) + plans(3, oblique=True)):
+            case = _Case()
+            case.walls, case.geom, case.free = _world(g, cell, r)
+            case.origins, case.dirs, case.distances = base
+            case.blank = np.zeros((2,) + case.free.shape, np.uint8)
+            found.append(case)
+    return _CASES[cell, r]
+
+
+_RENDERED = []
+
+
+def _rendered():
+    """[(origins, dirs, distances)] per plan: the oracle's render from two spawn-table points."""
+    if not _RENDERED:
         from megastep_amd import core, scene
         from tests import util
         from tests.test_raycast_host import camera_rays_np
@@ -165,13 +182,28 @@ def cases():
         ref = util.OracleWorld(c)
         distances = ref.render()['distances']
         dirs = camera_rays_np(ref.agents['angles'], 64, 130)
-        for e, g in enumerate(geoms):
-            case = _Case()
-            case.walls, case.geom, case.free = _world(g)
-            case.origins, case.dirs, case.distances = pos[e], dirs[e], np.asarray(distances[e], F)
-            case.blank = np.zeros((2,) + case.free.shape, np.uint8)
-            _CASES.append(case)
-    return _CASES
+        _RENDERED.extend((pos[e], dirs[e], np.asarray(distances[e], F)) for e in range(len(geoms)))
+    return _RENDERED
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_the_host_instantiation_is_the_rule_at_other_cell_widths(cell, r):
+    """The same viewers and rays over grids whose cell is no power of two: a ray's sample count len/(.5f*c) and a sample's cell
+    are rounded there."""
+    seen = 0
+    for case in cases(cell, r):
+        a = (case.geom, case.free, case.blank, [0, 0], case.origins, case.dirs, case.distances)
+        maps, gained, totals = _same(*a, cell=cell)
+        assert (gained > 0).all() and gained.tolist() == totals.tolist() == [int((m.astype(bool) & case.free).sum()) for m in maps]
+        seen += int(gained.sum())
+        short = _same(*a, cell=cell, max_range=1.)
+        assert (short[1] <= gained).all() and 0 < short[1].sum() < gained.sum()
+        _same(*a, cell=cell, max_range=1000.)
+        one = (case.geom, case.free, case.blank[:1], [0], case.origins, case.dirs, case.distances)
+        shared = _same(*one, cell=cell, slot=[0, 0])
+        assert np.array_equal(shared[0][0], maps[0] | maps[1])
+        _same(case.geom, case.free, short[0], short[2], case.origins, case.dirs, case.distances, cell=cell, reset=[1, 0])
+    assert seen > 2000*(CELL/cell)**2                                    # (the same floor, in cells)
 
 
 def test_the_host_instantiation_is_the_rule_bit_for_bit():

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from tests.test_abi import ROOT, declared_symbols
-from tests.test_navfield_host import CELL, RADIUS, F, _world, nav_rule, plans, spawn_points
+from tests.test_navfield_host import CELL, CELLS, RADIUS, F, _world, nav_rule, plans, spawn_points
 from tests.test_navdraw_host import _aligned
 
 NAN = F(np.nan)
@@ -174,14 +174,14 @@ def _max_framed(geom):
 class _Host:
     """ms_host_nav_views on one grid of host arrays; the outputs start as sentinels."""
 
-    def __init__(self, geom, starts, free, walls, cell=CELL):
+    def __init__(self, geom, starts, free, walls, cell=CELL, clearance=RADIUS):
         from megastep_amd import _lib
         self.geom, self.starts = _aligned(geom), np.ascontiguousarray(starts, np.int64)
         self.free = np.ascontiguousarray(np.concatenate([np.asarray(free, np.uint8).reshape(-1), np.zeros(1, np.uint8)]))
         self.N, self.cell = len(self.geom), cell
         self.walls = np.ascontiguousarray(np.concatenate([np.asarray(w, F).reshape(-1, 4) for w in walls] + [np.zeros((1, 4), F)]))
         self.wall_starts = np.concatenate([[0], np.cumsum([len(np.asarray(w).reshape(-1, 4)) for w in walls])]).astype(np.int64)
-        self.grid = _lib.MsNavGrid(self.N, cell, RADIUS, self.geom.ctypes.data, self.starts.ctypes.data, _max_framed(self.geom), self.free.ctypes.data)
+        self.grid = _lib.MsNavGrid(self.N, cell, clearance, self.geom.ctypes.data, self.starts.ctypes.data, _max_framed(self.geom), self.free.ctypes.data)
         self.h = _lib.lib()
 
     def views(self, points, R, countable, headings=None, cos_half=0., unseen=None, S=0, slot=None, mask=None, before=None, capacity=0,
@@ -221,16 +221,17 @@ class _Plans:
     pass
 
 
-_PLANS = []
+_PLANS = {}
 
 
-def plan_views():
+def plan_views(cell=CELL, r=RADIUS, ranges=(4., 10.)):
     """The six plans as one ragged grid with two viewpoints a plan (the issue's draw), the rule's images for R in {4, 10} with and
     without the cone, a random half-seen pair of maps an env, and the host on it."""
-    if not _PLANS:
+    if (cell, r) not in _PLANS:
         w = _Plans()
+        w.cell = cell
         gs = plans(3) + plans(3, oblique=True)
-        worlds = [_world(g) for g in gs]
+        worlds = [_world(g, cell, r) for g in gs]
         w.walls = [np.asarray(walls, F).reshape(-1, 4) for walls, _, _ in worlds]
         w.geom = np.array([geom for _, geom, _ in worlds], np.int32)
         w.images = [free for _, _, free in worlds]
@@ -243,7 +244,7 @@ def plan_views():
             for p in range(2):
                 for _ in range(50):
                     cand = (sp[rng.choice(len(sp))] + rng.uniform(-.05, .05, 2)).astype(F)
-                    if wall_distance(cand, w.walls[n]) >= RADIUS:
+                    if wall_distance(cand, w.walls[n]) >= r:
                         w.points[n, p] = cand
                         break
         assert np.isfinite(w.points).all()
@@ -252,14 +253,14 @@ def plan_views():
         w.cos_half = cos_half_of(CONE)
         w.seen = (np.random.RandomState(12).rand(2*len(w.free)) < .5).astype(np.uint8)*np.random.RandomState(13).choice(np.array([1, 3], np.uint8), 2*len(w.free))
         w.vis = {}
-        for R in (4., 10.):
+        for R in ranges:
             for cone in (False, True):
-                w.vis[R, cone] = {(n, p): view_rule.visible(w.walls[n], tuple(int(v) for v in w.geom[n]), CELL, w.points[n, p], R,
+                w.vis[R, cone] = {(n, p): view_rule.visible(w.walls[n], tuple(int(v) for v in w.geom[n]), cell, w.points[n, p], R,
                                                             w.headings[n, p] if cone else None, w.cos_half if cone else None)
                                   for n in range(6) for p in range(2)}
-        w.host = _Host(w.geom, w.starts, w.free, w.walls)
-        _PLANS.append(w)
-    return _PLANS[0]
+        w.host = _Host(w.geom, w.starts, w.free, w.walls, cell, r)
+        _PLANS[cell, r] = w
+    return _PLANS[cell, r]
 
 
 @pytest.mark.parametrize('capacity', [0, 8])
@@ -267,10 +268,26 @@ def plan_views():
 @pytest.mark.parametrize('R', [4., 10.])
 def test_the_host_instantiation_is_the_rule_on_the_six_plans(R, cone, capacity):
     """Bytes, counts and gains (P = 2 against S = 2), staged walls and - with 8 rows of room - the sweep over all of them."""
-    w = plan_views()
+    _host_is_the_rule_on_the_six_plans(plan_views(), R, cone, capacity)
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+@pytest.mark.parametrize('cone', [False, True])
+def test_the_host_instantiation_is_the_rule_at_other_cell_widths(cone, cell, r):
+    """The same walls, viewpoints and headings over grids whose cell is no power of two, at a range of 4 m, through both wall paths:
+    the window of cells a viewpoint sweeps rests on rounded quotients there, and every cell in range must still be in it. Every
+    viewpoint has visible and hidden free cells."""
+    w = plan_views(cell, r, ranges=(4.,))
+    for image, (n, p) in ((w.vis[4., cone][n, p], (n, p)) for n in range(6) for p in range(2)):
+        assert (image & w.images[n]).any() and (~image & w.images[n]).any(), (n, p)
+    for capacity in (0, 8):
+        _host_is_the_rule_on_the_six_plans(w, 4., cone, capacity)
+
+
+def _host_is_the_rule_on_the_six_plans(w, R, cone, capacity):
     kw = dict(headings=w.headings, cos_half=w.cos_half) if cone else {}
     got = w.host.views(w.points, R, w.free, unseen=w.seen, S=2, capacity=capacity, **kw)
-    want = view_rule.call(w.geom, w.starts, CELL, w.walls, w.points, R, w.free, unseen=w.seen, S=2, images=w.vis[R, cone], **kw)
+    want = view_rule.call(w.geom, w.starts, w.cell, w.walls, w.points, R, w.free, unseen=w.seen, S=2, images=w.vis[R, cone], **kw)
     same(got, want)
     assert (want['counts'] > 0).all() and (want['gains'] <= want['counts']).all() and 0 < want['gains'].sum() < want['counts'].sum()
     if capacity:                                     # (every viewpoint keeps more rows than that: the other wall path)
@@ -424,7 +441,8 @@ def _store(w, out, n, p, P=8):
 @pytest.mark.parametrize('capacity', [0, 3])
 def test_the_hand_made_worlds_with_everything_in_range(capacity):
     """R = 20: the box's far room through the door, a viewpoint on a cell centre, on a wall's line, outside the grid, a NaN one;
-    the shared vertex; no cells; no walls; with room for three rows - more kept walls than fit - the same bytes."""
+    the shared vertex; no cells; no walls; with room for three rows - more kept walls than fit - the same bytes. At a cell of
+    0.125 only: the hand-made viewpoints and the cells named below are written out for it."""
     w = hand()
     want = _hand_call(w, 20., capacity=capacity)
     g0 = tuple(int(v) for v in w.geom[0])
@@ -475,6 +493,7 @@ def test_windows_clipped_by_every_edge_and_odd_headings(R, cone):
 
 
 def test_a_range_below_half_a_cell_sees_the_cell_it_stands_on_or_nothing():
+    """At a cell of 0.125 only: the range, the viewpoints and the cells named below are written out for it."""
     w = hand()
     want = _hand_call(w, .05)
     assert _store(w, want, 0, 2).sum() == 1 and _store(w, want, 0, 2)[12, 20] and _store(w, want, 3, 0).sum() == 1

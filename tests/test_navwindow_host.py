@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from tests.test_abi import ROOT, declared_symbols
-from tests.test_navfield_host import CELL, RADIUS, F, bits
+from tests.test_navfield_host import CELL, CELLS, RADIUS, F, bits
 from tests.test_navseen_host import cases, seen_rule
 
 INF, NAN = F(np.inf), F(np.nan)
@@ -133,7 +133,7 @@ def _spec(layer, keep):
     return _lib.MsNavLayer(layer.values.ctypes.data, int(layer.is_float), layer.n_fields, None if layer.field is None else layer.field.ctypes.data)
 
 
-def _host(geom, starts, cell, free, views, size, channels, samples=1):
+def _host(geom, starts, cell, free, views, size, channels, samples=1, clearance=RADIUS):
     """ms_host_nav_windows on host arrays: (N, P, C, H, W)."""
     from megastep_amd import _lib
     geom = np.ascontiguousarray(geom, np.int32)
@@ -152,7 +152,7 @@ def _host(geom, starts, cell, free, views, size, channels, samples=1):
         if ch.gate is not None:
             spec.gate = _spec(ch.gate, keep)
         spec.where, spec.scale, spec.outside, spec.hidden = int(ch.where), float(ch.scale), float(ch.outside), float(ch.hidden)
-    grid = _lib.MsNavGrid(N, cell, RADIUS, geom.ctypes.data, starts.ctypes.data, 0, free.ctypes.data)
+    grid = _lib.MsNavGrid(N, cell, clearance, geom.ctypes.data, starts.ctypes.data, 0, free.ctypes.data)
     w = _lib.MsNavWindows(P, size[0], size[1], samples, views.ctypes.data, len(channels), specs, out.ctypes.data)
     assert _lib.lib().ms_host_nav_windows(ctypes.byref(grid), ctypes.byref(w)) == 0
     return out
@@ -166,20 +166,21 @@ class _World:
     pass
 
 
-_WORLD = []
+_WORLD = {}
 
 
-def world():
-    if not _WORLD:
+def world(cell=CELL, r=RADIUS):
+    if (cell, r) not in _WORLD:
         from megastep_amd import _lib
         h = _lib.lib()
         w = _World()
-        cs = cases()
+        w.cell, w.clearance = cell, r
+        cs = cases(cell, r)
         w.geom = np.array([c.geom for c in cs] + [(3, 4, 0, 7)], np.int32)
         sizes = [c.free.size for c in cs] + [0]
         w.starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         w.free = np.concatenate([c.free.reshape(-1).astype(np.uint8) for c in cs] + [np.zeros(1, np.uint8)])
-        w.seen_images = [seen_rule.call(c.geom, CELL, c.free, c.blank, [0, 0], c.origins, c.dirs, c.distances)[0] for c in cs]
+        w.seen_images = [seen_rule.call(c.geom, cell, c.free, c.blank, [0, 0], c.origins, c.dirs, c.distances)[0] for c in cs]
         w.seen = np.concatenate([m.reshape(-1) for m in w.seen_images] + [np.zeros(2, np.uint8)])
         w.blank = np.zeros_like(w.seen)
         fields = []
@@ -188,15 +189,15 @@ def world():
             for s in range(2):
                 D = np.empty(c.free.shape, F)
                 marks = np.ascontiguousarray(maps[s])
-                assert h.ms_host_nav_seed_field(geom.ctypes.data, CELL, free.ctypes.data, marks.ctypes.data, 0, None, 1, D.ctypes.data, None) > 0
+                assert h.ms_host_nav_seed_field(geom.ctypes.data, cell, free.ctypes.data, marks.ctypes.data, 0, None, 1, D.ctypes.data, None) > 0
                 fields.append(D.reshape(-1))
         w.fields = np.concatenate(fields + [np.zeros(2, F)])
         assert np.isinf(w.fields).any() and (w.fields == 0).any() and (np.isfinite(w.fields) & (w.fields > 1)).any()
         w.odd = w.fields.copy()
         w.odd[5::97] = NAN
         w.centres = np.stack([c.origins for c in cs] + [np.zeros((2, 2), F)]).astype(np.float64)       # (7, 2, 2)
-        _WORLD.append(w)
-    return _WORLD[0]
+        _WORLD[cell, r] = w
+    return _WORLD[cell, r]
 
 
 def views_round(centres, size, angle, pixel):
@@ -213,8 +214,8 @@ def views_round(centres, size, angle, pixel):
 
 
 def _same(w, views, size, channels, samples=1):
-    want = window_rule.call(w.geom, w.starts, CELL, views, size, channels, samples)
-    got = _host(w.geom, w.starts, CELL, w.free, views, size, channels, samples)
+    want = window_rule.call(w.geom, w.starts, w.cell, views, size, channels, samples)
+    got = _host(w.geom, w.starts, w.cell, w.free, views, size, channels, samples, w.clearance)
     assert np.array_equal(bits(got), bits(want)), (int((bits(got) != bits(want)).sum()), size, samples)
     return want
 
@@ -256,6 +257,25 @@ def test_the_host_instantiation_is_the_rule_bit_for_bit():
     views[4, 1] = [3e38, 3e38, 3e38, 1e30, 0, 1e30]
     got = _same(w, views, (16, 16), chans, 2)
     assert (got[1, 0, 7] == F(.5)).all() and (got[3, 0, 5] == F(.5)).all() and (got[4, 1, 0] == 0).all() and (got[1, 1, 0] > 0).any()
+
+
+@pytest.mark.parametrize('cell,r', CELLS)
+def test_the_host_instantiation_is_the_rule_at_other_cell_widths(cell, r):
+    """The same views - pixels of half a cell, a cell and three cells, four angles, one to three samples - over grids whose cell
+    is no power of two: the cell under a sample, floorf(x/c), is a rounded quotient there."""
+    w = world(cell, r)
+    chans = _channels(w)
+    some, k = 0, 0
+    for angle in (0., 37., 90., 180.5):
+        for pixel in (.5*cell, cell, 3*cell):
+            samples = 1 + k % 3
+            k += 1
+            sel = slice(k % 2, 8, 2) if samples == 3 else slice(0, 6)
+            got = _same(w, views_round(w.centres, (16, 16), angle, pixel), (16, 16), chans[sel], samples)
+            some += int(((got[:6] > 0) & (got[:6] < 1)).sum())
+    assert some > 1000
+    got = _same(w, views_round(w.centres, (13, 21), 37., cell), (13, 21), chans, 3)
+    assert (got[:6, :, 0] > 0).any() and (got[:6, :, 2] > 0).any()
 
 
 def test_fields_name_the_store_and_a_bad_index_blanks_the_image():
