@@ -327,7 +327,10 @@ int ms_deathmatch_shoot(int n_envs, int n_agents, const MsDeathmatch* dm, void* 
 /* What the reference's Explorer env does between one frame and the next - `_reward`'s arithmetic, `_reset`'s counters and the
  * episode rule of `step`, megastep/demo/envs/explorer.py:45-90 - as one launch of N threads behind ms_render, whose first-sight
  * tally (MsRender.seen_count; the stamps and epochs are MsRender.seen_stamp / seen_epoch) it reads.  Per env n, in this order:
- *   reward   reset_out = over (this step began with a respawn); reward = over ? 0 : (tally - before) / pixels;
+ *   reward   reset_out = over (this step began with a respawn); reward = over ? 0 : (tally - before) * (1.f/pixels) - in
+ *            binary32, the reciprocal rounded first: what ATen makes of an int tensor over a Python int on the device (as of
+ *            every tensor over a scalar: see ms_step_physics' IMU), so the env's tensor-op path gives the same bits at any
+ *            pixel count, not only at powers of two;
  *            potential = tally, length_out = lengths - as this step leaves them (for display; optional)
  *   next     lengths += 1;  over = lengths >= tally + slack - the NEXT step's respawn mask (MsStepExtras.respawn_mask,
  *            respawn_after = 1) - and where it is set: epoch += 1 (the env forgets every texel at once), tally = lengths = 0;

@@ -67,7 +67,10 @@ __global__ __launch_bounds__(WG) void explorer_kernel(const MsExplorer ex, const
     int tally = ex.tally[n], length = ex.lengths[n];
     const int gained = tally - ex.before[n];
     if (ex.reset_out) ex.reset_out[n] = fresh ? 1 : 0;
-    ex.reward[n] = fresh ? 0.f : (float)gained/(float)ex.pixels;     // explorer.py:52-56 (an int tensor over an int: true division in binary32)
+    // explorer.py:52-56: an int tensor over an int - on the device ATen multiplies by the rounded reciprocal, `a * (1.f/b)`, which
+    // is not the correctly rounded quotient unless b is a power of two (5/48, 5/100 differ by an ulp): torch's form, so that the
+    // env's tensor-op path and this kernel agree bit for bit at every pixel count (as the pooled depth and the IMU do)
+    ex.reward[n] = fresh ? 0.f : (float)gained*(1.f/(float)ex.pixels);
     if (ex.potential) ex.potential[n] = (float)tally;    // (as this step leaves them, for Explorer.state())
     if (ex.length_out) ex.length_out[n] = length;
     // ---- the next step's top (explorer.py:86-89)

@@ -18,7 +18,8 @@ def _bits(t):
 
 def test_depth_only_at_c2_full_size_is_the_oracles_distances_bit_for_bit():
     """4096 envs x 1 agent x 64 rays: `fields=('distances',)` and depth-only pooling, three steps; sampled envs against the
-    oracle's raycast - every distance the same binary32, misses +inf - and the pooled depth against modules.Depth on them."""
+    oracle's raycast - every distance the same binary32, misses +inf - and the pooled depth against the pooled rule (DESIGN 3.7,
+    util.pooled_rule) on them, bit for bit."""
     from megastep_amd import cuda, modules
     c, _, _ = _big_world(4096, 1, 64, 130, n_distinct=512, fast=True)
     envs = [0, 1, 511, 512, 1023, 2500, 4000, 4095]
@@ -37,9 +38,8 @@ def test_depth_only_at_c2_full_size_is_the_oracles_distances_bit_for_bit():
         np.testing.assert_array_equal(_bits(out.distances[e]), want['distances'].view(np.int32))
         pooled = modules.render(c, observers=(depth,), fields=())
         assert set(pooled.keys()) >= {'pooled_depth'} and 'pooled_rgb' not in pooled and 'screen' not in pooled
-        d = torch.as_tensor(want['distances'])
-        d_ref = (1 - ((d - c.agent_radius)/10.).clamp(0, 1)).view(len(envs), 1, 16, 4).mean(-1)
-        np.testing.assert_allclose(depth(pooled)[e, :, 0, 0].cpu().numpy(), d_ref.numpy(), rtol=0, atol=1e-6)
+        d_ref = util.pooled_rule(np.zeros(want['distances'].shape + (3,), np.float32), want['distances'], c.agent_radius, 10., 4)[1]
+        util.assert_bits(depth(pooled)[e, :, 0, 0], d_ref, 'pooled depth')
     assert np.isfinite(want['distances']).mean() > .9
 
 
@@ -59,7 +59,7 @@ def test_every_colourless_request_leaves_the_full_renderers_bits(monkeypatch, n_
     lines_after = c.scenery.lines.vals.clone()
     ref = util.OracleWorld(c)
     ref.pull_baked(c); ref.pull_agents(c)
-    util.assert_render_matches(c, full, ref.render())
+    util.assert_render_bits(c, full, ref.render())
     af = c.scenery.n_agents*c.scenery.model.shape[0]
     rows = (c.scenery.lines.starts.long()[:, None] + torch.arange(af, device='cuda')[None]).flatten()   # the agents' lines
     for fields in [('distances',), ('indices',), ('indices', 'distances'), ('locations',), ('dots', 'distances'),
@@ -77,7 +77,7 @@ def test_every_colourless_request_leaves_the_full_renderers_bits(monkeypatch, n_
         lean = cuda.render(c.scenery, c.agents, fields=('distances',), pooled=dict(subsample=4, max_depth=7., rgb=False, centre=True))
         assert lean.obs_rgb is None and lean.obs_depth.shape == (6, n_agents, res//4)
         want = (1 - ((full.distances - c.agent_radius)/7.).clamp(0, 1)).view(6, n_agents, res//4, 4).mean(-1)
-        torch.testing.assert_close(lean.obs_depth, want, rtol=0, atol=1e-6)
+        util.assert_bits(lean.obs_depth, want, 'pooled depth')            # (torch's own bits on the device: DESIGN 3.7)
         idx = full.indices.view(6, n_agents, res//4, 4)[..., 2]              # the middle ray of a pixel (deathmatch.py:74-80)
         mid = idx[..., [res//8 - 1, res//8]]
         af = n_agents*c.scenery.model.shape[0]

@@ -3,6 +3,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import util
+
 pytestmark = pytest.mark.gpu
 
 
@@ -85,9 +87,9 @@ def test_deathmatch_logic_kernel_equals_the_references_observe_and_shoot(tag):
     reset, reward, health_obs, matchings = cuda.deathmatch_shoot(centre, positions, upper, health, damage, dead, matchings=True)
     np.testing.assert_array_equal(matchings.cpu().numpy(), g[f'dm_{tag}_matchings'])
     np.testing.assert_array_equal(reward.reshape(-1).cpu().numpy(), g[f'dm_{tag}_hits'])
-    np.testing.assert_allclose(health.cpu().numpy(), g[f'dm_{tag}_health'], rtol=0, atol=1e-6)
-    np.testing.assert_allclose(damage.cpu().numpy(), g[f'dm_{tag}_damage'], rtol=0, atol=1e-6)
-    np.testing.assert_allclose(health_obs.unsqueeze(-1).cpu().numpy(), g[f'dm_{tag}_obs_health'], rtol=0, atol=1e-6)
+    np.testing.assert_array_equal(health.cpu().numpy(), g[f'dm_{tag}_health'])
+    np.testing.assert_array_equal(damage.cpu().numpy(), g[f'dm_{tag}_damage'])
+    np.testing.assert_array_equal(health_obs.unsqueeze(-1).cpu().numpy(), g[f'dm_{tag}_obs_health'])
     # bit for bit the reference's statements in binary32 (deathmatch.py:64,70)
     m = torch.as_tensor(g[f'dm_{tag}_matchings']).cuda()
     pos = positions
@@ -109,7 +111,7 @@ def test_deathmatch_logic_kernel_equals_the_references_observe_and_shoot(tag):
 
 def test_deathmatch_steps_the_same_with_and_without_the_logic_kernel():
     """Two Deathmatch envs from the same seeds, one settling each frame with the tensor ops, one with the single launch: the same
-    observations, rewards, resets and agent state step after step - through deaths (health pushed down by hand so that agents
+    observations, rewards, resets and agent state, bit for bit, step after step - through deaths (health pushed down by hand so that agents
     die and respawn inside the physics launch) - and the same matchings when asked."""
     from megastep_amd.demo import Deathmatch
     from megastep_amd import arrdict, cubicasa
@@ -137,10 +139,10 @@ def test_deathmatch_steps_the_same_with_and_without_the_logic_kernel():
     for t, (fa, fb) in enumerate(zip(a, b)):
         assert torch.equal(fa.reset, fb.reset) and torch.equal(fa.reward, fb.reward), t
         for k in ('rgb', 'd', 'imu', 'health'):
-            torch.testing.assert_close(fa.obs[k], fb.obs[k], rtol=0, atol=1e-6, msg=f'{k} at step {t}')
+            util.assert_bits(fa.obs[k], fb.obs[k], f'{k} at step {t}')
         if t:
             assert torch.equal(fa.matchings, fb.matchings)
-            torch.testing.assert_close(fa.state, fb.state, rtol=0, atol=1e-6)
+            util.assert_bits(fa.state, fb.state, f'state at step {t}')
             resets += int(fa.reset.sum())
     assert a[0].reset.all() and resets >= 3
 
@@ -239,7 +241,7 @@ def test_explorer_reward_equals_the_reference_formula():
 @pytest.mark.parametrize('depth_only', [False, True])
 def test_explorer_steps_the_same_with_and_without_the_books_kernel(depth_only):
     """Two Explorers from the same seeds, one keeping its books between frames with the tensor ops, one with the single launch
-    (ms_explorer_books): the same observations, rewards, resets, potentials and seen-masks step after step, through respawns -
+    (ms_explorer_books): the same observations, rewards, resets, potentials and seen-masks, bit for bit, step after step, through respawns -
     two forced (an episode length pushed past its limit: the tensor ops apply the rule at the top of the step, the kernel at
     the end of the step before, so the push comes a step earlier there) and the reference's formula for the rest."""
     from megastep_amd.demo import Explorer
@@ -266,20 +268,42 @@ def test_explorer_steps_the_same_with_and_without_the_books_kernel(depth_only):
     a, b = rollout(False), rollout(True)
     for t, (fa, fb) in enumerate(zip(a, b)):
         assert torch.equal(fa.reset, fb.reset), t
-        torch.testing.assert_close(fa.reward, fb.reward, rtol=0, atol=0, msg=f'reward at step {t}')
+        util.assert_bits(fa.reward, fb.reward, f'reward at step {t}')
         for k in fa.obs:
-            torch.testing.assert_close(fa.obs[k], fb.obs[k], rtol=0, atol=1e-6, msg=f'{k} at step {t}')
+            util.assert_bits(fa.obs[k], fb.obs[k], f'{k} at step {t}')
         if t:
             assert torch.equal(fa.potential, fb.potential) and torch.equal(fa.seen, fb.seen) and torch.equal(fa.pose, fb.pose), t
     assert a[0].reset.all() and sum(int(f.reset.sum()) for f in a[1:]) == 2 and a[8].reset[2] and a[16].reset[5]
     assert (torch.stack([f.reward for f in a[1:]]) > 0).any()
 
 
+@pytest.mark.parametrize('pixels', [48, 100, 64])
+def test_explorer_reward_at_other_pixel_counts(pixels):
+    """explorer_kernel's reward against the env's own statement of it (explorer.py `_world`: `gained/pixels`, an int tensor over a
+    Python int, evaluated by torch on the device) - at pixel counts that are no power of two, where the correctly rounded quotient
+    and a product with the rounded reciprocal part: in binary32 g/48 and g*(1/48) differ at g = 5, 7, 10, 14, ..., g/100 and
+    g*(1/100) at 5, 9, 10, 15, ..., g/64 and g*(1/64) nowhere. 64 envs gaining 0..63 texels; the flagged ones get nothing."""
+    from megastep_amd import cuda
+    g = torch.arange(64, dtype=torch.int32, device='cuda')
+    before = torch.randint(0, 1000, (64,), dtype=torch.int32, device='cuda', generator=torch.Generator('cuda').manual_seed(pixels))
+    tally = before + g
+    over = (g % 5 == 3)
+    lengths, epoch = torch.zeros_like(g), torch.ones_like(g)
+    want = ((tally - before)/pixels).masked_fill_(over, 0.)
+    assert want.dtype == torch.float32
+    quotient, product = np.arange(64, dtype=np.float32)/np.float32(pixels), np.arange(64, dtype=np.float32)*(np.float32(1)/np.float32(pixels))
+    assert (quotient != product)[~over.cpu().numpy()].any() == (pixels != 64), 'these inputs tell the two forms apart'
+    reset, reward = cuda.explorer_books(tally.clone(), before.clone(), lengths, epoch, over.clone(), 10_000, pixels)
+    assert torch.equal(reset, over) and (reward[over] == 0).all()
+    util.assert_bits(reward, want, 'reward')
+
+
 @pytest.mark.parametrize('cls,kwargs', [('MomentumMovement', dict(accel=5, ang_accel=180, decay=.125)),
                                         ('SimpleMovement', dict(speed=10, ang_speed=180))])
 def test_movement_inside_the_physics_launch_equals_the_tensor_ops(cls, kwargs):
     """the movement modules' velocity update, done by the physics kernel's prologue, against the same
-    update done with the reference's tensor ops (modules.py:57-66,106-118) followed by a plain physics call."""
+    update done with the reference's tensor ops (modules.py:57-66,106-118) followed by a plain physics call: the same bits (the
+    kernel's blend and its turn into the global frame are torch's own operations on the device, sin and cos included)."""
     from megastep_amd import core, cubicasa, cuda, modules, scene
     np.random.seed(2); torch.manual_seed(2)
     gs = cubicasa.sample(16, n_unique=16)
@@ -309,9 +333,9 @@ def test_movement_inside_the_physics_launch_equals_the_tensor_ops(cls, kwargs):
             a, b = getattr(c.agents, name), getattr(ref, name)
             both = torch.isfinite(a) & torch.isfinite(b)
             assert torch.equal(torch.isfinite(a), torch.isfinite(b)), name
-            torch.testing.assert_close(a[both], b[both], rtol=0, atol=2e-6, msg=name)
+            util.assert_bits(a[both], b[both], name)
         both = torch.isfinite(p.progress) & torch.isfinite(p_ref.progress)
-        torch.testing.assert_close(p.progress[both], p_ref.progress[both], rtol=0, atol=2e-6)
+        util.assert_bits(p.progress[both], p_ref.progress[both], 'progress')
         assert (p.progress < 1).any() or step < 2
         if keep != 0:
             c.agents.velocity[0, 0] = 0.
@@ -320,7 +344,8 @@ def test_movement_inside_the_physics_launch_equals_the_tensor_ops(cls, kwargs):
 @pytest.mark.parametrize('after,n_agents', [(False, 3), (True, 3), (False, 1), (True, 70), (False, 66)])
 def test_respawn_and_imu_inside_the_physics_launch_equal_the_tensor_ops(after, n_agents):
     """respawn (before the step - Deathmatch's order - or after it - Explorer's) and the IMU reading, done
-    by the physics launch, against the modules' tensor ops (modules.py:263-270,312-326) around a plain movement call.
+    by the physics launch, against the modules' tensor ops (modules.py:263-270,312-326) around a plain movement call: both
+    sides run the same physics kernel and the IMU's two quotients are the device's own, so bit for bit.
     More than 64 agents per env: the ones past a wavefront's lanes go through memory."""
     from megastep_amd import arrdict, core, cubicasa, cuda, modules, scene
     np.random.seed(3); torch.manual_seed(3)
@@ -349,9 +374,9 @@ def test_respawn_and_imu_inside_the_physics_launch_equal_the_tensor_ops(after, n
         reading = imu()
         assert imu._pending is None and reading.shape == (24, A, 3)
         for name in ('angles', 'positions', 'angvelocity', 'velocity'):
-            torch.testing.assert_close(getattr(c.agents, name), getattr(ref, name), rtol=0, atol=2e-6, msg=name)
-        torch.testing.assert_close(p.progress, p_ref.progress, rtol=0, atol=2e-6)
-        torch.testing.assert_close(reading, imu_ref, rtol=0, atol=2e-6)
+            util.assert_bits(getattr(c.agents, name), getattr(ref, name), name)
+        util.assert_bits(p.progress, p_ref.progress, 'progress')
+        util.assert_bits(reading, imu_ref, 'imu')
         if reset.any():
             assert (c.agents.velocity[reset] == 0).all() or not after
         # the renderer must see the respawned pose (the heading cache follows the new angle)
@@ -432,7 +457,6 @@ def test_first_sight_bookkeeping_in_the_render_kernel():
             which = torch.zeros(16, dtype=torch.bool, device='cuda'); which[[2, 9]] = True
             memory.forget(which)
             seen[which[memory.texel_env]] = False
-        from tests import util
         util.random_velocities(c, rng)
         cuda.physics(c.scenery, c.agents)
         frame = modules.render(c, fields=('indices', 'locations'), seen=memory.books)

@@ -1,6 +1,6 @@
 """GPU parity: the HIP path (through the C-ABI) against the CPU oracle on identical seeded inputs.
 
-Bar (BASELINE.json north_star): bit-exact collision masks and hit indices; <= 1e-5 on float positions / pixels."""
+Bar: the oracle's results, bit for bit - collision masks, hit indices and every float (tests/util.py: assert_bits)."""
 
 import numpy as np
 import pytest
@@ -29,10 +29,9 @@ def test_step_matches_oracle(n_envs, n_agents, res, fov, toy):
     from megastep_amd import cuda
     c, geometries = _world(n_envs, n_agents, res, fov, toy=toy)
     ref = util.OracleWorld(c)
-    np.testing.assert_allclose(c.scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
+    util.assert_bits(c.scenery.baked.vals, ref.bake(), 'baked')
     ref.pull_baked(c)
     rng = np.random.RandomState(7)
-    exact = []
     for step in range(4):
         util.random_velocities(c, rng, speed=4. if step % 2 else 40.)
         ref.pull_agents(c)
@@ -40,13 +39,9 @@ def test_step_matches_oracle(n_envs, n_agents, res, fov, toy):
         r = cuda.render(c.scenery, c.agents)
         prog_ref, agents_ref = ref.physics()
         render_ref = ref.render()
-        util.assert_physics_matches(c, p, prog_ref, agents_ref)
-        util.assert_render_matches(c, r, render_ref)
-        np.testing.assert_allclose(c.scenery.lines.vals.cpu().numpy(), ref.scene.lines_vals, rtol=0, atol=1e-6)
-        exact.append([util.exact_fraction(p.progress.cpu().numpy(), prog_ref),
-                      util.exact_fraction(r.distances.cpu().numpy(), render_ref['distances']),
-                      util.exact_fraction(r.screen.cpu().numpy(), render_ref['screen'])])
-    print('bitwise-equal fractions (progress, distances, screen):', np.mean(exact, 0))
+        util.assert_physics_bits(c, p, prog_ref, agents_ref)
+        util.assert_render_bits(c, r, render_ref)
+        util.assert_bits(c.scenery.lines.vals, ref.scene.lines_vals, 'lines')
 
 
 def test_agents_see_each_other():
@@ -62,7 +57,7 @@ def test_agents_see_each_other():
     idx = r.indices.cpu().numpy()
     assert ((idx >= 0) & (idx < 16)).any(), 'expected rays to land on the other agent'
     assert (r.screen.cpu().numpy()[(idx >= 0) & (idx < 16)] > 0).any()
-    util.assert_render_matches(c, r, want)
+    util.assert_render_bits(c, r, want)
 
 
 def test_known_answer_from_the_docs():
@@ -116,7 +111,7 @@ def test_hysteresis_band_adversarial():
     ref = util.OracleWorld(c)
     ref.bake(); ref.pull_baked(c); ref.pull_agents(c)
     r = cuda.render(c.scenery, c.agents, telemetry=True)
-    util.assert_render_matches(c, r, ref.render())
+    util.assert_render_bits(c, r, ref.render())
     # the scenes are there to drive the sequential-fold fallbacks: make sure they did (render_prep_kernel's telemetry)
     _, folded_rays, lane_parallel_waves = r._telemetry[:3].tolist()
     assert folded_rays > 100 and lane_parallel_waves > 5, (folded_rays, lane_parallel_waves)
@@ -129,7 +124,7 @@ def test_agent_wedged_between_coincident_walls():
     ref = util.OracleWorld(c)
     ref.bake(); ref.pull_baked(c); ref.pull_agents(c)
     r = cuda.render(c.scenery, c.agents)
-    util.assert_render_matches(c, r, ref.render())
+    util.assert_render_bits(c, r, ref.render())
 
 
 def test_full_benchmark_size_matches_oracle():
@@ -150,8 +145,8 @@ def test_full_benchmark_size_matches_oracle():
         p = cuda.physics(c.scenery, c.agents)
         r = cuda.render(c.scenery, c.agents)
         prog_ref, agents_ref = ref.physics()
-        util.assert_physics_matches(c, p, prog_ref, agents_ref)
-        util.assert_render_matches(c, r, ref.render())
+        util.assert_physics_bits(c, p, prog_ref, agents_ref)
+        util.assert_render_bits(c, r, ref.render())
 
 
 def test_full_benchmark_size_on_oblique_floorplans_matches_oracle():
@@ -168,7 +163,7 @@ def test_full_benchmark_size_on_oblique_floorplans_matches_oracle():
     d = walls[:, 1] - walls[:, 0]
     assert (np.abs(d).min(1) > 1e-3).mean() > .9, 'hardly a wall of an oblique plan is aligned with an axis'
     ref = util.OracleWorld(c)
-    np.testing.assert_allclose(c.scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
+    util.assert_bits(c.scenery.baked.vals, ref.bake(), 'baked')
     ref.pull_baked(c)
     rng = np.random.RandomState(6)
     for step in range(2):
@@ -177,8 +172,8 @@ def test_full_benchmark_size_on_oblique_floorplans_matches_oracle():
         p = cuda.physics(c.scenery, c.agents)
         r = cuda.render(c.scenery, c.agents)
         prog_ref, agents_ref = ref.physics()
-        util.assert_physics_matches(c, p, prog_ref, agents_ref)
-        util.assert_render_matches(c, r, ref.render())
+        util.assert_physics_bits(c, p, prog_ref, agents_ref)
+        util.assert_render_bits(c, r, ref.render())
 
 
 @pytest.mark.parametrize('n_envs,n_agents,res,fov,large', [(8, 4, 64, 130, False), (6, 1, 256, 130, True), (5, 4, 512, 70, False), (4, 2, 100, 160, False)])
@@ -188,7 +183,7 @@ def test_step_on_oblique_floorplans_matches_oracle(n_envs, n_agents, res, fov, l
     from megastep_amd import cuda
     c, geometries = util.oblique_world(n_envs, n_agents, res, fov, large)
     ref = util.OracleWorld(c)
-    np.testing.assert_allclose(c.scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
+    util.assert_bits(c.scenery.baked.vals, ref.bake(), 'baked')
     ref.pull_baked(c)
     rng = np.random.RandomState(8)
     for step in range(4):
@@ -197,9 +192,9 @@ def test_step_on_oblique_floorplans_matches_oracle(n_envs, n_agents, res, fov, l
         p = cuda.physics(c.scenery, c.agents)
         r = cuda.render(c.scenery, c.agents)
         prog_ref, agents_ref = ref.physics()
-        util.assert_physics_matches(c, p, prog_ref, agents_ref)
-        util.assert_render_matches(c, r, ref.render())
-        np.testing.assert_allclose(c.scenery.lines.vals.cpu().numpy(), ref.scene.lines_vals, rtol=0, atol=1e-6)
+        util.assert_physics_bits(c, p, prog_ref, agents_ref)
+        util.assert_render_bits(c, r, ref.render())
+        util.assert_bits(c.scenery.lines.vals, ref.scene.lines_vals, 'lines')
 
 
 _obstructed = util.obstructed
@@ -298,7 +293,7 @@ def test_crowded_rooms_exercise_dynamic_lighting(monkeypatch, res, fov, cell, bu
     if cell > .25:
         counts = (c.scenery._lg.lists.view(-1, 2)[:, 1].cpu().numpy().astype(np.int64)) & 0x7fffffff
         assert counts.max() > 64, 'expected candidate lists longer than one batch'
-    util.assert_render_matches(c, r, ref.render())
+    util.assert_render_bits(c, r, ref.render())
 
 
 @pytest.mark.parametrize('n_envs,n_agents,res,fov', [(3, 1, 256, 130), (2, 2, 64, 170), (2, 1, 1, 90)])
@@ -307,7 +302,7 @@ def test_large_maps_and_extreme_views(n_envs, n_agents, res, fov):
     from megastep_amd import cuda
     c, _ = _world(n_envs, n_agents, res, fov, seed=9, large=True)
     ref = util.OracleWorld(c)
-    np.testing.assert_allclose(c.scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
+    util.assert_bits(c.scenery.baked.vals, ref.bake(), 'baked')
     ref.pull_baked(c)
     rng = np.random.RandomState(3)
     for _ in range(2):
@@ -315,8 +310,8 @@ def test_large_maps_and_extreme_views(n_envs, n_agents, res, fov):
         ref.pull_agents(c)
         p = cuda.physics(c.scenery, c.agents)
         r = cuda.render(c.scenery, c.agents)
-        util.assert_physics_matches(c, p, *ref.physics())
-        util.assert_render_matches(c, r, ref.render())
+        util.assert_physics_bits(c, p, *ref.physics())
+        util.assert_render_bits(c, r, ref.render())
 
 
 def test_ragged_edge_cases():
@@ -327,15 +322,15 @@ def test_ragged_edge_cases():
     c = util.ragged_edge_world(rng)
     scenery = c.scenery
     ref = util.OracleWorld(c)
-    np.testing.assert_allclose(scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
+    util.assert_bits(scenery.baked.vals, ref.bake(), 'baked')
     ref.pull_baked(c)
     for _ in range(2):
         util.random_velocities(c, rng, speed=5.)
         ref.pull_agents(c)
         p = cuda.physics(c.scenery, c.agents)
         r = cuda.render(c.scenery, c.agents)
-        util.assert_physics_matches(c, p, *ref.physics())
-        util.assert_render_matches(c, r, ref.render())
+        util.assert_physics_bits(c, p, *ref.physics())
+        util.assert_render_bits(c, r, ref.render())
     assert (r.screen[0][r.indices[0] >= 16] > 0).any()        # ambient light only, but not black
 
 
@@ -365,7 +360,7 @@ def test_unbaked_scenery_and_shards_render_exactly():
         c.agents.positions[:, 1] = c.agents.positions[:, 0] + torch.tensor([.4, .1], device=c.device)     # someone to look at
         ref = util.OracleWorld(c)
         ref.pull_agents(c)
-        util.assert_render_matches(c, cuda.render(c.scenery, c.agents), ref.render())
+        util.assert_render_bits(c, cuda.render(c.scenery, c.agents), ref.render())
     full = scene.scenery(gs, 3, device='cuda', random=np.random.RandomState(0))
     shard = sharding.shard_scenery(full, 1, 2)
     assert torch.equal(shard._lg.vals[:-1], full._lg.vals[int(full._lg.starts[3]):-1]) and shard._lg.vals.any()     # (both end in a padding row)
@@ -374,7 +369,7 @@ def test_unbaked_scenery_and_shards_render_exactly():
     c.agents.positions[:, 2] = c.agents.positions[:, 0] + torch.tensor([.1, .45], device=c.device)
     ref = util.OracleWorld(c)
     ref.pull_agents(c)
-    util.assert_render_matches(c, cuda.render(c.scenery, c.agents), ref.render())
+    util.assert_render_bits(c, cuda.render(c.scenery, c.agents), ref.render())
 
 
 def test_more_than_64_lights_and_agents(monkeypatch):
@@ -393,19 +388,18 @@ def test_more_than_64_lights_and_agents(monkeypatch):
         if grid:                                                    # cells for the envs the grid can hold, none for the others
             assert (sc._lg.geom[:, 2] > 0).tolist() == [False, True, False, True]
         ref = util.OracleWorld(c)
-        np.testing.assert_allclose(sc.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
+        util.assert_bits(sc.baked.vals, ref.bake(), 'baked')
         ref.pull_baked(c); ref.pull_agents(c)
         r = cuda.render(c.scenery, c.agents)
         lit = (r.indices >= 0) & (r.indices < 24)
         assert all(lit[e].any() for e in range(4)), 'rays should land on agents in every env'
         want = ref.render()
-        util.assert_render_matches(c, r, want)
+        util.assert_render_bits(c, r, want)
         if grid:                                                    # ... and the fused observations stay available
             rgb, depth = modules.RGB(c, subsample=4), modules.Depth(c, subsample=4)
             frame = modules.render(c, observers=(rgb, depth), fields=(), centre=True)
             assert 'pooled_rgb' in frame and 'screen' not in frame
-            full = torch.as_tensor(want['screen'], device=c.device).permute(0, 1, 3, 2).unsqueeze(3)
-            torch.testing.assert_close(rgb(frame), modules.downsample(full, 4).mean(-1), rtol=0, atol=1e-5)
+            util.assert_bits(rgb(frame)[:, :, :, 0], util.pooled_rule(want['screen'], want['distances'], c.agent_radius, 10., 4)[0], 'pooled rgb')
     monkeypatch.setattr(cuda.Scenery, 'LIGHT_GRID', True)
 
     c = util.crowd_world(rng)
@@ -415,15 +409,15 @@ def test_more_than_64_lights_and_agents(monkeypatch):
     ref.pull_agents(c)
     p = cuda.physics(c.scenery, c.agents)
     r = cuda.render(c.scenery, c.agents)
-    util.assert_physics_matches(c, p, *ref.physics())
-    util.assert_render_matches(c, r, ref.render())
+    util.assert_physics_bits(c, p, *ref.physics())
+    util.assert_render_bits(c, r, ref.render())
 
 
 @pytest.mark.parametrize('n_agents,res,subsample', [(3, 256, 4), (4, 64, 1), (2, 128, 8), (1, 96, 2), (2, 512, 4)])
 def test_fused_observations_match_the_host_modules(n_agents, res, subsample):
     """The pooled RGB-D the render kernel writes itself against the reference's chain of tensor ops
-    (modules.py:138-145,170-184,211-224) on the full-resolution outputs of the same scene - and against the oracle's
-    render run through the same modules on the CPU."""
+    (modules.py:138-145,170-184,211-224) on the device, on the full-resolution outputs of the same scene: torch's own bits
+    there. What those numbers are is stated, and held to the oracle's planes, by the next test."""
     from megastep_amd import cuda, modules
     c, _ = _world(6, n_agents, res, 130, seed=11)
     rgb, depth = modules.RGB(c, subsample=subsample), modules.Depth(c, subsample=subsample, max_depth=7.)
@@ -435,21 +429,33 @@ def test_fused_observations_match_the_host_modules(n_agents, res, subsample):
     assert got_rgb.shape == want_rgb.shape == (6, n_agents, 3, 1, res//subsample)
     assert got_d.shape == want_d.shape == (6, n_agents, 1, 1, res//subsample)
     assert torch.equal(fused.indices, full.indices)
-    torch.testing.assert_close(got_rgb, want_rgb, rtol=0, atol=1e-6)
-    torch.testing.assert_close(got_d, want_d, rtol=0, atol=1e-6)
-    # the oracle's render through the same modules, on the CPU
+    util.assert_bits(got_rgb, want_rgb, 'pooled rgb')
+    util.assert_bits(got_d, want_d, 'pooled depth')
+    assert float(got_rgb.max()) > 0 and 0 < float(got_d.mean()) < 1
+
+
+@pytest.mark.parametrize('n_agents,res,subsample', [(3, 256, 4), (4, 64, 1), (2, 128, 8), (1, 96, 2), (2, 512, 4)])
+def test_fused_observations_are_the_pooled_rule_on_the_oracles_planes(n_agents, res, subsample):
+    """DESIGN 3.7's rule - util.pooled_rule: per ray 1 - clamp((d - agent_radius)*(1.f/max_depth), 0, 1), pairwise sums over adjacent
+    rays, times an exact power of two - applied to the ORACLE's `screen` and `distances`: the pooled RGB-D of the render kernel, bit
+    for bit. (That the rule is the observation modules' mean: tests/test_bits.py, on the CPU.) (1, 96, 2): a ragged second ray group."""
+    from megastep_amd import modules
+    c, _ = _world(6, n_agents, res, 130, seed=11)
+    # (the plans are closed rooms: the last env's first agent is put outside its plan, looking past it, so that part of its fan misses)
+    c.agents.positions[-1, 0] = torch.tensor([-2., 3.], device=c.device)
+    c.agents.angles[-1, 0] = 100.
+    rgb, depth = modules.RGB(c, subsample=subsample), modules.Depth(c, subsample=subsample, max_depth=7.)
+    fused = modules.render(c, observers=(rgb, depth), fields=())
     ref = util.OracleWorld(c)
     ref.pull_baked(c); ref.pull_agents(c)
     o = ref.render()
-    class CpuCore: agent_radius, res = c.agent_radius, c.res
-    from megastep_amd import arrdict
-    r_cpu = arrdict.arrdict(distances=torch.as_tensor(o['distances']).unsqueeze(2),
-                            screen=torch.as_tensor(o['screen']).unsqueeze(2).permute(0, 1, 4, 2, 3))
-    cpu_rgb = modules.RGB(CpuCore, n_agents=n_agents, subsample=subsample)(r_cpu)
-    cpu_d = modules.Depth(CpuCore, n_agents=n_agents, subsample=subsample, max_depth=7.)(r_cpu)
-    np.testing.assert_allclose(got_rgb.cpu().numpy(), cpu_rgb.numpy(), rtol=0, atol=1e-5)
-    np.testing.assert_allclose(got_d.cpu().numpy(), cpu_d.numpy(), rtol=0, atol=1e-5)
-    assert float(got_rgb.max()) > 0 and 0 < float(got_d.mean()) < 1
+    want_rgb, want_d = util.pooled_rule(o['screen'], o['distances'], c.agent_radius, 7., subsample)
+    assert np.isposinf(o['distances']).any(), 'a ray of this world should miss'
+    missed = np.isposinf(o['distances']).reshape(want_d.shape + (subsample,)).all(-1)
+    assert missed.any() and (want_d[missed] == 0).all(), 'a pixel whose rays all missed has depth 0'
+    assert ((want_d > 0) & (want_d < 1)).any()
+    util.assert_bits(fused.pooled_rgb[:, :, :, 0], want_rgb, 'pooled rgb')
+    util.assert_bits(fused.pooled_depth[:, :, 0, 0], want_d, 'pooled depth')
 
 
 def test_unwanted_outputs_are_skipped_and_wanted_ones_unchanged():
@@ -498,7 +504,7 @@ def test_heading_cache_is_used_only_while_it_is_true():
     assert same(fresh, cuda.render(c.scenery, c.agents, telemetry=True))
     ref = util.OracleWorld(c)
     ref.pull_baked(c); ref.pull_agents(c)
-    util.assert_render_matches(c, fresh, ref.render())
+    util.assert_render_bits(c, fresh, ref.render())
 
 
 def test_outputs_can_be_reused_between_calls():
@@ -583,9 +589,9 @@ def test_more_than_65536_walls_in_an_env():
         c.agents.angles[0] = angle
         ref.pull_agents(c)
         r = cuda.render(c.scenery, c.agents)
-        util.assert_render_matches(c, r, ref.render())
+        util.assert_render_bits(c, r, ref.render())
         assert int(r.indices[0].max()) > 66_000
     util.random_velocities(c, rng, speed=30.)
     ref.pull_agents(c)
     p = cuda.physics(c.scenery, c.agents)
-    util.assert_physics_matches(c, p, *ref.physics())
+    util.assert_physics_bits(c, p, *ref.physics())

@@ -4,8 +4,8 @@ tests/golden/reference_kernels.npz holds, for a fixed list of small cases, the f
 what the reference's kernels - compiled for the host, oracle/reference.py - made of them: the baked light, one physics step
 and the render from the state it left (tests/golden/make_reference_kernels.py). Here cuda.bake / cuda.physics / cuda.render
 (and cuda.step_render where it is one launch: one agent, at most 64 rays) run on the stored inputs, with the wall grid and
-the light grid on and off, and are held to the stored outputs by the suite's usual criteria (tests/util.py): collision
-masks, hit indices and NaN / inf patterns exact, floats to 1e-5, angles to 2e-5, the bake to 1e-5.
+the light grid on and off, and are held to the stored outputs bit for bit (tests/util.py: assert_bits - any NaN equals any NaN):
+collision masks, hit indices, every float of the agents' state and of the four render planes (also where a ray missed), the bake.
 
 Neither the oracle nor the reference is touched: only the npz."""
 import os
@@ -45,10 +45,6 @@ def _place(c, g):
         getattr(c.agents, k)[:] = torch.as_tensor(g['agents_' + k], device=c.device)
 
 
-def _exact(got, g, names):
-    return ' '.join(f"{k}={util.exact_fraction(v.cpu().numpy(), g[k]):.3f}" for k, v in zip(names, got))
-
-
 @pytest.mark.parametrize('light_grid', [True, False], ids=['lightgrid', 'nolightgrid'])
 @pytest.mark.parametrize('wall_grid', [True, False], ids=['wallgrid', 'nowallgrid'])
 @pytest.mark.parametrize('name', list(CASES))
@@ -61,21 +57,16 @@ def test_kernels_give_what_the_references_kernels_gave(monkeypatch, name, wall_g
     after = {k: g['after_' + k] for k in AGENT_FIELDS}
     ref = {k: g[k] for k in PLANES}
 
-    baked = c.scenery.baked.vals.cpu().numpy()
-    print(f"{name}: exact fractions: baked={util.exact_fraction(baked, g['baked']):.3f}", end=' ')
-    np.testing.assert_allclose(baked, g['baked'], rtol=0, atol=1e-5, err_msg='baked')
+    util.assert_bits(c.scenery.baked.vals, g['baked'], 'baked')
 
     _place(c, g)
     p = cuda.physics(c.scenery, c.agents)
     r = cuda.render(c.scenery, c.agents)
-    print(_exact([p.progress] + [getattr(c.agents, k) for k in AGENT_FIELDS], dict(after, progress=g['progress']), ('progress',) + AGENT_FIELDS),
-          _exact([getattr(r, k) for k in PLANES], ref, PLANES))
-    util.assert_physics_matches(c, p, g['progress'], after)
-    util.assert_render_matches(c, r, ref)
+    util.assert_physics_bits(c, p, g['progress'], after)
+    util.assert_render_bits(c, r, ref)
 
     if c.n_agents == 1 and c.res <= 64:             # the shape where a step is one launch
         _place(c, g)
         p, r = cuda.step_render(c.scenery, c.agents)
-        print('   one launch:', _exact([getattr(r, k) for k in PLANES], ref, PLANES))
-        util.assert_physics_matches(c, p, g['progress'], after)
-        util.assert_render_matches(c, r, ref)
+        util.assert_physics_bits(c, p, g['progress'], after)
+        util.assert_render_bits(c, r, ref)

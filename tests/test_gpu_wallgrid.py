@@ -107,12 +107,12 @@ def test_where_the_lists_do_not_apply_every_wall_is_met():
         got, want = p.progress.cpu().numpy(), prog_ref
         np.testing.assert_array_equal(np.nan_to_num(got, nan=-7.), np.nan_to_num(want, nan=-7.))
         ref.agents = util.agents_dict(c.agents)
-        util.assert_render_matches(c, r, ref.render())
+        util.assert_render_bits(c, r, ref.render())
     wide = core.Core(c.scenery, res=64, fov=172., fps=10)              # beyond MS_WALLGRID_MAX_FOV: no vis lists
     wide.agents.positions[:] = torch.nan_to_num(c.agents.positions, nan=3.)
     wide.agents.angles[:] = c.agents.angles
     ref = util.OracleWorld(wide)
-    util.assert_render_matches(wide, cuda.render(wide.scenery, wide.agents), ref.render())
+    util.assert_render_bits(wide, cuda.render(wide.scenery, wide.agents), ref.render())
 
 
 def test_a_grid_too_big_for_its_budget_is_coarsened_or_left_out(monkeypatch):
@@ -123,12 +123,12 @@ def test_a_grid_too_big_for_its_budget_is_coarsened_or_left_out(monkeypatch):
     c, _ = _world(4, 1, n_unique=2)
     assert c.scenery._wg is not None and c.scenery._wg.cell > cuda.Scenery.WALL_GRID_CELL
     ref = util.OracleWorld(c)
-    util.assert_render_matches(c, cuda.render(c.scenery, c.agents), ref.render())
+    util.assert_render_bits(c, cuda.render(c.scenery, c.agents), ref.render())
     monkeypatch.setattr(cuda.Scenery, 'WALL_GRID_BYTES', 100)
     c, _ = _world(4, 1, n_unique=2)
     assert c.scenery._wg is None
     ref = util.OracleWorld(c)
-    util.assert_render_matches(c, cuda.render(c.scenery, c.agents), ref.render())
+    util.assert_render_bits(c, cuda.render(c.scenery, c.agents), ref.render())
 
 
 def test_more_agents_than_lanes_take_the_sweep():
@@ -151,7 +151,7 @@ def test_more_agents_than_lanes_take_the_sweep():
     ref = util.OracleWorld(c)
     p = cuda.physics(c.scenery, c.agents)
     prog_ref, agents_ref = ref.physics()
-    util.assert_physics_matches(c, p, prog_ref, agents_ref)
+    util.assert_physics_bits(c, p, prog_ref, agents_ref)
     assert (prog_ref[:, 64:] < 1).any() and (prog_ref < 1).mean() > .5
 
 
@@ -177,4 +177,4 @@ def test_walls_moved_after_bake_are_caught():
     cuda.bake(c.scenery)
     ref = util.OracleWorld(c)
     ref.pull_baked(c); ref.pull_agents(c)
-    util.assert_render_matches(c, cuda.render(c.scenery, c.agents), ref.render())
+    util.assert_render_bits(c, cuda.render(c.scenery, c.agents), ref.render())

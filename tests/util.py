@@ -93,9 +93,98 @@ def assert_render_matches(core, r, ref, atol=1e-5):
     np.testing.assert_allclose(_np(r.screen), ref['screen'], rtol=0, atol=atol, err_msg='screen')
 
 
-def exact_fraction(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(((a == b) | (np.isnan(a) & np.isnan(b))).mean())
+# ---- bits: the product is defined as the oracle's binary32 results, so the GPU comparisons hold every float to its
+# 32-bit pattern. Any NaN equals any NaN (DESIGN 5's convention); -0. differs from +0.; integers compare by ==.
+
+def _arr(t):
+    return _np(t) if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def _same_kind(got, want, what='arrays'):
+    assert got.shape == want.shape, f'{what}: shapes differ: {got.shape} vs {want.shape}'
+    assert got.dtype == want.dtype, f'{what}: dtypes differ: {got.dtype} vs {want.dtype}'
+    assert got.dtype == np.float32 or got.dtype.kind in 'iub', f'{what}: binary32 or integers, not {got.dtype}'
+
+
+def same_bits(got, want):
+    """Elementwise, for two arrays of one shape and dtype: binary32 values are the same when their 32-bit patterns are, or when
+    both are NaN (of whatever payload); integers and booleans when they are =="""
+    got, want = _arr(got), _arr(want)
+    _same_kind(got, want)
+    if got.dtype != np.float32:
+        return got == want
+    return (np.ascontiguousarray(got).view(np.uint32) == np.ascontiguousarray(want).view(np.uint32)) | (np.isnan(got) & np.isnan(want))
+
+
+def _on_the_line(x):
+    """Binary32 patterns (sign and magnitude) as int64 points of one monotone line: -0. and +0. both at 0, the smallest
+    denormals at -1 and +1, the infinities at -/+ 0x7f800000, NaNs beyond them."""
+    b = np.ascontiguousarray(x).view(np.uint32).astype(np.int64)
+    mag = b & 0x7fffffff
+    return np.where(b >> 31 != 0, -mag, mag)
+
+
+def ulp_distance(got, want):
+    """How many binary32 values lie between two floats (elementwise, int64), across zero too."""
+    return np.abs(_on_the_line(np.asarray(got, np.float32)) - _on_the_line(np.asarray(want, np.float32)))
+
+
+def assert_bits(got, want, what='values'):
+    """Fails unless same_bits() holds everywhere, saying how many elements differ, where the first five are and what they hold
+    (as float.hex), the largest distance in ulps and the largest absolute difference."""
+    got, want = _arr(got), _arr(want)
+    _same_kind(got, want, what)
+    bad = ~same_bits(got, want)
+    if not bad.any():
+        return
+    where = np.argwhere(bad)
+    show = (lambda v: float(v).hex()) if got.dtype == np.float32 else (lambda v: repr(v.item()))
+    first = '; '.join(f'{tuple(int(i) for i in ix)}: got {show(got[tuple(ix)])}, want {show(want[tuple(ix)])}' for ix in where[:5])
+    msg = f'{what}: {int(bad.sum())} of {bad.size} elements differ in their bits. First: {first}.'
+    if got.dtype == np.float32:
+        g, w = got[bad], want[bad]
+        with np.errstate(invalid='ignore', over='ignore'):
+            diff = np.abs(g.astype(np.float64) - w.astype(np.float64))
+        diff = diff[~np.isnan(diff)]                    # (a NaN against a number, inf against inf of the other sign...: no difference to name)
+        largest = f'{diff.max():.3g}' if diff.size else 'nan'
+        msg += f' Largest distance: {int(ulp_distance(g, w).max())} ulp; largest absolute difference: {largest}.'
+    raise AssertionError(msg)
+
+
+def assert_physics_bits(core, p, progress_ref, agents_ref):
+    """The collision masks first (their message says most), then progress and the agents' state, bit for bit."""
+    progress = _np(p.progress)
+    np.testing.assert_array_equal(progress < 1, progress_ref < 1, err_msg='collision masks differ')
+    assert_bits(progress, progress_ref, 'progress')
+    for k in ('positions', 'velocity', 'angvelocity', 'angles'):
+        assert_bits(getattr(core.agents, k), agents_ref[k], k)
+
+
+def assert_render_bits(core, r, ref):
+    """Hit indices (and miss sentinels) equal; the four float planes bit for bit, everywhere - also where a ray missed."""
+    np.testing.assert_array_equal(_np(r.indices), ref['indices'], err_msg='hit indices differ')
+    for k in ('locations', 'dots', 'distances', 'screen'):
+        assert_bits(getattr(r, k), ref[k], k)
+
+
+def pooled_rule(screen, distances, agent_radius, max_depth, sub):
+    """The pooled observations' rule (render.h, "pooled observations") in numpy's binary32, on full-resolution
+    planes - screen (N, A, R, 3) and distances (N, A, R) - giving rgb (N, A, 3, R/sub) and depth (N, A, R/sub). Per ray the depth
+    1 - clamp((d - agent_radius)*(1.f/max_depth), 0, 1), a ray that missed (+inf) giving 0; then, for depth and each colour, the
+    sum of `sub` adjacent rays as a pairwise tree - (x0 + x1) + (x2 + x3), ... - times 2^-log2(sub)."""
+    f = np.float32
+    assert sub >= 1 and sub & (sub - 1) == 0 and distances.shape[-1] % sub == 0
+    screen, distances = np.asarray(screen, f), np.asarray(distances, f)
+    depth = f(1) - np.minimum(np.maximum((distances - f(agent_radius))*(f(1)/f(max_depth)), f(0)), f(1))
+
+    def pool(x):
+        x = x.reshape(x.shape[:-1] + (x.shape[-1]//sub, sub))
+        while x.shape[-1] > 1:
+            x = x[..., 0::2] + x[..., 1::2]
+        return x[..., 0]*f(1./sub)
+    rgb = pool(np.moveaxis(screen, -1, -2))
+    assert rgb.dtype == f and depth.dtype == f
+    return rgb, pool(depth)
 
 
 def scenery_by_the_book(geometries, n_agents, random=np.random):
@@ -183,6 +272,22 @@ def assert_subset_matches(core, sub, p, r):
     for k in ('indices', 'locations', 'dots', 'distances', 'screen'):
         setattr(R, k, getattr(r, k)[e])
     assert_render_matches(None, R, sub.render())
+
+
+def assert_subset_bits(core, sub, p, r):
+    """assert_subset_matches, to the bit."""
+    e = torch.as_tensor(sub.envs, device=core.device)
+    prog_ref, agents_ref = sub.physics()
+
+    class P:
+        progress = p.progress[e]
+    assert_physics_bits(_Rows(core, e), P, prog_ref, agents_ref)
+
+    class R:
+        pass
+    for k in ('indices', 'locations', 'dots', 'distances', 'screen'):
+        setattr(R, k, getattr(r, k)[e])
+    assert_render_bits(None, R, sub.render())
 
 
 def obstructed(I, C, walls):

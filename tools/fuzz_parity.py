@@ -64,7 +64,7 @@ def one(seed, oblique=None):
         c.scenery = sc
         mutated = ' mutated'
     ref = util.OracleWorld(c)
-    np.testing.assert_allclose(c.scenery.baked.vals.cpu().numpy(), ref.bake(), rtol=0, atol=1e-5)
+    util.assert_bits(c.scenery.baked.vals, ref.bake(), 'baked')
     ref.pull_baked(c)
     fields = cuda.FIELDS
     for step in range(3):
@@ -80,8 +80,8 @@ def one(seed, oblique=None):
             p = cuda.physics(c.scenery, c.agents)
             r = cuda.render(c.scenery, c.agents)
         prog_ref, agents_ref = ref.physics()
-        util.assert_physics_matches(c, p, prog_ref, agents_ref)
-        util.assert_render_matches(c, r, ref.render())
+        util.assert_physics_bits(c, p, prog_ref, agents_ref)
+        util.assert_render_bits(c, r, ref.render())
     return f'{kind:8s} envs {n_envs:2d} agents {n_agents:2d} rays {res:3d} fov {fov:5.1f}{mutated}'
 
 
@@ -131,6 +131,8 @@ def one_fused(seed):
             assert torch.equal(torch.nan_to_num(getattr(fused, f).float(), nan=-7.), torch.nan_to_num(getattr(full, f).float(), nan=-7.)), f
         else:
             assert getattr(fused, f) is None, f
+    # (against torch's `mean` on the device, for pixels of up to 64 rays - its order of summation is its own: a tolerance. The
+    # kernel's order is held bit for bit in tests/test_gpu_parity.py)
     torch.testing.assert_close(fused.obs_rgb, want_rgb, rtol=0, atol=1e-6)
     torch.testing.assert_close(fused.obs_depth, want_d, rtol=0, atol=1e-6)
     assert torch.equal(fused.obs_centre, want_centre.int())
