@@ -389,7 +389,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
     static_assert(NG == 1 || NG == 2 || NG == 4, "one, two or four ray groups per wave");
     [[maybe_unused]] constexpr int NR = WAVE*NG;  // rays per wave
     // (NG > 1: the list is shared by the wave's groups and must outlive their epilogues, whose scratch - the lighting's pair
-    // list and shadow words, the RGB staging - therefore sits in the per-group region behind it, O_EPI, not on top of it)
+    // list and shadow words - therefore sits in the per-group region behind it, O_EPI, not on top of it)
     constexpr int VCAP = NG == 1 ? MS_VCAP : MS_VCAP_WIDE;
     constexpr int O_EPI = NG > 1 ? 24*VCAP + 256 : 0;
     constexpr int LDS_PER_WAVE = NG == 1 ? 24*VCAP + 3072 : O_EPI + 2816 + 6*VCAP;
@@ -401,7 +401,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
     // 80 the kernel is held to.  Made opaque at the top of every iteration, the lane is worked with afresh each time.
 #define LANE_AFRESH asm volatile("" : "+v"(lane))
     Cand* const s_cand_w = reinterpret_cast<Cand*>(&s_raw[0]);
-    float* const s_screen_w = reinterpret_cast<float*>(&s_raw[O_EPI]);   // (the raycast is over by then)
 
     // (With one wave per workgroup the grid is exactly the blocks render_block() deals - ms_render launches it so: the count
     // comes from the kernel's own arguments, not from the dispatch packet, and at one group per wave there is no early exit -
@@ -839,17 +838,17 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         if constexpr (PLANES) {
         float* const o_screen = late->out.screen;
         if (!OBS || MS_WANTED(OUT_SCREEN, o_screen)) {
-            // stage RGB through LDS so the (R, 3) rows leave as three fully coalesced 256 B stores
-            s_screen_w[3*lane] = s0; s_screen_w[3*lane + 1] = s1; s_screen_w[3*lane + 2] = s2;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int nfl = 3*min(n_live - q*WAVE, WAVE);
-            float* __restrict__ scr = o_screen + 3*(((size_t)n*A + a)*R + r0 + q*WAVE);
-            #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const int j = lane + k*WAVE;
-                if (j < nfl) __builtin_nontemporal_store(s_screen_w[j], &scr[j]);
+            // A lane's three floats are 12 adjacent bytes of its (R, 3) row and the lanes' follow one another: they leave as they
+            // are, one 12-byte store a lane (the three below come out as a single global_store_dwordx3 nt) - the same 768 bytes
+            // as three coalesced rows of dwords.  Those took a staging through LDS - three writes, a barrier, three reads - at the
+            // very end of a wave's life, where nothing is left to run behind it.
+            if (lane < min(n_live - q*WAVE, WAVE)) {
+                // (the group's first float from the wave's scalars, the lane's three from there: spelled `o_screen + 3*o` it is
+                // 64-bit arithmetic in every lane)
+                float* __restrict__ px = o_screen + 3*(((size_t)n*A + a)*R + r0 + q*WAVE) + 3*lane;
+                __builtin_nontemporal_store(s0, &px[0]);
+                __builtin_nontemporal_store(s1, &px[1]);
+                __builtin_nontemporal_store(s2, &px[2]);
             }
         }
         }
@@ -1002,32 +1001,55 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
             // the mark bits of all 64 possible windows in one read: lane w holds window w's, and each window fetches
         // its own with two v_readlane - no LDS round trip per window
         const unsigned long long my_marks = reinterpret_cast<const unsigned long long*>(s_mark_w)[lane];
-        for (int p0 = 0; p0 < n_pairs; p0 += WAVE) {
-            const unsigned mlo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)my_marks, p0 >> 6);
-            const unsigned mhi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(my_marks >> 32), p0 >> 6);
+        // A window's LDS reads wait only for what they depend on.  The list entry k of a lane's pair follows from the mark words
+        // alone, so a window's `info` and `cand` are asked for a window AHEAD - behind the last use of this window's, in the
+        // registers those leave, and in front of this window's atomics, with whose answer they arrive - and `near` has `ray`'s
+        // address and travels with it, hit or no hit.  A window is then two LDS round trips, (ray, near) and the atomic, where
+        // it was four, one behind the other.
+        // the entry of this lane's pair in the window at p0 (`before`: the marks of the windows in front of it, moved on)
+        auto entry_at = [&](const int p0) {
+            const int wdw = min(p0 >> 6, WAVE - 1);      // (the window past pair 4095 is asked of lane 63: thrown away, see below)
+            const unsigned mlo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)my_marks, wdw);
+            const unsigned mhi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(my_marks >> 32), wdw);
             const unsigned long long M = ((unsigned long long)mhi << 32) | mlo;
             // marks at positions 0..lane of this window, via the bits of M >> 1 below the lane
             const unsigned long long Ms = M >> 1;
             const int upto = (int)(mlo & 1u) + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(Ms >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)Ms, 0u));
-            const int p = p0 + lane;
-            const bool valid = p < n_pairs;
             const int k = before + upto - 1;             // (past the last pair there are no marks: the last line, harmless)
             before += __popcll(M);
-            const int2 info = s_info_w[k];
+            return k;
+        };
+        const int k_first = entry_at(0);
+        int2 info = s_info_w[k_first];
+        Cand cd = s_cand_w[k_first];
+        for (int p0 = 0; p0 < n_pairs; p0 += WAVE) {
+            const int p = p0 + lane;
+            const bool valid = p < n_pairs;
             const int rr = (p + info.x) & 63;            // ray of this pair, wave-local (in range as it is for valid pairs)
-            const Cand cd = s_cand_w[k];
+            const int line = info.y;
             const float2 ray = s_ray_w[rr];
+            float near_rr = s_near_w[rr];
+            // (pinned in front of the arithmetic, and the entry's last use behind it: left to itself hipcc sinks both into the
+            // branch below - `near` a round trip of its own again, the entry alive across the reads that are to take its
+            // registers, and six moves a window to hand them over)
+            asm volatile("" : "+v"(near_rr));
             const float d = ray.x*cd.vy - ray.y*cd.vx;                   // cross(ru, v)
             const float nt = cd.pqx*ray.y - cd.pqy*ray.x;                // cross(PQ, ru)
             const float ad = fabsf(d);
             const float ntp = bits_f(f_bits(nt) ^ (f_bits(d) & 0x80000000u));
             // hit: 0 <= t <= 1 with t = nt/d  <=>  0 <= nt' <= |d| (exact, see light_blocked)
             const bool hit = valid & (ad >= 1.e-3f) & (ntp >= 0.f) & (ntp <= ad);
+            float cpv = cd.pqx*cd.vy - cd.pqy*cd.vx;                     // cross(PQ, V): the entry's last use
+            asm volatile("" : "+v"(cpv));
+            // the next window's entry: past the last window one that exists, read and thrown away
+            const int k_next = min(entry_at(p0 + WAVE), n_list - 1);
+            info = s_info_w[k_next];
+            cd = s_cand_w[k_next];
             if (hit) {
-                const float sv = div_inrange(cd.pqx*cd.vy - cd.pqy*cd.vx, d);        // q.s = cross(PQ, V)/UxV
-                const bool beyond = s_near_w[rr] < sv;                          // beyond the near plane, kernels.cu:369
+                const float sv = div_inrange(cpv, d);                            // q.s = cross(PQ, V)/UxV
+                const bool beyond = near_rr < sv;                               // beyond the near plane, kernels.cu:369
                 if (beyond) {
-                    const unsigned long long key = ((unsigned long long)f_bits(sv) << 32) | (unsigned)info.y;
+                    const unsigned long long key = ((unsigned long long)f_bits(sv) << 32) | (unsigned)line;
                     const unsigned long long old = atomicMin(&s_best_w[rr], key);
                     const unsigned oh = (unsigned)(old >> 32);
                     if (oh != 0xffffffffu) {                             // there was a hit before: is the loser anywhere near?
@@ -1404,6 +1426,8 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
                     const Cand cd = s_cand_w[k];
                     const int line = s_info_w[k].y;
                     const float2 ray = s_ray_w[rr];
+                    float near_g = s_near_w[rr];                                 // (with `ray`, hit or no hit, and pinned there: see drain)
+                    asm volatile("" : "+v"(near_g));
                     const float d = ray.x*cd.vy - ray.y*cd.vx;                   // cross(ru, v)
                     const float nt = cd.pqx*ray.y - cd.pqy*ray.x;                // cross(PQ, ru)
                     const float ad = fabsf(d);
@@ -1411,7 +1435,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
                     const bool hit = valid & (ad >= 1.e-3f) & (ntp >= 0.f) & (ntp <= ad);
                     if (hit) {
                         const float sv = div_inrange(cd.pqx*cd.vy - cd.pqy*cd.vx, d);        // q.s = cross(PQ, V)/UxV
-                        const bool beyond = s_near_w[rr] < sv;                   // beyond the near plane, kernels.cu:369
+                        const bool beyond = near_g < sv;                         // beyond the near plane, kernels.cu:369
                         if (beyond) {
                             const unsigned long long key = ((unsigned long long)f_bits(sv) << 32) | (unsigned)line;
                             const unsigned long long old = atomicMin(&s_best_w[rr], key);
