@@ -945,6 +945,64 @@ int ms_nav_basins(const MsNavGrid* grid, const MsNavBasins* basins, void* hip_st
 int ms_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* query, void* hip_stream);
 int ms_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* marks, void* hip_stream);
 
+/* Clearance: how much room there is - the distance from a place to the nearest wall, which wall that is, and which way it lies;
+ * per cell of the nav grid (a float layer: a band for ms_nav_draws, a channel for ms_nav_windows; and the free bytes of several
+ * body sizes from one pass over the walls) and per point, the other agents' bodies counted (a proximity reading).  What
+ * ms_nav_free folds and throws away, kept.  Every step below is one binary32 operation, in the order given, without
+ * contraction; tests/test_navclear_host.py restates it in numpy (clear_rule) and the kernels - and their host instantiations,
+ * ms_host_nav_clearance / ms_host_nav_clear_query - are held to EQUALITY with it.  With R = max_range:
+ *   a line        For a point (x, y) and row l = (ax, ay, bx, by) of its env: vx, vy, px, py, vv, t, dx, dy, d2 by MsOverhead's
+ *                 statements, statement for statement.  The row is a CANDIDATE when d2 <= R*R (R*R formed once; a NaN never is).
+ *   the winner    the candidate of least d2, of least l among those: MsOverhead's winner at half_width R.
+ *   field         for cell (i, j) of env n's grid, at its centre (MsNavGrid's), over the env's STATIC rows (l from
+ *                 n_agents*n_model on: the rows ms_nav_free reads):
+ *                   values   sqrtf(d2) of the winner, the root correctly rounded; +inf without one.  (starts[N],) float32, free
+ *                            cells' layout: an MsNavLayer of one store.
+ *                   nearest  the winner's l (env-local, agent rows counted: ms_overhead's indices); -1 without one.
+ *                   fits     K = n_radii stores an env in the fields' layout - store (n, k) at K*starts[n] + k*nx*ny - byte k
+ *                            0 when there is a winner and its d2 <= r_k*r_k (r_k = radii[k], the square formed once), else 1:
+ *                            with r_k <= R, exactly the free byte ms_nav_free writes at clearance r_k.
+ *                 mask (N,) bytes: an env marked 0 keeps all its stores untouched.  An env without cells: nothing stored.
+ *   query         for point (n, p) = (x, y), anywhere (no grid): the same statements and winner over the env's static rows and,
+ *                 with agents, the agent rows 0 .. n_agents*n_model - 1 too, drawn at the agents' current poses as ms_overhead
+ *                 draws them (nothing is written to the scenery) - except rows s*n_model .. (s + 1)*n_model - 1 of the agent
+ *                 s = skip[n, p]; a value outside 0 .. n_agents - 1 (-1, say) skips none.  Without agents no agent row is met
+ *                 and skip is not read.
+ *                   distances  as values.    nearest  as above.
+ *                   towards    (-dx/d, -dy/d) with d = sqrtf(d2) and the winner's dx, dy: the unit vector from the point to the
+ *                              nearest point of the winner; (0, 0) when d == 0 or there is no winner.
+ *                 A point with a NaN coordinate has no winner.  mask (N, P) bytes: a point marked 0 keeps its outputs untouched.
+ * Refused before any launch (MS_EINVAL): a NULL struct or values; a scenery (or query) of another number of envs; max_range not
+ * positive and finite; n_radii outside 0..8; fits NULL with n_radii > 0 or given with 0; a radius that is not positive or is
+ * above max_range (as binary32); max_tiles < 1 for a grid with cells; a query with P < 1, NULL points, no output at all, or points
+ * or towards not 8-byte aligned.  One launch each; every value has one writer; no atomics; nothing allocated, nothing waits:
+ * both calls can be captured in a HIP graph. */
+typedef struct MsNavClearance {
+    float                max_range;    /* R, metres (> 0, finite)                                                      */
+    int                  n_radii;      /* K, 0..8                                                                      */
+    float                radii[8];     /* r_k, metres (> 0, <= R); the first K are read                                */
+    int                  max_tiles;    /* the most 16 x 16 tiles - ceil(nx/16)*ceil(ny/16) - of any env: sizes the launch; an
+                                          env of more still gets the right bits, a tile after another                  */
+    const unsigned char* mask;         /* (N,) non-zero: compute this env; NULL: all.  Read on the device only.        */
+    float*               values;       /* (starts[N],) out                                                             */
+    int*                 nearest;      /* (starts[N],) out, or NULL                                                    */
+    unsigned char*       fits;         /* K*starts[N] bytes out; NULL exactly when K == 0                              */
+} MsNavClearance;
+typedef struct MsNavClearQuery {
+    int                  n_envs;       /* N: the scenery's                                                             */
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y; 8-byte aligned                                               */
+    const int*           skip;         /* (N, P) the agent whose own rows each point passes over, or NULL: none        */
+    float                max_range;    /* R, metres (> 0, finite)                                                      */
+    const unsigned char* mask;         /* (N, P) non-zero: compute this point; NULL: all.  Read on the device only.    */
+    float*               distances;    /* (N, P) out, or NULL                                                          */
+    int*                 nearest;      /* (N, P) out, or NULL                                                          */
+    float*               towards;      /* (N, P, 2) out, or NULL; 8-byte aligned                                       */
+} MsNavClearQuery;
+int ms_nav_clearance(const MsScenery* scenery, const MsNavGrid* grid, const MsNavClearance* clearance, void* hip_stream);
+int ms_nav_clear_query(const MsScenery* scenery, const MsAgents* agents /* NULL: static walls only */, const MsNavClearQuery* query,
+                       void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

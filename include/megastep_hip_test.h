@@ -138,6 +138,30 @@ int ms_host_nav_basin_capacity(int* capacities);
  * ms_nav_views would: MS_OK, or MS_EINVAL for arguments it would refuse (and for a capacity above the kernel's). */
 int ms_host_nav_views(const MsNavGrid* grid, const MsNavViews* views, const float* walls, const long long* wall_starts, int capacity);
 int ms_host_nav_view_capacity(void);
+/* Host instantiations of the clearance rule (kernels/navclear.h: the tile's box, the list, ov_keeps and ov_fold, the second cull,
+ * the winner's order and the stores - the very functions every lane of nav_clear_kernel and nav_clear_query_kernel evaluates) for
+ * one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the argument struct is host memory.
+ * ms_host_nav_clearance: in place of an MsScenery `walls` holds the STATIC rows of all envs, four floats each, env n's rows
+ * wall_starts[n] .. wall_starts[n + 1] - 1, and `nearest` numbers them from 0 within their env (the device's index less
+ * n_agents*n_model).  It goes through the kernel's 16 x 16 tiles, its windows of 256 rows and its list of
+ * ms_host_nav_clear_chunk() rows, folded and emptied when it could overflow.  flags: 0 = no cull (every tile keeps every row:
+ * brute force), 1 = the tile cull, 2 = the tile cull and the second cull, emulated over the same 16 x 4 groups of cells and the
+ * same runs of 64 list rows in the same order.  ms_host_nav_clear_folds: the (cell, row) pairs the calling thread's last
+ * ms_host_nav_clearance folded, and into *pairs (or NULL) all the pairs there were.
+ * ms_host_nav_clear_query: `rows` holds ALL rows of all envs as the query is to meet them - the n_agents*n_model agent rows of an
+ * env first, at whatever poses the caller drew them (the host draws none), env n's rows row_starts[n] .. row_starts[n + 1] - 1;
+ * with_agents = 0 passes over them as a query without agents does.  flags: 0 = one serial fold, 1 = the rows dealt to 64 bests as
+ * the kernel's lanes stride them, merged by the kernel's butterfly.
+ * Both return what the device entries would: MS_OK, or MS_EINVAL for arguments they would refuse (and for NULL rows or flags out
+ * of range).
+ * ms_debug_nav_clear_cull: which culls ms_nav_clearance's launch runs - 0, 1, 2 as the flags above; -1 = the library's own choice.
+ * Per calling thread; A/B runs and tests - every setting produces the same bits. */
+int ms_host_nav_clearance(const MsNavGrid* grid, const MsNavClearance* clearance, const float* walls, const long long* wall_starts, int flags);
+long long ms_host_nav_clear_folds(long long* pairs);
+int ms_host_nav_clear_chunk(void);
+int ms_host_nav_clear_query(const MsNavClearQuery* query, const float* rows, const long long* row_starts, int n_agents, int n_model,
+                            int with_agents, int flags);
+int ms_debug_nav_clear_cull(int mode);
 /* The kernels' arithmetic shortcuts against what they stand for, element by element on the device (DEVICE pointers, `count`
  * elements each): q_inrange[i] = div_inrange(n[i], d[i]) - the division without range scaling the render kernel uses where its
  * operands are in range by construction (kernels/math.h) - next to q_ieee[i] = n[i] / d[i] as the compiler expands a correctly

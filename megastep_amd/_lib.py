@@ -194,6 +194,16 @@ class MsNavViews(C.Structure):
                 ('values', C.c_void_p), ('counts', C.c_void_p), ('gains', C.c_void_p)]
 
 
+class MsNavClearance(C.Structure):
+    _fields_ = [('max_range', C.c_float), ('n_radii', C.c_int), ('radii', C.c_float*8), ('max_tiles', C.c_int), ('mask', C.c_void_p),
+                ('values', C.c_void_p), ('nearest', C.c_void_p), ('fits', C.c_void_p)]
+
+
+class MsNavClearQuery(C.Structure):
+    _fields_ = [('n_envs', C.c_int), ('n_points', C.c_int), ('points', C.c_void_p), ('skip', C.c_void_p), ('max_range', C.c_float),
+                ('mask', C.c_void_p), ('distances', C.c_void_p), ('nearest', C.c_void_p), ('towards', C.c_void_p)]
+
+
 _int, _flt, _ptr, _p = C.c_int, C.c_float, C.c_void_p, C.POINTER
 
 #: every symbol include/megastep_hip.h (the boundary) and include/megastep_hip_test.h (test hooks) declare, as
@@ -231,6 +241,8 @@ PROTOTYPES = {
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
     'ms_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery), _ptr]),
     'ms_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks), _ptr]),
+    'ms_nav_clearance': (_int, [_p(MsScenery), _p(MsNavGrid), _p(MsNavClearance), _ptr]),
+    'ms_nav_clear_query': (_int, [_p(MsScenery), _p(MsAgents), _p(MsNavClearQuery), _ptr]),
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
     'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
     'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
@@ -271,6 +283,11 @@ PROTOTYPES = {
     'ms_host_nav_basin_capacity': (_int, [_ptr]),
     'ms_host_nav_views': (_int, [_p(MsNavGrid), _p(MsNavViews), _ptr, _ptr, _int]),
     'ms_host_nav_view_capacity': (_int, []),
+    'ms_host_nav_clearance': (_int, [_p(MsNavGrid), _p(MsNavClearance), _ptr, _ptr, _int]),
+    'ms_host_nav_clear_folds': (C.c_longlong, [_ptr]),
+    'ms_host_nav_clear_chunk': (_int, []),
+    'ms_host_nav_clear_query': (_int, [_p(MsNavClearQuery), _ptr, _ptr, _int, _int, _int, _int]),
+    'ms_debug_nav_clear_cull': (_int, [_int]),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),

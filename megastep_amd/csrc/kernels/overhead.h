@@ -86,7 +86,7 @@ __host__ __device__ inline bool ov_keeps(const OvBox& b, const float h, const fl
 struct OvBest { float d2; int idx; float t; };
 
 // One line of the rule for the pixel centre (x, y): statement for statement include/megastep_hip.h's MsOverhead.
-__device__ inline void ov_fold(const float x, const float y, const float4 L, const int l, const float h2, OvBest& b) {
+__host__ __device__ inline void ov_fold(const float x, const float y, const float4 L, const int l, const float h2, OvBest& b) {
     const float vx = L.z - L.x, vy = L.w - L.y, px = x - L.x, py = y - L.y;
     const float vv = vx*vx + vy*vy;
     float t = vv > 0.f ? (px*vx + py*vy)/vv : 0.f;

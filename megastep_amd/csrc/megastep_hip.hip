@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navregion.h, navview.h, navpath.h, navbasin.h, navseen.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navbasin.h, navseen.h, navwindow.h, navdraw.h.
 //
-// Twenty-four kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Twenty-six kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -65,6 +65,10 @@
 //   nav_view_kernel     view fields: one workgroup per viewpoint culls the env's static walls into LDS and tests the centre of
 //                   every cell in range against them, a lane a cell: the cells in sight, how many count, how many are new.
 //                                                            (no counterpart)
+//   nav_clear_kernel, nav_clear_query_kernel   clearance: the distance to the nearest wall - per cell, overhead_kernel's scheme on
+//                   the grid's 16 x 16 tiles (the env's static rows culled against the tile's box into LDS, a second cull by the
+//                   wave's own worst best while it folds); per point one wave, the lanes striding the rows (the other agents'
+//                   bodies too) and a shuffle minimum.   (no counterpart)
 //   explorer_kernel    the Explorer env's books between frames (reward, episode rule, forgetting) as one launch.
 //                                                            (reference: demo/envs/explorer.py:45-90)
 //   deathmatch_kernel   the Deathmatch env's game logic between frames (revive, crosshairs, hits and wounds, health, damage,
@@ -106,6 +110,8 @@ thread_local int g_tail_envs = -1;          //   ... >= 0: that many envs exactl
 thread_local int g_last_step_fused = 0;     // ms_debug_last_step_fused: did this thread's last ms_step_render go out as one launch?
 thread_local int g_last_render_groups = 0;  // ms_debug_last_render_groups: the NG this thread's last ms_render launched
 thread_local int g_overhead_cull = 1;       // ms_debug_overhead_cull: 0 = ms_overhead's tiles keep every line
+thread_local int g_nav_clear_cull = -1;     // ms_debug_nav_clear_cull: which culls ms_nav_clearance's launch runs (-1: its own choice)
+thread_local long long g_clear_folds = 0, g_clear_pairs = 0;      // ms_host_nav_clear_folds: the last ms_host_nav_clearance's
 thread_local int g_render_order = 1;        // ms_debug_render_order: 0 = MsAgents.schedule is neither sorted nor followed
 
 // The agents as the kernels take them: MsAgents less its fan schedule, which only physics_kernel's sort waves (FanSort) and the
@@ -164,6 +170,7 @@ struct Probe {
 #include "kernels/raycast.h"
 #include "kernels/overhead.h"
 #include "kernels/navfield.h"
+#include "kernels/navclear.h"
 #include "kernels/navregion.h"
 #include "kernels/navview.h"
 #include "kernels/navpath.h"
@@ -1361,6 +1368,91 @@ int ms_host_nav_views(const MsNavGrid* grid, const MsNavViews* v, const float* w
 }
 
 int ms_host_nav_view_capacity(void) { return VIEW_WALL_CAPACITY; }
+
+// Clearance (navclear.h): the same discipline.  CLEAR_DEFAULT_CULL is the instantiation ms_nav_clearance launches (DESIGN.md 3.23
+// has the measurements that chose it); the other stays reachable through ms_debug_nav_clear_cull for A/B runs.
+constexpr int CLEAR_DEFAULT_CULL = CLEAR_TILE_WAVE;
+static int nav_clearance_check(const MsNavGrid* grid, const MsNavClearance* c) {
+    if (!nav_grid_ok(grid) || !c || !(c->max_range > 0.f) || !(c->max_range < INFINITY) || c->n_radii < 0 || c->n_radii > CLEAR_MAX_RADII ||
+        !c->values || (c->n_radii > 0) != (c->fits != nullptr) || ((uintptr_t)c->values % 4) || ((uintptr_t)c->nearest % 4) ||
+        (grid->max_framed > 0 && c->max_tiles < 1)) return MS_EINVAL;
+    for (int k = 0; k < c->n_radii; k++)
+        if (!(c->radii[k] > 0.f) || !(c->radii[k] <= c->max_range)) return MS_EINVAL;
+    if (grid->n_envs > 65535) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static ClearArgs nav_clear_args(const MsNavClearance* c, const int cull) {
+    ClearArgs q{c->mask, c->values, c->nearest, c->fits, c->n_radii, cull, c->max_range, c->max_range*c->max_range, {}};
+    for (int k = 0; k < c->n_radii; k++) q.r2[k] = c->radii[k]*c->radii[k];
+    return q;
+}
+static int nav_clear_query_check(const MsNavClearQuery* q) {
+    if (!q || q->n_envs < 1 || q->n_points < 1 || !q->points || (!q->distances && !q->nearest && !q->towards) || !(q->max_range > 0.f) ||
+        !(q->max_range < INFINITY) || ((uintptr_t)q->points % 8) || ((uintptr_t)q->towards % 8) || ((uintptr_t)q->skip % 4) ||
+        ((uintptr_t)q->distances % 4) || ((uintptr_t)q->nearest % 4)) return MS_EINVAL;
+    if ((long long)q->n_envs*q->n_points > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static ClearQueryArgs nav_clear_query_args(const MsNavClearQuery* q, const bool with_agents) {
+    return ClearQueryArgs{q->points, with_agents ? q->skip : nullptr, q->mask, q->distances, q->nearest, q->towards, q->n_points, with_agents ? 1 : 0,
+                          (long long)q->n_envs*q->n_points, q->max_range*q->max_range};
+}
+
+int ms_nav_clearance(const MsScenery* sc, const MsNavGrid* grid, const MsNavClearance* c, void* stream) {
+    if (!scenery_ok(sc) || !nav_grid_ok(grid) || grid->n_envs != sc->n_envs) return MS_EINVAL;
+    const int status = nav_clearance_check(grid, c);
+    if (status != MS_OK) return status;
+    if (grid->max_framed == 0) return MS_OK;
+    const int cull = g_nav_clear_cull < 0 ? CLEAR_DEFAULT_CULL : g_nav_clear_cull;
+    const dim3 blocks((unsigned)c->max_tiles, (unsigned)grid->n_envs);
+    if (cull == CLEAR_TILE_WAVE)
+        hipLaunchKernelGGL(nav_clear_kernel<true>, blocks, dim3(WG), 0, (hipStream_t)stream, *sc, nav_args(grid), nav_clear_args(c, 1));
+    else
+        hipLaunchKernelGGL(nav_clear_kernel<false>, blocks, dim3(WG), 0, (hipStream_t)stream, *sc, nav_args(grid), nav_clear_args(c, cull != CLEAR_BRUTE));
+    return launch_status();
+}
+
+int ms_nav_clear_query(const MsScenery* sc, const MsAgents* ag, const MsNavClearQuery* q, void* stream) {
+    if (!scenery_ok(sc)) return MS_EINVAL;
+    const int status = nav_clear_query_check(q);
+    if (status != MS_OK) return status;
+    if (q->n_envs != sc->n_envs || (ag && (!ag->angles || !ag->positions || ((uintptr_t)ag->positions % 8)))) return MS_EINVAL;
+    const long long total = (long long)q->n_envs*q->n_points;
+    hipLaunchKernelGGL(nav_clear_query_kernel, dim3((unsigned)((total + WAVES - 1)/WAVES)), dim3(WG), 0, (hipStream_t)stream, *sc, agents_or_none(ag),
+                       nav_clear_query_args(q, ag != nullptr));
+    return launch_status();
+}
+
+int ms_debug_nav_clear_cull(int mode) {
+    if (mode < -1 || mode > CLEAR_TILE_WAVE) return MS_EINVAL;
+    g_nav_clear_cull = mode;
+    return MS_OK;
+}
+
+int ms_host_nav_clearance(const MsNavGrid* grid, const MsNavClearance* c, const float* walls, const long long* wall_starts, int flags) {
+    const int status = nav_clearance_check(grid, c);
+    if (status != MS_OK) return status;
+    if (!walls || !wall_starts || flags < CLEAR_BRUTE || flags > CLEAR_TILE_WAVE) return MS_EINVAL;
+    clear_serial(nav_args(grid), nav_clear_args(c, flags != CLEAR_BRUTE), reinterpret_cast<const float4*>(walls), wall_starts, 0, flags, &g_clear_folds,
+                 &g_clear_pairs);
+    return MS_OK;
+}
+
+long long ms_host_nav_clear_folds(long long* pairs) {
+    if (pairs) *pairs = g_clear_pairs;
+    return g_clear_folds;
+}
+
+int ms_host_nav_clear_chunk(void) { return OV_CHUNK; }
+
+int ms_host_nav_clear_query(const MsNavClearQuery* q, const float* rows, const long long* row_starts, int n_agents, int n_model, int with_agents,
+                            int flags) {
+    const int status = nav_clear_query_check(q);
+    if (status != MS_OK) return status;
+    if (!rows || !row_starts || n_agents < 1 || n_model < 1 || flags < 0 || flags > 1) return MS_EINVAL;
+    clear_query_serial(nav_clear_query_args(q, with_agents != 0), n_agents, n_model, reinterpret_cast<const float4*>(rows), row_starts, flags != 0);
+    return MS_OK;
+}
 
 int ms_bake(const MsScenery* sc, const MsConfig* cfg, void* stream) {
     (void)cfg;

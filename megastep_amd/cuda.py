@@ -695,4 +695,5 @@ from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
 from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, plan_views, agent_views
 from .nav import nav_geometry, NavGrid, nav_grid, FIELD_CAPACITY, DistanceFields, Paths, distance_fields, geodesic, SeenMaps, seen_maps, SeededFields, seeded_fields, \
     CellLayer, cell_layer, MapChannel, map_channel, local_maps, CellDraws, cell_draws, REGION_CAPACITY, Regions, regions, \
-    VIEW_WALL_CAPACITY, ViewFields, view_fields, BASIN_CAPACITY, BASIN_MAX_IDS, PointMarks, point_marks, Basins, basins
+    VIEW_WALL_CAPACITY, ViewFields, view_fields, BASIN_CAPACITY, BASIN_MAX_IDS, PointMarks, point_marks, Basins, basins, \
+    CLEARANCE_MAX_RADII, ClearanceFields, clearance_fields, Clearance, clearance

@@ -292,6 +292,40 @@ class IMU:
             to_local_frame(agents.angles, agents.velocity)/self.speed_scale], -1)
 
 
+class Proximity:
+
+    def __init__(self, core, max_range=2., others=True):
+        """How near the nearest thing is, and which way, (n_env, n_agent, 3) (:func:`cuda.clearance`; no counterpart in the
+        reference): element 0 is ``min(d/max_range, 1)`` with ``d`` the distance from the agent's centre to the nearest line within
+        ``max_range`` metres - 1 when nothing is in range - and elements 1, 2 the unit vector towards it in the agent's frame
+        (:func:`to_local_frame`: the frame :class:`IMU` and :meth:`Goals.observation` use), (0, 0) when nothing is in range. With
+        ``others`` the other agents' bodies count, at their current poses, and the agent's own are passed over; without, only the
+        building's walls. The input of a wall-hugging penalty or a safety reward. One launch and a few elementwise ops; the module
+        keeps the launch's buffers, nothing waits for the host: a call can sit in a HIP graph."""
+        self.core = core
+        self.max_range, self.others = float(max_range), bool(others)
+        self.space = spaces.MultiVector(core.n_agents, 3)
+        n, a = core.n_envs, core.n_agents
+        self._skip = torch.arange(a, dtype=torch.int32, device=core.device).expand(n, a).contiguous() if self.others else None
+        self._reading = None
+
+    #: the :class:`cuda.Clearance` of the last call (None before the first)
+    reading = property(lambda self: self._reading)
+
+    @staticmethod
+    def observation(distances, towards, angles, max_range):
+        """The rule, a pure function: ``distances`` (N, A), ``towards`` (N, A, 2) in the world frame, ``angles`` (N, A) degrees ->
+        (N, A, 3)."""
+        near = (distances/max_range).clamp(max=1.)
+        return torch.cat([near[..., None], to_local_frame(angles, towards)], -1)
+
+    def __call__(self):
+        agents = self.core.agents
+        self._reading = cuda.clearance(self.core.scenery, agents.positions, self.max_range, agents=agents if self.others else None,
+                                       skip=self._skip, out=self._reading)
+        return self.observation(self._reading.distances, self._reading.towards, agents.angles, self.max_range)
+
+
 def random_empty_positions(geometries, n_agents, n_points):
     """(n_geometries, n_agents, n_points, 2) randomly chosen free-cell centres, precomputed so respawns are cheap
     (reference: modules.py:272-296; consumes the global ``np.random`` in the same order, env by env). The free cells of

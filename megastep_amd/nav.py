@@ -2,14 +2,15 @@
 floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
 they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``,
 ``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), the cells in sight of a
-point (``csrc/kernels/navview.h``), and the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``).
+point (``csrc/kernels/navview.h``), the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``), and the distance
+to the nearest wall, per cell and per point (``csrc/kernels/navclear.h``).
 No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
 import torch
 from . import _lib
 from ._lib import _on, _stream
-from ._call import _cfg, _check, _hw, _require_gpu
+from ._call import _cfg, _check, _hw, _query_device, _require_gpu, _result_for
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -594,8 +595,9 @@ def cell_layer(values, n_fields=1, field=None):
     can be the source. ``field``: an (N, P) integer tensor naming the store each view reads; without it store 0 is read when
     ``n_fields`` is 1 and view p reads store p when ``n_fields`` is the number of views. A :class:`NavGrid` (its ``free``), a
     :class:`SeenMaps`, a :class:`DistanceFields` and a :class:`SeededFields` are layers as they are, with their own number of
-    stores, and so are a :class:`Regions` (its ``areas``, square metres) and a :class:`ViewFields` (its ``values``, a store a
-    viewpoint); ``cell_layer(maps, field=slot)`` gives one of them a ``field``."""
+    stores, and so are a :class:`Regions` (its ``areas``, square metres), a :class:`ViewFields` (its ``values``, a store a
+    viewpoint) and a :class:`ClearanceFields` (its ``values``, metres to the nearest wall: one float store);
+    ``cell_layer(maps, field=slot)`` gives one of them a ``field``."""
     if isinstance(values, CellLayer):
         values, n_fields = values.values, values.n_fields
     elif isinstance(values, NavGrid):
@@ -608,6 +610,8 @@ def cell_layer(values, n_fields=1, field=None):
         values, n_fields = values.areas, values.n_fields
     elif isinstance(values, ViewFields):
         values, n_fields = values.values, values.n_points
+    elif isinstance(values, ClearanceFields):
+        values, n_fields = values.values, 1
     if not isinstance(n_fields, int) or n_fields < 1:
         raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
     if not isinstance(values, torch.Tensor) or values.dtype not in (torch.uint8, torch.bool, torch.float32) or values.ndim != 1 or \
@@ -631,7 +635,7 @@ class MapChannel:
 
 def map_channel(source, where=True, scale=None, gate=None, outside=0., hidden=0.):
     """One channel of :func:`local_maps`. ``source``: a layer (:func:`cell_layer`, or a :class:`NavGrid`, :class:`SeenMaps`,
-    :class:`DistanceFields`, :class:`SeededFields`, :class:`Regions` or :class:`ViewFields` as it is). A byte source gives 1 where ``(byte != 0) == where`` and 0
+    :class:`DistanceFields`, :class:`SeededFields`, :class:`Regions`, :class:`ViewFields` or :class:`ClearanceFields` as it is). A byte source gives 1 where ``(byte != 0) == where`` and 0
     elsewhere; a float source holding D gives ``D*scale`` clamped to [0, 1] (a NaN and +inf: 1), and ``scale`` is required.
     ``gate``: a byte layer with a ``field`` of its own; where its byte is 0 the channel shows ``hidden`` - ``grid.free`` gated by
     an agent's seen map is the floor that agent knows. ``outside``: what a sample beyond the env's grid shows."""
@@ -758,7 +762,7 @@ class CellDraws:
 def cell_draws(grid, source, n_sets, n_draws, lo=None, hi=None, where=True, gate=None, seed=0, mask=None, out=None):
     """Cells of the :func:`nav_grid` drawn uniformly at random: for every env ``n_sets`` draw sets of ``n_draws`` (1..256) draws each,
     with replacement, among the env's free cells that satisfy a predicate on ``source`` - a layer (:func:`cell_layer`, or a
-    :class:`NavGrid`, :class:`SeenMaps`, :class:`DistanceFields`, :class:`SeededFields`, :class:`Regions` or :class:`ViewFields` as it is), read per set the way
+    :class:`NavGrid`, :class:`SeenMaps`, :class:`DistanceFields`, :class:`SeededFields`, :class:`Regions`, :class:`ViewFields` or :class:`ClearanceFields` as it is), read per set the way
     :func:`local_maps` reads a layer per view: one store an env, one per set, or the one the layer's ``field`` (N, P) names. A byte
     source qualifies a cell where ``(byte != 0) == where``; a float32 source holding D where ``lo <= D <= hi`` (both required
     then, both ends in; a NaN never qualifies) - a band of a distance field is a goal at a chosen walking distance, reachable by
@@ -1227,3 +1231,175 @@ def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
     result = Basins(fields, ids, n_ids, new((size,), torch.int32, -1), new(shape + (n_ids,), torch.int32, 0) if n_ids else None,
                     new(shape, torch.int32, 0), new(shape, torch.int32, 0) if passes else None)
     return result.update(mask)
+
+
+#: the most body sizes one :func:`clearance_fields` call grids for
+CLEARANCE_MAX_RADII = 8
+_CLEAR_TILE = 16
+
+
+def _range(max_range):
+    if not isinstance(max_range, (int, float)) or isinstance(max_range, bool) or not (0 < max_range < float('inf')):
+        raise RuntimeError(f'max_range must be a positive number; got {max_range}')
+    return float(max_range)
+
+
+class ClearanceFields:
+    """Result of :func:`clearance_fields`: how much room there is at every cell of the grid. ``values``: flat float32, a value a cell in
+    ``grid.free``'s layout - the distance from the cell's centre to the nearest static wall within ``max_range`` metres, +inf where
+    there is none: a float layer of one store as it is (:func:`cell_draws`' band, :func:`map_channel`'s source). ``nearest``: flat
+    int32 or None, that wall's env-local line index (:func:`overhead`'s ``indices``), -1 without one. ``fits``: flat uint8 or None,
+    ``K = len(radii)`` stores an env in the fields' layout - store (n, k) at ``K*grid.starts[n] + k*nx*ny`` - byte k 1 where a body
+    of radius ``radii[k]`` fits, exactly the ``free`` byte of ``nav_grid(scenery, cell, clearance=radii[k])``: ``marks`` for
+    :func:`regions` and :func:`seeded_fields` (``n_fields=K``), ``cell_layer(clear.fits, n_fields=K)``. The scenery is kept by
+    reference: :meth:`update` reads its walls as they stand. The rule: include/megastep_hip.h (``MsNavClearance``), DESIGN.md 3.23."""
+
+    def __init__(self, grid, scenery, max_range, radii, values, nearest, fits):
+        self.grid, self.scenery, self.max_range, self.radii = grid, scenery, float(max_range), tuple(float(r) for r in radii)
+        self.values, self.nearest, self.fits = values, nearest, fits
+        geom = grid._host_geom.astype('int64')
+        self._max_tiles = max(int((((geom[:, 2] + _CLEAR_TILE - 1)//_CLEAR_TILE)*((geom[:, 3] + _CLEAR_TILE - 1)//_CLEAR_TILE)).max(initial=0)), 1)
+
+    def image(self, e):
+        """(ny, nx) float32 view of env ``e``'s distances, row 0 at the lowest y."""
+        return _store_view(self.grid, self.values, 1, e, 0)
+
+    def nearest_image(self, e):
+        """(ny, nx) int32 view of env ``e``'s nearest walls, row 0 at the lowest y."""
+        if self.nearest is None:
+            raise RuntimeError('these clearance fields keep no nearest wall (nearest=False)')
+        return _store_view(self.grid, self.nearest, 1, e, 0)
+
+    def fits_image(self, e, k=0):
+        """(ny, nx) bool view of where a body of ``radii[k]`` fits in env ``e``, row 0 at the lowest y."""
+        if self.fits is None:
+            raise RuntimeError('these clearance fields keep no fits (radii=None)')
+        if not 0 <= k < len(self.radii):
+            raise RuntimeError(f'k must be in 0..{len(self.radii) - 1}; got {k}')
+        return _store_view(self.grid, self.fits.view(torch.bool), len(self.radii), e, k)
+
+    def update(self, mask=None):
+        """Computes the envs marked in the (N,) bool ``mask`` (default all) again in place, from the scenery's walls as they stand;
+        the others keep their stores. One launch, no host synchronisation, nothing allocated: the call can be captured in a HIP
+        graph."""
+        grid = self.grid
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != (grid.n_envs,):
+                raise RuntimeError(f'mask must be an (N,) = ({grid.n_envs},) bool tensor')
+            mask = mask.contiguous()
+        dev = _require_gpu(self.values, grid.free, *_some(self.nearest, self.fits, mask))
+        if self.scenery._device() != dev:
+            raise RuntimeError(f'all tensors must live on one device; got {self.scenery._device()} and {dev}')
+        radii = (C.c_float*8)(*self.radii)
+        spec = _lib.MsNavClearance(self.max_range, len(self.radii), radii, self._max_tiles, _ptr(mask), self.values.data_ptr(), _ptr(self.nearest),
+                                   _ptr(self.fits))
+        _launch(dev, 'clearance', grid, spec, self.scenery._as_struct())
+        return self
+
+    def nav_grid(self, k=0):
+        """The :class:`NavGrid` of body size ``radii[k]``: this grid's geometry, ``free`` a compact copy of store ``k`` of ``fits`` and
+        ``clearance = radii[k]`` - what ``nav_grid(scenery, cell, clearance=radii[k])`` gives, byte for byte, without another pass
+        over the walls. Raises unless ``cell <= 1.4*radii[k]`` (:func:`nav_grid`'s own condition)."""
+        import numpy as np
+        if self.fits is None:
+            raise RuntimeError('these clearance fields keep no fits (radii=None)')
+        if not isinstance(k, int) or not 0 <= k < len(self.radii):
+            raise RuntimeError(f'k must be an integer in 0..{len(self.radii) - 1}; got {k}')
+        grid, r, n_radii = self.grid, self.radii[k], len(self.radii)
+        if np.float32(grid.cell) > np.float32(1.4)*np.float32(r):
+            raise RuntimeError(f'cell ({grid.cell}) must be at most 1.4 x clearance ({r}): a coarser grid could step through a wall')
+        dev = self.fits.device
+        starts = grid._host_starts
+        counts = torch.as_tensor(starts[1:] - starts[:-1], device=dev)
+        first = torch.as_tensor(starts[:-1], device=dev)
+        env = torch.repeat_interleave(torch.arange(grid.n_envs, device=dev), counts, output_size=grid.n_cells)
+        at = torch.arange(grid.n_cells, device=dev) + (n_radii - 1)*first[env] + k*counts[env]
+        free = torch.zeros_like(grid.free)
+        free[:grid.n_cells] = self.fits[at]
+        return NavGrid(grid.geom, grid.starts, free, grid.cell, r, grid._host_geom, grid._host_starts)
+
+
+def clearance_fields(grid, scenery, max_range=2., nearest=False, radii=None, mask=None, out=None):
+    """How much room there is: for every cell of the :func:`nav_grid` the distance from its centre to the nearest STATIC wall of
+    ``scenery`` within ``max_range`` metres (+inf beyond) - the point-to-segment rule :func:`nav_grid` and :func:`overhead` test
+    against a threshold, its minimum kept. The agents' own lines are not looked at: the grid is the building. See
+    :class:`ClearanceFields`: ``values`` is a float layer - ``cell_draws(grid, clear, 1, 64, lo=.5, hi=inf)`` draws spawns half a
+    metre from any wall, ``map_channel(clear, scale=1/max_range)`` shows the policy a distance-to-obstacle channel.
+    ``nearest=True`` also keeps which wall it is. ``radii``: up to 8 body sizes (metres, each at most ``max_range``); then ``fits``
+    holds, per size, the free byte :func:`nav_grid` would compute at that clearance - a scenery gridded for several bodies from one
+    pass over the walls (:meth:`ClearanceFields.nav_grid`).
+
+    One launch, a workgroup per 16 x 16 tile of cells: the env's walls culled against the tile into LDS, culled again against what
+    each wave has found so far; exact - every operation is binary32 in a fixed order (include/megastep_hip.h, ``MsNavClearance``;
+    DESIGN.md 3.23) and the kernel computes the rule bit for bit.
+
+    ``mask`` (N,) bool: compute only the marked envs (the others keep what ``out`` held; +inf, -1 and 1 without ``out``); ``out``:
+    the :class:`ClearanceFields` of an earlier call with the same grid, kinds of outputs and number of radii to write into - it
+    takes this call's arguments. No host synchronisation: the call can be captured in a HIP graph."""
+    import numpy as np
+    max_range = _range(max_range)
+    radii = () if radii is None else tuple(float(r) for r in radii)
+    if len(radii) > CLEARANCE_MAX_RADII:
+        raise RuntimeError(f'at most {CLEARANCE_MAX_RADII} radii; got {len(radii)}')
+    for r in radii:
+        if not (r > 0 and np.float32(r) <= np.float32(max_range)):
+            raise RuntimeError(f'every radius must be positive and at most max_range ({max_range}); got {r}')
+    if not hasattr(scenery, 'lines') or len(scenery.lines) != grid.n_envs:
+        raise RuntimeError(f'scenery must be the Scenery the grid was laid over: {grid.n_envs} envs')
+    if out is not None:
+        if not isinstance(out, ClearanceFields) or out.grid is not grid or (out.nearest is not None) != bool(nearest) or len(out.radii) != len(radii):
+            raise RuntimeError('`out` must come from a clearance_fields call with the same grid, use of nearest and number of radii')
+        out.scenery, out.max_range, out.radii = scenery, max_range, radii
+        return out.update(mask)
+    new = _new(_require_gpu(grid.free))
+    size = max(grid.n_cells, 1)
+    result = ClearanceFields(grid, scenery, max_range, radii, new((size,), torch.float32, float('inf')),
+                             new((size,), torch.int32, -1) if nearest else None, new((len(radii)*size,), torch.uint8, 1) if radii else None)
+    return result.update(mask)
+
+
+class Clearance:
+    """Result of :func:`clearance`: ``distances`` (N, P) float32 - from each point to the nearest line within ``max_range``, +inf
+    without one; ``nearest`` (N, P) int32 - that line's env-local index (below ``n_agents*n_model``: an agent's), -1 without one;
+    ``towards`` (N, P, 2) float32 - the unit vector from the point to the nearest point of that line, (0, 0) on the line and
+    without one."""
+
+    def __init__(self, distances, nearest, towards):
+        self.distances, self.nearest, self.towards = distances, nearest, towards
+
+
+def clearance(scenery, points, max_range=2., agents=None, skip=None, mask=None, out=None):
+    """A proximity reading at arbitrary points: for ``points`` (N, P, 2) float32 world points - no grid is needed - how near the
+    nearest static wall of the point's env within ``max_range`` metres is, which line it is and in which direction it lies
+    (:class:`Clearance`). With ``agents`` the agents' bodies count too, at their current poses; ``skip`` (N, P) integers names the
+    agent whose own body each point passes over (-1, or anything else outside 0..A-1: none) - with the agents' positions as points
+    and ``skip`` the agent's own number, every agent reads how near the nearest thing that is not itself is.
+
+    One launch, one wave a point, exact: the rule of :func:`clearance_fields` (include/megastep_hip.h, ``MsNavClearQuery``;
+    DESIGN.md 3.23) - at a cell's centre, without agents, the field's ``values`` and ``nearest`` bit for bit.
+
+    ``mask`` (N, P) bool: compute only the marked points (the others keep what ``out`` held; +inf, -1 and 0 without ``out``);
+    ``out``: the :class:`Clearance` of an earlier call with the same shapes. No host synchronisation: the call can be captured in
+    a HIP graph."""
+    _check(points, 'points', torch.float32, 3)
+    n, p = points.shape[:2]
+    if not hasattr(scenery, 'lines') or n != len(scenery.lines) or points.shape[2] != 2 or p < 1:
+        raise RuntimeError(f'points must be (N, P, 2) with N = {len(scenery.lines)} and P >= 1; got {tuple(points.shape)}')
+    max_range = _range(max_range)
+    if agents is not None and tuple(agents.angles.shape) != (n, scenery.n_agents):
+        raise RuntimeError('agents do not match the scenery')
+    if skip is not None:
+        if agents is None:
+            raise RuntimeError('skip goes with agents: it names the agent whose own body each point passes over')
+        skip = _index(skip, 'skip', n, p)
+    mask = _mask(mask, n, p, 'P')
+    dev = _query_device(scenery, agents, points, *_some(skip, mask))
+    new = _new(dev)
+    result = _result_for(out, (n, p, dev), 'a clearance', lambda: Clearance(new((n, p), torch.float32, float('inf')), new((n, p), torch.int32, -1),
+                                                                             new((n, p, 2), torch.float32, 0.)))
+    spec = _lib.MsNavClearQuery(n, p, points.data_ptr(), _ptr(skip), max_range, _ptr(mask), result.distances.data_ptr(), result.nearest.data_ptr(),
+                                result.towards.data_ptr())
+    with _on(dev):
+        _lib.check(_lib.lib().ms_nav_clear_query(C.byref(scenery._as_struct()), C.byref(agents._plain) if agents is not None else None,
+                                                 C.byref(spec), _stream(dev)))
+    return result

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance] [--large]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -67,6 +67,13 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       `--envs` x 1 points; FloorCoverage(envs, n_agents=2, shared=True): expert('split') + step() eager and replayed as a HIP
       graph, next to expert() + step(); and FloorCoverage(64, n_agents=2, shared=True), 300 steps, in one run under
       expert('split'), expert('frontier') and uniformly random actions: episodes ended by coverage and mean final fraction.
+  (c2) clearance, at `--envs` envs and R = 2: one cuda.clearance_fields (ms_nav_clearance) with values alone and with nearest and
+      three radii, for BOTH instantiations of its kernel (the tile cull alone; the tile cull and the wave's own: ms_debug_nav_clear_cull);
+      next to them cuda.nav_grid's ms_nav_free launch on the same grid (brute force over the same (cell, wall) pairs) and the torch
+      formulation of the same rule (the grids padded to the largest plan, the walls padded to the most an env has, a loop over the
+      wall index; the first `--torch-envs` envs, scaled; values and nearest compared for equality); one cuda.clearance of
+      `--envs` x 4 points with four agents an env; modules.Proximity eager and replayed as a HIP graph, next to modules.IMU.
+      `--large` draws the large plans instead.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -451,6 +458,45 @@ def torch_views(grid, scenery, points, R, countable, maps, slot, envs):
     return run
 
 
+def torch_clearance(grid, scenery, R, envs):
+    """ms_nav_clearance's rule for the first `envs` envs by tensor ops: (envs, H, W) binary32 tensors padded to the largest grid, the
+    walls padded to the most an env has with NaN rows (never a candidate), a loop over the wall index in ascending order (so a
+    strict `<` keeps the tie rule).  Returns run() -> (values, nearest)."""
+    dev = grid.free.device
+    geom = grid._host_geom[:envs]
+    H, W = int(geom[:, 3].max()), int(geom[:, 2].max())
+    c = torch.tensor(grid.cell, dtype=torch.float32, device=dev)
+    g = torch.as_tensor(geom, device=dev)
+    x = (((g[:, 0, None] + torch.arange(W, device=dev)).float() + .5)*c)[:, None, :]
+    y = (((g[:, 1, None] + torch.arange(H, device=dev)).float() + .5)*c)[:, :, None]
+    lines = scenery.lines
+    af = scenery.n_agents*scenery.model.shape[0]
+    vals, starts, widths = lines.vals.reshape(-1, 4), lines.starts.cpu().numpy(), lines.widths.cpu().numpy()
+    most = int((widths[:envs] - af).max())
+    rows = torch.full((envs, most, 4), float('nan'), dtype=torch.float32, device=dev)
+    for e in range(envs):
+        rows[e, :widths[e] - af] = vals[starts[e] + af:starts[e] + widths[e]]
+    R2 = torch.tensor(R, dtype=torch.float32, device=dev)**2
+    zero, one = torch.zeros((), device=dev), torch.ones((), device=dev)
+
+    def run():
+        bd = torch.full((envs, H, W), float('inf'), device=dev)
+        bi = torch.full((envs, H, W), -1, dtype=torch.int32, device=dev)
+        for l in range(most):
+            ax, ay, bx, by = (rows[:, l, k][:, None, None] for k in range(4))
+            vx, vy, px, py = bx - ax, by - ay, x - ax, y - ay
+            vv = vx*vx + vy*vy
+            t = torch.where(vv > 0, (px*vx + py*vy)/vv, zero)
+            t = torch.where(t < 0, zero, torch.where(t > 1, one, t))
+            dx, dy = px - t*vx, py - t*vy
+            d2 = dx*dx + dy*dy
+            take = (d2 <= R2) & (d2 < bd)
+            bd = torch.where(take, d2, bd)
+            bi = torch.where(take, l + af, bi)
+        return torch.where(bi >= 0, bd.sqrt(), torch.full_like(bd, float('inf'))), bi
+    return run
+
+
 def coverage_score(env, steps, policy, seed=1):
     """(episodes ended by coverage, by lifespan, mean final fraction over all episodes) of `steps` steps of a FloorCoverage under
     expert(policy), or uniformly random actions."""
@@ -516,14 +562,15 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance'))
+    ap.add_argument('--large', action='store_true')
     ap.add_argument('--json')
     args = ap.parse_args()
     from megastep_amd import core, cubicasa, cuda, modules, scene
     from megastep_amd.demo import Explorer, FloorCoverage, PointGoal
 
     np.random.seed(0); torch.manual_seed(0)
-    pool = cubicasa.sample(args.distinct, split='all', n_unique=args.distinct, workers=16, context='subprocess')
+    pool = cubicasa.sample(args.distinct, split='all', n_unique=args.distinct, workers=16, context='subprocess', **(dict(large=True) if args.large else {}))
     geoms = [pool[i % len(pool)] for i in range(args.envs)]
     out = dict(envs=args.envs, distinct=len(pool))
     want = lambda part: args.only in (None, part)
@@ -962,6 +1009,64 @@ def main():
             env = FloorCoverage(64, n_agents=2, shared=True, geometries=small, max_lifespan=300)
             out['shared_coverage_' + policy] = score = coverage_score(env, 300, policy)
             print(f'(z) FloorCoverage(64, n_agents=2, shared=True), 300 steps, {policy}: {score}')
+
+    if want('clearance'):
+        from megastep_amd import _lib, nav
+        R, radii = 2., (core.AGENT_RADIUS, .2, .3)
+        sc = scene.scenery(geoms, 1, device='cuda', bake=False)
+        grid = cuda.nav_grid(sc, clearance=core.AGENT_RADIUS)
+        cells = np.diff(grid._host_starts)
+        walls = sc.lines.widths.cpu().numpy() - sc.model.shape[0]
+        shape = dict(cells_total=int(grid.n_cells), cells_largest=int(cells.max()), cells_median=int(np.median(cells)), walls_most=int(walls.max()),
+                     walls_median=int(np.median(walls)), max_range=R)
+        h = _lib.lib()
+        bare = cuda.clearance_fields(grid, sc, R)
+        full = cuda.clearance_fields(grid, sc, R, nearest=True, radii=radii)
+        try:
+            for mode, name in ((1, 'tile'), (2, 'tile_wave')):
+                h.ms_debug_nav_clear_cull(mode)
+                for clear, kind in ((bare, 'values'), (full, 'all')):
+                    med, lo, hi = timed(lambda: clear.update(), 20, args.warmup)
+                    out[f'clearance_{name}_{kind}'] = dict(seconds=med, min=lo, max=hi, **shape)
+                    print(f'(c2) clearance_fields, {name} cull, {kind}: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]')
+        finally:
+            h.ms_debug_nav_clear_cull(-1)
+        med, lo, hi = timed(lambda: nav._launch(grid.free.device, 'free', grid, None, sc._as_struct()), 20, args.warmup)
+        out['clearance_nav_free'] = dict(seconds=med, min=lo, max=hi)
+        print(f'(c2) ms_nav_free on the same grid: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]')
+        k = min(args.torch_envs, args.envs)
+        run = torch_clearance(grid, sc, R, k)
+        V, I = run()
+        same = all(torch.equal(V[e, :grid.cells(e)[1], :grid.cells(e)[2]].view(torch.int32), full.image(e).view(torch.int32)) and
+                   torch.equal(I[e, :grid.cells(e)[1], :grid.cells(e)[2]], full.nearest_image(e)) for e in range(k))
+        tmed = timed(lambda: run(), 2, 1)[0]
+        out['clearance_torch'] = dict(envs=k, seconds=tmed, scaled_seconds=tmed*args.envs/k, equal_bits=bool(same))
+        print(f'(c2) torch loop over walls, {k} grids: {tmed*1e3:.1f} ms -> {tmed*args.envs/k*1e3:.1f} ms for {args.envs}; equal bits: {same}')
+        del sc, grid, bare, full, run, V, I
+        torch.cuda.empty_cache()
+        sc = scene.scenery(geoms, 4, device='cuda', bake=False)
+        c = core.Core(sc, res=64)
+        c.agents.positions[:] = torch.as_tensor(modules.random_empty_positions(geoms, 4, 1), dtype=torch.float32, device='cuda')[:, :, 0]
+        own = torch.arange(4, dtype=torch.int32, device='cuda').expand(args.envs, 4).contiguous()
+        reading = cuda.clearance(sc, c.agents.positions, R, agents=c.agents, skip=own)
+        med, lo, hi = timed(lambda: cuda.clearance(sc, c.agents.positions, R, agents=c.agents, skip=own, out=reading), 5*args.repeats, args.warmup)
+        out['clearance_query'] = dict(seconds=med, min=lo, max=hi, points=4*args.envs, in_range=float(torch.isfinite(reading.distances).float().mean()))
+        print(f'(c2) clearance, {args.envs} x 4 points with agents: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        for name, module in (('Proximity', modules.Proximity(c, R)), ('IMU', modules.IMU(c))):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                module()
+            torch.cuda.current_stream().wait_stream(side)
+            eager = timed(lambda: module(), 5*args.repeats, args.warmup)[0]
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                module()
+            graphed = timed(lambda: g.replay(), 5*args.repeats, args.warmup)[0]
+            out[f'clearance_{name}'] = dict(eager_seconds=eager, graph_seconds=graphed, envs=args.envs, agents=4)
+            print(f'(c2) modules.{name}({args.envs} x 4): eager {eager*1e6:.1f} us, graph replay {graphed*1e6:.1f} us')
+        del sc, c
+        torch.cuda.empty_cache()
 
     if args.json:
         with open(args.json, 'w') as f:
