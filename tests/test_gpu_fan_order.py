@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from tests import util
-from tests.test_fan_order_host import SORT_MAX, klass, runs
+from tests.test_fan_order_host import assert_order_follows_the_rule, klass
 
 pytestmark = pytest.mark.gpu
 
@@ -90,17 +90,12 @@ def _assert_equal(ref, got, what):
 
 
 def _check_order_on_device(c):
-    """After a physics step: every XCD's run of `order` is a permutation of the run's fans, and every sort wave's share of its slots
-    - every K-th, K waves a run - has its classes descending."""
+    """After a physics step: the order row is, class for class and share for share, the rule's for the costs row next to it
+    (tests/test_fan_order_host.py, order_rule) - every slot written, every sort wave's share of the slots a permutation of its own
+    fans, the classes' sequence the rule's."""
     costs, order = (t.cpu().numpy() for t in c.agents._schedule)
-    cls = klass(costs)
-    per_run = -(-max(length for _, length in runs(len(costs)))//SORT_MAX)
-    for first, length in runs(len(costs)):
-        got = order[first:first + length]
-        assert sorted(got.tolist()) == list(range(first, first + length))
-        for k in range(per_run):
-            assert (np.diff(cls[got[k::per_run]]) <= 0).all()
-    return cls
+    assert_order_follows_the_rule(costs, order, what=f'{len(costs)} fans')
+    return klass(costs)
 
 
 @pytest.mark.parametrize('n_envs, n_agents', [(4096, 4), (4096, 1)], ids=['headline', 'c2'])
@@ -131,6 +126,7 @@ def test_the_order_changes_no_bit(n_envs, n_agents):
 
 def _check_order_on_device_after_a_step(c):
     from megastep_amd import cuda
+    c.agents._schedule[1].fill_(-12345)          # (no slot may keep it)
     cuda.physics(c.scenery, c.agents)            # (sorts what the last render left)
     torch.cuda.synchronize()
     return _check_order_on_device(c)
