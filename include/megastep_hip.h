@@ -590,6 +590,75 @@ int ms_nav_seed_fields(const MsNavGrid* grid, const MsNavSeedFields* fields, voi
 int ms_nav_seed_waypoints(const MsNavGrid* grid, const MsNavSeedWaypoints* waypoints, void* hip_stream);
 int ms_nav_seed_paths(const MsNavGrid* grid, const MsNavSeedPaths* paths, void* hip_stream);
 
+/* Cost fields: seeded fields over per-cell cost layers - an inflation layer that keeps paths off the walls, unseen floor priced
+ * instead of forbidden, cells an opponent sees or another agent's territory made dear.  Grid, seeds (marks, where, among), graph
+ * and corner rule are MsNavSeedFields' as they stand; tests/test_navcost_host.py restates the rule in numpy (cost_rule) and the
+ * kernels - and their host instantiations, ms_host_nav_cost_field / _waypoint / _path - are held to EQUALITY with it.
+ *   costs         a float per cell: one store per env in free_cells' layout (n_costs == 1: env n's nx*ny floats from starts[n],
+ *                 shared by its fields) or one per field in the fields' layout (n_costs == n_fields: field (n, g)'s from
+ *                 G*starts[n] + g*nx*ny).  Read when the call runs, not kept.
+ *   multiplier    of cell v, from x = costs[v] in binary32: k_v = x >= 1.f ? fminf(x, 256.f) : (x < 1.f ? 1.f : 256.f) - values
+ *                 below 1 count as 1, +inf counts as 256 (NAV_COST_MAX), and a NaN is the dearest, not the cheapest.  No cost
+ *                 closes a cell: which cells are free, which diagonals are open and what a waypoint's sight crosses are untouched.
+ *   weights       a step from v to a neighbour, towards the seeds, costs ws_v = fl(c*k_v) when straight and
+ *                 wd_v = fl(fl(c*1.41421356f)*k_v) when diagonal: the weight depends on the cell being LEFT and on the kind of
+ *                 step only.  Multiplying by 1.f is exact: k = 1 everywhere gives MsNavSeedFields' weights, and its bits.
+ *   field         D[seed] = +0.f whatever the seed's own cost, then the least fixed point of
+ *                 D[v] = min(D[v], fl(min over straight u of D[u] + ws_v), fl(min over open diagonal u of D[u] + wd_v)).
+ *                 x -> fl(x + w) is monotone for every w, so the min may be taken first, every value is the left-to-right
+ *                 binary32 sum along a path from some seed, and the fixed point does not depend on the order of relaxation: it
+ *                 is what a multi-source Dijkstra with binary32 additions over these directed weights returns, as bits.
+ *   following     MsNavSeedFields' rule with the weights of the cell the hop leaves: from v the first of the eight neighbours,
+ *                 in MsNavWaypoints' order, that attains the least fl(D[u] + w_t(v)), provided D[u] < D[v]; the chain ends on
+ *                 D == 0.f.  Start, sight, look-ahead, the base index and the paths' counts: unchanged.
+ *   query         ms_nav_query serves a cost field as it is: the leg from a point to its anchor's centre, under a cell long,
+ *                 is charged at 1, whatever the cells under it cost.
+ *   strictness    a hop needs fl(D + w) > D, which holds while D < c*2^24; with k <= 256 that is so for chains of fewer than
+ *                 about 46 000 hops at the maximal cost - more cells than the largest LDS tier holds.  Beyond that a chain is
+ *                 reported broken (NaN waypoint, negated count), as a stale field is today.  Nothing hangs.
+ * One launch each; masked-out fields keep fields, passes and n_seeds as they are.  Nothing is allocated, nothing waits: all can
+ * be captured in a HIP graph.  Every argument is checked in full before the launch (MS_EINVAL): what the seeded entries refuse,
+ * a NULL or misaligned costs, an n_costs that is neither 1 nor the number of fields. */
+typedef struct MsNavCostFields {
+    int                  n_fields;     /* G: fields per env                                                            */
+    const unsigned char* marks;        /* as MsNavSeedFields.marks                                                     */
+    int                  where;        /* 0 or 1: a seed's mark                                                        */
+    const unsigned char* among;        /* as MsNavSeedFields.among, or NULL                                            */
+    const unsigned char* mask;         /* (N, G) non-zero: compute this field; NULL: all.  Read on the device only.    */
+    float*               fields;       /* G*starts[N] floats out                                                       */
+    int*                 passes;       /* (N, G) or NULL                                                               */
+    int*                 n_seeds;      /* (N, G) or NULL                                                               */
+    const float*         costs;        /* n_costs*starts[N] floats; 4-byte aligned                                     */
+    int                  n_costs;      /* 1: a store per env; G: a store per field                                     */
+} MsNavCostFields;
+typedef struct MsNavCostWaypoints {    /* MsNavSeedWaypoints and the costs the fields were made with                   */
+    int                  n_points;
+    const float*         points;       /* (N, P, 2); 8-byte aligned                                                    */
+    const int*           goal;         /* (N, P) which of the env's fields each point follows; NULL: P == G            */
+    const float*         fields;       /* as MsNavCostFields.fields                                                    */
+    int                  n_goals;      /* G of `fields`                                                                */
+    int                  lookahead;    /* L, 1..64                                                                     */
+    float*               waypoints;    /* (N, P, 2) out; 8-byte aligned                                                */
+    int*                 hops;         /* (N, P) out, or NULL                                                          */
+    const float*         costs;        /* as MsNavCostFields.costs                                                     */
+    int                  n_costs;      /* 1 or G                                                                       */
+} MsNavCostWaypoints;
+typedef struct MsNavCostPaths {        /* MsNavSeedPaths and the costs the fields were made with                       */
+    int                  n_points;
+    const float*         points;       /* (N, P, 2); 8-byte aligned                                                    */
+    const int*           goal;         /* (N, P) or NULL, as above                                                     */
+    const float*         fields;
+    int                  n_goals;
+    int                  max_points;   /* M >= 2                                                                       */
+    float*               paths;        /* (N, P, M, 2) out                                                             */
+    int*                 counts;       /* (N, P) out                                                                   */
+    const float*         costs;        /* as MsNavCostFields.costs                                                     */
+    int                  n_costs;      /* 1 or G                                                                       */
+} MsNavCostPaths;
+int ms_nav_cost_fields(const MsNavGrid* grid, const MsNavCostFields* fields, void* hip_stream);
+int ms_nav_cost_waypoints(const MsNavGrid* grid, const MsNavCostWaypoints* waypoints, void* hip_stream);
+int ms_nav_cost_paths(const MsNavGrid* grid, const MsNavCostPaths* paths, void* hip_stream);
+
 /* Seen maps: which cells of the nav grid the depth rays of an agent (of any viewer) have passed over - floor coverage for
  * exploration rewards, a mask to hand a policy or to draw.  As above every step is one binary32 operation in the order given,
  * without contraction, divisions and roots correctly rounded; tests/test_navseen_host.py restates it in numpy (seen_rule) and

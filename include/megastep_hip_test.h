@@ -89,6 +89,23 @@ int ms_host_nav_seed_path(const int* geom, float cell, const unsigned char* free
 /* ms_host_nav_field_capacity writes the three capacities, in framed cells, of nav_relax_kernel's instantiations (single-goal and
  * seeded alike): MS_OK, or MS_EINVAL for NULL. */
 int ms_host_nav_field_capacity(int* capacities);
+/* Host instantiations of the cost fields (MsNavCostFields) for ONE env on HOST arrays: ms_host_nav_seed_field / _waypoint / _path
+ * with `costs` (ny x nx floats: one field's) - the kernel's own multiplier and weights, a cell's multiplier kept beside the framed
+ * copy (framed != 0, as the kernel's LDS variant keeps it) or read from `costs` every sweep (the global-memory path, and the other
+ * variant); the followers hop with the weights of the cell they leave.  Returns as the seeded hooks', -1 also for NULL costs.
+ * ms_host_nav_cost_capacity writes the three capacities, in framed cells, of the instantiations that keep the multipliers in LDS
+ * (a float, a float and a byte a cell): MS_OK, or MS_EINVAL for NULL.
+ * ms_debug_nav_cost_variant: where ms_nav_cost_fields' launch keeps the multipliers - 0 = read from global memory every pass (the
+ * seeded kernel's capacities, ms_host_nav_field_capacity), 1 = in LDS (ms_host_nav_cost_capacity); -1 = the library's own choice;
+ * anything else: MS_EINVAL.  Per calling thread; A/B runs and tests - every setting produces the same bits. */
+int ms_host_nav_cost_field(const int* geom, float cell, const unsigned char* free_cells, const unsigned char* marks, int where,
+                           const unsigned char* among, const float* costs, int framed, float* D, int* n_seeds);
+int ms_host_nav_cost_waypoint(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* costs,
+                              const float* point, int lookahead, float* waypoint);
+int ms_host_nav_cost_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* costs,
+                          const float* point, int max_points, float* points);
+int ms_host_nav_cost_capacity(int* capacities);
+int ms_debug_nav_cost_variant(int variant);
 /* Host instantiation of the seen maps' rule (kernels/navseen.h: the ray, the sample - the very functions every lane of
  * nav_seen_kernel evaluates) for ONE env on HOST arrays, one call of ms_nav_seen: geom = (jx0, iy0, nx, ny), countable
  * (ny x nx bytes), origins (P, 2), dirs (P, R, 2), distances (P, R), slot (P) or NULL (then P == S), reset (S) or NULL, maps

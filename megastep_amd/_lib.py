@@ -131,6 +131,18 @@ class MsNavSeedPaths(C.Structure):
                 ('max_points', C.c_int), ('paths', C.c_void_p), ('counts', C.c_void_p)]
 
 
+class MsNavCostFields(C.Structure):
+    _fields_ = MsNavSeedFields._fields_ + [('costs', C.c_void_p), ('n_costs', C.c_int)]
+
+
+class MsNavCostWaypoints(C.Structure):
+    _fields_ = MsNavSeedWaypoints._fields_ + [('costs', C.c_void_p), ('n_costs', C.c_int)]
+
+
+class MsNavCostPaths(C.Structure):
+    _fields_ = MsNavSeedPaths._fields_ + [('costs', C.c_void_p), ('n_costs', C.c_int)]
+
+
 class MsNavSeen(C.Structure):
     _fields_ = [('n_maps', C.c_int), ('n_viewers', C.c_int), ('n_rays', C.c_int), ('origins', C.c_void_p), ('dirs', C.c_void_p),
                 ('distances', C.c_void_p), ('slot', C.c_void_p), ('max_range', C.c_float), ('reset', C.c_void_p), ('countable', C.c_void_p),
@@ -246,6 +258,9 @@ PROTOTYPES = {
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
     'ms_nav_seed_waypoints': (_int, [_p(MsNavGrid), _p(MsNavSeedWaypoints), _ptr]),
     'ms_nav_seed_paths': (_int, [_p(MsNavGrid), _p(MsNavSeedPaths), _ptr]),
+    'ms_nav_cost_fields': (_int, [_p(MsNavGrid), _p(MsNavCostFields), _ptr]),
+    'ms_nav_cost_waypoints': (_int, [_p(MsNavGrid), _p(MsNavCostWaypoints), _ptr]),
+    'ms_nav_cost_paths': (_int, [_p(MsNavGrid), _p(MsNavCostPaths), _ptr]),
     'ms_wallgrid_scan': (_int, [_p(MsScenery), _p(MsWallGridParent), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr]),
     'ms_wallgrid_fill': (_int, [_p(MsScenery), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # the test hooks
@@ -270,6 +285,11 @@ PROTOTYPES = {
     'ms_host_nav_seed_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_seed_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_field_capacity': (_int, [_ptr]),
+    'ms_host_nav_cost_field': (_int, [_ptr, _flt, _ptr, _ptr, _int, _ptr, _ptr, _int, _ptr, _ptr]),
+    'ms_host_nav_cost_waypoint': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_host_nav_cost_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    'ms_host_nav_cost_capacity': (_int, [_ptr]),
+    'ms_debug_nav_cost_variant': (_int, [_int]),
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
     'ms_host_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows)]),
     'ms_host_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws)]),

@@ -24,10 +24,18 @@
 //                      one runs the same relaxation on the field in global memory - slower, the same bits.
 //                      SEEDED (MsNavSeedFields): the sources are a set of cells at +0.f instead of a goal's
 //                      anchors at their legs - the fill, the passes and the store are the single-goal kernel's.
+//                      COST (MsNavCostFields), seeded only: the weights of a cell are c and c*1.41421356f times
+//                      the cell's own multiplier k_v (nav_cost_multiplier of its cost) - only the per-cell weights differ.  Two
+//                      variants of where k_v lives: NAV_COST_GLOBAL reads the cost every pass, by the cell's own lane, and
+//                      keeps the seeded kernel's 5 bytes a cell and its tiers; NAV_COST_LDS keeps k_v in LDS beside the value
+//                      and the byte, 9 bytes a cell (nav_cost_capacity).  Both give the same bits.
 //   nav_query_kernel   one lane a point: the point's (at most four) anchors gathered from its field.
 constexpr int NAV_LDS_SMALL = 40*1024, NAV_LDS_MEDIUM = 80*1024, NAV_LDS_LARGE = 160*1024;
 constexpr int nav_capacity(const int lds_bytes) { return (lds_bytes - 64)/5/4*4; }      // framed cells: a float and a byte each
+constexpr int nav_cost_capacity(const int lds_bytes) { return (lds_bytes - 64)/9/4*4; } // ... and the cell's multiplier, a float
 constexpr float NAV_DIAGONAL = 1.41421356f;
+constexpr float NAV_COST_MAX = 256.f;
+constexpr int NAV_UNWEIGHTED = 0, NAV_COST_GLOBAL = 1, NAV_COST_LDS = 2;       // nav_relax_kernel's COST
 constexpr float NAV_INDEX_LIMIT = 1073741824.f;      // |floorf(x/c - .5f)| at or beyond 2^30 (or a NaN): the point has no anchor
 
 struct NavArgs {                                     // MsNavGrid, checked
@@ -149,6 +157,8 @@ struct NavFieldArgs {
     const unsigned char* among;                      //   a byte a cell (free_cells' layout) or NULL
     int where;                                       //   0 or 1: the value of a seed's mark
     int* n_seeds;                                    //   (N, G) or NULL: the seeds of every computed field
+    const float* costs;                              // cost fields only: a float a cell, free_cells' layout (n_costs 1) or the
+    int n_costs;                                     //   fields' (n_costs n_goals)
 };
 
 // The per-cell pieces of the relaxation are __host__ __device__ functions over plain pointers: ms_host_nav_seed_field sweeps
@@ -159,6 +169,14 @@ struct NavFieldArgs {
 __host__ __device__ inline float nav_relaxed(const float d, const float straight, const float diagonal, const float ws, const float wd) {
     return fminf(d, fminf(straight + ws, diagonal + wd));
 }
+
+// The multiplier of a cell from its cost (MsNavCostFields): below 1 counts as 1, above NAV_COST_MAX - +inf too - as that, and a
+// NaN is the dearest, not the cheapest.
+__host__ __device__ inline float nav_cost_multiplier(const float x) { return x >= 1.f ? fminf(x, NAV_COST_MAX) : (x < 1.f ? 1.f : NAV_COST_MAX); }
+
+// The weights of a step out of a cell of multiplier k towards the seeds: fl(c k) straight, fl(fl(c 1.41421356f) k) diagonal -
+// times 1.f is exact, so k = 1 gives the unweighted weights' bits.
+__host__ __device__ inline void nav_cost_weights(const float c, const float k, float& ws, float& wd) { ws = c*k; wd = (c*NAV_DIAGONAL)*k; }
 
 // Is cell k of its env a seed (MsNavSeedFields): free, among the cells that may be one, its mark's bit 0 equal to `where`.
 __host__ __device__ inline bool nav_is_seed(const unsigned char* fr, const unsigned char* among, const unsigned char* marks, const long long k,
@@ -209,11 +227,13 @@ __host__ __device__ inline float nav_cell_stored(const float* out, const unsigne
 // SEEDED: the field's sources are the cells nav_is_seed names (value +0.f) instead of a goal's anchors (value: their leg).  A
 // seed keeps bit 5 of its byte; the seeds are counted a wave at a time - one ballot a round, one LDS atomic a wave - into
 // s_flag[3].
-template <int LDS_BYTES, int THREADS, bool SEEDED>
+template <int LDS_BYTES, int THREADS, bool SEEDED, int COST = NAV_UNWEIGHTED>
 __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, const NavFieldArgs f) {
-    constexpr int CAP = nav_capacity(LDS_BYTES);
+    static_assert(SEEDED || COST == NAV_UNWEIGHTED, "cost fields are seeded fields");
+    constexpr int CAP = COST == NAV_COST_LDS ? nav_cost_capacity(LDS_BYTES) : nav_capacity(LDS_BYTES);
     constexpr int FLAGS = SEEDED ? 4 : 3;
     __shared__ float s_d[CAP];
+    __shared__ float s_k[COST == NAV_COST_LDS ? CAP : 1];               // (NAV_COST_LDS alone touches it)
     __shared__ unsigned char s_m[CAP];
     __shared__ int s_flag[FLAGS];
     const int tid = threadIdx.x;
@@ -233,6 +253,7 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
     float* const out = f.fields + first;
     const unsigned char* const marks = SEEDED ? f.marks + first : nullptr;
     const unsigned char* const among = SEEDED && f.among ? f.among + a.starts[e] : nullptr;
+    const float* const cost = COST != NAV_UNWEIGHTED ? f.costs + (f.n_costs == 1 ? a.starts[e] : first) : nullptr;
     const float c = a.cell, ws = c, wd = c*NAV_DIAGONAL;
     float2 p = make_float2(0.f, 0.f);
     long long i0 = 0, j0 = 0;
@@ -253,6 +274,7 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
             if constexpr (SEEDED) seed = fb && nav_is_seed(fr, among, marks, cell, f.where);
             s_d[k] = seed ? 0.f : INFINITY;
             s_m[k] = (unsigned char)(fb | (seed ? 32 : 0));
+            if constexpr (COST == NAV_COST_LDS) s_k[k] = fb ? nav_cost_multiplier(cost[cell]) : 1.f;
         }
         if (tid < FLAGS) s_flag[tid] = 0;
         __syncthreads();
@@ -274,7 +296,13 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
         passes = nav_settle<THREADS>(s_flag, n, [=](const int k) {
             const int m = s_m[k];
             if (!(m & 1)) return false;
-            const float d = nav_load(s_d + k), v = nav_cell_framed(s_d, m, k, P, d, ws, wd);
+            float w_s = ws, w_d = wd;
+            if constexpr (COST == NAV_COST_LDS) nav_cost_weights(c, s_k[k], w_s, w_d);
+            if constexpr (COST == NAV_COST_GLOBAL) {
+                const int i = k / P - 1, j = k - (i + 1)*P - 1;         // (a free framed cell is inside)
+                nav_cost_weights(c, nav_cost_multiplier(cost[(long long)i*nx + j]), w_s, w_d);
+            }
+            const float d = nav_load(s_d + k), v = nav_cell_framed(s_d, m, k, P, d, w_s, w_d);
             if (v < d) nav_store(s_d + k, v);
             return v < d;
         });
@@ -303,7 +331,9 @@ __global__ __launch_bounds__(THREADS) void nav_relax_kernel(const NavArgs a, con
         __syncthreads();
         passes = nav_settle<THREADS>(s_flag, cells, [=](const long long k) {
             if (!(fr[k] & 1)) return false;
-            const float d = nav_load(out + k), v = nav_cell_stored(out, fr, nx, ny, k, d, ws, wd);
+            float w_s = ws, w_d = wd;
+            if constexpr (COST != NAV_UNWEIGHTED) nav_cost_weights(c, nav_cost_multiplier(cost[k]), w_s, w_d);
+            const float d = nav_load(out + k), v = nav_cell_stored(out, fr, nx, ny, k, d, w_s, w_d);
             if (v < d) nav_store(out + k, v);
             return v < d;
         });

@@ -10,7 +10,7 @@
 // waypoint is the furthest of the first L points of that chain the point can see, a sight being a run of samples half a
 // cell apart whose four surrounding cells are all free.  tests/test_navpath_host.py restates all of it in numpy (path_rule).
 //
-// The rule's pieces - nav_start, nav_neighbour / nav_hop, nav_sight_samples / nav_sample_clear / nav_sight - are
+// The rule's pieces - nav_start, nav_hop_weights / nav_neighbour / nav_hop, nav_sight_samples / nav_sample_clear / nav_sight - are
 // __host__ __device__ functions over plain pointers: ms_host_nav_waypoint / ms_host_nav_path run them on host arrays, so the
 // CPU suite holds this very text to path_rule, bit for bit.
 //
@@ -22,11 +22,14 @@
 //                        them, four byte gathers each), one ballot a round; the first candidate in sight is the largest
 //                        admissible index, and the loop stops there.  Every branch is wave-uniform.
 //   nav_path_kernel      one lane a path (not hot): nav_hop to the chain's end for the count, the first M points written.
+// Both are instantiated on WEIGHTED: the fields are cost fields (MsNavCostFields) and a hop runs with the weights
+// of the cell it leaves.
 struct NavEnv {                                      // one env's grid and one of its fields: what the pieces read
     int jx0, iy0, nx, ny;
     float c;
     const unsigned char* free;                       // (ny, nx)
     const float* D;                                  // (ny, nx)
+    const float* cost = nullptr;                     // (ny, nx) a cost field's costs (MsNavCostFields); NULL: every cell at 1
 };
 struct NavGoal {                                     // the field's goal q and its anchor corner
     float x, y;
@@ -71,14 +74,20 @@ __host__ __device__ inline int nav_di(const int t) { return ((0xa19 >> 2*t) & 3)
 __host__ __device__ inline int nav_dj(const int t) { return ((0x8246 >> 2*t) & 3) - 1; }
 
 // The value fl(D[u] + w) of neighbour u = t of cell (i, j), D[u] in du; +inf (never the least: the fold replaces on <
-// from +inf) for a neighbour that does not count.
-__host__ __device__ inline float nav_neighbour(const NavEnv& g, const int i, const int j, const int t, float& du) {
+// from +inf) for a neighbour that does not count.  ws, wd: the hop's weights (nav_hop_weights).
+__host__ __device__ inline float nav_neighbour(const NavEnv& g, const int i, const int j, const int t, const float ws, const float wd, float& du) {
     const int ui = i + nav_di(t), uj = j + nav_dj(t);
     du = INFINITY;
     if (!nav_is_free(g, ui, uj)) return INFINITY;
     if (t >= 4 && !(nav_is_free(g, ui, j) && nav_is_free(g, i, uj))) return INFINITY;      // no corner is cut
     du = g.D[(long long)ui*g.nx + uj];
-    return du + (t < 4 ? g.c : g.c*NAV_DIAGONAL);
+    return du + (t < 4 ? ws : wd);
+}
+
+// The weights of a hop out of cell (i, j), formed once a hop: those of the cell the hop LEAVES - on a cost field c and
+// c*1.41421356f times its multiplier (nav_cost_weights), which a NULL cost folds to the plain ones.
+__host__ __device__ inline void nav_hop_weights(const NavEnv& g, const int i, const int j, float& ws, float& wd) {
+    nav_cost_weights(g.c, g.cost ? nav_cost_multiplier(g.cost[(long long)i*g.nx + j]) : 1.f, ws, wd);
 }
 
 // Does the chain end at cell (i, j): one of the goal's anchor cells whose value is its own leg to the goal; on a seeded
@@ -93,11 +102,12 @@ __host__ __device__ inline bool nav_chain_ends(const NavEnv& g, const NavGoal& q
 // itself (seeded: this cell's centre); -1: broken (no neighbour below D[v]: a stale or foreign field) - it stops.
 __host__ __device__ inline int nav_hop(const NavEnv& g, const NavGoal& q, int& i, int& j) {
     if (nav_chain_ends(g, q, i, j)) return 0;
-    float best = INFINITY, dbest = INFINITY;
+    float best = INFINITY, dbest = INFINITY, ws, wd;
+    nav_hop_weights(g, i, j, ws, wd);
     int bt = -1;
     for (int t = 0; t < 8; t++) {
         float du;
-        const float v = nav_neighbour(g, i, j, t, du);
+        const float v = nav_neighbour(g, i, j, t, ws, wd, du);
         if (v < best) { best = v; bt = t; dbest = du; }
     }
     if (bt < 0 || !(dbest < g.D[(long long)i*g.nx + j])) return -1;
@@ -186,16 +196,22 @@ struct NavPathArgs {                                 // MsNavWaypoints / MsNavPa
     int* counts;                                     // (N, P)
     int n_points, n_goals, lookahead, max_points;
     long long total;                                 // N P
+    const float* costs;                              // cost fields only (WEIGHTED): as NavFieldArgs'
+    int n_costs;
 };
 
-// Query `at`'s env, field and goal; false: a goal index out of range or an env without cells - no path.
+// Query `at`'s env, field and goal; false: a goal index out of range or an env without cells - no path.  WEIGHTED: the field's
+// costs too - every other instantiation builds its NavEnv with a literal null, and nav_neighbour's branch folds away.
+template <bool WEIGHTED>
 __device__ inline bool nav_bind(const NavArgs& a, const NavPathArgs& q, const long long at, NavEnv& g, NavGoal& goal, long long& cells) {
     const int e = (int)(at / q.n_points), k = (int)(at - (long long)e*q.n_points);
     const int gi = q.goal ? q.goal[at] : k;
     const int4 geom = reinterpret_cast<const int4*>(a.geom)[e];
     cells = (long long)geom.z*geom.w;
     if ((gi < 0) | (gi >= q.n_goals) || cells <= 0) return false;
-    g = NavEnv{geom.x, geom.y, geom.z, geom.w, a.cell, q.free_cells + a.starts[e], q.fields + (long long)q.n_goals*a.starts[e] + (long long)gi*cells};
+    const long long first = (long long)q.n_goals*a.starts[e] + (long long)gi*cells;
+    g = NavEnv{geom.x, geom.y, geom.z, geom.w, a.cell, q.free_cells + a.starts[e], q.fields + first, nullptr};
+    if constexpr (WEIGHTED) g.cost = q.costs + (q.n_costs == 1 ? a.starts[e] : first);
     if (q.goals) {
         const float2 p = reinterpret_cast<const float2*>(q.goals)[(long long)e*q.n_goals + gi];
         goal = nav_goal(g, p.x, p.y);
@@ -203,6 +219,7 @@ __device__ inline bool nav_bind(const NavArgs& a, const NavPathArgs& q, const lo
     return true;
 }
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(WG) void nav_waypoint_kernel(const NavArgs a, const NavPathArgs q) {
     const int lane = threadIdx.x & 63;
     const long long at = (long long)blockIdx.x*(WG/64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -213,7 +230,7 @@ __global__ __launch_bounds__(WG) void nav_waypoint_kernel(const NavArgs a, const
     long long cells;
     float wx = NAN, wy = NAN, leg0 = 0.f;
     int chosen = -1, i = 0, j = 0;
-    if (nav_bind(a, q, at, g, goal, cells) && nav_start(g, p.x, p.y, i, j, leg0)) {
+    if (nav_bind<WEIGHTED>(a, q, at, g, goal, cells) && nav_start(g, p.x, p.y, i, j, leg0)) {
         // the chain: lane k keeps x_k
         const int L = q.lookahead;
         float mx = NAN, my = NAN;
@@ -230,8 +247,9 @@ __global__ __launch_bounds__(WG) void nav_waypoint_kernel(const NavArgs a, const
                 break;
             }
             // nav_hop's fold, a neighbour a lane: the least value, then the first lane that holds it
-            float du = INFINITY;
-            const float v = lane < 8 ? nav_neighbour(g, i, j, lane, du) : INFINITY;
+            float du = INFINITY, ws, wd;
+            nav_hop_weights(g, i, j, ws, wd);                           // (uniform: the cell the wave's hop leaves)
+            const float v = lane < 8 ? nav_neighbour(g, i, j, lane, ws, wd, du) : INFINITY;
             float least = v < INFINITY ? v : INFINITY;                  // (a NaN is never the least)
             least = fminf(least, __shfl_xor(least, 1));
             least = fminf(least, __shfl_xor(least, 2));
@@ -265,6 +283,7 @@ __global__ __launch_bounds__(WG) void nav_waypoint_kernel(const NavArgs a, const
     }
 }
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(WG) void nav_path_kernel(const NavArgs a, const NavPathArgs q) {
     const long long at = (long long)blockIdx.x*WG + threadIdx.x;
     if (at >= q.total) return;
@@ -273,7 +292,7 @@ __global__ __launch_bounds__(WG) void nav_path_kernel(const NavArgs a, const Nav
     NavEnv g;
     NavGoal goal;
     long long cells;
-    if (nav_bind(a, q, at, g, goal, cells)) q.counts[at] = nav_path(g, goal, p.x, p.y, cells, q.max_points, out);
+    if (nav_bind<WEIGHTED>(a, q, at, g, goal, cells)) q.counts[at] = nav_path(g, goal, p.x, p.y, cells, q.max_points, out);
     else {
         for (int k = 0; k < 2*q.max_points; k++) out[k] = NAN;
         q.counts[at] = 0;

@@ -110,6 +110,7 @@ thread_local int g_tail_envs = -1;          //   ... >= 0: that many envs exactl
 thread_local int g_last_step_fused = 0;     // ms_debug_last_step_fused: did this thread's last ms_step_render go out as one launch?
 thread_local int g_last_render_groups = 0;  // ms_debug_last_render_groups: the NG this thread's last ms_render launched
 thread_local int g_overhead_cull = 1;       // ms_debug_overhead_cull: 0 = ms_overhead's tiles keep every line
+thread_local int g_nav_cost_variant = -1;   // ms_debug_nav_cost_variant: where ms_nav_cost_fields' launch keeps the multipliers (-1: its own choice)
 thread_local int g_nav_clear_cull = -1;     // ms_debug_nav_clear_cull: which culls ms_nav_clearance's launch runs (-1: its own choice)
 thread_local long long g_clear_folds = 0, g_clear_pairs = 0;      // ms_host_nav_clear_folds: the last ms_host_nav_clearance's
 thread_local int g_render_order = 1;        // ms_debug_render_order: 0 = MsAgents.schedule is neither sorted nor followed
@@ -855,11 +856,25 @@ static int nav_relax_launch(const MsNavGrid* grid, const NavFieldArgs& f, long l
     return launch_status();
 }
 
+// ... and of the weighted one (MsNavCostFields), in either variant of where a cell's multiplier lives: read from global memory
+// every pass (the seeded kernel's bytes a cell and its tiers) or kept in LDS (its own capacity, its own tier).  The library's
+// choice is the first (DESIGN.md 3.24 has the reasons); the other stays reachable through ms_debug_nav_cost_variant for A/B runs.
+static int nav_cost_launch(const MsNavGrid* grid, const NavFieldArgs& f, long long total, void* stream) {
+    static void (*const kernels[3][2])(NavArgs, NavFieldArgs) = {                   // [tier][from global memory, in LDS]
+        {nav_relax_kernel<NAV_LDS_SMALL, 512, true, NAV_COST_GLOBAL>, nav_relax_kernel<NAV_LDS_SMALL, 512, true, NAV_COST_LDS>},
+        {nav_relax_kernel<NAV_LDS_MEDIUM, 1024, true, NAV_COST_GLOBAL>, nav_relax_kernel<NAV_LDS_MEDIUM, 1024, true, NAV_COST_LDS>},
+        {nav_relax_kernel<NAV_LDS_LARGE, 1024, true, NAV_COST_GLOBAL>, nav_relax_kernel<NAV_LDS_LARGE, 1024, true, NAV_COST_LDS>}};
+    const int in_lds = g_nav_cost_variant == 1 ? 1 : 0;
+    const int t = in_lds ? nav_tier(grid, nav_cost_capacity) : nav_tier(grid, nav_capacity);
+    hipLaunchKernelGGL(kernels[t][in_lds], dim3((unsigned)total), dim3(NAV_TIER_THREADS[t]), 0, (hipStream_t)stream, nav_args(grid), f);
+    return launch_status();
+}
+
 int ms_nav_fields(const MsNavGrid* grid, const MsNavFields* nf, void* stream) {
     if (!nav_grid_ok(grid) || !nf || nf->n_goals < 1 || !nf->goals || !nf->fields || ((uintptr_t)nf->goals % 8)) return MS_EINVAL;
     const long long total = (long long)grid->n_envs*nf->n_goals;
     if (total > 0x7fffffffLL) return MS_EUNSUPPORTED;
-    const NavFieldArgs f{nf->goals, nf->mask, grid->free_cells, nf->fields, nf->passes, nf->n_goals, nullptr, nullptr, 0, nullptr};
+    const NavFieldArgs f{nf->goals, nf->mask, grid->free_cells, nf->fields, nf->passes, nf->n_goals, nullptr, nullptr, 0, nullptr, nullptr, 0};
     return nav_relax_launch(grid, f, total, false, stream);
 }
 
@@ -868,8 +883,31 @@ int ms_nav_seed_fields(const MsNavGrid* grid, const MsNavSeedFields* sf, void* s
         ((uintptr_t)sf->fields % 4) || ((uintptr_t)sf->passes % 4) || ((uintptr_t)sf->n_seeds % 4)) return MS_EINVAL;
     const long long total = (long long)grid->n_envs*sf->n_fields;
     if (total > 0x7fffffffLL) return MS_EUNSUPPORTED;
-    const NavFieldArgs f{nullptr, sf->mask, grid->free_cells, sf->fields, sf->passes, sf->n_fields, sf->marks, sf->among, sf->where, sf->n_seeds};
+    const NavFieldArgs f{nullptr, sf->mask, grid->free_cells, sf->fields, sf->passes, sf->n_fields, sf->marks, sf->among, sf->where, sf->n_seeds,
+                         nullptr, 0};
     return nav_relax_launch(grid, f, total, true, stream);
+}
+
+// Cost fields (MsNavCostFields): the seeded entries' checks, and the costs'.
+static bool nav_costs_ok(const float* costs, int n_costs, int n_fields) {
+    return costs && ((uintptr_t)costs % 4 == 0) && (n_costs == 1 || n_costs == n_fields);
+}
+
+int ms_nav_cost_fields(const MsNavGrid* grid, const MsNavCostFields* cf, void* stream) {
+    if (!nav_grid_ok(grid) || !cf || cf->n_fields < 1 || !cf->marks || !cf->fields || (cf->where != 0 && cf->where != 1) ||
+        ((uintptr_t)cf->fields % 4) || ((uintptr_t)cf->passes % 4) || ((uintptr_t)cf->n_seeds % 4) ||
+        !nav_costs_ok(cf->costs, cf->n_costs, cf->n_fields)) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*cf->n_fields;
+    if (total > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    const NavFieldArgs f{nullptr, cf->mask, grid->free_cells, cf->fields, cf->passes, cf->n_fields, cf->marks, cf->among, cf->where, cf->n_seeds,
+                         cf->costs, cf->n_costs};
+    return nav_cost_launch(grid, f, total, stream);
+}
+
+int ms_debug_nav_cost_variant(int variant) {
+    if (variant < -1 || variant > 1) return MS_EINVAL;
+    g_nav_cost_variant = variant;
+    return MS_OK;
 }
 
 int ms_nav_query(const MsNavGrid* grid, const MsNavQuery* nq, void* stream) {
@@ -889,21 +927,26 @@ static bool nav_follow_ok(const MsNavGrid* grid, int n_points, const float* poin
 }
 static bool nav_goals_ok(const float* goals) { return goals && ((uintptr_t)goals % 8 == 0); }
 
-// The two launches, for fields of goals and - goals NULL - for seeded fields; the arguments are checked by then.
+// The two launches, for fields of goals and - goals NULL - for seeded fields, and - costs not NULL, n_costs 1 or n_goals - for cost
+// fields (the WEIGHTED instantiations); the arguments are checked by then.
 static int nav_waypoints_launch(const MsNavGrid* grid, int n_points, const float* points, const int* goal, const float* fields, const float* goals,
-                                int n_goals, int lookahead, float* waypoints, int* hops, void* stream) {
+                                int n_goals, int lookahead, float* waypoints, int* hops, const float* costs, int n_costs, void* stream) {
     const long long total = (long long)grid->n_envs*n_points;
     if ((total + WAVES - 1)/WAVES > 0x7fffffffLL) return MS_EUNSUPPORTED;
-    const NavPathArgs q{points, goal, fields, goals, grid->free_cells, waypoints, hops, nullptr, nullptr, n_points, n_goals, lookahead, 0, total};
-    hipLaunchKernelGGL(nav_waypoint_kernel, dim3((unsigned)((total + WAVES - 1)/WAVES)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
+    const NavPathArgs q{points, goal, fields, goals, grid->free_cells, waypoints, hops, nullptr, nullptr, n_points, n_goals, lookahead, 0, total,
+                        costs, n_costs};
+    const bool weighted = costs != nullptr;
+    hipLaunchKernelGGL(weighted ? nav_waypoint_kernel<true> : nav_waypoint_kernel<false>, dim3((unsigned)((total + WAVES - 1)/WAVES)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
     return launch_status();
 }
 static int nav_paths_launch(const MsNavGrid* grid, int n_points, const float* points, const int* goal, const float* fields, const float* goals,
-                            int n_goals, int max_points, float* paths, int* counts, void* stream) {
+                            int n_goals, int max_points, float* paths, int* counts, const float* costs, int n_costs, void* stream) {
     const long long total = (long long)grid->n_envs*n_points;
     if (total > 0x7fffff00LL) return MS_EUNSUPPORTED;
-    const NavPathArgs q{points, goal, fields, goals, grid->free_cells, nullptr, nullptr, paths, counts, n_points, n_goals, 0, max_points, total};
-    hipLaunchKernelGGL(nav_path_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
+    const NavPathArgs q{points, goal, fields, goals, grid->free_cells, nullptr, nullptr, paths, counts, n_points, n_goals, 0, max_points, total,
+                        costs, n_costs};
+    const bool weighted = costs != nullptr;
+    hipLaunchKernelGGL(weighted ? nav_path_kernel<true> : nav_path_kernel<false>, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), q);
     return launch_status();
 }
 static bool nav_waypoints_ok(int lookahead, const float* waypoints, const int* hops) {
@@ -916,31 +959,45 @@ static bool nav_paths_ok(int max_points, const float* paths, const int* counts) 
 int ms_nav_waypoints(const MsNavGrid* grid, const MsNavWaypoints* w, void* stream) {
     if (!w || !nav_follow_ok(grid, w->n_points, w->points, w->goal, w->fields, w->n_goals) || !nav_goals_ok(w->goals) ||
         !nav_waypoints_ok(w->lookahead, w->waypoints, w->hops)) return MS_EINVAL;
-    return nav_waypoints_launch(grid, w->n_points, w->points, w->goal, w->fields, w->goals, w->n_goals, w->lookahead, w->waypoints, w->hops, stream);
+    return nav_waypoints_launch(grid, w->n_points, w->points, w->goal, w->fields, w->goals, w->n_goals, w->lookahead, w->waypoints, w->hops, nullptr, 0, stream);
 }
 
 int ms_nav_paths(const MsNavGrid* grid, const MsNavPaths* np, void* stream) {
     if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->n_goals) || !nav_goals_ok(np->goals) ||
         !nav_paths_ok(np->max_points, np->paths, np->counts)) return MS_EINVAL;
-    return nav_paths_launch(grid, np->n_points, np->points, np->goal, np->fields, np->goals, np->n_goals, np->max_points, np->paths, np->counts, stream);
+    return nav_paths_launch(grid, np->n_points, np->points, np->goal, np->fields, np->goals, np->n_goals, np->max_points, np->paths, np->counts, nullptr, 0, stream);
 }
 
 int ms_nav_seed_waypoints(const MsNavGrid* grid, const MsNavSeedWaypoints* w, void* stream) {
     if (!w || !nav_follow_ok(grid, w->n_points, w->points, w->goal, w->fields, w->n_goals) ||
         !nav_waypoints_ok(w->lookahead, w->waypoints, w->hops)) return MS_EINVAL;
-    return nav_waypoints_launch(grid, w->n_points, w->points, w->goal, w->fields, nullptr, w->n_goals, w->lookahead, w->waypoints, w->hops, stream);
+    return nav_waypoints_launch(grid, w->n_points, w->points, w->goal, w->fields, nullptr, w->n_goals, w->lookahead, w->waypoints, w->hops, nullptr, 0, stream);
 }
 
 int ms_nav_seed_paths(const MsNavGrid* grid, const MsNavSeedPaths* np, void* stream) {
     if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->n_goals) ||
         !nav_paths_ok(np->max_points, np->paths, np->counts)) return MS_EINVAL;
-    return nav_paths_launch(grid, np->n_points, np->points, np->goal, np->fields, nullptr, np->n_goals, np->max_points, np->paths, np->counts, stream);
+    return nav_paths_launch(grid, np->n_points, np->points, np->goal, np->fields, nullptr, np->n_goals, np->max_points, np->paths, np->counts, nullptr, 0, stream);
+}
+
+int ms_nav_cost_waypoints(const MsNavGrid* grid, const MsNavCostWaypoints* w, void* stream) {
+    if (!w || !nav_follow_ok(grid, w->n_points, w->points, w->goal, w->fields, w->n_goals) ||
+        !nav_waypoints_ok(w->lookahead, w->waypoints, w->hops) || !nav_costs_ok(w->costs, w->n_costs, w->n_goals)) return MS_EINVAL;
+    return nav_waypoints_launch(grid, w->n_points, w->points, w->goal, w->fields, nullptr, w->n_goals, w->lookahead, w->waypoints, w->hops, w->costs,
+                                w->n_costs, stream);
+}
+
+int ms_nav_cost_paths(const MsNavGrid* grid, const MsNavCostPaths* np, void* stream) {
+    if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->n_goals) ||
+        !nav_paths_ok(np->max_points, np->paths, np->counts) || !nav_costs_ok(np->costs, np->n_costs, np->n_goals)) return MS_EINVAL;
+    return nav_paths_launch(grid, np->n_points, np->points, np->goal, np->fields, nullptr, np->n_goals, np->max_points, np->paths, np->counts,
+                            np->costs, np->n_costs, stream);
 }
 
 static bool nav_host_env(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal, const float* point,
                          NavEnv& g) {
     if (!geom || !free_cells || !D || !goal || !point || !(cell > 0.f) || geom[2] <= 0 || geom[3] <= 0) return false;
-    g = NavEnv{geom[0], geom[1], geom[2], geom[3], cell, free_cells, D};
+    g = NavEnv{geom[0], geom[1], geom[2], geom[3], cell, free_cells, D, nullptr};
     return true;
 }
 
@@ -984,27 +1041,52 @@ int ms_host_nav_seed_path(const int* geom, float cell, const unsigned char* free
     return nav_path(g, nav_seeded(), point[0], point[1], (long long)g.nx*g.ny, max_points, points);
 }
 
-int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* free_cells, const unsigned char* marks, int where,
-                           const unsigned char* among, int framed, float* D, int* n_seeds) {
+int ms_host_nav_cost_waypoint(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* costs, const float* point,
+                              int lookahead, float* waypoint) {
+    if (lookahead < 1 || lookahead > WAVE || !waypoint) return -2;
+    waypoint[0] = waypoint[1] = NAN;
+    NavEnv g;
+    if (!costs || !nav_host_env(geom, cell, free_cells, D, point, point, g)) return -1;
+    g.cost = costs;
+    return nav_waypoint_serial(g, nav_seeded(), point[0], point[1], lookahead, waypoint[0], waypoint[1]);
+}
+
+int ms_host_nav_cost_path(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* costs, const float* point,
+                          int max_points, float* points) {
+    if (max_points < 2 || !points) return 0;
+    NavEnv g;
+    if (!costs || !nav_host_env(geom, cell, free_cells, D, point, point, g)) {
+        for (int k = 0; k < 2*max_points; k++) points[k] = NAN;
+        return 0;
+    }
+    g.cost = costs;
+    return nav_path(g, nav_seeded(), point[0], point[1], (long long)g.nx*g.ny, max_points, points);
+}
+
+// The seeded relaxation on host arrays, and - costs not NULL - the weighted one: the kernel's fill and per-cell functions, swept.
+static int nav_host_seed_field(const int* geom, float cell, const unsigned char* free_cells, const unsigned char* marks, int where,
+                               const unsigned char* among, const float* costs, int framed, float* D, int* n_seeds) {
     if (!geom || !(cell > 0.f) || !(cell < INFINITY) || (where != 0 && where != 1) || geom[2] < 0 || geom[3] < 0) return -1;
     const int nx = geom[2], ny = geom[3];
     const long long cells = (long long)nx*ny;
     if (n_seeds) *n_seeds = 0;
     if (cells <= 0) return 0;
     if (!free_cells || !marks || !D || (long long)(nx + 2)*(ny + 2) > 0x7fffffffLL) return -1;
-    const float ws = cell, wd = cell*NAV_DIAGONAL;
+    float ws = cell, wd = cell*NAV_DIAGONAL;
     int seeds = 0, sweeps = 0;
     if (framed) {
         // as the kernel fills its LDS: the frame, the bytes, the seeds; then nav_cell_framed swept in place
         const int P = nx + 2, n = (nx + 2)*(ny + 2);
         std::vector<float> d(n);
         std::vector<unsigned char> m(n);
+        std::vector<float> mult(costs ? n : 0);                         // (as NAV_COST_LDS keeps them)
         for (int k = 0; k < n; k++) {
             long long at;
             const int fb = nav_frame_free(free_cells, nx, ny, P, k, at);
             const bool seed = fb && nav_is_seed(free_cells, among, marks, at, where);
             d[k] = seed ? 0.f : INFINITY;
             m[k] = (unsigned char)(fb | (seed ? 32 : 0));
+            if (costs) mult[k] = fb ? nav_cost_multiplier(costs[at]) : 1.f;
             seeds += seed;
         }
         for (int k = 0; k < n; k++)
@@ -1013,6 +1095,7 @@ int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* fre
             changed = false;
             for (int k = 0; k < n; k++) {
                 if (!(m[k] & 1)) continue;
+                if (costs) nav_cost_weights(cell, mult[k], ws, wd);
                 const float v = nav_cell_framed(d.data(), m[k], k, P, d[k], ws, wd);
                 if (v < d[k]) { d[k] = v; changed = true; }
             }
@@ -1028,6 +1111,7 @@ int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* fre
             changed = false;
             for (long long k = 0; k < cells; k++) {
                 if (!(free_cells[k] & 1)) continue;
+                if (costs) nav_cost_weights(cell, nav_cost_multiplier(costs[k]), ws, wd);
                 const float v = nav_cell_stored(D, free_cells, nx, ny, k, D[k], ws, wd);
                 if (v < D[k]) { D[k] = v; changed = true; }
             }
@@ -1037,7 +1121,19 @@ int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* fre
     return sweeps;
 }
 
+int ms_host_nav_seed_field(const int* geom, float cell, const unsigned char* free_cells, const unsigned char* marks, int where,
+                           const unsigned char* among, int framed, float* D, int* n_seeds) {
+    return nav_host_seed_field(geom, cell, free_cells, marks, where, among, nullptr, framed, D, n_seeds);
+}
+
+int ms_host_nav_cost_field(const int* geom, float cell, const unsigned char* free_cells, const unsigned char* marks, int where,
+                           const unsigned char* among, const float* costs, int framed, float* D, int* n_seeds) {
+    if (!costs && geom && (long long)geom[2]*geom[3] > 0) return -1;
+    return nav_host_seed_field(geom, cell, free_cells, marks, where, among, costs, framed, D, n_seeds);
+}
+
 int ms_host_nav_field_capacity(int* capacities) { return nav_host_capacities(capacities, nav_capacity); }
+int ms_host_nav_cost_capacity(int* capacities) { return nav_host_capacities(capacities, nav_cost_capacity); }
 
 // Seen maps (navseen.h): the same discipline; an env of more than 2^20 cells is refused, and nothing is enqueued.
 constexpr int NAV_SEEN_MAX_CELLS = 1 << 20;

@@ -26,7 +26,7 @@ def books(before, now, reset, stranded, arrive, bonus):
 class PointGoal:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, arrive=.5, bonus=1., max_lifespan=512,
-                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, **kwargs):
+                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, margin=None, **kwargs):
         """``cell``: the nav grid's cell size; ``arrive``: how near the goal counts as there, metres (walking distance);
         ``bonus``: the reward for arriving; ``max_lifespan``: episodes end after a random number of steps up to this
         (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`.
@@ -35,7 +35,10 @@ class PointGoal:
         drawn on the device among the nav grid's free cells (:class:`~megastep_amd.modules.SampledSpawns`) instead of from a
         table made on the host. ``one_region=True`` (with ``sampled_spawns``): the spawns are drawn in the env's largest connected
         space only (:func:`~megastep_amd.cuda.regions` of the grid, once), so all agents of an env can reach one another and no
-        spawn lands in a closet."""
+        spawn lands in a closet. ``margin``: metres; then the expert does not follow the shortest path, which runs along the walls at
+        exactly the body's clearance, but the cheapest route (:class:`~megastep_amd.modules.Routes`) over an inflation layer -
+        ``inflation_costs(clearance_fields(grid, scenery, margin), margin)`` - that makes a cell dearer the nearer a wall comes
+        within ``margin``: it keeps to the middle where there is room. Reward and observations do not change."""
         if one_region and not sampled_spawns:
             raise RuntimeError('one_region gates the sampled spawns: it needs sampled_spawns=True')
         if geometries is None:
@@ -60,7 +63,15 @@ class PointGoal:
             # goals come from the spawn table; one closer than twice `arrive` would be a bonus for nothing
             self._goals = modules.Goals(geometries, c, self.grid, candidates=candidates, min_distance=2*self.arrive,
                                         table=None if sampled_spawns else self._respawner._spawns.positions, n_spawns=n_spawns)
-        self._follower = modules.PathFollower(c, self._goals, cone=15.)     # (under momentum a narrow cone walks a third less far: DESIGN 3.15)
+        self.clearance = self.costs = self._routes = None
+        if margin is not None:
+            if not (margin > 0 and margin < float('inf')):
+                raise RuntimeError(f'margin must be a positive number of metres; got {margin}')
+            self.clearance = cuda.clearance_fields(self.grid, c.scenery, max_range=float(margin))
+            self.costs = cuda.inflation_costs(self.clearance, float(margin))
+            self._routes = modules.Routes(c, self.grid, self._goals, self.costs)
+        # (under momentum a narrow cone walks a third less far: DESIGN 3.15)
+        self._follower = modules.PathFollower(c, self._goals if self._routes is None else self._routes, cone=15.)
         self.action_space = self._mover.space
         self.obs_space = dotdict.dotdict(rgb=self._rgb.space, d=self._depth.space, goal=self._goals.space)
 
@@ -81,6 +92,8 @@ class PointGoal:
 
     def _world(self, reset):
         self._goals(reset)
+        if self._routes is not None:
+            self._routes(reset)
         now = self._goals.distances()
         # An agent can squeeze into a spot the grid has no free cell near (a gap between a pillar and a wall that is wider than
         # the agent and narrower than the grid can see): from there no distance is defined. It counts as stranded from then on -

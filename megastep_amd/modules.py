@@ -570,6 +570,43 @@ class SampledGoals:
     distances, waypoints, observation, state = Goals.distances, Goals.waypoints, Goals.observation, Goals.state
 
 
+class Routes:
+
+    def __init__(self, core, grid, goals, cost):
+        """Weighted routes to the goals of a :class:`Goals` or a :class:`SampledGoals` (anything with ``.goals`` (n_env, n_agent, 2)):
+        the cells round every agent's goal are the seeds (:func:`cuda.point_marks`, agent k store k) of a :func:`cuda.cost_fields`
+        over ``cost`` - an :func:`cuda.inflation_costs` layer keeps the routes off the walls, a :func:`cuda.mark_costs` layer prices
+        unknown or watched floor - kept by reference, so a layer rewritten in place bends the routes computed after it.
+        :meth:`waypoints` and :meth:`distances` have the shape :class:`PathFollower` takes from :class:`Goals`; a route ends on the
+        centre of a cell next to the goal, which is as near as an env's ``arrive`` asks. The goals module draws the goals, so call
+        it first; the stores are made by the first call, and from then on a call is a fill, two launches and nothing that waits
+        for the host: it can sit in a HIP graph."""
+        self.core, self.grid, self.goals, self.cost = core, grid, goals, cost
+        #: the :class:`cuda.PointMarks` of the goals and the :class:`cuda.CostFields` seeded by them (None before the first call)
+        self.seeds = self.fields = None
+
+    def __call__(self, reset=None):
+        """Marks the goals as they stand and recomputes the routes of the agents marked in the (n_env, n_agent) bool ``reset``
+        (default all) - those whose goal was drawn anew. Call once per step, after the goals module."""
+        if self.seeds is None:
+            self.seeds = cuda.point_marks(self.grid, self.goals.goals, self.core.n_agents)
+            self.fields = cuda.cost_fields(self.grid, self.seeds.marks, self.core.n_agents, self.cost)
+        else:
+            self.seeds.points = self.goals.goals
+            self.seeds.update()
+            self.fields.update(None if reset is None else reset.contiguous())
+        return self.fields
+
+    def distances(self):
+        """(n_env, n_agent): what the route from where every agent stands costs - metres where the cost is 1; +inf without one."""
+        return self.fields.at(self.core.agents.positions)
+
+    def waypoints(self, lookahead=16):
+        """(n_env, n_agent, 2): where every agent should head for now to follow its route (:meth:`cuda.CostFields.waypoints`); NaN
+        where no route exists."""
+        return self.fields.waypoints(self.core.agents.positions, lookahead=lookahead)
+
+
 class SampledSpawns:
 
     def __init__(self, core, grid, seed=0, within=None, gate=None):
@@ -743,7 +780,7 @@ class Territories:
 
 class Frontiers:
 
-    def __init__(self, core, coverage, refresh=8, territories=None):
+    def __init__(self, core, coverage, refresh=8, territories=None, cost=None):
         """How far every agent has to walk to the nearest floor its map has not seen, and which way (no counterpart in the
         reference): the frontier fields of a :class:`Coverage`'s maps (:meth:`cuda.SeenMaps.frontier_fields`), one field per
         map. A field is recomputed every ``refresh`` steps of its agent and when the agent starts over; in between it is a
@@ -756,7 +793,10 @@ class Frontiers:
         of its own (:attr:`own`) - the walk to the nearest unseen floor within its own territory,
         ``seeded_fields(grid, territories.masks.values, A, where=True, among=unseen)`` - and follows that, so that an env's agents
         part ways instead of walking to the same unseen cell; an agent whose territory holds no unseen floor follows the env's
-        shared field (:meth:`fallback`). The module calls the territories itself, once per call."""
+        shared field (:meth:`fallback`). The module calls the territories itself, once per call.
+
+        ``cost``: a cost layer as :func:`cuda.cost_fields` takes it, kept by reference; the frontier fields (and the agents' own)
+        are then :class:`cuda.CostFields`, and the walk to the nearest unseen floor is the cheapest one, not the shortest."""
         self.core, self.coverage, self.refresh = core, coverage, int(refresh)
         if self.refresh < 1:
             raise RuntimeError(f'refresh must be a positive integer; got {refresh}')
@@ -764,13 +804,17 @@ class Frontiers:
             raise RuntimeError('territories go with a shared coverage: with a map of its own each agent has its own frontier already')
         self._steps = torch.zeros((core.n_envs, core.n_agents), dtype=torch.long, device=core.device)
         self._field = coverage._slot                    # (n_env, n_agent) zeros when the map is shared, else None: agent k field k
-        self.fields = coverage.maps.frontier_fields()
+        self.cost = cost
+        self.fields = coverage.maps.frontier_fields(cost=cost)
         self.territories, self.own = territories, None
         if territories is not None:
             maps = coverage.maps
             self._unseen = torch.zeros_like(maps.countable)           # (grid.free's layout: the shared map is one store an env)
             self._refresh_unseen()
-            self.own = cuda.seeded_fields(coverage.grid, territories.masks.values, core.n_agents, where=True, among=self._unseen)
+            if cost is None:
+                self.own = cuda.seeded_fields(coverage.grid, territories.masks.values, core.n_agents, where=True, among=self._unseen)
+            else:
+                self.own = cuda.cost_fields(coverage.grid, territories.masks.values, core.n_agents, cost, where=True, among=self._unseen)
 
     def _refresh_unseen(self):
         """unseen = ~seen & countable, in place, by byte ops on the env-layout stores."""

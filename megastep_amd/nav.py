@@ -452,6 +452,163 @@ def seeded_fields(grid, marks, n_fields, where=True, among=None, mask=None, out=
     return fields.update(mask)
 
 
+#: the framed cells an env may have for :func:`cost_fields` to relax it in LDS when the launch keeps the cells' multipliers there too
+#: (a float, a float and a byte a cell in 40, 80 and 160 KiB); the library's own launch reads them from global memory instead and
+#: has :data:`FIELD_CAPACITY`. A larger env is relaxed in global memory, to the same bits
+COST_CAPACITY = (4544, 9092, 18196)
+#: the dearest a cell can be: a cost above it - +inf, a NaN - counts as this; a cost below 1 counts as 1
+COST_MAX = 256.
+
+
+_WEIGHTED_BASINS = 'basins follow the unweighted hop: they cannot be taken of cost fields (weighted basins are not built)'
+
+
+class CostFields(SeededFields):
+    """Result of :func:`cost_fields`: a :class:`SeededFields` whose steps are weighted by ``cost`` - the flat float32 store of
+    ``n_costs`` (1 or G) stores per env, kept by reference as ``marks`` are, so :meth:`update` sees both as they stand. Field
+    (n, g) holds the cost of the cheapest 8-connected path from each cell to a seed: a step out of cell v costs its length times
+    ``clamp(cost[v], 1, COST_MAX)``. :meth:`at` is the seeded query on the weighted values (the leg from the point to its cell,
+    under a cell long, is charged at 1); :meth:`waypoints` and :meth:`paths` descend the weighted field with the weights of the
+    cell each hop leaves. The rule: include/megastep_hip.h (``MsNavCostFields``), DESIGN.md 3.24."""
+
+    def __init__(self, grid, marks, n_fields, where, among, cost, n_costs, values, n_seeds, passes=None):
+        super().__init__(grid, marks, n_fields, where, among, values, n_seeds, passes)
+        self.cost, self.n_costs = cost, int(n_costs)
+
+    def _own(self):
+        return (self.cost,)
+
+    def _waypoints_call(self, p, points, goal, lookahead, out, hops):
+        return 'cost_waypoints', self.grid, _lib.MsNavCostWaypoints(p, points, goal, self.values.data_ptr(), self.n_goals, lookahead, out, hops,
+                                                                    self.cost.data_ptr(), self.n_costs)
+
+    def _paths_call(self, p, points, goal, max_points, out, counts):
+        return 'cost_paths', self.grid, _lib.MsNavCostPaths(p, points, goal, self.values.data_ptr(), self.n_goals, max_points, out, counts,
+                                                            self.cost.data_ptr(), self.n_costs)
+
+    def basins(self, ids=None, n_ids=0, mask=None, out=None, passes=False):
+        """Not served: :func:`basins` follow the unweighted hop, which does not descend a weighted field."""
+        raise RuntimeError(_WEIGHTED_BASINS)
+
+    def update(self, mask=None):
+        """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place, from :attr:`marks` and :attr:`cost` as
+        they stand now. One launch, no host synchronisation."""
+        grid, g = self.grid, self.n_goals
+        mask = _mask(mask, grid.n_envs, g, 'G')
+        dev = _require_gpu(self.marks, self.cost, self.values, self.n_seeds, grid.free, *_some(self.among, mask, self.passes))
+        _launch(dev, 'cost_fields', grid, _lib.MsNavCostFields(g, self.marks.data_ptr(), int(self.where), _ptr(self.among), _ptr(mask),
+                                                               self.values.data_ptr(), _ptr(self.passes), self.n_seeds.data_ptr(),
+                                                               self.cost.data_ptr(), self.n_costs))
+        return self
+
+
+def _cost_store(grid, cost, n_fields):
+    """``cost`` as the flat float32 store the kernels read, sharing its memory, and its stores an env (1 or ``n_fields``)."""
+    if isinstance(cost, torch.Tensor):
+        values, n_costs = cost, None
+    else:
+        layer = _layer(cost)
+        if layer.field is not None:
+            raise RuntimeError("cost must be a layer without a `field`: a cell's cost is its env's or its field's")
+        values, n_costs = layer.values, layer.n_fields
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.ndim != 1 or not values.is_contiguous():
+        raise RuntimeError('cost must be a contiguous 1-dimensional float32 tensor, or a layer of one')
+    lengths = {max(k*grid.n_cells, 1): k for k in (n_fields, 1)}        # (n_fields == 1: one store either way)
+    if n_costs is None:
+        n_costs = lengths.get(values.shape[0])
+    if n_costs not in (1, n_fields) or values.shape[0] < max(n_costs*grid.n_cells, 1):
+        raise RuntimeError(f'cost must hold a float per cell ({grid.n_cells} entries: one store an env) or per cell and field '
+                           f'({n_fields}*{grid.n_cells}); got {values.shape[0]} entries' + ('' if n_costs is None else f' in {n_costs} stores an env'))
+    return values, n_costs
+
+
+def cost_fields(grid, marks, n_fields, cost, where=True, among=None, mask=None, out=None, passes=False):
+    """:func:`seeded_fields` over a per-cell cost layer: weighted shortest paths to the nearest seed. ``cost``: a float32 tensor of
+    one entry per cell of the grid (``grid.free``'s layout, shared by an env's fields) or of ``n_fields*grid.n_cells`` entries (the
+    fields' layout, a store a field), or any float layer - a :class:`ClearanceFields`, fields, a :func:`cell_layer`; kept by
+    reference, as ``marks`` are. A step out of cell v costs its length times ``k_v``, the cell's cost clamped to
+    [1, :data:`COST_MAX`] (a NaN counts as the dearest): costs bend paths, they never close a cell - connectivity, the corner rule
+    and a waypoint's sight are :func:`seeded_fields`'. A cost of 1 everywhere gives :func:`seeded_fields`' bits.
+    :func:`inflation_costs` and :func:`mark_costs` build the usual layers.
+
+    One launch, one workgroup per field, the seeded relaxation with per-cell weights; the result does not depend on the order of
+    relaxation and equals a multi-source Dijkstra's with binary32 additions bit for bit (include/megastep_hip.h,
+    ``MsNavCostFields``). ``where``, ``among``, ``mask``, ``out`` (a :class:`CostFields` of the same grid, marks,
+    cost and arguments), ``passes``: as :func:`seeded_fields`. No host synchronisation: the call can be captured in a HIP graph."""
+    if not isinstance(n_fields, int) or n_fields < 1:
+        raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
+    marks = _cell_bytes(marks, 'marks', max(n_fields*grid.n_cells, 1), f'a byte per cell and field (n_fields*n_cells = {n_fields}*{grid.n_cells})')
+    if among is not None:
+        among = _cell_bytes(among, 'among', grid.free.shape[0], 'one per cell of the grid')
+    cost, n_costs = _cost_store(grid, cost, n_fields)
+    where = bool(where)
+    if out is not None:
+        if not isinstance(out, CostFields) or out.grid is not grid or out.n_goals != n_fields or out.where != where or \
+                not _same(out.marks, marks) or not _same(out.among, among) or not _same(out.cost, cost) or out.n_costs != n_costs:
+            raise RuntimeError('`out` must come from a cost_fields call with the same grid, marks, n_fields, cost, where and among')
+        return out.update(mask)
+    dev = _require_gpu(marks, cost, grid.free, *_some(among))
+    values = torch.empty(max(n_fields*grid.n_cells, 1), dtype=torch.float32, device=dev)
+    if mask is not None:
+        values.fill_(float('inf'))                                      # (a field never computed is a field nothing reaches)
+    shape = (grid.n_envs, n_fields)
+    fields = CostFields(grid, marks, n_fields, where, among, cost, n_costs, values, torch.zeros(shape, dtype=torch.int32, device=dev),
+                        torch.zeros(shape, dtype=torch.int32, device=dev) if passes else None)
+    return fields.update(mask)
+
+
+def _cost_out(like, out):
+    """The float32 tensor a cost builder writes: ``out`` if it fits the layer ``like``, a fresh one without."""
+    if out is None:
+        return torch.empty(like.shape, dtype=torch.float32, device=like.device)
+    if not _fits(out, like.shape, torch.float32) or out.device != like.device:
+        raise RuntimeError('`out` must be a contiguous float32 tensor of the layer\'s length, on its device')
+    return out
+
+
+def inflation_costs(clear, radius, weight=4., out=None):
+    """An inflation layer for :func:`cost_fields`: ``1 + weight*clamp(1 - d/radius, 0, 1)`` per cell, from ``clear`` - a
+    :class:`ClearanceFields` or its flat float32 ``values``, d metres to the nearest wall: 1 from ``radius`` metres out (and where
+    the clearance is +inf, beyond its range), rising linearly to ``1 + weight`` at the wall, so that paths keep to the middle
+    where there is room. Plain element-wise torch: capturable; ``out``: the tensor of an earlier call to rewrite in place - every
+    step is then written into it (it may not be the clearance itself)."""
+    d = clear.values if isinstance(clear, ClearanceFields) else clear
+    if not isinstance(d, torch.Tensor) or d.dtype != torch.float32:
+        raise RuntimeError('clear must be a ClearanceFields or a float32 tensor of distances to the nearest wall')
+    if not (radius > 0 and radius < float('inf')) or not (weight >= 0 and weight < float('inf')):
+        raise RuntimeError(f'radius must be a positive number and weight a number >= 0; got {radius}, {weight}')
+    if out is not None and out.data_ptr() == d.data_ptr():
+        raise RuntimeError('`out` must not be the clearance itself')
+    out = _cost_out(d, out)
+    # every step written into `out`: nothing is allocated but two 0-dimensional tensors - the radius as a tensor makes a true
+    # division (by a host scalar torch multiplies by the reciprocal on the device, which is not the formula's bits); so is the 1
+    torch.div(d, torch.full((), float(radius), dtype=torch.float32, device=d.device), out=out)
+    torch.sub(torch.ones((), dtype=torch.float32, device=d.device), out, out=out)      # (1 - q as written: a NaN keeps its bits)
+    return out.clamp_(0, 1).mul_(weight).add_(1)
+
+
+def mark_costs(layer, on=1., off=256., where=True, gate=None, out=None):
+    """A cost layer for :func:`cost_fields` from any byte layer - a :class:`SeenMaps`, a :class:`ViewFields`, a territory mask, a
+    :func:`cell_layer`: ``on`` where ``(byte != 0) == where``, ``off`` elsewhere, in the layer's own layout (so a layer of G stores
+    an env prices field g by store g). The defaults are known-space planning over a seen map: a seen cell costs 1, an unseen one
+    256, and a route crosses unknown floor only when there is no other. ``gate``: a byte layer of the same layout; where its byte
+    is 0 the layer says nothing and the cell costs 1. Plain element-wise torch: capturable; ``out``: the tensor of an earlier call to
+    write the result into (the mask and the chosen values on the way are torch's temporaries)."""
+    layer = _layer(layer)
+    if layer.is_float:
+        raise RuntimeError('mark_costs reads a byte layer (uint8 or bool), not float32')
+    if gate is not None:
+        gate = _layer(gate)
+        if gate.is_float or gate.values.shape != layer.values.shape:
+            raise RuntimeError("a gate must be a byte layer (uint8 or bool) of the layer's own layout")
+    out = _cost_out(layer.values, out)
+    # (an exact choice of two values: the mask and the chosen values are torch's temporaries, the result lands in `out`)
+    value = torch.where((layer.values != 0) == bool(where), float(on), float(off))
+    if gate is not None:
+        value = torch.where(gate.values != 0, value, 1.)
+    return out.copy_(value)
+
+
 #: the most cells an env may have for :func:`seen_maps`: the kernel keeps a call's marks as one bit per cell in LDS (128 KiB)
 SEEN_MAX_CELLS = 2**20
 
@@ -529,12 +686,15 @@ class SeenMaps:
         return self.mark(agents.positions, dirs, distances.reshape(n, a, r), slot=slot, max_range=max_range, reset=reset, out=out)
 
 
-    def frontier_fields(self, mask=None, out=None, passes=False):
+    def frontier_fields(self, mask=None, out=None, passes=False, cost=None):
         """The walking distance from every cell to the nearest countable cell each map has NOT seen, as a :class:`SeededFields`
         of one field per map: ``seeded_fields(grid, self.values, self.n_maps, where=False, among=self.countable)``. The fields
         read the maps by reference: :meth:`SeededFields.update` follows the marks. With a countable mask of cells that can be
         walked to (:class:`~megastep_amd.demo.envs.floorcoverage.FloorCoverage`'s) every seed can be reached; a field without
-        a seed - nothing is left to see - is +inf throughout. ``mask``, ``out``, ``passes``: as :func:`seeded_fields`."""
+        a seed - nothing is left to see - is +inf throughout. ``mask``, ``out``, ``passes``: as :func:`seeded_fields`. ``cost``:
+        a cost layer as :func:`cost_fields` takes it; the frontier fields are then :class:`CostFields`."""
+        if cost is not None:
+            return cost_fields(self.grid, self.values, self.n_maps, cost, where=False, among=self.countable, mask=mask, out=out, passes=passes)
         return seeded_fields(self.grid, self.values, self.n_maps, where=False, among=self.countable, mask=mask, out=out, passes=passes)
 
     def frontier_regions(self, mask=None, out=None, passes=False):
@@ -1206,11 +1366,14 @@ def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
 
     ``mask`` (N, G) bool: label only the marked fields (the others keep what ``out`` held; -1 and 0 without ``out``); ``out``: the
     :class:`Basins` of an earlier call with the same fields, ids and n_ids to write into; ``passes=True`` also records the passes
-    each field took. A :class:`DistanceFields` is refused: a single goal's chains end on the goal's four anchors, not on a seed. No
+    each field took. A :class:`DistanceFields` is refused: a single goal's chains end on the goal's four anchors, not on a seed; so is
+    a :class:`CostFields`: the basins' hop is unweighted and does not descend a weighted field. No
     host synchronisation: the call can be captured in a HIP graph."""
     if isinstance(fields, DistanceFields):
         raise RuntimeError("basins are of seeded fields: a DistanceFields has one goal, and its chains end on the goal's four anchors - "
                            'nothing to tell apart')
+    if isinstance(fields, CostFields):
+        raise RuntimeError(_WEIGHTED_BASINS)
     if not isinstance(fields, SeededFields):
         raise RuntimeError('fields must be a SeededFields')
     grid, g = fields.grid, fields.n_goals

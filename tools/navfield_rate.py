@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance] [--large]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance|cost] [--large]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -74,6 +74,14 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       wall index; the first `--torch-envs` envs, scaled; values and nearest compared for equality); one cuda.clearance of
       `--envs` x 4 points with four agents an env; modules.Proximity eager and replayed as a HIP graph, next to modules.IMU.
       `--large` draws the large plans instead.
+  (k) cost fields, at `--envs` envs, the maximum and median `passes` reported for each: one cuda.cost_fields (ms_nav_cost_fields) for
+      BOTH variants of where the kernel keeps a cell's multiplier (read from global memory every pass; in LDS:
+      ms_debug_nav_cost_variant) next to cuda.seeded_fields on the same marks - the cells round a spawn point - for a cost of all
+      ones, an inflation layer (cuda.inflation_costs of cuda.clearance_fields, radius 0.5) and a known-space layer (cuda.mark_costs
+      of a seen map after one marked frame); one weighted waypoints call of `--envs` x 1 points next to the seeded one; the torch
+      formulation of the same rule under the inflation layer (the first `--torch-envs` envs, scaled; compared for equal bits);
+      PointGoal(envs, margin=.3): expert() + step() eager and replayed as a HIP graph, next to PointGoal(envs); and PointGoal(64),
+      300 steps under the expert with and without margin=.3: arrivals, steps the follower spent stuck, mean clearance under the agents.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -497,6 +505,69 @@ def torch_clearance(grid, scenery, R, envs):
     return run
 
 
+def torch_cost_fields(grid, marks, cost, envs):
+    """The cost fields of the first `envs` envs (one field an env, a cost store an env) by tensor ops, as (envs, H, W) padded to the
+    largest grid: the weights of the cell a step leaves, the min first and one addition per weight."""
+    geom = grid._host_geom[:envs]
+    H, W = int(geom[:, 3].max()) + 2, int(geom[:, 2].max()) + 2
+    dev = grid.free.device
+    c = torch.tensor(grid.cell, dtype=torch.float32, device=dev)
+    free = torch.zeros((envs, H, W), dtype=torch.bool, device=dev)
+    seeds = torch.zeros((envs, H, W), dtype=torch.bool, device=dev)
+    k = torch.ones((envs, H, W), dtype=torch.float32, device=dev)
+    for e in range(envs):
+        s, ny, nx = grid.cells(e)
+        free[e, 1:ny + 1, 1:nx + 1] = grid.free[s:s + ny*nx].reshape(ny, nx).bool()
+        seeds[e, 1:ny + 1, 1:nx + 1] = (marks[s:s + ny*nx].reshape(ny, nx) & 1).bool()
+        k[e, 1:ny + 1, 1:nx + 1] = cost[s:s + ny*nx].reshape(ny, nx)
+    seeds &= free
+    k = torch.where(k >= 1, k.clamp(max=256.), torch.where(k < 1, torch.ones_like(k), torch.full_like(k, 256.)))
+    ws, wd = c*k, (c*torch.tensor(1.41421356, dtype=torch.float32, device=dev))*k
+    inf = torch.tensor(float('inf'), device=dev)
+
+    def shifted(t, di, dj, fill):
+        out = torch.full_like(t, fill)
+        out[:, max(di, 0):H + min(di, 0), max(dj, 0):W + min(dj, 0)] = t[:, max(-di, 0):H + min(-di, 0), max(-dj, 0):W + min(-dj, 0)]
+        return out
+
+    open_ = {}
+    for di in (-1, 1):
+        for dj in (-1, 1):
+            open_[di, dj] = free & shifted(free, di, dj, False) & shifted(free, di, 0, False) & shifted(free, 0, dj, False)
+
+    def run():
+        D = torch.where(seeds, torch.zeros((), device=dev), inf).expand(envs, H, W).contiguous()
+        sweeps = 0
+        while True:
+            before = D
+            for _ in range(16):
+                straight, diagonal = inf.expand_as(D), inf.expand_as(D)
+                for di, dj in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+                    straight = torch.minimum(straight, shifted(D, di, dj, float('inf')))
+                for (di, dj), ok in open_.items():
+                    diagonal = torch.minimum(diagonal, torch.where(ok, shifted(D, di, dj, float('inf')), inf))
+                D = torch.where(free, torch.minimum(D, torch.minimum(straight + ws, diagonal + wd)), inf)
+                sweeps += 1
+            if torch.equal(D, before):
+                return D, sweeps
+    return run
+
+
+def follower_score(env, steps):
+    """`steps` steps of a PointGoal under its expert: arrivals, the (agent, step) pairs the follower counted at a dead stop, and the
+    mean distance to the nearest wall under the agents."""
+    from megastep_amd import cuda
+    env.reset()
+    arrivals = stuck = 0
+    room = []
+    for _ in range(steps):
+        env.step(env.expert())
+        arrivals += int(((env._distance < env.arrive) & ~env._goals.stranded).sum())
+        stuck += int((env._follower._blocked > 0).sum())
+        room.append(float(cuda.clearance(env.core.scenery, env.core.agents.positions, 2.).distances.clamp(max=2.).mean()))
+    return dict(arrivals=arrivals, stuck_steps=stuck, mean_clearance=float(np.mean(room)))
+
+
 def coverage_score(env, steps, policy, seed=1):
     """(episodes ended by coverage, by lifespan, mean final fraction over all episodes) of `steps` steps of a FloorCoverage under
     expert(policy), or uniformly random actions."""
@@ -562,7 +633,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance', 'cost'))
     ap.add_argument('--large', action='store_true')
     ap.add_argument('--json')
     args = ap.parse_args()
@@ -1067,6 +1138,70 @@ def main():
             print(f'(c2) modules.{name}({args.envs} x 4): eager {eager*1e6:.1f} us, graph replay {graphed*1e6:.1f} us')
         del sc, c
         torch.cuda.empty_cache()
+
+    if want('cost'):
+        from megastep_amd import _lib
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        cells = np.diff(grid._host_starts)
+        seeds = cuda.point_marks(grid, table[:, :, 1].contiguous(), 1)
+        points = table[:, :, 0].contiguous()
+        seeded = cuda.seeded_fields(grid, seeds.marks, 1, passes=True)
+        med, lo, hi = timed(lambda: seeded.update(), args.repeats, args.warmup)
+        out['cost_seeded'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, passes_most=int(seeded.passes.max()), passes_median=int(seeded.passes.median()),
+                                  cells_largest=int(cells.max()), cells_median=int(np.median(cells)))
+        print(f"(k) seeded_fields on the goal's cells, {args.envs} fields: {med*1e3:.3f} ms [{lo*1e3:.3f}, {hi*1e3:.3f}]; {out['cost_seeded']}")
+        maps = cuda.seen_maps(grid, 1)
+        maps.mark_render(c.agents, cuda.render(sc, c.agents, fields=('distances',)))
+        clear = cuda.clearance_fields(grid, sc, max_range=.5)
+        layers = dict(ones=torch.ones(max(grid.n_cells, 1), device='cuda'), inflation=cuda.inflation_costs(clear, .5), known_space=cuda.mark_costs(maps))
+        for name, layer in layers.items():
+            fields = cuda.cost_fields(grid, seeds.marks, 1, layer, passes=True)
+            values = {}
+            for which, label in ((0, 'global'), (1, 'lds')):
+                _lib.lib().ms_debug_nav_cost_variant(which)
+                med, lo, hi = timed(lambda: fields.update(), args.repeats, args.warmup)
+                values[label] = fields.values.clone()
+                out[f'cost_{name}_{label}'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, passes_most=int(fields.passes.max()),
+                                                   passes_median=int(fields.passes.median()))
+                print(f"(k) cost_fields, {name}, multipliers {'in LDS' if which else 'from global memory'}, {args.envs} fields: {med*1e3:.3f} ms "
+                      f"[{lo*1e3:.3f}, {hi*1e3:.3f}]; passes most {int(fields.passes.max())}, median {int(fields.passes.median())}")
+            _lib.lib().ms_debug_nav_cost_variant(-1)
+            out[f'cost_{name}_variants_equal_bits'] = bool(torch.equal(values['global'].view(torch.int32), values['lds'].view(torch.int32)))
+            if name == 'ones':
+                out['cost_ones_equals_seeded_bits'] = bool(torch.equal(values['global'].view(torch.int32), seeded.values.view(torch.int32)))
+        inflated = cuda.cost_fields(grid, seeds.marks, 1, layers['inflation'])
+        way = torch.empty_like(points)
+        for name, fields in (('seeded', seeded), ('cost', inflated)):
+            med, lo, hi = timed(lambda: fields.waypoints(points, out=way), 5*args.repeats, args.warmup)
+            chosen = fields.waypoints(points, hops=True)[1]
+            out[f'cost_waypoints_{name}'] = dict(seconds=med, min=lo, max=hi, points=args.envs, lookahead=16, mean_index=float(chosen[chosen >= 0].float().mean()))
+            print(f'(k) {name} waypoints, {args.envs} x 1 points: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        k = min(args.torch_envs, args.envs)
+        run = torch_cost_fields(grid, seeds.marks, layers['inflation'], k)
+        D, sweeps = run()
+        same = all(torch.equal(D[e, 1:grid.cells(e)[1] + 1, 1:grid.cells(e)[2] + 1].view(torch.int32), inflated.image(e, 0).view(torch.int32)) for e in range(k))
+        med, lo, hi = timed(lambda: run(), max(args.repeats//3, 2), 1)
+        out['cost_torch'] = dict(envs=k, seconds=med, scaled_seconds=med*args.envs/k, sweeps=sweeps, equal_bits=bool(same))
+        print(f'(k) torch sweeps, inflation, {k} fields: {med*1e3:.1f} ms, {sweeps} sweeps -> {med*args.envs/k*1e3:.1f} ms for {args.envs}; equal bits: {same}')
+        del sc, c, grid, maps, clear, seeded, inflated, fields, layers
+        torch.cuda.empty_cache()
+        for name, kw in (('PointGoal', {}), ('PointGoal_margin', dict(margin=.3))):
+            env = ExpertStep(PointGoal(args.envs, geometries=geoms, **kw))
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[f'cost_{name}_expert_step'] = dict(eager_seconds=eager, graph_seconds=graphed)
+            print(f'(k) {name}({args.envs}): expert + step eager {eager*1e3:.3f} ms, graph {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+        small = cubicasa.sample(64, seed=7, n_unique=64)
+        for name, kw in (('plain', {}), ('margin', dict(margin=.3))):
+            torch.manual_seed(3); np.random.seed(3)
+            out['cost_follower_' + name] = score = follower_score(PointGoal(64, geometries=small, **kw), 300)
+            print(f'(k) PointGoal(64), 300 steps under the expert, {name}: {score}')
 
     if args.json:
         with open(args.json, 'w') as f:
