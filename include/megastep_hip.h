@@ -710,6 +710,62 @@ typedef struct MsNavSeen {
 } MsNavSeen;
 int ms_nav_seen(const MsNavGrid* grid, const MsNavSeen* seen, void* hip_stream);
 
+/* Age maps: WHEN each cell of the nav grid was last passed over by a depth ray - idleness, for patrol, surveillance and search
+ * tasks that do not end when the floor runs out.  Grid, geometry, the stores' layout, rays, samples and the cell under a sample
+ * are MsNavSeen's, word for word (kernels/navseen.h: seen_ray, seen_sample).  Every number below is an integer, or an integer
+ * binary32 holds exactly; tests/test_navage_host.py restates the rule in numpy (age_rule) and the kernel - and its host
+ * instantiation, ms_host_nav_ages - are held to EQUALITY with it.
+ *   last          S stores per env in MsNavSeen.maps' layout, one binary32 per cell: the tick at which the cell was last seen;
+ *                 0.f: never since the map was cleared.  Ticks start at 1.
+ *   clock         (N, S) int32 on the device: the tick of the map's last advancing call.
+ *   a call        for map (n, s), in this order:  1. reset[n, s] non-zero: last of the map and clock[n, s] go to 0;
+ *                 2. now = advance ? min(clock[n, s] + 1, 16777216) : clock[n, s] - 2^24, where binary32 stops holding ticks
+ *                 exactly;  3. with advance, the cells under the samples of the rays of the map's viewers are the call's marked
+ *                 SET: a cell under many samples, or under two viewers' rays, is in it once.  Without advance nothing is marked,
+ *                 and origins, dirs, distances, slot, n_viewers and n_rays are not read;  4. for every marked cell
+ *                 age = now - (int)last, then last = (float)now;  5. swept[n, s] = the marked cells that are countable;
+ *                 6. gained[n, s] = those of them whose last was 0;  7. idle[n, s] = the sum of age over them, an int64;
+ *                 8. clock[n, s] = now.  swept, gained and idle may each be NULL.
+ *   the survey    runs after the marks of the same call - a cell just marked has age 0 - unless oldest, total_age, n_stale,
+ *                 stale and ages are all NULL.  For every cell age = now - (int)last.  Over the countable cells:
+ *                 oldest[n, s] = the largest age (0 when no cell counts; never below 0), total_age[n, s] = the sum of the ages,
+ *                 an int64, n_stale[n, s] = the cells with age >= threshold (an int >= 1).  stale, a byte store in the maps'
+ *                 layout: (countable & 1) && age >= threshold ? 1 : 0 for every cell - marks for MsNavSeedFields and
+ *                 MsNavRegions, a layer for MsNavWindows and MsNavDraws as it is.  ages, a binary32 store in the same layout:
+ *                 (float)age for every cell, countable or not.  Each may be NULL.
+ *   an env without cells, and one with more cells than max_cells says, leaves its stores alone: its clock moves as above and
+ *                 its counts, sums and oldest are 0.
+ * One launch, one workgroup per map - the map's only writer - with the call's marks as a bitmask in LDS, as MsNavSeen's:
+ * max_cells sizes it, more than 2^20 is MS_EUNSUPPORTED.  No global atomics, nothing allocated, nothing waits, and the clock
+ * lives on the device: the call can be captured in a HIP graph, and every replay is a later tick.  Every argument is checked in
+ * full before the launch (MS_EINVAL). */
+typedef struct MsNavAges {
+    int                  n_maps;       /* S: maps per env                                                              */
+    int                  n_viewers;    /* P: viewers per env (advance; else ignored)                                   */
+    int                  n_rays;       /* R: rays per viewer (advance; else ignored)                                   */
+    const float*         origins;      /* (N, P, 2); 8-byte aligned                                                    */
+    const float*         dirs;         /* (N, P, R, 2); 8-byte aligned                                                 */
+    const float*         distances;    /* (N, P, R)                                                                    */
+    const int*           slot;         /* (N, P) the map each viewer marks; NULL: P == S, viewer k map k               */
+    float                max_range;    /* metres, finite and > 0                                                       */
+    const unsigned char* reset;        /* (N, S) non-zero: clear the map and its clock first; NULL: none               */
+    const unsigned char* countable;    /* (starts[N],) bit 0: the cell counts; NULL: the grid's free_cells             */
+    int                  advance;      /* 1: the clock ticks and the rays mark; 0: the survey alone                    */
+    int                  threshold;    /* T >= 1: a cell is stale at age >= T                                          */
+    float*               last;         /* S*starts[N] floats in / out: map (n, s) at S*starts[n] + s*nx*ny             */
+    int*                 clock;        /* (N, S) in / out                                                              */
+    int*                 swept;        /* (N, S) out, or NULL                                                          */
+    int*                 gained;       /* (N, S) out, or NULL                                                          */
+    long long*           idle;         /* (N, S) out, or NULL; 8-byte aligned                                          */
+    int*                 oldest;       /* (N, S) out, or NULL                                                          */
+    long long*           total_age;    /* (N, S) out, or NULL; 8-byte aligned                                          */
+    int*                 n_stale;      /* (N, S) out, or NULL                                                          */
+    unsigned char*       stale;        /* S*starts[N] bytes out, in last's layout, or NULL                             */
+    float*               ages;         /* S*starts[N] floats out, in last's layout, or NULL                            */
+    int                  max_cells;    /* the largest nx*ny of any env (0: no env has cells), at most 2^20             */
+} MsNavAges;
+int ms_nav_ages(const MsNavGrid* grid, const MsNavAges* ages, void* hip_stream);
+
 /* Map windows: per-cell stores of the nav grid - free cells, seen maps, distance fields, any marks - cropped, turned and
  * resampled into images through affine views: the egocentric map of an agent, its heading up, of what IT has seen.  As above
  * every step is one binary32 operation in the order given, without contraction, divisions correctly rounded;

@@ -114,6 +114,13 @@ int ms_debug_nav_cost_variant(int variant);
 int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable, int n_maps, int n_viewers, int n_rays,
                      const float* origins, const float* dirs, const float* distances, const int* slot, float max_range,
                      const unsigned char* reset, unsigned char* maps, int* gained, int* total);
+/* Host instantiation of the age maps' rule (kernels/navage.h over navseen.h's ray and sample - the very functions every lane of
+ * nav_age_kernel evaluates - with a call's marks as the kernel's bitmask, and the merge and the survey stated serially) for ONE
+ * env on HOST arrays, one call of ms_nav_ages: geom = (jx0, iy0, nx, ny); every pointer of `ages` is host memory and holds the
+ * one env's share - countable (ny x nx bytes, required), origins (P, 2), dirs (P, R, 2), distances (P, R), slot (P), reset (S),
+ * last, stale and ages (S, ny, nx), clock and the counts (S); max_cells is not read.  Returns what ms_nav_ages would: MS_OK,
+ * MS_EINVAL for arguments it would refuse (a NULL countable too), MS_EUNSUPPORTED for more than 2^20 cells. */
+int ms_host_nav_ages(const int* geom, float cell, const MsNavAges* ages);
 /* Host instantiation of the map windows' rule (kernels/navwindow.h: the sample point, the cell, the channel value and the
  * pixel's sum - the very functions every lane of nav_window_kernel evaluates) for one whole call of ms_nav_windows on HOST
  * arrays: every pointer of `grid` (geom, starts; free_cells is checked, not read) and of `windows` (views, the layers' values and

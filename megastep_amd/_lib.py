@@ -149,6 +149,14 @@ class MsNavSeen(C.Structure):
                 ('maps', C.c_void_p), ('gained', C.c_void_p), ('total', C.c_void_p), ('max_cells', C.c_int)]
 
 
+class MsNavAges(C.Structure):
+    _fields_ = [('n_maps', C.c_int), ('n_viewers', C.c_int), ('n_rays', C.c_int), ('origins', C.c_void_p), ('dirs', C.c_void_p),
+                ('distances', C.c_void_p), ('slot', C.c_void_p), ('max_range', C.c_float), ('reset', C.c_void_p), ('countable', C.c_void_p),
+                ('advance', C.c_int), ('threshold', C.c_int), ('last', C.c_void_p), ('clock', C.c_void_p), ('swept', C.c_void_p),
+                ('gained', C.c_void_p), ('idle', C.c_void_p), ('oldest', C.c_void_p), ('total_age', C.c_void_p), ('n_stale', C.c_void_p),
+                ('stale', C.c_void_p), ('ages', C.c_void_p), ('max_cells', C.c_int)]
+
+
 class MsNavLayer(C.Structure):
     _fields_ = [('values', C.c_void_p), ('is_float', C.c_int), ('n_fields', C.c_int), ('field', C.c_void_p)]
 
@@ -244,6 +252,7 @@ PROTOTYPES = {
     'ms_nav_waypoints': (_int, [_p(MsNavGrid), _p(MsNavWaypoints), _ptr]),
     'ms_nav_paths': (_int, [_p(MsNavGrid), _p(MsNavPaths), _ptr]),
     'ms_nav_seen': (_int, [_p(MsNavGrid), _p(MsNavSeen), _ptr]),
+    'ms_nav_ages': (_int, [_p(MsNavGrid), _p(MsNavAges), _ptr]),
     'ms_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows), _ptr]),
     'ms_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws), _ptr]),
     'ms_nav_regions': (_int, [_p(MsNavGrid), _p(MsNavRegions), _ptr]),
@@ -291,6 +300,7 @@ PROTOTYPES = {
     'ms_host_nav_cost_capacity': (_int, [_ptr]),
     'ms_debug_nav_cost_variant': (_int, [_int]),
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
+    'ms_host_nav_ages': (_int, [_ptr, _flt, _p(MsNavAges)]),
     'ms_host_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows)]),
     'ms_host_nav_draws': (_int, [_p(MsNavGrid), _p(MsNavDraws)]),
     'ms_host_nav_regions': (_int, [_p(MsNavGrid), _p(MsNavRegions)]),

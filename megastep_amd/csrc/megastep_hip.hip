@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navbasin.h, navseen.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navbasin.h, navseen.h, navage.h, navwindow.h, navdraw.h.
 //
-// Twenty-six kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Twenty-seven kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -55,6 +55,10 @@
 //                   each.   (no counterpart)
 //   nav_seen_kernel     seen maps: one workgroup per map marks the grid cells under the samples of its viewers' depth rays in
 //                   an LDS bitmask, merges it into the map and counts the countable cells seen for the first time.
+//                                                            (no counterpart)
+//   nav_age_kernel      age maps: the same scheme with a binary32 tick per cell - the marked set takes the map's clock, the
+//                   countable cells swept, gained and their summed age are counted, and a survey behind a second barrier gives
+//                   every cell's age, the largest and the summed age and the stale cells.
 //                                                            (no counterpart)
 //   nav_window_kernel   map windows: per-cell stores (free cells, seen maps, fields) cropped and turned into images through
 //                   affine views, every image and channel in one launch, a lane a pixel.
@@ -177,6 +181,7 @@ struct Probe {
 #include "kernels/navpath.h"
 #include "kernels/navbasin.h"
 #include "kernels/navseen.h"
+#include "kernels/navage.h"
 #include "kernels/navwindow.h"
 #include "kernels/navdraw.h"
 #include "kernels/envlogic.h"
@@ -1166,6 +1171,48 @@ int ms_host_nav_seen(const int* geom, float cell, const unsigned char* countable
     seen_serial(NavCells{geom[0], geom[1], geom[2], geom[3], cell}, countable, n_maps, n_viewers, n_rays, origins, dirs, distances, slot,
                 max_range, reset, maps, gained, total);
     return 0;
+}
+
+// Age maps (navage.h): the same discipline, and the seen maps' limit; one check serves the launch and the host instantiation.
+static int nav_ages_check(const MsNavAges* v) {
+    if (!v || v->n_maps < 1 || !v->last || !v->clock || v->threshold < 1 || (v->advance != 0 && v->advance != 1) ||
+        !(v->max_range > 0.f) || !(v->max_range < INFINITY) || v->max_cells < 0 ||
+        ((uintptr_t)v->last % 4) || ((uintptr_t)v->clock % 4) || ((uintptr_t)v->swept % 4) || ((uintptr_t)v->gained % 4) ||
+        ((uintptr_t)v->idle % 8) || ((uintptr_t)v->oldest % 4) || ((uintptr_t)v->total_age % 8) || ((uintptr_t)v->n_stale % 4) ||
+        ((uintptr_t)v->ages % 4)) return MS_EINVAL;
+    if (v->advance && (v->n_viewers < 1 || v->n_rays < 1 || !v->origins || !v->dirs || !v->distances ||
+                       !(v->slot || v->n_viewers == v->n_maps) || ((uintptr_t)v->origins % 8) || ((uintptr_t)v->dirs % 8) ||
+                       ((uintptr_t)v->distances % 4) || ((uintptr_t)v->slot % 4))) return MS_EINVAL;
+    return v->max_cells > NAV_SEEN_MAX_CELLS ? MS_EUNSUPPORTED : MS_OK;
+}
+static NavAgeArgs nav_age_args(const MsNavAges* v, const unsigned char* countable) {
+    return NavAgeArgs{v->origins, v->dirs, v->distances, v->slot, v->reset, countable, v->last, v->clock, v->swept, v->gained, v->idle,
+                      v->oldest, v->total_age, v->n_stale, v->stale, v->ages, v->n_maps, v->advance ? v->n_viewers : 0,
+                      v->advance ? v->n_rays : 0, v->max_cells, v->advance, v->threshold, v->max_range};
+}
+
+int ms_nav_ages(const MsNavGrid* grid, const MsNavAges* v, void* stream) {
+    if (!nav_grid_ok(grid)) return MS_EINVAL;
+    const int status = nav_ages_check(v);
+    if (status != MS_OK) return status;
+    const long long total = (long long)grid->n_envs*v->n_maps;
+    if (total > 0x7fffffffLL || (v->advance && (long long)grid->n_envs*v->n_viewers > 0x7fffffffLL/v->n_rays)) return MS_EUNSUPPORTED;
+    const size_t lds = (size_t)((v->max_cells + 31)/32)*sizeof(unsigned);                   // (at most 128 KiB of the CU's 160)
+    if (lds > 64*1024 - 256 && hipFuncSetAttribute(reinterpret_cast<const void*>(nav_age_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)lds) != hipSuccess) return hip_fail(hipGetLastError());
+    hipLaunchKernelGGL(nav_age_kernel, dim3((unsigned)total), dim3(WG), lds, (hipStream_t)stream, nav_args(grid),
+                       nav_age_args(v, v->countable ? v->countable : grid->free_cells));
+    return launch_status();
+}
+
+int ms_host_nav_ages(const int* geom, float cell, const MsNavAges* v) {
+    if (!geom || !(cell > 0.f) || !(cell < INFINITY)) return MS_EINVAL;
+    const int status = nav_ages_check(v);
+    if (status != MS_OK) return status;
+    if (!v->countable) return MS_EINVAL;
+    if (geom[2] > 0 && geom[3] > 0 && (long long)geom[2]*geom[3] > NAV_SEEN_MAX_CELLS) return MS_EUNSUPPORTED;
+    age_serial(NavCells{geom[0], geom[1], geom[2], geom[3], cell}, nav_age_args(v, v->countable));
+    return MS_OK;
 }
 
 // Map windows (navwindow.h): the same discipline; the channels go into the kernel's arguments by value.

@@ -3,3 +3,4 @@ from .explorer import Explorer  # noqa: F401
 from .deathmatch import Deathmatch  # noqa: F401
 from .pointgoal import PointGoal  # noqa: F401
 from .floorcoverage import FloorCoverage  # noqa: F401
+from .patrol import Patrol  # noqa: F401

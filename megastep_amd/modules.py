@@ -864,6 +864,98 @@ class Frontiers:
         return self.fallback(self.own.waypoints(self.core.agents.positions, lookahead=lookahead), shared)
 
 
+class Idleness:
+
+    def __init__(self, core, grid, max_range=10., shared=False, threshold=64, countable=None):
+        """Floor idleness: how long ago every cell of the nav grid was last under one of an agent's depth rays, and a reward for
+        looking again at floor that was left alone (:func:`cuda.age_maps`; no counterpart in the reference) - what patrol,
+        surveillance and search tasks are made of, and unlike :class:`Coverage` never used up. ``grid`` is the scenery's
+        :func:`cuda.nav_grid`; rays are followed for at most ``max_range`` metres; a countable cell (default: the grid's free
+        cells) is stale once it has not been seen for ``threshold`` steps. Every agent has a map of its own; ``shared=True``
+        gives an env's agents ONE map, which any of them starting over clears, and each of them the map's whole reward. One
+        launch behind the render's, nothing waits for the host; the maps' clocks live on the device."""
+        self.core, self.grid = core, grid
+        self.max_range, self.shared, self.threshold = float(max_range), bool(shared), int(threshold)
+        n, s = core.n_envs, 1 if shared else core.n_agents
+        self.ages = cuda.age_maps(grid, s, countable, self.threshold)
+        self.space = spaces.MultiVector(core.n_agents, 2)
+        self._slot = torch.zeros((n, core.n_agents), dtype=torch.int32, device=core.device) if shared else None
+        self._sweep = cuda.Sweep(torch.zeros((n, s), dtype=torch.int32, device=core.device), torch.zeros((n, s), dtype=torch.int32, device=core.device),
+                                 torch.zeros((n, s), dtype=torch.int64, device=core.device))
+        self._area = torch.tensor(grid.cell, dtype=torch.float32, device=core.device)**2
+
+    def _per_agent(self, t):
+        return t.expand(-1, self.core.n_agents) if self.shared else t
+
+    def __call__(self, frame, reset=None):
+        """(n_env, n_agent) float32: ``(idle - swept).float()*cell**2/threshold`` over the countable cells ``frame`` - a render of
+        the agents as they stand, with its ``distances`` - passes over: ``swept`` how many they are, ``idle`` the steps since each
+        was last seen, summed (:class:`cuda.Sweep`). Floor seen again a step later pays nothing; floor left alone for
+        ``threshold`` steps pays its area in square metres, less a ``threshold``-th; floor never seen pays by the map's clock.
+        ``reset`` (n_env, n_agent) bool: the agents that started over this step; their maps and clocks are cleared first."""
+        if reset is not None and self.shared:
+            reset = reset.any(-1, keepdim=True)
+        sweep = self.ages.mark_render(self.core.agents, frame, slot=self._slot, max_range=self.max_range, reset=reset, out=self._sweep)
+        return self._per_agent((sweep.idle - sweep.swept).float()*self._area/self.threshold)
+
+    def mean_age(self):
+        """(n_env, n_agent) float32: the mean age, in steps, of the countable floor of each agent('s map)."""
+        return self._per_agent(self.ages.mean_age())
+
+    def oldest(self):
+        """(n_env, n_agent) int32: the worst age, in steps, of the countable floor of each agent('s map)."""
+        return self._per_agent(self.ages.oldest)
+
+    def observation(self):
+        """(n_env, n_agent, 2): ``min(mean_age/threshold, 1)`` and ``min(oldest/threshold, 1)``."""
+        both = torch.stack([self.mean_age(), self.oldest().float()], -1)
+        return (both/self.threshold).clamp(max=1.)
+
+    def state(self, e=0):
+        """(S, ny, nx) float32: a copy of the ages in env ``e``'s maps, row 0 at the lowest y."""
+        return torch.stack([self.ages.age_image(e, s) for s in range(self.ages.n_maps)]).clone()
+
+
+class Patrols:
+
+    def __init__(self, core, idleness, refresh=8, cost=None):
+        """How far every agent has to walk to the nearest stale floor of its map, and which way (no counterpart in the
+        reference): :class:`Frontiers`' interface - so :class:`PathFollower` takes it unchanged - over the stale cells of an
+        :class:`Idleness`' maps (:meth:`cuda.AgeMaps.stale_fields`), one field per map. A field is recomputed every ``refresh``
+        steps of its agent and when the agent starts over; with ``idleness.shared`` an env has one field, which all its agents
+        follow. An agent whose map holds no stale cell gets NaN. ``cost``: a cost layer as :func:`cuda.cost_fields` takes it.
+        Nothing waits for the host: which fields are due is decided on the device, so a call can sit in a HIP graph."""
+        self.core, self.idleness, self.refresh = core, idleness, int(refresh)
+        if self.refresh < 1:
+            raise RuntimeError(f'refresh must be a positive integer; got {refresh}')
+        self._steps = torch.zeros((core.n_envs, core.n_agents), dtype=torch.long, device=core.device)
+        self._field = idleness._slot                    # (n_env, n_agent) zeros when the map is shared, else None: agent k field k
+        self.cost = cost
+        self.fields = idleness.ages.stale_fields(cost=cost)
+
+    def __call__(self, reset=None):
+        """Recomputes the fields that are due: those of the agents marked in the (n_env, n_agent) bool ``reset`` and those whose
+        agent has taken a multiple of ``refresh`` steps since. Call once per step, after the maps were marked and surveyed."""
+        if reset is not None:
+            self._steps.masked_fill_(reset, 0)
+        due = self._steps % self.refresh == 0
+        self._steps += 1
+        self.due = due                                  # ((n_env, n_agent) bool: whose field was due at this call)
+        if self.idleness.shared:
+            due = due.any(-1, keepdim=True)
+        self.fields.update(due)
+        return self.fields
+
+    def distance(self):
+        """(n_env, n_agent): how far every agent has to walk to the nearest stale floor; +inf where there is none it can reach."""
+        return self.fields.at(self.core.agents.positions, goal=self._field)
+
+    def waypoints(self, lookahead=16):
+        """(n_env, n_agent, 2): where every agent should head for now to walk to the nearest stale floor; NaN where
+        :meth:`distance` is +inf."""
+        return self.fields.waypoints(self.core.agents.positions, goal=self._field, lookahead=lookahead)
+
+
 class BestViews:
 
     def __init__(self, core, coverage, n_candidates=16, max_range=None, band=(.25, 3.), refresh=8, seed=0):

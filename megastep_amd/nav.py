@@ -1,6 +1,7 @@
 """Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
 floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
-they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navwindow.h``,
+they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navage.h``
+- when each cell was last seen -, ``csrc/kernels/navwindow.h``,
 ``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), the cells in sight of a
 point (``csrc/kernels/navview.h``), the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``), and the distance
 to the nearest wall, per cell and per point (``csrc/kernels/navclear.h``).
@@ -594,11 +595,11 @@ def mark_costs(layer, on=1., off=256., where=True, gate=None, out=None):
     256, and a route crosses unknown floor only when there is no other. ``gate``: a byte layer of the same layout; where its byte
     is 0 the layer says nothing and the cell costs 1. Plain element-wise torch: capturable; ``out``: the tensor of an earlier call to
     write the result into (the mask and the chosen values on the way are torch's temporaries)."""
-    layer = _layer(layer)
+    layer = _layer(layer, byte=True)
     if layer.is_float:
         raise RuntimeError('mark_costs reads a byte layer (uint8 or bool), not float32')
     if gate is not None:
-        gate = _layer(gate)
+        gate = _layer(gate, byte=True)
         if gate.is_float or gate.values.shape != layer.values.shape:
             raise RuntimeError("a gate must be a byte layer (uint8 or bool) of the layer's own layout")
     out = _cost_out(layer.values, out)
@@ -607,6 +608,38 @@ def mark_costs(layer, on=1., off=256., where=True, gate=None, out=None):
     if gate is not None:
         value = torch.where(gate.values != 0, value, 1.)
     return out.copy_(value)
+
+
+def _viewers(grid, S, origins, dirs, distances, slot, max_range, reset):
+    """The argument rule of the calls that mark what rays pass over in ``S`` maps an env (:meth:`SeenMaps.mark`,
+    :meth:`AgeMaps.mark`); returns (N, P, R, slot, reset) as the kernels read them."""
+    _check(origins, 'origins', torch.float32, 3)
+    _check(dirs, 'dirs', torch.float32, 4)
+    _check(distances, 'distances', torch.float32, 3)
+    n, p = origins.shape[:2]
+    r = dirs.shape[2]
+    if n != grid.n_envs or origins.shape[2] != 2 or p < 1 or r < 1 or dirs.shape != (n, p, r, 2) or distances.shape != (n, p, r):
+        raise RuntimeError(f'origins, dirs and distances must be (N, P, 2), (N, P, R, 2) and (N, P, R) with N = {grid.n_envs}; got '
+                           f'{tuple(origins.shape)}, {tuple(dirs.shape)} and {tuple(distances.shape)}')
+    if slot is not None:
+        slot = _index(slot, 'slot', n, p)
+    elif p != S:
+        raise RuntimeError(f'without slot, the viewers must be one per map ({S}); got {p}')
+    reset = _mask(reset, n, S, 'S', 'reset')
+    if not (0 < max_range < float('inf')):
+        raise RuntimeError(f'max_range must be a positive number; got {max_range}')
+    return n, p, r, slot, reset
+
+
+def _render_rays(agents, frame, config):
+    """(origins, dirs, distances) of the agents' own camera rays and the ``distances`` of ``frame``, a render of them."""
+    from .rays import camera_rays
+    dirs = camera_rays(agents, config=config)
+    n, a, r = dirs.shape[:3]
+    distances = getattr(frame, 'distances', None) if not isinstance(frame, dict) else frame.get('distances')
+    if distances is None:
+        raise RuntimeError('the frame has no distances: render with fields that include them')
+    return agents.positions, dirs, distances.reshape(n, a, r)
 
 
 #: the most cells an env may have for :func:`seen_maps`: the kernel keeps a call's marks as one bit per cell in LDS (128 KiB)
@@ -646,21 +679,7 @@ class SeenMaps:
         a wall runs through, has its centre within the clearance of that wall, so it is blocked and never counts. One launch, a
         workgroup a map, no host synchronisation. The rule: include/megastep_hip.h (``MsNavSeen``), DESIGN.md 3.16."""
         grid, S = self.grid, self.n_maps
-        _check(origins, 'origins', torch.float32, 3)
-        _check(dirs, 'dirs', torch.float32, 4)
-        _check(distances, 'distances', torch.float32, 3)
-        n, p = origins.shape[:2]
-        r = dirs.shape[2]
-        if n != grid.n_envs or origins.shape[2] != 2 or p < 1 or r < 1 or dirs.shape != (n, p, r, 2) or distances.shape != (n, p, r):
-            raise RuntimeError(f'origins, dirs and distances must be (N, P, 2), (N, P, R, 2) and (N, P, R) with N = {grid.n_envs}; got '
-                               f'{tuple(origins.shape)}, {tuple(dirs.shape)} and {tuple(distances.shape)}')
-        if slot is not None:
-            slot = _index(slot, 'slot', n, p)
-        elif p != S:
-            raise RuntimeError(f'without slot, the viewers must be one per map ({S}); got {p}')
-        reset = _mask(reset, n, S, 'S', 'reset')
-        if not (0 < max_range < float('inf')):
-            raise RuntimeError(f'max_range must be a positive number; got {max_range}')
+        n, p, r, slot, reset = _viewers(grid, S, origins, dirs, distances, slot, max_range, reset)
         if grid._max_cells > SEEN_MAX_CELLS:
             raise RuntimeError(f'an env of this grid has {grid._max_cells} cells; seen maps take at most {SEEN_MAX_CELLS} an env')
         dev = _require_gpu(origins, dirs, distances, self.values, self.countable, self.totals, grid.free, *_some(slot, reset))
@@ -677,13 +696,7 @@ class SeenMaps:
         """:meth:`mark` for the agents' own camera rays: ``frame`` is what :func:`render` (or ``modules.render``) returned for
         ``agents``, with its ``distances``; the directions are :func:`camera_rays`' and the origins the agents' positions. The
         viewers are the agents: by default agent k marks map k."""
-        from .rays import camera_rays
-        dirs = camera_rays(agents, config=config)
-        n, a, r = dirs.shape[:3]
-        distances = getattr(frame, 'distances', None) if not isinstance(frame, dict) else frame.get('distances')
-        if distances is None:
-            raise RuntimeError('the frame has no distances: render with fields that include them')
-        return self.mark(agents.positions, dirs, distances.reshape(n, a, r), slot=slot, max_range=max_range, reset=reset, out=out)
+        return self.mark(*_render_rays(agents, frame, config), slot=slot, max_range=max_range, reset=reset, out=out)
 
 
     def frontier_fields(self, mask=None, out=None, passes=False, cost=None):
@@ -715,6 +728,15 @@ def seen_maps(grid, n_maps, countable=None):
     if not isinstance(n_maps, int) or n_maps < 1:
         raise RuntimeError(f'n_maps must be a positive integer; got {n_maps}')
     dev = grid.free.device
+    countable, n_countable = _countable(grid, countable, 'seen maps')
+    n = grid.n_envs
+    values = torch.zeros(max(n_maps*grid.n_cells, 1), dtype=torch.uint8, device=dev)
+    return SeenMaps(grid, n_maps, values, countable, torch.zeros((n, n_maps), dtype=torch.int32, device=dev), n_countable)
+
+
+def _countable(grid, countable, what):
+    """The countable mask of a set of maps (``what``) as the kernels read it, and (N,) int32: how many cells of each env count."""
+    dev = grid.free.device
     if countable is None:
         countable = grid.free
     else:
@@ -722,13 +744,135 @@ def seen_maps(grid, n_maps, countable=None):
             raise RuntimeError(f'countable must be a uint8 or bool tensor of {tuple(grid.free.shape)}, one entry per cell of the grid')
         countable = countable.to(device=dev, dtype=torch.uint8).contiguous()
     if grid._max_cells > SEEN_MAX_CELLS:
-        raise RuntimeError(f'seen maps take at most {SEEN_MAX_CELLS} cells an env')
-    n = grid.n_envs
-    values = torch.zeros(max(n_maps*grid.n_cells, 1), dtype=torch.uint8, device=dev)
+        raise RuntimeError(f'{what} take at most {SEEN_MAX_CELLS} cells an env')
     starts = torch.as_tensor(grid._host_starts, device=dev)
     sums = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (countable[:grid.n_cells] & 1).long().cumsum(0)])
-    n_countable = (sums[starts[1:]] - sums[starts[:-1]]).int()
-    return SeenMaps(grid, n_maps, values, countable, torch.zeros((n, n_maps), dtype=torch.int32, device=dev), n_countable)
+    return countable, (sums[starts[1:]] - sums[starts[:-1]]).int()
+
+
+#: the last tick an :class:`AgeMaps`' clock reaches: binary32 holds every tick up to here exactly
+AGE_MAX_TICK = 2**24
+
+
+class Sweep:
+    """Result of :meth:`AgeMaps.mark`, each (N, S): ``swept`` int32, the countable cells the call's rays passed over; ``gained``
+    int32, those of them never seen since the map was cleared; ``idle`` int64, the sum over them of the ticks since each was last
+    seen (its whole clock for one never seen)."""
+
+    def __init__(self, swept, gained, idle):
+        self.swept, self.gained, self.idle = swept, gained, idle
+
+
+class AgeMaps:
+    """Result of :func:`age_maps`: for each env ``S`` maps, map (n, s) holding one float32 per cell of env n's grid - the tick of
+    the map's clock at which a depth ray of one of its viewers last passed over the cell, 0 where none has since the map was
+    cleared. ``last`` is the flat float32 store in :class:`SeenMaps`' layout; ``clock`` (N, S) int32 the tick of each map's last
+    :meth:`mark`, on the device; ``countable`` the uint8 mask of the cells that count, ``n_countable`` (N,) int32 how many there
+    are; ``threshold`` the age from which a cell is stale. The survey's outputs, rewritten in place by every surveying call:
+    ``oldest`` (N, S) int32 and ``total_age`` (N, S) int64 - the largest and the summed age of the countable cells, ``n_stale``
+    (N, S) int32 - how many of them are stale, ``stale`` - a byte store in the maps' layout, 1 on the stale countable cells, and
+    ``ages`` - a float32 store of every cell's age (None when made with ``ages=False``). As a layer (:func:`cell_layer`,
+    :func:`map_channel`, :func:`cell_draws`) the maps present ``ages``, and as a gate or a byte layer (:func:`mark_costs`)
+    ``stale``."""
+
+    def __init__(self, grid, n_maps, threshold, last, clock, countable, n_countable, oldest, total_age, n_stale, stale, ages):
+        self.grid, self.n_maps, self.threshold = grid, int(n_maps), int(threshold)
+        self.last, self.clock, self.countable, self.n_countable = last, clock, countable, n_countable
+        self.oldest, self.total_age, self.n_stale, self.stale, self.ages = oldest, total_age, n_stale, stale, ages
+
+    def image(self, e, s=0):
+        """(ny, nx) float32 view of the ticks of map ``s`` of env ``e``, row 0 at the lowest y (:meth:`NavGrid.image`'s convention)."""
+        return _store_view(self.grid, self.last, self.n_maps, e, s)
+
+    def age_image(self, e, s=0):
+        """(ny, nx) float32 view of the ages the last survey found in map ``s`` of env ``e``."""
+        if self.ages is None:
+            raise RuntimeError('these maps were made with ages=False: there is no store of ages')
+        return _store_view(self.grid, self.ages, self.n_maps, e, s)
+
+    def stale_image(self, e, s=0):
+        """(ny, nx) bool view of the stale cells the last survey found in map ``s`` of env ``e``."""
+        return _store_view(self.grid, self.stale.view(torch.bool), self.n_maps, e, s)
+
+    def mean_age(self):
+        """(N, S) float32: the mean age of its env's countable cells at each map's last survey; 0 where nothing is countable."""
+        return self.total_age.float()/self.n_countable.clamp(min=1)[:, None].float()
+
+    def _call(self, dev, advance, survey, p, r, origins, dirs, distances, slot, max_range, reset, sweep):
+        some = lambda t: _ptr(t) if survey else None
+        _launch(dev, 'ages', self.grid, _lib.MsNavAges(
+            self.n_maps, p, r, _ptr(origins), _ptr(dirs), _ptr(distances), _ptr(slot), float(max_range), _ptr(reset), self.countable.data_ptr(),
+            int(advance), self.threshold, self.last.data_ptr(), self.clock.data_ptr(), _ptr(sweep and sweep.swept), _ptr(sweep and sweep.gained),
+            _ptr(sweep and sweep.idle), some(self.oldest), some(self.total_age), some(self.n_stale), some(self.stale), some(self.ages),
+            self.grid._max_cells))
+
+    def _tensors(self):
+        return [self.last, self.clock, self.countable, self.oldest, self.total_age, self.n_stale, self.stale, self.grid.free, *_some(self.ages)]
+
+    def mark(self, origins, dirs, distances, slot=None, max_range=10., reset=None, survey=True, out=None):
+        """Moves every map's clock on by one tick, stamps the cells the rays pass over with it and returns a :class:`Sweep`.
+        ``origins``, ``dirs``, ``distances``, ``slot``, ``max_range``: as :meth:`SeenMaps.mark`'s, and the cells marked are the
+        ones it would mark. ``reset`` (N, S) bool: maps cleared, and their clocks set to 0, before the tick. ``survey``: the
+        survey behind the marks, in the same launch - :attr:`oldest`, :attr:`total_age`, :attr:`n_stale`, :attr:`stale` and
+        :attr:`ages` are rewritten, a cell just marked with age 0; without it they keep what the last survey left. ``out``: the
+        :class:`Sweep` of an earlier call to write into; then nothing is allocated. One launch, a workgroup a map, no host
+        synchronisation; the clock lives on the device, so in a HIP graph every replay is a later tick. A clock stops at
+        ``AGE_MAX_TICK``. The rule: include/megastep_hip.h (``MsNavAges``), DESIGN.md 3.25."""
+        grid, S = self.grid, self.n_maps
+        n, p, r, slot, reset = _viewers(grid, S, origins, dirs, distances, slot, max_range, reset)
+        dev = _require_gpu(origins, dirs, distances, *self._tensors(), *_some(slot, reset))
+        if out is None:
+            out = Sweep(torch.empty((n, S), dtype=torch.int32, device=dev), torch.empty((n, S), dtype=torch.int32, device=dev),
+                        torch.empty((n, S), dtype=torch.int64, device=dev))
+        elif not isinstance(out, Sweep) or not _fits(out.swept, (n, S), torch.int32) or not _fits(out.gained, (n, S), torch.int32) or \
+                not _fits(out.idle, (n, S), torch.int64) or {out.swept.device, out.gained.device, out.idle.device} != {dev}:
+            raise RuntimeError("`out` must be a Sweep of contiguous (N, S) int32, int32 and int64 tensors on the maps' device")
+        self._call(dev, True, survey, p, r, origins, dirs, distances, slot, max_range, reset, out)
+        return out
+
+    def mark_render(self, agents, frame, slot=None, max_range=10., reset=None, survey=True, out=None, config=None):
+        """:meth:`mark` for the agents' own camera rays, as :meth:`SeenMaps.mark_render`: ``frame`` is what :func:`render` (or
+        ``modules.render``) returned for ``agents``, with its ``distances``. By default agent k marks map k."""
+        return self.mark(*_render_rays(agents, frame, config), slot=slot, max_range=max_range, reset=reset, survey=survey, out=out)
+
+    def survey(self):
+        """The survey alone: nothing is marked and the clocks stand; :attr:`oldest`, :attr:`total_age`, :attr:`n_stale`,
+        :attr:`stale` and :attr:`ages` are rewritten from the maps as they are. One launch; returns the maps."""
+        dev = _require_gpu(*self._tensors())
+        self._call(dev, False, True, 0, 0, None, None, None, None, 1., None, None)
+        return self
+
+    def stale_fields(self, cost=None, mask=None, out=None, passes=False):
+        """The walking distance from every cell to the nearest stale cell of each map, as a :class:`SeededFields` of one field per
+        map: ``seeded_fields(grid, self.stale, self.n_maps)`` - or, with ``cost`` (a cost layer as :func:`cost_fields` takes it),
+        a :class:`CostFields`. The fields read :attr:`stale` by reference: :meth:`SeededFields.update` follows the surveys. A
+        field without a seed - nothing is stale - is +inf throughout. ``mask``, ``out``, ``passes``: as :func:`seeded_fields`."""
+        if cost is not None:
+            return cost_fields(self.grid, self.stale, self.n_maps, cost, mask=mask, out=out, passes=passes)
+        return seeded_fields(self.grid, self.stale, self.n_maps, mask=mask, out=out, passes=passes)
+
+    def stale_regions(self, mask=None, out=None, passes=False):
+        """The clusters the stale cells of each map fall into, as a :class:`Regions` of one field per map:
+        ``regions(grid, self.stale, self.n_maps)``, read by reference. ``mask``, ``out``, ``passes``: as :func:`regions`."""
+        return regions(self.grid, self.stale, self.n_maps, mask=mask, out=out, passes=passes)
+
+
+def age_maps(grid, n_maps, countable=None, threshold=64, ages=True):
+    """``n_maps`` age maps per env on the :func:`nav_grid`, all never seen and their clocks at 0: WHEN each cell of the floor was
+    last passed over by a depth ray of an agent (:meth:`AgeMaps.mark`) - idleness, for patrol, surveillance and search tasks, which
+    do not end when the floor runs out as those on :func:`seen_maps` do. ``countable``: as :func:`seen_maps`'; ``threshold``: the
+    age, in ticks, from which a countable cell is stale (an integer, at least 1); ``ages=False``: no store of every cell's age
+    (the survey then writes four bytes a cell less)."""
+    if not isinstance(n_maps, int) or n_maps < 1:
+        raise RuntimeError(f'n_maps must be a positive integer; got {n_maps}')
+    if not isinstance(threshold, int) or isinstance(threshold, bool) or threshold < 1:
+        raise RuntimeError(f'threshold must be an integer of at least 1; got {threshold}')
+    countable, n_countable = _countable(grid, countable, 'age maps')
+    new = _new(grid.free.device)
+    n, size = grid.n_envs, max(n_maps*grid.n_cells, 1)
+    return AgeMaps(grid, n_maps, threshold, new((size,), torch.float32, 0.), new((n, n_maps), torch.int32, 0), countable, n_countable,
+                   new((n, n_maps), torch.int32, 0), new((n, n_maps), torch.int64, 0), new((n, n_maps), torch.int32, 0),
+                   new((size,), torch.uint8, 0), new((size,), torch.float32, 0.) if ages else None)
 
 
 #: the most channels, samples a side and pixels a side of :func:`local_maps`
@@ -755,7 +899,7 @@ def cell_layer(values, n_fields=1, field=None):
     can be the source. ``field``: an (N, P) integer tensor naming the store each view reads; without it store 0 is read when
     ``n_fields`` is 1 and view p reads store p when ``n_fields`` is the number of views. A :class:`NavGrid` (its ``free``), a
     :class:`SeenMaps`, a :class:`DistanceFields` and a :class:`SeededFields` are layers as they are, with their own number of
-    stores, and so are a :class:`Regions` (its ``areas``, square metres), a :class:`ViewFields` (its ``values``, a store a
+    stores, an :class:`AgeMaps` too (its ``ages``, in ticks; as a gate its ``stale``), and so are a :class:`Regions` (its ``areas``, square metres), a :class:`ViewFields` (its ``values``, a store a
     viewpoint) and a :class:`ClearanceFields` (its ``values``, metres to the nearest wall: one float store);
     ``cell_layer(maps, field=slot)`` gives one of them a ``field``."""
     if isinstance(values, CellLayer):
@@ -764,6 +908,10 @@ def cell_layer(values, n_fields=1, field=None):
         values, n_fields = values.free, 1
     elif isinstance(values, SeenMaps):
         values, n_fields = values.values, values.n_maps
+    elif isinstance(values, AgeMaps):
+        if values.ages is None:
+            raise RuntimeError('these age maps were made with ages=False: as a float layer they have nothing to present')
+        values, n_fields = values.ages, values.n_maps
     elif isinstance(values, _Fields):
         values, n_fields = values.values, values.n_goals
     elif isinstance(values, Regions):
@@ -782,7 +930,11 @@ def cell_layer(values, n_fields=1, field=None):
     return CellLayer(values, n_fields, None if field is None else _index(field, 'field'))
 
 
-def _layer(x):
+def _layer(x, byte=False):
+    """``x`` as a :class:`CellLayer`. ``byte``: the place asks for a byte layer - a gate, marks to price - and an :class:`AgeMaps`,
+    which as a float layer presents its ages, presents its stale cells there."""
+    if byte and isinstance(x, AgeMaps):
+        return cell_layer(x.stale, x.n_maps)
     return x if isinstance(x, CellLayer) else cell_layer(x)
 
 
@@ -800,7 +952,7 @@ def map_channel(source, where=True, scale=None, gate=None, outside=0., hidden=0.
     ``gate``: a byte layer with a ``field`` of its own; where its byte is 0 the channel shows ``hidden`` - ``grid.free`` gated by
     an agent's seen map is the floor that agent knows. ``outside``: what a sample beyond the env's grid shows."""
     source = _layer(source)
-    gate = None if gate is None else _layer(gate)
+    gate = None if gate is None else _layer(gate, byte=True)
     if gate is not None and gate.is_float:
         raise RuntimeError('a gate must be a byte layer (uint8 or bool), not float32')
     if source.is_float:
@@ -942,7 +1094,7 @@ def cell_draws(grid, source, n_sets, n_draws, lo=None, hi=None, where=True, gate
     if not isinstance(seed, int) or not 0 <= seed < 2**64:
         raise RuntimeError(f'seed must be an integer in 0..2^64 - 1; got {seed}')
     source = _layer(source)
-    gate = None if gate is None else _layer(gate)
+    gate = None if gate is None else _layer(gate, byte=True)
     if gate is not None and gate.is_float:
         raise RuntimeError('a gate must be a byte layer (uint8 or bool), not float32')
     if source.is_float:

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance|cost] [--large]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance|cost|ages] [--large]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -82,6 +82,11 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       formulation of the same rule under the inflation layer (the first `--torch-envs` envs, scaled; compared for equal bits);
       PointGoal(envs, margin=.3): expert() + step() eager and replayed as a HIP graph, next to PointGoal(envs); and PointGoal(64),
       300 steps under the expert with and without margin=.3: arrivals, steps the follower spent stuck, mean clearance under the agents.
+  (g) age maps, at `--envs` envs x 1 agent x 256 rays, medians of twice `--repeats` calls back to back: SeenMaps.mark on a rendered
+      frame - the yardstick - and on the same frame one AgeMaps.mark (ms_nav_ages) without the survey, with it, and with it and the
+      store of ages; the survey alone; the torch formulation of the same rule (the first `--torch-envs` envs from empty maps,
+      scaled; every output compared for equality); Patrol(envs).step next to FloorCoverage(envs).step, eager and replayed as a HIP
+      graph; and Patrol(64), 300 steps under expert() and under random actions: the final mean and worst idleness, in steps.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -324,6 +329,36 @@ def torch_seen(grid, countable, origins, dirs, distances, max_range, envs):
         seen[torch.where(ok, cell, torch.full_like(cell, n_cells))] = True                 # the scatter (the spare slot: skipped samples)
         new = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (seen[:n_cells] & counts).long().cumsum(0)])   # the second pass
         return seen[:n_cells], (new[starts[1:]] - new[starts[:-1]]).int()
+    return run
+
+
+def torch_ages(grid, countable, origins, dirs, distances, max_range, threshold, envs):
+    """The age maps' rule by tensor ops for the first `envs` envs, one viewer and one map each - the marked set as torch_seen makes
+    it, then a dense pass over every cell: returns run(last, clock) -> (last, clock, swept, gained, idle, oldest, total_age, n_stale,
+    stale, ages), the maps flat over those envs and the numbers (envs,)."""
+    dev = origins.device
+    marks = torch_seen(grid, countable, origins, dirs, distances, max_range, envs)
+    starts = torch.as_tensor(grid._host_starts[:envs + 1], device=dev)
+    n_cells = int(grid._host_starts[envs])
+    env = torch.repeat_interleave(torch.arange(envs, device=dev), starts[1:] - starts[:-1])
+    counts = (countable[:n_cells] & 1).bool()
+
+    def per_env(values):
+        return torch.zeros(envs, dtype=torch.int64, device=dev).index_add_(0, env, values.long())
+
+    def run(last, clock):
+        marked, _ = marks()
+        now = (clock.long() + 1).clamp(max=2**24)
+        tick = now[env]
+        age = tick - last.long()
+        counted = marked & counts
+        swept, gained, idle = per_env(counted), per_env(counted & (last == 0)), per_env(torch.where(counted, age, 0))
+        last = torch.where(marked, tick.float(), last)
+        age = tick - last.long()
+        stale = counts & (age >= threshold)
+        oldest = torch.zeros(envs, dtype=torch.int64, device=dev).scatter_reduce_(0, env, torch.where(counts, age, 0), 'amax')
+        return (last, now.int(), swept.int(), gained.int(), idle, oldest.int(), per_env(torch.where(counts, age, 0)), per_env(stale).int(),
+                stale.to(torch.uint8), age.float())
     return run
 
 
@@ -633,12 +668,12 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance', 'cost'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance', 'cost', 'ages'))
     ap.add_argument('--large', action='store_true')
     ap.add_argument('--json')
     args = ap.parse_args()
-    from megastep_amd import core, cubicasa, cuda, modules, scene
-    from megastep_amd.demo import Explorer, FloorCoverage, PointGoal
+    from megastep_amd import arrdict, core, cubicasa, cuda, modules, scene
+    from megastep_amd.demo import Explorer, FloorCoverage, Patrol, PointGoal
 
     np.random.seed(0); torch.manual_seed(0)
     pool = cubicasa.sample(args.distinct, split='all', n_unique=args.distinct, workers=16, context='subprocess', **(dict(large=True) if args.large else {}))
@@ -1202,6 +1237,64 @@ def main():
             torch.manual_seed(3); np.random.seed(3)
             out['cost_follower_' + name] = score = follower_score(PointGoal(64, geometries=small, **kw), 300)
             print(f'(k) PointGoal(64), 300 steps under the expert, {name}: {score}')
+
+    if want('ages'):
+        sc = scene.scenery(geoms, 1, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        frame = cuda.render(sc, c.agents, fields=('distances',))
+        origins, dirs, distances = c.agents.positions, cuda.camera_rays(c.agents), frame.distances
+        repeats = 2*args.repeats                                         # (medians of 20 calls back to back at the defaults)
+        seen = cuda.seen_maps(grid, 1)
+        buffer = seen.mark(origins, dirs, distances)
+        med, lo, hi = timed(lambda: seen.mark(origins, dirs, distances, out=buffer), repeats, args.warmup)
+        out['ages_seen_mark'] = dict(seconds=med, min=lo, max=hi, rays=256)
+        print(f'(g) SeenMaps.mark, {args.envs} x 1 x 256 rays, the yardstick: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        ages, lean = cuda.age_maps(grid, 1), cuda.age_maps(grid, 1, ages=False)
+        sweep = ages.mark(origins, dirs, distances)
+        first = {k: getattr(sweep, k).clone() for k in ('swept', 'gained', 'idle')}
+        first.update({k: getattr(ages, k).clone() for k in ('last', 'clock', 'oldest', 'total_age', 'n_stale', 'stale', 'ages')})
+        lean.mark(origins, dirs, distances)
+        for name, maps, survey in (('mark(survey=False)', ages, False), ('mark + survey, no store of ages', lean, True), ('mark + survey + ages', ages, True)):
+            med, lo, hi = timed(lambda: maps.mark(origins, dirs, distances, survey=survey, out=sweep), repeats, args.warmup)
+            key = 'ages_mark' + ('' if not survey else '_survey' if maps is lean else '_survey_ages')
+            out[key] = dict(seconds=med, min=lo, max=hi, rays=256, over_seen_mark=med/out['ages_seen_mark']['seconds'])
+            print(f"(g) {name}, {args.envs} x 1 x 256 rays: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}], {out[key]['over_seen_mark']:.2f} x SeenMaps.mark")
+        med, lo, hi = timed(lambda: ages.survey(), repeats, args.warmup)
+        out['ages_survey'] = dict(seconds=med, min=lo, max=hi)
+        print(f'(g) survey alone, {args.envs} maps: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        k = min(args.torch_envs, args.envs)
+        run = torch_ages(grid, ages.countable, origins, dirs, distances, 10., ages.threshold, k)
+        n_cells = int(grid._host_starts[k])
+        blank = (torch.zeros(n_cells, dtype=torch.float32, device='cuda'), torch.zeros(k, dtype=torch.int32, device='cuda'))
+        got = dict(zip(('last', 'clock', 'swept', 'gained', 'idle', 'oldest', 'total_age', 'n_stale', 'stale', 'ages'), run(*blank)))
+        same = all(torch.equal(v, first[name][:n_cells] if v.shape[0] == n_cells else first[name][:k, 0]) for name, v in got.items())
+        med, lo, hi = timed(lambda: run(*blank), max(args.repeats//3, 2), 1)
+        out['ages_torch'] = dict(envs=k, seconds=med, scaled_seconds=med*args.envs/k, equal=bool(same))
+        print(f'(g) torch samples + scatter + dense pass, {k} envs: {med*1e3:.2f} ms -> {med*args.envs/k*1e3:.1f} ms for {args.envs}; equal results: {same}')
+        del sc, c, grid, seen, ages, lean
+        torch.cuda.empty_cache()
+        for name, make in (('FloorCoverage', lambda: FloorCoverage(args.envs, geometries=geoms)), ('Patrol', lambda: Patrol(args.envs, geometries=geoms))):
+            env = make()
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out['ages_' + name] = dict(eager_seconds=eager, graph_seconds=graphed)
+            print(f'(g) {name}({args.envs}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+        small = cubicasa.sample(64, seed=7, n_unique=64)
+        for policy in ('expert', 'random'):
+            torch.manual_seed(3); np.random.seed(3)
+            env = Patrol(64, geometries=small, max_lifespan=10**6)
+            world = env.reset()
+            for _ in range(300):
+                decision = env.expert() if policy == 'expert' else arrdict.arrdict(actions=torch.randint(0, 7, (64, 1), device='cuda'))
+                world = env.step(decision)
+            out['ages_rollout_' + policy] = score = dict(mean_idleness=float(env.ages.mean_age().mean()), worst_idleness=float(env.ages.oldest.float().mean()),
+                                                       reward=float(world.reward.mean()))
+            print(f'(g) Patrol(64), 300 steps, {policy}: {score}')
 
     if args.json:
         with open(args.json, 'w') as f:
