@@ -659,6 +659,54 @@ int ms_nav_cost_fields(const MsNavGrid* grid, const MsNavCostFields* fields, voi
 int ms_nav_cost_waypoints(const MsNavGrid* grid, const MsNavCostWaypoints* waypoints, void* hip_stream);
 int ms_nav_cost_paths(const MsNavGrid* grid, const MsNavCostPaths* paths, void* hip_stream);
 
+/* Pulled paths: a field's path straightened by sight - a handful of corners where the chain is a staircase of hundreds of cells,
+ * and the length of the walk along them, the any-angle reference length a score such as SPL divides by.  Grid, fields, start, hop,
+ * chain and sight are MsNavWaypoints' as they stand; on a seeded field (goals NULL) they are MsNavSeedFields', on a cost field
+ * (costs not NULL) MsNavCostFields', hopping with the weights of the cell left.  Nothing is restated: the kernel calls the same
+ * functions.  tests/test_navpull_host.py restates the rule in numpy (pull_rule) and the kernel - and its serial host statement,
+ * ms_host_nav_pull - are held to EQUALITY with it.
+ *   points        P_0 = p, P_1 = x_0, P_2 = x_1, ... the points MsNavPaths would write with unlimited max_points; the last is
+ *                 the goal q, on a seeded field the seed's centre.  n is their number: cells = n is MsNavPaths' count, negated
+ *                 for a broken chain.  A broken chain is pulled over the points it got.
+ *   pull          with reach R (1..1024), a = 0 and V = [0], while a < n-1: k is the LARGEST index in (a, min(a + R, n-1)] that
+ *                 is admissible - a+1 always is (the chain's own step; the leg from p to its anchor when a = 0), any k > a+1
+ *                 when sight(P_a, P_k) holds, MsNavWaypoints' sight unchanged.  Append k to V and set a = k.  R = 1 gives the
+ *                 chain itself.
+ *   vertices      (N, P, M, 2): the first M of P_V[.], NaN in the slots not written.  indices (N, P, M) or NULL: V, -1 beyond.
+ *   counts        (N, P): len(V) however long, negated when the chain is broken, 0 without a path.  cells (N, P) or NULL: as above.
+ *   lengths       (N, P): from +0.f, in vertex order, L = fl(L + sqrtf(fl(fl(dx*dx) + fl(dy*dy)))), dx, dy the binary32
+ *                 differences of consecutive vertices, without contraction; +inf without a path, the length got for a broken
+ *                 chain.
+ *   mask          (N, P) bytes read on the device, or NULL: a point whose byte is 0 keeps every output as it stands.
+ * This is greedy string pulling, not the exact Euclidean shortest path: a pulled path is an upper bound on the true shortest walk
+ * and - a step of the chain being always admissible, and a sight never longer than the chain it replaces - at most the chain's
+ * own length up to rounding.  Its segments keep sight's clearance argument (MsNavWaypoints, "sight"); the first, from p to x_0,
+ * and every step of the chain itself keep the edges' (MsNavGrid).
+ * Every loop is bounded by the input: hops by the env's cells (D falls at every hop), anchors by n, candidates by reach, samples
+ * by 2^20 - a stale or garbage field ends, as it does for MsNavPaths.  One launch, a wavefront a path; nothing is allocated,
+ * nothing waits, no float atomics: the call can be captured in a HIP graph.  Every argument is checked in full before the launch
+ * (MS_EINVAL): what MsNavPaths refuses, a reach outside 1..1024, a max_points outside 2..2^20, an n_costs that is neither 0, 1
+ * nor G, costs NULL with n_costs != 0 (or given with n_costs == 0), a NULL vertices, counts or lengths, a misaligned pointer. */
+typedef struct MsNavPulls {
+    int                  n_points;     /* P                                                                            */
+    const float*         points;       /* (N, P, 2); 8-byte aligned                                                    */
+    const int*           goal;         /* (N, P) which of the env's fields each point follows; NULL: P == G            */
+    const float*         fields;       /* as MsNavFields.fields (or MsNavSeedFields', MsNavCostFields')                */
+    const float*         goals;        /* (N, G, 2) the fields' goals; 8-byte aligned.  NULL: seeded fields            */
+    int                  n_goals;      /* G of `fields` and `goals`                                                    */
+    const float*         costs;        /* as MsNavCostFields.costs; NULL: unweighted                                   */
+    int                  n_costs;      /* 0 (costs NULL), 1 or G                                                       */
+    int                  reach;        /* R, 1..1024: how many points ahead an anchor looks                            */
+    int                  max_points;   /* M, 2..2^20: vertices written per path                                        */
+    const unsigned char* mask;         /* (N, P) non-zero: pull this point; NULL: all.  Read on the device only.       */
+    float*               vertices;     /* (N, P, M, 2) out                                                             */
+    int*                 indices;      /* (N, P, M) out, or NULL                                                       */
+    int*                 counts;       /* (N, P) out                                                                   */
+    int*                 cells;        /* (N, P) out, or NULL                                                          */
+    float*               lengths;      /* (N, P) out                                                                   */
+} MsNavPulls;
+int ms_nav_pulls(const MsNavGrid* grid, const MsNavPulls* pulls, void* hip_stream);
+
 /* Seen maps: which cells of the nav grid the depth rays of an agent (of any viewer) have passed over - floor coverage for
  * exploration rewards, a mask to hand a policy or to draw.  As above every step is one binary32 operation in the order given,
  * without contraction, divisions and roots correctly rounded; tests/test_navseen_host.py restates it in numpy (seen_rule) and

@@ -106,6 +106,18 @@ int ms_host_nav_cost_path(const int* geom, float cell, const unsigned char* free
                           const float* point, int max_points, float* points);
 int ms_host_nav_cost_capacity(int* capacities);
 int ms_debug_nav_cost_variant(int variant);
+/* The pulled paths' rule (MsNavPulls) stated serially over the path rule's own functions (kernels/navpull.h: nav_pull_serial over
+ * nav_start, nav_hop and nav_sight) for ONE env and ONE query on HOST arrays: geom, free_cells, D and point as above; goal (x, y),
+ * or NULL for a seeded field; costs (ny x nx floats), or NULL for unweighted hops.  Writes max_points x 2 floats to vertices (NaN
+ * in the slots not written), max_points ints to indices (or NULL; -1 beyond) and the length (+inf without a path); returns
+ * MsNavPulls' counts.  -2: reach outside 1..1024; max_points outside 2..2^20, a NULL vertices or length: 0, nothing written.
+ * ms_debug_nav_pull_scheme: how ms_nav_pulls' waves test a window's sights - 0 = a lane a candidate, each walking its own samples;
+ * 1 = candidate after candidate, its samples a lane each (the waypoint kernel's scheme); -1 = the library's own choice (0);
+ * anything else: MS_EINVAL.  Per calling thread; A/B runs and tests - either setting produces the same bits. */
+int ms_host_nav_pull(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal,
+                     const float* costs, const float* point, int reach, int max_points, float* vertices, int* indices,
+                     float* length);
+int ms_debug_nav_pull_scheme(int scheme);
 /* Host instantiation of the seen maps' rule (kernels/navseen.h: the ray, the sample - the very functions every lane of
  * nav_seen_kernel evaluates) for ONE env on HOST arrays, one call of ms_nav_seen: geom = (jx0, iy0, nx, ny), countable
  * (ny x nx bytes), origins (P, 2), dirs (P, R, 2), distances (P, R), slot (P) or NULL (then P == S), reset (S) or NULL, maps

@@ -143,6 +143,13 @@ class MsNavCostPaths(C.Structure):
     _fields_ = MsNavSeedPaths._fields_ + [('costs', C.c_void_p), ('n_costs', C.c_int)]
 
 
+class MsNavPulls(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('goal', C.c_void_p), ('fields', C.c_void_p), ('goals', C.c_void_p),
+                ('n_goals', C.c_int), ('costs', C.c_void_p), ('n_costs', C.c_int), ('reach', C.c_int), ('max_points', C.c_int),
+                ('mask', C.c_void_p), ('vertices', C.c_void_p), ('indices', C.c_void_p), ('counts', C.c_void_p), ('cells', C.c_void_p),
+                ('lengths', C.c_void_p)]
+
+
 class MsNavSeen(C.Structure):
     _fields_ = [('n_maps', C.c_int), ('n_viewers', C.c_int), ('n_rays', C.c_int), ('origins', C.c_void_p), ('dirs', C.c_void_p),
                 ('distances', C.c_void_p), ('slot', C.c_void_p), ('max_range', C.c_float), ('reset', C.c_void_p), ('countable', C.c_void_p),
@@ -270,7 +277,8 @@ PROTOTYPES = {
     'ms_nav_cost_fields': (_int, [_p(MsNavGrid), _p(MsNavCostFields), _ptr]),
     'ms_nav_cost_waypoints': (_int, [_p(MsNavGrid), _p(MsNavCostWaypoints), _ptr]),
     'ms_nav_cost_paths': (_int, [_p(MsNavGrid), _p(MsNavCostPaths), _ptr]),
-    'ms_wallgrid_scan': (_int, [_p(MsScenery), _p(MsWallGridParent), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr]),
+    'ms_nav_pulls': (_int, [_p(MsNavGrid), _p(MsNavPulls), _ptr]),
+    'ms_wallgrid_scan':(_int, [_p(MsScenery), _p(MsWallGridParent), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr]),
     'ms_wallgrid_fill': (_int, [_p(MsScenery), _ptr, _int, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # the test hooks
     'ms_host_ray_interval': (None, [_f32p, _f32p, _int, _flt, _flt, _int, _i32p, _i32p]),
@@ -299,6 +307,8 @@ PROTOTYPES = {
     'ms_host_nav_cost_path': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
     'ms_host_nav_cost_capacity': (_int, [_ptr]),
     'ms_debug_nav_cost_variant': (_int, [_int]),
+    'ms_host_nav_pull': (_int, [_ptr, _flt, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr, _ptr, _ptr]),
+    'ms_debug_nav_pull_scheme': (_int, [_int]),
     'ms_host_nav_seen': (_int, [_ptr, _flt, _ptr, _int, _int, _int, _ptr, _ptr, _ptr, _ptr, _flt, _ptr, _ptr, _ptr, _ptr]),
     'ms_host_nav_ages': (_int, [_ptr, _flt, _p(MsNavAges)]),
     'ms_host_nav_windows': (_int, [_p(MsNavGrid), _p(MsNavWindows)]),

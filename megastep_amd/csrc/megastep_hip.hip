@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navbasin.h, navseen.h, navage.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navseen.h, navage.h, navwindow.h, navdraw.h.
 //
-// Twenty-seven kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Twenty-eight kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -53,6 +53,9 @@
 //   nav_waypoint_kernel, nav_path_kernel   which way to go on those fields: one wavefront per point descends the field a
 //                   neighbour a lane and picks the furthest of the next cells the point can see; and whole paths, a lane
 //                   each.   (no counterpart)
+//   nav_pull_kernel     pulled paths: one wavefront per path walks the whole chain once through a ring in LDS and straightens
+//                   it by sight, the candidates of a window a lane each: a handful of vertices, and the path's length.
+//                                                            (no counterpart)
 //   nav_seen_kernel     seen maps: one workgroup per map marks the grid cells under the samples of its viewers' depth rays in
 //                   an LDS bitmask, merges it into the map and counts the countable cells seen for the first time.
 //                                                            (no counterpart)
@@ -115,6 +118,7 @@ thread_local int g_last_step_fused = 0;     // ms_debug_last_step_fused: did thi
 thread_local int g_last_render_groups = 0;  // ms_debug_last_render_groups: the NG this thread's last ms_render launched
 thread_local int g_overhead_cull = 1;       // ms_debug_overhead_cull: 0 = ms_overhead's tiles keep every line
 thread_local int g_nav_cost_variant = -1;   // ms_debug_nav_cost_variant: where ms_nav_cost_fields' launch keeps the multipliers (-1: its own choice)
+thread_local int g_nav_pull_scheme = -1;    // ms_debug_nav_pull_scheme: how ms_nav_pulls' waves test their sights (-1: its own choice)
 thread_local int g_nav_clear_cull = -1;     // ms_debug_nav_clear_cull: which culls ms_nav_clearance's launch runs (-1: its own choice)
 thread_local long long g_clear_folds = 0, g_clear_pairs = 0;      // ms_host_nav_clear_folds: the last ms_host_nav_clearance's
 thread_local int g_render_order = 1;        // ms_debug_render_order: 0 = MsAgents.schedule is neither sorted nor followed
@@ -179,6 +183,7 @@ struct Probe {
 #include "kernels/navregion.h"
 #include "kernels/navview.h"
 #include "kernels/navpath.h"
+#include "kernels/navpull.h"
 #include "kernels/navbasin.h"
 #include "kernels/navseen.h"
 #include "kernels/navage.h"
@@ -999,6 +1004,33 @@ int ms_nav_cost_paths(const MsNavGrid* grid, const MsNavCostPaths* np, void* str
                             np->costs, np->n_costs, stream);
 }
 
+// Pulled paths (navpull.h, MsNavPulls): one entry for fields of goals, seeded fields (goals NULL) and cost fields (costs not NULL).
+// The library's scheme is a lane a candidate; the waypoint kernel's, a lane a sample, stays reachable through
+// ms_debug_nav_pull_scheme for A/B runs.
+int ms_nav_pulls(const MsNavGrid* grid, const MsNavPulls* np, void* stream) {
+    if (!np || !nav_follow_ok(grid, np->n_points, np->points, np->goal, np->fields, np->n_goals) || ((uintptr_t)np->goals % 8) ||
+        np->reach < 1 || np->reach > NAV_PULL_REACH || np->max_points < 2 || np->max_points > NAV_PULL_POINTS ||
+        !np->vertices || !np->counts || !np->lengths || ((uintptr_t)np->vertices % 4) || ((uintptr_t)np->indices % 4) ||
+        ((uintptr_t)np->counts % 4) || ((uintptr_t)np->cells % 4) || ((uintptr_t)np->lengths % 4) ||
+        (np->n_costs == 0 ? np->costs != nullptr : !nav_costs_ok(np->costs, np->n_costs, np->n_goals))) return MS_EINVAL;
+    const long long total = (long long)grid->n_envs*np->n_points;
+    if ((total + WAVES - 1)/WAVES > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    const NavPullArgs u{NavPathArgs{np->points, np->goal, np->fields, np->goals, grid->free_cells, nullptr, nullptr, np->vertices, np->counts,
+                                    np->n_points, np->n_goals, 0, np->max_points, total, np->costs, np->n_costs},
+                        np->mask, np->indices, np->cells, np->lengths, np->reach, nav_pull_ring(np->reach)};
+    static void (*const kernels[2][2])(NavArgs, NavPullArgs) = {                    // [weighted][a lane a candidate, a lane a sample]
+        {nav_pull_kernel<false, false>, nav_pull_kernel<false, true>}, {nav_pull_kernel<true, false>, nav_pull_kernel<true, true>}};
+    hipLaunchKernelGGL(kernels[np->costs != nullptr][g_nav_pull_scheme == 1], dim3((unsigned)((total + WAVES - 1)/WAVES)), dim3(WG),
+                       (size_t)WAVES*u.ring*sizeof(int), (hipStream_t)stream, nav_args(grid), u);
+    return launch_status();
+}
+
+int ms_debug_nav_pull_scheme(int scheme) {
+    if (scheme < -1 || scheme > 1) return MS_EINVAL;
+    g_nav_pull_scheme = scheme;
+    return MS_OK;
+}
+
 static bool nav_host_env(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal, const float* point,
                          NavEnv& g) {
     if (!geom || !free_cells || !D || !goal || !point || !(cell > 0.f) || geom[2] <= 0 || geom[3] <= 0) return false;
@@ -1066,6 +1098,24 @@ int ms_host_nav_cost_path(const int* geom, float cell, const unsigned char* free
     }
     g.cost = costs;
     return nav_path(g, nav_seeded(), point[0], point[1], (long long)g.nx*g.ny, max_points, points);
+}
+
+int ms_host_nav_pull(const int* geom, float cell, const unsigned char* free_cells, const float* D, const float* goal, const float* costs,
+                     const float* point, int reach, int max_points, float* vertices, int* indices, float* length) {
+    if (reach < 1 || reach > NAV_PULL_REACH) return -2;
+    if (max_points < 2 || max_points > NAV_PULL_POINTS || !vertices || !length) return 0;
+    NavEnv g;
+    if (!nav_host_env(geom, cell, free_cells, D, point, point, g)) {
+        for (int k = 0; k < max_points; k++) {
+            vertices[2*k] = vertices[2*k + 1] = NAN;
+            if (indices) indices[k] = -1;
+        }
+        *length = INFINITY;
+        return 0;
+    }
+    g.cost = costs;
+    return nav_pull_serial(g, goal ? nav_goal(g, goal[0], goal[1]) : nav_seeded(), point[0], point[1], reach, max_points, vertices, indices,
+                           nullptr, *length);
 }
 
 // The seeded relaxation on host arrays, and - costs not NULL - the weighted one: the kernel's fill and per-cell functions, swept.

@@ -26,7 +26,7 @@ def books(before, now, reset, stranded, arrive, bonus):
 class PointGoal:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, arrive=.5, bonus=1., max_lifespan=512,
-                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, margin=None, **kwargs):
+                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, margin=None, spl=False, **kwargs):
         """``cell``: the nav grid's cell size; ``arrive``: how near the goal counts as there, metres (walking distance);
         ``bonus``: the reward for arriving; ``max_lifespan``: episodes end after a random number of steps up to this
         (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`.
@@ -38,7 +38,9 @@ class PointGoal:
         spawn lands in a closet. ``margin``: metres; then the expert does not follow the shortest path, which runs along the walls at
         exactly the body's clearance, but the cheapest route (:class:`~megastep_amd.modules.Routes`) over an inflation layer -
         ``inflation_costs(clearance_fields(grid, scenery, margin), margin)`` - that makes a cell dearer the nearer a wall comes
-        within ``margin``: it keeps to the middle where there is room. Reward and observations do not change."""
+        within ``margin``: it keeps to the middle where there is room. Reward and observations do not change. ``spl=True``: the
+        world also carries ``spl`` (n_env, n_agent) - :class:`~megastep_amd.modules.SPL` over the goals: the score of every
+        episode that ended at this step, NaN elsewhere - and ``env.spl`` holds the module."""
         if one_region and not sampled_spawns:
             raise RuntimeError('one_region gates the sampled spawns: it needs sampled_spawns=True')
         if geometries is None:
@@ -72,6 +74,7 @@ class PointGoal:
             self._routes = modules.Routes(c, self.grid, self._goals, self.costs)
         # (under momentum a narrow cone walks a third less far: DESIGN 3.15)
         self._follower = modules.PathFollower(c, self._goals if self._routes is None else self._routes, cone=15.)
+        self.spl = modules.SPL(c, self._goals) if spl else None
         self.action_space = self._mover.space
         self.obs_space = dotdict.dotdict(rgb=self._rgb.space, d=self._depth.space, goal=self._goals.space)
 
@@ -104,7 +107,11 @@ class PointGoal:
         self._over.copy_(self._lifespans(ended))
         frame = modules.render(self.core, observers=(self._rgb, self._depth), fields=())
         obs = arrdict.arrdict(rgb=self._rgb(frame), d=self._depth(frame), goal=self._goals.observation())
-        return arrdict.arrdict(obs=obs, reset=reset.any(-1), reward=reward)
+        world = arrdict.arrdict(obs=obs, reset=reset.any(-1), reward=reward)
+        if self.spl is not None:
+            # (an episode ends when its agent arrives, is stranded or outlives its lifespan: only the first scores above 0)
+            world['spl'] = self.spl(reset, (now < self.arrive) & ~self._goals.stranded, self._over)
+        return world
 
     @torch.no_grad()
     def reset(self):

@@ -1,6 +1,7 @@
 """Navigation grids, shortest-path distance fields (to a goal, or to the nearest of a set of cells), waypoints and paths on the
 floorplans, the seen maps of the depth rays, windows of all of them as images round the agents, and random draws of cells by what
-they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navseen.h``, ``csrc/kernels/navage.h``
+they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``csrc/kernels/navpull.h`` - paths pulled straight
+and their lengths -, ``csrc/kernels/navseen.h``, ``csrc/kernels/navage.h``
 - when each cell was last seen -, ``csrc/kernels/navwindow.h``,
 ``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), the cells in sight of a
 point (``csrc/kernels/navview.h``), the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``), and the distance
@@ -259,6 +260,42 @@ class _Fields:
         _launch(dev, *self._paths_call(p, points.data_ptr(), _ptr(goal), max_points, pts.data_ptr(), counts.data_ptr()))
         return Paths(pts, counts)
 
+    def pulled(self, points, goal=None, reach=256, max_points=64, indices=False, mask=None, out=None):
+        """The path from each of ``points`` (N, P, 2) to its goal (``goal``: as :meth:`at`) pulled straight, as a
+        :class:`PulledPaths`: of :meth:`paths`' points - the point, the centres of the cells down the field, the goal - the
+        corners that are left when, from the point on, each vertex is followed by the furthest of the next ``reach`` (1..1024)
+        points it can see in a straight line clear of the walls (:meth:`waypoints`' sight), or by the chain's own next point when
+        it sees none. A handful of vertices where the chain has hundreds of points, the first ``max_points`` (2..2^20) of them
+        written; and ``lengths``, the length of the walk along ALL of them: some 5 % below :meth:`at`, whose 8-direction metric
+        overstates open floor - the any-angle length a score such as SPL divides by. This is greedy string pulling: an upper
+        bound on the true shortest walk, not that walk. ``reach=1`` keeps every point: the chain itself.
+
+        ``indices=True`` also records each vertex's index in the chain; ``mask`` (N, P) bool: pull only the marked points, the
+        others keep what ``out`` held; ``out``: a :class:`PulledPaths` of an earlier call with the same shapes to rewrite in
+        place. One launch, a wavefront a path, no host synchronisation: the call can be captured in a HIP graph. The rule:
+        include/megastep_hip.h (``MsNavPulls``), DESIGN.md 3.26."""
+        if not isinstance(reach, int) or not 1 <= reach <= 1024:
+            raise RuntimeError(f'reach must be an integer in 1..1024; got {reach}')
+        if not isinstance(max_points, int) or not 2 <= max_points <= 2**20:
+            raise RuntimeError(f'max_points must be an integer in 2..2^20; got {max_points}')
+        n, p = _points(self.grid, points)
+        mask = _mask(mask, n, p, 'P')
+        if out is not None and (not isinstance(out, PulledPaths) or out.points.shape != (n, p, max_points, 2) or
+                                (out.indices is None) == bool(indices)):
+            raise RuntimeError(f'`out` must be the PulledPaths of a call with the same shapes: ({n}, {p}) paths of {max_points} vertices, '
+                               f'{"with" if indices else "without"} indices')
+        n, p, goal, dev = self._queries(points, goal)
+        if out is None:
+            new = _new(dev)
+            out = PulledPaths(new((n, p, max_points, 2), torch.float32, float('nan')), new((n, p), torch.int32, 0),
+                              new((n, p), torch.float32, float('inf')), new((n, p), torch.int32, 0),
+                              new((n, p, max_points), torch.int32, -1) if indices else None)
+        _require_gpu(points, *out._own(), *_some(mask))
+        _launch(dev, *self._pulls_call((p, points.data_ptr(), _ptr(goal)),
+                                       (reach, max_points, _ptr(mask), out.points.data_ptr(), _ptr(out.indices), out.counts.data_ptr(),
+                                        out.cells.data_ptr(), out.lengths.data_ptr())))
+        return out
+
 
 class DistanceFields(_Fields):
     """Result of :func:`distance_fields`: for each env ``G`` fields, field (n, g) holding for every cell of env n's grid the
@@ -278,6 +315,9 @@ class DistanceFields(_Fields):
 
     def _paths_call(self, p, points, goal, max_points, out, counts):
         return 'paths', self.grid, _lib.MsNavPaths(p, points, goal, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, max_points, out, counts)
+
+    def _pulls_call(self, query, rest):
+        return 'pulls', self.grid, _lib.MsNavPulls(*query, self.values.data_ptr(), self.goals.data_ptr(), self.n_goals, None, 0, *rest)
 
     def update(self, goals=None, mask=None):
         """Recomputes the fields marked in the (N, G) bool ``mask`` (default all) in place - for ``goals`` (N, G, 2), which are
@@ -319,6 +359,21 @@ class Paths:
         return self.points[e, k, :n]
 
 
+class PulledPaths(Paths):
+    """Result of :meth:`DistanceFields.pulled`: a :class:`Paths` of the pulled paths' vertices - ``points`` (N, P, M, 2), NaN in the
+    slots not written; ``counts`` (N, P) int32: the vertices of the whole pulled path, 0 where no path exists, negated where the
+    field did not lead to its goal - and ``lengths`` (N, P) float32: the length of the walk along all the vertices, +inf where no
+    path exists; ``cells`` (N, P) int32: the points of the chain that was pulled, :meth:`DistanceFields.paths`' count; ``indices``
+    (N, P, M) int32 or None: each written vertex's index in that chain, -1 in the slots not written."""
+
+    def __init__(self, points, counts, lengths, cells, indices=None):
+        super().__init__(points, counts)
+        self.lengths, self.cells, self.indices = lengths, cells, indices
+
+    def _own(self):
+        return _some(self.points, self.counts, self.lengths, self.cells, self.indices)
+
+
 def _nav_fields_call(fields, mask):
     grid = fields.grid
     n, g = fields.goals.shape[:2]
@@ -332,7 +387,8 @@ def distance_fields(grid, goals, mask=None, out=None, passes=False):
     float32 world points) the distance from every free cell to the goal along the grid's 8-connected graph - straight steps
     of ``cell``, diagonal steps of ``cell*1.41421356`` that cut no corner - joined to the goal by the straight legs from the
     free cells round it. The 8-connected metric is up to 8 % longer than the true (any-angle) shortest path in open space;
-    an agent that heads for :meth:`DistanceFields.waypoints` cuts the staircase short and walks less than the field says.
+    an agent that heads for :meth:`DistanceFields.waypoints` cuts the staircase short and walks less than the field says, and
+    :meth:`DistanceFields.pulled` gives the length of the path pulled straight.
     One launch, one workgroup per field, the field relaxed in LDS until nothing changes; the result does not depend on the
     order of relaxation and equals Dijkstra's with binary32 additions bit for bit (include/megastep_hip.h, ``MsNavGrid``).
 
@@ -389,6 +445,9 @@ class SeededFields(_Fields):
 
     def _paths_call(self, p, points, goal, max_points, out, counts):
         return 'seed_paths', self.grid, _lib.MsNavSeedPaths(p, points, goal, self.values.data_ptr(), self.n_goals, max_points, out, counts)
+
+    def _pulls_call(self, query, rest):
+        return 'pulls', self.grid, _lib.MsNavPulls(*query, self.values.data_ptr(), None, self.n_goals, None, 0, *rest)
 
     def basins(self, ids=None, n_ids=0, mask=None, out=None, passes=False):
         """:func:`basins` of these fields: which seed each cell leads to."""
@@ -486,6 +545,9 @@ class CostFields(SeededFields):
     def _paths_call(self, p, points, goal, max_points, out, counts):
         return 'cost_paths', self.grid, _lib.MsNavCostPaths(p, points, goal, self.values.data_ptr(), self.n_goals, max_points, out, counts,
                                                             self.cost.data_ptr(), self.n_costs)
+
+    def _pulls_call(self, query, rest):
+        return 'pulls', self.grid, _lib.MsNavPulls(*query, self.values.data_ptr(), None, self.n_goals, self.cost.data_ptr(), self.n_costs, *rest)
 
     def basins(self, ids=None, n_ids=0, mask=None, out=None, passes=False):
         """Not served: :func:`basins` follow the unweighted hop, which does not descend a weighted field."""

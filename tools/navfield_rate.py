@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance|cost|ages] [--large]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance|cost|ages|pulls] [--large]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -87,6 +87,11 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       store of ages; the survey alone; the torch formulation of the same rule (the first `--torch-envs` envs from empty maps,
       scaled; every output compared for equality); Patrol(envs).step next to FloorCoverage(envs).step, eager and replayed as a HIP
       graph; and Patrol(64), 300 steps under expert() and under random actions: the final mean and worst idleness, in steps.
+  (h) pulled paths, at `--envs` envs x 1 point, medians of 20 calls back to back: one DistanceFields.pulled (ms_nav_pulls) at reach 64
+      and at 256, under either of the wave's sight schemes (a lane a candidate - the library's - and a lane a sample), next to
+      paths(max_points=256) and waypoints() on the same fields and points; the mean vertices, and the pulled length over the
+      chain's and over `at`; PointGoal(envs, spl=True).step eager and replayed as a HIP graph, next to the plain env; and
+      PointGoal(64, spl=True), 300 steps under expert() and under random actions: the mean SPL of the episodes that ended.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -668,7 +673,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance', 'cost', 'ages'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance', 'cost', 'ages', 'pulls'))
     ap.add_argument('--large', action='store_true')
     ap.add_argument('--json')
     args = ap.parse_args()
@@ -1295,6 +1300,65 @@ def main():
             out['ages_rollout_' + policy] = score = dict(mean_idleness=float(env.ages.mean_age().mean()), worst_idleness=float(env.ages.oldest.float().mean()),
                                                        reward=float(world.reward.mean()))
             print(f'(g) Patrol(64), 300 steps, {policy}: {score}')
+
+    if want('pulls'):
+        from megastep_amd import _lib
+        sc = scene.scenery(geoms, 1, device='cuda', bake=False)
+        c = core.Core(sc, res=64)
+        grid = cuda.nav_grid(sc, config=c.config)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 1, 4), dtype=torch.float32, device='cuda')
+        goals, points = table[:, :, 0].contiguous(), table[:, :, 1].contiguous()
+        fields = cuda.distance_fields(grid, goals)
+        at = fields.at(points)
+        chain = fields.pulled(points, reach=1, max_points=2)
+        there = chain.counts > 0
+        out['pulls'] = dict(points=args.envs, with_a_path=float(there.float().mean()), chain_points_mean=float(chain.cells[there].float().mean()),
+                            chain_points_most=int(chain.cells.max()))
+        for reach in (64, 256):
+            held = fields.pulled(points, reach=reach)
+            for scheme, name in ((0, 'lane_a_candidate'), (1, 'lane_a_sample')):
+                _lib.check(_lib.lib().ms_debug_nav_pull_scheme(scheme))
+                med, lo, hi = timed(lambda: fields.pulled(points, reach=reach, out=held), 20, args.warmup)
+                _lib.check(_lib.lib().ms_debug_nav_pull_scheme(-1))
+                out['pulls'][f'reach_{reach}_{name}'] = dict(seconds=med, min=lo, max=hi)
+                print(f'(h) pulled, {args.envs} x 1 paths, reach {reach}, {name.replace("_", " ")}: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+            out['pulls'][f'reach_{reach}'] = score = dict(
+                vertices_mean=float(held.counts[there].float().mean()), vertices_most=int(held.counts.max()),
+                pulled_over_chain=float((held.lengths[there]/chain.lengths[there]).mean()), pulled_over_at=float((held.lengths[there]/at[there]).mean()),
+                shortened_by_2_per_cent=float((held.lengths[there] <= .98*chain.lengths[there]).float().mean()))
+            print(f'(h) reach {reach}: {score}')
+        med, lo, hi = timed(lambda: fields.paths(points, max_points=256), 20, args.warmup)
+        out['pulls']['paths_256'] = dict(seconds=med, min=lo, max=hi)
+        print(f'(h) paths(max_points=256) on the same fields and points: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        way = torch.empty_like(points)
+        med, lo, hi = timed(lambda: fields.waypoints(points, out=way), 20, args.warmup)
+        out['pulls']['waypoints_16'] = dict(seconds=med, min=lo, max=hi)
+        print(f'(h) waypoints() on the same fields and points: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}]')
+        del sc, grid, fields, held, chain
+        torch.cuda.empty_cache()
+        for name, kw in (('PointGoal', {}), ('PointGoal_spl', dict(spl=True))):
+            env = PointGoal(args.envs, geometries=geoms, **kw)
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out['pulls_' + name] = dict(eager_seconds=eager, graph_seconds=graphed)
+            print(f'(h) PointGoal({args.envs}{", spl=True" if kw else ""}).step: eager {eager*1e3:.3f} ms, graph replay {graphed*1e3:.3f} ms')
+            del env
+            torch.cuda.empty_cache()
+        small = cubicasa.sample(64, seed=7, n_unique=64)
+        for policy in ('expert', 'random'):
+            torch.manual_seed(3); np.random.seed(3)
+            env = PointGoal(64, geometries=small, max_lifespan=120, spl=True)
+            world = env.reset()
+            scores = []
+            for _ in range(300):
+                decision = env.expert() if policy == 'expert' else arrdict.arrdict(actions=torch.randint(0, 7, (64, 1), device='cuda'))
+                world = env.step(decision)
+                scores.append(world.spl.clone())
+            scores = torch.stack(scores)
+            ended = ~torch.isnan(scores)
+            out['pulls_rollout_' + policy] = score = dict(episodes=int(ended.sum()), arrivals=int((scores[ended] > 0).sum()),
+                                                        mean_spl=float(scores[ended].mean()) if ended.any() else None,
+                                                        mean_spl_of_arrivals=float(scores[ended][scores[ended] > 0].mean()) if (scores[ended] > 0).any() else None)
+            print(f'(h) PointGoal(64, spl=True), 300 steps, {policy}: {score}')
 
     if args.json:
         with open(args.json, 'w') as f:
