@@ -406,6 +406,45 @@ typedef struct MsOverhead {
 int ms_overhead(const MsScenery* scenery, const MsAgents* agents /* NULL: agent rows as stored */, const MsOverhead* overhead,
                 void* hip_stream);
 
+/* Rollouts: what happens if agent (n, a) takes each of K candidate action plans of H steps, in one launch (no counterpart in
+ * the reference, where the only way to know is to step a copy of the world once per plan and step).  The scenery and the
+ * agents are READ ONLY.  For every (n, a, k), from agent (n, a)'s (p, ang, v, w) as they stand, for h = 0 .. H-1 in this order
+ * - every statement the one ms_move_physics makes (kernels.cu:179-230, modules.py:57-66,106-118), on the same functions:
+ *   move      (v, w) <- the movement prologue (MsMovement) of table row actions[n, a, k, h], clamped to the table
+ *   walls     x = min(1, collision_cs(p, v/fps, wall, agent_radius)) over ALL static lines of env n (those from
+ *             n_agents*n_model on); the wall grid's near lists and the reach culls stand in front of the test where
+ *             ms_physics uses them - the pose inside the grid, the reach at most wg_reach - and every static line otherwise:
+ *             every value lies in [+0, 1] and the fold is a minimum, so the bits are the same
+ *   others    with others = 1: x = min(x, collision_cc(p, v/fps, p_b, (0, 0), agent_radius)) over the env's other agents b != a
+ *             where the call found them - they stand still for the whole horizon; others = 0: they are absent
+ *   advance   the integration epilogue: p += x v/fps, ang likewise and normalised; x < 1: v = w = 0
+ * Outputs (one writer each): the state after step H-1, progress = the least x, stops = the steps with x < 1, first_stop = the
+ * first of them (H: none), and optionally the position after every step.  With a mask only the marked agents are rolled and
+ * the rows of the others are left as they are.  Not in a rollout: other agents that move, respawns, lifespans, the IMU.
+ * Nothing is allocated, no global atomics, nothing waits for the host: the call can be captured in a HIP graph.  1 <= K <= 256,
+ * 1 <= H <= 64, n_actions >= 1, others in {0, 1}: MS_EINVAL otherwise, before anything is launched. */
+typedef struct MsRollouts {
+    int                  n_candidates;  /* K                                                                           */
+    int                  horizon;       /* H                                                                           */
+    const long long*     actions;       /* (N, A, K, H) rows of `table`; shared_plans != 0: (K, H), the same for every agent */
+    int                  shared_plans;
+    const float*         table;         /* (n_actions, 3) [dx, dy, dw], as MsMovement's                                */
+    int                  n_actions;
+    float                keep;          /* as MsMovement's                                                             */
+    int                  others;        /* 1: the env's other agents are obstacles, at rest; 0: absent                 */
+    const unsigned char* mask;          /* (N, A) bytes, optional: non-zero = roll this agent                          */
+    float*               positions;     /* (N, A, K, 2) out, 8-byte aligned                                            */
+    float*               angles;        /* (N, A, K) out                                                               */
+    float*               velocity;      /* (N, A, K, 2) out, 8-byte aligned                                            */
+    float*               angvelocity;   /* (N, A, K) out                                                               */
+    float*               progress;      /* (N, A, K) out                                                               */
+    int*                 stops;         /* (N, A, K) out                                                               */
+    int*                 first_stop;    /* (N, A, K) out                                                               */
+    float*               trail;         /* (N, A, K, H, 2) out, optional, 8-byte aligned                               */
+} MsRollouts;
+int ms_rollouts(const MsScenery* scenery, const MsAgents* agents, const MsRollouts* rollouts, const MsConfig* config,
+                void* hip_stream);
+
 /* Shortest-path distance fields on the floorplans: how far it is from a point to a goal when one has to walk round the
  * walls.  Every step below is one binary32 operation, in the order given, without contraction: tests/test_navfield_host.py
  * restates it in numpy bit for bit (nav_rule), and the GPU tests hold the kernels to EQUALITY with it.

@@ -227,6 +227,22 @@ int ms_host_agents_apart(const float* me, const float* other, float agent_radius
 int ms_host_wall_beyond_reach(const float* agent, const float* wall, float agent_radius);
 /* ... and the reach itself, which also picks the tier of the cell's near list (wg_reach_lo, wg_reach) or the sweep. */
 float ms_host_wall_reach(const float* agent, float agent_radius);
+/* Host instantiation of the movement prologue (kernels/physics.h: move_velocity), for CPU tests: delta = (dx, dy, dw), v (2 floats)
+ * and w in / out.  Its sine and cosine are the host libm's, which need not round as torch's or the device's do. */
+void ms_host_move_velocity(float keep, float ang, const float* delta, float* v, float* w);
+/* The rollouts' rule (MsRollouts) stated serially over the kernel's own per-step functions (kernels/rollout.h) for ONE env on HOST
+ * arrays: `walls` the env's n_walls STATIC rows, four floats each; every pointer of `agents` ((A,) and (A, 2) arrays; headings and
+ * schedule are not read) and of `rollouts` is host memory and holds the one env's share - actions (A, K, H), or (K, H) with
+ * shared_plans; mask (A,) or NULL; the outputs (A, K, ..).  There is no wall grid on the host: every candidate meets every wall,
+ * behind the reach cull.  Returns what ms_rollouts would: MS_OK, MS_EINVAL for arguments it would refuse (and for NULL walls with
+ * n_walls > 0, n_agents < 1). */
+int ms_host_rollouts(const float* walls, int n_walls, const MsAgents* agents, int n_agents, const MsRollouts* rollouts,
+                     const MsConfig* config);
+/* ms_debug_rollout_scheme: how ms_rollouts' waves meet a step's walls - 0 = a lane a candidate, each walking the near list of its
+ * own cell; 1 = physics_kernel's scheme: a lane a wall, the wave's candidates one after another, the surviving pairs compacted in
+ * LDS before the exact test; -1 = the library's own choice (1 up to 24 candidates an agent, else 0); anything else: MS_EINVAL.  Per calling thread; A/B runs and tests -
+ * either setting produces the same bits. */
+int ms_debug_rollout_scheme(int scheme);
 /* Host instantiation of the scan's test, for CPU tests: does wall o = (ax, ay, bx, by) hide wall w from every point of
  * the cell [x0, x1] x [y0, y1] (as ms_wallgrid_scan grows it) for near planes below `near_plane`? */
 int ms_host_wall_hidden(float x0, float y0, float x1, float y1, const float* o, const float* w, float near_plane);

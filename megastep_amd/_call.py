@@ -1,4 +1,4 @@
-"""What every call of :mod:`megastep_amd.cuda` and of the modules beside it (``rays``, ``overhead``, ``nav``, ``envlogic``) does
+"""What every call of :mod:`megastep_amd.cuda` and of the modules beside it (``rays``, ``rollouts``, ``overhead``, ``nav``, ``envlogic``) does
 before its launch: the tensor checks, the device its tensors share, and the constants of :func:`~megastep_amd.cuda.initialize`."""
 import torch
 from . import _lib

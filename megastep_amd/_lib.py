@@ -92,6 +92,13 @@ class MsOverhead(C.Structure):
                 ('rgb', C.c_void_p), ('indices', C.c_void_p)]
 
 
+class MsRollouts(C.Structure):
+    _fields_ = [('n_candidates', C.c_int), ('horizon', C.c_int), ('actions', C.c_void_p), ('shared_plans', C.c_int), ('table', C.c_void_p),
+                ('n_actions', C.c_int), ('keep', C.c_float), ('others', C.c_int), ('mask', C.c_void_p), ('positions', C.c_void_p),
+                ('angles', C.c_void_p), ('velocity', C.c_void_p), ('angvelocity', C.c_void_p), ('progress', C.c_void_p), ('stops', C.c_void_p),
+                ('first_stop', C.c_void_p), ('trail', C.c_void_p)]
+
+
 class MsNavGrid(C.Structure):
     _fields_ = [('n_envs', C.c_int), ('cell', C.c_float), ('clearance', C.c_float), ('geom', C.c_void_p), ('starts', C.c_void_p),
                 ('max_framed', C.c_int), ('free_cells', C.c_void_p)]
@@ -253,6 +260,7 @@ PROTOTYPES = {
     'ms_raycast': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRaycast), _p(MsConfig), _ptr]),
     'ms_camera_rays': (_int, [_p(MsAgents), _int, _int, _p(MsConfig), _ptr, _ptr]),
     'ms_overhead': (_int, [_p(MsScenery), _p(MsAgents), _p(MsOverhead), _ptr]),
+    'ms_rollouts': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRollouts), _p(MsConfig), _ptr]),
     'ms_nav_free': (_int, [_p(MsScenery), _p(MsNavGrid), _ptr]),
     'ms_nav_fields': (_int, [_p(MsNavGrid), _p(MsNavFields), _ptr]),
     'ms_nav_query': (_int, [_p(MsNavGrid), _p(MsNavQuery), _ptr]),
@@ -334,6 +342,9 @@ PROTOTYPES = {
     'ms_host_agents_apart': (_int, [_f32p, _f32p, _flt]),
     'ms_host_wall_beyond_reach': (_int, [_f32p, _f32p, _flt]),
     'ms_host_wall_reach': (_flt, [_f32p, _flt]),
+    'ms_host_move_velocity': (None, [_flt, _flt, _f32p, _f32p, _f32p]),
+    'ms_host_rollouts': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsRollouts), _p(MsConfig)]),
+    'ms_debug_rollout_scheme': (_int, [_int]),
     'ms_host_wall_hidden': (_int, [_flt]*4 + [_f32p, _f32p, _flt]),
     'ms_host_wall_sectors': (None, [_flt]*4 + [_f32p, _i32p, _i32p, _f32p, _i32p]),
     'ms_host_wallgrid_cell': (None, [_ptr, _int, _flt, _flt, _int, _int, _flt, _int, _flt, _flt, _flt, _ptr, _ptr]),

@@ -120,18 +120,18 @@ __host__ __device__ inline void sincospi_f(float x, float& s, float& c) {
 }
 
 // ATen `%` on floats (remainder): fmod then sign fix-up.            kernels.cu:173-175
-__device__ inline float remainder_f(float a, float b) {
+__host__ __device__ inline float remainder_f(float a, float b) {
     float m = fmodf(a, b);
     if ((m != 0.f) && ((b < 0.f) != (m < 0.f))) m += b;
     return m;
 }
-__device__ inline float normalize_degrees(float a) {
+__host__ __device__ inline float normalize_degrees(float a) {
     return remainder_f(remainder_f(a, 360.f) + 180.f, 360.f) - 180.f;
 }
 
 struct Isect { float s, t; };
 // kernels.cu:67-89
-__device__ inline Isect intersect(P2 P, P2 U, P2 Q, P2 V) {
+__host__ __device__ inline Isect intersect(P2 P, P2 U, P2 Q, P2 V) {
     const float UxV = cross(U, V);
     if (fabsf(UxV) < 1.e-3f) return Isect{INFINITY, INFINITY};
     const P2 PQ = Q - P;
@@ -140,21 +140,21 @@ __device__ inline Isect intersect(P2 P, P2 U, P2 Q, P2 V) {
 
 struct Proj { float s, d; };
 // kernels.cu:91-107
-__device__ inline Proj project(P2 P, P2 U, P2 Q) {
+__host__ __device__ inline Proj project(P2 P, P2 U, P2 Q) {
     const float u = len(U) + 1e-6f;
     const P2 PQ = Q - P;
     return Proj{dot(PQ, U)/(u*u), fabsf(cross(PQ, U))/u};
 }
 
 // kernels.cu:109-118; never returns NaN or -0, so the folds over it are order-independent.
-__device__ inline float sensibilize(float p) {
+__host__ __device__ inline float sensibilize(float p) {
     const float q = p*.99f;
     if (!(q > 0.f)) return 0.f;
     return (q < 1.f) ? q : 1.f;
 }
 
 // kernels.cu:119-133
-__device__ inline float collision_cc(P2 p0, P2 v0, P2 p1, P2 v1, float agent_radius) {
+__host__ __device__ inline float collision_cc(P2 p0, P2 v0, P2 p1, P2 v1, float agent_radius) {
     const float r = 1.001f*2.f*agent_radius;
     float x = 1.f;
     const P2 dv = v0 - v1;
@@ -218,7 +218,7 @@ __host__ __device__ inline bool wall_beyond(const float4 tk, const float4 u, con
 }
 
 // kernels.cu:135-171
-__device__ inline float collision_cs(P2 p, P2 v, P2 la, P2 lb, float agent_radius) {
+__host__ __device__ inline float collision_cs(P2 p, P2 v, P2 la, P2 lb, float agent_radius) {
     const float r = 1.001f*agent_radius;
     float x = 1.f;
     const P2 lv = lb - la;

@@ -35,7 +35,7 @@ __device__ inline int lifespan_tick(const MsStepExtras& ex, const int i, bool& r
     return reset ? 0 : life;
 }
 // the movement modules' velocity update (modules.py:57-66,106-118): the action's delta turned into the global frame, blended in
-__device__ inline void move_velocity(const float keep, const float ang, const float dx, const float dy, const float dw, float2& v, float& w) {
+__host__ __device__ inline void move_velocity(const float keep, const float ang, const float dx, const float dy, const float dw, float2& v, float& w) {
     const float a_ = 0.017453292519943295f*ang;                         // np.pi/180*angles, in binary32 like torch
     const float s_ = sinf(a_), c_ = cosf(a_);
     const float gx = c_*dx - s_*dy, gy = s_*dx + c_*dy;
@@ -43,11 +43,11 @@ __device__ inline void move_velocity(const float keep, const float ang, const fl
     else { w = keep*w + dw; v = make_float2(keep*v.x + gx, keep*v.y + gy); }
 }
 // how many of a cell's near walls (its header hdr) an agent of this reach meets: the short tier if the reach is within wg_reach_lo
-__device__ inline int near_count(const uint4 hdr, const float reach, const float reach_lo) {
+__host__ __device__ inline int near_count(const uint4 hdr, const float reach, const float reach_lo) {
     return (int)((reach <= reach_lo) ? (hdr.w & 0xffffu) : (hdr.w >> 16));
 }
 // the integration epilogue (kernels.cu:224-227): the fraction x of the step the agent can take; stopped (x < 1): at rest
-__device__ inline bool integrate(const float x, const float fps, float2& p, float& ang, float2& v, float& w) {
+__host__ __device__ inline bool integrate(const float x, const float fps, float2& p, float& ang, float2& v, float& w) {
     p.x = p.x + x*v.x/fps;
     p.y = p.y + x*v.y/fps;
     ang = normalize_degrees(ang + x*w/fps);

@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navseen.h, navage.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navseen.h, navage.h, navwindow.h, navdraw.h.
 //
-// Twenty-eight kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -16,6 +16,11 @@
 //                   EXTRA = 1 the envs' respawn / lifespan / IMU bookkeeping.  Where the agents carry a fan schedule, the
 //                   launch's first blocks sort the last render's costs into the next render's starting order.
 //                                                            (reference: kernels.cu:179-230, modules.py:24-118,263-366)
+//   rollout_kernel      candidate action plans rolled through that step: one wavefront per (agent, 64 plans), a lane a plan,
+//                   the state in registers for the whole horizon; each step a lane walks the near list of the cell it stands
+//                   in (or, where no list applies, its env's static rows) through the step's own functions.   (no counterpart)
+//   rollout_walls_kernel   the same rule by physics_kernel's scheme - a lane a wall, the candidates one after another, the
+//                   surviving pairs compacted in LDS before the exact test: behind ms_debug_rollout_scheme, for A/B runs.
 //   render_kernel<OBS, SHADE, NG, STEP>   (OBS = 2: pooled observations only, no plane stores in the kernel; STEP = 1: a
 //                   single-agent env's physics step first, in the same wave - ms_step_render's one launch a step)
 //                   one wavefront per (env, agent, 64-ray group) - or, NG = 4, per four such groups
@@ -119,6 +124,7 @@ thread_local int g_last_render_groups = 0;  // ms_debug_last_render_groups: the 
 thread_local int g_overhead_cull = 1;       // ms_debug_overhead_cull: 0 = ms_overhead's tiles keep every line
 thread_local int g_nav_cost_variant = -1;   // ms_debug_nav_cost_variant: where ms_nav_cost_fields' launch keeps the multipliers (-1: its own choice)
 thread_local int g_nav_pull_scheme = -1;    // ms_debug_nav_pull_scheme: how ms_nav_pulls' waves test their sights (-1: its own choice)
+thread_local int g_rollout_scheme = -1;     // ms_debug_rollout_scheme: how ms_rollouts' waves meet their walls (-1: its own choice)
 thread_local int g_nav_clear_cull = -1;     // ms_debug_nav_clear_cull: which culls ms_nav_clearance's launch runs (-1: its own choice)
 thread_local long long g_clear_folds = 0, g_clear_pairs = 0;      // ms_host_nav_clear_folds: the last ms_host_nav_clearance's
 thread_local int g_render_order = 1;        // ms_debug_render_order: 0 = MsAgents.schedule is neither sorted nor followed
@@ -172,6 +178,7 @@ struct Probe {
 
 #include "kernels/math.h"
 #include "kernels/physics.h"
+#include "kernels/rollout.h"
 #include "kernels/lighting.h"
 #include "kernels/render.h"
 #include "kernels/bake.h"
@@ -591,6 +598,54 @@ int ms_move_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* m
 
 int ms_physics(const MsScenery* sc, const MsAgents* ag, float* progress, const MsConfig* cfg, void* stream) {
     return ms_step_physics(sc, ag, nullptr, nullptr, progress, cfg, stream);
+}
+
+void ms_host_move_velocity(float keep, float ang, const float* delta, float* v, float* w) {
+    float2 vv = make_float2(v[0], v[1]);
+    move_velocity(keep, ang, delta[0], delta[1], delta[2], vv, *w);
+    v[0] = vv.x; v[1] = vv.y;
+}
+
+// what ms_rollouts and ms_host_rollouts refuse alike: the limits and the pointers of an MsRollouts
+static int rollouts_status(const MsRollouts* r) {
+    if (!r || r->n_candidates < 1 || r->n_candidates > 256 || r->horizon < 1 || r->horizon > 64 || r->n_actions < 1 ||
+        (r->others != 0 && r->others != 1) || !(r->keep == r->keep) || !r->actions || !r->table || !r->positions || !r->angles ||
+        !r->velocity || !r->angvelocity || !r->progress || !r->stops || !r->first_stop) return MS_EINVAL;
+    return MS_OK;
+}
+
+int ms_rollouts(const MsScenery* sc, const MsAgents* ag, const MsRollouts* r, const MsConfig* cfg, void* stream) {
+    if (!scenery_ok(sc) || !agents_ok(ag) || !config_ok(cfg) || rollouts_status(r) != MS_OK) return MS_EINVAL;
+    if (((uintptr_t)r->actions % 8) || ((uintptr_t)r->positions % 8) || ((uintptr_t)r->velocity % 8) || ((uintptr_t)r->trail % 8) ||
+        ((uintptr_t)ag->positions % 8) || ((uintptr_t)ag->velocity % 8)) return MS_EINVAL;
+    if (sc->wg_cells && (!sc->wg_starts || !sc->wg_geom || !sc->wg_near_rows || !(sc->wg_cell > 0.f) || ((uintptr_t)sc->wg_cells % 16) ||
+                         ((uintptr_t)sc->wg_geom % 16) || ((uintptr_t)sc->wg_near_rows % 16))) return MS_EINVAL;
+    const int groups = (r->n_candidates + WAVE - 1)/WAVE;
+    const long long blocks = (long long)sc->n_envs*sc->n_agents*groups;
+    if (blocks > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    // Which scheme: a lane a candidate pays a wall's whole exact test however few of its lanes are candidates - measured (DESIGN
+    // 3.27; 4096 envs, H = 8) 117.7 us at K = 7 against 51.9 us for a lane a wall, 151.6 against 124.9 at 24, 153.4 against 163.1 at
+    // 32, 164.3 against 301.2 at 64: few candidates go candidate by candidate, a wave's worth and more a lane each.
+    const int scheme = g_rollout_scheme >= 0 ? g_rollout_scheme : (r->n_candidates <= ROLL_FEW ? 1 : 0);
+    if (scheme == 1)
+        hipLaunchKernelGGL(rollout_walls_kernel, dim3((unsigned)blocks), dim3(WAVE), 0, (hipStream_t)stream, *sc, agents_k(*ag), *r,
+                           cfg->agent_radius, cfg->fps, groups, divisor_of((unsigned)groups), divisor_of((unsigned)sc->n_agents));
+    else
+        hipLaunchKernelGGL(rollout_kernel, dim3((unsigned)blocks), dim3(WAVE), 0, (hipStream_t)stream, *sc, agents_k(*ag), *r,
+                           cfg->agent_radius, cfg->fps, groups, divisor_of((unsigned)groups), divisor_of((unsigned)sc->n_agents));
+    return launch_status();
+}
+
+int ms_debug_rollout_scheme(int scheme) {
+    if (scheme < -1 || scheme > 1) return MS_EINVAL;
+    g_rollout_scheme = scheme;
+    return MS_OK;
+}
+
+int ms_host_rollouts(const float* walls, int n_walls, const MsAgents* ag, int n_agents, const MsRollouts* r, const MsConfig* cfg) {
+    if (!agents_ok(ag) || !config_ok(cfg) || rollouts_status(r) != MS_OK || n_agents < 1 || n_walls < 0 || (n_walls > 0 && !walls)) return MS_EINVAL;
+    rollout_serial(walls, n_walls, *ag, n_agents, *r, cfg->agent_radius, cfg->fps);
+    return MS_OK;
 }
 
 // The render call, decided in full before anything is launched: render_prepare makes every check and choice, render_enqueue

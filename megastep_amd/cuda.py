@@ -6,7 +6,7 @@ point is a hand-written gfx950 kernel reached through the C-ABI in ``include/meg
 (PyTorch-ROCm is the allocator/stream plumbing); the kernels run on ``torch.cuda.current_stream()``.
 
 The calls without a counterpart in the reference live in modules named after the kernel files they drive - ``rays``,
-``overhead``, ``nav`` and ``envlogic`` - and are imported at the end of this one, so each is still ``cuda.<name>``.
+``rollouts``, ``overhead``, ``nav`` and ``envlogic`` - and are imported at the end of this one, so each is still ``cuda.<name>``.
 
 There is no CPU implementation here, exactly as in the reference ("If you haven't got CUDA, megastep will not work",
 reference: docs/faq.rst:23-26): calling bake/physics/render on non-GPU tensors raises.
@@ -692,6 +692,7 @@ def _render_layout(n, a, r, fields, pooled, lit):
 # ---------------------------------------------------------------------------------------------------------------------
 from .envlogic import deathmatch_shoot, explorer_books
 from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
+from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans
 from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, plan_views, agent_views
 from .nav import nav_geometry, NavGrid, nav_grid, FIELD_CAPACITY, DistanceFields, Paths, PulledPaths, distance_fields, geodesic, SeenMaps, seen_maps, AGE_MAX_TICK, Sweep, AgeMaps, age_maps, SeededFields, seeded_fields, \
     COST_CAPACITY, COST_MAX, CostFields, cost_fields, inflation_costs, mark_costs, \

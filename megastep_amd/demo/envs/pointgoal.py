@@ -74,6 +74,7 @@ class PointGoal:
             self._routes = modules.Routes(c, self.grid, self._goals, self.costs)
         # (under momentum a narrow cone walks a third less far: DESIGN 3.15)
         self._follower = modules.PathFollower(c, self._goals if self._routes is None else self._routes, cone=15.)
+        self._lookahead = None                          # (the 'lookahead' expert: made when first asked for)
         self.spl = modules.SPL(c, self._goals) if spl else None
         self.action_space = self._mover.space
         self.obs_space = dotdict.dotdict(rgb=self._rgb.space, d=self._depth.space, goal=self._goals.space)
@@ -128,12 +129,21 @@ class PointGoal:
         return self._world(over)
 
     @torch.no_grad()
-    def expert(self):
+    def expert(self, kind='follow'):
         """``arrdict(actions=(n_env, n_agent))``: what the shortest-path follower (:class:`~megastep_amd.modules.PathFollower`)
         does in the current state - every agent towards the waypoint of its own goal. Nothing waits for the host:
         ``env.step(env.expert())`` can sit in one graph. The follower counts the steps an agent has been stuck, so ask once
-        per step."""
-        return self._follower()
+        per step. ``kind='lookahead'``: what :class:`~megastep_amd.modules.LookAhead` does instead - it rolls its plans through
+        the physics step and takes the one that ends nearest the goal (by the env's routes, with ``margin``) - with a follower
+        of its own to fall back on; as capturable, and made by the first call that asks for it (outside a graph)."""
+        if kind == 'follow':
+            return self._follower()
+        if kind != 'lookahead':
+            raise RuntimeError(f"kind must be 'follow' or 'lookahead'; got {kind!r}")
+        if self._lookahead is None:
+            source = self._goals if self._routes is None else self._routes
+            self._lookahead = modules.LookAhead(self.core, source, self._mover, fallback=modules.PathFollower(self.core, source, cone=15.))
+        return self._lookahead()
 
     def state(self, e=0):
         return arrdict.arrdict(core=self.core.state(e), rgb=self._rgb.state(e), d=self._depth.state(e), goals=self._goals.state(e),

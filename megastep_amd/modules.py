@@ -95,6 +95,11 @@ class SimpleMovement:
         ``respawn`` / ``imu``: see :func:`_move`."""
         return _move(self.core, self._actionset, decision.actions, 0., respawn, imu, self._table)
 
+    def rollouts(self, actions, **kw):
+        """:func:`cuda.rollouts` of ``actions`` ((n_env, n_agent, K, H) or (K, H) int64) under this module's table and ``keep``:
+        where each plan would take every agent as it stands, without moving anybody. ``kw``: ``others``, ``trail``, ``mask``, ``out``."""
+        return cuda.rollouts(self.core.scenery, self.core.agents, actions, self._table, keep=self.keep, **kw)
+
 
 class MomentumMovement:
 
@@ -112,6 +117,8 @@ class MomentumMovement:
 
     def __call__(self, decision, respawn=None, imu=None):
         return _move(self.core, self._actionset, decision.actions, self.keep, respawn, imu, self._table)
+
+    rollouts = SimpleMovement.rollouts
 
 
 def unpack(d):
@@ -1108,6 +1115,61 @@ class PathFollower:
         local = to_local_frame(agents.angles, self.goals.waypoints(self.lookahead) - agents.positions)
         velocity = to_local_frame(agents.angles, agents.velocity)
         return arrdict.arrdict(actions=self.choose(local, self.cone, velocity, self._blocked, self.speed))
+
+
+class LookAhead:
+
+    def __init__(self, core, goals, mover, horizon=8, switch=2, stop_cost=.5, fallback=None):
+        """A look-ahead expert with :class:`PathFollower`'s call interface (a local planner in the style of the dynamic-window
+        approach; no counterpart in the reference): every agent rolls the plans ``cuda.plans(n_actions, horizon, switch)`` -
+        "action i for ``switch`` steps, then action j" - through the physics step itself (``mover.rollouts``, with the env's other
+        agents as obstacles at rest when there are any), values the pose each plan ends on by the walking distance from there
+        to its goal (``goals.fields.at``: a :class:`Goals`, a :class:`SampledGoals`, a :class:`Routes` - anything with
+        ``.fields``), adds ``stop_cost`` metres for every step the plan was stopped dead at, and takes the first action of the
+        cheapest plan - the lowest-numbered of several (:meth:`choose`). Where no plan ends on a pose with a finite value, the
+        agent does what ``fallback`` does (default: a :class:`PathFollower` on the same goals). Unlike the follower, which plans
+        for a point, it knows what physics does to the disc. One rollout launch, one ``at`` and a few tensor ops; the module
+        keeps the launch's buffers and nothing waits for the host: a call can sit in a HIP graph. The fallback counts dead
+        stops, so call the module once per step."""
+        self.core, self.goals, self.mover = core, goals, mover
+        self.horizon, self.switch, self.stop_cost = int(horizon), switch, float(stop_cost)
+        self.fallback = PathFollower(core, goals) if fallback is None else fallback
+        n_actions = mover._table.shape[0]
+        #: (K, H) int64: the plans every agent rolls
+        self.plans = cuda.plans(n_actions, self.horizon, switch, device=core.device)
+        n, a, k = core.n_envs, core.n_agents, self.plans.shape[0]
+        self._agent = torch.arange(a, dtype=torch.int32, device=core.device)[None, :, None].expand(n, a, k).reshape(n, -1).contiguous()
+        self._others = 'rest' if a > 1 else None
+        self._rolled = None
+        #: (n_env, n_agent, K): what the last call's plans were worth (None before the first)
+        self.values = None
+
+    #: the :class:`cuda.Rollouts` of the last call (None before the first)
+    rolled = property(lambda self: self._rolled)
+
+    @staticmethod
+    def choose(values, stops, plans, stop_cost):
+        """The rule, a pure function: ``values`` (..., K) floats, ``stops`` (..., K) integers, ``plans`` (K, H) or (..., K, H) ->
+        ((...) int64: the first action of the lowest-numbered plan of least ``values + stop_cost*stops``, a NaN or +inf value
+        scoring +inf; (...) bool ``none``: every plan scores +inf - the action is plan 0's then)."""
+        k = values.shape[-1]
+        score = values + stop_cost*stops.to(values.dtype)
+        score = torch.where(torch.isnan(score), torch.full_like(score, float('inf')), score)
+        least = score.amin(-1, keepdim=True)
+        order = torch.arange(k, device=values.device).expand(score.shape)
+        index = torch.where(score == least, order, torch.full_like(order, k)).amin(-1)
+        none = torch.isinf(least[..., 0]) & (least[..., 0] > 0)
+        first = plans[..., 0]
+        action = first[index] if first.ndim == 1 else first.gather(-1, index[..., None]).squeeze(-1)
+        return action, none
+
+    def __call__(self):
+        """``arrdict(actions=(n_env, n_agent) int64)``: the decision for the agents as they stand."""
+        n, a, k = self.core.n_envs, self.core.n_agents, self.plans.shape[0]
+        self._rolled = self.mover.rollouts(self.plans, others=self._others, out=self._rolled)
+        self.values = self.goals.fields.at(self._rolled.positions.view(n, a*k, 2), goal=self._agent).view(n, a, k)
+        action, none = self.choose(self.values, self._rolled.stops, self.plans, self.stop_cost)
+        return arrdict.arrdict(actions=torch.where(none, self.fallback().actions, action))
 
 
 class SPL:
