@@ -1157,6 +1157,63 @@ int ms_nav_basins(const MsNavGrid* grid, const MsNavBasins* basins, void* hip_st
 int ms_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* query, void* hip_stream);
 int ms_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* marks, void* hip_stream);
 
+/* Zones: a label and a number together - per zone of a labels layer the cells, the marked cells, the least value and the cell that
+ * attains it: how far each agent is from the nearest cell of each frontier cluster and which cell that is, how much of each room has
+ * been seen, the oldest cell of each territory.  Every output is an integer or a copied float with one definition;
+ * tests/test_navzone_host.py restates it in numpy (zone_rule: loops over cells, a min over (value bits, cell)) and the kernel - and
+ * its host instantiation, ms_host_nav_zones - are held to EQUALITY with it.  geom, starts and c are MsNavGrid's.
+ *   stores        A call covers F = n_fields fields per env and reads three layers in the fields' layout - a layer of S stores per
+ *                 env keeps store (n, f) at S*starts[n] + f*nx*ny, row-major: labels (int32, L = n_labels stores), values (float32,
+ *                 V = n_values stores, or NULL) and marks (uint8, M = n_marks stores, or NULL, with `where`).  Each of L, V, M is 1
+ *                 or F; a layer with one store serves every field.  K = max_zones, 1..256.
+ *   zone(v)       ranked = 1: the labels are canonical cell indices (MsNavRegions.labels, MsNavBasins.labels without ids).  A cell v
+ *                 is a ROOT when labels[v] == v; zone k is the k-th root in ascending index order, and zone(v) is the rank of
+ *                 labels[v] among the roots - none when labels[v] < 0, when it is not a cell of the env, when it is not a root, and
+ *                 when its rank is K or more.  ranked = 0: the label is the zone (MsNavBasins.labels with ids, any int layer):
+ *                 zone(v) = labels[v] when 0 <= labels[v] < K, else none.
+ *   cells         cells[n, f, k] = the cells v with zone(v) == k.
+ *   marked        those of them with (marks[v] != 0) == where; equals cells without marks.
+ *   least         the least values[v] over the zone's cells that TAKE PART: the value's sign bit is clear and it is < +inf (NaN,
+ *                 negatives and -0 are left out), and - with within_marks = 1 - the cell is marked.  +inf when none does, and
+ *                 without values.  The float is copied, never computed.
+ *   nearest       the least cell index (row-major within the env) attaining `least`; -1 when none.
+ *   points        the centre of the `nearest` cell, x = ((float)(jx0 + j) + 0.5f)*c, y likewise - the very function the paths and
+ *                 the cell draws give a cell's centre by; (NaN, NaN) when nearest is -1.
+ *   roots         ranked = 1: the label zone k stands for - the k-th root - and -1 beyond the last zone; ranked = 0: k where
+ *                 cells[n, f, k] > 0, else -1.
+ *   n_zones       ranked = 1: the number of roots - it may exceed K: zones from K on are counted here and nowhere else;
+ *                 ranked = 0: the number of k with cells[n, f, k] > 0.
+ * Fields that are masked out keep every output as it is.  An env without cells writes zeros, +inf, -1 and NaN.
+ * ms_nav_zones: one launch, one workgroup of 256 lanes per field; its LDS (5 KiB: the list of roots, two counters and one 64-bit
+ * key a zone) does not grow with the env, so there are no tiers and no global-memory path.  Ranked: the first K roots are compacted
+ * in index order by ballots and a workgroup prefix, every cell then finds its label in that list by binary search; per zone integer
+ * atomics for the counts and ONE 64-bit LDS atomic min on (value bits << 32) | cell - a non-negative binary32 orders as its bits,
+ * so this is the rule exactly.  One writer per output element, nothing allocated, nothing waits: the call can be captured in a HIP
+ * graph.  Every argument is checked in full before the launch: NULL labels or outputs, a store count that is neither 1 nor F,
+ * max_zones outside 1..256, where / ranked / within_marks other than 0 or 1, a misaligned pointer: MS_EINVAL, nothing enqueued. */
+typedef struct MsNavZones {
+    int                  n_fields;     /* F: fields per env                                                            */
+    const int*           labels;       /* L*starts[N] int32                                                            */
+    int                  n_labels;     /* L: 1 or F                                                                    */
+    const float*         values;       /* V*starts[N] floats, or NULL: least is +inf, nearest -1                       */
+    int                  n_values;     /* V: 1 or F (not read without values)                                          */
+    const unsigned char* marks;        /* M*starts[N] bytes, or NULL: every cell counts as marked                      */
+    int                  n_marks;      /* M: 1 or F (not read without marks)                                           */
+    int                  where;        /* 0 or 1: a cell is marked when (marks[v] != 0) == where (not read without marks) */
+    int                  within_marks; /* 0 or 1: only marked cells take part in least and nearest                      */
+    int                  ranked;       /* 1: zone = the rank of the label among the roots; 0: zone = the label          */
+    int                  max_zones;    /* K, 1..256                                                                    */
+    const unsigned char* mask;         /* (N, F) non-zero: compute this field; NULL: all.  Read on the device only.    */
+    int*                 cells;        /* (N, F, K) out                                                                */
+    int*                 marked;       /* (N, F, K) out                                                                */
+    float*               least;        /* (N, F, K) out                                                                */
+    int*                 nearest;      /* (N, F, K) out                                                                */
+    float*               points;       /* (N, F, K, 2) out                                                             */
+    int*                 roots;        /* (N, F, K) out                                                                */
+    int*                 n_zones;      /* (N, F) out                                                                   */
+} MsNavZones;
+int ms_nav_zones(const MsNavGrid* grid, const MsNavZones* zones, void* hip_stream);
+
 /* Clearance: how much room there is - the distance from a place to the nearest wall, which wall that is, and which way it lies;
  * per cell of the nav grid (a float layer: a band for ms_nav_draws, a channel for ms_nav_windows; and the free bytes of several
  * body sizes from one pass over the walls) and per point, the other agents' bodies counted (a proximity reading).  What

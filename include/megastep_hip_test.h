@@ -165,6 +165,11 @@ int ms_host_nav_basins(const MsNavGrid* grid, const MsNavBasins* basins);
 int ms_host_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* query);
 int ms_host_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* marks);
 int ms_host_nav_basin_capacity(int* capacities);
+/* Host instantiation of the zones' rule (kernels/navzone.h: the root test, the rank of a label in the list of roots, a cell's zone,
+ * its mark, its key and a zone's stores - the very functions every lane of nav_zone_kernel evaluates) for one whole call of
+ * ms_nav_zones on HOST arrays, swept serially: every pointer of `grid` and of `zones` is host memory.  Returns what ms_nav_zones
+ * would: MS_OK, or MS_EINVAL for arguments it would refuse. */
+int ms_host_nav_zones(const MsNavGrid* grid, const MsNavZones* zones);
 /* Host instantiation of the view fields' rule (kernels/navview.h: view_in_range, view_in_cone, view_wall_blocks, the window and the
  * wall cull - the very functions every lane of nav_view_kernel evaluates) for one whole call of ms_nav_views on HOST arrays, swept
  * serially: every pointer of `grid` and of `views` is host memory, and in place of an MsScenery `walls` holds the STATIC rows of all

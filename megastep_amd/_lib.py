@@ -222,6 +222,13 @@ class MsNavPointMarks(C.Structure):
                 ('marks', C.c_void_p), ('ids', C.c_void_p)]
 
 
+class MsNavZones(C.Structure):
+    _fields_ = [('n_fields', C.c_int), ('labels', C.c_void_p), ('n_labels', C.c_int), ('values', C.c_void_p), ('n_values', C.c_int),
+                ('marks', C.c_void_p), ('n_marks', C.c_int), ('where', C.c_int), ('within_marks', C.c_int), ('ranked', C.c_int),
+                ('max_zones', C.c_int), ('mask', C.c_void_p), ('cells', C.c_void_p), ('marked', C.c_void_p), ('least', C.c_void_p),
+                ('nearest', C.c_void_p), ('points', C.c_void_p), ('roots', C.c_void_p), ('n_zones', C.c_void_p)]
+
+
 class MsNavViews(C.Structure):
     _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('headings', C.c_void_p), ('max_range', C.c_float), ('cos_half', C.c_float),
                 ('countable', C.c_void_p), ('unseen', C.c_void_p), ('n_maps', C.c_int), ('slot', C.c_void_p), ('mask', C.c_void_p),
@@ -277,6 +284,7 @@ PROTOTYPES = {
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
     'ms_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery), _ptr]),
     'ms_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks), _ptr]),
+    'ms_nav_zones': (_int, [_p(MsNavGrid), _p(MsNavZones), _ptr]),
     'ms_nav_clearance': (_int, [_p(MsScenery), _p(MsNavGrid), _p(MsNavClearance), _ptr]),
     'ms_nav_clear_query': (_int, [_p(MsScenery), _p(MsAgents), _p(MsNavClearQuery), _ptr]),
     'ms_nav_seed_fields': (_int, [_p(MsNavGrid), _p(MsNavSeedFields), _ptr]),
@@ -329,6 +337,7 @@ PROTOTYPES = {
     'ms_host_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery)]),
     'ms_host_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks)]),
     'ms_host_nav_basin_capacity': (_int, [_ptr]),
+    'ms_host_nav_zones': (_int, [_p(MsNavGrid), _p(MsNavZones)]),
     'ms_host_nav_views': (_int, [_p(MsNavGrid), _p(MsNavViews), _ptr, _ptr, _int]),
     'ms_host_nav_view_capacity': (_int, []),
     'ms_host_nav_clearance': (_int, [_p(MsNavGrid), _p(MsNavClearance), _ptr, _ptr, _int]),

@@ -2,7 +2,7 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navseen.h, navage.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
 //
 // Thirty kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
@@ -192,6 +192,7 @@ struct Probe {
 #include "kernels/navpath.h"
 #include "kernels/navpull.h"
 #include "kernels/navbasin.h"
+#include "kernels/navzone.h"
 #include "kernels/navseen.h"
 #include "kernels/navage.h"
 #include "kernels/navwindow.h"
@@ -1581,6 +1582,39 @@ int ms_host_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* m) {
 }
 
 int ms_host_nav_basin_capacity(int* capacities) { return nav_host_capacities(capacities, basin_capacity); }
+
+// Zones (navzone.h): the same discipline; one instantiation - the kernel's LDS does not grow with the env.
+static int nav_zones_check(const MsNavGrid* grid, const MsNavZones* z) {
+    const auto stores_ok = [&](int count) { return count == 1 || count == z->n_fields; };
+    if (!nav_grid_ok(grid) || !z || z->n_fields < 1 || z->max_zones < 1 || z->max_zones > ZONE_MAX || !z->labels || !stores_ok(z->n_labels) ||
+        (z->values && !stores_ok(z->n_values)) || (z->marks && (!stores_ok(z->n_marks) || (z->where != 0 && z->where != 1))) ||
+        (z->ranked != 0 && z->ranked != 1) || (z->within_marks != 0 && z->within_marks != 1) || !z->cells || !z->marked || !z->least ||
+        !z->nearest || !z->points || !z->roots || !z->n_zones || ((uintptr_t)z->labels % 4) || ((uintptr_t)z->values % 4) ||
+        ((uintptr_t)z->cells % 4) || ((uintptr_t)z->marked % 4) || ((uintptr_t)z->least % 4) || ((uintptr_t)z->nearest % 4) ||
+        ((uintptr_t)z->points % 4) || ((uintptr_t)z->roots % 4) || ((uintptr_t)z->n_zones % 4)) return MS_EINVAL;
+    if ((long long)grid->n_envs*z->n_fields > 0x7fffffffLL/(2*z->max_zones)) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+static NavZoneArgs nav_zone_args(const MsNavZones* z) {
+    return NavZoneArgs{z->labels, z->values, z->marks, z->mask, z->cells, z->marked, z->least, z->nearest, z->points, z->roots, z->n_zones,
+                       z->n_fields, z->n_labels, z->values ? z->n_values : 1, z->marks ? z->n_marks : 1, z->marks ? z->where : 1,
+                       z->within_marks, z->ranked, z->max_zones};
+}
+
+int ms_nav_zones(const MsNavGrid* grid, const MsNavZones* z, void* stream) {
+    const int status = nav_zones_check(grid, z);
+    if (status != MS_OK) return status;
+    hipLaunchKernelGGL(nav_zone_kernel, dim3((unsigned)((long long)grid->n_envs*z->n_fields)), dim3(ZONE_THREADS), 0, (hipStream_t)stream,
+                       nav_args(grid), nav_zone_args(z));
+    return launch_status();
+}
+
+int ms_host_nav_zones(const MsNavGrid* grid, const MsNavZones* z) {
+    const int status = nav_zones_check(grid, z);
+    if (status != MS_OK) return status;
+    zone_serial(nav_args(grid), nav_zone_args(z));
+    return MS_OK;
+}
 
 // View fields (navview.h): the same discipline.  An env of more than 2^30 cells cannot be (MsNavGrid's geom is 32768 a side at most
 // in cuda.nav_grid; here it is max_framed, an int, that bounds it).

@@ -697,5 +697,5 @@ from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, 
 from .nav import nav_geometry, NavGrid, nav_grid, FIELD_CAPACITY, DistanceFields, Paths, PulledPaths, distance_fields, geodesic, SeenMaps, seen_maps, AGE_MAX_TICK, Sweep, AgeMaps, age_maps, SeededFields, seeded_fields, \
     COST_CAPACITY, COST_MAX, CostFields, cost_fields, inflation_costs, mark_costs, \
     CellLayer, cell_layer, MapChannel, map_channel, local_maps, CellDraws, cell_draws, REGION_CAPACITY, Regions, regions, \
-    VIEW_WALL_CAPACITY, ViewFields, view_fields, BASIN_CAPACITY, BASIN_MAX_IDS, PointMarks, point_marks, Basins, basins, \
+    VIEW_WALL_CAPACITY, ViewFields, view_fields, BASIN_CAPACITY, BASIN_MAX_IDS, PointMarks, point_marks, Basins, basins, ZONE_MAX, Zones, zones, \
     CLEARANCE_MAX_RADII, ClearanceFields, clearance_fields, Clearance, clearance

@@ -57,6 +57,7 @@ class FloorCoverage:
         self._frontiers = self._follower = None         # made when the expert is first asked: they cost nothing until then
         self._views = self._views_follower = None
         self._split = self._split_follower = self.territories = None
+        self._assign = self._assign_follower = None
 
     #: the :class:`~megastep_amd.cuda.SeenMaps`
     maps = property(lambda self: self._coverage.maps)
@@ -105,10 +106,20 @@ class FloorCoverage:
         ``kind='views'``: the next-best-view follower instead - every agent towards the candidate standpoint that would reveal
         the most unseen floor per metre walked (:class:`~megastep_amd.modules.BestViews`). ``kind='split'``, for ``shared=True``
         with several agents: the frontier follower over ``Frontiers(territories=Territories(...))`` - every agent towards the
-        nearest unseen floor of the part of the plan it is the nearest agent to, so that an env's agents part ways. Ask one kind
-        per step."""
-        if kind not in ('frontier', 'views', 'split'):
-            raise RuntimeError(f"kind must be 'frontier', 'views' or 'split'; got {kind!r}")
+        nearest unseen floor of the part of the plan it is the nearest agent to, so that an env's agents part ways.
+        ``kind='assign'``, for ``shared=True``: the frontier follower over :class:`~megastep_amd.modules.Assignments` - every agent
+        towards a frontier cluster of its own, the clusters dealt to the agents by walking distance. Ask one kind per step."""
+        if kind not in ('frontier', 'views', 'split', 'assign'):
+            raise RuntimeError(f"kind must be 'frontier', 'views', 'split' or 'assign'; got {kind!r}")
+        if kind == 'assign':
+            if not self._coverage.shared:
+                raise RuntimeError("expert('assign') needs shared=True: agents with a map each have a frontier each already")
+            if self._assign is None:
+                self._assign = modules.Assignments(self.core, self._coverage)
+                self._assign_follower = modules.PathFollower(self.core, self._assign, cone=15.)
+            self._assign(self._fresh)
+            self._fresh.zero_()
+            return self._assign_follower()
         if kind == 'split':
             if not self._coverage.shared:
                 raise RuntimeError("expert('split') needs shared=True: agents with a map each have a frontier each already")

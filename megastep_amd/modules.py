@@ -871,6 +871,128 @@ class Frontiers:
         return self.fallback(self.own.waypoints(self.core.agents.positions, lookahead=lookahead), shared)
 
 
+class Assignments:
+
+    def __init__(self, core, coverage, n_zones=64, refresh=8, cost=None):
+        """Which frontier cluster each agent of an env should walk to, by walking distance (no counterpart in the reference): the
+        standard multi-robot answer to a shared map - not the floor split by where the agents stand (:class:`Territories`), but a
+        different cluster of unseen floor for every agent. Per refresh, for the envs that are due: the clusters the unseen floor
+        falls into (:meth:`cuda.SeenMaps.frontier_regions`), a distance field round every agent (:func:`cuda.distance_fields` of
+        their positions), and ONE :func:`cuda.zones` launch of the two - ``zones.least`` (n_env, n_agent, K) is each agent's walk to
+        the nearest cell of each of the first ``n_zones`` clusters; :meth:`choose` then assigns clusters to agents, the chosen
+        clusters become byte masks (:meth:`cuda.Regions.masks`) and every agent gets a field of its own to its cluster's cells
+        (:attr:`own`: :func:`cuda.seeded_fields` over the masks, among the unseen cells exactly as :attr:`Frontiers.own`; with
+        ``cost`` a :func:`cuda.cost_fields`). An agent without a cluster it can walk to follows the env's shared frontier field
+        (:meth:`Frontiers.fallback`).
+
+        :class:`Frontiers`' interface: call once per step after the maps were marked, then :meth:`distance` and :meth:`waypoints`;
+        :class:`PathFollower` takes it unchanged. For a shared coverage only. An env is refreshed every ``refresh`` steps and when
+        one of its agents starts over. Nothing waits for the host: which envs are due is decided on the device, so a call can sit
+        in a HIP graph."""
+        self.core, self.coverage, self.refresh, self.cost = core, coverage, int(refresh), cost
+        if self.refresh < 1:
+            raise RuntimeError(f'refresh must be a positive integer; got {refresh}')
+        if not coverage.shared:
+            raise RuntimeError('assignments go with a shared coverage: with a map of its own each agent has its own frontier already')
+        n, a = core.n_envs, core.n_agents
+        grid, maps = coverage.grid, coverage.maps
+        self._steps = torch.zeros((n,), dtype=torch.long, device=core.device)
+        self._field = coverage._slot                    # ((n_env, n_agent) zeros: every agent reads the env's one shared field)
+        self.fields = maps.frontier_fields(cost=cost)   # the env's shared frontier field: the fallback
+        self.clusters = maps.frontier_regions()
+        self.around = cuda.distance_fields(grid, core.agents.positions)
+        self.zones = cuda.zones(self.clusters, values=self.around, n_zones=n_zones)
+        #: (n_env, n_agent) int64: the zone each agent was assigned at its env's last refresh, -1 without one
+        self.choice = torch.full((n, a), -1, dtype=torch.long, device=core.device)
+        self._wanted = torch.full((n, a), -1, dtype=torch.int32, device=core.device)
+        self._assign(torch.ones((n, 1), dtype=torch.bool, device=core.device))
+        #: a :class:`cuda.CellLayer` of one byte store per agent: 1 on the cells of the cluster it was assigned
+        self.masks = self.clusters.masks(labels=self._wanted)
+        self._unseen = torch.zeros_like(maps.countable)                 # (grid.free's layout: the shared map is one store an env)
+        self._refresh_unseen()
+        if cost is None:
+            self.own = cuda.seeded_fields(grid, self.masks.values, a, where=True, among=self._unseen)
+        else:
+            self.own = cuda.cost_fields(grid, self.masks.values, a, cost, where=True, among=self._unseen)
+
+    _refresh_unseen = Frontiers._refresh_unseen
+
+    @staticmethod
+    def choose(costs):
+        """The rule, a pure function: ``costs`` (..., A, K) float - agent a's walk to zone k, +inf (or NaN) where it cannot get
+        there. Returns ``(choice, none)``: ``choice`` (..., A) int64, the zone of every agent, -1 without one; ``none`` (..., A)
+        bool, ``choice < 0``.
+
+        1. A times over: among the pairs (a, k) with agent a unassigned, zone k untaken and a finite cost, the least cost - ties to
+           the least a, then the least k - is assigned.
+        2. Every agent still unassigned that has a finite cost takes its own least-cost zone, taken or not; ties to the least k.
+        3. Otherwise -1.
+
+        Greedy and deterministic - NOT the optimal assignment (the least total walk), which it can miss by taking the best pair
+        first. Ties are broken by ``where(c == c.amin) -> least index``, never by ``argmin``, whose choice among equals is not
+        defined. No host synchronisation."""
+        a, k = costs.shape[-2:]
+        inf = torch.full_like(costs, float('inf'))
+        finite = torch.isfinite(costs)
+        open_costs = torch.where(finite, costs, inf)
+        flat_index = torch.arange(a*k, device=costs.device)
+        zone_index = torch.arange(k, device=costs.device)
+        choice = torch.full(costs.shape[:-1], -1, dtype=torch.long, device=costs.device)
+        taken = torch.zeros(costs.shape[:-2] + (k,), dtype=torch.bool, device=costs.device)
+        for _ in range(a):
+            c = torch.where((choice < 0)[..., :, None] & ~taken[..., None, :], open_costs, inf).flatten(-2)
+            least = c.amin(-1, keepdim=True)
+            pair = torch.where(c == least, flat_index, a*k).amin(-1)   # (row-major: the least a, then the least k)
+            found = torch.isfinite(least[..., 0])
+            agent, zone = pair // k, pair % k
+            hit = found[..., None] & (torch.arange(a, device=costs.device) == agent[..., None])
+            choice = torch.where(hit, zone[..., None], choice)
+            taken = taken | (found[..., None] & (zone_index == zone[..., None]))
+        least = open_costs.amin(-1, keepdim=True)
+        nearest = torch.where(open_costs == least, zone_index, k).amin(-1)
+        choice = torch.where((choice < 0) & torch.isfinite(least[..., 0]), nearest, choice)
+        return choice, choice < 0
+
+    def _assign(self, due):
+        """The zones, the choice and the wanted labels of the envs marked in ``due`` (n_env, 1) bool; the others keep theirs."""
+        a = self.core.n_agents
+        self.clusters.update(due)
+        self.around.update(self.core.agents.positions, due.expand(-1, a).contiguous())
+        self.zones.update(due.expand(-1, a).contiguous())
+        choice, none = self.choose(self.zones.least)
+        roots = self.zones.roots.gather(-1, choice.clamp(min=0)[..., None])[..., 0]      # ((n_env, n_agent): F = A fields, one an agent)
+        self.choice.copy_(torch.where(due, choice, self.choice))
+        self._wanted.copy_(torch.where(due, torch.where(none, -1, roots).int(), self._wanted))
+
+    def __call__(self, reset=None):
+        """Refreshes the envs that are due: those with an agent marked in the (n_env, n_agent) bool ``reset`` - it started over, the
+        env's map is empty again - and those that have taken a multiple of ``refresh`` steps since. Call once per step, after the
+        maps were marked."""
+        if reset is not None:
+            self._steps.masked_fill_(reset.any(-1), 0)
+        due = (self._steps % self.refresh == 0)[:, None]
+        self._steps += 1
+        self.due = due                                  # ((n_env, 1) bool: which envs were due at this call)
+        self._assign(due)
+        self.clusters.masks(labels=self._wanted, out=self.masks)
+        self._refresh_unseen()
+        self.own.update(due.expand(-1, self.core.n_agents).contiguous())
+        self.fields.update(due)
+        return self.own
+
+    def distance(self):
+        """(n_env, n_agent): how far every agent has to walk to the nearest unseen floor of its cluster (of the env, without one);
+        +inf where there is none it can reach."""
+        positions = self.core.agents.positions
+        return Frontiers.fallback(self.own.at(positions), self.fields.at(positions, goal=self._field))
+
+    def waypoints(self, lookahead=16):
+        """(n_env, n_agent, 2): where every agent should head for now; NaN where :meth:`distance` is +inf."""
+        positions = self.core.agents.positions
+        return Frontiers.fallback(self.own.waypoints(positions, lookahead=lookahead),
+                                  self.fields.waypoints(positions, goal=self._field, lookahead=lookahead))
+
+
 class Idleness:
 
     def __init__(self, core, grid, max_range=10., shared=False, threshold=64, countable=None):

@@ -4,8 +4,8 @@ they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``c
 and their lengths -, ``csrc/kernels/navseen.h``, ``csrc/kernels/navage.h``
 - when each cell was last seen -, ``csrc/kernels/navwindow.h``,
 ``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), the cells in sight of a
-point (``csrc/kernels/navview.h``), the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``), and the distance
-to the nearest wall, per cell and per point (``csrc/kernels/navclear.h``).
+point (``csrc/kernels/navview.h``), the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``), per-zone counts, least values and nearest cells of any labels (``csrc/kernels/navzone.h``), and
+the distance to the nearest wall, per cell and per point (``csrc/kernels/navclear.h``).
 No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
 import ctypes as C
@@ -963,7 +963,8 @@ def cell_layer(values, n_fields=1, field=None):
     :class:`SeenMaps`, a :class:`DistanceFields` and a :class:`SeededFields` are layers as they are, with their own number of
     stores, an :class:`AgeMaps` too (its ``ages``, in ticks; as a gate its ``stale``), and so are a :class:`Regions` (its ``areas``, square metres), a :class:`ViewFields` (its ``values``, a store a
     viewpoint) and a :class:`ClearanceFields` (its ``values``, metres to the nearest wall: one float store);
-    ``cell_layer(maps, field=slot)`` gives one of them a ``field``."""
+    ``cell_layer(maps, field=slot)`` gives one of them a ``field``. An int32 tensor makes a layer of labels, which only
+    :func:`zones` takes."""
     if isinstance(values, CellLayer):
         values, n_fields = values.values, values.n_fields
     elif isinstance(values, NavGrid):
@@ -984,9 +985,9 @@ def cell_layer(values, n_fields=1, field=None):
         values, n_fields = values.values, 1
     if not isinstance(n_fields, int) or n_fields < 1:
         raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
-    if not isinstance(values, torch.Tensor) or values.dtype not in (torch.uint8, torch.bool, torch.float32) or values.ndim != 1 or \
+    if not isinstance(values, torch.Tensor) or values.dtype not in (torch.uint8, torch.bool, torch.float32, torch.int32) or values.ndim != 1 or \
             not values.is_contiguous():
-        raise RuntimeError('a layer must be a contiguous 1-dimensional uint8, bool or float32 tensor')
+        raise RuntimeError('a layer must be a contiguous 1-dimensional uint8, bool or float32 tensor (or int32: labels, for zones)')
     if values.dtype == torch.bool:
         values = values.view(torch.uint8)
     return CellLayer(values, n_fields, None if field is None else _index(field, 'field'))
@@ -997,7 +998,10 @@ def _layer(x, byte=False):
     which as a float layer presents its ages, presents its stale cells there."""
     if byte and isinstance(x, AgeMaps):
         return cell_layer(x.stale, x.n_maps)
-    return x if isinstance(x, CellLayer) else cell_layer(x)
+    layer = x if isinstance(x, CellLayer) else cell_layer(x)
+    if layer.values.dtype == torch.int32:
+        raise RuntimeError('an int32 layer holds labels: only zones takes it')
+    return layer
 
 
 class MapChannel:
@@ -1287,6 +1291,10 @@ class Regions:
             raise RuntimeError('exactly one of points and labels must be given')
         return _masks(self.grid, self.labels, self.n_fields, points, labels, field, out)
 
+    def zones(self, values=None, marks=None, n_zones=16, where=True, within_marks=False, mask=None, out=None):
+        """:func:`zones` of these regions: per region the cells, the marked cells, the least value and the cell attaining it."""
+        return zones(self, values=values, marks=marks, n_zones=n_zones, where=where, within_marks=within_marks, mask=mask, out=out)
+
     def largest_mask(self, out=None):
         """The byte mask of every env's largest region, ``grid.free``'s layout: ``masks(labels=self.largest[:, :1])``. One regions
         field per env only."""
@@ -1564,6 +1572,10 @@ class Basins:
         synchronisation."""
         return _masks(self.grid, self.labels, self.n_fields, None, labels, field, out)
 
+    def zones(self, values=None, marks=None, n_zones=16, where=True, within_marks=False, mask=None, out=None):
+        """:func:`zones` of these basins: ranked by seed without ``ids``, the id itself the zone with them."""
+        return zones(self, values=values, marks=marks, n_zones=n_zones, where=where, within_marks=within_marks, mask=mask, out=out)
+
 
 def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
     """Which seed each cell of a :class:`SeededFields` leads to: for every field and every cell of its env the seed that the chain
@@ -1608,6 +1620,121 @@ def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
     result = Basins(fields, ids, n_ids, new((size,), torch.int32, -1), new(shape + (n_ids,), torch.int32, 0) if n_ids else None,
                     new(shape, torch.int32, 0), new(shape, torch.int32, 0) if passes else None)
     return result.update(mask)
+
+
+#: the most zones one :func:`zones` call tells apart
+ZONE_MAX = 256
+
+
+class Zones:
+    """Result of :func:`zones`: for each env ``F`` fields and ``K`` zones a field. ``cells`` (N, F, K) int32: the cells of zone k;
+    ``marked`` (N, F, K) int32: those of them that are marked (``cells`` without marks); ``least`` (N, F, K) float32: the least value
+    over the zone's cells that take part - non-negative and below +inf, and marked under ``within_marks`` - +inf when none does;
+    ``nearest`` (N, F, K) int32: the least cell index attaining it, -1 without one; ``points`` (N, F, K, 2) float32: that cell's
+    centre, NaN without one; ``roots`` (N, F, K) int32: the label zone k stands for (ranked: the k-th root, -1 beyond the last;
+    direct: k where the zone has cells, else -1); ``n_zones`` (N, F) int32: the roots there are - which may exceed K: zones from K
+    on are counted there and nowhere else - or, direct, the zones that have cells. ``K``: the zones a field. The labels, values and
+    marks are kept by reference: :meth:`update` reads them as they stand. The rule: include/megastep_hip.h (``MsNavZones``),
+    DESIGN.md 3.28."""
+
+    def __init__(self, grid, source, labels, n_labels, values, n_values, marks, n_marks, where, within_marks, ranked, n_fields, K, new):
+        self.grid, self.source, self.labels, self.values, self.marks = grid, source, labels, values, marks
+        self.n_labels, self.n_values, self.n_marks = int(n_labels), int(n_values), int(n_marks)
+        self.where, self.within_marks, self.ranked = bool(where), bool(within_marks), bool(ranked)
+        self._n_fields, self.K = int(n_fields), int(K)
+        shape = (grid.n_envs, self._n_fields, self.K)
+        self.cells, self.marked = new(shape, torch.int32, 0), new(shape, torch.int32, 0)
+        self.least, self.nearest = new(shape, torch.float32, float('inf')), new(shape, torch.int32, -1)
+        self.points, self.roots = new(shape + (2,), torch.float32, float('nan')), new(shape, torch.int32, -1)
+        self.n_zones = new(shape[:2], torch.int32, 0)
+        self._area = new((), torch.float32, grid.cell)**2
+
+    n_fields = property(lambda self: self._n_fields)
+
+    def update(self, mask=None):
+        """Takes the fields marked in the (N, F) bool ``mask`` (default all) again in place, from the labels, values and marks as
+        they stand now; the others keep every output. One launch, no host synchronisation, nothing allocated: the call can be
+        captured in a HIP graph."""
+        grid, f = self.grid, self.n_fields
+        mask = _mask(mask, grid.n_envs, f, 'F')
+        dev = _require_gpu(self.labels, self.cells, self.marked, self.least, self.nearest, self.points, self.roots, self.n_zones, grid.free,
+                           *_some(self.values, self.marks, mask))
+        _launch(dev, 'zones', grid, _lib.MsNavZones(f, self.labels.data_ptr(), self.n_labels, _ptr(self.values), self.n_values, _ptr(self.marks),
+                                                    self.n_marks, int(self.where), int(self.within_marks), int(self.ranked), self.K, _ptr(mask),
+                                                    self.cells.data_ptr(), self.marked.data_ptr(), self.least.data_ptr(), self.nearest.data_ptr(),
+                                                    self.points.data_ptr(), self.roots.data_ptr(), self.n_zones.data_ptr()))
+        return self
+
+    def areas(self):
+        """(N, F, K) float32: the zones' areas in square metres, ``cells*cell**2``."""
+        return self.cells.float()*self._area
+
+
+def _zone_store(grid, layer, what, dtype):
+    """A zones layer's flat store and its stores per env: no ``field`` (store f serves field f), the dtype the place asks, and an
+    entry per store and cell of the grid."""
+    name = lambda d: str(d).replace('torch.', '')
+    if layer.field is not None:
+        raise RuntimeError(f'{what} must be a layer without a `field`: store f serves field f, one store every field')
+    if layer.values.dtype != dtype:
+        raise RuntimeError(f'{what} must be a layer of {name(dtype)}, not {name(layer.values.dtype)}')
+    if layer.values.shape[0] < max(layer.n_fields*grid.n_cells, 1):
+        raise RuntimeError(f'{what} must have {layer.n_fields}*{grid.n_cells} entries, one per store and cell; got {layer.values.shape[0]}')
+    return layer.values, layer.n_fields
+
+
+def zones(labels, values=None, marks=None, n_zones=16, where=True, within_marks=False, mask=None, out=None, ranked=None, grid=None):
+    """A label and a number together: per zone of a labels layer the cells, the marked cells, the least value and where it is - how
+    far each agent is from the nearest cell of each frontier cluster and which cell that is
+    (``zones(maps.frontier_regions(), values=distance_fields(grid, positions))``), how much of each room has been seen
+    (``zones(regions(grid), marks=maps)``), the oldest cell of each territory.
+
+    ``labels``: a :class:`Regions` (ranked: zone k is the k-th region in the order of their labels), a :class:`Basins` (ranked without
+    ``ids``; with them the id is the zone), or a :func:`cell_layer` of int32 with ``ranked=`` and ``grid=`` given explicitly.
+    ``values``: any float layer :func:`map_channel` and :func:`cell_draws` take; ``marks``: any byte layer, with ``where``.
+    Each of the three has 1 or F stores per env - F the largest of the three counts - and one store serves every field.
+    ``n_zones`` (1..256): K, the zones a field. ``within_marks``: only marked cells take part in ``least``. See :class:`Zones`.
+
+    One launch, one workgroup per field, whatever the env's size: counts by integer atomics in LDS, least and nearest by one 64-bit
+    atomic min on ``(value bits, cell)``; every output is an integer or a copied float (include/megastep_hip.h, ``MsNavZones``;
+    DESIGN.md 3.28).
+
+    ``mask`` (N, F) bool: take only the marked fields (the others keep what ``out`` held; zeros, +inf, -1 and NaN without ``out``);
+    ``out``: the :class:`Zones` of an earlier call with the same labels, values, marks and arguments to write into. No host
+    synchronisation: the call can be captured in a HIP graph."""
+    if isinstance(labels, Regions):
+        own_grid, layer, is_ranked = labels.grid, CellLayer(labels.labels, labels.n_fields, None), True
+    elif isinstance(labels, Basins):
+        own_grid, layer, is_ranked = labels.grid, CellLayer(labels.labels, labels.n_fields, None), labels.ids is None
+    elif isinstance(labels, CellLayer):
+        if ranked is None or grid is None:
+            raise RuntimeError('a cell_layer of labels needs ranked= (are the labels canonical cell indices?) and grid= given explicitly')
+        own_grid, layer, is_ranked = grid, labels, bool(ranked)
+    else:
+        raise RuntimeError('labels must be a Regions, a Basins or a cell_layer of int32')
+    if ranked is not None and bool(ranked) != is_ranked:
+        raise RuntimeError(f'these labels are {"ranked" if is_ranked else "direct"}: ranked={ranked} contradicts them')
+    if grid is not None and grid is not own_grid:
+        raise RuntimeError('grid must be the grid of the labels')
+    grid = own_grid
+    store, n_labels = _zone_store(grid, layer, 'labels', torch.int32)
+    v_store, n_values = (None, 1) if values is None else _zone_store(grid, _layer(values), 'values', torch.float32)
+    m_store, n_marks = (None, 1) if marks is None else _zone_store(grid, _layer(marks, byte=True), 'marks', torch.uint8)
+    f = max(n_labels, n_values, n_marks)
+    for name, count in (('labels', n_labels), ('values', n_values), ('marks', n_marks)):
+        if count not in (1, f):
+            raise RuntimeError(f'{name} has {count} stores per env: each of labels, values and marks must have 1 or F = {f}')
+    if not isinstance(n_zones, int) or isinstance(n_zones, bool) or not 1 <= n_zones <= ZONE_MAX:
+        raise RuntimeError(f'n_zones must be an integer in 1..{ZONE_MAX}; got {n_zones}')
+    where, within_marks = bool(where), bool(within_marks)
+    if out is not None:
+        if not isinstance(out, Zones) or out.grid is not grid or out.K != n_zones or out.n_fields != f or out.ranked != is_ranked or \
+                out.where != where or out.within_marks != within_marks or not _same(out.labels, store) or not _same(out.values, v_store) or \
+                not _same(out.marks, m_store) or (out.n_labels, out.n_values, out.n_marks) != (n_labels, n_values, n_marks):
+            raise RuntimeError('`out` must come from a zones call with the same labels, values, marks, n_zones, where and within_marks')
+        return out.update(mask)
+    new = _new(_require_gpu(store, grid.free, *_some(v_store, m_store)))
+    return Zones(grid, labels, store, n_labels, v_store, n_values, m_store, n_marks, where, within_marks, is_ranked, f, n_zones, new).update(mask)
 
 
 #: the most body sizes one :func:`clearance_fields` call grids for

@@ -1,7 +1,7 @@
 """What the distance fields cost on the MI355X, next to the torch formulation a user would otherwise write:
 
     python tools/navfield_rate.py [--envs 4096] [--distinct 1024] [--repeats 10] [--warmup 3] [--torch-envs 256] [--json out.json]
-                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance|cost|ages|pulls] [--large]
+                                  [--only fields|query|torch|envs|expert|seen|frontier|window|draws|regions|views|basins|clearance|cost|ages|pulls|zones] [--large]
 
 The world is the headline's: `--envs` envs over `--distinct` distinct synthetic floorplans, one agent each, one goal an env
 from the spawn table.  Timed with HIP events around single calls after a warm-up, the median of the repeats reported:
@@ -92,6 +92,15 @@ from the spawn table.  Timed with HIP events around single calls after a warm-up
       paths(max_points=256) and waypoints() on the same fields and points; the mean vertices, and the pulled length over the
       chain's and over `at`; PointGoal(envs, spl=True).step eager and replayed as a HIP graph, next to the plain env; and
       PointGoal(64, spl=True), 300 steps under expert() and under random actions: the mean SPL of the episodes that ended.
+  (n) zones, at `--envs` envs x 2 agents, K = 64: one cuda.zones (ms_nav_zones) of the grid's regions with one distance field, next to
+      the cuda.regions launch before it - the yardstick: the zones launch reads each cell once -; one of the frontier clusters right
+      after a marked frame with a distance field round each of the two agents (F = 2), next to the frontier_regions launch before it;
+      for each the torch formulation of the same rule (the labels padded to the largest plan, the rank of a root by a cumulative sum,
+      scatter_add counts and a scatter_reduce amin over (value bits << 32) | cell; the first `--torch-envs` envs, scaled; cells,
+      least, nearest and n_zones compared for equality); FloorCoverage(envs, n_agents=2, shared=True): expert('assign') + step()
+      eager and replayed as a HIP graph, next to expert('split') and expert('frontier') in the same run; and
+      FloorCoverage(64, n_agents=2, shared=True), 300 steps, in one run under expert('assign'), expert('split'), expert('frontier')
+      and uniformly random actions: episodes ended by coverage and mean final fraction.
 `--only` picks one part (for a profiler run of its own: `rocprofv3 --kernel-trace --stats -- python tools/navfield_rate.py
 --only fields`).  Needs a GPU: there is no CPU fall-back.
 """
@@ -593,6 +602,47 @@ def torch_cost_fields(grid, marks, cost, envs):
     return run
 
 
+def torch_zones(grid, labels, values, n_values, K, envs):
+    """ms_nav_zones' rule, ranked, one labels store and `n_values` value stores an env, for the first `envs` envs by tensor ops on
+    (envs, C) tensors padded to the largest grid's cells: run() -> (cells (envs, K), key (envs, F, K) int64 - (bits << 32) | cell,
+    the int64 maximum without one -, n_zones (envs,))."""
+    dev = labels.device
+    cells = [grid.cells(e) for e in range(envs)]
+    C = max(ny*nx for _, ny, nx in cells)
+    lab = torch.full((envs, C), -1, dtype=torch.int64, device=dev)
+    val = torch.full((envs, n_values, C), float('inf'), device=dev)
+    for e, (first, ny, nx) in enumerate(cells):
+        n = ny*nx
+        lab[e, :n] = labels[first:first + n]
+        val[e, :, :n] = values[n_values*first:n_values*first + n_values*n].reshape(n_values, n)
+    index = torch.arange(C, device=dev)
+    none = torch.iinfo(torch.int64).max
+
+    def run():
+        root = lab == index
+        rank = root.cumsum(-1) - 1
+        safe = lab.clamp(min=0)
+        zone = torch.where((lab >= 0) & root.gather(-1, safe), rank.gather(-1, safe), -1)
+        slot = torch.where((zone >= 0) & (zone < K), zone, K)          # (a spare column for the cells without a zone)
+        count = torch.zeros((envs, K + 1), dtype=torch.int64, device=dev).scatter_add_(-1, slot, torch.ones_like(slot))
+        bits = val.contiguous().view(torch.int32).to(torch.int64)
+        key = torch.where((bits >= 0) & (bits < 0x7f800000), (bits << 32) | index, none)
+        best = torch.full((envs, n_values, K + 1), none, dtype=torch.int64, device=dev)
+        best = best.scatter_reduce(-1, slot[:, None].expand(-1, n_values, -1), key, 'amin')
+        return count[:, :K], best[..., :K], root.sum(-1)
+    return run
+
+
+def zones_equal(z, result, envs):
+    """Are a Zones' cells, least, nearest and n_zones of its first `envs` envs what torch_zones' run() returned?"""
+    count, best, n_zones = result
+    none = best == torch.iinfo(torch.int64).max
+    least = torch.where(none, 0x7f800000, best >> 32).int()
+    nearest = torch.where(none, -1, best & 0xffffffff).int()
+    return bool(torch.equal(z.cells[:envs], count[:, None].expand(-1, z.n_fields, -1).int()) and torch.equal(z.least[:envs].view(torch.int32), least) and
+                torch.equal(z.nearest[:envs], nearest) and torch.equal(z.n_zones[:envs], n_zones[:, None].expand(-1, z.n_fields).int()))
+
+
 def follower_score(env, steps):
     """`steps` steps of a PointGoal under its expert: arrivals, the (agent, step) pairs the follower counted at a dead stop, and the
     mean distance to the nearest wall under the agents."""
@@ -673,7 +723,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--torch-envs', type=int, default=256)
-    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance', 'cost', 'ages', 'pulls'))
+    ap.add_argument('--only', choices=('fields', 'query', 'torch', 'envs', 'expert', 'seen', 'frontier', 'window', 'draws', 'regions', 'views', 'basins', 'clearance', 'cost', 'ages', 'pulls', 'zones'))
     ap.add_argument('--large', action='store_true')
     ap.add_argument('--json')
     args = ap.parse_args()
@@ -1359,6 +1409,66 @@ def main():
                                                         mean_spl=float(scores[ended].mean()) if ended.any() else None,
                                                         mean_spl_of_arrivals=float(scores[ended][scores[ended] > 0].mean()) if (scores[ended] > 0).any() else None)
             print(f'(h) PointGoal(64, spl=True), 300 steps, {policy}: {score}')
+
+    if want('zones'):
+        from megastep_amd.demo.envs.floorcoverage import reachable
+        K = 64
+        sc = scene.scenery(geoms, 2, device='cuda')
+        c = core.Core(sc, res=256, fov=130)
+        table = torch.as_tensor(modules.random_empty_positions(geoms, 2, 2), dtype=torch.float32, device='cuda')
+        c.agents.positions[:] = table[:, :, 0]
+        c.agents.angles.uniform_(-180, 180)
+        grid = cuda.nav_grid(sc, config=c.config)
+        k = min(args.torch_envs, args.envs)
+        # the grid's regions with one distance field
+        rooms = cuda.regions(grid)
+        field = cuda.distance_fields(grid, c.agents.positions[:, :1].contiguous())
+        z = rooms.zones(values=field, n_zones=K)
+        rmed, rlo, rhi = timed(lambda: rooms.update(), args.repeats, args.warmup)
+        med, lo, hi = timed(lambda: z.update(), 2*args.repeats, args.warmup)
+        run = torch_zones(grid, rooms.labels, field.values, 1, K, k)
+        same = zones_equal(z, run(), k)
+        tmed = timed(lambda: run(), max(args.repeats//3, 2), 1)[0]
+        out['zones_regions'] = dict(seconds=med, min=lo, max=hi, fields=args.envs, regions_seconds=rmed, regions_min=rlo, regions_max=rhi,
+                                    zones_mean=float(z.n_zones.float().mean()), zones_most=int(z.n_zones.max()), cells_total=int(grid.n_cells),
+                                    torch_envs=k, torch_seconds=tmed, torch_scaled_seconds=tmed*args.envs/k, torch_equal=same)
+        print(f"(n) zones of the grid's regions with a distance field, {args.envs} fields, K = {K}: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}] next to "
+              f"regions {rmed*1e3:.3f} ms; torch, {k} envs: {tmed*1e3:.2f} ms -> {tmed*args.envs/k*1e3:.1f} ms, equal: {same}; {out['zones_regions']}")
+        # the frontier clusters right after a marked frame, a distance field round each of the two agents
+        maps = cuda.seen_maps(grid, 1, reachable(grid, table[:, 0, 0].contiguous()))
+        slot = torch.zeros((args.envs, 2), dtype=torch.int32, device='cuda')
+        maps.mark_render(c.agents, cuda.render(sc, c.agents, fields=('distances',)), slot=slot)
+        clusters = maps.frontier_regions()
+        around = cuda.distance_fields(grid, c.agents.positions.contiguous())
+        z2 = cuda.zones(clusters, values=around, n_zones=K)
+        cmed, clo, chi = timed(lambda: clusters.update(), args.repeats, args.warmup)
+        amed = timed(lambda: around.update(), args.repeats, args.warmup)[0]
+        med, lo, hi = timed(lambda: z2.update(), 2*args.repeats, args.warmup)
+        run = torch_zones(grid, clusters.labels, around.values, 2, K, k)
+        same = zones_equal(z2, run(), k)
+        tmed = timed(lambda: run(), max(args.repeats//3, 2), 1)[0]
+        out['zones_clusters'] = dict(seconds=med, min=lo, max=hi, fields=2*args.envs, frontier_regions_seconds=cmed, frontier_regions_min=clo,
+                                     frontier_regions_max=chi, distance_fields_seconds=amed, clusters_mean=float(z2.n_zones.float().mean()),
+                                     clusters_most=int(z2.n_zones.max()), reached_share=float(torch.isfinite(z2.least).any(-1).float().mean()),
+                                     torch_envs=k, torch_seconds=tmed, torch_scaled_seconds=tmed*args.envs/k, torch_equal=same)
+        print(f"(n) zones of the frontier clusters after one frame, {args.envs} envs x 2 agents, K = {K}: {med*1e6:.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}] next to "
+              f"frontier_regions {cmed*1e3:.3f} ms and distance_fields {amed*1e3:.3f} ms; torch, {k} envs: {tmed*1e3:.2f} ms -> "
+              f"{tmed*args.envs/k*1e3:.1f} ms, equal: {same}; {out['zones_clusters']}")
+        del sc, c, grid, rooms, field, z, maps, clusters, around, z2, run
+        torch.cuda.empty_cache()
+        for kind in ('assign', 'split', 'frontier'):
+            env = ExpertStep(FloorCoverage(args.envs, n_agents=2, shared=True, geometries=geoms), kind)
+            eager, graphed = env_rates(env, args.envs, 60, 10)
+            out[f'FloorCoverage_shared_{kind}_expert'] = dict(expert_step_eager_seconds=eager, expert_step_graph_seconds=graphed)
+            print(f"(n) FloorCoverage({args.envs}, n_agents=2, shared=True), expert('{kind}') + step: eager {eager*1e3:.3f} ms, graph {graphed*1e3:.3f} ms")
+            del env
+            torch.cuda.empty_cache()
+        small = cubicasa.sample(64, seed=7, n_unique=64)
+        for policy in ('assign', 'split', 'frontier', 'random'):
+            torch.manual_seed(3); np.random.seed(3)
+            env = FloorCoverage(64, n_agents=2, shared=True, geometries=small, max_lifespan=300)
+            out['zones_shared_coverage_' + policy] = score = coverage_score(env, 300, policy)
+            print(f'(n) FloorCoverage(64, n_agents=2, shared=True), 300 steps, {policy}: {score}')
 
     if args.json:
         with open(args.json, 'w') as f:
