@@ -279,6 +279,33 @@ int ms_physics(const MsScenery* scenery, const MsAgents* agents, float* progress
 int ms_step_physics(const MsScenery* scenery, const MsAgents* agents, const MsMovement* movement, const MsStepExtras* extras,
                     float* progress, const MsConfig* config, void* hip_stream);
 
+/* Sliding contacts (no counterpart in the reference, whose step stops an agent dead - velocity and spin - at
+ * whatever its disc touches): the same step with a second contact phase in the same launch, opt-in.  Per agent, after the
+ * respawn, lifespan and movement prologue of ms_step_physics, every operation in binary32 in the order written:
+ *   phase A   u = v/fps; x1 = the least of collision_cc against the env's other agents at their start-of-step (p_b, u_b) and of
+ *             collision_cs over the env's static rows: ms_step_physics' `progress`, bit for bit.  !(x1 < 1): the step ends as
+ *             ms_step_physics ends it - every output of every agent of an env in which nobody was blocked is the plain step's.
+ *   contact   (p1, ang1) = the integration with x1.  A blocker is an obstacle whose own collision value equals x1; its offset d
+ *             = p1 - q, q the nearest point of a static row (a, b) - a + t (b - a), t = dot(p1 - a, b - a)/dot(b - a, b - a)
+ *             clamped to [0, 1], NaN as 0 - or, of agent b, p_b + x1 u_b.  l = |d|; !(l > 0) or a non-finite l: passed over.
+ *             n = (d.x/l + 0, d.y/l + 0), vn = dot(v, n); the winner is the least (vn, n.x, n.y), lexicographically under
+ *             float < - by value, so that any order of meeting the obstacles, and copies of a row, agree.  No winner, or
+ *             !(vn < 0): the plain step's dead stop at p1.
+ *   phase B   v' = v - ((1 + bounce) vn) n; r1 = 1 - x1; u2 = (v' r1)/fps; x2 = the least of collision_cs(p1, u2, row) and of
+ *             collision_cc(p1, u2, p1_b, u2_b) against the other agents as phase A left them (u2_b = 0 for one that does not
+ *             slide); p = p1 + x2 u2; angle = normalize(ang1 + x2 (r1 w)/fps); x2 < 1: v = 0, w = 0 - a dead stop as ever -
+ *             else v = v', w kept.
+ * `progress` = x1, as before.  Respawns after the step, the IMU reading and the heading cache take the final state.
+ * 0 <= bounce <= 1 (0.05 is a good value: without an outward part a tangential second move is stopped by collision_cs' side
+ * test at once), n_agents <= 64: MS_EINVAL / MS_EUNSUPPORTED otherwise, before anything is launched. */
+typedef struct MsSlide {
+    float          bounce;
+    float*         slid;      /* (N, A) or NULL: x2 r1, the share of the step spent sliding; 0 where no slide was attempted       */
+    unsigned char* stopped;   /* (N, A) or NULL: 1 where the step's collisions zeroed the velocity (a respawn is not counted)     */
+} MsSlide;
+int ms_slide_physics(const MsScenery* scenery, const MsAgents* agents, const MsMovement* movement, const MsStepExtras* extras,
+                     const MsSlide* slide, float* progress, const MsConfig* config, void* hip_stream);
+
 /* Replaces `render(scenery, agents) -> Render` (wrappers.cpp:82, kernels.cu:297-475):
  * draw (rewrites the agent rows of lines_vals) -> raycast -> shade, one fused launch. */
 int ms_render(const MsScenery* scenery, const MsAgents* agents, const MsRender* out,
@@ -422,7 +449,11 @@ int ms_overhead(const MsScenery* scenery, const MsAgents* agents /* NULL: agent 
  * first of them (H: none), and optionally the position after every step.  With a mask only the marked agents are rolled and
  * the rows of the others are left as they are.  Not in a rollout: other agents that move, respawns, lifespans, the IMU.
  * Nothing is allocated, no global atomics, nothing waits for the host: the call can be captured in a HIP graph.  1 <= K <= 256,
- * 1 <= H <= 64, n_actions >= 1, others in {0, 1}: MS_EINVAL otherwise, before anything is launched. */
+ * 1 <= H <= 64, n_actions >= 1, others in {0, 1}: MS_EINVAL otherwise, before anything is launched.
+ * slide = 1: `walls`, `others` and `advance` are the sliding step's (MsSlide above: phase A, the contact, phase B with `bounce`),
+ * the others at rest in both phases; stops and first_stop count the steps whose velocity was zeroed, and `slides` the steps
+ * that slid the whole of their remainder (x2 = 1).  slide in {0, 1}, 0 <= bounce <= 1 with slide: MS_EINVAL otherwise.  (The
+ * three fields are the struct's last and MS_ABI_VERSION stays 17: a zeroed tail is the call as it was.) */
 typedef struct MsRollouts {
     int                  n_candidates;  /* K                                                                           */
     int                  horizon;       /* H                                                                           */
@@ -441,6 +472,9 @@ typedef struct MsRollouts {
     int*                 stops;         /* (N, A, K) out                                                               */
     int*                 first_stop;    /* (N, A, K) out                                                               */
     float*               trail;         /* (N, A, K, H, 2) out, optional, 8-byte aligned                               */
+    int                  slide;         /* 1: every step is the sliding step                                           */
+    float                bounce;        /* as MsSlide's                                                                */
+    int*                 slides;        /* (N, A, K) out, optional: the steps that slid their whole remainder          */
 } MsRollouts;
 int ms_rollouts(const MsScenery* scenery, const MsAgents* agents, const MsRollouts* rollouts, const MsConfig* config,
                 void* hip_stream);

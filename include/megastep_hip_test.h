@@ -29,7 +29,8 @@ int ms_debug_physics_pack(int envs);
  * account, which a caller re-deriving the rule cannot know; 0 before the thread's first call.  bench.py labels its
  * lines with it. */
 int ms_debug_last_render_groups(void);
-/* Did the calling thread's last ms_step_render go out as one launch (1) or as ms_physics + ms_render (0)? */
+/* Did the calling thread's last ms_step_render go out as one launch (1) or as ms_physics + ms_render (0)?  (ms_slide_physics
+ * sets it to 0: a sliding step followed by ms_render is always two launches.) */
 int ms_debug_last_step_fused(void);
 /* The launch geometry ms_render / ms_step_physics decide on the host, and the render kernel's own block -> rays mapping
  * (render_block), for tests that walk whole launches on the CPU.  `slots`: the machine's wave slots for the render kernel (CUs x
@@ -248,6 +249,16 @@ int ms_host_rollouts(const float* walls, int n_walls, const MsAgents* agents, in
  * LDS before the exact test; -1 = the library's own choice (1 up to 24 candidates an agent, else 0); anything else: MS_EINVAL.  Per calling thread; A/B runs and tests -
  * either setting produces the same bits. */
 int ms_debug_rollout_scheme(int scheme);
+/* The sliding step (MsSlide) stated serially over the kernel's own per-agent functions (kernels/slide.h) for n_envs whole envs on
+ * HOST arrays: `walls` holds the STATIC rows of all envs, four floats each, env n's rows wall_starts[n] .. wall_starts[n + 1] - 1;
+ * every pointer of `agents` (headings and schedule are not read), `movement`, `extras` (either may be NULL), `slide` and
+ * `progress` is host memory, shaped as ms_slide_physics'.  There is no wall grid on the host: every agent meets every row of its
+ * env, behind the reach cull.  The movement and the IMU reading use the host libm's sine and cosine.  Returns what
+ * ms_slide_physics would: MS_OK, MS_EINVAL for arguments it would refuse (and for NULL walls or wall_starts, n_envs < 1,
+ * n_agents < 1), MS_EUNSUPPORTED for more than 64 agents an env. */
+int ms_host_slide(const float* walls, const long long* wall_starts, int n_envs, int n_agents, const MsAgents* agents,
+                  const MsMovement* movement, const MsStepExtras* extras, const MsSlide* slide, float* progress,
+                  const MsConfig* config);
 /* Host instantiation of the scan's test, for CPU tests: does wall o = (ax, ay, bx, by) hide wall w from every point of
  * the cell [x0, x1] x [y0, y1] (as ms_wallgrid_scan grows it) for near planes below `near_plane`? */
 int ms_host_wall_hidden(float x0, float y0, float x1, float y1, const float* o, const float* w, float near_plane);

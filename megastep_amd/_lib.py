@@ -61,6 +61,10 @@ class MsStepExtras(C.Structure):
                 ('imu', C.c_void_p), ('imu_ang_scale', C.c_float), ('imu_speed_scale', C.c_float)]
 
 
+class MsSlide(C.Structure):
+    _fields_ = [('bounce', C.c_float), ('slid', C.c_void_p), ('stopped', C.c_void_p)]
+
+
 class MsRender(C.Structure):
     _fields_ = [('indices', C.c_void_p), ('locations', C.c_void_p), ('dots', C.c_void_p), ('distances', C.c_void_p),
                 ('screen', C.c_void_p), ('workspace', C.c_void_p), ('obs_rgb', C.c_void_p), ('obs_depth', C.c_void_p),
@@ -96,7 +100,7 @@ class MsRollouts(C.Structure):
     _fields_ = [('n_candidates', C.c_int), ('horizon', C.c_int), ('actions', C.c_void_p), ('shared_plans', C.c_int), ('table', C.c_void_p),
                 ('n_actions', C.c_int), ('keep', C.c_float), ('others', C.c_int), ('mask', C.c_void_p), ('positions', C.c_void_p),
                 ('angles', C.c_void_p), ('velocity', C.c_void_p), ('angvelocity', C.c_void_p), ('progress', C.c_void_p), ('stops', C.c_void_p),
-                ('first_stop', C.c_void_p), ('trail', C.c_void_p)]
+                ('first_stop', C.c_void_p), ('trail', C.c_void_p), ('slide', C.c_int), ('bounce', C.c_float), ('slides', C.c_void_p)]
 
 
 class MsNavGrid(C.Structure):
@@ -259,6 +263,7 @@ PROTOTYPES = {
     'ms_physics': (_int, [_p(MsScenery), _p(MsAgents), _ptr, _p(MsConfig), _ptr]),
     'ms_move_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _ptr, _p(MsConfig), _ptr]),
     'ms_step_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _ptr, _p(MsConfig), _ptr]),
+    'ms_slide_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsSlide), _ptr, _p(MsConfig), _ptr]),
     'ms_render': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRender), _p(MsConfig), _ptr]),
     'ms_step_render': (_int, [_p(MsScenery), _p(MsAgents), _ptr, _p(MsRender), _p(MsConfig), _ptr]),
     'ms_move_step_render': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _ptr, _p(MsRender), _p(MsConfig), _ptr]),
@@ -354,6 +359,7 @@ PROTOTYPES = {
     'ms_host_move_velocity': (None, [_flt, _flt, _f32p, _f32p, _f32p]),
     'ms_host_rollouts': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsRollouts), _p(MsConfig)]),
     'ms_debug_rollout_scheme': (_int, [_int]),
+    'ms_host_slide': (_int, [_ptr, _ptr, _int, _int, _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsSlide), _ptr, _p(MsConfig)]),
     'ms_host_wall_hidden': (_int, [_flt]*4 + [_f32p, _f32p, _flt]),
     'ms_host_wall_sectors': (None, [_flt]*4 + [_f32p, _i32p, _i32p, _f32p, _i32p]),
     'ms_host_wallgrid_cell': (None, [_ptr, _int, _flt, _flt, _int, _int, _flt, _int, _flt, _flt, _flt, _ptr, _ptr]),

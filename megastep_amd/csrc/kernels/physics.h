@@ -23,13 +23,13 @@ constexpr int PHYS_PAIRS = (PHYS_FEW + 1)*WAVE;   // capacity of a wave's (wall,
 
 // The per-agent rules of a step, on values: physics_kernel and the one-launch step (render.h) call them with loads, stores and lanes of their own.
 // the spawn pose of agent i, if it is to be respawned (modules.py:321-326)
-__device__ inline void spawn_pose(const MsStepExtras& ex, const int i, float2& p, float& ang) {
+__host__ __device__ inline void spawn_pose(const MsStepExtras& ex, const int i, float2& p, float& ang) {
     const long long c = min(max(ex.respawn_choice[i], 0ll), (long long)ex.n_spawns - 1);
     p = reinterpret_cast<const float2*>(ex.spawn_positions)[(size_t)i*ex.n_spawns + c];
     ang = ex.spawn_angles[(size_t)i*ex.n_spawns + c];
 }
 // agent i's new age (modules.py:361-366): 0 if `reset` (its respawn mask) is set or comes out set because it has lived its span
-__device__ inline int lifespan_tick(const MsStepExtras& ex, const int i, bool& reset) {
+__host__ __device__ inline int lifespan_tick(const MsStepExtras& ex, const int i, bool& reset) {
     const int life = ex.lifespans[i] + 1;
     reset = reset | (life >= ex.max_lifespans[i]);
     return reset ? 0 : life;
@@ -56,7 +56,7 @@ __host__ __device__ inline bool integrate(const float x, const float fps, float2
     return stopped;
 }
 // the IMU reading (modules.py:263-270, to_local_frame :24-31); the scales are reciprocals: ATen's `a * (1.f/b)` for tensor / scalar
-__device__ inline float3 imu_reading(const MsStepExtras& ex, const float ang, const float2 v, const float w) {
+__host__ __device__ inline float3 imu_reading(const MsStepExtras& ex, const float ang, const float2 v, const float w) {
     const float a_ = 0.017453292519943295f*ang;                         // (as move_velocity)
     const float s_ = sinf(a_), c_ = cosf(a_);
     return make_float3(w*ex.imu_ang_scale, (c_*v.x + s_*v.y)*ex.imu_speed_scale, (-s_*v.x + c_*v.y)*ex.imu_speed_scale);

@@ -52,9 +52,45 @@ __host__ __device__ inline void rollout_advance(RolloutState& st, const float x,
     if (stopped) { st.stops++; st.first = h < st.first ? h : st.first; }
 }
 
+// Under MsRollouts.slide a step is the sliding step (kernels/slide.h), the others at rest in both phases.  The contact's pass:
+// a row, or an agent at rest at pb, whose own collision value is x1 offers its normal at p1, weighed by v
+__host__ __device__ inline void rollout_offer_wall(SlideBest& best, const RolloutTask& t, const float4 u, const float x1, const float2 p1,
+                                                   const float2 v, const float agent_radius) {
+    if (wall_beyond(t.tk, u, t.reach2)) return;
+    const float c = collision_cs(p2(t.tk.x, t.tk.y), p2(t.tk.z, t.tk.w), p2(u.x, u.y), p2(u.z, u.w), agent_radius);
+    float nx, ny;
+    if (c == x1 && slide_normal_wall(p2(p1.x, p1.y), u, nx, ny)) slide_offer(best, v, nx, ny);
+}
+__host__ __device__ inline void rollout_offer_agent(SlideBest& best, const RolloutTask& t, const float2 pb, const float x1, const float2 p1,
+                                                    const float2 v, const float agent_radius) {
+    const float4 o = make_float4(pb.x, pb.y, 0.f, 0.f);
+    if (agents_apart(t.tk, o, agent_radius)) return;
+    const float c = collision_cc(p2(t.tk.x, t.tk.y), p2(t.tk.z, t.tk.w), p2(o.x, o.y), p2(o.z, o.w), agent_radius);
+    float nx, ny;
+    if (c == x1 && slide_normal_agent(p2(p1.x, p1.y), p2(o.x, o.y), p2(0.f, 0.f), x1, nx, ny)) slide_offer(best, v, nx, ny);
+}
+// phase B's task: from where phase A left the candidate, the displacement it tries
+__host__ __device__ inline RolloutTask rollout_task_b(const SlideContact& c, const float agent_radius) {
+    const P2 p0 = p2(c.p1.x, c.p1.y), v0 = p2(c.u2.x, c.u2.y);
+    const float reach = wall_reach(p0, v0, agent_radius);
+    return RolloutTask{make_float4(p0.x, p0.y, v0.x, v0.y), (reach == reach) ? reach : INFINITY, reach_squared(reach)};
+}
+// the sliding step's end and the rollout's books for step h: a stop is a step whose velocity was zeroed
+__host__ __device__ inline void rollout_advance_slide(RolloutState& st, int& slides, const SlideContact& c, const float x1, const float x2,
+                                                      const float fps, const int h) {
+    float slid;
+    const bool stopped = slide_finish(c, x2, fps, st.p, st.ang, st.v, st.w, slid);
+    st.least = x1 < st.least ? x1 : st.least;
+    if (stopped) { st.stops++; st.first = h < st.first ? h : st.first; }
+    else if (c.slides) slides++;
+}
+
 constexpr int ROLL_AHEAD = 4;          // rows of a near list a lane has in flight
 
 // r.n_candidates candidates in groups of 64: block = (n A + a)*groups + group (by_g divides by groups, by_a by n_agents)
+// SLIDE = 1: the sliding step - a lane's obstacles are met by one walk, called for phase A, then (only in a wave with a blocked
+// candidate, and for those) for the contact, then (only with one that slides) for phase B from the cell the candidate stands in then
+template <int SLIDE>
 __global__ __launch_bounds__(WAVE) void rollout_kernel(
         const MsScenery sc, const AgentsK ag, const MsRollouts r, const float agent_radius, const float fps, const int groups,
         const Divisor by_g, const Divisor by_a) {
@@ -82,6 +118,7 @@ __global__ __launch_bounds__(WAVE) void rollout_kernel(
     const float tab = r.table[min(lane, 3*r.n_actions - 1)];
     float2* __restrict__ trail = reinterpret_cast<float2*>(r.trail);
     const size_t cand = (size_t)row*K + kk;
+    [[maybe_unused]] int slides = 0;
     long long act = plan[0];
     for (int h = 0; h < H; h++) {
         const long long next = plan[min(h + 1, H - 1)];                  // (asked for a step ahead)
@@ -91,38 +128,63 @@ __global__ __launch_bounds__(WAVE) void rollout_kernel(
         else { dx = r.table[3*c]; dy = r.table[3*c + 1]; dw = r.table[3*c + 2]; }
         move_velocity(r.keep, st.ang, dx, dy, dw, st.v, st.w);
         const RolloutTask t = rollout_task(st, agent_radius, fps);
-        float x = 1.f;
-        if (r.others) {
-            for (int b = 0; b < A; b++) {
-                if (b != a) x = rollout_meet_agent(x, t, pos2[n*A + b], agent_radius);
-            }
-        }
-        bool covered = false;
-        if (gridded) {
-            bool inside;
-            const int cell = wg_cell_at(geom, sc.wg_cell, st.p.x, st.p.y, inside);
-            const uint4 hdr = reinterpret_cast<const uint4*>(sc.wg_cells)[wg_start + cell];
-            covered = inside & (t.reach <= sc.wg_reach);
-            const int count = covered ? near_count(hdr, t.reach, sc.wg_reach_lo) : 0;
-            const float4* __restrict__ near = reinterpret_cast<const float4*>(sc.wg_near_rows) + hdr.z;
-            for (int j0 = 0; __ballot(j0 < count) != 0ull; j0 += ROLL_AHEAD) {
-                float4 u[ROLL_AHEAD];
-                #pragma unroll
-                for (int q = 0; q < ROLL_AHEAD; q++) u[q] = (j0 + q < count) ? near[j0 + q] : make_float4(0.f, 0.f, 0.f, 0.f);
-                #pragma unroll
-                for (int q = 0; q < ROLL_AHEAD; q++) {
-                    if (j0 + q < count) x = rollout_meet_wall(x, t, u[q], agent_radius);
+        // a candidate's obstacles - the others at rest, then the near list of the cell `at` lies in, or the env's static rows -
+        // met for `mode` (0: the fold of the least value; 1, SLIDE: the contact's offers) by the lanes that are `on`
+        SlideBest best{0.f, 0.f, 0.f, 0};
+        float2 p1 = st.p;
+        float x1 = 1.f;
+        auto walk = [&](const RolloutTask& t, const float2 at, const bool on, const int mode) -> float {
+            float x = 1.f;
+            auto wall = [&](const float4 u) {
+                if (SLIDE == 0 || mode != 1) x = rollout_meet_wall(x, t, u, agent_radius);
+                else rollout_offer_wall(best, t, u, x1, p1, st.v, agent_radius);
+            };
+            if (r.others && on) {
+                for (int b = 0; b < A; b++) {
+                    if (b == a) continue;
+                    if (SLIDE == 0 || mode != 1) x = rollout_meet_agent(x, t, pos2[n*A + b], agent_radius);
+                    else rollout_offer_agent(best, t, pos2[n*A + b], x1, p1, st.v, agent_radius);
                 }
             }
-        }
-        if (__ballot(!covered) != 0ull) {
-            // (rare with a grid, and plain: every static row of the env to the lanes no list covers - the rows' addresses are the wave's)
-            for (int l = AF; l < L; l++) {
-                const float4 u = ln[l];
-                if (!covered) x = rollout_meet_wall(x, t, u, agent_radius);
+            bool covered = !on;
+            if (gridded) {
+                bool inside;
+                const int cell = wg_cell_at(geom, sc.wg_cell, at.x, at.y, inside);
+                const uint4 hdr = reinterpret_cast<const uint4*>(sc.wg_cells)[wg_start + cell];
+                covered = !on | (inside & (t.reach <= sc.wg_reach));
+                const int count = (on && covered) ? near_count(hdr, t.reach, sc.wg_reach_lo) : 0;
+                const float4* __restrict__ near = reinterpret_cast<const float4*>(sc.wg_near_rows) + hdr.z;
+                for (int j0 = 0; __ballot(j0 < count) != 0ull; j0 += ROLL_AHEAD) {
+                    float4 u[ROLL_AHEAD];
+                    #pragma unroll
+                    for (int q = 0; q < ROLL_AHEAD; q++) u[q] = (j0 + q < count) ? near[j0 + q] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    #pragma unroll
+                    for (int q = 0; q < ROLL_AHEAD; q++) {
+                        if (j0 + q < count) wall(u[q]);
+                    }
+                }
             }
+            if (__ballot(!covered) != 0ull) {
+                // (rare with a grid, and plain: every static row of the env to the lanes no list covers - the rows' addresses are the wave's)
+                for (int l = AF; l < L; l++) {
+                    const float4 u = ln[l];
+                    if (!covered) wall(u);
+                }
+            }
+            return x;
+        };
+        if constexpr (SLIDE == 0) {
+            rollout_advance(st, walk(t, st.p, true, 0), fps, h);
+        } else {
+            x1 = walk(t, st.p, true, 0);
+            const bool blocked = x1 < 1;
+            p1 = make_float2(st.p.x + x1*st.v.x/fps, st.p.y + x1*st.v.y/fps);
+            if (__ballot(blocked) != 0ull) walk(t, st.p, blocked, 1);
+            const SlideContact con = slide_contact(st.p, st.ang, st.v, st.w, x1, fps, best, r.bounce);
+            float x2 = 1.f;
+            if (__ballot(con.slides) != 0ull) x2 = walk(rollout_task_b(con, agent_radius), con.p1, con.slides, 2);
+            rollout_advance_slide(st, slides, con, x1, x2, fps, h);
         }
-        rollout_advance(st, x, fps, h);
         if (trail && live) trail[cand*H + h] = st.p;
         act = next;
     }
@@ -134,6 +196,7 @@ __global__ __launch_bounds__(WAVE) void rollout_kernel(
         r.progress[cand] = st.least;
         r.stops[cand] = st.stops;
         r.first_stop[cand] = st.first;
+        if constexpr (SLIDE == 1) { if (r.slides) r.slides[cand] = slides; }
     }
 }
 
@@ -283,6 +346,7 @@ inline void rollout_serial(const float* walls, const int n_walls, const MsAgents
                                             make_float2(ag.velocity[2*a], ag.velocity[2*a + 1]), ag.angvelocity[a], H);
             const long long* plan = r.actions + ((r.shared_plans ? (size_t)0 : (size_t)a*K) + k)*H;
             const size_t cand = (size_t)a*K + k;
+            int slides = 0;
             for (int h = 0; h < H; h++) {
                 const int c = rollout_action(plan[h], r.n_actions);
                 move_velocity(r.keep, st.ang, r.table[3*c], r.table[3*c + 1], r.table[3*c + 2], st.v, st.w);
@@ -295,7 +359,33 @@ inline void rollout_serial(const float* walls, const int n_walls, const MsAgents
                 }
                 for (int l = 0; l < n_walls; l++)
                     x = rollout_meet_wall(x, t, make_float4(walls[4*l], walls[4*l + 1], walls[4*l + 2], walls[4*l + 3]), agent_radius);
-                rollout_advance(st, x, fps, h);
+                if (!r.slide) rollout_advance(st, x, fps, h);
+                else {
+                    SlideBest best{0.f, 0.f, 0.f, 0};
+                    SlideContact con = slide_contact(st.p, st.ang, st.v, st.w, x, fps, best, r.bounce);
+                    if (con.blocked) {
+                        if (r.others) {
+                            for (int b = 0; b < A; b++) {
+                                if (b != a) rollout_offer_agent(best, t, make_float2(ag.positions[2*b], ag.positions[2*b + 1]), x, con.p1, st.v, agent_radius);
+                            }
+                        }
+                        for (int l = 0; l < n_walls; l++)
+                            rollout_offer_wall(best, t, make_float4(walls[4*l], walls[4*l + 1], walls[4*l + 2], walls[4*l + 3]), x, con.p1, st.v, agent_radius);
+                        con = slide_contact(st.p, st.ang, st.v, st.w, x, fps, best, r.bounce);
+                    }
+                    float x2 = 1.f;
+                    if (con.slides) {
+                        const RolloutTask t2 = rollout_task_b(con, agent_radius);
+                        if (r.others) {
+                            for (int b = 0; b < A; b++) {
+                                if (b != a) x2 = rollout_meet_agent(x2, t2, make_float2(ag.positions[2*b], ag.positions[2*b + 1]), agent_radius);
+                            }
+                        }
+                        for (int l = 0; l < n_walls; l++)
+                            x2 = rollout_meet_wall(x2, t2, make_float4(walls[4*l], walls[4*l + 1], walls[4*l + 2], walls[4*l + 3]), agent_radius);
+                    }
+                    rollout_advance_slide(st, slides, con, x, x2, fps, h);
+                }
                 if (r.trail) { r.trail[2*(cand*H + h)] = st.p.x; r.trail[2*(cand*H + h) + 1] = st.p.y; }
             }
             r.positions[2*cand] = st.p.x; r.positions[2*cand + 1] = st.p.y;
@@ -305,6 +395,7 @@ inline void rollout_serial(const float* walls, const int n_walls, const MsAgents
             r.progress[cand] = st.least;
             r.stops[cand] = st.stops;
             r.first_stop[cand] = st.first;
+            if (r.slide && r.slides) r.slides[cand] = slides;
         }
     }
 }

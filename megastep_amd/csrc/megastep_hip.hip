@@ -2,7 +2,7 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, slide.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
 //
 // Thirty kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
@@ -178,6 +178,7 @@ struct Probe {
 
 #include "kernels/math.h"
 #include "kernels/physics.h"
+#include "kernels/slide.h"
 #include "kernels/rollout.h"
 #include "kernels/lighting.h"
 #include "kernels/render.h"
@@ -607,17 +608,64 @@ void ms_host_move_velocity(float keep, float ang, const float* delta, float* v, 
     v[0] = vv.x; v[1] = vv.y;
 }
 
+// what ms_slide_physics and ms_host_slide refuse alike of an MsSlide and the shape it is for
+static int slide_status(const MsSlide* sl, const int n_agents) {
+    if (!sl || !(sl->bounce >= 0.f && sl->bounce <= 1.f)) return MS_EINVAL;
+    if (n_agents > WAVE) return MS_EUNSUPPORTED;                         // (a lane an agent)
+    return MS_OK;
+}
+
+int ms_slide_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* mv, const MsStepExtras* ex, const MsSlide* sl,
+                     float* progress, const MsConfig* cfg, void* stream) {
+    if (!scenery_ok(sc) || !agents_ok(ag) || !progress || !config_ok(cfg)) return MS_EINVAL;
+    if (!step_options_ok(mv, ex) || ((uintptr_t)ag->schedule % 4)) return MS_EINVAL;
+    if (sc->wg_cells && (!sc->wg_starts || !sc->wg_geom || !sc->wg_near_rows || !(sc->wg_cell > 0.f) || ((uintptr_t)sc->wg_cells % 16) ||
+                         ((uintptr_t)sc->wg_geom % 16) || ((uintptr_t)sc->wg_near_rows % 16))) return MS_EINVAL;
+    if (((uintptr_t)ag->positions % 8) || ((uintptr_t)ag->velocity % 8) || ((uintptr_t)ag->headings % 16)) return MS_EINVAL;
+    if (const int st = slide_status(sl, sc->n_agents)) return st;
+    g_last_step_fused = 0;                                               // (a sliding step is never the one-launch step)
+    MsMovement mvv; MsStepExtras exv;
+    step_options_of(mv, ex, mvv, exv);
+    const hipStream_t hs = (hipStream_t)stream;
+    // the fan schedule's sort waves, in front of the launch's own, as ms_step_physics'
+    FanSort fs{nullptr, 0, 1, 0};
+    if (schedule_serves(ag, sc, cfg->res)) {
+        fs.schedule = ag->schedule; fs.n_fans = sc->n_envs*sc->n_agents;
+        fs.per_run = fan_sort_per_run(fs.n_fans); fs.n_blocks = 8*fs.per_run;
+    }
+#define MS_LAUNCH_SLIDE(M, E) \
+    hipLaunchKernelGGL((physics_slide_kernel<M, E>), dim3(fs.n_blocks + sc->n_envs), dim3(WAVE), 0, hs, *sc, agents_k(*ag), progress, cfg->agent_radius, cfg->fps, mvv, exv, *sl, divisor_of((unsigned)sc->n_agents), fs)
+    if (mv && ex) MS_LAUNCH_SLIDE(1, 1);
+    else if (ex) MS_LAUNCH_SLIDE(0, 1);
+    else if (mv) MS_LAUNCH_SLIDE(1, 0);
+    else MS_LAUNCH_SLIDE(0, 0);
+#undef MS_LAUNCH_SLIDE
+    return launch_status();
+}
+
+int ms_host_slide(const float* walls, const long long* wall_starts, int n_envs, int n_agents, const MsAgents* ag, const MsMovement* mv,
+                  const MsStepExtras* ex, const MsSlide* sl, float* progress, const MsConfig* cfg) {
+    if (!walls || !wall_starts || n_envs < 1 || n_agents < 1 || !agents_ok(ag) || !progress || !config_ok(cfg)) return MS_EINVAL;
+    if (!step_options_ok(mv, ex)) return MS_EINVAL;
+    if (const int st = slide_status(sl, n_agents)) return st;
+    MsMovement mvv; MsStepExtras exv;
+    step_options_of(mv, ex, mvv, exv);
+    slide_serial(walls, wall_starts, n_envs, n_agents, *ag, mv ? &mvv : nullptr, exv, ex != nullptr, *sl, progress, cfg->agent_radius, cfg->fps);
+    return MS_OK;
+}
+
 // what ms_rollouts and ms_host_rollouts refuse alike: the limits and the pointers of an MsRollouts
 static int rollouts_status(const MsRollouts* r) {
     if (!r || r->n_candidates < 1 || r->n_candidates > 256 || r->horizon < 1 || r->horizon > 64 || r->n_actions < 1 ||
         (r->others != 0 && r->others != 1) || !(r->keep == r->keep) || !r->actions || !r->table || !r->positions || !r->angles ||
         !r->velocity || !r->angvelocity || !r->progress || !r->stops || !r->first_stop) return MS_EINVAL;
+    if ((r->slide != 0 && r->slide != 1) || (r->slide && !(r->bounce >= 0.f && r->bounce <= 1.f))) return MS_EINVAL;
     return MS_OK;
 }
 
 int ms_rollouts(const MsScenery* sc, const MsAgents* ag, const MsRollouts* r, const MsConfig* cfg, void* stream) {
     if (!scenery_ok(sc) || !agents_ok(ag) || !config_ok(cfg) || rollouts_status(r) != MS_OK) return MS_EINVAL;
-    if (((uintptr_t)r->actions % 8) || ((uintptr_t)r->positions % 8) || ((uintptr_t)r->velocity % 8) || ((uintptr_t)r->trail % 8) ||
+    if (((uintptr_t)r->actions % 8) || ((uintptr_t)r->positions % 8) || ((uintptr_t)r->velocity % 8) || ((uintptr_t)r->trail % 8) || ((uintptr_t)r->slides % 4) ||
         ((uintptr_t)ag->positions % 8) || ((uintptr_t)ag->velocity % 8)) return MS_EINVAL;
     if (sc->wg_cells && (!sc->wg_starts || !sc->wg_geom || !sc->wg_near_rows || !(sc->wg_cell > 0.f) || ((uintptr_t)sc->wg_cells % 16) ||
                          ((uintptr_t)sc->wg_geom % 16) || ((uintptr_t)sc->wg_near_rows % 16))) return MS_EINVAL;
@@ -627,12 +675,17 @@ int ms_rollouts(const MsScenery* sc, const MsAgents* ag, const MsRollouts* r, co
     // Which scheme: a lane a candidate pays a wall's whole exact test however few of its lanes are candidates - measured (DESIGN
     // 3.27; 4096 envs, H = 8) 117.7 us at K = 7 against 51.9 us for a lane a wall, 151.6 against 124.9 at 24, 153.4 against 163.1 at
     // 32, 164.3 against 301.2 at 64: few candidates go candidate by candidate, a wave's worth and more a lane each.
-    const int scheme = g_rollout_scheme >= 0 ? g_rollout_scheme : (r->n_candidates <= ROLL_FEW ? 1 : 0);
-    if (scheme == 1)
+    // (The sliding step is stated for a lane a candidate only: pinning the other scheme with it is refused, not ignored.)
+    if (r->slide && g_rollout_scheme == 1) return MS_EINVAL;
+    const int scheme = r->slide ? 0 : g_rollout_scheme >= 0 ? g_rollout_scheme : (r->n_candidates <= ROLL_FEW ? 1 : 0);
+    if (r->slide)
+        hipLaunchKernelGGL(rollout_kernel<1>, dim3((unsigned)blocks), dim3(WAVE), 0, (hipStream_t)stream, *sc, agents_k(*ag), *r,
+                           cfg->agent_radius, cfg->fps, groups, divisor_of((unsigned)groups), divisor_of((unsigned)sc->n_agents));
+    else if (scheme == 1)
         hipLaunchKernelGGL(rollout_walls_kernel, dim3((unsigned)blocks), dim3(WAVE), 0, (hipStream_t)stream, *sc, agents_k(*ag), *r,
                            cfg->agent_radius, cfg->fps, groups, divisor_of((unsigned)groups), divisor_of((unsigned)sc->n_agents));
     else
-        hipLaunchKernelGGL(rollout_kernel, dim3((unsigned)blocks), dim3(WAVE), 0, (hipStream_t)stream, *sc, agents_k(*ag), *r,
+        hipLaunchKernelGGL(rollout_kernel<0>, dim3((unsigned)blocks), dim3(WAVE), 0, (hipStream_t)stream, *sc, agents_k(*ag), *r,
                            cfg->agent_radius, cfg->fps, groups, divisor_of((unsigned)groups), divisor_of((unsigned)sc->n_agents));
     return launch_status();
 }

@@ -366,10 +366,15 @@ class Render:
 class Physics:
     """Result of :func:`physics` (reference: common.h:224-226, wrappers.cpp:166-172)."""
 
-    def __init__(self, progress):
+    def __init__(self, progress, slid=None, stopped=None):
         self._progress = progress
+        self._slid, self._stopped = slid, stopped
 
     progress = property(lambda self: self._progress)
+    #: of a sliding step (``slide=``), else None: (N, A) float32, the share of the step each agent spent sliding along what blocked it
+    slid = property(lambda self: self._slid)
+    #: of a sliding step, else None: (N, A) uint8, 1 where the step's collisions zeroed the agent's velocity - a dead stop
+    stopped = property(lambda self: self._stopped)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -466,7 +471,29 @@ def _step_options(agents, shape, movement, respawn, lifespans, imu):
     return mv, ex
 
 
-def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=None, imu=None, config=None):
+def _slide_options(slide, agents, out):
+    """``physics``' ``slide`` argument (see there) as ``(MsSlide by reference, slid, stopped)``, or ``(None, None, None)``. The two
+    outputs are the ones of ``out``, an earlier sliding call's Physics, else fresh."""
+    bounce = _bounce(slide)
+    if bounce is None:
+        return None, None, None
+    if out is not None and (out.slid is None or out.stopped is None):
+        raise RuntimeError('out must be the Physics of an earlier sliding step')
+    slid = torch.empty_like(agents.angles) if out is None else out.slid
+    stopped = torch.empty(agents.angles.shape, dtype=torch.uint8, device=agents.angles.device) if out is None else out.stopped
+    return C.byref(_lib.MsSlide(bounce, slid.data_ptr(), stopped.data_ptr())), slid, stopped
+
+
+def _step_launch(scenery, agents, mv, ex, sl, progress, cfg, dev):
+    """The physics launch of :func:`physics` and of a two-launch :func:`step_render`: the sliding step where ``sl`` is given."""
+    args = (C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)), mv, ex)
+    if sl is None:
+        _lib.check(_lib.lib().ms_step_physics(*args, C.c_void_p(progress.data_ptr()), C.byref(cfg), _stream(dev)))
+    else:
+        _lib.check(_lib.lib().ms_slide_physics(*args, sl, C.c_void_p(progress.data_ptr()), C.byref(cfg), _stream(dev)))
+
+
+def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=None, imu=None, config=None, slide=None):
     """Advances the agents by one step, stopping them at walls and at each other; updates ``agents`` in place and
     returns :class:`Physics` with the (N, A) ``progress`` (reference: wrappers.cpp:69, kernels.cu:179-230).
 
@@ -480,9 +507,14 @@ def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=No
       movement), or after it with ``after=True``;
     * ``lifespans=dict(lifespans, max_lifespans, fresh)``: (N, A) int32 ages tick first; agents at their maximum are
       added to ``respawn['mask']`` (required with it), start over and take ``fresh`` as their new maximum;
-    * ``imu=(out, ang_scale, speed_scale)``: the (N, A, 3) IMU observation of the state the step leaves behind.
+    * ``imu=(out, ang_scale, speed_scale)``: the (N, A, 3) IMU observation of the state the step leaves behind;
+    * ``slide=True`` or ``dict(bounce=.05)``: sliding contacts (include/megastep_hip.h, MsSlide). The reference's
+      step stops an agent dead, velocity and spin, at whatever it touches; with ``slide`` a blocked agent spends the rest of the
+      step along what blocked it, its velocity deflected off the contact normal with ``bounce`` of it turned outwards, in the
+      same launch. ``progress`` stays the plain step's, bit for bit, and the result also has ``slid`` and ``stopped``
+      (:class:`Physics`). At most 64 agents an env.
 
-    ``out``: the :class:`Physics` of an earlier call, to write ``progress`` into instead of allocating.
+    ``out``: the :class:`Physics` of an earlier call, to write ``progress`` (and ``slid``, ``stopped``) into instead of allocating.
     ``config``: the constants of this call (:func:`config`); default: the ones ``agents`` carry (a Core's do), else initialize()'s."""
     dev = scenery._device()
     _agents_on(agents, dev)
@@ -491,13 +523,13 @@ def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=No
         raise RuntimeError('agents do not match the scenery: expected (n_envs, n_agents) = '
                            f'{shape}, got {tuple(agents.angles.shape)}')
     mv, ex = _step_options(agents, shape, movement, respawn, lifespans, imu)
+    sl, slid, stopped = _slide_options(slide, agents, out)
     progress = _progress(agents, out)
     _ab_switches()
     scenery._check_grid(dev)
     with _on(dev):
-        _lib.check(_lib.lib().ms_step_physics(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)),
-                                              mv, ex, C.c_void_p(progress.data_ptr()), C.byref(_cfg(agents, config)), _stream(dev)))
-    return _stepped(agents, progress, out)
+        _step_launch(scenery, agents, mv, ex, sl, progress, _cfg(agents, config), dev)
+    return _stepped(agents, progress, out, slid, stopped)
 
 
 def _progress(agents, out):
@@ -505,12 +537,12 @@ def _progress(agents, out):
     return torch.empty_like(agents.angles) if out is None else out.progress
 
 
-def _stepped(agents, progress, out):
+def _stepped(agents, progress, out, slid=None, stopped=None):
     """What a step leaves behind: the agents' heading cache filled (where they use it) and their epoch moved on; ``progress``
-    as a :class:`Physics` - ``out`` if the step wrote into one."""
+    (and a sliding step's ``slid`` and ``stopped``) as a :class:`Physics` - ``out`` if the step wrote into one."""
     agents._cached = agents._use_cache
     agents._epoch += 1
-    return Physics(progress) if out is None else out
+    return Physics(progress, slid, stopped) if out is None else out
 
 
 FIELDS = ('indices', 'locations', 'dots', 'distances', 'screen')
@@ -520,7 +552,7 @@ CHECK_GRID = os.environ.get('MEGASTEP_CHECK_GRID', '0') not in ('', '0')
 
 
 def step_render(scenery, agents, fields=None, pooled=None, out=None, seen=None, config=None, movement=None, respawn=None,
-                lifespans=None, imu=None):
+                lifespans=None, imu=None, slide=None):
     """One step of the hot path - :func:`physics` then :func:`render`, what every ``env.step()`` of the reference runs
     (wrappers.cpp:69 + :82) - as one call, and where the shapes allow it as ONE LAUNCH (include/megastep_hip.h,
     ``ms_step_render``): with one agent per env and at most 64 rays (BASELINE config 2, the Explorer shape) an agent is a single
@@ -529,15 +561,25 @@ def step_render(scenery, agents, fields=None, pooled=None, out=None, seen=None, 
 
     Arguments as :func:`render`'s, and :func:`physics`' ``movement`` / ``respawn`` / ``lifespans`` / ``imu`` (a whole env.step() of a
     single-agent env of up to 64 rays - the reference's tutorial env - is then one launch); ``out``: the ``(Physics, Render)`` of an
-    earlier call, to write into. Returns ``(Physics, Render)``."""
+    earlier call, to write into. Returns ``(Physics, Render)``.
+
+    ``slide``: :func:`physics`' sliding contacts. A sliding step is always the two launches - the sliding physics launch, then the
+    render - whatever the shape."""
     physics_out, render_out = out if out is not None else (None, None)
     dev, cfg, result = _render_call(scenery, agents, fields, pooled, render_out, seen, config)
     mv, ex = _step_options(agents, tuple(agents.angles.shape), movement, respawn, lifespans, imu)
+    sl, slid, stopped = _slide_options(slide, agents, physics_out)
     progress = _progress(agents, physics_out)
     with _on(dev):
-        _lib.check(_lib.lib().ms_move_step_render(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)), mv, ex,
-                                                  C.c_void_p(progress.data_ptr()), C.byref(result._struct), C.byref(cfg), _stream(dev)))
-    return _stepped(agents, progress, physics_out), result
+        if sl is None:
+            _lib.check(_lib.lib().ms_move_step_render(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)), mv, ex,
+                                                      C.c_void_p(progress.data_ptr()), C.byref(result._struct), C.byref(cfg), _stream(dev)))
+        else:
+            _step_launch(scenery, agents, mv, ex, sl, progress, cfg, dev)
+            agents._cached = agents._use_cache                  # (the sliding launch has filled the heading cache the render reads)
+            _lib.check(_lib.lib().ms_render(C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=False)),
+                                            C.byref(result._struct), C.byref(cfg), _stream(dev)))
+    return _stepped(agents, progress, physics_out, slid, stopped), result
 
 
 def render(scenery, agents, fields=None, pooled=None, telemetry=False, out=None, seen=None, config=None):
@@ -692,7 +734,7 @@ def _render_layout(n, a, r, fields, pooled, lit):
 # ---------------------------------------------------------------------------------------------------------------------
 from .envlogic import deathmatch_shoot, explorer_books
 from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
-from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans
+from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans, _bounce
 from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, plan_views, agent_views
 from .nav import nav_geometry, NavGrid, nav_grid, FIELD_CAPACITY, DistanceFields, Paths, PulledPaths, distance_fields, geodesic, SeenMaps, seen_maps, AGE_MAX_TICK, Sweep, AgeMaps, age_maps, SeededFields, seeded_fields, \
     COST_CAPACITY, COST_MAX, CostFields, cost_fields, inflation_costs, mark_costs, \

@@ -20,7 +20,7 @@ def reachable(grid, points):
 class FloorCoverage:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, max_range=10., complete=.9, max_lifespan=512,
-                 n_spawns=100, shared=False, local_map=None, **kwargs):
+                 n_spawns=100, shared=False, local_map=None, slide=False, **kwargs):
         """``cell``: the nav grid's cell size; ``max_range``: how far a ray is followed, metres; ``complete``: the share of the
         floor that ends an episode; ``max_lifespan``: episodes end after a random number of steps up to this
         (:class:`~megastep_amd.modules.RandomLifespans`); ``shared``: see :class:`~megastep_amd.modules.Coverage`; ``local_map``:
@@ -28,7 +28,8 @@ class FloorCoverage:
         window of what the agent has seen so far, taken after the frame's marks; without it the env makes no such launch.
 
         The floor that counts is what can be walked to from the env's first spawn point: the free margin the grid keeps round
-        the building, and rooms without a door, are never in the denominator."""
+        the building, and rooms without a door, are never in the denominator. ``slide``: ``True`` or ``dict(bounce=.05)`` - the
+        agents slide along what they hit instead of stopping dead (:func:`~megastep_amd.cuda.physics`)."""
         if geometries is None:
             geometries = cubicasa.sample(n_envs, workers=_plan_workers(), context='subprocess')
         self.core = core.Core(scene.scenery(geometries, n_agents, device=device), *args, res=4*64, fov=130, **kwargs)
@@ -36,7 +37,7 @@ class FloorCoverage:
         self.device = c.device
         self.complete = float(complete)
 
-        self._mover = modules.MomentumMovement(c)
+        self._mover = modules.MomentumMovement(c, slide=slide or None)
         self._respawner = modules.RandomSpawns(geometries, c, n_spawns=n_spawns)
         self._lifespans = modules.RandomLifespans(c, max_lifespan)
         self._rgb = modules.RGB(c, subsample=4)

@@ -15,7 +15,7 @@ from .floorcoverage import reachable
 class Patrol:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, max_range=10., threshold=64, shared=True,
-                 local_map=False, max_lifespan=512, n_spawns=100, **kwargs):
+                 local_map=False, max_lifespan=512, n_spawns=100, slide=False, **kwargs):
         """``cell``: the nav grid's cell size; ``max_range``: how far a ray is followed, metres; ``threshold``: the steps after
         which floor not looked at is stale; ``shared``: an env's agents keep ONE map (:class:`~megastep_amd.modules.Idleness`) -
         a patrol is a team's; ``max_lifespan``: episodes end after a random number of steps up to this
@@ -25,14 +25,15 @@ class Patrol:
         floor in the agent's map over ``threshold``, clamped to 1.
 
         The floor that counts is what can be walked to from the env's first spawn point, as in
-        :class:`~megastep_amd.demo.envs.floorcoverage.FloorCoverage`."""
+        :class:`~megastep_amd.demo.envs.floorcoverage.FloorCoverage`. ``slide``: ``True`` or ``dict(bounce=.05)`` - the agents
+        slide along what they hit instead of stopping dead (:func:`~megastep_amd.cuda.physics`)."""
         if geometries is None:
             geometries = cubicasa.sample(n_envs, workers=_plan_workers(), context='subprocess')
         self.core = core.Core(scene.scenery(geometries, n_agents, device=device), *args, res=4*64, fov=130, **kwargs)
         c = self.core
         self.device = c.device
 
-        self._mover = modules.MomentumMovement(c)
+        self._mover = modules.MomentumMovement(c, slide=slide or None)
         self._respawner = modules.RandomSpawns(geometries, c, n_spawns=n_spawns)
         self._lifespans = modules.RandomLifespans(c, max_lifespan)
         self._rgb = modules.RGB(c, subsample=4)

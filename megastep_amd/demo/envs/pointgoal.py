@@ -26,7 +26,7 @@ def books(before, now, reset, stranded, arrive, bonus):
 class PointGoal:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, arrive=.5, bonus=1., max_lifespan=512,
-                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, margin=None, spl=False, **kwargs):
+                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, margin=None, spl=False, slide=False, **kwargs):
         """``cell``: the nav grid's cell size; ``arrive``: how near the goal counts as there, metres (walking distance);
         ``bonus``: the reward for arriving; ``max_lifespan``: episodes end after a random number of steps up to this
         (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`.
@@ -40,7 +40,8 @@ class PointGoal:
         ``inflation_costs(clearance_fields(grid, scenery, margin), margin)`` - that makes a cell dearer the nearer a wall comes
         within ``margin``: it keeps to the middle where there is room. Reward and observations do not change. ``spl=True``: the
         world also carries ``spl`` (n_env, n_agent) - :class:`~megastep_amd.modules.SPL` over the goals: the score of every
-        episode that ended at this step, NaN elsewhere - and ``env.spl`` holds the module."""
+        episode that ended at this step, NaN elsewhere - and ``env.spl`` holds the module. ``slide``: ``True`` or
+        ``dict(bounce=.05)`` - the agents slide along what they hit instead of stopping dead (:func:`~megastep_amd.cuda.physics`)."""
         if one_region and not sampled_spawns:
             raise RuntimeError('one_region gates the sampled spawns: it needs sampled_spawns=True')
         if geometries is None:
@@ -50,7 +51,7 @@ class PointGoal:
         self.device = c.device
         self.arrive, self.bonus = float(arrive), float(bonus)
 
-        self._mover = modules.MomentumMovement(c)
+        self._mover = modules.MomentumMovement(c, slide=slide or None)
         self._respawner = None if sampled_spawns else modules.RandomSpawns(geometries, c, n_spawns=n_spawns)
         self._lifespans = modules.RandomLifespans(c, max_lifespan)
         self._rgb = modules.RGB(c, subsample=4)

@@ -38,20 +38,23 @@ def _table(actionset):
     return torch.cat([actionset.velocity, actionset.angvelocity[:, None]], 1).contiguous()
 
 
-def _move(core, actionset, actions, keep, respawn=None, imu=None, table=None):
+def _move(core, actionset, actions, keep, respawn=None, imu=None, table=None, slide=None):
     """The velocity update of both movement modules, then physics. On the GPU it is part of the physics launch
     (cuda.physics' ``movement``) - as are, when the env hands them over, the respawn of the agents it wants respawned
     (``respawn``: :meth:`RandomSpawns.draw`) and the IMU observation of the new state (``imu``: the :class:`IMU`
     module, which then returns it from its next call). The tensor ops below are the same arithmetic, and what the
-    reference runs."""
+    reference runs. ``slide``: cuda.physics' sliding contacts - a second phase of the launch, which the tensor ops do not have."""
     agents = core.agents
     if agents.angles.is_cuda:
         table = _table(actionset) if table is None else table
         reading = None if imu is None else (torch.empty(agents.angles.shape + (3,), device=core.device), imu.ang_scale, imu.speed_scale)
-        result = cuda.physics(core.scenery, agents, movement=(actions.long().contiguous(), table, keep), respawn=respawn, imu=reading)
+        result = cuda.physics(core.scenery, agents, movement=(actions.long().contiguous(), table, keep), respawn=respawn, imu=reading,
+                              slide=slide)
         if imu is not None:
             imu._pending = (reading[0], agents._epoch)          # valid until somebody else touches the agents
         return result
+    if slide:
+        raise RuntimeError('sliding contacts are part of the physics launch: they need the agents on a GPU')
     if respawn is not None and not respawn['after']:
         _respawn(agents, respawn)
     delta = actionset[actions.long()]
@@ -81,10 +84,11 @@ def _respawn(agents, request):
 
 class SimpleMovement:
 
-    def __init__(self, core, speed=10, ang_speed=180, n_agents=None):
+    def __init__(self, core, speed=10, ang_speed=180, n_agents=None, slide=None):
         """Movement without momentum: seven actions - nothing, forward/backward, strafe left/right, turn left/right
-        (reference: modules.py:24-66)."""
+        (reference: modules.py:24-66). ``slide``: cuda.physics' sliding contacts (True, or dict(bounce=.05)) for every step."""
         self.core = core
+        self.slide = slide
         self._actionset = _actionset(core, speed, ang_speed)
         self._table = _table(self._actionset)
         self.keep = 0.                           # (of the old velocity: none - see cuda.physics' ``movement``)
@@ -93,20 +97,24 @@ class SimpleMovement:
     def __call__(self, decision, respawn=None, imu=None):
         """Sets the agents' velocities from ``decision.actions`` ((n_env, n_agent) ints in 0..6), then steps physics.
         ``respawn`` / ``imu``: see :func:`_move`."""
-        return _move(self.core, self._actionset, decision.actions, 0., respawn, imu, self._table)
+        return _move(self.core, self._actionset, decision.actions, 0., respawn, imu, self._table, self.slide)
 
     def rollouts(self, actions, **kw):
         """:func:`cuda.rollouts` of ``actions`` ((n_env, n_agent, K, H) or (K, H) int64) under this module's table and ``keep``:
-        where each plan would take every agent as it stands, without moving anybody. ``kw``: ``others``, ``trail``, ``mask``, ``out``."""
+        where each plan would take every agent as it stands, without moving anybody - sliding, where the module's steps slide.
+        ``kw``: ``others``, ``trail``, ``mask``, ``out``."""
+        if self.slide:
+            kw.setdefault('slide', self.slide)
         return cuda.rollouts(self.core.scenery, self.core.agents, actions, self._table, keep=self.keep, **kw)
 
 
 class MomentumMovement:
 
-    def __init__(self, core, accel=5, ang_accel=180, decay=.125, n_agents=None):
+    def __init__(self, core, accel=5, ang_accel=180, decay=.125, n_agents=None, slide=None):
         """Movement with momentum: the seven actions accelerate rather than move, and velocity decays by ``decay``
-        each step (reference: modules.py:68-118)."""
+        each step (reference: modules.py:68-118). ``slide``: as SimpleMovement's."""
         self.core = core
+        self.slide = slide
         self._actionset = _actionset(core, accel, ang_accel)
         self._table = _table(self._actionset)
         self.decay = decay
@@ -116,7 +124,7 @@ class MomentumMovement:
     keep = property(lambda self: 1 - self.decay)
 
     def __call__(self, decision, respawn=None, imu=None):
-        return _move(self.core, self._actionset, decision.actions, self.keep, respawn, imu, self._table)
+        return _move(self.core, self._actionset, decision.actions, self.keep, respawn, imu, self._table, self.slide)
 
     rollouts = SimpleMovement.rollouts
 
@@ -153,7 +161,8 @@ def move_render(core, mover, decision, observers=None, fields=None, centre=False
     pooled = _pooling(tuple(observers), bool(centre)) if observers else None
     reading = None if imu is None else (torch.empty(agents.angles.shape + (3,), device=core.device), imu.ang_scale, imu.speed_scale)
     _, raw = cuda.step_render(core.scenery, agents, fields=fields, pooled=pooled, seen=seen,
-                              movement=(decision.actions.long().contiguous(), mover._table, mover.keep), respawn=respawn, imu=reading)
+                              movement=(decision.actions.long().contiguous(), mover._table, mover.keep), respawn=respawn, imu=reading,
+                              slide=mover.slide)
     if imu is not None:
         imu._pending = (reading[0], agents._epoch)
     return _frame(raw, pooled)

@@ -16,10 +16,11 @@ class Rollouts:
     ``velocity`` (N, A, K, 2) and ``angvelocity`` (N, A, K) after the plan's last step; ``progress`` (N, A, K) float32, the least
     share of a step the candidate could take; ``stops`` (N, A, K) int32, the steps at which it was stopped; ``first_stop``
     (N, A, K) int32, the first of them, ``H`` when there was none; ``trail`` (N, A, K, H, 2), the position after every step, or
-    ``None`` when it was not asked for."""
+    ``None`` when it was not asked for. Of a call with ``slide``: ``stops`` and ``first_stop`` count the steps that ended in a dead
+    stop - the velocity zeroed - and ``slides`` (N, A, K) int32 the steps that slid the whole of their remainder; else ``None``."""
 
-    def __init__(self, positions, angles, velocity, angvelocity, progress, stops, first_stop, trail):
-        self._t = (positions, angles, velocity, angvelocity, progress, stops, first_stop, trail)
+    def __init__(self, positions, angles, velocity, angvelocity, progress, stops, first_stop, trail, slides=None):
+        self._t = (positions, angles, velocity, angvelocity, progress, stops, first_stop, trail, slides)
 
     positions = property(lambda self: self._t[0])
     angles = property(lambda self: self._t[1])
@@ -29,6 +30,7 @@ class Rollouts:
     stops = property(lambda self: self._t[5])
     first_stop = property(lambda self: self._t[6])
     trail = property(lambda self: self._t[7])
+    slides = property(lambda self: self._t[8])
 
 
 def plans(n_actions, horizon, switch=None, device=None):
@@ -48,15 +50,30 @@ def plans(n_actions, horizon, switch=None, device=None):
     return torch.where(late, then, first).reshape(n_actions*n_actions, horizon).contiguous()
 
 
-def _fresh(n, a, k, h, trail, dev):
+def _bounce(slide):
+    """``slide`` (None / False, True, or dict(bounce=...)) as the bounce of a sliding call, or None for a plain one."""
+    if slide is None or slide is False:
+        return None
+    if slide is not True and not isinstance(slide, dict):
+        raise RuntimeError('slide must be True or a dict(bounce=...)')
+    options = {} if slide is True else dict(slide)
+    bounce = float(options.pop('bounce', .05))
+    if options:
+        raise RuntimeError(f'slide takes bounce only, got {sorted(options)}')
+    if not 0 <= bounce <= 1:
+        raise RuntimeError(f'slide needs 0 <= bounce <= 1, got {bounce}')
+    return bounce
+
+
+def _fresh(n, a, k, h, trail, dev, slide=False):
     """The buffers of a call without ``out``, holding what an agent that is not rolled reads as: NaN poses, progress 1, no stop."""
     nan = lambda *shape: torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
     return Rollouts(nan(n, a, k, 2), nan(n, a, k), nan(n, a, k, 2), nan(n, a, k), torch.ones((n, a, k), dtype=torch.float32, device=dev),
                     torch.zeros((n, a, k), dtype=torch.int32, device=dev), torch.full((n, a, k), h, dtype=torch.int32, device=dev),
-                    nan(n, a, k, h, 2) if trail else None)
+                    nan(n, a, k, h, 2) if trail else None, torch.zeros((n, a, k), dtype=torch.int32, device=dev) if slide else None)
 
 
-def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False, mask=None, out=None, config=None):
+def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False, mask=None, out=None, config=None, slide=None):
     """Rolls ``K`` candidate plans of ``H`` actions for every agent through the step :func:`physics` takes, in one launch, and
     returns :class:`Rollouts`. Neither the scenery nor the agents are modified.
 
@@ -69,6 +86,8 @@ def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False,
     ``trail=True`` also gives the position after every step. ``mask`` (N, A) bool: only the marked agents are rolled; the others
     keep what ``out`` held, and without ``out`` read as NaN poses, progress 1, no stops. ``out``: the :class:`Rollouts` of an
     earlier call with the same shapes, to write into. ``config``: see :func:`physics` (``agent_radius`` and ``fps`` are read).
+    ``slide``: ``True`` or ``dict(bounce=.05)`` - every step is :func:`physics`' sliding step, the others at rest in both its
+    phases; the result then has ``slides``, and its ``stops`` count dead stops.
 
     ``1 <= K <= 256`` and ``1 <= H <= 64``. Other agents that move, respawns, lifespans and the IMU are not part of a rollout.
     No host synchronisation, nothing allocated with ``out``: the call can be captured in a HIP graph."""
@@ -103,10 +122,13 @@ def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False,
     dev = _query_device(scenery, agents, *tensors)
     cfg = _cfg(agents, config)
     trail = bool(trail)
-    result = _result_for(out, (n, a, k, h, trail, dev), 'a rollouts', lambda: _fresh(n, a, k, h, trail, dev))
+    bounce = _bounce(slide)
+    sliding = bounce is not None
+    key = (n, a, k, h, trail, dev) + ((True,) if sliding else ())       # (a plain call's key is what it was)
+    result = _result_for(out, key, 'a rollouts', lambda: _fresh(n, a, k, h, trail, dev, sliding))
     ptrs = [t.data_ptr() if t is not None else None for t in result._t]
     query = _lib.MsRollouts(k, h, actions.data_ptr(), int(shared), table.data_ptr(), table.shape[0], keep, int(others == 'rest'),
-                            mask.data_ptr() if mask is not None else None, *ptrs)
+                            mask.data_ptr() if mask is not None else None, *ptrs[:8], int(sliding), bounce if sliding else 0., ptrs[8])
     scenery._check_grid(dev)
     with _on(dev):
         _lib.check(_lib.lib().ms_rollouts(C.byref(scenery._as_struct()), C.byref(agents._plain), C.byref(query), C.byref(cfg), _stream(dev)))
