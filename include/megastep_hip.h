@@ -405,6 +405,45 @@ int ms_raycast(const MsScenery* scenery, const MsAgents* agents /* NULL: static 
  * and the agents, these rays give ms_render's indices, locations, dots and distances bit for bit.  Reads angles only. */
 int ms_camera_rays(const MsAgents* agents, int n_envs, int n_agents, const MsConfig* config, float* dirs, void* hip_stream);
 
+/* Shading of rays the caller gives (the reference shades only the rays of its own render, shader_kernel, kernels.cu:407-450):
+ * for ray r of env n, with the index, location and dot ms_raycast wrote for it, screen[n, r] is what ms_render's `screen` holds
+ * for a ray with those values - (0, 0, 0) on a miss (index < 0) and for an index that is no line of the env (nothing is read for
+ * it) or a location outside [0, 1] (which ms_raycast never writes for a hit); else, with f = the 2-tap texel filter at `location` along the line, (1 - dot^2) intensity (f.lw tl[k] + f.rw tr[k]), where
+ * intensity is the baked light under the filter on a static line, and on an agent's row (index < n_agents n_model) the
+ * reference's light_intensity at the hit point a (1 - location) + b location of the row (a, b) drawn from the agent's CURRENT
+ * pose - in registers: lines_vals is neither read for it nor written.  Without agents (NULL) rays on an agent's row are black.
+ * Every operation is the render's own binary32 operation in the render's order: on the rays of ms_camera_rays, cast from the
+ * agents' positions, the result is ms_render's `screen` bit for bit.  A light grid in the scenery (lg_vals) is used where it is
+ * there; without one the lights are tested against every static line.  Same bits either way. */
+typedef struct MsShade {
+    int          n_rays;      /* R: rays per env                                                              */
+    const int*   indices;     /* (N, R) as ms_raycast writes them                                             */
+    const float* locations;   /* (N, R)                                                                       */
+    const float* dots;        /* (N, R)                                                                       */
+    float*       screen;      /* (N, R, 3) out                                                                */
+} MsShade;
+/* config: nothing of it is needed; it may be NULL. */
+int ms_shade(const MsScenery* scenery, const MsAgents* agents /* NULL: agent rows are black */, const MsShade* query,
+             const MsConfig* config, void* hip_stream);
+
+/* Rays of cameras that stand anywhere: camera c of env n at poses[n, c] = (x, y, heading in degrees) casts `res` rays, ray 0
+ * leftmost as in the render; origins and dirs are (N, C res, 2), camera after camera, ready for ms_raycast.
+ *   MS_CAMERA_PLANE  the render's projection, 0 < fov < 180: sincospi(heading/180) and the column's ray on the screen plane, by
+ *                    the device code behind ms_camera_rays (same bits for the same heading, res and fov)
+ *   MS_CAMERA_RING   rays evenly spaced in angle, 0 < fov <= 360: ray r points along heading + fov (res - 2r - 1)/(2 res)
+ *                    degrees; unit vectors.  360 is a panorama, which no plane can show. */
+#define MS_CAMERA_PLANE 0
+#define MS_CAMERA_RING  1
+typedef struct MsCameraPoses {
+    int          n_envs, n_cameras, res;   /* N, C, rays per camera                                           */
+    const float* poses;       /* (N, C, 3) x, y, heading in degrees                                           */
+    float        fov;         /* degrees                                                                      */
+    int          projection;  /* MS_CAMERA_PLANE or MS_CAMERA_RING                                            */
+    float*       origins;     /* (N, C res, 2) out, 8-byte aligned                                            */
+    float*       dirs;        /* (N, C res, 2) out, 8-byte aligned                                            */
+} MsCameraPoses;
+int ms_camera_pose_rays(const MsCameraPoses* cameras, void* hip_stream);
+
 /* Top-down pictures of the envs (the reference draws them with matplotlib, plotting.py; no kernel): image k shows env
  * envs[k] through n_views views.  A view is six floats g, an affine map from pixel coordinates to world metres; every
  * step below is one binary32 operation, in this order, without contraction.

@@ -259,6 +259,13 @@ int ms_debug_rollout_scheme(int scheme);
 int ms_host_slide(const float* walls, const long long* wall_starts, int n_envs, int n_agents, const MsAgents* agents,
                   const MsMovement* movement, const MsStepExtras* extras, const MsSlide* slide, float* progress,
                   const MsConfig* config);
+/* The serial host statement of ms_shade (kernels/shade.h), on HOST arrays: ray after ray through the per-ray
+ * functions shade_kernel calls - the texel filter, the drawn row, the shadow test, the sum - the lights taken the plain way,
+ * light after light against row after row.  Of `scenery` it reads n_envs, n_agents, n_model, lights_*, lines_vals / widths /
+ * starts, textures_vals / widths / starts, model and baked_vals (host pointers, lines_vals and model 16-byte aligned); of
+ * `agents` (NULL: agent rows are black) angles and positions.  Returns what ms_shade would for such arguments: MS_OK or
+ * MS_EINVAL. */
+int ms_host_shade(const MsScenery* scenery, const MsAgents* agents, const MsShade* query);
 /* Host instantiation of the scan's test, for CPU tests: does wall o = (ax, ay, bx, by) hide wall w from every point of
  * the cell [x0, x1] x [y0, y1] (as ms_wallgrid_scan grows it) for near planes below `near_plane`? */
 int ms_host_wall_hidden(float x0, float y0, float x1, float y1, const float* o, const float* w, float near_plane);

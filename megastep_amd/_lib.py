@@ -90,6 +90,15 @@ class MsRaycast(C.Structure):
                 ('agents', C.c_void_p), ('grid_rays', C.c_void_p)]
 
 
+class MsShade(C.Structure):
+    _fields_ = [('n_rays', C.c_int), ('indices', C.c_void_p), ('locations', C.c_void_p), ('dots', C.c_void_p), ('screen', C.c_void_p)]
+
+
+class MsCameraPoses(C.Structure):
+    _fields_ = [('n_envs', C.c_int), ('n_cameras', C.c_int), ('res', C.c_int), ('poses', C.c_void_p), ('fov', C.c_float),
+                ('projection', C.c_int), ('origins', C.c_void_p), ('dirs', C.c_void_p)]
+
+
 class MsOverhead(C.Structure):
     _fields_ = [('n_images', C.c_int), ('n_views', C.c_int), ('height', C.c_int), ('width', C.c_int), ('envs', C.c_void_p),
                 ('views', C.c_void_p), ('half_width', C.c_float), ('lit', C.c_int), ('background', C.c_float*3),
@@ -271,6 +280,8 @@ PROTOTYPES = {
     'ms_explorer_books': (_int, [_int, _p(MsExplorer), _ptr]),
     'ms_raycast': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRaycast), _p(MsConfig), _ptr]),
     'ms_camera_rays': (_int, [_p(MsAgents), _int, _int, _p(MsConfig), _ptr, _ptr]),
+    'ms_shade': (_int, [_p(MsScenery), _p(MsAgents), _p(MsShade), _p(MsConfig), _ptr]),
+    'ms_camera_pose_rays': (_int, [_p(MsCameraPoses), _ptr]),
     'ms_overhead': (_int, [_p(MsScenery), _p(MsAgents), _p(MsOverhead), _ptr]),
     'ms_rollouts': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRollouts), _p(MsConfig), _ptr]),
     'ms_nav_free': (_int, [_p(MsScenery), _p(MsNavGrid), _ptr]),
@@ -360,6 +371,7 @@ PROTOTYPES = {
     'ms_host_rollouts': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsRollouts), _p(MsConfig)]),
     'ms_debug_rollout_scheme': (_int, [_int]),
     'ms_host_slide': (_int, [_ptr, _ptr, _int, _int, _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsSlide), _ptr, _p(MsConfig)]),
+    'ms_host_shade': (_int, [_p(MsScenery), _p(MsAgents), _p(MsShade)]),
     'ms_host_wall_hidden': (_int, [_flt]*4 + [_f32p, _f32p, _flt]),
     'ms_host_wall_sectors': (None, [_flt]*4 + [_f32p, _i32p, _i32p, _f32p, _i32p]),
     'ms_host_wallgrid_cell': (None, [_ptr, _int, _flt, _flt, _int, _int, _flt, _int, _flt, _flt, _flt, _ptr, _ptr]),

@@ -185,6 +185,7 @@ struct Probe {
 #include "kernels/bake.h"
 #include "kernels/wallgrid.h"
 #include "kernels/raycast.h"
+#include "kernels/shade.h"
 #include "kernels/overhead.h"
 #include "kernels/navfield.h"
 #include "kernels/navclear.h"
@@ -895,6 +896,49 @@ int ms_camera_rays(const MsAgents* ag, int n_envs, int n_agents, const MsConfig*
     const float half_screen = half_screen_of(cfg->fov);
     hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, ag->angles,
                        n_envs*n_agents, cfg->res, half_screen, camera_inv_res(cfg->res, half_screen), reinterpret_cast<float2*>(dirs));
+    return launch_status();
+}
+
+// Shading of given rays (shade.h): arguments checked in full before anything is launched.  What both ms_shade and ms_host_shade
+// refuse: a scenery without textures or baked light, lights announced but not given, a query that lacks a plane, R < 1, agents
+// without poses.
+static int shade_status(const MsScenery* sc, const MsAgents* ag, const MsShade* q) {
+    if (!scenery_ok(sc) || !q || q->n_rays < 1 || !q->indices || !q->locations || !q->dots || !q->screen || !sc->textures_vals ||
+        !sc->textures_widths || !sc->textures_starts || !sc->baked_vals || !sc->lights_widths || !sc->lights_starts ||
+        (sc->n_lights_total > 0 && !sc->lights_vals) || ((uintptr_t)q->indices % 4) || ((uintptr_t)q->locations % 4) ||
+        ((uintptr_t)q->dots % 4) || ((uintptr_t)q->screen % 4)) return MS_EINVAL;
+    if (ag && (!ag->angles || !ag->positions || ((uintptr_t)ag->positions % 8))) return MS_EINVAL;
+    if ((long long)sc->n_envs*q->n_rays > 0x7fffff00LL/3) return MS_EUNSUPPORTED;
+    return MS_OK;
+}
+int ms_shade(const MsScenery* sc, const MsAgents* ag, const MsShade* q, const MsConfig* cfg, void* stream) {
+    (void)cfg;
+    if (const int status = shade_status(sc, ag, q); status != MS_OK) return status;
+    // a light grid is used whole or refused: verdict rows are read 16 bytes at a time, list headers 8, the candidates' rows 16
+    const bool gridded = sc->lg_vals != nullptr;
+    if (gridded && (!light_grid_in(sc) || ((uintptr_t)sc->lg_vals % 16) || ((uintptr_t)sc->lg_geom % 16) || ((uintptr_t)sc->lg_list % 8) ||
+                    ((uintptr_t)sc->lg_pool_rows % 16) || (sc->lg_list && !sc->lg_pool))) return MS_EINVAL;
+    const long long total = (long long)sc->n_envs*q->n_rays;
+    hipLaunchKernelGGL(shade_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, *sc, agents_or_none(ag), *q,
+                       ag ? 1 : 0, gridded ? 1 : 0, divisor_of((unsigned)sc->n_model), (int)total);
+    return launch_status();
+}
+int ms_host_shade(const MsScenery* sc, const MsAgents* ag, const MsShade* q) {
+    if (const int status = shade_status(sc, ag, q); status != MS_OK) return status;
+    shade_serial(*sc, ag, *q);
+    return MS_OK;
+}
+
+int ms_camera_pose_rays(const MsCameraPoses* cams, void* stream) {
+    if (!cams || cams->n_envs < 1 || cams->n_cameras < 1 || cams->res < 1 || !cams->poses || !cams->origins || !cams->dirs ||
+        ((uintptr_t)cams->poses % 4) || ((uintptr_t)cams->origins % 8) || ((uintptr_t)cams->dirs % 8) || !(cams->fov > 0.f)) return MS_EINVAL;
+    if (cams->projection == MS_CAMERA_PLANE ? !(cams->fov < 180.f) : (cams->projection != MS_CAMERA_RING || !(cams->fov <= 360.f))) return MS_EINVAL;
+    const long long total = (long long)cams->n_envs*cams->n_cameras*cams->res;
+    if (total > 0x7fffff00LL) return MS_EUNSUPPORTED;
+    const bool plane = cams->projection == MS_CAMERA_PLANE;
+    const float half_screen = plane ? half_screen_of(cams->fov) : 0.f;
+    hipLaunchKernelGGL(camera_pose_rays_kernel, dim3((unsigned)((total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, *cams, half_screen,
+                       plane ? camera_inv_res(cams->res, half_screen) : 0.f, total);
     return launch_status();
 }
 

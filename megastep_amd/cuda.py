@@ -734,6 +734,7 @@ def _render_layout(n, a, r, fields, pooled, lit):
 # ---------------------------------------------------------------------------------------------------------------------
 from .envlogic import deathmatch_shoot, explorer_books
 from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
+from .cameras import PROJECTIONS, LOOK_FIELDS, Cameras, Look, shade, cameras, mounted, look
 from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans, _bounce
 from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, plan_views, agent_views
 from .nav import nav_geometry, NavGrid, nav_grid, FIELD_CAPACITY, DistanceFields, Paths, PulledPaths, distance_fields, geodesic, SeenMaps, seen_maps, AGE_MAX_TICK, Sweep, AgeMaps, age_maps, SeededFields, seeded_fields, \

@@ -26,7 +26,8 @@ def books(before, now, reset, stranded, arrive, bonus):
 class PointGoal:
 
     def __init__(self, n_envs, n_agents=1, *args, device='cuda', geometries=None, cell=.125, arrive=.5, bonus=1., max_lifespan=512,
-                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, margin=None, spl=False, slide=False, **kwargs):
+                 candidates=8, n_spawns=100, goal_range=None, sampled_spawns=False, one_region=False, margin=None, spl=False, slide=False, panorama=False,
+                 **kwargs):
         """``cell``: the nav grid's cell size; ``arrive``: how near the goal counts as there, metres (walking distance);
         ``bonus``: the reward for arriving; ``max_lifespan``: episodes end after a random number of steps up to this
         (:class:`~megastep_amd.modules.RandomLifespans`); ``candidates``: see :class:`~megastep_amd.modules.Goals`.
@@ -41,7 +42,9 @@ class PointGoal:
         within ``margin``: it keeps to the middle where there is room. Reward and observations do not change. ``spl=True``: the
         world also carries ``spl`` (n_env, n_agent) - :class:`~megastep_amd.modules.SPL` over the goals: the score of every
         episode that ended at this step, NaN elsewhere - and ``env.spl`` holds the module. ``slide``: ``True`` or
-        ``dict(bounce=.05)`` - the agents slide along what they hit instead of stopping dead (:func:`~megastep_amd.cuda.physics`)."""
+        ``dict(bounce=.05)`` - the agents slide along what they hit instead of stopping dead (:func:`~megastep_amd.cuda.physics`).
+        ``panorama=True``: the observations also hold ``pano_rgb`` and ``pano_d`` - a 360-degree ring camera on every agent
+        (:class:`~megastep_amd.modules.Panorama`: 256 rays pooled by 4)."""
         if one_region and not sampled_spawns:
             raise RuntimeError('one_region gates the sampled spawns: it needs sampled_spawns=True')
         if geometries is None:
@@ -77,8 +80,11 @@ class PointGoal:
         self._follower = modules.PathFollower(c, self._goals if self._routes is None else self._routes, cone=15.)
         self._lookahead = None                          # (the 'lookahead' expert: made when first asked for)
         self.spl = modules.SPL(c, self._goals) if spl else None
+        self._pano = modules.Panorama(c) if panorama else None
         self.action_space = self._mover.space
         self.obs_space = dotdict.dotdict(rgb=self._rgb.space, d=self._depth.space, goal=self._goals.space)
+        if panorama:
+            self.obs_space.update(pano_rgb=self._pano.space, pano_d=self._pano.depth_space)
 
         self._over = c.agent_full(True)                 # who starts over at the next step
         self._episodes = torch.zeros((c.n_envs, c.n_agents), dtype=torch.long, device=c.device)
@@ -109,6 +115,9 @@ class PointGoal:
         self._over.copy_(self._lifespans(ended))
         frame = modules.render(self.core, observers=(self._rgb, self._depth), fields=())
         obs = arrdict.arrdict(rgb=self._rgb(frame), d=self._depth(frame), goal=self._goals.observation())
+        if self._pano is not None:
+            around = self._pano()
+            obs['pano_rgb'], obs['pano_d'] = around.rgb, around.d
         world = arrdict.arrdict(obs=obs, reset=reset.any(-1), reward=reward)
         if self.spl is not None:
             # (an episode ends when its agent arrives, is stranded or outlives its lifespan: only the first scores above 0)

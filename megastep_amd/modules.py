@@ -255,6 +255,48 @@ class RGB:
         return self._last_obs[e].clone()
 
 
+class Cameras:
+
+    def __init__(self, core, mounts, res, fov, projection='plane', subsample=1, max_depth=10, n_agents=None):
+        """Cameras mounted on every agent (:func:`cuda.mounted`: ``mounts`` (C, 3) - x, y in the agent's frame, turn in degrees)
+        of ``res`` rays each, as observations: a call returns ``arrdict(rgb=(n_env, n_agent, 3, C, res/subsample),
+        d=(n_env, n_agent, 1, C, res/subsample))`` - the cameras are the image's rows - colour mean-pooled as :class:`RGB`'s and
+        depth by :class:`Depth`'s formula, from one :func:`cuda.look` (a raycast launch and a shade launch; no counterpart in
+        the reference, whose agents have one camera each). ``projection='ring'`` takes fields of view up to 360 degrees.
+        Nothing is allocated after the first call and nothing waits for the host: it sits in a graphed step."""
+        if res % subsample:
+            raise ValueError('res must be a multiple of subsample')
+        self.core = core
+        self.subsample, self.max_depth = subsample, max_depth
+        self.cameras = cuda.mounted(core.agents, mounts, res, fov, projection)
+        self.n_mounts = self.cameras.n_cameras//core.n_agents
+        self.space = spaces.MultiImage(n_agents or core.n_agents, 3, self.n_mounts, res//subsample)
+        self.depth_space = spaces.MultiImage(n_agents or core.n_agents, 1, self.n_mounts, res//subsample)
+        self._look = None
+
+    def __call__(self):
+        c = self.core
+        self.cameras.update()
+        self._look = cuda.look(c.scenery, self.cameras, agents=c.agents, fields=('screen', 'distances'), out=self._look)
+        shape = (c.n_envs, c.n_agents, self.n_mounts, self.cameras.res)
+        screen = self._look.screen.view(*shape, 3).permute(0, 1, 4, 2, 3)
+        depth = 1 - ((self._look.distances.view(*shape) - c.agent_radius)/self.max_depth).clamp(0, 1)
+        self._last_obs = arrdict.arrdict(rgb=downsample(screen, self.subsample).mean(-1),
+                                         d=downsample(depth, self.subsample).mean(-1).unsqueeze(2))
+        return self._last_obs
+
+    def state(self, e=0):
+        return self._last_obs[e].clone()
+
+
+class Panorama(Cameras):
+
+    def __init__(self, core, res=256, subsample=4, max_depth=10, n_agents=None):
+        """One ring camera of 360 degrees at every agent's centre, looking along its heading - ray 0 just left of straight
+        behind, the middle of the image straight ahead: what no plane projection can show. See :class:`Cameras`."""
+        super().__init__(core, [[0., 0., 0.]], res, 360., 'ring', subsample, max_depth, n_agents)
+
+
 class Overhead:
 
     def __init__(self, core, size=32, radius=4., n_agents=None, half_width=None):
