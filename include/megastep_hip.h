@@ -1162,6 +1162,62 @@ typedef struct MsNavViews {
 } MsNavViews;
 int ms_nav_views(const MsScenery* scenery, const MsNavGrid* grid, const MsNavViews* views, void* hip_stream);
 
+/* Percepts: which of a set of points - the other agents, pickups, a goal object - each eye of an env can see, how far away and
+ * which way each is, and which are nearest: the entity observation behind a visibility mask of tag, hide-and-seek, foraging and
+ * search tasks, and their "seen by" predicate.  The rule is the view fields' (MsNavViews above), applied to eye/point pairs instead
+ * of a viewpoint and cell centres - the kernel calls the very functions nav_view_kernel calls - so a point is visible exactly when
+ * a cell whose centre it is would be.  Every step is one binary32 operation, in the order given, without contraction;
+ * tests/percept_rule.py restates it in numpy and the kernel - and its host instantiation, ms_host_percepts - is held to EQUALITY
+ * with it.  Per env E eyes, P points and the env's STATIC walls as they stand in MsScenery.lines_vals (rows n_agents*n_model ..
+ * L - 1): the agents' rows are not read, BODIES DO NOT OCCLUDE.  For eye (px, py) = eyes[n, e] and point (x, y) = points[n, p]:
+ *   candidate     iff valid[n, p] != 0 (NULL: every point exists), pairs allows it (pairs[e, p] != 0 with pairs_shape 1,
+ *                 pairs[n, e, p] != 0 with pairs_shape 2; NULL: every pair), px and py are finite, with headings (hx, hy) =
+ *                 headings[n, e] hlen = sqrtf(hx*hx + hy*hy) is finite and > 0, and rx = x - px, ry = y - py, rr = rx*rx + ry*ry,
+ *                 rr <= R2 (R2 = max_range*max_range formed once), and with headings hx*rx + hy*ry >= (cos_half*sqrtf(rr))*hlen.
+ *                 A NaN point is never a candidate (rr <= R2 fails); a point on the eye (rr == 0) is one, in every cone.
+ *   visible       iff a candidate and no static wall blocks it - MsNavViews' meets, apart and across.  Nothing blocks a point on
+ *                 the eye; a wall with a NaN blocks nothing.
+ *   visible       (N, E, P) bytes: 1 visible, 0 not.
+ *   squares       (N, E, P): rr where visible, +inf elsewhere.
+ *   offsets       (N, E, P, 2): (rx, ry), in the world frame, where visible, NaN elsewhere.
+ *   counts        (N, E): the visible points.
+ *   nearest       (N, E, K): the visible points in ascending order of the pair (bits of rr, p) - rr is not negative, so its
+ *                 binary32 bits order as its value, and equal distances go to the lower index; entries beyond counts hold -1.
+ *   near_offsets, near_distances   (N, E, K, 2) and (N, E, K): (rx, ry) and sqrtf(rr) of those K; NaN and +inf beyond counts.
+ *   mask          (N, E) bytes: an eye marked 0 is not computed, and every output row of it keeps what it held.
+ * No trigonometry and no division: a frame of the eye's own (forward, left) is the caller's arithmetic.  Each output may be NULL
+ * (not wanted), each element has exactly one writer.  Limits: 1 <= E <= 64, 1 <= P <= 1024, 0 <= K <= 16.
+ * Refused before any launch (MS_EINVAL): a NULL eyes or points; E, P or K outside those limits; every output NULL; max_range not
+ * positive and finite; cos_half outside [-1, 1] (or a NaN) when headings is given; pairs without pairs_shape 1 or 2, or a
+ * pairs_shape other than 0 without pairs; eyes, headings, points, offsets or near_offsets not 8-byte aligned; squares, counts,
+ * nearest or near_distances not 4-byte aligned.
+ * One launch, one workgroup per env: the walls whose box meets the box of everything in range of some unmasked eye are staged in
+ * LDS (more than 512 of them: read from the scenery instead, same result), a wave an eye, a lane the points lane + 64 j, the
+ * nearest K by K rounds of a wave-wide minimum.  No atomics, nothing allocated, nothing waits: the call can be captured in a
+ * HIP graph. */
+typedef struct MsPercepts {
+    int                  n_eyes;         /* E: eyes per env (1 .. 64)                                                     */
+    int                  n_points;       /* P: points per env (1 .. 1024)                                                 */
+    int                  n_nearest;      /* K: nearest visible points listed per eye (0 .. 16)                            */
+    const float*         eyes;           /* (N, E, 2) x, y; 8-byte aligned                                                */
+    const float*         headings;       /* (N, E, 2) any length, or NULL: no cone; 8-byte aligned                        */
+    const float*         points;         /* (N, P, 2) x, y; 8-byte aligned                                                */
+    const unsigned char* valid;          /* (N, P) non-zero: the point exists; NULL: all                                  */
+    const unsigned char* pairs;          /* non-zero: the eye takes an interest in the point; NULL: every pair            */
+    int                  pairs_shape;    /* 0: no pairs; 1: pairs is (E, P), shared by all envs; 2: pairs is (N, E, P)    */
+    const unsigned char* mask;           /* (N, E) non-zero: compute this eye; NULL: all.  Read on the device only.       */
+    float                max_range;      /* R, metres (> 0, finite)                                                       */
+    float                cos_half;       /* the cosine of half the cone's angle, in [-1, 1] (with headings)               */
+    unsigned char*       visible;        /* (N, E, P) out, or NULL                                                        */
+    float*               squares;        /* (N, E, P) out, or NULL                                                        */
+    float*               offsets;        /* (N, E, P, 2) out, or NULL; 8-byte aligned                                     */
+    int*                 counts;         /* (N, E) out, or NULL                                                           */
+    int*                 nearest;        /* (N, E, K) out, or NULL                                                        */
+    float*               near_offsets;   /* (N, E, K, 2) out, or NULL; 8-byte aligned                                     */
+    float*               near_distances; /* (N, E, K) out, or NULL                                                        */
+} MsPercepts;
+int ms_percepts(const MsScenery* scenery, const MsPercepts* percepts, void* hip_stream);
+
 /* Basins: WHICH seed a cell of a seeded field leads to - whose agent is nearest (a geodesic Voronoi diagram of the floor), which
  * frontier cluster, which pickup a cell drains to - and how many cells each seed, or each id, holds.  Every output is an integer
  * with one definition; tests/test_navbasin_host.py restates it in numpy (basin_rule, point_mark_rule, basin_query_rule: chains

@@ -180,6 +180,15 @@ int ms_host_nav_zones(const MsNavGrid* grid, const MsNavZones* zones);
  * ms_nav_views would: MS_OK, or MS_EINVAL for arguments it would refuse (and for a capacity above the kernel's). */
 int ms_host_nav_views(const MsNavGrid* grid, const MsNavViews* views, const float* walls, const long long* wall_starts, int capacity);
 int ms_host_nav_view_capacity(void);
+/* Host instantiation of the percepts' rule (kernels/percept.h over kernels/navview.h: the eye, the candidate, view_wall_blocks, the
+ * wall cull, the box of a wave's 64 points, the key of the nearest and the stores - the very functions every lane of percept_kernel
+ * evaluates) for one whole call of ms_percepts on HOST arrays, swept serially: every pointer of `percepts` is host memory, and in
+ * place of an MsScenery there are n_envs and `walls`, the STATIC rows of all envs, four floats each, env n's rows wall_starts[n] ..
+ * wall_starts[n + 1] - 1.  It goes through both wall paths: an env that keeps more than `capacity` rows (0: the kernel's,
+ * ms_host_nav_view_capacity(); a smaller one lets a test reach the other path with few walls) sweeps all its rows instead of the
+ * staged ones.  Returns what ms_percepts would: MS_OK, or MS_EINVAL for arguments it would refuse (and for n_envs < 1, NULL walls
+ * or a capacity above the kernel's). */
+int ms_host_percepts(const MsPercepts* percepts, int n_envs, const float* walls, const long long* wall_starts, int capacity);
 /* Host instantiations of the clearance rule (kernels/navclear.h: the tile's box, the list, ov_keeps and ov_fold, the second cull,
  * the winner's order and the stores - the very functions every lane of nav_clear_kernel and nav_clear_query_kernel evaluates) for
  * one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the argument struct is host memory.

@@ -248,6 +248,13 @@ class MsNavViews(C.Structure):
                 ('values', C.c_void_p), ('counts', C.c_void_p), ('gains', C.c_void_p)]
 
 
+class MsPercepts(C.Structure):
+    _fields_ = [('n_eyes', C.c_int), ('n_points', C.c_int), ('n_nearest', C.c_int), ('eyes', C.c_void_p), ('headings', C.c_void_p),
+                ('points', C.c_void_p), ('valid', C.c_void_p), ('pairs', C.c_void_p), ('pairs_shape', C.c_int), ('mask', C.c_void_p),
+                ('max_range', C.c_float), ('cos_half', C.c_float), ('visible', C.c_void_p), ('squares', C.c_void_p), ('offsets', C.c_void_p),
+                ('counts', C.c_void_p), ('nearest', C.c_void_p), ('near_offsets', C.c_void_p), ('near_distances', C.c_void_p)]
+
+
 class MsNavClearance(C.Structure):
     _fields_ = [('max_range', C.c_float), ('n_radii', C.c_int), ('radii', C.c_float*8), ('max_tiles', C.c_int), ('mask', C.c_void_p),
                 ('values', C.c_void_p), ('nearest', C.c_void_p), ('fits', C.c_void_p)]
@@ -297,6 +304,7 @@ PROTOTYPES = {
     'ms_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery), _ptr]),
     'ms_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks), _ptr]),
     'ms_nav_views': (_int, [_p(MsScenery), _p(MsNavGrid), _p(MsNavViews), _ptr]),
+    'ms_percepts': (_int, [_p(MsScenery), _p(MsPercepts), _ptr]),
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
     'ms_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery), _ptr]),
     'ms_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks), _ptr]),
@@ -356,6 +364,7 @@ PROTOTYPES = {
     'ms_host_nav_zones': (_int, [_p(MsNavGrid), _p(MsNavZones)]),
     'ms_host_nav_views': (_int, [_p(MsNavGrid), _p(MsNavViews), _ptr, _ptr, _int]),
     'ms_host_nav_view_capacity': (_int, []),
+    'ms_host_percepts': (_int, [_p(MsPercepts), _int, _ptr, _ptr, _int]),
     'ms_host_nav_clearance': (_int, [_p(MsNavGrid), _p(MsNavClearance), _ptr, _ptr, _int]),
     'ms_host_nav_clear_folds': (C.c_longlong, [_ptr]),
     'ms_host_nav_clear_chunk': (_int, []),

@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, slide.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, slide.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, percept.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
 //
-// Thirty kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty-one kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -76,6 +76,10 @@
 //                                                            (no counterpart)
 //   nav_view_kernel     view fields: one workgroup per viewpoint culls the env's static walls into LDS and tests the centre of
 //                   every cell in range against them, a lane a cell: the cells in sight, how many count, how many are new.
+//                                                            (no counterpart)
+//   percept_kernel      percepts: one workgroup per env culls the env's static walls into LDS; a wave an eye, a lane the points
+//                   lane + 64 j, each pair through the view fields' own predicates: which points each eye sees, how far and which
+//                   way, the count, and the nearest K by K rounds of a wave-wide minimum.
 //                                                            (no counterpart)
 //   nav_clear_kernel, nav_clear_query_kernel   clearance: the distance to the nearest wall - per cell, overhead_kernel's scheme on
 //                   the grid's 16 x 16 tiles (the env's static rows culled against the tile's box into LDS, a second cull by the
@@ -191,6 +195,7 @@ struct Probe {
 #include "kernels/navclear.h"
 #include "kernels/navregion.h"
 #include "kernels/navview.h"
+#include "kernels/percept.h"
 #include "kernels/navpath.h"
 #include "kernels/navpull.h"
 #include "kernels/navbasin.h"
@@ -1747,6 +1752,40 @@ int ms_host_nav_views(const MsNavGrid* grid, const MsNavViews* v, const float* w
 }
 
 int ms_host_nav_view_capacity(void) { return VIEW_WALL_CAPACITY; }
+
+// Percepts (percept.h): the same discipline.  The limits keep a lane's points within sixteen and a round's key within a lane.
+static int percepts_check(const MsPercepts* p) {
+    if (!p || p->n_eyes < 1 || p->n_eyes > PERCEPT_MAX_EYES || p->n_points < 1 || p->n_points > PERCEPT_MAX_POINTS || p->n_nearest < 0 ||
+        p->n_nearest > PERCEPT_MAX_NEAREST || !p->eyes || !p->points || !(p->max_range > 0.f) || !(p->max_range < INFINITY) ||
+        (p->headings && !(p->cos_half >= -1.f && p->cos_half <= 1.f)) || p->pairs_shape < 0 || p->pairs_shape > 2 ||
+        (p->pairs != nullptr) != (p->pairs_shape != 0) ||
+        (!p->visible && !p->squares && !p->offsets && !p->counts && !p->nearest && !p->near_offsets && !p->near_distances) ||
+        ((uintptr_t)p->eyes % 8) || ((uintptr_t)p->headings % 8) || ((uintptr_t)p->points % 8) || ((uintptr_t)p->offsets % 8) ||
+        ((uintptr_t)p->near_offsets % 8) || ((uintptr_t)p->squares % 4) || ((uintptr_t)p->counts % 4) || ((uintptr_t)p->nearest % 4) ||
+        ((uintptr_t)p->near_distances % 4)) return MS_EINVAL;
+    return MS_OK;
+}
+static PerceptArgs percept_args(const MsPercepts* p, const int capacity) {
+    return PerceptArgs{p->eyes, p->headings, p->points, p->valid, p->pairs, p->mask, p->visible, p->squares, p->offsets, p->counts, p->nearest,
+                       p->near_offsets, p->near_distances, p->n_eyes, p->n_points, p->n_nearest, p->pairs_shape == 2 ? 1 : 0, capacity,
+                       p->max_range, p->max_range*p->max_range, p->headings ? p->cos_half : 0.f};
+}
+
+int ms_percepts(const MsScenery* sc, const MsPercepts* p, void* stream) {
+    if (!scenery_ok(sc)) return MS_EINVAL;
+    const int status = percepts_check(p);
+    if (status != MS_OK) return status;
+    hipLaunchKernelGGL(percept_kernel, dim3((unsigned)sc->n_envs), dim3(WG), 0, (hipStream_t)stream, *sc, percept_args(p, VIEW_WALL_CAPACITY));
+    return launch_status();
+}
+
+int ms_host_percepts(const MsPercepts* p, int n_envs, const float* walls, const long long* wall_starts, int capacity) {
+    const int status = percepts_check(p);
+    if (status != MS_OK) return status;
+    if (n_envs < 1 || !walls || !wall_starts || capacity < 0 || capacity > VIEW_WALL_CAPACITY) return MS_EINVAL;
+    percept_serial(percept_args(p, capacity > 0 ? capacity : VIEW_WALL_CAPACITY), n_envs, reinterpret_cast<const float4*>(walls), wall_starts);
+    return MS_OK;
+}
 
 // Clearance (navclear.h): the same discipline.  CLEAR_DEFAULT_CULL is the instantiation ms_nav_clearance launches (DESIGN.md 3.23
 // has the measurements that chose it); the other stays reachable through ms_debug_nav_clear_cull for A/B runs.

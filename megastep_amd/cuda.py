@@ -734,6 +734,7 @@ def _render_layout(n, a, r, fields, pooled, lit):
 # ---------------------------------------------------------------------------------------------------------------------
 from .envlogic import deathmatch_shoot, explorer_books
 from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
+from .percepts import PERCEPT_FIELDS, PERCEPT_MAX_EYES, PERCEPT_MAX_POINTS, PERCEPT_MAX_NEAREST, Percepts, percepts
 from .cameras import PROJECTIONS, LOOK_FIELDS, Cameras, Look, shade, cameras, mounted, look
 from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans, _bounce
 from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, plan_views, agent_views

@@ -384,6 +384,48 @@ class Proximity:
         return self.observation(self._reading.distances, self._reading.towards, agents.angles, self.max_range)
 
 
+class Percepts:
+
+    def __init__(self, core, points=None, max_range=10., fov=None, k=4, pairs=None):
+        """The nearest things each agent SEES, (n_env, n_agent, k, 4) (:func:`cuda.percepts`; no counterpart in the reference): row j
+        is ``[1, forward/max_range, left/max_range, distance/max_range]`` for the j-th nearest of the points in sight of the agent -
+        the point's offset turned into the agent's frame by :func:`to_local_frame`'s arithmetic, whose first axis is the camera's -
+        and zeros beyond the ones it sees: the entity observation behind a visibility mask of tag, hide-and-seek and foraging
+        tasks. ``points``: an (n_env, P, 2) float32 tensor kept by reference - pickups, goal objects; move them in place - or None:
+        the other agents. In sight: no further than ``max_range`` metres, within ``fov`` degrees round the agent's heading when
+        ``fov`` is given, no static wall in between; the agents' bodies do not occlude. ``pairs``: :func:`cuda.percepts`'. One
+        launch and a few elementwise ops; the module keeps the launch's buffers, nothing waits for the host: a call can sit in a
+        HIP graph."""
+        self.core = core
+        self.points, self.max_range, self.fov, self.k, self.pairs = points, float(max_range), fov, int(k), pairs
+        self.space = spaces.MultiRows(core.n_agents, self.k, 4)
+        self._reading = None
+
+    #: the :class:`cuda.Percepts` of the last call (None before the first)
+    reading = property(lambda self: self._reading)
+
+    @staticmethod
+    def pack(counts, near_offsets, near_distances, angles, max_range):
+        """The rule, a pure function: ``counts`` (N, A) integers, ``near_offsets`` (N, A, K, 2) in the world frame, ``near_distances``
+        (N, A, K), ``angles`` (N, A) degrees -> (N, A, K, 4)."""
+        k = near_distances.shape[-1]
+        listed = torch.arange(k, device=counts.device) < counts[..., None]
+        local = to_local_frame(angles[..., None], near_offsets)
+        rows = torch.cat([torch.ones_like(near_distances)[..., None], local/max_range, (near_distances/max_range)[..., None]], -1)
+        return torch.where(listed[..., None], rows, torch.zeros_like(rows))
+
+    def __call__(self):
+        agents = self.core.agents
+        self._reading = cuda.percepts(self.core.scenery, self.points, agents=agents, max_range=self.max_range, fov=self.fov, k=self.k,
+                                      pairs=self.pairs, fields=('counts', 'near_offsets', 'near_distances'), out=self._reading)
+        r = self._reading
+        self._last_obs = self.pack(r.counts, r.near_offsets, r.near_distances, agents.angles, self.max_range)
+        return self._last_obs
+
+    def state(self, e=0):
+        return self._last_obs[e].clone()
+
+
 def random_empty_positions(geometries, n_agents, n_points):
     """(n_geometries, n_agents, n_points, 2) randomly chosen free-cell centres, precomputed so respawns are cheap
     (reference: modules.py:272-296; consumes the global ``np.random`` in the same order, env by env). The free cells of

@@ -1,5 +1,5 @@
 """What an env's observations and actions look like, per agent-row: nothing but shapes, which is all a policy
-constructor needs (same five names and ``.shape`` tuples as megastep/spaces.py:1-28). The leading axis is the
+constructor needs (the five names and ``.shape`` tuples of megastep/spaces.py:1-28, and ``MultiRows``). The leading axis is the
 agents-per-row axis the modules are built with."""
 
 
@@ -13,6 +13,13 @@ class MultiVector:
 
     def __init__(self, n_agents, dim):
         self.shape = (n_agents, dim)
+
+
+class MultiRows:
+    """``rows`` rows of ``dim`` floats per agent (percepts: a row per thing seen)."""
+
+    def __init__(self, n_agents, rows, dim):
+        self.shape = (n_agents, rows, dim)
 
 
 class MultiImage:
