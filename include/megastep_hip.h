@@ -486,7 +486,8 @@ int ms_overhead(const MsScenery* scenery, const MsAgents* agents /* NULL: agent 
  *   advance   the integration epilogue: p += x v/fps, ang likewise and normalised; x < 1: v = w = 0
  * Outputs (one writer each): the state after step H-1, progress = the least x, stops = the steps with x < 1, first_stop = the
  * first of them (H: none), and optionally the position after every step.  With a mask only the marked agents are rolled and
- * the rows of the others are left as they are.  Not in a rollout: other agents that move, respawns, lifespans, the IMU.
+ * the rows of the others are left as they are.  Not in a rollout: other agents that move (MsScenarios below), respawns,
+ * lifespans, the IMU.
  * Nothing is allocated, no global atomics, nothing waits for the host: the call can be captured in a HIP graph.  1 <= K <= 256,
  * 1 <= H <= 64, n_actions >= 1, others in {0, 1}: MS_EINVAL otherwise, before anything is launched.
  * slide = 1: `walls`, `others` and `advance` are the sliding step's (MsSlide above: phase A, the contact, phase B with `bounce`),
@@ -517,6 +518,52 @@ typedef struct MsRollouts {
 } MsRollouts;
 int ms_rollouts(const MsScenery* scenery, const MsAgents* agents, const MsRollouts* rollouts, const MsConfig* config,
                 void* hip_stream);
+
+/* Scenarios: whole envs forked S ways and stepped H times, every agent on a plan of its own, in one launch - the multi-agent
+ * completion of MsRollouts (no counterpart in the reference, where the only way to know is to step a copy of the world once
+ * per scenario and step).  The scenery and the agents are READ ONLY.  For every env n and scenario s, from ALL agents'
+ * (p, ang, v, w) as they stand, for h = 0 .. H-1 in this order - every statement the one ms_move_physics makes of a copy of
+ * env n (kernels.cu:179-230, modules.py:57-66,106-118), on the same functions:
+ *   move      for every agent a: (v_a, w_a) <- the movement prologue (MsMovement) of table row act(n, s, a, h), clamped
+ *   meet      for every agent a: x_a = min(1, collision_cs(p_a, v_a/fps, wall, agent_radius) over ALL static lines of env n,
+ *             collision_cc(p_a, v_a/fps, p_b, v_b/fps, agent_radius) over every other agent b != a) - everybody's (p, v) after
+ *             `move` and before `advance`: the ordered-pair test of kernels.cu:193-205, the other's moved velocity where
+ *             MsRollouts has (0, 0).  The reach culls and the wall grid's near lists stand in front of the tests where
+ *             ms_physics uses them - the pose inside the grid, the reach at most wg_reach - and every static line otherwise:
+ *             every value lies in [+0, 1] and the fold is a minimum, so the bits are the same
+ *   advance   for every agent: the integration epilogue with x_a; x_a < 1: v_a = w_a = 0
+ * Where act comes from - focal = 0 (joint): actions (N, S, A, H), or (S, A, H) with shared != 0; the outputs have one row per
+ * (n, s, a) and the mask is (N,).  focal = 1: n_scenarios is K; scenario (f, k) puts agent f on actions[n, f, k, :] - (N, A, K, H),
+ * or (K, H) with shared != 0 - and every other agent b on base[n, b, :] ((N, A, H)); only agent f's row is written, the outputs
+ * are MsRollouts' (N, A, K, ..) and the mask is (N, A), the focal agents.  Focal is joint on the expanded tensor.
+ * Outputs (one writer each): the state after step H-1, progress = the least x, stops = the steps with x < 1, first_stop = the
+ * first of them (H: none), and optionally the position after every step.  A row the mask leaves out is not written.
+ * Not in a scenario: sliding steps, respawns, lifespans, the IMU.  Nothing is allocated, no global atomics, nothing waits
+ * for the host: the call can be captured in a HIP graph.  1 <= n_scenarios <= 256, 1 <= H <= 64, n_actions >= 1, keep a number,
+ * focal and shared in {0, 1}, every pointer and its alignment, a wall grid given whole: MS_EINVAL otherwise; more than 64
+ * agents an env: MS_EUNSUPPORTED (a lane an agent) - all before anything is launched. */
+typedef struct MsScenarios {
+    int                  n_scenarios;   /* S; focal: K                                                                 */
+    int                  horizon;       /* H                                                                           */
+    int                  focal;         /* 0: joint; 1: focal                                                          */
+    const long long*     actions;       /* joint (N, S, A, H) | shared (S, A, H); focal (N, A, K, H) | shared (K, H); 8-byte aligned */
+    int                  shared;
+    const long long*     base;          /* focal: (N, A, H), what the agents that are not focal do; joint: not read    */
+    const float*         table;         /* (n_actions, 3) [dx, dy, dw], as MsMovement's                                */
+    int                  n_actions;
+    float                keep;          /* as MsMovement's                                                             */
+    const unsigned char* mask;          /* joint (N,), focal (N, A) bytes, optional: non-zero = roll                   */
+    float*               positions;     /* joint (N, S, A, 2), focal (N, A, K, 2) out, 8-byte aligned                  */
+    float*               angles;        /* (N, S, A) | (N, A, K) out, as every output below                            */
+    float*               velocity;      /* (.., 2) out, 8-byte aligned                                                 */
+    float*               angvelocity;
+    float*               progress;
+    int*                 stops;
+    int*                 first_stop;
+    float*               trail;         /* (.., H, 2) out, optional, 8-byte aligned                                    */
+} MsScenarios;
+int ms_scenarios(const MsScenery* scenery, const MsAgents* agents, const MsScenarios* scenarios, const MsConfig* config,
+                 void* hip_stream);
 
 /* Shortest-path distance fields on the floorplans: how far it is from a point to a goal when one has to walk round the
  * walls.  Every step below is one binary32 operation, in the order given, without contraction: tests/test_navfield_host.py

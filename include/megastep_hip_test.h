@@ -253,6 +253,14 @@ void ms_host_move_velocity(float keep, float ang, const float* delta, float* v, 
  * n_walls > 0, n_agents < 1). */
 int ms_host_rollouts(const float* walls, int n_walls, const MsAgents* agents, int n_agents, const MsRollouts* rollouts,
                      const MsConfig* config);
+/* The scenarios' rule (MsScenarios) stated serially over the kernel's own per-step functions (kernels/scenario.h, kernels/rollout.h)
+ * for ONE env on HOST arrays, as ms_host_rollouts: `walls` the env's n_walls STATIC rows; every pointer of `agents` and of
+ * `scenarios` is host memory and holds the one env's share - joint actions (S, A, H), focal (A, K, H) or shared (K, H), base
+ * (A, H); mask (1,) joint, (A,) focal, or NULL; the outputs (S, A, ..) or (A, K, ..).  Every agent meets every other agent and
+ * every wall, behind the reach culls.  Returns what ms_scenarios would: MS_OK, MS_EINVAL for arguments it would refuse (and
+ * for NULL walls with n_walls > 0, n_agents < 1), MS_EUNSUPPORTED for more than 64 agents. */
+int ms_host_scenarios(const float* walls, int n_walls, const MsAgents* agents, int n_agents, const MsScenarios* scenarios,
+                      const MsConfig* config);
 /* ms_debug_rollout_scheme: how ms_rollouts' waves meet a step's walls - 0 = a lane a candidate, each walking the near list of its
  * own cell; 1 = physics_kernel's scheme: a lane a wall, the wave's candidates one after another, the surviving pairs compacted in
  * LDS before the exact test; -1 = the library's own choice (1 up to 24 candidates an agent, else 0); anything else: MS_EINVAL.  Per calling thread; A/B runs and tests -

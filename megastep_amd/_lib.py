@@ -105,6 +105,13 @@ class MsOverhead(C.Structure):
                 ('rgb', C.c_void_p), ('indices', C.c_void_p)]
 
 
+class MsScenarios(C.Structure):
+    _fields_ = [('n_scenarios', C.c_int), ('horizon', C.c_int), ('focal', C.c_int), ('actions', C.c_void_p), ('shared', C.c_int),
+                ('base', C.c_void_p), ('table', C.c_void_p), ('n_actions', C.c_int), ('keep', C.c_float), ('mask', C.c_void_p),
+                ('positions', C.c_void_p), ('angles', C.c_void_p), ('velocity', C.c_void_p), ('angvelocity', C.c_void_p),
+                ('progress', C.c_void_p), ('stops', C.c_void_p), ('first_stop', C.c_void_p), ('trail', C.c_void_p)]
+
+
 class MsRollouts(C.Structure):
     _fields_ = [('n_candidates', C.c_int), ('horizon', C.c_int), ('actions', C.c_void_p), ('shared_plans', C.c_int), ('table', C.c_void_p),
                 ('n_actions', C.c_int), ('keep', C.c_float), ('others', C.c_int), ('mask', C.c_void_p), ('positions', C.c_void_p),
@@ -291,6 +298,7 @@ PROTOTYPES = {
     'ms_camera_pose_rays': (_int, [_p(MsCameraPoses), _ptr]),
     'ms_overhead': (_int, [_p(MsScenery), _p(MsAgents), _p(MsOverhead), _ptr]),
     'ms_rollouts': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRollouts), _p(MsConfig), _ptr]),
+    'ms_scenarios': (_int, [_p(MsScenery), _p(MsAgents), _p(MsScenarios), _p(MsConfig), _ptr]),
     'ms_nav_free': (_int, [_p(MsScenery), _p(MsNavGrid), _ptr]),
     'ms_nav_fields': (_int, [_p(MsNavGrid), _p(MsNavFields), _ptr]),
     'ms_nav_query': (_int, [_p(MsNavGrid), _p(MsNavQuery), _ptr]),
@@ -379,6 +387,7 @@ PROTOTYPES = {
     'ms_host_move_velocity': (None, [_flt, _flt, _f32p, _f32p, _f32p]),
     'ms_host_rollouts': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsRollouts), _p(MsConfig)]),
     'ms_debug_rollout_scheme': (_int, [_int]),
+    'ms_host_scenarios': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsScenarios), _p(MsConfig)]),
     'ms_host_slide': (_int, [_ptr, _ptr, _int, _int, _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsSlide), _ptr, _p(MsConfig)]),
     'ms_host_shade': (_int, [_p(MsScenery), _p(MsAgents), _p(MsShade)]),
     'ms_host_wall_hidden': (_int, [_flt]*4 + [_f32p, _f32p, _flt]),

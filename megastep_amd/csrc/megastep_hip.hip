@@ -2,9 +2,9 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, slide.h, rollout.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, percept.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, slide.h, rollout.h, scenario.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, percept.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
 //
-// Thirty-one kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty-two kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -21,6 +21,9 @@
 //                   in (or, where no list applies, its env's static rows) through the step's own functions.   (no counterpart)
 //   rollout_walls_kernel   the same rule by physics_kernel's scheme - a lane a wall, the candidates one after another, the
 //                   surviving pairs compacted in LDS before the exact test: behind ms_debug_rollout_scheme, for A/B runs.
+//   scenario_kernel     whole envs forked S ways, every agent on its own plan: a wavefront holds 64 / A whole scenarios, a lane
+//                   an agent of one; each step the lanes of a scenario show each other their moved (p, v/fps) through LDS and
+//                   meet as physics_kernel's ordered pairs do, then walk their cells' near lists as rollout_kernel.  (no counterpart)
 //   render_kernel<OBS, SHADE, NG, STEP>   (OBS = 2: pooled observations only, no plane stores in the kernel; STEP = 1: a
 //                   single-agent env's physics step first, in the same wave - ms_step_render's one launch a step)
 //                   one wavefront per (env, agent, 64-ray group) - or, NG = 4, per four such groups
@@ -184,6 +187,7 @@ struct Probe {
 #include "kernels/physics.h"
 #include "kernels/slide.h"
 #include "kernels/rollout.h"
+#include "kernels/scenario.h"
 #include "kernels/lighting.h"
 #include "kernels/render.h"
 #include "kernels/bake.h"
@@ -705,6 +709,42 @@ int ms_debug_rollout_scheme(int scheme) {
 int ms_host_rollouts(const float* walls, int n_walls, const MsAgents* ag, int n_agents, const MsRollouts* r, const MsConfig* cfg) {
     if (!agents_ok(ag) || !config_ok(cfg) || rollouts_status(r) != MS_OK || n_agents < 1 || n_walls < 0 || (n_walls > 0 && !walls)) return MS_EINVAL;
     rollout_serial(walls, n_walls, *ag, n_agents, *r, cfg->agent_radius, cfg->fps);
+    return MS_OK;
+}
+
+// what ms_scenarios and ms_host_scenarios refuse alike: the limits and the pointers of an MsScenarios, and the agents an env
+static int scenarios_status(const MsScenarios* q, const int n_agents) {
+    if (!q || q->n_scenarios < 1 || q->n_scenarios > 256 || q->horizon < 1 || q->horizon > 64 || q->n_actions < 1 ||
+        (q->focal != 0 && q->focal != 1) || (q->shared != 0 && q->shared != 1) || !(q->keep == q->keep) || !q->actions ||
+        (q->focal && !q->base) || !q->table || !q->positions || !q->angles || !q->velocity || !q->angvelocity || !q->progress ||
+        !q->stops || !q->first_stop || n_agents < 1) return MS_EINVAL;
+    if (n_agents > WAVE) return MS_EUNSUPPORTED;                         // (a lane an agent, as ms_slide_physics)
+    return MS_OK;
+}
+
+int ms_scenarios(const MsScenery* sc, const MsAgents* ag, const MsScenarios* q, const MsConfig* cfg, void* stream) {
+    if (!scenery_ok(sc) || !agents_ok(ag) || !config_ok(cfg)) return MS_EINVAL;
+    if (const int st = scenarios_status(q, sc->n_agents)) return st;
+    if (((uintptr_t)q->actions % 8) || ((uintptr_t)q->base % 8) || ((uintptr_t)q->table % 4) || ((uintptr_t)q->positions % 8) ||
+        ((uintptr_t)q->velocity % 8) || ((uintptr_t)q->trail % 8) || ((uintptr_t)q->angles % 4) || ((uintptr_t)q->angvelocity % 4) ||
+        ((uintptr_t)q->progress % 4) || ((uintptr_t)q->stops % 4) || ((uintptr_t)q->first_stop % 4) ||
+        ((uintptr_t)ag->positions % 8) || ((uintptr_t)ag->velocity % 8)) return MS_EINVAL;
+    if (sc->wg_cells && (!sc->wg_starts || !sc->wg_geom || !sc->wg_near_rows || !(sc->wg_cell > 0.f) || ((uintptr_t)sc->wg_cells % 16) ||
+                         ((uintptr_t)sc->wg_geom % 16) || ((uintptr_t)sc->wg_near_rows % 16))) return MS_EINVAL;
+    const int G = WAVE/sc->n_agents;                                     // whole scenarios a wave
+    const int S = scenario_count(*q, sc->n_agents);
+    const int groups = (S + G - 1)/G;
+    const long long blocks = (long long)sc->n_envs*groups;
+    if (blocks > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    hipLaunchKernelGGL(scenario_kernel, dim3((unsigned)blocks), dim3(WAVE), 0, (hipStream_t)stream, *sc, agents_k(*ag), *q,
+                       cfg->agent_radius, cfg->fps, groups, G, divisor_of((unsigned)groups), divisor_of((unsigned)sc->n_agents));
+    return launch_status();
+}
+
+int ms_host_scenarios(const float* walls, int n_walls, const MsAgents* ag, int n_agents, const MsScenarios* q, const MsConfig* cfg) {
+    if (!agents_ok(ag) || !config_ok(cfg) || n_walls < 0 || (n_walls > 0 && !walls)) return MS_EINVAL;
+    if (const int st = scenarios_status(q, n_agents)) return st;
+    scenario_serial(walls, n_walls, *ag, n_agents, *q, cfg->agent_radius, cfg->fps);
     return MS_OK;
 }
 

@@ -6,7 +6,7 @@ point is a hand-written gfx950 kernel reached through the C-ABI in ``include/meg
 (PyTorch-ROCm is the allocator/stream plumbing); the kernels run on ``torch.cuda.current_stream()``.
 
 The calls without a counterpart in the reference live in modules named after the kernel files they drive - ``rays``,
-``rollouts``, ``overhead``, ``nav`` and ``envlogic`` - and are imported at the end of this one, so each is still ``cuda.<name>``.
+``rollouts``, ``scenarios``, ``overhead``, ``nav`` and ``envlogic`` - and are imported at the end of this one, so each is still ``cuda.<name>``.
 
 There is no CPU implementation here, exactly as in the reference ("If you haven't got CUDA, megastep will not work",
 reference: docs/faq.rst:23-26): calling bake/physics/render on non-GPU tensors raises.
@@ -737,6 +737,7 @@ from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
 from .percepts import PERCEPT_FIELDS, PERCEPT_MAX_EYES, PERCEPT_MAX_POINTS, PERCEPT_MAX_NEAREST, Percepts, percepts
 from .cameras import PROJECTIONS, LOOK_FIELDS, Cameras, Look, shade, cameras, mounted, look
 from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans, _bounce
+from .scenarios import SCENARIO_MAX_SCENARIOS, SCENARIO_MAX_AGENTS, Scenarios, scenarios
 from .overhead import OVERHEAD_FIELDS, OVERHEAD_BACKGROUND, Overhead, overhead, plan_views, agent_views
 from .nav import nav_geometry, NavGrid, nav_grid, FIELD_CAPACITY, DistanceFields, Paths, PulledPaths, distance_fields, geodesic, SeenMaps, seen_maps, AGE_MAX_TICK, Sweep, AgeMaps, age_maps, SeededFields, seeded_fields, \
     COST_CAPACITY, COST_MAX, CostFields, cost_fields, inflation_costs, mark_costs, \

@@ -79,6 +79,7 @@ class PointGoal:
         # (under momentum a narrow cone walks a third less far: DESIGN 3.15)
         self._follower = modules.PathFollower(c, self._goals if self._routes is None else self._routes, cone=15.)
         self._lookahead = None                          # (the 'lookahead' expert: made when first asked for)
+        self._anticipate = None                         # (the 'anticipate' expert, likewise)
         self.spl = modules.SPL(c, self._goals) if spl else None
         self._pano = modules.Panorama(c) if panorama else None
         self.action_space = self._mover.space
@@ -145,13 +146,20 @@ class PointGoal:
         ``env.step(env.expert())`` can sit in one graph. The follower counts the steps an agent has been stuck, so ask once
         per step. ``kind='lookahead'``: what :class:`~megastep_amd.modules.LookAhead` does instead - it rolls its plans through
         the physics step and takes the one that ends nearest the goal (by the env's routes, with ``margin``) - with a follower
-        of its own to fall back on; as capturable, and made by the first call that asks for it (outside a graph)."""
+        of its own to fall back on; as capturable, and made by the first call that asks for it (outside a graph).
+        ``kind='anticipate'``: a ``LookAhead(others='repeat')`` - the same plans rolled among the env's other agents MOVING, each
+        taken to repeat what this expert last chose for it, where ``'lookahead'`` has them stand still; made likewise."""
         if kind == 'follow':
             return self._follower()
-        if kind != 'lookahead':
-            raise RuntimeError(f"kind must be 'follow' or 'lookahead'; got {kind!r}")
+        if kind not in ('lookahead', 'anticipate'):
+            raise RuntimeError(f"kind must be 'follow', 'lookahead' or 'anticipate'; got {kind!r}")
+        source = self._goals if self._routes is None else self._routes
+        if kind == 'anticipate':
+            if self._anticipate is None:
+                self._anticipate = modules.LookAhead(self.core, source, self._mover, fallback=modules.PathFollower(self.core, source, cone=15.),
+                                                     others='repeat')
+            return self._anticipate()
         if self._lookahead is None:
-            source = self._goals if self._routes is None else self._routes
             self._lookahead = modules.LookAhead(self.core, source, self._mover, fallback=modules.PathFollower(self.core, source, cone=15.))
         return self._lookahead()
 

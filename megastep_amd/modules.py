@@ -107,6 +107,14 @@ class SimpleMovement:
             kw.setdefault('slide', self.slide)
         return cuda.rollouts(self.core.scenery, self.core.agents, actions, self._table, keep=self.keep, **kw)
 
+    def scenarios(self, actions, **kw):
+        """:func:`cuda.scenarios` of ``actions`` ((n_env, S, n_agent, H) or (S, n_agent, H) int64) under this module's table and
+        ``keep``: where every agent of every env would end up if all of them took the plans of scenario ``s`` together, without
+        moving anybody. Scenarios take plain steps: a module whose steps slide refuses. ``kw``: ``trail``, ``mask``, ``out``."""
+        if self.slide:
+            raise RuntimeError('scenarios take plain steps: sliding steps are not part of a scenario')
+        return cuda.scenarios(self.core.scenery, self.core.agents, actions, self._table, keep=self.keep, **kw)
+
 
 class MomentumMovement:
 
@@ -127,6 +135,7 @@ class MomentumMovement:
         return _move(self.core, self._actionset, decision.actions, self.keep, respawn, imu, self._table, self.slide)
 
     rollouts = SimpleMovement.rollouts
+    scenarios = SimpleMovement.scenarios
 
 
 def unpack(d):
@@ -1334,7 +1343,7 @@ class PathFollower:
 
 class LookAhead:
 
-    def __init__(self, core, goals, mover, horizon=8, switch=2, stop_cost=.5, fallback=None):
+    def __init__(self, core, goals, mover, horizon=8, switch=2, stop_cost=.5, fallback=None, others='rest'):
         """A look-ahead expert with :class:`PathFollower`'s call interface (a local planner in the style of the dynamic-window
         approach; no counterpart in the reference): every agent rolls the plans ``cuda.plans(n_actions, horizon, switch)`` -
         "action i for ``switch`` steps, then action j" - through the physics step itself (``mover.rollouts``, with the env's other
@@ -1345,7 +1354,14 @@ class LookAhead:
         agent does what ``fallback`` does (default: a :class:`PathFollower` on the same goals). Unlike the follower, which plans
         for a point, it knows what physics does to the disc. One rollout launch, one ``at`` and a few tensor ops; the module
         keeps the launch's buffers and nothing waits for the host: a call can sit in a HIP graph. The fallback counts dead
-        stops, so call the module once per step."""
+        stops, so call the module once per step.
+
+        ``others='repeat'``: the env's other agents are not at rest - every one of them is taken to repeat, for the whole
+        horizon, the action this module returned for it at its previous call (the no-op, 0, before the first), all of them
+        moving and meeting together as in the step itself (``mover.rollouts(plans, others=base)``). ``base`` is
+        an (n_env, n_agent, H) buffer written in place, so the call still captures."""
+        if others not in ('rest', 'repeat'):
+            raise RuntimeError(f"others must be 'rest' or 'repeat'; got {others!r}")
         self.core, self.goals, self.mover = core, goals, mover
         self.horizon, self.switch, self.stop_cost = int(horizon), switch, float(stop_cost)
         self.fallback = PathFollower(core, goals) if fallback is None else fallback
@@ -1355,6 +1371,8 @@ class LookAhead:
         n, a, k = core.n_envs, core.n_agents, self.plans.shape[0]
         self._agent = torch.arange(a, dtype=torch.int32, device=core.device)[None, :, None].expand(n, a, k).reshape(n, -1).contiguous()
         self._others = 'rest' if a > 1 else None
+        #: (n_env, n_agent, H) int64 with ``others='repeat'``: what every agent is taken to do when it is one of the others
+        self.base = torch.zeros((n, a, self.horizon), dtype=torch.int64, device=core.device) if others == 'repeat' else None
         self._rolled = None
         #: (n_env, n_agent, K): what the last call's plans were worth (None before the first)
         self.values = None
@@ -1378,13 +1396,21 @@ class LookAhead:
         action = first[index] if first.ndim == 1 else first.gather(-1, index[..., None]).squeeze(-1)
         return action, none
 
+    @staticmethod
+    def repeat(base, actions):
+        """The buffer rule of ``others='repeat'``, in place: ``base`` (..., H) <- ``actions`` (...) at every step. Returns ``base``."""
+        return base.copy_(actions[..., None].expand_as(base))
+
     def __call__(self):
         """``arrdict(actions=(n_env, n_agent) int64)``: the decision for the agents as they stand."""
         n, a, k = self.core.n_envs, self.core.n_agents, self.plans.shape[0]
-        self._rolled = self.mover.rollouts(self.plans, others=self._others, out=self._rolled)
+        self._rolled = self.mover.rollouts(self.plans, others=self._others if self.base is None else self.base, out=self._rolled)
         self.values = self.goals.fields.at(self._rolled.positions.view(n, a*k, 2), goal=self._agent).view(n, a, k)
         action, none = self.choose(self.values, self._rolled.stops, self.plans, self.stop_cost)
-        return arrdict.arrdict(actions=torch.where(none, self.fallback().actions, action))
+        actions = torch.where(none, self.fallback().actions, action)
+        if self.base is not None:
+            self.repeat(self.base, actions)
+        return arrdict.arrdict(actions=actions)
 
 
 class SPL:

@@ -82,14 +82,16 @@ def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False,
     ``keep``: a movement module's, as :func:`physics`' ``movement``. Every candidate starts from its agent's state as it stands
     and takes, per step, the movement update, the collision tests against all static walls of its env - through the wall grid's
     lists where they are exact, against every wall where not: the same bits - and the integration. ``others='rest'``: the env's
-    other agents are obstacles too, standing still where the call found them for the whole horizon; ``None``: they are absent.
-    ``trail=True`` also gives the position after every step. ``mask`` (N, A) bool: only the marked agents are rolled; the others
+    other agents are obstacles too, standing still where the call found them for the whole horizon; ``None``: they are absent;
+    a (N, A, H) int64 tensor: they MOVE - while agent ``f`` rolls its plan ``k``, every other agent ``b`` of its env takes the
+    actions ``others[n, b, :]``, everybody meeting everybody as in one :func:`physics` step (the focal mode of
+    :func:`scenarios`; at most 64 agents an env, not with ``slide``). ``trail=True`` also gives the position after every step. ``mask`` (N, A) bool: only the marked agents are rolled; the others
     keep what ``out`` held, and without ``out`` read as NaN poses, progress 1, no stops. ``out``: the :class:`Rollouts` of an
     earlier call with the same shapes, to write into. ``config``: see :func:`physics` (``agent_radius`` and ``fps`` are read).
     ``slide``: ``True`` or ``dict(bounce=.05)`` - every step is :func:`physics`' sliding step, the others at rest in both its
     phases; the result then has ``slides``, and its ``stops`` count dead stops.
 
-    ``1 <= K <= 256`` and ``1 <= H <= 64``. Other agents that move, respawns, lifespans and the IMU are not part of a rollout.
+    ``1 <= K <= 256`` and ``1 <= H <= 64``. Respawns, lifespans and the IMU are not part of a rollout.
     No host synchronisation, nothing allocated with ``out``: the call can be captured in a HIP graph."""
     n, a = len(scenery.lines), scenery.n_agents
     if tuple(agents.angles.shape) != (n, a):
@@ -108,8 +110,13 @@ def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False,
         raise RuntimeError(f'the horizon H must be in 1..{ROLLOUT_MAX_HORIZON}; got {h}')
     if table.shape[1] != 3 or table.shape[0] < 1:
         raise RuntimeError(f'table must be (n_actions, 3) with n_actions >= 1; got {tuple(table.shape)}')
+    if isinstance(others, torch.Tensor):
+        if slide is not None and slide is not False:
+            raise RuntimeError('slide is not part of a rollout among moving others: sliding steps are stated for others at rest only')
+        from .scenarios import _focal
+        return _focal(scenery, agents, actions, others, table, keep, trail, mask, out, config, k, h, shared)
     if others not in (None, 'rest'):
-        raise RuntimeError(f"others must be None or 'rest'; got {others!r}")
+        raise RuntimeError(f"others must be None, 'rest' or a (N, A, H) int64 tensor; got {others!r}")
     keep = float(keep)
     if keep != keep:
         raise RuntimeError('keep must be a number')
