@@ -220,6 +220,33 @@ int ms_debug_nav_clear_cull(int mode);
  * each other bit for bit over the ranges the call sites guarantee.  Any output pointer may be NULL. */
 int ms_test_arithmetic(const float* n, const float* d, float* q_inrange, float* q_ieee, const float* x, float* r_any, float* r_ieee,
                        long long count, void* hip_stream);
+/* The DEVICE builds of the culls and shortcuts whose device text is not the host's (v_rcp_f32 for a division, one refined
+ * reciprocal for two divisions, sign tests for two quotients), element by element (kernels/culltest.h): each evaluates the very
+ * functions the product kernels call on `count` elements - DEVICE pointers, one element a lane; rows of 4 floats are (count, 4),
+ * points (count, 2).  Any output pointer may be NULL; MS_EINVAL for a NULL input, a negative count or (ms_test_ray_interval) a
+ * shape no render launch has.  tests/test_gpu_culls.py holds them to the oracle at their thresholds.
+ *   ms_test_agents_apart   apart[i] = agents_apart(me[i], other[i], radius[i]): ms_host_agents_apart's arguments.
+ *   ms_test_wall_beyond    reach[i] = wall_reach(agent[i], radius[i]), beyond[i] = wall_beyond(agent[i], wall[i], reach_squared(reach[i])):
+ *                          ms_host_wall_reach's and ms_host_wall_beyond_reach's arguments.
+ *   ms_test_ray_interval   first[i], rays[i] = agent_frame + ray_interval of line[i] from pose[i] = (x, y, sin, cos) for wave `wave` of
+ *                          64 x groups rays: ms_host_ray_interval_wide's arguments, the launch-invariant values formed by the same code.
+ *   ms_test_wedge          wa[i], wb[i] = wg_wedge(pseudo_angle_fast(right[i]), pseudo_angle_fast(left[i])): the run of steps of a wave
+ *                          whose rightmost / leftmost ray point along right[i] / left[i], as render_kernel forms it.
+ *   ms_test_cell_at        index[i], inside[i] = wg_cell_at(geom[i] = (x0, y0, nx, ny), cell[i], point[i]).
+ *   ms_test_tex_filter     l[i], r[i], lw[i], rw[i] = tex_filter(x[i], w[i]).
+ *   ms_test_light_blocked  blocked[i] = light_blocked(I = light[i], U = to[i], a[i], v[i]): does the wall (a, a + v) stand between the
+ *                          light and the point I + U? */
+int ms_test_agents_apart(const float* me, const float* other, const float* radius, unsigned char* apart, long long count, void* hip_stream);
+int ms_test_wall_beyond(const float* agent, const float* wall, const float* radius, float* reach, unsigned char* beyond, long long count,
+                        void* hip_stream);
+int ms_test_ray_interval(const float* pose, const float* line, int res, float fov, float agent_radius, int groups, int wave, int* first,
+                         int* rays, long long count, void* hip_stream);
+int ms_test_wedge(const float* right, const float* left, int* wa, int* wb, long long count, void* hip_stream);
+int ms_test_cell_at(const float* geom, const float* cell, const float* point, int* index, unsigned char* inside, long long count,
+                    void* hip_stream);
+int ms_test_tex_filter(const float* x, const int* w, int* l, int* r, float* lw, float* rw, long long count, void* hip_stream);
+int ms_test_light_blocked(const float* light, const float* to, const float* a, const float* v, unsigned char* blocked, long long count,
+                          void* hip_stream);
 /* Host instantiation of the light grid's build (ms_bake; accelerates kernels.cu:238-268) for one cell c (row-major in a grid
  * of nx x ny cells of size `cell` from (ox, oy)), over n_walls walls (n_walls x 4 floats: ax, ay, bx, by) and n_lights
  * lights (n_lights x 3: x, y, intensity), HOST memory: words[4] = the lights' 2-bit verdicts as in lg_vals (0 unknown, 1 lit,
@@ -238,7 +265,8 @@ int ms_host_fold_hits(const float* s, const int* line, int n_hits, const int* or
 int ms_host_agents_apart(const float* me, const float* other, float agent_radius);
 /* ... and of the reach cull in front of the agent-wall test (kernels.cu:135-171,202-205): agent = (x, y, vx/fps, vy/fps),
  * wall = (ax, ay, bx, by); 1 = the wall is beyond the agent's reach this step, the test is skipped.  (The host evaluates the
- * foot of the perpendicular with a true division, the kernel with v_rcp_f32: both are lower bounds on the distance.) */
+ * foot of the perpendicular with a true division, the kernel with v_rcp_f32: this is NOT the device's arithmetic.  The device's
+ * verdicts are probed by ms_test_wall_beyond, at the threshold this one bisects to: tests/test_gpu_culls.py.) */
 int ms_host_wall_beyond_reach(const float* agent, const float* wall, float agent_radius);
 /* ... and the reach itself, which also picks the tier of the cell's near list (wg_reach_lo, wg_reach) or the sweep. */
 float ms_host_wall_reach(const float* agent, float agent_radius);
@@ -298,8 +326,11 @@ void ms_host_wallgrid_cell(const float* walls, int n_walls, float ox, float oy, 
                            float near_plane, float reach_lo, float reach, unsigned char* vis, unsigned char* close);
 
 /* ... and of the arcs: the run of steps [*lo8, *hi8] (modulo 256) of directions wall w can be seen in from the cell; and
- * whether a wave whose rightmost / leftmost ray point along (right_x, right_y) / (left_x, left_y) would keep such a wall. */
+ * whether a wave whose rightmost / leftmost ray point along (right_x, right_y) / (left_x, left_y) would keep such a wall;
+ * ms_host_wedge: that wave's own run of steps [*wa8, *wb8].  (The host takes pseudo_angle with a division, render_kernel
+ * pseudo_angle_fast with v_rcp_f32: ms_test_wedge gives the device's run.) */
 void ms_host_wall_arc(float x0, float y0, float x1, float y1, const float* w, int* lo8, int* hi8);
+void ms_host_wedge(float right_x, float right_y, float left_x, float left_y, int* wa8, int* wb8);
 int  ms_host_wedge_meets(float right_x, float right_y, float left_x, float left_y, int lo8, int hi8);
 
 /* Scalar helper exported for tests: sin(pi x), cos(pi x) exactly as the kernels evaluate them. */

@@ -379,6 +379,13 @@ PROTOTYPES = {
     'ms_host_nav_clear_query': (_int, [_p(MsNavClearQuery), _ptr, _ptr, _int, _int, _int, _int]),
     'ms_debug_nav_clear_cull': (_int, [_int]),
     'ms_test_arithmetic': (_int, [_ptr]*7 + [C.c_longlong, _ptr]),
+    'ms_test_agents_apart': (_int, [_ptr]*4 + [C.c_longlong, _ptr]),
+    'ms_test_wall_beyond': (_int, [_ptr]*5 + [C.c_longlong, _ptr]),
+    'ms_test_ray_interval': (_int, [_ptr, _ptr, _int, _flt, _flt, _int, _int, _ptr, _ptr, C.c_longlong, _ptr]),
+    'ms_test_wedge': (_int, [_ptr]*4 + [C.c_longlong, _ptr]),
+    'ms_test_cell_at': (_int, [_ptr]*5 + [C.c_longlong, _ptr]),
+    'ms_test_tex_filter': (_int, [_ptr]*6 + [C.c_longlong, _ptr]),
+    'ms_test_light_blocked': (_int, [_ptr]*5 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),
     'ms_host_agents_apart': (_int, [_f32p, _f32p, _flt]),
@@ -394,6 +401,7 @@ PROTOTYPES = {
     'ms_host_wall_sectors': (None, [_flt]*4 + [_f32p, _i32p, _i32p, _f32p, _i32p]),
     'ms_host_wallgrid_cell': (None, [_ptr, _int, _flt, _flt, _int, _int, _flt, _int, _flt, _flt, _flt, _ptr, _ptr]),
     'ms_host_wall_arc': (None, [_flt]*4 + [_f32p, _i32p, _i32p]),
+    'ms_host_wedge': (None, [_flt]*4 + [_i32p, _i32p]),
     'ms_host_wedge_meets': (_int, [_flt]*4 + [_int, _int]),
     'ms_host_sincospi': (None, [_flt, _f32p, _f32p]),
     'ms_host_bake_point_bin': (_int, [_flt]*4),

@@ -8,6 +8,11 @@
 // numerators sign-flipped by sign(UxV), 0 < n/d < 1  <=>  0 < n' < d' exactly in round-to-nearest
 // (a quotient of two binary32 values can only round to 1 when it is 1), and 0 < s <=> 0 < c'.
 // Only s < .999f needs the quotient itself.
+// Exact while the reference's quotients do not underflow: a numerator that is not zero must exceed 2^-150 |UxV| - below that
+// n/d rounds to zero and the reference sees no shadow where the sign test sees one.  With |UxV| >= 1e-3 and coordinates within
+// 10^6 m (|UxV| < 2^43) that is a numerator below 2^-107: an end of the wall, or the lit point, within some 1e-32 m of the
+// other's line without being on it.  (tests/test_gpu_culls.py: the same bytes as the plain form for coordinates of 2^-10 .. 2^10 and at every
+// threshold; with coordinates down to 1e-30 every disagreement is such a pair - DESIGN.md 2.1.)
 __device__ inline bool light_blocked(P2 I, P2 U, float ax, float ay, float vx, float vy) {
     const P2 V = p2(vx, vy);
     const float UxV = cross(U, V);

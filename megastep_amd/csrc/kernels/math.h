@@ -64,6 +64,12 @@ __host__ __device__ inline float pseudo_angle(float x, float y) {
     const float p = y/(fabsf(x) + fabsf(y));
     return x < 0.f ? 2.f - p : (p < 0.f ? 4.f + p : p);
 }
+// ... with the reciprocal the hardware offers, for the wedge of a render wave's rays: wg_wedge's margin is 10^4 of its roundings
+// wide (ms_test_wedge probes the pair against the binary64 pseudo-angle)
+__device__ inline float pseudo_angle_fast(const float x, const float y) {
+    const float p = y*__builtin_amdgcn_rcpf(fabsf(x) + fabsf(y));
+    return x < 0.f ? 2.f - p : (p < 0.f ? 4.f + p : p);
+}
 // Runs of directions in 1/64ths of a pseudo-angle unit, modulo 256 (wg_arc, where the wall grid is built, has the whole
 // story): the steps wa..wb (inclusive) that hold the directions from a wave's rightmost ray to its leftmost, widened by
 // the same margin as the walls' arcs; and whether two such runs share a step.

@@ -958,11 +958,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(NG > 1 ? M
         s_third_w[lane] = ~0ull;
     }
     // the run of directions of this wave's rays, from its rightmost ray (the last live one) to its leftmost (lane 0's of
-    // the first group)                    (pseudo_angle with the reciprocal the hardware offers: the margin is 10^4 of its roundings wide)
-    auto pseudo_angle_fast = [](const float x_, const float y_) {
-        const float pq_ = y_*__builtin_amdgcn_rcpf(fabsf(x_) + fabsf(y_));
-        return x_ < 0.f ? 2.f - pq_ : (pq_ < 0.f ? 4.f + pq_ : pq_);
-    };
+    // the first group)                    (pseudo_angle_fast: math.h)
     const float pa_first = readlane_f(pseudo_angle_fast(rx, ry), 0);
     float pa_last = readlane_f(pseudo_angle_fast(rx, ry), min(n_live, WAVE) - 1);
     // the rays a list is made for - the wave's (NG = 1), or one span of its groups after the other: first ray, last live

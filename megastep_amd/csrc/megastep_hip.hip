@@ -2,7 +2,7 @@
 //
 // One translation unit: this file holds the switches, the probe macros and the host side of the C-ABI (argument checks,
 // launches); the kernels are in kernels/*.h, included below inside the anonymous namespace - math.h (scalar helpers shared
-// with the ms_host_* test hooks), physics.h, slide.h, rollout.h, scenario.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, percept.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h.
+// with the ms_host_* test hooks), physics.h, slide.h, rollout.h, scenario.h, lighting.h, render.h, bake.h, wallgrid.h, raycast.h, overhead.h, navfield.h, navclear.h, navregion.h, navview.h, percept.h, navpath.h, navpull.h, navbasin.h, navzone.h, navseen.h, navage.h, navwindow.h, navdraw.h; culltest.h (the ms_test_* probes of the culls) last.
 //
 // Thirty-two kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
@@ -209,6 +209,7 @@ struct Probe {
 #include "kernels/navwindow.h"
 #include "kernels/navdraw.h"
 #include "kernels/envlogic.h"
+#include "kernels/culltest.h"
 
 // ------------------------------------------------------------------------------------------------
 // launch geometry (host): what ms_render / ms_step_physics decide before a launch - also behind ms_host_render_plan /
@@ -330,6 +331,28 @@ void step_options_of(const MsMovement* mv, const MsStepExtras* ex, MsMovement& m
     exv.imu_ang_scale = 1.f/exv.imu_ang_scale; exv.imu_speed_scale = 1.f/exv.imu_speed_scale;
 }
 
+// ray_interval's launch-invariant values as ms_render works them out, the per-wave ones as render_kernel does: wave `wave` of
+// 64 x groups rays (ms_host_ray_interval_wide and ms_test_ray_interval)
+RaySpan ray_span_of(const int res, const float fov, const float agent_radius, const int groups, const int wave) {
+    const float half_screen = half_screen_of(fov);
+    const float x_clip = 0.5f*agent_radius/sqrtf(1.f + half_screen*half_screen), c_b = 0.5f*(float)res/half_screen;
+    const int nr = WAVE*groups, r0 = wave*nr;
+    const float c_a = 0.5f*((float)res - 1.f), g0 = (float)r0;
+    const int r_last = (r0 + nr - 1 < res - 1) ? r0 + nr - 1 : res - 1;
+    return RaySpan{x_clip, c_a, c_b, g0, (float)(r_last - r0), (float)nr};
+}
+
+// One element a lane (arithmetic_test_kernel and kernels/culltest.h): `ok` = every pointer the kernel reads is there.
+template <typename... Params, typename... Args>
+int launch_elements(void (*kernel)(Params...), const bool ok, const long long count, void* stream, Args... args) {
+    if (count < 0 || !ok) return MS_EINVAL;
+    if (count == 0) return MS_OK;
+    const long long blocks = (count + WG - 1)/WG;
+    if (blocks > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, args..., count);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -409,26 +432,40 @@ int ms_host_order_fans(int n_fans, const int* costs, int* order) {
 
 int ms_test_arithmetic(const float* n, const float* d, float* q_inrange, float* q_ieee, const float* x, float* r_any, float* r_ieee,
                        long long count, void* stream) {
-    if (count < 0 || ((q_inrange || q_ieee) && !(n && d)) || ((r_any || r_ieee) && !x)) return MS_EINVAL;
-    if (count == 0) return MS_OK;
-    const long long blocks = (count + WG - 1)/WG;
-    if (blocks > 0x7fffffffLL) return MS_EUNSUPPORTED;
-    hipLaunchKernelGGL(arithmetic_test_kernel, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, n, d, q_inrange, q_ieee, x, r_any, r_ieee, count);
-    return launch_status();
+    const bool ok = !((q_inrange || q_ieee) && !(n && d)) && !((r_any || r_ieee) && !x);
+    return launch_elements(arithmetic_test_kernel, ok, count, stream, n, d, q_inrange, q_ieee, x, r_any, r_ieee);
+}
+int ms_test_agents_apart(const float* me, const float* other, const float* radius, unsigned char* apart, long long count, void* stream) {
+    return launch_elements(agents_apart_test_kernel, me && other && radius, count, stream, me, other, radius, apart);
+}
+int ms_test_wall_beyond(const float* agent, const float* wall, const float* radius, float* reach, unsigned char* beyond, long long count,
+                        void* stream) {
+    return launch_elements(wall_beyond_test_kernel, agent && wall && radius, count, stream, agent, wall, radius, reach, beyond);
+}
+int ms_test_ray_interval(const float* pose, const float* line, int res, float fov, float agent_radius, int groups, int wave, int* first,
+                         int* rays, long long count, void* stream) {
+    // (a wave of a launch ms_render could make: config_ok's ranges, NG of 1, 2 or 4, a run of rays that starts below res)
+    if (!(res > 0 && fov > 0.f && fov < 180.f && agent_radius > 0.f && (groups == 1 || groups == 2 || groups == 4) && wave >= 0 &&
+          (long long)wave*WAVE*groups < res)) return MS_EINVAL;
+    return launch_elements(ray_interval_test_kernel, pose && line, count, stream, pose, line, ray_span_of(res, fov, agent_radius, groups, wave), first, rays);
+}
+int ms_test_wedge(const float* right, const float* left, int* wa, int* wb, long long count, void* stream) {
+    return launch_elements(wedge_test_kernel, right && left, count, stream, right, left, wa, wb);
+}
+int ms_test_cell_at(const float* geom, const float* cell, const float* point, int* index, unsigned char* inside, long long count, void* stream) {
+    return launch_elements(cell_at_test_kernel, geom && cell && point, count, stream, geom, cell, point, index, inside);
+}
+int ms_test_tex_filter(const float* x, const int* w, int* l, int* r, float* lw, float* rw, long long count, void* stream) {
+    return launch_elements(tex_filter_test_kernel, x && w, count, stream, x, w, l, r, lw, rw);
+}
+int ms_test_light_blocked(const float* light, const float* to, const float* a, const float* v, unsigned char* blocked, long long count,
+                          void* stream) {
+    return launch_elements(light_blocked_test_kernel, light && to && a && v, count, stream, light, to, a, v, blocked);
 }
 
 void ms_host_ray_interval_wide(const float* pose, const float* line, int res, float fov, float agent_radius, int groups, int wave,
                                int* first, int* count) {
-    // (the launch-invariant values as ms_render works them out, the per-wave ones as render_kernel does)
-    const float half_screen = half_screen_of(fov);
-    const float x_clip = 0.5f*agent_radius/sqrtf(1.f + half_screen*half_screen), c_b = 0.5f*(float)res/half_screen;
-    const int nr = WAVE*groups, r0 = wave*nr;
-    const float c_a = 0.5f*((float)res - 1.f), g0 = (float)r0;
-    const int r_last = (r0 + nr - 1 < res - 1) ? r0 + nr - 1 : res - 1;
-    const float last_local = (float)(r_last - r0);
-    float xa, ya, xb, yb;
-    agent_frame(pose[3], pose[2], line[0] - pose[0], line[1] - pose[1], line[2] - pose[0], line[3] - pose[1], xa, ya, xb, yb);
-    ray_interval(xa, ya, xb, yb, true, x_clip, c_a, c_b, g0, last_local, *first, *count, (float)nr);
+    ray_interval_of(pose, line, ray_span_of(res, fov, agent_radius, groups, wave), *first, *count);
 }
 void ms_host_ray_interval(const float* pose, const float* line, int res, float fov, float agent_radius, int group, int* first, int* count) {
     ms_host_ray_interval_wide(pose, line, res, fov, agent_radius, 1, group, first, count);
@@ -526,9 +563,12 @@ void ms_host_wall_sectors(float x0, float y0, float x1, float y1, const float* o
 void ms_host_wall_arc(float x0, float y0, float x1, float y1, const float* w, int* lo8, int* hi8) {
     wg_arc(WgCell{x0, y0, x1, y1}, make_float4(w[0], w[1], w[2], w[3]), *lo8, *hi8);
 }
+void ms_host_wedge(float right_x, float right_y, float left_x, float left_y, int* wa8, int* wb8) {
+    wg_wedge(pseudo_angle(right_x, right_y), pseudo_angle(left_x, left_y), *wa8, *wb8);
+}
 int ms_host_wedge_meets(float right_x, float right_y, float left_x, float left_y, int lo8, int hi8) {
     int wa8, wb8;
-    wg_wedge(pseudo_angle(right_x, right_y), pseudo_angle(left_x, left_y), wa8, wb8);
+    ms_host_wedge(right_x, right_y, left_x, left_y, &wa8, &wb8);
     return wg_arcs_meet(lo8, hi8, wa8, wb8) ? 1 : 0;
 }
 

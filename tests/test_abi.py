@@ -115,6 +115,29 @@ def test_bad_arguments_are_rejected_before_any_launch():
     assert h.ms_overhead(C.byref(sc), C.byref(ag), C.byref(_lib.MsOverhead()), None) == -1
 
 
+def test_the_cull_probes_refuse_what_cannot_be_launched():
+    """ms_test_*: a NULL input, a negative count and (the ray intervals) a shape no render launch has are MS_EINVAL; no element is
+    no launch.  (Host memory stands in for the device's: nothing here gets as far as a kernel.)"""
+    from megastep_amd import _lib
+    h = _lib.lib()
+    buf = np.zeros(16, np.float32)
+    p = C.c_void_p(buf.ctypes.data)
+    for name, n_in, n_out in (('agents_apart', 3, 1), ('wall_beyond', 3, 2), ('wedge', 2, 2), ('cell_at', 3, 2), ('tex_filter', 2, 4),
+                              ('light_blocked', 4, 1)):
+        fn = getattr(h, 'ms_test_' + name)
+        assert fn(*[p]*n_in, *[None]*n_out, 0, None) == 0, name
+        assert fn(*[p]*n_in, *[None]*n_out, -1, None) == -1, name
+        for k in range(n_in):
+            assert fn(*[None if j == k else p for j in range(n_in)], *[None]*n_out, 0, None) == -1, (name, k)
+    ri = h.ms_test_ray_interval
+    assert ri(p, p, 64, 130., .1, 1, 0, None, None, 0, None) == 0 and ri(p, p, 512, 130., .1, 4, 1, None, None, 0, None) == 0
+    assert ri(None, p, 64, 130., .1, 1, 0, None, None, 0, None) == -1 and ri(p, None, 64, 130., .1, 1, 0, None, None, 0, None) == -1
+    assert ri(p, p, 64, 130., .1, 1, 0, None, None, -1, None) == -1
+    for res, fov, radius, groups, wave in ((0, 130., .1, 1, 0), (64, 180., .1, 1, 0), (64, 0., .1, 1, 0), (64, 130., 0., 1, 0),
+                                           (64, 130., .1, 3, 0), (64, 130., .1, 1, 1), (64, 130., .1, 1, -1), (512, 130., .1, 4, 2)):
+        assert ri(p, p, res, fov, radius, groups, wave, None, None, 0, None) == -1, (res, fov, radius, groups, wave)
+
+
 def test_kernel_sincospi_is_bitwise_the_oracles(oracle):
     """The product's sin/cos(pi x) (host instantiation of the device function) against the oracle's restatement."""
     from megastep_amd import _lib

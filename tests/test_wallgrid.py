@@ -13,6 +13,7 @@ import zlib
 import numpy as np
 import pytest
 from megastep_amd import _lib, cubicasa, scene, toys, core
+from tests import cull_samples
 
 CELL, NEAR, REACH_LO, REACH = .25, .12, .7, 1.3
 
@@ -271,24 +272,13 @@ def test_agents_the_cull_calls_apart_cannot_collide(oracle):
     oracle's collision_cc (kernels.cu:119-133) must leave x = 1 - at every distance around the threshold, relative
     velocities from a sprint down to 1e-12 a step (project()'s `+ 1e-6` stretches the reach of a pair that moves almost in
     step), pairs in perfect step, coordinates far from the origin, and a NaN or an infinity here and there (apart only when in step)."""
-    rng = np.random.RandomState(0)
     lib, cc = _lib.lib(), oracle.lib().oracle_collision_cc
     f32p = C.POINTER(C.c_float)
-    n, culled, hits, hits_kept = 60000, 0, 0, 0
+    mes, others, radii = cull_samples.agent_pairs()
+    n, culled, hits, hits_kept = len(mes), 0, 0, 0
+    assert n == 60000
     for i in range(n):
-        R = float(np.float32(10.**rng.uniform(-2, 0)))
-        base = rng.uniform(-1, 1, 2)*10.**rng.uniform(0, 3)
-        common = rng.uniform(-1, 1, 2)*10.**rng.uniform(-3, 1)*(rng.rand() < .8)
-        rel = 10.**rng.uniform(-12, .7)
-        a = rng.uniform(0, 2*np.pi)
-        dv = rel*np.array([np.cos(a), np.sin(a)])*(rng.rand() < .95)             # 5 %: in perfect step
-        # distances around what the pair can cover: |dv| + 2R, scaled by 0.2 .. 30; now and then much closer / farther
-        D = (rel + 2*R)*10.**rng.uniform(-.7, 1.5) if rng.rand() < .8 else 10.**rng.uniform(-3, 2)
-        b = a + rng.normal(0, .5) if rng.rand() < .7 else rng.uniform(0, 2*np.pi)   # mostly closing in on each other
-        me = np.array([*base, *(common + dv)], np.float32)
-        other = np.array([*(base + D*np.array([np.cos(b), np.sin(b)])), *common], np.float32)
-        if i % 997 == 0: me[rng.randint(4)] = [np.nan, np.inf, -np.inf][i % 3]
-        if i % 1009 == 0: other[rng.randint(4)] = [np.nan, np.inf, -np.inf][i % 3]
+        me, other, R = mes[i], others[i], float(radii[i])
         apart = lib.ms_host_agents_apart(me.ctypes.data_as(f32p), other.ctypes.data_as(f32p), R)
         x = cc(*[float(v) for v in me], *[float(v) for v in other], R)
         hits += x < 1
@@ -307,28 +297,13 @@ def test_walls_the_cull_calls_beyond_reach_cannot_stop_the_agent(oracle):
     every such pair the oracle's collision_cs (kernels.cu:135-171) must leave x = 1 - walls at every distance around the
     reach, agents from a sprint down to 1e-12 a step (project()'s `+ 1e-6`: a crawling agent is stopped by walls metres
     away), walls from 10 m down to a micrometre (its `+ 1e-6` on the wall's length), a NaN or an infinity now and then."""
-    rng = np.random.RandomState(1)
     lib, cs = _lib.lib(), oracle.lib().oracle_collision_cs
     f32p = C.POINTER(C.c_float)
-    n, culled, hits, hits_kept = 80000, 0, 0, 0
+    agents, walls, radii = cull_samples.agents_and_walls()
+    n, culled, hits, hits_kept = len(agents), 0, 0, 0
+    assert n == 80000
     for i in range(n):
-        R = float(np.float32(10.**rng.uniform(-2, 0)))
-        p = rng.uniform(-1, 1, 2)*10.**rng.uniform(0, 3)
-        speed = 10.**rng.uniform(-12, .7)*(rng.rand() < .97)                     # 3 %: standing still
-        a = rng.uniform(0, 2*np.pi)
-        v = speed*np.array([np.cos(a), np.sin(a)])
-        reach = (speed + 2*R)*(1 + 1e-6/max(speed, 1e-30))**2 if speed > 0 else 2*R
-        D = min(reach, 1e4)*10.**rng.uniform(-.7, 1.) if rng.rand() < .8 else 10.**rng.uniform(-3, 2)
-        b = a + rng.normal(0, .6) if rng.rand() < .7 else rng.uniform(0, 2*np.pi)   # mostly ahead of the agent
-        mid = p + D*np.array([np.cos(b), np.sin(b)])
-        length = 10.**rng.uniform(-6, 1)
-        c = rng.uniform(0, 2*np.pi)
-        half = .5*length*np.array([np.cos(c), np.sin(c)])
-        shift = rng.uniform(-1, 1)*half*(rng.rand() < .5)                         # the nearest point: an end as often as not
-        agent = np.array([*p, *v], np.float32)
-        wall = np.array([*(mid - half + shift), *(mid + half + shift)], np.float32)
-        if i % 997 == 0: agent[rng.randint(4)] = [np.nan, np.inf, -np.inf][i % 3]
-        if i % 1009 == 0: wall[rng.randint(4)] = [np.nan, np.inf, -np.inf][i % 3]
+        agent, wall, R = agents[i], walls[i], float(radii[i])
         beyond = lib.ms_host_wall_beyond_reach(agent.ctypes.data_as(f32p), wall.ctypes.data_as(f32p), R)
         x = cs(*[float(t) for t in agent], *[float(t) for t in wall], R)
         hits += x < 1
@@ -342,47 +317,22 @@ def test_walls_the_cull_calls_beyond_reach_cannot_stop_the_agent(oracle):
     assert culled > n//4, 'and the cull does cull'
 
 
-def _groups_for(res):
-    """How many 64-ray groups a wave may be given at this resolution (render_kernel's NG; ms_debug_ray_groups)."""
-    return 4 if res > 128 else 2 if res > 64 else 1
+_groups_for = cull_samples.groups_for
 
 
-@pytest.mark.parametrize('res,fov', [(64, 130.), (512, 130.), (200, 60.), (7, 170.), (1, 90.), (128, 165.)])
+@pytest.mark.parametrize('res,fov', cull_samples.RAY_SHAPES)
 def test_no_ray_outside_a_lines_interval_hits_it(oracle, res, fov):
     """render_kernel's pass 1 turns a line into an interval of the wave's rays and intersects it with no others
     (DESIGN.md 3.2): every ray the oracle's raycast (kernels.cu:352-377, which tries them all) lands on the line must be
     inside - lines near and far, behind the agent, through its near plane, across the edges of the fan, end-on, tiny."""
-    from megastep_amd import scene as scene_
-    rng = np.random.RandomState(res)
     lib = _lib.lib()
-    E, M = 3000, len(scene_.agent_model())
-    radius = float(np.float32(.15/2**.5))
-    pos = rng.uniform(-5, 5, (E, 2)).astype(np.float32)
-    ang = rng.uniform(-180, 180, E).astype(np.float32)
-    # a wall somewhere around the agent: its middle at a log-uniform distance in a direction anywhere, any orientation
-    dist = 10.**rng.uniform(-1.3, 1.3, E)
-    where = rng.uniform(0, 2*np.pi, E)
-    mid = pos + (dist*np.array([np.cos(where), np.sin(where)])).T
-    length = 10.**rng.uniform(-3, 1.3, E)
-    along = np.where(rng.rand(E) < .3, where + rng.normal(0, .02, E), rng.uniform(0, 2*np.pi, E))   # a third: end-on
-    half = (.5*length*np.array([np.cos(along), np.sin(along)])).T
-    walls = np.concatenate([mid - half, mid + half], 1).astype(np.float32).reshape(E, 1, 2, 2)
-    model = scene_.agent_model()
-    lines = np.concatenate([np.tile(model[None], (E, 1, 1, 1)), walls], 1)              # (agent rows are redrawn by the oracle)
-    texw = np.full(E*(M + 1), 4, np.int32)
-    S = oracle.Scene(dict(n_agents=1, model=model, lights_vals=np.zeros((0, 3)), lights_widths=[0]*E,
-                          lines_vals=lines.reshape(-1, 2, 2), lines_widths=[M + 1]*E,
-                          textures_vals=np.full((texw.sum(), 3), .5), textures_widths=texw))
-    ag = dict(angles=ang.reshape(E, 1), positions=pos.reshape(E, 1, 2), angvelocity=np.zeros((E, 1), np.float32),
-              velocity=np.zeros((E, 1, 2), np.float32))
-    idx = oracle.render(S, ag, oracle.config(radius, res, fov, 10))['indices'][:, 0]
+    poses, lines, idx, M, radius = cull_samples.lines_in_view(oracle, res, fov)
+    E = len(poses)
+    assert E == 3000
     f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int)
     hits = covered = 0
     for e in range(E):
-        s_, c_ = C.c_float(), C.c_float()
-        lib.ms_host_sincospi(float(np.float32(ang[e])/np.float32(180.)), C.byref(s_), C.byref(c_))
-        pose = np.array([pos[e, 0], pos[e, 1], s_.value, c_.value], np.float32)
-        line = walls[e].reshape(4)
+        pose, line = poses[e], lines[e]
         # a wave serves 64 rays, or - as ms_render picks above 64 rays - 128 or 256 of them (render_kernel's NG)
         for groups in sorted({1, _groups_for(res)}):
             W = 64*groups

@@ -290,17 +290,21 @@ def assert_subset_bits(core, sub, p, r):
     assert_render_bits(None, R, sub.render())
 
 
-def obstructed(I, C, walls):
-    """obstructed() of kernels.cu:253-257 in float32 numpy: (n_points, n_walls) booleans."""
+def obstructed_pairs(I, U, a, v):
+    """obstructed() of kernels.cu:253-257 in float32 numpy, pair by pair: does the wall (a, a + v) stand between the light I and
+    the point I + U? Arrays (..., 2) of float32 that broadcast against each other; booleans of the broadcast shape."""
     f = np.float32
-    a, v = walls[None, :, 0], (walls[:, 1] - walls[:, 0])[None]
-    U = (C - I)[:, None]
-    d = U[..., 0]*v[..., 1] - U[..., 1]*v[..., 0]
-    PQ = a - I
-    with np.errstate(divide='ignore', invalid='ignore'):
-        s = (PQ[..., 0]*v[..., 1] - PQ[..., 1]*v[..., 0])/d
+    with np.errstate(all='ignore'):
+        d = U[..., 0]*v[..., 1] - U[..., 1]*v[..., 0]
+        PQ = a - I
+        s =(PQ[..., 0]*v[..., 1] - PQ[..., 1]*v[..., 0])/d
         t = (PQ[..., 0]*U[..., 1] - PQ[..., 1]*U[..., 0])/d
-    return (np.abs(d) >= f(1e-3)) & (t > 0) & (t < 1) & (s > 0) & (s < f(.999))
+        return (np.abs(d) >= f(1e-3)) & (t > 0) & (t < 1) & (s > 0) & (s < f(.999))
+
+
+def obstructed(I, C, walls):
+    """... of n_points points C from one light I against n_walls walls: (n_points, n_walls) booleans."""
+    return obstructed_pairs(I, (C - I)[:, None], walls[None, :, 0], (walls[:, 1] - walls[:, 0])[None])
 
 
 # ---- worlds that the GPU suite and the reference pin (tests/test_reference_pin.py) both run ---------------------------
