@@ -115,6 +115,57 @@ def test_bad_arguments_are_rejected_before_any_launch():
     assert h.ms_overhead(C.byref(sc), C.byref(ag), C.byref(_lib.MsOverhead()), None) == -1
 
 
+def test_the_step_entries_refuse_a_broken_near_list_alike():
+    """A scenery whose wall grid carries near lists carries all of them, 16-byte aligned: ms_step_physics, ms_slide_physics,
+    ms_rollouts and ms_scenarios hold it to one rule (near_lists_ok, csrc/host/step.h).  One env of one agent, every other argument a
+    valid dummy - host memory stands in for the device's, so the sound call is never made: nothing here may get as far as a launch."""
+    from megastep_amd import _lib
+    h = _lib.lib()
+    buf = np.zeros(64, np.float32)
+    base = buf.ctypes.data + (-buf.ctypes.data) % 16
+    p, odd = C.c_void_p(base), C.c_void_p(base + 8)                      # (16-byte aligned; 8 bytes off it)
+    cfg = _lib.MsConfig(.1, 64, 130., 10.)
+    ag = _lib.MsAgents(angles=p, positions=p, angvelocity=p, velocity=p)
+    sl = _lib.MsSlide(bounce=0.)
+    plans = dict(horizon=1, actions=p, table=p, n_actions=1, keep=0., positions=p, angles=p, velocity=p, angvelocity=p, progress=p,
+                 stops=p, first_stop=p)
+    ro, sq = _lib.MsRollouts(n_candidates=1, **plans), _lib.MsScenarios(n_scenarios=1, **plans)
+    entries = {
+        'ms_step_physics': lambda sc: h.ms_step_physics(C.byref(sc), C.byref(ag), None, None, p, C.byref(cfg), None),
+        'ms_slide_physics': lambda sc: h.ms_slide_physics(C.byref(sc), C.byref(ag), None, None, C.byref(sl), p, C.byref(cfg), None),
+        'ms_rollouts': lambda sc: h.ms_rollouts(C.byref(sc), C.byref(ag), C.byref(ro), C.byref(cfg), None),
+        'ms_scenarios': lambda sc: h.ms_scenarios(C.byref(sc), C.byref(ag), C.byref(sq), C.byref(cfg), None)}
+    defects = {'no near rows': dict(wg_near_rows=None), 'near rows off 16 bytes': dict(wg_near_rows=odd),
+               'geometry off 16 bytes': dict(wg_geom=odd), 'no cell size': dict(wg_cell=0.)}
+    for name, call in entries.items():
+        for defect, fields in defects.items():
+            sc = _lib.MsScenery(n_envs=1, n_agents=1, n_model=1, lines_vals=p, lines_widths=p, lines_starts=p, model=p,
+                                wg_cells=p, wg_starts=p, wg_geom=p, wg_cell=1., wg_near_rows=p)
+            for field, value in fields.items():
+                setattr(sc, field, value)
+            assert call(sc) == -1, (name, defect)
+
+
+def test_the_stamp_covers_the_host_files(monkeypatch, tmp_path):
+    """The stamp `make` writes next to the library is _source_hash() of the sources it was built from, and the hash takes in
+    csrc/host/*.h: an edit there can never run against yesterday's library."""
+    import shutil
+    from megastep_amd import _lib
+    monkeypatch.setattr(_lib, 'LIB_PATH', os.path.join(_lib.CSRC, 'libmegastep_hip.so'))
+    _lib.build()
+    assert open(_lib.LIB_PATH + '.srchash').read().strip() == _lib._source_hash()
+    built = _lib._source_hash()
+    copy = str(tmp_path / 'csrc')
+    shutil.copytree(_lib.CSRC, copy, ignore=shutil.ignore_patterns('*.so', '*.srchash', '.build.lock'))
+    monkeypatch.setattr(_lib, 'CSRC', copy)
+    assert _lib._source_hash() == built                                  # (the copy is faithful ...)
+    hosts = sorted(os.listdir(os.path.join(copy, 'host')))
+    assert hosts and all(name.endswith('.h') for name in hosts)
+    with open(os.path.join(copy, 'host', hosts[-1]), 'a') as f:
+        f.write('// edited\n')
+    assert _lib._source_hash() != built                                  # (... and a comment in a host file is a new hash)
+
+
 def test_the_cull_probes_refuse_what_cannot_be_launched():
     """ms_test_*: a NULL input, a negative count and (the ray intervals) a shape no render launch has are MS_EINVAL; no element is
     no launch.  (Host memory stands in for the device's: nothing here gets as far as a kernel.)"""

@@ -398,7 +398,7 @@ def test_agents_without_a_table_step_and_render_the_same_bits():
 # 3. the followers under orders that are not the identity
 # ------------------------------------------------------------------------------------------------------------------------
 MAX_DEPTH = 7.
-# Which instantiation a request reaches (render_prepare / render_enqueue, megastep_hip.hip): colour = screen or pooled RGB wanted;
+# Which instantiation a request reaches (render_prepare / render_enqueue, csrc/host/render.h): colour = screen or pooled RGB wanted;
 # no colour -> <1,0,1,0>; colour and not one per-ray plane -> <2,1,1,0>; colour with pooled outputs, books or some plane missing ->
 # <1,1,1,0>; all five planes and nothing else -> <0,1,1,0>, and without a light grid (several agents an env) dynlight_kernel
 # behind it, whose queue names the fans it has to light. All at one ray group a wave: ms_debug_last_render_groups() == 1.
