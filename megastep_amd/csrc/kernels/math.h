@@ -1,6 +1,6 @@
 // kernels/math.h -- scalar math and the small helpers the kernels share (and ms_host_* instantiate on the host).
-// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, in this order: math,
-// physics, lighting, render, bake, wallgrid); not a header to compile on its own.
+// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, first: step.h,
+// physics.h and the other families follow); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // Scalar math shared by the kernels (device) and ms_host_sincospi (host).
 // ------------------------------------------------------------------------------------------------
@@ -284,6 +284,12 @@ __device__ inline float wave_max_f(float x) {                          // all-la
     return __int_as_float(__builtin_amdgcn_readlane(v, 63));
 }
 __device__ inline uint32_t f_bits(float f) { return __float_as_uint(f); }
+// what the wave's lanes wrote to LDS before it, every lane reads after it
+__device__ inline void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // One env's rows of `lines` behind a buffer descriptor.  A chunk of 64 rows is then ONE instruction with no address
 // arithmetic in front of it - `buffer_load_dwordx4` takes the lane's byte offset from a VGPR that never changes and the

@@ -1,6 +1,6 @@
-// kernels/physics.h -- physics_kernel<MOVE, EXTRA>.
-// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, in this order: math,
-// physics, lighting, render, bake, wallgrid); not a header to compile on its own.
+// kernels/physics.h -- physics_kernel<MOVE, EXTRA, PACK>, and the fan schedule's sort waves in front of it.
+// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, behind math.h and step.h,
+// whose rules and pieces it calls); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // physics                                                                    kernels.cu:179-230
 // ------------------------------------------------------------------------------------------------
@@ -20,47 +20,6 @@
 constexpr int PHYS_AHEAD = 4;          // wall chunks in flight per wave (six: no faster at 300 walls, 12 % slower at 1000 - fewer waves fit)
 constexpr int PHYS_FEW = 4;            // up to this many agents per env, their reach boxes ride in scalar registers
 constexpr int PHYS_PAIRS = (PHYS_FEW + 1)*WAVE;   // capacity of a wave's (wall, agent) pair list: a flush's worth + one chunk's worth for PHYS_FEW agents
-
-// The per-agent rules of a step, on values: physics_kernel and the one-launch step (render.h) call them with loads, stores and lanes of their own.
-// the spawn pose of agent i, if it is to be respawned (modules.py:321-326)
-__host__ __device__ inline void spawn_pose(const MsStepExtras& ex, const int i, float2& p, float& ang) {
-    const long long c = min(max(ex.respawn_choice[i], 0ll), (long long)ex.n_spawns - 1);
-    p = reinterpret_cast<const float2*>(ex.spawn_positions)[(size_t)i*ex.n_spawns + c];
-    ang = ex.spawn_angles[(size_t)i*ex.n_spawns + c];
-}
-// agent i's new age (modules.py:361-366): 0 if `reset` (its respawn mask) is set or comes out set because it has lived its span
-__host__ __device__ inline int lifespan_tick(const MsStepExtras& ex, const int i, bool& reset) {
-    const int life = ex.lifespans[i] + 1;
-    reset = reset | (life >= ex.max_lifespans[i]);
-    return reset ? 0 : life;
-}
-// the movement modules' velocity update (modules.py:57-66,106-118): the action's delta turned into the global frame, blended in
-__host__ __device__ inline void move_velocity(const float keep, const float ang, const float dx, const float dy, const float dw, float2& v, float& w) {
-    const float a_ = 0.017453292519943295f*ang;                         // np.pi/180*angles, in binary32 like torch
-    const float s_ = sinf(a_), c_ = cosf(a_);
-    const float gx = c_*dx - s_*dy, gy = s_*dx + c_*dy;
-    if (keep == 0.f) { w = dw; v = make_float2(gx, gy); }
-    else { w = keep*w + dw; v = make_float2(keep*v.x + gx, keep*v.y + gy); }
-}
-// how many of a cell's near walls (its header hdr) an agent of this reach meets: the short tier if the reach is within wg_reach_lo
-__host__ __device__ inline int near_count(const uint4 hdr, const float reach, const float reach_lo) {
-    return (int)((reach <= reach_lo) ? (hdr.w & 0xffffu) : (hdr.w >> 16));
-}
-// the integration epilogue (kernels.cu:224-227): the fraction x of the step the agent can take; stopped (x < 1): at rest
-__host__ __device__ inline bool integrate(const float x, const float fps, float2& p, float& ang, float2& v, float& w) {
-    p.x = p.x + x*v.x/fps;
-    p.y = p.y + x*v.y/fps;
-    ang = normalize_degrees(ang + x*w/fps);
-    const bool stopped = x < 1;
-    if (stopped) { v = make_float2(0.f, 0.f); w = 0.f; }
-    return stopped;
-}
-// the IMU reading (modules.py:263-270, to_local_frame :24-31); the scales are reciprocals: ATen's `a * (1.f/b)` for tensor / scalar
-__host__ __device__ inline float3 imu_reading(const MsStepExtras& ex, const float ang, const float2 v, const float w) {
-    const float a_ = 0.017453292519943295f*ang;                         // (as move_velocity)
-    const float s_ = sinf(a_), c_ = cosf(a_);
-    return make_float3(w*ex.imu_ang_scale, (c_*v.x + s_*v.y)*ex.imu_speed_scale, (-s_*v.x + c_*v.y)*ex.imu_speed_scale);
-}
 
 // ------------------------------------------------------------------------------------------------
 // the fan schedule (MsAgents.schedule): last frame's render costs sorted into this frame's starting order
@@ -106,17 +65,13 @@ __device__ inline void fan_sort_wave(const FanSort fs, const int block, const in
     __builtin_amdgcn_wave_barrier();
     #pragma unroll
     for (int j = 0; j < FAN_SORT_EACH; j++) if (j*WAVE + lane < count) atomicAdd(&s_cnt[cls[j]], 1);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     // lane j looks after class 63 - j: the slowest class takes the first ranks
     const int mine = s_cnt[FAN_CLASSES - 1 - lane];
     const int incl = wave_scan_add(mine);
     __builtin_amdgcn_wave_barrier();
     s_cnt[FAN_CLASSES - 1 - lane] = incl - mine;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     #pragma unroll
     for (int j = 0; j < FAN_SORT_EACH; j++) {
         const int i = j*WAVE + lane;
@@ -206,6 +161,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
     if constexpr (EXTRA == 1) {
         for (int t = lane; t < A; t += WAVE) {
             const int i = nA + t;
+            // (step_books, kernels/step.h, in this kernel's own text: the call changes its instructions)
             bool reset = ex.respawn_mask && ex.respawn_mask[i];
             if (ex.lifespans) {
                 ex.lifespans[i] = lifespan_tick(ex, i, reset);
@@ -228,6 +184,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
     if constexpr (MOVE == 1) {
         // (the table - seven actions, three floats each - rides in the lanes of one register, asked for up front: looked
         // up in memory by the action it would be a round trip behind the actions' own)
+        // (ActionTable, kernels/step.h, in this kernel's own text)
         const bool small_table = 3*mv.n_actions <= WAVE;
         const float tab = mv.table[min(lane, 3*mv.n_actions - 1)];
         auto moved = [&](const int i, const float ang, float2& v, float& w, const float dx, const float dy, const float dw) {
@@ -238,6 +195,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         {
             // (every lane looks an action up - its agent's, or the last agent's again: the lanes exchange table entries, which
             // only works among lanes that are all there)
+            // (action_row, kernels/step.h, in this kernel's own text - here and for the agents beyond the first 64)
             const long long act = min(max(mv.actions[nA + min(lane, A - 1)], 0ll), (long long)mv.n_actions - 1);
             float dx, dy, dw;
             if (small_table) { dx = __shfl(tab, 3*(int)act, WAVE); dy = __shfl(tab, 3*(int)act + 1, WAVE); dw = __shfl(tab, 3*(int)act + 2, WAVE); }
@@ -255,6 +213,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
     float my_reach = 0.f;
     for (int t = lane; t < A; t += WAVE) {
         const float2 pp = (t == lane) ? my_p : pos2[nA + t], mm = (t == lane) ? my_v : vel2[nA + t];
+        // (step_task, kernels/step.h, in this kernel's own text - and the reach box, from the reach as it comes)
         const P2 p0 = p2(pp.x, pp.y);
         const P2 v0 = p2(mm.x, mm.y)/fps;
         const float reach = wall_reach(p0, v0, agent_radius);
@@ -265,9 +224,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         s_task[t] = make_float4(p0.x, p0.y, v0.x, v0.y);
         s_prog[t] = f_bits(1.f);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     PROBE_AT(1, my_box.x)                                                // agent state has arrived
     // ... and the agent-agent tests (kernels.cu:193-200), one ordered pair per lane
     // (behind agents_apart(): agents of one env are mostly rooms apart, and then no lane of the wave goes into the test at
@@ -275,6 +232,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
     for (int i = lane; i < A*A1; i += WAVE) {                            // (t, one of its env's agents)
         const int t = div_by(i, by_a), d1 = (PACK ? div_by(t, by_a)*A1 : 0) + i - t*A1;
         if (d1 != t) {
+            // (meet_agent and fold_least, kernels/step.h, in this kernel's own text)
             const float4 me = s_task[t], o = s_task[d1];
             if (!agents_apart(me, o, agent_radius)) {
                 const float x = collision_cc(p2(me.x, me.y), p2(me.z, me.w), p2(o.x, o.y), p2(o.z, o.w), agent_radius);
@@ -285,6 +243,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
 
     // one (wall, agent) pair: the reach cull on the true distance, then the reference's test (kernels.cu:135-171,202-205)
     auto meet = [&](const float4 u, const int t) {
+        // (meet_wall and fold_least, kernels/step.h, in this kernel's own text)
         const float4 tk = s_task[t];
         if (!wall_beyond(tk, u, s_reach2[t])) {
             const float x = collision_cs(p2(tk.x, tk.y), p2(tk.z, tk.w), p2(u.x, u.y), p2(u.z, u.w), agent_radius);
@@ -293,10 +252,9 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
     };
     // (wall, agent) pairs collect in an LDS list with room for one agent's worth of a chunk on top of a flush's worth.
     int cnt = 0;
+    // (PairList::drain, kernels/step.h, in this kernel's own text: one barrier behind the loop, no fences)
     auto flush = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         #pragma unroll 1
         for (int p0 = 0; p0 < cnt; p0 += WAVE) {
             if (p0 + lane < cnt) meet(s_wall[p0 + lane], s_tag[p0 + lane]);
@@ -315,6 +273,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         int count = 0;
         bool ok = A <= WAVE;
         if (lane < A) {
+            // (near_list, kernels/step.h, in this kernel's own text)
             const float4 me = s_task[lane];
             bool inside;
             const uint4 hdr = reinterpret_cast<const uint4*>(sc.wg_cells)[wg_start_n + wg_cell_at(wg_geom_n, sc.wg_cell, me.x, me.y, inside)];
@@ -341,6 +300,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
             // instead of once per round over the few lanes that got through (physics 9.0 -> 8.7 us at the headline shape).
             for (int p0 = 0; p0 < P; p0 += WAVE) {
                 const int q = p0 + lane;
+                // (deal_pair, kernels/step.h, in this kernel's own text)
                 int t = 0;
                 for (int j = 0; j < A - 1; j++) t += (__builtin_amdgcn_readlane(incl, j) <= q) ? 1 : 0;   // whose list is pair q in?
                 const int k = q - __shfl(excl, t, WAVE);
@@ -354,6 +314,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
                         u = reinterpret_cast<const float4*>(sc.wg_near_rows)[at];
                         in_reach = !wall_beyond(s_task[t], u, s_reach2[t]);
                     }
+                    // (PairList::append, kernels/step.h, in this kernel's own text: the sweep below appends to the same list by masks)
                     const unsigned long long m = __ballot(in_reach);
                     if (cnt > PHYS_PAIRS - WAVE) flush();
                     if (in_reach) {
@@ -456,12 +417,13 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         if (t != lane) { p = pos2w[i]; v = vel2w[i]; w_ = ag.angvelocity[i]; ang = ag.angles[i]; }
         bool stopped = integrate(x, fps, p, ang, v, w_);
         if constexpr (EXTRA == 1) {
-            if (ex.spawn_positions && ex.respawn_after && ex.respawn_mask && ex.respawn_mask[i]) {
+            if (respawns_after(ex, i)) {
                 spawn_pose(ex, i, p, ang);
                 v = make_float2(0.f, 0.f); w_ = 0.f;
                 stopped = true;
             }
         }
+        // (step_store, kernels/step.h, in this kernel's own text: `progress` goes out between the velocity and the IMU)
         pos2w[i] = p;
         ag.angles[i] = ang;
         if (ag.headings) {                                   // what render_prep_kernel would compute, one launch earlier
@@ -475,12 +437,7 @@ __global__ __launch_bounds__(WAVE) void physics_kernel(
         }
         progress[i] = x;
         if constexpr (EXTRA == 1) {
-            if (ex.imu) {
-                const float3 m = imu_reading(ex, ang, v, w_);
-                ex.imu[3*i] = m.x;
-                ex.imu[3*i + 1] = m.y;
-                ex.imu[3*i + 2] = m.z;
-            }
+            imu_store(ex, i, ang, v, w_);
         }
     }
     PROBE_DONE(n)

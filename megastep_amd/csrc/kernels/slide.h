@@ -1,6 +1,6 @@
 // kernels/slide.h -- physics_slide_kernel<MOVE, EXTRA>: the physics step with a second contact phase (MsSlide).
-// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, behind math.h and physics.h,
-// whose per-agent rules it chains, and in front of rollout.h, which chains its); not a header to compile on its own.
+// Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, behind step.h, whose rules and
+// pieces it calls, and physics.h, and in front of rollout.h, which chains its rule); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // sliding contacts                                             (MsSlide; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
@@ -91,9 +91,19 @@ __host__ __device__ inline bool slide_finish(const SlideContact& c, const float 
     return false;
 }
 
-// the row of the table an action means: clamped, as physics_kernel's prologue clamps it
-__host__ __device__ inline int table_row(const long long act, const int n_actions) {
-    return (int)(act < 0 ? 0 : act > (long long)n_actions - 1 ? (long long)n_actions - 1 : act);
+// The contact's pass over one obstacle of task t - a static row u, or another agent as its own task has it, o = (p_b, u_b): is it a
+// blocker - its own collision value IS x1 - and then its normal at p1 (meet_wall's and meet_agent's culls and tests, kernels/step.h)
+__host__ __device__ inline bool offer_wall(const StepTask& t, const float4 u, const float x1, const float2 p1, const float agent_radius,
+                                           float& nx, float& ny) {
+    if (wall_beyond(t.tk, u, t.reach2)) return false;
+    const float c = collision_cs(p2(t.tk.x, t.tk.y), p2(t.tk.z, t.tk.w), p2(u.x, u.y), p2(u.z, u.w), agent_radius);
+    return c == x1 && slide_normal_wall(p2(p1.x, p1.y), u, nx, ny);
+}
+__host__ __device__ inline bool offer_agent(const StepTask& t, const float4 o, const float x1, const float2 p1, const float agent_radius,
+                                            float& nx, float& ny) {
+    if (agents_apart(t.tk, o, agent_radius)) return false;
+    const float c = collision_cc(p2(t.tk.x, t.tk.y), p2(t.tk.z, t.tk.w), p2(o.x, o.y), p2(o.z, o.w), agent_radius);
+    return c == x1 && slide_normal_agent(p2(p1.x, p1.y), p2(o.x, o.y), p2(o.z, o.w), c, nx, ny);
 }
 
 // ONE WAVEFRONT PER ENV, a lane an agent (n_agents <= 64), as physics_kernel without PACK - and up to three passes over the env's
@@ -130,54 +140,37 @@ __global__ __launch_bounds__(WAVE) void physics_slide_kernel(
     const int i = nA + (mine ? lane : 0);
     const float2* pos2 = reinterpret_cast<const float2*>(ag.positions);
     const float2* vel2 = reinterpret_cast<const float2*>(ag.velocity);
-    const int L = sc.lines_widths[n];
-    const float4* __restrict__ ln = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[n];
-    const bool gridded = sc.wg_cells != nullptr;
-    float4 wg_geom_n = make_float4(0.f, 0.f, 0.f, 0.f);
-    int wg_start_n = 0;
-    if (gridded) { wg_geom_n = reinterpret_cast<const float4*>(sc.wg_geom)[n]; wg_start_n = sc.wg_starts[n]; }
+    const EnvRows env = env_rows(sc, n);
 
     float2 my_p = make_float2(0.f, 0.f), my_v = make_float2(0.f, 0.f);
     float my_w = 0.f, my_ang = 0.f;
     if (mine) { my_p = pos2[i]; my_v = vel2[i]; my_w = ag.angvelocity[i]; my_ang = ag.angles[i]; }
     if constexpr (EXTRA == 1) {
-        if (mine) {
-            bool reset = ex.respawn_mask && ex.respawn_mask[i];
-            if (ex.lifespans) {
-                ex.lifespans[i] = lifespan_tick(ex, i, reset);
-                if (reset) ex.max_lifespans[i] = ex.fresh_max[i];
-                if (ex.respawn_mask) ex.respawn_mask[i] = reset ? 1 : 0;
-            }
-            if (reset && ex.spawn_positions && !ex.respawn_after) {
-                spawn_pose(ex, i, my_p, my_ang);
-                my_v = make_float2(0.f, 0.f); my_w = 0.f;
-                reinterpret_cast<float2*>(ag.velocity)[i] = my_v;       // (the epilogue writes velocities only where they change)
-                ag.angvelocity[i] = 0.f;
-            }
+        if (mine && step_books(ex, i)) {
+            spawn_pose(ex, i, my_p, my_ang);
+            my_v = make_float2(0.f, 0.f); my_w = 0.f;
+            reinterpret_cast<float2*>(ag.velocity)[i] = my_v;           // (the epilogue writes velocities only where they change)
+            ag.angvelocity[i] = 0.f;
         }
     }
     if constexpr (MOVE == 1) {
         if (mine) {
-            const int c = table_row(mv.actions[i], mv.n_actions);
+            const int c = action_row(mv.actions[i], mv.n_actions);
             move_velocity(mv.keep, my_ang, mv.table[3*c], mv.table[3*c + 1], mv.table[3*c + 2], my_v, my_w);
             ag.angvelocity[i] = my_w;
             reinterpret_cast<float2*>(ag.velocity)[i] = my_v;
         }
     }
-    auto wave_sync = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     // a pass's tasks: lane = agent
     float my_reach = 0.f;
     auto task = [&](const float2 p, const P2 u) {
-        const float reach = wall_reach(p2(p.x, p.y), u, agent_radius);
-        my_reach = (reach == reach) ? reach : INFINITY;
-        s_reach2[lane] = reach_squared(reach);
-        s_task[lane] = make_float4(p.x, p.y, u.x, u.y);
+        const StepTask t = step_task(p, u, agent_radius);
+        my_reach = t.reach;
+        s_reach2[lane] = t.reach2;
+        s_task[lane] = t.tk;
         s_prog[lane] = f_bits(1.f);
     };
+    auto task_of = [&](const int t) { return StepTask{s_task[t], 0.f, s_reach2[t]}; };
     if (mine) {
         task(my_p, p2(my_v.x, my_v.y)/fps);
         s_vel[lane] = my_v;
@@ -200,33 +193,19 @@ __global__ __launch_bounds__(WAVE) void physics_slide_kernel(
             }
         }
     };
-    // one (row, agent) pair: the reach cull on the true distance, then the reference's test; pass 1: is it a blocker, and its normal
-    auto meet = [&](const float4 u, const int t, float& nx, float& ny) -> bool {
-        const float4 tk = s_task[t];
-        if (wall_beyond(tk, u, s_reach2[t])) return false;
-        const float x = collision_cs(p2(tk.x, tk.y), p2(tk.z, tk.w), p2(u.x, u.y), p2(u.z, u.w), agent_radius);
-        if (mode != 1) {
-            if (x < 1.f) atomicMin(&s_prog[t], f_bits(x));
-            return false;
+    // one (row, agent) pair of the lanes that have one (every lane of the wave comes here): passes 0 and 2 fold its value; pass 1:
+    // is it a blocker, and its normal
+    auto meet = [&](const bool has, const float4 u, const int t) {
+        float nx = 0.f, ny = 0.f;
+        bool blocker = false;
+        if (has) {
+            if (mode != 1) fold_least(&s_prog[t], meet_wall(1.f, task_of(t), u, agent_radius));
+            else blocker = offer_wall(task_of(t), u, bits_f(s_prog[t]), s_p1[t], agent_radius, nx, ny);
         }
-        if (f_bits(x) != s_prog[t]) return false;
-        const float2 p1 = s_p1[t];
-        return slide_normal_wall(p2(p1.x, p1.y), u, nx, ny);
+        if (mode == 1) offer(blocker, t, nx, ny);
     };
-    int cnt = 0;
-    auto flush = [&]() {
-        wave_sync();
-        #pragma unroll 1
-        for (int p0 = 0; p0 < cnt; p0 += WAVE) {
-            float nx = 0.f, ny = 0.f;
-            bool has = false;
-            const int t = (p0 + lane < cnt) ? s_tag[p0 + lane] : 0;
-            if (p0 + lane < cnt) has = meet(s_wall[p0 + lane], t, nx, ny);
-            if (mode == 1) offer(has, t, nx, ny);
-        }
-        wave_sync();
-        cnt = 0;
-    };
+    PairList pairs{s_wall, s_tag, PHYS_PAIRS, 0};
+    auto flush = [&]() { pairs.drain(lane, meet); };
     SlideContact con;
     float my_x1 = 1.f;
     for (; mode < 3; mode++) {
@@ -265,82 +244,44 @@ __global__ __launch_bounds__(WAVE) void physics_slide_kernel(
             float nx = 0.f, ny = 0.f;
             bool has = false;
             if (q < A*A && d1 != t && ((active >> t) & 1ull)) {
-                const float4 me = s_task[t], o = s_task[d1];
-                if (!agents_apart(me, o, agent_radius)) {
-                    const float x = collision_cc(p2(me.x, me.y), p2(me.z, me.w), p2(o.x, o.y), p2(o.z, o.w), agent_radius);
-                    if (mode != 1) {
-                        if (x < 1.f) atomicMin(&s_prog[t], f_bits(x));
-                    } else if (f_bits(x) == s_prog[t]) {
-                        const float2 p1 = s_p1[t];
-                        has = slide_normal_agent(p2(p1.x, p1.y), p2(o.x, o.y), p2(o.z, o.w), x, nx, ny);
-                    }
-                }
+                if (mode != 1) fold_least(&s_prog[t], meet_agent(1.f, task_of(t), s_task[d1], agent_radius));
+                else has = offer_agent(task_of(t), s_task[d1], bits_f(s_prog[t]), s_p1[t], agent_radius, nx, ny);
             }
             if (mode == 1) offer(has, t, nx, ny);
         }
-        // the static rows
+        // the static rows: the agents' near lists laid end to end, if every agent of the pass is covered by its own
         bool swept = true;
-        if (gridded) {
-            unsigned first = 0u;
-            int count = 0;
-            bool ok = true;
-            if ((active >> lane) & 1ull) {
-                const float4 me = s_task[lane];
-                bool inside;
-                const uint4 hdr = reinterpret_cast<const uint4*>(sc.wg_cells)[wg_start_n + wg_cell_at(wg_geom_n, sc.wg_cell, me.x, me.y, inside)];
-                ok = inside & (my_reach <= sc.wg_reach);
-                first = hdr.z;
-                count = ok ? near_count(hdr, my_reach, sc.wg_reach_lo) : 0;
-            }
-            if (!__ballot(!ok)) {
+        if (env.gridded) {
+            NearList nl{true, 0, 0u, nullptr};
+            if ((active >> lane) & 1ull) nl = near_list(sc, env.geom, env.wg_start, s_task[lane].x, s_task[lane].y, my_reach);
+            if (!__ballot(!nl.covered)) {
                 swept = false;
-                const int incl = wave_scan_add(count);
-                const int excl = incl - count;
+                const int incl = wave_scan_add(nl.count);
+                const int excl = incl - nl.count;
                 const int P = __builtin_amdgcn_readlane(incl, 63);
                 for (int p0 = 0; p0 < P; p0 += WAVE) {
                     const int q = p0 + lane;
-                    int t = 0;
-                    for (int j = 0; j < A - 1; j++) t += (__builtin_amdgcn_readlane(incl, j) <= q) ? 1 : 0;   // whose list is pair q in?
-                    const int k = q - __shfl(excl, t, WAVE);
-                    const unsigned at = (unsigned)__shfl((int)first, t, WAVE) + (unsigned)k;
-                    if (P <= WAVE) {
-                        float nx = 0.f, ny = 0.f;
-                        bool has = false;
-                        if (q < P) has = meet(reinterpret_cast<const float4*>(sc.wg_near_rows)[at], t, nx, ny);
-                        if (mode == 1) offer(has, t, nx, ny);
-                    } else {
-                        float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
-                        bool in_reach = false;
-                        if (q < P) {
-                            u = reinterpret_cast<const float4*>(sc.wg_near_rows)[at];
-                            in_reach = !wall_beyond(s_task[t], u, s_reach2[t]);
-                        }
-                        const unsigned long long m = __ballot(in_reach);
-                        if (cnt > PHYS_PAIRS - WAVE) flush();
-                        if (in_reach) {
-                            const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
-                            s_wall[pos] = u;
-                            s_tag[pos] = t;
-                        }
-                        cnt += __popcll(m);
-                    }
+                    int t;
+                    unsigned at;
+                    deal_pair(incl, excl, nl.first, A, q, t, at);
+                    const float4 u = (q < P) ? reinterpret_cast<const float4*>(sc.wg_near_rows)[at] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    // (up to 64 pairs: one each, cull and test; more: the cull alone first, its survivors compacted - physics_kernel's scheme)
+                    if (P <= WAVE) meet(q < P, u, t);
+                    else pairs.append(lane, q < P && !wall_beyond(s_task[t], u, s_reach2[t]), u, t, flush);
                 }
-                if (cnt) flush();
+                if (pairs.cnt) flush();
             }
         }
         if (swept) {
             // (plain: every static row of the env, a lane a row, to every agent of the pass - meet() has the cull)
-            for (int l0 = AF; l0 < L; l0 += WAVE) {
-                const bool row = l0 + lane < L;
-                const float4 u = row ? ln[l0 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int l0 = AF; l0 < env.L; l0 += WAVE) {
+                const bool row = l0 + lane < env.L;
+                const float4 u = row ? env.ln[l0 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
                 unsigned long long todo = active;
                 while (todo) {
                     const int t = __ffsll((long long)todo) - 1;
                     todo &= todo - 1ull;
-                    float nx = 0.f, ny = 0.f;
-                    bool has = false;
-                    if (row) has = meet(u, t, nx, ny);
-                    if (mode == 1) offer(has, t, nx, ny);
+                    meet(row, u, t);
                 }
             }
         }
@@ -355,34 +296,16 @@ __global__ __launch_bounds__(WAVE) void physics_slide_kernel(
         const bool stopped = slide_finish(con, x2, fps, p, ang, v, w_, slid);
         bool changed = con.blocked;                                      // (a velocity only changes on a collision)
         if constexpr (EXTRA == 1) {
-            if (ex.spawn_positions && ex.respawn_after && ex.respawn_mask && ex.respawn_mask[i]) {
+            if (respawns_after(ex, i)) {
                 spawn_pose(ex, i, p, ang);
                 v = make_float2(0.f, 0.f); w_ = 0.f;
                 changed = true;
             }
         }
-        reinterpret_cast<float2*>(ag.positions)[i] = p;
-        ag.angles[i] = ang;
-        if (ag.headings) {                                               // what render_prep_kernel would compute, one launch earlier
-            float hs, hc;
-            sincospi_f(ang/180.f, hs, hc);
-            reinterpret_cast<float4*>(ag.headings)[i] = make_float4(ang, hs, hc, 0.f);
-        }
-        if (changed) {
-            reinterpret_cast<float2*>(ag.velocity)[i] = v;
-            ag.angvelocity[i] = w_;
-        }
+        step_store(ag, ex, i, p, ang, v, w_, changed, EXTRA == 1);
         progress[i] = my_x1;
         if (sl.slid) sl.slid[i] = slid;
         if (sl.stopped) sl.stopped[i] = stopped ? 1 : 0;
-        if constexpr (EXTRA == 1) {
-            if (ex.imu) {
-                const float3 m = imu_reading(ex, ang, v, w_);
-                ex.imu[3*i] = m.x;
-                ex.imu[3*i + 1] = m.y;
-                ex.imu[3*i + 2] = m.z;
-            }
-        }
     }
 }
 
@@ -392,7 +315,7 @@ __global__ __launch_bounds__(WAVE) void physics_slide_kernel(
 inline void slide_serial(const float* walls, const long long* wall_starts, const int N, const int A, const MsAgents& ag,
                          const MsMovement* mv, const MsStepExtras& ex, const bool extras, const MsSlide& sl, float* progress,
                          const float agent_radius, const float fps) {
-    struct Agent { float2 p, v; float ang, w; float4 tk; float reach2, x1; SlideContact con; };
+    struct Agent { float2 p, v; float ang, w, x1; StepTask t; SlideContact con; };
     Agent* as = new Agent[A];
     const auto row_of = [&](const long long l) { return make_float4(walls[4*l], walls[4*l + 1], walls[4*l + 2], walls[4*l + 3]); };
     for (int n = 0; n < N; n++) {
@@ -400,54 +323,34 @@ inline void slide_serial(const float* walls, const long long* wall_starts, const
         for (int a = 0; a < A; a++) {
             const int i = n*A + a;
             Agent& me = as[a];
-            me.p = make_float2(ag.positions[2*i], ag.positions[2*i + 1]); me.v = make_float2(ag.velocity[2*i], ag.velocity[2*i + 1]);
+            me.p = load2(ag.positions, i); me.v = load2(ag.velocity, i);
             me.ang = ag.angles[i]; me.w = ag.angvelocity[i];
-            if (extras) {
-                bool reset = ex.respawn_mask && ex.respawn_mask[i];
-                if (ex.lifespans) {
-                    ex.lifespans[i] = lifespan_tick(ex, i, reset);
-                    if (reset) ex.max_lifespans[i] = ex.fresh_max[i];
-                    if (ex.respawn_mask) ex.respawn_mask[i] = reset ? 1 : 0;
-                }
-                if (reset && ex.spawn_positions && !ex.respawn_after) {
-                    spawn_pose(ex, i, me.p, me.ang);
-                    me.v = make_float2(0.f, 0.f); me.w = 0.f;
-                }
+            if (extras && step_books(ex, i)) {
+                spawn_pose(ex, i, me.p, me.ang);
+                me.v = make_float2(0.f, 0.f); me.w = 0.f;
             }
             if (mv) {
-                const int c = table_row(mv->actions[i], mv->n_actions);
+                const int c = action_row(mv->actions[i], mv->n_actions);
                 move_velocity(mv->keep, me.ang, mv->table[3*c], mv->table[3*c + 1], mv->table[3*c + 2], me.v, me.w);
             }
         }
         // a pass: pass 0 and 2 fold the least collision value of agent a's task, pass 1 offers the obstacles whose value is x1
         const auto pass = [&](const int a, const int mode, SlideBest& best) {
             const Agent& me = as[a];
-            float least = 1.f;
-            const P2 p1 = p2(me.con.p1.x, me.con.p1.y);
+            float least = 1.f, nx, ny;
             for (int b = 0; b < A; b++) {
-                if (b == a || agents_apart(me.tk, as[b].tk, agent_radius)) continue;
-                const float4 o = as[b].tk;
-                const float x = collision_cc(p2(me.tk.x, me.tk.y), p2(me.tk.z, me.tk.w), p2(o.x, o.y), p2(o.z, o.w), agent_radius);
-                float nx, ny;
-                if (mode != 1) least = x < least ? x : least;
-                else if (x == me.x1 && slide_normal_agent(p1, p2(o.x, o.y), p2(o.z, o.w), x, nx, ny)) slide_offer(best, me.v, nx, ny);
+                if (b == a) continue;
+                if (mode != 1) least = meet_agent(least, me.t, as[b].t.tk, agent_radius);
+                else if (offer_agent(me.t, as[b].t.tk, me.x1, me.con.p1, agent_radius, nx, ny)) slide_offer(best, me.v, nx, ny);
             }
             for (long long l = l0; l < l1; l++) {
-                const float4 u = row_of(l);
-                if (wall_beyond(me.tk, u, me.reach2)) continue;
-                const float x = collision_cs(p2(me.tk.x, me.tk.y), p2(me.tk.z, me.tk.w), p2(u.x, u.y), p2(u.z, u.w), agent_radius);
-                float nx, ny;
-                if (mode != 1) least = x < least ? x : least;
-                else if (x == me.x1 && slide_normal_wall(p1, u, nx, ny)) slide_offer(best, me.v, nx, ny);
+                if (mode != 1) least = meet_wall(least, me.t, row_of(l), agent_radius);
+                else if (offer_wall(me.t, row_of(l), me.x1, me.con.p1, agent_radius, nx, ny)) slide_offer(best, me.v, nx, ny);
             }
             return least;
         };
-        const auto task = [&](Agent& me, const float2 p, const P2 u) {
-            me.tk = make_float4(p.x, p.y, u.x, u.y);
-            me.reach2 = reach_squared(wall_reach(p2(p.x, p.y), u, agent_radius));
-        };
         SlideBest none{0.f, 0.f, 0.f, 0};
-        for (int a = 0; a < A; a++) task(as[a], as[a].p, p2(as[a].v.x, as[a].v.y)/fps);
+        for (int a = 0; a < A; a++) as[a].t = step_task(as[a].p, p2(as[a].v.x, as[a].v.y)/fps, agent_radius);
         for (int a = 0; a < A; a++) as[a].x1 = pass(a, 0, none);
         for (int a = 0; a < A; a++) {
             Agent& me = as[a];
@@ -458,7 +361,7 @@ inline void slide_serial(const float* walls, const long long* wall_starts, const
                 me.con = slide_contact(me.p, me.ang, me.v, me.w, me.x1, fps, best, sl.bounce);
             }
         }
-        for (int a = 0; a < A; a++) task(as[a], as[a].con.p1, p2(as[a].con.u2.x, as[a].con.u2.y));
+        for (int a = 0; a < A; a++) as[a].t = step_task(as[a].con.p1, p2(as[a].con.u2.x, as[a].con.u2.y), agent_radius);
         for (int a = 0; a < A; a++) {
             const int i = n*A + a;
             Agent& me = as[a];
@@ -466,21 +369,18 @@ inline void slide_serial(const float* walls, const long long* wall_starts, const
             float2 p, v = me.v;
             float w = me.w, ang, slid;
             const bool stopped = slide_finish(me.con, x2, fps, p, ang, v, w, slid);
-            if (extras && ex.spawn_positions && ex.respawn_after && ex.respawn_mask && ex.respawn_mask[i]) {
+            if (extras && respawns_after(ex, i)) {
                 spawn_pose(ex, i, p, ang);
                 v = make_float2(0.f, 0.f); w = 0.f;
             }
-            ag.positions[2*i] = p.x; ag.positions[2*i + 1] = p.y;
+            store2(ag.positions, i, p);
             ag.angles[i] = ang;
-            ag.velocity[2*i] = v.x; ag.velocity[2*i + 1] = v.y;
+            store2(ag.velocity, i, v);
             ag.angvelocity[i] = w;
             progress[i] = me.x1;
             if (sl.slid) sl.slid[i] = slid;
             if (sl.stopped) sl.stopped[i] = stopped ? 1 : 0;
-            if (extras && ex.imu) {
-                const float3 m = imu_reading(ex, ang, v, w);
-                ex.imu[3*i] = m.x; ex.imu[3*i + 1] = m.y; ex.imu[3*i + 2] = m.z;
-            }
+            if (extras) imu_store(ex, i, ang, v, w);
         }
     }
     delete[] as;

@@ -2,7 +2,8 @@
 //
 // One translation unit: this file holds the constants, the switches and the probe macros, and includes the rest, a family a file:
 //   kernels/*.h   the kernels, inside the anonymous namespace: math.h (scalar helpers shared with the ms_host_* test hooks)
-//                 first, culltest.h (the ms_test_* probes of the culls) last;
+//                 first, step.h (what the step kernels share: physics, slide, rollout, scenario) behind it, culltest.h (the
+//                 ms_test_* probes of the culls) last;
 //   host/*.h      the host side of the C-ABI - argument checks, argument structs, launches, the ms_host_* / ms_test_* /
 //                 ms_debug_* hooks: common.h (what every family shares) first, then a file a family as under kernels/.
 //
@@ -186,6 +187,7 @@ struct Probe {
 #endif
 
 #include "kernels/math.h"
+#include "kernels/step.h"
 #include "kernels/physics.h"
 #include "kernels/slide.h"
 #include "kernels/rollout.h"

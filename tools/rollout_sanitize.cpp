@@ -1,4 +1,4 @@
-// A stand-alone program for a sanitizer run of the rollouts' HOST code (csrc/kernels/rollout.h over math.h and physics.h, through
+// A stand-alone program for a sanitizer run of the rollouts' HOST code (csrc/kernels/rollout.h over math.h, step.h and physics.h, through
 // ms_host_rollouts and ms_host_move_velocity): no GPU, no Python.  Build the library's translation unit and this file with the host
 // sanitizers and run the result:
 //

@@ -1,4 +1,4 @@
-// A stand-alone program for a sanitizer run of the scenarios' HOST code (csrc/kernels/scenario.h over rollout.h, math.h and
+// A stand-alone program for a sanitizer run of the scenarios' HOST code (csrc/kernels/scenario.h over rollout.h, math.h, step.h and
 // physics.h, through ms_host_scenarios): no GPU, no Python.  Build the library's translation unit and this file with the host
 // sanitizers and run the result:
 //

@@ -1,5 +1,5 @@
-// A stand-alone program for a sanitizer run of the sliding step's HOST code (csrc/kernels/slide.h and rollout.h over math.h and
-// physics.h, through ms_host_slide and ms_host_rollouts with slide on): no GPU, no Python.  Build the library's translation unit and
+// A stand-alone program for a sanitizer run of the sliding step's HOST code (csrc/kernels/slide.h and rollout.h over math.h, step.h
+// and physics.h, through ms_host_slide and ms_host_rollouts with slide on): no GPU, no Python.  Build the library's translation unit and
 // this file with the host sanitizers and run the result:
 //
 //     cd megastep_amd/csrc
