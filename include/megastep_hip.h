@@ -1448,6 +1448,99 @@ int ms_nav_clearance(const MsScenery* scenery, const MsNavGrid* grid, const MsNa
 int ms_nav_clear_query(const MsScenery* scenery, const MsAgents* agents /* NULL: static walls only */, const MsNavClearQuery* query,
                        void* hip_stream);
 
+/* Items: things in the world that agents see, touch and collect - pickups, a goal object.  A store the caller owns, one call a step
+ * that takes items (ms_item_collect) and one that draws them into rendered or cast rays (ms_item_overlay); the return of a taken
+ * item composes what exists (MsNavDraws with mask = due, then a select).  Every step below is one binary32 operation, in the order
+ * given, without contraction; tests/item_rule.py restates it in numpy and the kernels - and their host instantiations,
+ * ms_host_item_collect and ms_host_item_overlay - are held to EQUALITY with it.  DESIGN.md section 3.34.
+ * The store, P items an env (1 .. 1024):
+ *   positions     (N, P, 2).  AN ITEM IS PRESENT EXACTLY WHEN BOTH COORDINATES ARE FINITE; an absent item holds (NaN, NaN), which
+ *                 ms_nav_point_marks marks nothing for, ms_percepts never sees, the overlay's fold never hits and the reach test
+ *                 fails for: every consumer treats an absent item correctly without a `valid` mask.
+ *   timers        (N, P) int32: the calls left until an absent item is due to return; negative: never.
+ *   kinds         (N, P) int32 in [0, K), 1 <= K <= 8 (an item of a kind outside that range is taken and counted nowhere).
+ *   colors        (N, P, 3) linear RGB (the overlay's).
+ * ms_item_collect, one call a step, the agents (px, py) = agents->positions[n, a] as they stand; reach2 = reach*reach formed once:
+ *   reset         reset[n] != 0 ((N,) bytes; NULL: none): every item of the env becomes absent with timer 0, taker -1 and due 1,
+ *                 the env's counts are 0; nothing is collected in that env in this call.
+ *   candidate     otherwise, for a present item k at (x, y), agent a is a candidate iff takers[n, a] != 0 (NULL: everyone), px and
+ *                 py are finite, rx = x - px, ry = y - py, rr = rx*rx + ry*ry, rr <= reach2, and - unless through_walls - no
+ *                 static wall of the env (rows n_agents*n_model .. L - 1) blocks the pair: MsNavViews' meets, apart and across,
+ *                 the agent as the viewpoint and the item as the centre, by the function ms_percepts calls.  BODIES DO NOT OCCLUDE.
+ *   taker         (N, P): the candidate with the least (bits of rr, a) - the nearest, equal distances to the lower index; -1
+ *                 without one (and for an absent item).
+ *   taken         an item with a taker becomes absent - (NaN, NaN) is stored - and its timer is set to `delay`.
+ *   tick          an item that was absent on entry has timer = timer > 0 ? timer - 1 : timer.
+ *   due           (N, P) bytes: 1 exactly when the item is absent after this call and its timer is 0; otherwise 0.
+ *   counts        (N, A, K): the items of kind j that agent a took in this call; rewritten whole by every call.
+ * Every output is an integer or a stored NaN and each element has one writer.  taker, counts and due may each be NULL (not wanted).
+ * Limits: 1 <= A <= 64 (MsScenery.n_agents), 1 <= P <= 1024, 1 <= K <= 8; `delay` is any int.
+ * Refused before any launch (MS_EINVAL): a NULL agents or agents->positions, or positions not 8-byte aligned; A, P or K outside
+ * those limits; a NULL positions, timers or kinds; reach not positive and finite; through_walls neither 0 nor 1; the store's
+ * positions not 8-byte aligned; timers, kinds, taker or counts not 4-byte aligned.
+ * One launch, a wave an env, a lane the items lane + 64 j; integer LDS atomics for the counts, no float atomics; nothing
+ * allocated, nothing waits: the call can be captured in a HIP graph. */
+typedef struct MsItemCollect {
+    int                  n_items;        /* P: items per env (1 .. 1024)                                                   */
+    int                  n_kinds;        /* K: kinds (1 .. 8)                                                              */
+    float*               positions;      /* (N, P, 2) in/out; 8-byte aligned                                               */
+    int*                 timers;         /* (N, P) in/out                                                                  */
+    const int*           kinds;          /* (N, P)                                                                         */
+    const unsigned char* takers;         /* (N, A) non-zero: the agent may take; NULL: everyone                            */
+    const unsigned char* reset;          /* (N,) non-zero: empty the env's store; NULL: none                               */
+    float                reach;          /* metres (> 0, finite)                                                           */
+    int                  delay;          /* the timer of a taken item                                                      */
+    int                  through_walls;  /* 1: walls do not block a taker                                                  */
+    int*                 taker;          /* (N, P) out, or NULL                                                            */
+    int*                 counts;         /* (N, A, K) out, or NULL                                                         */
+    unsigned char*       due;            /* (N, P) out, or NULL                                                            */
+} MsItemCollect;
+int ms_item_collect(const MsScenery* scenery, const MsAgents* agents, const MsItemCollect* collect, void* hip_stream);
+
+/* ms_item_overlay draws the items over the planes ms_render or ms_raycast wrote for a set of rays - a pass of its own: those
+ * kernels are not touched.  Rays as ms_raycast takes them: dirs (N, R, 2), origins (N, Q, 2) with R % Q == 0, ray r starting at
+ * origin r / (R/Q) (a render's fan: Q = A, the agents' positions, dirs of ms_camera_rays, the MsRender's planes as (N, A res); a
+ * raycast's rays: Q = R).  For origin p = (px, py), ray direction ru and item k at c = (cx, cy):
+ *   billboard     a segment of length 2*radius that always faces p: ux = cx - px, uy = cy - py, l = sqrtf(ux*ux + uy*uy),
+ *                 nx = (-uy/l)*radius, ny = (ux/l)*radius, row = (cx - nx, cy - ny, cx + nx, cy + ny).  An absent item and an
+ *                 origin that sits on the item give a row with a NaN, which is never hit.
+ *   fold          from the state (s, idx, t) = (+inf, -1, NaN) the env's items are met in ascending k by the very function
+ *                 ms_raycast folds its lines with (kernels.cu:352-377: hit iff 0 <= t <= 1, better iff near_plane/|ru| < s and
+ *                 s < best s - 1e-4, the 1e-4 hysteresis included), |ru| = sqrtf(ru.x*ru.x + ru.y*ru.y).
+ *   winner        item k with d = s*|ru|, dt = dtop/(dbot + 1e-6f) by ms_raycast's own closing lines (dtop = ru . v, dbot =
+ *                 |ru|*|v|, v the billboard's direction) and dn = 1 - dt*dt REPLACES THE RAY WHEN d < distances[n, r] - strict; a
+ *                 miss holds +inf.  Written only where the item wins: distances = d; screen[c] = dn*colors[n, k, c] (items are
+ *                 emissive: no light is read); indices = lines_widths[n] + k, deliberately no line of the env - ms_shade reads
+ *                 nothing for such an index and leaves black; locations = t; dots = dt.
+ *   items         (N, R) int32, written for every ray: the k that won it, else -1.
+ * An agent's body nearer than the item hides it, an item nearer than a wall hides the wall; items do not hide each other beyond
+ * the fold's own rule.  distances is required, the other planes may be NULL; screen needs colors.
+ * Refused before any launch (MS_EINVAL): P outside 1 .. 1024; R < 1, Q < 1 or R % Q != 0; a NULL positions, origins, dirs or
+ * distances; screen without colors; radius not positive and finite; near_plane negative or a NaN; positions, origins or dirs not
+ * 8-byte aligned; colors, distances, indices, locations, dots, screen or items not 4-byte aligned.  MS_EUNSUPPORTED: N*R, or the
+ * launch's workgroups, beyond 2^31 - 1.
+ * One launch: a workgroup takes up to 256 rays of one origin, builds the P billboards for that origin a lane an item (one sqrtf
+ * and two divisions per item and origin, not per ray), compacts the rows without a NaN in ascending k into LDS, and every lane
+ * folds its ray over them.  Nothing allocated, nothing waits: the call can be captured in a HIP graph. */
+typedef struct MsItemOverlay {
+    int          n_items;      /* P: items per env (1 .. 1024)                                                              */
+    int          n_rays;       /* R: rays per env                                                                           */
+    int          n_origins;    /* Q: origins per env; R % Q == 0                                                            */
+    const float* positions;    /* (N, P, 2) the store's; 8-byte aligned                                                     */
+    const float* colors;       /* (N, P, 3), or NULL (then no screen)                                                       */
+    const float* origins;      /* (N, Q, 2); 8-byte aligned                                                                 */
+    const float* dirs;         /* (N, R, 2); 8-byte aligned                                                                 */
+    float        radius;       /* half the billboard's length, metres (> 0, finite)                                         */
+    float        near_plane;   /* as MsRaycast's (>= 0)                                                                     */
+    float*       distances;    /* (N, R) in/out                                                                             */
+    int*         indices;      /* (N, R) in/out, or NULL                                                                    */
+    float*       locations;    /* (N, R) in/out, or NULL                                                                    */
+    float*       dots;         /* (N, R) in/out, or NULL                                                                    */
+    float*       screen;       /* (N, R, 3) in/out, or NULL                                                                 */
+    int*         items;        /* (N, R) out, or NULL                                                                       */
+} MsItemOverlay;
+int ms_item_overlay(const MsScenery* scenery, const MsItemOverlay* overlay, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

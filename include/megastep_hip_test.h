@@ -189,6 +189,18 @@ int ms_host_nav_view_capacity(void);
  * staged ones.  Returns what ms_percepts would: MS_OK, or MS_EINVAL for arguments it would refuse (and for n_envs < 1, NULL walls
  * or a capacity above the kernel's). */
 int ms_host_percepts(const MsPercepts* percepts, int n_envs, const float* walls, const long long* wall_starts, int capacity);
+/* Host instantiations of the items' rule (kernels/items.h: the reach test over view_wall_blocks, the key, the settling of an item
+ * and its stores; the billboard, ray_fold itself, the winner's closing lines and its stores - the very functions every lane of
+ * item_collect_kernel and item_overlay_kernel evaluates) for one whole call each on HOST arrays, swept serially: every pointer of
+ * the argument struct is host memory.  ms_host_item_collect: in place of an MsScenery and an MsAgents there are n_envs, n_agents,
+ * `agent_positions` (N, A, 2) and `walls`, the STATIC rows of all envs, four floats each, env n's rows wall_starts[n] ..
+ * wall_starts[n + 1] - 1.  ms_host_item_overlay: in place of an MsScenery there are n_envs and `lines_widths` (N,), each env's
+ * number of lines (agents' rows included; NULL is allowed where `indices` is).  They return what the device calls would: MS_OK, or
+ * MS_EINVAL / MS_EUNSUPPORTED for arguments those would refuse (and for n_envs < 1, n_agents outside 1 .. 64, a NULL
+ * agent_positions, walls or wall_starts, or `indices` without lines_widths). */
+int ms_host_item_collect(const MsItemCollect* collect, int n_envs, int n_agents, const float* agent_positions, const float* walls,
+                         const long long* wall_starts);
+int ms_host_item_overlay(const MsItemOverlay* overlay, int n_envs, const int* lines_widths);
 /* Host instantiations of the clearance rule (kernels/navclear.h: the tile's box, the list, ov_keeps and ov_fold, the second cull,
  * the winner's order and the stores - the very functions every lane of nav_clear_kernel and nav_clear_query_kernel evaluates) for
  * one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the argument struct is host memory.

@@ -262,6 +262,18 @@ class MsPercepts(C.Structure):
                 ('counts', C.c_void_p), ('nearest', C.c_void_p), ('near_offsets', C.c_void_p), ('near_distances', C.c_void_p)]
 
 
+class MsItemCollect(C.Structure):
+    _fields_ = [('n_items', C.c_int), ('n_kinds', C.c_int), ('positions', C.c_void_p), ('timers', C.c_void_p), ('kinds', C.c_void_p),
+                ('takers', C.c_void_p), ('reset', C.c_void_p), ('reach', C.c_float), ('delay', C.c_int), ('through_walls', C.c_int),
+                ('taker', C.c_void_p), ('counts', C.c_void_p), ('due', C.c_void_p)]
+
+
+class MsItemOverlay(C.Structure):
+    _fields_ = [('n_items', C.c_int), ('n_rays', C.c_int), ('n_origins', C.c_int), ('positions', C.c_void_p), ('colors', C.c_void_p),
+                ('origins', C.c_void_p), ('dirs', C.c_void_p), ('radius', C.c_float), ('near_plane', C.c_float), ('distances', C.c_void_p),
+                ('indices', C.c_void_p), ('locations', C.c_void_p), ('dots', C.c_void_p), ('screen', C.c_void_p), ('items', C.c_void_p)]
+
+
 class MsNavClearance(C.Structure):
     _fields_ = [('max_range', C.c_float), ('n_radii', C.c_int), ('radii', C.c_float*8), ('max_tiles', C.c_int), ('mask', C.c_void_p),
                 ('values', C.c_void_p), ('nearest', C.c_void_p), ('fits', C.c_void_p)]
@@ -313,6 +325,8 @@ PROTOTYPES = {
     'ms_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks), _ptr]),
     'ms_nav_views': (_int, [_p(MsScenery), _p(MsNavGrid), _p(MsNavViews), _ptr]),
     'ms_percepts': (_int, [_p(MsScenery), _p(MsPercepts), _ptr]),
+    'ms_item_collect': (_int, [_p(MsScenery), _p(MsAgents), _p(MsItemCollect), _ptr]),
+    'ms_item_overlay': (_int, [_p(MsScenery), _p(MsItemOverlay), _ptr]),
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
     'ms_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery), _ptr]),
     'ms_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks), _ptr]),
@@ -373,6 +387,8 @@ PROTOTYPES = {
     'ms_host_nav_views': (_int, [_p(MsNavGrid), _p(MsNavViews), _ptr, _ptr, _int]),
     'ms_host_nav_view_capacity': (_int, []),
     'ms_host_percepts': (_int, [_p(MsPercepts), _int, _ptr, _ptr, _int]),
+    'ms_host_item_collect': (_int, [_p(MsItemCollect), _int, _int, _ptr, _ptr, _ptr]),
+    'ms_host_item_overlay': (_int, [_p(MsItemOverlay), _int, _ptr]),
     'ms_host_nav_clearance': (_int, [_p(MsNavGrid), _p(MsNavClearance), _ptr, _ptr, _int]),
     'ms_host_nav_clear_folds': (C.c_longlong, [_ptr]),
     'ms_host_nav_clear_chunk': (_int, []),

@@ -18,12 +18,13 @@ struct RayFold { float s; int idx; float t, vx, vy; };
 // |nt| <= |d| with nt of d's sign (an exact quotient of floats above 1 exceeds 1 + 2^-24 and never rounds down to 1; one
 // below 0 rounds to -0 only when it is below 2^-150, i.e. nt above -2^-150 |d|), and only if |d| >= 1e-3 (kernels.cu:77).
 // NaNs fail the test and could not have hit.  (d and nt are intersect()'s own cross products, the same bits.)
-__device__ inline void ray_fold(const P2 p, const P2 ru, const float near_s, const float4 L, const int l, RayFold& f) {
+// (__host__ too: kernels/items.h folds an item's billboard by it, on the device and in its host instantiation)
+__host__ __device__ inline void ray_fold(const P2 p, const P2 ru, const float near_s, const float4 L, const int l, RayFold& f) {
     const P2 v = p2(L.z - L.x, L.w - L.y);
     const P2 pq = p2(L.x, L.y) - p;
     const float d = cross(ru, v), nt = cross(pq, ru);
     const float ad = fabsf(d);
-    const float ntp = __uint_as_float(__float_as_uint(nt) ^ (__float_as_uint(d) & 0x80000000u));    // nt with d's sign taken out
+    const float ntp = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, nt) ^ (__builtin_bit_cast(unsigned, d) & 0x80000000u));    // nt with d's sign taken out
     if ((ad >= 1.e-3f) & (ntp <= ad) & (ntp >= -1e-30f*ad)) {
         const Isect q = intersect(p, ru, p2(L.x, L.y), v);
         const bool hit = (0 <= q.t) & (q.t <= 1);

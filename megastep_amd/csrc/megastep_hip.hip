@@ -7,7 +7,7 @@
 //   host/*.h      the host side of the C-ABI - argument checks, argument structs, launches, the ms_host_* / ms_test_* /
 //                 ms_debug_* hooks: common.h (what every family shares) first, then a file a family as under kernels/.
 //
-// Thirty-two kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty-four kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -87,6 +87,11 @@
 //                   lane + 64 j, each pair through the view fields' own predicates: which points each eye sees, how far and which
 //                   way, the count, and the nearest K by K rounds of a wave-wide minimum.
 //                                                            (no counterpart)
+//   item_collect_kernel, item_overlay_kernel   items: a wave an env takes the items in an agent's reach - a lane the items
+//                   lane + 64 j, the agents at uniform addresses, the walls walked only where a ballot finds an item in reach - and
+//                   settles timers, due flags and per-kind counts; a workgroup an origin builds the items' billboards once into
+//                   LDS and folds each of its rays over them by raycast_kernel's own ray_fold, over the planes a render or a
+//                   raycast wrote.   (no counterpart)
 //   nav_clear_kernel, nav_clear_query_kernel   clearance: the distance to the nearest wall - per cell, overhead_kernel's scheme on
 //                   the grid's 16 x 16 tiles (the env's static rows culled against the tile's box into LDS, a second cull by the
 //                   wave's own worst best while it folds); per point one wave, the lanes striding the rows (the other agents'
@@ -204,6 +209,7 @@ struct Probe {
 #include "kernels/navregion.h"
 #include "kernels/navview.h"
 #include "kernels/percept.h"
+#include "kernels/items.h"
 #include "kernels/navpath.h"
 #include "kernels/navpull.h"
 #include "kernels/navbasin.h"
@@ -229,4 +235,5 @@ struct Probe {
 #include "host/navmaps.h"
 #include "host/navsets.h"
 #include "host/sight.h"
+#include "host/items.h"
 #include "host/bake.h"

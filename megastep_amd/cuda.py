@@ -650,6 +650,7 @@ def _render_call(scenery, agents, fields, pooled, out, seen, config):
         result._spec = spec
         if seen is not None:
             result._struct.seen_stamp, result._struct.seen_epoch, result._struct.seen_count = seen_ptrs
+    result._scenery = scenery                                           # (overlay_items reads the envs' numbers of lines)
     _ab_switches()
     scenery._check_grid(dev)
     return dev, cfg, result
@@ -735,6 +736,7 @@ def _render_layout(n, a, r, fields, pooled, lit):
 from .envlogic import deathmatch_shoot, explorer_books
 from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
 from .percepts import PERCEPT_FIELDS, PERCEPT_MAX_EYES, PERCEPT_MAX_POINTS, PERCEPT_MAX_NEAREST, Percepts, percepts
+from .items import ITEM_MAX_ITEMS, ITEM_MAX_AGENTS, ITEM_MAX_KINDS, Items, Collected, items, collect_items, place_items, overlay_items
 from .cameras import PROJECTIONS, LOOK_FIELDS, Cameras, Look, shade, cameras, mounted, look
 from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans, _bounce
 from .scenarios import SCENARIO_MAX_SCENARIOS, SCENARIO_MAX_AGENTS, Scenarios, scenarios

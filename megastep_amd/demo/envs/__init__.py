@@ -5,3 +5,4 @@ from .pointgoal import PointGoal  # noqa: F401
 from .floorcoverage import FloorCoverage  # noqa: F401
 from .patrol import Patrol  # noqa: F401
 from .tag import Tag  # noqa: F401
+from .forage import Forage  # noqa: F401

@@ -435,6 +435,76 @@ class Percepts:
         return self._last_obs[e].clone()
 
 
+class Items:
+
+    def __init__(self, core, grid, n_items, values=(1.,), colors=None, radius=.1, reach=None, delay=32, source=None, gate=None, seed=0,
+                 kinds=None):
+        """Things the agents see, touch and collect (:func:`cuda.collect_items`, :func:`cuda.overlay_items`; no counterpart in the
+        reference): ``n_items`` items an env of ``len(values)`` kinds - item k is of kind ``k % len(values)`` unless ``kinds``
+        ((P,) or (n_env, P) integers) says otherwise - worth ``values[kind]`` to the agent that takes one. An agent takes an item by
+        coming within ``reach`` metres of it (default ``agent_radius + radius``) with no wall in between; the item is gone then and
+        returns ``delay`` steps later (negative: never) on a cell drawn by :func:`cuda.cell_draws` from ``source`` (default: the
+        free cells of ``grid``; a float32 layer is drawn where it is finite) through ``gate``. ``colors``: (3,), (P, 3) or
+        (n_env, P, 3) linear RGB, default white; ``radius``: half the width an item shows in a camera. All items start absent
+        and due: the first call puts them down.
+
+        ``positions`` - (n_env, P, 2), NaN where an item is absent - goes to ``Percepts(core, points=items.positions)`` and to
+        :func:`cuda.point_marks` as it is. A call is three launches and a select, keeps its buffers and never waits for the host:
+        it can sit in a HIP graph, and every replay draws afresh."""
+        self.core, self.grid = core, grid
+        self.values = torch.as_tensor(values, dtype=torch.float32, device=core.device).reshape(-1)
+        k = len(self.values)
+        if kinds is None:
+            kinds = torch.arange(int(n_items)) % k
+        self.store = cuda.items(core.n_envs, int(n_items), kinds=kinds, colors=colors, n_kinds=k, device=core.device)
+        self.radius = float(radius)
+        self.reach = float(core.agent_radius + radius if reach is None else reach)
+        self.delay, self.seed = int(delay), int(seed)
+        self._source, self._gate = grid if source is None else source, gate
+        self._collected = self._draws = self._dirs = self._shown = None
+
+    #: (n_env, P, 2) float32: where the items are, NaN for an absent one; the store's own tensor
+    positions = property(lambda self: self.store.positions)
+    #: the :class:`cuda.Collected` of the last call (None before the first)
+    collected = property(lambda self: self._collected)
+    space = property(lambda self: spaces.MultiVector(self.core.n_agents, 1))
+
+    @staticmethod
+    def reward(counts, values):
+        """The rule, a pure function: ``counts`` (N, A, K) integers, ``values`` (K,) -> (N, A) float32, ``counts.float() @ values``."""
+        return counts.float() @ values
+
+    def __call__(self, reset=None):
+        """Collect, draw, place: ``reset`` (n_env,) bool - the envs whose items are all drawn anew. Returns the (n_env, n_agent)
+        reward of this step."""
+        c = self.core
+        self._collected = cuda.collect_items(c.scenery, c.agents, self.store, self.reach, delay=self.delay, reset=reset, out=self._collected)
+        due = self._collected.due
+        if self._draws is None:
+            gate = {} if self._gate is None else dict(gate=self._gate)
+            band = dict(lo=-float('inf'), hi=torch.finfo(torch.float32).max) if cuda.cell_layer(self._source).is_float else {}
+            self._draws = cuda.cell_draws(self.grid, self._source, self.store.n_items, 1, seed=self.seed, mask=due, **band, **gate)
+            torch.where(due[:, :, None], self._draws.points[:, :, 0], self.store.positions, out=self.store.positions)
+        else:
+            cuda.place_items(self.store, self._draws, due)
+        return self.reward(self._collected.counts, self.values)
+
+    def draw(self, frame):
+        """Draws the items into ``frame`` - the :class:`cuda.Render` of the agents as they stand - in place
+        (:func:`cuda.overlay_items`); the frame gains ``.items``."""
+        agents = self.core.agents
+        if self._dirs is None:
+            self._dirs = torch.empty(agents.angles.shape + (self.core.res, 2), dtype=torch.float32, device=self.core.device)
+        cuda.camera_rays(agents, out=self._dirs)
+        if self._shown is None or self._shown.shape != frame.distances.shape:
+            self._shown = torch.empty(frame.distances.shape, dtype=torch.int32, device=self.core.device)
+        return cuda.overlay_items(self.store, frame, agents=agents, dirs=self._dirs, radius=self.radius, out_items=self._shown,
+                                  scenery=self.core.scenery)
+
+    def state(self, e=0):
+        return arrdict.arrdict(positions=self.store.positions[e].clone(), timers=self.store.timers[e].clone(), kinds=self.store.kinds[e].clone())
+
+
 def random_empty_positions(geometries, n_agents, n_points):
     """(n_geometries, n_agents, n_points, 2) randomly chosen free-cell centres, precomputed so respawns are cheap
     (reference: modules.py:272-296; consumes the global ``np.random`` in the same order, env by env). The free cells of

@@ -59,6 +59,7 @@ def raycast(scenery, origins, directions, agents=None, near=None, fields=None, o
     result = _result_for(out, (n, r, want, dev), 'a raycast', lambda: Raycast(*(
         torch.empty((n, r), dtype=torch.int32 if f in ('indices', 'agents') else torch.float32, device=dev) if f in want else None
         for f in RAYCAST_FIELDS)))
+    result._scenery = scenery                                           # (overlay_items reads the envs' numbers of lines)
     ptrs = [t.data_ptr() if t is not None else None for t in result._t]
     query = _lib.MsRaycast(r, origins.data_ptr(), directions.data_ptr(), float(near), *ptrs,
                            grid_rays.data_ptr() if grid_rays is not None else None)
@@ -69,17 +70,20 @@ def raycast(scenery, origins, directions, agents=None, near=None, fields=None, o
     return result
 
 
-def camera_rays(agents, config=None):
+def camera_rays(agents, config=None, out=None):
     """The direction vector of every ray :func:`render` casts, (N, A, res, 2) float32 - by the render's own device code (ray_y,
     reference kernels.cu:234-236,334-337). ``raycast(scenery, positions broadcast over the rays, camera_rays(agents),
     agents=agents)`` then gives the render's ``indices``, ``locations``, ``dots`` and ``distances`` bit for bit.
-    ``config``: see :func:`physics` (``res`` and ``fov`` are read)."""
+    ``config``: see :func:`physics` (``res`` and ``fov`` are read). ``out``: the tensor of an earlier call to write into."""
     dev = agents._dev
     if dev is None or dev.type != 'cuda':
         raise RuntimeError('megastep_amd kernels need GPU (HIP) tensors; the agents are on ' + str(dev or 'several devices'))
     cfg = _cfg(agents, config)
     n, a = agents.angles.shape
-    dirs = torch.empty((n, a, cfg.res, 2), dtype=torch.float32, device=dev)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, a, cfg.res, 2)
+                            or not out.is_contiguous() or out.device != dev):
+        raise RuntimeError(f'`out` must be a contiguous float32 tensor of shape {(n, a, cfg.res, 2)} on {dev}')
+    dirs = torch.empty((n, a, cfg.res, 2), dtype=torch.float32, device=dev) if out is None else out
     with _on(dev):
         _lib.check(_lib.lib().ms_camera_rays(C.byref(agents._plain), n, a, C.byref(cfg), C.c_void_p(dirs.data_ptr()), _stream(dev)))
     return dirs

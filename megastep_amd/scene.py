@@ -249,12 +249,13 @@ def line_half_width(metres_per_pixel):
     return max(.05, float(metres_per_pixel)/2**.5)
 
 
-def display(scenery, e=0, size=512, agents=None):
+def display(scenery, e=0, size=512, agents=None, items=None):
     """Env ``e`` from above as a ``(size, size, 3)`` uint8 image (the reference's ``scene.display``, scene.py:102-114,
     without matplotlib): the floorplan framed as ``plotting.extent(zoom=False)`` frames it, on the reference's background,
     drawn by :func:`cuda.overhead` with the baked light, gamma-encoded; the lights as yellow dots whose opacity is their
     normalised intensity (``plotting.plot_lights``). The agents are where the last render drew them, or with ``agents`` at
-    their current poses."""
+    their current poses. ``items``: a :class:`cuda.Items` (or a :class:`modules.Items`); its present items of env ``e`` are painted
+    as dots in their colours, the way the lights are. Without it the image is what it always was."""
     views = cuda.plan_views(scenery, size, envs=[e])
     g = views[0, 0].cpu().numpy().astype(np.float64)
     envs = torch.tensor([e], dtype=torch.int32, device=views.device)
@@ -271,4 +272,15 @@ def display(scenery, e=0, size=512, agents=None):
             alpha = (intensity - vmin)/(vmax - vmin)
             dot = (x - lx)**2 + (y - ly)**2 <= radius**2
             image[dot] = (1 - alpha)*image[dot] + alpha*np.array([1., 1., 0.])
+    if items is not None:
+        store = getattr(items, 'store', items)
+        where = store.positions[e].cpu().numpy().astype(np.float64)
+        colours = core.gamma_encode(np.clip(store.colors[e].cpu().numpy().astype(np.float64), 0, 1))
+        centres = np.arange(size) + .5
+        x = g[0]*centres[None, :] + g[1]*centres[:, None] + g[2]
+        y = g[3]*centres[None, :] + g[4]*centres[:, None] + g[5]
+        radius = max(.05, abs(g[0]))
+        for (ix, iy), colour in zip(where, colours):
+            if np.isfinite(ix) and np.isfinite(iy):
+                image[(x - ix)**2 + (y - iy)**2 <= radius**2] = colour
     return np.round(255*image).astype(np.uint8)
