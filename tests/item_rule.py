@@ -316,6 +316,59 @@ def hand_items(P, A, seed=0):
     return kept(('hand', P, A, seed), make)
 
 
+WIDE_SETS = ('sprinkled', 'late', 'full', 'on')
+OVERLAY_WINDOW = 256                                                        # item_overlay_kernel's WG: items a window, rays a chunk
+WIDE_RADIUS = .03                                                           # billboards thin enough that rays pass between a thousand
+
+
+def wide_items(P, which, A=3):
+    """hand_items(P, A) with more items than one window of item_overlay_kernel's compaction holds, present as `which` says:
+    'sprinkled' every fifth absent, as hand_items() has them; 'late' the first window's 256 all absent and every later one present;
+    'full' every item present; 'on' as 'sprinkled', with item 1 exactly on agent 0 and item 256 exactly on agent 1 (a NaN billboard
+    for that origin alone)."""
+    def make():
+        base = hand_items(P, A)
+        rng = np.random.RandomState(77 + P)
+        w = _World()
+        w.__dict__.update(base.__dict__)
+        w.positions = base.positions.copy()
+        if which in ('late', 'full'):
+            absent = np.isnan(w.positions[0, :, 0])
+            w.positions[0, absent] = rng.uniform((-.5, -.5), (8.5, 4.5), (absent.sum(), 2)).astype(F)
+        if which == 'late':
+            w.positions[0, :OVERLAY_WINDOW] = NAN
+        if which == 'on':
+            w.positions[0, 1], w.positions[0, OVERLAY_WINDOW] = base.agents[0, 0], base.agents[0, 1]
+        return w
+    assert which in WIDE_SETS and P > OVERLAY_WINDOW
+    return kept(('wide', P, which, A), make)
+
+
+def overlay_windows(positions, origin):
+    """The live billboards (no NaN: the item present and not exactly at `origin`) one origin keeps of an env's items ((P, 2)) in
+    each window of item_overlay_kernel's compaction, in the kernel's order; their sum is the `kept` its rays fold over."""
+    positions = np.asarray(positions, F)
+    live = ~np.isnan(positions).any(-1) & ~(positions == np.asarray(origin, F)).all(-1)
+    return [int(live[k0:k0 + OVERLAY_WINDOW].sum()) for k0 in range(0, len(live), OVERLAY_WINDOW)]
+
+
+def check_wide(w, which):
+    """The counted facts of wide_items(P, which), origin by origin: what each set is there to put the kernel through."""
+    P = w.positions.shape[1]
+    for a, origin in enumerate(w.agents[0]):
+        wins = overlay_windows(w.positions[0], origin)
+        assert len(wins) == -(-P//OVERLAY_WINDOW) >= 2
+        if which == 'sprinkled':
+            assert wins[0] % 64 and wins[0] < OVERLAY_WINDOW and all(wins), wins     # (the second window starts inside a wave's 64)
+        elif which == 'late':
+            assert wins[0] == 0 and all(wins[1:]) and sum(wins) == P - OVERLAY_WINDOW, wins
+        elif which == 'full':
+            assert sum(wins) == P, wins                                               # (P = 1024: the last slot of the LDS is written)
+        else:
+            plain = overlay_windows(hand_items(P, w.agents.shape[1]).positions[0], origin)
+            assert [x - y for x, y in zip(plain, wins)] == [[1, 0], [0, 1], [0, 0]][a] + [0]*(len(wins) - 2), (plain, wins)
+
+
 def wall_planes(walls, origins, dirs, near, widths, offset):
     """The planes a cast against the static walls leaves, numbered as the device numbers an env's lines (the agents' rows first:
     `offset` of them), with a screen of a flat grey where something was hit."""

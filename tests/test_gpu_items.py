@@ -125,6 +125,57 @@ def test_the_overlay_kernel_is_its_host_statement_on_the_hand_made_world(per, P)
     ir.same(_overlaid(cast), want, [k for k in OVERLAY_KEYS if k != 'screen'])
 
 
+@pytest.mark.parametrize('P', [257, 512, 1023, 1024])
+@pytest.mark.parametrize('per', [255, 256, 257, 600])
+def test_the_overlay_kernel_past_one_window_of_items_and_one_chunk_of_rays(per, P):
+    """item_overlay_kernel's compaction loop run two to four times (`kept` carried from window to window) and its rays in one to
+    three chunks, over item_rule.wide_items()' sets - whose counts, window by window, tests/test_item_host.py asserts and holds to
+    the rule; the host statement compacts serially and takes an origin's rays in one go."""
+    from megastep_amd import cuda
+    sc, agents = _box(3)
+    dirs = np.concatenate([ir.ring(per, phase=.37*a) for a in range(3)])[None]
+    chunks = -(-per//ir.OVERLAY_WINDOW)
+    for which in ir.WIDE_SETS:
+        w = ir.wide_items(P, which)
+        ir.check_wide(w, which)
+        each = np.repeat(w.agents, per, 1)
+        cast = cuda.raycast(sc, _dev(each), _dev(dirs), near=.1, fields=('indices', 'locations', 'dots', 'distances'))
+        want = ir.host_overlay(w.positions, w.colors, w.agents, dirs, ir.WIDE_RADIUS, .1, _np(sc.lines.widths), _planes(cast))
+        cuda.overlay_items(_store(w, 8), cast, origins=_dev(w.agents), dirs=_dev(dirs), near=.1, radius=ir.WIDE_RADIUS)
+        got = _overlaid(cast)
+        ir.same(got, want, [k for k in OVERLAY_KEYS if k != 'screen'])
+        shown = (got['items'] >= 0).reshape(3, per)
+        assert shown.any() and not shown.all(), which
+        # the rays of the last chunk (('late', 257): one item in all)
+        assert shown[:, (chunks - 1)*ir.OVERLAY_WINDOW:].any() or (which, P) == ('late', 257), which
+        if which == 'late':
+            assert got['items'][shown.reshape(1, -1)].min() >= ir.OVERLAY_WINDOW
+
+
+def test_the_overlay_kernel_in_three_chunks_beside_an_env_without_items():
+    """5 envs x 3 agents x 600 rays x 512 items: every origin's rays in three workgroups, each of which compacts two windows of
+    items; env 2 holds no present item (`kept == 0` in all three chunks of its origins)."""
+    from megastep_amd import cuda
+    c, w = _plan_world(512, 3, 600)
+    positions = w.positions[:5].copy()
+    positions[2] = np.nan
+    for n in (0, 1, 3, 4):
+        assert all(ir.overlay_windows(positions[n], o)[1] > 0 for o in w.agents[n])
+    assert sum(ir.overlay_windows(positions[2], w.agents[2, 0])) == 0
+    store = cuda.Items(_dev(positions), _dev(w.timers[:5]), _dev(w.kinds[:5]), _dev(w.colors[:5]), 3)
+    origins, dirs = _dev(w.agents[:5]), _dev(w.dirs[:5])
+    cast = cuda.raycast(c.scenery, origins.repeat_interleave(600, 1).contiguous(), dirs, near=.1,
+                        fields=('indices', 'locations', 'dots', 'distances'))
+    before = _planes(cast)
+    want = ir.host_overlay(positions, w.colors[:5], w.agents[:5], w.dirs[:5], .1, .1, _np(c.scenery.lines.widths), before)
+    cuda.overlay_items(store, cast, origins=origins, dirs=dirs, near=.1)
+    got = _overlaid(cast)
+    ir.same(got, want, [k for k in OVERLAY_KEYS if k != 'screen'])
+    assert (got['items'][2] == -1).all() and np.array_equal(ir.bits(got['distances'][2]), ir.bits(before['distances'][2]))
+    last = (got['items'] >= 0).reshape(5, 3, 600)[:, :, 2*ir.OVERLAY_WINDOW:]
+    assert last[[0, 1, 3, 4]].any((-1, -2)).all() and (got['items'] >= ir.OVERLAY_WINDOW).any()         # (every env's last chunks)
+
+
 @pytest.mark.parametrize('res', [64, 37])
 def test_the_overlay_on_a_real_render(res):
     """5 envs x 3 agents x res rays: every plane of the Render, screen included, and the items plane."""

@@ -150,7 +150,8 @@ def scheme():
 @pytest.mark.parametrize('n_agents,others,grid', [(1, None, True), (3, 'rest', True), (2, 'rest', False)])
 def test_either_scheme_leaves_the_same_bits(scheme, n_agents, others, grid):
     """A lane a candidate (the library's) against a lane a wall, the candidates one after another (physics_kernel's scheme): with a
-    wall grid and without, lists longer than a flush of the pair list leaves room for, K past one wave and not a multiple of it."""
+    wall grid and without, lists longer than a flush of the pair list leaves room for (the list's lengths window by window are
+    counted in tests/test_gpu_step_edges.py::test_the_rollouts_list_at_its_capacity), K past one wave and not a multiple of it."""
     from megastep_amd import cuda
     N, K, H = 11, 100, 5
     c, _ = _world(N, n_agents, seed=13, n_unique=5, grid=grid)

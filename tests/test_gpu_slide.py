@@ -112,7 +112,8 @@ def _mixed(p):
 @pytest.mark.parametrize('n_envs,n_agents', [(37, 1), (9, 4), (3, 5), (2, 64)])
 def test_the_kernel_is_the_host_statement_on_plans(n_envs, n_agents, grid):
     """(3, 5): beyond PHYS_FEW; five agents' near lists - a dozen rows or two each - and 64 agents' are more than 64 (row, agent)
-    pairs an env: the cull-first, compact-in-LDS path. Three steps on: the second from the state the first left."""
+    pairs an env: the cull-first, compact-in-LDS path (how many pairs, and the list at its capacity, are counted in
+    tests/test_gpu_step_edges.py::test_the_deals_list_at_its_capacity). Three steps on: the second from the state the first left."""
     c, _ = _world(n_envs, n_agents, seed=4 + n_agents, n_unique=min(n_envs, 6), grid=grid)
     assert (c.scenery._wg is not None) == grid
     rng = np.random.RandomState(5)

@@ -176,6 +176,35 @@ def test_the_overlay_is_the_rule_on_the_hand_made_world(per, P):
     ir.same(again, want, OVERLAY_KEYS)
 
 
+@pytest.mark.parametrize('P', [257, 512, 1023, 1024])
+@pytest.mark.parametrize('per', [255, 256, 257, 600])
+def test_the_wide_item_sets_hold_what_they_are_named_for(per, P):
+    """The sets tests/test_gpu_items.py puts item_overlay_kernel's second window and second chunk through: their counts, window by
+    window, and - over the box's walls as the numpy cast leaves them - rays of every origin and of the last chunk that show an item."""
+    w0 = ir.hand_items(P, 3)
+    dirs, base = _hand_rays(w0, per)
+    chunks = -(-per//ir.OVERLAY_WINDOW)
+    for which in ir.WIDE_SETS:
+        w = ir.wide_items(P, which)
+        ir.check_wide(w, which)
+        got = ir.host_overlay(w.positions, w.colors, w.agents, dirs, ir.WIDE_RADIUS, .1, w.widths, base)
+        shown = (got['items'] >= 0).reshape(3, per)
+        assert shown.any() and not shown.all(), which
+        assert shown[:, (chunks - 1)*ir.OVERLAY_WINDOW:].any() or (which, P) == ('late', 257), which     # ('late', 257): one item in all
+
+
+@pytest.mark.parametrize('P', [257, 512, 1023, 1024])
+@pytest.mark.parametrize('per', [257, 600])
+def test_the_overlay_is_the_rule_on_the_wide_item_sets(per, P):
+    w0 = ir.hand_items(P, 3)
+    dirs, base = _hand_rays(w0, per)
+    for which in ir.WIDE_SETS:
+        w = ir.wide_items(P, which)
+        want = _both_overlay(w.positions, w.colors, w.agents, dirs, ir.WIDE_RADIUS, .1, w.widths, base)
+        if which == 'on':                                                # (the item under an origin is never what that origin sees)
+            assert not (want['items'].reshape(3, per)[0] == 1).any() and not (want['items'].reshape(3, per)[1] == ir.OVERLAY_WINDOW).any()
+
+
 def test_the_overlay_is_the_rule_on_the_six_plans():
     w = ir.plan_items()
     base = ir.wall_planes(w.walls, w.agents, w.dirs, .1, w.widths, 6)
