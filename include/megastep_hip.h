@@ -1541,6 +1541,75 @@ typedef struct MsItemOverlay {
 } MsItemOverlay;
 int ms_item_overlay(const MsScenery* scenery, const MsItemOverlay* overlay, void* hip_stream);
 
+/* Scent fields: a per-cell quantity that something leaves behind, that spreads through doorways and round corners but not through
+ * walls, and that fades - a runner's trail, the smell of an item behind a door, "somebody was here recently".  The one store of
+ * the nav family that EVOLVES: a call is one tick.  Every step below is one binary32 operation, in the order written, without
+ * contraction, underflow gradual; tests/scent_rule.py restates it in numpy and the kernels - and their host instantiations,
+ * ms_host_nav_scent and ms_host_nav_scent_query - are held to EQUALITY with it.  DESIGN.md section 3.35.  c, geom, starts and
+ * free_cells are MsNavGrid's; a cell is OPEN when free_cells[k] & 1.
+ *   stores        G per env in the fields' layout: store (n, g) starts at G*starts[n] + g*nx*ny, row-major, row 0 at the lowest
+ *                 y - a float MsNavLayer as it is.  A new store is all 0.f; between calls it holds what the last call left.
+ * ms_nav_scent is one tick of every store that mask (N, G) marks (NULL: all); the others keep values, peaks and scented:
+ *   1 reset       a store marked in reset (N, G) (NULL: none) is set to 0.f everywhere.
+ *   2 deposit     P sources per env, 0 <= P <= 1024: points (N, P, 2), amounts (N, P), field (N, P) - the store each source
+ *                 feeds; NULL: MsNavLayer's rule, store 0 when G == 1, else G == P and source k feeds store k.  The cell under
+ *                 a point is found as MsNavSeen finds it: fx = floorf(x/c), fy = floorf(y/c), no cell when either is a NaN or
+ *                 |.| >= 2^30, else j = (int)fx - jx0, i = (int)fy - iy0, no cell outside the grid.  A source deposits nothing
+ *                 when it has no cell, its cell is closed, its field index is outside [0, G), or its amount is not > 0.f (a
+ *                 NaN included).  The others are applied IN ASCENDING k: V[cell] = fl(V[cell] + amount_k) - two sources on one
+ *                 cell add in a fixed order.
+ *   3 sub-steps   T = substeps of them, each a Jacobi sweep - every new value from the old store only.  For an open cell with
+ *                 value x: s = 0.f; for the neighbours west, east, south, north (k - 1, k + 1, k - nx, k + nx; rows do not
+ *                 wrap), each that is in the grid and open and holds y: s = fl(s + fl(y - x)); then
+ *                 v = fl(fl(x + fl(rate*s))*keep), and the new value is v >= floor ? v : 0.f.  A closed cell holds 0.f.
+ *   4 summary     rewritten for every computed store: peaks (N, G) the largest value, 0.f without an open cell; scented (N, G)
+ *                 int32 the cells with a value > 0.f.  Both are order-independent.
+ *   no value is ever negative, -0.f or a NaN (given a store that held none): every flux term fl(y - x) is at least -x, so
+ *                 s >= -4x; rate <= 0.25 and monotone rounding give fl(rate*s) >= -x and fl(x + fl(rate*s)) >= +0.f; keep >= 0
+ *                 keeps the sign.  An implementation may therefore mark closed cells in the value store itself with a negative
+ *                 number, which nav_scent_kernel does in LDS.
+ * Limits, else MS_EINVAL: G >= 1; 0 <= P <= 1024 (P > 0: points, amounts present, points 8-byte aligned, field given or G == 1 or
+ * G == P); 0 <= rate <= 0.25f; 0 <= keep <= 1; floor >= 0 and finite; 1 <= substeps <= 64; values, peaks, scented present;
+ * workspace - as large as values, not values itself - may be NULL only when grid->max_framed fits the kernel's largest LDS
+ * (40 944 framed cells); every float and int pointer 4-byte aligned.  MS_EUNSUPPORTED: N*G beyond 2^31 - 1.
+ * One launch, one workgroup per store, the store resident in LDS while it fits; a larger one is swept between values and
+ * workspace in global memory and ends in values, to the same bits.  (An env larger than max_framed says, in a call without a
+ * workspace, is left as it is and reports 0 and 0.)  Integer atomics only.
+ * ms_nav_scent_query: P >= 1 points per env, field as above, the cell as above.  out (N, P) holds the cell's value, 0.f without a
+ * cell, on a closed cell and for a bad field index; gradients (N, P, 2), or NULL, the central differences with zero-flux sides:
+ * e the east neighbour's value when it is in the grid and open, else x; w, s, n likewise; gx = fl(fl(e - w)/fl(2.f*c)),
+ * gy = fl(fl(n - s)/fl(2.f*c)); (0, 0) where out is forced to 0.f.  One launch, a lane a point.
+ * All outputs are the caller's; nothing is allocated, nothing waits for the host: both calls can be captured in a HIP graph.  Every
+ * argument is checked in full before the launch. */
+typedef struct MsNavScent {
+    int                  n_fields;     /* G: stores per env                                                            */
+    int                  n_sources;    /* P: sources per env (0 .. 1024)                                               */
+    const float*         points;       /* (N, P, 2) x, y; 8-byte aligned (P == 0: not looked at)                       */
+    const float*         amounts;      /* (N, P)                                                                       */
+    const int*           field;        /* (N, P) the store each source feeds; NULL: G == 1 or G == P                   */
+    const unsigned char* reset;        /* (N, G) non-zero: clear the store first; NULL: none                           */
+    const unsigned char* mask;         /* (N, G) non-zero: tick this store; NULL: all                                  */
+    float                rate;         /* 0 .. 0.25f                                                                   */
+    float                keep;         /* 0 .. 1: what a sub-step leaves of a value                                    */
+    float                floor;        /* >= 0, finite: a smaller value becomes 0.f                                    */
+    int                  substeps;     /* T: 1 .. 64                                                                   */
+    float*               values;       /* G*starts[N] floats in / out                                                  */
+    float*               workspace;    /* as values, or NULL where max_framed fits the largest LDS                     */
+    float*               peaks;        /* (N, G) out                                                                   */
+    int*                 scented;      /* (N, G) out                                                                   */
+} MsNavScent;
+typedef struct MsNavScentQuery {
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y; 8-byte aligned                                               */
+    const int*           field;        /* (N, P) the store each point asks; NULL: G == 1 or G == P                     */
+    const float*         values;       /* as MsNavScent.values                                                         */
+    int                  n_fields;     /* G of `values`                                                                */
+    float*               out;          /* (N, P) the value under each point                                            */
+    float*               gradients;    /* (N, P, 2) out, or NULL                                                       */
+} MsNavScentQuery;
+int ms_nav_scent(const MsNavGrid* grid, const MsNavScent* scent, void* hip_stream);
+int ms_nav_scent_query(const MsNavGrid* grid, const MsNavScentQuery* query, void* hip_stream);
+
 /* Builds the wall grid (MsScenery.wg_*): per level of cells two launches with a prefix sum by the caller in between.
  *   ms_wallgrid_scan  for every cell of every env listed in `reps` (the representatives, MsScenery.env_geom; n_reps of
  *                     them) works out which static walls belong on the cell's lists: one bit per wall into `bits` - the

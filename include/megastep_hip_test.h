@@ -155,6 +155,16 @@ int ms_host_nav_regions(const MsNavGrid* grid, const MsNavRegions* regions);
 int ms_host_nav_region_query(const MsNavGrid* grid, const MsNavRegionQuery* query);
 int ms_host_nav_region_masks(const MsNavGrid* grid, const MsNavRegionMasks* masks);
 int ms_host_nav_region_capacity(int* capacities);
+/* Host instantiations of the scent fields' rule (kernels/navscent.h: one cell's new value from its five reads, the cell under a
+ * source, the deposit test and the gradient - the very functions every lane of nav_scent_kernel and nav_scent_query_kernel
+ * evaluates) for one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the argument struct is host
+ * memory.  ms_host_nav_scent ticks a store on a framed copy with the kernel's sentinel when it fits the LDS of the launch
+ * ms_nav_scent would choose by grid->max_framed, else between its `values` and its `workspace` - the kernel's two paths.  They
+ * return what the device entries would: MS_OK, or MS_EINVAL for arguments they would refuse.  ms_host_nav_scent_capacity writes
+ * the three capacities, in framed cells, of nav_scent_kernel's instantiations. */
+int ms_host_nav_scent(const MsNavGrid* grid, const MsNavScent* scent);
+int ms_host_nav_scent_query(const MsNavGrid* grid, const MsNavScentQuery* query);
+int ms_host_nav_scent_capacity(int* capacities);
 /* Host instantiations of the basins' rule (kernels/navbasin.h: a cell's successor through nav_hop, the jump, the label, the anchor
  * nav_start picks and a point's marks - the very functions every lane of nav_basin_kernel, nav_basin_query_kernel and
  * nav_point_mark_kernel evaluates) for one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the

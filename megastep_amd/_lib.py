@@ -274,6 +274,17 @@ class MsItemOverlay(C.Structure):
                 ('indices', C.c_void_p), ('locations', C.c_void_p), ('dots', C.c_void_p), ('screen', C.c_void_p), ('items', C.c_void_p)]
 
 
+class MsNavScent(C.Structure):
+    _fields_ = [('n_fields', C.c_int), ('n_sources', C.c_int), ('points', C.c_void_p), ('amounts', C.c_void_p), ('field', C.c_void_p),
+                ('reset', C.c_void_p), ('mask', C.c_void_p), ('rate', C.c_float), ('keep', C.c_float), ('floor', C.c_float),
+                ('substeps', C.c_int), ('values', C.c_void_p), ('workspace', C.c_void_p), ('peaks', C.c_void_p), ('scented', C.c_void_p)]
+
+
+class MsNavScentQuery(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('field', C.c_void_p), ('values', C.c_void_p), ('n_fields', C.c_int),
+                ('out', C.c_void_p), ('gradients', C.c_void_p)]
+
+
 class MsNavClearance(C.Structure):
     _fields_ = [('max_range', C.c_float), ('n_radii', C.c_int), ('radii', C.c_float*8), ('max_tiles', C.c_int), ('mask', C.c_void_p),
                 ('values', C.c_void_p), ('nearest', C.c_void_p), ('fits', C.c_void_p)]
@@ -327,6 +338,8 @@ PROTOTYPES = {
     'ms_percepts': (_int, [_p(MsScenery), _p(MsPercepts), _ptr]),
     'ms_item_collect': (_int, [_p(MsScenery), _p(MsAgents), _p(MsItemCollect), _ptr]),
     'ms_item_overlay': (_int, [_p(MsScenery), _p(MsItemOverlay), _ptr]),
+    'ms_nav_scent': (_int, [_p(MsNavGrid), _p(MsNavScent), _ptr]),
+    'ms_nav_scent_query': (_int, [_p(MsNavGrid), _p(MsNavScentQuery), _ptr]),
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
     'ms_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery), _ptr]),
     'ms_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks), _ptr]),
@@ -379,6 +392,9 @@ PROTOTYPES = {
     'ms_host_nav_region_query': (_int, [_p(MsNavGrid), _p(MsNavRegionQuery)]),
     'ms_host_nav_region_masks': (_int, [_p(MsNavGrid), _p(MsNavRegionMasks)]),
     'ms_host_nav_region_capacity': (_int, [_ptr]),
+    'ms_host_nav_scent': (_int, [_p(MsNavGrid), _p(MsNavScent)]),
+    'ms_host_nav_scent_query': (_int, [_p(MsNavGrid), _p(MsNavScentQuery)]),
+    'ms_host_nav_scent_capacity': (_int, [_ptr]),
     'ms_host_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins)]),
     'ms_host_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery)]),
     'ms_host_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks)]),

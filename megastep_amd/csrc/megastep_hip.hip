@@ -7,7 +7,7 @@
 //   host/*.h      the host side of the C-ABI - argument checks, argument structs, launches, the ms_host_* / ms_test_* /
 //                 ms_debug_* hooks: common.h (what every family shares) first, then a file a family as under kernels/.
 //
-// Thirty-four kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty-six kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -92,6 +92,10 @@
 //                   settles timers, due flags and per-kind counts; a workgroup an origin builds the items' billboards once into
 //                   LDS and folds each of its rays over them by raycast_kernel's own ray_fold, over the planes a render or a
 //                   raycast wrote.   (no counterpart)
+//   nav_scent_kernel, nav_scent_query_kernel   scent fields: one workgroup per store keeps it in LDS, a float a framed cell with a
+//                   negative sentinel on the frame and the closed cells, applies the deposits wave by wave in the rule's order and
+//                   runs the sub-steps of the diffusion with each lane's cells in registers between two barriers; per point the
+//                   value and its central differences, a lane each.   (no counterpart)
 //   nav_clear_kernel, nav_clear_query_kernel   clearance: the distance to the nearest wall - per cell, overhead_kernel's scheme on
 //                   the grid's 16 x 16 tiles (the env's static rows culled against the tile's box into LDS, a second cull by the
 //                   wave's own worst best while it folds); per point one wave, the lanes striding the rows (the other agents'
@@ -207,6 +211,7 @@ struct Probe {
 #include "kernels/navfield.h"
 #include "kernels/navclear.h"
 #include "kernels/navregion.h"
+#include "kernels/navscent.h"
 #include "kernels/navview.h"
 #include "kernels/percept.h"
 #include "kernels/items.h"
@@ -234,6 +239,7 @@ struct Probe {
 #include "host/nav.h"
 #include "host/navmaps.h"
 #include "host/navsets.h"
+#include "host/navscent.h"
 #include "host/sight.h"
 #include "host/items.h"
 #include "host/bake.h"

@@ -505,6 +505,42 @@ class Items:
         return arrdict.arrdict(positions=self.store.positions[e].clone(), timers=self.store.timers[e].clone(), kinds=self.store.kinds[e].clone())
 
 
+class Scent:
+
+    def __init__(self, core, grid, amount=1., own=False, **scent_args):
+        """A scent the agents leave and smell (:func:`cuda.scent_fields`; no counterpart in the reference): every call each agent
+        deposits ``amount`` on the cell it stands on - into one store an env that all share, or with ``own=True`` into a store of its
+        own - and the stores tick once: the scent spreads through the open cells, round corners but not through walls, and fades.
+        ``scent_args`` are :func:`cuda.scent_fields`' (``rate``, ``keep``, ``substeps``, ``floor``). A call is one launch, keeps its
+        buffers and never waits for the host: it can sit in a HIP graph."""
+        self.core, self.grid, self.own = core, grid, bool(own)
+        self.fields = cuda.scent_fields(grid, n_fields=core.n_agents if own else 1, **scent_args)
+        self._amounts = torch.full((core.n_envs, core.n_agents), float(amount), dtype=torch.float32, device=core.device)
+        self._reset = torch.zeros((core.n_envs, self.fields.n_fields), dtype=torch.bool, device=core.device)
+        self._sniff = None
+
+    space = property(lambda self: spaces.MultiVector(self.core.n_agents, 3))
+
+    def __call__(self, reset=None):
+        """Deposit and tick: ``reset`` (n_env,) bool - the envs whose stores are cleared first. Returns the :class:`cuda.ScentFields`."""
+        if reset is not None:
+            self._reset.copy_(reset[:, None].expand_as(self._reset))
+        return self.fields.step(self.core.agents.positions, self._amounts, reset=None if reset is None else self._reset)
+
+    @staticmethod
+    def pack(values, gradients, angles):
+        """The rule, a pure function: ``values`` (N, A), ``gradients`` (N, A, 2) in the world frame, ``angles`` (N, A) degrees ->
+        (N, A, 3): the value and the gradient in the agent's frame."""
+        return torch.cat([values[..., None], to_local_frame(angles, gradients)], -1)
+
+    def observation(self):
+        """(n_env, n_agent, 3) float32: the scent under each agent - of the shared store, or of its own - and its gradient turned
+        into the agent's frame."""
+        agents = self.core.agents
+        self._sniff = self.fields.sniff(agents.positions, out=self._sniff)
+        return self.pack(self._sniff.values, self._sniff.gradients, agents.angles)
+
+
 def random_empty_positions(geometries, n_agents, n_points):
     """(n_geometries, n_agents, n_points, 2) randomly chosen free-cell centres, precomputed so respawns are cheap
     (reference: modules.py:272-296; consumes the global ``np.random`` in the same order, env by env). The free cells of

@@ -962,9 +962,10 @@ def cell_layer(values, n_fields=1, field=None):
     ``n_fields`` is 1 and view p reads store p when ``n_fields`` is the number of views. A :class:`NavGrid` (its ``free``), a
     :class:`SeenMaps`, a :class:`DistanceFields` and a :class:`SeededFields` are layers as they are, with their own number of
     stores, an :class:`AgeMaps` too (its ``ages``, in ticks; as a gate its ``stale``), and so are a :class:`Regions` (its ``areas``, square metres), a :class:`ViewFields` (its ``values``, a store a
-    viewpoint) and a :class:`ClearanceFields` (its ``values``, metres to the nearest wall: one float store);
+    viewpoint), a :class:`ClearanceFields` (its ``values``, metres to the nearest wall: one float store) and a :class:`ScentFields` (its ``values``);
     ``cell_layer(maps, field=slot)`` gives one of them a ``field``. An int32 tensor makes a layer of labels, which only
     :func:`zones` takes."""
+    from .scents import ScentFields                                      # (scents.py imports this module)
     if isinstance(values, CellLayer):
         values, n_fields = values.values, values.n_fields
     elif isinstance(values, NavGrid):
@@ -983,6 +984,8 @@ def cell_layer(values, n_fields=1, field=None):
         values, n_fields = values.values, values.n_points
     elif isinstance(values, ClearanceFields):
         values, n_fields = values.values, 1
+    elif isinstance(values, ScentFields):
+        values, n_fields = values.values, values.n_fields
     if not isinstance(n_fields, int) or n_fields < 1:
         raise RuntimeError(f'n_fields must be a positive integer; got {n_fields}')
     if not isinstance(values, torch.Tensor) or values.dtype not in (torch.uint8, torch.bool, torch.float32, torch.int32) or values.ndim != 1 or \
