@@ -1541,6 +1541,77 @@ typedef struct MsItemOverlay {
 } MsItemOverlay;
 int ms_item_overlay(const MsScenery* scenery, const MsItemOverlay* overlay, void* hip_stream);
 
+/* Projectiles: things that fly, bounce off walls and strike agents - a thrown ball, a dodgeable bullet, a puck.  A store the caller
+ * owns, shaped as the items' (a slot is PRESENT exactly when both coordinates of its position are finite, an absent one holds
+ * (NaN, NaN): ms_item_overlay, ms_percepts and ms_nav_point_marks take `positions` as they are), and one call a step that moves it.
+ * Every step below is one binary32 operation, in the order given, without contraction; tests/projectile_rule.py restates it in
+ * numpy and the kernel - and its host instantiation, ms_host_projectiles - is held to EQUALITY with it.  DESIGN.md section 3.36.
+ * The store, P = A*S slots an env, agent a's the slots a*S .. a*S + S - 1 (1 <= A <= 64, 1 <= S <= 16, P <= 1024):
+ *   positions (N, P, 2); velocities (N, P, 2) metres a second; owners (N, P) int32; timers (N, P) int32 - the ticks left to a
+ *   present projectile (one that starts a tick at 0 or below never runs out); bounces (N, P) int32 - the bounces left to it.
+ * ms_projectiles is one tick, env by env:
+ *   1 reset     reset[n] != 0 ((N,) bytes; NULL: none): every slot of the env becomes absent, its timer and bounces 0, struck -1,
+ *               ended 4; hits, scored and misfires of the env 0.  Nothing else happens to the env in this call.
+ *   2 fire      for every agent a with fire[n, a] != 0 ((N, A) bytes; NULL: none) whose angle and position are finite: the slot
+ *               is the least-numbered absent one among the agent's S as the store stands when the call begins; without one
+ *               nothing is fired and misfires[n, a] = 1 (0 in every other case).  (s, c) = sincospi_f(angle/180) - the heading
+ *               as ms_raycast evaluates it; position = (ax + muzzle*c, ay + muzzle*s); velocity = (speed*c, speed*s); owner = a,
+ *               timer = life, bounces = n_bounces.  A projectile fired in this call flies in this call.
+ *   3 fly       every present projectile at p with velocity v: u = v/fps per component; r = (|ux| + |uy|)*1.01f + 1e-3f; its REACH
+ *               BOX [px - r, px + r] x [py - r, py + r] is fixed for the tick; left = 1.f; then at most 4 LEGS:
+ *       ray     ru = (v/fps)*left, rlen = sqrtf(ru.x*ru.x + ru.y*ru.y); a leg with rlen == 0 or a NaN ends the flight where it is.
+ *       fold    from the state (s, idx) = (1.001f, -1), with near_plane 0, by the very function ms_raycast folds its lines with:
+ *               first the agents' rows a*M + m ascending, drawn from the poses as they stand (ms_render's arithmetic), the rows
+ *               of the projectile's own `owner` left out; then the env's static rows l ascending (numbered as MsScenery's, from
+ *               A*M), those whose box meets the reach box - no coordinate a NaN, min(x0, x1) <= bx1 && max(x0, x1) >= bx0, the
+ *               same in y - and that the previous leg of this flight did not end on.
+ *       no hit  p += ru; the flight ends, ended 0.
+ *       a body  (idx < A*M) struck = idx/M; the slot becomes absent, ended 1.
+ *       a wall  with bounces == 0: the slot becomes absent, ended 2.  With bounces > 0: s1 = min(s, 1.f);
+ *               p += ru*max(s1 - 1e-3f/rlen, 0.f) - a millimetre short of the wall and never behind where it was; bounces -= 1;
+ *               left = left*(1.f - s1); with the wall's direction w = (x1 - x0, y1 - y0) and n = (-w.y, w.x):
+ *               k = ((1.f + restitution)*(v.x*n.x + v.y*n.y))/(n.x*n.x + n.y*n.y), v = v - k*n; the next leg starts.  What is
+ *               left after the fourth leg is dropped.
+ *       timer   a projectile still present has timer -= 1; at 0 it becomes absent, ended 3.
+ *   struck      (N, P): the agent the projectile hit in this call, else -1.    ended (N, P) bytes: 0 still flying, 1 struck an
+ *               agent, 2 stopped by a wall, 3 ran out of time, 4 the slot was absent going into the fly step.
+ *   hits        (N, A): the projectiles that struck agent a in this call.      scored (N, A): the projectiles of owner a that
+ *               struck someone (an owner outside [0, A) scores nowhere).
+ * Projectiles do not meet each other; bodies are the agents' model rows as ms_raycast sees them.  An absent slot keeps its
+ * velocity, owner, timer and bounces.  Every output has one writer and one definition and the counts are integers.  struck, ended,
+ * hits, scored and misfires may each be NULL (not wanted).
+ * Refused before any launch (MS_EINVAL): a NULL agents, positions, velocities, owners, timers or bounces; agents' positions, the
+ * store's positions or velocities not 8-byte aligned, an int or float pointer not 4-byte aligned; A, S or P outside the limits or
+ * P != A*S; speed, muzzle or fps not positive and finite; restitution outside [0, 1]; life < 1; n_bounces < 0.
+ * MS_EUNSUPPORTED: A*M beyond 1024.
+ * One launch, a workgroup an env, a lane the slots lane + 256 j: the shots go through LDS, the agents' rows are drawn once into
+ * LDS, the static rows that meet the union of the env's reach boxes are listed in LDS (512; an env that keeps more walks its rows
+ * in global memory, to the same bits), the legs are flown wave by wave while any lane has one; integer LDS atomics for hits and
+ * scored.  Nothing allocated, nothing waits: the call can be captured in a HIP graph. */
+typedef struct MsProjectiles {
+    int                  n_slots;        /* P = A*S: slots per env (1 .. 1024)                                             */
+    int                  per_agent;      /* S: slots per agent (1 .. 16)                                                   */
+    float*               positions;      /* (N, P, 2) in/out; 8-byte aligned                                               */
+    float*               velocities;     /* (N, P, 2) in/out; 8-byte aligned                                               */
+    int*                 owners;         /* (N, P) in/out                                                                  */
+    int*                 timers;         /* (N, P) in/out                                                                  */
+    int*                 bounces;        /* (N, P) in/out                                                                  */
+    const unsigned char* fire;           /* (N, A) non-zero: the agent fires; NULL: nobody                                 */
+    const unsigned char* reset;          /* (N,) non-zero: empty the env's store; NULL: none                               */
+    float                speed;          /* of a shot, metres a second (> 0, finite)                                       */
+    float                muzzle;         /* how far in front of its agent a shot starts, metres (> 0, finite)              */
+    int                  life;           /* the timer of a shot (>= 1)                                                     */
+    int                  n_bounces;      /* the bounces of a shot (>= 0)                                                   */
+    float                restitution;    /* 0 .. 1: what a bounce keeps of the speed into the wall                         */
+    float                fps;            /* ticks a second (> 0, finite): MsConfig's                                       */
+    int*                 struck;         /* (N, P) out, or NULL                                                            */
+    unsigned char*       ended;          /* (N, P) out, or NULL                                                            */
+    int*                 hits;           /* (N, A) out, or NULL                                                            */
+    int*                 scored;         /* (N, A) out, or NULL                                                            */
+    unsigned char*       misfires;       /* (N, A) out, or NULL                                                            */
+} MsProjectiles;
+int ms_projectiles(const MsScenery* scenery, const MsAgents* agents, const MsProjectiles* projectiles, void* hip_stream);
+
 /* Scent fields: a per-cell quantity that something leaves behind, that spreads through doorways and round corners but not through
  * walls, and that fades - a runner's trail, the smell of an item behind a door, "somebody was here recently".  The one store of
  * the nav family that EVOLVES: a call is one tick.  Every step below is one binary32 operation, in the order written, without

@@ -211,6 +211,16 @@ int ms_host_percepts(const MsPercepts* percepts, int n_envs, const float* walls,
 int ms_host_item_collect(const MsItemCollect* collect, int n_envs, int n_agents, const float* agent_positions, const float* walls,
                          const long long* wall_starts);
 int ms_host_item_overlay(const MsItemOverlay* overlay, int n_envs, const int* lines_widths);
+/* Host instantiation of the projectiles' rule (kernels/projectile.h: the pose and the shot, the reach box and the row test, the
+ * leg's ray, ray_fold itself, the leg's end with its bounce, the settling of a slot - the very functions every lane of
+ * projectile_kernel evaluates) for one whole call of ms_projectiles on HOST arrays, swept serially: every pointer of `projectiles`
+ * is host memory.  In place of an MsScenery and an MsAgents there are n_envs, n_agents, `agent_positions` (N, A, 2),
+ * `agent_angles` (N, A), `model` - the n_model rows of an agent's body in its own frame, four floats each - and `walls`, the STATIC
+ * rows of all envs, four floats each, env n's rows wall_starts[n] .. wall_starts[n + 1] - 1 (a static row counts from
+ * n_agents*n_model, as on the device).  Returns what ms_projectiles would: MS_OK, or MS_EINVAL / MS_EUNSUPPORTED for arguments
+ * it would refuse (and for n_envs < 1, a NULL model, walls or wall_starts, model or walls not 16-byte aligned). */
+int ms_host_projectiles(const MsProjectiles* projectiles, int n_envs, int n_agents, const float* agent_positions, const float* agent_angles,
+                        const float* model, int n_model, const float* walls, const long long* wall_starts);
 /* Host instantiations of the clearance rule (kernels/navclear.h: the tile's box, the list, ov_keeps and ov_fold, the second cull,
  * the winner's order and the stores - the very functions every lane of nav_clear_kernel and nav_clear_query_kernel evaluates) for
  * one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the argument struct is host memory.

@@ -274,6 +274,13 @@ class MsItemOverlay(C.Structure):
                 ('indices', C.c_void_p), ('locations', C.c_void_p), ('dots', C.c_void_p), ('screen', C.c_void_p), ('items', C.c_void_p)]
 
 
+class MsProjectiles(C.Structure):
+    _fields_ = [('n_slots', C.c_int), ('per_agent', C.c_int), ('positions', C.c_void_p), ('velocities', C.c_void_p), ('owners', C.c_void_p),
+                ('timers', C.c_void_p), ('bounces', C.c_void_p), ('fire', C.c_void_p), ('reset', C.c_void_p), ('speed', C.c_float),
+                ('muzzle', C.c_float), ('life', C.c_int), ('n_bounces', C.c_int), ('restitution', C.c_float), ('fps', C.c_float),
+                ('struck', C.c_void_p), ('ended', C.c_void_p), ('hits', C.c_void_p), ('scored', C.c_void_p), ('misfires', C.c_void_p)]
+
+
 class MsNavScent(C.Structure):
     _fields_ = [('n_fields', C.c_int), ('n_sources', C.c_int), ('points', C.c_void_p), ('amounts', C.c_void_p), ('field', C.c_void_p),
                 ('reset', C.c_void_p), ('mask', C.c_void_p), ('rate', C.c_float), ('keep', C.c_float), ('floor', C.c_float),
@@ -338,6 +345,7 @@ PROTOTYPES = {
     'ms_percepts': (_int, [_p(MsScenery), _p(MsPercepts), _ptr]),
     'ms_item_collect': (_int, [_p(MsScenery), _p(MsAgents), _p(MsItemCollect), _ptr]),
     'ms_item_overlay': (_int, [_p(MsScenery), _p(MsItemOverlay), _ptr]),
+    'ms_projectiles': (_int, [_p(MsScenery), _p(MsAgents), _p(MsProjectiles), _ptr]),
     'ms_nav_scent': (_int, [_p(MsNavGrid), _p(MsNavScent), _ptr]),
     'ms_nav_scent_query': (_int, [_p(MsNavGrid), _p(MsNavScentQuery), _ptr]),
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
@@ -405,6 +413,7 @@ PROTOTYPES = {
     'ms_host_percepts': (_int, [_p(MsPercepts), _int, _ptr, _ptr, _int]),
     'ms_host_item_collect': (_int, [_p(MsItemCollect), _int, _int, _ptr, _ptr, _ptr]),
     'ms_host_item_overlay': (_int, [_p(MsItemOverlay), _int, _ptr]),
+    'ms_host_projectiles': (_int, [_p(MsProjectiles), _int, _int, _ptr, _ptr, _ptr, _int, _ptr, _ptr]),
     'ms_host_nav_clearance': (_int, [_p(MsNavGrid), _p(MsNavClearance), _ptr, _ptr, _int]),
     'ms_host_nav_clear_folds': (C.c_longlong, [_ptr]),
     'ms_host_nav_clear_chunk': (_int, []),

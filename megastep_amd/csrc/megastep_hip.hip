@@ -7,7 +7,7 @@
 //   host/*.h      the host side of the C-ABI - argument checks, argument structs, launches, the ms_host_* / ms_test_* /
 //                 ms_debug_* hooks: common.h (what every family shares) first, then a file a family as under kernels/.
 //
-// Thirty-six kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty-seven kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -92,6 +92,11 @@
 //                   settles timers, due flags and per-kind counts; a workgroup an origin builds the items' billboards once into
 //                   LDS and folds each of its rays over them by raycast_kernel's own ray_fold, over the planes a render or a
 //                   raycast wrote.   (no counterpart)
+//   projectile_kernel   projectiles: one workgroup an env, a lane a slot of the store in chunks of 256 - the lanes a < A fire into
+//                   LDS, the agents' rows are drawn once into LDS, the union of the reach boxes (shuffles, then LDS) culls the env's
+//                   static rows into an LDS list, and a wave-level loop flies the legs - up to four a tick, a bounce between two -
+//                   by raycast_kernel's own ray_fold while a ballot finds a lane with one left; integer LDS atomics for the
+//                   records.   (no counterpart)
 //   nav_scent_kernel, nav_scent_query_kernel   scent fields: one workgroup per store keeps it in LDS, a float a framed cell with a
 //                   negative sentinel on the frame and the closed cells, applies the deposits wave by wave in the rule's order and
 //                   runs the sub-steps of the diffusion with each lane's cells in registers between two barriers; per point the
@@ -215,6 +220,7 @@ struct Probe {
 #include "kernels/navview.h"
 #include "kernels/percept.h"
 #include "kernels/items.h"
+#include "kernels/projectile.h"
 #include "kernels/navpath.h"
 #include "kernels/navpull.h"
 #include "kernels/navbasin.h"
@@ -242,4 +248,5 @@ struct Probe {
 #include "host/navscent.h"
 #include "host/sight.h"
 #include "host/items.h"
+#include "host/projectile.h"
 #include "host/bake.h"

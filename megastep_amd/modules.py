@@ -505,6 +505,46 @@ class Items:
         return arrdict.arrdict(positions=self.store.positions[e].clone(), timers=self.store.timers[e].clone(), kinds=self.store.kinds[e].clone())
 
 
+class Projectiles:
+
+    def __init__(self, core, per_agent=4, speed=8., life=64, bounces=0, damage=1., muzzle=.25, restitution=1., colors=None, radius=.05):
+        """Things that fly (:func:`cuda.fly`; no counterpart in the reference, whose shots are hit-scan): every agent owns
+        ``per_agent`` slots; a shot leaves ``muzzle`` metres in front of its agent at ``speed`` m/s, lives ``life`` steps, bounces
+        off walls ``bounces`` times keeping ``restitution`` of its speed into the wall, and strikes the first agent it meets that
+        is not its owner. ``damage``: what a hit is worth - :meth:`reward` is ``damage*(scored - hits)``. ``colors``, ``radius``:
+        how a projectile shows in a camera (:func:`cuda.overlay_items`).
+
+        ``positions`` - (n_env, P, 2), NaN where a slot is empty - goes to ``Percepts(core, points=projectiles.positions)`` as it
+        is. A call is one launch, keeps its buffers and never waits for the host: it can sit in a HIP graph."""
+        self.core = core
+        self.store = cuda.projectiles(core.n_envs, core.n_agents, int(per_agent), colors=colors, device=core.device)
+        self.speed, self.muzzle, self.restitution, self.damage, self.radius = float(speed), float(muzzle), float(restitution), float(damage), float(radius)
+        self.life, self.bounces = int(life), int(bounces)
+        self._flown = self._dirs = self._shown = None
+
+    #: (n_env, P, 2) float32: where the projectiles are, NaN for an empty slot; the store's own tensor
+    positions = property(lambda self: self.store.positions)
+    #: the :class:`cuda.Flown` of the last call (None before the first)
+    flown = property(lambda self: self._flown)
+
+    def __call__(self, fire, reset=None):
+        """One tick: ``fire`` (n_env, n_agent) bool - who shoots; ``reset`` (n_env,) bool - the envs to empty. Returns the
+        :class:`cuda.Flown`."""
+        c = self.core
+        self._flown = cuda.fly(c.scenery, c.agents, self.store, fire=fire, speed=self.speed, muzzle=self.muzzle, life=self.life,
+                               bounces=self.bounces, restitution=self.restitution, reset=reset, out=self._flown)
+        return self._flown
+
+    def reward(self):
+        """(n_env, n_agent) float32 of the last tick: ``damage*(scored - hits)``."""
+        return self.damage*(self._flown.scored - self._flown.hits).float()
+
+    draw = Items.draw
+
+    def state(self, e=0):
+        return arrdict.arrdict(positions=self.store.positions[e].clone(), velocities=self.store.velocities[e].clone(), owners=self.store.owners[e].clone())
+
+
 class Scent:
 
     def __init__(self, core, grid, amount=1., own=False, **scent_args):
