@@ -1612,6 +1612,70 @@ typedef struct MsProjectiles {
 } MsProjectiles;
 int ms_projectiles(const MsScenery* scenery, const MsAgents* agents, const MsProjectiles* projectiles, void* hip_stream);
 
+/* Walkers: bodies that steer towards a point, keep apart from the bodies near them and are stopped by walls, by each other and by
+ * the agents - pedestrians, guards, a crowd - without being agents: no camera, no rays, no place among MsScenery's n_agents.  A
+ * store the caller owns, shaped as the items' (a slot is PRESENT exactly when both coordinates of its position are finite, an
+ * absent one holds (NaN, NaN): ms_item_overlay, ms_percepts and ms_nav_point_marks take `positions` as they are), and one call a
+ * step that moves it.  Every step below is one binary32 operation, in the order given, without contraction; tests/walker_rule.py
+ * restates it in numpy and the kernel - and its host instantiation, ms_host_walkers - is held to EQUALITY with it.  DESIGN.md 3.37.
+ * The store, P slots an env (1 <= P <= 1024): positions (N, P, 2); velocities (N, P, 2) metres a second; speeds (N, P) - each
+ * walker's preferred speed, metres a second.  A WALKER'S BODY IS A DISC OF agent_radius, the agents' own: the contact rule below is
+ * the agents' as it stands.  EVERYTHING A WALKER READS OF ANOTHER BODY IS THAT BODY'S STATE AT THE START OF THE CALL.
+ * ms_walkers is one tick, env by env (A = MsScenery's n_agents <= 64; a BODY is an agent whose position is finite in both
+ * coordinates, or a present walker):
+ *   1 reset     reset[n] != 0 ((N,) bytes; NULL: none): every slot of the env becomes absent, progress NaN, blocked 4; bumps and
+ *               close of the env 0.  Nothing else happens to the env in this call.
+ *   2 steer     for present walker k at p with t = towards[n, k]: d = t - p, l = sqrtf(d.x*d.x + d.y*d.y); pref = (0, 0) unless
+ *               l > 0, else s = l*fps, g = (s < speed_k ? s : speed_k)/l, pref = (d.x*g, d.y*g): a NaN target means "stand", and a
+ *               walker never oversteps its target within one tick.
+ *   3 apart     sep = (0, 0); over the agents a = 0 .. A-1 that are bodies, then the present walkers j = 0 .. P-1, j != k, IN THAT
+ *               ORDER: r = p - p_j, l2 = r.x*r.x + r.y*r.y; if 0 < l2 && l2 < personal*personal the body is NEAR, and - for a
+ *               walker always, for an agent when agents_push - lj = sqrtf(l2), f = (push*(personal - lj))/(personal*lj),
+ *               sep = (sep.x + r.x*f, sep.y + r.y*f).
+ *   4 blend     want = pref + sep; wl = sqrtf(want.x*want.x + want.y*want.y); if wl > speed_k: want = want*(speed_k/wl).
+ *               v = (keep*v_old.x + (1.f - keep)*want.x, the same in y).  A v with a component that is not finite - a stored NaN or
+ *               infinity, a NaN speed, an infinite target - is (0, 0): THE WALKER STANDS THIS TICK and is stored at rest.
+ *               u = (v.x/fps, v.y/fps).
+ *   5 meet      x = 1, class 0.  With the step's own tests (ms_step_physics': the reach culls are exact) at agent_radius, each
+ *               from 1: every agent that is a body, AT REST - collision_cc(p, u, p_a, (0, 0)), class 1: the call is meant to
+ *               follow the agents' own step, they are where they stand; every other present walker with its own u_j of this
+ *               tick - collision_cc(p, u, p_j, u_j), class 2: the symmetric rule the step applies between agents; every static
+ *               row of the env - collision_cs, class 3.  x is the least fraction; among equal fractions the lowest class counts.
+ *   6 move      p = (p.x + x*v.x/fps, p.y + x*v.y/fps); x < 1 leaves the walker at rest, v = (0, 0) - the step's own epilogue.
+ *   progress    (N, P): x; NaN for an absent slot.      blocked (N, P) bytes: the class of x - 0 nothing (x == 1), 1 an agent,
+ *               2 a walker, 3 a wall - and 4 for an absent slot.
+ *   bumps       (N, A): the present walkers whose test with agent a gave a fraction below 1.
+ *   close       (N, A): the present walkers agent a was NEAR to in step 3 (whether or not agents_push).
+ * AGENTS ARE NOT STOPPED BY WALKERS: ms_step_physics does not know them, an agent can walk through one; bumps and close are what
+ * an env penalises.  An absent slot keeps its velocity and speed.  Every output has one writer and one definition and the counts are
+ * integers.  progress, blocked, bumps and close may each be NULL (not wanted).
+ * Refused before any launch (MS_EINVAL): a NULL agents, positions, velocities, speeds or towards; agents' positions, the store's
+ * positions or velocities or towards not 8-byte aligned, a float or int pointer not 4-byte aligned; P outside 1 .. 1024, A above 64;
+ * personal, fps or agent_radius not positive and finite; push negative, infinite or a NaN; keep outside [0, 1); agents_push not 0 or 1.
+ * One launch.  P <= 64: a wavefront an env, a lane a walker, four envs a block, no workgroup barrier; beyond: a workgroup an env,
+ * a lane the slots lane + 256 j.  The bodies' (p, u) go through LDS, walked at a uniform index; the walls come from the near list of
+ * the walker's cell of the wall grid where that covers its reach, else from the env's rows; integer LDS atomics for bumps and
+ * close.  Nothing allocated, nothing waits: the call can be captured in a HIP graph. */
+typedef struct MsWalkers {
+    int                  n_slots;        /* P: slots per env (1 .. 1024)                                                   */
+    float*               positions;      /* (N, P, 2) in/out; 8-byte aligned                                               */
+    float*               velocities;     /* (N, P, 2) in/out; 8-byte aligned                                               */
+    const float*         speeds;         /* (N, P) preferred speeds, metres a second                                       */
+    const float*         towards;        /* (N, P, 2) where each walker steers; 8-byte aligned                             */
+    const unsigned char* reset;          /* (N,) non-zero: empty the env's store; NULL: none                               */
+    float                personal;       /* the distance bodies keep, metres (> 0, finite)                                 */
+    float                push;           /* the separation's strength, metres a second at contact (>= 0, finite)           */
+    float                keep;           /* what a tick keeps of the stored velocity, 0 <= keep < 1                        */
+    int                  agents_push;    /* 1: the agents push the walkers apart as walkers do; 0: only walkers do         */
+    float                fps;            /* ticks a second (> 0, finite): MsConfig's                                       */
+    float                agent_radius;   /* the bodies' radius, metres (> 0, finite): MsConfig's                           */
+    float*               progress;       /* (N, P) out, or NULL                                                            */
+    unsigned char*       blocked;        /* (N, P) out, or NULL                                                            */
+    int*                 bumps;          /* (N, A) out, or NULL                                                            */
+    int*                 close;          /* (N, A) out, or NULL                                                            */
+} MsWalkers;
+int ms_walkers(const MsScenery* scenery, const MsAgents* agents, const MsWalkers* walkers, void* hip_stream);
+
 /* Scent fields: a per-cell quantity that something leaves behind, that spreads through doorways and round corners but not through
  * walls, and that fades - a runner's trail, the smell of an item behind a door, "somebody was here recently".  The one store of
  * the nav family that EVOLVES: a call is one tick.  Every step below is one binary32 operation, in the order written, without

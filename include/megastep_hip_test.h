@@ -221,6 +221,15 @@ int ms_host_item_overlay(const MsItemOverlay* overlay, int n_envs, const int* li
  * it would refuse (and for n_envs < 1, a NULL model, walls or wall_starts, model or walls not 16-byte aligned). */
 int ms_host_projectiles(const MsProjectiles* projectiles, int n_envs, int n_agents, const float* agent_positions, const float* agent_angles,
                         const float* model, int n_model, const float* walls, const long long* wall_starts);
+/* Host instantiation of the walkers' rule (kernels/walker.h: the steer, the push of a near body, the blend, the key and its fold,
+ * the pair tests and the wall test through the step's own meet_agent and meet_wall, the settling of a slot - the very functions
+ * every lane of walker_kernel evaluates) for one whole call of ms_walkers on HOST arrays, swept serially: every pointer of
+ * `walkers` is host memory.  In place of an MsScenery and an MsAgents there are n_envs, n_agents, `agent_positions` (N, A, 2) and
+ * `walls`, the STATIC rows of all envs, four floats each, env n's rows wall_starts[n] .. wall_starts[n + 1] - 1.  Returns what
+ * ms_walkers would: MS_OK, or MS_EINVAL for arguments it would refuse (and for n_envs < 1, a NULL walls or wall_starts, walls not
+ * 16-byte aligned). */
+int ms_host_walkers(const MsWalkers* walkers, int n_envs, int n_agents, const float* agent_positions, const float* walls,
+                    const long long* wall_starts);
 /* Host instantiations of the clearance rule (kernels/navclear.h: the tile's box, the list, ov_keeps and ov_fold, the second cull,
  * the winner's order and the stores - the very functions every lane of nav_clear_kernel and nav_clear_query_kernel evaluates) for
  * one whole call each on HOST arrays, swept serially: every pointer of `grid` and of the argument struct is host memory.

@@ -281,6 +281,13 @@ class MsProjectiles(C.Structure):
                 ('struck', C.c_void_p), ('ended', C.c_void_p), ('hits', C.c_void_p), ('scored', C.c_void_p), ('misfires', C.c_void_p)]
 
 
+class MsWalkers(C.Structure):
+    _fields_ = [('n_slots', C.c_int), ('positions', C.c_void_p), ('velocities', C.c_void_p), ('speeds', C.c_void_p), ('towards', C.c_void_p),
+                ('reset', C.c_void_p), ('personal', C.c_float), ('push', C.c_float), ('keep', C.c_float), ('agents_push', C.c_int),
+                ('fps', C.c_float), ('agent_radius', C.c_float), ('progress', C.c_void_p), ('blocked', C.c_void_p), ('bumps', C.c_void_p),
+                ('close', C.c_void_p)]
+
+
 class MsNavScent(C.Structure):
     _fields_ = [('n_fields', C.c_int), ('n_sources', C.c_int), ('points', C.c_void_p), ('amounts', C.c_void_p), ('field', C.c_void_p),
                 ('reset', C.c_void_p), ('mask', C.c_void_p), ('rate', C.c_float), ('keep', C.c_float), ('floor', C.c_float),
@@ -346,6 +353,7 @@ PROTOTYPES = {
     'ms_item_collect': (_int, [_p(MsScenery), _p(MsAgents), _p(MsItemCollect), _ptr]),
     'ms_item_overlay': (_int, [_p(MsScenery), _p(MsItemOverlay), _ptr]),
     'ms_projectiles': (_int, [_p(MsScenery), _p(MsAgents), _p(MsProjectiles), _ptr]),
+    'ms_walkers': (_int, [_p(MsScenery), _p(MsAgents), _p(MsWalkers), _ptr]),
     'ms_nav_scent': (_int, [_p(MsNavGrid), _p(MsNavScent), _ptr]),
     'ms_nav_scent_query': (_int, [_p(MsNavGrid), _p(MsNavScentQuery), _ptr]),
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
@@ -414,6 +422,7 @@ PROTOTYPES = {
     'ms_host_item_collect': (_int, [_p(MsItemCollect), _int, _int, _ptr, _ptr, _ptr]),
     'ms_host_item_overlay': (_int, [_p(MsItemOverlay), _int, _ptr]),
     'ms_host_projectiles': (_int, [_p(MsProjectiles), _int, _int, _ptr, _ptr, _ptr, _int, _ptr, _ptr]),
+    'ms_host_walkers': (_int, [_p(MsWalkers), _int, _int, _ptr, _ptr, _ptr]),
     'ms_host_nav_clearance': (_int, [_p(MsNavGrid), _p(MsNavClearance), _ptr, _ptr, _int]),
     'ms_host_nav_clear_folds': (C.c_longlong, [_ptr]),
     'ms_host_nav_clear_chunk': (_int, []),

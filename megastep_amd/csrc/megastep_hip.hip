@@ -7,7 +7,7 @@
 //   host/*.h      the host side of the C-ABI - argument checks, argument structs, launches, the ms_host_* / ms_test_* /
 //                 ms_debug_* hooks: common.h (what every family shares) first, then a file a family as under kernels/.
 //
-// Thirty-seven kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty-eight kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -97,6 +97,11 @@
 //                   static rows into an LDS list, and a wave-level loop flies the legs - up to four a tick, a bounce between two -
 //                   by raycast_kernel's own ray_fold while a ballot finds a lane with one left; integer LDS atomics for the
 //                   records.   (no counterpart)
+//   walker_kernel<WIDE>   walkers: a wavefront an env and a lane a walker while 64 lanes cover the store (four envs a block, no
+//                   workgroup barrier), a workgroup an env beyond - the bodies' (p, u) go through LDS and are walked at a uniform
+//                   index, once to steer and keep apart and once, behind a barrier, through the step's own meet_agent; the walls
+//                   by near_list / walk_rows; x and its class folded as one unsigned key; integer LDS atomics for the counts.
+//                                                            (no counterpart)
 //   nav_scent_kernel, nav_scent_query_kernel   scent fields: one workgroup per store keeps it in LDS, a float a framed cell with a
 //                   negative sentinel on the frame and the closed cells, applies the deposits wave by wave in the rule's order and
 //                   runs the sub-steps of the diffusion with each lane's cells in registers between two barriers; per point the
@@ -221,6 +226,7 @@ struct Probe {
 #include "kernels/percept.h"
 #include "kernels/items.h"
 #include "kernels/projectile.h"
+#include "kernels/walker.h"
 #include "kernels/navpath.h"
 #include "kernels/navpull.h"
 #include "kernels/navbasin.h"
@@ -249,4 +255,5 @@ struct Probe {
 #include "host/sight.h"
 #include "host/items.h"
 #include "host/projectile.h"
+#include "host/walker.h"
 #include "host/bake.h"

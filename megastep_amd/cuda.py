@@ -738,6 +738,7 @@ from .rays import RAYCAST_FIELDS, Raycast, raycast, camera_rays, line_of_sight
 from .percepts import PERCEPT_FIELDS, PERCEPT_MAX_EYES, PERCEPT_MAX_POINTS, PERCEPT_MAX_NEAREST, Percepts, percepts
 from .items import ITEM_MAX_ITEMS, ITEM_MAX_AGENTS, ITEM_MAX_KINDS, Items, Collected, items, collect_items, place_items, overlay_items
 from .projectiles import PROJ_MAX_SLOTS, PROJ_MAX_AGENTS, PROJ_MAX_PER_AGENT, Projectiles, Flown, projectiles, fly
+from .walkers import WALK_MAX_SLOTS, WALK_MAX_AGENTS, Walkers, Walked, walkers, walk
 from .scents import SCENT_CAPACITY, SCENT_MAX_SOURCES, SCENT_MAX_SUBSTEPS, ScentFields, Sniff, scent_fields
 from .cameras import PROJECTIONS, LOOK_FIELDS, Cameras, Look, shade, cameras, mounted, look
 from .rollouts import ROLLOUT_MAX_CANDIDATES, ROLLOUT_MAX_HORIZON, Rollouts, rollouts, plans, _bounce

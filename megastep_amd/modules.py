@@ -545,6 +545,74 @@ class Projectiles:
         return arrdict.arrdict(positions=self.store.positions[e].clone(), velocities=self.store.velocities[e].clone(), owners=self.store.owners[e].clone())
 
 
+class Walkers:
+
+    def __init__(self, core, grid, n_walkers, n_goals=4, speeds=(.6, 1.4), arrive=.3, seed=0, colors=None, **walk):
+        """Others who walk (:func:`cuda.walk`; no counterpart in the reference): ``n_walkers`` bodies an env that go from
+        destination to destination among the agents, without being agents - no camera, no rays. Every env draws ``n_goals``
+        destination cells (:func:`cuda.cell_draws`) in its largest connected space (:meth:`cuda.Regions.largest_mask`) and keeps
+        their :func:`cuda.distance_fields`; the walkers start on drawn cells of the same space with preferred speeds drawn
+        between ``speeds`` m/s, walker k bound for destination ``k % n_goals``. A call heads every walker for the waypoint of its
+        destination (:meth:`cuda.DistanceFields.waypoints`), ticks :func:`cuda.walk` - ``**walk``: its ``personal``, ``push``,
+        ``keep``, ``agents_push`` - and sends those within ``arrive`` metres (walking distance) of their destination on to the next
+        one. A walker is a disc of the core's ``agent_radius``, and is drawn as wide.
+
+        ``positions`` - (n_env, P, 2) - goes to ``Percepts(core, points=walkers.positions)`` as it is. A call is three launches
+        and a few element-wise ops, keeps its buffers and never waits for the host: it can sit in a HIP graph. The envs marked in
+        ``reset`` draw destinations and walkers anew, and only their fields are computed again."""
+        self.core, self.grid = core, grid
+        n, p, g = core.n_envs, int(n_walkers), int(n_goals)
+        self.store = cuda.walkers(n, p, colors=colors, device=core.device)
+        self.radius, self.arrive, self._lo, self._hi, self._walk = float(core.agent_radius), float(arrive), float(speeds[0]), float(speeds[1]), walk
+        self._gate = cuda.regions(grid).largest_mask()
+        self._cells = cuda.cell_draws(grid, grid, 1, g, gate=self._gate, seed=int(seed))
+        #: the :class:`cuda.DistanceFields` of the destinations, ``n_goals`` an env
+        self.fields = cuda.distance_fields(grid, self._cells.points[:, 0].clone())
+        self._spawns = cuda.cell_draws(grid, grid, p, 1, gate=self._gate, seed=int(seed) + 1)
+        #: (n_env, P) int32: the destination each walker is bound for
+        self.goal = (torch.arange(p, dtype=torch.int32, device=core.device) % g).expand(n, p).contiguous()
+        self._towards = torch.empty((n, p, 2), dtype=torch.float32, device=core.device)
+        self._left = torch.empty((n, p), dtype=torch.float32, device=core.device)
+        self._walked = self._dirs = self._shown = None
+        self._spawn(torch.ones((n, 1), dtype=torch.bool, device=core.device))
+
+    def _spawn(self, sets):
+        """The walkers of the envs marked in ``sets`` (n_env, 1) on their drawn cells, at rest, at their drawn speeds."""
+        s, d = self.store, self._spawns
+        torch.where(sets[:, :, None], d.points[:, :, 0], s.positions, out=s.positions)
+        torch.where(sets[:, :, None], torch.zeros_like(s.velocities), s.velocities, out=s.velocities)
+        torch.where(sets, self._lo + (self._hi - self._lo)*d.uniforms[:, :, 0], s.speeds, out=s.speeds)
+
+    #: (n_env, P, 2) float32: where the walkers are; the store's own tensor
+    positions = property(lambda self: self.store.positions)
+    #: the :class:`cuda.Walked` of the last call (None before the first)
+    walked = property(lambda self: self._walked)
+    #: (n_env, n_agent) int32 of the last tick: the walkers that ran into each agent, and those within ``personal`` of it
+    bumps = property(lambda self: self._walked.bumps)
+    close = property(lambda self: self._walked.close)
+
+    def __call__(self, reset=None):
+        """One tick; ``reset`` (n_env,) bool - the envs whose destinations and walkers are drawn anew. Returns the
+        :class:`cuda.Walked`. Meant to follow the agents' own step."""
+        c, s, g = self.core, self.store, self.fields.n_goals
+        if reset is not None:
+            sets = reset[:, None]
+            self._cells.again(mask=sets)
+            self.fields.update(self._cells.points[:, 0], mask=sets.expand(-1, g))
+            self._spawns.again(mask=sets.expand(-1, s.n_slots))
+            self._spawn(sets)
+        self.fields.waypoints(s.positions, goal=self.goal, out=self._towards)
+        self._walked = cuda.walk(c.scenery, c.agents, s, self._towards, out=self._walked, **self._walk)
+        self.fields.at(s.positions, goal=self.goal, out=self._left)
+        self.goal.add_(self._left < self.arrive).remainder_(g)
+        return self._walked
+
+    draw = Items.draw
+
+    def state(self, e=0):
+        return arrdict.arrdict(positions=self.store.positions[e].clone(), velocities=self.store.velocities[e].clone(), goal=self.goal[e].clone())
+
+
 class Scent:
 
     def __init__(self, core, grid, amount=1., own=False, **scent_args):
