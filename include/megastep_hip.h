@@ -1333,6 +1333,62 @@ int ms_nav_basins(const MsNavGrid* grid, const MsNavBasins* basins, void* hip_st
 int ms_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* query, void* hip_stream);
 int ms_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* marks, void* hip_stream);
 
+/* Flow fields: for every cell of a field WHERE A BODY STANDING THERE SHOULD HEAD - the look-ahead waypoint of the cell, computed once
+ * per field and per change of the field, so that a crowd bound for one destination costs a lookup and at most one sight test each.
+ * Every output is an integer, or a float copied or formed by MsNavGrid's centre; tests/flow_rule.py restates the rule in numpy on
+ * path_rule's hop, sight and start, and the kernels - and their host instantiations, ms_host_nav_flows / _flow_query - are held to
+ * EQUALITY with it.  It adds no geometry: hop, sight and start are MsNavWaypoints'.  Take field (n, g) of any fields store - of goals
+ * (`goals` given), seeded (goals NULL) or cost fields (costs given too; a hop then runs with the weights of the cell it leaves) - its
+ * values D AS THEY STAND, and the look-ahead L in 1..64.  A cell v is LIVE when it is free and D[v] < +inf.
+ *   chain(v)      of a live cell: x_0 = v's centre; x_{k+1} = the centre of the cell MsNavWaypoints' hop moves to from x_k's cell.
+ *                 The chain ends where the hop ends (the cell is a goal's anchor holding its own leg; a seed) or breaks (no
+ *                 neighbour below D: a stale field), or at L points.  With goals, a chain that ends with room left gains the goal
+ *                 point q as its last point.
+ *   target(v)     x_k for the largest k in 1 .. n - 1 with sight(x_0, x_k) - MsNavWaypoints' sight, FROM THE CELL'S CENTRE; k = 1 is
+ *                 taken without a test; a chain of one point (a seed, a chain broken at once, L = 1) gives k = 0, v itself.  This is
+ *                 MsNavWaypoints' choice entered at a cell with p = x_0 (whose leg to x_0 is 0).
+ *   targets       int32 per cell and field in the fields' layout (field (n, g) at G*starts[n] + g*nx*ny): a target that is a
+ *                 centre as its row-major cell index within the env, MS_FLOW_GOAL (-2) when it is q, -1 on a cell that is not live.
+ *   query         of a point p: MsNavWaypoints' start gives the anchor a* and leg0; without one (a NaN point, a field index outside
+ *                 [0, G), an env without cells) the answer is (NaN, NaN).  Let w be the point targets[a*] names: -1 there - or
+ *                 anything that names no cell, which a stale store may hold - gives NaN.  If the target is a* itself or
+ *                 sight(p, w) holds, the answer is w; otherwise it is MsNavWaypoints' waypoint from p at L = 2 - the floor that
+ *                 rule itself falls back on, which reads only the eight neighbours of a*.  took (or NULL): 1 the cell's target,
+ *                 0 the fallback, -1 no answer.  goal (N, P): the field each point asks; NULL: G == P and point k asks field k.
+ * This is NOT MsNavWaypoints' answer: there the sight runs from the point and the chain starts at the point's anchor; here the
+ * sight runs from the cell's centre and is checked once more from the point.  No equality between the two is promised.
+ * ms_nav_flows: one launch, one workgroup per field: what the hop does at each cell of the FRAMED env as one byte in LDS (16, 64 or
+ * 160 KiB, chosen by max_framed), then a lane a cell; an env beyond the launch's LDS takes hops and free bytes from global memory,
+ * to the same result.  Fields that are masked out keep their targets.  ms_nav_flow_query: a lane a point.  One writer per output
+ * element, no atomics, nothing allocated, nothing waits: both can be captured in a HIP graph.  Every argument is checked in full
+ * before the launch (MS_EINVAL): NULL stores, L outside 1..64, targets aliasing the fields, costs without n_costs 1 or G. */
+#define MS_FLOW_GOAL (-2)
+typedef struct MsNavFlows {
+    int                  n_fields;     /* G: fields per env                                                            */
+    const float*         fields;       /* G*starts[N] floats: MsNavFields', MsNavSeedFields' or MsNavCostFields'        */
+    const float*         goals;        /* (N, G, 2) the fields' goals, 8-byte aligned; NULL: seeded or cost fields      */
+    const float*         costs;        /* as MsNavCostFields.costs; NULL: unweighted (n_costs 0)                        */
+    int                  n_costs;      /* 1 or G with costs, else 0                                                     */
+    int                  lookahead;    /* L, 1..64                                                                      */
+    const unsigned char* mask;         /* (N, G) non-zero: compute this field; NULL: all.  Read on the device only.    */
+    int*                 targets;      /* G*starts[N] int32 out                                                        */
+} MsNavFlows;
+typedef struct MsNavFlowQuery {
+    int                  n_points;     /* P: points per env                                                            */
+    const float*         points;       /* (N, P, 2) x, y; 8-byte aligned                                               */
+    const int*           goal;         /* (N, P) the field each point asks; NULL: G == P                               */
+    const float*         fields;       /* as MsNavFlows.fields                                                         */
+    const float*         goals;        /* as MsNavFlows.goals                                                          */
+    const float*         costs;        /* as MsNavFlows.costs                                                          */
+    int                  n_costs;
+    int                  n_fields;     /* G of `fields` and `targets`                                                  */
+    const int*           targets;      /* as MsNavFlows.targets                                                        */
+    float*               waypoints;    /* (N, P, 2) out; 8-byte aligned                                                */
+    int*                 took;         /* (N, P) out, or NULL                                                          */
+} MsNavFlowQuery;
+int ms_nav_flows(const MsNavGrid* grid, const MsNavFlows* flows, void* hip_stream);
+int ms_nav_flow_query(const MsNavGrid* grid, const MsNavFlowQuery* query, void* hip_stream);
+
 /* Zones: a label and a number together - per zone of a labels layer the cells, the marked cells, the least value and the cell that
  * attains it: how far each agent is from the nearest cell of each frontier cluster and which cell that is, how much of each room has
  * been seen, the oldest cell of each territory.  Every output is an integer or a copied float with one definition;

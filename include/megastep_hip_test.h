@@ -176,6 +176,15 @@ int ms_host_nav_basins(const MsNavGrid* grid, const MsNavBasins* basins);
 int ms_host_nav_basin_query(const MsNavGrid* grid, const MsNavBasinQuery* query);
 int ms_host_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* marks);
 int ms_host_nav_basin_capacity(int* capacities);
+/* Host instantiations of the flow fields' rule (kernels/navflow.h: a cell's code through nav_hop, its target, the sight over codes
+ * and the query - the very functions every lane of nav_flow_kernel and nav_flow_query_kernel evaluates) for one whole call each on
+ * HOST arrays, swept serially: every pointer of `grid` and of the argument struct is host memory.  ms_host_nav_flows keeps an env's
+ * codes in a framed array when it fits the LDS of the launch ms_nav_flows would choose by grid->max_framed, else takes them from
+ * the stores - the kernel's two paths.  They return what the device entries would: MS_OK, or MS_EINVAL for arguments they would
+ * refuse.  ms_host_nav_flow_capacity writes the three capacities, in framed cells, of nav_flow_kernel's instantiations. */
+int ms_host_nav_flows(const MsNavGrid* grid, const MsNavFlows* flows);
+int ms_host_nav_flow_query(const MsNavGrid* grid, const MsNavFlowQuery* query);
+int ms_host_nav_flow_capacity(int* capacities);
 /* Host instantiation of the zones' rule (kernels/navzone.h: the root test, the rank of a label in the list of roots, a cell's zone,
  * its mark, its key and a zone's stores - the very functions every lane of nav_zone_kernel evaluates) for one whole call of
  * ms_nav_zones on HOST arrays, swept serially: every pointer of `grid` and of `zones` is host memory.  Returns what ms_nav_zones

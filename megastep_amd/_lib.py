@@ -237,6 +237,17 @@ class MsNavBasinQuery(C.Structure):
                 ('n_fields', C.c_int), ('out', C.c_void_p)]
 
 
+class MsNavFlows(C.Structure):
+    _fields_ = [('n_fields', C.c_int), ('fields', C.c_void_p), ('goals', C.c_void_p), ('costs', C.c_void_p), ('n_costs', C.c_int),
+                ('lookahead', C.c_int), ('mask', C.c_void_p), ('targets', C.c_void_p)]
+
+
+class MsNavFlowQuery(C.Structure):
+    _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('goal', C.c_void_p), ('fields', C.c_void_p), ('goals', C.c_void_p),
+                ('costs', C.c_void_p), ('n_costs', C.c_int), ('n_fields', C.c_int), ('targets', C.c_void_p), ('waypoints', C.c_void_p),
+                ('took', C.c_void_p)]
+
+
 class MsNavPointMarks(C.Structure):
     _fields_ = [('n_points', C.c_int), ('points', C.c_void_p), ('field', C.c_void_p), ('point_ids', C.c_void_p), ('n_fields', C.c_int),
                 ('marks', C.c_void_p), ('ids', C.c_void_p)]
@@ -359,6 +370,8 @@ PROTOTYPES = {
     'ms_nav_basins': (_int, [_p(MsNavGrid), _p(MsNavBasins), _ptr]),
     'ms_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery), _ptr]),
     'ms_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks), _ptr]),
+    'ms_nav_flows': (_int, [_p(MsNavGrid), _p(MsNavFlows), _ptr]),
+    'ms_nav_flow_query': (_int, [_p(MsNavGrid), _p(MsNavFlowQuery), _ptr]),
     'ms_nav_zones': (_int, [_p(MsNavGrid), _p(MsNavZones), _ptr]),
     'ms_nav_clearance': (_int, [_p(MsScenery), _p(MsNavGrid), _p(MsNavClearance), _ptr]),
     'ms_nav_clear_query': (_int, [_p(MsScenery), _p(MsAgents), _p(MsNavClearQuery), _ptr]),
@@ -415,6 +428,9 @@ PROTOTYPES = {
     'ms_host_nav_basin_query': (_int, [_p(MsNavGrid), _p(MsNavBasinQuery)]),
     'ms_host_nav_point_marks': (_int, [_p(MsNavGrid), _p(MsNavPointMarks)]),
     'ms_host_nav_basin_capacity': (_int, [_ptr]),
+    'ms_host_nav_flows': (_int, [_p(MsNavGrid), _p(MsNavFlows)]),
+    'ms_host_nav_flow_query': (_int, [_p(MsNavGrid), _p(MsNavFlowQuery)]),
+    'ms_host_nav_flow_capacity': (_int, [_ptr]),
     'ms_host_nav_zones': (_int, [_p(MsNavGrid), _p(MsNavZones)]),
     'ms_host_nav_views': (_int, [_p(MsNavGrid), _p(MsNavViews), _ptr, _ptr, _int]),
     'ms_host_nav_view_capacity': (_int, []),

@@ -1,6 +1,6 @@
 // host/navsets.h -- sets of cells of the nav grid: ms_nav_regions, ms_nav_region_query, ms_nav_region_masks
-// (kernels/navregion.h), ms_nav_basins, ms_nav_basin_query, ms_nav_point_marks (navbasin.h), ms_nav_zones (navzone.h), and the host
-// instantiation of each.  One check serves a launch and its host instantiation.
+// (kernels/navregion.h), ms_nav_basins, ms_nav_basin_query, ms_nav_point_marks (navbasin.h), ms_nav_flows, ms_nav_flow_query
+// (navflow.h), ms_nav_zones (navzone.h), and the host instantiation of each.  One check serves a launch and its host instantiation.
 namespace {
 // Regions: the launch's LDS is chosen as the relaxation's, by the largest framed field.
 int nav_regions_check(const MsNavGrid* grid, const MsNavRegions* r) {
@@ -55,6 +55,34 @@ int nav_point_marks_check(const MsNavGrid* grid, const MsNavPointMarks* m) {
 NavPointMarkArgs nav_point_mark_args(const MsNavGrid* grid, const MsNavPointMarks* m) {
     return NavPointMarkArgs{m->points, m->field, m->point_ids, grid->free_cells, m->marks, m->ids, m->n_points, m->n_fields,
                             (long long)grid->n_envs*m->n_points};
+}
+
+// Flow fields: the launch's LDS is chosen by max_framed among the flows' own tiers (a byte a framed cell).
+bool nav_flow_costs_ok(const float* goals, const float* costs, int n_costs, int n_fields) {
+    return costs ? !goals && nav_costs_ok(costs, n_costs, n_fields) : n_costs == 0;
+}
+int nav_flows_check(const MsNavGrid* grid, const MsNavFlows* f) {
+    if (!nav_grid_ok(grid) || !f || f->n_fields < 1 || !f->fields || !f->targets || (const void*)f->targets == (const void*)f->fields ||
+        f->lookahead < 1 || f->lookahead > WAVE || !nav_flow_costs_ok(f->goals, f->costs, f->n_costs, f->n_fields) || !aligned(f->goals, 8) ||
+        !all_aligned<4>(f->fields, f->targets)) return MS_EINVAL;
+    return (long long)grid->n_envs*f->n_fields > 0x7fffffffLL ? MS_EUNSUPPORTED : MS_OK;
+}
+NavFlowArgs nav_flow_args(const MsNavGrid* grid, const MsNavFlows* f) {
+    return NavFlowArgs{grid->free_cells, f->fields, f->goals, f->costs, f->mask, f->targets, f->n_fields, f->n_costs, f->lookahead};
+}
+int nav_flow_tier(const MsNavGrid* grid) {
+    return grid->max_framed <= flow_capacity(FLOW_LDS[0]) ? 0 : grid->max_framed <= flow_capacity(FLOW_LDS[1]) ? 1 : 2;
+}
+int nav_flow_query_check(const MsNavGrid* grid, const MsNavFlowQuery* q) {
+    if (!nav_grid_ok(grid) || !q || q->n_points < 1 || q->n_fields < 1 || !q->points || !q->fields || !q->targets || !q->waypoints ||
+        (!q->goal && q->n_points != q->n_fields) || !nav_flow_costs_ok(q->goals, q->costs, q->n_costs, q->n_fields) ||
+        !aligned(q->points, 8) || !aligned(q->waypoints, 8) || !aligned(q->goals, 8) ||
+        !all_aligned<4>(q->goal, q->fields, q->targets, q->took)) return MS_EINVAL;
+    return (long long)grid->n_envs*q->n_points > 0x7fffff00LL ? MS_EUNSUPPORTED : MS_OK;
+}
+NavFlowQueryArgs nav_flow_query_args(const MsNavGrid* grid, const MsNavFlowQuery* q) {
+    return NavFlowQueryArgs{q->points, q->goal, grid->free_cells, q->fields, q->goals, q->costs, q->targets, q->waypoints, q->took,
+                            q->n_points, q->n_fields, q->n_costs, (long long)grid->n_envs*q->n_points};
 }
 
 // Zones: one instantiation - the kernel's LDS does not grow with the env.
@@ -170,6 +198,42 @@ int ms_host_nav_point_marks(const MsNavGrid* grid, const MsNavPointMarks* m) {
 }
 
 int ms_host_nav_basin_capacity(int* capacities) { return nav_host_capacities(capacities, basin_capacity); }
+
+int ms_nav_flows(const MsNavGrid* grid, const MsNavFlows* f, void* stream) {
+    if (const int status = nav_flows_check(grid, f)) return status;
+    static void (*const kernels[3])(NavArgs, NavFlowArgs) = {nav_flow_kernel<FLOW_LDS[0], FLOW_THREADS[0]>, nav_flow_kernel<FLOW_LDS[1], FLOW_THREADS[1]>,
+                                                             nav_flow_kernel<FLOW_LDS[2], FLOW_THREADS[2]>};
+    const int t = nav_flow_tier(grid);
+    hipLaunchKernelGGL(kernels[t], dim3((unsigned)((long long)grid->n_envs*f->n_fields)), dim3(FLOW_THREADS[t]), 0, (hipStream_t)stream,
+                       nav_args(grid), nav_flow_args(grid, f));
+    return launch_status();
+}
+
+int ms_nav_flow_query(const MsNavGrid* grid, const MsNavFlowQuery* q, void* stream) {
+    if (const int status = nav_flow_query_check(grid, q)) return status;
+    const NavFlowQueryArgs a = nav_flow_query_args(grid, q);
+    hipLaunchKernelGGL(nav_flow_query_kernel, dim3((unsigned)((a.total + WG - 1)/WG)), dim3(WG), 0, (hipStream_t)stream, nav_args(grid), a);
+    return launch_status();
+}
+
+int ms_host_nav_flows(const MsNavGrid* grid, const MsNavFlows* f) {
+    if (const int status = nav_flows_check(grid, f)) return status;
+    flow_serial(nav_args(grid), nav_flow_args(grid, f), flow_capacity(FLOW_LDS[nav_flow_tier(grid)]));
+    return MS_OK;
+}
+
+int ms_host_nav_flow_query(const MsNavGrid* grid, const MsNavFlowQuery* q) {
+    if (const int status = nav_flow_query_check(grid, q)) return status;
+    const NavFlowQueryArgs a = nav_flow_query_args(grid, q);
+    for (long long at = 0; at < a.total; at++) flow_query_one(nav_args(grid), a, at);
+    return MS_OK;
+}
+
+int ms_host_nav_flow_capacity(int* capacities) {
+    if (!capacities) return MS_EINVAL;
+    for (int t = 0; t < 3; t++) capacities[t] = flow_capacity(FLOW_LDS[t]);
+    return MS_OK;
+}
 
 int ms_nav_zones(const MsNavGrid* grid, const MsNavZones* z, void* stream) {
     if (const int status = nav_zones_check(grid, z)) return status;

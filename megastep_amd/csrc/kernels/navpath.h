@@ -163,13 +163,22 @@ __host__ __device__ inline int nav_path(const NavEnv& g, const NavGoal& q, const
     return state == 0 || count == 0 ? count : -count;
 }
 
-// The waypoint from p with look-ahead L, serially, as the wave does it side by side (host instantiation only: the chain's
-// points live in an array).  Returns the chosen index k, -1 without a path.
-inline int nav_waypoint_serial(const NavEnv& g, const NavGoal& q, const float px, const float py, const int L, float& wx, float& wy) {
-    wx = wy = NAN;
-    int i = 0, j = 0, n = 0;
-    float leg0, xs[64], ys[64];
-    if (!nav_start(g, px, py, i, j, leg0)) return -1;
+// The choice a waypoint and a flow target (navflow.h) both make among the n points of a chain: the largest k in b + 1 .. n - 1
+// whose point is in sight - seen(k) - else b.
+template <typename Seen>
+__host__ __device__ inline int nav_furthest_seen(const int n, const int b, const Seen seen) {
+    int k = n - 1;
+    while (k > b && !seen(k)) k--;
+    return k;
+}
+
+// The waypoint's body entered at cell (i, j) with the leg leg0 from p to its centre, serially: the chain's first L <= CAP points
+// in an array, then the choice.  Returns the chosen index k.
+template <int CAP>
+__host__ __device__ inline int nav_waypoint_from(const NavEnv& g, const NavGoal& q, const float px, const float py, int i, int j, const float leg0,
+                                                 const int L, float& wx, float& wy) {
+    int n = 0;
+    float xs[CAP], ys[CAP];
     for (;;) {
         xs[n] = nav_centre(g.jx0, j, g.c); ys[n] = nav_centre(g.iy0, i, g.c); n++;
         if (n >= L) break;
@@ -178,10 +187,19 @@ inline int nav_waypoint_serial(const NavEnv& g, const NavGoal& q, const float px
         if (state != 1) break;
     }
     const int b = (leg0 <= .5f*g.c && n >= 2) ? 1 : 0;
-    int k = n - 1;
-    while (k > b && !nav_sight(g, px, py, xs[k], ys[k])) k--;
+    const int k = nav_furthest_seen(n, b, [&](const int c) { return nav_sight(g, px, py, xs[c], ys[c]); });
     wx = xs[k]; wy = ys[k];
     return k;
+}
+
+// The waypoint from p with look-ahead L, serially, as the wave does it side by side (host instantiation only: the chain's
+// points live in an array).  Returns the chosen index k, -1 without a path.
+inline int nav_waypoint_serial(const NavEnv& g, const NavGoal& q, const float px, const float py, const int L, float& wx, float& wy) {
+    wx = wy = NAN;
+    int i = 0, j = 0;
+    float leg0;
+    if (!nav_start(g, px, py, i, j, leg0)) return -1;
+    return nav_waypoint_from<64>(g, q, px, py, i, j, leg0, L, wx, wy);
 }
 
 struct NavPathArgs {                                 // MsNavWaypoints / MsNavPaths, checked

@@ -230,6 +230,7 @@ struct Probe {
 #include "kernels/navpath.h"
 #include "kernels/navpull.h"
 #include "kernels/navbasin.h"
+#include "kernels/navflow.h"
 #include "kernels/navzone.h"
 #include "kernels/navseen.h"
 #include "kernels/navage.h"

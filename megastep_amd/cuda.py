@@ -748,4 +748,5 @@ from .nav import nav_geometry, NavGrid, nav_grid, FIELD_CAPACITY, DistanceFields
     COST_CAPACITY, COST_MAX, CostFields, cost_fields, inflation_costs, mark_costs, \
     CellLayer, cell_layer, MapChannel, map_channel, local_maps, CellDraws, cell_draws, REGION_CAPACITY, Regions, regions, \
     VIEW_WALL_CAPACITY, ViewFields, view_fields, BASIN_CAPACITY, BASIN_MAX_IDS, PointMarks, point_marks, Basins, basins, ZONE_MAX, Zones, zones, \
+    FLOW_CAPACITY, FLOW_GOAL, FlowFields, flow_fields, \
     CLEARANCE_MAX_RADII, ClearanceFields, clearance_fields, Clearance, clearance

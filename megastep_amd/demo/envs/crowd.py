@@ -16,16 +16,17 @@ from .pointgoal import PointGoal, books
 
 class Crowd(PointGoal):
 
-    def __init__(self, n_envs, n_walkers=16, *args, n_goals=4, speeds=(.6, 1.4), bump=.5, close=.05, seed=0, walk=None, **kwargs):
+    def __init__(self, n_envs, n_walkers=16, *args, n_goals=4, speeds=(.6, 1.4), bump=.5, close=.05, seed=0, walk=None, flow=False, **kwargs):
         """``n_walkers``, ``n_goals``, ``speeds``, ``seed``, ``walk`` (a dict of :func:`~megastep_amd.cuda.walk`'s ``personal``,
-        ``push``, ``keep``, ``agents_push``): :class:`~megastep_amd.modules.Walkers`'; ``bump``, ``close``: what a walker that runs into
+        ``push``, ``keep``, ``agents_push``), ``flow``: :class:`~megastep_amd.modules.Walkers`'; ``bump``, ``close``: what a walker that runs into
         an agent, and one within ``personal`` of it, take off the agent's reward of the step. Everything else is
         :class:`PointGoal`'s, less ``spl`` and ``panorama``. The crowd keeps walking across the agents' episodes."""
         if kwargs.get('spl') or kwargs.get('panorama'):
             raise RuntimeError('Crowd takes neither spl nor panorama')
         super().__init__(n_envs, *args, **kwargs)
         #: the :class:`~megastep_amd.modules.Walkers` of the env
-        self.walkers = modules.Walkers(self.core, self.grid, n_walkers, n_goals=n_goals, speeds=speeds, seed=seed, colors=(.9, .6, .1), **(walk or {}))
+        self.walkers = modules.Walkers(self.core, self.grid, n_walkers, n_goals=n_goals, speeds=speeds, seed=seed, colors=(.9, .6, .1), flow=flow,
+                                       **(walk or {}))
         self.bump, self.close = float(bump), float(close)
         self._frame = None
 

@@ -547,7 +547,7 @@ class Projectiles:
 
 class Walkers:
 
-    def __init__(self, core, grid, n_walkers, n_goals=4, speeds=(.6, 1.4), arrive=.3, seed=0, colors=None, **walk):
+    def __init__(self, core, grid, n_walkers, n_goals=4, speeds=(.6, 1.4), arrive=.3, seed=0, colors=None, flow=False, **walk):
         """Others who walk (:func:`cuda.walk`; no counterpart in the reference): ``n_walkers`` bodies an env that go from
         destination to destination among the agents, without being agents - no camera, no rays. Every env draws ``n_goals``
         destination cells (:func:`cuda.cell_draws`) in its largest connected space (:meth:`cuda.Regions.largest_mask`) and keeps
@@ -559,7 +559,12 @@ class Walkers:
 
         ``positions`` - (n_env, P, 2) - goes to ``Percepts(core, points=walkers.positions)`` as it is. A call is three launches
         and a few element-wise ops, keeps its buffers and never waits for the host: it can sit in a HIP graph. The envs marked in
-        ``reset`` draw destinations and walkers anew, and only their fields are computed again."""
+        ``reset`` draw destinations and walkers anew, and only their fields are computed again.
+
+        ``flow=True`` heads the walkers by the destinations' flow fields instead (:func:`cuda.flow_fields`, kept as ``flows``):
+        every cell's waypoint is computed with the fields, when an env is reset, and a call looks each walker's up
+        (:meth:`cuda.FlowFields.at`: a lane a walker) where it otherwise spends a wavefront on each. The walkers' courses are close
+        to, not the same as, those without it: the sight runs from the cell's centre first."""
         self.core, self.grid = core, grid
         n, p, g = core.n_envs, int(n_walkers), int(n_goals)
         self.store = cuda.walkers(n, p, colors=colors, device=core.device)
@@ -568,6 +573,8 @@ class Walkers:
         self._cells = cuda.cell_draws(grid, grid, 1, g, gate=self._gate, seed=int(seed))
         #: the :class:`cuda.DistanceFields` of the destinations, ``n_goals`` an env
         self.fields = cuda.distance_fields(grid, self._cells.points[:, 0].clone())
+        #: the :class:`cuda.FlowFields` of :attr:`fields` with ``flow=True``, else None
+        self.flows = self.fields.flows() if flow else None
         self._spawns = cuda.cell_draws(grid, grid, p, 1, gate=self._gate, seed=int(seed) + 1)
         #: (n_env, P) int32: the destination each walker is bound for
         self.goal = (torch.arange(p, dtype=torch.int32, device=core.device) % g).expand(n, p).contiguous()
@@ -599,9 +606,14 @@ class Walkers:
             sets = reset[:, None]
             self._cells.again(mask=sets)
             self.fields.update(self._cells.points[:, 0], mask=sets.expand(-1, g))
+            if self.flows is not None:
+                self.flows.update(mask=sets.expand(-1, g))
             self._spawns.again(mask=sets.expand(-1, s.n_slots))
             self._spawn(sets)
-        self.fields.waypoints(s.positions, goal=self.goal, out=self._towards)
+        if self.flows is not None:
+            self.flows.at(s.positions, goal=self.goal, out=self._towards)
+        else:
+            self.fields.waypoints(s.positions, goal=self.goal, out=self._towards)
         self._walked = cuda.walk(c.scenery, c.agents, s, self._towards, out=self._walked, **self._walk)
         self.fields.at(s.positions, goal=self.goal, out=self._left)
         self.goal.add_(self._left < self.arrive).remainder_(g)

@@ -4,7 +4,7 @@ they hold (kernels: ``csrc/kernels/navfield.h``, ``csrc/kernels/navpath.h``, ``c
 and their lengths -, ``csrc/kernels/navseen.h``, ``csrc/kernels/navage.h``
 - when each cell was last seen -, ``csrc/kernels/navwindow.h``,
 ``csrc/kernels/navdraw.h``), the connected regions of any per-cell mask (``csrc/kernels/navregion.h``), the cells in sight of a
-point (``csrc/kernels/navview.h``), the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``), per-zone counts, least values and nearest cells of any labels (``csrc/kernels/navzone.h``), and
+point (``csrc/kernels/navview.h``), the seed each cell of a seeded field leads to (``csrc/kernels/navbasin.h``), every cell's look-ahead waypoint (``csrc/kernels/navflow.h``), per-zone counts, least values and nearest cells of any labels (``csrc/kernels/navzone.h``), and
 the distance to the nearest wall, per cell and per point (``csrc/kernels/navclear.h``).
 No counterpart in the reference;
 reached as ``megastep_amd.cuda.<name>``."""
@@ -247,6 +247,10 @@ class _Fields:
         chosen = torch.empty((n, p), dtype=torch.int32, device=dev) if hops else None
         _launch(dev, *self._waypoints_call(p, points.data_ptr(), _ptr(goal), lookahead, out.data_ptr(), _ptr(chosen)))
         return (out, chosen) if hops else out
+
+    def flows(self, lookahead=16, mask=None, out=None):
+        """:func:`flow_fields` of these fields: every cell's look-ahead waypoint, for crowds."""
+        return flow_fields(self, lookahead=lookahead, mask=mask, out=out)
 
     def paths(self, points, goal=None, max_points=256):
         """The whole path from each of ``points`` (N, P, 2) to its goal (``goal``: as :meth:`at`), as a :class:`Paths`: the point,
@@ -1623,6 +1627,93 @@ def basins(fields, ids=None, n_ids=0, mask=None, out=None, passes=False):
     result = Basins(fields, ids, n_ids, new((size,), torch.int32, -1), new(shape + (n_ids,), torch.int32, 0) if n_ids else None,
                     new(shape, torch.int32, 0), new(shape, torch.int32, 0) if passes else None)
     return result.update(mask)
+
+
+#: the framed cells - ``(nx + 2)*(ny + 2)`` - an env may have for :func:`flow_fields` to keep its hops in LDS, a byte a cell, for each
+#: of the kernel's three instantiations (16, 64 and 160 KiB); the launch is the least that holds the grid's largest env, and a larger
+#: env takes its hops from global memory, to the same result
+FLOW_CAPACITY = (16384, 65536, 163840)
+#: what :attr:`FlowFields.targets` holds on a cell whose target is the field's goal point itself
+FLOW_GOAL = -2
+
+
+class FlowFields:
+    """Result of :func:`flow_fields`: for each field of a :class:`DistanceFields`, :class:`SeededFields` or :class:`CostFields` where a
+    body standing on each cell should head. ``targets``: the flat int32 store in the fields' layout (field (n, g) at
+    ``G*grid.starts[n] + g*nx*ny``) - the row-major index within the env of the cell whose centre is the target, :data:`FLOW_GOAL`
+    where it is the goal point, -1 on a blocked cell and on one no path leaves; a seed, and a cell whose chain breaks at once,
+    names itself. ``fields`` is kept by reference: :meth:`update` reads its values as they stand. ``took`` (N, P) int32: what the
+    last :meth:`at` with ``took=True`` recorded. The rule: include/megastep_hip.h (``MsNavFlows``), DESIGN.md 3.38."""
+
+    def __init__(self, fields, lookahead, targets):
+        self.fields, self.grid, self.lookahead, self.targets, self.took = fields, fields.grid, int(lookahead), targets, None
+
+    n_fields = property(lambda self: self.fields.n_goals)
+
+    def _kind(self):
+        """(goals, costs, n_costs) as the two structs take them: what kind of field the chains follow."""
+        f = self.fields
+        if isinstance(f, CostFields):
+            return None, f.cost.data_ptr(), f.n_costs
+        return (None if isinstance(f, SeededFields) else f.goals.data_ptr()), None, 0
+
+    def image(self, e, g=0):
+        """(ny, nx) int32 view of the targets of field ``g`` of env ``e``, row 0 at the lowest y."""
+        return _store_view(self.grid, self.targets, self.n_fields, e, g)
+
+    def update(self, mask=None):
+        """Computes the targets of the fields marked in the (N, G) bool ``mask`` (default all) again in place, from the fields'
+        values as they stand now; the others keep theirs. One launch, no host synchronisation, nothing allocated: the call can be
+        captured in a HIP graph."""
+        grid, g = self.grid, self.n_fields
+        mask = _mask(mask, grid.n_envs, g, 'G')
+        dev = _require_gpu(self.fields.values, self.targets, grid.free, *self.fields._own(), *_some(mask))
+        goals, costs, n_costs = self._kind()
+        _launch(dev, 'flows', grid, _lib.MsNavFlows(g, self.fields.values.data_ptr(), goals, costs, n_costs, self.lookahead, _ptr(mask),
+                                                    self.targets.data_ptr()))
+        return self
+
+    def at(self, points, goal=None, out=None, took=False):
+        """(N, P, 2) float32: where to head for from each of ``points`` (N, P, 2) - the target of the cell the point is anchored on
+        (:meth:`DistanceFields.waypoints`' start) when that is the cell itself or the point can see it, else the point's own
+        waypoint at look-ahead 2; NaN exactly where :meth:`DistanceFields.at` gives +inf, and where a stale store names no target.
+        ``goal`` (N, P) integers name the field each point asks, default point k field k (then P must be G). ``out``: the (N, P, 2)
+        tensor to write; ``took=True`` also records, in :attr:`took`, 1 where the cell's target was taken, 0 the fallback, -1 no
+        answer. One launch, a lane a point, no host synchronisation; with ``out`` (and, for ``took``, after the first call of the
+        shape) nothing is allocated. This is not :meth:`DistanceFields.waypoints`' answer: there the sight runs from the point."""
+        n, p, goal, dev = self.fields._queries(points, goal)
+        out = _answer(out, (n, p, 2), dev)
+        if took and (self.took is None or self.took.shape != (n, p)):
+            self.took = torch.empty((n, p), dtype=torch.int32, device=dev)
+        goals, costs, n_costs = self._kind()
+        _launch(dev, 'flow_query', self.grid, _lib.MsNavFlowQuery(p, points.data_ptr(), _ptr(goal), self.fields.values.data_ptr(), goals, costs,
+                                                                  n_costs, self.n_fields, self.targets.data_ptr(), out.data_ptr(),
+                                                                  _ptr(self.took) if took else None))
+        return out
+
+
+def flow_fields(fields, lookahead=16, mask=None, out=None):
+    """Flow fields: for every cell of every field of ``fields`` - a :class:`DistanceFields`, a :class:`SeededFields` or a
+    :class:`CostFields` - the look-ahead waypoint of a body standing on the cell: the furthest of the next ``lookahead`` (1..64)
+    cells down the field that the cell's centre can see, the goal point itself once that is in sight. Every walker bound for one
+    destination reads the same field, and a field changes only when it is computed again; so the answer is kept per cell, and
+    :meth:`FlowFields.at` serves a crowd with one lookup and at most one sight test a body, a lane a body, where
+    :meth:`DistanceFields.waypoints` spends a wavefront on each.
+
+    One launch, one workgroup per field: what the hop does at each cell as a byte in LDS, then a lane a cell
+    (include/megastep_hip.h, ``MsNavFlows``). ``mask`` (N, G) bool: compute only the marked fields (the others keep
+    what ``out`` held; -1 without ``out``); ``out``: the :class:`FlowFields` of an earlier call with the same fields and
+    look-ahead to write into. No host synchronisation: the call can be captured in a HIP graph."""
+    if not isinstance(fields, _Fields):
+        raise RuntimeError('fields must be a DistanceFields, a SeededFields or a CostFields')
+    if not isinstance(lookahead, int) or isinstance(lookahead, bool) or not 1 <= lookahead <= 64:
+        raise RuntimeError(f'lookahead must be an integer in 1..64; got {lookahead}')
+    if out is not None:
+        if not isinstance(out, FlowFields) or out.fields is not fields or out.lookahead != lookahead:
+            raise RuntimeError('`out` must come from a flow_fields call with the same fields and lookahead')
+        return out.update(mask)
+    dev = _require_gpu(fields.values, fields.grid.free)
+    return FlowFields(fields, lookahead, torch.full((max(fields.n_goals*fields.grid.n_cells, 1),), -1, dtype=torch.int32, device=dev)).update(mask)
 
 
 #: the most zones one :func:`zones` call tells apart
