@@ -306,6 +306,34 @@ typedef struct MsSlide {
 int ms_slide_physics(const MsScenery* scenery, const MsAgents* agents, const MsMovement* movement, const MsStepExtras* extras,
                      const MsSlide* slide, float* progress, const MsConfig* config, void* hip_stream);
 
+/* Solid bodies (no counterpart in the reference): ms_step_physics' step with the slots of an Items-shaped store in
+ * the agents' way, opt-in.  A BODY is a slot of `positions` (N, P, 2), P in 1 .. 1024, whose two coordinates are finite; it is a
+ * DISC OF THE CONFIG'S agent_radius, as a walker is.  The step is ms_step_physics' - movement, books, respawn before or after,
+ * lifespans, IMU, headings, fan schedule: MsMovement and MsStepExtras as they stand - with one addition to an agent's fold.  After
+ * the env's other agents and its static rows, from the same x, every body k of the env is folded by the rule physics applies
+ * between two agents - x = the least of x and collision_cc(p, u, o_k), behind the exact reach cull (meet_agent, kernels/step.h):
+ *   velocities == NULL          o_k = (p_k, 0, 0): the body at rest, where it stands when the call begins
+ *   velocities (N, P, 2), m/s   o_k = (p_k, v_k.x/fps, v_k.y/fps), the symmetric rule; a v_k that is not finite in both
+ *                               components counts as (0, 0)
+ * x is a least value of floats in [+0, 1]: the same in any order.  The epilogue is the plain step's: x < 1 is a dead stop.
+ * `progress` = x.  With c_k body k's own fraction (1 where the cull passes it over):
+ *   blocker   (N, A) int32 or NULL: the least k with c_k == x, when x < 1; else -1 - so an agent stopped by a wall or another
+ *             agent nearer than every body gets -1
+ *   contacts  (N, A) int32 or NULL: how many bodies gave c_k < 1
+ * THE STORE IS READ ONLY: the call never moves a body, and agents do not push one.  Bodies of another radius are out of scope.
+ * Refused with MS_EINVAL before anything is launched: a NULL `bodies` or `positions`; `positions` or `velocities` not 8-byte
+ * aligned, the agents' positions or velocity likewise; `blocker` or `contacts` not 4-byte aligned; n_slots outside 1 .. 1024; more
+ * than 64 agents an env (a lane an agent). */
+typedef struct MsBodies {
+    int          n_slots;     /* P, 1 .. 1024                                                                          */
+    const float* positions;   /* (N, P, 2); a slot with a coordinate that is not finite is absent; 8-byte aligned      */
+    const float* velocities;  /* (N, P, 2) m/s or NULL (every body at rest); 8-byte aligned                            */
+    int*         blocker;     /* (N, A) out or NULL                                                                    */
+    int*         contacts;    /* (N, A) out or NULL                                                                    */
+} MsBodies;
+int ms_bodies_physics(const MsScenery* scenery, const MsAgents* agents, const MsMovement* movement, const MsStepExtras* extras,
+                      const MsBodies* bodies, float* progress, const MsConfig* config, void* hip_stream);
+
 /* Replaces `render(scenery, agents) -> Render` (wrappers.cpp:82, kernels.cu:297-475):
  * draw (rewrites the agent rows of lines_vals) -> raycast -> shade, one fused launch. */
 int ms_render(const MsScenery* scenery, const MsAgents* agents, const MsRender* out,

@@ -354,6 +354,14 @@ int ms_debug_rollout_scheme(int scheme);
 int ms_host_slide(const float* walls, const long long* wall_starts, int n_envs, int n_agents, const MsAgents* agents,
                   const MsMovement* movement, const MsStepExtras* extras, const MsSlide* slide, float* progress,
                   const MsConfig* config);
+/* The step among bodies (MsBodies) stated serially over the kernel's own per-pair functions (kernels/bodies.h), as ms_host_slide
+ * states the sliding step: `walls`, `wall_starts`, `agents`, `movement`, `extras` and `progress` as there, every pointer of `bodies`
+ * host memory shaped as ms_bodies_physics'.  Every agent meets every other agent, every static row and every present body of its
+ * env, each behind its own reach cull: no grid and no box.  Returns what ms_bodies_physics would: MS_OK, or MS_EINVAL for
+ * arguments it would refuse (and for NULL walls or wall_starts, n_envs < 1, n_agents < 1). */
+int ms_host_bodies(const float* walls, const long long* wall_starts, int n_envs, int n_agents, const MsAgents* agents,
+                   const MsMovement* movement, const MsStepExtras* extras, const MsBodies* bodies, float* progress,
+                   const MsConfig* config);
 /* The serial host statement of ms_shade (kernels/shade.h), on HOST arrays: ray after ray through the per-ray
  * functions shade_kernel calls - the texel filter, the drawn row, the shadow test, the sum - the lights taken the plain way,
  * light after light against row after row.  Of `scenery` it reads n_envs, n_agents, n_model, lights_*, lines_vals / widths /

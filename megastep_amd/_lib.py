@@ -65,6 +65,10 @@ class MsSlide(C.Structure):
     _fields_ = [('bounce', C.c_float), ('slid', C.c_void_p), ('stopped', C.c_void_p)]
 
 
+class MsBodies(C.Structure):
+    _fields_ = [('n_slots', C.c_int), ('positions', C.c_void_p), ('velocities', C.c_void_p), ('blocker', C.c_void_p), ('contacts', C.c_void_p)]
+
+
 class MsRender(C.Structure):
     _fields_ = [('indices', C.c_void_p), ('locations', C.c_void_p), ('dots', C.c_void_p), ('distances', C.c_void_p),
                 ('screen', C.c_void_p), ('workspace', C.c_void_p), ('obs_rgb', C.c_void_p), ('obs_depth', C.c_void_p),
@@ -335,6 +339,7 @@ PROTOTYPES = {
     'ms_move_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _ptr, _p(MsConfig), _ptr]),
     'ms_step_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _ptr, _p(MsConfig), _ptr]),
     'ms_slide_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsSlide), _ptr, _p(MsConfig), _ptr]),
+    'ms_bodies_physics': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsBodies), _ptr, _p(MsConfig), _ptr]),
     'ms_render': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRender), _p(MsConfig), _ptr]),
     'ms_step_render': (_int, [_p(MsScenery), _p(MsAgents), _ptr, _p(MsRender), _p(MsConfig), _ptr]),
     'ms_move_step_render': (_int, [_p(MsScenery), _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _ptr, _p(MsRender), _p(MsConfig), _ptr]),
@@ -462,6 +467,7 @@ PROTOTYPES = {
     'ms_debug_rollout_scheme': (_int, [_int]),
     'ms_host_scenarios': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsScenarios), _p(MsConfig)]),
     'ms_host_slide': (_int, [_ptr, _ptr, _int, _int, _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsSlide), _ptr, _p(MsConfig)]),
+    'ms_host_bodies': (_int, [_ptr, _ptr, _int, _int, _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsBodies), _ptr, _p(MsConfig)]),
     'ms_host_shade': (_int, [_p(MsScenery), _p(MsAgents), _p(MsShade)]),
     'ms_host_wall_hidden': (_int, [_flt]*4 + [_f32p, _f32p, _flt]),
     'ms_host_wall_sectors': (None, [_flt]*4 + [_f32p, _i32p, _i32p, _f32p, _i32p]),

@@ -1,6 +1,6 @@
 // host/step.h -- the step family: ms_step_physics with ms_move_physics and ms_physics (kernels/physics.h), ms_slide_physics
-// (slide.h), ms_rollouts (rollout.h), ms_scenarios (scenario.h); their host instantiations ms_host_slide, ms_host_rollouts,
-// ms_host_scenarios; the hooks ms_host_physics_pack, ms_host_move_velocity, ms_host_order_fans; and the step's debug switches.
+// (slide.h), ms_bodies_physics (bodies.h), ms_rollouts (rollout.h), ms_scenarios (scenario.h); their host instantiations
+// ms_host_slide, ms_host_bodies, ms_host_rollouts, ms_host_scenarios; the hooks ms_host_physics_pack, ms_host_move_velocity, ms_host_order_fans; and the step's debug switches.
 namespace {
 // Envs per wave (physics_kernel's PACK), with a wall grid (without one an env's walls are streamed, and there is nothing to put
 // side by side) and while a wave's agents stay within half its lanes: as many as bring the launch down to about 4096 waves -
@@ -64,6 +64,14 @@ FanSort fan_sort_for(const MsAgents* ag, const MsScenery* sc, const int R) {
 int slide_status(const MsSlide* sl, const int n_agents) {
     if (!sl || !(sl->bounce >= 0.f && sl->bounce <= 1.f)) return MS_EINVAL;
     return n_agents > WAVE ? MS_EUNSUPPORTED : MS_OK;                    // (a lane an agent)
+}
+
+// what ms_bodies_physics and ms_host_bodies refuse alike of an MsBodies, the agents it stops and the shape it is for: a NULL
+// store, a misaligned pointer (8 bytes for the (.., 2) arrays, 4 for the ints), P outside 1 .. 1024, more than 64 agents an env
+int bodies_status(const MsBodies* bd, const MsAgents* ag, const int n_agents) {
+    if (!bd || !bd->positions || bd->n_slots < 1 || bd->n_slots > BODY_MAX_SLOTS || n_agents > WAVE) return MS_EINVAL;
+    if (!all_aligned<8>(bd->positions, bd->velocities, ag->positions, ag->velocity) || !all_aligned<4>(bd->blocker, bd->contacts)) return MS_EINVAL;
+    return MS_OK;
 }
 
 // what ms_rollouts and ms_host_rollouts refuse alike: the limits and the pointers of an MsRollouts
@@ -166,6 +174,33 @@ int ms_host_slide(const float* walls, const long long* wall_starts, int n_envs, 
     MsMovement mvv; MsStepExtras exv;
     step_options_of(mv, ex, mvv, exv);
     slide_serial(walls, wall_starts, n_envs, n_agents, *ag, mv ? &mvv : nullptr, exv, ex != nullptr, *sl, progress, cfg->agent_radius, cfg->fps);
+    return MS_OK;
+}
+
+int ms_bodies_physics(const MsScenery* sc, const MsAgents* ag, const MsMovement* mv, const MsStepExtras* ex, const MsBodies* bd,
+                      float* progress, const MsConfig* cfg, void* stream) {
+    if (!scenery_ok(sc) || !agents_ok(ag) || !progress || !config_ok(cfg)) return MS_EINVAL;
+    if (!step_options_ok(mv, ex) || !aligned(ag->schedule, 4) || !near_lists_ok(sc) || !aligned(ag->headings, 16)) return MS_EINVAL;
+    if (const int st = bodies_status(bd, ag, sc->n_agents)) return st;
+    g_last_step_fused = 0;                                               // (a step among bodies is never the one-launch step)
+    MsMovement mvv; MsStepExtras exv;
+    step_options_of(mv, ex, mvv, exv);
+    const FanSort fs = fan_sort_for(ag, sc, cfg->res);
+    static void (*const kernels[2][2])(MsScenery, AgentsK, float*, float, float, MsMovement, MsStepExtras, MsBodies, Divisor, FanSort) = {
+        {physics_bodies_kernel<1, 1>, physics_bodies_kernel<0, 1>}, {physics_bodies_kernel<1, 0>, physics_bodies_kernel<0, 0>}};   // [no extras][no movement], as above
+    hipLaunchKernelGGL(kernels[ex == nullptr][mv == nullptr], dim3(fs.n_blocks + sc->n_envs), dim3(WAVE), 0, (hipStream_t)stream, *sc,
+                       agents_k(*ag), progress, cfg->agent_radius, cfg->fps, mvv, exv, *bd, divisor_of((unsigned)sc->n_agents), fs);
+    return launch_status();
+}
+
+int ms_host_bodies(const float* walls, const long long* wall_starts, int n_envs, int n_agents, const MsAgents* ag, const MsMovement* mv,
+                   const MsStepExtras* ex, const MsBodies* bd, float* progress, const MsConfig* cfg) {
+    if (!walls || !wall_starts || n_envs < 1 || n_agents < 1 || !agents_ok(ag) || !progress || !config_ok(cfg)) return MS_EINVAL;
+    if (!step_options_ok(mv, ex)) return MS_EINVAL;
+    if (const int st = bodies_status(bd, ag, n_agents)) return st;
+    MsMovement mvv; MsStepExtras exv;
+    step_options_of(mv, ex, mvv, exv);
+    bodies_serial(walls, wall_starts, n_envs, n_agents, *ag, mv ? &mvv : nullptr, exv, ex != nullptr, *bd, progress, cfg->agent_radius, cfg->fps);
     return MS_OK;
 }
 

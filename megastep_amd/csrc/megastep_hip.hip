@@ -7,7 +7,7 @@
 //   host/*.h      the host side of the C-ABI - argument checks, argument structs, launches, the ms_host_* / ms_test_* /
 //                 ms_debug_* hooks: common.h (what every family shares) first, then a file a family as under kernels/.
 //
-// Thirty-eight kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Thirty-nine kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -19,6 +19,11 @@
 //                   EXTRA = 1 the envs' respawn / lifespan / IMU bookkeeping.  Where the agents carry a fan schedule, the
 //                   launch's first blocks sort the last render's costs into the next render's starting order.
 //                                                            (reference: kernels.cu:179-230, modules.py:24-118,263-366)
+//   physics_bodies_kernel<MOVE, EXTRA>   that step with the slots of a store in the agents' way (MsBodies): physics_slide_kernel's
+//                   frame - a wavefront an env, a lane an agent, the walls' pairs through the LDS pair list - and a pass over the
+//                   store: the lanes stride the slots, a body at rest is put to the union of the agents' reach boxes (shuffles),
+//                   then to agents_apart agent by agent, and the surviving (body, agent) pairs share the walls' pair list, a bit of
+//                   the tag apart; x by atomicMin on its bits, the blocker as a 64-bit (bits(c), k) key beside it.   (no counterpart)
 //   rollout_kernel      candidate action plans rolled through that step: one wavefront per (agent, 64 plans), a lane a plan,
 //                   the state in registers for the whole horizon; each step a lane walks the near list of the cell it stands
 //                   in (or, where no list applies, its env's static rows) through the step's own functions.   (no counterpart)
@@ -209,6 +214,7 @@ struct Probe {
 #include "kernels/step.h"
 #include "kernels/physics.h"
 #include "kernels/slide.h"
+#include "kernels/bodies.h"
 #include "kernels/rollout.h"
 #include "kernels/scenario.h"
 #include "kernels/lighting.h"

@@ -366,15 +366,21 @@ class Render:
 class Physics:
     """Result of :func:`physics` (reference: common.h:224-226, wrappers.cpp:166-172)."""
 
-    def __init__(self, progress, slid=None, stopped=None):
+    def __init__(self, progress, slid=None, stopped=None, blocker=None, contacts=None):
         self._progress = progress
         self._slid, self._stopped = slid, stopped
+        self._blocker, self._contacts = blocker, contacts
 
     progress = property(lambda self: self._progress)
     #: of a sliding step (``slide=``), else None: (N, A) float32, the share of the step each agent spent sliding along what blocked it
     slid = property(lambda self: self._slid)
     #: of a sliding step, else None: (N, A) uint8, 1 where the step's collisions zeroed the agent's velocity - a dead stop
     stopped = property(lambda self: self._stopped)
+    #: of a step among bodies (``bodies=``), else None: (N, A) int32, the slot of the body that stopped each agent - the least one
+    #: whose own fraction is the agent's ``progress`` - or -1: nothing stopped it, or a wall or an agent nearer than every body did
+    blocker = property(lambda self: self._blocker)
+    #: of a step among bodies, else None: (N, A) int32, how many bodies each agent's step ran into
+    contacts = property(lambda self: self._contacts)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -484,16 +490,56 @@ def _slide_options(slide, agents, out):
     return C.byref(_lib.MsSlide(bounce, slid.data_ptr(), stopped.data_ptr())), slid, stopped
 
 
-def _step_launch(scenery, agents, mv, ex, sl, progress, cfg, dev):
-    """The physics launch of :func:`physics` and of a two-launch :func:`step_render`: the sliding step where ``sl`` is given."""
+def _bodies_options(bodies, slide, agents, out):
+    """``physics``' ``bodies`` argument (see there) as ``(MsBodies by reference, blocker, contacts)``, or ``(None, None, None)``.
+    The two outputs are the ones of ``out``, an earlier such call's Physics, else fresh."""
+    if bodies is None:
+        return None, None, None
+    if slide is not None and slide is not False:
+        raise RuntimeError('bodies and slide do not go together: the normals of bodies that block are not part of the sliding step')
+    options = dict(bodies) if isinstance(bodies, dict) else dict(store=bodies)
+    store, moving = options.pop('store', None), options.pop('moving', False)
+    if options or moving not in (True, False):
+        raise RuntimeError(f'bodies takes a store or dict(store=..., moving=False); got {sorted(options)} besides, moving = {moving!r}')
+    positions = getattr(store, 'positions', None)
+    n, a = agents.angles.shape
+    if not isinstance(positions, torch.Tensor) or positions.ndim != 3 or positions.shape[0] != n or positions.shape[2] != 2 \
+            or not 1 <= positions.shape[1] <= 1024:
+        raise RuntimeError(f'bodies needs a store (cuda.Items, cuda.Projectiles, cuda.Walkers) of ({n}, P, 2) positions, P in 1 .. 1024')
+    _check(positions, 'the store\'s positions', torch.float32, 3)
+    velocities = None
+    if moving:
+        velocities = getattr(store, 'velocities', None)
+        if not isinstance(velocities, torch.Tensor) or velocities.shape != positions.shape:
+            raise RuntimeError('moving bodies need a store with velocities shaped as its positions (cuda.Projectiles, cuda.Walkers)')
+        _check(velocities, 'the store\'s velocities', torch.float32, 3)
+    _require_gpu(positions, *(() if velocities is None else (velocities,)))
+    if positions.device != agents.angles.device:
+        raise RuntimeError('the store and the agents are on different devices')
+    if a > 64:
+        raise RuntimeError(f'bodies stop at most 64 agents an env; got {a}')
+    if out is not None and (out.blocker is None or out.contacts is None):
+        raise RuntimeError('out must be the Physics of an earlier step among bodies')
+    blocker = torch.empty((n, a), dtype=torch.int32, device=positions.device) if out is None else out.blocker
+    contacts = torch.empty((n, a), dtype=torch.int32, device=positions.device) if out is None else out.contacts
+    spec = _lib.MsBodies(positions.shape[1], positions.data_ptr(), None if velocities is None else velocities.data_ptr(),
+                         blocker.data_ptr(), contacts.data_ptr())
+    return C.byref(spec), blocker, contacts
+
+
+def _step_launch(scenery, agents, mv, ex, sl, progress, cfg, dev, bd=None):
+    """The physics launch of :func:`physics` and of a two-launch :func:`step_render`: the sliding step where ``sl`` is given, the
+    step among bodies where ``bd`` is."""
     args = (C.byref(scenery._as_struct()), C.byref(_ms_agents(agents, step=True)), mv, ex)
-    if sl is None:
+    if bd is not None:
+        _lib.check(_lib.lib().ms_bodies_physics(*args, bd, C.c_void_p(progress.data_ptr()), C.byref(cfg), _stream(dev)))
+    elif sl is None:
         _lib.check(_lib.lib().ms_step_physics(*args, C.c_void_p(progress.data_ptr()), C.byref(cfg), _stream(dev)))
     else:
         _lib.check(_lib.lib().ms_slide_physics(*args, sl, C.c_void_p(progress.data_ptr()), C.byref(cfg), _stream(dev)))
 
 
-def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=None, imu=None, config=None, slide=None):
+def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=None, imu=None, config=None, slide=None, bodies=None):
     """Advances the agents by one step, stopping them at walls and at each other; updates ``agents`` in place and
     returns :class:`Physics` with the (N, A) ``progress`` (reference: wrappers.cpp:69, kernels.cu:179-230).
 
@@ -513,8 +559,14 @@ def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=No
       step along what blocked it, its velocity deflected off the contact normal with ``bounce`` of it turned outwards, in the
       same launch. ``progress`` stays the plain step's, bit for bit, and the result also has ``slid`` and ``stopped``
       (:class:`Physics`). At most 64 agents an env.
+    * ``bodies=store`` or ``dict(store=..., moving=False)``: solid bodies (include/megastep_hip.h, MsBodies). Every
+      present slot of the store - a :class:`Items`, :class:`Projectiles` or :class:`Walkers`, up to 1024 slots an env - is a disc of
+      ``agent_radius`` that stops an agent as another agent would, in the same launch as the walls and the other agents: at rest
+      where it stands, or with ``moving=True`` by the symmetric rule with the store's ``velocities``. The store is only read. The
+      result also has ``blocker`` and ``contacts`` (:class:`Physics`). At most 64 agents an env; not together with ``slide``.
 
-    ``out``: the :class:`Physics` of an earlier call, to write ``progress`` (and ``slid``, ``stopped``) into instead of allocating.
+    ``out``: the :class:`Physics` of an earlier call, to write ``progress`` (and ``slid``, ``stopped``; ``blocker``, ``contacts``)
+    into instead of allocating.
     ``config``: the constants of this call (:func:`config`); default: the ones ``agents`` carry (a Core's do), else initialize()'s."""
     dev = scenery._device()
     _agents_on(agents, dev)
@@ -524,12 +576,13 @@ def physics(scenery, agents, movement=None, out=None, respawn=None, lifespans=No
                            f'{shape}, got {tuple(agents.angles.shape)}')
     mv, ex = _step_options(agents, shape, movement, respawn, lifespans, imu)
     sl, slid, stopped = _slide_options(slide, agents, out)
+    bd, blocker, contacts = _bodies_options(bodies, slide, agents, out)
     progress = _progress(agents, out)
     _ab_switches()
     scenery._check_grid(dev)
     with _on(dev):
-        _step_launch(scenery, agents, mv, ex, sl, progress, _cfg(agents, config), dev)
-    return _stepped(agents, progress, out, slid, stopped)
+        _step_launch(scenery, agents, mv, ex, sl, progress, _cfg(agents, config), dev, bd)
+    return _stepped(agents, progress, out, slid, stopped, blocker, contacts)
 
 
 def _progress(agents, out):
@@ -537,12 +590,13 @@ def _progress(agents, out):
     return torch.empty_like(agents.angles) if out is None else out.progress
 
 
-def _stepped(agents, progress, out, slid=None, stopped=None):
+def _stepped(agents, progress, out, slid=None, stopped=None, blocker=None, contacts=None):
     """What a step leaves behind: the agents' heading cache filled (where they use it) and their epoch moved on; ``progress``
-    (and a sliding step's ``slid`` and ``stopped``) as a :class:`Physics` - ``out`` if the step wrote into one."""
+    (and a sliding step's ``slid`` and ``stopped``, a step among bodies' ``blocker`` and ``contacts``) as a :class:`Physics` -
+    ``out`` if the step wrote into one."""
     agents._cached = agents._use_cache
     agents._epoch += 1
-    return Physics(progress, slid, stopped) if out is None else out
+    return Physics(progress, slid, stopped, blocker, contacts) if out is None else out
 
 
 FIELDS = ('indices', 'locations', 'dots', 'distances', 'screen')

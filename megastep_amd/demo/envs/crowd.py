@@ -2,7 +2,9 @@
 go from destination to destination along the shortest paths, keep apart from each other and from the agents, and are stopped by
 walls, by each other and by the agents - pedestrians, not learners: they have no camera and cast no rays. The agents see them,
 drawn into the camera's RGB-D fan (:func:`megastep_amd.cuda.overlay_items`), and are not stopped by them: walking into one costs
-``bump``, coming within the walkers' personal distance of one costs ``close``. No counterpart in the reference.
+``bump``, coming within the walkers' personal distance of one costs ``close``. With ``solid=True`` the crowd is in the agents' way
+(:func:`megastep_amd.cuda.physics`, ``bodies``): an agent is stopped at a walker as it is at another agent. No counterpart in the
+reference.
 
 The observations come from the full-resolution frame through :class:`~megastep_amd.modules.RGB`'s and
 :class:`~megastep_amd.modules.Depth`'s tensor-op path, as Forage's do and for its reason. A step has no host synchronisation and
@@ -16,17 +18,23 @@ from .pointgoal import PointGoal, books
 
 class Crowd(PointGoal):
 
-    def __init__(self, n_envs, n_walkers=16, *args, n_goals=4, speeds=(.6, 1.4), bump=.5, close=.05, seed=0, walk=None, flow=False, **kwargs):
+    def __init__(self, n_envs, n_walkers=16, *args, n_goals=4, speeds=(.6, 1.4), bump=.5, close=.05, seed=0, walk=None, flow=False, solid=False,
+                 **kwargs):
         """``n_walkers``, ``n_goals``, ``speeds``, ``seed``, ``walk`` (a dict of :func:`~megastep_amd.cuda.walk`'s ``personal``,
         ``push``, ``keep``, ``agents_push``), ``flow``: :class:`~megastep_amd.modules.Walkers`'; ``bump``, ``close``: what a walker that runs into
         an agent, and one within ``personal`` of it, take off the agent's reward of the step. Everything else is
-        :class:`PointGoal`'s, less ``spl`` and ``panorama``. The crowd keeps walking across the agents' episodes."""
+        :class:`PointGoal`'s, less ``spl`` and ``panorama``. The crowd keeps walking across the agents' episodes. ``solid=True``: the
+        walkers stop the agents (not with ``slide``); the observation and the reward keep their keys."""
         if kwargs.get('spl') or kwargs.get('panorama'):
             raise RuntimeError('Crowd takes neither spl nor panorama')
+        if solid and kwargs.get('slide'):
+            raise RuntimeError('a solid Crowd does not slide: bodies and slide do not go together')
         super().__init__(n_envs, *args, **kwargs)
         #: the :class:`~megastep_amd.modules.Walkers` of the env
         self.walkers = modules.Walkers(self.core, self.grid, n_walkers, n_goals=n_goals, speeds=speeds, seed=seed, colors=(.9, .6, .1), flow=flow,
-                                       **(walk or {}))
+                                       solid=solid, **(walk or {}))
+        if solid:
+            self.walkers.stop(self._mover)
         self.bump, self.close = float(bump), float(close)
         self._frame = None
 

@@ -38,23 +38,24 @@ def _table(actionset):
     return torch.cat([actionset.velocity, actionset.angvelocity[:, None]], 1).contiguous()
 
 
-def _move(core, actionset, actions, keep, respawn=None, imu=None, table=None, slide=None):
+def _move(core, actionset, actions, keep, respawn=None, imu=None, table=None, slide=None, bodies=None):
     """The velocity update of both movement modules, then physics. On the GPU it is part of the physics launch
     (cuda.physics' ``movement``) - as are, when the env hands them over, the respawn of the agents it wants respawned
     (``respawn``: :meth:`RandomSpawns.draw`) and the IMU observation of the new state (``imu``: the :class:`IMU`
     module, which then returns it from its next call). The tensor ops below are the same arithmetic, and what the
-    reference runs. ``slide``: cuda.physics' sliding contacts - a second phase of the launch, which the tensor ops do not have."""
+    reference runs. ``slide``: cuda.physics' sliding contacts - a second phase of the launch, which the tensor ops do not have; ``bodies``:
+    its solid bodies, a pass of the launch they do not have either."""
     agents = core.agents
     if agents.angles.is_cuda:
         table = _table(actionset) if table is None else table
         reading = None if imu is None else (torch.empty(agents.angles.shape + (3,), device=core.device), imu.ang_scale, imu.speed_scale)
         result = cuda.physics(core.scenery, agents, movement=(actions.long().contiguous(), table, keep), respawn=respawn, imu=reading,
-                              slide=slide)
+                              slide=slide, bodies=bodies)
         if imu is not None:
             imu._pending = (reading[0], agents._epoch)          # valid until somebody else touches the agents
         return result
-    if slide:
-        raise RuntimeError('sliding contacts are part of the physics launch: they need the agents on a GPU')
+    if slide or bodies is not None:
+        raise RuntimeError('sliding contacts and solid bodies are part of the physics launch: they need the agents on a GPU')
     if respawn is not None and not respawn['after']:
         _respawn(agents, respawn)
     delta = actionset[actions.long()]
@@ -84,11 +85,15 @@ def _respawn(agents, request):
 
 class SimpleMovement:
 
-    def __init__(self, core, speed=10, ang_speed=180, n_agents=None, slide=None):
+    def __init__(self, core, speed=10, ang_speed=180, n_agents=None, slide=None, bodies=None):
         """Movement without momentum: seven actions - nothing, forward/backward, strafe left/right, turn left/right
-        (reference: modules.py:24-66). ``slide``: cuda.physics' sliding contacts (True, or dict(bounce=.05)) for every step."""
+        (reference: modules.py:24-66). ``slide``: cuda.physics' sliding contacts (True, or dict(bounce=.05)) for every step.
+        ``bodies``: cuda.physics' solid bodies (a store, or dict(store=..., moving=False)) for every step - not with ``slide``;
+        :attr:`stepped` then has each step's ``blocker`` and ``contacts``. Rollouts and scenarios do not see the bodies."""
         self.core = core
-        self.slide = slide
+        self.slide, self.bodies = slide, bodies
+        #: the :class:`cuda.Physics` of the last step (None before the first)
+        self.stepped = None
         self._actionset = _actionset(core, speed, ang_speed)
         self._table = _table(self._actionset)
         self.keep = 0.                           # (of the old velocity: none - see cuda.physics' ``movement``)
@@ -97,7 +102,8 @@ class SimpleMovement:
     def __call__(self, decision, respawn=None, imu=None):
         """Sets the agents' velocities from ``decision.actions`` ((n_env, n_agent) ints in 0..6), then steps physics.
         ``respawn`` / ``imu``: see :func:`_move`."""
-        return _move(self.core, self._actionset, decision.actions, 0., respawn, imu, self._table, self.slide)
+        self.stepped = _move(self.core, self._actionset, decision.actions, 0., respawn, imu, self._table, self.slide, self.bodies)
+        return self.stepped
 
     def rollouts(self, actions, **kw):
         """:func:`cuda.rollouts` of ``actions`` ((n_env, n_agent, K, H) or (K, H) int64) under this module's table and ``keep``:
@@ -118,11 +124,12 @@ class SimpleMovement:
 
 class MomentumMovement:
 
-    def __init__(self, core, accel=5, ang_accel=180, decay=.125, n_agents=None, slide=None):
+    def __init__(self, core, accel=5, ang_accel=180, decay=.125, n_agents=None, slide=None, bodies=None):
         """Movement with momentum: the seven actions accelerate rather than move, and velocity decays by ``decay``
-        each step (reference: modules.py:68-118). ``slide``: as SimpleMovement's."""
+        each step (reference: modules.py:68-118). ``slide``, ``bodies``: as SimpleMovement's."""
         self.core = core
-        self.slide = slide
+        self.slide, self.bodies = slide, bodies
+        self.stepped = None
         self._actionset = _actionset(core, accel, ang_accel)
         self._table = _table(self._actionset)
         self.decay = decay
@@ -132,7 +139,8 @@ class MomentumMovement:
     keep = property(lambda self: 1 - self.decay)
 
     def __call__(self, decision, respawn=None, imu=None):
-        return _move(self.core, self._actionset, decision.actions, self.keep, respawn, imu, self._table, self.slide)
+        self.stepped = _move(self.core, self._actionset, decision.actions, self.keep, respawn, imu, self._table, self.slide, self.bodies)
+        return self.stepped
 
     rollouts = SimpleMovement.rollouts
     scenarios = SimpleMovement.scenarios
@@ -167,6 +175,8 @@ def move_render(core, mover, decision, observers=None, fields=None, centre=False
     arguments, same result - through :func:`cuda.step_render`: for a single-agent world of up to 64 rays (the reference's tutorial
     env, demo/envs/minimal.py) a whole ``env.step()`` is then one launch; any other shape is the two launches it always was."""
     agents = core.agents
+    if mover.bodies is not None:
+        raise RuntimeError('the one-call step and render does not take solid bodies: call the mover, then render')
     pooled = _pooling(tuple(observers), bool(centre)) if observers else None
     reading = None if imu is None else (torch.empty(agents.angles.shape + (3,), device=core.device), imu.ang_scale, imu.speed_scale)
     _, raw = cuda.step_render(core.scenery, agents, fields=fields, pooled=pooled, seen=seen,
@@ -547,7 +557,7 @@ class Projectiles:
 
 class Walkers:
 
-    def __init__(self, core, grid, n_walkers, n_goals=4, speeds=(.6, 1.4), arrive=.3, seed=0, colors=None, flow=False, **walk):
+    def __init__(self, core, grid, n_walkers, n_goals=4, speeds=(.6, 1.4), arrive=.3, seed=0, colors=None, flow=False, solid=False, **walk):
         """Others who walk (:func:`cuda.walk`; no counterpart in the reference): ``n_walkers`` bodies an env that go from
         destination to destination among the agents, without being agents - no camera, no rays. Every env draws ``n_goals``
         destination cells (:func:`cuda.cell_draws`) in its largest connected space (:meth:`cuda.Regions.largest_mask`) and keeps
@@ -564,8 +574,13 @@ class Walkers:
         ``flow=True`` heads the walkers by the destinations' flow fields instead (:func:`cuda.flow_fields`, kept as ``flows``):
         every cell's waypoint is computed with the fields, when an env is reset, and a call looks each walker's up
         (:meth:`cuda.FlowFields.at`: a lane a walker) where it otherwise spends a wavefront on each. The walkers' courses are close
-        to, not the same as, those without it: the sight runs from the cell's centre first."""
-        self.core, self.grid = core, grid
+        to, not the same as, those without it: the sight runs from the cell's centre first.
+
+        ``solid=True``: the walkers are in the agents' way. :attr:`bodies` is then the store as a movement module's ``bodies=``
+        takes it - :meth:`stop` hands it to one - and :attr:`blocker` the walker that stopped each agent at that module's last
+        step. The agents' step runs first and meets the walkers at rest where they stand; the tick follows and meets the agents
+        where they stand (:func:`cuda.physics`, ``bodies``)."""
+        self.core, self.grid, self.solid, self._mover = core, grid, bool(solid), None
         n, p, g = core.n_envs, int(n_walkers), int(n_goals)
         self.store = cuda.walkers(n, p, colors=colors, device=core.device)
         self.radius, self.arrive, self._lo, self._hi, self._walk = float(core.agent_radius), float(arrive), float(speeds[0]), float(speeds[1]), walk
@@ -592,6 +607,24 @@ class Walkers:
 
     #: (n_env, P, 2) float32: where the walkers are; the store's own tensor
     positions = property(lambda self: self.store.positions)
+    #: the store, for a movement module's ``bodies=``, with ``solid=True``; else None
+    bodies = property(lambda self: self.store if self.solid else None)
+
+    def stop(self, mover):
+        """Puts the walkers in the way of ``mover``'s agents (``solid=True`` only): its steps get the store as ``bodies``."""
+        if not self.solid:
+            raise RuntimeError('only solid walkers stop agents: modules.Walkers(..., solid=True)')
+        if mover.slide:
+            raise RuntimeError('bodies and slide do not go together')
+        mover.bodies, self._mover = self.store, mover
+        return mover
+
+    @property
+    def blocker(self):
+        """(n_env, n_agent) int32: the walker that stopped each agent at the last step of the mover given to :meth:`stop`, or -1."""
+        if self._mover is None or self._mover.stepped is None:
+            raise RuntimeError('no step yet: give a movement module to stop() and call it')
+        return self._mover.stepped.blocker
     #: the :class:`cuda.Walked` of the last call (None before the first)
     walked = property(lambda self: self._walked)
     #: (n_env, n_agent) int32 of the last tick: the walkers that ran into each agent, and those within ``personal`` of it
