@@ -297,6 +297,12 @@ int ms_test_cell_at(const float* geom, const float* cell, const float* point, in
 int ms_test_tex_filter(const float* x, const int* w, int* l, int* r, float* lw, float* rw, long long count, void* hip_stream);
 int ms_test_light_blocked(const float* light, const float* to, const float* a, const float* v, unsigned char* blocked, long long count,
                           void* hip_stream);
+/* The workgroup's ordered compaction (kernels/math.h: block_compact) alone, on the device: ONE workgroup walks the `count` flags
+ * keep[i] (DEVICE pointers) in rounds of 256 as the kernels that stage rows in LDS walk an env's rows, and writes slot[i] - the
+ * place of flag i among the kept ones, counted from 0 in ascending i; -1 where keep[i] == 0 - and total[0], how many are kept.
+ * MS_EINVAL for a NULL pointer or a negative count (or one beyond 2^31 - 1); count == 0 launches and writes nothing.
+ * tests/test_gpu_compact.py holds it to numpy.cumsum. */
+int ms_test_block_compact(const unsigned char* keep, int* slot, int* total, long long count, void* hip_stream);
 /* Host instantiation of the light grid's build (ms_bake; accelerates kernels.cu:238-268) for one cell c (row-major in a grid
  * of nx x ny cells of size `cell` from (ox, oy)), over n_walls walls (n_walls x 4 floats: ax, ay, bx, by) and n_lights
  * lights (n_lights x 3: x, y, intensity), HOST memory: words[4] = the lights' 2-bit verdicts as in lg_vals (0 unknown, 1 lit,

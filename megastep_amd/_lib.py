@@ -457,6 +457,7 @@ PROTOTYPES = {
     'ms_test_cell_at': (_int, [_ptr]*5 + [C.c_longlong, _ptr]),
     'ms_test_tex_filter': (_int, [_ptr]*6 + [C.c_longlong, _ptr]),
     'ms_test_light_blocked': (_int, [_ptr]*5 + [C.c_longlong, _ptr]),
+    'ms_test_block_compact': (_int, [_ptr]*3 + [C.c_longlong, _ptr]),
     'ms_host_lightgrid_cell': (_int, [_ptr, _int, _ptr, _int, _flt, _flt, _int, _int, _flt, _int, _ptr, _ptr, _int]),
     'ms_host_fold_hits': (_int, [_f32p, _i32p, _int, _i32p, _f32p, _i32p]),
     'ms_host_agents_apart': (_int, [_f32p, _f32p, _flt]),

@@ -1,5 +1,5 @@
 // host/probes.h -- the ms_test_* probes (kernels/culltest.h and math.h's arithmetic_test_kernel: the device builds of the culls
-// and shortcuts, an element a lane) and the host hooks of the same predicates: ms_host_ray_interval*, ms_host_agents_apart,
+// and shortcuts, an element a lane; block_compact, one workgroup) and the host hooks of the same predicates: ms_host_ray_interval*, ms_host_agents_apart,
 // ms_host_wall_reach, ms_host_wall_beyond_reach, ms_host_sincospi.
 namespace {
 // ray_interval's launch-invariant values as ms_render works them out, the per-wave ones as render_kernel does: wave `wave` of
@@ -48,6 +48,12 @@ int ms_test_tex_filter(const float* x, const int* w, int* l, int* r, float* lw, 
 int ms_test_light_blocked(const float* light, const float* to, const float* a, const float* v, unsigned char* blocked, long long count,
                           void* stream) {
     return launch_elements(light_blocked_test_kernel, light && to && a && v, count, stream, light, to, a, v, blocked);
+}
+int ms_test_block_compact(const unsigned char* keep, int* slot, int* total, long long count, void* stream) {
+    if (!keep || !slot || !total || count < 0 || count > 0x7fffffffLL) return MS_EINVAL;      // (a slot is an int)
+    if (count == 0) return MS_OK;                                                              // (as launch_elements: no element is no launch)
+    hipLaunchKernelGGL(block_compact_test_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, keep, slot, total, count);
+    return launch_status();
 }
 
 void ms_host_ray_interval_wide(const float* pose, const float* line, int res, float fov, float agent_radius, int groups, int wave,

@@ -7,6 +7,7 @@
 // quotients - a host instantiation says nothing about the device's arithmetic.  These kernels evaluate the very functions the
 // product kernels call, one element a lane, on operands a test hands them (tests/test_gpu_culls.py aims them at the
 // thresholds).  No LDS, no atomics; they read and write only the `count` elements they are given, any output may be NULL.
+// Behind them, the one probe of a workgroup-wide piece: math.h's block_compact (tests/test_gpu_compact.py).
 // ------------------------------------------------------------------------------------------------
 
 #define MS_TEST_ELEMENT const long long i = (long long)blockIdx.x*WG + threadIdx.x; if (i >= count) return;
@@ -83,3 +84,20 @@ __global__ __launch_bounds__(WG) void light_blocked_test_kernel(const float* __r
 }
 
 #undef MS_TEST_ELEMENT
+
+// math.h's block_compact alone: ONE workgroup walks `count` flags in rounds of WG, as the product kernels walk an env's rows - the
+// thread beyond the end keeps nothing - and writes each flag's slot (-1 where it keeps nothing) and the total.  Reads keep[0 .. count),
+// writes slot[0 .. count) and total[0]; every thread makes every round, so the barriers are whole.
+__global__ __launch_bounds__(WG) void block_compact_test_kernel(const unsigned char* __restrict__ keep, int* __restrict__ slot, int* __restrict__ total,
+                                                                const long long count) {
+    __shared__ int s_kept[WAVES];
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    int kept = 0;                                                       // (uniform)
+    for (long long i0 = 0; i0 < count; i0 += WG) {
+        const long long i = i0 + tid;
+        const bool mine = i < count && keep[i] != 0;
+        if (i < count) slot[i] = -1;
+        block_compact(mine, lane, wave, s_kept, kept, [&](const int at) { slot[i] = at; });
+    }
+    if (tid == 0) *total = kept;
+}

@@ -21,8 +21,8 @@
 //                     counts go through integer LDS atomics into the wave's slice and are stored whole.  No float atomics.
 //   item_overlay_kernel   one WORKGROUP up to 256 rays of one origin.  A lane an item, it builds the P billboards for that origin -
 //                     one sqrtf and two divisions per item and origin, not per ray - drops the rows with a NaN and compacts the
-//                     rest in ascending k into LDS by ballot, popcount and a prefix over the waves (nav_draw_kernel's and
-//                     percept_kernel's idiom); then every lane folds its ray over the compacted rows (LDS broadcasts).  A workgroup
+//                     rest in ascending k into LDS (math.h's block_compact); then every lane folds its ray over the compacted
+//                     rows (LDS broadcasts).  A workgroup
 //                     without a live row writes items = -1 and returns.  No cull: none is part of the rule.
 constexpr int ITEM_MAX_ITEMS = 1024, ITEM_MAX_AGENTS = 64, ITEM_MAX_KINDS = 8;
 constexpr unsigned long long ITEM_NONE = ~0ull;      // the key of "no candidate"
@@ -121,9 +121,7 @@ __global__ __launch_bounds__(WG) void item_collect_kernel(const MsScenery sc, co
     __syncthreads();
     if (live) {
         const bool reset = q.reset && q.reset[n];                       // (uniform)
-        const int AF = sc.n_agents*sc.n_model;
-        const int L = sc.lines_widths[n];
-        const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[n];
+        const EnvLines ln = env_lines(sc, n);
         for (int k = lane; k - lane < P; k += WAVE) {                   // (the wave's chunks in step: the ballots below are whole)
             const bool mine = k < P;
             const long long at = (long long)n*P + (mine ? k : P - 1);   // (spare lanes of the last chunk read its last item, store nothing)
@@ -138,9 +136,9 @@ __global__ __launch_bounds__(WG) void item_collect_kernel(const MsScenery sc, co
                     if (__ballot(reached) == 0ull) continue;            // (uniform: nobody's item is in this agent's reach)
                     bool blocked = !reached;
                     if (!q.through_walls)
-                        for (int l = AF; l < L; l++) {
+                        for (int l = ln.AF; l < ln.L; l++) {
                             if (__ballot(!blocked) == 0ull) break;
-                            const float4 row = rows[l];
+                            const float4 row = ln.rows[l];
                             if (!blocked) blocked = view_wall_blocks(px, py, c.x, c.y, rx, ry, row);
                         }
                     if (!blocked) { const unsigned long long key = item_key(rr, a); best = key < best ? key : best; }
@@ -257,15 +255,8 @@ __global__ __launch_bounds__(WG) void item_overlay_kernel(const ItemOverlayArgs 
             row = item_billboard(p, c.x, c.y, q.radius);
             keep = item_row_live(row);
         }
-        const unsigned long long votes = __ballot(keep);
-        if (lane == 0) s_kept[wave] = (int)__popcll(votes);
-        __syncthreads();
-        int at = kept, all = 0;
-        for (int w = 0; w < WAVES; w++) { const int c = s_kept[w]; at += w < wave ? c : 0; all += c; }
-        at += (int)__popcll(votes & ((1ull << lane) - 1ull));
-        if (keep) { s_rows[at] = row; s_ks[at] = k; }                   // (at < P <= 1024: ms_item_overlay checks P)
-        kept += all;
-        __syncthreads();
+        // (no guard: at < P <= 1024, ms_item_overlay checks P)
+        block_compact(keep, lane, wave, s_kept, kept, [&](const int at) { s_rows[at] = row; s_ks[at] = k; });
     }
 
     const int r = chunk*WG + tid;

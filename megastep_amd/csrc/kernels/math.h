@@ -283,12 +283,44 @@ __device__ inline float wave_max_f(float x) {                          // all-la
     asm volatile(MS_SCAN6("v_max_i32_dpp") : "+v"(v));
     return __int_as_float(__builtin_amdgcn_readlane(v, 63));
 }
+// ... and of ANY floats, compared as floats through six xor shuffles (negative values, +-inf; a NaN loses), where wave_max_f
+// compares bit patterns
+__device__ inline float wave_min_f(float v) {
+    for (int s = 32; s > 0; s >>= 1) { const float o = __shfl_xor(v, s); v = o < v ? o : v; }
+    return v;
+}
+__device__ inline float wave_max_any_f(float v) {
+    for (int s = 32; s > 0; s >>= 1) { const float o = __shfl_xor(v, s); v = o > v ? o : v; }
+    return v;
+}
 __device__ inline uint32_t f_bits(float f) { return __float_as_uint(f); }
 // what the wave's lanes wrote to LDS before it, every lane reads after it
 __device__ inline void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The workgroup's ordered compaction, one round of WG candidates: this thread's slot in a list that holds `kept` entries so far.
+// The wave's survivors by ballot, the waves' counts through s_counts (WAVES ints of the caller's LDS), the lane's rank in its ballot.
+// A thread with `keep` hands its slot to `store` - the caller's, written at the call: lists and guards differ.
+//   - all WG threads call it, under uniform control flow: two __syncthreads(), after the counts are written, and after they are
+//     read and the survivors stored - behind the call every thread sees the list, and the next round may write the counts;
+//   - slots ascend with the thread index: the list keeps the candidates' order, and a fold's tie rule its bits;
+//   - `kept` (uniform) grows by the round's total whatever `store` does with its slot: `slot < capacity` guards a store,
+//     `kept > capacity` afterwards says "overflowed".
+// Probed alone by ms_test_block_compact (tests/test_gpu_compact.py).
+template <typename Store>
+__device__ inline void block_compact(const bool keep, const int lane, const int wave, int* const s_counts, int& kept, Store&& store) {
+    const unsigned long long votes = __ballot(keep);
+    if (lane == 0) s_counts[wave] = (int)__popcll(votes);
+    __syncthreads();
+    int slot = kept, total = 0;
+    for (int w = 0; w < WAVES; w++) { const int c = s_counts[w]; slot += w < wave ? c : 0; total += c; }
+    slot += (int)__popcll(votes & ((1ull << lane) - 1ull));
+    if (keep) store(slot);
+    kept += total;
+    __syncthreads();
 }
 
 // One env's rows of `lines` behind a buffer descriptor.  A chunk of 64 rows is then ONE instruction with no address
@@ -309,3 +341,9 @@ struct LineRows {
     __device__ float4 chunk(int lane, int first_row) const { return load((first_row + lane)*16, 0); }
     __device__ float4 row(int i) const { return load(i*16, 0); }
 };
+
+// Env e's rows of `lines`: rows[0 .. AF) the agents', rows[AF .. L) the static ones.  (With the wall grid: step.h's env_rows.)
+struct EnvLines { int AF, L; const float4* rows; };
+__device__ inline EnvLines env_lines(const MsScenery& sc, const int e) {
+    return EnvLines{sc.n_agents*sc.n_model, sc.lines_widths[e], reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[e]};
+}

@@ -15,7 +15,7 @@
 //   nav_clear_kernel<WAVE_CULL>   overhead_kernel's scheme on grid cells: a workgroup a 16 x 16 tile of an env's cells, a lane a
 //                     cell (the grid is sized for the env of most tiles; an env of fewer leaves its spare blocks at once, one of
 //                     more takes a tile after another).  The env's static rows WG at a time: those ov_keeps cannot rule out for
-//                     the box of the tile's centres at R go into an LDS list with their indices, ascending; the list is folded
+//                     the box of the tile's centres at R go into an LDS list with their indices, ascending (block_compact); the list is folded
 //                     when it could overflow and at the end.  ov_keeps drops a row only when no centre in the box can have
 //                     d2 <= R*R with it, so the fold over the list is the fold over all rows, and ascending order keeps the
 //                     tie rule.
@@ -238,9 +238,8 @@ __global__ __launch_bounds__(WG) void nav_clear_kernel(const MsScenery sc, const
     const int tiles_x = (g.nx + OV_TILE - 1)/OV_TILE, tiles_y = (g.ny + OV_TILE - 1)/OV_TILE;
     const long long tiles = (long long)tiles_x*tiles_y;
     const long long first = a.starts[e];
-    const int AF = sc.n_agents*sc.n_model;
-    const int L = sc.lines_widths[e];
-    const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[e];
+    const EnvLines ln = env_lines(sc, e);
+    const int L = ln.L;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {                // (uniform: the grid is sized for the env of most tiles)
         const int ty = (int)(tile / tiles_x), tx = (int)(tile - (long long)ty*tiles_x);
         const int i0 = ty*OV_TILE, j0 = tx*OV_TILE, i1 = min(i0 + OV_TILE - 1, g.ny - 1), j1 = min(j0 + OV_TILE - 1, g.nx - 1);
@@ -251,29 +250,16 @@ __global__ __launch_bounds__(WG) void nav_clear_kernel(const MsScenery sc, const
         const OvBox box = clear_box(g, i0, j0, i1, j1);
         const OvBox wbox = clear_box(g, min(i0 + CLEAR_WAVE_ROWS*wave, i1), j0, min(i0 + CLEAR_WAVE_ROWS*wave + CLEAR_WAVE_ROWS - 1, i1), j1);
         OvBest best{INFINITY, INT_MAX, 0.f};
-        int count = 0;
-        for (int l0 = AF; l0 < L; l0 += WG) {
+        int count = 0;                                                  // (uniform)
+        for (int l0 = ln.AF; l0 < L; l0 += WG) {
             const int l = l0 + tid;
             bool keep = false;
             float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
             if (l < L) {
-                row = rows[l];
+                row = ln.rows[l];
                 keep = !q.cull || ov_keeps(box, q.R, row);
             }
-            // compaction: the wave's survivors by ballot, the waves' counts through LDS (overhead_kernel's)
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) s_wave[wave] = (int)__popcll(m);
-            __syncthreads();
-            int off = count, total = 0;
-            for (int w = 0; w < WAVES; w++) {
-                const int c = s_wave[w];
-                off += w < wave ? c : 0;
-                total += c;
-            }
-            off += (int)__popcll(m & ((1ull << lane) - 1ull));
-            if (keep) { s_rows[off] = row; s_idx[off] = l; }
-            count += total;
-            __syncthreads();
+            block_compact(keep, lane, wave, s_wave, count, [&](const int off) { s_rows[off] = row; s_idx[off] = l; });      // (no guard: the window fits)
             if (count > OV_CHUNK - WG || l0 + WG >= L) {                // (uniform) the list is full, or the env's rows are done
                 clear_fold_list<WAVE_CULL>(s_rows, s_idx, count, x, y, wbox, q.R2, lane, best);
                 count = 0;
@@ -290,14 +276,13 @@ __global__ __launch_bounds__(WG) void nav_clear_query_kernel(const MsScenery sc,
     if (at >= q.total) return;                                          // (uniform in the wave; the kernel has no barrier)
     if (q.mask && !q.mask[at]) return;
     const int e = (int)(at / q.n_points);
-    const int A = sc.n_agents, M = sc.n_model, AF = A*M;
-    const int L = sc.lines_widths[e];
-    const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[e];
+    const EnvLines ln = env_lines(sc, e);
+    const int A = sc.n_agents, M = sc.n_model, AF = ln.AF, L = ln.L;
     const float2 p = reinterpret_cast<const float2*>(q.points)[at];
     const int s = q.with_agents ? clear_skipped(q.skip, at, A) : -1;
     // row l of the env as the query meets it: an agent's at its current pose, as ms_render draws it; a wall's as stored
     auto row_at = [&](const int l) {
-        if (l >= AF) return rows[l];
+        if (l >= AF) return ln.rows[l];
         const int agent = l / M;
         float sn, cs;
         sincospi_f(ag.angles[e*A + agent]/180.f, sn, cs);

@@ -17,13 +17,11 @@
 //
 //   nav_view_kernel   one WORKGROUP a viewpoint (n, p).  The window: the rows and columns whose centres can be in range; the
 //                     bytes of the store outside it are written 0.  The env's static rows are read WG at a time, a row kept
-//                     when its box meets the box of everything in range, and the kept rows compacted into LDS by ballot and
-//                     prefix count (VIEW_WALL_CAPACITY rows; more than fit: the viewpoint sweeps the env's rows in global memory
-//                     at wave-uniform addresses instead, to the same bits).  A wave takes tiles of 8 x 8 window cells, a lane a
-//                     cell, and walks the walls at a wave-uniform index (LDS broadcasts) until every lane is blocked, passing
-//                     over - for four comparisons - a wall whose box misses the box of the tile and the viewpoint: it fails
-//                     `meets` for every cell of the tile.  Then the bytes are stored and the ballots visible & countable
-//                     (& !seen) counted.  The counts go
+//                     when its box meets the box of everything in range, and the kept rows compacted into LDS in their own
+//                     order (math.h's block_compact; VIEW_WALL_CAPACITY rows; more than fit: the viewpoint sweeps the env's rows
+//                     in global memory at wave-uniform addresses instead, to the same bits).  A wave takes tiles of 8 x 8 window
+//                     cells, a lane a cell, and walks the walls (view_walk, below) with the box of the tile and the viewpoint.
+//                     Then the bytes are stored and the ballots visible & countable (& !seen) counted.  The counts go
 //                     through LDS across the waves; one lane stores them.  No atomics, no scratch; with values == NULL no
 //                     byte is written at all - scoring candidate standpoints needs no store.
 constexpr int VIEW_WALL_CAPACITY = 512;              // rows of four floats staged in LDS, 8 KiB: every wall of a plan of the headline's kind
@@ -102,6 +100,31 @@ __host__ __device__ inline bool view_keeps(const ViewBox& b, const float4 w) {
 constexpr int VIEW_TILE = 8;                         // a wave's cells: 8 x 8
 __host__ __device__ inline ViewBox view_tile_box(const ViewPoint& v, const float xa, const float ya, const float xb, const float yb) {
     return ViewBox{v.px < xa ? v.px : xa, v.py < ya ? v.py : ya, v.px > xb ? v.px : xb, v.py > yb ? v.py : yb};
+}
+
+// A wave's walk over the walls at a wave-uniform index: a lane holds the target (x, y), (rx, ry) from the viewpoint, and comes in
+// `blocked` when it has none; `tile`: the box of the viewpoint and the wave's targets.  The `kept` rows staged in s_walls (LDS
+// broadcasts), or on `overflow` the env's static rows in global memory, to the same bits.  Stops when every lane is blocked; passes
+// over - for four comparisons - a wall whose box misses the tile's: it fails `meets` for every target.  (Measured: fetching the next
+// row while this one is tested costs a third more time, not less - the walk is bound by its arithmetic)
+__device__ inline bool view_walk(const ViewPoint& v, const ViewBox& tile, const float x, const float y, const float rx, const float ry, bool blocked,
+                                 const float4* s_walls, const int kept, const bool overflow, const EnvLines& ln) {
+    if (!overflow) {
+        for (int l = 0; l < kept; l++) {
+            if (__ballot(!blocked) == 0ull) break;
+            const float4 row = s_walls[l];
+            if (__ballot(view_keeps(tile, row)) == 0ull) continue;      // (uniform)
+            if (!blocked) blocked = view_wall_blocks(v.px, v.py, x, y, rx, ry, row);
+        }
+    } else {
+        for (int l = ln.AF; l < ln.L; l++) {
+            if (__ballot(!blocked) == 0ull) break;
+            const float4 row = ln.rows[l];
+            if (__ballot(view_keeps(tile, row)) == 0ull) continue;
+            if (!blocked) blocked = view_wall_blocks(v.px, v.py, x, y, rx, ry, row);
+        }
+    }
+    return blocked;
 }
 
 struct NavViewArgs {                                 // MsNavViews, checked
@@ -237,26 +260,17 @@ __global__ __launch_bounds__(WG) void nav_view_kernel(const MsScenery sc, const 
         }
 
     // the walls that can matter, compacted into LDS in their own order
-    const int AF = sc.n_agents*sc.n_model;
-    const int L = sc.lines_widths[e];
-    const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[e];
+    const EnvLines ln = env_lines(sc, e);
     int kept = 0;                                                       // (uniform)
     if (window > 0) {
         const ViewBox box = view_box(v, q.R, a.cell);
-        for (int l0 = AF; l0 < L; l0 += WG) {
+        for (int l0 = ln.AF; l0 < ln.L; l0 += WG) {
             const int l = l0 + tid;
             float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
             bool keep = false;
-            if (l < L) { row = rows[l]; keep = view_keeps(box, row); }
-            const unsigned long long votes = __ballot(keep);
-            if (lane == 0) s_kept[wave] = (int)__popcll(votes);
-            __syncthreads();
-            int at = kept, all = 0;
-            for (int k = 0; k < WAVES; k++) { const int c = s_kept[k]; at += k < wave ? c : 0; all += c; }
-            at += (int)__popcll(votes & ((1ull << lane) - 1ull));
-            if (keep && at < q.capacity) s_walls[at] = row;
-            kept += all;
-            __syncthreads();
+            if (l < ln.L) { row = ln.rows[l]; keep = view_keeps(box, row); }
+            // (kept counts on past the capacity: that is `overflow`)
+            block_compact(keep, lane, wave, s_kept, kept, [&](const int at) { if (at < q.capacity) s_walls[at] = row; });
         }
     }
     const bool overflow = kept > q.capacity;                            // (uniform)
@@ -275,24 +289,9 @@ __global__ __launch_bounds__(WG) void nav_view_kernel(const MsScenery sc, const 
         const float x = nav_centre(geom.x, j, a.cell), y = nav_centre(geom.y, i, a.cell);
         const ViewBox tile = view_tile_box(v, nav_centre(geom.x, ja, a.cell), nav_centre(geom.y, ia, a.cell), nav_centre(geom.x, jb, a.cell),
                                            nav_centre(geom.y, ib, a.cell));
-        float rx, ry;
+        float rx = 0.f, ry = 0.f;
         const bool candidate = mine && view_candidate(v, x, y, q.R2, q.cos_half, rx, ry);
-        bool blocked = !candidate;
-        if (!overflow) {
-            for (int l = 0; l < kept; l++) {
-                if (__ballot(!blocked) == 0ull) break;
-                const float4 row = s_walls[l];
-                if (__ballot(view_keeps(tile, row)) == 0ull) continue;  // (uniform: the wall fails `meets` for every cell of the tile)
-                if (!blocked) blocked = view_wall_blocks(v.px, v.py, x, y, rx, ry, row);
-            }
-        } else {
-            for (int l = AF; l < L; l++) {
-                if (__ballot(!blocked) == 0ull) break;
-                const float4 row = rows[l];
-                if (__ballot(view_keeps(tile, row)) == 0ull) continue;
-                if (!blocked) blocked = view_wall_blocks(v.px, v.py, x, y, rx, ry, row);
-            }
-        }
+        const bool blocked = view_walk(v, tile, x, y, rx, ry, !candidate, s_walls, kept, overflow, ln);
         const bool visible = candidate & !blocked;
         if (out && mine) out[cell] = visible ? 1 : 0;
         const bool counted = visible && (counts[cell] & 1);

@@ -12,7 +12,8 @@
 //
 // One 256-lane workgroup per 16 x 16 tile of one image: env, view and line rows are the same for the whole block.
 //   pass 1 (cull)  the block's lanes test the env's lines 256 at a time against the tile's footprint - the box of the
-//                  tile's pixel centres grown by h and by slack for rounding - and compact the survivors into LDS;
+//                  tile's pixel centres grown by h and by slack for rounding - and compact the survivors into LDS
+//                  (math.h's block_compact);
 //   pass 2 (fold)  each lane folds its pixel over the LDS list by (d2, index): the order of the list does not matter;
 //   chunking       when the list could overflow its OV_CHUNK rows, the block folds it, empties it and culls on, the
 //                  pixels' best (d2, index, t) carried in registers;
@@ -123,12 +124,11 @@ __global__ __launch_bounds__(WG) void overhead_kernel(const MsScenery sc, const 
         const float x = (g0*u + g1*w) + g2, y = (g3*u + g4*w) + g5;
         const OvBox box = ov_footprint(g0, g1, g2, g3, g4, g5, i0, j0, min(i0 + OV_TILE - 1, a.height - 1),
                                        min(j0 + OV_TILE - 1, a.width - 1));
-        const int L = sc.lines_widths[e];
+        const EnvLines ln = env_lines(sc, e);
+        const int L = ln.L, A = sc.n_agents, M = sc.n_model;
         base = sc.lines_starts[e];
-        const int A = sc.n_agents, M = sc.n_model;
-        AF = A*M;
-        const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + base;
-        int count = 0;
+        AF = ln.AF;
+        int count = 0;                                                  // (uniform)
         for (int l0 = 0; l0 < L; l0 += WG) {
             const int l = l0 + tid;
             bool keep = false;
@@ -141,24 +141,11 @@ __global__ __launch_bounds__(WG) void overhead_kernel(const MsScenery sc, const 
                     const float2 p = reinterpret_cast<const float2*>(ag.positions)[e*A + agent];
                     row = drawn_row(s, c, p.x, p.y, reinterpret_cast<const float4*>(sc.model)[l - agent*M]);
                 } else {
-                    row = rows[l];
+                    row = ln.rows[l];
                 }
                 keep = !a.cull || ov_keeps(box, a.half_width, row);
             }
-            // compaction: the wave's survivors by ballot, the waves' counts through LDS
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) s_wave[wave] = (int)__popcll(m);
-            __syncthreads();
-            int off = count, total = 0;
-            for (int q = 0; q < WAVES; q++) {
-                const int c = s_wave[q];
-                off += q < wave ? c : 0;
-                total += c;
-            }
-            off += (int)__popcll(m & ((1ull << lane) - 1ull));
-            if (keep) { s_rows[off] = row; s_idx[off] = l; }
-            count += total;
-            __syncthreads();
+            block_compact(keep, lane, wave, s_wave, count, [&](const int off) { s_rows[off] = row; s_idx[off] = l; });      // (no guard: the window fits)
             if (count > OV_CHUNK - WG || l0 + WG >= L) {                // (uniform) the list is full, or the env's lines are done
                 for (int q = 0; q < count; q++) ov_fold(x, y, s_rows[q], s_idx[q], a.h2, best);
                 count = 0;

@@ -16,12 +16,11 @@
 // cull, its boxes of 64 points and both wall paths, so the CPU suite holds this very text to percept_rule, bit for bit.
 //
 //   percept_kernel    one WORKGROUP an env.  The env's static rows are read WG at a time, a row kept when its box meets the union of
-//                     the unmasked eyes' view_boxes, and the kept rows compacted into LDS by ballot and prefix count
-//                     (VIEW_WALL_CAPACITY rows; more than fit: the env's rows are walked in global memory at wave-uniform addresses
-//                     instead, to the same bits).  A wave takes eyes wave, wave + 4, ...; its lanes take points lane + 64 j.  For
-//                     each 64 points the wave walks the walls at a uniform index (LDS broadcasts) until no lane holds an unblocked
-//                     candidate, passing over - for four comparisons - a wall whose box misses the box of the eye and the wave's
-//                     candidates: it fails `meets` for every one of them.  The per-pair outputs are stored, the count is a
+//                     the unmasked eyes' view_boxes, and the kept rows compacted into LDS in their own order (math.h's
+//                     block_compact; VIEW_WALL_CAPACITY rows; more than fit: the env's rows are walked in global memory at
+//                     wave-uniform addresses instead, to the same bits).  A wave takes eyes wave, wave + 4, ...; its lanes take
+//                     points lane + 64 j.  For each 64 points the wave walks the walls (navview.h's view_walk) with the box of the
+//                     eye and the wave's candidates (math.h's wave_min_f / wave_max_any_f).  The per-pair outputs are stored, the count is a
 //                     popcount of ballots, and the bits of rr of a lane's visible points go to the wave's slice of LDS (each lane
 //                     reads only what it wrote).  The nearest K take K rounds: every lane offers its least unused key
 //                     (bits(rr) << 32) | p, the wave's minimum goes by shuffles, the lane that owns it retires it and rescans
@@ -191,15 +190,6 @@ __device__ inline unsigned long long percept_lane_least(const unsigned* keys, co
     return best;
 }
 
-__device__ inline float percept_wave_min(float v) {
-    for (int s = 32; s > 0; s >>= 1) { const float o = __shfl_xor(v, s); v = o < v ? o : v; }
-    return v;
-}
-__device__ inline float percept_wave_max(float v) {
-    for (int s = 32; s > 0; s >>= 1) { const float o = __shfl_xor(v, s); v = o > v ? o : v; }
-    return v;
-}
-
 __global__ __launch_bounds__(WG) void percept_kernel(const MsScenery sc, const PerceptArgs q) {
     __shared__ float4 s_walls[VIEW_WALL_CAPACITY];
     __shared__ unsigned s_keys[WAVES][PERCEPT_MAX_POINTS];
@@ -209,26 +199,17 @@ __global__ __launch_bounds__(WG) void percept_kernel(const MsScenery sc, const P
     const int E = q.n_eyes, P = q.n_points, K = q.n_nearest;
 
     // the walls that can matter to any eye of the env, compacted into LDS in their own order
-    const int AF = sc.n_agents*sc.n_model;
-    const int L = sc.lines_widths[n];
-    const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[n];
+    const EnvLines ln = env_lines(sc, n);
     int kept = 0;                                                       // (uniform)
     ViewBox box{0.f, 0.f, 0.f, 0.f};
     if (percept_box(q, n, box)) {                                       // (uniform)
-        for (int l0 = AF; l0 < L; l0 += WG) {
+        for (int l0 = ln.AF; l0 < ln.L; l0 += WG) {
             const int l = l0 + tid;
             float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
             bool keep = false;
-            if (l < L) { row = rows[l]; keep = view_keeps(box, row); }
-            const unsigned long long votes = __ballot(keep);
-            if (lane == 0) s_kept[wave] = (int)__popcll(votes);
-            __syncthreads();
-            int at = kept, all = 0;
-            for (int k = 0; k < WAVES; k++) { const int c = s_kept[k]; at += k < wave ? c : 0; all += c; }
-            at += (int)__popcll(votes & ((1ull << lane) - 1ull));
-            if (keep && at < q.capacity) s_walls[at] = row;
-            kept += all;
-            __syncthreads();
+            if (l < ln.L) { row = ln.rows[l]; keep = view_keeps(box, row); }
+            // (kept counts on past the capacity: that is `overflow`)
+            block_compact(keep, lane, wave, s_kept, kept, [&](const int at) { if (at < q.capacity) s_walls[at] = row; });
         }
     }
     const bool overflow = kept > q.capacity;                            // (uniform)
@@ -247,26 +228,9 @@ __global__ __launch_bounds__(WG) void percept_kernel(const MsScenery sc, const P
             const bool mine = p < P;
             float x = 0.f, y = 0.f, rx = 0.f, ry = 0.f, rr = 0.f;
             const bool candidate = mine && live && percept_wanted(q, n, e, p) && percept_point(q, v, n, p, x, y, rx, ry, rr);
-            const ViewBox tile = view_tile_box(v, percept_wave_min(candidate ? x : INFINITY), percept_wave_min(candidate ? y : INFINITY),
-                                               percept_wave_max(candidate ? x : -INFINITY), percept_wave_max(candidate ? y : -INFINITY));
-            bool blocked = !candidate;
-            // (measured: fetching the next row while this one is tested costs a third more time, not less - the walk is bound by
-            // its arithmetic, not by the rows' latency)
-            if (!overflow) {
-                for (int l = 0; l < kept; l++) {
-                    if (__ballot(!blocked) == 0ull) break;
-                    const float4 row = s_walls[l];
-                    if (__ballot(view_keeps(tile, row)) == 0ull) continue;  // (uniform: the wall fails `meets` for every candidate of the wave)
-                    if (!blocked) blocked = view_wall_blocks(v.px, v.py, x, y, rx, ry, row);
-                }
-            } else {
-                for (int l = AF; l < L; l++) {
-                    if (__ballot(!blocked) == 0ull) break;
-                    const float4 row = rows[l];
-                    if (__ballot(view_keeps(tile, row)) == 0ull) continue;
-                    if (!blocked) blocked = view_wall_blocks(v.px, v.py, x, y, rx, ry, row);
-                }
-            }
+            const ViewBox tile = view_tile_box(v, wave_min_f(candidate ? x : INFINITY), wave_min_f(candidate ? y : INFINITY),
+                                               wave_max_any_f(candidate ? x : -INFINITY), wave_max_any_f(candidate ? y : -INFINITY));
+            const bool blocked = view_walk(v, tile, x, y, rx, ry, !candidate, s_walls, kept, overflow, ln);
             const bool visible = candidate & !blocked;
             if (mine) percept_store_pair(q, at*P + p, visible, rx, ry, rr);
             keys[j*WAVE + lane] = visible ? percept_bits(rr) : PERCEPT_HIDDEN;      // (j*64 + lane < 1024: ms_percepts checks P)

@@ -1,7 +1,7 @@
 // kernels/projectile.h -- projectile_kernel.
 // Part of megastep_hip.hip's one translation unit (included there, inside its anonymous namespace, after items.h: a leg is folded by
 // raycast.h's ray_fold, an agent's row drawn by shade.h's shade_row - render.h's drawn_row on the device, its arithmetic on the
-// host - presence is items.h's item_present, the wave-wide min and max percept.h's); not a header to compile on its own.
+// host - presence is items.h's item_present, the wave-wide min and max and the compaction math.h's); not a header to compile on its own.
 // ------------------------------------------------------------------------------------------------
 // projectiles: things that fly, bounce off walls and strike agents           no counterpart in the reference
 // ------------------------------------------------------------------------------------------------
@@ -22,8 +22,8 @@
 //              the store holds.  Nothing of a fired projectile reaches global memory before it has flown.
 //     bodies   the A M agent rows are drawn once per workgroup into LDS, not once per lane.
 //     cull     every lane forms its slots' reach boxes; their union goes through shuffles, then across the waves through LDS.  The
-//              static rows whose box meets the union are compacted into LDS in ascending order by ballot, popcount and a prefix
-//              over the waves (percept_kernel's and item_overlay_kernel's idiom), PROJ_LIST_ROWS of them; an env that keeps more
+//              static rows whose box meets the union are compacted into LDS in ascending order (math.h's block_compact),
+//              PROJ_LIST_ROWS of them; an env that keeps more
 //              walks its rows in global memory, to the same bits.  THE CULL IS EXACT BY CONSTRUCTION: min and max of floats are
 //              exact, so the union box contains every projectile's own box, and a row that fails proj_row_meets against the
 //              union fails the very same comparisons against each box in it - the rule would not have folded it for anyone.
@@ -319,8 +319,8 @@ __global__ __launch_bounds__(WG) void projectile_kernel(const MsScenery sc, cons
             all.x1 = b.x1 > all.x1 ? b.x1 : all.x1; all.y1 = b.y1 > all.y1 ? b.y1 : all.y1;
         }
     }
-    all.x0 = percept_wave_min(all.x0); all.y0 = percept_wave_min(all.y0);
-    all.x1 = percept_wave_max(all.x1); all.y1 = percept_wave_max(all.y1);
+    all.x0 = wave_min_f(all.x0); all.y0 = wave_min_f(all.y0);
+    all.x1 = wave_max_any_f(all.x1); all.y1 = wave_max_any_f(all.y1);
     if (lane == 0) { s_union[wave][0] = all.x0; s_union[wave][1] = all.y0; s_union[wave][2] = all.x1; s_union[wave][3] = all.y1; }
     __syncthreads();                                                    // (also: the bodies are drawn)
     for (int w = 0; w < WAVES; w++) {
@@ -331,8 +331,9 @@ __global__ __launch_bounds__(WG) void projectile_kernel(const MsScenery sc, cons
 
     // the static rows that meet the union, compacted into LDS in ascending order.  Exact: a row that misses the union misses
     // every box in it by proj_row_meets' own comparisons (min and max of floats round nothing).
-    const int L = sc.lines_widths[n];
-    const float4* const rows = reinterpret_cast<const float4*>(sc.lines_vals) + sc.lines_starts[n];
+    const EnvLines ln = env_lines(sc, n);                               // (its AF is the arguments' A M: ms_projectiles fills them from sc)
+    const int L = ln.L;
+    const float4* const rows = ln.rows;
     int kept = 0;                                                       // (uniform)
     if (boxed)
         for (int l0 = AF; l0 < L; l0 += WG) {
@@ -340,15 +341,8 @@ __global__ __launch_bounds__(WG) void projectile_kernel(const MsScenery sc, cons
             float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
             bool keep = false;
             if (l < L) { row = rows[l]; keep = proj_row_meets(all, row); }
-            const unsigned long long votes = __ballot(keep);
-            if (lane == 0) s_kept[wave] = (int)__popcll(votes);
-            __syncthreads();
-            int at = kept, sum = 0;
-            for (int w = 0; w < WAVES; w++) { const int c = s_kept[w]; at += w < wave ? c : 0; sum += c; }
-            at += (int)__popcll(votes & ((1ull << lane) - 1ull));
-            if (keep && at < PROJ_LIST_ROWS) { s_rows[at] = row; s_ls[at] = l; }
-            kept += sum;
-            __syncthreads();
+            // (kept counts on past the list: that is !listed)
+            block_compact(keep, lane, wave, s_kept, kept, [&](const int at) { if (at < PROJ_LIST_ROWS) { s_rows[at] = row; s_ls[at] = l; } });
         }
     const bool listed = kept <= PROJ_LIST_ROWS;                         // (uniform; else: the env's rows in global memory)
 

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from tests.test_navfield_host import CELL, RADIUS, F, plans, spawn_points
-from tests.test_navview_host import CONE, box_walls, hand, plan_views, same, view_rule
+from tests.test_navview_host import CONE, EDGE_R, box_walls, edge_world, hand, kept_rows, plan_views, same, view_rule
 from tests.test_gpu_navseen import _np, _six
 
 pytestmark = pytest.mark.gpu
@@ -104,6 +104,29 @@ def test_a_large_plan_whose_kept_walls_overflow_the_lds():
     want = _same(v, _walls(sc))
     assert (want['counts'] > 200).all()
     print('kept walls:', int(kept.max()), int(kept.min()), 'of', len(walls), '- visible free cells:', want['counts'].reshape(-1).tolist())
+
+
+def _edge_scenery(w):
+    """tests/test_navview_host.edge_world's walls as a scenery of one agent, read back row for row."""
+    from megastep_amd import scene
+    sc = scene.scenery([dict(walls=w.walls[0].reshape(-1, 2, 2), lights=np.array([[1., 1.]]))], 1, device='cuda', bake=False)
+    assert np.array_equal(_walls(sc)[0], w.walls[0])
+    return sc
+
+
+@pytest.mark.parametrize('extra', [0, 1])
+def test_a_viewpoint_that_keeps_exactly_the_capacity_and_one_more(extra):
+    """The edge the capacity guard and the walk share: VIEW_WALL_CAPACITY kept walls fill the LDS list to its last row, one more
+    sends the viewpoint over the env's rows in global memory (the CPU suite shows which world takes which path)."""
+    from megastep_amd import cuda
+    w = edge_world(extra)
+    assert w.capacity == cuda.VIEW_WALL_CAPACITY and kept_rows(w.points[0, 0], EDGE_R, CELL, w.walls[0]) == cuda.VIEW_WALL_CAPACITY + extra
+    sc = _edge_scenery(w)
+    dev = lambda a: torch.as_tensor(a, device='cuda')
+    grid = cuda.NavGrid(dev(w.geom), dev(w.starts), dev(np.concatenate([w.free, np.zeros(1, np.uint8)])), CELL, RADIUS, w.geom, w.starts)
+    v = cuda.view_fields(grid, sc, dev(w.points), EDGE_R)
+    want = _same(v, w.walls)
+    assert 40 < want['counts'][0, 0] < 200
 
 
 def _hand_world():

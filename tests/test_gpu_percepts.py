@@ -8,9 +8,9 @@ import torch
 
 from tests.percept_rule import KEYS, hand_shape, percept_rule, plan_percepts, plan_rule, same
 from tests.test_navfield_host import RADIUS, F, plans, spawn_points
-from tests.test_navview_host import CONE, plan_views
+from tests.test_navview_host import CONE, EDGE_R, edge_world, kept_rows, plan_views
 from tests.test_gpu_navseen import _np, _six
-from tests.test_gpu_navview import _walls
+from tests.test_gpu_navview import _edge_scenery, _walls
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +60,19 @@ def test_a_large_plan_whose_kept_walls_overflow_the_lds():
     same(_result(seen), want)
     assert (want['counts'] > 0).all() and (want['counts'] < 200).all()
     print('kept walls: at least', int(kept.max()), 'of', len(walls), '- visible points:', want['counts'].reshape(-1).tolist())
+
+
+@pytest.mark.parametrize('extra', [0, 1])
+def test_an_eye_that_keeps_exactly_the_capacity_and_one_more(extra):
+    """The edge the capacity guard and the walk share: VIEW_WALL_CAPACITY kept walls fill the LDS list to its last row, one more
+    sends the env's eyes over its rows in global memory (the CPU suite shows which world takes which path)."""
+    from megastep_amd import cuda
+    w = edge_world(extra)
+    assert w.capacity == cuda.VIEW_WALL_CAPACITY and kept_rows(w.points[0, 0], EDGE_R, 0., w.walls[0]) == cuda.VIEW_WALL_CAPACITY + extra
+    seen = cuda.percepts(_edge_scenery(w), _dev(w.targets), eyes=_dev(w.points), max_range=EDGE_R, k=16)
+    want = percept_rule.call(w.walls, w.points, w.targets, EDGE_R, 16)
+    same(_result(seen), want)
+    assert 8 < want['counts'][0, 0] < 56
 
 
 _BOX = []

@@ -501,6 +501,68 @@ def test_a_range_below_half_a_cell_sees_the_cell_it_stands_on_or_nothing():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the edge of the wall capacity
+# ---------------------------------------------------------------------------------------------------------------------
+EDGE_R = 1.5                                         # the range the edge worlds are looked at from
+_EDGE = {}
+
+
+def edge_world(extra):
+    """One env, a 16 x 16-cell grid over [0, 2]^2, one viewpoint near its middle and 64 points over it, and walls of which the
+    viewpoint (or an eye there: tests/test_percept_host.py) keeps exactly capacity + extra at EDGE_R: that many walls 2 cm long
+    well inside [0, 2]^2 - the last of them a longer one next to the viewpoint that nothing else stands in for - and nine well
+    outside every box in question (x >= 4), dealt among them so that no kept row keeps its place. All free, all countable."""
+    if extra not in _EDGE:
+        from megastep_amd import _lib
+        capacity = _lib.lib().ms_host_nav_view_capacity()
+        w = _Hand()
+        rng = np.random.RandomState(31)
+        n_in = capacity + extra
+        mid = rng.uniform(.05, 1.95, (n_in, 2))
+        turn = rng.uniform(0, np.pi, n_in)
+        half = .01*np.stack([np.cos(turn), np.sin(turn)], 1)
+        inside = np.concatenate([mid - half, mid + half], 1).astype(F)
+        inside[-1] = (1.25, .75, 1.25, 1.25)
+        outside = np.array([(4 + k, -3 + k, 4.5 + k, -3 + k) for k in range(9)], F)
+        at = np.sort(rng.choice(n_in - 1, len(outside), replace=False)) + np.arange(len(outside))         # (none behind the last kept row)
+        walls = np.insert(inside, at - np.arange(len(outside)), outside, axis=0)
+        assert len(walls) == n_in + 9 and np.array_equal(walls[-1], inside[-1]) and np.array_equal(walls[at], outside)
+        w.walls, w.capacity, w.last = [walls], capacity, len(walls) - 1
+        w.geom = np.array([(0, 0, 16, 16)], np.int32)
+        w.starts = np.array([0, 256], np.int64)
+        w.free = np.ones(256, np.uint8)
+        w.points = np.array([[(1.03, .97)]], F)
+        w.targets = rng.uniform(.05, 1.95, (1, 64, 2)).astype(F)
+        w.host = _Host(w.geom, w.starts, w.free, w.walls)
+        _EDGE[extra] = w
+    return _EDGE[extra]
+
+
+def kept_rows(p, R, c, walls):
+    """How many rows view_keeps keeps against view_box(p, R, c): navview.h's statements, one binary32 operation each."""
+    R1 = F(F(R)*F(1.0001)) + F(c)
+    x0, y0, x1, y1 = F(p[0]) - R1, F(p[1]) - R1, F(p[0]) + R1, F(p[1]) + R1
+    lo, hi = np.minimum(walls[:, :2], walls[:, 2:]), np.maximum(walls[:, :2], walls[:, 2:])
+    return int(((lo[:, 0] <= x1) & (hi[:, 0] >= x0) & (lo[:, 1] <= y1) & (hi[:, 1] >= y0)).sum())
+
+
+@pytest.mark.parametrize('extra', [0, 1])
+def test_a_viewpoint_that_keeps_exactly_the_capacity_and_one_more(extra):
+    """At the kernel's own capacity (capacity=0) the first world's walls all fit the list and the second's do not, by one: the
+    listed walk, the walk over the env's rows - forced on the first world too, with room for 8 - and the rule agree, byte for byte.
+    The row the list has no room for matters: without it the rule sees more."""
+    w = edge_world(extra)
+    walls, p = w.walls[0], w.points[0, 0]
+    assert kept_rows(p, EDGE_R, CELL, walls) == w.capacity + extra and len(walls) == w.capacity + extra + 9
+    want = view_rule.call(w.geom, w.starts, CELL, w.walls, w.points, EDGE_R, w.free)
+    same(w.host.views(w.points, EDGE_R, w.free), want, ('values', 'counts'))
+    same(w.host.views(w.points, EDGE_R, w.free, capacity=8), want, ('values', 'counts'))
+    assert 40 < want['counts'][0, 0] < 200
+    less = view_rule.call(w.geom, w.starts, CELL, [walls[:w.last]], w.points, EDGE_R, w.free)
+    assert less['counts'][0, 0] > want['counts'][0, 0] + 5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # header, loader, refusals
 # ---------------------------------------------------------------------------------------------------------------------
 FIELDS = ('n_points', 'points', 'headings', 'max_range', 'cos_half', 'countable', 'unseen', 'n_maps', 'slot', 'mask', 'values', 'counts', 'gains')

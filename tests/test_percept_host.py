@@ -14,7 +14,7 @@ import torch
 from tests.percept_rule import KEYS, blank, hand_shape, host, percept_rule, plan_percepts, plan_rule, same
 from tests.test_abi import ROOT, declared_symbols
 from tests.test_navfield_host import F
-from tests.test_navview_host import CONE, _crossings, box_walls, cos_half_of, view_rule
+from tests.test_navview_host import CONE, EDGE_R, _crossings, box_walls, cos_half_of, edge_world, kept_rows, view_rule
 
 INF = float('inf')
 
@@ -99,6 +99,21 @@ def test_shapes_round_the_wave_and_the_workgroup(E, P):
         same(host(w.walls, w.eyes, w.points, 6., K, capacity=capacity, **kw), want)
         if P >= 63 and not cone:
             assert 0 < want['counts'].sum() < E*P
+
+
+@pytest.mark.parametrize('extra', [0, 1])
+def test_an_eye_that_keeps_exactly_the_capacity_and_one_more(extra):
+    """tests/test_navview_host.py's edge worlds through an eye at their viewpoint and their 64 points: at the kernel's own capacity
+    the first world's walls all fit the list and the second's do not, by one; the listed walk, the walk over the env's rows and the
+    rule agree in every output, and the row the list has no room for matters."""
+    w = edge_world(extra)
+    walls = w.walls[0]
+    assert kept_rows(w.points[0, 0], EDGE_R, 0., walls) == w.capacity + extra
+    want = percept_rule.call(w.walls, w.points, w.targets, EDGE_R, 16)
+    same(host(w.walls, w.points, w.targets, EDGE_R, 16), want)
+    same(host(w.walls, w.points, w.targets, EDGE_R, 16, capacity=8), want)
+    assert 8 < want['counts'][0, 0] < 56
+    assert percept_rule.call([walls[:w.last]], w.points, w.targets, EDGE_R, 16)['counts'][0, 0] > want['counts'][0, 0]
 
 
 def _one(eye, points, R=20., K=4, walls=None, **kw):
