@@ -547,6 +547,35 @@ typedef struct MsRollouts {
 int ms_rollouts(const MsScenery* scenery, const MsAgents* agents, const MsRollouts* rollouts, const MsConfig* config,
                 void* hip_stream);
 
+/* Rollouts among bodies (no counterpart in the reference): MsRollouts as it stands, with others 0 or 1 and no slide,
+ * rolled through the step ms_bodies_physics takes - the slots of an Items-shaped store in every candidate's way, in one launch,
+ * where the only other way to know is K H calls of ms_bodies_physics on copies of the world.  n_slots, positions and velocities
+ * read as MsBodies' do: a slot with a coordinate that is not finite is absent, a present one is a disc of agent_radius.
+ * WHERE A BODY IS AT EACH STEP.  For every candidate and h = 0 .. H-1 body k is at q_k^h: q_k^0 its stored position, and
+ * q_k^{h+1} = q_k^h + u_k, one binary32 addition a component a step, in this order, with u_k = v_k/fps - or (0, 0) where v_k is
+ * not finite in both components, and for every body where velocities is NULL: it stands still.  A BODY IS EXTRAPOLATED IN A
+ * STRAIGHT LINE AND IS STOPPED BY NOTHING - not walls, not agents, not other bodies: a forecast, as others = 1 is of the agents.
+ * WHAT STEP h FOLDS.  After the other agents (at rest where the call found them) and the static rows, and from the same x, every
+ * present body: o = (q_k^h, u_k); the pair is passed over when the exact reach cull says so (agents_apart, kernels/math.h), else
+ * c = collision_cc(p, u, o), and x = min(x, c) where c < 1.  Everything else is MsRollouts': the integration, progress, stops,
+ * first_stop, the trail, the mask.  Every c lies in [+0, 1] and the fold is a least value: path and order do not matter to the bits.
+ *   body_stops     (N, A, K) int32 or NULL: the steps whose x < 1 is a body's own fraction - stopped by a body and by nothing nearer
+ *   first_blocker  (N, A, K) int32 or NULL: at the first such step, the least k with c_k == x (MsBodies' blocker); -1: none
+ * The store is READ ONLY.  Nothing is allocated, no global atomics: the call can be captured in a HIP graph.  Sliding steps and
+ * bodies of another radius are out of scope.  Refused with MS_EINVAL before anything is launched: what ms_rollouts refuses; a
+ * NULL `bodies` or `positions`; `positions` or `velocities` not 8-byte aligned, `body_stops` or `first_blocker` not 4-byte
+ * aligned; n_slots outside 1 .. 1024; rollouts->slide != 0; ms_debug_rollout_scheme(1) pinned (the call is a lane a candidate
+ * whatever K is). */
+typedef struct MsRolloutBodies {
+    int          n_slots;        /* P, 1 .. 1024                                                                          */
+    const float* positions;      /* (N, P, 2); a slot with a coordinate that is not finite is absent; 8-byte aligned      */
+    const float* velocities;     /* (N, P, 2) m/s or NULL (every body at rest); 8-byte aligned                            */
+    int*         body_stops;     /* (N, A, K) out or NULL                                                                 */
+    int*         first_blocker;  /* (N, A, K) out or NULL                                                                 */
+} MsRolloutBodies;
+int ms_rollouts_bodies(const MsScenery* scenery, const MsAgents* agents, const MsRollouts* rollouts, const MsRolloutBodies* bodies,
+                       const MsConfig* config, void* hip_stream);
+
 /* Scenarios: whole envs forked S ways and stepped H times, every agent on a plan of its own, in one launch - the multi-agent
  * completion of MsRollouts (no counterpart in the reference, where the only way to know is to step a copy of the world once
  * per scenario and step).  The scenery and the agents are READ ONLY.  For every env n and scenario s, from ALL agents'

@@ -337,6 +337,13 @@ void ms_host_move_velocity(float keep, float ang, const float* delta, float* v, 
  * n_walls > 0, n_agents < 1). */
 int ms_host_rollouts(const float* walls, int n_walls, const MsAgents* agents, int n_agents, const MsRollouts* rollouts,
                      const MsConfig* config);
+/* The rollouts among bodies (MsRolloutBodies) stated serially for ONE env on HOST arrays, as ms_host_rollouts states the plain
+ * ones: rollout_serial's step plus the body loop, the same functions in the same order (kernels/rollout_bodies.h).  `bodies`
+ * holds the one env's share: positions and velocities (P, 2), the outputs (A, K).  Every candidate meets every wall and every
+ * present body, each behind its own reach cull: no grid and no box.  Returns what ms_rollouts_bodies would: MS_OK, or MS_EINVAL
+ * for arguments it would refuse (and for NULL walls with n_walls > 0, n_agents < 1). */
+int ms_host_rollouts_bodies(const float* walls, int n_walls, const MsAgents* agents, int n_agents, const MsRollouts* rollouts,
+                            const MsRolloutBodies* bodies, const MsConfig* config);
 /* The scenarios' rule (MsScenarios) stated serially over the kernel's own per-step functions (kernels/scenario.h, kernels/rollout.h)
  * for ONE env on HOST arrays, as ms_host_rollouts: `walls` the env's n_walls STATIC rows; every pointer of `agents` and of
  * `scenarios` is host memory and holds the one env's share - joint actions (S, A, H), focal (A, K, H) or shared (K, H), base

@@ -123,6 +123,11 @@ class MsRollouts(C.Structure):
                 ('first_stop', C.c_void_p), ('trail', C.c_void_p), ('slide', C.c_int), ('bounce', C.c_float), ('slides', C.c_void_p)]
 
 
+class MsRolloutBodies(C.Structure):
+    _fields_ = [('n_slots', C.c_int), ('positions', C.c_void_p), ('velocities', C.c_void_p), ('body_stops', C.c_void_p),
+                ('first_blocker', C.c_void_p)]
+
+
 class MsNavGrid(C.Structure):
     _fields_ = [('n_envs', C.c_int), ('cell', C.c_float), ('clearance', C.c_float), ('geom', C.c_void_p), ('starts', C.c_void_p),
                 ('max_framed', C.c_int), ('free_cells', C.c_void_p)]
@@ -351,6 +356,7 @@ PROTOTYPES = {
     'ms_camera_pose_rays': (_int, [_p(MsCameraPoses), _ptr]),
     'ms_overhead': (_int, [_p(MsScenery), _p(MsAgents), _p(MsOverhead), _ptr]),
     'ms_rollouts': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRollouts), _p(MsConfig), _ptr]),
+    'ms_rollouts_bodies': (_int, [_p(MsScenery), _p(MsAgents), _p(MsRollouts), _p(MsRolloutBodies), _p(MsConfig), _ptr]),
     'ms_scenarios': (_int, [_p(MsScenery), _p(MsAgents), _p(MsScenarios), _p(MsConfig), _ptr]),
     'ms_nav_free': (_int, [_p(MsScenery), _p(MsNavGrid), _ptr]),
     'ms_nav_fields': (_int, [_p(MsNavGrid), _p(MsNavFields), _ptr]),
@@ -465,6 +471,7 @@ PROTOTYPES = {
     'ms_host_wall_reach': (_flt, [_f32p, _flt]),
     'ms_host_move_velocity': (None, [_flt, _flt, _f32p, _f32p, _f32p]),
     'ms_host_rollouts': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsRollouts), _p(MsConfig)]),
+    'ms_host_rollouts_bodies': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsRollouts), _p(MsRolloutBodies), _p(MsConfig)]),
     'ms_debug_rollout_scheme': (_int, [_int]),
     'ms_host_scenarios': (_int, [_ptr, _int, _p(MsAgents), _int, _p(MsScenarios), _p(MsConfig)]),
     'ms_host_slide': (_int, [_ptr, _ptr, _int, _int, _p(MsAgents), _p(MsMovement), _p(MsStepExtras), _p(MsSlide), _ptr, _p(MsConfig)]),

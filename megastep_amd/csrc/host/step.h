@@ -1,6 +1,6 @@
 // host/step.h -- the step family: ms_step_physics with ms_move_physics and ms_physics (kernels/physics.h), ms_slide_physics
-// (slide.h), ms_bodies_physics (bodies.h), ms_rollouts (rollout.h), ms_scenarios (scenario.h); their host instantiations
-// ms_host_slide, ms_host_bodies, ms_host_rollouts, ms_host_scenarios; the hooks ms_host_physics_pack, ms_host_move_velocity, ms_host_order_fans; and the step's debug switches.
+// (slide.h), ms_bodies_physics (bodies.h), ms_rollouts (rollout.h), ms_rollouts_bodies (rollout_bodies.h), ms_scenarios (scenario.h);
+// their host instantiations ms_host_slide, ms_host_bodies, ms_host_rollouts, ms_host_rollouts_bodies, ms_host_scenarios; the hooks ms_host_physics_pack, ms_host_move_velocity, ms_host_order_fans; and the step's debug switches.
 namespace {
 // Envs per wave (physics_kernel's PACK), with a wall grid (without one an env's walls are streamed, and there is nothing to put
 // side by side) and while a wave's agents stay within half its lanes: as many as bring the launch down to about 4096 waves -
@@ -80,6 +80,14 @@ int rollouts_status(const MsRollouts* r) {
         !is_flag(r->others) || !(r->keep == r->keep) || !r->actions || !r->table || !r->positions || !r->angles ||
         !r->velocity || !r->angvelocity || !r->progress || !r->stops || !r->first_stop) return MS_EINVAL;
     return (!is_flag(r->slide) || (r->slide && !(r->bounce >= 0.f && r->bounce <= 1.f))) ? MS_EINVAL : MS_OK;
+}
+
+// what ms_rollouts_bodies and ms_host_rollouts_bodies refuse alike beyond rollouts_status: a NULL store, a misaligned pointer (8
+// bytes for the (.., 2) arrays, 4 for the ints), P outside 1 .. 1024, a sliding rollout, the lane-a-wall scheme pinned
+int rollout_bodies_status(const MsRollouts* r, const MsRolloutBodies* rb) {
+    if (rollouts_status(r) != MS_OK || !rb || !rb->positions || rb->n_slots < 1 || rb->n_slots > BODY_MAX_SLOTS) return MS_EINVAL;
+    if (!all_aligned<8>(rb->positions, rb->velocities) || !all_aligned<4>(rb->body_stops, rb->first_blocker)) return MS_EINVAL;
+    return (r->slide || g_rollout_scheme == 1) ? MS_EINVAL : MS_OK;
 }
 
 // what ms_scenarios and ms_host_scenarios refuse alike: the limits and the pointers of an MsScenarios, and the agents an env
@@ -232,6 +240,28 @@ int ms_debug_rollout_scheme(int scheme) {
 int ms_host_rollouts(const float* walls, int n_walls, const MsAgents* ag, int n_agents, const MsRollouts* r, const MsConfig* cfg) {
     if (!agents_ok(ag) || !config_ok(cfg) || rollouts_status(r) != MS_OK || n_agents < 1 || n_walls < 0 || (n_walls > 0 && !walls)) return MS_EINVAL;
     rollout_serial(walls, n_walls, *ag, n_agents, *r, cfg->agent_radius, cfg->fps);
+    return MS_OK;
+}
+
+int ms_rollouts_bodies(const MsScenery* sc, const MsAgents* ag, const MsRollouts* r, const MsRolloutBodies* rb, const MsConfig* cfg,
+                       void* stream) {
+    if (!scenery_ok(sc) || !agents_ok(ag) || !config_ok(cfg) || rollout_bodies_status(r, rb) != MS_OK) return MS_EINVAL;
+    if (!all_aligned<8>(r->actions, r->positions, r->velocity, r->trail, ag->positions, ag->velocity) || !near_lists_ok(sc)) return MS_EINVAL;
+    const int groups = (r->n_candidates + WAVE - 1)/WAVE;
+    const long long blocks = (long long)sc->n_envs*sc->n_agents*groups;
+    if (blocks > 0x7fffffffLL) return MS_EUNSUPPORTED;
+    // a lane a candidate whatever K is: the staged list is the wave's, and a candidate's fold stays in its lane's registers.
+    // Dynamic LDS: a float4 and an int a slot - 1.25 KiB at 64 slots, 20 KiB at 1024
+    const size_t lds = (sizeof(float4) + sizeof(int))*(size_t)rb->n_slots;
+    hipLaunchKernelGGL(rollout_bodies_kernel, dim3((unsigned)blocks), dim3(WAVE), lds, (hipStream_t)stream, *sc, agents_k(*ag), *r, *rb,
+                       cfg->agent_radius, cfg->fps, groups, divisor_of((unsigned)groups), divisor_of((unsigned)sc->n_agents));
+    return launch_status();
+}
+
+int ms_host_rollouts_bodies(const float* walls, int n_walls, const MsAgents* ag, int n_agents, const MsRollouts* r, const MsRolloutBodies* rb,
+                            const MsConfig* cfg) {
+    if (!agents_ok(ag) || !config_ok(cfg) || rollout_bodies_status(r, rb) != MS_OK || n_agents < 1 || n_walls < 0 || (n_walls > 0 && !walls)) return MS_EINVAL;
+    rollout_bodies_serial(walls, n_walls, *ag, n_agents, *r, *rb, cfg->agent_radius, cfg->fps);
     return MS_OK;
 }
 

@@ -7,7 +7,7 @@
 //   host/*.h      the host side of the C-ABI - argument checks, argument structs, launches, the ms_host_* / ms_test_* /
 //                 ms_debug_* hooks: common.h (what every family shares) first, then a file a family as under kernels/.
 //
-// Thirty-nine kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
+// Forty kernels, all written wave64-first (DESIGN.md section 3 has the full story of each):
 //
 //   physics_kernel<MOVE, EXTRA, PACK>   one wavefront per env (PACK = 1: per few consecutive envs, side by side - large
 //                   worlds of few agents per env): lane = agent for the state, the reach and the agent-agent
@@ -29,6 +29,10 @@
 //                   in (or, where no list applies, its env's static rows) through the step's own functions.   (no counterpart)
 //   rollout_walls_kernel   the same rule by physics_kernel's scheme - a lane a wall, the candidates one after another, the
 //                   surviving pairs compacted in LDS before the exact test: behind ms_debug_rollout_scheme, for A/B runs.
+//   rollout_bodies_kernel   rollout_kernel's frame with the slots of a store in the candidates' way (MsRolloutBodies): the wave
+//                   stages the env's present bodies once, compacted, in dynamic LDS; each step a body at rest is put to the union
+//                   of the lanes' reach boxes (shuffles), the survivors are read as broadcasts and met by every lane against its
+//                   own task, x and the blocker's key in registers; moving bodies are advanced in LDS between steps.  (no counterpart)
 //   scenario_kernel     whole envs forked S ways, every agent on its own plan: a wavefront holds 64 / A whole scenarios, a lane
 //                   an agent of one; each step the lanes of a scenario show each other their moved (p, v/fps) through LDS and
 //                   meet as physics_kernel's ordered pairs do, then walk their cells' near lists as rollout_kernel.  (no counterpart)
@@ -216,6 +220,7 @@ struct Probe {
 #include "kernels/slide.h"
 #include "kernels/bodies.h"
 #include "kernels/rollout.h"
+#include "kernels/rollout_bodies.h"
 #include "kernels/scenario.h"
 #include "kernels/lighting.h"
 #include "kernels/render.h"

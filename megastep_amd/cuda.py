@@ -490,11 +490,9 @@ def _slide_options(slide, agents, out):
     return C.byref(_lib.MsSlide(bounce, slid.data_ptr(), stopped.data_ptr())), slid, stopped
 
 
-def _bodies_options(bodies, slide, agents, out):
-    """``physics``' ``bodies`` argument (see there) as ``(MsBodies by reference, blocker, contacts)``, or ``(None, None, None)``.
-    The two outputs are the ones of ``out``, an earlier such call's Physics, else fresh."""
-    if bodies is None:
-        return None, None, None
+def _bodies_store(bodies, slide, agents):
+    """A ``bodies`` argument - ``physics``' and ``rollouts``' (see there) - checked against the agents it stops: the store's
+    ``(positions, velocities)``, the velocities None for bodies at rest."""
     if slide is not None and slide is not False:
         raise RuntimeError('bodies and slide do not go together: the normals of bodies that block are not part of the sliding step')
     options = dict(bodies) if isinstance(bodies, dict) else dict(store=bodies)
@@ -516,6 +514,16 @@ def _bodies_options(bodies, slide, agents, out):
     _require_gpu(positions, *(() if velocities is None else (velocities,)))
     if positions.device != agents.angles.device:
         raise RuntimeError('the store and the agents are on different devices')
+    return positions, velocities
+
+
+def _bodies_options(bodies, slide, agents, out):
+    """``physics``' ``bodies`` argument (see there) as ``(MsBodies by reference, blocker, contacts)``, or ``(None, None, None)``.
+    The two outputs are the ones of ``out``, an earlier such call's Physics, else fresh."""
+    if bodies is None:
+        return None, None, None
+    positions, velocities = _bodies_store(bodies, slide, agents)
+    n, a = agents.angles.shape
     if a > 64:
         raise RuntimeError(f'bodies stop at most 64 agents an env; got {a}')
     if out is not None and (out.blocker is None or out.contacts is None):

@@ -57,6 +57,10 @@ class Crowd(PointGoal):
         obs = arrdict.arrdict(rgb=self._rgb(frame), d=self._depth(frame), goal=self._goals.observation())
         return arrdict.arrdict(obs=obs, reset=reset.any(-1), reward=reward - self.bump*walked.bumps - self.close*walked.close)
 
+    def _among(self):
+        """A solid crowd's 'lookahead' expert rolls its plans among the walkers, each going on as it goes now (:func:`cuda.rollouts`, ``bodies``)."""
+        return dict(bodies=dict(store=self.walkers.store, moving=True)) if self.walkers.solid else {}
+
     def state(self, e=0):
         state = super().state(e)
         state['walkers'] = self.walkers.state(e)

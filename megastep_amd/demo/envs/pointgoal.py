@@ -160,8 +160,14 @@ class PointGoal:
                                                      others='repeat')
             return self._anticipate()
         if self._lookahead is None:
-            self._lookahead = modules.LookAhead(self.core, source, self._mover, fallback=modules.PathFollower(self.core, source, cone=15.))
+            self._lookahead = modules.LookAhead(self.core, source, self._mover, fallback=modules.PathFollower(self.core, source, cone=15.),
+                                                **self._among())
         return self._lookahead()
+
+    def _among(self):
+        """What the 'lookahead' expert's plans are rolled among besides the walls and the other agents, as
+        :class:`~megastep_amd.modules.LookAhead`'s keywords: nothing here."""
+        return {}
 
     def state(self, e=0):
         return arrdict.arrdict(core=self.core.state(e), rgb=self._rgb.state(e), d=self._depth.state(e), goals=self._goals.state(e),

@@ -89,7 +89,7 @@ class SimpleMovement:
         """Movement without momentum: seven actions - nothing, forward/backward, strafe left/right, turn left/right
         (reference: modules.py:24-66). ``slide``: cuda.physics' sliding contacts (True, or dict(bounce=.05)) for every step.
         ``bodies``: cuda.physics' solid bodies (a store, or dict(store=..., moving=False)) for every step - not with ``slide``;
-        :attr:`stepped` then has each step's ``blocker`` and ``contacts``. Rollouts and scenarios do not see the bodies."""
+        :attr:`stepped` then has each step's ``blocker`` and ``contacts``. :meth:`rollouts` sees bodies where it is handed them (``bodies=``); scenarios do not."""
         self.core = core
         self.slide, self.bodies = slide, bodies
         #: the :class:`cuda.Physics` of the last step (None before the first)
@@ -108,7 +108,7 @@ class SimpleMovement:
     def rollouts(self, actions, **kw):
         """:func:`cuda.rollouts` of ``actions`` ((n_env, n_agent, K, H) or (K, H) int64) under this module's table and ``keep``:
         where each plan would take every agent as it stands, without moving anybody - sliding, where the module's steps slide.
-        ``kw``: ``others``, ``trail``, ``mask``, ``out``."""
+        ``kw``: ``others``, ``trail``, ``mask``, ``out``, ``bodies``."""
         if self.slide:
             kw.setdefault('slide', self.slide)
         return cuda.rollouts(self.core.scenery, self.core.agents, actions, self._table, keep=self.keep, **kw)
@@ -1602,7 +1602,7 @@ class PathFollower:
 
 class LookAhead:
 
-    def __init__(self, core, goals, mover, horizon=8, switch=2, stop_cost=.5, fallback=None, others='rest'):
+    def __init__(self, core, goals, mover, horizon=8, switch=2, stop_cost=.5, fallback=None, others='rest', bodies=None, body_cost=None):
         """A look-ahead expert with :class:`PathFollower`'s call interface (a local planner in the style of the dynamic-window
         approach; no counterpart in the reference): every agent rolls the plans ``cuda.plans(n_actions, horizon, switch)`` -
         "action i for ``switch`` steps, then action j" - through the physics step itself (``mover.rollouts``, with the env's other
@@ -1618,11 +1618,21 @@ class LookAhead:
         ``others='repeat'``: the env's other agents are not at rest - every one of them is taken to repeat, for the whole
         horizon, the action this module returned for it at its previous call (the no-op, 0, before the first), all of them
         moving and meeting together as in the step itself (``mover.rollouts(plans, others=base)``). ``base`` is
-        an (n_env, n_agent, H) buffer written in place, so the call still captures."""
+        an (n_env, n_agent, H) buffer written in place, so the call still captures.
+
+        ``bodies``: a store or ``dict(store=..., moving=False)``, handed to the rollout (:func:`cuda.rollouts`, ``bodies``;
+        DESIGN.md 3.40): the plans are rolled among the store's bodies, which stop a plan as they stop the agent - not with
+        ``others='repeat'``. A step a body stopped (``body_stops``) then costs a plan ``body_cost`` metres where every other dead
+        stop costs ``stop_cost``; the default, ``None``, is ``stop_cost``, which changes nothing: those steps are in ``stops``."""
         if others not in ('rest', 'repeat'):
             raise RuntimeError(f"others must be 'rest' or 'repeat'; got {others!r}")
+        if bodies is not None and others == 'repeat':
+            raise RuntimeError("bodies are rolled among others at rest: not with others='repeat'")
+        if body_cost is not None and bodies is None:
+            raise RuntimeError('body_cost prices the steps a body stopped: it needs bodies')
         self.core, self.goals, self.mover = core, goals, mover
         self.horizon, self.switch, self.stop_cost = int(horizon), switch, float(stop_cost)
+        self.bodies, self.body_cost = bodies, self.stop_cost if body_cost is None else float(body_cost)
         self.fallback = PathFollower(core, goals) if fallback is None else fallback
         n_actions = mover._table.shape[0]
         #: (K, H) int64: the plans every agent rolls
@@ -1663,8 +1673,11 @@ class LookAhead:
     def __call__(self):
         """``arrdict(actions=(n_env, n_agent) int64)``: the decision for the agents as they stand."""
         n, a, k = self.core.n_envs, self.core.n_agents, self.plans.shape[0]
-        self._rolled = self.mover.rollouts(self.plans, others=self._others if self.base is None else self.base, out=self._rolled)
+        among = {} if self.bodies is None else dict(bodies=self.bodies)
+        self._rolled = self.mover.rollouts(self.plans, others=self._others if self.base is None else self.base, out=self._rolled, **among)
         self.values = self.goals.fields.at(self._rolled.positions.view(n, a*k, 2), goal=self._agent).view(n, a, k)
+        if self.body_cost != self.stop_cost:                             # (choose() prices every stop at stop_cost: the difference here)
+            self.values = self.values + (self.body_cost - self.stop_cost)*self._rolled.body_stops.to(self.values.dtype)
         action, none = self.choose(self.values, self._rolled.stops, self.plans, self.stop_cost)
         actions = torch.where(none, self.fallback().actions, action)
         if self.base is not None:

@@ -17,10 +17,13 @@ class Rollouts:
     share of a step the candidate could take; ``stops`` (N, A, K) int32, the steps at which it was stopped; ``first_stop``
     (N, A, K) int32, the first of them, ``H`` when there was none; ``trail`` (N, A, K, H, 2), the position after every step, or
     ``None`` when it was not asked for. Of a call with ``slide``: ``stops`` and ``first_stop`` count the steps that ended in a dead
-    stop - the velocity zeroed - and ``slides`` (N, A, K) int32 the steps that slid the whole of their remainder; else ``None``."""
+    stop - the velocity zeroed - and ``slides`` (N, A, K) int32 the steps that slid the whole of their remainder; else ``None``.
+    Of a call with ``bodies``: ``body_stops`` (N, A, K) int32, the steps stopped by a body and by nothing nearer, and
+    ``first_blocker`` (N, A, K) int32, the slot that stopped the first of them, -1 where there was none; else ``None``."""
 
-    def __init__(self, positions, angles, velocity, angvelocity, progress, stops, first_stop, trail, slides=None):
-        self._t = (positions, angles, velocity, angvelocity, progress, stops, first_stop, trail, slides)
+    def __init__(self, positions, angles, velocity, angvelocity, progress, stops, first_stop, trail, slides=None, body_stops=None,
+                 first_blocker=None):
+        self._t = (positions, angles, velocity, angvelocity, progress, stops, first_stop, trail, slides, body_stops, first_blocker)
 
     positions = property(lambda self: self._t[0])
     angles = property(lambda self: self._t[1])
@@ -31,6 +34,8 @@ class Rollouts:
     first_stop = property(lambda self: self._t[6])
     trail = property(lambda self: self._t[7])
     slides = property(lambda self: self._t[8])
+    body_stops = property(lambda self: self._t[9])
+    first_blocker = property(lambda self: self._t[10])
 
 
 def plans(n_actions, horizon, switch=None, device=None):
@@ -65,15 +70,17 @@ def _bounce(slide):
     return bounce
 
 
-def _fresh(n, a, k, h, trail, dev, slide=False):
+def _fresh(n, a, k, h, trail, dev, slide=False, bodies=False):
     """The buffers of a call without ``out``, holding what an agent that is not rolled reads as: NaN poses, progress 1, no stop."""
     nan = lambda *shape: torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
+    ints = lambda value: torch.full((n, a, k), value, dtype=torch.int32, device=dev)
     return Rollouts(nan(n, a, k, 2), nan(n, a, k), nan(n, a, k, 2), nan(n, a, k), torch.ones((n, a, k), dtype=torch.float32, device=dev),
-                    torch.zeros((n, a, k), dtype=torch.int32, device=dev), torch.full((n, a, k), h, dtype=torch.int32, device=dev),
-                    nan(n, a, k, h, 2) if trail else None, torch.zeros((n, a, k), dtype=torch.int32, device=dev) if slide else None)
+                    ints(0), ints(h), nan(n, a, k, h, 2) if trail else None, ints(0) if slide else None,
+                    ints(0) if bodies else None, ints(-1) if bodies else None)
 
 
-def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False, mask=None, out=None, config=None, slide=None):
+def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False, mask=None, out=None, config=None, slide=None,
+             bodies=None):
     """Rolls ``K`` candidate plans of ``H`` actions for every agent through the step :func:`physics` takes, in one launch, and
     returns :class:`Rollouts`. Neither the scenery nor the agents are modified.
 
@@ -90,6 +97,11 @@ def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False,
     earlier call with the same shapes, to write into. ``config``: see :func:`physics` (``agent_radius`` and ``fps`` are read).
     ``slide``: ``True`` or ``dict(bounce=.05)`` - every step is :func:`physics`' sliding step, the others at rest in both its
     phases; the result then has ``slides``, and its ``stops`` count dead stops.
+    ``bodies``: a store or ``dict(store=..., moving=False)``, as :func:`physics`' - every step is its step among bodies
+    (include/megastep_hip.h, MsRolloutBodies): the store's present slots, up to 1024 an env, stop a candidate as
+    they stop an agent. At rest they stand where the call found them; with ``moving=True`` each goes on in a straight line at
+    its velocity, step after step, stopped by nothing - a forecast, as ``others='rest'`` is. The result then has ``body_stops``
+    and ``first_blocker``. Not with ``slide``, and not among moving others.
 
     ``1 <= K <= 256`` and ``1 <= H <= 64``. Respawns, lifespans and the IMU are not part of a rollout.
     No host synchronisation, nothing allocated with ``out``: the call can be captured in a HIP graph."""
@@ -113,6 +125,8 @@ def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False,
     if isinstance(others, torch.Tensor):
         if slide is not None and slide is not False:
             raise RuntimeError('slide is not part of a rollout among moving others: sliding steps are stated for others at rest only')
+        if bodies is not None:
+            raise RuntimeError('bodies are not part of a rollout among moving others: they are stated for others at rest or absent only')
         from .scenarios import _focal
         return _focal(scenery, agents, actions, others, table, keep, trail, mask, out, config, k, h, shared)
     if others not in (None, 'rest'):
@@ -131,12 +145,21 @@ def rollouts(scenery, agents, actions, table, keep=0., others=None, trail=False,
     trail = bool(trail)
     bounce = _bounce(slide)
     sliding = bounce is not None
-    key = (n, a, k, h, trail, dev) + ((True,) if sliding else ())       # (a plain call's key is what it was)
-    result = _result_for(out, key, 'a rollouts', lambda: _fresh(n, a, k, h, trail, dev, sliding))
+    store = None
+    if bodies is not None:
+        from .cuda import _bodies_store
+        store = _bodies_store(bodies, slide, agents)
+    key = (n, a, k, h, trail, dev) + ((True,) if sliding else ()) + (('bodies',) if store is not None else ())   # (a plain call's key is what it was)
+    result = _result_for(out, key, 'a rollouts', lambda: _fresh(n, a, k, h, trail, dev, sliding, store is not None))
     ptrs = [t.data_ptr() if t is not None else None for t in result._t]
     query = _lib.MsRollouts(k, h, actions.data_ptr(), int(shared), table.data_ptr(), table.shape[0], keep, int(others == 'rest'),
                             mask.data_ptr() if mask is not None else None, *ptrs[:8], int(sliding), bounce if sliding else 0., ptrs[8])
     scenery._check_grid(dev)
+    args = (C.byref(scenery._as_struct()), C.byref(agents._plain), C.byref(query))
     with _on(dev):
-        _lib.check(_lib.lib().ms_rollouts(C.byref(scenery._as_struct()), C.byref(agents._plain), C.byref(query), C.byref(cfg), _stream(dev)))
+        if store is None:
+            _lib.check(_lib.lib().ms_rollouts(*args, C.byref(cfg), _stream(dev)))
+        else:
+            among = _lib.MsRolloutBodies(store[0].shape[1], store[0].data_ptr(), None if store[1] is None else store[1].data_ptr(), *ptrs[9:11])
+            _lib.check(_lib.lib().ms_rollouts_bodies(*args, C.byref(among), C.byref(cfg), _stream(dev)))
     return result
