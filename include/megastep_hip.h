@@ -1768,7 +1768,33 @@ int ms_projectiles(const MsScenery* scenery, const MsAgents* agents, const MsPro
  * One launch.  P <= 64: a wavefront an env, a lane a walker, four envs a block, no workgroup barrier; beyond: a workgroup an env,
  * a lane the slots lane + 256 j.  The bodies' (p, u) go through LDS, walked at a uniform index; the walls come from the near list of
  * the walker's cell of the wall grid where that covers its reach, else from the env's rows; integer LDS atomics for bumps and
- * close.  Nothing allocated, nothing waits: the call can be captured in a HIP graph. */
+ * close.  Nothing allocated, nothing waits: the call can be captured in a HIP graph.
+ *
+ * SLIDING WALKERS (slide = 1; opt-in - the four fields are the struct's last and MS_ABI_VERSION stays 17: a zeroed tail is the call
+ * as it was, bit for bit).  Steps 1 to 4 are unchanged; a walker that step 5 blocks gets the agents' second contact phase (MsSlide,
+ * DESIGN.md 3.29) instead of a dead stop - the same functions, angle and spin passed as 0 and ignored.  tests/walker_slide_rule.py
+ * restates it in numpy; DESIGN.md 3.41.
+ *   phase A     step 5 as it stands: x1 its least fraction.  progress, blocked, bumps and close are defined as above and hold the
+ *               bits a plain call from the same state gives.  p1 = (p.x + x1*v.x/fps, p.y + x1*v.y/fps).
+ *   contact     (x1 < 1) a BLOCKER is any obstacle of any class whose own collision value equals x1: an agent at rest (p_a, 0, 0),
+ *               another present walker (p_j, u_j), a static row.  Its unit normal n at p1 is MsSlide's: from the row's nearest point
+ *               to p1, or from where the body is at x1 of ITS step, (p_j.x + x1*u_j.x, ..), to p1; no length to speak of: passed
+ *               over.  vn = v.x*n.x + v.y*n.y; the winner is the least (vn, n.x, n.y) by value.  No winner, or !(vn < 0): the
+ *               walker stops dead at p1, v = (0, 0), as in step 6.
+ *   phase B     k = (1.f + bounce)*vn, v' = (v.x - k*n.x, v.y - k*n.y), r1 = 1.f - x1, u2 = ((v'.x*r1)/fps, (v'.y*r1)/fps).  x2 is
+ *               the least, from 1, of the step's own tests from (p1, u2): every agent that is a body, at rest where it stands;
+ *               every other present walker AS PHASE A LEFT IT, (p1_j, u2_j) - u2_j = (0, 0) for a walker that does not slide, and
+ *               p1_j is its whole step if nothing blocked it; every static row of the env.  p = (p1.x + x2*u2.x, p1.y + x2*u2.y);
+ *               x2 < 1: v = (0, 0), else v = v' is stored and the next tick's blend starts from it.
+ *   slid        (N, P): x2*r1, 0 where no slide was tried, NaN for an absent slot.
+ *   stopped     (N, P) bytes: 1 where the tick zeroed the velocity, 0 otherwise, 4 for an absent slot.  Both may be NULL.
+ * What a walker reads of another body in phase A and in the contact is start-of-tick state, in phase B a function of phase A's
+ * result alone; every output has one writer, the folds are minima and the contact a least-by-value: any schedule gives the same bits.
+ * Refused before any launch (MS_EINVAL): slide not 0 or 1; with slide, bounce outside [0, 1] or a NaN, slid not 4-byte aligned.
+ * With slide = 0 the other three fields are not read.  One launch, walker_slide_kernel<WIDE>, in walker_kernel's frame: one walk
+ * folds x1 and the blockers' least normal in a lane's registers, the lane overwrites its own LDS rows with (p1, u2) behind a barrier
+ * that also tells whether anybody in the env slides (nobody: the env is done), and the lanes that slide walk the rows and a fresh
+ * near list at p1 again.  No float atomics, no scratch, nothing allocated, nothing waits. */
 typedef struct MsWalkers {
     int                  n_slots;        /* P: slots per env (1 .. 1024)                                                   */
     float*               positions;      /* (N, P, 2) in/out; 8-byte aligned                                               */
@@ -1786,6 +1812,10 @@ typedef struct MsWalkers {
     unsigned char*       blocked;        /* (N, P) out, or NULL                                                            */
     int*                 bumps;          /* (N, A) out, or NULL                                                            */
     int*                 close;          /* (N, A) out, or NULL                                                            */
+    int                  slide;          /* 1: blocked walkers slide (above); 0: the plain tick, the fields below not read */
+    float                bounce;         /* 0 .. 1: the part of the velocity into the blocker that is turned outwards      */
+    float*               slid;           /* (N, P) out, or NULL                                                            */
+    unsigned char*       stopped;        /* (N, P) out, or NULL                                                            */
 } MsWalkers;
 int ms_walkers(const MsScenery* scenery, const MsAgents* agents, const MsWalkers* walkers, void* hip_stream);
 

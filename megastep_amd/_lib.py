@@ -305,7 +305,7 @@ class MsWalkers(C.Structure):
     _fields_ = [('n_slots', C.c_int), ('positions', C.c_void_p), ('velocities', C.c_void_p), ('speeds', C.c_void_p), ('towards', C.c_void_p),
                 ('reset', C.c_void_p), ('personal', C.c_float), ('push', C.c_float), ('keep', C.c_float), ('agents_push', C.c_int),
                 ('fps', C.c_float), ('agent_radius', C.c_float), ('progress', C.c_void_p), ('blocked', C.c_void_p), ('bumps', C.c_void_p),
-                ('close', C.c_void_p)]
+                ('close', C.c_void_p), ('slide', C.c_int), ('bounce', C.c_float), ('slid', C.c_void_p), ('stopped', C.c_void_p)]
 
 
 class MsNavScent(C.Structure):

@@ -47,6 +47,10 @@ struct WalkArgs {                                    // MsWalkers, checked
     int* close;                                      // (N, A) or NULL
     int n_envs, n_agents, n_slots, agents_push;
     float personal, push, keep, fps, agent_radius;
+    int slide;                                       // 1: walker_slide_kernel's tick (kernels/walker_slide.h) - the rest are its own
+    float bounce;
+    float* slid;                                     // (N, P) or NULL
+    unsigned char* stopped;                          // (N, P) or NULL
 };
 
 __host__ __device__ inline unsigned walk_bits(const float x) { return __builtin_bit_cast(unsigned, x); }
@@ -146,7 +150,10 @@ __host__ __device__ inline void walk_wipe(const WalkArgs& q, const long long at)
     if (q.blocked) q.blocked[at] = 4;
 }
 
-// One whole call on host arrays, serially: `walls` holds every env's STATIC rows, env n's from wall_starts[n] on.
+// One whole call on host arrays, serially: `walls` holds every env's STATIC rows, env n's from wall_starts[n] on.  With q.slide the
+// meet and the move are kernels/walker_slide.h's, which adds its records to an emptied env's and an absent slot's.
+__host__ __device__ inline void walk_slide_records(const WalkArgs& q, long long at, bool present, float slid, bool stopped);
+inline void walk_slide_env(const WalkArgs& q, int n, std::vector<float4>& body, const std::vector<P2>& v, const float4* rows, long long n_rows);
 inline void walkers_serial(const WalkArgs& q, const float4* walls, const long long* wall_starts) {
     const int A = q.n_agents, P = q.n_slots;
     std::vector<float4> body((size_t)(A + P));
@@ -157,7 +164,10 @@ inline void walkers_serial(const WalkArgs& q, const float4* walls, const long lo
             if (q.close) q.close[(long long)n*A + a] = 0;
         }
         if (q.reset && q.reset[n]) {
-            for (int k = 0; k < P; k++) walk_wipe(q, (long long)n*P + k);
+            for (int k = 0; k < P; k++) {
+                walk_wipe(q, (long long)n*P + k);
+                if (q.slide) walk_slide_records(q, (long long)n*P + k, false, 0.f, false);
+            }
             continue;
         }
         for (int a = 0; a < A; a++) {
@@ -185,6 +195,10 @@ inline void walkers_serial(const WalkArgs& q, const float4* walls, const long lo
         }
         const float4* const rows = walls + wall_starts[n];
         const long long n_rows = wall_starts[n + 1] - wall_starts[n];
+        if (q.slide) {
+            walk_slide_env(q, n, body, v, rows, n_rows);
+            continue;
+        }
         for (int k = 0; k < P; k++) {
             const float4 me = body[(size_t)(A + k)];
             const bool present = item_present(me.x, me.y);

@@ -111,6 +111,9 @@
 //                   index, once to steer and keep apart and once, behind a barrier, through the step's own meet_agent; the walls
 //                   by near_list / walk_rows; x and its class folded as one unsigned key; integer LDS atomics for the counts.
 //                                                            (no counterpart)
+//   walker_slide_kernel<WIDE>   sliding walkers: walker_kernel's frame with the agents' second contact phase - one walk folds x1 and
+//                   the least normal among the obstacles at it in registers, a lane overwrites its own LDS rows with (p1, u2) behind
+//                   a barrier, and the lanes that slide walk the rows and a fresh near list again.   (no counterpart)
 //   nav_scent_kernel, nav_scent_query_kernel   scent fields: one workgroup per store keeps it in LDS, a float a framed cell with a
 //                   negative sentinel on the frame and the closed cells, applies the deposits wave by wave in the rule's order and
 //                   runs the sub-steps of the diffusion with each lane's cells in registers between two barriers; per point the
@@ -238,6 +241,7 @@ struct Probe {
 #include "kernels/items.h"
 #include "kernels/projectile.h"
 #include "kernels/walker.h"
+#include "kernels/walker_slide.h"
 #include "kernels/navpath.h"
 #include "kernels/navpull.h"
 #include "kernels/navbasin.h"

@@ -21,7 +21,7 @@ class Crowd(PointGoal):
     def __init__(self, n_envs, n_walkers=16, *args, n_goals=4, speeds=(.6, 1.4), bump=.5, close=.05, seed=0, walk=None, flow=False, solid=False,
                  **kwargs):
         """``n_walkers``, ``n_goals``, ``speeds``, ``seed``, ``walk`` (a dict of :func:`~megastep_amd.cuda.walk`'s ``personal``,
-        ``push``, ``keep``, ``agents_push``), ``flow``: :class:`~megastep_amd.modules.Walkers`'; ``bump``, ``close``: what a walker that runs into
+        ``push``, ``keep``, ``agents_push``, ``slide``), ``flow``: :class:`~megastep_amd.modules.Walkers`'; ``bump``, ``close``: what a walker that runs into
         an agent, and one within ``personal`` of it, take off the agent's reward of the step. Everything else is
         :class:`PointGoal`'s, less ``spl`` and ``panorama``. The crowd keeps walking across the agents' episodes. ``solid=True``: the
         walkers stop the agents (not with ``slide``); the observation and the reward keep their keys."""

@@ -564,7 +564,7 @@ class Walkers:
         their :func:`cuda.distance_fields`; the walkers start on drawn cells of the same space with preferred speeds drawn
         between ``speeds`` m/s, walker k bound for destination ``k % n_goals``. A call heads every walker for the waypoint of its
         destination (:meth:`cuda.DistanceFields.waypoints`), ticks :func:`cuda.walk` - ``**walk``: its ``personal``, ``push``,
-        ``keep``, ``agents_push`` - and sends those within ``arrive`` metres (walking distance) of their destination on to the next
+        ``keep``, ``agents_push``, ``slide`` (True: a blocked walker slides along what it hit) - and sends those within ``arrive`` metres (walking distance) of their destination on to the next
         one. A walker is a disc of the core's ``agent_radius``, and is drawn as wide.
 
         ``positions`` - (n_env, P, 2) - goes to ``Percepts(core, points=walkers.positions)`` as it is. A call is three launches
@@ -630,6 +630,9 @@ class Walkers:
     #: (n_env, n_agent) int32 of the last tick: the walkers that ran into each agent, and those within ``personal`` of it
     bumps = property(lambda self: self._walked.bumps)
     close = property(lambda self: self._walked.close)
+    #: (n_env, P) of the last tick with ``slide``: the share of its step each walker slid, and whether it was left at rest; else None
+    slid = property(lambda self: self._walked.slid)
+    stopped = property(lambda self: self._walked.stopped)
 
     def __call__(self, reset=None):
         """One tick; ``reset`` (n_env,) bool - the envs whose destinations and walkers are drawn anew. Returns the

@@ -7,6 +7,7 @@ from ._lib import _on, _stream
 from ._call import _cfg, _check, _query_device, _result_for
 from .items import Items
 from .percepts import _bytes
+from .rollouts import _bounce
 
 #: the most slots an env may hold, and the most agents an env may have for :func:`walk`
 WALK_MAX_SLOTS, WALK_MAX_AGENTS = 1024, 64
@@ -49,13 +50,15 @@ class Walked:
     """Result of :func:`walk`: ``progress`` (N, P) float32 - the fraction of its step each walker took, NaN for an empty slot;
     ``blocked`` (N, P) uint8 - what stopped it: 0 nothing, 1 an agent, 2 a walker, 3 a wall, 4 the slot is empty; ``bumps`` (N, A)
     int32 - the walkers that ran into each agent; ``close`` (N, A) int32 - the walkers within ``personal`` of each agent when the
-    tick began."""
+    tick began. Of a walk with ``slide`` also ``slid`` (N, P) float32 - the share of its step each walker spent sliding, 0 where it
+    did not, NaN for an empty slot - and ``stopped`` (N, P) uint8 - 1 where the tick left the walker at rest, 4 for an empty slot;
+    both are ``None`` when the walk did not slide."""
 
-    def __init__(self, progress, blocked, bumps, close):
-        self.progress, self.blocked, self.bumps, self.close = progress, blocked, bumps, close
+    def __init__(self, progress, blocked, bumps, close, slid=None, stopped=None):
+        self.progress, self.blocked, self.bumps, self.close, self.slid, self.stopped = progress, blocked, bumps, close, slid, stopped
 
 
-def walk(scenery, agents, store, towards, personal=.6, push=1., keep=.5, agents_push=True, reset=None, out=None, config=None):
+def walk(scenery, agents, store, towards, personal=.6, push=1., keep=.5, agents_push=True, reset=None, out=None, config=None, slide=False):
     """One tick of the walkers. The envs marked in ``reset`` (N,) are emptied and nothing else happens there. Every present walker
     steers at its preferred speed towards its point of ``towards`` (N, P, 2) - a NaN there means "stand", and it never oversteps
     the point within the tick - is pushed away from the bodies within ``personal`` metres of it (the agents too when
@@ -69,6 +72,12 @@ def walk(scenery, agents, store, towards, personal=.6, push=1., keep=.5, agents_
     :func:`physics` does not know them, an agent can walk through one - ``bumps`` and ``close`` are what an env penalises. The
     call is meant to follow :func:`physics`: the agents are met at rest, where they stand. A velocity that does not come out finite
     (a stored NaN, a NaN speed, an infinite target) makes the walker stand for the tick.
+
+    ``slide=True`` or ``dict(bounce=.05)``: a walker that something blocks is not stopped dead but spends the rest of its tick along
+    what blocked it, as an agent does under ``cuda.physics(slide=)`` - its velocity deflected off the contact normal with ``bounce``
+    (0..1) of it turned outwards, the second move stopped by the agents, by the other walkers where their first move left them and
+    by the walls (``MsWalkers``' slide). ``progress``, ``blocked``, ``bumps`` and ``close`` are the plain walk's; the
+    result also carries ``slid`` and ``stopped``. A walk nobody is blocked in is the plain walk, bit for bit.
 
     One launch - a wavefront an env up to 64 slots, a workgroup an env beyond; exact - the rule is written out in
     include/megastep_hip.h (``MsWalkers``) and DESIGN.md 3.37 and the kernel computes it bit for bit. No host synchronisation, and
@@ -94,14 +103,19 @@ def walk(scenery, agents, store, towards, personal=.6, push=1., keep=.5, agents_
     reset = _bytes(reset, 'reset', ((n,),), '(N,)')
     given = [t for t in (reset,) if t is not None]
     dev = _query_device(scenery, agents, store.positions, store.velocities, store.speeds, towards, *given)
-    result = _result_for(out, (n, a, p, dev), 'a walk', lambda: Walked(
+    bounce = _bounce(slide)
+    sliding = bounce is not None
+    result = _result_for(out, (n, a, p, dev) + ((True,) if sliding else ()), 'a walk', lambda: Walked(
         torch.empty((n, p), dtype=torch.float32, device=dev), torch.empty((n, p), dtype=torch.uint8, device=dev),
-        torch.empty((n, a), dtype=torch.int32, device=dev), torch.empty((n, a), dtype=torch.int32, device=dev)))
+        torch.empty((n, a), dtype=torch.int32, device=dev), torch.empty((n, a), dtype=torch.int32, device=dev),
+        torch.empty((n, p), dtype=torch.float32, device=dev) if sliding else None,
+        torch.empty((n, p), dtype=torch.uint8, device=dev) if sliding else None))
     cfg = _cfg(agents, config)
     spec = _lib.MsWalkers(p, store.positions.data_ptr(), store.velocities.data_ptr(), store.speeds.data_ptr(), towards.data_ptr(),
                           reset.data_ptr() if reset is not None else None, float(personal), float(push), float(keep), int(bool(agents_push)),
                           float(cfg.fps), float(cfg.agent_radius), result.progress.data_ptr(), result.blocked.data_ptr(),
-                          result.bumps.data_ptr(), result.close.data_ptr())
+                          result.bumps.data_ptr(), result.close.data_ptr(), int(sliding), bounce if sliding else 0.,
+                          result.slid.data_ptr() if sliding else None, result.stopped.data_ptr() if sliding else None)
     with _on(dev):
         _lib.check(_lib.lib().ms_walkers(C.byref(scenery._as_struct()), C.byref(agents._plain), C.byref(spec), _stream(dev)))
     return result

@@ -5,13 +5,14 @@
   (a) at `--envs` envs over `--distinct` distinct synthetic floorplans (the headline's world), 4 agents at their spawn poses, each
       call between two HIP events of its own, `--repeats` calls back to back, the median and the range (the store is put back
       before every call by two small copies, which are inside the events of every cuda.walk row alike):
-        cuda.walk at P = 16 and 64 (a wavefront an env) and 256 (a workgroup an env), `towards` precomputed
+        cuda.walk at P = 16 and 64 (a wavefront an env) and 256 (a workgroup an env), `towards` precomputed, plainly and with slide=True
         the waypoints launch in front of it
         the route a caller had before: the same crowd as P extra agents through cuda.physics with the steering in torch ops, at
         P = 16 and 60, and what those extra agents add to cuda.render at 64 rays
-  (b) Crowd(`--envs`).step under random actions, eager and as one HIP graph, next to PointGoal(`--envs`).step in the same run.
-  (c) Crowd(64), 300 steps under expert() and under random actions: arrivals, bumps a step, and the walkers' mean speed over
-      their preferred speed.
+  (b) Crowd(`--envs`).step under random actions, eager and as one HIP graph, next to PointGoal(`--envs`).step in the same run;
+      Crowd(`--envs`, n_walkers=16 | 64, flow=True).step as one HIP graph, with and without walk=dict(slide=True).
+  (c) Crowd(64), 300 steps under expert(), under random actions and under expert() with sliding walkers: arrivals, bumps a step,
+      the walkers' mean speed over their preferred speed, what blocked them and how many a tick left at rest.
 `--only` picks one part (for a profiler run of its own).  Needs a GPU: there is no CPU fall-back.
 """
 import argparse
@@ -93,6 +94,17 @@ def main():
             stopped = float((walked.progress < 1).float().mean())
             out['launches'][f'walk_P{p}'] = dict(t=t, restore=t0, stopped=stopped)
             print(f'    P = {p}: restore + cuda.walk {us(t)}; the restore alone {us(t0)}; {stopped:.3f} of the walkers stopped')
+            sliding = cuda.walk(sc, ag, store, towards, slide=True)
+
+            def tick_sliding():
+                restore()
+                cuda.walk(sc, ag, store, towards, out=sliding, slide=True)
+
+            t = back_to_back(tick_sliding, args.repeats)
+            slid, dead = float((sliding.slid > 0).float().mean()), float((sliding.stopped == 1).float().mean())
+            out['launches'][f'walk_slide_P{p}'] = dict(t=t, slid=slid, stopped=dead)
+            print(f'    P = {p}: restore + cuda.walk(slide=True) {us(t)}; {slid:.3f} of the walkers slid, {dead:.3f} were left at rest')
+            restore()
             t = back_to_back(lambda: crowd.fields.waypoints(store.positions, goal=crowd.goal, out=towards), args.repeats)
             out['launches'][f'waypoints_P{p}'] = t
             print(f'    P = {p}: the waypoints launch {us(t)}')
@@ -135,25 +147,42 @@ def main():
                 out['env'][f"{name}_{'graphed' if graphed else 'eager'}"] = t
                 print(f'(b) {name}({args.envs}).step, {"one HIP graph" if graphed else "eager"}: {us(t)}')
                 del env, inner
+        for p in (16, 64):
+            for slide in (False, True):
+                np.random.seed(0); torch.manual_seed(0)
+                inner = Crowd(args.envs, n_walkers=p, flow=True, walk=dict(slide=True) if slide else None, geometries=geoms)
+                env = graphs.GraphedStep(inner)
+                env.reset()
+                actions = arrdict.arrdict(actions=torch.randint(0, 7, (args.envs, 1), device='cuda'))
+                t = back_to_back(lambda: env.step(actions), args.repeats)
+                out['env'][f"Crowd_flow_P{p}_{'slide' if slide else 'plain'}"] = t
+                print(f'(b) Crowd({args.envs}, n_walkers={p}, flow=True{", walk=dict(slide=True)" if slide else ""}).step, one HIP graph: {us(t)}')
+                del env, inner
 
     if want('crowd'):
         out['crowd'] = {}
-        for policy in ('expert', 'random'):
+        for policy in ('expert', 'random', 'expert, walkers sliding'):
             np.random.seed(0); torch.manual_seed(0)
-            env = Crowd(64, geometries=geoms[:64])
+            env = Crowd(64, geometries=geoms[:64], walk=dict(slide=True) if 'sliding' in policy else None)
             env.reset()
             arrivals = bumps = close = 0
-            ratio = []
+            ratio, rest = [], []
             for _ in range(300):
-                decision = env.expert() if policy == 'expert' else arrdict.arrdict(actions=torch.randint(0, 7, (64, 1), device='cuda'))
+                decision = env.expert() if policy != 'random' else arrdict.arrdict(actions=torch.randint(0, 7, (64, 1), device='cuda'))
                 before = env.walkers.positions.clone()
                 world = env.step(decision)
                 arrivals += int((world.reward > .5).sum())
                 bumps += int(env.walkers.bumps.sum()); close += int(env.walkers.close.sum())
                 ratio.append(float(((env.walkers.positions - before).norm(dim=-1)*env.core.fps/env.walkers.store.speeds).mean()))
-            out['crowd'][policy] = dict(arrivals=arrivals, bumps_a_step=bumps/300/64, close_a_step=close/300/64, speed_ratio=float(np.mean(ratio)))
+                walked = env.walkers.walked                  # (at rest after the tick: blocked and, when sliding, not carried on)
+                rest.append([float((walked.blocked == c).float().mean()) for c in (1, 2, 3)]
+                            + [float(((walked.progress < 1) if walked.stopped is None else (walked.stopped == 1)).float().mean())])
+            blocked = np.mean(rest, 0)
+            out['crowd'][policy] = dict(arrivals=arrivals, bumps_a_step=bumps/300/64, close_a_step=close/300/64, speed_ratio=float(np.mean(ratio)),
+                                        blocked_by_agent=blocked[0], blocked_by_walker=blocked[1], blocked_by_wall=blocked[2], left_at_rest=blocked[3])
             print(f'(c) Crowd(64), 300 steps, {policy}: {arrivals} arrivals, {bumps/300/64:.4f} bumps and {close/300/64:.4f} close an env-step, '
-                  f'the walkers at {np.mean(ratio):.3f} of their preferred speed')
+                  f'the walkers at {np.mean(ratio):.3f} of their preferred speed; blocked a tick by an agent {blocked[0]:.3f}, a walker {blocked[1]:.3f}, '
+                  f'a wall {blocked[2]:.3f} of them, left at rest {blocked[3]:.3f}')
 
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
